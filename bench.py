@@ -1,8 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- polar images/s of the radar hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N > 1: launched by torch.distributed.run, one rank per GPU, RCCL)
+
+A plain run sets up, warms up (W steps, then >= 0.3 s of untimed steps), times exactly K steps and prints the headline line:
+metric, value, unit, higher_is_better, dtype, ms_per_step (milliseconds of one timed step = the timed region / K), config.
+`--full` adds everything else this file measures or checks, as described below: the wave-pass statistics, per-kernel,
+contention and roofline figures (and the per-kernel events inside the timed region they need), the N = 1 extras, the
+`rccl` block and the CPU baseline.  `--dump-outputs DIR` (N = 1) writes the images the last timed step delivered to host
+memory as DIR/images.npy (float32, [frame][range bin][azimuth], frames in the order the step rendered them; a fixed, seeded sample of range bins
+when all of them would exceed 64 MB, listed in DIR/images_range_bins.npy).  The inputs are fixed by the arguments alone.
 
 Workload (default): the configuration BASELINE.json's north_star target is quoted on --
 400 azimuths x 3424 range bins, 200 rays per beam, 4 ray-cast passes (Snell/Fresnel split), 10M-triangle
@@ -20,7 +28,7 @@ HOST memory (m_polar_image, RadarCPU.cpp:542,555-561), so the K steps are timed 
 page-locked host memory (N = 1: rr_simulate_batch_host_async; N > 1: every rank delivers the frames it assembled,
 AzimuthShard(host_out=True); either way the images ride out on the trace launches of the next batch on the same stream, a few
 waves with one store in flight each).  Inputs (mesh, tree, parameters, beam) are resident in HBM before the timed region.
-The same line carries `hbm_resident` (the same steps with the images left in HBM: `value` of rounds 1-4) and `single_pose`: one pose per
+The --full line carries `hbm_resident` (the same steps with the images left in HBM: `value` of rounds 1-4) and `single_pose`: one pose per
 launch set (the latency-oriented shape a live ROS node would use).  Before every timed region the GPU is
 pre-warmed by wall time (>= 0.3 s of steps, untimed) so that `--steps 20` reads sustained clocks.
 
@@ -43,7 +51,7 @@ transpose of its F frames -- on this one GPU against the N = 1 step: the per-GPU
 radar_simulator.cpp:197-212) and `strong_scaling_proxy` (a block of 400/N azimuth columns alone on the GPU against the
 whole frame: the bound of what sharding ONE frame over N GPUs can win; the default N > 1 mode is weak scaling).
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full):
   "roofline"     the kernel that takes the most GPU time (picked from the measured per-kernel times, normally the
                  later-pass k_trace) against the bound that really limits it: VALU instruction issue.
                  achieved = wave-instructions/s = SQ_INSTS_VALU per launch (rocprofv3 PMC of this same command,
@@ -72,6 +80,31 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s
 # MI355X_MICROARCH.md "Wave scheduling": 4 SIMD-32 per CU, a wave64 VALU instruction issues over 2 cycles
 VALU_PEAK_WAVE_INSTR_S = 256 * 4 * 2.4e9 / 2.0
 PREWARM_S = 0.3
+DUMP_MAX_BYTES = 64 * 10 ** 6  # --dump-outputs: all files together
+DUMP_SEED = 20240217
+
+
+def dump_images(out_dir, images):
+    """--dump-outputs: `images` [frames][range bins][azimuths] (uint8, as delivered) -> out_dir/images.npy as float32 (exact
+    for u8) and out_dir/images_range_bins.npy (float64, the bins kept).  When all bins do not fit in DUMP_MAX_BYTES, a
+    fixed, seeded sample of range bins is kept -- every frame and every azimuth of them -- so that two runs or two builds
+    with the same arguments write the same selection.  Returns the paths written."""
+    images = np.asarray(images)
+    n_frames, n_bins, n_az = images.shape
+    row_bytes = n_frames * n_az * 4
+    budget = DUMP_MAX_BYTES - 2 ** 20                    # headroom for the .npy headers and the bin list
+    if n_bins * row_bytes <= budget:
+        bins = np.arange(n_bins)
+    else:
+        keep = budget // row_bytes
+        if keep < 1:
+            raise ValueError("--dump-outputs: one range bin of %d frames x %d azimuths exceeds %d bytes" % (n_frames, n_az, budget))
+        bins = np.sort(np.random.RandomState(DUMP_SEED).choice(n_bins, keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    paths = [os.path.join(out_dir, "images.npy"), os.path.join(out_dir, "images_range_bins.npy")]
+    np.save(paths[0], images[:, bins, :].astype(np.float32))
+    np.save(paths[1], bins.astype(np.float64))
+    return paths
 
 
 def prefer_system_hip_runtime(world):
@@ -347,13 +380,25 @@ def main(argv=None):
     ap.add_argument("--frames-per-rank", type=int, default=8,
                     help="frames each GPU finishes per batch (one set of launches); a batch = N x this many frames")
     ap.add_argument("--batches-per-step", type=int, default=2, help="batches per step (default: 2 x 8 = the 16-pose trajectory)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: wave-pass statistics, per-kernel and roofline figures, contention, "
+                         "the N = 1 extras (hbm_resident, single_pose, single_frame_sync, scaling proxies), the rccl block and the "
+                         "CPU baseline.  Without it a run sets up, warms up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the images the last timed step delivered as DIR/images.npy (float32; "
+                         "a fixed, seeded sample of range bins when the step's images exceed %d MB) and the sampled bins as "
+                         "DIR/images_range_bins.npy (float64)" % (DUMP_MAX_BYTES // 10 ** 6))
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.slots is None:
         args.slots = 3 if (args.frames_per_rank >= 8 and not args.strong) else 4
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if args.dump_outputs and (args.gpus > 1 or world > 1 or args.force_slots):
+        raise SystemExit("bench.py: --dump-outputs covers the single-GPU run (host delivery through rr_simulate_batch_host_async)")
     if "RANK" not in os.environ and (args.gpus > 1 or args.self_launch):
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves, BEFORE anything in this
         # process touches the GPU (the parent only counts devices and waits for the child)
@@ -428,8 +473,9 @@ def main(argv=None):
         F = args.frames_per_rank
         h_streams = [tc.Stream(device=dev) for _ in range(args.slots)]
         # a ring of host buffers twice as deep as the batches in flight: the consumer side (rr_wait_host before a
-        # buffer is handed out again) then never stalls the producer
-        hosts = [native.HostImages((F, cfg.n_cells, params.N_ANGLES)) for _ in range(2 * args.slots)]
+        # buffer is handed out again) then never stalls the producer; at least one step deep, so that the images of the
+        # last timed step are all still there for --dump-outputs
+        hosts = [native.HostImages((F, cfg.n_cells, params.N_ANGLES)) for _ in range(max(2 * args.slots, bps))]
         h_state = {"n": 0}
 
         def step_main(k, done=None):
@@ -477,37 +523,40 @@ def main(argv=None):
     for k in range(args.warmup):
         step(k)
     tc.synchronize()
-    # ---- instrumentation, all of it outside (and before) the timed region ---------------------------------
-    # one batch: wave-pass count of this workload
-    shard.step([poses[f % len(poses)] for f in range(fpb)], None)
-    tc.synchronize()
-    st = ctx.stats()
-    wave_passes_batch_rank = st["wave_passes"]
-    assert st["overflow"] == 0, st
-    # one batch with the counting build of k_trace: measured node / triangle fetches per wave-pass
-    ctx.set_stats_mode(True)
-    shard.step([poses[f % len(poses)] for f in range(fpb)], None)
-    tc.synchronize()
-    st2 = ctx.stats()
-    shape = ctx.traversal_shape()
-    ctx.set_stats_mode(False)
-    # every kernel alone on the GPU (one batch at a time, nothing else in flight): which kernel takes the most
-    # time, and its own speed -- as opposed to its duration while several batches share the chip below
-    prewarm(step, collective=True)
-    ctx.reserve_timing_events(4096)
-    ctx.set_timing_mode(1)
-    for name in KERNEL_LABEL:
-        ctx.kernel_time(name, reset=True)
-    for k in range(6):
-        shard.step([poses[(k * fpb + f) % len(poses)] for f in range(fpb)], None)
+    # ---- instrumentation (--full), all of it outside (and before) the timed region ---------------------------
+    if args.full:
+        # one batch: wave-pass count of this workload
+        shard.step([poses[f % len(poses)] for f in range(fpb)], None)
         tc.synchronize()
-    iso = {name: ctx.kernel_time(name, reset=True) for name in KERNEL_LABEL}      # (total ms, launches)
-    ctx.set_timing_mode(0)
-    dominant = max(iso, key=lambda n: iso[n][0])
+        st = ctx.stats()
+        wave_passes_batch_rank = st["wave_passes"]
+        assert st["overflow"] == 0, st
+        # one batch with the counting build of k_trace: measured node / triangle fetches per wave-pass
+        ctx.set_stats_mode(True)
+        shard.step([poses[f % len(poses)] for f in range(fpb)], None)
+        tc.synchronize()
+        st2 = ctx.stats()
+        shape = ctx.traversal_shape()
+        ctx.set_stats_mode(False)
+        # every kernel alone on the GPU (one batch at a time, nothing else in flight): which kernel takes the most
+        # time, and its own speed -- as opposed to its duration while several batches share the chip below
+        prewarm(step, collective=True)
+        ctx.reserve_timing_events(4096)
+        ctx.set_timing_mode(1)
+        for name in KERNEL_LABEL:
+            ctx.kernel_time(name, reset=True)
+        for k in range(6):
+            shard.step([poses[(k * fpb + f) % len(poses)] for f in range(fpb)], None)
+            tc.synchronize()
+        iso = {name: ctx.kernel_time(name, reset=True) for name in KERNEL_LABEL}      # (total ms, launches)
+        ctx.set_timing_mode(0)
+        dominant = max(iso, key=lambda n: iso[n][0])
     # ---- the timed region: exactly `steps` steps between two synchronisation points ------------------------
-    # (timing mode 2: pooled hipExtLaunchKernel events around the k_trace launches only, on the launch stream)
-    done = [tc.Event(enable_timing=True) for _ in range(args.steps + 1)]
-    ctx.reserve_timing_events(4 * n_pass * bps * args.steps + 64)
+    # (--full, timing mode 2: pooled hipExtLaunchKernel events around the k_trace launches only, on the launch stream;
+    # per-step completion events.  Without --full the timed region carries no events of its own)
+    done = [tc.Event(enable_timing=True) for _ in range(args.steps + 1)] if args.full else [None] * (args.steps + 1)
+    if args.full:
+        ctx.reserve_timing_events(4 * n_pass * bps * args.steps + 64)
     prewarm(step_main, collective=True)
     finish_main(); tc.synchronize()
     # (RR_BENCH_LIVE_TIMING=0: a diagnostic -- the timed region without the begin / end events around its k_trace launches;
@@ -517,14 +566,16 @@ def main(argv=None):
     # chains of a one-pass workload are then issued kernel by kernel instead of being replayed from launch graphs, 34.7k ->
     # 27.8k images/s on config 2 (round 6, same box) -- that was the "regression" of the round-5 line (30.9k against the 39.0k
     # round 4 had measured in an untimed extra region)
-    live_timing = os.environ.get("RR_BENCH_LIVE_TIMING", "1") != "0" and dominant in ("trace", "trace0")
-    graphs_before = ctx.graph_stats() if hasattr(ctx, "graph_stats") else (0, 0)
-    ctx.set_timing_mode(2 if live_timing else 0)
-    ctx.kernel_time("trace", reset=True); ctx.kernel_time("trace0", reset=True); ctx.kernel_time("trace_repair", reset=True)
+    if args.full:
+        live_timing = os.environ.get("RR_BENCH_LIVE_TIMING", "1") != "0" and dominant in ("trace", "trace0")
+        graphs_before = ctx.graph_stats() if hasattr(ctx, "graph_stats") else (0, 0)
+        ctx.set_timing_mode(2 if live_timing else 0)
+        ctx.kernel_time("trace", reset=True); ctx.kernel_time("trace0", reset=True); ctx.kernel_time("trace_repair", reset=True)
     if world > 1:
         dist.barrier()
     tc.synchronize()
-    done[0].record(tc.current_stream())
+    if args.full:
+        done[0].record(tc.current_stream())
     t0 = time.perf_counter()
     for k in range(args.steps):
         step_main(k, done[k + 1])
@@ -534,6 +585,56 @@ def main(argv=None):
     if world > 1:
         dist.barrier()
     t1 = time.perf_counter()
+    if args.dump_outputs:
+        # the images of the last timed step: its bps batches went to the last bps buffers of the ring, frame f of batch b
+        # being pose ((k * bps + b) * F + f) % 16 with k = steps - 1
+        n_end = h_state["n"]
+        last = np.concatenate([hosts[n % len(hosts)].array for n in range(n_end - bps, n_end)])
+        for path in dump_images(args.dump_outputs, last):
+            print("bench.py: wrote %s" % path, file=sys.stderr)
+    elapsed = t1 - t0
+    if world > 1:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    img_per_s = args.steps * fps / elapsed
+    # the headline: what every run prints (--full adds the objects below to the same line)
+    out = {
+        "metric": "polar images/sec (400 az x 3424 bins)",
+        "value": round(img_per_s, 2),
+        "unit": "images/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(1e3 * elapsed / args.steps, 4),
+        "higher_is_better": True,
+        "scaling": "strong" if (world > 1 and args.strong) else "weak",
+        "vs_baseline": None,
+        "dtype": "f32 rays / f64 energy+time",
+        "data": "synthetic",
+        "config": {"workload": args.workload, "triangles": int(n_tris), "azimuths": params.N_ANGLES,
+                   "range_bins": int(cfg.n_cells), "rays_per_beam": n_rays, "passes": n_pass,
+                   "ambient_noise": int(cfg.ambient_noise),
+                   "frames_per_step": fps, "frames_per_batch": fpb, "batches_per_step": bps,
+                   "images": "delivered to page-locked host memory; timed through the last D2H copy (SURVEY §8d bracket = the reference's stopwatch, RadarCPU.cpp:147-550)",
+                   "d2h_GBps": round(img_per_s * cfg.n_cells * params.N_ANGLES / 1e9, 3),
+                   "hip_runtime": runtime,
+                   "host_delivery": (ctx.host_delivery_route() if hasattr(ctx, "host_delivery_route") else None),
+                   "sharding": ("single GPU" if world == 1 else
+                                "azimuth columns x%d, 1 frame/batch + 1 all-gather" % world if args.strong else
+                                "azimuth columns x%d, %d frames/batch, 1 all_to_all/batch (frame f -> rank f)" % (world, fpb))},
+        "full": bool(args.full),
+    } if rank == 0 else None
+    if not args.full:
+        if host_mode:
+            for h in hosts:
+                h.close()
+        shard.close()
+        ctx.close()
+        if world > 1 or args.force_slots:
+            dist.destroy_process_group()
+        if rank == 0:
+            json_out.write(json.dumps(out) + "\n")
+            json_out.flush()
+        return
     live = {n: ctx.kernel_time(n, reset=True) for n in ("trace", "trace0", "trace_repair")}
     ctx.set_timing_mode(0)
     graphs_after = ctx.graph_stats() if hasattr(ctx, "graph_stats") else (0, 0)
@@ -559,11 +660,7 @@ def main(argv=None):
     win = max(1, min(args.slots, len(tdone) - 1))
     periods_ms = [(tdone[i + win] - tdone[i]) / win for i in range(len(tdone) - win)]
 
-    elapsed = t1 - t0
     if world > 1:
-        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
         wp = torch.tensor([wave_passes_batch_rank], dtype=torch.int64, device=dev)
         dist.all_reduce(wp, op=dist.ReduceOp.SUM)
         wave_passes_batch = int(wp.item())
@@ -702,9 +799,7 @@ def main(argv=None):
         own = args.steps * bps * shard.fpr / t_own        # frames THIS rank assembled and delivered per second of its own time
         rccl = rccl_block(rank, world, desc, coll, nbytes, own)
 
-    out = None
     if rank == 0:
-        img_per_s = args.steps * fps / elapsed
         b_wp = algorithmic_bytes_per_wave_pass(n_tris)
         wp2 = max(int(st2["wave_passes"]), 1)
         measured_b_wp = (st2["nodes_visited"] * 128 + st2["tris_tested"] * 48) / wp2 + 132
@@ -815,28 +910,7 @@ def main(argv=None):
                                   "the chip; batch_ms_live = the timed region's time per batch with %d batches in flight: what running them "
                                   "concurrently buys is the ratio of the two.  *_live_over_alone = a launch's duration (stream events "
                                   "around it, a short region after the timed one) with %d batches sharing the chip / alone" % (args.slots, args.slots)}
-        out = {
-            "metric": "polar images/sec (400 az x 3424 bins)",
-            "value": round(img_per_s, 2),
-            "unit": "images/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(1e3 * elapsed / args.steps, 4),
-            "higher_is_better": True,
-            "scaling": "strong" if (world > 1 and args.strong) else "weak",
-            "vs_baseline": None,
-            "dtype": "f32 rays / f64 energy+time",
-            "data": "synthetic",
-            "config": {"workload": args.workload, "triangles": int(n_tris), "azimuths": params.N_ANGLES,
-                       "range_bins": int(cfg.n_cells), "rays_per_beam": n_rays, "passes": n_pass,
-                       "ambient_noise": int(cfg.ambient_noise),
-                       "frames_per_step": fps, "frames_per_batch": fpb, "batches_per_step": bps,
-                       "images": "delivered to page-locked host memory; timed through the last D2H copy (SURVEY §8d bracket = the reference's stopwatch, RadarCPU.cpp:147-550)",
-                       "d2h_GBps": round(img_per_s * cfg.n_cells * params.N_ANGLES / 1e9, 3),
-                       "hip_runtime": runtime,
-                       "host_delivery": (ctx.host_delivery_route() if hasattr(ctx, "host_delivery_route") else None),
-                       "sharding": ("single GPU" if world == 1 else
-                                    "azimuth columns x%d, 1 frame/batch + 1 all-gather" % world if args.strong else
-                                    "azimuth columns x%d, %d frames/batch, 1 all_to_all/batch (frame f -> rank f)" % (world, fpb))},
+        out.update({
             "rays_per_s": round(wave_passes_batch / fpb * img_per_s, 1),
             "wave_passes_per_frame": int(wave_passes_batch // fpb),
             "images_per_s_per_step": {"median": round(fps / (1e-3 * pct(periods_ms, 0.5)), 2) if periods_ms else None,
@@ -861,7 +935,7 @@ def main(argv=None):
                                       "kernel -- GPU time is the same either way, a replay saves host time; `hbm_resident` and "
                                       "`single_pose` replay graphs.  (In the fallback delivery route, RR_HOST_SDMA=0, the multi-pass chains "
                                       "also carry the previous batch's host copy and are never replayed.)"},
-        }
+        })
 
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(scene, cfg, mats, beams, noise, poses, args.cpu_seconds,

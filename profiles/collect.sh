@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 tag=${1:-r06}; shift
 OUT=$R/gpurun_out/profiles_$tag; mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
-ARGS="--steps 60 --warmup 5 --no-cpu-baseline --no-extras $@"
+ARGS="--full --steps 60 --warmup 5 --no-cpu-baseline --no-extras $@"
 export RR_GRAPHS=0   # every chain kernel by kernel (as in rounds 3-5, whose timed loop carried host copies and was never replayed from a graph)
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ktrace -- python3 $R/bench.py $ARGS > $OUT/bench_under_rocprof.json 2> $OUT/ktrace.log
 cp $(find $OUT/ktrace -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats.csv 2>/dev/null

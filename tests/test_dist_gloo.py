@@ -338,7 +338,7 @@ class _BenchMockCtx:
         self._view(img_ptr, self.C * self.A)[:] = 1
 
 
-def _worker_bench_dryrun(rank, world, port, out_dir, fail_rank):
+def _worker_bench_dryrun(rank, world, port, out_dir, fail_rank, extra=("--full",)):
     sys.path.insert(0, os.path.dirname(HERE))
     os.environ.update({"MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port), "RANK": str(rank), "WORLD_SIZE": str(world),
                        "LOCAL_RANK": str(rank), "RR_BENCH_DRYRUN": "1", "RR_BENCH_ERRDIR": os.path.join(out_dir, "err")})
@@ -355,7 +355,8 @@ def _worker_bench_dryrun(rank, world, port, out_dir, fail_rank):
     fd = os.open(os.path.join(out_dir, "stdout_rank%d.txt" % rank), os.O_CREAT | os.O_WRONLY | os.O_TRUNC)
     os.dup2(fd, 1)                       # what a launcher would see on the rank's stdout
     try:
-        bench.main(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--workload", "config2_100k_400x200_1pass"])
+        bench.main(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--workload", "config2_100k_400x200_1pass"]
+                   + list(extra))
     except BaseException as exc:         # noqa: BLE001  what `python bench.py` does at top level
         bench.report_failure(exc)
         os._exit(7 if rank == fail_rank else 0)       # (the other rank would hang in its collective: a launcher kills it)
@@ -379,6 +380,46 @@ def test_bench_two_rank_dry_run_prints_the_full_line(tmp_path):
     assert d["n1_reference"] is not None and d["n1_reference"]["source"].startswith("profiles/")
     assert d["roofline"] is not None and "cpu_baseline" not in d and d["hbm_resident"] is None
     assert abs(d["value"] - 3 * 32 / (1e-3 * d["ms_per_step"] * 3)) < 1e-6 * d["value"] + 0.01       # value = all ranks' frames / slowest rank's time
+
+
+def test_bench_dump_images_budget_and_seeded_sample(tmp_path):
+    """--dump-outputs: float32 copies of the delivered u8 images; a step too large for the budget keeps every frame and
+    azimuth of a fixed, seeded set of range bins -- the same set from run to run."""
+    import bench
+    rs = np.random.RandomState(3)
+    small = rs.randint(0, 256, (2, 50, 40)).astype(np.uint8)
+    p_img, p_bins = bench.dump_images(str(tmp_path / "a"), small)
+    a = np.load(p_img)
+    assert a.dtype == np.float32 and np.array_equal(a, small.astype(np.float32))
+    assert np.array_equal(np.load(p_bins), np.arange(50, dtype=np.float64))
+    big = np.zeros((16, 3424, 400), np.uint8)
+    big[:, :, :] = (np.arange(3424) % 251).astype(np.uint8)[None, :, None]
+    dirs = [str(tmp_path / d) for d in ("b", "c")]
+    for d in dirs:
+        bench.dump_images(d, big)
+    total = sum(os.path.getsize(os.path.join(dirs[0], f)) for f in os.listdir(dirs[0]))
+    assert total <= bench.DUMP_MAX_BYTES
+    b0, b1 = (np.load(os.path.join(d, "images_range_bins.npy")) for d in dirs)
+    assert np.array_equal(b0, b1) and len(b0) > 2000 and np.all(np.diff(b0) > 0)
+    imgs = np.load(os.path.join(dirs[0], "images.npy"))
+    assert imgs.dtype == np.float32 and imgs.shape == (16, len(b0), 400)
+    assert np.array_equal(imgs, big[:, b0.astype(np.int64), :].astype(np.float32))
+
+
+def test_bench_two_rank_dry_run_plain_line_is_the_headline(tmp_path):
+    """`bench.py --gpus 2` without --full: the same timed steps, a line that holds the headline keys and none of what --full
+    measures (no statistics batch, no per-kernel timing, no rccl block)."""
+    import json
+    port = _free_port()
+    mp.spawn(_worker_bench_dryrun, args=(2, port, str(tmp_path), -1, ()), nprocs=2, join=True)
+    out0 = open(os.path.join(str(tmp_path), "stdout_rank0.txt")).read().strip().splitlines()
+    assert len(out0) == 1 and open(os.path.join(str(tmp_path), "stdout_rank1.txt")).read().strip() == ""
+    d = json.loads(out0[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert d[k] is not None, k
+    assert d["full"] is False and d["n_gpus"] == 2 and d["steps"] == 3 and d["config"]["frames_per_batch"] == 16
+    assert not {"roofline", "rccl", "contention", "hbm_resident", "cpu_baseline", "rays_per_s"} & set(d)
+    assert abs(d["value"] - 3 * 32 / (1e-3 * d["ms_per_step"] * 3)) < 1e-6 * d["value"] + 0.01
 
 
 def test_bench_rank_failure_prints_one_error_line(tmp_path):

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/pmc_extra; mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
-ARGS="--steps 30 --warmup 5 --no-cpu-baseline --no-extras"
+ARGS="--full --steps 30 --warmup 5 --no-cpu-baseline --no-extras"
 i=0
 # (a set of TA_* counters made rocprofv3 abort with signal 6 on this pool: left out)
 for set in "TCP_GATE_EN1_sum TCP_GATE_EN2_sum TCP_TCC_READ_REQ_LATENCY_sum TCP_TCP_LATENCY_sum" "TCP_UTCL1_TRANSLATION_MISS_sum TCP_UTCL1_TRANSLATION_HIT_sum TCP_UTCL1_REQUEST_sum TCP_TCC_READ_REQ_sum" "GRBM_GUI_ACTIVE SQ_BUSY_CYCLES TCP_TOTAL_ACCESSES_sum TD_TD_BUSY_sum"; do
