@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define RR_ABI_VERSION 6
+#define RR_ABI_VERSION 7
 #define RR_MAX_BATCH 64   /* frames (poses or material sets) one call renders in one set of launches */
 
 typedef struct rr_ctx rr_ctx;
@@ -183,18 +183,6 @@ int rr_simulate_columns_device(rr_ctx* ctx, const float pose_qxyzw_t[7], int az_
 int rr_simulate_batch_columns_device(rr_ctx* ctx, const float* poses, int n_frames, int az_begin, int az_end,
                                      uint8_t* d_cols_u8, void* stream);
 
-/* The same, carrying a device -> host copy of the CALLER's: carry_bytes from d_carry_src (device memory written by earlier
- * work on `stream`, e.g. the images this rank assembled from its previous batch on this stream) to h_carry_dst (page-locked:
- * rr_host_alloc) travel on this batch's later-pass trace launches -- a few waves with one 1-KB store in flight each, the
- * route rr_simulate_batch_host_async uses, which keeps the stores of the running kernels from queueing behind a bulk
- * copy.  The bytes are complete once `stream` has passed this call's launches.  With a single ray-cast pass, a pageable
- * destination or sizes that are not multiples of 16 the copy is a plain hipMemcpyAsync ahead of the batch.  This is how
- * the sharded step loop (one process per GPU, radarays_ros_amd/dist.py) leaves every frame in HOST memory like the
- * reference's simulate() does (RadarCPU.cpp:542,555-561) without paying a copy per batch. */
-int rr_simulate_batch_columns_carry_device(rr_ctx* ctx, const float* poses, int n_frames, int az_begin, int az_end,
-                                           uint8_t* d_cols_u8, void* stream,
-                                           const void* d_carry_src, void* h_carry_dst, size_t carry_bytes);
-
 /* Whole frames of n_frames (1..RR_MAX_BATCH) poses in one set of launches, everything on `stream` (no internal
  * streams: callers that want several batches in flight issue them on several streams, 4 is the measured
  * optimum): d_imgs_u8 = [n_frames][n_cells][n_angles].  The throughput entry point for offline generation
@@ -210,24 +198,21 @@ int rr_simulate_batch_device(rr_ctx* ctx, const float* poses, int n_frames, uint
  * frame lane, so the host does not wait for a copy before it issues the lane's next batch): no shader core stores a byte of
  * them, and it is the same engine whichever HIP runtime serves the process (a ROCm 7.0.2 runtime, e.g. the one a Python ML
  * wheel bundles, would carry a hipMemcpyAsync as a blit kernel: 27-35k images/s on config 2 where SDMA delivers the link's
- * 39k).  Where that path is not available (RR_HOST_SDMA=0, a pageable buffer, no reachable ROCr) a batch's images wait in
- * device memory and ride out on the trace launches of the next batch that uses the same frame lane (a few waves trickle them over PCIe with one store in
- * flight each, which keeps the stores of the running kernels from queueing behind them: within 1 % of the rate with the
- * images left in HBM, where a plain copy behind each batch costs 7 %); rr_wait_host / rr_synchronize / any other use of
- * the lane send what is still waiting with a plain copy.  Issue batches on up to four streams (HIP maps streams onto
- * four hardware queues) and hand the buffers out from a ring twice as deep as the batches in flight.  h_imgs_u8
- * should be page-locked (rr_host_alloc / rr_host_free = hipHostMalloc); a pageable buffer works through the plain copy.
- * rr_destroy drops images that nobody waited for.
- * `stream` must stay valid until rr_wait_host() / rr_synchronize() has returned for this buffer: a copy that did not
- * ride on a later batch is issued on it then.  "Returns at once" has two exceptions: a lane whose two previous
- * deliveries are both still in flight makes the call wait for the older one, and so does a buffer reallocation. */
+ * 39k).  Where that path is not available (RR_HOST_SDMA=0, a pageable buffer, statistics mode, no reachable ROCr) the
+ * images leave on a plain copy behind the batch, on `stream` (rr_copy_to_host_async's route: about 7 % fewer images/s than
+ * SDMA on the target, where the copy's PCIe-paced stores hold up the stores of the kernels beside it).  Issue batches on
+ * up to four streams (HIP maps streams onto four hardware queues) and hand the buffers out from a ring twice as deep as
+ * the batches in flight.  h_imgs_u8 should be page-locked (rr_host_alloc / rr_host_free = hipHostMalloc); a pageable
+ * buffer works through the plain copy.  rr_destroy drops images that nobody waited for.  "Returns at once" has two
+ * exceptions: a lane whose two previous deliveries are both still in flight makes the call wait for the older one, and
+ * so does a buffer reallocation. */
 int rr_simulate_batch_host_async(rr_ctx* ctx, const float* poses, int n_frames, uint8_t* h_imgs_u8, void* stream);
 int rr_wait_host(rr_ctx* ctx, const void* h_imgs_u8);
 void* rr_host_alloc(size_t bytes);
 void  rr_host_free(void* p);
 
-/* bytes of device memory -> host memory, asynchronous on `stream`, by the library's own copy kernel (one-wave workgroups,
- * 1 KB per wave and store, a bounded number of stores outstanding per wave) when h_dst is page-locked and both pointers
+/* bytes of device memory -> host memory, asynchronous on `stream`, by the library's own copy kernel (8 workgroups of 256
+ * threads on one XCD, 16 B per thread and store) when h_dst is page-locked and both pointers
  * and the size are multiples of 16 -- else a plain hipMemcpyAsync.  Why an entry point: which engine carries a
  * hipMemcpyAsync to page-locked memory is the choice of the HIP runtime in the caller's process (a ROCm 7.0.2 runtime
  * launches a blit kernel per copy and reads 27-36k images/s on config 2, the image's own ROCm 7.2 uses SDMA: 39.4k);
@@ -240,11 +225,11 @@ int rr_copy_to_host_async(rr_ctx* ctx, const void* d_src, void* h_dst, size_t by
  * over the SDMA engines (the route of rr_simulate_batch_host_async, csrc/rr_sdma.cpp) once the work enqueued on `stream` so
  * far has completed.  Returns at once; h_dst is complete -- and d_src may be overwritten -- after rr_wait_host(ctx, h_dst)
  * (NULL: everything outstanding) or rr_synchronize().  Where the SDMA path is not available it is rr_copy_to_host_async plus
- * an event.  rr_multi's root and the sharded step loop's flush deliver this way. */
+ * an event.  rr_multi's root and the sharded step loop (radarays_ros_amd/dist.py) deliver this way. */
 int rr_deliver_to_host_async(rr_ctx* ctx, const void* d_src, void* h_dst, size_t bytes, void* stream);
 /* Which route the host deliveries of this context take: 2 = SDMA through ROCr (csrc/rr_sdma.cpp) is in use; 1 = it will be
- * tried by the first delivery; 0 = stream-ordered copies (RR_HOST_SDMA=0, or the path was not available / was switched off --
- * RR_HOST_SDMA_VERBOSE=1 says why).  bench.py prints it on its line, the GPU tests assert it. */
+ * tried by the first delivery; 0 = a stream-ordered copy behind the batch (RR_HOST_SDMA=0, or the path was not available /
+ * was switched off -- RR_HOST_SDMA_VERBOSE=1 says why).  bench.py prints it on its line, the GPU tests assert it. */
 int rr_host_delivery_route(rr_ctx* ctx);
 
 /* Assemble the mono8 image from column-major columns, applying scroll_image
@@ -380,8 +365,8 @@ int rr_get_trace_grid(rr_ctx* ctx, uint32_t out_rows[24], uint32_t out_hist[24],
  * rr_multi's device entries) that has been issued before with the same shape -- azimuth block, frames, output buffer,
  * trace rows -- is captured in a hipGraph on its second use and replayed from then on: one hipGraphLaunch instead of
  * 4..20 kernel launches (host time per chain 46 -> ~11 us at 4 passes); the poses of a replay travel as the parameters of the
- * graph's first node.  Chains that carry a host copy, parameter batches and instrumented runs (timing / statistics /
- * roctx) are issued kernel by kernel.  Any setter, mesh change or buffer reallocation drops the captured graphs.
+ * graph's first node.  Parameter batches and instrumented runs (timing / statistics / roctx) are issued kernel by
+ * kernel.  Any setter, mesh change or buffer reallocation drops the captured graphs.
  * Returns how many chains this context has captured / replayed. */
 int rr_get_graph_stats(rr_ctx* ctx, uint64_t* captures, uint64_t* replays);
 /* average duration (ms) of the trace kernel launches since the last call with
@@ -452,7 +437,7 @@ int rr_multi_simulate_batch(rr_multi* m, const float* poses, int n_frames, uint8
  * BATCH IN FLIGHT: error bits are kept per frame lane, not per batch, and the drain reads and clears them all, so the other
  * batches that were in flight report the same code from the rr_multi_wait for their own buffer (or from the call that next
  * uses their slot), whatever their images look like; rr_multi_wait(m, NULL) reports the error once for all of them.
- * With ONE device a batch takes rr_simulate_batch_host_async's route (deferred, trickled host copy). */
+ * With ONE device a batch takes rr_simulate_batch_host_async's route (SDMA, or the stream-ordered copy behind the batch). */
 int rr_multi_simulate_batch_async(rr_multi* m, const float* poses, int n_frames, uint8_t* h_imgs_u8);
 int rr_multi_wait(rr_multi* m, const void* h_imgs_u8);
 
@@ -501,21 +486,10 @@ void rr_free_mesh(rr_mesh* m);
  * RR_STREAM_LANES (3)     lanes whose own stream rr_simulate_device rotates over
  * RR_STACKLESS (0)        1: k_trace walks the tree WITHOUT a stack (parent links, a node re-fetched each time the walk returns to it;
  *                         no LDS) -- the traversal north_star names, built and measured in round 6: same images, slower
- * RR_COPY_BLOCKS (8)      one-wave workgroups of a trace launch that trickle a deferred host copy; 0: never fold
  * RR_HOST_SDMA (1)         rr_simulate_batch_host_async hands a batch's images to the SDMA engines through ROCr (hsa_amd_memory_async_copy,
- *                         a worker thread per context; page-locked destinations) -- the same engine under every HIP runtime; 0: the
- *                         deferred copies below (trickled out by the next batch's trace launches / the copy kernel).  RR_HOST_SDMA_VERBOSE=1
- *                         says on stderr why the path was not available or was switched off
- * RR_SDMA_ACTIVE_US (0)    ... a worker waits this long actively for a copy's completion signal before it sleeps on it (measured: no
- *                         gain with two workers, the other one has the next copy queued already)
- * RR_HOST_COPY_STREAM (0) 1: one-pass frames (nothing later could carry their images) are copied out at once on one dedicated stream
- * RR_FLUSH_KERNEL (1)     a host copy that does not ride on a trace launch (one-pass frames, the end of a run, rr_copy_to_host_async)
- *                         is stored by the library's own kernel when the destination is page-locked; 0: hipMemcpyAsync
- * RR_FLUSH_BLOCKS (8)     ... its workgroups
- * RR_FLUSH_INFLIGHT (0)   ... 1-KB stores a wave keeps outstanding (0: no limit)
- * RR_FLUSH_THREADS (256)  ... threads per workgroup (64..1024)
- * RR_FLUSH_XCD (0)        ... the XCD all of them run on (PCIe-paced stores then fill the write queues of one XCD only); -1: all eight
- * RR_FOLD_MIN_BUSY (2)    other lanes that must be busy for a host copy to be folded into the next batch
+ *                         a worker thread per context; page-locked destinations) -- the same engine under every HIP runtime; 0: a
+ *                         stream-ordered copy behind the batch (the library's copy kernel, or hipMemcpyAsync for a pageable buffer).
+ *                         RR_HOST_SDMA_VERBOSE=1 says on stderr why the path was not available or was switched off
  * RR_CULL_POP (1)         later passes drop stack entries at pop time by their distance bound; 0: off (same images)
  * RR_GRAPH_GUARD (1)      launch graphs: two execs per shape used alternately, the host waits for an exec's previous launch before it re-sets
  *                         its poses; 0 (probe): one exec, no wait -- relies on in-flight launches being unaffected by node updates

@@ -35,9 +35,8 @@ void launch_debug_trace(const Params& P, const float* origs, const float* dirs, 
 void launch_encode_refs(Node4* nodes, size_t n_nodes, uint32_t tri_base4, hipStream_t s, size_t n_tris);
 void launch_mat_limits(const float4* materials, size_t n, double* limits, hipStream_t s);
 void* trace0_kernel(bool spill, bool stackless);
-Params trace0_params(const Params& P);
 void launch_score(const uint8_t* imgs, const uint8_t* ref, size_t npx, int n_images, unsigned long long* sse, hipStream_t s);
-void launch_copy_host(const void* src, void* dst, size_t bytes, int blocks, int inflight, int xcd, hipStream_t s, int threads);
+void launch_copy_host(const void* src, void* dst, size_t bytes, int blocks, int xcd, hipStream_t s);
 void launch_copy_words(const void* src, void* dst, size_t bytes, hipStream_t s);
 void launch_debug_brdf(size_t n, const float* in, int model, float* out, hipStream_t s);
 void launch_store_u32(const uint32_t* src, uint32_t* h_dst, hipStream_t s);
@@ -131,10 +130,7 @@ struct Lane {
     // buffer that is in no record any more has been delivered.
     struct CopyRec { const void* dst = nullptr; hipEvent_t ev = nullptr; bool pending = false; } rec[2];
     int rec_next = 0;
-    // a batch's images stay in d_img_u8 ("deferred") until the lane's NEXT host-delivery batch, whose later-pass trace
-    // launches carry the copy (see Params::copy_src); rr_wait_host / rr_synchronize / any other use of the lane flush a
-    // deferred copy with a plain hipMemcpyAsync
-    // ... or, the default: the batch's images leave at once over SDMA (rr_sdma.cpp).  TWO image buffers per lane, used alternately
+    // the default route: a batch's images leave at once over SDMA (rr_sdma.cpp).  TWO image buffers per lane, used alternately
     // (d_img_u8 and d_img_u8_b), each with its event (behind the assemble that filled it) and the job that empties it: a buffer
     // is written again two uses of the lane later (eight batches with four lanes), by which time its copy has long left -- the
     // host checks the job before it reuses the buffer and practically never has to wait (with ONE buffer it waited for the lane's
@@ -142,8 +138,6 @@ struct Lane {
     // on config 2 from a C++ caller, 2.5k instead of 4.3k with one pose per batch on the target)
     DevBuf<uint8_t> d_img_u8_b; hipEvent_t ev_img[2] = { nullptr, nullptr }; int img_flip = 0;
     uint64_t sdma_job[2] = { 0, 0 }; const void* sdma_dst[2] = { nullptr, nullptr };
-    bool deferred = false;
-    uint8_t* def_dst = nullptr; size_t def_bytes = 0; hipStream_t def_stream = nullptr; bool def_foldable = false;
 };
 
 struct rr_ctx {
@@ -215,31 +209,19 @@ struct rr_ctx {
     void* h_frame = nullptr; size_t h_frame_bytes = 0;   // page-locked: error bits + per-pass counters of rr_simulate's frame
 
     bool roctx = false;
-    int fold_min_busy = 2;       // other lanes that must have a batch in flight for a host copy to be folded (RR_FOLD_MIN_BUSY)
     int seg_chunk = 16;          // later-pass trace grids in chunks of S neighbouring segments, segment-fast inside a chunk (RR_TRACE_CHUNK; 0: rows of one segment)
     int stackless = 0;           // RR_STACKLESS=1: the stack-free traversal (no LDS; DESIGN.md §3 says what it costs)
     int cull_pop = 1;            // k_trace's later passes drop stack entries at pop time (RR_CULL_POP=0: off; the images are the same either way)
-    // a deferred host copy that cannot ride on a later-pass trace launch (one-pass frames, the last batch of a run, a caller
-    // with a single batch in flight) is stored by the library's own kernel (k_copy_host) when the destination is page-locked:
-    // flush_blocks one-wave workgroups with at most flush_inflight 1-KB stores outstanding each (RR_FLUSH_BLOCKS, RR_FLUSH_INFLIGHT;
-    // RR_FLUSH_KERNEL=0: hipMemcpyAsync, i.e. whichever engine the process' HIP runtime picks)
-    int flush_kernel = 1, flush_blocks = 8, flush_inflight = 0;
-    int flush_threads = 256;     // threads per workgroup of the copy kernel (RR_FLUSH_THREADS)
-    int flush_xcd = 0;           // the copy kernel's workgroups all on this XCD (RR_FLUSH_XCD 0..7; -1: dealt out over all eight)
-    // RR_HOST_COPY_STREAM=1 (experiment, round 6): a batch that cannot fold its predecessor's images into a trace launch (one-pass
-    // frames) sends its OWN images at once on one dedicated copy stream -- copies then run one at a time, in order, beside the
-    // batches instead of in front of the lane's next one
-    int host_copy_stream = 0; hipStream_t copy_stream = nullptr;
     // RR_HOST_SDMA (1): rr_simulate_batch_host_async hands a batch's images to ROCr's SDMA path (rr_sdma.cpp: one worker thread,
     // copies in order, each behind its batch's last kernel) instead of a copy the HIP runtime would pick an engine for; 0, a
-    // pageable destination or a runtime ROCr cannot be reached through: the deferred / trickled copies below
+    // pageable destination, statistics mode or a runtime ROCr cannot be reached through: a stream-ordered copy behind the batch
+    // (copy_out)
     int host_sdma = 1; SdmaCopier* sdma = nullptr; bool sdma_tried = false;
     // rr_deliver_to_host_async: copies of caller-owned device buffers that rr_wait_host fences (an SDMA job, or -- fallback -- an
     // event behind a stream-ordered copy); events are pooled
     struct Delivery { const void* dst; uint64_t job; hipEvent_t ev; };
     std::vector<Delivery> deliveries;
     std::vector<hipEvent_t> delivery_events;
-    int copy_blocks = 8;         // workgroups (one wave each) of a later-pass trace launch that trickle a folded host copy (RR_COPY_BLOCKS; 0: never fold)
     int tight_grid = 1;          // later-pass trace rows sized by what earlier batches needed (RR_TIGHT_GRID=0: the doubling bound)
     int tight_force = 0;         // RR_TIGHT_FORCE=n: rows of n workgroups whatever the history says (tests of the repair path)
     int hist_gen = 1;            // bumped whenever mesh / materials / beam / config change: the lanes' histories start over
@@ -374,7 +356,7 @@ void beam_trace_orders(const float* beams, size_t nb, std::vector<uint32_t>& ord
 hipError_t upload_table(rr_ctx* c, void* d_dst, const void* src, size_t bytes)
 {
     if (bytes == 0) return hipSuccess;
-    if (!c->flush_kernel || bytes % 4 != 0 || bytes > ((size_t)4 << 20)) return hipMemcpy(d_dst, src, bytes, hipMemcpyHostToDevice);
+    if (bytes % 4 != 0 || bytes > ((size_t)4 << 20)) return hipMemcpy(d_dst, src, bytes, hipMemcpyHostToDevice);
     if (c->h_rb_bytes < bytes) {
         if (c->h_rb) (void)hipHostFree(c->h_rb);
         c->h_rb = nullptr; c->h_rb_bytes = 0;
@@ -642,13 +624,13 @@ int take_rec(rr_ctx* c, Lane& L, Lane::CopyRec** out)
     return 0;
 }
 
-// device -> host on stream s: the library's own copy kernel when the destination is page-locked (`visible`) and everything is
-// 16-byte aligned, else hipMemcpyAsync (rr_copy_to_host_async in the header says why)
+// device -> host on stream s: the library's own copy kernel (8 workgroups, all on XCD 0) when the destination is page-locked
+// (`visible`) and everything is 16-byte aligned, else hipMemcpyAsync (rr_copy_to_host_async in the header says why)
 int copy_out(rr_ctx* c, const void* d_src, void* h_dst, size_t bytes, bool visible, hipStream_t s)
 {
     if (bytes == 0) return 0;
-    if (c->flush_kernel && visible && bytes % 16 == 0 && ((uintptr_t)h_dst | (uintptr_t)d_src) % 16 == 0) {
-        launch_copy_host(d_src, h_dst, bytes, c->flush_blocks, c->flush_inflight, c->flush_xcd, s, c->flush_threads);
+    if (visible && bytes % 16 == 0 && ((uintptr_t)h_dst | (uintptr_t)d_src) % 16 == 0) {
+        launch_copy_host(d_src, h_dst, bytes, 8, 0, s);
         RR_HIP(c, hipGetLastError());
     } else RR_HIP(c, hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, s));
     return 0;
@@ -667,23 +649,23 @@ bool host_visible(const void* p)
 int read_back(rr_ctx* c, void* dst, const void* d_src, size_t bytes)
 {
     if (bytes == 0) return 0;
-    if (!c->flush_kernel || bytes % 16 != 0 || (uintptr_t)d_src % 16 != 0) { RR_HIP(c, hipMemcpy(dst, d_src, bytes, hipMemcpyDeviceToHost)); return 0; }
+    if (bytes % 16 != 0 || (uintptr_t)d_src % 16 != 0) { RR_HIP(c, hipMemcpy(dst, d_src, bytes, hipMemcpyDeviceToHost)); return 0; }
     if (c->h_rb_bytes < bytes) {
         if (c->h_rb) (void)hipHostFree(c->h_rb);
         c->h_rb = nullptr; c->h_rb_bytes = 0;
         RR_HIP(c, hipHostMalloc(&c->h_rb, bytes + 4096, hipHostMallocDefault));
         c->h_rb_bytes = bytes + 4096;
     }
-    launch_copy_host(d_src, c->h_rb, bytes, 4, 0, -1, c->stream, 256);
+    launch_copy_host(d_src, c->h_rb, bytes, 4, -1, c->stream);
     RR_HIP(c, hipGetLastError());
     RR_HIP(c, hipStreamSynchronize(c->stream));
     std::memcpy(dst, c->h_rb, bytes);
     return 0;
 }
 
-// the lane's deferred host copy, now, as a plain copy on the stream its batch ran on
-// the images the lane's last host-delivery batch handed to the SDMA worker have left d_img_u8 (host wait; over long before a
-// lane comes round again)
+// the images the lane's last host-delivery batches handed to the SDMA worker have left the lane's image buffers (host wait;
+// over long before a lane comes round again).  Every user of the lane but the SDMA route itself, which looks after its two
+// buffers, calls it before it touches the lane
 void settle_sdma(rr_ctx* c, Lane& L, int slot = -1, const void* only_dst = nullptr)
 {
     for (int b = 0; b < 2; b++) {
@@ -692,21 +674,6 @@ void settle_sdma(rr_ctx* c, Lane& L, int slot = -1, const void* only_dst = nullp
         if (c->sdma) sdma_wait(c->sdma, L.sdma_job[b]);
         L.sdma_job[b] = 0; L.sdma_dst[b] = nullptr;
     }
-}
-
-int flush_deferred(rr_ctx* c, Lane& L, bool settle = true)
-{
-    if (settle) settle_sdma(c, L);       // (every user of the lane but the SDMA route itself, which looks after its two buffers)
-    if (!L.deferred) return 0;
-    Lane::CopyRec* r = nullptr;
-    int rc = take_rec(c, L, &r); if (rc) return rc;
-    { const int rcc = copy_out(c, L.d_img_u8.p, L.def_dst, L.def_bytes, L.def_foldable, L.def_stream); if (rcc) return rcc; }
-    RR_HIP(c, hipEventRecord(r->ev, L.def_stream));
-    r->dst = L.def_dst; r->pending = true;
-    RR_HIP(c, hipEventRecord(L.ev_consumed, L.def_stream));
-    L.pending_consume = true;
-    L.deferred = false;
-    return 0;
 }
 
 struct TimedScope {
@@ -764,9 +731,7 @@ struct SetPlan {
 
 int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end,
               uint8_t* d_cols_u8 /* null: the lane's own buffer */, float* d_cols_f32, hipStream_t s, int n_frames = 1,
-              const float4* d_matsets = nullptr, int mat_stride = 0, bool lane_f32 = false,
-              const uint8_t* copy_src = nullptr, uint8_t* copy_dst = nullptr, size_t copy_bytes = 0,
-              const SetPlan* plan = nullptr)
+              const float4* d_matsets = nullptr, int mat_stride = 0, bool lane_f32 = false, const SetPlan* plan = nullptr)
 {
     const rr_config g = eff_config(c);      // (a parameter batch may ask for more passes than the config)
     if (az_begin < 0 || az_end > g.n_angles || az_begin > az_end) return fail(c, -3, "azimuth range out of bounds");
@@ -838,16 +803,8 @@ int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end,
     for (int f = 0; f < pa.n; f++) for (int k = 0; k < 7; k++) pa.p[f][k] = pose[7 * f + k];
     P.pose_table = reinterpret_cast<float4*>(L.d_poses.p);
     // the launch chain of the batch
-    auto enqueue = [&](Params& Q) -> int {
+    auto enqueue = [&](const Params& Q) -> int {
     for (int pass = 0; pass < g.n_reflections; pass++) {
-        // the previous batch's images ride on the later-pass launches, one slice each (rr_simulate_batch_host_async)
-        Q.copy_blocks = 0;
-        if (pass >= 1 && copy_src) {
-            const size_t n16 = copy_bytes / 16, slices = (size_t)g.n_reflections - 1, k = (size_t)pass - 1;
-            const size_t b = n16 * k / slices, e = n16 * (k + 1) / slices;
-            Q.copy_src = reinterpret_cast<const uint4*>(copy_src) + b; Q.copy_dst = reinterpret_cast<uint4*>(copy_dst) + b;
-            Q.copy_n16 = e - b; Q.copy_blocks = c->copy_blocks;
-        }
         if (c->roctx) roctx_push(pass == 0 ? "trace pass 0" : "trace");
         if (c->timing) {
             // the kernel's own begin/end timestamps (hipExtLaunchKernel events), on its launch stream
@@ -872,11 +829,10 @@ int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end,
     };
     // Launch graphs: a chain that has been issued before with the same shape is captured once and replayed -- one
     // hipGraphLaunch instead of 4..20 launches (host time per device entry of rr_multi: 45-81 -> ~25 us).  Only plain pose
-    // batches: no carried host copy (its pointers move from call to call), no parameter batch, no timing / statistics /
-    // roctx instrumentation; whatever a captured launch bakes in is covered by graph_gen (tables, tree, lane buffers) or
-    // by the key (azimuth block, frames, output buffer, trace rows)
+    // batches: no parameter batch, no timing / statistics / roctx instrumentation; whatever a captured launch bakes in is
+    // covered by graph_gen (tables, tree, lane buffers) or by the key (azimuth block, frames, output buffer, trace rows)
     if (L.graph_gen != c->graph_gen) { drop_graphs(L); L.graph_gen = c->graph_gen; }
-    const bool graphable = !d_matsets && c->use_graphs && !copy_src && !c->timing && !c->stats_mode && !c->roctx && !d_cols_f32 && g.n_reflections > 0;
+    const bool graphable = !d_matsets && c->use_graphs && !c->timing && !c->stats_mode && !c->roctx && !d_cols_f32 && g.n_reflections > 0;
     if (graphable) {
         Lane::FrameGraph* fg = nullptr;
         for (Lane::FrameGraph& x : L.graphs)
@@ -901,10 +857,9 @@ int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end,
             // hipEventSynchronize on an event whose stream is capturing as an error and invalidates the capture -- found by
             // fuzz_batch in round 6.  Captures are rare, once per shape: let the deliveries in flight finish first.)
             if (c->sdma) sdma_wait_all(c->sdma);
-            Params Q = P;
             hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
             if (e == hipSuccess) {
-                const int rcq = enqueue(Q);
+                const int rcq = enqueue(P);
                 hipGraph_t gph = nullptr;
                 e = hipStreamEndCapture(s, &gph);
                 if (rcq == 0 && e == hipSuccess && gph) {
@@ -917,7 +872,7 @@ int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end,
                             hipGraphNodeType ty; hipKernelNodeParams kp{};
                             if (hipGraphNodeGetType(nd, &ty) == hipSuccess && ty == hipGraphNodeTypeKernel &&
                                 hipGraphKernelNodeGetParams(nd, &kp) == hipSuccess && kp.func == trace0_kernel(P.spill_depth > 0, P.stackless != 0)) {
-                                fg->pose_node = nd; fg->pose_kp = kp; fg->pose_P = trace0_params(P); break;
+                                fg->pose_node = nd; fg->pose_kp = kp; fg->pose_P = P; break;
                             }
                         }
                         if (fg->pose_node) { fg->g = gph; fg->ge = ge; fg->ge2 = ge2; c->graph_captures++; }
@@ -1017,20 +972,12 @@ rr_ctx* rr_create(int device)
     if (getenv("RR_PASS0_AZ")) { const int a = atoi(getenv("RR_PASS0_AZ")); if (a == 1 || a == 2 || a == 4 || a == 8 || a == 16) c->pass0_az = a; }
     if (getenv("RR_STACK_LDS")) c->stack_lds_max = std::max(1, std::min(64, atoi(getenv("RR_STACK_LDS"))));
     if (getenv("RR_ROCTX") && atoi(getenv("RR_ROCTX")) != 0) c->roctx = roctx_load();
-    if (getenv("RR_FOLD_MIN_BUSY")) c->fold_min_busy = std::max(0, atoi(getenv("RR_FOLD_MIN_BUSY")));
     if (getenv("RR_CULL_POP")) c->cull_pop = atoi(getenv("RR_CULL_POP")) != 0;
     if (getenv("RR_STACKLESS")) c->stackless = atoi(getenv("RR_STACKLESS")) != 0;
     if (getenv("RR_TRACE_CHUNK")) c->seg_chunk = std::max(0, std::min(1024, atoi(getenv("RR_TRACE_CHUNK"))));
-    if (getenv("RR_COPY_BLOCKS")) c->copy_blocks = std::max(0, std::min(26, atoi(getenv("RR_COPY_BLOCKS"))));
     if (getenv("RR_GRAPHS")) c->use_graphs = atoi(getenv("RR_GRAPHS")) != 0;
     if (getenv("RR_GRAPH_GUARD")) c->graph_guard = atoi(getenv("RR_GRAPH_GUARD")) != 0;
-    if (getenv("RR_FLUSH_KERNEL")) c->flush_kernel = atoi(getenv("RR_FLUSH_KERNEL")) != 0;
-    if (getenv("RR_HOST_COPY_STREAM")) c->host_copy_stream = atoi(getenv("RR_HOST_COPY_STREAM"));
     if (getenv("RR_HOST_SDMA")) c->host_sdma = atoi(getenv("RR_HOST_SDMA")) != 0;
-    if (getenv("RR_FLUSH_BLOCKS")) c->flush_blocks = std::max(1, std::min(1024, atoi(getenv("RR_FLUSH_BLOCKS"))));
-    if (getenv("RR_FLUSH_INFLIGHT")) c->flush_inflight = std::max(0, std::min(64, atoi(getenv("RR_FLUSH_INFLIGHT"))));
-    if (getenv("RR_FLUSH_XCD")) c->flush_xcd = std::max(-1, std::min(7, atoi(getenv("RR_FLUSH_XCD"))));
-    if (getenv("RR_FLUSH_THREADS")) c->flush_threads = std::max(64, std::min(1024, atoi(getenv("RR_FLUSH_THREADS"))));
     if (getenv("RR_TIGHT_GRID")) c->tight_grid = atoi(getenv("RR_TIGHT_GRID")) != 0;
     if (getenv("RR_TIGHT_FORCE")) c->tight_force = std::max(0, atoi(getenv("RR_TIGHT_FORCE")));
     {   // the one angle of total reflection that does not depend on the material table
@@ -1090,7 +1037,6 @@ void rr_destroy(rr_ctx* c)
         if (L.stream) (void)hipStreamDestroy(L.stream);
     }
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->h_frame) (void)hipHostFree(c->h_frame);
     if (c->h_rb) (void)hipHostFree(c->h_rb);
     delete c;
@@ -1395,7 +1341,7 @@ int rr_simulate_columns_device(rr_ctx* c, const float pose[7], int az_begin, int
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     const size_t li = c->next_lane++ % c->lanes.size();
     Lane& L = c->lanes[li];
-    { int rcf = flush_deferred(c, L); if (rcf) return rcf; }   // images a host-delivery batch left on this lane
+    settle_sdma(c, L);   // images a host-delivery batch is still sending from this lane
     c->last_lane = li;
     if (L.pending_consume) RR_HIP(c, hipStreamWaitEvent(s, L.ev_consumed, 0));
     rc = run_frame(c, L, pose, az_begin, az_end, d_cols_u8, d_cols_f32, s); if (rc) return rc;
@@ -1413,7 +1359,7 @@ int rr_simulate_batch_columns_device(rr_ctx* c, const float* poses, int n_frames
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     const size_t li = c->next_lane++ % c->lanes.size();
     Lane& L = c->lanes[li];
-    { int rcf = flush_deferred(c, L); if (rcf) return rcf; }   // images a host-delivery batch left on this lane
+    settle_sdma(c, L);   // images a host-delivery batch is still sending from this lane
     c->last_lane = li;
     { HostProfScope hp(0, "ctx: wait for the lane's event");
       if (L.pending_consume) RR_HIP(c, hipStreamWaitEvent(s, L.ev_consumed, 0)); }
@@ -1421,37 +1367,6 @@ int rr_simulate_batch_columns_device(rr_ctx* c, const float* poses, int n_frames
       rc = run_frame(c, L, poses, az_begin, az_end, d_cols_u8, nullptr, s, n_frames); if (rc) return rc; }
     { HostProfScope hp(2, "ctx: record the lane's event");
       RR_HIP(c, hipEventRecord(L.ev_consumed, s)); }
-    L.pending_consume = true;
-    return 0;
-}
-
-int rr_simulate_batch_columns_carry_device(rr_ctx* c, const float* poses, int n_frames, int az_begin, int az_end,
-                                           uint8_t* d_cols_u8, void* stream, const void* d_carry_src, void* h_carry_dst, size_t carry_bytes)
-{
-    int rc = check_ready(c); if (rc) return rc;
-    if (!poses || !d_cols_u8) return fail(c, -3, "rr_simulate_batch_columns_carry_device: null poses/output");
-    if (carry_bytes && (!d_carry_src || !h_carry_dst)) return fail(c, -3, "rr_simulate_batch_columns_carry_device: null carry pointer");
-    RR_HIP(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    rc = upload_tables(c); if (rc) return rc;
-    const size_t li = c->next_lane++ % c->lanes.size();
-    Lane& L = c->lanes[li];
-    { int rcf = flush_deferred(c, L); if (rcf) return rcf; }
-    c->last_lane = li;
-    if (L.pending_consume) RR_HIP(c, hipStreamWaitEvent(s, L.ev_consumed, 0));
-    // the carried copy rides on the later-pass trace launches (a few waves, one 1-KB store per wave in flight: Params::copy_src)
-    // when there are such launches and the destination is page-locked; else it is a plain copy ahead of the batch
-    const bool visible = carry_bytes > 0 && host_visible(h_carry_dst);
-    const bool fold = visible && c->copy_blocks > 0 && eff_config(c).n_reflections >= 2 && carry_bytes % 16 == 0 && !c->stats_mode &&
-                      ((uintptr_t)d_carry_src | (uintptr_t)h_carry_dst) % 16 == 0;
-    if (carry_bytes && !fold) { const int rcc = copy_out(c, d_carry_src, h_carry_dst, carry_bytes, visible, s); if (rcc) return rcc; }
-    rc = run_frame(c, L, poses, az_begin, az_end, d_cols_u8, nullptr, s, n_frames, nullptr, 0, false,
-                   fold ? (const uint8_t*)d_carry_src : nullptr, fold ? (uint8_t*)h_carry_dst : nullptr, fold ? carry_bytes : 0);
-    if (rc) {
-        if (fold) (void)copy_out(c, d_carry_src, h_carry_dst, carry_bytes, true, s);    // refused before any launch: the copy still happens
-        return rc;
-    }
-    RR_HIP(c, hipEventRecord(L.ev_consumed, s));
     L.pending_consume = true;
     return 0;
 }
@@ -1467,7 +1382,7 @@ int rr_simulate_batch_device(rr_ctx* c, const float* poses, int n_frames, uint8_
     rc = upload_tables(c); if (rc) return rc;
     const size_t li = c->next_lane++ % c->lanes.size();
     Lane& L = c->lanes[li];
-    { int rcf = flush_deferred(c, L); if (rcf) return rcf; }   // images a host-delivery batch left on this lane
+    settle_sdma(c, L);   // images a host-delivery batch is still sending from this lane
     c->last_lane = li;
     if (L.pending_consume) RR_HIP(c, hipStreamWaitEvent(s, L.ev_consumed, 0));
     rc = run_frame(c, L, poses, 0, g.n_angles, nullptr, nullptr, s, n_frames); if (rc) return rc;
@@ -1541,7 +1456,7 @@ int rr_host_delivery_route(rr_ctx* c)
     if (!c) return -1;
     if (c->sdma && c->host_sdma && !sdma_failed(c->sdma, nullptr)) return 2;      // SDMA through ROCr: in use
     if (c->host_sdma && !c->sdma_tried) return 1;                                  // ... will be tried by the first delivery
-    return 0;                                                                      // stream-ordered copies (deferred / trickled / copy kernel)
+    return 0;                                                                      // stream-ordered copies behind the batch (copy_out)
 }
 
 int rr_copy_to_host_async(rr_ctx* c, const void* d_src, void* h_dst, size_t bytes, void* stream)
@@ -1566,10 +1481,9 @@ int rr_simulate_batch_host_async(rr_ctx* c, const float* poses, int n_frames, ui
     c->last_lane = li;
     const size_t bytes = (size_t)n_frames * g.n_cells * g.n_angles;
     // The default route: over the SDMA engines through ROCr, at once, behind this batch's assemble -- no shader core stores a
-    // byte of it, so nothing has to be deferred or trickled, and it is the same engine under every HIP runtime
+    // byte of it, so the batches beside it run at their HBM-resident rate, and it is the same engine under every HIP runtime
     const bool device_visible = host_visible(h_imgs_u8);
     if (SdmaCopier* sd = (device_visible && !c->stats_mode) ? sdma_of(c, c->d_bvh.p) : nullptr) {
-        rc = flush_deferred(c, L, false); if (rc) return rc;     // (images an earlier batch left on the lane by the other route)
         const int b = L.img_flip;
         settle_sdma(c, L, b);                                   // the job that empties THIS buffer: two uses of the lane ago
         DevBuf<uint8_t>& img = b ? L.d_img_u8_b : L.d_img_u8;
@@ -1592,67 +1506,27 @@ int rr_simulate_batch_host_async(rr_ctx* c, const float* poses, int n_frames, ui
         L.img_flip ^= 1;
         return 0;
     }
+    // The fallback (SDMA switched off or not available, a pageable destination, statistics mode): the images leave on a plain
+    // copy behind the batch, on its stream (copy_out).  Stores to host memory drain at PCIe speed, and the stores of the
+    // kernels beside them wait behind them: on the target this route delivers some 7 % fewer images/s than SDMA
     settle_sdma(c, L);
-    if (L.pending_consume) RR_HIP(c, hipStreamWaitEvent(s, L.ev_consumed, 0));   // the lane's previous batch, incl. its assemble
-    // the images the lane's previous batch left behind ride on this batch's later-pass launches when possible
-    // ... and worthwhile: the trickle (one 1-KB store per wave in flight, a few waves) needs about 1 ms per launch for 8
-    // images, which hides behind a launch only while other batches share the GPU with it; a caller with a single batch
-    // in flight gets the plain copy
-    int busy = 0;
-    for (Lane& M : c->lanes) if (&M != &L && M.pending_consume && hipEventQuery(M.ev_consumed) == hipErrorNotReady) busy++;
-    (void)hipGetLastError();
-    const bool fold = L.deferred && L.def_foldable && c->copy_blocks > 0 && g.n_reflections >= 2 && L.def_bytes % 16 == 0 &&
-                      L.d_img_u8.n >= bytes && !c->stats_mode && busy >= c->fold_min_busy;
-    const uint8_t* job_src = nullptr; uint8_t* job_dst = nullptr; size_t job_bytes = 0;
-    Lane::CopyRec* rec = nullptr;
-    if (fold) {
-        rc = take_rec(c, L, &rec); if (rc) return rc;
-        job_src = L.d_img_u8.p; job_dst = L.def_dst; job_bytes = L.def_bytes; L.deferred = false;
-    }
-    else { rc = flush_deferred(c, L); if (rc) return rc; if (L.pending_consume) RR_HIP(c, hipStreamWaitEvent(s, L.ev_consumed, 0)); }
+    if (L.pending_consume) RR_HIP(c, hipStreamWaitEvent(s, L.ev_consumed, 0));   // the lane's previous batch, incl. its copy
     if (L.d_img_u8.n < bytes) {
         RR_HIP(c, hipDeviceSynchronize());      // an earlier copy may still read the old buffer
         RR_HIP(c, L.d_img_u8.ensure(bytes));
     }
-    rc = run_frame(c, L, poses, 0, g.n_angles, nullptr, nullptr, s, n_frames, nullptr, 0, false, job_src, job_dst, job_bytes);
-    if (rc) {
-        if (fold) {     // the frame was refused before any launch: the folded copy still has to happen
-            (void)copy_out(c, job_src, job_dst, job_bytes, true, s);
-            RR_HIP(c, hipEventRecord(rec->ev, s)); rec->dst = job_dst; rec->pending = true;
-        }
-        return rc;
-    }
-    if (fold) { RR_HIP(c, hipEventRecord(rec->ev, s)); rec->dst = job_dst; rec->pending = true; }   // behind the launches that carried it
+    rc = run_frame(c, L, poses, 0, g.n_angles, nullptr, nullptr, s, n_frames); if (rc) return rc;
     { TimedScope t(c, s, "assemble");
       launch_assemble_u8(L.d_cols_u8.p, L.d_img_u8.p, g.n_angles, g.n_cells, g.scroll_image, s, g.n_angles,
                          (size_t)g.n_angles * g.n_cells, n_frames, (size_t)g.n_angles * g.n_cells); }
     RR_HIP(c, hipGetLastError());
-    RR_HIP(c, hipEventRecord(L.ev_consumed, s));
+    Lane::CopyRec* r = nullptr;
+    rc = take_rec(c, L, &r); if (rc) return rc;
+    rc = copy_out(c, L.d_img_u8.p, h_imgs_u8, bytes, device_visible, s); if (rc) return rc;
+    RR_HIP(c, hipEventRecord(r->ev, s));
+    r->dst = h_imgs_u8; r->pending = true;
+    RR_HIP(c, hipEventRecord(L.ev_consumed, s));      // what the lane's next user waits for: the batch and its copy
     L.pending_consume = true;
-    // Where do the images go from here?  A copy issued behind the batch costs the frame rate about the PCIe transfer
-    // time of the images, whoever stores the bytes (tools/probe_hostpath.py, 10M-triangle target, 8 poses per batch, 4
-    // streams; 3,950-4,050 images/s with the images left in HBM): hipMemcpyAsync on this stream 3,670-3,775; a separate
-    // copy stream 3,250-3,840 (a fifth stream shares a hardware queue with a batch stream); the assemble kernel writing
-    // straight into the host buffer 3,515; an own copy kernel of 4..128 workgroups 3,590-3,650; the copy folded into a
-    // trace launch with all its stores in flight 3,580-3,650 -- while copies of 1 MB per batch cost nothing
-    // (tools/probe_fence.py).  What stalls is the memory pipeline: stores to host memory drain at PCIe speed, and once
-    // they fill its write queues the stores of every other kernel wait behind them.  So the copy is DEFERRED to the lane's
-    // next batch and trickled out by a few waves of its later-pass trace launches with ONE store per wave in flight
-    // (k_trace, Params::copy_src): 3,980-4,025 images/s, within 1 % of the HBM-resident rate.
-    if (c->host_copy_stream && g.n_reflections < 2) {
-        // nothing later could carry these images: out they go now, on the copy stream, behind this batch's assemble; the lane's
-        // next batch waits for the copy (device side) before it touches the lane
-        if (!c->copy_stream) RR_HIP(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-        Lane::CopyRec* r = nullptr;
-        rc = take_rec(c, L, &r); if (rc) return rc;
-        RR_HIP(c, hipStreamWaitEvent(c->copy_stream, L.ev_consumed, 0));
-        rc = copy_out(c, L.d_img_u8.p, h_imgs_u8, bytes, device_visible, c->copy_stream); if (rc) return rc;
-        RR_HIP(c, hipEventRecord(r->ev, c->copy_stream));
-        r->dst = h_imgs_u8; r->pending = true;
-        RR_HIP(c, hipEventRecord(L.ev_consumed, c->copy_stream));      // what the lane's next user waits for
-        return 0;
-    }
-    L.deferred = true; L.def_dst = h_imgs_u8; L.def_bytes = bytes; L.def_stream = s; L.def_foldable = device_visible;
     return 0;
 }
 
@@ -1675,7 +1549,6 @@ int rr_wait_host(rr_ctx* c, const void* h_imgs_u8)
     for (size_t k = 0; k < nl; k++) {
         Lane& L = c->lanes[(c->next_lane + k) % nl];
         settle_sdma(c, L, -1, h_imgs_u8);
-        if (L.deferred && (h_imgs_u8 == nullptr || L.def_dst == h_imgs_u8)) { int rc = flush_deferred(c, L); if (rc) return rc; }
         for (Lane::CopyRec& r : L.rec)
             if (r.pending && (h_imgs_u8 == nullptr || r.dst == h_imgs_u8)) {
                 RR_HIP(c, hipEventSynchronize(r.ev));
@@ -1728,7 +1601,7 @@ int rr_simulate_param_sets_device(rr_ctx* c, const float pose[7], const rr_param
     rc = upload_tables(c); if (rc) return rc;
     const size_t li = c->next_lane++ % c->lanes.size();
     Lane& L = c->lanes[li];
-    { int rcf = flush_deferred(c, L); if (rcf) return rcf; }   // images a host-delivery batch left on this lane
+    settle_sdma(c, L);   // images a host-delivery batch is still sending from this lane
     c->last_lane = li;
     if (L.pending_consume) RR_HIP(c, hipStreamWaitEvent(s, L.ev_consumed, 0));
     static_assert(sizeof(rr_material) == sizeof(float4), "rr_material is {velocity, ambient, diffuse, specular}");
@@ -1772,7 +1645,7 @@ int rr_simulate_param_sets_device(rr_ctx* c, const float pose[7], const rr_param
     }
     if (!rc) {
         launch_mat_limits(L.d_matsets.p, (size_t)n_sets * n_mat, L.d_matset_limits.p, s);
-        rc = run_frame(c, L, pose, 0, g0.n_angles, nullptr, nullptr, s, n_sets, L.d_matsets.p, (int)n_mat, false, nullptr, nullptr, 0, &plan);
+        rc = run_frame(c, L, pose, 0, g0.n_angles, nullptr, nullptr, s, n_sets, L.d_matsets.p, (int)n_mat, false, &plan);
     }
     c->passes_override = -1;
     if (rc) {
@@ -1935,7 +1808,7 @@ int rr_simulate_device(rr_ctx* c, const float pose[7], uint8_t* d_img_u8, void* 
     const int A = c->cfg.n_angles;
     if (c->lanes.size() == 1) {
         Lane& L = c->lanes[0];
-        { int rcf = flush_deferred(c, L); if (rcf) return rcf; }   // images a host-delivery batch left on this lane
+        settle_sdma(c, L);   // images a host-delivery batch is still sending from this lane
         c->last_lane = 0;
         // With ONE lane every launch of the frame goes to the caller's stream, so the call can be CAPTURED into a hipGraph
         // (hipStreamBeginCapture on `user`, this call, hipStreamEndCapture) and replayed -- tools/cpp_bench.cpp `graph`.  While
@@ -1957,7 +1830,7 @@ int rr_simulate_device(rr_ctx* c, const float pose[7], uint8_t* d_img_u8, void* 
     // that assemble has consumed its columns.
     const size_t li = c->next_stream_lane++ % (size_t)c->stream_lanes;
     Lane& L = c->lanes[li];
-    { int rcf = flush_deferred(c, L); if (rcf) return rcf; }   // images a host-delivery batch left on this lane
+    settle_sdma(c, L);   // images a host-delivery batch is still sending from this lane
     c->last_lane = li;
     if (L.pending_consume) RR_HIP(c, hipStreamWaitEvent(L.stream, L.ev_consumed, 0));
     rc = run_frame(c, L, pose, 0, A, nullptr, nullptr, L.stream); if (rc) return rc;
@@ -1973,7 +1846,7 @@ int rr_synchronize(rr_ctx* c, void* stream)
 {
     if (!c) return -1;
     RR_HIP(c, hipSetDevice(c->device));
-    for (Lane& L : c->lanes) { int rc = flush_deferred(c, L); if (rc) return rc; }
+    for (Lane& L : c->lanes) settle_sdma(c, L);
     if (!c->deliveries.empty()) { const int rc = rr_wait_host(c, nullptr); if (rc) return rc; }
     for (Lane& L : c->lanes) RR_HIP(c, hipStreamSynchronize(L.stream));
     RR_HIP(c, hipStreamSynchronize(stream ? (hipStream_t)stream : c->stream));
@@ -2004,7 +1877,7 @@ int rr_peek_error_bits_async(rr_ctx* c, uint32_t* h_bits, void* stream)
     Lane& L = c->lanes[c->last_lane];
     if (!L.d_sticky.p) { *h_bits = 0; return 0; }     // no frame has run on this lane yet
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (c->flush_kernel && host_visible(h_bits)) { launch_store_u32(L.d_sticky.p, h_bits, s); RR_HIP(c, hipGetLastError()); }     // (a kernel's store: no copy engine involved)
+    if (host_visible(h_bits)) { launch_store_u32(L.d_sticky.p, h_bits, s); RR_HIP(c, hipGetLastError()); }     // (a kernel's store: no copy engine involved)
     else RR_HIP(c, hipMemcpyAsync(h_bits, L.d_sticky.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     return 0;
 }
@@ -2046,7 +1919,7 @@ int rr_simulate(rr_ctx* c, const float pose[7], int az_begin, int az_end,
     if (n_seg == 0) { if (stats) std::memset(stats, 0, sizeof(*stats)); return 0; }
     rc = upload_tables(c); if (rc) return rc;
     Lane& L = c->lanes[0];
-    { int rcf = flush_deferred(c, L); if (rcf) return rcf; }   // images a host-delivery batch left on this lane
+    settle_sdma(c, L);   // images a host-delivery batch is still sending from this lane
     c->last_lane = 0;
     // The reference's call shape: one synchronous simulate() per frame (radar_simulator.cpp:197-212).  Its latency is
     // the chain of kernels plus what the host adds around it, so the host adds as little as it can: the frame is

@@ -487,27 +487,11 @@ __global__ __launch_bounds__(kTraceThreads) void k_trace(const Params P, const i
     // so the waves that run at the same time are neighbours in azimuth: k_trace 128 us (round 1: Morton
     // order of the samples inside one azimuth, azimuth after azimuth) -> 80 us per 640k rays at config 2.
     // Every wave is full, too (200 rays per azimuth would otherwise leave a 13th wave with 8 rays)
-    // later passes may carry a host copy in row 0 of the grid (see Params::copy_src)
-    const int row0 = FIRST ? 0 : (P.copy_blocks > 0 ? 1 : 0);
-    if (!FIRST && row0 && blockIdx.y == 0) {
-        if ((int)blockIdx.x < P.copy_blocks) {
-            __builtin_amdgcn_s_setprio(0);
-            const size_t nthreads = (size_t)P.copy_blocks * kTraceThreads;
-            for (size_t i = (size_t)blockIdx.x * kTraceThreads + threadIdx.x; i < P.copy_n16; i += nthreads) {
-                const uint4 v = P.copy_src[i];
-                P.copy_dst[i] = v;
-                // ONE store per wave in flight: the writes leave at the pace PCIe takes them instead of filling the
-                // memory pipeline's write queues, where the stores of every other kernel would wait behind them
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-        }
-        return;
-    }
-    int seg_y = (int)blockIdx.y - row0, gx = (int)blockIdx.x, gdim = (int)gridDim.x;
+    int seg_y = (int)blockIdx.y, gx = (int)blockIdx.x, gdim = (int)gridDim.x;
     if (!FIRST && P.seg_chunk > 0) {
-        // chunks of S neighbouring segments; inside a chunk the segment is the fast dimension: y - row0 = chunk * row + group
+        // chunks of S neighbouring segments; inside a chunk the segment is the fast dimension: y = chunk * row + group
         gdim = P.trace_row;
-        const int yy = (int)blockIdx.y - row0, ch = yy / gdim;
+        const int yy = (int)blockIdx.y, ch = yy / gdim;
         gx = yy - ch * gdim;
         seg_y = ch * P.seg_chunk + (int)blockIdx.x;
         if (seg_y >= P.n_seg) return;
@@ -1524,17 +1508,16 @@ __global__ __launch_bounds__(256) void k_score(const uint8_t* __restrict__ imgs,
 // Which engine a hipMemcpyAsync to page-locked memory runs on is the HIP runtime's choice -- the runtime bundled with the
 // torch wheel (ROCm 7.0.2) launches a blit kernel (`__amd_rocclr_copyBuffer`) that competes with the frame kernels and reads
 // 27-36k images/s on config 2, the image's own runtime uses SDMA (39.4k = the link) -- so a caller's process decided how fast
-// the library delivers.  This kernel is the library's own: one-wave workgroups, 16 B per lane (1 KB per wave and store),
-// at most `inflight` stores per wave outstanding (0: no limit).  The limit is what keeps the stores of OTHER kernels from
-// queueing behind PCIe-paced writes in the memory pipeline (the 7 % of DESIGN.md §5); a flush at the end of a run, with
-// nothing else on the chip, takes none.
+// the library delivers.  This kernel is the library's own: workgroups of 256 threads, 16 B per lane, every store issued
+// without a limit on those outstanding.
 // XCD confinement (xcd >= 0): the hardware deals the workgroups of a launch out to the 8 XCDs round robin in flat order, and
 // each XCD has its own L2 and its own path into the fabric; PCIe-paced stores fill the write queues of the XCD they come
 // from, and every other kernel's stores on THAT XCD wait behind them.  A launch of 8 x blocks workgroups of which only those
 // with blockIdx % 8 == xcd work keeps the damage to one eighth of the chip.
-// grid `blocks` (8 x blocks when confined), block 64
+// grid `blocks` (8 x blocks when confined), block 256
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void k_copy_host(const uint4* __restrict__ src, uint4* __restrict__ dst, size_t n16, int inflight, int xcd)
+constexpr int kCopyThreads = 256;
+__global__ __launch_bounds__(kCopyThreads) void k_copy_host(const uint4* __restrict__ src, uint4* __restrict__ dst, size_t n16, int xcd)
 {
     unsigned b = blockIdx.x, nb = gridDim.x;
     if (xcd >= 0) {
@@ -1543,22 +1526,19 @@ __global__ __launch_bounds__(1024) void k_copy_host(const uint4* __restrict__ sr
     }
     // (more loads in flight per lane -- the loop unrolled 2 / 4 / 8 times -- were measured and change nothing: 24-25k images/s
     // on config 2 in every shape; the runtime's own blit kernel is this very loop)
-    const size_t nthreads = (size_t)nb * blockDim.x;
-    int k = 0;
-    for (size_t i = (size_t)b * blockDim.x + threadIdx.x; i < n16; i += nthreads) {
+    const size_t nthreads = (size_t)nb * kCopyThreads;
+    for (size_t i = (size_t)b * kCopyThreads + threadIdx.x; i < n16; i += nthreads) {
         const uint4 v = src[i];
         dst[i] = v;
-        if (inflight > 0 && ++k >= inflight) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); k = 0; }
     }
 }
-void launch_copy_host(const void* src, void* dst, size_t bytes, int blocks, int inflight, int xcd, hipStream_t s, int threads)
+void launch_copy_host(const void* src, void* dst, size_t bytes, int blocks, int xcd, hipStream_t s)
 {
     const size_t n16 = bytes / 16;
     if (n16 == 0) return;
-    threads = std::max(64, std::min(1024, threads)) & ~63;
-    unsigned g = (unsigned)std::max<size_t>(1, std::min<size_t>((size_t)blocks, (n16 + threads - 1) / threads));
+    unsigned g = (unsigned)std::max<size_t>(1, std::min<size_t>((size_t)blocks, (n16 + kCopyThreads - 1) / kCopyThreads));
     if (xcd >= 0) g *= 8u;
-    hipLaunchKernelGGL(k_copy_host, dim3(g), dim3(threads), 0, s, reinterpret_cast<const uint4*>(src), reinterpret_cast<uint4*>(dst), n16, inflight, xcd);
+    hipLaunchKernelGGL(k_copy_host, dim3(g), dim3(kCopyThreads), 0, s, reinterpret_cast<const uint4*>(src), reinterpret_cast<uint4*>(dst), n16, xcd);
 }
 
 // rr_peek_error_bits_async: one word into a page-locked host word, by a kernel's store (no copy engine involved)
@@ -1649,15 +1629,13 @@ void launch_trace(const Params& P, int pass, const PoseArgs* poses, bool stats, 
     const bool tightened = pass > 0 && pass < kMaxPasses && P.tight_groups[pass];     // (the host keeps tightened rows odd itself)
     const unsigned row_odd = (pass > 0 && P.spill_depth == 0 && !tightened) ? (row | 1u) : row;
     dim3 grid = pass == 0 ? dim3((unsigned)((waves0 + (kTraceThreads / 64) - 1) / (kTraceThreads / 64)))
-                          : dim3(row_odd, n_seg + (P.copy_blocks > 0 ? 1 : 0));
+                          : dim3(row_odd, n_seg);
     Params Pl = P;
     if (pass > 0 && P.seg_chunk > 0) {
         const unsigned S = (unsigned)P.seg_chunk, n_chunks = ((unsigned)n_seg + S - 1) / S;
-        if ((size_t)n_chunks * row + 1 <= 65535) { grid = dim3(S, n_chunks * row + (P.copy_blocks > 0 ? 1 : 0)); Pl.trace_row = (int)row; }
+        if ((size_t)n_chunks * row < 65535) { grid = dim3(S, n_chunks * row); Pl.trace_row = (int)row; }
         else Pl.seg_chunk = 0;        // (beyond the grid's y limit: the plain layout)
     }
-    if (pass == 0) Pl.copy_blocks = 0;
-    else Pl.copy_blocks = std::min<int>(P.copy_blocks, (int)grid.x);      // the copy's workgroups are the first of row 0
     dim3 block(kTraceThreads);
     // later passes cull stack entries at pop time (6-B entries) as long as 32 one-wave workgroups still fit a CU's 160 KB of LDS
     // (5 KB each: up to 53 entries); a deeper tree keeps the 4-B entries -- the lost occupancy would cost more than the
@@ -1703,8 +1681,6 @@ void* trace0_kernel(bool spill, bool stackless)
     if (stackless) return (void*)k_trace<true, false, false, false, true>;
     return spill ? (void*)k_trace<true, false, true, false> : (void*)k_trace<true, false, false, false>;
 }
-// ... and the Params bytes launch_trace hands that kernel
-Params trace0_params(const Params& P) { Params Pl = P; Pl.copy_blocks = 0; return Pl; }
 
 // (ev_start / ev_stop, timing mode: the dispatch's own begin / end timestamps -- what rocprofv3 reports as the kernel's
 // duration -- not the time the launch spent waiting for the kernels of other streams)

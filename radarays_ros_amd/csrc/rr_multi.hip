@@ -239,9 +239,9 @@ rr_multi* rr_create_multi(const int* devices, int n_devices)
     // batches in flight: 4 streams per device = its 4 hardware queues, the measured optimum of the one-GPU step loop
     int n_slots = getenv("RR_MULTI_SLOTS") ? atoi(getenv("RR_MULTI_SLOTS")) : 4;
     n_slots = std::max(1, std::min(n_slots, 8));
-    // One device: a batch owns no buffers here (its images wait on the ctx's frame lane until the lane's next batch carries
-    // them out), so the records outnumber the streams two to one -- a call then waits for the batch EIGHT back, not for
-    // the one whose deferred images its own launches are about to carry (that wait would force the plain copy every time)
+    // One device: a batch owns no buffers here (its images are assembled in the ctx's frame lane, which delivers them to the
+    // host itself), so the records outnumber the streams two to one -- a call waits for the batch EIGHT back, long finished,
+    // rather than for the one its stream ran last
     const bool self_rccl_early = n_devices == 1 && !loopback && getenv("RR_MULTI_SELF_RCCL") && atoi(getenv("RR_MULTI_SELF_RCCL")) != 0;
     m->slots.resize((size_t)((n_devices == 1 && !self_rccl_early) ? 2 * n_slots : n_slots));
     for (size_t si = 0; si < m->slots.size(); si++) {
@@ -305,6 +305,9 @@ void rr_destroy_multi(rr_multi* m)
 {
     if (!m) return;
     stop_workers(m);
+    // the root's deliveries (rr_deliver_to_host_async: SDMA copies issued by a worker thread, which no device sync waits for)
+    // may still read slot buffers: fence them before any slot buffer or stream goes
+    if (!m->ctx.empty()) (void)rr_wait_host(m->ctx[0], nullptr);
     for (size_t i = 0; i < m->ctx.size(); i++) { (void)hipSetDevice(m->devices[i]); (void)hipDeviceSynchronize(); }
     for (size_t i = 0; i < m->comms.size(); i++) if (m->comms[i]) g_rccl.CommDestroy(m->comms[i]);
     for (MultiSlot& S : m->slots) {
@@ -508,8 +511,8 @@ int rr_multi_simulate_batch_async(rr_multi* m, const float* poses, int n_frames,
     { rr::HostProfScope hp(9, "multi: wait for the slot"); const int rc = wait_slot(m, S); if (rc) return rc; }        // the batch that used this slot's buffers last
     const auto dev_msg = [&](int i) { return std::string("device ") + std::to_string(m->devices[(size_t)i]) + ": " + rr_last_error(m->ctx[(size_t)i]); };
     if (n == 1 && !m->self_rccl) {
-        // one device: no collective; the images take the ctx's own host delivery (deferred, trickled out by the next
-        // batch's trace launches: within 1 % of leaving them in HBM)
+        // one device: no collective; the images take the ctx's own host delivery (SDMA at once behind the batch, or the
+        // stream-ordered copy: rr_simulate_batch_host_async)
         RRM_HIP(m, hipSetDevice(m->devices[0]));
         int rc = rr_simulate_batch_host_async(m->ctx[0], poses, n_frames, out_imgs_u8, S.streams[0]);
         if (rc) return fail_drained(m, rc, dev_msg(0));

@@ -21,10 +21,9 @@ kernels of step k+1.
 
 `host_out=True`: the reference's simulate() ends with the image in HOST memory
 (m_polar_image, RadarCPU.cpp:542,555-561), so every rank also delivers the frames it
-assembled to page-locked host memory.  A copy behind each step costs ~7 % of the frame
-rate, so the images a slot assembled ride out on the later-pass trace
-launches of the slot's NEXT step (rr_simulate_batch_columns_carry_device, same stream:
-ordered behind the assemble that wrote them); `flush_host()` sends what is still waiting.
+assembled to page-locked host memory, right behind the assemble, over the SDMA engines
+(rr_deliver_to_host_async).  A slot's next step waits for that delivery before it
+enqueues anything on the slot.
 """
 import contextlib
 
@@ -67,7 +66,7 @@ class _Slot:
         self.recv = torch.zeros((max(n_frames * n_local, n_angles), n_cells), dtype=torch.uint8, device=device)
         self.images = torch.zeros((n_images, n_cells, n_angles), dtype=torch.uint8, device=device)
         self.done = torch.cuda.Event() if device.type == "cuda" else None
-        # host_out: where this slot's images end up, whether a set is still waiting in `images`, and the step it belongs to
+        # host_out: where this slot's images end up, whether their delivery is still outstanding, and the step they belong to
         self.host = None
         self.host_pending = False
         self.step_no = -1
@@ -120,6 +119,9 @@ class AzimuthShard:
         s = self.slots[self.k % len(self.slots)]
         self.k += 1
         C, nl = self.n_cells, self.n_loc
+        if self.host_out:
+            self._fence(s)           # the delivery of the slot's last step still reads s.images and writes s.host
+            s.host_step_no = -1
         with (torch.cuda.stream(s.stream) if s.stream is not None else contextlib.nullcontext()):
             sp = s.stream.cuda_stream if s.stream is not None else None
             if self.strong:
@@ -127,14 +129,7 @@ class AzimuthShard:
                 cols = gather_columns(s.block[0], self.n_angles, self.world, out=s.recv[:self.n_angles])
                 self.ctx.assemble_image_device(cols.data_ptr(), s.images[0].data_ptr(), sp)
             else:
-                if self.host_out and s.host_pending:
-                    # the images this slot assembled n_slots steps ago leave on this step's trace launches
-                    self.ctx.simulate_batch_columns_carry_device(poses, self.begin, self.end, s.block.data_ptr(), sp,
-                                                                 s.images.data_ptr(), s.host.data_ptr(), s.images.numel())
-                    s.host_pending = False
-                    s.host_step_no = s.step_no
-                else:
-                    self.ctx.simulate_batch_columns_device(poses, self.begin, self.end, s.block.data_ptr(), sp)
+                self.ctx.simulate_batch_columns_device(poses, self.begin, self.end, s.block.data_ptr(), sp)
                 if self.collective:
                     # frames d*fpr .. d*fpr+fpr-1 go to rank d; I receive [source rank][fpr][n_loc][C],
                     # source-rank order == azimuth order
@@ -147,11 +142,8 @@ class AzimuthShard:
                                                 s.images.data_ptr(), sp)
             s.step_no = self.k - 1
             if self.host_out:
-                if self.strong:          # latency mode: one frame, delivered at once
-                    self._deliver(s)
-                    s.host_step_no = s.step_no
-                else:
-                    s.host_pending = True
+                self._deliver(s)
+                s.host_step_no = s.step_no
             if s.done is not None:
                 s.done.record(s.stream)
             if done_event is not None:
@@ -164,38 +156,36 @@ class AzimuthShard:
 
     def _deliver(self, s):
         """slot.images -> slot.host behind the slot's stream, over the SDMA engines (rr_deliver_to_host_async: the delivered rate
-        then does not depend on which engine the process' HIP runtime would pick for a hipMemcpyAsync); a context without it
-        (the mock of the CPU tests) gets torch's copy"""
-        if s.stream is not None and hasattr(self.ctx, "deliver_to_host_async"):
+        then does not depend on which engine the process' HIP runtime would pick for a hipMemcpyAsync); fenced by _fence.  A
+        slot without a stream (the mock context of the CPU tests) gets torch's copy"""
+        if s.stream is not None:
             self.ctx.deliver_to_host_async(s.images.data_ptr(), s.host.data_ptr(), s.images.numel(), s.stream.cuda_stream)
-            self._delivered = True          # fenced by ctx.wait_host, not by the stream (the copy runs on the SDMA engines)
         else:
-            s.host.copy_(s.images, non_blocking=True)
+            s.host.copy_(s.images)
+        s.host_pending = True
+
+    def _fence(self, s):
+        """Wait until slot s's delivery (if one is outstanding) has completed: ctx.wait_host, not the stream (the copy runs on
+        the SDMA engines)"""
+        if s.host_pending:
+            if s.stream is not None:
+                self.ctx.wait_host(s.host.data_ptr())
+            s.host_pending = False
 
     def flush_host(self):
-        """host_out: deliver the images that are still waiting on their slots (copies on the slots' streams) and wait
-        for every delivery.  Afterwards slot.host holds the images of step slot.host_step_no for every slot."""
+        """host_out: wait for every delivery.  Afterwards slot.host holds the images of step slot.host_step_no for every slot."""
         if not self.host_out:
             return
         for s in self.slots:
-            if s.host_pending:
-                with (torch.cuda.stream(s.stream) if s.stream is not None else contextlib.nullcontext()):
-                    self._deliver(s)
-                s.host_pending = False
-                s.host_step_no = s.step_no
-        for s in self.slots:
-            if s.stream is not None:
-                s.stream.synchronize()
-        if getattr(self, "_delivered", False):
-            self.ctx.wait_host(None)
-            self._delivered = False
+            self._fence(s)
 
     def host_images(self, step_no):
-        """The host tensor [fpr][n_cells][n_angles] holding this rank's images of step `step_no`, or None when that step has
-        not been delivered (yet) or its slot has been handed to a later step.  Valid after flush_host(), or once the step
-        n_slots later on the same slot has completed."""
+        """The host tensor [fpr][n_cells][n_angles] holding this rank's images of step `step_no` (complete on return), or None
+        when that step has not been enqueued (yet) or its slot has been handed to a later step.  Valid until the slot is
+        reused, n_slots steps later."""
         for s in self.slots:
             if s.host is not None and s.host_step_no == step_no:
+                self._fence(s)
                 return s.host
         return None
 

@@ -50,8 +50,9 @@ def run(iters=20, seed=0, verbose=True):
         c.synchronize(sp); torch.cuda.synchronize()
         if not np.array_equal(imgs.cpu().numpy(), ref): what.append("batch_device")
         # (b3) host delivery: 5..9 batches of the K poses (rotated) on two streams, so that lanes and their copy records
-        # are reused; interleaved at random with a device-path batch on the same lanes (which must flush what waits
-        # there); waits in random order.  RR_FOLD_MIN_BUSY=0 (set by the caller's environment) forces the folded route
+        # are reused; interleaved at random with a device-path batch on the same lanes (which must wait for the
+        # deliveries still reading them); waits in random order.  RR_HOST_SDMA=0 (set by the caller's environment)
+        # selects the stream-ordered copy
         NB = int(rs.randint(5, 10))
         st2 = torch.cuda.Stream(device=dev)
         hosts = [native.HostImages((K, C, 400)) for _ in range(NB)]

@@ -146,11 +146,6 @@ class _MockCtx:
         for f, p in enumerate(poses):
             v[f * n:(f + 1) * n] = self._cols(p, b, e).ravel()
 
-    def simulate_batch_columns_carry_device(self, poses, b, e, ptr, sp, src, dst, nbytes):
-        self._view(dst, nbytes)[:] = self._view(src, nbytes)       # (the real call trickles it out on its trace launches)
-        self.carried = getattr(self, "carried", 0) + 1
-        self.simulate_batch_columns_device(poses, b, e, ptr, sp)
-
     def assemble_blocks_device(self, ptr, n_loc, stride, img_ptr, sp):
         img = self._view(img_ptr, self.C * self.A).reshape(self.C, self.A)
         for a in range(self.A):
@@ -195,18 +190,18 @@ def _worker_shard(rank, world, port, out_dir):
         imgs = weak.step(step_poses)
         for j in range(2):                               # I own frames rank*2 + j of the step
             ok &= int(np.array_equal(imgs[j].numpy(), full(step_poses[rank * 2 + j])))
-    # host_out: every frame also reaches host memory -- the images of step k ride out with step k + n_slots on the same slot,
-    # flush_host() sends the rest
+    # host_out: every frame also reaches host memory -- step k's images right behind its assemble, held until step
+    # k + n_slots reuses the slot; flush_host() waits for the rest
     hosty = AzimuthShard(ctx, cfg.n_cells, A, rank, world, dev, n_slots=2, frames_per_rank=2, host_out=True)
     kept = {}
     for k in range(5):
         step_poses = [poses[(k * 4 + f) % 8] for f in range(4)]
         kept[k] = [full(step_poses[rank * 2 + j]) for j in range(2)]
         hosty.step(step_poses)
-        if k >= 2:                                       # step k - 2 has been carried out by this call
-            h = hosty.host_images(k - 2)
-            ok &= int(h is not None and all(np.array_equal(h[j].numpy(), kept[k - 2][j]) for j in range(2)))
-    ok &= int(ctx.carried == 3 and hosty.host_images(4) is None)
+        h = hosty.host_images(k)                         # step k's images, right after step k
+        ok &= int(h is not None and all(np.array_equal(h[j].numpy(), kept[k][j]) for j in range(2)))
+        if k >= 2:                                       # step k - 2's slot has been handed to step k
+            ok &= int(hosty.host_images(k - 2) is None)
     hosty.flush_host()
     for k in (3, 4):
         h = hosty.host_images(k)
@@ -297,7 +292,7 @@ class _BenchMockCtx:
 
     def __init__(self, local_rank):
         self.rank = local_rank
-        self.calls = {"batch": 0, "carry": 0, "assemble": 0}
+        self.calls = {"batch": 0, "assemble": 0}
         self.C, self.A = 3424, 400
 
     def _view(self, ptr, n):
@@ -321,11 +316,6 @@ class _BenchMockCtx:
     def simulate_batch_columns_device(self, poses, b, e, ptr, sp):
         self.calls["batch"] += 1
         self._view(ptr, len(poses) * (e - b) * self.C)[:] = 10 + self.rank
-
-    def simulate_batch_columns_carry_device(self, poses, b, e, ptr, sp, src, dst, nbytes):
-        self.calls["carry"] += 1
-        self._view(dst, nbytes)[:] = self._view(src, nbytes)
-        self.simulate_batch_columns_device(poses, b, e, ptr, sp)
 
     def simulate_columns_device(self, pose, b, e, ptr, f32, sp):
         self._view(ptr, (e - b) * self.C)[:] = 10 + self.rank

@@ -70,7 +70,7 @@ def _reference_frames(native_lib, small, poses_batches):
 def test_multi_async_batches_in_flight(native_lib, small, monkeypatch, n_dev, threads):
     """rr_multi_simulate_batch_async: 7 batches of different sizes issued back to back over a ring of 5 host buffers
     (more batches than slots: a call that finds its slot busy waits for the older batch itself), waited for in a
-    scrambled order -- every image equals rr_simulate's.  n_dev = 1: the single-device route (deferred host copy);
+    scrambled order -- every image equals rr_simulate's.  n_dev = 1: the single-device route (the context's own host delivery);
     n_dev > 1: the n-device path in loopback (equal blocks 2 / 8, ragged 3); threads = 1: RR_MULTI_THREADS, one enqueue
     thread per device entry issues that entry's launches."""
     s, cfg, mats, beams, noise, poses = small
@@ -258,12 +258,9 @@ def _shard_worker(rank, world, port, strong, out_dir):
         sh.wait()
         torch.cuda.current_stream().synchronize()
         outs.append(imgs.cpu().numpy().copy())
-        # host delivery (bench.py's bracket): strong = at once; weak = carried out by the step n_slots later on the same slot
-        back = k if strong else k - 3
-        if back >= 0:
-            sh.slots[k % 3].stream.synchronize()
-            h = sh.host_images(back)
-            host_ok = host_ok and h is not None and np.array_equal(h.numpy(), outs[back])
+        # host delivery (bench.py's bracket): right behind the step's assemble in both modes, fenced by host_images
+        h = sh.host_images(k)
+        host_ok = host_ok and h is not None and np.array_equal(h.numpy(), outs[k])
     sh.flush_host()
     for k in range(len(steps) - 3, len(steps)):
         h = sh.host_images(k)

@@ -65,42 +65,45 @@ def test_multi_with_one_device_equals_rr_simulate(native_lib, small):
         native_lib.MultiContext([0, 977])
 
 
-@pytest.mark.parametrize("route", ["sdma", "deferred", "deferred_fold_always"])
+@pytest.mark.parametrize("route", ["sdma", "fallback", "fallback_pageable"])
 def test_batch_host_async_delivers_the_same_images(native_lib, small, route, monkeypatch):
-    """Images delivered to page-locked host memory, several batches in flight on two streams: every image equals
-    rr_simulate's; rr_wait_host(ptr) completes exactly that buffer.  Routes: `sdma` (the default since round 6: each batch's
-    images leave at once over the SDMA engines through ROCr, csrc/rr_sdma.cpp) and the fallback (RR_HOST_SDMA=0), where a
-    batch's images either leave with a plain copy or wait on their lane and ride out on the trace launches of the lane's next
-    batch (a few waves, one store in flight each) -- the library picks by how many other batches are in flight,
-    `deferred_fold_always` forces the second way wherever it is possible.  All checked byte for byte."""
+    """Images delivered to host memory, several batches in flight on two streams: every image equals rr_simulate's;
+    rr_wait_host(ptr) completes exactly that buffer.  Routes: `sdma` (the default since round 6: each batch's images leave
+    at once over the SDMA engines through ROCr, csrc/rr_sdma.cpp) and the fallback (RR_HOST_SDMA=0), where they leave on a
+    stream-ordered copy behind the batch -- into page-locked buffers (`fallback`: the library's copy kernel) or pageable
+    ones (`fallback_pageable`: hipMemcpyAsync).  All checked byte for byte."""
     import torch
     s, cfg, mats, beams, noise, poses = small
     monkeypatch.setenv("RR_HOST_SDMA", "1" if route == "sdma" else "0")
-    fold_always = route == "deferred_fold_always"
-    if fold_always:
-        monkeypatch.setenv("RR_FOLD_MIN_BUSY", "0")
     c = native_lib.Context(0)
     _setup(c, s, cfg, mats, beams, noise[0])
     ref = [c.simulate(p)[0] for p in poses]
     streams = [torch.cuda.Stream(), torch.cuda.Stream()]
     NB = 14                                  # 14 batches over 4 lanes: every lane is reused three times, its copy records too
-    bufs = [native_lib.HostImages((3, cfg.n_cells, 400)) for _ in range(NB)]
-    for b in bufs:
-        b.array[:] = 7
+    if route == "fallback_pageable":
+        bufs = []
+        arrays = [np.full((3, cfg.n_cells, 400), 7, np.uint8) for _ in range(NB)]
+        ptrs = [a.ctypes.data for a in arrays]
+    else:
+        bufs = [native_lib.HostImages((3, cfg.n_cells, 400)) for _ in range(NB)]
+        for b in bufs:
+            b.array[:] = 7
+        arrays = [b.array for b in bufs]
+        ptrs = [b.ptr for b in bufs]
     for k in range(NB):
         ps = [poses[(k + j) % 6] for j in range(3)]
-        c.simulate_batch_host_async(ps, bufs[k].ptr, streams[k % 2].cuda_stream)
-    # buffers are waited for one by one, the oldest (whose record has long been reused) and the newest (still deferred on
-    # its lane) first: each must be complete when its own wait returns, whatever the others are doing
+        c.simulate_batch_host_async(ps, ptrs[k], streams[k % 2].cuda_stream)
+    # buffers are waited for one by one, the oldest (whose record has long been reused) and the newest (its copy possibly
+    # still in flight) first: each must be complete when its own wait returns, whatever the others are doing
     for k in (0, NB - 1, 5, 9, 1, 12, 4):
-        c.wait_host(bufs[k].ptr)
+        c.wait_host(ptrs[k])
         for j in range(3):
-            assert np.array_equal(bufs[k].array[j], ref[(k + j) % 6]), (k, j)
+            assert np.array_equal(arrays[k][j], ref[(k + j) % 6]), (k, j)
     c.wait_host(None)
     c.synchronize()
     for k in range(NB):
         for j in range(3):
-            assert np.array_equal(bufs[k].array[j], ref[(k + j) % 6]), (k, j)
+            assert np.array_equal(arrays[k][j], ref[(k + j) % 6]), (k, j)
     # pageable memory works too (the copy then simply does not overlap)
     out = np.zeros((2, cfg.n_cells, 400), np.uint8)
     c.simulate_batch_host_async(poses[:2], out.ctypes.data, None)

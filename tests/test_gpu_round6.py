@@ -1,7 +1,7 @@
 """GPU tests of round 6 (include/radarays_mi355.h, ABI 6):
   * launch graphs replayed back to back with NO host synchronisation between the calls (advisor, round 5: a replay re-sets
     the pose node of an exec whose previous launch may still be queued) -- every batch must show ITS poses
-  * host delivery by the library's own copy kernel (rr_copy_to_host_async, k_copy_host): the bytes, whatever its shape
+  * host delivery by the library's own copy kernel (rr_copy_to_host_async, k_copy_host): the bytes, page-locked or pageable
   * the per-pass history reaches the host through a kernel's stores (no hipMemcpyAsync left in a chain)
   * k_trace with the root step peeled (RR_ROOT_PRELOAD builds) is covered by the ordinary parity suite: same code path
 """
@@ -73,9 +73,9 @@ def test_graph_replays_back_to_back_show_their_own_poses(native_lib, monkeypatch
     c.close()
 
 
-def test_copy_to_host_async_moves_the_bytes(native_lib, monkeypatch):
-    """rr_copy_to_host_async: page-locked destination -> the copy kernel (any number of workgroups / stores in flight),
-    pageable or misaligned -> hipMemcpyAsync; the same bytes either way."""
+def test_copy_to_host_async_moves_the_bytes(native_lib):
+    """rr_copy_to_host_async: page-locked destination -> the copy kernel, pageable or misaligned -> hipMemcpyAsync; the same
+    bytes either way."""
     import torch
     s = scenes.box12()
     cfg = params.kaist_preset(n_reflections=1, ambient_noise=0)
@@ -83,63 +83,69 @@ def test_copy_to_host_async_moves_the_bytes(native_lib, monkeypatch):
     n = 3 * 3424 * 400
     src = torch.from_numpy(rng.randint(0, 256, n + 64).astype(np.uint8)).to("cuda:0")
     st = torch.cuda.current_stream().cuda_stream
-    for blocks, inflight in (("1", "1"), ("7", "0"), ("64", "4"), ("1024", "64")):
-        monkeypatch.setenv("RR_FLUSH_BLOCKS", blocks)
-        monkeypatch.setenv("RR_FLUSH_INFLIGHT", inflight)
-        c = _ctx(native_lib, s, cfg, params.kaist_materials(), golden_beams(16))
-        h = native_lib.HostImages((n + 64,))
-        for off, nb in ((0, n), (16, 4096), (0, 16), (32, n - 32), (16, 1000), (3, 1000), (0, 0)):     # (16, 1000) / (3, 1000): not multiples of 16 / misaligned
-            h.array[:] = 0
-            c.copy_to_host_async(src.data_ptr() + off, h.ptr + off, nb, st)
-            c.synchronize(st)
-            assert np.array_equal(h.array[off:off + nb], src[off:off + nb].cpu().numpy()), (blocks, inflight, off, nb)
-            assert not h.array[off + nb:].any() and not h.array[:off].any()
-        pageable = np.zeros(n, np.uint8)
-        c.copy_to_host_async(src.data_ptr(), pageable.ctypes.data, n, st)
+    c = _ctx(native_lib, s, cfg, params.kaist_materials(), golden_beams(16))
+    h = native_lib.HostImages((n + 64,))
+    for off, nb in ((0, n), (16, 4096), (0, 16), (32, n - 32), (16, 1000), (3, 1000), (0, 0)):     # (16, 1000) / (3, 1000): not multiples of 16 / misaligned
+        h.array[:] = 0
+        c.copy_to_host_async(src.data_ptr() + off, h.ptr + off, nb, st)
         c.synchronize(st)
-        assert np.array_equal(pageable, src[:n].cpu().numpy())
-        h.close(); c.close()
+        assert np.array_equal(h.array[off:off + nb], src[off:off + nb].cpu().numpy()), (off, nb)
+        assert not h.array[off + nb:].any() and not h.array[:off].any()
+    pageable = np.zeros(n, np.uint8)
+    c.copy_to_host_async(src.data_ptr(), pageable.ctypes.data, n, st)
+    c.synchronize(st)
+    assert np.array_equal(pageable, src[:n].cpu().numpy())
+    h.close(); c.close()
 
 
 @pytest.mark.parametrize("passes", [1, 3])
-@pytest.mark.parametrize("flush", [("sdma",), ("1", "8", "1"), ("1", "64", "0"), ("0", "32", "4"), ("stream",)])
+@pytest.mark.parametrize("flush", [("sdma", "pinned"), ("off", "pinned"), ("stats", "pinned"), ("off", "pageable"),
+                                   ("sdma", "pageable")])
 def test_host_delivery_routes(native_lib, monkeypatch, passes, flush):
-    """rr_simulate_batch_host_async with one pass (no later-pass launch a copy could ride on) and with three, 18 batches over
-    four streams, under every route the images can take: `sdma` -- the default: ROCr's SDMA path, a worker thread, each copy
-    behind its batch's last kernel (csrc/rr_sdma.cpp) -- and, with RR_HOST_SDMA=0, the deferred copies: through k_copy_host
-    in several shapes, through hipMemcpyAsync (RR_FLUSH_KERNEL=0), one-pass frames on a dedicated copy stream
-    (RR_HOST_COPY_STREAM=1).  The images of rr_simulate, and each buffer complete when ITS wait returns."""
+    """rr_simulate_batch_host_async with one pass and with three, 18 batches over four streams, under every way the images
+    can take: the default -- ROCr's SDMA path, a worker thread, each copy behind its batch's last kernel (csrc/rr_sdma.cpp)
+    -- and the stream-ordered copy behind the batch wherever that path is not taken: RR_HOST_SDMA=0 or statistics mode
+    with page-locked buffers (k_copy_host), a pageable destination with RR_HOST_SDMA=0 or 1 (hipMemcpyAsync).  The images
+    of rr_simulate, and each buffer complete when ITS wait returns."""
     import torch
-    monkeypatch.setenv("RR_HOST_SDMA", "1" if flush[0] == "sdma" else "0")
+    how, dest = flush
+    monkeypatch.setenv("RR_HOST_SDMA", "0" if how == "off" else "1")
     monkeypatch.setenv("RR_HOST_SDMA_VERBOSE", "1")
-    if flush[0] == "stream":
-        monkeypatch.setenv("RR_HOST_COPY_STREAM", "1")
-    elif flush[0] != "sdma":
-        monkeypatch.setenv("RR_FLUSH_KERNEL", flush[0]); monkeypatch.setenv("RR_FLUSH_BLOCKS", flush[1]); monkeypatch.setenv("RR_FLUSH_INFLIGHT", flush[2])
     s = scenes.heightfield_room(64, n_buildings=40, seed=3)
     cfg = params.kaist_preset(n_reflections=passes, n_samples=60, ambient_noise=2)
     noise = (np.random.RandomState(5).uniform(0, 1, 400) * 1000.0).astype(np.float32)
     poses = scenes.trajectory(6, s["name"])
     c = _ctx(native_lib, s, cfg, materials_for(s), golden_beams(60), noise)
     ref = [c.simulate(p)[0] for p in poses]
+    if how == "stats":
+        c.set_stats_mode(True)
     streams = [torch.cuda.Stream() for _ in range(4)]
     NB = 18
-    bufs = [native_lib.HostImages((4, cfg.n_cells, 400)) for _ in range(NB)]
-    for b in bufs:
-        b.array[:] = 9
+    if dest == "pageable":
+        pinned = []
+        arrays = [np.full((4, cfg.n_cells, 400), 9, np.uint8) for _ in range(NB)]
+        ptrs = [a.ctypes.data for a in arrays]
+    else:
+        pinned = [native_lib.HostImages((4, cfg.n_cells, 400)) for _ in range(NB)]
+        for b in pinned:
+            b.array[:] = 9
+        arrays = [b.array for b in pinned]
+        ptrs = [b.ptr for b in pinned]
     for k in range(NB):
-        c.simulate_batch_host_async([poses[(k + j) % 6] for j in range(4)], bufs[k].ptr, streams[k % 4].cuda_stream)
+        c.simulate_batch_host_async([poses[(k + j) % 6] for j in range(4)], ptrs[k], streams[k % 4].cuda_stream)
     for k in (NB - 1, 0, 7, 16):
-        c.wait_host(bufs[k].ptr)
+        c.wait_host(ptrs[k])
         for j in range(4):
-            assert np.array_equal(bufs[k].array[j], ref[(k + j) % 6]), (k, j)
+            assert np.array_equal(arrays[k][j], ref[(k + j) % 6]), (k, j)
     c.wait_host(None)
     for k in range(NB):
         for j in range(4):
-            assert np.array_equal(bufs[k].array[j], ref[(k + j) % 6]), (k, j)
-    assert c.host_delivery_route() == ("sdma" if flush[0] == "sdma" else "stream copies")     # no silent fallback
+            assert np.array_equal(arrays[k][j], ref[(k + j) % 6]), (k, j)
+    # no silent fallback: SDMA in use exactly where it should be, never tried where the copy stays stream-ordered
+    assert c.host_delivery_route() == {"sdma": "sdma" if dest == "pinned" else "sdma (untried)", "stats": "sdma (untried)",
+                                       "off": "stream copies"}[how]
     c.synchronize()
-    for b in bufs:
+    for b in pinned:
         b.close()
     c.close()
 
