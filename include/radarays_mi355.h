@@ -123,8 +123,40 @@ int rr_set_mesh_gpu(rr_ctx* ctx, const float* verts /*[nv][3]*/, size_t nv,
 
 /* The finished tree of `src` (either builder), copied device to device into `ctx` -- `ctx` may sit on another GPU
  * (hipMemcpyPeer over xGMI) or on the same one.  What rr_multi_set_mesh uses to replicate the map after ONE build
- * (radar_simulator.cpp:149 loads the map once per process).  Both contexts are drained first; `src` keeps its tree. */
+ * (radar_simulator.cpp:149 loads the map once per process).  Both contexts are drained first; `src` keeps its tree.
+ * The rest geometry and the object poses (dynamic scenes, below) are copied too: the copy can be posed on its own. */
 int rr_copy_mesh(rr_ctx* ctx, rr_ctx* src);
+
+/* ---- dynamic scenes: per-object rigid poses, the tree refit in place ----
+ * A context with a mesh holds REST GEOMETRY -- the vertices and faces last given to rr_set_mesh, rr_set_mesh_gpu or
+ * rr_update_vertices, kept on the device (12 B per vertex + 12 B per face: about 180 MB at 10M triangles; an
+ * rr_update_vertices keeps a second vertex copy while it validates; the first dynamic call on a tree also keeps a copy of
+ * its nodes as built, 128 B per node) -- and ONE RIGID POSE PER OBJECT.  Objects are numbered
+ * as in face_object_id: n_objects = max(face_object_id) + 1, or 1 when the ids are NULL.  After rr_set_mesh* every pose is
+ * the identity.
+ * The traced scene is always face f's three rest corners moved by pose[object(f)].  A pose is float[7] = qx qy qz qw
+ * tx ty tz (the sensor pose's layout); moving a point is p' = q_rot(q, p) + t in f32 with rr_device.h's q_rot term order,
+ * not fused; the quaternion is used as given (not normalised); a pose equal to (0,0,0,1,0,0,0) is applied as a plain copy.
+ * Contract: after any of the calls below every image, hit and count equals what a fresh rr_set_mesh of the POSED TRIANGLE
+ * SOUP renders (the moved corners, same face order, same object ids), up to the grazing residual class DESIGN.md §2.2 states
+ * for spatially split trees -- a refit tree holds whole-triangle boxes, so it is closer to brute force than a fresh split
+ * tree is.  The tree keeps its topology; its boxes are recomputed level by level (rr_refit.hip), so traversal slows as
+ * objects travel far from where the tree was built: rr_get_tree_cost says when rr_rebuild_tree pays.  Objects still at
+ * their as-built pose keep the builder's clipped leaf boxes; after rr_update_vertices every leaf bounds whole triangles
+ * until the next rebuild (slow on maps whose large faces the host builder split: DESIGN.md §11).
+ * Each call drains the work in flight on the context first (as rr_set_mesh does) and returns when the tree is updated:
+ * batches submitted earlier render the old scene, later ones the new.  A refused call (< 0, rr_last_error: wrong count,
+ * non-finite value -- a pose, or a posed corner -- or no mesh) leaves the scene untouched.  A refit whose posed extent is
+ * unchanged keeps the captured launch graphs (the grazing guard's hit_pad is the only value they bake in that a refit can
+ * change); the traversal stack bound depends on the topology only. */
+int rr_set_object_poses(rr_ctx* ctx, const float* poses /*[n][7]*/, size_t n);        /* n == n_objects */
+int rr_update_vertices(rr_ctx* ctx, const float* verts /*[nv][3]*/, size_t nv);       /* nv == rest nv: new rest geometry, poses kept */
+/* SAH-style cost of the current boxes (sum over child records of half-area / the root's half-area, weighted 1 per inner
+ * child and `count` per leaf child) and of the tree as built (measured at the first dynamic call on the tree) */
+int rr_get_tree_cost(rr_ctx* ctx, double* cost_now, double* cost_at_build);
+/* a fresh tree of the posed scene with builder 0 (host SAH, as rr_set_mesh) or 1 (GPU LBVH, as rr_set_mesh_gpu); the rest
+ * geometry and the poses stay */
+int rr_rebuild_tree(rr_ctx* ctx, int builder);
 
 /* Radar::loadParams (Radar.cpp:220-226): materials, object_materials,
  * material_id_air. */
@@ -417,6 +449,10 @@ int rr_multi_plan(int n_angles, int n_cells, int n_devices, int n_frames, int* e
 /* rr_multi_set_mesh / _gpu: the tree is built ONCE (on the host / on device 0) and copied to the other devices (rr_copy_mesh) */
 int rr_multi_set_mesh(rr_multi* m, const float* verts, size_t nv, const uint32_t* faces, size_t nf, const uint32_t* face_object_id);
 int rr_multi_set_mesh_gpu(rr_multi* m, const float* verts, size_t nv, const uint32_t* faces, size_t nf, const uint32_t* face_object_id);
+/* dynamic scenes: the same contracts on every device; a rebuild runs on device 0 and the tree is copied (rr_copy_mesh) */
+int rr_multi_set_object_poses(rr_multi* m, const float* poses, size_t n);
+int rr_multi_update_vertices(rr_multi* m, const float* verts, size_t nv);
+int rr_multi_rebuild_tree(rr_multi* m, int builder);
 int rr_multi_set_materials(rr_multi* m, const rr_material* materials, size_t n_materials,
                            const int32_t* object_materials, size_t n_objects, int32_t material_id_air);
 int rr_multi_set_config(rr_multi* m, const rr_config* cfg);

@@ -33,6 +33,17 @@ bool build_bvh4_gpu(const float* verts, size_t nv, const uint32_t* faces, size_t
 void launch_debug_trace(const Params& P, const float* origs, const float* dirs, int n,
                         float* out_t, uint32_t* out_face, hipStream_t s, unsigned long long* steps = nullptr);
 void launch_encode_refs(Node4* nodes, size_t n_nodes, uint32_t tri_base4, hipStream_t s, size_t n_tris);
+// rr_refit.hip (dynamic scenes)
+int refit_reduce_groups();
+void launch_refit_extent(const TriRec* tris, size_t n, const float* verts, const uint32_t* faces, const float* poses,
+                         float* out8, hipStream_t s);
+void launch_refit_tris(TriRec* tris, size_t n, const float* verts, const uint32_t* faces, const float* poses, hipStream_t s);
+void launch_refit_levels(float4* base4, const uint32_t* level_nodes, const uint32_t* level_off, int n_levels, float inflate,
+                         const float4* built4, const uint8_t* moved, float extra, hipStream_t s);
+void launch_tree_cost(const Node4* nodes, size_t n_nodes, double* out, hipStream_t s);
+void launch_gather_refs(const Node4* nodes, size_t n_nodes, uint32_t* out, hipStream_t s);
+void launch_pose_soup(const TriRec* tris, size_t n, const float* verts, const uint32_t* faces, const float* poses,
+                      float* soup, uint32_t* obj, hipStream_t s);
 void launch_mat_limits(const float4* materials, size_t n, double* limits, hipStream_t s);
 void* trace0_kernel(bool spill, bool stackless);
 void launch_score(const uint8_t* imgs, const uint8_t* ref, size_t npx, int n_images, unsigned long long* sse, hipStream_t s);
@@ -154,6 +165,26 @@ struct rr_ctx {
     uint64_t n_nodes = 0, n_tris = 0;
     uint32_t depth = 0, stack_need = 0;
     float hit_pad = 0.f;           // grazing guard of the triangle test (traverse): 1e-5 x the extent of the faces' vertices = half the builders' box padding
+
+    // dynamic scenes (rr_refit.hip): the rest geometry of the last rr_set_mesh* / rr_update_vertices, one rigid pose per
+    // object; the traced scene is every face's rest corners moved by its object's pose
+    DevBuf<float> d_rest_v, d_stage_v;     // [rest_nv][3]; the staging copy holds a new rr_update_vertices until it is validated
+    DevBuf<uint32_t> d_rest_f;             // [rest_nf][3]
+    size_t rest_nv = 0, rest_nf = 0;
+    uint32_t n_objects = 1;
+    std::vector<float> poses;              // [n_objects][7] qx qy qz qw tx ty tz
+    DevBuf<float> d_poses, d_stage_poses;
+    bool dyn_ready = false;                // the per-level node lists below belong to the current tree
+    bool rebuilding = false;               // rr_rebuild_tree: the build it runs keeps the rest data
+    DevBuf<uint32_t> d_levels;             // node indices, root level first
+    std::vector<uint32_t> level_off;       // level d = [level_off[d], level_off[d + 1])
+    bool cost_known = false; double cost_at_build = 0.0;    // SAH cost of the tree as built (first dynamic call on it)
+    // what the builder knew: the nodes as built (copied before the first refit: a leaf of split parts keeps its clipped
+    // box while its objects stay where they were), the poses the tree was built for, whether the rest vertices changed since
+    DevBuf<float4> d_built; bool have_built = false; float built_hit_pad = 0.f;
+    std::vector<float> build_poses; bool verts_dirty = false;
+    DevBuf<uint8_t> d_moved;
+    DevBuf<float> d_red; DevBuf<double> d_cost;              // per-workgroup partials of the two reductions
 
     // params
     rr_config cfg;
@@ -1019,6 +1050,8 @@ void rr_destroy(rr_ctx* c)
     for (hipEvent_t e : c->delivery_events) (void)hipEventDestroy(e);
     for (auto& kv : c->timers) for (auto& p : kv.second.pending) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
+    c->d_rest_v.release(); c->d_stage_v.release(); c->d_rest_f.release(); c->d_poses.release(); c->d_stage_poses.release();
+    c->d_levels.release(); c->d_red.release(); c->d_cost.release(); c->d_built.release(); c->d_moved.release();
     c->d_bvh.release(); c->d_qas.release(); c->d_beams.release(); c->d_materials.release(); c->d_mat_limits.release();
     c->d_objmat.release(); c->d_smear.release(); c->d_noise.release(); c->d_decay.release(); c->d_param_imgs.release(); c->d_sse.release(); c->d_ref_img.release(); c->d_beam_order.release(); c->d_beam_order2.release(); c->d_motion.release();
     for (Lane& L : c->lanes) {
@@ -1060,6 +1093,158 @@ float guard_pad(const float* verts, const uint32_t* faces, size_t nf)
     float ext = 0.f, mag = 0.f;
     for (int k = 0; k < 3; k++) { ext = std::max(ext, hi[k] - lo[k]); mag = std::max(mag, std::max(std::fabs(lo[k]), std::fabs(hi[k]))); }
     return 1e-5f * std::max(ext, mag);
+}
+
+// ---- dynamic scenes -------------------------------------------------------------------------------------------------
+// rr_set_mesh* keeps a device copy of the rest geometry (12 B per vertex + 12 B per face; object ids ride in the triangle
+// records) and resets every object's pose to the identity
+int keep_rest(rr_ctx* c, const float* verts, size_t nv, const uint32_t* faces, size_t nf, const uint32_t* face_object_id)
+{
+    c->dyn_ready = false; c->cost_known = false; c->have_built = false; c->verts_dirty = false;
+    if (c->rebuilding) { c->build_poses = c->poses; return 0; }     // rr_rebuild_tree keeps the rest data it had
+    uint32_t n_obj = 1;
+    if (face_object_id) for (size_t f = 0; f < nf; f++) n_obj = std::max(n_obj, face_object_id[f] + 1u);
+    RR_HIP(c, c->d_rest_v.ensure(3 * nv));
+    RR_HIP(c, c->d_rest_f.ensure(3 * nf));
+    if (nv) RR_HIP(c, hipMemcpy(c->d_rest_v.p, verts, 3 * nv * sizeof(float), hipMemcpyHostToDevice));
+    if (nf) RR_HIP(c, hipMemcpy(c->d_rest_f.p, faces, 3 * nf * sizeof(uint32_t), hipMemcpyHostToDevice));
+    c->rest_nv = nv; c->rest_nf = nf; c->n_objects = n_obj;
+    c->poses.assign(7 * (size_t)n_obj, 0.0f);
+    for (uint32_t o = 0; o < n_obj; o++) c->poses[7 * (size_t)o + 3] = 1.0f;
+    c->build_poses = c->poses;
+    RR_HIP(c, c->d_poses.ensure(c->poses.size()));
+    RR_HIP(c, hipMemcpy(c->d_poses.p, c->poses.data(), c->poses.size() * sizeof(float), hipMemcpyHostToDevice));
+    c->d_stage_v.release(); c->d_stage_poses.release();
+    return 0;
+}
+
+TriRec* dev_tris(rr_ctx* c) { return reinterpret_cast<TriRec*>(c->d_bvh.p + c->tri_base4); }
+
+// SAH-style cost of the current boxes: sum over child records of half-area / the root's half-area, weighted 1 per inner
+// child and `count` per leaf child (the per-workgroup partials are summed here in a fixed order: the same boxes give the
+// same value)
+int tree_cost(rr_ctx* c, double* cost)
+{
+    const int G = refit_reduce_groups();
+    RR_HIP(c, c->d_cost.ensure((size_t)G));
+    launch_tree_cost(reinterpret_cast<const Node4*>(c->d_bvh.p), c->n_nodes, c->d_cost.p, c->stream);
+    RR_HIP(c, hipGetLastError());
+    RR_HIP(c, hipStreamSynchronize(c->stream));
+    std::vector<double> part((size_t)G);
+    RR_HIP(c, hipMemcpy(part.data(), c->d_cost.p, part.size() * sizeof(double), hipMemcpyDeviceToHost));
+    Node4 root;
+    RR_HIP(c, hipMemcpy(&root, c->d_bvh.p, sizeof(Node4), hipMemcpyDeviceToHost));
+    double sum = 0.0;
+    for (double x : part) sum += x;
+    double lo[3] = { 1e300, 1e300, 1e300 }, hi[3] = { -1e300, -1e300, -1e300 };
+    for (int q = 0; q < 4; q++) {
+        if (root.c[q].ref == kEmptyRef) continue;
+        for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], (double)root.c[q].lo[k]); hi[k] = std::max(hi[k], (double)root.c[q].hi[k]); }
+    }
+    const double dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
+    const double ha = (dx > 0.0 || dy > 0.0 || dz > 0.0) ? dx * dy + dy * dz + dz * dx : 0.0;
+    *cost = ha > 0.0 ? sum / ha : 0.0;
+    return 0;
+}
+
+// once per tree, at its first dynamic call: the per-level node lists (frontier expansion from the root over the child
+// references) and the cost of the boxes as built
+int refit_prepare(rr_ctx* c)
+{
+    if (c->dyn_ready) return 0;
+    const size_t nn = c->n_nodes;
+    std::vector<uint32_t> refs(4 * nn);
+    if (nn) {
+        DevBuf<uint32_t> d_refs;
+        hipError_t e = d_refs.ensure(4 * nn);
+        if (e == hipSuccess) { launch_gather_refs(reinterpret_cast<const Node4*>(c->d_bvh.p), nn, d_refs.p, c->stream); e = hipGetLastError(); }
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = hipMemcpy(refs.data(), d_refs.p, refs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
+        d_refs.release();
+        RR_HIP(c, e);
+    }
+    std::vector<uint32_t> order;
+    order.reserve(nn);
+    c->level_off.assign(1, 0u);
+    if (nn) order.push_back(0u);
+    for (size_t b = 0; b < order.size();) {
+        const size_t e = order.size();
+        for (size_t i = b; i < e; i++)
+            for (int q = 0; q < 4; q++) {
+                const uint32_t r = refs[4 * (size_t)order[i] + q];
+                if (r == kEmptyRef || (r & kLeafFlag)) continue;
+                if ((r >> 3) >= nn || order.size() >= nn) return fail(c, -4, "dynamic scene: the tree's references are inconsistent");
+                order.push_back(r >> 3);
+            }
+        c->level_off.push_back((uint32_t)e);
+        b = e;
+    }
+    RR_HIP(c, c->d_levels.ensure(order.size()));
+    if (!order.empty()) RR_HIP(c, hipMemcpy(c->d_levels.p, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (!c->have_built) {
+        RR_HIP(c, c->d_built.ensure(8 * nn));
+        if (nn) RR_HIP(c, hipMemcpy(c->d_built.p, c->d_bvh.p, nn * sizeof(Node4), hipMemcpyDeviceToDevice));
+        c->have_built = true; c->built_hit_pad = c->hit_pad;
+    }
+    if (!c->cost_known) {
+        int rc = nn ? tree_cost(c, &c->cost_at_build) : 0; if (rc) return rc;
+        c->cost_known = true;
+    }
+    c->dyn_ready = true;
+    return 0;
+}
+
+// the extent reduction over the posed corners of (verts, poses), read back once: validates the call (every posed corner
+// finite) and forms hit_pad with guard_pad's arithmetic and the box padding with the builders' rule
+int refit_measure(rr_ctx* c, const float* d_verts, const float* d_poses, float* hit_pad, float* inflate, const char* who)
+{
+    *hit_pad = 0.f; *inflate = 1e-6f;
+    if (c->n_tris == 0) return 0;
+    const int G = refit_reduce_groups();
+    RR_HIP(c, c->d_red.ensure((size_t)G * 8));
+    launch_refit_extent(dev_tris(c), c->n_tris, d_verts, c->d_rest_f.p, d_poses, c->d_red.p, c->stream);
+    RR_HIP(c, hipGetLastError());
+    RR_HIP(c, hipStreamSynchronize(c->stream));
+    std::vector<float> part((size_t)G * 8);
+    RR_HIP(c, hipMemcpy(part.data(), c->d_red.p, part.size() * sizeof(float), hipMemcpyDeviceToHost));
+    float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
+    bool bad = false;
+    for (int g = 0; g < G; g++) {
+        const float* p = &part[(size_t)g * 8];
+        for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], p[k]); hi[k] = std::max(hi[k], p[3 + k]); }
+        bad |= p[6] != 0.0f;
+    }
+    if (bad) return fail(c, -3, std::string(who) + ": a posed vertex is not finite (nothing was changed)");
+    float ext = 0.f, mag = 0.f;
+    for (int k = 0; k < 3; k++) { ext = std::max(ext, hi[k] - lo[k]); mag = std::max(mag, std::max(std::fabs(lo[k]), std::fabs(hi[k]))); }
+    *hit_pad = 1e-5f * std::max(ext, mag);                  // guard_pad
+    *inflate = 2e-5f * std::max(ext, mag) + 1e-6f;          // build_bvh4 / build_bvh4_gpu
+    return 0;
+}
+
+// the validated state -> the tree: triangle records, then the boxes level by level, deepest first
+int refit_commit(rr_ctx* c, float hit_pad, float inflate)
+{
+    if (c->n_tris) {
+        // which objects sit where the tree was built for them (same pose, same rest vertices)
+        std::vector<uint8_t> moved(c->n_objects, 1);
+        for (uint32_t o = 0; o < c->n_objects && !c->verts_dirty; o++)
+            moved[o] = std::memcmp(&c->poses[7 * (size_t)o], &c->build_poses[7 * (size_t)o], 7 * sizeof(float)) != 0;
+        RR_HIP(c, c->d_moved.ensure(moved.size()));
+        RR_HIP(c, hipMemcpy(c->d_moved.p, moved.data(), moved.size(), hipMemcpyHostToDevice));
+        // a grown extent grows the padding rule: the as-built boxes widen by the difference (2 x that of hit_pad, + 1 %)
+        const float extra = hit_pad > c->built_hit_pad ? 2.0f * (hit_pad - c->built_hit_pad) * 1.01f : 0.0f;
+        launch_refit_tris(dev_tris(c), c->n_tris, c->d_rest_v.p, c->d_rest_f.p, c->d_poses.p, c->stream);
+        launch_refit_levels(c->d_bvh.p, c->d_levels.p, c->level_off.data(), (int)c->level_off.size() - 1, inflate,
+                            c->d_built.p, c->d_moved.p, extra, c->stream);
+        RR_HIP(c, hipGetLastError());
+        RR_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    // hit_pad travels by value in Params: captured launches bake it in.  Nothing else a launch holds changed (the tree
+    // stays where it is, its depth and stack bound depend on its topology only), so a refit at the same extent keeps them
+    if (hit_pad != c->hit_pad) c->graph_gen++;
+    c->hit_pad = hit_pad;
+    return 0;
 }
 
 // the finished host tree -> the ctx's one allocation (nodes, then triangles; references re-encoded as offsets)
@@ -1179,7 +1364,7 @@ int rr_set_mesh(rr_ctx* c, const float* verts, size_t nv, const uint32_t* faces,
     }
     } catch (const std::exception& ex) { c->have_mesh = false; return fail(c, -4, std::string("rr_set_mesh: host BVH build failed: ") + ex.what());
     } catch (...) { c->have_mesh = false; return fail(c, -4, "rr_set_mesh: host BVH build failed"); }
-    return 0;
+    return keep_rest(c, verts, nv, faces, nf, face_object_id);
 }
 
 int rr_set_mesh_gpu(rr_ctx* c, const float* verts, size_t nv, const uint32_t* faces, size_t nf,
@@ -1217,7 +1402,7 @@ int rr_set_mesh_gpu(rr_ctx* c, const float* verts, size_t nv, const uint32_t* fa
     c->hit_pad = guard_pad(verts, faces, nf);
     c->have_mesh = true; c->hist_gen++; c->graph_gen++;
     for (Lane& L : c->lanes) L.buf_seg = 0;
-    return 0;
+    return keep_rest(c, verts, nv, faces, nf, face_object_id);
 }
 
 int rr_copy_mesh(rr_ctx* c, rr_ctx* src)
@@ -1240,8 +1425,121 @@ int rr_copy_mesh(rr_ctx* c, rr_ctx* src)
     RR_HIP(c, hipDeviceSynchronize());
     c->tri_base4 = src->tri_base4; c->n_nodes = src->n_nodes; c->n_tris = src->n_tris;
     c->depth = src->depth; c->stack_need = src->stack_need; c->hit_pad = src->hit_pad;
+    // the rest geometry and the poses too: the copy can be posed on its own
+    RR_HIP(c, c->d_rest_v.ensure(3 * src->rest_nv));
+    RR_HIP(c, c->d_rest_f.ensure(3 * src->rest_nf));
+    RR_HIP(c, c->d_poses.ensure(src->poses.size()));
+    if (src->device == c->device) {
+        RR_HIP(c, hipMemcpy(c->d_rest_v.p, src->d_rest_v.p, 3 * src->rest_nv * sizeof(float), hipMemcpyDeviceToDevice));
+        RR_HIP(c, hipMemcpy(c->d_rest_f.p, src->d_rest_f.p, 3 * src->rest_nf * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+    } else {
+        RR_HIP(c, hipMemcpyPeer(c->d_rest_v.p, c->device, src->d_rest_v.p, src->device, 3 * src->rest_nv * sizeof(float)));
+        RR_HIP(c, hipMemcpyPeer(c->d_rest_f.p, c->device, src->d_rest_f.p, src->device, 3 * src->rest_nf * sizeof(uint32_t)));
+    }
+    RR_HIP(c, hipMemcpy(c->d_poses.p, src->poses.data(), src->poses.size() * sizeof(float), hipMemcpyHostToDevice));
+    c->rest_nv = src->rest_nv; c->rest_nf = src->rest_nf; c->n_objects = src->n_objects; c->poses = src->poses;
+    c->d_stage_v.release(); c->d_stage_poses.release();
+    c->dyn_ready = false; c->cost_known = src->cost_known; c->cost_at_build = src->cost_at_build;
+    c->build_poses = src->build_poses; c->verts_dirty = src->verts_dirty; c->have_built = false;
+    if (src->have_built) {          // the source has refit its tree already: its snapshot is what the builder made
+        RR_HIP(c, c->d_built.ensure(8 * (size_t)src->n_nodes));
+        if (src->device == c->device) RR_HIP(c, hipMemcpy(c->d_built.p, src->d_built.p, src->n_nodes * sizeof(Node4), hipMemcpyDeviceToDevice));
+        else RR_HIP(c, hipMemcpyPeer(c->d_built.p, c->device, src->d_built.p, src->device, src->n_nodes * sizeof(Node4)));
+        c->have_built = true; c->built_hit_pad = src->built_hit_pad;
+    }
     c->have_mesh = true; c->hist_gen++; c->graph_gen++;
     return 0;
+}
+
+// ---- dynamic scenes (rr_refit.hip) ----------------------------------------------------------------------------------
+int rr_set_object_poses(rr_ctx* c, const float* poses, size_t n)
+{
+    if (!c) return -1;
+    if (!c->have_mesh) return fail(c, -2, "rr_set_mesh has not been called");
+    if (!poses) return fail(c, -3, "rr_set_object_poses: null poses");
+    if (n != c->n_objects)
+        return fail(c, -3, "rr_set_object_poses: expected " + std::to_string(c->n_objects) + " poses (one per object), got " + std::to_string(n));
+    for (size_t i = 0; i < 7 * n; i++) if (!std::isfinite(poses[i])) return fail(c, -3, "rr_set_object_poses: non-finite pose value");
+    RR_HIP(c, hipSetDevice(c->device));
+    RR_HIP(c, hipDeviceSynchronize());       // work in flight renders the old scene
+    int rc = refit_prepare(c); if (rc) return rc;
+    RR_HIP(c, c->d_stage_poses.ensure(7 * n));
+    RR_HIP(c, hipMemcpy(c->d_stage_poses.p, poses, 7 * n * sizeof(float), hipMemcpyHostToDevice));
+    float hp = 0.f, inflate = 0.f;
+    rc = refit_measure(c, c->d_rest_v.p, c->d_stage_poses.p, &hp, &inflate, "rr_set_object_poses"); if (rc) return rc;
+    std::swap(c->d_poses, c->d_stage_poses);
+    c->poses.assign(poses, poses + 7 * n);
+    return refit_commit(c, hp, inflate);
+}
+
+int rr_update_vertices(rr_ctx* c, const float* verts, size_t nv)
+{
+    if (!c) return -1;
+    if (!c->have_mesh) return fail(c, -2, "rr_set_mesh has not been called");
+    if (!verts) return fail(c, -3, "rr_update_vertices: null vertices");
+    if (nv != c->rest_nv)
+        return fail(c, -3, "rr_update_vertices: expected " + std::to_string(c->rest_nv) + " vertices (the mesh's), got " + std::to_string(nv));
+    RR_HIP(c, hipSetDevice(c->device));
+    RR_HIP(c, hipDeviceSynchronize());
+    int rc = refit_prepare(c); if (rc) return rc;
+    RR_HIP(c, c->d_stage_v.ensure(3 * nv));
+    if (nv) RR_HIP(c, hipMemcpy(c->d_stage_v.p, verts, 3 * nv * sizeof(float), hipMemcpyHostToDevice));
+    float hp = 0.f, inflate = 0.f;
+    rc = refit_measure(c, c->d_stage_v.p, c->d_poses.p, &hp, &inflate, "rr_update_vertices"); if (rc) return rc;
+    std::swap(c->d_rest_v, c->d_stage_v);
+    c->verts_dirty = true;          // (the same values count as new: the builder's clipped boxes are not checked against them)
+    return refit_commit(c, hp, inflate);
+}
+
+int rr_get_tree_cost(rr_ctx* c, double* cost_now, double* cost_at_build)
+{
+    if (!c) return -1;
+    if (!c->have_mesh) return fail(c, -2, "rr_set_mesh has not been called");
+    RR_HIP(c, hipSetDevice(c->device));
+    int rc = refit_prepare(c); if (rc) return rc;
+    double now = 0.0;
+    if (c->n_nodes) { rc = tree_cost(c, &now); if (rc) return rc; }
+    if (cost_now) *cost_now = now;
+    if (cost_at_build) *cost_at_build = c->cost_at_build;
+    return 0;
+}
+
+int rr_rebuild_tree(rr_ctx* c, int builder)
+{
+    if (!c) return -1;
+    if (builder != 0 && builder != 1) return fail(c, -3, "rr_rebuild_tree: builder must be 0 (host SAH) or 1 (GPU LBVH)");
+    if (!c->have_mesh) return fail(c, -2, "rr_set_mesh has not been called");
+    RR_HIP(c, hipSetDevice(c->device));
+    RR_HIP(c, hipDeviceSynchronize());
+    const size_t nf = c->rest_nf;
+    if (nf == 0 || c->n_tris == 0) return 0;
+    // the posed soup (face order, corners 3f .. 3f + 2) and its object ids, to the host: both builders take host arrays
+    std::vector<float> soup(9 * nf);
+    std::vector<uint32_t> obj(nf), faces(3 * nf);
+    {
+        DevBuf<float> d_soup; DevBuf<uint32_t> d_obj;
+        hipError_t e = d_soup.ensure(9 * nf);
+        if (e == hipSuccess) e = d_obj.ensure(nf);
+        if (e == hipSuccess) {
+            launch_pose_soup(dev_tris(c), c->n_tris, c->d_rest_v.p, c->d_rest_f.p, c->d_poses.p, d_soup.p, d_obj.p, c->stream);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = hipMemcpy(soup.data(), d_soup.p, soup.size() * sizeof(float), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(obj.data(), d_obj.p, obj.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
+        d_soup.release(); d_obj.release();
+        RR_HIP(c, e);
+    }
+    for (size_t i = 0; i < 3 * nf; i++) faces[i] = (uint32_t)i;
+    // the build replaces the tree (and bumps graph_gen: the tree moves); the rest data, the poses and the trace-grid
+    // history stay -- wave counts do not depend on the tree
+    const int hist = c->hist_gen;
+    c->rebuilding = true;
+    const int rc = builder == 0 ? rr_set_mesh(c, soup.data(), 3 * nf, faces.data(), nf, obj.data())
+                                : rr_set_mesh_gpu(c, soup.data(), 3 * nf, faces.data(), nf, obj.data());
+    c->rebuilding = false;
+    c->hist_gen = hist;
+    return rc;
 }
 
 int rr_set_materials(rr_ctx* c, const rr_material* materials, size_t n_materials,

@@ -355,6 +355,31 @@ int rr_multi_set_mesh_gpu(rr_multi* m, const float* verts, size_t nv, const uint
     }
     return 0;
 }
+// dynamic scenes: every device holds the same rest geometry and poses (rr_copy_mesh copies them), so a pose or vertex
+// update is the same refit on each; a rebuild runs once and the finished tree travels as rr_multi_set_mesh's does
+int rr_multi_set_object_poses(rr_multi* m, const float* poses, size_t n)
+{
+    if (!m) return -1;
+    RRM_EACH(m, rr_set_object_poses(c, poses, n));
+    return 0;
+}
+int rr_multi_update_vertices(rr_multi* m, const float* verts, size_t nv)
+{
+    if (!m) return -1;
+    RRM_EACH(m, rr_update_vertices(c, verts, nv));
+    return 0;
+}
+int rr_multi_rebuild_tree(rr_multi* m, int builder)
+{
+    if (!m) return -1;
+    { rr_ctx* c = m->ctx[0]; const int rc = rr_rebuild_tree(c, builder);
+      if (rc) return mfail(m, rc, std::string("device ") + std::to_string(m->devices[0]) + ": " + rr_last_error(c)); }
+    for (size_t i = 1; i < m->ctx.size(); i++) {
+        rr_ctx* c = m->ctx[i]; const int rc = rr_copy_mesh(c, m->ctx[0]);
+        if (rc) return mfail(m, rc, std::string("device ") + std::to_string(m->devices[i]) + ": " + rr_last_error(c));
+    }
+    return 0;
+}
 int rr_multi_set_materials(rr_multi* m, const rr_material* materials, size_t n_materials,
                            const int32_t* object_materials, size_t n_objects, int32_t material_id_air)
 {

@@ -28,6 +28,8 @@ SYMBOLS = [
     "rr_multi_simulate_batch_async", "rr_multi_wait", "rr_peek_error_bits_async", "rr_get_traversal_shape",
     "rr_cone_dirs", "rr_sample_cone_local", "rr_load_mesh_file", "rr_mesh_reorder_objects", "rr_free_mesh",
     "rr_simulate_param_sets_device", "rr_simulate_param_sets", "rr_score_images_device",
+    "rr_set_object_poses", "rr_update_vertices", "rr_get_tree_cost", "rr_rebuild_tree",
+    "rr_multi_set_object_poses", "rr_multi_update_vertices", "rr_multi_rebuild_tree",
 ]
 
 
@@ -185,10 +187,44 @@ def lib():
     L.rr_free_mesh.argtypes = [C.POINTER(RRMesh)]
     L.rr_mesh_reorder_objects.argtypes = [C.POINTER(RRMesh), C.POINTER(C.c_char_p), C.c_size_t, C.c_char_p, C.c_size_t]
     L.rr_free_mesh.restype = None
+    L.rr_set_object_poses.argtypes = [vp, vp, C.c_size_t]
+    L.rr_update_vertices.argtypes = [vp, vp, C.c_size_t]
+    L.rr_get_tree_cost.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.rr_rebuild_tree.argtypes = [vp, C.c_int]
+    L.rr_multi_set_object_poses.argtypes = [vp, vp, C.c_size_t]
+    L.rr_multi_update_vertices.argtypes = [vp, vp, C.c_size_t]
+    L.rr_multi_rebuild_tree.argtypes = [vp, C.c_int]
     for n in SYMBOLS:
         getattr(L, n)
     _LIB = L
     return L
+
+
+def _rows(a, width, what):
+    """a numeric array of shape [n][width] (or flat, n * width values) -> contiguous float32 [n][width]; ValueError otherwise"""
+    x = np.asarray(a)
+    if x.dtype.kind not in "fiu":
+        raise ValueError("%s must be real numbers, got dtype %s" % (what, x.dtype))
+    if not ((x.ndim == 2 and x.shape[1] == width) or (x.ndim == 1 and x.size % width == 0)):
+        raise ValueError("%s must have shape [n][%d], got %s" % (what, width, x.shape))
+    return np.ascontiguousarray(x, np.float32).reshape(-1, width)
+
+
+def object_poses_array(poses):
+    """[n_objects][7] (qx qy qz qw tx ty tz) -> float32, shape-checked before any call into the library"""
+    return _rows(poses, 7, "object poses")
+
+
+def vertex_array(verts):
+    """[nv][3] -> float32, shape-checked before any call into the library"""
+    return _rows(verts, 3, "vertices")
+
+
+def builder_id(builder):
+    b = {"host": 0, "gpu": 1, 0: 0, 1: 1}.get(builder) if isinstance(builder, (str, int)) else None
+    if b is None:
+        raise ValueError("builder must be 'host' or 'gpu', got %r" % (builder,))
+    return b
 
 
 def make_config(cfg, n_angles=400, max_waves_per_azimuth=0, wave_energy_threshold=0.001,
@@ -265,6 +301,28 @@ class Context:
     def copy_mesh(self, src):
         """take the finished tree of another context (same or another device): rr_copy_mesh"""
         self._ck(self._L.rr_copy_mesh(self._h, src._h))
+
+    # ---- dynamic scenes (include/radarays_mi355.h): the traced scene is every face's rest corners moved by its object's pose
+    def set_object_poses(self, poses):
+        """one rigid pose per object, [n_objects][7] = qx qy qz qw tx ty tz; the tree is refit in place (rr_set_object_poses)"""
+        p = object_poses_array(poses)
+        self._ck(self._L.rr_set_object_poses(self._h, p.ctypes.data, len(p)))
+
+    def update_vertices(self, verts):
+        """new rest vertices (same count as the mesh's), poses kept (rr_update_vertices)"""
+        v = vertex_array(verts)
+        self._ck(self._L.rr_update_vertices(self._h, v.ctypes.data, len(v)))
+
+    def tree_cost(self):
+        """(cost of the current boxes, cost of the tree as built): rr_get_tree_cost; their ratio says when a rebuild pays"""
+        a, b = C.c_double(), C.c_double()
+        self._ck(self._L.rr_get_tree_cost(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def rebuild_tree(self, builder="host"):
+        """a fresh tree of the posed scene ("host" SAH or "gpu" LBVH); rest geometry and poses stay (rr_rebuild_tree)"""
+        b = builder_id(builder)
+        self._ck(self._L.rr_rebuild_tree(self._h, b))
 
     def set_materials(self, materials, object_materials, material_id_air=0):
         m = (RRMaterial * len(materials))(*[RRMaterial(*[float(x) for x in (t.astuple() if hasattr(t, "astuple") else t)])
@@ -652,6 +710,27 @@ class MultiContext:
         o = None if face_object_id is None else np.ascontiguousarray(face_object_id, np.uint32)
         fn = {"host": self._L.rr_multi_set_mesh, "gpu": self._L.rr_multi_set_mesh_gpu}[builder]
         self._ck(fn(self._h, v.ctypes.data, len(v), f.ctypes.data, len(f), None if o is None else o.ctypes.data))
+
+    def set_object_poses(self, poses):
+        p = object_poses_array(poses)
+        self._ck(self._L.rr_multi_set_object_poses(self._h, p.ctypes.data, len(p)))
+
+    def update_vertices(self, verts):
+        v = vertex_array(verts)
+        self._ck(self._L.rr_multi_update_vertices(self._h, v.ctypes.data, len(v)))
+
+    def rebuild_tree(self, builder="host"):
+        b = builder_id(builder)
+        self._ck(self._L.rr_multi_rebuild_tree(self._h, b))
+
+    def tree_cost(self):
+        """device 0's (cost now, cost as built): every device holds the same tree"""
+        a, b = C.c_double(), C.c_double()
+        h = self._L.rr_multi_ctx(self._h, 0)
+        rc = self._L.rr_get_tree_cost(h, C.byref(a), C.byref(b))
+        if rc != 0:
+            raise RRError("%s (rc=%d)" % (self._L.rr_last_error(h).decode(), rc))
+        return a.value, b.value
 
     def set_materials(self, materials, object_materials, material_id_air=0):
         m = (RRMaterial * len(materials))(*[RRMaterial(*[float(x) for x in (t.astuple() if hasattr(t, "astuple") else t)])

@@ -113,6 +113,23 @@ class RadarHIP:
     def setNoiseOffsets(self, rnd):
         self._ctx.set_noise_offsets(rnd)
 
+    # ---- dynamic scenes: one rigid pose per object of face_object_id, the tree refit in place (include/radarays_mi355.h)
+    def setObjectPoses(self, poses):
+        """[n_objects][7] = qx qy qz qw tx ty tz: frames simulated after this call see every object moved by its pose."""
+        self._ctx.set_object_poses(poses)
+
+    def updateVertices(self, verts):
+        """new rest vertices (same count and faces as the loaded mesh); the object poses stay."""
+        self._ctx.update_vertices(verts)
+
+    def rebuildTree(self, builder="host"):
+        """a fresh tree of the posed scene ("host" or "gpu" builder): worth it when treeCost() has grown."""
+        self._ctx.rebuild_tree(builder)
+
+    def treeCost(self):
+        """(cost of the current boxes, cost of the tree as built)."""
+        return self._ctx.tree_cost()
+
     def _push(self):
         if self._dirty_cfg:
             cfg = self.m_cfg.copy(n_reflections=self.m_params.model.n_reflections)

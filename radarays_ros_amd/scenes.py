@@ -126,6 +126,48 @@ def heightfield_room(n_quads, extent=420.0, z_lo=-6.0, z_hi=24.0, n_buildings=0,
             "name": "heightfield%d_b%d" % (n_quads, n_buildings)}
 
 
+def add_vehicles(scene, n, seed=17, size=(4.5, 1.8, 1.6), material=None, center=(1.0, 1.5), ring=(12.0, 60.0)):
+    """A copy of `scene` with n vehicle-sized boxes (12 triangles each) appended, each its own object (ids max + 1 ...),
+    for dynamic scenes (rr_set_object_poses).  Rest positions: uniform on the annulus `ring` around `center`, random
+    heading, standing on the terrain (heightfield scenes) or on the scene's lowest z.  `object_materials`, where the scene
+    has one, gets `material` (default: its last entry) for every vehicle.  The original vertices, faces and ids stay a
+    prefix.  Adds "vehicle_objects" (object ids) and "vehicle_centers" ([n][3], the rest centre of each box's footprint)."""
+    rs = np.random.RandomState(seed)
+    verts, faces, obj = scene["verts"], scene["faces"], scene["face_object_id"]
+    first = int(obj.max()) + 1 if len(obj) else 0
+    z_floor = float(verts[:, 2].min()) if len(verts) else 0.0
+    terrain = scene.get("name", "").startswith("heightfield")
+    hx, hy, hz = (0.5 * float(size[0]), 0.5 * float(size[1]), float(size[2]))
+    local = np.array([[-hx, -hy, 0], [hx, -hy, 0], [hx, hy, 0], [-hx, hy, 0],
+                      [-hx, -hy, hz], [hx, -hy, hz], [hx, hy, hz], [-hx, hy, hz]], np.float64)
+    _, box_f = _box_tris([0, 0, 0], [1, 1, 1])
+    nv = len(verts)
+    bv, bf, cen = [], [], []
+    for k in range(n):
+        r = rs.uniform(ring[0], ring[1])
+        a = rs.uniform(0.0, 2.0 * np.pi)
+        yaw = rs.uniform(0.0, 2.0 * np.pi)
+        cx, cy = center[0] + r * np.cos(a), center[1] + r * np.sin(a)
+        cz = float(ground_height(cx, cy)) if terrain else z_floor
+        c, s_ = np.cos(yaw), np.sin(yaw)
+        w = np.stack([cx + c * local[:, 0] - s_ * local[:, 1], cy + s_ * local[:, 0] + c * local[:, 1], cz + local[:, 2]], -1)
+        bv.append(w.astype(np.float32))
+        bf.append(box_f + np.uint32(nv + 8 * k))
+        cen.append((cx, cy, cz))
+    out = dict(scene)
+    out["verts"] = np.concatenate([verts] + bv, 0).astype(np.float32) if n else verts.copy()
+    out["faces"] = np.concatenate([faces] + bf, 0).astype(np.uint32) if n else faces.copy()
+    out["face_object_id"] = np.concatenate([obj, np.repeat(np.arange(first, first + n, dtype=np.uint32), 12)])
+    if "object_materials" in scene:
+        m = scene["object_materials"][-1] if material is None else material
+        om = list(scene["object_materials"]) + [1] * max(0, first - len(scene["object_materials"]))
+        out["object_materials"] = om + [m] * n
+    out["vehicle_objects"] = list(range(first, first + n))
+    out["vehicle_centers"] = np.array(cen, np.float32).reshape(-1, 3)
+    out["name"] = scene.get("name", "") + "_veh%d" % n
+    return out
+
+
 # The 18 objects config/oru4_test.yaml:37-56 lists for the ORU4 scene (the .dae itself is author-local,
 # launch/mro_husky.launch:4): their names, in the order the reference's object_materials table indexes them
 ORU4_OBJECT_NAMES = ["HallwayGround", "DoorHallway1Glass", "HallwayWall", "DoorT1203Wood", "DoorT1203Glass", "DoorT1210Glass",
