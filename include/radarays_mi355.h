@@ -416,6 +416,80 @@ int rr_get_kernel_samples(rr_ctx* ctx, const char* kernel, float* out_ms, size_t
 /* pre-creates n timing events so that a timed region never calls hipEventCreate */
 int rr_reserve_timing_events(rr_ctx* ctx, size_t n);
 
+/* ---- radar point clouds and Cartesian images from polar images (rr_detect.hip) ----------------------------------
+ * The reference's pipeline turns every simulated image into a point cloud with radar_tools/radar_img_to_pcl
+ * (launch/tests/radar_sim_test.launch:80-84), a node outside the checkout: its algorithm is unknown, so parity with it is
+ * UNPINNED and the two detectors below are this build's own, stated exactly (a numpy restatement in tests/detect_ref.py
+ * checks them bit for bit).  Any context with a config converts images (a mesh is not needed: real MulRan / Navtech polar
+ * images go through the same calls).  The images are [n_frames][n_cells][n_angles] u8 in the context's current shape;
+ * geometry and config are read BY VALUE when the call is made (a later rr_set_config does not touch an enqueued call).
+ *   image column col holds azimuth a = (col - scroll_image) mod n_angles   (the inverse of the assemble, RadarCPU.cpp:457)
+ *   bin b lies at range r = (float)(((double)b + 0.5) * resolution)       (the bin centre of RadarCPU.cpp:521)
+ *   azimuth a points along yaw theta = theta_min + (float)a * theta_inc  (RadarCPU.cpp:202), so a point is
+ *   (x, y, z) = r * (cosf(theta), sinf(theta), 0) in the sensor frame of its own azimuth (no de-skew).
+ * A refused call (-3: a config field outside its range, n_frames outside 1..65535, a null buffer, max_points < 0) writes
+ * nothing; -2 without a config.  The device forms run on `stream` (NULL: the ctx's stream), write nothing but the caller's
+ * buffers and use no context-owned memory, so they may run on any stream beside batches in flight.  The host forms stage
+ * the images into context-owned buffers and are synchronous. */
+typedef struct rr_detect_config {
+    int32_t method;         /* 0 = CA-CFAR along range, 1 = k-strongest per azimuth */
+    int32_t guard_cells;    /* CA-CFAR: G cells skipped on each side of the cell under test, 0..1024 */
+    int32_t train_cells;    /* CA-CFAR: T training cells on each side, 1..1024 */
+    int32_t k;              /* k-strongest: detections per azimuth, 1..n_cells */
+    int32_t min_intensity;  /* 0..255: a cell below it is never a detection (both methods) */
+    int32_t min_bin;        /* 0..n_cells-1: bins below it are never detections (near-field / leakage) */
+    float   cfar_scale;     /* CA-CFAR threshold factor, finite, >= 0 */
+    int32_t reserved_;
+} rr_detect_config;
+
+typedef struct rr_radar_point {  /* 24 B; x,y,z + intensity = geometry_msgs/Point32 + one ChannelFloat32 */
+    float    x, y, z;       /* metres, sensor frame of that azimuth */
+    float    intensity;     /* the cell's u8 value */
+    uint32_t column;        /* image column */
+    uint32_t bin;           /* range bin (image row) */
+} rr_radar_point;
+
+typedef struct rr_cartesian_config {
+    int32_t width;          /* output is width x width pixels, 1..8192 */
+    int32_t interpolation;  /* 0 = nearest, 1 = bilinear */
+    float   pixel_size;     /* metres per pixel, finite, > 0 */
+    int32_t reserved_;
+} rr_cartesian_config;
+
+/* method 0 (CA-CFAR), guard_cells 2, train_cells 16, k 12, min_intensity 1 (an empty cell is never a detection), min_bin 0,
+ * cfar_scale 3.0 */
+void rr_default_detect_config(rr_detect_config* cfg);
+
+/* Detection, per column z[0..N) of every frame (N = n_cells):
+ * CA-CFAR (method 0): every bin i >= min_bin is tested; its training cells are [i-G-T, i-G-1] and [i+G+1, i+G+T] clipped to
+ *   [0, N) (cells below min_bin train too), n = their count, S = their uint32 sum; i is a detection iff z[i] >= min_intensity,
+ *   n > 0 and (float)(z[i] * n) > cfar_scale * (float)S  (exact integers in f32 and one rounded f32 multiply).
+ * k-strongest (method 1): the candidates are the bins i >= min_bin with z[i] >= min_intensity; the k largest are kept (value
+ *   descending, then bin ascending); a column with fewer candidates keeps all of them.
+ * Output: within a frame, points sorted by column ascending, then bin ascending, at d_points + f * max_points.
+ *   d_offsets[f][c] = the number of detections in columns 0..c-1 (exclusive prefix), so d_offsets[f][n_angles] is the frame's
+ *   TRUE total, also when it exceeds max_points: then the first max_points points in that order are written and nothing
+ *   beyond them.  max_points == 0 (d_points may be NULL) counts only. */
+int rr_detect_device(rr_ctx* ctx, const uint8_t* d_imgs_u8 /*[n][n_cells][n_angles]*/, int n_frames,
+                     const rr_detect_config* cfg, rr_radar_point* d_points /*[n][max_points] or NULL if max_points==0*/,
+                     int max_points, uint32_t* d_offsets /*[n][n_angles+1]*/, void* stream);
+int rr_detect(rr_ctx* ctx, const uint8_t* imgs_u8, int n_frames, const rr_detect_config* cfg,
+              rr_radar_point* points, int max_points, uint32_t* offsets);        /* host buffers, synchronous */
+/* Cartesian bird's-eye image, all in f32 with no fused operations.  c = (width - 1) * 0.5f; pixel (row i, col j) sits at
+ * x = (c - i) * pixel_size (forward = up), y = (c - j) * pixel_size (left = left); rho = sqrtf(x*x + y*y), phi = atan2f(y, x).
+ *   u = (phi - theta_min) / theta_inc, then u = fmodf(u, n_angles), + n_angles if negative, - n_angles if that gave n_angles
+ *   v = rho / (float)resolution - 0.5f; a pixel with v > n_cells - 0.5 is 0; otherwise v = max(v, 0) (the half bin in front
+ *       of the first bin centre reads bin 0)
+ *   nearest:  a = rintf(u) (n_angles wraps to 0), b = min(rintf(v), n_cells - 1); the value is z(b, a)
+ *   bilinear: a0 = floorf(u), fu = u - a0, a1 = a0 + 1 wrapped; b0 = floorf(v), fv = v - b0, b1 = min(b0 + 1, n_cells - 1);
+ *             p0 = (1 - fu) * z(b0, a0) + fu * z(b0, a1), p1 likewise on b1, value = rintf((1 - fv) * p0 + fv * p1)
+ * where z(b, a) reads azimuth a through the column mapping above; the value is saturated to u8.  theta_inc must be nonzero.
+ * d_cart_u8 = [n][width][width]. */
+int rr_polar_to_cartesian_device(rr_ctx* ctx, const uint8_t* d_imgs_u8, int n_frames, const rr_cartesian_config* cfg,
+                                 uint8_t* d_cart_u8 /*[n][width][width]*/, void* stream);
+int rr_polar_to_cartesian(rr_ctx* ctx, const uint8_t* imgs_u8, int n_frames, const rr_cartesian_config* cfg,
+                          uint8_t* cart_u8);                                         /* host buffers, synchronous */
+
 /* ---- several GPUs of one node behind one object (SURVEY.md §8b "Threading", §8e) -------------------------
  * The reference creates ONE backend object per process (src/radar_simulator.cpp:145-176) and fans out inside it
  * (OpenMP over azimuths, RadarCPU.cpp:155).  rr_multi is that object for n GPUs: one rr_ctx per device, mesh and

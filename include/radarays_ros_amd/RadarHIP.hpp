@@ -235,6 +235,39 @@ public:
         return true;
     }
     const std::string& lastError() const { return m_err; }
+    // radar_tools/radar_img_to_pcl (launch/tests/radar_sim_test.launch:80-84, outside the checkout) on the GPU: one mono8
+    // polar image of this model's shape (simulated or real) -> its detections, a PointCloud's points plus the intensity
+    // channel (and the column / bin each came from), sorted by column, then bin.  The detector is this build's own
+    // (rr_detect_config, include/radarays_mi355.h).  Empty on error (lastError()).
+    std::vector<rr_radar_point> detect(const ImagePtr& image, const rr_detect_config& cfg)
+    {
+        std::vector<rr_radar_point> pts;
+        if (!image || !push()) return pts;
+        if (image->height != (uint32_t)m_cfg.n_cells || image->width != (uint32_t)m_n_angles || image->data.size() != (size_t)image->height * image->width) {
+            m_err = "detect: the image is not n_cells x n_angles mono8"; std::cout << "[RadarHIP] " << m_err << std::endl; return pts;
+        }
+        std::vector<uint32_t> offs((size_t)m_n_angles + 1);
+        if (rr_detect(m_ctx, image->data.data(), 1, &cfg, nullptr, 0, offs.data())) { fail(); return pts; }      // count
+        pts.resize(offs.back());
+        if (!pts.empty() && rr_detect(m_ctx, image->data.data(), 1, &cfg, pts.data(), (int)pts.size(), offs.data())) { fail(); pts.clear(); }
+        return pts;
+    }
+    // the Cartesian bird's-eye image of one polar image: width x width mono8, forward = up, left = left, pixel_size m per pixel
+    ImagePtr toCartesian(const ImagePtr& image, int width, float pixel_size, bool bilinear = true)
+    {
+        if (!image || !push()) return {};
+        if (image->height != (uint32_t)m_cfg.n_cells || image->width != (uint32_t)m_n_angles || image->data.size() != (size_t)image->height * image->width) {
+            m_err = "toCartesian: the image is not n_cells x n_angles mono8"; std::cout << "[RadarHIP] " << m_err << std::endl; return {};
+        }
+        rr_cartesian_config c{};
+        c.width = width; c.interpolation = bilinear ? 1 : 0; c.pixel_size = pixel_size;
+        ImagePtr msg = std::make_shared<Image>();
+        msg->stamp = image->stamp; msg->frame_id = image->frame_id;
+        msg->height = msg->width = msg->step = width > 0 ? (uint32_t)width : 0u;
+        msg->data.resize((size_t)msg->height * msg->width);
+        if (rr_polar_to_cartesian(m_ctx, image->data.data(), 1, &c, msg->data.data())) return fail();
+        return msg;
+    }
     const rr_stats& lastStats() const { return m_stats; }
 
 private:

@@ -47,6 +47,12 @@ void launch_pose_soup(const TriRec* tris, size_t n, const float* verts, const ui
 void launch_mat_limits(const float4* materials, size_t n, double* limits, hipStream_t s);
 void* trace0_kernel(bool spill, bool stackless);
 void launch_score(const uint8_t* imgs, const uint8_t* ref, size_t npx, int n_images, unsigned long long* sse, hipStream_t s);
+// rr_detect.hip (point clouds and Cartesian images)
+void launch_detect(const uint8_t* imgs, int n_frames, const rr_detect_config& cfg, int n_cells, int n_angles, int scroll,
+                   float theta_min, float theta_inc, double resolution, rr_radar_point* points, int max_points,
+                   uint32_t* offsets, hipStream_t s);
+void launch_cartesian(const uint8_t* imgs, int n_frames, const rr_cartesian_config& cfg, int n_cells, int n_angles, int scroll,
+                      float theta_min, float theta_inc, float res, uint8_t* out, hipStream_t s);
 void launch_copy_host(const void* src, void* dst, size_t bytes, int blocks, int xcd, hipStream_t s);
 void launch_copy_words(const void* src, void* dst, size_t bytes, hipStream_t s);
 void launch_debug_brdf(size_t n, const float* in, int model, float* out, hipStream_t s);
@@ -236,6 +242,8 @@ struct rr_ctx {
 
     int passes_override = -1;    // a parameter batch in the making: the largest n_reflections of its sets sizes queues and launch loops
     DevBuf<unsigned long long> d_sse; DevBuf<uint8_t> d_ref_img;     // rr_score_images / rr_simulate_param_sets
+    // staging of the host forms of rr_detect / rr_polar_to_cartesian (the device forms use none of it)
+    DevBuf<uint8_t> d_conv_in, d_conv_cart; DevBuf<rr_radar_point> d_conv_points; DevBuf<uint32_t> d_conv_offs;
     void* h_rb = nullptr; size_t h_rb_bytes = 0;         // page-locked: read_back()
     void* h_frame = nullptr; size_t h_frame_bytes = 0;   // page-locked: error bits + per-pass counters of rr_simulate's frame
 
@@ -1053,7 +1061,7 @@ void rr_destroy(rr_ctx* c)
     c->d_rest_v.release(); c->d_stage_v.release(); c->d_rest_f.release(); c->d_poses.release(); c->d_stage_poses.release();
     c->d_levels.release(); c->d_red.release(); c->d_cost.release(); c->d_built.release(); c->d_moved.release();
     c->d_bvh.release(); c->d_qas.release(); c->d_beams.release(); c->d_materials.release(); c->d_mat_limits.release();
-    c->d_objmat.release(); c->d_smear.release(); c->d_noise.release(); c->d_decay.release(); c->d_param_imgs.release(); c->d_sse.release(); c->d_ref_img.release(); c->d_beam_order.release(); c->d_beam_order2.release(); c->d_motion.release();
+    c->d_objmat.release(); c->d_smear.release(); c->d_noise.release(); c->d_decay.release(); c->d_param_imgs.release(); c->d_sse.release(); c->d_ref_img.release(); c->d_conv_in.release(); c->d_conv_cart.release(); c->d_conv_points.release(); c->d_conv_offs.release(); c->d_beam_order.release(); c->d_beam_order2.release(); c->d_motion.release();
     for (Lane& L : c->lanes) {
         if (L.stream) (void)hipStreamSynchronize(L.stream);
         for (int k = 0; k < 2; k++) { L.d_wA[k].release(); L.d_wB[k].release(); L.d_wC[k].release(); L.d_idx[k].release(); L.d_count[k].release(); L.d_torder[k].release(); }
@@ -2052,6 +2060,124 @@ int rr_score_images_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_images, co
             out_psnr[k] = err > 0.0 ? 10.0 * std::log10((255.0 * 255.0) / err) : INFINITY;
         }
     }
+    return 0;
+}
+
+// ---- point clouds and Cartesian images (rr_detect.hip) ---------------------------------------------------------------
+void rr_default_detect_config(rr_detect_config* cfg)
+{
+    if (!cfg) return;
+    std::memset(cfg, 0, sizeof(*cfg));
+    cfg->method = 0; cfg->guard_cells = 2; cfg->train_cells = 16; cfg->k = 12;
+    cfg->min_intensity = 1; cfg->min_bin = 0; cfg->cfar_scale = 3.0f;
+}
+
+namespace {
+
+int check_frames(rr_ctx* c, const char* who, const void* imgs, int n_frames)
+{
+    if (!c) return -1;
+    if (!c->have_cfg) return fail(c, -2, "rr_set_config has not been called");
+    if (!imgs) return fail(c, -3, std::string(who) + ": null images");
+    if (n_frames < 1 || n_frames > 65535) return fail(c, -3, std::string(who) + ": n_frames must be 1..65535");
+    return 0;
+}
+
+int check_detect(rr_ctx* c, const char* who, const void* imgs, int n_frames, const rr_detect_config* d, const void* points,
+                 int max_points, const void* offsets)
+{
+    int rc = check_frames(c, who, imgs, n_frames); if (rc) return rc;
+    const std::string w(who);
+    if (!d) return fail(c, -3, w + ": null config");
+    if (!offsets) return fail(c, -3, w + ": null offsets");
+    if (max_points < 0) return fail(c, -3, w + ": max_points must be >= 0");
+    if (max_points > 0 && !points) return fail(c, -3, w + ": null points with max_points > 0");
+    const int n_cells = c->cfg.n_cells;
+    if (d->method != 0 && d->method != 1) return fail(c, -3, w + ": method must be 0 (CA-CFAR) or 1 (k-strongest)");
+    if (d->guard_cells < 0 || d->guard_cells > 1024) return fail(c, -3, w + ": guard_cells must be 0..1024");
+    if (d->train_cells < 1 || d->train_cells > 1024) return fail(c, -3, w + ": train_cells must be 1..1024");
+    if (d->k < 1 || d->k > n_cells) return fail(c, -3, w + ": k must be 1..n_cells (" + std::to_string(n_cells) + ")");
+    if (d->min_intensity < 0 || d->min_intensity > 255) return fail(c, -3, w + ": min_intensity must be 0..255");
+    if (d->min_bin < 0 || d->min_bin >= n_cells) return fail(c, -3, w + ": min_bin must be 0..n_cells-1");
+    if (!(std::isfinite(d->cfar_scale) && d->cfar_scale >= 0.0f)) return fail(c, -3, w + ": cfar_scale must be finite and >= 0");
+    return 0;
+}
+
+int check_cartesian(rr_ctx* c, const char* who, const void* imgs, int n_frames, const rr_cartesian_config* k, const void* out)
+{
+    int rc = check_frames(c, who, imgs, n_frames); if (rc) return rc;
+    const std::string w(who);
+    if (!k) return fail(c, -3, w + ": null config");
+    if (!out) return fail(c, -3, w + ": null output");
+    if (k->width < 1 || k->width > 8192) return fail(c, -3, w + ": width must be 1..8192");
+    if (k->interpolation != 0 && k->interpolation != 1) return fail(c, -3, w + ": interpolation must be 0 (nearest) or 1 (bilinear)");
+    if (!(std::isfinite(k->pixel_size) && k->pixel_size > 0.0f)) return fail(c, -3, w + ": pixel_size must be finite and > 0");
+    if (c->cfg.theta_inc == 0.0f) return fail(c, -3, w + ": the config's theta_inc is 0");
+    return 0;
+}
+
+}  // namespace
+
+int rr_detect_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_frames, const rr_detect_config* cfg, rr_radar_point* d_points,
+                     int max_points, uint32_t* d_offsets, void* stream)
+{
+    int rc = check_detect(c, "rr_detect_device", d_imgs_u8, n_frames, cfg, d_points, max_points, d_offsets); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const rr_config& g = c->cfg;
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    launch_detect(d_imgs_u8, n_frames, *cfg, g.n_cells, g.n_angles, g.scroll_image, g.theta_min, g.theta_inc, g.resolution,
+                  max_points > 0 ? d_points : nullptr, max_points, d_offsets, s);
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_detect(rr_ctx* c, const uint8_t* imgs_u8, int n_frames, const rr_detect_config* cfg, rr_radar_point* points,
+              int max_points, uint32_t* offsets)
+{
+    int rc = check_detect(c, "rr_detect", imgs_u8, n_frames, cfg, points, max_points, offsets); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const rr_config& g = c->cfg;
+    const size_t npx = (size_t)g.n_cells * g.n_angles, n_offs = (size_t)n_frames * (g.n_angles + 1);
+    const size_t n_pts = (size_t)n_frames * (size_t)max_points;
+    RR_HIP(c, hipStreamSynchronize(c->stream));        // the staging buffers may be reallocated below
+    RR_HIP(c, c->d_conv_in.ensure((size_t)n_frames * npx));
+    RR_HIP(c, c->d_conv_offs.ensure(n_offs));
+    if (n_pts) RR_HIP(c, c->d_conv_points.ensure(n_pts));
+    RR_HIP(c, hipMemcpyAsync(c->d_conv_in.p, imgs_u8, (size_t)n_frames * npx, hipMemcpyHostToDevice, c->stream));
+    rc = rr_detect_device(c, c->d_conv_in.p, n_frames, cfg, n_pts ? c->d_conv_points.p : nullptr, max_points, c->d_conv_offs.p, c->stream);
+    if (rc) return rc;
+    RR_HIP(c, hipMemcpyAsync(offsets, c->d_conv_offs.p, n_offs * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (n_pts) RR_HIP(c, hipMemcpyAsync(points, c->d_conv_points.p, n_pts * sizeof(rr_radar_point), hipMemcpyDeviceToHost, c->stream));
+    RR_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int rr_polar_to_cartesian_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_frames, const rr_cartesian_config* cfg,
+                                 uint8_t* d_cart_u8, void* stream)
+{
+    int rc = check_cartesian(c, "rr_polar_to_cartesian_device", d_imgs_u8, n_frames, cfg, d_cart_u8); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const rr_config& g = c->cfg;
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    launch_cartesian(d_imgs_u8, n_frames, *cfg, g.n_cells, g.n_angles, g.scroll_image, g.theta_min, g.theta_inc, (float)g.resolution,
+                     d_cart_u8, s);
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_polar_to_cartesian(rr_ctx* c, const uint8_t* imgs_u8, int n_frames, const rr_cartesian_config* cfg, uint8_t* cart_u8)
+{
+    int rc = check_cartesian(c, "rr_polar_to_cartesian", imgs_u8, n_frames, cfg, cart_u8); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const rr_config& g = c->cfg;
+    const size_t npx = (size_t)g.n_cells * g.n_angles, n_out = (size_t)n_frames * cfg->width * cfg->width;
+    RR_HIP(c, hipStreamSynchronize(c->stream));
+    RR_HIP(c, c->d_conv_in.ensure((size_t)n_frames * npx));
+    RR_HIP(c, c->d_conv_cart.ensure(n_out));
+    RR_HIP(c, hipMemcpyAsync(c->d_conv_in.p, imgs_u8, (size_t)n_frames * npx, hipMemcpyHostToDevice, c->stream));
+    rc = rr_polar_to_cartesian_device(c, c->d_conv_in.p, n_frames, cfg, c->d_conv_cart.p, c->stream); if (rc) return rc;
+    RR_HIP(c, hipMemcpyAsync(cart_u8, c->d_conv_cart.p, n_out, hipMemcpyDeviceToHost, c->stream));
+    RR_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 

@@ -30,6 +30,7 @@ SYMBOLS = [
     "rr_simulate_param_sets_device", "rr_simulate_param_sets", "rr_score_images_device",
     "rr_set_object_poses", "rr_update_vertices", "rr_get_tree_cost", "rr_rebuild_tree",
     "rr_multi_set_object_poses", "rr_multi_update_vertices", "rr_multi_rebuild_tree",
+    "rr_default_detect_config", "rr_detect_device", "rr_detect", "rr_polar_to_cartesian_device", "rr_polar_to_cartesian",
 ]
 
 
@@ -67,6 +68,28 @@ class RRParamSet(C.Structure):
 class RRMesh(C.Structure):
     _fields_ = [("verts", C.POINTER(C.c_float)), ("n_verts", C.c_size_t), ("faces", C.POINTER(C.c_uint32)), ("n_faces", C.c_size_t),
                 ("face_object_id", C.POINTER(C.c_uint32)), ("n_objects", C.c_size_t), ("object_names", C.POINTER(C.c_char_p))]
+
+
+class RRDetectConfig(C.Structure):
+    _fields_ = [("method", C.c_int32), ("guard_cells", C.c_int32), ("train_cells", C.c_int32), ("k", C.c_int32),
+                ("min_intensity", C.c_int32), ("min_bin", C.c_int32), ("cfar_scale", C.c_float), ("reserved_", C.c_int32)]
+
+
+class RRRadarPoint(C.Structure):
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("intensity", C.c_float),
+                ("column", C.c_uint32), ("bin", C.c_uint32)]
+
+
+class RRCartesianConfig(C.Structure):
+    _fields_ = [("width", C.c_int32), ("interpolation", C.c_int32), ("pixel_size", C.c_float), ("reserved_", C.c_int32)]
+
+
+# rr_radar_point as numpy sees it (24 B: a PointCloud's point + its intensity channel, and where it came from)
+POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("intensity", "<f4"), ("column", "<u4"), ("bin", "<u4")])
+
+# rr_default_detect_config
+DETECT_DEFAULTS = {"method": 0, "guard_cells": 2, "train_cells": 16, "k": 12, "min_intensity": 1, "min_bin": 0, "cfar_scale": 3.0}
+DETECT_METHODS = {"cfar": 0, "ca-cfar": 0, "kstrongest": 1, "k-strongest": 1, 0: 0, 1: 1}
 
 
 class RRStats(C.Structure):
@@ -194,6 +217,12 @@ def lib():
     L.rr_multi_set_object_poses.argtypes = [vp, vp, C.c_size_t]
     L.rr_multi_update_vertices.argtypes = [vp, vp, C.c_size_t]
     L.rr_multi_rebuild_tree.argtypes = [vp, C.c_int]
+    L.rr_default_detect_config.argtypes = [C.POINTER(RRDetectConfig)]
+    L.rr_default_detect_config.restype = None
+    L.rr_detect_device.argtypes = [vp, vp, C.c_int, C.POINTER(RRDetectConfig), vp, C.c_int, vp, vp]
+    L.rr_detect.argtypes = [vp, vp, C.c_int, C.POINTER(RRDetectConfig), vp, C.c_int, vp]
+    L.rr_polar_to_cartesian_device.argtypes = [vp, vp, C.c_int, C.POINTER(RRCartesianConfig), vp, vp]
+    L.rr_polar_to_cartesian.argtypes = [vp, vp, C.c_int, C.POINTER(RRCartesianConfig), vp]
     for n in SYMBOLS:
         getattr(L, n)
     _LIB = L
@@ -260,6 +289,70 @@ def make_config(cfg, n_angles=400, max_waves_per_azimuth=0, wave_energy_threshol
 
 class RRError(RuntimeError):
     pass
+
+
+def _int_in(v, lo, hi, what):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise ValueError("%s must be an integer in [%d, %d], got %r" % (what, lo, hi, v))
+    return int(v)
+
+
+def detect_config(cfg=None, n_cells=None, **kw):
+    """RRDetectConfig from an RRDetectConfig, a dict and/or keywords over DETECT_DEFAULTS; every field is range-checked here
+    (k and min_bin against n_cells when it is given), before any call into the library.  method: 0 / "cfar", 1 / "kstrongest"."""
+    d = dict(DETECT_DEFAULTS)
+    if isinstance(cfg, RRDetectConfig):
+        d.update({k: getattr(cfg, k) for k in DETECT_DEFAULTS})
+    elif isinstance(cfg, dict):
+        d.update(cfg)
+    elif cfg is not None:
+        raise ValueError("detection config must be an RRDetectConfig or a dict, got %r" % (cfg,))
+    d.update(kw)
+    unknown = set(d) - set(DETECT_DEFAULTS)
+    if unknown:
+        raise ValueError("unknown detection config fields: %s" % sorted(unknown))
+    m = DETECT_METHODS.get(d["method"]) if isinstance(d["method"], (str, int)) and not isinstance(d["method"], bool) else None
+    if m is None:
+        raise ValueError("method must be 0 / 'cfar' or 1 / 'kstrongest', got %r" % (d["method"],))
+    top = int(n_cells) if n_cells is not None else 8192
+    c = RRDetectConfig()
+    c.method = m
+    c.guard_cells = _int_in(d["guard_cells"], 0, 1024, "guard_cells")
+    c.train_cells = _int_in(d["train_cells"], 1, 1024, "train_cells")
+    c.k = _int_in(d["k"], 1, top, "k")
+    c.min_intensity = _int_in(d["min_intensity"], 0, 255, "min_intensity")
+    c.min_bin = _int_in(d["min_bin"], 0, top - 1, "min_bin")
+    try:
+        scale = float(d["cfar_scale"])
+    except (TypeError, ValueError):
+        raise ValueError("cfar_scale must be a number, got %r" % (d["cfar_scale"],))
+    with np.errstate(over="ignore"):
+        finite = bool(np.isfinite(np.float32(scale)))
+    if not (finite and scale >= 0.0):
+        raise ValueError("cfar_scale must be finite and >= 0, got %r" % (scale,))
+    c.cfar_scale = scale
+    return c
+
+
+def cartesian_config(width, pixel_size, bilinear=True):
+    """RRCartesianConfig, range-checked before any call into the library"""
+    c = RRCartesianConfig()
+    c.width = _int_in(width, 1, 8192, "width")
+    try:
+        ps = float(pixel_size)
+    except (TypeError, ValueError):
+        raise ValueError("pixel_size must be a number, got %r" % (pixel_size,))
+    with np.errstate(over="ignore", under="ignore"):
+        ok = bool(np.isfinite(np.float32(ps)) and ps > 0.0 and np.float32(ps) > 0.0)
+    if not ok:
+        raise ValueError("pixel_size must be finite and > 0, got %r" % (pixel_size,))
+    c.pixel_size = ps
+    c.interpolation = 1 if bilinear else 0
+    return c
+
+
+def _frames_arg(n_frames):
+    return _int_in(n_frames, 1, 65535, "n_frames")
 
 
 class Context:
@@ -503,6 +596,75 @@ class Context:
     def simulate_device(self, pose, d_img_ptr, stream=None):
         p = np.ascontiguousarray(pose, np.float32)
         self._ck(self._L.rr_simulate_device(self._h, p.ctypes.data, d_img_ptr, stream))
+
+    # ---- point clouds and Cartesian images from polar images (rr_detect.hip): any context with a config, mesh or not
+    def _polar_shape(self):
+        if self.cfg is None:
+            raise RRError("rr_set_config has not been called")
+        return int(self.cfg.n_cells), int(self.n_angles)
+
+    def _polar_images(self, imgs):
+        """uint8 [n][n_cells][n_angles] (or one [n_cells][n_angles] image) of this context's shape -> contiguous 3-D array"""
+        n_cells, n_angles = self._polar_shape()
+        x = np.asarray(imgs)
+        if x.dtype != np.uint8:
+            raise ValueError("polar images must be uint8, got dtype %s" % x.dtype)
+        if x.ndim == 2:
+            x = x[None]
+        if x.ndim != 3 or x.shape[1:] != (n_cells, n_angles) or not 1 <= x.shape[0] <= 65535:
+            raise ValueError("polar images must have shape [n][%d][%d] (n in 1..65535), got %s" % (n_cells, n_angles, np.asarray(imgs).shape))
+        return np.ascontiguousarray(x)
+
+    def detect_device(self, d_imgs_ptr, n_frames, cfg=None, d_points_ptr=None, max_points=0, d_offsets_ptr=None, stream=None, **kw):
+        """rr_detect_device: points [n_frames][max_points] (rr_radar_point, POINT_DTYPE) and offsets [n_frames][n_angles + 1]
+        (uint32) in HBM, on `stream`.  max_points = 0 counts only."""
+        n_cells, _ = self._polar_shape()
+        c = detect_config(cfg, n_cells=n_cells, **kw)
+        n = _frames_arg(n_frames)
+        mp = _int_in(max_points, 0, 2**31 - 1, "max_points")
+        if not d_imgs_ptr or not d_offsets_ptr or (mp > 0 and not d_points_ptr):
+            raise ValueError("detect_device needs image and offset buffers (and a point buffer when max_points > 0)")
+        self._ck(self._L.rr_detect_device(self._h, d_imgs_ptr, n, C.byref(c), d_points_ptr, mp, d_offsets_ptr, stream))
+
+    def detect(self, imgs, cfg=None, max_points=None, allow_truncation=False, **kw):
+        """rr_detect on host images [n][n_cells][n_angles] (or one image).  Returns (list of n POINT_DTYPE arrays, offsets
+        uint32 [n][n_angles + 1]); offsets[f][c] = points of frame f in columns before c, offsets[f][-1] = the true total.
+        max_points None: room for every detection (a count-only call first).  A frame with more detections than max_points
+        raises RRError naming it, unless allow_truncation=True (then it holds its first max_points points)."""
+        x = self._polar_images(imgs)
+        n_cells, n_angles = self._polar_shape()
+        c = detect_config(cfg, n_cells=n_cells, **kw)
+        n = len(x)
+        offs = np.zeros((n, n_angles + 1), np.uint32)
+        if max_points is None:
+            self._ck(self._L.rr_detect(self._h, x.ctypes.data, n, C.byref(c), None, 0, offs.ctypes.data))
+            max_points = int(offs[:, -1].max())
+        mp = _int_in(max_points, 0, 2**31 - 1, "max_points")
+        pts = np.zeros((n, max(mp, 1)), POINT_DTYPE)
+        self._ck(self._L.rr_detect(self._h, x.ctypes.data, n, C.byref(c), pts.ctypes.data if mp else None, mp, offs.ctypes.data))
+        totals = offs[:, -1]
+        over = np.nonzero(totals > mp)[0]
+        if len(over) and not allow_truncation:
+            f = int(over[0])
+            raise RRError("detect: frame %d has %d detections, max_points is %d (%d frame(s) truncated)" % (f, int(totals[f]), mp, len(over)))
+        return [pts[f, :min(int(totals[f]), mp)].copy() for f in range(n)], offs
+
+    def polar_to_cartesian_device(self, d_imgs_ptr, n_frames, width, pixel_size, d_out_ptr, bilinear=True, stream=None):
+        """rr_polar_to_cartesian_device: [n_frames][width][width] uint8 in HBM, on `stream`"""
+        self._polar_shape()
+        c = cartesian_config(width, pixel_size, bilinear)
+        n = _frames_arg(n_frames)
+        if not d_imgs_ptr or not d_out_ptr:
+            raise ValueError("polar_to_cartesian_device needs image and output buffers")
+        self._ck(self._L.rr_polar_to_cartesian_device(self._h, d_imgs_ptr, n, C.byref(c), d_out_ptr, stream))
+
+    def polar_to_cartesian(self, imgs, width, pixel_size, bilinear=True):
+        """rr_polar_to_cartesian on host images [n][n_cells][n_angles] (or one image) -> uint8 [n][width][width]"""
+        x = self._polar_images(imgs)
+        c = cartesian_config(width, pixel_size, bilinear)
+        out = np.zeros((len(x), c.width, c.width), np.uint8)
+        self._ck(self._L.rr_polar_to_cartesian(self._h, x.ctypes.data, len(x), C.byref(c), out.ctypes.data))
+        return out
 
     def synchronize(self, stream=None):
         self._ck(self._L.rr_synchronize(self._h, stream))

@@ -130,6 +130,56 @@ class RadarHIP:
         """(cost of the current boxes, cost of the tree as built)."""
         return self._ctx.tree_cost()
 
+    # ---- point clouds and Cartesian images of polar images, on the GPU (rr_detect.hip; the reference runs
+    # radar_tools/radar_img_to_pcl on every image, launch/tests/radar_sim_test.launch:80-84).  cfg: rr_detect_config fields
+    # (method 0 / "cfar", 1 / "kstrongest"; native.DETECT_DEFAULTS for the rest)
+    def _polar(self, image):
+        return image.data if isinstance(image, Image) else np.asarray(image)
+
+    def toPointCloud(self, image, **cfg):
+        """one mono8 polar Image (simulated or real, this model's shape) -> POINT_DTYPE array: x, y, z in the sensor frame of
+        each point's azimuth, intensity, column, bin; sorted by column, then bin"""
+        self._push()
+        pts, _ = self._ctx.detect(self._polar(image), cfg)
+        return pts[0]
+
+    def toCartesian(self, image, width, pixel_size, bilinear=True, stamp=0.0):
+        """one mono8 polar Image -> a mono8 width x width bird's-eye Image (forward = up, left = left, pixel_size m/pixel)"""
+        self._push()
+        u8 = self._ctx.polar_to_cartesian(self._polar(image), width, pixel_size, bilinear)[0]
+        return Image(header=Header(stamp=stamp, frame_id=self.m_sensor_frame), height=u8.shape[0], width=u8.shape[1],
+                     encoding="mono8", step=u8.shape[1], data=u8)
+
+    def simulatePointClouds(self, poses, **cfg):
+        """[n][7] poses -> n point clouds (POINT_DTYPE arrays).  Per 64 poses: rr_simulate_batch_device and rr_detect_device on
+        one stream into device buffers; only the offsets and the points come to the host, no image does."""
+        import torch
+        self._push()
+        n_cells = self.m_cfg.n_cells
+        det = native.detect_config(cfg, n_cells=n_cells)
+        poses = native.object_poses_array(poses)
+        dev = torch.device("cuda", self._ctx.device)
+        out = []
+        # an explicit stream: the library reads a null handle as "the context's own stream", torch as its default stream
+        stream = torch.cuda.Stream(device=dev)
+        s = stream.cuda_stream
+        with torch.cuda.device(dev), torch.cuda.stream(stream):
+            for at in range(0, len(poses), 64):
+                chunk = poses[at:at + 64]
+                n = len(chunk)
+                imgs = torch.empty((n, n_cells, N_ANGLES), dtype=torch.uint8, device=dev)
+                offs = torch.empty((n, N_ANGLES + 1), dtype=torch.int32, device=dev)
+                self._ctx.simulate_batch_device(chunk, imgs.data_ptr(), s)
+                self._ctx.detect_device(imgs.data_ptr(), n, det, None, 0, offs.data_ptr(), s)     # counts
+                totals = offs[:, -1].cpu().numpy().view(np.uint32)
+                mp = max(1, int(totals.max()))
+                pts = torch.empty((n, mp * native.POINT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+                self._ctx.detect_device(imgs.data_ptr(), n, det, pts.data_ptr(), mp, offs.data_ptr(), s)
+                host = pts.cpu().numpy().view(native.POINT_DTYPE)
+                out.extend(host[f, :int(totals[f])].copy() for f in range(n))
+        self._ctx.synchronize(s)
+        return out
+
     def _push(self):
         if self._dirty_cfg:
             cfg = self.m_cfg.copy(n_reflections=self.m_params.model.n_reflections)
