@@ -601,8 +601,6 @@ void rr_free_mesh(rr_mesh* m);
  *                         stream-ordered copy behind the batch (the library's copy kernel, or hipMemcpyAsync for a pageable buffer).
  *                         RR_HOST_SDMA_VERBOSE=1 says on stderr why the path was not available or was switched off
  * RR_CULL_POP (1)         later passes drop stack entries at pop time by their distance bound; 0: off (same images)
- * RR_GRAPH_GUARD (1)      launch graphs: two execs per shape used alternately, the host waits for an exec's previous launch before it re-sets
- *                         its poses; 0 (probe): one exec, no wait -- relies on in-flight launches being unaffected by node updates
  * RR_GRAPHS (1)           launch chains of pose batches captured and replayed as hipGraphs (rr_get_graph_stats); 0: kernel by kernel
  * RR_TIGHT_GRID (1)       later-pass trace rows sized by the history of earlier batches (rr_get_trace_grid); 0: the doubling bound
  * RR_TRACE_CHUNK (16)     later-pass trace launches walk chunks of S neighbouring azimuths with the azimuth as the fast grid dimension;

@@ -89,6 +89,15 @@ struct KernelTimer {
     std::vector<float> samples_ms;   // every launch since the last reset (median / percentiles)
 };
 
+// a copy to host memory that may still be in flight (wait_delivery): where it goes, the SDMA job that carries it (0: a
+// stream-ordered copy, complete once `ev` is) -- and, in a lane's delivery slot, the image buffer it reads
+struct Delivery {
+    DevBuf<uint8_t> img;
+    hipEvent_t ev = nullptr;
+    const void* dst = nullptr;     // nullptr: nothing in flight
+    uint64_t job = 0;
+};
+
 }  // namespace
 
 struct Lane {
@@ -103,7 +112,6 @@ struct Lane {
     DevBuf<float> d_cols_f32;
     DevBuf<Counters> d_counters;
     DevBuf<uint32_t> d_sticky;    // error bits of ALL frames since the last rr_synchronize (async entry points); the synchronous entry points clear them when they report an error themselves
-    DevBuf<uint8_t> d_img_u8;     // host-buffer path: assembled image before the D2H copy
     DevBuf<float> d_img_f32;
     DevBuf<SegStats> d_seg_stats;
     DevBuf<float4> d_matsets;     // material sets of a parameter batch [n_sets][n_materials]
@@ -142,19 +150,14 @@ struct Lane {
     hipStream_t stream = nullptr;
     hipEvent_t ev_ready = nullptr, ev_consumed = nullptr;
     bool pending_consume = false;
-    // host delivery (rr_simulate_batch_host_async): the copies of this lane that may still be in flight.  Two records:
-    // a lane's copies complete in order, and a record is reused only after its copy has completed (take_rec waits), so a
-    // buffer that is in no record any more has been delivered.
-    struct CopyRec { const void* dst = nullptr; hipEvent_t ev = nullptr; bool pending = false; } rec[2];
-    int rec_next = 0;
-    // the default route: a batch's images leave at once over SDMA (rr_sdma.cpp).  TWO image buffers per lane, used alternately
-    // (d_img_u8 and d_img_u8_b), each with its event (behind the assemble that filled it) and the job that empties it: a buffer
-    // is written again two uses of the lane later (eight batches with four lanes), by which time its copy has long left -- the
-    // host checks the job before it reuses the buffer and practically never has to wait (with ONE buffer it waited for the lane's
-    // previous batch every time: the lane's stream ran dry while the host issued the next chain -- 35.9k instead of 39.4k images/s
-    // on config 2 from a C++ caller, 2.5k instead of 4.3k with one pose per batch on the target)
-    DevBuf<uint8_t> d_img_u8_b; hipEvent_t ev_img[2] = { nullptr, nullptr }; int img_flip = 0;
-    uint64_t sdma_job[2] = { 0, 0 }; const void* sdma_dst[2] = { nullptr, nullptr };
+    // host delivery (rr_simulate_batch_host_async): TWO delivery slots per lane, used alternately, each an image buffer with its
+    // event (behind the assemble that filled it; on the stream-ordered route behind the copy) and the copy that empties it.  A
+    // slot is written again two uses of the lane later (eight batches with four lanes), by which time its copy has long left --
+    // the host settles the slot before it reuses the buffer and practically never has to wait (with ONE buffer the SDMA route
+    // waited for the lane's previous batch every time: the lane's stream ran dry while the host issued the next chain -- 35.9k
+    // instead of 39.4k images/s on config 2 from a C++ caller, 2.5k instead of 4.3k with one pose per batch on the target).
+    // Every other user of the lane settles both slots (take_lane); rr_simulate assembles its image in slot 0's buffer
+    Delivery slot[2]; int next_slot = 0;
 };
 
 struct rr_ctx {
@@ -256,15 +259,12 @@ struct rr_ctx {
     // pageable destination, statistics mode or a runtime ROCr cannot be reached through: a stream-ordered copy behind the batch
     // (copy_out)
     int host_sdma = 1; SdmaCopier* sdma = nullptr; bool sdma_tried = false;
-    // rr_deliver_to_host_async: copies of caller-owned device buffers that rr_wait_host fences (an SDMA job, or -- fallback -- an
-    // event behind a stream-ordered copy); events are pooled
-    struct Delivery { const void* dst; uint64_t job; hipEvent_t ev; };
+    // rr_deliver_to_host_async: copies of caller-owned device buffers that rr_wait_host fences (no image buffer); events are pooled
     std::vector<Delivery> deliveries;
     std::vector<hipEvent_t> delivery_events;
     int tight_grid = 1;          // later-pass trace rows sized by what earlier batches needed (RR_TIGHT_GRID=0: the doubling bound)
     int tight_force = 0;         // RR_TIGHT_FORCE=n: rows of n workgroups whatever the history says (tests of the repair path)
     int hist_gen = 1;            // bumped whenever mesh / materials / beam / config change: the lanes' histories start over
-    int graph_guard = 1;         // RR_GRAPH_GUARD=0 (probe): replay ONE exec per shape without waiting for its previous launch, as round 5 did
     int use_graphs = 1;          // RR_GRAPHS=0: every launch chain is issued kernel by kernel
     int graph_gen = 1;           // bumped whenever anything a captured launch bakes in may have changed (tables, tree, lane buffers)
     uint64_t graph_clock = 0, graph_replays = 0, graph_captures = 0;
@@ -301,6 +301,8 @@ int fail(rr_ctx* c, int code, const std::string& msg)
     if (c) c->err = msg; else g_create_error = msg;
     return code;
 }
+
+inline hipStream_t stream_of(const rr_ctx* c, void* stream) { return stream ? (hipStream_t)stream : c->stream; }
 
 #define RR_HIP(c, expr)                                                                        \
     do {                                                                                       \
@@ -653,16 +655,6 @@ void fill_params(rr_ctx* c, Lane& L, Params& P, const float pose[7], int az_begi
     P.hist_host = (c->tight_grid && g.n_reflections > 1) ? L.h_hist : nullptr;              // the chain's k_column stores the history there (read without a fence by later batches)
 }
 
-// a free copy record of the lane (waits for the oldest copy if both are still in flight)
-int take_rec(rr_ctx* c, Lane& L, Lane::CopyRec** out)
-{
-    Lane::CopyRec& r = L.rec[L.rec_next];
-    L.rec_next ^= 1;
-    if (r.pending) { RR_HIP(c, hipEventSynchronize(r.ev)); r.pending = false; r.dst = nullptr; }
-    *out = &r;
-    return 0;
-}
-
 // device -> host on stream s: the library's own copy kernel (8 workgroups, all on XCD 0) when the destination is page-locked
 // (`visible`) and everything is 16-byte aligned, else hipMemcpyAsync (rr_copy_to_host_async in the header says why)
 int copy_out(rr_ctx* c, const void* d_src, void* h_dst, size_t bytes, bool visible, hipStream_t s)
@@ -702,17 +694,60 @@ int read_back(rr_ctx* c, void* dst, const void* d_src, size_t bytes)
     return 0;
 }
 
-// the images the lane's last host-delivery batches handed to the SDMA worker have left the lane's image buffers (host wait;
-// over long before a lane comes round again).  Every user of the lane but the SDMA route itself, which looks after its two
-// buffers, calls it before it touches the lane
-void settle_sdma(rr_ctx* c, Lane& L, int slot = -1, const void* only_dst = nullptr)
+// the counters of the lane the last frame ran on (the callers have synchronised)
+int read_counters(rr_ctx* c, Counters& h) { return read_back(c, &h, c->lanes[c->last_lane].d_counters.p, sizeof(h)); }
+
+// a frame's error bits (Counters::overflow, the lanes' sticky words) as the failure of the call that reports them
+int overflow_error(rr_ctx* c, uint32_t bits, bool since_sync = false)
+{
+    if (bits & 1u)
+        return fail(c, -7, std::string("wave/signal queue capacity exceeded") + (since_sync ? " in a frame since the last rr_synchronize" : "") +
+                               "; raise rr_config.max_waves_per_azimuth");
+    if (bits & 2u)
+        return fail(c, -8, std::string("object id or material id out of range of the tables given to rr_set_materials") +
+                               (since_sync ? " (a frame since the last rr_synchronize)" : ""));
+    return 0;
+}
+
+// the delivery has left (host wait): its SDMA job has completed, or else the event behind its stream-ordered copy
+int wait_delivery(rr_ctx* c, Delivery& d)
+{
+    if (!d.dst) return 0;
+    if (d.job) sdma_wait(c->sdma, d.job);
+    else RR_HIP(c, hipEventSynchronize(d.ev));
+    d.dst = nullptr; d.job = 0;
+    return 0;
+}
+
+// the lane's deliveries (slot `slot`, or both; only those to `only_dst` if given) have left its image buffers -- over long
+// before a lane comes round again
+int settle_lane(rr_ctx* c, Lane& L, int slot = -1, const void* only_dst = nullptr)
 {
     for (int b = 0; b < 2; b++) {
-        if ((slot >= 0 && b != slot) || !L.sdma_job[b]) continue;
-        if (only_dst && L.sdma_dst[b] != only_dst) continue;
-        if (c->sdma) sdma_wait(c->sdma, L.sdma_job[b]);
-        L.sdma_job[b] = 0; L.sdma_dst[b] = nullptr;
+        if ((slot >= 0 && b != slot) || (only_dst && L.slot[b].dst != only_dst)) continue;
+        const int rc = wait_delivery(c, L.slot[b]); if (rc) return rc;
     }
+    return 0;
+}
+
+// A frame entry point takes lane li once its arguments have passed: the lane's delivery slots are settled (both, or only
+// the one rr_simulate_batch_host_async is about to reuse), rr_get_stats & co. read it from now on, and `s` waits for the
+// lane's previous user (its frame buffers) -- no stream: no wait (rr_simulate_device while the caller captures)
+int take_lane(rr_ctx* c, size_t li, hipStream_t s, int slot = -1)
+{
+    Lane& L = c->lanes[li];
+    const int rc = settle_lane(c, L, slot); if (rc) return rc;
+    c->last_lane = li;
+    if (s && L.pending_consume) RR_HIP(c, hipStreamWaitEvent(s, L.ev_consumed, 0));
+    return 0;
+}
+
+// ... and hands it back: the lane's next user waits for what `s` holds so far
+hipError_t give_lane(Lane& L, hipStream_t s)
+{
+    const hipError_t e = hipEventRecord(L.ev_consumed, s);
+    L.pending_consume = true;
+    return e;
 }
 
 struct TimedScope {
@@ -929,12 +964,12 @@ int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end,
             hipKernelNodeParams kp = fg->pose_kp;
             kp.kernelParams = args; kp.extra = nullptr;
             hipError_t e = hipSuccess;
-            const int w = c->graph_guard ? fg->flip : 0; fg->flip ^= 1;
+            const int w = fg->flip; fg->flip ^= 1;
             hipGraphExec_t ex = w ? fg->ge2 : fg->ge;
-            if (c->graph_guard && fg->ev_pending[w]) { HostProfScope hp(6, "ctx:   graph: wait for the exec's previous launch"); e = hipEventSynchronize(fg->ev[w]); fg->ev_pending[w] = false; }
+            if (fg->ev_pending[w]) { HostProfScope hp(6, "ctx:   graph: wait for the exec's previous launch"); e = hipEventSynchronize(fg->ev[w]); fg->ev_pending[w] = false; }
             { HostProfScope hp(3, "ctx:   graph: set the poses"); if (e == hipSuccess) e = hipGraphExecKernelNodeSetParams(ex, fg->pose_node, &kp); }
             { HostProfScope hp(4, "ctx:   graph: launch"); if (e == hipSuccess) e = hipGraphLaunch(ex, s); }
-            if (e == hipSuccess && c->graph_guard) { e = hipEventRecord(fg->ev[w], s); fg->ev_pending[w] = e == hipSuccess; }
+            if (e == hipSuccess) { e = hipEventRecord(fg->ev[w], s); fg->ev_pending[w] = e == hipSuccess; }
             if (e != hipSuccess) return fail(c, -100, std::string("launch graph replay: ") + hipGetErrorString(e));
             c->graph_replays++;
             return 0;
@@ -942,6 +977,60 @@ int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end,
         fg->hits++;
     }
     { HostProfScope hp(5, "ctx:   chain issued kernel by kernel"); const int rcq = enqueue(P); if (rcq) return rcq; }
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+// the lane's columns of n_frames whole frames -> images [n_frames][n_cells][n_angles] in dst, on s
+int assemble_frames(rr_ctx* c, const Lane& L, uint8_t* dst, int n_frames, hipStream_t s)
+{
+    const rr_config& g = c->cfg;
+    const size_t npx = (size_t)g.n_angles * g.n_cells;
+    { TimedScope t(c, s, "assemble");
+      launch_assemble_u8(L.d_cols_u8.p, dst, g.n_angles, g.n_cells, g.scroll_image, s, g.n_angles, npx, n_frames, npx); }
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+// a pose batch rendered on lane L and assembled into dst (rr_simulate_batch_device, rr_simulate_batch_host_async)
+int render_batch(rr_ctx* c, Lane& L, const float* poses, int n_frames, uint8_t* dst, hipStream_t s)
+{
+    const int rc = run_frame(c, L, poses, 0, c->cfg.n_angles, nullptr, nullptr, s, n_frames); if (rc) return rc;
+    return assemble_frames(c, L, dst, n_frames, s);
+}
+
+// rr_simulate_columns_device (one frame, optional f32 columns) and rr_simulate_batch_columns_device after their checks
+int simulate_columns(rr_ctx* c, const float* poses, int n_frames, int az_begin, int az_end, uint8_t* d_cols_u8, float* d_cols_f32,
+                     void* stream)
+{
+    RR_HIP(c, hipSetDevice(c->device));
+    // rotate over the frame lanes so that calls issued on DIFFERENT streams (pipelined multi-GPU slots) can overlap; a
+    // lane is reused only after its previous frame finished
+    hipStream_t s = stream_of(c, stream);
+    const size_t li = c->next_lane++ % c->lanes.size();
+    Lane& L = c->lanes[li];
+    int rc;
+    { HostProfScope hp(0, "ctx: wait for the lane's event");
+      rc = take_lane(c, li, s); if (rc) return rc; }
+    { HostProfScope hp(1, "ctx: run_frame");
+      rc = run_frame(c, L, poses, az_begin, az_end, d_cols_u8, d_cols_f32, s, n_frames); if (rc) return rc; }
+    { HostProfScope hp(2, "ctx: record the lane's event");
+      RR_HIP(c, give_lane(L, s)); }
+    return 0;
+}
+
+// rr_assemble_image_device (blocks = false: whole frames) / _blocks_device / _frames_device: checked, one launch on `stream`
+int assemble_device(rr_ctx* c, const char* who, bool blocks, const uint8_t* d_cols_u8, int n_loc, size_t block_stride, int n_frames,
+                    size_t frame_stride, uint8_t* d_imgs_u8, void* stream)
+{
+    if (!c) return -1;
+    if (!c->have_cfg) return fail(c, -2, "rr_set_config has not been called");
+    if (!d_cols_u8 || !d_imgs_u8) return fail(c, -3, std::string(who) + ": null buffer");
+    if (blocks && (n_loc < 1 || c->cfg.n_angles % n_loc != 0)) return fail(c, -3, std::string(who) + ": n_loc must divide n_angles");
+    if (n_frames < 1 || n_frames > RR_MAX_BATCH) return fail(c, -3, std::string(who) + ": n_frames must be 1..64");
+    RR_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = stream_of(c, stream);
+    { TimedScope t(c, s, "assemble"); launch_assemble_u8(d_cols_u8, d_imgs_u8, c->cfg.n_angles, c->cfg.n_cells, c->cfg.scroll_image, s, n_loc, block_stride, n_frames, frame_stride); }
     RR_HIP(c, hipGetLastError());
     return 0;
 }
@@ -1015,7 +1104,6 @@ rr_ctx* rr_create(int device)
     if (getenv("RR_STACKLESS")) c->stackless = atoi(getenv("RR_STACKLESS")) != 0;
     if (getenv("RR_TRACE_CHUNK")) c->seg_chunk = std::max(0, std::min(1024, atoi(getenv("RR_TRACE_CHUNK"))));
     if (getenv("RR_GRAPHS")) c->use_graphs = atoi(getenv("RR_GRAPHS")) != 0;
-    if (getenv("RR_GRAPH_GUARD")) c->graph_guard = atoi(getenv("RR_GRAPH_GUARD")) != 0;
     if (getenv("RR_HOST_SDMA")) c->host_sdma = atoi(getenv("RR_HOST_SDMA")) != 0;
     if (getenv("RR_TIGHT_GRID")) c->tight_grid = atoi(getenv("RR_TIGHT_GRID")) != 0;
     if (getenv("RR_TIGHT_FORCE")) c->tight_force = std::max(0, atoi(getenv("RR_TIGHT_FORCE")));
@@ -1038,10 +1126,8 @@ rr_ctx* rr_create(int device)
         if (hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking) != hipSuccess ||
             hipEventCreateWithFlags(&L.ev_ready, hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&L.ev_consumed, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&L.ev_img[0], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&L.ev_img[1], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&L.rec[0].ev, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&L.rec[1].ev, hipEventDisableTiming) != hipSuccess) {
+            hipEventCreateWithFlags(&L.slot[0].ev, hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&L.slot[1].ev, hipEventDisableTiming) != hipSuccess) {
             g_create_error = "rr_create: lane stream/event creation failed"; rr_destroy(c); return nullptr;
         }
     }
@@ -1054,7 +1140,7 @@ void rr_destroy(rr_ctx* c)
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();   // frames may still be in flight on the lanes' or the caller's streams
     if (c->sdma) { sdma_destroy(c->sdma); c->sdma = nullptr; }      // (its queued copies wait for events that have completed by now)
-    for (rr_ctx::Delivery& d : c->deliveries) (void)hipEventDestroy(d.ev);
+    for (Delivery& d : c->deliveries) (void)hipEventDestroy(d.ev);
     for (hipEvent_t e : c->delivery_events) (void)hipEventDestroy(e);
     for (auto& kv : c->timers) for (auto& p : kv.second.pending) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
@@ -1067,14 +1153,12 @@ void rr_destroy(rr_ctx* c)
         for (int k = 0; k < 2; k++) { L.d_wA[k].release(); L.d_wB[k].release(); L.d_wC[k].release(); L.d_idx[k].release(); L.d_count[k].release(); L.d_torder[k].release(); }
         L.d_refpos.release();
         L.d_hit.release(); L.d_sig_count.release(); L.d_spill.release(); L.d_cflag.release(); L.d_cols_u8.release();
-        L.d_sigtmp.release(); L.d_sig.release(); L.d_cols_f32.release(); L.d_counters.release(); L.d_sticky.release(); L.d_seg_stats.release(); L.d_matsets.release(); L.d_matset_limits.release(); L.d_set_beams.release(); L.d_set_order.release(); L.d_set_order2.release(); L.d_img_u8.release(); L.d_img_f32.release();
+        L.d_sigtmp.release(); L.d_sig.release(); L.d_cols_f32.release(); L.d_counters.release(); L.d_sticky.release(); L.d_seg_stats.release(); L.d_matsets.release(); L.d_matset_limits.release(); L.d_set_beams.release(); L.d_set_order.release(); L.d_set_order2.release(); L.d_img_f32.release();
         L.d_hint.release(); L.d_ovf_list.release(); if (L.h_hist) { (void)hipHostFree(L.h_hist); L.h_hist = nullptr; }
         drop_graphs(L); L.d_poses.release();
         if (L.ev_ready) (void)hipEventDestroy(L.ev_ready);
         if (L.ev_consumed) (void)hipEventDestroy(L.ev_consumed);
-        for (hipEvent_t e : L.ev_img) if (e) (void)hipEventDestroy(e);
-        L.d_img_u8_b.release();
-        for (Lane::CopyRec& r : L.rec) if (r.ev) (void)hipEventDestroy(r.ev);
+        for (Delivery& d : L.slot) { d.img.release(); if (d.ev) (void)hipEventDestroy(d.ev); }
         if (L.stream) (void)hipStreamDestroy(L.stream);
     }
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1641,19 +1725,7 @@ int rr_simulate_columns_device(rr_ctx* c, const float pose[7], int az_begin, int
 {
     int rc = check_ready(c); if (rc) return rc;
     if (!pose || !d_cols_u8) return fail(c, -3, "rr_simulate_columns_device: null pose/output");
-    RR_HIP(c, hipSetDevice(c->device));
-    // rotate over the frame lanes so that calls issued on DIFFERENT streams (pipelined
-    // multi-GPU slots) can overlap; a lane is reused only after its previous frame finished
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    const size_t li = c->next_lane++ % c->lanes.size();
-    Lane& L = c->lanes[li];
-    settle_sdma(c, L);   // images a host-delivery batch is still sending from this lane
-    c->last_lane = li;
-    if (L.pending_consume) RR_HIP(c, hipStreamWaitEvent(s, L.ev_consumed, 0));
-    rc = run_frame(c, L, pose, az_begin, az_end, d_cols_u8, d_cols_f32, s); if (rc) return rc;
-    RR_HIP(c, hipEventRecord(L.ev_consumed, s));
-    L.pending_consume = true;
-    return 0;
+    return simulate_columns(c, pose, 1, az_begin, az_end, d_cols_u8, d_cols_f32, stream);
 }
 
 int rr_simulate_batch_columns_device(rr_ctx* c, const float* poses, int n_frames, int az_begin, int az_end,
@@ -1661,20 +1733,7 @@ int rr_simulate_batch_columns_device(rr_ctx* c, const float* poses, int n_frames
 {
     int rc = check_ready(c); if (rc) return rc;
     if (!poses || !d_cols_u8) return fail(c, -3, "rr_simulate_batch_columns_device: null poses/output");
-    RR_HIP(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    const size_t li = c->next_lane++ % c->lanes.size();
-    Lane& L = c->lanes[li];
-    settle_sdma(c, L);   // images a host-delivery batch is still sending from this lane
-    c->last_lane = li;
-    { HostProfScope hp(0, "ctx: wait for the lane's event");
-      if (L.pending_consume) RR_HIP(c, hipStreamWaitEvent(s, L.ev_consumed, 0)); }
-    { HostProfScope hp(1, "ctx: run_frame");
-      rc = run_frame(c, L, poses, az_begin, az_end, d_cols_u8, nullptr, s, n_frames); if (rc) return rc; }
-    { HostProfScope hp(2, "ctx: record the lane's event");
-      RR_HIP(c, hipEventRecord(L.ev_consumed, s)); }
-    L.pending_consume = true;
-    return 0;
+    return simulate_columns(c, poses, n_frames, az_begin, az_end, d_cols_u8, nullptr, stream);
 }
 
 int rr_simulate_batch_device(rr_ctx* c, const float* poses, int n_frames, uint8_t* d_imgs_u8, void* stream)
@@ -1683,21 +1742,13 @@ int rr_simulate_batch_device(rr_ctx* c, const float* poses, int n_frames, uint8_
     if (!poses || !d_imgs_u8) return fail(c, -3, "rr_simulate_batch_device: null poses/output");
     if (n_frames < 1 || n_frames > RR_MAX_BATCH) return fail(c, -3, "rr_simulate_batch_device: n_frames must be 1..64");
     RR_HIP(c, hipSetDevice(c->device));
-    const rr_config& g = c->cfg;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t s = stream_of(c, stream);
     rc = upload_tables(c); if (rc) return rc;
     const size_t li = c->next_lane++ % c->lanes.size();
     Lane& L = c->lanes[li];
-    settle_sdma(c, L);   // images a host-delivery batch is still sending from this lane
-    c->last_lane = li;
-    if (L.pending_consume) RR_HIP(c, hipStreamWaitEvent(s, L.ev_consumed, 0));
-    rc = run_frame(c, L, poses, 0, g.n_angles, nullptr, nullptr, s, n_frames); if (rc) return rc;
-    { TimedScope t(c, s, "assemble");
-      launch_assemble_u8(L.d_cols_u8.p, d_imgs_u8, g.n_angles, g.n_cells, g.scroll_image, s, g.n_angles,
-                         (size_t)g.n_angles * g.n_cells, n_frames, (size_t)g.n_angles * g.n_cells); }
-    RR_HIP(c, hipGetLastError());
-    RR_HIP(c, hipEventRecord(L.ev_consumed, s));
-    L.pending_consume = true;
+    rc = take_lane(c, li, s); if (rc) return rc;
+    rc = render_batch(c, L, poses, n_frames, d_imgs_u8, s); if (rc) return rc;
+    RR_HIP(c, give_lane(L, s));
     return 0;
 }
 
@@ -1736,7 +1787,7 @@ int rr_deliver_to_host_async(rr_ctx* c, const void* d_src, void* h_dst, size_t b
     if (bytes == 0) return 0;
     if (!d_src || !h_dst) return fail(c, -3, "rr_deliver_to_host_async: null pointer");
     RR_HIP(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t s = stream_of(c, stream);
     hipEvent_t ev = nullptr;
     if (!c->delivery_events.empty()) { ev = c->delivery_events.back(); c->delivery_events.pop_back(); }
     else RR_HIP(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -1753,7 +1804,8 @@ int rr_deliver_to_host_async(rr_ctx* c, const void* d_src, void* h_dst, size_t b
         const hipError_t e = hipEventRecord(ev, s);        // ... is complete once the stream has got here
         if (e != hipSuccess) { c->delivery_events.push_back(ev); RR_HIP(c, e); }
     }
-    c->deliveries.push_back({ h_dst, job, ev });
+    Delivery d; d.ev = ev; d.dst = h_dst; d.job = job;
+    c->deliveries.push_back(d);
     return 0;
 }
 
@@ -1770,7 +1822,7 @@ int rr_copy_to_host_async(rr_ctx* c, const void* d_src, void* h_dst, size_t byte
     if (!c) return -1;
     if (bytes && (!d_src || !h_dst)) return fail(c, -3, "rr_copy_to_host_async: null pointer");
     RR_HIP(c, hipSetDevice(c->device));
-    return copy_out(c, d_src, h_dst, bytes, bytes > 0 && host_visible(h_dst), stream ? (hipStream_t)stream : c->stream);
+    return copy_out(c, d_src, h_dst, bytes, bytes > 0 && host_visible(h_dst), stream_of(c, stream));
 }
 
 int rr_simulate_batch_host_async(rr_ctx* c, const float* poses, int n_frames, uint8_t* h_imgs_u8, void* stream)
@@ -1780,59 +1832,37 @@ int rr_simulate_batch_host_async(rr_ctx* c, const float* poses, int n_frames, ui
     if (n_frames < 1 || n_frames > RR_MAX_BATCH) return fail(c, -3, "rr_simulate_batch_host_async: n_frames must be 1..64");
     RR_HIP(c, hipSetDevice(c->device));
     const rr_config& g = c->cfg;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t s = stream_of(c, stream);
     rc = upload_tables(c); if (rc) return rc;
     const size_t li = c->next_lane++ % c->lanes.size();
     Lane& L = c->lanes[li];
-    c->last_lane = li;
     const size_t bytes = (size_t)n_frames * g.n_cells * g.n_angles;
     // The default route: over the SDMA engines through ROCr, at once, behind this batch's assemble -- no shader core stores a
-    // byte of it, so the batches beside it run at their HBM-resident rate, and it is the same engine under every HIP runtime
-    const bool device_visible = host_visible(h_imgs_u8);
-    if (SdmaCopier* sd = (device_visible && !c->stats_mode) ? sdma_of(c, c->d_bvh.p) : nullptr) {
-        const int b = L.img_flip;
-        settle_sdma(c, L, b);                                   // the job that empties THIS buffer: two uses of the lane ago
-        DevBuf<uint8_t>& img = b ? L.d_img_u8_b : L.d_img_u8;
-        if (img.n < bytes) {
-            settle_sdma(c, L);
-            RR_HIP(c, hipDeviceSynchronize());
-            RR_HIP(c, img.ensure(bytes));
-        }
-        if (L.pending_consume) RR_HIP(c, hipStreamWaitEvent(s, L.ev_consumed, 0));   // the lane's previous batch (its frame buffers)
-        rc = run_frame(c, L, poses, 0, g.n_angles, nullptr, nullptr, s, n_frames); if (rc) return rc;
-        { TimedScope t(c, s, "assemble");
-          launch_assemble_u8(L.d_cols_u8.p, img.p, g.n_angles, g.n_cells, g.scroll_image, s, g.n_angles,
-                             (size_t)g.n_angles * g.n_cells, n_frames, (size_t)g.n_angles * g.n_cells); }
-        RR_HIP(c, hipGetLastError());
-        RR_HIP(c, hipEventRecord(L.ev_consumed, s));
-        L.pending_consume = true;
-        RR_HIP(c, hipEventRecord(L.ev_img[b], s));
-        L.sdma_job[b] = sdma_submit(sd, L.ev_img[b], img.p, h_imgs_u8, bytes);
-        L.sdma_dst[b] = h_imgs_u8;
-        L.img_flip ^= 1;
-        return 0;
-    }
+    // byte of it, so the batches beside it run at their HBM-resident rate, and it is the same engine under every HIP runtime.
     // The fallback (SDMA switched off or not available, a pageable destination, statistics mode): the images leave on a plain
     // copy behind the batch, on its stream (copy_out).  Stores to host memory drain at PCIe speed, and the stores of the
     // kernels beside them wait behind them: on the target this route delivers some 7 % fewer images/s than SDMA
-    settle_sdma(c, L);
-    if (L.pending_consume) RR_HIP(c, hipStreamWaitEvent(s, L.ev_consumed, 0));   // the lane's previous batch, incl. its copy
-    if (L.d_img_u8.n < bytes) {
-        RR_HIP(c, hipDeviceSynchronize());      // an earlier copy may still read the old buffer
-        RR_HIP(c, L.d_img_u8.ensure(bytes));
+    const bool device_visible = host_visible(h_imgs_u8);
+    SdmaCopier* sd = (device_visible && !c->stats_mode) ? sdma_of(c, c->d_bvh.p) : nullptr;
+    const int b = L.next_slot;
+    Delivery& d = L.slot[b];
+    rc = take_lane(c, li, s, b); if (rc) return rc;         // the copy that empties THIS buffer: two uses of the lane ago
+    if (d.img.n < bytes) {
+        rc = settle_lane(c, L); if (rc) return rc;
+        RR_HIP(c, hipDeviceSynchronize());                  // an earlier batch may still use the old buffer
+        RR_HIP(c, d.img.ensure(bytes));
     }
-    rc = run_frame(c, L, poses, 0, g.n_angles, nullptr, nullptr, s, n_frames); if (rc) return rc;
-    { TimedScope t(c, s, "assemble");
-      launch_assemble_u8(L.d_cols_u8.p, L.d_img_u8.p, g.n_angles, g.n_cells, g.scroll_image, s, g.n_angles,
-                         (size_t)g.n_angles * g.n_cells, n_frames, (size_t)g.n_angles * g.n_cells); }
-    RR_HIP(c, hipGetLastError());
-    Lane::CopyRec* r = nullptr;
-    rc = take_rec(c, L, &r); if (rc) return rc;
-    rc = copy_out(c, L.d_img_u8.p, h_imgs_u8, bytes, device_visible, s); if (rc) return rc;
-    RR_HIP(c, hipEventRecord(r->ev, s));
-    r->dst = h_imgs_u8; r->pending = true;
-    RR_HIP(c, hipEventRecord(L.ev_consumed, s));      // what the lane's next user waits for: the batch and its copy
-    L.pending_consume = true;
+    rc = render_batch(c, L, poses, n_frames, d.img.p, s); if (rc) return rc;
+    if (sd) {
+        RR_HIP(c, hipEventRecord(d.ev, s));
+        d.job = sdma_submit(sd, d.ev, d.img.p, h_imgs_u8, bytes);
+    } else {
+        rc = copy_out(c, d.img.p, h_imgs_u8, bytes, device_visible, s); if (rc) return rc;
+        RR_HIP(c, hipEventRecord(d.ev, s));
+    }
+    d.dst = h_imgs_u8;
+    L.next_slot ^= 1;
+    RR_HIP(c, give_lane(L, s));       // what the lane's next user waits for: the batch and its copy
     return 0;
 }
 
@@ -1844,23 +1874,14 @@ int rr_wait_host(rr_ctx* c, const void* h_imgs_u8)
     // while the younger batches still render, and only the youngest batch's copy is left when the kernels are done -- in lane
     // order the youngest batch may come first, and the copies of all the others then queue up behind the end of the run
     for (size_t i = 0; i < c->deliveries.size();) {       // rr_deliver_to_host_async's copies
-        rr_ctx::Delivery& d = c->deliveries[i];
+        Delivery& d = c->deliveries[i];
         if (h_imgs_u8 != nullptr && d.dst != h_imgs_u8) { i++; continue; }
-        if (d.job && c->sdma) sdma_wait(c->sdma, d.job);
-        else RR_HIP(c, hipEventSynchronize(d.ev));
+        const int rc = wait_delivery(c, d); if (rc) return rc;
         c->delivery_events.push_back(d.ev);
         c->deliveries.erase(c->deliveries.begin() + (long)i);
     }
     const size_t nl = c->lanes.size();
-    for (size_t k = 0; k < nl; k++) {
-        Lane& L = c->lanes[(c->next_lane + k) % nl];
-        settle_sdma(c, L, -1, h_imgs_u8);
-        for (Lane::CopyRec& r : L.rec)
-            if (r.pending && (h_imgs_u8 == nullptr || r.dst == h_imgs_u8)) {
-                RR_HIP(c, hipEventSynchronize(r.ev));
-                r.pending = false; r.dst = nullptr;
-            }
-    }
+    for (size_t k = 0; k < nl; k++) { const int rc = settle_lane(c, c->lanes[(c->next_lane + k) % nl], -1, h_imgs_u8); if (rc) return rc; }
     return 0;
 }
 
@@ -1903,13 +1924,11 @@ int rr_simulate_param_sets_device(rr_ctx* c, const float pose[7], const rr_param
     }
     RR_HIP(c, hipSetDevice(c->device));
     const rr_config& g0 = c->cfg;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t s = stream_of(c, stream);
     rc = upload_tables(c); if (rc) return rc;
     const size_t li = c->next_lane++ % c->lanes.size();
     Lane& L = c->lanes[li];
-    settle_sdma(c, L);   // images a host-delivery batch is still sending from this lane
-    c->last_lane = li;
-    if (L.pending_consume) RR_HIP(c, hipStreamWaitEvent(s, L.ev_consumed, 0));
+    rc = take_lane(c, li, s); if (rc) return rc;
     static_assert(sizeof(rr_material) == sizeof(float4), "rr_material is {velocity, ambient, diffuse, specular}");
     const size_t G = (size_t)plan.n_groups;
     const bool own_beams = !(G == 1 && group_dirs[0] == nullptr);
@@ -1957,16 +1976,11 @@ int rr_simulate_param_sets_device(rr_ctx* c, const float pose[7], const rr_param
     if (rc) {
         // staged copies from the lane's host vectors may already be enqueued (advisor, round 4): the next call on this lane
         // must not rewrite them underneath -- it waits for ev_consumed like after a complete batch
-        (void)hipEventRecord(L.ev_consumed, s);
-        L.pending_consume = true;
+        (void)give_lane(L, s);
         return rc;
     }
-    { TimedScope t(c, s, "assemble");
-      launch_assemble_u8(L.d_cols_u8.p, d_imgs_u8, g0.n_angles, g0.n_cells, g0.scroll_image, s, g0.n_angles,
-                         (size_t)g0.n_angles * g0.n_cells, n_sets, (size_t)g0.n_angles * g0.n_cells); }
-    RR_HIP(c, hipGetLastError());
-    RR_HIP(c, hipEventRecord(L.ev_consumed, s));
-    L.pending_consume = true;
+    rc = assemble_frames(c, L, d_imgs_u8, n_sets, s); if (rc) return rc;
+    RR_HIP(c, give_lane(L, s));
     return 0;
 }
 
@@ -1998,11 +2012,9 @@ int finish_param_batch(rr_ctx* c, int n_sets, uint8_t* out_imgs_u8, const uint8_
     }
     RR_HIP(c, hipStreamSynchronize(c->stream));
     Counters h;
-    { const int rcb = read_back(c, &h, c->lanes[c->last_lane].d_counters.p, sizeof(h)); if (rcb) return rcb; }
+    { const int rcb = read_counters(c, h); if (rcb) return rcb; }
     if (h.overflow) RR_HIP(c, hipMemset(c->lanes[c->last_lane].d_sticky.p, 0, sizeof(uint32_t)));
-    if (h.overflow & 1u) return fail(c, -7, "wave/signal queue capacity exceeded; raise rr_config.max_waves_per_azimuth");
-    if (h.overflow & 2u) return fail(c, -8, "object id or material id out of range of the tables given to rr_set_materials");
-    return 0;
+    return overflow_error(c, h.overflow);
 }
 }  // namespace
 
@@ -2041,7 +2053,7 @@ int rr_score_images_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_images, co
     if (!d_imgs_u8 || !d_ref_u8 || (!out_psnr && !out_sse)) return fail(c, -3, "rr_score_images_device: null buffer");
     if (n_images < 1 || n_images > 65535) return fail(c, -3, "rr_score_images_device: n_images must be 1..65535");
     RR_HIP(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t s = stream_of(c, stream);
     const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles;
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "sse words");
     if (c->d_sse.n < (size_t)n_images) { RR_HIP(c, hipStreamSynchronize(s)); RR_HIP(c, c->d_sse.ensure((size_t)n_images)); }
@@ -2124,7 +2136,7 @@ int rr_detect_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_frames, const rr
     int rc = check_detect(c, "rr_detect_device", d_imgs_u8, n_frames, cfg, d_points, max_points, d_offsets); if (rc) return rc;
     RR_HIP(c, hipSetDevice(c->device));
     const rr_config& g = c->cfg;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t s = stream_of(c, stream);
     launch_detect(d_imgs_u8, n_frames, *cfg, g.n_cells, g.n_angles, g.scroll_image, g.theta_min, g.theta_inc, g.resolution,
                   max_points > 0 ? d_points : nullptr, max_points, d_offsets, s);
     RR_HIP(c, hipGetLastError());
@@ -2158,7 +2170,7 @@ int rr_polar_to_cartesian_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_fram
     int rc = check_cartesian(c, "rr_polar_to_cartesian_device", d_imgs_u8, n_frames, cfg, d_cart_u8); if (rc) return rc;
     RR_HIP(c, hipSetDevice(c->device));
     const rr_config& g = c->cfg;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t s = stream_of(c, stream);
     launch_cartesian(d_imgs_u8, n_frames, *cfg, g.n_cells, g.n_angles, g.scroll_image, g.theta_min, g.theta_inc, (float)g.resolution,
                      d_cart_u8, s);
     RR_HIP(c, hipGetLastError());
@@ -2183,43 +2195,19 @@ int rr_polar_to_cartesian(rr_ctx* c, const uint8_t* imgs_u8, int n_frames, const
 
 int rr_assemble_image_device(rr_ctx* c, const uint8_t* d_cols_u8, uint8_t* d_img_u8, void* stream)
 {
-    if (!c) return -1;
-    if (!c->have_cfg) return fail(c, -2, "rr_set_config has not been called");
-    if (!d_cols_u8 || !d_img_u8) return fail(c, -3, "rr_assemble_image_device: null buffer");
-    RR_HIP(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    { TimedScope t(c, s, "assemble"); launch_assemble_u8(d_cols_u8, d_img_u8, c->cfg.n_angles, c->cfg.n_cells, c->cfg.scroll_image, s); }
-    RR_HIP(c, hipGetLastError());
-    return 0;
+    return assemble_device(c, "rr_assemble_image_device", false, d_cols_u8, 0, 0, 1, 0, d_img_u8, stream);
 }
 
 int rr_assemble_frames_device(rr_ctx* c, const uint8_t* d_cols_u8, int n_loc, size_t block_stride,
                               int n_frames, size_t frame_stride, uint8_t* d_imgs_u8, void* stream)
 {
-    if (!c) return -1;
-    if (!c->have_cfg) return fail(c, -2, "rr_set_config has not been called");
-    if (!d_cols_u8 || !d_imgs_u8) return fail(c, -3, "rr_assemble_frames_device: null buffer");
-    if (n_loc < 1 || c->cfg.n_angles % n_loc != 0) return fail(c, -3, "rr_assemble_frames_device: n_loc must divide n_angles");
-    if (n_frames < 1 || n_frames > RR_MAX_BATCH) return fail(c, -3, "rr_assemble_frames_device: n_frames must be 1..64");
-    RR_HIP(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    { TimedScope t(c, s, "assemble"); launch_assemble_u8(d_cols_u8, d_imgs_u8, c->cfg.n_angles, c->cfg.n_cells, c->cfg.scroll_image, s, n_loc, block_stride, n_frames, frame_stride); }
-    RR_HIP(c, hipGetLastError());
-    return 0;
+    return assemble_device(c, "rr_assemble_frames_device", true, d_cols_u8, n_loc, block_stride, n_frames, frame_stride, d_imgs_u8, stream);
 }
 
 int rr_assemble_blocks_device(rr_ctx* c, const uint8_t* d_cols_u8, int n_loc, size_t block_stride,
                               uint8_t* d_img_u8, void* stream)
 {
-    if (!c) return -1;
-    if (!c->have_cfg) return fail(c, -2, "rr_set_config has not been called");
-    if (!d_cols_u8 || !d_img_u8) return fail(c, -3, "rr_assemble_blocks_device: null buffer");
-    if (n_loc < 1 || c->cfg.n_angles % n_loc != 0) return fail(c, -3, "rr_assemble_blocks_device: n_loc must divide n_angles");
-    RR_HIP(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    { TimedScope t(c, s, "assemble"); launch_assemble_u8(d_cols_u8, d_img_u8, c->cfg.n_angles, c->cfg.n_cells, c->cfg.scroll_image, s, n_loc, block_stride); }
-    RR_HIP(c, hipGetLastError());
-    return 0;
+    return assemble_device(c, "rr_assemble_blocks_device", true, d_cols_u8, n_loc, block_stride, 1, 0, d_img_u8, stream);
 }
 
 int rr_simulate_device(rr_ctx* c, const float pose[7], uint8_t* d_img_u8, void* stream)
@@ -2227,13 +2215,11 @@ int rr_simulate_device(rr_ctx* c, const float pose[7], uint8_t* d_img_u8, void* 
     int rc = check_ready(c); if (rc) return rc;
     if (!pose || !d_img_u8) return fail(c, -3, "rr_simulate_device: null pose/output");
     RR_HIP(c, hipSetDevice(c->device));
-    hipStream_t user = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t user = stream_of(c, stream);
     rc = upload_tables(c); if (rc) return rc;
     const int A = c->cfg.n_angles;
     if (c->lanes.size() == 1) {
         Lane& L = c->lanes[0];
-        settle_sdma(c, L);   // images a host-delivery batch is still sending from this lane
-        c->last_lane = 0;
         // With ONE lane every launch of the frame goes to the caller's stream, so the call can be CAPTURED into a hipGraph
         // (hipStreamBeginCapture on `user`, this call, hipStreamEndCapture) and replayed -- tools/cpp_bench.cpp `graph`.  While
         // capturing, the lane's hand-over event stays out of it (an event recorded outside the capture cannot be waited
@@ -2242,10 +2228,10 @@ int rr_simulate_device(rr_ctx* c, const float pose[7], uint8_t* d_img_u8, void* 
         (void)hipStreamIsCapturing(user, &cap);
         const bool capturing = cap == hipStreamCaptureStatusActive;
         // the lane's previous frame may have run on ANOTHER caller stream (or a flushed host copy may still read the lane)
-        if (L.pending_consume && !capturing) RR_HIP(c, hipStreamWaitEvent(user, L.ev_consumed, 0));
+        rc = take_lane(c, 0, capturing ? nullptr : user); if (rc) return rc;
         rc = run_frame(c, L, pose, 0, A, nullptr, nullptr, user); if (rc) return rc;
         rc = rr_assemble_image_device(c, L.d_cols_u8.p, d_img_u8, user); if (rc) return rc;
-        if (!capturing) { RR_HIP(c, hipEventRecord(L.ev_consumed, user)); L.pending_consume = true; }
+        if (!capturing) RR_HIP(c, give_lane(L, user));
         return 0;
     }
     // Frame pipelining: trace/shade/scan/column of this frame run on the lane's own stream
@@ -2254,15 +2240,12 @@ int rr_simulate_device(rr_ctx* c, const float pose[7], uint8_t* d_img_u8, void* 
     // that assemble has consumed its columns.
     const size_t li = c->next_stream_lane++ % (size_t)c->stream_lanes;
     Lane& L = c->lanes[li];
-    settle_sdma(c, L);   // images a host-delivery batch is still sending from this lane
-    c->last_lane = li;
-    if (L.pending_consume) RR_HIP(c, hipStreamWaitEvent(L.stream, L.ev_consumed, 0));
+    rc = take_lane(c, li, L.stream); if (rc) return rc;
     rc = run_frame(c, L, pose, 0, A, nullptr, nullptr, L.stream); if (rc) return rc;
     RR_HIP(c, hipEventRecord(L.ev_ready, L.stream));
     RR_HIP(c, hipStreamWaitEvent(user, L.ev_ready, 0));
     rc = rr_assemble_image_device(c, L.d_cols_u8.p, d_img_u8, user); if (rc) return rc;
-    RR_HIP(c, hipEventRecord(L.ev_consumed, user));
-    L.pending_consume = true;
+    RR_HIP(c, give_lane(L, user));
     return 0;
 }
 
@@ -2270,15 +2253,14 @@ int rr_synchronize(rr_ctx* c, void* stream)
 {
     if (!c) return -1;
     RR_HIP(c, hipSetDevice(c->device));
-    for (Lane& L : c->lanes) settle_sdma(c, L);
+    for (Lane& L : c->lanes) { const int rc = settle_lane(c, L); if (rc) return rc; }
     if (!c->deliveries.empty()) { const int rc = rr_wait_host(c, nullptr); if (rc) return rc; }
     for (Lane& L : c->lanes) RR_HIP(c, hipStreamSynchronize(L.stream));
-    RR_HIP(c, hipStreamSynchronize(stream ? (hipStream_t)stream : c->stream));
+    RR_HIP(c, hipStreamSynchronize(stream_of(c, stream)));
     // batches may run on OTHER caller streams as well (the header recommends four): a frame there could set a
     // bit between the read and the clear below, so the whole device is drained first -- after this call no
     // frame of this context is in flight anywhere and every error bit raised so far is reported exactly once
     RR_HIP(c, hipDeviceSynchronize());
-    for (Lane& L : c->lanes) for (Lane::CopyRec& r : L.rec) { r.pending = false; r.dst = nullptr; }
     // error bits of every frame the asynchronous entry points enqueued since the last call (a frame that
     // overflowed its wave queue or met a bad material id is truncated, never silently)
     uint32_t bits = 0;
@@ -2288,9 +2270,7 @@ int rr_synchronize(rr_ctx* c, void* stream)
         RR_HIP(c, hipMemcpy(&b, L.d_sticky.p, sizeof(b), hipMemcpyDeviceToHost));
         if (b) { bits |= b; RR_HIP(c, hipMemset(L.d_sticky.p, 0, sizeof(b))); }
     }
-    if (bits & 1u) return fail(c, -7, "wave/signal queue capacity exceeded in a frame since the last rr_synchronize; raise rr_config.max_waves_per_azimuth");
-    if (bits & 2u) return fail(c, -8, "object id or material id out of range of the tables given to rr_set_materials (a frame since the last rr_synchronize)");
-    return 0;
+    return overflow_error(c, bits, true);
 }
 
 int rr_peek_error_bits_async(rr_ctx* c, uint32_t* h_bits, void* stream)
@@ -2300,7 +2280,7 @@ int rr_peek_error_bits_async(rr_ctx* c, uint32_t* h_bits, void* stream)
     RR_HIP(c, hipSetDevice(c->device));
     Lane& L = c->lanes[c->last_lane];
     if (!L.d_sticky.p) { *h_bits = 0; return 0; }     // no frame has run on this lane yet
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t s = stream_of(c, stream);
     if (host_visible(h_bits)) { launch_store_u32(L.d_sticky.p, h_bits, s); RR_HIP(c, hipGetLastError()); }     // (a kernel's store: no copy engine involved)
     else RR_HIP(c, hipMemcpyAsync(h_bits, L.d_sticky.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     return 0;
@@ -2315,7 +2295,7 @@ int rr_get_stats(rr_ctx* c, rr_stats* st)
     Lane& L = c->lanes[c->last_lane];
     if (!L.d_counters.p) return 0;
     Counters h;
-    { const int rcb = read_back(c, &h, L.d_counters.p, sizeof(h)); if (rcb) return rcb; }
+    { const int rcb = read_counters(c, h); if (rcb) return rcb; }
     st->nodes_visited = h.nodes; st->tris_tested = h.tris; st->overflow = h.overflow;
     if (getenv("RR_TRACE_STATS")) fprintf(stderr, "[rr stats] waves %u wave_iters %llu (avg %.1f) max_iters %u\n", h.n_waves, h.wave_iters, h.n_waves ? (double)h.wave_iters / h.n_waves : 0.0, h.max_iters);
     if (getenv("RR_TRACE_STATS") && h.n_waves)
@@ -2343,13 +2323,11 @@ int rr_simulate(rr_ctx* c, const float pose[7], int az_begin, int az_end,
     if (n_seg == 0) { if (stats) std::memset(stats, 0, sizeof(*stats)); return 0; }
     rc = upload_tables(c); if (rc) return rc;
     Lane& L = c->lanes[0];
-    settle_sdma(c, L);   // images a host-delivery batch is still sending from this lane
-    c->last_lane = 0;
     // The reference's call shape: one synchronous simulate() per frame (radar_simulator.cpp:197-212).  Its latency is
     // the chain of kernels plus what the host adds around it, so the host adds as little as it can: the frame is
     // ordered behind the lane's previous user by an event (no device-wide drain), the error bits and the per-pass
     // counters ride home behind the image on the same stream, and ONE hipStreamSynchronize ends the call.
-    if (L.pending_consume) RR_HIP(c, hipStreamWaitEvent(c->stream, L.ev_consumed, 0));
+    rc = take_lane(c, 0, c->stream); if (rc) return rc;
     rc = run_frame(c, L, pose, az_begin, az_end, nullptr, nullptr, c->stream, 1, nullptr, 0, out_f32 != nullptr);
     if (rc) return rc;
     const size_t n_st = (size_t)n_seg * (size_t)std::max(1, g.n_reflections);
@@ -2367,9 +2345,10 @@ int rr_simulate(rr_ctx* c, const float pose[7], int az_begin, int az_end,
         // whole frame: transpose on the GPU, one D2H copy straight into the caller's row-major buffer
         const size_t npx = (size_t)g.n_cells * g.n_angles;
         if (out_u8) {
-            RR_HIP(c, L.d_img_u8.ensure(npx));
-            launch_assemble_u8(L.d_cols_u8.p, L.d_img_u8.p, g.n_angles, g.n_cells, g.scroll_image, c->stream);
-            RR_HIP(c, hipMemcpyAsync(out_u8, L.d_img_u8.p, npx, hipMemcpyDeviceToHost, c->stream));
+            DevBuf<uint8_t>& img = L.slot[0].img;      // (settled by take_lane)
+            RR_HIP(c, img.ensure(npx));
+            launch_assemble_u8(L.d_cols_u8.p, img.p, g.n_angles, g.n_cells, g.scroll_image, c->stream);
+            RR_HIP(c, hipMemcpyAsync(out_u8, img.p, npx, hipMemcpyDeviceToHost, c->stream));
         }
         if (out_f32) {
             RR_HIP(c, L.d_img_f32.ensure(npx));
@@ -2388,8 +2367,7 @@ int rr_simulate(rr_ctx* c, const float pose[7], int az_begin, int az_end,
     RR_HIP(c, hipMemcpyAsync(h_cnt, L.d_counters.p, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
     if (stats && L.d_seg_stats.p && g.n_reflections > 0)
         RR_HIP(c, hipMemcpyAsync(h_ss, L.d_seg_stats.p, n_st * sizeof(SegStats), hipMemcpyDeviceToHost, c->stream));
-    RR_HIP(c, hipEventRecord(L.ev_consumed, c->stream));
-    L.pending_consume = true;
+    RR_HIP(c, give_lane(L, c->stream));
     RR_HIP(c, hipStreamSynchronize(c->stream));
     if (n_seg != g.n_angles) {
         for (int s = 0; s < n_seg; s++) {
@@ -2409,9 +2387,7 @@ int rr_simulate(rr_ctx* c, const float pose[7], int az_begin, int az_end,
         if (getenv("RR_TRACE_STATS")) { rr_stats tmp; (void)rr_get_stats(c, &tmp); }     // prints the wave-level loop shape
     }
     if (overflow) RR_HIP(c, hipMemset(L.d_sticky.p, 0, sizeof(uint32_t)));   // reported here, not again by rr_synchronize
-    if (overflow & 1u) return fail(c, -7, "wave/signal queue capacity exceeded; raise rr_config.max_waves_per_azimuth");
-    if (overflow & 2u) return fail(c, -8, "object id or material id out of range of the tables given to rr_set_materials");
-    return 0;
+    return overflow_error(c, overflow);
 }
 
 int rr_set_stats_mode(rr_ctx* c, int enable) { if (!c) return -1; c->stats_mode = enable != 0; return 0; }
@@ -2425,7 +2401,7 @@ int rr_get_traversal_shape(rr_ctx* c, uint64_t out[8])
     Lane& L = c->lanes[c->last_lane];
     if (!L.d_counters.p) return 0;
     Counters h;
-    { const int rcb = read_back(c, &h, L.d_counters.p, sizeof(h)); if (rcb) return rcb; }
+    { const int rcb = read_counters(c, h); if (rcb) return rcb; }
     out[0] = h.n_waves; out[1] = h.it_all; out[2] = h.it_node; out[3] = h.it_leaf; out[4] = h.quad_steps; out[5] = h.max_iters;
     out[6] = h.nodes; out[7] = h.quad_steps > h.nodes ? h.quad_steps - h.nodes : 0;
     return 0;
