@@ -17,6 +17,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 _REF = None
+_REFLOOP = None
 
 
 class OrcMaterial(C.Structure):
@@ -108,6 +109,7 @@ def lib():
     L.orc_noise_amplitude.argtypes = [C.c_float, C.c_float, C.c_double, C.c_double]
     L.orc_cone_radius.restype = C.c_float
     L.orc_cone_radius.argtypes = [C.c_float, C.c_int, C.c_float, C.c_float]
+    L.orc_set_uniform_stream.argtypes = [C.c_void_p, C.c_size_t]
     L.orc_saturate_u8.restype = C.c_uint8
     L.orc_saturate_u8.argtypes = [C.c_float]
     _LIB = L
@@ -127,6 +129,88 @@ def ref_lib():
             getattr(R, n).argtypes = [C.c_float]
         _REF = R
     return _REF
+
+
+def refloop_lib():
+    """oracle/_ref/libradarays_refloop.so (the reference's own RadarCPU.cpp / radar_algorithms.cpp compiled against the
+    behaving stand-ins of oracle/refshim/, `make -C oracle ref`) or None where it has not been built."""
+    global _REFLOOP
+    if _REFLOOP is None:
+        so = os.path.join(_HERE, "_ref", "libradarays_refloop.so")
+        if not os.path.exists(so):
+            return None
+        lib()                                   # its nearest hit is this library's orc_intersect
+        R = C.CDLL(so)
+        fp, dp, up = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_uint32)
+        R.ref_simulate.restype = C.c_int
+        R.ref_simulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                   C.POINTER(OrcConfig), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                   C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        R.ref_fresnel.argtypes = [fp, fp, C.c_double, C.c_double, C.c_double, C.c_double, fp, dp, fp, dp]
+        R.ref_back_reflection_shader.restype = C.c_float
+        R.ref_back_reflection_shader.argtypes = [C.c_float] * 5
+        for n in ("ref_incidence_angle", "ref_angle_between"):
+            getattr(R, n).restype = C.c_double
+            getattr(R, n).argtypes = [fp, fp]
+        for n in ("triangular", "gaussian", "maxwell_boltzmann"):
+            getattr(R, "ref_make_denoiser_" + n).argtypes = [C.c_int, C.c_int, fp]
+        R.ref_perlin_noise.restype = C.c_double
+        R.ref_perlin_noise.argtypes = [C.c_double] * 3
+        R.ref_wave_move.argtypes = [fp, fp, dp, C.c_double, C.c_double]
+        R.ref_sample_cone_local.restype = C.c_int
+        R.ref_sample_cone_local.argtypes = [C.c_uint32, C.c_float, C.c_int, C.c_int, C.c_float, fp, fp, fp]
+        R.ref_noise_offset.restype = C.c_double
+        R.ref_noise_offset.argtypes = [C.c_uint32]
+        R.ref_find_noise_seeds.argtypes = [C.c_uint32, C.c_size_t, up, fp]
+        R.ref_uniform_stream.argtypes = [C.c_uint32, C.c_size_t, fp]
+        _REFLOOP = R
+    return _REFLOOP
+
+
+def ref_noise_seeds(start, n):
+    """n seeds (from `start` upwards) for the reference loop's random device whose noise offset -- the f64 product
+    `uniform f32 draw * 1000.0` -- is exactly an f32, and those offsets: the build injects its offsets as f32."""
+    seeds, offs = np.zeros(n, np.uint32), np.zeros(n, np.float32)
+    refloop_lib().ref_find_noise_seeds(int(start), n, seeds.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                       offs.ctypes.data_as(C.POINTER(C.c_float)))
+    return seeds, offs
+
+
+def ref_uniform_stream(seeds, n_cells):
+    """[len(seeds)][n_cells]: the per-cell uniform variates the reference loop draws for ambient_noise == 1 in an azimuth
+    whose random device handed out that seed (the draws after the first, which is the noise offset)."""
+    out = np.zeros((len(seeds), n_cells), np.float32)
+    for k, sd in enumerate(seeds):
+        refloop_lib().ref_uniform_stream(int(sd), n_cells, out[k].ctypes.data_as(C.POINTER(C.c_float)))
+    return out
+
+
+def ref_simulate(scene, materials, object_materials, cfg, beam_dirs, pose, noise_seeds=None, n_angles=400,
+                 material_id_air=0):
+    """One call of the reference's RadarCPU::simulate (always the whole sweep) on an oracle Scene.  pose: [7], or
+    [n_angles][7] with cfg.include_motion.  noise_seeds: what the loop's random device hands out, one per azimuth.
+    Returns (u8 [n_cells][n_angles], the seeds the device handed out)."""
+    R = refloop_lib()
+    oc = make_config(cfg, n_angles, material_id_air)
+    mats = (OrcMaterial * len(materials))(*[OrcMaterial(*[float(x) for x in m]) for m in materials])
+    om = np.ascontiguousarray(object_materials, np.int32)
+    if scene.obj is not None and len(scene.obj):
+        assert int(scene.obj.max()) < len(om)   # the reference indexes its table unchecked
+    bd = np.ascontiguousarray(beam_dirs, np.float32)
+    ps = np.ascontiguousarray(pose, np.float32).reshape(-1, 7)
+    motion = bool(getattr(cfg, "include_motion", False)) and len(ps) > 1
+    assert len(ps) == (n_angles if motion else 1)
+    ns = None if noise_seeds is None else np.ascontiguousarray(noise_seeds, np.uint32)
+    u8 = np.zeros((oc.n_cells, n_angles), np.uint8)
+    log = np.zeros(n_angles + 8, np.uint32)
+    n_log = C.c_size_t(0)
+    rc = R.ref_simulate(scene._h, None if scene.obj is None else scene.obj.ctypes.data, mats, len(materials),
+                        om.ctypes.data, len(om), C.byref(oc), int(motion), bd.ctypes.data, len(bd),
+                        ps.ctypes.data, len(ps), None if ns is None else ns.ctypes.data, 0 if ns is None else len(ns),
+                        u8.ctypes.data, log.ctypes.data, len(log), C.byref(n_log))
+    if rc != 0:
+        raise RuntimeError("ref_simulate failed: %d" % rc)
+    return u8, log[:n_log.value].copy()
 
 
 def _f3(a):
@@ -250,7 +334,7 @@ class Scene:
 
 def simulate(scene, materials, object_materials, cfg, beam_dirs, pose, noise_rnd=None,
              az_begin=0, az_end=None, n_angles=400, material_id_air=0, want_f32=True,
-             n_threads=0, brdf_model=0):
+             n_threads=0, brdf_model=0, uniform_stream=None):
     """RadarCPU::simulate on the oracle. materials: [(velocity, ambient, diffuse, specular)].
     Returns (u8 [n_cells][n_angles], f32 or None, stats dict)."""
     L = lib()
@@ -267,12 +351,23 @@ def simulate(scene, materials, object_materials, cfg, beam_dirs, pose, noise_rnd
     u8 = np.zeros((oc.n_cells, n_angles), np.uint8)
     f32 = np.zeros((oc.n_cells, n_angles), np.float32) if want_f32 else None
     st = OrcStats()
-    rc = (L.orc_simulate_motion if motion else L.orc_simulate)(scene._h, mats, len(materials), om.ctypes.data, len(om), C.byref(oc),
-                        bd.ctypes.data, len(bd), ps.ctypes.data,
-                        None if nr is None else nr.ctypes.data,
-                        az_begin, az_end, u8.ctypes.data,
-                        None if f32 is None else f32.ctypes.data, n_threads, C.byref(st))
+    us = None if uniform_stream is None else np.ascontiguousarray(uniform_stream, np.float32).ravel()
+    if us is not None:                  # ambient_noise == 1 with a caller's variates [n_angles][n_cells] (test hook)
+        L.orc_set_uniform_stream(us.ctypes.data, len(us))
+    try:
+        rc = _run_simulate(L, motion, scene, mats, materials, om, oc, bd, ps, nr, az_begin, az_end, u8, f32, n_threads, st)
+    finally:
+        if us is not None:
+            L.orc_set_uniform_stream(None, 0)
     if rc != 0:
         raise RuntimeError("orc_simulate failed: %d" % rc)
     stats = {k: getattr(st, k) for k, _ in OrcStats._fields_}
     return u8, f32, stats
+
+
+def _run_simulate(L, motion, scene, mats, materials, om, oc, bd, ps, nr, az_begin, az_end, u8, f32, n_threads, st):
+    return (L.orc_simulate_motion if motion else L.orc_simulate)(scene._h, mats, len(materials), om.ctypes.data, len(om), C.byref(oc),
+                        bd.ctypes.data, len(bd), ps.ctypes.data,
+                        None if nr is None else nr.ctypes.data,
+                        az_begin, az_end, u8.ctypes.data,
+                        None if f32 is None else f32.ctypes.data, n_threads, C.byref(st))

@@ -785,6 +785,17 @@ static inline float uniform01(uint32_t seed, uint32_t col, uint32_t i)
     return (float)(z >> 40) * (1.0f / 16777216.0f);
 }
 
+/* test hook (tests/test_oracle_refloop.py): when set, ambient_noise == 1 takes the variate of (azimuth, cell) from
+ * stream[azimuth * n_cells + cell] instead of uniform01, so that everything AROUND the stream -- which stays the build's
+ * own definition -- can be compared with the reference loop fed the same draws. */
+static const float* g_uniform_stream = NULL;
+static size_t g_uniform_stream_n = 0;
+void orc_set_uniform_stream(const float* stream, size_t n)
+{
+    g_uniform_stream = stream;
+    g_uniform_stream_n = stream ? n : 0;
+}
+
 static double now_s(void)
 {
     struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts);
@@ -1034,7 +1045,9 @@ static int simulate_impl(const orc_scene* scene,
                 float signal = slice[i];
                 double p = 0.0;
                 if (cfg->ambient_noise == 1) {
-                    p = (double)uniform01((uint32_t)(int32_t)rnd, (uint32_t)col, (uint32_t)i);
+                    const size_t k = (size_t)angle_id * (size_t)n_cells + (size_t)i;
+                    p = k < g_uniform_stream_n ? (double)g_uniform_stream[k]
+                                               : (double)uniform01((uint32_t)(int32_t)rnd, (uint32_t)col, (uint32_t)i);
                 } else if (cfg->ambient_noise == 2) {
                     double p1 = orc_perlin_noise(random_begin + (double)i * scale, (double)col * scale, 0.0);
                     double p2 = orc_perlin_noise(random_begin + (double)i * scale2, (double)col * scale2, 0.0);

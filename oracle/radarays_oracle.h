@@ -19,11 +19,11 @@
  *       cases of the BRDF lobe) and,
  *       for erfinvf/quantile, to oracle/_ref (the reference's own
  *       radar_math.h compiled as-is).
- *   loop glue (RadarCPU.cpp:156-548) and the ray cast (rmagine/Embree, not in
- *       /root/reference): PARITY UNPINNED -- the reference holds no test,
- *       fixture or golden image for them and cannot be built here (needs ROS,
- *       OpenCV, rmagine >= 2.2.1, Embree).  They are restated line by line
- *       with the quirks of SURVEY.md Appendix A.
+ *   loop glue (RadarCPU.cpp:156-548): pinned by the reference's own loop compiled against behaving stand-ins
+ *       (oracle/refshim/, oracle/ref_loop_wrap.cpp, `make ref`): tests/test_oracle_refloop.py asks this file for the
+ *       same mono8 bytes on whole sweeps and the same bits from every per-hit function.
+ *   the ray cast (rmagine/Embree, not in /root/reference), rmagine's conventions, OpenCV's arithmetic: PARITY
+ *       UNPINNED -- the build's statements, held in those stand-ins.
  */
 #ifndef RADARAYS_ORACLE_H
 #define RADARAYS_ORACLE_H
@@ -131,6 +131,10 @@ int orc_simulate_motion(const orc_scene*,
                  int az_begin, int az_end,
                  uint8_t* out_u8, float* out_f32,
                  int n_threads, orc_stats* stats);
+
+/* test hook: a caller-supplied variate stream [n_angles * n_cells] for ambient_noise == 1 (NULL: the build's own
+ * hash stream).  Not thread-safe against a running orc_simulate; set, simulate, clear. */
+void orc_set_uniform_stream(const float* stream, size_t n);
 
 /* ---- per-hit math, exported one by one for the known-answer tests ---- */
 
