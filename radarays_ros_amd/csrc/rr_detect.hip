@@ -15,6 +15,7 @@
 // Every value a call needs travels as a kernel argument; the kernels use no scratch and at most 64 KB of LDS.
 #include "../../include/radarays_mi355.h"
 #include "rr_device.h"
+#include "rr_launch.h"
 
 #include <algorithm>
 

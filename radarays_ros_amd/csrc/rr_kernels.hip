@@ -13,6 +13,7 @@
 // prefix-sum based (no atomics), so the signal list of an azimuth is in exactly
 // the reference's order and the image does not depend on scheduling.
 #include "rr_device.h"
+#include "rr_launch.h"
 #include <hip/hip_ext.h>
 
 #include <algorithm>
@@ -1565,7 +1566,7 @@ void launch_score(const uint8_t* imgs, const uint8_t* ref, size_t npx, int n_ima
 }
 
 // ---------------------------------------------------------------------------
-// launchers (called from rr_api.cpp through plain C++ prototypes)
+// launchers (declared in rr_launch.h)
 // ---------------------------------------------------------------------------
 // once per tree upload: builder references (node index / first triangle) -> float4 offsets from the
 // base of the tree allocation (rr_bvh.h)
@@ -1675,7 +1676,7 @@ void launch_trace(const Params& P, int pass, const PoseArgs* poses, bool stats, 
 }
 
 // the pass-0 trace kernel of the plain build (no statistics): the node of a replayed launch graph whose parameters change from
-// replay to replay -- (Params, pass, PoseArgs) -- see rr_api.hip: run_frame
+// replay to replay -- (Params, pass, PoseArgs) -- see rr_frame.hip: run_frame
 void* trace0_kernel(bool spill, bool stackless)
 {
     if (stackless) return (void*)k_trace<true, false, false, false, true>;

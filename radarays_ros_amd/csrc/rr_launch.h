@@ -1,0 +1,51 @@
+// rr_launch.h -- every launcher of rr_kernels.hip, rr_refit.hip, rr_detect.hip and rr_lbvh.hip, declared ONCE: included where they
+// are defined (a definition that drifts from its declaration fails there) and where they are called.  Default arguments live here only.
+#pragma once
+#include "../../include/radarays_mi355.h"
+#include "rr_device.h"
+#include <string>
+
+namespace rr {
+void launch_trace(const Params& P, int pass, const PoseArgs* poses, bool stats, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,
+                  hipEvent_t ev_rep_start = nullptr, hipEvent_t ev_rep_stop = nullptr, bool* repair_launched = nullptr);
+void launch_shade(const Params& P, int pass, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+void launch_scan(const Params& P, int pass, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+void launch_column(const Params& P, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+void launch_decay_table(float* decay, int n_cells, double resolution, double energy_loss, hipStream_t s);
+void launch_assemble_u8(const uint8_t* cols, uint8_t* img, int n_angles, int n_cells, int scroll, hipStream_t s,
+                        int n_loc = 0, size_t block_stride = 0, int n_frames = 1, size_t frame_stride = 0);
+void launch_assemble_f32(const float* cols, float* img, int n_angles, int n_cells, int scroll, hipStream_t s);
+bool build_bvh4_gpu(const float* verts, size_t nv, const uint32_t* faces, size_t nf, const uint32_t* face_object,
+                    Node4** d_nodes_out, size_t* n_nodes_out, TriRec** d_tris_out, size_t* n_tris_out,
+                    uint32_t* depth_out, uint32_t* stack_need_out, float* inflate_out,
+                    std::string& err, hipStream_t stream);
+void launch_debug_trace(const Params& P, const float* origs, const float* dirs, int n,
+                        float* out_t, uint32_t* out_face, hipStream_t s, unsigned long long* steps = nullptr);
+void launch_encode_refs(Node4* nodes, size_t n_nodes, uint32_t tri_base4, hipStream_t s, size_t n_tris);
+// rr_refit.hip (dynamic scenes)
+int refit_reduce_groups();
+void launch_refit_extent(const TriRec* tris, size_t n, const float* verts, const uint32_t* faces, const float* poses,
+                         float* out8, hipStream_t s);
+void launch_refit_tris(TriRec* tris, size_t n, const float* verts, const uint32_t* faces, const float* poses, hipStream_t s);
+void launch_refit_levels(float4* base4, const uint32_t* level_nodes, const uint32_t* level_off, int n_levels, float inflate,
+                         const float4* built4, const uint8_t* moved, float extra, hipStream_t s);
+void launch_tree_cost(const Node4* nodes, size_t n_nodes, double* out, hipStream_t s);
+void launch_gather_refs(const Node4* nodes, size_t n_nodes, uint32_t* out, hipStream_t s);
+void launch_pose_soup(const TriRec* tris, size_t n, const float* verts, const uint32_t* faces, const float* poses,
+                      float* soup, uint32_t* obj, hipStream_t s);
+void launch_mat_limits(const float4* materials, size_t n, double* limits, hipStream_t s);
+void* trace0_kernel(bool spill, bool stackless);
+void launch_score(const uint8_t* imgs, const uint8_t* ref, size_t npx, int n_images, unsigned long long* sse, hipStream_t s);
+// rr_detect.hip (point clouds and Cartesian images)
+void launch_detect(const uint8_t* imgs, int n_frames, const rr_detect_config& cfg, int n_cells, int n_angles, int scroll,
+                   float theta_min, float theta_inc, double resolution, rr_radar_point* points, int max_points,
+                   uint32_t* offsets, hipStream_t s);
+void launch_cartesian(const uint8_t* imgs, int n_frames, const rr_cartesian_config& cfg, int n_cells, int n_angles, int scroll,
+                      float theta_min, float theta_inc, float res, uint8_t* out, hipStream_t s);
+void launch_copy_host(const void* src, void* dst, size_t bytes, int blocks, int xcd, hipStream_t s);
+void launch_copy_words(const void* src, void* dst, size_t bytes, hipStream_t s);
+void launch_debug_brdf(size_t n, const float* in, int model, float* out, hipStream_t s);
+void launch_store_u32(const uint32_t* src, uint32_t* h_dst, hipStream_t s);
+void launch_debug_fresnel(size_t n, const float* normals, const float* dirs, const double* energy, const double* v1, const float* v2,
+                          float* out_rdir, double* out_re, float* out_tdir, double* out_te, hipStream_t s);
+}  // namespace rr

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "rr_bvh.h"
+#include "rr_launch.h"
 
 namespace rr {
 

@@ -17,6 +17,7 @@
 // Kernel boundaries order the levels: a level reads only boxes the previous launch wrote, so no workgroup waits for
 // another and no cross-XCD fence is needed inside a launch.  No kernel here uses scratch (tests/test_dynamic_host.py).
 #include "rr_device.h"
+#include "rr_launch.h"
 
 namespace rr {
 
@@ -214,7 +215,7 @@ inline unsigned grid_for(size_t n) { return (unsigned)((n + kRefitTB - 1) / kRef
 }  // namespace
 
 // ---------------------------------------------------------------------------
-// launchers (called from rr_api.hip through plain prototypes)
+// launchers (declared in rr_launch.h, called from rr_scene.hip)
 // ---------------------------------------------------------------------------
 constexpr int kRefitReduceGroups = 1024;    // workgroups of the two reductions (fixed: the sums are formed in a fixed order)
 int refit_reduce_groups() { return kRefitReduceGroups; }

@@ -10,7 +10,7 @@
 // directly: two worker threads per context take (event, device source, host destination, bytes) jobs in turn; for each, a
 // worker waits for the HIP event (the batch's assemble), submits the copy with a completion signal and waits for that signal.  A
 // copy is therefore ordered behind the kernels that produce the image by the event and ahead of the lane's next use by the
-// job's completion (rr_api.hip waits for it before it lets a lane's next batch overwrite the image).
+// job's completion (rr_frame.hip waits for it before it lets a lane's next batch overwrite the image).
 //
 // The HSA instance is never initialised here: the one the active HIP runtime initialised is looked up among the loaded
 // objects (a process can hold two copies of libhsa-runtime64 -- the wheel's and the system's -- of which only one is live)

@@ -1,6 +1,6 @@
 """Where does the host-image path lose time?  Target workload, 8 poses per batch, 4 streams.
 modes: dev = rr_simulate_batch_device (images stay in HBM); host = rr_simulate_batch_host_async.
-The variants listed in rr_api.hip (copy stream, zero-copy assemble, own copy kernel, copy folded into a trace launch)
+The variants listed in rr_frame.hip (copy stream, zero-copy assemble, own copy kernel, copy folded into a trace launch)
 were measured with this script; only the shipped one is left in the library."""
 import sys, os, time
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, R)
