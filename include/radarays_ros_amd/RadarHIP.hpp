@@ -8,6 +8,9 @@
 // ROS / OpenCV / rmagine types this image does not have: TF lookup becomes updateTsm(pose),
 // sensor_msgs::Image becomes the plain `Image` struct with the same fields, rm::Transform
 // becomes float[7] (quaternion xyzw + translation).  INTEGRATION.md shows the ROS-typed twin.
+// What the two classes do alike -- config copy, materials, beam draw, chunked batches, parameter sets -- is marshal.hpp,
+// which both include: the marshalling the ROS-typed adapter ships is the one the GPU demo executes through this class.
+// Here: the `Radar` base, the dirty flags, `Image`s, detect / toCartesian and how errors are reported.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -18,7 +21,7 @@
 #include <string>
 #include <vector>
 
-#include "../radarays_mi355.h"
+#include "marshal.hpp"
 
 namespace radarays_ros_amd {
 
@@ -144,13 +147,10 @@ public:
             return msg;
         }
         if (!push()) return msg;
-        msg = std::make_shared<Image>();
-        msg->height = (uint32_t)m_cfg.n_cells; msg->width = (uint32_t)m_n_angles; msg->step = msg->width;
-        msg->data.assign((size_t)msg->height * msg->width, 0);
+        msg = image(nullptr, stamp);
         if (rr_multi_device_count(m_multi) > 1) {
-            if (rr_multi_simulate(m_multi, Tsm_last, msg->data.data())) { msg.reset(); m_err = rr_multi_last_error(m_multi); std::cout << "[RadarHIP] " << m_err << std::endl; return {}; }
-        } else if (rr_simulate(m_ctx, Tsm_last, 0, m_n_angles, msg->data.data(), nullptr, &m_stats)) { msg.reset(); return fail(); }
-        msg->stamp = stamp; msg->frame_id = m_sensor_frame;   // RadarCPU.cpp:560-561
+            if (rr_multi_simulate(m_multi, Tsm_last, msg->data.data())) { mfail(); return {}; }
+        } else if (rr_simulate(m_ctx, Tsm_last, 0, m_n_angles, msg->data.data(), nullptr, &m_stats)) return fail();
         return msg;
     }
     // Offline generation (the twin of integration/src/radarays_ros/RadarHIP.cpp: simulateBatch / simulateSweeps): one image
@@ -173,18 +173,12 @@ public:
         std::vector<rr_material> flat;
         for (const auto& set : sets) {
             if (set.size() != n_mat) { m_err = "every material set needs as many entries as loadParams() gave"; return out; }
-            for (const RadarMaterial& m : set) flat.push_back({ m.velocity, m.ambient, m.diffuse, m.specular });
+            marshal::append_materials(flat, set.begin(), set.end());
         }
         const size_t npx = (size_t)m_cfg.n_cells * m_n_angles;
         std::vector<uint8_t> px(sets.size() * npx);
         if (rr_simulate_material_sets(m_ctx, Tsm_last, flat.data(), (int)sets.size(), n_mat, px.data())) { fail(); return out; }
-        for (size_t k = 0; k < sets.size(); k++) {
-            ImagePtr msg = std::make_shared<Image>();
-            msg->height = (uint32_t)m_cfg.n_cells; msg->width = (uint32_t)m_n_angles; msg->step = msg->width;
-            msg->data.assign(px.begin() + k * npx, px.begin() + (k + 1) * npx);
-            msg->stamp = stamp; msg->frame_id = m_sensor_frame;
-            out.push_back(msg);
-        }
+        for (size_t k = 0; k < sets.size(); k++) out.push_back(image(&px[k * npx], stamp));
         return out;
     }
     // The same action with the optimiser's WHOLE parameter vector (scripts/radaray_opti.py:36-113: model.beam_width,
@@ -203,34 +197,17 @@ public:
         const size_t n_mat = m_params.materials.size(), nb = m_params.model.n_samples;
         const size_t npx = (size_t)m_cfg.n_cells * m_n_angles;
         if (real && (real->data.size() != npx || !psnr)) { m_err = "the real image must be n_cells x n_angles mono8 (and psnr given)"; return false; }
-        std::vector<rr_material> flat; flat.reserve(sets.size() * n_mat);
-        std::vector<std::vector<float>> dirs(sets.size());
-        std::vector<rr_param_set> ps(sets.size());
-        const uint32_t seed = m_beam_seed;     // the seed push() drew the CURRENT beam with: sets that differ only in beam_width see the same variates
-        for (size_t k = 0; k < sets.size(); k++) {
-            const RadarParams& p = sets[k];
-            if (p.materials.size() != n_mat || p.model.n_samples != nb) { m_err = "every parameter set needs the loaded number of materials and the current n_samples"; return false; }
-            for (const RadarMaterial& m : p.materials) flat.push_back({ m.velocity, m.ambient, m.diffuse, m.specular });
-            if (std::abs(p.model.beam_width - m_params.model.beam_width) > 1e-7f) {
-                dirs[k].assign(3 * nb, 0.0f);
-                if (rr_sample_cone_local(seed, p.model.beam_width, nb, m_cfg.beam_sample_dist, (float)m_cfg.beam_sample_dist_normal_p_in_cone, dirs[k].data())) { m_err = "sample_cone_local failed"; return false; }
-            }
-            ps[k].n_reflections = (int32_t)p.model.n_reflections; ps[k].reserved_ = 0;
-        }
-        for (size_t k = 0; k < sets.size(); k++) { ps[k].materials = flat.data() + k * n_mat; ps[k].beam_dirs = dirs[k].empty() ? nullptr : dirs[k].data(); }
+        // any number of sets goes on to the library (the ROS-typed adapter refuses more than RR_MAX_BATCH itself); the seed is
+        // the one push() drew the CURRENT beam with
+        marshal::ParamSetBatch b;
+        if (!b.build(sets, [](const RadarParams& p) -> const auto& { return p.materials; }, n_mat, nb,
+                     m_params.model.beam_width, m_beam_seed, m_cfg.beam_sample_dist, (float)m_cfg.beam_sample_dist_normal_p_in_cone, m_err)) return false;
         std::vector<uint8_t> px(images ? sets.size() * npx : 0);
         if (psnr) psnr->assign(sets.size(), 0.0);
-        if (rr_simulate_param_sets(m_ctx, Tsm_last, ps.data(), (int)sets.size(), n_mat, images ? px.data() : nullptr,
-                                   real ? real->data.data() : nullptr, real ? psnr->data() : nullptr)) { fail(); return false; }
+        if (!b.run(m_ctx, Tsm_last, n_mat, images ? px.data() : nullptr, real ? real->data.data() : nullptr, real ? psnr->data() : nullptr)) { fail(); return false; }
         if (images) {
             images->clear();
-            for (size_t k = 0; k < sets.size(); k++) {
-                ImagePtr msg = std::make_shared<Image>();
-                msg->height = (uint32_t)m_cfg.n_cells; msg->width = (uint32_t)m_n_angles; msg->step = msg->width;
-                msg->data.assign(px.begin() + k * npx, px.begin() + (k + 1) * npx);
-                msg->stamp = stamp; msg->frame_id = m_sensor_frame;
-                images->push_back(msg);
-            }
+            for (size_t k = 0; k < sets.size(); k++) images->push_back(image(&px[k * npx], stamp));
         }
         return true;
     }
@@ -277,67 +254,39 @@ private:
         if (!push()) return out;
         const size_t per = sweeps ? 7 * (size_t)m_n_angles : 7;
         if (poses.empty() || poses.size() % per) { m_err = "poses must be [n][7] (sweeps: [n][n_angles][7])"; return out; }
-        const size_t n_total = poses.size() / per, npx = (size_t)m_cfg.n_cells * m_n_angles;
-        std::vector<uint8_t> px((size_t)RR_MAX_BATCH * npx);
-        std::vector<float> first;
-        for (size_t at = 0; at < n_total; at += RR_MAX_BATCH) {
-            const size_t n = std::min(n_total - at, (size_t)RR_MAX_BATCH);
-            const float* p = poses.data() + at * per;
-            if (sweeps) {      // table k of the call = the per-azimuth poses of its frame k; the pose arguments are ignored but must be valid
-                first.clear();
-                for (size_t k = 0; k < n; k++) first.insert(first.end(), p + k * per, p + k * per + 7);
-                if (rr_multi_set_motion_poses(m_multi, p, n * (size_t)m_n_angles)) { mfail(); break; }
-            } else if (rr_multi_set_motion_poses(m_multi, nullptr, 0)) { mfail(); break; }
-            if (rr_multi_simulate_batch(m_multi, sweeps ? first.data() : p, (int)n, px.data())) { mfail(); break; }
-            for (size_t k = 0; k < n; k++) {
-                ImagePtr msg = std::make_shared<Image>();
-                msg->height = (uint32_t)m_cfg.n_cells; msg->width = (uint32_t)m_n_angles; msg->step = msg->width;
-                msg->data.assign(px.begin() + k * npx, px.begin() + (k + 1) * npx);
-                msg->stamp = stamp; msg->frame_id = m_sensor_frame;
-                out.push_back(msg);
-            }
-        }
+        // on an error: the frames of the chunks before it are kept, and the text is reported whichever call failed
+        if (!marshal::render_chunks(m_multi, poses.data(), poses.size() / per, sweeps, m_n_angles, (size_t)m_cfg.n_cells * m_n_angles,
+                                    [&](const uint8_t* px, size_t) { out.push_back(image(px, stamp)); })) mfail();
         m_push_motion = true;      // simulate() re-installs its own table (or none)
         return out;
+    }
+    // n_cells x n_angles mono8 as RadarCPU.cpp:555-561 fills it; px null: zeros, to be rendered into
+    ImagePtr image(const uint8_t* px, double stamp) const
+    {
+        ImagePtr msg = std::make_shared<Image>();
+        msg->height = (uint32_t)m_cfg.n_cells; msg->width = (uint32_t)m_n_angles; msg->step = msg->width;
+        const size_t npx = (size_t)msg->height * msg->width;
+        if (px) msg->data.assign(px, px + npx); else msg->data.assign(npx, 0);
+        msg->stamp = stamp; msg->frame_id = m_sensor_frame;
+        return msg;
     }
     // marshal the protected state of Radar into the context (what simulate() reads, Radar.hpp:66-105)
     bool push()
     {
         if (m_resample || m_waves_start.empty()) {    // RadarCPU.cpp:136-145
-            const size_t n = m_params.model.n_samples;
-            m_waves_start.assign(3 * n, 0.0f);
             // the reference seeds every re-draw from std::random_device (radar_algorithms.cpp:258-259); so does this, unless
             // setBeamSeed fixed one -- and the seed that was USED is kept, so that a parameter batch can repeat the draw for
             // other beam widths on the same variates (advisor, round 4)
             if (!m_have_seed) m_beam_seed = (uint32_t)std::random_device{}();
-            const uint32_t seed = m_beam_seed;
-            if (rr_sample_cone_local(seed, m_params.model.beam_width, n, m_cfg.beam_sample_dist,
-                                     (float)m_cfg.beam_sample_dist_normal_p_in_cone, m_waves_start.data())) {
+            if (!marshal::draw_beam(m_beam_seed, m_params.model.beam_width, m_params.model.n_samples, m_cfg.beam_sample_dist,
+                                    (float)m_cfg.beam_sample_dist_normal_p_in_cone, m_waves_start)) {
                 m_err = "sample_cone_local: beam_sample_dist must be 0..3"; std::cout << "[RadarHIP] " << m_err << std::endl; return false;
             }
             m_resample = false; m_push_beams = true;
         }
         if (m_dirty_cfg) {
-            rr_config c; rr_default_config(&c);
-            c.n_cells = m_cfg.n_cells; c.n_reflections = (int)m_params.model.n_reflections;
-            c.signal_denoising = m_cfg.signal_denoising;
-            c.signal_denoising_triangular_width = m_cfg.signal_denoising_triangular_width;
-            c.signal_denoising_triangular_mode = m_cfg.signal_denoising_triangular_mode;
-            c.signal_denoising_gaussian_width = m_cfg.signal_denoising_gaussian_width;
-            c.signal_denoising_gaussian_mode = m_cfg.signal_denoising_gaussian_mode;
-            c.signal_denoising_mb_width = m_cfg.signal_denoising_mb_width;
-            c.signal_denoising_mb_mode = m_cfg.signal_denoising_mb_mode;
-            c.ambient_noise = m_cfg.ambient_noise; c.scroll_image = m_cfg.scroll_image;
-            c.record_multi_reflection = m_cfg.record_multi_reflection; c.record_multi_path = m_cfg.record_multi_path;
-            c.multipath_threshold = m_cfg.multipath_threshold;
-            c.resolution = m_cfg.resolution; c.energy_max = m_cfg.energy_max; c.signal_max = m_cfg.signal_max;
-            c.ambient_noise_at_signal_0 = m_cfg.ambient_noise_at_signal_0;
-            c.ambient_noise_at_signal_1 = m_cfg.ambient_noise_at_signal_1;
-            c.ambient_noise_energy_max = m_cfg.ambient_noise_energy_max;
-            c.ambient_noise_energy_min = m_cfg.ambient_noise_energy_min;
-            c.ambient_noise_energy_loss = m_cfg.ambient_noise_energy_loss;
-            c.wave_energy_threshold = m_wave_energy_threshold;
-            c.range_max = 1000.0f;                  // make_model: range.max of the OnDn model (radar_algorithms.cpp:158)
+            rr_config c;       // n_angles / theta_min / theta_inc: the defaults
+            marshal::fill_config(c, m_cfg, (int)m_params.model.n_reflections, m_wave_energy_threshold);
             if (rr_multi_set_config(m_multi, &c)) { mfail(); return false; }
             m_n_angles = c.n_angles; m_dirty_cfg = false; m_push_motion = true;
         }
@@ -347,12 +296,9 @@ private:
             m_push_motion = false;
         }
         if (m_dirty_mat) {
-            std::vector<rr_material> mats(m_params.materials.size());
-            for (size_t i = 0; i < mats.size(); i++) {
-                const RadarMaterial& m = m_params.materials[i];
-                mats[i] = { m.velocity, m.ambient, m.diffuse, m.specular };
-            }
-            std::vector<int32_t> om(m_object_materials.begin(), m_object_materials.end());
+            std::vector<rr_material> mats;
+            marshal::append_materials(mats, m_params.materials.begin(), m_params.materials.end());
+            const std::vector<int32_t> om = marshal::object_material_ids(m_object_materials);
             if (rr_multi_set_materials(m_multi, mats.data(), mats.size(), om.data(), om.size(), m_material_id_air)) { mfail(); return false; }
             m_dirty_mat = false;
         }

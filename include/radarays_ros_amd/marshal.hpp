@@ -1,0 +1,133 @@
+// marshal.hpp -- the marshalling between the state of a `Radar` object and the C ABI, stated once.
+//
+// Both C++ classes named RadarHIP use it: the ROS-free one (RadarHIP.hpp next to this file) and the ROS-typed adapter
+// (integration/src/radarays_ros/RadarHIP.cpp).  The adapter cannot be built or run without ROS, so what runs on the GPU
+// under tests/cpp/radar_hip_demo.cpp is this header, instantiated with the plain structs of the ROS-free class; the adapter
+// instantiates the same templates with catkin's generated types.  No ROS / OpenCV / rmagine types, nothing is printed:
+// a failure comes back as `false` (and a reason where there is a choice), each class reports it its own way.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../radarays_mi355.h"
+
+namespace radarays_ros_amd::marshal {
+
+// cfg/RadarModel.cfg fields + the constants of Radar::Radar (Radar.cpp:22-32) -> rr_config.  Cfg: the dynamic-reconfigure
+// struct (generated or plain).  n_angles / theta_min / theta_inc keep rr_default_config's values: the caller's to set.
+template <typename Cfg>
+void fill_config(rr_config& c, const Cfg& cfg, int n_reflections, float wave_energy_threshold)
+{
+    rr_default_config(&c);
+    c.n_cells = cfg.n_cells;
+    c.n_reflections = n_reflections;
+    c.signal_denoising = cfg.signal_denoising;
+    c.signal_denoising_triangular_width = cfg.signal_denoising_triangular_width;
+    c.signal_denoising_triangular_mode = cfg.signal_denoising_triangular_mode;
+    c.signal_denoising_gaussian_width = cfg.signal_denoising_gaussian_width;
+    c.signal_denoising_gaussian_mode = cfg.signal_denoising_gaussian_mode;
+    c.signal_denoising_mb_width = cfg.signal_denoising_mb_width;
+    c.signal_denoising_mb_mode = cfg.signal_denoising_mb_mode;
+    c.ambient_noise = cfg.ambient_noise;
+    c.scroll_image = cfg.scroll_image;
+    c.record_multi_reflection = cfg.record_multi_reflection;
+    c.record_multi_path = cfg.record_multi_path;
+    c.multipath_threshold = cfg.multipath_threshold;
+    c.resolution = cfg.resolution;
+    c.energy_max = cfg.energy_max;
+    c.signal_max = cfg.signal_max;
+    c.ambient_noise_at_signal_0 = cfg.ambient_noise_at_signal_0;
+    c.ambient_noise_at_signal_1 = cfg.ambient_noise_at_signal_1;
+    c.ambient_noise_energy_max = cfg.ambient_noise_energy_max;
+    c.ambient_noise_energy_min = cfg.ambient_noise_energy_min;
+    c.ambient_noise_energy_loss = cfg.ambient_noise_energy_loss;
+    c.wave_energy_threshold = wave_energy_threshold;
+    c.range_max = 1000.0f;     // make_model gives every pass's OnDn model range [0, 1000] (radar_algorithms.cpp:157-158)
+}
+
+// RadarMaterial (msg/RadarMaterial.msg, or the plain struct) -> rr_material, appended
+template <typename It>
+void append_materials(std::vector<rr_material>& out, It first, It last)
+{
+    for (; first != last; ++first) {
+        const auto& m = *first;
+        out.push_back({ m.velocity, m.ambient, m.diffuse, m.specular });
+    }
+}
+// m_object_materials (Radar.hpp:97) as the ABI takes it
+inline std::vector<int32_t> object_material_ids(const std::vector<int>& ids) { return { ids.begin(), ids.end() }; }
+
+// sample_cone_local (RadarCPU.cpp:136-145) on a given seed: dirs = [n_samples][3].  Where the seed comes from is the
+// caller's policy; false: beam_sample_dist is not one of 0..3
+inline bool draw_beam(uint32_t seed, float beam_width, size_t n_samples, int dist, float p_in_cone, std::vector<float>& dirs)
+{
+    dirs.assign(3 * n_samples, 0.0f);
+    return rr_sample_cone_local(seed, beam_width, n_samples, dist, p_in_cone, dirs.data()) == 0;
+}
+
+// Offline generation: n_frames frames in chunks of RR_MAX_BATCH, one set of launches per chunk.  poses = [n_frames][7], or
+// with `sweeps` [n_frames][n_angles][7] (include_motion, RadarCPU.cpp:190-196): row k of a chunk's table = the per-azimuth
+// poses of its frame k.  emit(pixels, frame) is called once per finished frame, pixels = npx bytes valid during the call.
+// Returns whether it ran to the end; if not, rr_multi_last_error(m) says why.  A sweep table stays installed afterwards.
+template <typename Emit>
+bool render_chunks(rr_multi* m, const float* poses, size_t n_frames, bool sweeps, int n_angles, size_t npx, Emit emit)
+{
+    const size_t per = sweeps ? 7 * (size_t)n_angles : 7;
+    std::vector<uint8_t> px((size_t)RR_MAX_BATCH * npx);
+    std::vector<float> first;
+    for (size_t at = 0; at < n_frames; at += RR_MAX_BATCH) {
+        const size_t n = std::min(n_frames - at, (size_t)RR_MAX_BATCH);
+        const float* p = poses + at * per;
+        if (sweeps) {      // the pose arguments are ignored while a table is set, but must be valid: each frame's first pose
+            first.clear();
+            for (size_t k = 0; k < n; k++) first.insert(first.end(), p + k * per, p + k * per + 7);
+            if (rr_multi_set_motion_poses(m, p, n * (size_t)n_angles)) return false;
+        } else if (rr_multi_set_motion_poses(m, nullptr, 0)) return false;
+        if (rr_multi_simulate_batch(m, sweeps ? first.data() : p, (int)n, px.data())) return false;
+        for (size_t k = 0; k < n; k++) emit(px.data() + k * npx, at + k);
+    }
+    return true;
+}
+
+// The optimiser's parameter vectors (scripts/radaray_opti.py:36-113) as rr_simulate_param_sets takes them; owns what the
+// rr_param_set array points into
+struct ParamSetBatch {
+    std::vector<rr_material> mats;            // [n_sets][n_mat]
+    std::vector<std::vector<float>> dirs;     // per set: empty = the current beam, else its own draw
+    std::vector<rr_param_set> ps;
+
+    // sets: RadarParams-like (.model.beam_width / .n_samples / .n_reflections); materials_of(set) gives its material list.
+    // Every set needs n_mat materials and n_beam samples.  A set whose beam_width differs from the current one gets its
+    // own draw on `seed` -- the seed of the current beam, so that sets which differ only in beam_width share their variates
+    template <typename Sets, typename MaterialsOf>
+    bool build(const Sets& sets, MaterialsOf materials_of, size_t n_mat, size_t n_beam, float current_beam_width,
+               uint32_t seed, int dist, float p_in_cone, std::string& why)
+    {
+        mats.clear(); dirs.clear(); ps.clear();
+        dirs.resize(sets.size()); ps.resize(sets.size());
+        for (size_t k = 0; k < sets.size(); k++) {
+            const auto& p = sets[k];
+            const auto& list = materials_of(p);
+            if (list.size() != n_mat || p.model.n_samples != n_beam) { why = "every parameter set needs the loaded number of materials and the current n_samples"; return false; }
+            append_materials(mats, list.begin(), list.end());
+            if (std::abs(p.model.beam_width - current_beam_width) > 1e-7f &&
+                !draw_beam(seed, p.model.beam_width, n_beam, dist, p_in_cone, dirs[k])) { why = "sample_cone_local failed"; return false; }
+            ps[k].n_reflections = (int32_t)p.model.n_reflections; ps[k].reserved_ = 0;
+        }
+        for (size_t k = 0; k < sets.size(); k++) {      // only now: mats no longer moves
+            ps[k].materials = mats.data() + k * n_mat;
+            ps[k].beam_dirs = dirs[k].empty() ? nullptr : dirs[k].data();
+        }
+        return true;
+    }
+    // one pose -> ps.size() images [n_sets][npx] and / or their PSNR against `real` (each may be null); false: rr_last_error(ctx)
+    bool run(rr_ctx* ctx, const float pose[7], size_t n_mat, uint8_t* pixels, const uint8_t* real, double* psnr) const
+    {
+        return rr_simulate_param_sets(ctx, pose, ps.data(), (int)ps.size(), n_mat, pixels, real, psnr) == 0;
+    }
+};
+
+}  // namespace radarays_ros_amd::marshal

@@ -7,8 +7,9 @@
 // This file and src/radarays_ros/RadarHIP.cpp are copied into the reference tree by integration/apply.py, which also applies
 // the line-anchored insertions of integration/patches/*.json to src/radar_simulator.cpp and CMakeLists.txt.  They need ROS 1,
 // cv_bridge and rmagine's math types (what Radar.hpp itself includes) and are therefore NOT compiled in the image this
-// repository is developed in; its ROS-free twin (include/radarays_ros_amd/RadarHIP.hpp, same marshalling member for member)
-// is compiled and tested on the GPU against the oracle.
+// repository is developed in.  The marshalling itself (config copy, materials, beam draw, chunked batches, parameter sets)
+// is include/radarays_ros_amd/marshal.hpp, shared with the ROS-free twin (include/radarays_ros_amd/RadarHIP.hpp), which is
+// compiled and tested on the GPU against the oracle: what runs there is the code this class calls.
 
 #include "Radar.hpp"
 

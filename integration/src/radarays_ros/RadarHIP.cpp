@@ -2,6 +2,8 @@
 
 #include <cv_bridge/cv_bridge.h>
 
+// config copy, materials, beam draw, chunked batches, parameter sets: shared with the ROS-free class, which the GPU tests run
+#include <radarays_ros_amd/marshal.hpp>
 
 #include <cmath>
 #include <cstring>
@@ -9,6 +11,7 @@
 #include <stdexcept>
 
 namespace rm = rmagine;
+namespace marshal = radarays_ros_amd::marshal;
 
 namespace radarays_ros
 {
@@ -151,34 +154,10 @@ bool RadarHIP::pushState()
 {
     // ---- m_cfg + m_params.model + the constants of Radar::Radar (Radar.cpp:22-32) -> rr_config ----
     rr_config c;
-    rr_default_config(&c);
-    c.n_cells = m_cfg.n_cells;
+    marshal::fill_config(c, m_cfg, m_params.model.n_reflections, m_wave_energy_threshold);
     c.n_angles = m_radar_model.theta.size;
-    c.n_reflections = m_params.model.n_reflections;
-    c.signal_denoising = m_cfg.signal_denoising;
-    c.signal_denoising_triangular_width = m_cfg.signal_denoising_triangular_width;
-    c.signal_denoising_triangular_mode = m_cfg.signal_denoising_triangular_mode;
-    c.signal_denoising_gaussian_width = m_cfg.signal_denoising_gaussian_width;
-    c.signal_denoising_gaussian_mode = m_cfg.signal_denoising_gaussian_mode;
-    c.signal_denoising_mb_width = m_cfg.signal_denoising_mb_width;
-    c.signal_denoising_mb_mode = m_cfg.signal_denoising_mb_mode;
-    c.ambient_noise = m_cfg.ambient_noise;
-    c.scroll_image = m_cfg.scroll_image;
-    c.record_multi_reflection = m_cfg.record_multi_reflection;
-    c.record_multi_path = m_cfg.record_multi_path;
-    c.multipath_threshold = m_cfg.multipath_threshold;
-    c.resolution = m_cfg.resolution;
-    c.energy_max = m_cfg.energy_max;
-    c.signal_max = m_cfg.signal_max;
-    c.ambient_noise_at_signal_0 = m_cfg.ambient_noise_at_signal_0;
-    c.ambient_noise_at_signal_1 = m_cfg.ambient_noise_at_signal_1;
-    c.ambient_noise_energy_max = m_cfg.ambient_noise_energy_max;
-    c.ambient_noise_energy_min = m_cfg.ambient_noise_energy_min;
-    c.ambient_noise_energy_loss = m_cfg.ambient_noise_energy_loss;
-    c.wave_energy_threshold = m_wave_energy_threshold;
     c.theta_min = m_radar_model.theta.min;
     c.theta_inc = m_radar_model.theta.inc;
-    c.range_max = 1000.0f;     // make_model gives every pass's OnDn model range [0, 1000] (radar_algorithms.cpp:157-158)
     if(rr_multi_set_config(m_multi, &c))
     {
         fail();
@@ -187,16 +166,9 @@ bool RadarHIP::pushState()
     m_n_angles = c.n_angles;
 
     // ---- materials, re-read from the parameter server before every frame by the node (radar_simulator.cpp:85,200) ----
-    std::vector<rr_material> mats(m_params.materials.data.size());
-    for(size_t i = 0; i < mats.size(); i++)
-    {
-        const RadarMaterial& m = m_params.materials.data[i];
-        mats[i].velocity = m.velocity;
-        mats[i].ambient = m.ambient;
-        mats[i].diffuse = m.diffuse;
-        mats[i].specular = m.specular;
-    }
-    std::vector<int32_t> object_materials(m_object_materials.begin(), m_object_materials.end());
+    std::vector<rr_material> mats;
+    marshal::append_materials(mats, m_params.materials.data.begin(), m_params.materials.data.end());
+    const std::vector<int32_t> object_materials = marshal::object_material_ids(m_object_materials);
     if(rr_multi_set_materials(m_multi, mats.data(), mats.size(), object_materials.data(), object_materials.size(), m_material_id_air))
     {
         fail();
@@ -209,9 +181,9 @@ bool RadarHIP::pushState()
         // the reference's sample_cone_local seeds itself from std::random_device (radar_algorithms.cpp:258-259); the seeded
         // twin of the library draws the same distribution and lets parameter batches repeat the draw for other widths
         m_beam_seed = std::random_device()();
-        std::vector<float> dirs(3 * (size_t)m_params.model.n_samples);
-        if(rr_sample_cone_local(m_beam_seed, m_params.model.beam_width, m_params.model.n_samples, m_cfg.beam_sample_dist,
-                                m_cfg.beam_sample_dist_normal_p_in_cone, dirs.data()))
+        std::vector<float> dirs;
+        if(!marshal::draw_beam(m_beam_seed, m_params.model.beam_width, m_params.model.n_samples, m_cfg.beam_sample_dist,
+                               m_cfg.beam_sample_dist_normal_p_in_cone, dirs))
         {
             ROS_WARN_STREAM("[RadarHIP] beam_sample_dist " << m_cfg.beam_sample_dist << " is not one of 0..3");
             return false;
@@ -349,29 +321,19 @@ sensor_msgs::ImagePtr RadarHIP::simulate(ros::Time stamp)
 std::vector<sensor_msgs::ImagePtr> RadarHIP::simulateBatch(const std::vector<rm::Transform>& poses, ros::Time stamp)
 {
     std::vector<sensor_msgs::ImagePtr> out;
-    if(!pushState() || rr_multi_set_motion_poses(m_multi, nullptr, 0))
+    if(!pushState() || rr_multi_set_motion_poses(m_multi, nullptr, 0))     // a table that cannot be cleared: no warning here
     {
         return out;
     }
-    const size_t npx = (size_t)m_cfg.n_cells * m_n_angles;
-    std::vector<unsigned char> pixels((size_t)RR_MAX_BATCH * npx);
-    std::vector<float> flat(7 * (size_t)RR_MAX_BATCH);
-    for(size_t first = 0; first < poses.size(); first += RR_MAX_BATCH)
+    std::vector<float> flat(7 * poses.size());
+    for(size_t k = 0; k < poses.size(); k++)
     {
-        const size_t n = std::min(poses.size() - first, (size_t)RR_MAX_BATCH);
-        for(size_t k = 0; k < n; k++)
-        {
-            to_pose7(poses[first + k], &flat[7 * k]);
-        }
-        if(rr_multi_simulate_batch(m_multi, flat.data(), (int)n, pixels.data()))
-        {
-            fail();
-            return out;
-        }
-        for(size_t k = 0; k < n; k++)
-        {
-            out.push_back(wrap(&pixels[k * npx], stamp));
-        }
+        to_pose7(poses[k], &flat[7 * k]);
+    }
+    if(!marshal::render_chunks(m_multi, flat.data(), poses.size(), false, m_n_angles, (size_t)m_cfg.n_cells * m_n_angles,
+                               [&](const uint8_t* pixels, size_t) { out.push_back(wrap(pixels, stamp)); }))
+    {
+        fail();
     }
     return out;
 }
@@ -383,38 +345,23 @@ std::vector<sensor_msgs::ImagePtr> RadarHIP::simulateSweeps(const std::vector<st
     {
         return out;
     }
-    const size_t npx = (size_t)m_cfg.n_cells * m_n_angles;
-    std::vector<unsigned char> pixels((size_t)RR_MAX_BATCH * npx);
-    std::vector<float> table, flat;
-    for(size_t first = 0; first < sweeps.size(); first += RR_MAX_BATCH)
+    std::vector<float> table(sweeps.size() * 7 * (size_t)m_n_angles);
+    for(size_t k = 0; k < sweeps.size(); k++)
     {
-        const size_t n = std::min(sweeps.size() - first, (size_t)RR_MAX_BATCH);
-        table.assign(n * 7 * (size_t)m_n_angles, 0.0f);
-        flat.assign(7 * n, 0.0f);
-        for(size_t k = 0; k < n; k++)
+        if(sweeps[k].size() != (size_t)m_n_angles)
         {
-            if(sweeps[first + k].size() != (size_t)m_n_angles)
-            {
-                ROS_WARN_STREAM("[RadarHIP] a sweep needs one pose per azimuth (" << m_n_angles << ")");
-                return out;
-            }
-            for(int a = 0; a < m_n_angles; a++)
-            {
-                to_pose7(sweeps[first + k][a], &table[(k * m_n_angles + a) * 7]);
-            }
-            to_pose7(sweeps[first + k][0], &flat[7 * k]);     // ignored while a table is set, but must be a valid pose
+            ROS_WARN_STREAM("[RadarHIP] a sweep needs one pose per azimuth (" << m_n_angles << ")");
+            return out;
         }
-        // row k of the table = the per-azimuth poses of frame k of the batch
-        if(rr_multi_set_motion_poses(m_multi, table.data(), n * (size_t)m_n_angles)
-           || rr_multi_simulate_batch(m_multi, flat.data(), (int)n, pixels.data()))
+        for(int a = 0; a < m_n_angles; a++)
         {
-            fail();
-            break;
+            to_pose7(sweeps[k][a], &table[(k * m_n_angles + a) * 7]);
         }
-        for(size_t k = 0; k < n; k++)
-        {
-            out.push_back(wrap(&pixels[k * npx], stamp));
-        }
+    }
+    if(!marshal::render_chunks(m_multi, table.data(), sweeps.size(), true, m_n_angles, (size_t)m_cfg.n_cells * m_n_angles,
+                               [&](const uint8_t* pixels, size_t) { out.push_back(wrap(pixels, stamp)); }))
+    {
+        fail();
     }
     rr_multi_set_motion_poses(m_multi, nullptr, 0);
     return out;
@@ -445,44 +392,13 @@ bool RadarHIP::simulateParamSets(const std::vector<RadarParams>& sets, ros::Time
         ROS_WARN_STREAM("[RadarHIP] the real image must be n_cells x n_angles mono8 (and psnr given)");
         return false;
     }
-    std::vector<rr_material> mats;
-    mats.reserve(sets.size() * n_mat);
-    std::vector<std::vector<float> > dirs(sets.size());
-    std::vector<rr_param_set> ps(sets.size());
-    for(size_t k = 0; k < sets.size(); k++)
+    marshal::ParamSetBatch batch;
+    std::string why;
+    if(!batch.build(sets, [](const RadarParams& p) -> const auto& { return p.materials.data; }, n_mat, n_beam,
+                    m_params.model.beam_width, m_beam_seed, m_cfg.beam_sample_dist, m_cfg.beam_sample_dist_normal_p_in_cone, why))
     {
-        const RadarParams& p = sets[k];
-        if(p.materials.data.size() != n_mat || p.model.n_samples != n_beam)
-        {
-            ROS_WARN_STREAM("[RadarHIP] every parameter set needs the loaded number of materials and the current n_samples");
-            return false;
-        }
-        for(size_t i = 0; i < n_mat; i++)
-        {
-            rr_material m;
-            m.velocity = p.materials.data[i].velocity;
-            m.ambient = p.materials.data[i].ambient;
-            m.diffuse = p.materials.data[i].diffuse;
-            m.specular = p.materials.data[i].specular;
-            mats.push_back(m);
-        }
-        if(std::abs(p.model.beam_width - m_params.model.beam_width) > 1e-7f)
-        {
-            // same seed as the current beam: sets that differ only in beam_width see the same variates
-            dirs[k].assign(3 * n_beam, 0.0f);
-            if(rr_sample_cone_local(m_beam_seed, p.model.beam_width, n_beam, m_cfg.beam_sample_dist,
-                                    m_cfg.beam_sample_dist_normal_p_in_cone, dirs[k].data()))
-            {
-                return false;
-            }
-        }
-        ps[k].n_reflections = (int32_t)p.model.n_reflections;
-        ps[k].reserved_ = 0;
-    }
-    for(size_t k = 0; k < sets.size(); k++)
-    {
-        ps[k].materials = &mats[k * n_mat];
-        ps[k].beam_dirs = dirs[k].empty() ? nullptr : dirs[k].data();
+        ROS_WARN_STREAM("[RadarHIP] " << why);
+        return false;
     }
     std::vector<unsigned char> pixels(images ? sets.size() * npx : 0);
     if(psnr)
@@ -491,8 +407,8 @@ bool RadarHIP::simulateParamSets(const std::vector<RadarParams>& sets, ros::Time
     }
     float pose[7];
     to_pose7(Tsm_last, pose);
-    if(rr_simulate_param_sets(m_ctx, pose, ps.data(), (int)sets.size(), n_mat, images ? pixels.data() : nullptr,
-                              real ? real->data.data() : nullptr, real ? psnr->data() : nullptr))
+    if(!batch.run(m_ctx, pose, n_mat, images ? pixels.data() : nullptr, real ? real->data.data() : nullptr,
+                  real ? psnr->data() : nullptr))
     {
         ROS_WARN_STREAM("[RadarHIP] " << rr_last_error(m_ctx));
         return false;

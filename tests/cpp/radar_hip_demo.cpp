@@ -86,6 +86,26 @@ int main(int argc, char** argv)
             for (int k = 0; k < 3; k++) if (s3[k]->data != b3[k]->data) { std::fprintf(stderr, "simulateSweeps: frame %d differs from simulateBatch\n", k); return 20; }
             ImagePtr img4 = multi.simulate(42.5);                 // simulate() re-installs ITS sweep table
             if (!img4 || img4->data != img->data) { std::fprintf(stderr, "simulate() after simulateSweeps differs\n"); return 21; }
+            // across a chunk boundary: RR_MAX_BATCH + 1 frames are two sets of launches; the first frame of the first chunk and
+            // the only frame of the second are `pose`, the frames in between are not
+            const size_t nf = (size_t)RR_MAX_BATCH + 1;
+            std::vector<float> many;
+            for (size_t k = 0; k < nf; k++) {
+                many.insert(many.end(), pose.begin(), pose.end());
+                if (k % RR_MAX_BATCH) many[7 * k + 4] += 0.25f * (float)(1 + k % 4);
+            }
+            multi.updateDynCfg(cfg);
+            std::vector<ImagePtr> bn = multi.simulateBatch(many, 52.0);
+            if (bn.size() != nf) { std::fprintf(stderr, "simulateBatch over a chunk boundary: %zu images (%s)\n", bn.size(), multi.lastError().c_str()); return 22; }
+            if (bn[0]->data != img->data || bn[nf - 1]->data != img->data || bn[1]->data == bn[0]->data) {
+                std::fprintf(stderr, "simulateBatch over a chunk boundary: frames 0 and %zu must be the simulate() image, frame 1 another\n", nf - 1); return 22;
+            }
+            std::vector<float> sweepsn;
+            for (size_t k = 0; k < nf; k++) for (int a = 0; a < 400; a++) sweepsn.insert(sweepsn.end(), many.begin() + 7 * k, many.begin() + 7 * k + 7);
+            multi.updateDynCfg(cm);
+            std::vector<ImagePtr> sn = multi.simulateSweeps(sweepsn, 53.0);
+            if (sn.size() != nf) { std::fprintf(stderr, "simulateSweeps over a chunk boundary: %zu images (%s)\n", sn.size(), multi.lastError().c_str()); return 22; }
+            for (size_t k = 0; k < nf; k++) if (sn[k]->data != bn[k]->data) { std::fprintf(stderr, "simulateSweeps over a chunk boundary: frame %zu differs from simulateBatch\n", k); return 22; }
         }
         // the optimiser's evaluation, batched (radaray_opti.py): three RadarParams -- the current ones, a narrower beam with
         // two passes, other materials with one pass -- as images and as scores against the first image

@@ -20,6 +20,8 @@ sys.path.insert(0, os.path.join(ROOT, "integration"))
 import apply as integ  # noqa: E402
 
 needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference checkout is not on this machine")
+# the marshalling the adapter shares with its ROS-free twin: the adapter includes it, so its text counts as the adapter's
+MARSHAL = "../include/radarays_ros_amd/marshal.hpp"
 
 
 def strip_cpp(text):
@@ -192,12 +194,15 @@ def test_every_abi_call_of_the_adapter_matches_the_header():
     protos = header_prototypes()
     assert len(protos) >= 60
     seen = set()
-    for rel in integ.NEW_FILES + ["../include/radarays_ros_amd/RadarHIP.hpp", "../tests/cpp/radar_hip_demo.cpp"]:
+    adapter = integ.NEW_FILES + [MARSHAL]
+    for rel in adapter + ["../include/radarays_ros_amd/RadarHIP.hpp", "../tests/cpp/radar_hip_demo.cpp"]:
         for name, n in calls_of(open(os.path.join(ROOT, "integration", rel)).read()):
             assert name in protos, "%s: %s is not in radarays_mi355.h" % (rel, name)
             assert protos[name] == n, "%s: %s called with %d arguments, declared with %d" % (rel, name, n, protos[name])
-            seen.add(name)
-    # the ROS-typed adapter drives the multi-device object, the batch and the parameter-set entry points
+            if rel in adapter:
+                seen.add(name)
+    # the ROS-typed adapter, with the marshalling header it includes, drives the multi-device object, the batch and the
+    # parameter-set entry points
     assert {"rr_create_multi", "rr_multi_set_mesh", "rr_multi_set_mesh_gpu", "rr_multi_set_config", "rr_multi_set_materials",
             "rr_multi_set_beam_samples", "rr_multi_set_noise_offsets", "rr_multi_set_motion_poses", "rr_multi_simulate",
             "rr_multi_simulate_batch", "rr_simulate_param_sets", "rr_sample_cone_local", "rr_load_mesh_file", "rr_free_mesh",
@@ -210,7 +215,12 @@ def test_adapter_reads_only_what_the_reference_declares(tree):
     hpp = strip_cpp(open(os.path.join(tree, "include", "radarays_ros", "RadarHIP.hpp")).read())
     # dynamic-reconfigure fields: gen.add("<name>", ...) of cfg/RadarModel.cfg
     cfg_fields = set(re.findall(r'gen\.add\(\s*"(\w+)"', open(os.path.join(REF, "cfg", "RadarModel.cfg")).read()))
-    used = set(re.findall(r"\bm_cfg\.(\w+)", cpp))
+    # read by the adapter itself, or by fill_config of the marshalling header, which the adapter instantiates with m_cfg
+    shared = strip_cpp(open(os.path.join(ROOT, "integration", MARSHAL)).read())
+    fill = shared[shared.index("void fill_config("):]
+    fill = fill[:fill.index("\n}")]
+    assert re.search(r"marshal::fill_config\(\s*c\s*,\s*m_cfg\s*,", cpp)
+    used = set(re.findall(r"\bm_cfg\.(\w+)", cpp)) | set(re.findall(r"\bcfg\.(\w+)", fill))
     assert len(used) >= 24 and used <= cfg_fields, used - cfg_fields
     # every field RadarCPU::simulate reads from m_cfg is marshalled (beam_width / n_samples / n_reflections travel via
     # m_params.model, Radar.cpp:213-215; n_cells.. via rr_config)
@@ -219,7 +229,7 @@ def test_adapter_reads_only_what_the_reference_declares(tree):
     # message fields
     def msg_fields(name):
         return {l.split()[1] for l in open(os.path.join(REF, "msg", name)).read().splitlines() if len(l.split()) >= 2}
-    assert set(re.findall(r"\.model\.(\w+)", cpp)) <= msg_fields("RadarModel.msg")
+    assert set(re.findall(r"\.model\.(\w+)", cpp + shared)) <= msg_fields("RadarModel.msg")
     assert {"velocity", "ambient", "diffuse", "specular"} == msg_fields("RadarMaterial.msg")
     assert msg_fields("RadarParams.msg") == {"materials", "model"} and msg_fields("RadarMaterials.msg") == {"data"}
     # protected members of Radar (Radar.hpp:66-105) and its methods
@@ -253,21 +263,34 @@ def test_adapter_type_checks_against_the_reference_headers(tree, tmp_path):
     """g++ -fsyntax-only on the ROS-typed adapter: the reference's own Radar.hpp / radar_types.h, the headers catkin would
     generate derived from the reference's IDL at test time, and signature-only stand-ins for ROS / cv_bridge / rmagine
     (tests/cpp/ros_stubs/README.md: type-check scaffolding, not a build of the reference, pins nothing).  Also checked:
-    the scaffolding is not vacuous -- a misspelt config field or a wrong rr_* arity fails to compile."""
+    the scaffolding is not vacuous -- a misspelt config field or a wrong rr_* arity fails to compile.  The config copy and
+    the materials live in the marshalling header as templates: a misspelt field there fails only because the adapter
+    instantiates them with the reference's generated types."""
     import subprocess
     gen_dir = str(tmp_path / "gen")
     _generated_headers(gen_dir)
-    base = ["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Wno-unused-variable", "-I", os.path.join(ROOT, "tests", "cpp", "ros_stubs"),
-            "-I", gen_dir, "-I", os.path.join(tree, "include"), "-I", os.path.join(ROOT, "include")]
+    inc = os.path.join(ROOT, "include")
+    bad_inc = tmp_path / "bad_include"          # first on the include path: a mutated copy of the header shadows the tree's
+    (bad_inc / "radarays_ros_amd").mkdir(parents=True)
+    shutil.copy(os.path.join(inc, "radarays_mi355.h"), bad_inc)          # what the header includes as "../radarays_mi355.h"
+    base = ["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Wno-unused-variable", "-I", str(bad_inc),
+            "-I", os.path.join(ROOT, "tests", "cpp", "ros_stubs"), "-I", gen_dir, "-I", os.path.join(tree, "include"), "-I", inc]
     src = os.path.join(tree, "src", "radarays_ros", "RadarHIP.cpp")
+    shared = bad_inc / "radarays_ros_amd" / "marshal.hpp"
     r = subprocess.run(base + [src], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-4000:]
-    text = open(src).read()
-    for bad, why in ((text.replace("m_cfg.signal_max", "m_cfg.signal_maximum", 1), "a config field that does not exist"),
-                     (text.replace("rr_multi_set_config(m_multi, &c)", "rr_multi_set_config(m_multi, &c, 1)", 1), "an rr_* call with one argument too many"),
-                     (text.replace("m.velocity", "m.speed", 1), "a message field that does not exist")):
-        assert bad != text
-        p = tmp_path / "bad.cpp"
-        p.write_text(bad)
+    text = {src: open(src).read(), shared: open(os.path.join(inc, "radarays_ros_amd", "marshal.hpp")).read()}
+    p = tmp_path / "bad.cpp"
+    for where, old, new, named, why in (
+            (shared, "cfg.signal_max", "cfg.signal_maximum", "signal_maximum", "a config field that does not exist"),
+            (p, "rr_multi_set_config(m_multi, &c)", "rr_multi_set_config(m_multi, &c, 1)", "rr_multi_set_config", "an rr_* call with one argument too many"),
+            (shared, "m.velocity", "m.speed", "speed", "a message field that does not exist")):
+        good = text[src if where == p else shared]
+        bad = good.replace(old, new, 1)
+        assert bad != good
+        p.write_text(text[src])
+        where.write_text(bad)
         rb = subprocess.run(base + [str(p)], capture_output=True, text=True)
-        assert rb.returncode != 0, why
+        if where == shared:
+            shared.unlink()
+        assert rb.returncode != 0 and named in rb.stderr, (why, rb.stderr[-2000:])     # refused, and for that reason
