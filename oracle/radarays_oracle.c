@@ -470,7 +470,7 @@ struct orc_scene {
  * no bounding hierarchy over the triangle's box would ever visit, so the brute-force loop and a BVH (this file's own
  * intersect_bvh included) disagreed on such rays (1 in 39M fuzz rays, round 4).  Such a hit counts only if its point
  * o + t d lies inside the triangle's bounding box padded by guard_pad: the nearest hit is then a property of the mesh, not of
- * the structure that finds it.  Same arithmetic, un-fused, in the HIP kernel (traverse, rr_kernels.hip). */
+ * the structure that finds it.  Same arithmetic, un-fused, in the HIP kernel (leaf_step, rr_kernels.hip). */
 static inline int tri_hit(const struct orc_scene* s, uint32_t f, v3 o, v3 d, float* t_out)
 {
     const v3 e1 = s->e1[f], e2 = s->e2[f];

@@ -115,7 +115,7 @@ struct rr_ctx {
     uint32_t tri_base4 = 0;        // float4 offset of triangle 0
     uint64_t n_nodes = 0, n_tris = 0;
     uint32_t depth = 0, stack_need = 0;
-    float hit_pad = 0.f;           // grazing guard of the triangle test (traverse): 1e-5 x the extent of the faces' vertices = half the builders' box padding
+    float hit_pad = 0.f;           // grazing guard of the triangle test (leaf_step): 1e-5 x the extent of the faces' vertices = half the builders' box padding
 
     // dynamic scenes (rr_refit.hip): the rest geometry of the last rr_set_mesh* / rr_update_vertices, one rigid pose per
     // object; the traced scene is every face's rest corners moved by its object's pose

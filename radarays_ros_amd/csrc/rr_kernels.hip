@@ -105,6 +105,59 @@ __device__ inline RaySetup ray_setup(V3 o, V3 d)
     return R;
 }
 
+// The leaf step of both walks: lane q tests triangle q of the leaf (record words A, B, C) and the quad agrees on the
+// nearest hit of the leaf.  Returns the key (bits(t) << 32) | (face << 2 | slot in the leaf)
+__device__ __forceinline__ unsigned long long leaf_step(const float4 A, const float4 B, const float4 C, const V3 o, const V3 d,
+                                                        const int q, const uint32_t cnt, const float range_max, const float hit_pad)
+{
+    // Moeller-Trumbore, f32, un-fused: bit-identical to the CPU restatement.  Computed by every
+    // lane (padded triangle arrays keep q >= cnt in bounds), selected at the end: no branches
+    const V3 v0 = { A.x, A.y, A.z }, e1 = { B.x, B.y, B.z }, e2 = { C.x, C.y, C.z };
+    const V3 pvec = v_cross(d, e2);
+    const float det = v_dot(e1, pvec);
+    const float inv = 1.0f / det;
+    const V3 tvec = v_sub(o, v0);
+    const float u = v_dot(tvec, pvec) * inv;
+    const V3 qvec = v_cross(tvec, e1);
+    const float v = v_dot(d, qvec) * inv;
+    const float tt = v_dot(e2, qvec) * inv;
+    bool ok = ((uint32_t)q < cnt) && (det != 0.0f) && (u >= 0.0f && u <= 1.0f) && (v >= 0.0f && u + v <= 1.0f) &&
+              (tt > 0.0f && tt <= range_max);
+    // Grazing guard (round 5): a ray within 0.3 degrees of the triangle's plane -- det^2 < 2.5e-5 |e1 x e2|^2, the
+    // threshold rides in the record's spare word (k_tri_graze) -- makes Moeller-Trumbore ill-conditioned: its
+    // barycentric test can accept a point centimetres outside the triangle, outside the padded box any hierarchy
+    // holds the triangle in (seed 307 of round 4's nearest-hit fuzz).  Such a hit counts only if its point lies in
+    // the triangle's box padded by hit_pad (= half the builders' padding), which makes the nearest hit a property
+    // of the mesh alone, not of the tree; the oracle applies the same rule with the same un-fused arithmetic.
+    // Wave-uniform branch, taken by ~1 leaf step in 50: 4 instructions on the path everybody runs
+    const bool graze = ok && (det * det < C.w);
+    if (__builtin_amdgcn_ballot_w64(graze) != 0ull) {
+        const V3 ph = v_add(o, v_scale(d, tt));
+        const V3 v1 = v_add(v0, e1), v2 = v_add(v0, e2);
+        const bool inside =
+            ph.x >= fminf(v0.x, fminf(v1.x, v2.x)) - hit_pad && ph.x <= fmaxf(v0.x, fmaxf(v1.x, v2.x)) + hit_pad &&
+            ph.y >= fminf(v0.y, fminf(v1.y, v2.y)) - hit_pad && ph.y <= fmaxf(v0.y, fmaxf(v1.y, v2.y)) + hit_pad &&
+            ph.z >= fminf(v0.z, fminf(v1.z, v2.z)) - hit_pad && ph.z <= fmaxf(v0.z, fmaxf(v1.z, v2.z)) + hit_pad;
+        if (graze && !inside) ok = false;
+    }
+    // quad-wide nearest (t, then lower face index) in two 32-bit rounds: t is positive or +inf, so its
+    // order is the unsigned order of its bits -> minimum over the quad with two DPP mins; then, among
+    // the lanes that hold that minimum, the lowest (face << 2 | lane): the low bits name the winning
+    // lane, i.e. the triangle's slot in the leaf (face < 2^28).  A leaf without a hit yields
+    // (+inf : something), which never beats the initial (+inf : 0).
+    const uint32_t tb = ok ? __float_as_uint(tt) : 0x7F800000u;
+    uint32_t tm = min(tb, (uint32_t)RR_DPP_I(tb, RR_QXOR1));
+    tm = min(tm, (uint32_t)RR_DPP_I(tm, RR_QXOR2));
+    const uint32_t fk = (tb == tm) ? ((__float_as_uint(A.w) << 2) | (uint32_t)q) : 0xFFFFFFFFu;
+    uint32_t fm = min(fk, (uint32_t)RR_DPP_I(fk, RR_QXOR1));
+    fm = min(fm, (uint32_t)RR_DPP_I(fm, RR_QXOR2));
+    return ((unsigned long long)tm << 32) | fm;
+}
+
+// The LDS stack of a workgroup: stack_lds entries per ray.  The 4-B references of all its rays come first (entry e of the
+// ray at my[e * 16]), then -- CULL only -- their 2-B distance bounds in the same order (myk[e * 16]); traverse() forms my / myk
+__host__ __device__ constexpr size_t stack_bytes(int stack_lds, bool cull) { return (size_t)stack_lds * kRaysPerBlock * (cull ? 6 : 4); }
+
 template <bool STATS, bool SPILL, bool CULL>
 __device__ inline Hit traverse(const float4* __restrict__ base4, const uint32_t tri_base4,
                                const RaySetup& R, float range_max, float hit_pad,
@@ -186,52 +239,11 @@ __device__ inline Hit traverse(const float4* __restrict__ base4, const uint32_t 
             }
             if (nhit > 0) { sp += nhit - 1; cur = nxt; continue; }
         } else {
-            // Moeller-Trumbore, f32, un-fused: bit-identical to the CPU restatement.  Computed by every
-            // lane (padded triangle arrays keep q >= cnt in bounds), selected at the end: no branches
             if (STATS) n_tris += ((uint32_t)q < cnt);
-            const V3 v0 = { A.x, A.y, A.z }, e1 = { B.x, B.y, B.z }, e2 = { C.x, C.y, C.z };
-            const V3 pvec = v_cross(d, e2);
-            const float det = v_dot(e1, pvec);
-            const float inv = 1.0f / det;
-            const V3 tvec = v_sub(o, v0);
-            const float u = v_dot(tvec, pvec) * inv;
-            const V3 qvec = v_cross(tvec, e1);
-            const float v = v_dot(d, qvec) * inv;
-            const float tt = v_dot(e2, qvec) * inv;
-            bool ok = ((uint32_t)q < cnt) && (det != 0.0f) && (u >= 0.0f && u <= 1.0f) && (v >= 0.0f && u + v <= 1.0f) &&
-                      (tt > 0.0f && tt <= range_max);
-            // Grazing guard (round 5): a ray within 0.3 degrees of the triangle's plane -- det^2 < 2.5e-5 |e1 x e2|^2, the
-            // threshold rides in the record's spare word (k_tri_graze) -- makes Moeller-Trumbore ill-conditioned: its
-            // barycentric test can accept a point centimetres outside the triangle, outside the padded box any hierarchy
-            // holds the triangle in (seed 307 of round 4's nearest-hit fuzz).  Such a hit counts only if its point lies in
-            // the triangle's box padded by hit_pad (= half the builders' padding), which makes the nearest hit a property
-            // of the mesh alone, not of the tree; the oracle applies the same rule with the same un-fused arithmetic.
-            // Wave-uniform branch, taken by ~1 leaf step in 50: 4 instructions on the path everybody runs
-            const bool graze = ok && (det * det < C.w);
-            if (__builtin_amdgcn_ballot_w64(graze) != 0ull) {
-                const V3 ph = v_add(o, v_scale(d, tt));
-                const V3 v1 = v_add(v0, e1), v2 = v_add(v0, e2);
-                const bool inside =
-                    ph.x >= fminf(v0.x, fminf(v1.x, v2.x)) - hit_pad && ph.x <= fmaxf(v0.x, fmaxf(v1.x, v2.x)) + hit_pad &&
-                    ph.y >= fminf(v0.y, fminf(v1.y, v2.y)) - hit_pad && ph.y <= fmaxf(v0.y, fmaxf(v1.y, v2.y)) + hit_pad &&
-                    ph.z >= fminf(v0.z, fminf(v1.z, v2.z)) - hit_pad && ph.z <= fmaxf(v0.z, fmaxf(v1.z, v2.z)) + hit_pad;
-                if (graze && !inside) ok = false;
-            }
-            // quad-wide nearest (t, then lower face index) in two 32-bit rounds: t is positive or +inf, so its
-            // order is the unsigned order of its bits -> minimum over the quad with two DPP mins; then, among
-            // the lanes that hold that minimum, the lowest (face << 2 | lane): the low bits name the winning
-            // lane, i.e. the triangle's slot in the leaf (face < 2^28).  A leaf without a hit yields
-            // (+inf : something), which never beats the initial (+inf : 0).
-            const uint32_t tb = ok ? __float_as_uint(tt) : 0x7F800000u;
-            uint32_t tm = min(tb, (uint32_t)RR_DPP_I(tb, RR_QXOR1));
-            tm = min(tm, (uint32_t)RR_DPP_I(tm, RR_QXOR2));
-            const uint32_t fk = (tb == tm) ? ((__float_as_uint(A.w) << 2) | (uint32_t)q) : 0xFFFFFFFFu;
-            uint32_t fm = min(fk, (uint32_t)RR_DPP_I(fk, RR_QXOR1));
-            fm = min(fm, (uint32_t)RR_DPP_I(fm, RR_QXOR2));
-            const unsigned long long key = ((unsigned long long)tm << 32) | fm;
+            const unsigned long long key = leaf_step(A, B, C, o, d, q, cnt, range_max, hit_pad);
             if (key < bestkey) {
                 bestkey = key; best_first = first;
-                tcull = __builtin_fmaf(__uint_as_float(tm), 1.0001f, 1e-3f);   // a bound only: may be fused
+                tcull = __builtin_fmaf(__uint_as_float((uint32_t)(key >> 32)), 1.0001f, 1e-3f);   // a bound only: may be fused
             }
         }
         // pop
@@ -315,38 +327,10 @@ __device__ inline Hit traverse_stackless(const float4* __restrict__ base4, const
             pk |= (uint32_t)RR_DPP_I(pk, RR_QXOR2);
             prev = from >= 0 ? (int)pk : -1;
         } else {
-            // (the leaf step of traverse(): Moeller-Trumbore, grazing guard, quad-wide nearest)
-            const V3 v0 = { A.x, A.y, A.z }, e1 = { B.x, B.y, B.z }, e2 = { C.x, C.y, C.z };
-            const V3 pvec = v_cross(d, e2);
-            const float det = v_dot(e1, pvec);
-            const float inv = 1.0f / det;
-            const V3 tvec = v_sub(o, v0);
-            const float u = v_dot(tvec, pvec) * inv;
-            const V3 qvec = v_cross(tvec, e1);
-            const float v = v_dot(d, qvec) * inv;
-            const float tt = v_dot(e2, qvec) * inv;
-            bool ok = ((uint32_t)q < cnt) && (det != 0.0f) && (u >= 0.0f && u <= 1.0f) && (v >= 0.0f && u + v <= 1.0f) &&
-                      (tt > 0.0f && tt <= range_max);
-            const bool graze = ok && (det * det < C.w);
-            if (__builtin_amdgcn_ballot_w64(graze) != 0ull) {
-                const V3 ph = v_add(o, v_scale(d, tt));
-                const V3 v1 = v_add(v0, e1), v2 = v_add(v0, e2);
-                const bool inside =
-                    ph.x >= fminf(v0.x, fminf(v1.x, v2.x)) - hit_pad && ph.x <= fmaxf(v0.x, fmaxf(v1.x, v2.x)) + hit_pad &&
-                    ph.y >= fminf(v0.y, fminf(v1.y, v2.y)) - hit_pad && ph.y <= fmaxf(v0.y, fmaxf(v1.y, v2.y)) + hit_pad &&
-                    ph.z >= fminf(v0.z, fminf(v1.z, v2.z)) - hit_pad && ph.z <= fmaxf(v0.z, fmaxf(v1.z, v2.z)) + hit_pad;
-                if (graze && !inside) ok = false;
-            }
-            const uint32_t tb = ok ? __float_as_uint(tt) : 0x7F800000u;
-            uint32_t tm = min(tb, (uint32_t)RR_DPP_I(tb, RR_QXOR1));
-            tm = min(tm, (uint32_t)RR_DPP_I(tm, RR_QXOR2));
-            const uint32_t fk = (tb == tm) ? ((__float_as_uint(A.w) << 2) | (uint32_t)q) : 0xFFFFFFFFu;
-            uint32_t fm = min(fk, (uint32_t)RR_DPP_I(fk, RR_QXOR1));
-            fm = min(fm, (uint32_t)RR_DPP_I(fm, RR_QXOR2));
-            const unsigned long long key = ((unsigned long long)tm << 32) | fm;
+            const unsigned long long key = leaf_step(A, B, C, o, d, q, cnt, range_max, hit_pad);
             if (key < bestkey) {
                 bestkey = key; best_first = first;
-                tcull = __builtin_fmaf(__uint_as_float(tm), 1.0001f, 1e-3f);
+                tcull = __builtin_fmaf(__uint_as_float((uint32_t)(key >> 32)), 1.0001f, 1e-3f);
             }
             prev = (int)leafkey;
         }
@@ -464,7 +448,7 @@ __device__ __forceinline__ void trace_group(const Params& P, const int pass, con
     }
 }
 
-// grid: (ceil(bound/16) [+ a copy row], n_seg), block 64 (= one wave = 16 rays), dynamic LDS = stack_lds * 16 * (4 | 6) B
+// grid: (ceil(bound/16) [+ a copy row], n_seg), block 64 (= one wave = 16 rays), dynamic LDS = stack_bytes()
 template <bool FIRST, bool STATS, bool SPILL, bool CULL, bool SL = false>
 __global__ __launch_bounds__(kTraceThreads) void k_trace(const Params P, const int pass, const typename PosesOf<FIRST>::type poses)
 {
@@ -1228,19 +1212,26 @@ __global__ __launch_bounds__(kColThreads) void k_column(const Params P)
             const char* wbytes = reinterpret_cast<const char*>(s_w);
             int2* list = s_list[wid];
             // one replay: acc = (float)((double)acc + (double)strength * w[g - first])   (RadarCPU.cpp:426)
-#define RR_REPLAY(E)                                                                                     \
-            {                                                                                            \
-                const unsigned off = (unsigned)(gb8 - (E).x);                                            \
-                const double wv = *reinterpret_cast<const double*>(wbytes + 8 * kWPad + (int)off);       \
-                const float nv = (float)((double)acc + (double)__int_as_float((E).y) * wv);              \
-                acc = (off < W8) ? nv : acc;                                                             \
-                rmax = fmaxf(rmax, acc);       /* `if (slice > max_val) max_val = slice` (NaN never wins) */  \
-            }
-#define RR_REPLAY_S(E)                                                                                   \
-            {                                                                                            \
-                const double wv = *reinterpret_cast<const double*>(wbytes + 8 * kWPad + (gb8 - (E).x));  \
-                acc = (float)((double)acc + (double)__int_as_float((E).y) * wv);                         \
-            }
+            auto replay = [&](const int2 e) {
+                const unsigned off = (unsigned)(gb8 - e.x);
+                const double wv = *reinterpret_cast<const double*>(wbytes + 8 * kWPad + (int)off);
+                const float nv = (float)((double)acc + (double)__int_as_float(e.y) * wv);
+                acc = (off < W8) ? nv : acc;
+                rmax = fmaxf(rmax, acc);       // `if (slice > max_val) max_val = slice` (NaN never wins)
+            };
+            auto replay_s = [&](const int2 e) {
+                const double wv = *reinterpret_cast<const double*>(wbytes + 8 * kWPad + (gb8 - e.x));
+                acc = (float)((double)acc + (double)__int_as_float(e.y) * wv);
+            };
+            // the first cnt entries of the wave's list through one of the two, in order: four list reads in flight per step
+            auto replay_list = [&](auto one, const int cnt) {
+                int k = 0;
+                for (; k + 4 <= cnt; k += 4) {
+                    const int2 e0 = list[k], e1 = list[k + 1], e2 = list[k + 2], e3 = list[k + 3];
+                    one(e0); one(e1); one(e2); one(e3);
+                }
+                for (; k < cnt; k++) one(list[k]);
+            };
             for (int b0 = 0; b0 < n; b0 += 64) {
                 const int i = b0 + lane;
                 SigRec r; r.cell = 0x40000000; r.strength = 0.0f;
@@ -1261,20 +1252,7 @@ __global__ __launch_bounds__(kColThreads) void k_column(const Params P)
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                    int k = 0;
-                    if (simple) {
-                        for (; k + 4 <= cnt; k += 4) {
-                            const int2 e0 = list[k], e1 = list[k + 1], e2 = list[k + 2], e3 = list[k + 3];
-                            RR_REPLAY_S(e0) RR_REPLAY_S(e1) RR_REPLAY_S(e2) RR_REPLAY_S(e3)
-                        }
-                        for (; k < cnt; k++) { const int2 e = list[k]; RR_REPLAY_S(e) }
-                    } else {
-                        for (; k + 4 <= cnt; k += 4) {
-                            const int2 e0 = list[k], e1 = list[k + 1], e2 = list[k + 2], e3 = list[k + 3];
-                            RR_REPLAY(e0) RR_REPLAY(e1) RR_REPLAY(e2) RR_REPLAY(e3)
-                        }
-                        for (; k < cnt; k++) { const int2 e = list[k]; RR_REPLAY(e) }
-                    }
+                    if (simple) replay_list(replay_s, cnt); else replay_list(replay, cnt);
                 } else {
                     while (m) {
                         const int b = __builtin_ctzll(m); m &= m - 1;
@@ -1284,8 +1262,6 @@ __global__ __launch_bounds__(kColThreads) void k_column(const Params P)
                     }
                 }
             }
-#undef RR_REPLAY
-#undef RR_REPLAY_S
             if (simple && P.signal_denoising > 0) {
                 acc = g_ok ? acc : acc_in;            // bin 0 (RadarCPU.cpp:424) and the lanes beyond the column took part blindly
                 rmax = fmaxf(rmax, acc);              // non-negative echoes: the running maximum of a bin is where it ends
@@ -1580,7 +1556,7 @@ __global__ void k_encode_refs(Node4* nodes, size_t n_children, uint32_t tri_base
     if (r & kLeafFlag) ref = (r & 0xF0000000u) | (tri_base4 + 3u * (r & 0x0FFFFFFFu));
     else ref = r * 8u;
 }
-// ... and the grazing threshold of every triangle record into its spare word: 2.5e-5 |e1 x e2|^2 (see traverse)
+// ... and the grazing threshold of every triangle record into its spare word: 2.5e-5 |e1 x e2|^2 (see leaf_step)
 __global__ void k_tri_graze(TriRec* tris, size_t n)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1610,6 +1586,37 @@ void launch_encode_refs(Node4* nodes, size_t n_nodes, uint32_t tri_base4, hipStr
                                    reinterpret_cast<TriRec*>(reinterpret_cast<float4*>(nodes) + tri_base4), n_tris);
 }
 
+// One launch, with or without the timing events.  ev_start / ev_stop (timing mode) take the dispatch's own begin / end
+// timestamps -- what rocprofv3 reports as the kernel's duration -- not the time the launch spent waiting for CUs held by the
+// kernels of other streams
+template <typename... KArgs, typename... Args>
+static void launch_k(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop,
+                     const Args&... args)
+{
+    if (!ev_start) hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+    else hipExtLaunchKernelGGL(kernel, grid, block, lds, s, ev_start, ev_stop, 0, args...);
+}
+
+// a segment holds at most n_beam * 2^pass waves in pass `pass` (each wave has <= 2 children), and never more than cap
+static long pass_bound(const Params& P, int pass) { return std::min<long>((long)P.cap, pass < 20 ? (long)P.n_beam << pass : (long)P.cap); }
+
+// Every k_trace instantiation there is: what launch_trace launches and what trace0_kernel names come from this one place.
+// sl: the stack-free walk (no statistics build, no spill path, no cull of its own); cull: later passes only
+template <bool FIRST> using TraceKernel = void (*)(Params, int, typename PosesOf<FIRST>::type);
+template <bool FIRST>
+static TraceKernel<FIRST> trace_kernel(bool stats, bool spill, bool cull, bool sl)
+{
+    static const TraceKernel<true> first[2][2] = {        // [stats][spill]
+        { k_trace<true, false, false, false>, k_trace<true, false, true, false> },
+        { k_trace<true, true, false, false>, k_trace<true, true, true, false> } };
+    static const TraceKernel<false> later[2][2][2] = {    // [stats][spill][cull]
+        { { k_trace<false, false, false, false>, k_trace<false, false, false, true> }, { k_trace<false, false, true, false>, k_trace<false, false, true, true> } },
+        { { k_trace<false, true, false, false>, k_trace<false, true, false, true> }, { k_trace<false, true, true, false>, k_trace<false, true, true, true> } } };
+    if (sl) return k_trace<FIRST, false, false, false, true>;
+    if constexpr (FIRST) return first[stats][spill];
+    else return later[stats][spill][cull];
+}
+
 void launch_trace(const Params& P, int pass, const PoseArgs* poses, bool stats, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop,
                   hipEvent_t ev_rep_start, hipEvent_t ev_rep_stop, bool* repair_launched)
 {
@@ -1618,16 +1625,14 @@ void launch_trace(const Params& P, int pass, const PoseArgs* poses, bool stats, 
     // pass 0: one flat sequence of n_seg x n_beam rays; later passes: a row of blocks per segment
     const int A0 = P.pass0_az, Sw0 = kRaysPerWave / A0;
     const size_t waves0 = (size_t)((n_seg + A0 - 1) / A0) * (size_t)((P.n_beam + Sw0 - 1) / Sw0);
-    // later passes: a segment holds at most n_beam * 2^pass waves (each wave has <= 2 children) -- no blocks are
-    // launched beyond that bound (pass 1 of the KAIST preset: 13 instead of 50 blocks per segment; the rest would
-    // read their segment's count and exit)
-    const long bound = std::min<long>((long)P.cap, pass < 20 ? (long)P.n_beam << pass : (long)P.cap);
+    // later passes: no blocks are launched beyond the pass's bound (pass 1 of the KAIST preset: 13 instead of 50 blocks per
+    // segment; the rest would read their segment's count and exit)
+    const long bound = pass_bound(P, pass);
     // ... and since round 5 the row is as long as earlier batches needed (GridHint): tight_groups[pass], 0 = the bound
-    const unsigned row = (pass > 0 && pass < kMaxPasses && P.tight_groups[pass]) ? (unsigned)P.tight_groups[pass]
-                                                                               : (unsigned)((bound + kRaysPerBlock - 1) / kRaysPerBlock);
+    const bool tightened = pass > 0 && pass < kMaxPasses && P.tight_groups[pass];     // (the host keeps tightened rows odd itself)
+    const unsigned row = tightened ? (unsigned)P.tight_groups[pass] : (unsigned)((bound + kRaysPerBlock - 1) / kRaysPerBlock);
     // (an odd row length deals the rows' workgroups evenly over the 8 XCDs, see run_frame; the extra workgroup of a full row
     // exits on its segment's count.  Not on the spill path, whose columns are laid out for the bound)
-    const bool tightened = pass > 0 && pass < kMaxPasses && P.tight_groups[pass];     // (the host keeps tightened rows odd itself)
     const unsigned row_odd = (pass > 0 && P.spill_depth == 0 && !tightened) ? (row | 1u) : row;
     dim3 grid = pass == 0 ? dim3((unsigned)((waves0 + (kTraceThreads / 64) - 1) / (kTraceThreads / 64)))
                           : dim3(row_odd, n_seg);
@@ -1641,80 +1646,40 @@ void launch_trace(const Params& P, int pass, const PoseArgs* poses, bool stats, 
     // later passes cull stack entries at pop time (6-B entries) as long as 32 one-wave workgroups still fit a CU's 160 KB of LDS
     // (5 KB each: up to 53 entries); a deeper tree keeps the 4-B entries -- the lost occupancy would cost more than the
     // cull returns (GPU-built tree of the 10M-triangle target, 56 entries: 0.465 vs 0.442 ms per frame)
-    const bool cull = kCullPop && P.cull_pop && pass > 0 && (size_t)P.stack_lds * kRaysPerBlock * 6 <= 10240 / (128 / kTraceThreads);
-    const size_t lds = (size_t)P.stack_lds * kRaysPerBlock * (cull ? 6 : 4);
+    const bool cull = kCullPop && P.cull_pop && pass > 0 && stack_bytes(P.stack_lds, true) <= 10240 / (128 / kTraceThreads);
+    const size_t lds = stack_bytes(P.stack_lds, cull);
     const bool spill = P.spill_depth > 0;
-// hipExtLaunchKernelGGL: the optional events take the dispatch's own begin/end timestamps (what
-    // rocprofv3 reports), not the time the launch spent waiting for CUs held by other streams
-#define RR_LAUNCH_TRACE0(S, X) hipExtLaunchKernelGGL((k_trace<true, S, X, false>), grid, block, lds, s, ev_start, ev_stop, 0, Pl, pass, *poses)
-#define RR_LAUNCH_TRACE(F, S, X, C) hipExtLaunchKernelGGL((k_trace<F, S, X, C>), grid, block, lds, s, ev_start, ev_stop, 0, Pl, pass, NoPoses{})
-    if (P.stackless && !stats) {       // the stack-free walk: no LDS at all (RR_STACKLESS=1; the statistics build keeps the stack walk)
-        if (pass == 0) hipExtLaunchKernelGGL((k_trace<true, false, false, false, true>), grid, block, 0, s, ev_start, ev_stop, 0, Pl, pass, *poses);
-        else hipExtLaunchKernelGGL((k_trace<false, false, false, false, true>), grid, block, 0, s, ev_start, ev_stop, 0, Pl, pass, NoPoses{});
-    } else if (pass == 0) {
-        if (stats) { if (spill) RR_LAUNCH_TRACE0(true, true); else RR_LAUNCH_TRACE0(true, false); }
-        else       { if (spill) RR_LAUNCH_TRACE0(false, true); else RR_LAUNCH_TRACE0(false, false); }
-    } else if (cull) {
-        if (stats) { if (spill) RR_LAUNCH_TRACE(false, true, true, true); else RR_LAUNCH_TRACE(false, true, false, true); }
-        else       { if (spill) RR_LAUNCH_TRACE(false, false, true, true); else RR_LAUNCH_TRACE(false, false, false, true); }
-    } else {
-        if (stats) { if (spill) RR_LAUNCH_TRACE(false, true, true, false); else RR_LAUNCH_TRACE(false, true, false, false); }
-        else       { if (spill) RR_LAUNCH_TRACE(false, false, true, false); else RR_LAUNCH_TRACE(false, false, false, false); }
-    }
-#undef RR_LAUNCH_TRACE
-#undef RR_LAUNCH_TRACE0
-    if (pass > 0 && pass < kMaxPasses && P.tight_groups[pass]) {     // host guarantees: no statistics build, no spill path
-        const dim3 rgrid(128);
+    const bool sl = P.stackless && !stats;    // the stack-free walk: no LDS at all (RR_STACKLESS=1; the statistics build keeps the stack walk)
+    // (hipExtLaunchKernelGGL with or without events, as these launches always were: the chains are captured into graphs)
+    if (pass == 0) hipExtLaunchKernelGGL(trace_kernel<true>(stats, spill, false, sl), grid, block, sl ? 0 : lds, s, ev_start, ev_stop, 0, Pl, pass, *poses);
+    else hipExtLaunchKernelGGL(trace_kernel<false>(stats, spill, cull, sl), grid, block, sl ? 0 : lds, s, ev_start, ev_stop, 0, Pl, pass, NoPoses{});
+    if (tightened) {     // host guarantees: no statistics build, no spill path
         // (its own pair of events in timing mode: the repair is not inside the trace launch's begin / end)
-        if (!ev_rep_start) {
-            if (cull) hipLaunchKernelGGL((k_trace_repair<true>), rgrid, block, lds, s, Pl, pass);
-            else      hipLaunchKernelGGL((k_trace_repair<false>), rgrid, block, lds, s, Pl, pass);
-        } else if (cull) hipExtLaunchKernelGGL((k_trace_repair<true>), rgrid, block, lds, s, ev_rep_start, ev_rep_stop, 0, Pl, pass);
-        else             hipExtLaunchKernelGGL((k_trace_repair<false>), rgrid, block, lds, s, ev_rep_start, ev_rep_stop, 0, Pl, pass);
+        launch_k(cull ? k_trace_repair<true> : k_trace_repair<false>, dim3(128), block, lds, s, ev_rep_start, ev_rep_stop, Pl, pass);
         if (repair_launched) *repair_launched = true;
     }
 }
 
 // the pass-0 trace kernel of the plain build (no statistics): the node of a replayed launch graph whose parameters change from
 // replay to replay -- (Params, pass, PoseArgs) -- see rr_frame.hip: run_frame
-void* trace0_kernel(bool spill, bool stackless)
-{
-    if (stackless) return (void*)k_trace<true, false, false, false, true>;
-    return spill ? (void*)k_trace<true, false, true, false> : (void*)k_trace<true, false, false, false>;
-}
+void* trace0_kernel(bool spill, bool stackless) { return (void*)trace_kernel<true>(false, spill, false, stackless); }
 
-// (ev_start / ev_stop, timing mode: the dispatch's own begin / end timestamps -- what rocprofv3 reports as the kernel's
-// duration -- not the time the launch spent waiting for the kernels of other streams)
 void launch_shade(const Params& P, int pass, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop)
 {
-    const int cap_p = (int)std::min<long>((long)P.cap, pass < 20 ? (long)P.n_beam << pass : (long)P.cap);   // see launch_trace
-    dim3 grid((cap_p + 63) / 64, P.n_seg), block(64);
-    if (!ev_start) {
-        if (pass == 0) hipLaunchKernelGGL((k_shade<true>), grid, block, 0, s, P, pass);
-        else           hipLaunchKernelGGL((k_shade<false>), grid, block, 0, s, P, pass);
-    } else if (pass == 0) hipExtLaunchKernelGGL((k_shade<true>), grid, block, 0, s, ev_start, ev_stop, 0, P, pass);
-    else                  hipExtLaunchKernelGGL((k_shade<false>), grid, block, 0, s, ev_start, ev_stop, 0, P, pass);
+    dim3 grid(((int)pass_bound(P, pass) + 63) / 64, P.n_seg);
+    launch_k(pass == 0 ? k_shade<true> : k_shade<false>, grid, dim3(64), 0, s, ev_start, ev_stop, P, pass);
 }
 
 void launch_scan(const Params& P, int pass, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop)
 {
-    dim3 grid(P.n_seg), block(256);
-    if (!ev_start) {
-        if (pass == 0) hipLaunchKernelGGL((k_scan<true>), grid, block, 0, s, P, pass);
-        else           hipLaunchKernelGGL((k_scan<false>), grid, block, 0, s, P, pass);
-    } else if (pass == 0) hipExtLaunchKernelGGL((k_scan<true>), grid, block, 0, s, ev_start, ev_stop, 0, P, pass);
-    else                  hipExtLaunchKernelGGL((k_scan<false>), grid, block, 0, s, ev_start, ev_stop, 0, P, pass);
+    launch_k(pass == 0 ? k_scan<true> : k_scan<false>, dim3(P.n_seg), dim3(256), 0, s, ev_start, ev_stop, P, pass);
 }
 
 void launch_column(const Params& P, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop)
 {
-    dim3 grid(P.n_seg);
     const size_t lds = (((size_t)P.n_cells * sizeof(float)) + 15) & ~(size_t)15;
-    if (!ev_start) {
-        if (P.n_seg >= 1024) hipLaunchKernelGGL(k_column<256>, grid, dim3(256), lds, s, P);
-        else hipLaunchKernelGGL(k_column<512>, grid, dim3(512), lds, s, P);
-    } else if (P.n_seg >= 1024) hipExtLaunchKernelGGL(k_column<256>, grid, dim3(256), lds, s, ev_start, ev_stop, 0, P);
-    else hipExtLaunchKernelGGL(k_column<512>, grid, dim3(512), lds, s, ev_start, ev_stop, 0, P);
+    const bool narrow = P.n_seg >= 1024;
+    launch_k(narrow ? k_column<256> : k_column<512>, dim3(P.n_seg), dim3(narrow ? 256 : 512), lds, s, ev_start, ev_stop, P);
 }
 
 void launch_assemble_u8(const uint8_t* cols, uint8_t* img, int n_angles, int n_cells, int scroll, hipStream_t s,
@@ -1745,14 +1710,9 @@ void launch_debug_trace(const Params& P, const float* origs, const float* dirs, 
 {
     dim3 grid((n + kRaysPerBlock - 1) / kRaysPerBlock), block(kTraceThreads);
     const bool cull = kCullPop && P.cull_pop;
-    const size_t lds = (size_t)P.stack_lds * kRaysPerBlock * (cull ? 6 : 4);
-    if (steps) {
-        if (cull) hipLaunchKernelGGL((k_debug_trace<true, true>), grid, block, lds, s, P, origs, dirs, n, out_t, out_face, steps);
-        else hipLaunchKernelGGL((k_debug_trace<false, true>), grid, block, lds, s, P, origs, dirs, n, out_t, out_face, steps);
-    } else {
-        if (cull) hipLaunchKernelGGL((k_debug_trace<true, false>), grid, block, lds, s, P, origs, dirs, n, out_t, out_face, steps);
-        else hipLaunchKernelGGL((k_debug_trace<false, false>), grid, block, lds, s, P, origs, dirs, n, out_t, out_face, steps);
-    }
+    const auto k = steps ? (cull ? k_debug_trace<true, true> : k_debug_trace<false, true>)
+                         : (cull ? k_debug_trace<true, false> : k_debug_trace<false, false>);
+    launch_k(k, grid, block, stack_bytes(P.stack_lds, cull), s, nullptr, nullptr, P, origs, dirs, n, out_t, out_face, steps);
 }
 
 }  // namespace rr

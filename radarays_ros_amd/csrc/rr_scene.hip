@@ -17,7 +17,7 @@ int check_bvh_size(rr_ctx* c, size_t n_nodes, size_t n_tris)
     return 0;
 }
 
-// The grazing guard's padding (traverse, rr_kernels.hip): 1e-5 x max(extent, largest |coordinate|) of the vertices the faces
+// The grazing guard's padding (leaf_step, rr_kernels.hip): 1e-5 x max(extent, largest |coordinate|) of the vertices the faces
 // use -- half of what both builders pad their boxes with (2e-5 x the same measure + 1e-6; the GPU builder measures ALL
 // vertices, which can only give more).  One multiplication: nothing a compiler could contract; the oracle forms the same value
 float guard_pad(const float* verts, const uint32_t* faces, size_t nf)

@@ -477,6 +477,63 @@ def test_launch_graphs_replay_identical_images_and_are_dropped_on_any_change(nat
     c.close(); c0.close()
 
 
+@pytest.mark.parametrize("variant", ["default", "spill", "stackless"])
+def test_every_pass0_trace_variant_is_captured_and_replayed(native_lib, monkeypatch, variant):
+    """The poses of a replay go into the graph node that holds the pass-0 k_trace launch, and capture_graph finds that node
+    by the kernel trace0_kernel() names.  For each of the three pass-0 variants of the plain build (stack walk, stack walk
+    that spills under RR_STACK_LDS, stack-free walk under RR_STACKLESS=1): three batches of two poses, every image equal to
+    the kernel-by-kernel render (RR_GRAPHS=0), and the chain is captured AND replayed.  The replay is the point: if the
+    kernel launch_trace launches were not the one trace0_kernel names, the capture would be dropped without a trace --
+    right images, no replay."""
+    import torch
+    s = gen.two_room_scene()
+    cfg = params.kaist_preset(n_reflections=3, ambient_noise=2)
+    mats = params.kaist_materials() + [params.PENETRABLE]
+    noise = (np.random.RandomState(3).uniform(0, 1, (4, 400)) * 1000.0).astype(np.float32)
+    poses = scenes.trajectory(6, "box12")
+    batches = [poses[0:2], poses[2:4], poses[4:6]]       # issued kernel by kernel, captured, replayed
+
+    def ctx():
+        c = native_lib.Context(0)
+        c.set_mesh(s["verts"], s["faces"], s["face_object_id"])
+        c.set_materials(mats, s["object_materials"], 0)
+        c.set_config(cfg)
+        c.set_beam_samples(golden_beams(32))
+        c.set_noise_offsets(noise)
+        return c
+    for name in ("RR_STACK_LDS", "RR_STACKLESS", "RR_TIGHT_FORCE"):       # (the suite may run under one of them)
+        monkeypatch.delenv(name, raising=False)
+    if variant == "spill":
+        monkeypatch.setenv("RR_STACK_LDS", "4")
+    if variant == "stackless":
+        monkeypatch.setenv("RR_STACKLESS", "1")
+    monkeypatch.setenv("RR_LANES", "1")          # one frame lane: every batch meets the same buffers (and the same graph)
+    # The lengths of the tightened trace rows are part of a graph's shape and follow the history of the first batches (the
+    # test above: "a few captures"), so with three calls the second would be the first use of another shape.  Full rows
+    # (as the spill path has anyway) make the three calls exactly: issued, captured, replayed
+    monkeypatch.setenv("RR_TIGHT_GRID", "0")
+    monkeypatch.setenv("RR_GRAPHS", "0")
+    c0 = ctx()
+    want = [_batch(c0, b, cfg) for b in batches]
+    assert c0.graph_stats() == (0, 0)
+    c0.close()
+    assert not np.array_equal(want[0], want[1]) and not np.array_equal(want[1], want[2])
+    monkeypatch.delenv("RR_GRAPHS")
+    c = ctx()
+    if variant == "spill":
+        assert c.bvh_info()["stack_need"] > 4        # ... so that this case is the spilling kernel indeed
+    imgs = torch.zeros((2, cfg.n_cells, 400), dtype=torch.uint8, device="cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    for k, b in enumerate(batches):
+        c.simulate_batch_device(b, imgs.data_ptr(), st)
+        c.synchronize(st)
+        assert np.array_equal(imgs.cpu().numpy(), want[k]), k
+    cap, rep = c.graph_stats()
+    print("variant %s: captures %d, replays %d" % (variant, cap, rep))
+    c.close()
+    assert cap >= 1 and rep >= 1, (cap, rep)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # Later-pass trace grids in chunks of 16 azimuths (RR_TRACE_CHUNK): a launch shape, never a different image
 # ---------------------------------------------------------------------------------------------------------------------

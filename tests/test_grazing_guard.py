@@ -1,4 +1,4 @@
-"""The grazing guard of the triangle test (round 5; oracle/radarays_oracle.c: tri_hit, csrc/rr_kernels.hip: traverse).
+"""The grazing guard of the triangle test (round 5; oracle/radarays_oracle.c: tri_hit, csrc/rr_kernels.hip: leaf_step).
 
 Round 4's nearest-hit fuzz found ONE ray in 39 M (seed 307, ray 389) on which the brute-force loop and every hierarchy
 disagreed: it grazes a triangle's plane at |d . n| = 4.3e-5, Moeller-Trumbore's barycentric test accepts a point 6.4 mm
