@@ -1,6 +1,7 @@
 // rr_ctx.h -- the context as the library's host files share it (rr_api.hip, rr_scene.hip, rr_frame.hip, rr_sets.hip, rr_probe.hip): rr_ctx and its
 // lanes, the error / timing / roctx helpers, the helpers that cross a file boundary.  Nothing here is public: the interface is include/radarays_mi355.h.
 #pragma once
+#include "rr_devbuf.h"
 #include "rr_launch.h"
 #include "rr_sdma.h"
 #include <map>
@@ -8,21 +9,6 @@
 #include <vector>
 
 namespace rr {
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    hipError_t ensure(size_t count) {
-        if (count <= n && p) return hipSuccess;
-        if (p) { (void)hipFree(p); p = nullptr; n = 0; }
-        if (count == 0) count = 1;
-        hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
-        if (e == hipSuccess) n = count;
-        return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-};
-
 struct KernelTimer {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
     double total_ms = 0.0;

@@ -159,6 +159,70 @@ def test_multi_async_error_is_reported_once_and_drains(native_lib, small, monkey
     m.close()
 
 
+@pytest.fixture(scope="module")
+def plan_refs(native_lib, small):
+    """rr_simulate's frames for one batch of 4 poses and one of 1 pose, computed once (read only)"""
+    poses = small[5]
+    batches = [poses[0:4], poses[4:5]]
+    return batches, _reference_frames(native_lib, small, batches)
+
+
+@pytest.mark.parametrize("n_dev,threads", [(1, 0), (3, 0), (3, 1)])
+def test_multi_launch_time_failure_hands_the_object_back_drained(native_lib, small, plan_refs, monkeypatch, n_dev, threads):
+    """A call that fails while it is being issued (a NaN in its second pose: run_frame refuses it on the host, nothing of it
+    reaches the GPU) returns ITS message -- and the object drained: the healthy batch that was in flight beside it reports
+    the invalidation from the wait for its own buffer, once; then everything is clean and the next batches are right."""
+    s, cfg, mats, beams, noise, poses = small
+    if n_dev > 1:
+        monkeypatch.setenv("RR_MULTI_LOOPBACK", "1")
+    if threads:
+        monkeypatch.setenv("RR_MULTI_THREADS", "1")
+    m = native_lib.MultiContext([0] * n_dev)
+    _setup(m, s, cfg, mats, beams, noise)
+    (batch4, _), (ref4, _) = plan_refs
+    good, ref = batch4[0:2], ref4[0:2]
+    bad = np.array(good, np.float32); bad[1, 4] = np.nan
+    a, b = [native_lib.HostImages((2, cfg.n_cells, 400)) for _ in range(2)]
+    m.simulate_batch_async(good, a.ptr)
+    with pytest.raises(native_lib.RRError, match=r"device 0: non-finite pose.*\(rc=-3\)"):
+        m.simulate_batch_async(bad, b.ptr)
+    with pytest.raises(native_lib.RRError, match=r"invalidates every batch in flight\) \(rc=-3\)"):
+        m.wait(a.ptr)
+    m.wait(a.ptr); m.wait(None)                                # reported once
+    b.array[:] = 0xAB
+    m.simulate_batch_async(good, b.ptr)
+    m.wait(b.ptr)
+    assert np.array_equal(b.array, ref)
+    assert np.array_equal(m.simulate_batch(good), ref)
+    m.wait(None)
+    a.close(); b.close()
+    m.close()
+
+
+@pytest.mark.parametrize("n_dev", [2, 5, 8, 3, 7])
+def test_multi_equal_and_ragged_plans_deliver_the_same_bytes(native_lib, small, plan_refs, monkeypatch, n_dev):
+    """rr_multi_plan's two shapes in loopback: 400 / 2, 400 / 5 and 400 / 8 are equal blocks (one piece per device into
+    [device][frame][n_loc][n_cells]), 3 and 7 ragged ones (one piece per device and frame into [frame][n_angles][n_cells]);
+    batches of 4 frames and of 1, synchronous and pipelined -- every image equals rr_simulate's."""
+    s, cfg, mats, beams, noise, _ = small
+    monkeypatch.setenv("RR_MULTI_LOOPBACK", "1")
+    m = native_lib.MultiContext([0] * n_dev)
+    assert m.device_count() == n_dev
+    _setup(m, s, cfg, mats, beams, noise)
+    batches, refs = plan_refs
+    ring = [native_lib.HostImages((len(batch), cfg.n_cells, 400)) for batch in batches]
+    for h, batch in zip(ring, batches):
+        h.array[:] = 0xAB
+        m.simulate_batch_async(batch, h.ptr)
+    m.wait(None)
+    for h, batch, ref in zip(ring, batches, refs):
+        assert np.array_equal(h.array, ref), (n_dev, len(batch))
+        assert np.array_equal(m.simulate_batch(batch), ref), (n_dev, len(batch))
+    for h in ring:
+        h.close()
+    m.close()
+
+
 @pytest.mark.parametrize("mode", ["1", "2"])
 def test_multi_real_rccl_calls_on_one_gpu(native_lib, small, monkeypatch, mode):
     """RR_MULTI_SELF_RCCL: what the loopback leaves out, on a one-GPU box -- librccl loaded at run time, ncclCommInitAll
