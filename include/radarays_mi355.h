@@ -329,6 +329,61 @@ int rr_score_images_device(rr_ctx* ctx, const uint8_t* d_imgs_u8, int n_images, 
 int rr_simulate_param_sets(rr_ctx* ctx, const float pose[7], const rr_param_set* sets, int n_sets, size_t n_materials,
                            uint8_t* out_imgs_u8, const uint8_t* ref_img_u8, double* out_psnr);
 
+/* ---- real-to-sim image metrics (rr_metrics.hip) -------------------------------------------------------------------
+ * The reference's calibration loop imports five metrics (scripts/radaray_opti.py: structural_similarity,
+ * peak_signal_noise_ratio, normalized_mutual_information, variation_of_information, mutual_info_score) and its evaluation
+ * launch file publishes a "real to sim gap" between /Navtech/Polar and /radar/image (launch/tests/eval_real_to_sim.launch).
+ * rr_compare_images_device computes all of them for n mono8 images in HBM against ONE reference image in HBM; one
+ * rr_image_metrics record per image comes back to the host.  Images are uint8 [n_cells][n_angles] in the context's current
+ * shape, N = n_cells * n_angles.
+ *   PSNR / SSE (RR_METRIC_PSNR): exactly what rr_score_images_device returns (the same bits).
+ *   SSIM (RR_METRIC_SSIM): skimage.metrics.structural_similarity on uint8 with its defaults -- a uniform w x w window
+ *     (w = win_size, odd, 3..15; skimage's default is 7), K1 = 0.01, K2 = 0.03, data_range = 255 (C1 = (K1 * 255)^2,
+ *     C2 = (K2 * 255)^2), sample covariance (cov_norm = w^2 / (w^2 - 1)); with ux, uy, uxx, uyy, uxy the window means of x, y,
+ *     x^2, y^2, xy:  vx = cov_norm (uxx - ux^2), vy likewise, vxy = cov_norm (uxy - ux uy),
+ *     S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2)), and ssim = the mean of S over the pixels whose whole
+ *     window lies inside the image (skimage's crop by (w - 1) / 2: no border rule is needed).  THE AZIMUTH AXIS IS NOT
+ *     WRAPPED: columns 0 and n_angles - 1 are not neighbours here, as they are not in skimage.  The five window sums are
+ *     exact integers, S and its mean are f64 in a fixed order.  win_size is read only with RR_METRIC_SSIM; an image smaller
+ *     than the window in either direction is refused (-3).
+ *   Joint histogram (RR_METRIC_INFO): H[a][b] = the number of pixels with image value a and reference value b, 256 x 256,
+ *     exact uint32.  In nats, f64, skipping empty bins:  hxy = ln N - (1/N) sum c ln c over the joint counts -- summed as
+ *     (1/N) sum c (ln N - ln c), the same number, which is exactly 0 when one bin holds every pixel -- and hx, hy the same
+ *     over the marginals of the image (a) and of the reference (b);
+ *     mi = hx + hy - hxy   (sklearn.metrics.mutual_info_score of the flattened images)
+ *     nmi = (hx + hy) / hxy  (skimage's normalized_mutual_information at one bin per grey level); hxy == 0 -- both images
+ *           constant, where skimage returns NaN -- gives nmi = 1
+ *     voi = 2 hxy - hx - hy  (the sum of skimage's two variation_of_information terms)
+ * `which` is a mask of RR_METRIC_* bits; the fields of a metric not asked for are 0.  d_joint_hist (HBM, uint32
+ * [n_images][256][256], or NULL) receives the histograms; it needs RR_METRIC_INFO.  Synchronous on `stream` like
+ * rr_score_images_device, and like it the call uses context-owned scratch (at most 64 images' histograms, 16 MB: more images
+ * are worked through in chunks), so one call per context at a time.  A config is needed, a mesh is not.
+ * Refused with a message and nothing written: -2 without a config; -3 for a null buffer, n_images outside 1..65535, which == 0
+ * or with unknown bits, an even or out-of-range win_size, an image smaller than the window, d_joint_hist without
+ * RR_METRIC_INFO. */
+#define RR_METRIC_PSNR 1u
+#define RR_METRIC_SSIM 2u
+#define RR_METRIC_INFO 4u
+typedef struct rr_image_metrics {
+    double psnr; uint64_t sse;
+    double ssim;
+    double hx, hy, hxy, mi, nmi, voi;
+} rr_image_metrics;
+int rr_compare_images_device(rr_ctx* ctx, const uint8_t* d_imgs_u8, int n_images, const uint8_t* d_ref_u8, uint32_t which,
+                             int win_size, rr_image_metrics* out /* host [n_images] */,
+                             uint32_t* d_joint_hist /* HBM [n_images][256][256], or NULL */, void* stream);
+/* The host-buffer form, for real images from a bag: imgs_u8 [n_images][n_cells][n_angles], ref_u8 [n_cells][n_angles],
+ * joint_hist host [n_images][256][256] or NULL.  Synchronous.  The images are staged 64 at a time; the records are written
+ * once all of them are done, the histograms chunk by chunk (a refusal writes nothing; a device error, -100, in a later
+ * chunk leaves `out` untouched and joint_hist with the chunks before it). */
+int rr_compare_images(rr_ctx* ctx, const uint8_t* imgs_u8, int n_images, const uint8_t* ref_u8, uint32_t which, int win_size,
+                      rr_image_metrics* out, uint32_t* joint_hist);
+/* rr_simulate_param_sets with any of the metrics as the objective: out [n_sets] records of the simulated images against
+ * ref_img_u8 (host, [n_cells][n_angles]); out_imgs_u8 (host) or NULL, and with NULL no image leaves the GPU. */
+int rr_simulate_param_sets_metrics(rr_ctx* ctx, const float pose[7], const rr_param_set* sets, int n_sets, size_t n_materials,
+                                   uint8_t* out_imgs_u8, const uint8_t* ref_img_u8, uint32_t which, int win_size,
+                                   rr_image_metrics* out);
+
 /* All frames of a multi-frame step in ONE launch: frame j reads its columns frame_stride bytes after
  * frame j-1 (block addressing as above) and writes image j of d_imgs_u8 [n_frames][n_cells][n_angles]. */
 int rr_assemble_frames_device(rr_ctx* ctx, const uint8_t* d_cols_u8, int n_loc, size_t block_stride,
@@ -615,6 +670,9 @@ void rr_free_mesh(rr_mesh* m);
  * RR_BVH_CHOOSE (1)       host builder, meshes up to 2M triangles: build the candidates (SAH with spatial splits; plain SAH with
  *                         vertical weight 0.5 / 1.0), trace one sample of radar-like rays through each, keep the tree with
  *                         the fewest traversal steps; 0: the default tree only (images are the same whichever tree)
+ * RR_METRICS_HIST (0)     1: rr_compare_images_device counts its joint histograms with global atomics instead of workgroup-private
+ *                         LDS histograms (the same counts, measured 24-32x slower: BASELINE.md §10; kept selectable for
+ *                         tools/probe_metrics.py)
  * RR_MULTI_LOOPBACK (0)   1: rr_create_multi accepts one device several times (tests, see above)
  * RR_MULTI_SELF_RCCL (0)  1 with ONE device: its block travels to itself through the real RCCL calls (one-rank communicator, a
  *                         group of ncclSend / ncclRecv to self; 2: one pair per frame, the ragged plan) instead of the

@@ -211,6 +211,44 @@ public:
         }
         return true;
     }
+    // ... and with any of the metrics the reference's script imports as the objective (SSIM, PSNR, NMI, VoI, mutual information:
+    // rr_image_metrics, include/radarays_mi355.h): one record per set against `real`; `images` may be null
+    bool simulateParamSetsMetrics(const std::vector<RadarParams>& sets, double stamp, std::vector<ImagePtr>* images, const Image& real,
+                                  uint32_t which, int win_size, std::vector<rr_image_metrics>* out)
+    {
+        if (!updateTsm()) { std::cout << "Couldn't get Transform between sensor and map. Skipping..." << std::endl; return false; }
+        if (!push()) return false;
+        const size_t n_mat = m_params.materials.size(), nb = m_params.model.n_samples;
+        const size_t npx = (size_t)m_cfg.n_cells * m_n_angles;
+        if (real.data.size() != npx || !out) { m_err = "the real image must be n_cells x n_angles mono8 (and out given)"; return false; }
+        marshal::ParamSetBatch b;
+        if (!b.build(sets, [](const RadarParams& p) -> const auto& { return p.materials; }, n_mat, nb,
+                     m_params.model.beam_width, m_beam_seed, m_cfg.beam_sample_dist, (float)m_cfg.beam_sample_dist_normal_p_in_cone, m_err)) return false;
+        std::vector<uint8_t> px(images ? sets.size() * npx : 0);
+        out->assign(sets.size(), rr_image_metrics{});
+        if (!b.run_metrics(m_ctx, Tsm_last, n_mat, images ? px.data() : nullptr, real.data.data(), which, win_size, out->data())) { fail(); return false; }
+        if (images) {
+            images->clear();
+            for (size_t k = 0; k < sets.size(); k++) images->push_back(image(&px[k * npx], stamp));
+        }
+        return true;
+    }
+    // The "real to sim gap" (launch/tests/eval_real_to_sim.launch): mono8 polar images of this model's shape against ONE
+    // real image, one record per image (fields of metrics not in `which` are 0).  Empty on error (lastError()).
+    std::vector<rr_image_metrics> compareImages(const std::vector<ImagePtr>& images, const Image& real,
+                                                uint32_t which = RR_METRIC_PSNR | RR_METRIC_SSIM | RR_METRIC_INFO, int win_size = 7)
+    {
+        std::vector<rr_image_metrics> out;
+        if (images.empty() || !push()) return out;
+        const size_t npx = (size_t)m_cfg.n_cells * m_n_angles;
+        bool ok = real.height == (uint32_t)m_cfg.n_cells && real.width == (uint32_t)m_n_angles && real.data.size() == npx;
+        for (const ImagePtr& im : images) ok = ok && im && im->height == real.height && im->width == real.width && im->data.size() == npx;
+        if (!ok) { m_err = "compareImages: every image must be n_cells x n_angles mono8"; std::cout << "[RadarHIP] " << m_err << std::endl; return out; }
+        if (!marshal::compare_images(m_ctx, images.size(), npx, [&](size_t k) { return images[k]->data.data(); }, real.data.data(), which, win_size, out)) {
+            fail(); out.clear();
+        }
+        return out;
+    }
     const std::string& lastError() const { return m_err; }
     // radar_tools/radar_img_to_pcl (launch/tests/radar_sim_test.launch:80-84, outside the checkout) on the GPU: one mono8
     // polar image of this model's shape (simulated or real) -> its detections, a PointCloud's points plus the intensity

@@ -128,6 +128,24 @@ struct ParamSetBatch {
     {
         return rr_simulate_param_sets(ctx, pose, ps.data(), (int)ps.size(), n_mat, pixels, real, psnr) == 0;
     }
+    // the same with any of the image metrics as the objective: one record per set against `real` (pixels may be null)
+    bool run_metrics(rr_ctx* ctx, const float pose[7], size_t n_mat, uint8_t* pixels, const uint8_t* real, uint32_t which, int win_size,
+                     rr_image_metrics* out) const
+    {
+        return rr_simulate_param_sets_metrics(ctx, pose, ps.data(), (int)ps.size(), n_mat, pixels, real, which, win_size, out) == 0;
+    }
 };
+
+// n mono8 images (each npx bytes, wherever they lie) against one real image: one record per image.  image_pixels(k) gives
+// image k's bytes.  false: rr_last_error(ctx)
+template <typename PixelsOf>
+bool compare_images(rr_ctx* ctx, size_t n, size_t npx, PixelsOf image_pixels, const uint8_t* real, uint32_t which, int win_size,
+                    std::vector<rr_image_metrics>& out)
+{
+    std::vector<uint8_t> flat(n * npx);
+    for (size_t k = 0; k < n; k++) std::copy(image_pixels(k), image_pixels(k) + npx, flat.begin() + (std::ptrdiff_t)(k * npx));
+    out.assign(n, rr_image_metrics{});
+    return rr_compare_images(ctx, flat.data(), (int)n, real, which, win_size, out.data(), nullptr) == 0;
+}
 
 }  // namespace radarays_ros_amd::marshal

@@ -259,6 +259,34 @@ int check_ready(rr_ctx* c)
     return 0;
 }
 
+// the refusals of rr_compare_images_device / rr_compare_images / rr_simulate_param_sets_metrics
+int check_compare(rr_ctx* c, const char* who, const void* imgs, int n_images, const void* ref, uint32_t which, int win_size, const void* out,
+                  const void* hist)
+{
+    if (!c) return -1;
+    if (!c->have_cfg) return fail(c, -2, "rr_set_config has not been called");
+    const std::string w(who);
+    if (!imgs || !ref || !out) return fail(c, -3, w + ": null buffer");
+    if (n_images < 1 || n_images > 65535) return fail(c, -3, w + ": n_images must be 1..65535");
+    const uint32_t all = RR_METRIC_PSNR | RR_METRIC_SSIM | RR_METRIC_INFO;
+    if (which == 0 || (which & ~all)) return fail(c, -3, w + ": which must be a non-empty mask of RR_METRIC_PSNR | RR_METRIC_SSIM | RR_METRIC_INFO");
+    if (which & RR_METRIC_SSIM) {
+        if (win_size < 3 || win_size > 15 || win_size % 2 == 0) return fail(c, -3, w + ": win_size must be odd and in 3..15");
+        if (c->cfg.n_cells < win_size || c->cfg.n_angles < win_size)
+            return fail(c, -3, w + ": the image (" + std::to_string(c->cfg.n_cells) + " x " + std::to_string(c->cfg.n_angles) + ") is smaller than the window");
+    }
+    if (hist && !(which & RR_METRIC_INFO)) return fail(c, -3, w + ": a joint histogram buffer needs RR_METRIC_INFO");
+    return 0;
+}
+
+// skimage.metrics.peak_signal_noise_ratio for uint8 (scripts/radaray_opti.py:196): data_range 255,
+// err = mean of the squared differences in f64 (exact here: an integer sum below 2^53), 10 log10(255^2 / err)
+double psnr_of(uint64_t sse, size_t npx)
+{
+    const double err = (double)sse / (double)npx;
+    return err > 0.0 ? 10.0 * std::log10((255.0 * 255.0) / err) : INFINITY;
+}
+
 }  // namespace rr
 
 // ---------------------------------------------------------------------------
@@ -330,6 +358,7 @@ rr_ctx* rr_create(int device)
     if (getenv("RR_GRAPHS")) c->use_graphs = atoi(getenv("RR_GRAPHS")) != 0;
     if (getenv("RR_HOST_SDMA")) c->host_sdma = atoi(getenv("RR_HOST_SDMA")) != 0;
     if (getenv("RR_TIGHT_GRID")) c->tight_grid = atoi(getenv("RR_TIGHT_GRID")) != 0;
+    if (getenv("RR_METRICS_HIST")) c->metrics_hist = atoi(getenv("RR_METRICS_HIST")) != 0;
     if (getenv("RR_TIGHT_FORCE")) c->tight_force = std::max(0, atoi(getenv("RR_TIGHT_FORCE")));
     {   // the one angle of total reflection that does not depend on the material table
         const float4 same = make_float4(0.3f, 0.f, 0.f, 0.f);
@@ -371,7 +400,7 @@ void rr_destroy(rr_ctx* c)
     c->d_rest_v.release(); c->d_stage_v.release(); c->d_rest_f.release(); c->d_poses.release(); c->d_stage_poses.release();
     c->d_levels.release(); c->d_red.release(); c->d_cost.release(); c->d_built.release(); c->d_moved.release();
     c->d_bvh.release(); c->d_qas.release(); c->d_beams.release(); c->d_materials.release(); c->d_mat_limits.release();
-    c->d_objmat.release(); c->d_smear.release(); c->d_noise.release(); c->d_decay.release(); c->d_param_imgs.release(); c->d_sse.release(); c->d_ref_img.release(); c->d_conv_in.release(); c->d_conv_cart.release(); c->d_conv_points.release(); c->d_conv_offs.release(); c->d_beam_order.release(); c->d_beam_order2.release(); c->d_motion.release();
+    c->d_objmat.release(); c->d_smear.release(); c->d_noise.release(); c->d_decay.release(); c->d_param_imgs.release(); c->d_sse.release(); c->d_ref_img.release(); c->d_mhist.release(); c->d_conv_hist.release(); c->d_ssim_part.release(); c->d_mrec.release(); c->d_conv_in.release(); c->d_conv_cart.release(); c->d_conv_points.release(); c->d_conv_offs.release(); c->d_beam_order.release(); c->d_beam_order2.release(); c->d_motion.release();
     for (Lane& L : c->lanes) {
         if (L.stream) (void)hipStreamSynchronize(L.stream);
         for (int k = 0; k < 2; k++) { L.d_wA[k].release(); L.d_wB[k].release(); L.d_wC[k].release(); L.d_idx[k].release(); L.d_count[k].release(); L.d_torder[k].release(); }
@@ -509,12 +538,83 @@ int rr_score_images_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_images, co
     for (int k = 0; k < n_images; k++) {
         if (out_sse) out_sse[k] = sse[(size_t)k];
         if (out_psnr) {
-            // skimage.metrics.peak_signal_noise_ratio for uint8 (scripts/radaray_opti.py:196): data_range 255,
-            // err = mean of the squared differences in f64 (exact here: an integer sum below 2^53), 10 log10(255^2 / err)
-            const double err = (double)sse[(size_t)k] / (double)npx;
-            out_psnr[k] = err > 0.0 ? 10.0 * std::log10((255.0 * 255.0) / err) : INFINITY;
+            out_psnr[k] = psnr_of(sse[(size_t)k], npx);
         }
     }
+    return 0;
+}
+
+// ---- images against one reference image: PSNR, SSIM, joint histogram and its entropies (rr_metrics.hip) --------------
+
+int rr_compare_images_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_images, const uint8_t* d_ref_u8, uint32_t which, int win_size,
+                             rr_image_metrics* out, uint32_t* d_joint_hist, void* stream)
+{
+    int rc = check_compare(c, "rr_compare_images_device", d_imgs_u8, n_images, d_ref_u8, which, win_size, out, d_joint_hist); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = stream_of(c, stream);
+    const rr_config& g = c->cfg;
+    const size_t npx = (size_t)g.n_cells * g.n_angles, n = (size_t)n_images;
+    const bool psnr = which & RR_METRIC_PSNR, ssim = which & RR_METRIC_SSIM, info = which & RR_METRIC_INFO;
+    constexpr size_t kChunk = 64, kBins = 65536;        // histogram scratch: 256 KB per image, at most 64 images' worth
+    const size_t chunk = std::min(n, kChunk);
+    const int n_blocks = ssim ? ssim_blocks(g.n_cells, g.n_angles, win_size) : 0;
+    const double ssim_count = ssim ? (double)(g.n_cells - win_size + 1) * (double)(g.n_angles - win_size + 1) : 1.0;
+    const bool own_hist = info && !d_joint_hist;
+    if ((psnr && c->d_sse.n < n) || (own_hist && c->d_mhist.n < chunk * kBins) || (ssim && c->d_ssim_part.n < chunk * (size_t)n_blocks) || c->d_mrec.n < n) {
+        RR_HIP(c, hipStreamSynchronize(s));             // an earlier call's kernels may still read what is freed here
+        if (psnr) RR_HIP(c, c->d_sse.ensure(n));
+        if (own_hist) RR_HIP(c, c->d_mhist.ensure(chunk * kBins));
+        if (ssim) RR_HIP(c, c->d_ssim_part.ensure(chunk * (size_t)n_blocks));
+        RR_HIP(c, c->d_mrec.ensure(n));
+    }
+    if (psnr) {
+        RR_HIP(c, hipMemsetAsync(c->d_sse.p, 0, n * sizeof(uint64_t), s));
+        launch_score(d_imgs_u8, d_ref_u8, npx, n_images, c->d_sse.p, s);
+    }
+    for (size_t at = 0; at < n; at += kChunk) {
+        const int m = (int)std::min(kChunk, n - at);
+        const uint8_t* imgs = d_imgs_u8 + at * npx;
+        uint32_t* H = !info ? nullptr : d_joint_hist ? d_joint_hist + at * kBins : c->d_mhist.p;
+        if (info) {
+            RR_HIP(c, hipMemsetAsync(H, 0, (size_t)m * kBins * sizeof(uint32_t), s));
+            launch_joint_hist(imgs, d_ref_u8, npx, m, H, c->metrics_hist, s);
+        }
+        if (ssim) launch_ssim(imgs, d_ref_u8, g.n_cells, g.n_angles, win_size, m, c->d_ssim_part.p, s);
+        launch_metrics_finish(H, ssim ? c->d_ssim_part.p : nullptr, n_blocks, ssim_count, psnr ? c->d_sse.p + at : nullptr, npx,
+                              c->d_mrec.p + at, m, s);
+    }
+    RR_HIP(c, hipGetLastError());
+    std::vector<rr_image_metrics> rec(n);
+    RR_HIP(c, hipMemcpyAsync(rec.data(), c->d_mrec.p, n * sizeof(rr_image_metrics), hipMemcpyDeviceToHost, s));
+    RR_HIP(c, hipStreamSynchronize(s));
+    for (size_t k = 0; k < n; k++) {
+        if (psnr) rec[k].psnr = psnr_of(rec[k].sse, npx);     // the host's log10, as rr_score_images_device: the same bits
+        out[k] = rec[k];
+    }
+    return 0;
+}
+
+int rr_compare_images(rr_ctx* c, const uint8_t* imgs_u8, int n_images, const uint8_t* ref_u8, uint32_t which, int win_size,
+                      rr_image_metrics* out, uint32_t* joint_hist)
+{
+    int rc = check_compare(c, "rr_compare_images", imgs_u8, n_images, ref_u8, which, win_size, out, joint_hist); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles, n = (size_t)n_images, kChunk = 64, kBins = 65536;
+    RR_HIP(c, hipStreamSynchronize(c->stream));        // the staging buffers may be reallocated below
+    RR_HIP(c, c->d_conv_in.ensure(std::min(n, kChunk) * npx));
+    RR_HIP(c, c->d_ref_img.ensure(npx));
+    if (joint_hist) RR_HIP(c, c->d_conv_hist.ensure(std::min(n, kChunk) * kBins));
+    RR_HIP(c, hipMemcpyAsync(c->d_ref_img.p, ref_u8, npx, hipMemcpyHostToDevice, c->stream));
+    std::vector<rr_image_metrics> rec(n);              // (the caller's records are written once every chunk has succeeded)
+    for (size_t at = 0; at < n; at += kChunk) {
+        const size_t m = std::min(kChunk, n - at);
+        RR_HIP(c, hipMemcpyAsync(c->d_conv_in.p, imgs_u8 + at * npx, m * npx, hipMemcpyHostToDevice, c->stream));
+        // one chunk of the device form, its histograms into this form's own staging buffer
+        rc = rr_compare_images_device(c, c->d_conv_in.p, (int)m, c->d_ref_img.p, which, win_size, rec.data() + at,
+                                      joint_hist ? c->d_conv_hist.p : nullptr, c->stream); if (rc) return rc;
+        if (joint_hist) RR_HIP(c, hipMemcpy(joint_hist + at * kBins, c->d_conv_hist.p, m * kBins * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    std::copy(rec.begin(), rec.end(), out);
     return 0;
 }
 

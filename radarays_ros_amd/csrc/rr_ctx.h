@@ -173,8 +173,11 @@ struct rr_ctx {
 
     int passes_override = -1;    // a parameter batch in the making: the largest n_reflections of its sets sizes queues and launch loops
     DevBuf<unsigned long long> d_sse; DevBuf<uint8_t> d_ref_img;     // rr_score_images / rr_simulate_param_sets
+    // rr_compare_images_device: histograms of one chunk of images, SSIM partials [image][block], the records; RR_METRICS_HIST
+    DevBuf<uint32_t> d_mhist; DevBuf<double> d_ssim_part; DevBuf<rr_image_metrics> d_mrec; int metrics_hist = 0;
     // staging of the host forms of rr_detect / rr_polar_to_cartesian (the device forms use none of it)
     DevBuf<uint8_t> d_conv_in, d_conv_cart; DevBuf<rr_radar_point> d_conv_points; DevBuf<uint32_t> d_conv_offs;
+    DevBuf<uint32_t> d_conv_hist;      // ... and of rr_compare_images: one chunk's joint histograms on their way to the host
     void* h_rb = nullptr; size_t h_rb_bytes = 0;         // page-locked: read_back()
     void* h_frame = nullptr; size_t h_frame_bytes = 0;   // page-locked: error bits + per-pass counters of rr_simulate's frame
 
@@ -258,6 +261,8 @@ int upload_tables(rr_ctx* c);
 void beam_trace_orders(const float* beams, size_t nb, std::vector<uint32_t>& order, std::vector<uint32_t>& order2);
 int read_back(rr_ctx* c, void* dst, const void* d_src, size_t bytes);
 int overflow_error(rr_ctx* c, uint32_t bits, bool since_sync = false);
+int check_compare(rr_ctx* c, const char* who, const void* imgs, int n_images, const void* ref, uint32_t which, int win_size, const void* out,
+                  const void* hist);      // the refusals of rr_compare_images* / rr_simulate_param_sets_metrics
 // the counters of the lane the last frame ran on (the callers have synchronised)
 inline int read_counters(rr_ctx* c, Counters& h) { return read_back(c, &h, c->lanes[c->last_lane].d_counters.p, sizeof(h)); }
 

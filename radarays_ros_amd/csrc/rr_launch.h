@@ -1,4 +1,4 @@
-// rr_launch.h -- every launcher of rr_kernels.hip, rr_refit.hip, rr_detect.hip and rr_lbvh.hip, declared ONCE: included where they
+// rr_launch.h -- every launcher of rr_kernels.hip, rr_refit.hip, rr_detect.hip, rr_metrics.hip and rr_lbvh.hip, declared ONCE: included where they
 // are defined (a definition that drifts from its declaration fails there) and where they are called.  Default arguments live here only.
 #pragma once
 #include "../../include/radarays_mi355.h"
@@ -42,6 +42,12 @@ void launch_detect(const uint8_t* imgs, int n_frames, const rr_detect_config& cf
                    uint32_t* offsets, hipStream_t s);
 void launch_cartesian(const uint8_t* imgs, int n_frames, const rr_cartesian_config& cfg, int n_cells, int n_angles, int scroll,
                       float theta_min, float theta_inc, float res, uint8_t* out, hipStream_t s);
+// rr_metrics.hip (images against one reference image).  hist_shape 0: workgroup-private LDS histograms, 1: global atomics
+void launch_joint_hist(const uint8_t* imgs, const uint8_t* ref, size_t npx, int n_images, uint32_t* hist, int hist_shape, hipStream_t s);
+int ssim_blocks(int n_cells, int n_angles, int win);          // workgroups (= f64 partials) per image of launch_ssim
+void launch_ssim(const uint8_t* imgs, const uint8_t* ref, int n_cells, int n_angles, int win, int n_images, double* partial, hipStream_t s);
+void launch_metrics_finish(const uint32_t* hist, const double* ssim_part, int n_blocks, double ssim_count, const unsigned long long* sse,
+                           size_t npx, rr_image_metrics* out, int n_images, hipStream_t s);
 void launch_copy_host(const void* src, void* dst, size_t bytes, int blocks, int xcd, hipStream_t s);
 void launch_copy_words(const void* src, void* dst, size_t bytes, hipStream_t s);
 void launch_debug_brdf(size_t n, const float* in, int model, float* out, hipStream_t s);

@@ -121,7 +121,8 @@ int rr_simulate_material_sets_device(rr_ctx* c, const float pose[7], const rr_ma
 
 namespace {
 // the images of a parameter batch in c->d_param_imgs: copy out and / or score, report the frame's error bits
-int finish_param_batch(rr_ctx* c, int n_sets, uint8_t* out_imgs_u8, const uint8_t* ref_img_u8, double* out_psnr)
+int finish_param_batch(rr_ctx* c, int n_sets, uint8_t* out_imgs_u8, const uint8_t* ref_img_u8, double* out_psnr,
+                       uint32_t which = 0, int win_size = 0, rr_image_metrics* out_metrics = nullptr)
 {
     const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles;
     if (out_imgs_u8) RR_HIP(c, hipMemcpyAsync(out_imgs_u8, c->d_param_imgs.p, (size_t)n_sets * npx, hipMemcpyDeviceToHost, c->stream));
@@ -129,6 +130,12 @@ int finish_param_batch(rr_ctx* c, int n_sets, uint8_t* out_imgs_u8, const uint8_
         RR_HIP(c, c->d_ref_img.ensure(npx));
         RR_HIP(c, hipMemcpyAsync(c->d_ref_img.p, ref_img_u8, npx, hipMemcpyHostToDevice, c->stream));
         const int rc = rr_score_images_device(c, c->d_param_imgs.p, n_sets, c->d_ref_img.p, out_psnr, nullptr, c->stream);   // synchronises the stream
+        if (rc) return rc;
+    }
+    if (ref_img_u8 && out_metrics) {
+        RR_HIP(c, c->d_ref_img.ensure(npx));
+        RR_HIP(c, hipMemcpyAsync(c->d_ref_img.p, ref_img_u8, npx, hipMemcpyHostToDevice, c->stream));
+        const int rc = rr_compare_images_device(c, c->d_param_imgs.p, n_sets, c->d_ref_img.p, which, win_size, out_metrics, nullptr, c->stream);
         if (rc) return rc;
     }
     RR_HIP(c, hipStreamSynchronize(c->stream));
@@ -164,6 +171,19 @@ int rr_simulate_param_sets(rr_ctx* c, const float pose[7], const rr_param_set* s
     RR_HIP(c, c->d_param_imgs.ensure(bytes));
     int rc = rr_simulate_param_sets_device(c, pose, sets, n_sets, n_materials, c->d_param_imgs.p, c->stream); if (rc) return rc;
     return finish_param_batch(c, n_sets, out_imgs_u8, ref_img_u8, out_psnr);
+}
+
+int rr_simulate_param_sets_metrics(rr_ctx* c, const float pose[7], const rr_param_set* sets, int n_sets, size_t n_materials,
+                                   uint8_t* out_imgs_u8, const uint8_t* ref_img_u8, uint32_t which, int win_size, rr_image_metrics* out)
+{
+    // refused before anything is simulated (d_param_imgs stands in for the images: they are the context's own)
+    int rc = check_compare(c, "rr_simulate_param_sets_metrics", c, 1, ref_img_u8, which, win_size, out, nullptr); if (rc) return rc;
+    if (n_sets < 1 || n_sets > RR_MAX_BATCH) return fail(c, -3, "rr_simulate_param_sets_metrics: n_sets must be 1..64");
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)n_sets * c->cfg.n_cells * c->cfg.n_angles;
+    RR_HIP(c, c->d_param_imgs.ensure(bytes));
+    rc = rr_simulate_param_sets_device(c, pose, sets, n_sets, n_materials, c->d_param_imgs.p, c->stream); if (rc) return rc;
+    return finish_param_batch(c, n_sets, out_imgs_u8, ref_img_u8, nullptr, which, win_size, out);
 }
 
 }  // extern "C"

@@ -31,6 +31,7 @@ SYMBOLS = [
     "rr_set_object_poses", "rr_update_vertices", "rr_get_tree_cost", "rr_rebuild_tree",
     "rr_multi_set_object_poses", "rr_multi_update_vertices", "rr_multi_rebuild_tree",
     "rr_default_detect_config", "rr_detect_device", "rr_detect", "rr_polar_to_cartesian_device", "rr_polar_to_cartesian",
+    "rr_compare_images_device", "rr_compare_images", "rr_simulate_param_sets_metrics",
 ]
 
 
@@ -90,6 +91,85 @@ POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("intensity", 
 # rr_default_detect_config
 DETECT_DEFAULTS = {"method": 0, "guard_cells": 2, "train_cells": 16, "k": 12, "min_intensity": 1, "min_bin": 0, "cfar_scale": 3.0}
 DETECT_METHODS = {"cfar": 0, "ca-cfar": 0, "kstrongest": 1, "k-strongest": 1, 0: 0, 1: 1}
+
+
+class RRImageMetrics(C.Structure):
+    _fields_ = [("psnr", C.c_double), ("sse", C.c_uint64), ("ssim", C.c_double), ("hx", C.c_double), ("hy", C.c_double),
+                ("hxy", C.c_double), ("mi", C.c_double), ("nmi", C.c_double), ("voi", C.c_double)]
+
+
+# rr_image_metrics as numpy sees it (72 B), and the RR_METRIC_* bits of `which`
+METRICS_DTYPE = np.dtype([("psnr", "<f8"), ("sse", "<u8"), ("ssim", "<f8"), ("hx", "<f8"), ("hy", "<f8"), ("hxy", "<f8"),
+                          ("mi", "<f8"), ("nmi", "<f8"), ("voi", "<f8")])
+METRIC_PSNR, METRIC_SSIM, METRIC_INFO = 1, 2, 4
+METRIC_ALL = METRIC_PSNR | METRIC_SSIM | METRIC_INFO
+METRIC_NAMES = {"psnr": METRIC_PSNR, "ssim": METRIC_SSIM, "info": METRIC_INFO}
+
+
+def metrics_mask(which):
+    """RR_METRIC_* mask from an int, a name ("psnr", "ssim", "info") or an iterable of names; ValueError otherwise"""
+    if isinstance(which, str):
+        which = [which]
+    if isinstance(which, (int, np.integer)) and not isinstance(which, bool):
+        m = int(which)
+    else:
+        try:
+            m = 0
+            for w in which:
+                m |= METRIC_NAMES[w]
+        except (TypeError, KeyError):
+            raise ValueError("metrics must be a mask of METRIC_PSNR | METRIC_SSIM | METRIC_INFO or names from %s, got %r" % (sorted(METRIC_NAMES), which))
+    if m <= 0 or m & ~METRIC_ALL:
+        raise ValueError("metrics must be a non-empty mask of METRIC_PSNR | METRIC_SSIM | METRIC_INFO, got %r" % (which,))
+    return m
+
+
+def _win_arg(which, win_size):
+    if which & METRIC_SSIM and (isinstance(win_size, bool) or not isinstance(win_size, (int, np.integer)) or not 3 <= win_size <= 15 or win_size % 2 == 0):
+        raise ValueError("win_size must be an odd integer in 3..15, got %r" % (win_size,))
+    return int(win_size)
+
+
+def entropies_from_counts(H):
+    """hx, hy, hxy, mi, nmi, voi (nats, the definitions of include/radarays_mi355.h) of a 2-D array of joint counts"""
+    H = np.asarray(H, np.float64)
+    n = H.sum()
+
+    def ent(c):
+        c = c[c > 0]
+        return float(np.sum(c * (np.log(n) - np.log(c))) / n)
+    hx, hy, hxy = ent(H.sum(1)), ent(H.sum(0)), ent(H.ravel())
+    return {"hx": hx, "hy": hy, "hxy": hxy, "mi": hx + hy - hxy, "nmi": 1.0 if hxy == 0.0 else (hx + hy) / hxy, "voi": 2.0 * hxy - hx - hy}
+
+
+def metrics_from_joint_histogram(H, bins=256):
+    """The information metrics from one exact joint histogram (uint32 [256][256], H[a][b] = pixels with image value a and
+    reference value b) without a second pass over the images.  bins = 256: one bin per grey level, what the library's
+    record holds.  Fewer bins (skimage's normalized_mutual_information defaults to 100): the counts are regrouped by numpy's
+    histogram rule -- per image, `bins` equal-width bins over its own min..max (read off the non-empty marginals; a constant
+    image gets min - 0.5 .. max + 0.5), a value on an inner edge goes to the bin on its right, the maximum to the last bin."""
+    H = np.asarray(H)
+    if H.shape != (256, 256):
+        raise ValueError("joint histogram must be [256][256], got %s" % (H.shape,))
+    bins = _int_in(bins, 1, 256, "bins")
+    if H.sum() == 0:
+        raise ValueError("empty joint histogram")
+    if bins == 256:
+        return entropies_from_counts(H)
+    idx = []
+    for marg in (H.sum(1), H.sum(0)):
+        used = np.nonzero(marg)[0]
+        lo, hi = float(used[0]), float(used[-1])
+        if lo == hi:
+            lo, hi = lo - 0.5, hi + 0.5
+        edges = np.linspace(lo, hi, bins + 1)
+        g = np.arange(256, dtype=np.float64)
+        i = np.searchsorted(edges, g, side="right") - 1
+        i[g == edges[-1]] = bins - 1
+        idx.append(np.clip(i, 0, bins - 1))          # (levels outside min..max hold no pixels)
+    B = np.zeros((bins, bins), np.int64)
+    np.add.at(B, (idx[0][:, None], idx[1][None, :]), H.astype(np.int64))
+    return entropies_from_counts(B)
 
 
 class RRStats(C.Structure):
@@ -223,6 +303,9 @@ def lib():
     L.rr_detect.argtypes = [vp, vp, C.c_int, C.POINTER(RRDetectConfig), vp, C.c_int, vp]
     L.rr_polar_to_cartesian_device.argtypes = [vp, vp, C.c_int, C.POINTER(RRCartesianConfig), vp, vp]
     L.rr_polar_to_cartesian.argtypes = [vp, vp, C.c_int, C.POINTER(RRCartesianConfig), vp]
+    L.rr_compare_images_device.argtypes = [vp, vp, C.c_int, vp, C.c_uint32, C.c_int, vp, vp, vp]
+    L.rr_compare_images.argtypes = [vp, vp, C.c_int, vp, C.c_uint32, C.c_int, vp, vp]
+    L.rr_simulate_param_sets_metrics.argtypes = [vp, vp, C.POINTER(RRParamSet), C.c_int, C.c_size_t, vp, vp, C.c_uint32, C.c_int, vp]
     for n in SYMBOLS:
         getattr(L, n)
     _LIB = L
@@ -564,13 +647,24 @@ class Context:
             arr[k].n_reflections = -1 if nr is None else int(nr)
         return arr, keep, n_mat
 
-    def simulate_param_sets(self, pose, sets, n_materials, ref_u8=None, want_images=True):
+    def simulate_param_sets(self, pose, sets, n_materials, ref_u8=None, want_images=True, metrics=None, win_size=7):
         """rr_simulate_param_sets: one pose, n parameter sets (see _param_sets).  Returns (images uint8
-        [n][n_cells][n_angles] or None, psnr float64 [n] or None against ref_u8)."""
+        [n][n_cells][n_angles] or None, psnr float64 [n] or None against ref_u8).  With `metrics` (a METRIC_* mask or names,
+        see metrics_mask) the second value is a METRICS_DTYPE array [n] instead: rr_simulate_param_sets_metrics."""
         arr, keep, n_mat = self._param_sets(sets)
         p = np.ascontiguousarray(pose, dtype=np.float32)
         n_cells = self.cfg.n_cells if self.cfg is not None else 1
         out = np.zeros((len(sets), n_cells, self.n_angles), dtype=np.uint8) if want_images else None
+        if metrics is not None:
+            which = metrics_mask(metrics)
+            win = _win_arg(which, win_size)
+            ref = None if ref_u8 is None else np.ascontiguousarray(ref_u8, np.uint8)
+            if ref is None or ref.shape != (n_cells, self.n_angles):
+                raise ValueError("metrics need a reference image [n_cells][n_angles] uint8")
+            rec = np.zeros(len(sets), METRICS_DTYPE)
+            self._ck(self._L.rr_simulate_param_sets_metrics(self._h, p.ctypes.data, arr, len(sets), int(n_materials),
+                                                            None if out is None else out.ctypes.data, ref.ctypes.data, which, win, rec.ctypes.data))
+            return out, rec
         psnr = ref = None
         if ref_u8 is not None:
             ref = np.ascontiguousarray(ref_u8, np.uint8)
@@ -592,6 +686,35 @@ class Context:
         psnr = np.zeros(n_images, np.float64); sse = np.zeros(n_images, np.uint64)
         self._ck(self._L.rr_score_images_device(self._h, d_imgs_ptr, int(n_images), d_ref_ptr, psnr.ctypes.data, sse.ctypes.data, stream))
         return (psnr, sse) if want_sse else psnr
+
+    # ---- images against one reference image (rr_metrics.hip): PSNR, SSIM, joint histogram and its entropies
+    def compare_images_device(self, d_imgs_ptr, n_images, d_ref_ptr, which=METRIC_ALL, win_size=7, d_joint_hist_ptr=None, stream=None):
+        """rr_compare_images_device: n images [n][n_cells][n_angles] and one reference image in HBM -> METRICS_DTYPE array [n];
+        d_joint_hist_ptr (HBM, uint32 [n][256][256]) receives the joint histograms.  Synchronous on `stream`."""
+        self._polar_shape()
+        which = metrics_mask(which)
+        win = _win_arg(which, win_size)
+        n = _frames_arg(n_images)
+        if not d_imgs_ptr or not d_ref_ptr:
+            raise ValueError("compare_images_device needs image and reference buffers")
+        rec = np.zeros(n, METRICS_DTYPE)
+        self._ck(self._L.rr_compare_images_device(self._h, d_imgs_ptr, n, d_ref_ptr, which, win, rec.ctypes.data, d_joint_hist_ptr, stream))
+        return rec
+
+    def compare_images(self, imgs, ref, which=METRIC_ALL, win_size=7, want_hist=False):
+        """rr_compare_images on host images [n][n_cells][n_angles] (or one image) against ref [n_cells][n_angles] ->
+        METRICS_DTYPE array [n], and with want_hist the joint histograms uint32 [n][256][256] as well"""
+        x = self._polar_images(imgs)
+        r = self._polar_images(ref)
+        if len(r) != 1:
+            raise ValueError("one reference image, got %d" % len(r))
+        which = metrics_mask(which)
+        win = _win_arg(which, win_size)
+        rec = np.zeros(len(x), METRICS_DTYPE)
+        hist = np.zeros((len(x), 256, 256), np.uint32) if want_hist else None
+        self._ck(self._L.rr_compare_images(self._h, x.ctypes.data, len(x), r.ctypes.data, which, win, rec.ctypes.data,
+                                           None if hist is None else hist.ctypes.data))
+        return (rec, hist) if want_hist else rec
 
     def simulate_device(self, pose, d_img_ptr, stream=None):
         p = np.ascontiguousarray(pose, np.float32)

@@ -180,6 +180,16 @@ class RadarHIP:
         self._ctx.synchronize(s)
         return out
 
+    # ---- the "real to sim gap" (launch/tests/eval_real_to_sim.launch) and the optimiser's other objectives
+    # (scripts/radaray_opti.py imports SSIM, PSNR, NMI, VoI and mutual information), on the GPU (rr_metrics.hip)
+    def compareImages(self, images, real, which=native.METRIC_ALL, win_size=7):
+        """mono8 polar Images (or arrays; one or a list, this model's shape) against ONE real image -> a native.METRICS_DTYPE
+        array with one record per image: psnr, sse, ssim, hx, hy, hxy, mi, nmi, voi (fields not asked for are 0)"""
+        self._push()
+        if isinstance(images, Image) or (isinstance(images, np.ndarray) and images.ndim == 2):
+            images = [images]
+        return self._ctx.compare_images(np.stack([self._polar(im) for im in images]), self._polar(real), which, win_size)
+
     def _push(self):
         if self._dirty_cfg:
             cfg = self.m_cfg.copy(n_reflections=self.m_params.model.n_reflections)
@@ -260,11 +270,13 @@ class RadarHIP:
         return [Image(header=Header(stamp=stamp, frame_id=self.m_sensor_frame), height=u8.shape[0], width=u8.shape[1],
                       encoding="mono8", step=u8.shape[1], data=u8) for u8 in imgs]
 
-    def simulateParamSets(self, sets, stamp=0.0, real=None, want_images=True):
+    def simulateParamSets(self, sets, stamp=0.0, real=None, want_images=True, metrics=None, win_size=7):
         """The same action over the optimiser's WHOLE parameter vector (scripts/radaray_opti.py:36-113): `sets` is a list
         of RadarParams (materials + model.beam_width [rad] / n_samples / n_reflections); one rr_simulate_param_sets call.
         Beams are drawn like _push() draws them (same seed: equal widths share pass 0).  Returns (images or None,
-        psnr or None) -- with `real` (mono8 [n_cells][400]) the objective values of radaray_opti.py:196."""
+        psnr or None) -- with `real` (mono8 [n_cells][400]) the objective values of radaray_opti.py:196.  With `metrics`
+        (a native.METRIC_* mask or names) the second value is a native.METRICS_DTYPE array instead: any of the script's
+        metrics as the objective (rr_simulate_param_sets_metrics)."""
         if not self.updateTsm():
             print("Couldn't get Transform between sensor and map. Skipping...")
             return None, None
@@ -279,7 +291,8 @@ class RadarHIP:
                 dirs = beams.sample_cone_local_rad(p.model.beam_width, nb, self.m_cfg.beam_sample_dist,
                                                    self.m_cfg.beam_sample_dist_normal_p_in_cone, seed=self._beam_seed)
             ps.append({"materials": [m.astuple() for m in p.materials], "beam_dirs": dirs, "n_reflections": int(p.model.n_reflections)})
-        imgs, psnr = self._ctx.simulate_param_sets(self.Tsm_last, ps, n_mat, ref_u8=real, want_images=want_images)
+        imgs, psnr = self._ctx.simulate_param_sets(self.Tsm_last, ps, n_mat, ref_u8=None if real is None else self._polar(real),
+                                                   want_images=want_images, metrics=metrics, win_size=win_size)
         msgs = None if imgs is None else [
             Image(header=Header(stamp=stamp, frame_id=self.m_sensor_frame), height=u8.shape[0], width=u8.shape[1],
                   encoding="mono8", step=u8.shape[1], data=u8) for u8 in imgs]
