@@ -384,6 +384,50 @@ int rr_simulate_param_sets_metrics(rr_ctx* ctx, const float pose[7], const rr_pa
                                    uint8_t* out_imgs_u8, const uint8_t* ref_img_u8, uint32_t which, int win_size,
                                    rr_image_metrics* out);
 
+/* ---- azimuth registration (rr_align.hip) --------------------------------------------------------------------------
+ * The metrics above compare at ONE azimuth alignment, but a real sweep and a simulated one do not start at the same azimuth
+ * (hence scroll_image: azimuth k is written to column (scroll_image + k) % n_angles), and a change of sensor yaw is, to first
+ * order, a circular shift along the azimuth axis.  Under such a shift the sums of x, x^2, r, r^2 do not change, so the cross
+ * term alone gives the exact SSE, PSNR and normalised cross-correlation at EVERY shift.  The reference has no registration
+ * step: this is the build's own definition.
+ * Images are uint8 [n_cells][n_angles] in the context's current shape.  A cell window [cell_begin, cell_end) selects the rows
+ * that take part (a real image has a bright near-field ring a caller wants to leave out); N = (cell_end - cell_begin) * n_angles.
+ * For image x and reference r, and s in 0..n_angles-1:
+ *   xcorr[s] = sum over c in the window and a of x[c][a] * r[c][(a + s) mod n_angles]        exact int64
+ *            = sum(np.roll(x, s, axis=1) * r)
+ *   s is the amount to ADD TO scroll_image so that x lines up with r.
+ * With the exact integers Sx, Sxx, Sr, Srr (sums of x, x^2, r, r^2 over the window):
+ *   sse[s]  = Sxx + Srr - 2 xcorr[s]                                                         exact uint64
+ *   psnr    = from sse and N with the expression of rr_score_images_device (+inf at sse == 0)
+ *   ncc[s]  = (N xcorr[s] - Sx Sr) / sqrt((N Sxx - Sx^2)(N Srr - Sr^2)): the numerator and the two factors are exact int64,
+ *             converted to f64, then one multiply, one sqrt, one divide; 0 when either factor is 0
+ *   shift   = the smallest s that attains max xcorr (also the minimum SSE and the maximum ncc: everything else is
+ *             shift-invariant); n_best = the number of shifts that attain it
+ * A record holds xcorr, sse, psnr and ncc AT `shift`; d_xcorr (HBM, int64 [n_images][n_angles], or NULL) receives the whole
+ * curve.  Synchronous on `stream`, context-owned scratch, more than 64 images in chunks, one call per context at a time: the
+ * conventions of rr_compare_images_device.  A config is needed, a mesh is not (rr_simulate_batch_align needs what
+ * rr_simulate_batch_device needs).
+ * Refused with a message and nothing written: -2 without a config; -3 for a null buffer, n_images outside 1..65535, a window
+ * that is empty or outside 0..n_cells, a window of more than 2^23 pixels (which keeps N xcorr inside int64). */
+typedef struct rr_align_record {
+    int32_t shift, n_best;
+    int64_t xcorr;            /* at `shift` */
+    uint64_t sse; double psnr, ncc;   /* at `shift` */
+    uint64_t sum_x, sum_xx, sum_r, sum_rr;   /* over the window */
+} rr_align_record;
+int rr_align_images_device(rr_ctx* ctx, const uint8_t* d_imgs_u8, int n_images, const uint8_t* d_ref_u8, int cell_begin, int cell_end,
+                           rr_align_record* out /* host [n_images] */, int64_t* d_xcorr /* HBM [n_images][n_angles], or NULL */,
+                           void* stream);
+/* The host-buffer form: imgs_u8 [n_images][n_cells][n_angles], ref_u8 [n_cells][n_angles], xcorr host [n_images][n_angles] or
+ * NULL.  Synchronous; staged 64 images at a time, the records written once all of them are done, the curves chunk by chunk. */
+int rr_align_images(rr_ctx* ctx, const uint8_t* imgs_u8, int n_images, const uint8_t* ref_u8, int cell_begin, int cell_end,
+                    rr_align_record* out, int64_t* xcorr);
+/* rr_simulate_batch_device into a context-owned image buffer, then rr_align_images_device against ref_img_u8 (host,
+ * [n_cells][n_angles]): n candidate poses x all n_angles yaws from n simulated images.  n_frames is 1..RR_MAX_BATCH;
+ * out_imgs_u8 (host) or NULL, and with NULL no image leaves the GPU; xcorr host [n_frames][n_angles] or NULL. */
+int rr_simulate_batch_align(rr_ctx* ctx, const float* poses, int n_frames, const uint8_t* ref_img_u8, int cell_begin, int cell_end,
+                            uint8_t* out_imgs_u8, rr_align_record* out, int64_t* xcorr);
+
 /* All frames of a multi-frame step in ONE launch: frame j reads its columns frame_stride bytes after
  * frame j-1 (block addressing as above) and writes image j of d_imgs_u8 [n_frames][n_cells][n_angles]. */
 int rr_assemble_frames_device(rr_ctx* ctx, const uint8_t* d_cols_u8, int n_loc, size_t block_stride,

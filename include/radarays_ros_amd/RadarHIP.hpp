@@ -249,6 +249,24 @@ public:
         }
         return out;
     }
+    // Azimuth registration (rr_align_record, include/radarays_mi355.h): the circular shift along the azimuth axis -- the amount
+    // to add to scroll_image -- at which each image matches `real` best over the cell window [cell_begin, cell_end) (cell_end < 0:
+    // n_cells), with the exact SSE, PSNR and NCC there; `curve` (or null) receives xcorr at every shift, [n][n_angles].  Empty on error.
+    std::vector<rr_align_record> alignImages(const std::vector<ImagePtr>& images, const Image& real, int cell_begin = 0, int cell_end = -1,
+                                             std::vector<int64_t>* curve = nullptr)
+    {
+        std::vector<rr_align_record> out;
+        if (images.empty() || !push()) return out;
+        const size_t npx = (size_t)m_cfg.n_cells * m_n_angles;
+        bool ok = real.height == (uint32_t)m_cfg.n_cells && real.width == (uint32_t)m_n_angles && real.data.size() == npx;
+        for (const ImagePtr& im : images) ok = ok && im && im->height == real.height && im->width == real.width && im->data.size() == npx;
+        if (!ok) { m_err = "alignImages: every image must be n_cells x n_angles mono8"; std::cout << "[RadarHIP] " << m_err << std::endl; return out; }
+        if (!marshal::align_images(m_ctx, images.size(), npx, (size_t)m_n_angles, [&](size_t k) { return images[k]->data.data(); }, real.data.data(),
+                                   cell_begin, cell_end < 0 ? m_cfg.n_cells : cell_end, out, curve)) {
+            fail(); out.clear();
+        }
+        return out;
+    }
     const std::string& lastError() const { return m_err; }
     // radar_tools/radar_img_to_pcl (launch/tests/radar_sim_test.launch:80-84, outside the checkout) on the GPU: one mono8
     // polar image of this model's shape (simulated or real) -> its detections, a PointCloud's points plus the intensity

@@ -148,4 +148,17 @@ bool compare_images(rr_ctx* ctx, size_t n, size_t npx, PixelsOf image_pixels, co
     return rr_compare_images(ctx, flat.data(), (int)n, real, which, win_size, out.data(), nullptr) == 0;
 }
 
+// the same images registered against the real one along the azimuth axis (rr_align_images): one record per image over the cell
+// window [cell_begin, cell_end), and with `curve` xcorr at every shift, [n][n_angles].  false: rr_last_error(ctx)
+template <typename PixelsOf>
+bool align_images(rr_ctx* ctx, size_t n, size_t npx, size_t n_angles, PixelsOf image_pixels, const uint8_t* real, int cell_begin, int cell_end,
+                  std::vector<rr_align_record>& out, std::vector<int64_t>* curve)
+{
+    std::vector<uint8_t> flat(n * npx);
+    for (size_t k = 0; k < n; k++) std::copy(image_pixels(k), image_pixels(k) + npx, flat.begin() + (std::ptrdiff_t)(k * npx));
+    out.assign(n, rr_align_record{});
+    if (curve) curve->assign(n * n_angles, 0);
+    return rr_align_images(ctx, flat.data(), (int)n, real, cell_begin, cell_end, out.data(), curve ? curve->data() : nullptr) == 0;
+}
+
 }  // namespace radarays_ros_amd::marshal

@@ -400,7 +400,7 @@ void rr_destroy(rr_ctx* c)
     c->d_rest_v.release(); c->d_stage_v.release(); c->d_rest_f.release(); c->d_poses.release(); c->d_stage_poses.release();
     c->d_levels.release(); c->d_red.release(); c->d_cost.release(); c->d_built.release(); c->d_moved.release();
     c->d_bvh.release(); c->d_qas.release(); c->d_beams.release(); c->d_materials.release(); c->d_mat_limits.release();
-    c->d_objmat.release(); c->d_smear.release(); c->d_noise.release(); c->d_decay.release(); c->d_param_imgs.release(); c->d_sse.release(); c->d_ref_img.release(); c->d_mhist.release(); c->d_conv_hist.release(); c->d_ssim_part.release(); c->d_mrec.release(); c->d_conv_in.release(); c->d_conv_cart.release(); c->d_conv_points.release(); c->d_conv_offs.release(); c->d_beam_order.release(); c->d_beam_order2.release(); c->d_motion.release();
+    c->d_objmat.release(); c->d_smear.release(); c->d_noise.release(); c->d_decay.release(); c->d_param_imgs.release(); c->d_sse.release(); c->d_ref_img.release(); c->d_mhist.release(); c->d_conv_hist.release(); c->d_align_curve.release(); c->d_conv_curve.release(); c->d_align_sums.release(); c->d_align_rec.release();c->d_ssim_part.release(); c->d_mrec.release(); c->d_conv_in.release(); c->d_conv_cart.release(); c->d_conv_points.release(); c->d_conv_offs.release(); c->d_beam_order.release(); c->d_beam_order2.release(); c->d_motion.release();
     for (Lane& L : c->lanes) {
         if (L.stream) (void)hipStreamSynchronize(L.stream);
         for (int k = 0; k < 2; k++) { L.d_wA[k].release(); L.d_wB[k].release(); L.d_wC[k].release(); L.d_idx[k].release(); L.d_count[k].release(); L.d_torder[k].release(); }
@@ -614,6 +614,117 @@ int rr_compare_images(rr_ctx* c, const uint8_t* imgs_u8, int n_images, const uin
                                       joint_hist ? c->d_conv_hist.p : nullptr, c->stream); if (rc) return rc;
         if (joint_hist) RR_HIP(c, hipMemcpy(joint_hist + at * kBins, c->d_conv_hist.p, m * kBins * sizeof(uint32_t), hipMemcpyDeviceToHost));
     }
+    std::copy(rec.begin(), rec.end(), out);
+    return 0;
+}
+
+// ---- azimuth registration: the circular cross-correlation over all shifts (rr_align.hip) ------------------------------
+
+namespace {
+// the refusals of rr_align_images_device / rr_align_images / rr_simulate_batch_align
+int check_align(rr_ctx* c, const char* who, const void* imgs, int n_images, int n_max, const void* ref, int cell_begin, int cell_end, const void* out)
+{
+    if (!c) return -1;
+    if (!c->have_cfg) return fail(c, -2, "rr_set_config has not been called");
+    const std::string w(who);
+    if (!imgs || !ref || !out) return fail(c, -3, w + ": null buffer");
+    if (n_images < 1 || n_images > n_max) return fail(c, -3, w + ": n_images must be 1.." + std::to_string(n_max));
+    if (cell_begin < 0 || cell_end > c->cfg.n_cells || cell_begin >= cell_end)
+        return fail(c, -3, w + ": the cell window [" + std::to_string(cell_begin) + ", " + std::to_string(cell_end) + ") must be non-empty and inside 0.." +
+                               std::to_string(c->cfg.n_cells));
+    if ((long long)(cell_end - cell_begin) * c->cfg.n_angles > (1ll << 23))
+        return fail(c, -3, w + ": a window of more than 2^23 pixels");
+    return 0;
+}
+}  // namespace
+
+int rr_align_images_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_images, const uint8_t* d_ref_u8, int cell_begin, int cell_end,
+                           rr_align_record* out, int64_t* d_xcorr, void* stream)
+{
+    int rc = check_align(c, "rr_align_images_device", d_imgs_u8, n_images, 65535, d_ref_u8, cell_begin, cell_end, out); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = stream_of(c, stream);
+    const rr_config& g = c->cfg;
+    const size_t npx = (size_t)g.n_cells * g.n_angles, n = (size_t)n_images, A = (size_t)g.n_angles;
+    constexpr size_t kChunk = 64;
+    const size_t chunk = std::min(n, kChunk);
+    static_assert(sizeof(long long) == sizeof(int64_t), "curve words");
+    if ((!d_xcorr && c->d_align_curve.n < chunk * A) || c->d_align_sums.n < 2 * (chunk + 1) || c->d_align_rec.n < n) {
+        RR_HIP(c, hipStreamSynchronize(s));             // an earlier call's kernels may still read what is freed here
+        if (!d_xcorr) RR_HIP(c, c->d_align_curve.ensure(chunk * A));
+        RR_HIP(c, c->d_align_sums.ensure(2 * (chunk + 1)));
+        RR_HIP(c, c->d_align_rec.ensure(n));
+    }
+    for (size_t at = 0; at < n; at += kChunk) {
+        const int m = (int)std::min(kChunk, n - at);
+        const uint8_t* imgs = d_imgs_u8 + at * npx;
+        long long* curve = d_xcorr ? reinterpret_cast<long long*>(d_xcorr) + at * A : c->d_align_curve.p;
+        RR_HIP(c, hipMemsetAsync(curve, 0, (size_t)m * A * sizeof(long long), s));
+        RR_HIP(c, hipMemsetAsync(c->d_align_sums.p, 0, 2 * ((size_t)m + 1) * sizeof(unsigned long long), s));
+        launch_align_sums(imgs, d_ref_u8, g.n_cells, g.n_angles, cell_begin, cell_end, m, c->d_align_sums.p, s);
+        launch_align_gram(imgs, d_ref_u8, g.n_cells, g.n_angles, cell_begin, cell_end, m, curve, s);
+        launch_align_finish(curve, c->d_align_sums.p, m, g.n_angles, cell_begin, cell_end, c->d_align_rec.p + at, s);
+    }
+    RR_HIP(c, hipGetLastError());
+    std::vector<rr_align_record> rec(n);
+    RR_HIP(c, hipMemcpyAsync(rec.data(), c->d_align_rec.p, n * sizeof(rr_align_record), hipMemcpyDeviceToHost, s));
+    RR_HIP(c, hipStreamSynchronize(s));
+    const size_t n_win = (size_t)(cell_end - cell_begin) * A;
+    for (size_t k = 0; k < n; k++) {
+        rec[k].psnr = psnr_of(rec[k].sse, n_win);       // the host's log10, as rr_score_images_device
+        out[k] = rec[k];
+    }
+    return 0;
+}
+
+int rr_align_images(rr_ctx* c, const uint8_t* imgs_u8, int n_images, const uint8_t* ref_u8, int cell_begin, int cell_end,
+                    rr_align_record* out, int64_t* xcorr)
+{
+    int rc = check_align(c, "rr_align_images", imgs_u8, n_images, 65535, ref_u8, cell_begin, cell_end, out); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles, n = (size_t)n_images, kChunk = 64, A = (size_t)c->cfg.n_angles;
+    RR_HIP(c, hipStreamSynchronize(c->stream));        // the staging buffers may be reallocated below
+    RR_HIP(c, c->d_conv_in.ensure(std::min(n, kChunk) * npx));
+    RR_HIP(c, c->d_ref_img.ensure(npx));
+    if (xcorr) RR_HIP(c, c->d_conv_curve.ensure(std::min(n, kChunk) * A));
+    RR_HIP(c, hipMemcpyAsync(c->d_ref_img.p, ref_u8, npx, hipMemcpyHostToDevice, c->stream));
+    std::vector<rr_align_record> rec(n);               // (the caller's records are written once every chunk has succeeded)
+    for (size_t at = 0; at < n; at += kChunk) {
+        const size_t m = std::min(kChunk, n - at);
+        RR_HIP(c, hipMemcpyAsync(c->d_conv_in.p, imgs_u8 + at * npx, m * npx, hipMemcpyHostToDevice, c->stream));
+        rc = rr_align_images_device(c, c->d_conv_in.p, (int)m, c->d_ref_img.p, cell_begin, cell_end, rec.data() + at,
+                                    xcorr ? reinterpret_cast<int64_t*>(c->d_conv_curve.p) : nullptr, c->stream); if (rc) return rc;
+        if (xcorr) RR_HIP(c, hipMemcpy(xcorr + at * A, c->d_conv_curve.p, m * A * sizeof(int64_t), hipMemcpyDeviceToHost));
+    }
+    std::copy(rec.begin(), rec.end(), out);
+    return 0;
+}
+
+int rr_simulate_batch_align(rr_ctx* c, const float* poses, int n_frames, const uint8_t* ref_img_u8, int cell_begin, int cell_end,
+                            uint8_t* out_imgs_u8, rr_align_record* out, int64_t* xcorr)
+{
+    // refused before anything is simulated (the context stands in for the images: they are its own)
+    int rc = check_align(c, "rr_simulate_batch_align", c, n_frames, RR_MAX_BATCH, ref_img_u8, cell_begin, cell_end, out); if (rc) return rc;
+    rc = check_ready(c); if (rc) return rc;
+    if (!poses) return fail(c, -3, "rr_simulate_batch_align: null poses");
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles, n = (size_t)n_frames, A = (size_t)c->cfg.n_angles;
+    RR_HIP(c, hipStreamSynchronize(c->stream));        // the buffers may be reallocated below
+    RR_HIP(c, c->d_param_imgs.ensure(n * npx));
+    RR_HIP(c, c->d_ref_img.ensure(npx));
+    if (xcorr) RR_HIP(c, c->d_conv_curve.ensure(n * A));
+    RR_HIP(c, hipMemcpyAsync(c->d_ref_img.p, ref_img_u8, npx, hipMemcpyHostToDevice, c->stream));
+    rc = rr_simulate_batch_device(c, poses, n_frames, c->d_param_imgs.p, c->stream); if (rc) return rc;
+    std::vector<rr_align_record> rec(n);
+    rc = rr_align_images_device(c, c->d_param_imgs.p, n_frames, c->d_ref_img.p, cell_begin, cell_end, rec.data(),
+                                xcorr ? reinterpret_cast<int64_t*>(c->d_conv_curve.p) : nullptr, c->stream); if (rc) return rc;   // synchronises the stream
+    // the frames' error bits before anything is handed out
+    Counters h;
+    rc = read_counters(c, h); if (rc) return rc;
+    if (h.overflow) RR_HIP(c, hipMemset(c->lanes[c->last_lane].d_sticky.p, 0, sizeof(uint32_t)));
+    rc = overflow_error(c, h.overflow); if (rc) return rc;
+    if (out_imgs_u8) RR_HIP(c, hipMemcpy(out_imgs_u8, c->d_param_imgs.p, n * npx, hipMemcpyDeviceToHost));
+    if (xcorr) RR_HIP(c, hipMemcpy(xcorr, c->d_conv_curve.p, n * A * sizeof(int64_t), hipMemcpyDeviceToHost));
     std::copy(rec.begin(), rec.end(), out);
     return 0;
 }

@@ -178,6 +178,8 @@ struct rr_ctx {
     // staging of the host forms of rr_detect / rr_polar_to_cartesian (the device forms use none of it)
     DevBuf<uint8_t> d_conv_in, d_conv_cart; DevBuf<rr_radar_point> d_conv_points; DevBuf<uint32_t> d_conv_offs;
     DevBuf<uint32_t> d_conv_hist;      // ... and of rr_compare_images: one chunk's joint histograms on their way to the host
+    // rr_align_images_device: one chunk's curves (when the caller gives no buffer) and sums, the records; and the host forms' curves
+    DevBuf<long long> d_align_curve, d_conv_curve; DevBuf<unsigned long long> d_align_sums; DevBuf<rr_align_record> d_align_rec;
     void* h_rb = nullptr; size_t h_rb_bytes = 0;         // page-locked: read_back()
     void* h_frame = nullptr; size_t h_frame_bytes = 0;   // page-locked: error bits + per-pass counters of rr_simulate's frame
 

@@ -1,4 +1,4 @@
-// rr_launch.h -- every launcher of rr_kernels.hip, rr_refit.hip, rr_detect.hip, rr_metrics.hip and rr_lbvh.hip, declared ONCE: included where they
+// rr_launch.h -- every launcher of rr_kernels.hip, rr_refit.hip, rr_detect.hip, rr_metrics.hip, rr_align.hip and rr_lbvh.hip, declared ONCE: included where they
 // are defined (a definition that drifts from its declaration fails there) and where they are called.  Default arguments live here only.
 #pragma once
 #include "../../include/radarays_mi355.h"
@@ -48,6 +48,13 @@ int ssim_blocks(int n_cells, int n_angles, int win);          // workgroups (= f
 void launch_ssim(const uint8_t* imgs, const uint8_t* ref, int n_cells, int n_angles, int win, int n_images, double* partial, hipStream_t s);
 void launch_metrics_finish(const uint32_t* hist, const double* ssim_part, int n_blocks, double ssim_count, const unsigned long long* sse,
                            size_t npx, rr_image_metrics* out, int n_images, hipStream_t s);
+// rr_align.hip (azimuth registration).  sums [n_images + 1][2] and curve [n_images][n_angles] must be zero before their launches
+void launch_align_sums(const uint8_t* imgs, const uint8_t* ref, int n_cells, int n_angles, int cell_begin, int cell_end, int n_images,
+                       unsigned long long* sums, hipStream_t s);
+void launch_align_gram(const uint8_t* imgs, const uint8_t* ref, int n_cells, int n_angles, int cell_begin, int cell_end, int n_images,
+                       long long* curve, hipStream_t s);
+void launch_align_finish(long long* curve, const unsigned long long* sums, int n_images, int n_angles, int cell_begin, int cell_end,
+                         rr_align_record* out, hipStream_t s);
 void launch_copy_host(const void* src, void* dst, size_t bytes, int blocks, int xcd, hipStream_t s);
 void launch_copy_words(const void* src, void* dst, size_t bytes, hipStream_t s);
 void launch_debug_brdf(size_t n, const float* in, int model, float* out, hipStream_t s);

@@ -32,6 +32,7 @@ SYMBOLS = [
     "rr_multi_set_object_poses", "rr_multi_update_vertices", "rr_multi_rebuild_tree",
     "rr_default_detect_config", "rr_detect_device", "rr_detect", "rr_polar_to_cartesian_device", "rr_polar_to_cartesian",
     "rr_compare_images_device", "rr_compare_images", "rr_simulate_param_sets_metrics",
+    "rr_align_images_device", "rr_align_images", "rr_simulate_batch_align",
 ]
 
 
@@ -104,6 +105,16 @@ METRICS_DTYPE = np.dtype([("psnr", "<f8"), ("sse", "<u8"), ("ssim", "<f8"), ("hx
 METRIC_PSNR, METRIC_SSIM, METRIC_INFO = 1, 2, 4
 METRIC_ALL = METRIC_PSNR | METRIC_SSIM | METRIC_INFO
 METRIC_NAMES = {"psnr": METRIC_PSNR, "ssim": METRIC_SSIM, "info": METRIC_INFO}
+
+
+class RRAlignRecord(C.Structure):
+    _fields_ = [("shift", C.c_int32), ("n_best", C.c_int32), ("xcorr", C.c_int64), ("sse", C.c_uint64), ("psnr", C.c_double),
+                ("ncc", C.c_double), ("sum_x", C.c_uint64), ("sum_xx", C.c_uint64), ("sum_r", C.c_uint64), ("sum_rr", C.c_uint64)]
+
+
+# rr_align_record as numpy sees it (72 B)
+ALIGN_DTYPE = np.dtype([("shift", "<i4"), ("n_best", "<i4"), ("xcorr", "<i8"), ("sse", "<u8"), ("psnr", "<f8"), ("ncc", "<f8"),
+                        ("sum_x", "<u8"), ("sum_xx", "<u8"), ("sum_r", "<u8"), ("sum_rr", "<u8")])
 
 
 def metrics_mask(which):
@@ -306,6 +317,9 @@ def lib():
     L.rr_compare_images_device.argtypes = [vp, vp, C.c_int, vp, C.c_uint32, C.c_int, vp, vp, vp]
     L.rr_compare_images.argtypes = [vp, vp, C.c_int, vp, C.c_uint32, C.c_int, vp, vp]
     L.rr_simulate_param_sets_metrics.argtypes = [vp, vp, C.POINTER(RRParamSet), C.c_int, C.c_size_t, vp, vp, C.c_uint32, C.c_int, vp]
+    L.rr_align_images_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp]
+    L.rr_align_images.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]
+    L.rr_simulate_batch_align.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp]
     for n in SYMBOLS:
         getattr(L, n)
     _LIB = L
@@ -715,6 +729,66 @@ class Context:
         self._ck(self._L.rr_compare_images(self._h, x.ctypes.data, len(x), r.ctypes.data, which, win, rec.ctypes.data,
                                            None if hist is None else hist.ctypes.data))
         return (rec, hist) if want_hist else rec
+
+    # ---- azimuth registration (rr_align.hip): the circular cross-correlation of images with one reference over all shifts
+    def _cell_window(self, cell_begin, cell_end):
+        """(cell_begin, cell_end) of a window inside this context's image, at most 2^23 pixels; cell_end None: n_cells"""
+        n_cells, n_angles = self._polar_shape()
+        if cell_end is None:
+            cell_end = n_cells
+        for v in (cell_begin, cell_end):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError("cell_begin and cell_end must be integers, got %r, %r" % (cell_begin, cell_end))
+        if not 0 <= cell_begin < cell_end <= n_cells:
+            raise ValueError("the cell window [%d, %d) must be non-empty and inside 0..%d" % (cell_begin, cell_end, n_cells))
+        if (cell_end - cell_begin) * n_angles > 1 << 23:
+            raise ValueError("the cell window [%d, %d) x %d azimuths holds more than 2^23 pixels" % (cell_begin, cell_end, n_angles))
+        return int(cell_begin), int(cell_end)
+
+    def align_images_device(self, d_imgs_ptr, n_images, d_ref_ptr, cell_begin=0, cell_end=None, d_xcorr_ptr=None, stream=None):
+        """rr_align_images_device: n images [n][n_cells][n_angles] and one reference image in HBM -> ALIGN_DTYPE array [n] (the
+        best circular azimuth shift and the scores at it); d_xcorr_ptr (HBM, int64 [n][n_angles]) receives xcorr at every shift.
+        Synchronous on `stream`."""
+        cb, ce = self._cell_window(cell_begin, cell_end)
+        n = _frames_arg(n_images)
+        if not d_imgs_ptr or not d_ref_ptr:
+            raise ValueError("align_images_device needs image and reference buffers")
+        rec = np.zeros(n, ALIGN_DTYPE)
+        self._ck(self._L.rr_align_images_device(self._h, d_imgs_ptr, n, d_ref_ptr, cb, ce, rec.ctypes.data, d_xcorr_ptr, stream))
+        return rec
+
+    def align_images(self, imgs, ref, cell_begin=0, cell_end=None, want_curve=False):
+        """rr_align_images on host images [n][n_cells][n_angles] (or one image) against ref [n_cells][n_angles] -> ALIGN_DTYPE
+        array [n], and with want_curve xcorr int64 [n][n_angles] as well"""
+        x = self._polar_images(imgs)
+        r = self._polar_images(ref)
+        if len(r) != 1:
+            raise ValueError("one reference image, got %d" % len(r))
+        cb, ce = self._cell_window(cell_begin, cell_end)
+        rec = np.zeros(len(x), ALIGN_DTYPE)
+        curve = np.zeros((len(x), self.n_angles), np.int64) if want_curve else None
+        self._ck(self._L.rr_align_images(self._h, x.ctypes.data, len(x), r.ctypes.data, cb, ce, rec.ctypes.data,
+                                         None if curve is None else curve.ctypes.data))
+        return (rec, curve) if want_curve else rec
+
+    def simulate_batch_align(self, poses, ref, cell_begin=0, cell_end=None, want_images=False, want_curve=False):
+        """rr_simulate_batch_align: up to 64 poses simulated and registered against ref [n_cells][n_angles] ->
+        (images uint8 [n][n_cells][n_angles] or None, ALIGN_DTYPE array [n], xcorr int64 [n][n_angles] or None)"""
+        r = self._polar_images(ref)
+        if len(r) != 1:
+            raise ValueError("one reference image, got %d" % len(r))
+        cb, ce = self._cell_window(cell_begin, cell_end)
+        p = _rows(poses, 7, "poses")
+        if not 1 <= len(p) <= 64:
+            raise ValueError("1..64 poses, got %d" % len(p))
+        n_cells, n_angles = self._polar_shape()
+        out = np.zeros((len(p), n_cells, n_angles), np.uint8) if want_images else None
+        rec = np.zeros(len(p), ALIGN_DTYPE)
+        curve = np.zeros((len(p), n_angles), np.int64) if want_curve else None
+        self._ck(self._L.rr_simulate_batch_align(self._h, p.ctypes.data, len(p), r.ctypes.data, cb, ce,
+                                                 None if out is None else out.ctypes.data, rec.ctypes.data,
+                                                 None if curve is None else curve.ctypes.data))
+        return out, rec, curve
 
     def simulate_device(self, pose, d_img_ptr, stream=None):
         p = np.ascontiguousarray(pose, np.float32)

@@ -190,6 +190,17 @@ class RadarHIP:
             images = [images]
         return self._ctx.compare_images(np.stack([self._polar(im) for im in images]), self._polar(real), which, win_size)
 
+    # ---- azimuth registration (rr_align.hip): a real sweep and a simulated one do not start at the same azimuth
+    def alignImages(self, images, real, cell_begin=0, cell_end=None, want_curve=False):
+        """mono8 polar Images (or arrays; one or a list, this model's shape) against ONE real image -> a native.ALIGN_DTYPE array
+        with one record per image: the circular azimuth shift (the amount to add to scroll_image) at which the image matches
+        `real` best over the cell window [cell_begin, cell_end), and xcorr, sse, psnr, ncc there; with want_curve also xcorr at
+        every shift, int64 [n][n_angles]"""
+        self._push()
+        if isinstance(images, Image) or (isinstance(images, np.ndarray) and images.ndim == 2):
+            images = [images]
+        return self._ctx.align_images(np.stack([self._polar(im) for im in images]), self._polar(real), cell_begin, cell_end, want_curve)
+
     def _push(self):
         if self._dirty_cfg:
             cfg = self.m_cfg.copy(n_reflections=self.m_params.model.n_reflections)
