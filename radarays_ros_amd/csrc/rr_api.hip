@@ -1,5 +1,5 @@
 // rr_api.hip -- C ABI of libradarays_mi355.so (include/radarays_mi355.h): the context's life, its parameter tables and their upload, synchronisation and errors,
-// image-in/image-out conversions; the rest is rr_scene.hip, rr_frame.hip, rr_sets.hip, rr_probe.hip.  No CPU fallback: a compute call runs the gfx950 kernels or fails with an error string.
+// page-locked memory; the rest is rr_scene.hip, rr_frame.hip, rr_sets.hip, rr_images.hip, rr_probe.hip.  No CPU fallback: a compute call runs the gfx950 kernels or fails with an error string.
 #include "rr_ctx.h"
 #include <algorithm>
 #include <cmath>
@@ -62,6 +62,17 @@ void make_smear(const rr_config& cfg, std::vector<float>& w, int& mode)
     for (int i = 0; i < width; i++) w[i] = (float)((double)w[i] / mode_val);
 }
 
+// the context's page-locked block (upload_table, read_back) with room for `bytes`
+hipError_t ensure_h_rb(rr_ctx* c, size_t bytes)
+{
+    if (c->h_rb_bytes >= bytes) return hipSuccess;
+    if (c->h_rb) (void)hipHostFree(c->h_rb);
+    c->h_rb = nullptr; c->h_rb_bytes = 0;
+    hipError_t e = hipHostMalloc(&c->h_rb, bytes + 4096, hipHostMallocDefault);
+    if (e == hipSuccess) c->h_rb_bytes = bytes + 4096;
+    return e;
+}
+
 // a set-up table goes up through a page-locked staging block and a word-copy kernel on the NULL stream (ordered exactly like the
 // hipMemcpy it replaces, and complete on return): no dispatch of the runtime's own copy kernel is left in a run's kernel trace.
 // Larger than 4 MB, or not whole words: hipMemcpy
@@ -69,18 +80,28 @@ hipError_t upload_table(rr_ctx* c, void* d_dst, const void* src, size_t bytes)
 {
     if (bytes == 0) return hipSuccess;
     if (bytes % 4 != 0 || bytes > ((size_t)4 << 20)) return hipMemcpy(d_dst, src, bytes, hipMemcpyHostToDevice);
-    if (c->h_rb_bytes < bytes) {
-        if (c->h_rb) (void)hipHostFree(c->h_rb);
-        c->h_rb = nullptr; c->h_rb_bytes = 0;
-        hipError_t e = hipHostMalloc(&c->h_rb, bytes + 4096, hipHostMallocDefault);
-        if (e != hipSuccess) return e;
-        c->h_rb_bytes = bytes + 4096;
-    }
+    hipError_t e = ensure_h_rb(c, bytes);
+    if (e != hipSuccess) return e;
     std::memcpy(c->h_rb, src, bytes);
     launch_copy_words(c->h_rb, d_dst, bytes, nullptr);
-    hipError_t e = hipGetLastError();
+    e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     return e;
+}
+
+// the one angle of total reflection that does not depend on the material table (rr_create)
+int limit_of_same_material(rr_ctx* c)
+{
+    const float4 same = make_float4(0.3f, 0.f, 0.f, 0.f);
+    DevBuf<float4> m1; DevBuf<double> l1;
+    RR_HIP(c, m1.ensure(1)); RR_HIP(c, l1.ensure(2));
+    RR_HIP(c, upload_table(c, m1.p, &same, sizeof(same)));
+    launch_mat_limits(m1.p, 1, l1.p, nullptr);
+    RR_HIP(c, hipStreamSynchronize(nullptr));
+    double two[2] = {0.0, 0.0};
+    const int rc = read_back(c, two, l1.p, sizeof(two));
+    c->limit_same = two[0];
+    return rc;
 }
 
 }  // namespace
@@ -224,12 +245,7 @@ int read_back(rr_ctx* c, void* dst, const void* d_src, size_t bytes)
 {
     if (bytes == 0) return 0;
     if (bytes % 16 != 0 || (uintptr_t)d_src % 16 != 0) { RR_HIP(c, hipMemcpy(dst, d_src, bytes, hipMemcpyDeviceToHost)); return 0; }
-    if (c->h_rb_bytes < bytes) {
-        if (c->h_rb) (void)hipHostFree(c->h_rb);
-        c->h_rb = nullptr; c->h_rb_bytes = 0;
-        RR_HIP(c, hipHostMalloc(&c->h_rb, bytes + 4096, hipHostMallocDefault));
-        c->h_rb_bytes = bytes + 4096;
-    }
+    RR_HIP(c, ensure_h_rb(c, bytes));
     launch_copy_host(d_src, c->h_rb, bytes, 4, -1, c->stream);
     RR_HIP(c, hipGetLastError());
     RR_HIP(c, hipStreamSynchronize(c->stream));
@@ -257,34 +273,6 @@ int check_ready(rr_ctx* c)
     if (!c->have_materials) return fail(c, -2, "rr_set_materials has not been called");
     if (c->beams.empty() && c->cfg.n_reflections > 0) return fail(c, -2, "rr_set_beam_samples has not been called");
     return 0;
-}
-
-// the refusals of rr_compare_images_device / rr_compare_images / rr_simulate_param_sets_metrics
-int check_compare(rr_ctx* c, const char* who, const void* imgs, int n_images, const void* ref, uint32_t which, int win_size, const void* out,
-                  const void* hist)
-{
-    if (!c) return -1;
-    if (!c->have_cfg) return fail(c, -2, "rr_set_config has not been called");
-    const std::string w(who);
-    if (!imgs || !ref || !out) return fail(c, -3, w + ": null buffer");
-    if (n_images < 1 || n_images > 65535) return fail(c, -3, w + ": n_images must be 1..65535");
-    const uint32_t all = RR_METRIC_PSNR | RR_METRIC_SSIM | RR_METRIC_INFO;
-    if (which == 0 || (which & ~all)) return fail(c, -3, w + ": which must be a non-empty mask of RR_METRIC_PSNR | RR_METRIC_SSIM | RR_METRIC_INFO");
-    if (which & RR_METRIC_SSIM) {
-        if (win_size < 3 || win_size > 15 || win_size % 2 == 0) return fail(c, -3, w + ": win_size must be odd and in 3..15");
-        if (c->cfg.n_cells < win_size || c->cfg.n_angles < win_size)
-            return fail(c, -3, w + ": the image (" + std::to_string(c->cfg.n_cells) + " x " + std::to_string(c->cfg.n_angles) + ") is smaller than the window");
-    }
-    if (hist && !(which & RR_METRIC_INFO)) return fail(c, -3, w + ": a joint histogram buffer needs RR_METRIC_INFO");
-    return 0;
-}
-
-// skimage.metrics.peak_signal_noise_ratio for uint8 (scripts/radaray_opti.py:196): data_range 255,
-// err = mean of the squared differences in f64 (exact here: an integer sum below 2^53), 10 log10(255^2 / err)
-double psnr_of(uint64_t sse, size_t npx)
-{
-    const double err = (double)sse / (double)npx;
-    return err > 0.0 ? 10.0 * std::log10((255.0 * 255.0) / err) : INFINITY;
 }
 
 }  // namespace rr
@@ -360,20 +348,7 @@ rr_ctx* rr_create(int device)
     if (getenv("RR_TIGHT_GRID")) c->tight_grid = atoi(getenv("RR_TIGHT_GRID")) != 0;
     if (getenv("RR_METRICS_HIST")) c->metrics_hist = atoi(getenv("RR_METRICS_HIST")) != 0;
     if (getenv("RR_TIGHT_FORCE")) c->tight_force = std::max(0, atoi(getenv("RR_TIGHT_FORCE")));
-    {   // the one angle of total reflection that does not depend on the material table
-        const float4 same = make_float4(0.3f, 0.f, 0.f, 0.f);
-        DevBuf<float4> m1; DevBuf<double> l1;
-        bool ok = m1.ensure(1) == hipSuccess && l1.ensure(2) == hipSuccess &&
-                  upload_table(c, m1.p, &same, sizeof(same)) == hipSuccess;
-        if (ok) {
-            launch_mat_limits(m1.p, 1, l1.p, nullptr);
-            double two[2] = {0.0, 0.0};
-            ok = hipStreamSynchronize(nullptr) == hipSuccess && read_back(c, two, l1.p, sizeof(two)) == 0;
-            c->limit_same = two[0];
-        }
-        m1.release(); l1.release();
-        if (!ok) { g_create_error = "rr_create: device set-up failed"; rr_destroy(c); return nullptr; }
-    }
+    if (limit_of_same_material(c)) { g_create_error = "rr_create: device set-up failed"; rr_destroy(c); return nullptr; }
     c->lanes.resize((size_t)n_lanes);
     for (Lane& L : c->lanes) {
         if (hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking) != hipSuccess ||
@@ -397,27 +372,19 @@ void rr_destroy(rr_ctx* c)
     for (hipEvent_t e : c->delivery_events) (void)hipEventDestroy(e);
     for (auto& kv : c->timers) for (auto& p : kv.second.pending) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
-    c->d_rest_v.release(); c->d_stage_v.release(); c->d_rest_f.release(); c->d_poses.release(); c->d_stage_poses.release();
-    c->d_levels.release(); c->d_red.release(); c->d_cost.release(); c->d_built.release(); c->d_moved.release();
-    c->d_bvh.release(); c->d_qas.release(); c->d_beams.release(); c->d_materials.release(); c->d_mat_limits.release();
-    c->d_objmat.release(); c->d_smear.release(); c->d_noise.release(); c->d_decay.release(); c->d_param_imgs.release(); c->d_sse.release(); c->d_ref_img.release(); c->d_mhist.release(); c->d_conv_hist.release(); c->d_align_curve.release(); c->d_conv_curve.release(); c->d_align_sums.release(); c->d_align_rec.release();c->d_ssim_part.release(); c->d_mrec.release(); c->d_conv_in.release(); c->d_conv_cart.release(); c->d_conv_points.release(); c->d_conv_offs.release(); c->d_beam_order.release(); c->d_beam_order2.release(); c->d_motion.release();
     for (Lane& L : c->lanes) {
         if (L.stream) (void)hipStreamSynchronize(L.stream);
-        for (int k = 0; k < 2; k++) { L.d_wA[k].release(); L.d_wB[k].release(); L.d_wC[k].release(); L.d_idx[k].release(); L.d_count[k].release(); L.d_torder[k].release(); }
-        L.d_refpos.release();
-        L.d_hit.release(); L.d_sig_count.release(); L.d_spill.release(); L.d_cflag.release(); L.d_cols_u8.release();
-        L.d_sigtmp.release(); L.d_sig.release(); L.d_cols_f32.release(); L.d_counters.release(); L.d_sticky.release(); L.d_seg_stats.release(); L.d_matsets.release(); L.d_matset_limits.release(); L.d_set_beams.release(); L.d_set_order.release(); L.d_set_order2.release(); L.d_img_f32.release();
-        L.d_hint.release(); L.d_ovf_list.release(); if (L.h_hist) { (void)hipHostFree(L.h_hist); L.h_hist = nullptr; }
-        drop_graphs(L); L.d_poses.release();
+        if (L.h_hist) { (void)hipHostFree(L.h_hist); L.h_hist = nullptr; }
+        drop_graphs(L);
         if (L.ev_ready) (void)hipEventDestroy(L.ev_ready);
         if (L.ev_consumed) (void)hipEventDestroy(L.ev_consumed);
-        for (Delivery& d : L.slot) { d.img.release(); if (d.ev) (void)hipEventDestroy(d.ev); }
+        for (Delivery& d : L.slot) if (d.ev) (void)hipEventDestroy(d.ev);
         if (L.stream) (void)hipStreamDestroy(L.stream);
     }
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->h_frame) (void)hipHostFree(c->h_frame);
     if (c->h_rb) (void)hipHostFree(c->h_rb);
-    delete c;
+    delete c;      // frees every DevBuf of the context and its lanes: after their streams are gone, which is harmless on an idle device
 }
 
 const char* rr_last_error(const rr_ctx* c) { return c ? c->err.c_str() : g_create_error.c_str(); }
@@ -516,336 +483,6 @@ void* rr_host_alloc(size_t bytes)
 }
 
 void rr_host_free(void* p) { if (p) (void)hipHostFree(p); }
-
-int rr_score_images_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_images, const uint8_t* d_ref_u8, double* out_psnr,
-                           uint64_t* out_sse, void* stream)
-{
-    if (!c) return -1;
-    if (!c->have_cfg) return fail(c, -2, "rr_set_config has not been called");
-    if (!d_imgs_u8 || !d_ref_u8 || (!out_psnr && !out_sse)) return fail(c, -3, "rr_score_images_device: null buffer");
-    if (n_images < 1 || n_images > 65535) return fail(c, -3, "rr_score_images_device: n_images must be 1..65535");
-    RR_HIP(c, hipSetDevice(c->device));
-    hipStream_t s = stream_of(c, stream);
-    const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles;
-    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "sse words");
-    if (c->d_sse.n < (size_t)n_images) { RR_HIP(c, hipStreamSynchronize(s)); RR_HIP(c, c->d_sse.ensure((size_t)n_images)); }
-    RR_HIP(c, hipMemsetAsync(c->d_sse.p, 0, (size_t)n_images * sizeof(uint64_t), s));
-    launch_score(d_imgs_u8, d_ref_u8, npx, n_images, c->d_sse.p, s);
-    RR_HIP(c, hipGetLastError());
-    std::vector<uint64_t> sse((size_t)n_images);
-    RR_HIP(c, hipMemcpyAsync(sse.data(), c->d_sse.p, (size_t)n_images * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    RR_HIP(c, hipStreamSynchronize(s));
-    for (int k = 0; k < n_images; k++) {
-        if (out_sse) out_sse[k] = sse[(size_t)k];
-        if (out_psnr) {
-            out_psnr[k] = psnr_of(sse[(size_t)k], npx);
-        }
-    }
-    return 0;
-}
-
-// ---- images against one reference image: PSNR, SSIM, joint histogram and its entropies (rr_metrics.hip) --------------
-
-int rr_compare_images_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_images, const uint8_t* d_ref_u8, uint32_t which, int win_size,
-                             rr_image_metrics* out, uint32_t* d_joint_hist, void* stream)
-{
-    int rc = check_compare(c, "rr_compare_images_device", d_imgs_u8, n_images, d_ref_u8, which, win_size, out, d_joint_hist); if (rc) return rc;
-    RR_HIP(c, hipSetDevice(c->device));
-    hipStream_t s = stream_of(c, stream);
-    const rr_config& g = c->cfg;
-    const size_t npx = (size_t)g.n_cells * g.n_angles, n = (size_t)n_images;
-    const bool psnr = which & RR_METRIC_PSNR, ssim = which & RR_METRIC_SSIM, info = which & RR_METRIC_INFO;
-    constexpr size_t kChunk = 64, kBins = 65536;        // histogram scratch: 256 KB per image, at most 64 images' worth
-    const size_t chunk = std::min(n, kChunk);
-    const int n_blocks = ssim ? ssim_blocks(g.n_cells, g.n_angles, win_size) : 0;
-    const double ssim_count = ssim ? (double)(g.n_cells - win_size + 1) * (double)(g.n_angles - win_size + 1) : 1.0;
-    const bool own_hist = info && !d_joint_hist;
-    if ((psnr && c->d_sse.n < n) || (own_hist && c->d_mhist.n < chunk * kBins) || (ssim && c->d_ssim_part.n < chunk * (size_t)n_blocks) || c->d_mrec.n < n) {
-        RR_HIP(c, hipStreamSynchronize(s));             // an earlier call's kernels may still read what is freed here
-        if (psnr) RR_HIP(c, c->d_sse.ensure(n));
-        if (own_hist) RR_HIP(c, c->d_mhist.ensure(chunk * kBins));
-        if (ssim) RR_HIP(c, c->d_ssim_part.ensure(chunk * (size_t)n_blocks));
-        RR_HIP(c, c->d_mrec.ensure(n));
-    }
-    if (psnr) {
-        RR_HIP(c, hipMemsetAsync(c->d_sse.p, 0, n * sizeof(uint64_t), s));
-        launch_score(d_imgs_u8, d_ref_u8, npx, n_images, c->d_sse.p, s);
-    }
-    for (size_t at = 0; at < n; at += kChunk) {
-        const int m = (int)std::min(kChunk, n - at);
-        const uint8_t* imgs = d_imgs_u8 + at * npx;
-        uint32_t* H = !info ? nullptr : d_joint_hist ? d_joint_hist + at * kBins : c->d_mhist.p;
-        if (info) {
-            RR_HIP(c, hipMemsetAsync(H, 0, (size_t)m * kBins * sizeof(uint32_t), s));
-            launch_joint_hist(imgs, d_ref_u8, npx, m, H, c->metrics_hist, s);
-        }
-        if (ssim) launch_ssim(imgs, d_ref_u8, g.n_cells, g.n_angles, win_size, m, c->d_ssim_part.p, s);
-        launch_metrics_finish(H, ssim ? c->d_ssim_part.p : nullptr, n_blocks, ssim_count, psnr ? c->d_sse.p + at : nullptr, npx,
-                              c->d_mrec.p + at, m, s);
-    }
-    RR_HIP(c, hipGetLastError());
-    std::vector<rr_image_metrics> rec(n);
-    RR_HIP(c, hipMemcpyAsync(rec.data(), c->d_mrec.p, n * sizeof(rr_image_metrics), hipMemcpyDeviceToHost, s));
-    RR_HIP(c, hipStreamSynchronize(s));
-    for (size_t k = 0; k < n; k++) {
-        if (psnr) rec[k].psnr = psnr_of(rec[k].sse, npx);     // the host's log10, as rr_score_images_device: the same bits
-        out[k] = rec[k];
-    }
-    return 0;
-}
-
-int rr_compare_images(rr_ctx* c, const uint8_t* imgs_u8, int n_images, const uint8_t* ref_u8, uint32_t which, int win_size,
-                      rr_image_metrics* out, uint32_t* joint_hist)
-{
-    int rc = check_compare(c, "rr_compare_images", imgs_u8, n_images, ref_u8, which, win_size, out, joint_hist); if (rc) return rc;
-    RR_HIP(c, hipSetDevice(c->device));
-    const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles, n = (size_t)n_images, kChunk = 64, kBins = 65536;
-    RR_HIP(c, hipStreamSynchronize(c->stream));        // the staging buffers may be reallocated below
-    RR_HIP(c, c->d_conv_in.ensure(std::min(n, kChunk) * npx));
-    RR_HIP(c, c->d_ref_img.ensure(npx));
-    if (joint_hist) RR_HIP(c, c->d_conv_hist.ensure(std::min(n, kChunk) * kBins));
-    RR_HIP(c, hipMemcpyAsync(c->d_ref_img.p, ref_u8, npx, hipMemcpyHostToDevice, c->stream));
-    std::vector<rr_image_metrics> rec(n);              // (the caller's records are written once every chunk has succeeded)
-    for (size_t at = 0; at < n; at += kChunk) {
-        const size_t m = std::min(kChunk, n - at);
-        RR_HIP(c, hipMemcpyAsync(c->d_conv_in.p, imgs_u8 + at * npx, m * npx, hipMemcpyHostToDevice, c->stream));
-        // one chunk of the device form, its histograms into this form's own staging buffer
-        rc = rr_compare_images_device(c, c->d_conv_in.p, (int)m, c->d_ref_img.p, which, win_size, rec.data() + at,
-                                      joint_hist ? c->d_conv_hist.p : nullptr, c->stream); if (rc) return rc;
-        if (joint_hist) RR_HIP(c, hipMemcpy(joint_hist + at * kBins, c->d_conv_hist.p, m * kBins * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    }
-    std::copy(rec.begin(), rec.end(), out);
-    return 0;
-}
-
-// ---- azimuth registration: the circular cross-correlation over all shifts (rr_align.hip) ------------------------------
-
-namespace {
-// the refusals of rr_align_images_device / rr_align_images / rr_simulate_batch_align
-int check_align(rr_ctx* c, const char* who, const void* imgs, int n_images, int n_max, const void* ref, int cell_begin, int cell_end, const void* out)
-{
-    if (!c) return -1;
-    if (!c->have_cfg) return fail(c, -2, "rr_set_config has not been called");
-    const std::string w(who);
-    if (!imgs || !ref || !out) return fail(c, -3, w + ": null buffer");
-    if (n_images < 1 || n_images > n_max) return fail(c, -3, w + ": n_images must be 1.." + std::to_string(n_max));
-    if (cell_begin < 0 || cell_end > c->cfg.n_cells || cell_begin >= cell_end)
-        return fail(c, -3, w + ": the cell window [" + std::to_string(cell_begin) + ", " + std::to_string(cell_end) + ") must be non-empty and inside 0.." +
-                               std::to_string(c->cfg.n_cells));
-    if ((long long)(cell_end - cell_begin) * c->cfg.n_angles > (1ll << 23))
-        return fail(c, -3, w + ": a window of more than 2^23 pixels");
-    return 0;
-}
-}  // namespace
-
-int rr_align_images_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_images, const uint8_t* d_ref_u8, int cell_begin, int cell_end,
-                           rr_align_record* out, int64_t* d_xcorr, void* stream)
-{
-    int rc = check_align(c, "rr_align_images_device", d_imgs_u8, n_images, 65535, d_ref_u8, cell_begin, cell_end, out); if (rc) return rc;
-    RR_HIP(c, hipSetDevice(c->device));
-    hipStream_t s = stream_of(c, stream);
-    const rr_config& g = c->cfg;
-    const size_t npx = (size_t)g.n_cells * g.n_angles, n = (size_t)n_images, A = (size_t)g.n_angles;
-    constexpr size_t kChunk = 64;
-    const size_t chunk = std::min(n, kChunk);
-    static_assert(sizeof(long long) == sizeof(int64_t), "curve words");
-    if ((!d_xcorr && c->d_align_curve.n < chunk * A) || c->d_align_sums.n < 2 * (chunk + 1) || c->d_align_rec.n < n) {
-        RR_HIP(c, hipStreamSynchronize(s));             // an earlier call's kernels may still read what is freed here
-        if (!d_xcorr) RR_HIP(c, c->d_align_curve.ensure(chunk * A));
-        RR_HIP(c, c->d_align_sums.ensure(2 * (chunk + 1)));
-        RR_HIP(c, c->d_align_rec.ensure(n));
-    }
-    for (size_t at = 0; at < n; at += kChunk) {
-        const int m = (int)std::min(kChunk, n - at);
-        const uint8_t* imgs = d_imgs_u8 + at * npx;
-        long long* curve = d_xcorr ? reinterpret_cast<long long*>(d_xcorr) + at * A : c->d_align_curve.p;
-        RR_HIP(c, hipMemsetAsync(curve, 0, (size_t)m * A * sizeof(long long), s));
-        RR_HIP(c, hipMemsetAsync(c->d_align_sums.p, 0, 2 * ((size_t)m + 1) * sizeof(unsigned long long), s));
-        launch_align_sums(imgs, d_ref_u8, g.n_cells, g.n_angles, cell_begin, cell_end, m, c->d_align_sums.p, s);
-        launch_align_gram(imgs, d_ref_u8, g.n_cells, g.n_angles, cell_begin, cell_end, m, curve, s);
-        launch_align_finish(curve, c->d_align_sums.p, m, g.n_angles, cell_begin, cell_end, c->d_align_rec.p + at, s);
-    }
-    RR_HIP(c, hipGetLastError());
-    std::vector<rr_align_record> rec(n);
-    RR_HIP(c, hipMemcpyAsync(rec.data(), c->d_align_rec.p, n * sizeof(rr_align_record), hipMemcpyDeviceToHost, s));
-    RR_HIP(c, hipStreamSynchronize(s));
-    const size_t n_win = (size_t)(cell_end - cell_begin) * A;
-    for (size_t k = 0; k < n; k++) {
-        rec[k].psnr = psnr_of(rec[k].sse, n_win);       // the host's log10, as rr_score_images_device
-        out[k] = rec[k];
-    }
-    return 0;
-}
-
-int rr_align_images(rr_ctx* c, const uint8_t* imgs_u8, int n_images, const uint8_t* ref_u8, int cell_begin, int cell_end,
-                    rr_align_record* out, int64_t* xcorr)
-{
-    int rc = check_align(c, "rr_align_images", imgs_u8, n_images, 65535, ref_u8, cell_begin, cell_end, out); if (rc) return rc;
-    RR_HIP(c, hipSetDevice(c->device));
-    const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles, n = (size_t)n_images, kChunk = 64, A = (size_t)c->cfg.n_angles;
-    RR_HIP(c, hipStreamSynchronize(c->stream));        // the staging buffers may be reallocated below
-    RR_HIP(c, c->d_conv_in.ensure(std::min(n, kChunk) * npx));
-    RR_HIP(c, c->d_ref_img.ensure(npx));
-    if (xcorr) RR_HIP(c, c->d_conv_curve.ensure(std::min(n, kChunk) * A));
-    RR_HIP(c, hipMemcpyAsync(c->d_ref_img.p, ref_u8, npx, hipMemcpyHostToDevice, c->stream));
-    std::vector<rr_align_record> rec(n);               // (the caller's records are written once every chunk has succeeded)
-    for (size_t at = 0; at < n; at += kChunk) {
-        const size_t m = std::min(kChunk, n - at);
-        RR_HIP(c, hipMemcpyAsync(c->d_conv_in.p, imgs_u8 + at * npx, m * npx, hipMemcpyHostToDevice, c->stream));
-        rc = rr_align_images_device(c, c->d_conv_in.p, (int)m, c->d_ref_img.p, cell_begin, cell_end, rec.data() + at,
-                                    xcorr ? reinterpret_cast<int64_t*>(c->d_conv_curve.p) : nullptr, c->stream); if (rc) return rc;
-        if (xcorr) RR_HIP(c, hipMemcpy(xcorr + at * A, c->d_conv_curve.p, m * A * sizeof(int64_t), hipMemcpyDeviceToHost));
-    }
-    std::copy(rec.begin(), rec.end(), out);
-    return 0;
-}
-
-int rr_simulate_batch_align(rr_ctx* c, const float* poses, int n_frames, const uint8_t* ref_img_u8, int cell_begin, int cell_end,
-                            uint8_t* out_imgs_u8, rr_align_record* out, int64_t* xcorr)
-{
-    // refused before anything is simulated (the context stands in for the images: they are its own)
-    int rc = check_align(c, "rr_simulate_batch_align", c, n_frames, RR_MAX_BATCH, ref_img_u8, cell_begin, cell_end, out); if (rc) return rc;
-    rc = check_ready(c); if (rc) return rc;
-    if (!poses) return fail(c, -3, "rr_simulate_batch_align: null poses");
-    RR_HIP(c, hipSetDevice(c->device));
-    const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles, n = (size_t)n_frames, A = (size_t)c->cfg.n_angles;
-    RR_HIP(c, hipStreamSynchronize(c->stream));        // the buffers may be reallocated below
-    RR_HIP(c, c->d_param_imgs.ensure(n * npx));
-    RR_HIP(c, c->d_ref_img.ensure(npx));
-    if (xcorr) RR_HIP(c, c->d_conv_curve.ensure(n * A));
-    RR_HIP(c, hipMemcpyAsync(c->d_ref_img.p, ref_img_u8, npx, hipMemcpyHostToDevice, c->stream));
-    rc = rr_simulate_batch_device(c, poses, n_frames, c->d_param_imgs.p, c->stream); if (rc) return rc;
-    std::vector<rr_align_record> rec(n);
-    rc = rr_align_images_device(c, c->d_param_imgs.p, n_frames, c->d_ref_img.p, cell_begin, cell_end, rec.data(),
-                                xcorr ? reinterpret_cast<int64_t*>(c->d_conv_curve.p) : nullptr, c->stream); if (rc) return rc;   // synchronises the stream
-    // the frames' error bits before anything is handed out
-    Counters h;
-    rc = read_counters(c, h); if (rc) return rc;
-    if (h.overflow) RR_HIP(c, hipMemset(c->lanes[c->last_lane].d_sticky.p, 0, sizeof(uint32_t)));
-    rc = overflow_error(c, h.overflow); if (rc) return rc;
-    if (out_imgs_u8) RR_HIP(c, hipMemcpy(out_imgs_u8, c->d_param_imgs.p, n * npx, hipMemcpyDeviceToHost));
-    if (xcorr) RR_HIP(c, hipMemcpy(xcorr, c->d_conv_curve.p, n * A * sizeof(int64_t), hipMemcpyDeviceToHost));
-    std::copy(rec.begin(), rec.end(), out);
-    return 0;
-}
-
-// ---- point clouds and Cartesian images (rr_detect.hip) ---------------------------------------------------------------
-void rr_default_detect_config(rr_detect_config* cfg)
-{
-    if (!cfg) return;
-    std::memset(cfg, 0, sizeof(*cfg));
-    cfg->method = 0; cfg->guard_cells = 2; cfg->train_cells = 16; cfg->k = 12;
-    cfg->min_intensity = 1; cfg->min_bin = 0; cfg->cfar_scale = 3.0f;
-}
-
-namespace {
-
-int check_frames(rr_ctx* c, const char* who, const void* imgs, int n_frames)
-{
-    if (!c) return -1;
-    if (!c->have_cfg) return fail(c, -2, "rr_set_config has not been called");
-    if (!imgs) return fail(c, -3, std::string(who) + ": null images");
-    if (n_frames < 1 || n_frames > 65535) return fail(c, -3, std::string(who) + ": n_frames must be 1..65535");
-    return 0;
-}
-
-int check_detect(rr_ctx* c, const char* who, const void* imgs, int n_frames, const rr_detect_config* d, const void* points,
-                 int max_points, const void* offsets)
-{
-    int rc = check_frames(c, who, imgs, n_frames); if (rc) return rc;
-    const std::string w(who);
-    if (!d) return fail(c, -3, w + ": null config");
-    if (!offsets) return fail(c, -3, w + ": null offsets");
-    if (max_points < 0) return fail(c, -3, w + ": max_points must be >= 0");
-    if (max_points > 0 && !points) return fail(c, -3, w + ": null points with max_points > 0");
-    const int n_cells = c->cfg.n_cells;
-    if (d->method != 0 && d->method != 1) return fail(c, -3, w + ": method must be 0 (CA-CFAR) or 1 (k-strongest)");
-    if (d->guard_cells < 0 || d->guard_cells > 1024) return fail(c, -3, w + ": guard_cells must be 0..1024");
-    if (d->train_cells < 1 || d->train_cells > 1024) return fail(c, -3, w + ": train_cells must be 1..1024");
-    if (d->k < 1 || d->k > n_cells) return fail(c, -3, w + ": k must be 1..n_cells (" + std::to_string(n_cells) + ")");
-    if (d->min_intensity < 0 || d->min_intensity > 255) return fail(c, -3, w + ": min_intensity must be 0..255");
-    if (d->min_bin < 0 || d->min_bin >= n_cells) return fail(c, -3, w + ": min_bin must be 0..n_cells-1");
-    if (!(std::isfinite(d->cfar_scale) && d->cfar_scale >= 0.0f)) return fail(c, -3, w + ": cfar_scale must be finite and >= 0");
-    return 0;
-}
-
-int check_cartesian(rr_ctx* c, const char* who, const void* imgs, int n_frames, const rr_cartesian_config* k, const void* out)
-{
-    int rc = check_frames(c, who, imgs, n_frames); if (rc) return rc;
-    const std::string w(who);
-    if (!k) return fail(c, -3, w + ": null config");
-    if (!out) return fail(c, -3, w + ": null output");
-    if (k->width < 1 || k->width > 8192) return fail(c, -3, w + ": width must be 1..8192");
-    if (k->interpolation != 0 && k->interpolation != 1) return fail(c, -3, w + ": interpolation must be 0 (nearest) or 1 (bilinear)");
-    if (!(std::isfinite(k->pixel_size) && k->pixel_size > 0.0f)) return fail(c, -3, w + ": pixel_size must be finite and > 0");
-    if (c->cfg.theta_inc == 0.0f) return fail(c, -3, w + ": the config's theta_inc is 0");
-    return 0;
-}
-
-}  // namespace
-
-int rr_detect_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_frames, const rr_detect_config* cfg, rr_radar_point* d_points,
-                     int max_points, uint32_t* d_offsets, void* stream)
-{
-    int rc = check_detect(c, "rr_detect_device", d_imgs_u8, n_frames, cfg, d_points, max_points, d_offsets); if (rc) return rc;
-    RR_HIP(c, hipSetDevice(c->device));
-    const rr_config& g = c->cfg;
-    hipStream_t s = stream_of(c, stream);
-    launch_detect(d_imgs_u8, n_frames, *cfg, g.n_cells, g.n_angles, g.scroll_image, g.theta_min, g.theta_inc, g.resolution,
-                  max_points > 0 ? d_points : nullptr, max_points, d_offsets, s);
-    RR_HIP(c, hipGetLastError());
-    return 0;
-}
-
-int rr_detect(rr_ctx* c, const uint8_t* imgs_u8, int n_frames, const rr_detect_config* cfg, rr_radar_point* points,
-              int max_points, uint32_t* offsets)
-{
-    int rc = check_detect(c, "rr_detect", imgs_u8, n_frames, cfg, points, max_points, offsets); if (rc) return rc;
-    RR_HIP(c, hipSetDevice(c->device));
-    const rr_config& g = c->cfg;
-    const size_t npx = (size_t)g.n_cells * g.n_angles, n_offs = (size_t)n_frames * (g.n_angles + 1);
-    const size_t n_pts = (size_t)n_frames * (size_t)max_points;
-    RR_HIP(c, hipStreamSynchronize(c->stream));        // the staging buffers may be reallocated below
-    RR_HIP(c, c->d_conv_in.ensure((size_t)n_frames * npx));
-    RR_HIP(c, c->d_conv_offs.ensure(n_offs));
-    if (n_pts) RR_HIP(c, c->d_conv_points.ensure(n_pts));
-    RR_HIP(c, hipMemcpyAsync(c->d_conv_in.p, imgs_u8, (size_t)n_frames * npx, hipMemcpyHostToDevice, c->stream));
-    rc = rr_detect_device(c, c->d_conv_in.p, n_frames, cfg, n_pts ? c->d_conv_points.p : nullptr, max_points, c->d_conv_offs.p, c->stream);
-    if (rc) return rc;
-    RR_HIP(c, hipMemcpyAsync(offsets, c->d_conv_offs.p, n_offs * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    if (n_pts) RR_HIP(c, hipMemcpyAsync(points, c->d_conv_points.p, n_pts * sizeof(rr_radar_point), hipMemcpyDeviceToHost, c->stream));
-    RR_HIP(c, hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-int rr_polar_to_cartesian_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_frames, const rr_cartesian_config* cfg,
-                                 uint8_t* d_cart_u8, void* stream)
-{
-    int rc = check_cartesian(c, "rr_polar_to_cartesian_device", d_imgs_u8, n_frames, cfg, d_cart_u8); if (rc) return rc;
-    RR_HIP(c, hipSetDevice(c->device));
-    const rr_config& g = c->cfg;
-    hipStream_t s = stream_of(c, stream);
-    launch_cartesian(d_imgs_u8, n_frames, *cfg, g.n_cells, g.n_angles, g.scroll_image, g.theta_min, g.theta_inc, (float)g.resolution,
-                     d_cart_u8, s);
-    RR_HIP(c, hipGetLastError());
-    return 0;
-}
-
-int rr_polar_to_cartesian(rr_ctx* c, const uint8_t* imgs_u8, int n_frames, const rr_cartesian_config* cfg, uint8_t* cart_u8)
-{
-    int rc = check_cartesian(c, "rr_polar_to_cartesian", imgs_u8, n_frames, cfg, cart_u8); if (rc) return rc;
-    RR_HIP(c, hipSetDevice(c->device));
-    const rr_config& g = c->cfg;
-    const size_t npx = (size_t)g.n_cells * g.n_angles, n_out = (size_t)n_frames * cfg->width * cfg->width;
-    RR_HIP(c, hipStreamSynchronize(c->stream));
-    RR_HIP(c, c->d_conv_in.ensure((size_t)n_frames * npx));
-    RR_HIP(c, c->d_conv_cart.ensure(n_out));
-    RR_HIP(c, hipMemcpyAsync(c->d_conv_in.p, imgs_u8, (size_t)n_frames * npx, hipMemcpyHostToDevice, c->stream));
-    rc = rr_polar_to_cartesian_device(c, c->d_conv_in.p, n_frames, cfg, c->d_conv_cart.p, c->stream); if (rc) return rc;
-    RR_HIP(c, hipMemcpyAsync(cart_u8, c->d_conv_cart.p, n_out, hipMemcpyDeviceToHost, c->stream));
-    RR_HIP(c, hipStreamSynchronize(c->stream));
-    return 0;
-}
 
 int rr_synchronize(rr_ctx* c, void* stream)
 {

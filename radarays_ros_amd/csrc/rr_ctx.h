@@ -1,4 +1,4 @@
-// rr_ctx.h -- the context as the library's host files share it (rr_api.hip, rr_scene.hip, rr_frame.hip, rr_sets.hip, rr_probe.hip): rr_ctx and its
+// rr_ctx.h -- the context as the library's host files share it (rr_api.hip, rr_scene.hip, rr_frame.hip, rr_sets.hip, rr_images.hip, rr_probe.hip): rr_ctx and its
 // lanes, the error / timing / roctx helpers, the helpers that cross a file boundary.  Nothing here is public: the interface is include/radarays_mi355.h.
 #pragma once
 #include "rr_devbuf.h"
@@ -263,10 +263,20 @@ int upload_tables(rr_ctx* c);
 void beam_trace_orders(const float* beams, size_t nb, std::vector<uint32_t>& order, std::vector<uint32_t>& order2);
 int read_back(rr_ctx* c, void* dst, const void* d_src, size_t bytes);
 int overflow_error(rr_ctx* c, uint32_t bits, bool since_sync = false);
-int check_compare(rr_ctx* c, const char* who, const void* imgs, int n_images, const void* ref, uint32_t which, int win_size, const void* out,
-                  const void* hist);      // the refusals of rr_compare_images* / rr_simulate_param_sets_metrics
 // the counters of the lane the last frame ran on (the callers have synchronised)
 inline int read_counters(rr_ctx* c, Counters& h) { return read_back(c, &h, c->lanes[c->last_lane].d_counters.p, sizeof(h)); }
+// ... and its error bits as the failure of a synchronous call: reported here, so cleared from the lane's sticky word
+inline int report_frame_errors(rr_ctx* c)
+{
+    Counters h;
+    const int rc = read_counters(c, h); if (rc) return rc;
+    if (h.overflow) RR_HIP(c, hipMemset(c->lanes[c->last_lane].d_sticky.p, 0, sizeof(uint32_t)));
+    return overflow_error(c, h.overflow);
+}
+
+// rr_images.hip
+int check_compare(rr_ctx* c, const char* who, const void* imgs, int n_images, const void* ref, uint32_t which, int win_size, const void* out,
+                  const void* hist);      // the refusals of rr_compare_images* / rr_simulate_param_sets_metrics
 
 // rr_frame.hip
 void drop_graphs(Lane& L);

@@ -569,7 +569,7 @@ int rr_deliver_to_host_async(rr_ctx* c, const void* d_src, void* h_dst, size_t b
         if (e != hipSuccess) { c->delivery_events.push_back(ev); RR_HIP(c, e); }
     }
     Delivery d; d.ev = ev; d.dst = h_dst; d.job = job;
-    c->deliveries.push_back(d);
+    c->deliveries.push_back(std::move(d));
     return 0;
 }
 

@@ -1,0 +1,376 @@
+// rr_images.hip -- the C ABI's image entry points: images in, records / points / images out.  PSNR scores and metrics against a reference image
+// (rr_metrics.hip), azimuth registration (rr_align.hip), point clouds and Cartesian images (rr_detect.hip): each in a device form, which runs on the
+// caller's buffers and stream, and a host form, which stages through the context's own buffers on c->stream.
+#include "rr_ctx.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+namespace rr {
+namespace {
+
+// the compare and align forms work through their images 64 at a time: scratch of 256 KB of histogram (kBins words) or one curve per image of a chunk
+constexpr size_t kChunk = 64, kBins = 65536;
+
+// skimage.metrics.peak_signal_noise_ratio for uint8 (scripts/radaray_opti.py:196): data_range 255,
+// err = mean of the squared differences in f64 (exact here: an integer sum below 2^53), 10 log10(255^2 / err)
+double psnr_of(uint64_t sse, size_t npx)
+{
+    const double err = (double)sse / (double)npx;
+    return err > 0.0 ? 10.0 * std::log10((255.0 * 255.0) / err) : INFINITY;
+}
+
+// ---- refusals ---------------------------------------------------------------------------------------------------------
+// what every check below opens with: a context with a config, the caller's buffers, a count in range
+int check_images(rr_ctx* c, const std::string& w, bool have_buffers, const char* buffers, const char* count, int n, int n_max)
+{
+    if (!c) return -1;
+    if (!c->have_cfg) return fail(c, -2, "rr_set_config has not been called");
+    if (!have_buffers) return fail(c, -3, w + ": null " + buffers);
+    if (n < 1 || n > n_max) return fail(c, -3, w + ": " + count + " must be 1.." + std::to_string(n_max));
+    return 0;
+}
+
+// the refusals of rr_align_images_device / rr_align_images / rr_simulate_batch_align
+int check_align(rr_ctx* c, const char* who, const void* imgs, int n_images, int n_max, const void* ref, int cell_begin, int cell_end, const void* out)
+{
+    const std::string w(who);
+    int rc = check_images(c, w, imgs && ref && out, "buffer", "n_images", n_images, n_max); if (rc) return rc;
+    if (cell_begin < 0 || cell_end > c->cfg.n_cells || cell_begin >= cell_end)
+        return fail(c, -3, w + ": the cell window [" + std::to_string(cell_begin) + ", " + std::to_string(cell_end) + ") must be non-empty and inside 0.." +
+                               std::to_string(c->cfg.n_cells));
+    if ((long long)(cell_end - cell_begin) * c->cfg.n_angles > (1ll << 23))
+        return fail(c, -3, w + ": a window of more than 2^23 pixels");
+    return 0;
+}
+
+int check_detect(rr_ctx* c, const char* who, const void* imgs, int n_frames, const rr_detect_config* d, const void* points,
+                 int max_points, const void* offsets)
+{
+    const std::string w(who);
+    int rc = check_images(c, w, imgs != nullptr, "images", "n_frames", n_frames, 65535); if (rc) return rc;
+    if (!d) return fail(c, -3, w + ": null config");
+    if (!offsets) return fail(c, -3, w + ": null offsets");
+    if (max_points < 0) return fail(c, -3, w + ": max_points must be >= 0");
+    if (max_points > 0 && !points) return fail(c, -3, w + ": null points with max_points > 0");
+    const int n_cells = c->cfg.n_cells;
+    if (d->method != 0 && d->method != 1) return fail(c, -3, w + ": method must be 0 (CA-CFAR) or 1 (k-strongest)");
+    if (d->guard_cells < 0 || d->guard_cells > 1024) return fail(c, -3, w + ": guard_cells must be 0..1024");
+    if (d->train_cells < 1 || d->train_cells > 1024) return fail(c, -3, w + ": train_cells must be 1..1024");
+    if (d->k < 1 || d->k > n_cells) return fail(c, -3, w + ": k must be 1..n_cells (" + std::to_string(n_cells) + ")");
+    if (d->min_intensity < 0 || d->min_intensity > 255) return fail(c, -3, w + ": min_intensity must be 0..255");
+    if (d->min_bin < 0 || d->min_bin >= n_cells) return fail(c, -3, w + ": min_bin must be 0..n_cells-1");
+    if (!(std::isfinite(d->cfar_scale) && d->cfar_scale >= 0.0f)) return fail(c, -3, w + ": cfar_scale must be finite and >= 0");
+    return 0;
+}
+
+int check_cartesian(rr_ctx* c, const char* who, const void* imgs, int n_frames, const rr_cartesian_config* k, const void* out)
+{
+    const std::string w(who);
+    int rc = check_images(c, w, imgs != nullptr, "images", "n_frames", n_frames, 65535); if (rc) return rc;
+    if (!k) return fail(c, -3, w + ": null config");
+    if (!out) return fail(c, -3, w + ": null output");
+    if (k->width < 1 || k->width > 8192) return fail(c, -3, w + ": width must be 1..8192");
+    if (k->interpolation != 0 && k->interpolation != 1) return fail(c, -3, w + ": interpolation must be 0 (nearest) or 1 (bilinear)");
+    if (!(std::isfinite(k->pixel_size) && k->pixel_size > 0.0f)) return fail(c, -3, w + ": pixel_size must be finite and > 0");
+    if (c->cfg.theta_inc == 0.0f) return fail(c, -3, w + ": the config's theta_inc is 0");
+    return 0;
+}
+
+// ---- the steps the forms share ----------------------------------------------------------------------------------------
+// the way out of a device form: the launches' error, its records to the host, the stream drained
+int records_back(rr_ctx* c, void* rec, const void* d_rec, size_t bytes, hipStream_t s)
+{
+    RR_HIP(c, hipGetLastError());
+    RR_HIP(c, hipMemcpyAsync(rec, d_rec, bytes, hipMemcpyDeviceToHost, s));
+    RR_HIP(c, hipStreamSynchronize(s));
+    return 0;
+}
+
+// the way into a host form: c->stream drained (the staging buffers may be reallocated), room for `m` images in d_conv_in, for the
+// reference image if there is one, and for whatever `ensure_more` sizes; then the reference and the `m` images go up on c->stream
+template <typename EnsureMore>
+int stage_images(rr_ctx* c, const uint8_t* imgs_u8, size_t m, const uint8_t* ref_u8, EnsureMore ensure_more)
+{
+    const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles;
+    RR_HIP(c, hipStreamSynchronize(c->stream));
+    RR_HIP(c, c->d_conv_in.ensure(m * npx));
+    if (ref_u8) RR_HIP(c, c->d_ref_img.ensure(npx));
+    int rc = ensure_more(); if (rc) return rc;
+    if (ref_u8) RR_HIP(c, hipMemcpyAsync(c->d_ref_img.p, ref_u8, npx, hipMemcpyHostToDevice, c->stream));
+    RR_HIP(c, hipMemcpyAsync(c->d_conv_in.p, imgs_u8, m * npx, hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+
+// rr_compare_images / rr_align_images: `n` images against a reference, kChunk at a time through d_conv_in.  `chunk(at, m, rec)` runs the device
+// form on the `m` staged images and brings that chunk's histograms or curves down; the caller's records are written once every chunk has succeeded
+template <typename Rec, typename EnsureMore, typename Chunk>
+int in_chunks(rr_ctx* c, const uint8_t* imgs_u8, size_t n, const uint8_t* ref_u8, Rec* out, EnsureMore ensure_more, Chunk chunk)
+{
+    const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles;
+    int rc = stage_images(c, imgs_u8, std::min(n, kChunk), ref_u8, ensure_more); if (rc) return rc;
+    std::vector<Rec> rec(n);
+    for (size_t at = 0; at < n; at += kChunk) {
+        const size_t m = std::min(kChunk, n - at);
+        if (at) RR_HIP(c, hipMemcpyAsync(c->d_conv_in.p, imgs_u8 + at * npx, m * npx, hipMemcpyHostToDevice, c->stream));
+        rc = chunk(at, m, rec.data() + at); if (rc) return rc;
+    }
+    std::copy(rec.begin(), rec.end(), out);
+    return 0;
+}
+
+}  // namespace
+
+// the refusals of rr_compare_images_device / rr_compare_images / rr_simulate_param_sets_metrics
+int check_compare(rr_ctx* c, const char* who, const void* imgs, int n_images, const void* ref, uint32_t which, int win_size, const void* out,
+                  const void* hist)
+{
+    const std::string w(who);
+    int rc = check_images(c, w, imgs && ref && out, "buffer", "n_images", n_images, 65535); if (rc) return rc;
+    const uint32_t all = RR_METRIC_PSNR | RR_METRIC_SSIM | RR_METRIC_INFO;
+    if (which == 0 || (which & ~all)) return fail(c, -3, w + ": which must be a non-empty mask of RR_METRIC_PSNR | RR_METRIC_SSIM | RR_METRIC_INFO");
+    if (which & RR_METRIC_SSIM) {
+        if (win_size < 3 || win_size > 15 || win_size % 2 == 0) return fail(c, -3, w + ": win_size must be odd and in 3..15");
+        if (c->cfg.n_cells < win_size || c->cfg.n_angles < win_size)
+            return fail(c, -3, w + ": the image (" + std::to_string(c->cfg.n_cells) + " x " + std::to_string(c->cfg.n_angles) + ") is smaller than the window");
+    }
+    if (hist && !(which & RR_METRIC_INFO)) return fail(c, -3, w + ": a joint histogram buffer needs RR_METRIC_INFO");
+    return 0;
+}
+
+}  // namespace rr
+
+extern "C" {
+
+int rr_score_images_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_images, const uint8_t* d_ref_u8, double* out_psnr,
+                           uint64_t* out_sse, void* stream)
+{
+    int rc = check_images(c, "rr_score_images_device", d_imgs_u8 && d_ref_u8 && (out_psnr || out_sse), "buffer", "n_images", n_images, 65535); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = stream_of(c, stream);
+    const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles;
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "sse words");
+    if (c->d_sse.n < (size_t)n_images) { RR_HIP(c, hipStreamSynchronize(s)); RR_HIP(c, c->d_sse.ensure((size_t)n_images)); }
+    RR_HIP(c, hipMemsetAsync(c->d_sse.p, 0, (size_t)n_images * sizeof(uint64_t), s));
+    launch_score(d_imgs_u8, d_ref_u8, npx, n_images, c->d_sse.p, s);
+    std::vector<uint64_t> sse((size_t)n_images);
+    rc = records_back(c, sse.data(), c->d_sse.p, sse.size() * sizeof(uint64_t), s); if (rc) return rc;
+    for (int k = 0; k < n_images; k++) {
+        if (out_sse) out_sse[k] = sse[(size_t)k];
+        if (out_psnr) out_psnr[k] = psnr_of(sse[(size_t)k], npx);
+    }
+    return 0;
+}
+
+// ---- images against one reference image: PSNR, SSIM, joint histogram and its entropies (rr_metrics.hip) --------------
+
+int rr_compare_images_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_images, const uint8_t* d_ref_u8, uint32_t which, int win_size,
+                             rr_image_metrics* out, uint32_t* d_joint_hist, void* stream)
+{
+    int rc = check_compare(c, "rr_compare_images_device", d_imgs_u8, n_images, d_ref_u8, which, win_size, out, d_joint_hist); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = stream_of(c, stream);
+    const rr_config& g = c->cfg;
+    const size_t npx = (size_t)g.n_cells * g.n_angles, n = (size_t)n_images;
+    const bool psnr = which & RR_METRIC_PSNR, ssim = which & RR_METRIC_SSIM, info = which & RR_METRIC_INFO;
+    const size_t chunk = std::min(n, kChunk);
+    const int n_blocks = ssim ? ssim_blocks(g.n_cells, g.n_angles, win_size) : 0;
+    const double ssim_count = ssim ? (double)(g.n_cells - win_size + 1) * (double)(g.n_angles - win_size + 1) : 1.0;
+    const bool own_hist = info && !d_joint_hist;
+    if ((psnr && c->d_sse.n < n) || (own_hist && c->d_mhist.n < chunk * kBins) || (ssim && c->d_ssim_part.n < chunk * (size_t)n_blocks) || c->d_mrec.n < n) {
+        RR_HIP(c, hipStreamSynchronize(s));             // an earlier call's kernels may still read what is freed here
+        if (psnr) RR_HIP(c, c->d_sse.ensure(n));
+        if (own_hist) RR_HIP(c, c->d_mhist.ensure(chunk * kBins));
+        if (ssim) RR_HIP(c, c->d_ssim_part.ensure(chunk * (size_t)n_blocks));
+        RR_HIP(c, c->d_mrec.ensure(n));
+    }
+    if (psnr) {
+        RR_HIP(c, hipMemsetAsync(c->d_sse.p, 0, n * sizeof(uint64_t), s));
+        launch_score(d_imgs_u8, d_ref_u8, npx, n_images, c->d_sse.p, s);
+    }
+    for (size_t at = 0; at < n; at += kChunk) {
+        const int m = (int)std::min(kChunk, n - at);
+        const uint8_t* imgs = d_imgs_u8 + at * npx;
+        uint32_t* H = !info ? nullptr : d_joint_hist ? d_joint_hist + at * kBins : c->d_mhist.p;
+        if (info) {
+            RR_HIP(c, hipMemsetAsync(H, 0, (size_t)m * kBins * sizeof(uint32_t), s));
+            launch_joint_hist(imgs, d_ref_u8, npx, m, H, c->metrics_hist, s);
+        }
+        if (ssim) launch_ssim(imgs, d_ref_u8, g.n_cells, g.n_angles, win_size, m, c->d_ssim_part.p, s);
+        launch_metrics_finish(H, ssim ? c->d_ssim_part.p : nullptr, n_blocks, ssim_count, psnr ? c->d_sse.p + at : nullptr, npx,
+                              c->d_mrec.p + at, m, s);
+    }
+    std::vector<rr_image_metrics> rec(n);
+    rc = records_back(c, rec.data(), c->d_mrec.p, n * sizeof(rr_image_metrics), s); if (rc) return rc;
+    for (size_t k = 0; k < n; k++) {
+        if (psnr) rec[k].psnr = psnr_of(rec[k].sse, npx);     // the host's log10, as rr_score_images_device: the same bits
+        out[k] = rec[k];
+    }
+    return 0;
+}
+
+int rr_compare_images(rr_ctx* c, const uint8_t* imgs_u8, int n_images, const uint8_t* ref_u8, uint32_t which, int win_size,
+                      rr_image_metrics* out, uint32_t* joint_hist)
+{
+    int rc = check_compare(c, "rr_compare_images", imgs_u8, n_images, ref_u8, which, win_size, out, joint_hist); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)n_images;
+    return in_chunks(c, imgs_u8, n, ref_u8, out,
+        [&]() { if (joint_hist) RR_HIP(c, c->d_conv_hist.ensure(std::min(n, kChunk) * kBins)); return 0; },
+        [&](size_t at, size_t m, rr_image_metrics* rec) {
+            // one chunk of the device form, its histograms into this form's own staging buffer
+            const int rcc = rr_compare_images_device(c, c->d_conv_in.p, (int)m, c->d_ref_img.p, which, win_size, rec,
+                                                     joint_hist ? c->d_conv_hist.p : nullptr, c->stream); if (rcc) return rcc;
+            if (joint_hist) RR_HIP(c, hipMemcpy(joint_hist + at * kBins, c->d_conv_hist.p, m * kBins * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            return 0;
+        });
+}
+
+// ---- azimuth registration: the circular cross-correlation over all shifts (rr_align.hip) ------------------------------
+
+int rr_align_images_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_images, const uint8_t* d_ref_u8, int cell_begin, int cell_end,
+                           rr_align_record* out, int64_t* d_xcorr, void* stream)
+{
+    int rc = check_align(c, "rr_align_images_device", d_imgs_u8, n_images, 65535, d_ref_u8, cell_begin, cell_end, out); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = stream_of(c, stream);
+    const rr_config& g = c->cfg;
+    const size_t npx = (size_t)g.n_cells * g.n_angles, n = (size_t)n_images, A = (size_t)g.n_angles;
+    const size_t chunk = std::min(n, kChunk);
+    static_assert(sizeof(long long) == sizeof(int64_t), "curve words");
+    if ((!d_xcorr && c->d_align_curve.n < chunk * A) || c->d_align_sums.n < 2 * (chunk + 1) || c->d_align_rec.n < n) {
+        RR_HIP(c, hipStreamSynchronize(s));             // an earlier call's kernels may still read what is freed here
+        if (!d_xcorr) RR_HIP(c, c->d_align_curve.ensure(chunk * A));
+        RR_HIP(c, c->d_align_sums.ensure(2 * (chunk + 1)));
+        RR_HIP(c, c->d_align_rec.ensure(n));
+    }
+    for (size_t at = 0; at < n; at += kChunk) {
+        const int m = (int)std::min(kChunk, n - at);
+        const uint8_t* imgs = d_imgs_u8 + at * npx;
+        long long* curve = d_xcorr ? reinterpret_cast<long long*>(d_xcorr) + at * A : c->d_align_curve.p;
+        RR_HIP(c, hipMemsetAsync(curve, 0, (size_t)m * A * sizeof(long long), s));
+        RR_HIP(c, hipMemsetAsync(c->d_align_sums.p, 0, 2 * ((size_t)m + 1) * sizeof(unsigned long long), s));
+        launch_align_sums(imgs, d_ref_u8, g.n_cells, g.n_angles, cell_begin, cell_end, m, c->d_align_sums.p, s);
+        launch_align_gram(imgs, d_ref_u8, g.n_cells, g.n_angles, cell_begin, cell_end, m, curve, s);
+        launch_align_finish(curve, c->d_align_sums.p, m, g.n_angles, cell_begin, cell_end, c->d_align_rec.p + at, s);
+    }
+    std::vector<rr_align_record> rec(n);
+    rc = records_back(c, rec.data(), c->d_align_rec.p, n * sizeof(rr_align_record), s); if (rc) return rc;
+    const size_t n_win = (size_t)(cell_end - cell_begin) * A;
+    for (size_t k = 0; k < n; k++) {
+        rec[k].psnr = psnr_of(rec[k].sse, n_win);       // the host's log10, as rr_score_images_device
+        out[k] = rec[k];
+    }
+    return 0;
+}
+
+int rr_align_images(rr_ctx* c, const uint8_t* imgs_u8, int n_images, const uint8_t* ref_u8, int cell_begin, int cell_end,
+                    rr_align_record* out, int64_t* xcorr)
+{
+    int rc = check_align(c, "rr_align_images", imgs_u8, n_images, 65535, ref_u8, cell_begin, cell_end, out); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)n_images, A = (size_t)c->cfg.n_angles;
+    return in_chunks(c, imgs_u8, n, ref_u8, out,
+        [&]() { if (xcorr) RR_HIP(c, c->d_conv_curve.ensure(std::min(n, kChunk) * A)); return 0; },
+        [&](size_t at, size_t m, rr_align_record* rec) {
+            const int rcc = rr_align_images_device(c, c->d_conv_in.p, (int)m, c->d_ref_img.p, cell_begin, cell_end, rec,
+                                                   xcorr ? reinterpret_cast<int64_t*>(c->d_conv_curve.p) : nullptr, c->stream); if (rcc) return rcc;
+            if (xcorr) RR_HIP(c, hipMemcpy(xcorr + at * A, c->d_conv_curve.p, m * A * sizeof(int64_t), hipMemcpyDeviceToHost));
+            return 0;
+        });
+}
+
+int rr_simulate_batch_align(rr_ctx* c, const float* poses, int n_frames, const uint8_t* ref_img_u8, int cell_begin, int cell_end,
+                            uint8_t* out_imgs_u8, rr_align_record* out, int64_t* xcorr)
+{
+    // refused before anything is simulated (the context stands in for the images: they are its own)
+    int rc = check_align(c, "rr_simulate_batch_align", c, n_frames, RR_MAX_BATCH, ref_img_u8, cell_begin, cell_end, out); if (rc) return rc;
+    rc = check_ready(c); if (rc) return rc;
+    if (!poses) return fail(c, -3, "rr_simulate_batch_align: null poses");
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles, n = (size_t)n_frames, A = (size_t)c->cfg.n_angles;
+    RR_HIP(c, hipStreamSynchronize(c->stream));        // the buffers may be reallocated below
+    RR_HIP(c, c->d_param_imgs.ensure(n * npx));
+    RR_HIP(c, c->d_ref_img.ensure(npx));
+    if (xcorr) RR_HIP(c, c->d_conv_curve.ensure(n * A));
+    RR_HIP(c, hipMemcpyAsync(c->d_ref_img.p, ref_img_u8, npx, hipMemcpyHostToDevice, c->stream));
+    rc = rr_simulate_batch_device(c, poses, n_frames, c->d_param_imgs.p, c->stream); if (rc) return rc;
+    std::vector<rr_align_record> rec(n);
+    rc = rr_align_images_device(c, c->d_param_imgs.p, n_frames, c->d_ref_img.p, cell_begin, cell_end, rec.data(),
+                                xcorr ? reinterpret_cast<int64_t*>(c->d_conv_curve.p) : nullptr, c->stream); if (rc) return rc;   // synchronises the stream
+    rc = report_frame_errors(c); if (rc) return rc;     // before anything is handed out
+    if (out_imgs_u8) RR_HIP(c, hipMemcpy(out_imgs_u8, c->d_param_imgs.p, n * npx, hipMemcpyDeviceToHost));
+    if (xcorr) RR_HIP(c, hipMemcpy(xcorr, c->d_conv_curve.p, n * A * sizeof(int64_t), hipMemcpyDeviceToHost));
+    std::copy(rec.begin(), rec.end(), out);
+    return 0;
+}
+
+// ---- point clouds and Cartesian images (rr_detect.hip) ---------------------------------------------------------------
+void rr_default_detect_config(rr_detect_config* cfg)
+{
+    if (!cfg) return;
+    std::memset(cfg, 0, sizeof(*cfg));
+    cfg->method = 0; cfg->guard_cells = 2; cfg->train_cells = 16; cfg->k = 12;
+    cfg->min_intensity = 1; cfg->min_bin = 0; cfg->cfar_scale = 3.0f;
+}
+
+int rr_detect_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_frames, const rr_detect_config* cfg, rr_radar_point* d_points,
+                     int max_points, uint32_t* d_offsets, void* stream)
+{
+    int rc = check_detect(c, "rr_detect_device", d_imgs_u8, n_frames, cfg, d_points, max_points, d_offsets); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const rr_config& g = c->cfg;
+    hipStream_t s = stream_of(c, stream);
+    launch_detect(d_imgs_u8, n_frames, *cfg, g.n_cells, g.n_angles, g.scroll_image, g.theta_min, g.theta_inc, g.resolution,
+                  max_points > 0 ? d_points : nullptr, max_points, d_offsets, s);
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_detect(rr_ctx* c, const uint8_t* imgs_u8, int n_frames, const rr_detect_config* cfg, rr_radar_point* points,
+              int max_points, uint32_t* offsets)
+{
+    int rc = check_detect(c, "rr_detect", imgs_u8, n_frames, cfg, points, max_points, offsets); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t n_offs = (size_t)n_frames * (c->cfg.n_angles + 1), n_pts = (size_t)n_frames * (size_t)max_points;
+    rc = stage_images(c, imgs_u8, (size_t)n_frames, nullptr, [&]() {
+        RR_HIP(c, c->d_conv_offs.ensure(n_offs));
+        if (n_pts) RR_HIP(c, c->d_conv_points.ensure(n_pts));
+        return 0;
+    });
+    if (rc) return rc;
+    rc = rr_detect_device(c, c->d_conv_in.p, n_frames, cfg, n_pts ? c->d_conv_points.p : nullptr, max_points, c->d_conv_offs.p, c->stream);
+    if (rc) return rc;
+    RR_HIP(c, hipMemcpyAsync(offsets, c->d_conv_offs.p, n_offs * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (n_pts) RR_HIP(c, hipMemcpyAsync(points, c->d_conv_points.p, n_pts * sizeof(rr_radar_point), hipMemcpyDeviceToHost, c->stream));
+    RR_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int rr_polar_to_cartesian_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_frames, const rr_cartesian_config* cfg,
+                                 uint8_t* d_cart_u8, void* stream)
+{
+    int rc = check_cartesian(c, "rr_polar_to_cartesian_device", d_imgs_u8, n_frames, cfg, d_cart_u8); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const rr_config& g = c->cfg;
+    hipStream_t s = stream_of(c, stream);
+    launch_cartesian(d_imgs_u8, n_frames, *cfg, g.n_cells, g.n_angles, g.scroll_image, g.theta_min, g.theta_inc, (float)g.resolution,
+                     d_cart_u8, s);
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_polar_to_cartesian(rr_ctx* c, const uint8_t* imgs_u8, int n_frames, const rr_cartesian_config* cfg, uint8_t* cart_u8)
+{
+    int rc = check_cartesian(c, "rr_polar_to_cartesian", imgs_u8, n_frames, cfg, cart_u8); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t n_out = (size_t)n_frames * cfg->width * cfg->width;
+    rc = stage_images(c, imgs_u8, (size_t)n_frames, nullptr, [&]() { RR_HIP(c, c->d_conv_cart.ensure(n_out)); return 0; });
+    if (rc) return rc;
+    rc = rr_polar_to_cartesian_device(c, c->d_conv_in.p, n_frames, cfg, c->d_conv_cart.p, c->stream); if (rc) return rc;
+    RR_HIP(c, hipMemcpyAsync(cart_u8, c->d_conv_cart.p, n_out, hipMemcpyDeviceToHost, c->stream));
+    RR_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+}  // extern "C"

@@ -507,15 +507,14 @@ void rr_destroy_multi(rr_multi* m)
     for (MultiSlot& S : m->slots) {
         for (size_t i = 0; i < S.streams.size(); i++) {
             (void)hipSetDevice(m->devices[i]);
-            if (i < S.block.size()) S.block[i].release();
             if (S.ev_block[i]) (void)hipEventDestroy(S.ev_block[i]);
             if (S.owns_streams && S.streams[i]) (void)hipStreamDestroy(S.streams[i]);
         }
         (void)hipSetDevice(m->devices[0]);
-        S.gathered.release(); S.d_imgs.release();
         if (S.ev_done) (void)hipEventDestroy(S.ev_done);
         if (S.h_bits) (void)hipHostFree(S.h_bits);
     }
+    m->slots.clear();             // the slots' buffers go here, ahead of their devices' contexts (hipFree finds a pointer's device itself)
     for (size_t i = 0; i < m->ctx.size(); i++) rr_destroy(m->ctx[i]);
     delete m;
 }

@@ -123,31 +123,20 @@ int rr_debug_fresnel(rr_ctx* c, size_t n, const float* normals, const float* dir
         return fail(c, -3, "rr_debug_fresnel: null pointer");
     RR_HIP(c, hipSetDevice(c->device));
     DevBuf<float> d_n, d_d, d_v2, d_rd, d_td; DevBuf<double> d_e, d_v1, d_re, d_te;
-    hipError_t e = d_n.ensure(3 * n);
-    if (e == hipSuccess) e = d_d.ensure(3 * n);
-    if (e == hipSuccess) e = d_v2.ensure(n);
-    if (e == hipSuccess) e = d_rd.ensure(3 * n);
-    if (e == hipSuccess) e = d_td.ensure(3 * n);
-    if (e == hipSuccess) e = d_e.ensure(n);
-    if (e == hipSuccess) e = d_v1.ensure(n);
-    if (e == hipSuccess) e = d_re.ensure(n);
-    if (e == hipSuccess) e = d_te.ensure(n);
-    if (e == hipSuccess) e = hipMemcpy(d_n.p, normals, 3 * n * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_d.p, dirs, 3 * n * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_v2.p, v2, n * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_e.p, energy, n * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_v1.p, v1, n * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        launch_debug_fresnel(n, d_n.p, d_d.p, d_e.p, d_v1.p, d_v2.p, d_rd.p, d_re.p, d_td.p, d_te.p, c->stream);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    }
-    if (e == hipSuccess) e = hipMemcpy(out_refl_dir, d_rd.p, 3 * n * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(out_refr_dir, d_td.p, 3 * n * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(out_refl_energy, d_re.p, n * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(out_refr_energy, d_te.p, n * sizeof(double), hipMemcpyDeviceToHost);
-    d_n.release(); d_d.release(); d_v2.release(); d_rd.release(); d_td.release(); d_e.release(); d_v1.release(); d_re.release(); d_te.release();
-    if (e != hipSuccess) return fail(c, -100, std::string("rr_debug_fresnel: ") + hipGetErrorString(e));
+    RR_HIP(c, d_n.ensure(3 * n)); RR_HIP(c, d_d.ensure(3 * n)); RR_HIP(c, d_v2.ensure(n)); RR_HIP(c, d_rd.ensure(3 * n)); RR_HIP(c, d_td.ensure(3 * n));
+    RR_HIP(c, d_e.ensure(n)); RR_HIP(c, d_v1.ensure(n)); RR_HIP(c, d_re.ensure(n)); RR_HIP(c, d_te.ensure(n));
+    RR_HIP(c, hipMemcpy(d_n.p, normals, 3 * n * sizeof(float), hipMemcpyHostToDevice));
+    RR_HIP(c, hipMemcpy(d_d.p, dirs, 3 * n * sizeof(float), hipMemcpyHostToDevice));
+    RR_HIP(c, hipMemcpy(d_v2.p, v2, n * sizeof(float), hipMemcpyHostToDevice));
+    RR_HIP(c, hipMemcpy(d_e.p, energy, n * sizeof(double), hipMemcpyHostToDevice));
+    RR_HIP(c, hipMemcpy(d_v1.p, v1, n * sizeof(double), hipMemcpyHostToDevice));
+    launch_debug_fresnel(n, d_n.p, d_d.p, d_e.p, d_v1.p, d_v2.p, d_rd.p, d_re.p, d_td.p, d_te.p, c->stream);
+    RR_HIP(c, hipGetLastError());
+    RR_HIP(c, hipStreamSynchronize(c->stream));
+    RR_HIP(c, hipMemcpy(out_refl_dir, d_rd.p, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
+    RR_HIP(c, hipMemcpy(out_refr_dir, d_td.p, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
+    RR_HIP(c, hipMemcpy(out_refl_energy, d_re.p, n * sizeof(double), hipMemcpyDeviceToHost));
+    RR_HIP(c, hipMemcpy(out_refr_energy, d_te.p, n * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -159,17 +148,13 @@ int rr_debug_brdf(rr_ctx* c, size_t n, const float* in5, int brdf_model, float* 
     if (brdf_model != 0 && brdf_model != 1) return fail(c, -3, "rr_debug_brdf: brdf_model must be 0 or 1");
     RR_HIP(c, hipSetDevice(c->device));
     DevBuf<float> d_in, d_out;
-    hipError_t e = d_in.ensure(5 * n);
-    if (e == hipSuccess) e = d_out.ensure(n);
-    if (e == hipSuccess) e = hipMemcpy(d_in.p, in5, 5 * n * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        launch_debug_brdf(n, d_in.p, brdf_model, d_out.p, c->stream);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    }
-    if (e == hipSuccess) e = hipMemcpy(out, d_out.p, n * sizeof(float), hipMemcpyDeviceToHost);
-    d_in.release(); d_out.release();
-    if (e != hipSuccess) return fail(c, -100, std::string("rr_debug_brdf: ") + hipGetErrorString(e));
+    RR_HIP(c, d_in.ensure(5 * n));
+    RR_HIP(c, d_out.ensure(n));
+    RR_HIP(c, hipMemcpy(d_in.p, in5, 5 * n * sizeof(float), hipMemcpyHostToDevice));
+    launch_debug_brdf(n, d_in.p, brdf_model, d_out.p, c->stream);
+    RR_HIP(c, hipGetLastError());
+    RR_HIP(c, hipStreamSynchronize(c->stream));
+    RR_HIP(c, hipMemcpy(out, d_out.p, n * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -191,18 +176,16 @@ int rr_debug_trace(rr_ctx* c, const float* origs, const float* dirs, size_t n, f
     P.tri_base4 = c->tri_base4; P.range_max = c->have_cfg ? c->cfg.range_max : 1000.0f; P.hit_pad = c->hit_pad;
     P.spill = d_spill.p; P.spill_stride = (int)chunk; P.stack_lds = stack_lds; P.spill_depth = std::max(0, spill_depth);
     P.cull_pop = c->cull_pop;
-    int rc = 0;
-    for (size_t b = 0; b < n && !rc; b += chunk) {
+    for (size_t b = 0; b < n; b += chunk) {
         const size_t m = std::min(chunk, n - b);
-        hipError_t e = hipMemcpy(d_o.p, origs + 3 * b, 3 * m * sizeof(float), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_d.p, dirs + 3 * b, 3 * m * sizeof(float), hipMemcpyHostToDevice);
-        if (e == hipSuccess) { launch_debug_trace(P, d_o.p, d_d.p, (int)m, d_t.p, d_f.p, c->stream); e = hipStreamSynchronize(c->stream); }
-        if (e == hipSuccess) e = hipMemcpy(out_t + b, d_t.p, m * sizeof(float), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(out_face + b, d_f.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(c, -100, std::string("rr_debug_trace: ") + hipGetErrorString(e));
+        RR_HIP(c, hipMemcpy(d_o.p, origs + 3 * b, 3 * m * sizeof(float), hipMemcpyHostToDevice));
+        RR_HIP(c, hipMemcpy(d_d.p, dirs + 3 * b, 3 * m * sizeof(float), hipMemcpyHostToDevice));
+        launch_debug_trace(P, d_o.p, d_d.p, (int)m, d_t.p, d_f.p, c->stream);
+        RR_HIP(c, hipStreamSynchronize(c->stream));
+        RR_HIP(c, hipMemcpy(out_t + b, d_t.p, m * sizeof(float), hipMemcpyDeviceToHost));
+        RR_HIP(c, hipMemcpy(out_face + b, d_f.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
     }
-    d_o.release(); d_d.release(); d_t.release(); d_f.release(); d_spill.release();
-    return rc;
+    return 0;
 }
 
 }  // extern "C"

@@ -94,12 +94,11 @@ int refit_prepare(rr_ctx* c)
     std::vector<uint32_t> refs(4 * nn);
     if (nn) {
         DevBuf<uint32_t> d_refs;
-        hipError_t e = d_refs.ensure(4 * nn);
-        if (e == hipSuccess) { launch_gather_refs(reinterpret_cast<const Node4*>(c->d_bvh.p), nn, d_refs.p, c->stream); e = hipGetLastError(); }
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) e = hipMemcpy(refs.data(), d_refs.p, refs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
-        d_refs.release();
-        RR_HIP(c, e);
+        RR_HIP(c, d_refs.ensure(4 * nn));
+        launch_gather_refs(reinterpret_cast<const Node4*>(c->d_bvh.p), nn, d_refs.p, c->stream);
+        RR_HIP(c, hipGetLastError());
+        RR_HIP(c, hipStreamSynchronize(c->stream));
+        RR_HIP(c, hipMemcpy(refs.data(), d_refs.p, refs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     }
     std::vector<uint32_t> order;
     order.reserve(nn);
@@ -226,26 +225,22 @@ int measure_tree_steps(rr_ctx* c, const float lo[3], const float hi[3], double* 
     const int stack_lds = (int)std::max<uint32_t>(1, std::min<uint32_t>(c->stack_need, (uint32_t)c->stack_lds_max));
     const int spill_depth = (int)c->stack_need - stack_lds;
     DevBuf<float> d_o, d_d; DevBuf<uint32_t> d_spill; DevBuf<unsigned long long> d_steps;
-    hipError_t e = d_o.ensure(3 * (size_t)n);
-    if (e == hipSuccess) e = d_d.ensure(3 * (size_t)n);
-    if (e == hipSuccess) e = d_spill.ensure(spill_depth > 0 ? (size_t)spill_depth * n : 1);
-    if (e == hipSuccess) e = d_steps.ensure(1);
-    if (e == hipSuccess) e = hipMemcpy(d_o.p, o.data(), o.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_d.p, d.data(), d.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(d_steps.p, 0, sizeof(unsigned long long));
+    RR_HIP(c, d_o.ensure(3 * (size_t)n));
+    RR_HIP(c, d_d.ensure(3 * (size_t)n));
+    RR_HIP(c, d_spill.ensure(spill_depth > 0 ? (size_t)spill_depth * n : 1));
+    RR_HIP(c, d_steps.ensure(1));
+    RR_HIP(c, hipMemcpy(d_o.p, o.data(), o.size() * sizeof(float), hipMemcpyHostToDevice));
+    RR_HIP(c, hipMemcpy(d_d.p, d.data(), d.size() * sizeof(float), hipMemcpyHostToDevice));
+    RR_HIP(c, hipMemset(d_steps.p, 0, sizeof(unsigned long long)));
+    Params P; std::memset(&P, 0, sizeof(P));
+    P.nodes = reinterpret_cast<const Node4*>(c->d_bvh.p); P.tris = reinterpret_cast<const TriRec*>(c->d_bvh.p + c->tri_base4);
+    P.tri_base4 = c->tri_base4; P.range_max = c->have_cfg ? c->cfg.range_max : 1000.0f; P.hit_pad = c->hit_pad;
+    P.spill = d_spill.p; P.spill_stride = n; P.stack_lds = stack_lds; P.spill_depth = std::max(0, spill_depth);
+    P.cull_pop = c->cull_pop;
+    launch_debug_trace(P, d_o.p, d_d.p, n, nullptr, nullptr, c->stream, d_steps.p);
+    RR_HIP(c, hipStreamSynchronize(c->stream));
     unsigned long long h = 0;
-    if (e == hipSuccess) {
-        Params P; std::memset(&P, 0, sizeof(P));
-        P.nodes = reinterpret_cast<const Node4*>(c->d_bvh.p); P.tris = reinterpret_cast<const TriRec*>(c->d_bvh.p + c->tri_base4);
-        P.tri_base4 = c->tri_base4; P.range_max = c->have_cfg ? c->cfg.range_max : 1000.0f; P.hit_pad = c->hit_pad;
-        P.spill = d_spill.p; P.spill_stride = n; P.stack_lds = stack_lds; P.spill_depth = std::max(0, spill_depth);
-        P.cull_pop = c->cull_pop;
-        launch_debug_trace(P, d_o.p, d_d.p, n, nullptr, nullptr, c->stream, d_steps.p);
-        e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) e = hipMemcpy(&h, d_steps.p, sizeof(h), hipMemcpyDeviceToHost);
-    }
-    d_o.release(); d_d.release(); d_spill.release(); d_steps.release();
-    if (e != hipSuccess) return fail(c, -100, std::string("rr_set_mesh (tree choice): ") + hipGetErrorString(e));
+    RR_HIP(c, hipMemcpy(&h, d_steps.p, sizeof(h), hipMemcpyDeviceToHost));
     *steps_per_ray = (double)h / n;
     return 0;
 }
@@ -458,17 +453,13 @@ int rr_rebuild_tree(rr_ctx* c, int builder)
     std::vector<uint32_t> obj(nf), faces(3 * nf);
     {
         DevBuf<float> d_soup; DevBuf<uint32_t> d_obj;
-        hipError_t e = d_soup.ensure(9 * nf);
-        if (e == hipSuccess) e = d_obj.ensure(nf);
-        if (e == hipSuccess) {
-            launch_pose_soup(dev_tris(c), c->n_tris, c->d_rest_v.p, c->d_rest_f.p, c->d_poses.p, d_soup.p, d_obj.p, c->stream);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) e = hipMemcpy(soup.data(), d_soup.p, soup.size() * sizeof(float), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(obj.data(), d_obj.p, obj.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
-        d_soup.release(); d_obj.release();
-        RR_HIP(c, e);
+        RR_HIP(c, d_soup.ensure(9 * nf));
+        RR_HIP(c, d_obj.ensure(nf));
+        launch_pose_soup(dev_tris(c), c->n_tris, c->d_rest_v.p, c->d_rest_f.p, c->d_poses.p, d_soup.p, d_obj.p, c->stream);
+        RR_HIP(c, hipGetLastError());
+        RR_HIP(c, hipStreamSynchronize(c->stream));
+        RR_HIP(c, hipMemcpy(soup.data(), d_soup.p, soup.size() * sizeof(float), hipMemcpyDeviceToHost));
+        RR_HIP(c, hipMemcpy(obj.data(), d_obj.p, obj.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     }
     for (size_t i = 0; i < 3 * nf; i++) faces[i] = (uint32_t)i;
     // the build replaces the tree (and bumps graph_gen: the tree moves); the rest data, the poses and the trace-grid

@@ -126,23 +126,16 @@ int finish_param_batch(rr_ctx* c, int n_sets, uint8_t* out_imgs_u8, const uint8_
 {
     const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles;
     if (out_imgs_u8) RR_HIP(c, hipMemcpyAsync(out_imgs_u8, c->d_param_imgs.p, (size_t)n_sets * npx, hipMemcpyDeviceToHost, c->stream));
-    if (ref_img_u8 && out_psnr) {
+    if (ref_img_u8 && (out_psnr || out_metrics)) {
         RR_HIP(c, c->d_ref_img.ensure(npx));
         RR_HIP(c, hipMemcpyAsync(c->d_ref_img.p, ref_img_u8, npx, hipMemcpyHostToDevice, c->stream));
-        const int rc = rr_score_images_device(c, c->d_param_imgs.p, n_sets, c->d_ref_img.p, out_psnr, nullptr, c->stream);   // synchronises the stream
-        if (rc) return rc;
-    }
-    if (ref_img_u8 && out_metrics) {
-        RR_HIP(c, c->d_ref_img.ensure(npx));
-        RR_HIP(c, hipMemcpyAsync(c->d_ref_img.p, ref_img_u8, npx, hipMemcpyHostToDevice, c->stream));
-        const int rc = rr_compare_images_device(c, c->d_param_imgs.p, n_sets, c->d_ref_img.p, which, win_size, out_metrics, nullptr, c->stream);
+        int rc = 0;     // (both synchronise the stream)
+        if (out_psnr) rc = rr_score_images_device(c, c->d_param_imgs.p, n_sets, c->d_ref_img.p, out_psnr, nullptr, c->stream);
+        if (!rc && out_metrics) rc = rr_compare_images_device(c, c->d_param_imgs.p, n_sets, c->d_ref_img.p, which, win_size, out_metrics, nullptr, c->stream);
         if (rc) return rc;
     }
     RR_HIP(c, hipStreamSynchronize(c->stream));
-    Counters h;
-    { const int rcb = read_counters(c, h); if (rcb) return rcb; }
-    if (h.overflow) RR_HIP(c, hipMemset(c->lanes[c->last_lane].d_sticky.p, 0, sizeof(uint32_t)));
-    return overflow_error(c, h.overflow);
+    return report_frame_errors(c);
 }
 }  // namespace
 
