@@ -589,6 +589,64 @@ int rr_polar_to_cartesian_device(rr_ctx* ctx, const uint8_t* d_imgs_u8, int n_fr
 int rr_polar_to_cartesian(rr_ctx* ctx, const uint8_t* imgs_u8, int n_frames, const rr_cartesian_config* cfg,
                           uint8_t* cart_u8);                                         /* host buffers, synchronous */
 
+/* ---- translation registration (rr_shift.hip) ----------------------------------------------------------------------
+ * rr_align_images settles the yaw; the other two degrees of freedom of a planar pose, x and y, are to first order a
+ * translation of the Cartesian bird's-eye image (rr_polar_to_cartesian).  One exact 2-D cross-correlation over a window of
+ * pixel shifts replaces a grid of simulated positions.  The reference has no registration step: this is the build's own
+ * definition, unpinned by anything the reference holds.
+ * Images are uint8 [H][W], row-major; n images x_k are compared with one reference r.  H = height, W = width and
+ * S = max_shift are call arguments: the call depends on no config and no mesh.  T is the template window, rows [S, H-S) by
+ * columns [S, W-S), N = (H-2S)(W-2S) pixels; every index of r below is in range, nothing wraps and nothing is padded.
+ * For dy, dx in -S..S:
+ *   xcorr[dy][dx] = sum over (i,j) in T of x[i][j] * r[i+dy][j+dx]                           exact int64
+ *   (dy, dx) is where the content of x is found in r.
+ * Sx, Sxx are the sums of x and x^2 over T; Sr[dy][dx], Srr[dy][dx] the sums of r and r^2 over T moved by (dy, dx) (box sums
+ * of the reference, computed once per call and shared by all n images).  All exact uint64.
+ *   sse[d]  = Sxx + Srr[d] - 2 xcorr[d]                                                      exact uint64
+ *   psnr    = from sse and N with the expression of rr_score_images_device (+inf at sse == 0)
+ *   ncc[d]  = (N xcorr[d] - Sx Sr[d]) / sqrt((N Sxx - Sx^2)(N Srr[d] - Sr[d]^2)): the numerator and the two factors are exact
+ *             int64, converted to f64, then one multiply, one sqrt, one divide; 0 when either factor is 0
+ *   best    = the shift with the smallest sse (NOT the largest xcorr: Srr depends on the shift); a tie goes to the smallest
+ *             index (dy+S)(2S+1) + (dx+S); n_best = the number of shifts that attain it
+ *   sub_dy, sub_dx = 0.5 (e[-1] - e[+1]) / (e[-1] - 2 e[0] + e[+1]) along each axis at the best shift, e = sse: numerator and
+ *             denominator are exact integers, converted to f64, the numerator halved, one divide; 0 when a neighbour lies
+ *             outside -S..S or the denominator is <= 0
+ * A record holds xcorr, sse, psnr, ncc, sum_r and sum_rr AT the best shift, and the SSE of its four neighbours (UINT64_MAX
+ * where a neighbour lies outside -S..S).  d_xcorr and d_sse (HBM, [n_images][2S+1][2S+1], index [dy+S][dx+S], or NULL)
+ * receive the whole surfaces.  Synchronous on `stream`, context-owned scratch, more than 64 images in chunks, one call per
+ * context at a time: the conventions of rr_align_images_device.
+ * Limits: H, W in 1..8192; 0 <= S <= 64; H > 2S and W > 2S; N <= 2^23 (which keeps N xcorr inside int64); n_images 1..65535.
+ * Refused with a message and nothing written: -3 for a null buffer or an argument outside these limits.
+ * Pose meaning.  rr_polar_to_cartesian puts pixel (i, j) at forward (c - i) pixel_size and left (c - j) pixel_size, and a
+ * world point p seen from pose t lies at p - t in the sensor frame.  So if x was rendered at t_x and r taken at t_r with the
+ * same yaw, content moves by t_x - t_r, which in metres is (-dy, -dx) pixel_size.  The correction to ADD to the simulated
+ * pose, in the sensor's own (forward, left) axes, is therefore (+dy pixel_size, +dx pixel_size). */
+typedef struct rr_shift_record {   /* 128 B */
+    int32_t dy, dx, n_best, reserved_;
+    int64_t xcorr;            /* at (dy, dx) */
+    uint64_t sse;             /* at (dy, dx) */
+    double psnr, ncc;         /* at (dy, dx) */
+    double sub_dy, sub_dx;    /* sub-pixel offsets to add to dy, dx */
+    uint64_t sse_nb[4];       /* sse at dy-1, dy+1, dx-1, dx+1; UINT64_MAX outside -S..S */
+    uint64_t sum_x, sum_xx;   /* over T */
+    uint64_t sum_r, sum_rr;   /* over T moved by (dy, dx) */
+} rr_shift_record;
+int rr_shift_images_device(rr_ctx* ctx, const uint8_t* d_imgs_u8, int n_images, const uint8_t* d_ref_u8, int height, int width,
+                           int max_shift, rr_shift_record* out /* host [n_images] */,
+                           int64_t* d_xcorr /* HBM [n_images][2S+1][2S+1], or NULL */,
+                           uint64_t* d_sse /* HBM [n_images][2S+1][2S+1], or NULL */, void* stream);
+/* The host-buffer form: imgs_u8 [n_images][H][W], ref_u8 [H][W], xcorr and sse host [n_images][2S+1][2S+1] or NULL.
+ * Synchronous; staged 64 images at a time, the records written once all of them are done, the surfaces chunk by chunk. */
+int rr_shift_images(rr_ctx* ctx, const uint8_t* imgs_u8, int n_images, const uint8_t* ref_u8, int height, int width, int max_shift,
+                    rr_shift_record* out, int64_t* xcorr, uint64_t* sse);
+/* rr_simulate_batch_device into a context-owned image buffer, rr_polar_to_cartesian_device on the n images and on
+ * ref_polar_u8 (host, [n_cells][n_angles]), then rr_shift_images_device with H = W = cfg->width: one simulated pose in, its
+ * translation against the real scan out.  n_frames is 1..RR_MAX_BATCH; out_cart_u8 (host, [n_frames][width][width]) or NULL,
+ * and with NULL no image leaves the GPU; xcorr host [n_frames][2S+1][2S+1] or NULL.  Refusals: those of
+ * rr_simulate_batch_align, rr_polar_to_cartesian and rr_shift_images_device. */
+int rr_simulate_batch_shift(rr_ctx* ctx, const float* poses, int n_frames, const uint8_t* ref_polar_u8, const rr_cartesian_config* cfg,
+                            int max_shift, uint8_t* out_cart_u8, rr_shift_record* out, int64_t* xcorr);
+
 /* ---- several GPUs of one node behind one object (SURVEY.md §8b "Threading", §8e) -------------------------
  * The reference creates ONE backend object per process (src/radar_simulator.cpp:145-176) and fans out inside it
  * (OpenMP over azimuths, RadarCPU.cpp:155).  rr_multi is that object for n GPUs: one rr_ctx per device, mesh and

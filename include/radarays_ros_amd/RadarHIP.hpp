@@ -267,6 +267,25 @@ public:
         }
         return out;
     }
+    // Translation registration (rr_shift_record, include/radarays_mi355.h): the images and `real` made Cartesian (width x width,
+    // pixel_size m/pixel) and compared over -max_shift..max_shift pixels on both axes; (dy, dx) is where an image's content is found in
+    // `real`, with the exact SSE, PSNR and NCC there.  `correction` (or null) receives what to add to each image's pose in the
+    // sensor's own axes, metres [n][2] = (forward, left).  Empty on error.
+    std::vector<rr_shift_record> registerTranslation(const std::vector<ImagePtr>& images, const Image& real, int width, float pixel_size, int max_shift,
+                                                     bool bilinear = true, std::vector<double>* correction = nullptr)
+    {
+        std::vector<rr_shift_record> out;
+        if (images.empty() || !push()) return out;
+        const size_t npx = (size_t)m_cfg.n_cells * m_n_angles;
+        bool ok = real.height == (uint32_t)m_cfg.n_cells && real.width == (uint32_t)m_n_angles && real.data.size() == npx;
+        for (const ImagePtr& im : images) ok = ok && im && im->height == real.height && im->width == real.width && im->data.size() == npx;
+        if (!ok) { m_err = "registerTranslation: every image must be n_cells x n_angles mono8"; std::cout << "[RadarHIP] " << m_err << std::endl; return out; }
+        if (!marshal::register_translation(m_ctx, images.size(), npx, [&](size_t k) { return images[k]->data.data(); }, real.data.data(),
+                                           width, pixel_size, max_shift, bilinear, out, correction)) {
+            fail(); out.clear();
+        }
+        return out;
+    }
     const std::string& lastError() const { return m_err; }
     // radar_tools/radar_img_to_pcl (launch/tests/radar_sim_test.launch:80-84, outside the checkout) on the GPU: one mono8
     // polar image of this model's shape (simulated or real) -> its detections, a PointCloud's points plus the intensity

@@ -161,4 +161,31 @@ bool align_images(rr_ctx* ctx, size_t n, size_t npx, size_t n_angles, PixelsOf i
     return rr_align_images(ctx, flat.data(), (int)n, real, cell_begin, cell_end, out.data(), curve ? curve->data() : nullptr) == 0;
 }
 
+// the same images and the real one made Cartesian (rr_polar_to_cartesian: width x width, pixel_size m/pixel) and registered over
+// -max_shift..max_shift pixels (rr_shift_images): one record per image, and with `correction` the amount to add to each image's
+// pose in the sensor's own axes, metres [n][2] = (forward, left) = ((dy + sub_dy), (dx + sub_dx)) * pixel_size.  false: rr_last_error(ctx)
+template <typename PixelsOf>
+bool register_translation(rr_ctx* ctx, size_t n, size_t npx, PixelsOf image_pixels, const uint8_t* real, int width, float pixel_size, int max_shift,
+                          bool bilinear, std::vector<rr_shift_record>& out, std::vector<double>* correction)
+{
+    std::vector<uint8_t> flat((n + 1) * npx);           // the real image rides behind the others: one conversion
+    for (size_t k = 0; k < n; k++) std::copy(image_pixels(k), image_pixels(k) + npx, flat.begin() + (std::ptrdiff_t)(k * npx));
+    std::copy(real, real + npx, flat.begin() + (std::ptrdiff_t)(n * npx));
+    rr_cartesian_config cc{};
+    cc.width = width; cc.interpolation = bilinear ? 1 : 0; cc.pixel_size = pixel_size;
+    const size_t ncart = width > 0 ? (size_t)width * (size_t)width : 0;
+    std::vector<uint8_t> cart((n + 1) * ncart);
+    out.assign(n, rr_shift_record{});
+    if (rr_polar_to_cartesian(ctx, flat.data(), (int)(n + 1), &cc, cart.data()) != 0) return false;
+    if (rr_shift_images(ctx, cart.data(), (int)n, cart.data() + n * ncart, width, width, max_shift, out.data(), nullptr, nullptr) != 0) return false;
+    if (correction) {
+        correction->assign(2 * n, 0.0);
+        for (size_t k = 0; k < n; k++) {
+            (*correction)[2 * k] = ((double)out[k].dy + out[k].sub_dy) * (double)pixel_size;
+            (*correction)[2 * k + 1] = ((double)out[k].dx + out[k].sub_dx) * (double)pixel_size;
+        }
+    }
+    return true;
+}
+
 }  // namespace radarays_ros_amd::marshal

@@ -180,6 +180,10 @@ struct rr_ctx {
     DevBuf<uint32_t> d_conv_hist;      // ... and of rr_compare_images: one chunk's joint histograms on their way to the host
     // rr_align_images_device: one chunk's curves (when the caller gives no buffer) and sums, the records; and the host forms' curves
     DevBuf<long long> d_align_curve, d_conv_curve; DevBuf<unsigned long long> d_align_sums; DevBuf<rr_align_record> d_align_rec;
+    // rr_shift_images_device: one chunk's surface (when the caller gives no buffer) and sums, the reference's column and box sums, the
+    // records; and the host forms' own staging: images [chunk][H][W] (d_conv_in is sized for polar images), the reference, the surfaces
+    DevBuf<long long> d_shift_surf, d_shift_conv_xcorr; DevBuf<unsigned long long> d_shift_sums, d_shift_col, d_shift_box, d_shift_conv_sse;
+    DevBuf<rr_shift_record> d_shift_rec; DevBuf<uint8_t> d_shift_in, d_shift_ref;
     void* h_rb = nullptr; size_t h_rb_bytes = 0;         // page-locked: read_back()
     void* h_frame = nullptr; size_t h_frame_bytes = 0;   // page-locked: error bits + per-pass counters of rr_simulate's frame
 

@@ -1,5 +1,5 @@
 // rr_images.hip -- the C ABI's image entry points: images in, records / points / images out.  PSNR scores and metrics against a reference image
-// (rr_metrics.hip), azimuth registration (rr_align.hip), point clouds and Cartesian images (rr_detect.hip): each in a device form, which runs on the
+// (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), point clouds and Cartesian images (rr_detect.hip): each in a device form, which runs on the
 // caller's buffers and stream, and a host form, which stages through the context's own buffers on c->stream.
 #include "rr_ctx.h"
 #include <algorithm>
@@ -41,6 +41,21 @@ int check_align(rr_ctx* c, const char* who, const void* imgs, int n_images, int 
                                std::to_string(c->cfg.n_cells));
     if ((long long)(cell_end - cell_begin) * c->cfg.n_angles > (1ll << 23))
         return fail(c, -3, w + ": a window of more than 2^23 pixels");
+    return 0;
+}
+
+// the refusals of rr_shift_images_device / rr_shift_images / rr_simulate_batch_shift: no config is needed, the shape comes with the call
+int check_shift(rr_ctx* c, const char* who, const void* imgs, int n_images, int n_max, const void* ref, int H, int W, int S, const void* out)
+{
+    if (!c) return -1;
+    const std::string w(who);
+    if (!(imgs && ref && out)) return fail(c, -3, w + ": null buffer");
+    if (n_images < 1 || n_images > n_max) return fail(c, -3, w + ": n_images must be 1.." + std::to_string(n_max));
+    if (H < 1 || H > 8192 || W < 1 || W > 8192) return fail(c, -3, w + ": height and width must be 1..8192");
+    if (S < 0 || S > 64) return fail(c, -3, w + ": max_shift must be 0..64");
+    if (H <= 2 * S || W <= 2 * S)
+        return fail(c, -3, w + ": the image (" + std::to_string(H) + " x " + std::to_string(W) + ") leaves no template window at max_shift " + std::to_string(S));
+    if ((long long)(H - 2 * S) * (W - 2 * S) > (1ll << 23)) return fail(c, -3, w + ": a template window of more than 2^23 pixels");
     return 0;
 }
 
@@ -301,6 +316,118 @@ int rr_simulate_batch_align(rr_ctx* c, const float* poses, int n_frames, const u
     rc = report_frame_errors(c); if (rc) return rc;     // before anything is handed out
     if (out_imgs_u8) RR_HIP(c, hipMemcpy(out_imgs_u8, c->d_param_imgs.p, n * npx, hipMemcpyDeviceToHost));
     if (xcorr) RR_HIP(c, hipMemcpy(xcorr, c->d_conv_curve.p, n * A * sizeof(int64_t), hipMemcpyDeviceToHost));
+    std::copy(rec.begin(), rec.end(), out);
+    return 0;
+}
+
+// ---- translation registration: the 2-D cross-correlation over a window of pixel shifts (rr_shift.hip) ----------------
+
+int rr_shift_images_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_images, const uint8_t* d_ref_u8, int height, int width, int max_shift,
+                           rr_shift_record* out, int64_t* d_xcorr, uint64_t* d_sse, void* stream)
+{
+    int rc = check_shift(c, "rr_shift_images_device", d_imgs_u8, n_images, 65535, d_ref_u8, height, width, max_shift, out); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = stream_of(c, stream);
+    const int H = height, W = width, S = max_shift, D = 2 * S + 1;
+    const size_t npx = (size_t)H * W, n = (size_t)n_images, ND = (size_t)D * D, n_col = 2 * (size_t)D * W;
+    const size_t chunk = std::min(n, kChunk);
+    static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(unsigned long long) == sizeof(uint64_t), "surface words");
+    if ((!d_xcorr && c->d_shift_surf.n < chunk * ND) || c->d_shift_sums.n < 2 * chunk || c->d_shift_col.n < n_col || c->d_shift_box.n < 2 * ND ||
+        c->d_shift_rec.n < n) {
+        RR_HIP(c, hipStreamSynchronize(s));             // an earlier call's kernels may still read what is freed here
+        if (!d_xcorr) RR_HIP(c, c->d_shift_surf.ensure(chunk * ND));
+        RR_HIP(c, c->d_shift_sums.ensure(2 * chunk));
+        RR_HIP(c, c->d_shift_col.ensure(n_col));
+        RR_HIP(c, c->d_shift_box.ensure(2 * ND));
+        RR_HIP(c, c->d_shift_rec.ensure(n));
+    }
+    launch_shift_box(d_ref_u8, H, W, S, c->d_shift_col.p, c->d_shift_box.p, s);      // once per call: every image meets the same reference
+    for (size_t at = 0; at < n; at += kChunk) {
+        const int m = (int)std::min(kChunk, n - at);
+        const uint8_t* imgs = d_imgs_u8 + at * npx;
+        long long* surf = d_xcorr ? reinterpret_cast<long long*>(d_xcorr) + at * ND : c->d_shift_surf.p;
+        unsigned long long* sse = d_sse ? reinterpret_cast<unsigned long long*>(d_sse) + at * ND : nullptr;
+        RR_HIP(c, hipMemsetAsync(surf, 0, (size_t)m * ND * sizeof(long long), s));
+        RR_HIP(c, hipMemsetAsync(c->d_shift_sums.p, 0, 2 * (size_t)m * sizeof(unsigned long long), s));
+        launch_shift_sums(imgs, H, W, S, m, c->d_shift_sums.p, s);
+        launch_shift_gram(imgs, d_ref_u8, H, W, S, m, surf, s);
+        launch_shift_finish(surf, sse, c->d_shift_sums.p, c->d_shift_box.p, H, W, S, m, c->d_shift_rec.p + at, s);
+    }
+    std::vector<rr_shift_record> rec(n);
+    rc = records_back(c, rec.data(), c->d_shift_rec.p, n * sizeof(rr_shift_record), s); if (rc) return rc;
+    const size_t n_win = (size_t)(H - 2 * S) * (W - 2 * S);
+    // the sub-pixel offset along one axis from the exact SSE before, at and after the best shift (each below 2^39)
+    auto sub = [](uint64_t before, uint64_t at_best, uint64_t after) {
+        if (before == UINT64_MAX || after == UINT64_MAX) return 0.0;
+        const int64_t num = (int64_t)before - (int64_t)after, den = (int64_t)before - 2 * (int64_t)at_best + (int64_t)after;
+        return den <= 0 ? 0.0 : 0.5 * (double)num / (double)den;
+    };
+    for (size_t k = 0; k < n; k++) {
+        rr_shift_record& r = rec[k];
+        r.psnr = psnr_of(r.sse, n_win);                 // the host's log10, as rr_score_images_device
+        r.sub_dy = sub(r.sse_nb[0], r.sse, r.sse_nb[1]);
+        r.sub_dx = sub(r.sse_nb[2], r.sse, r.sse_nb[3]);
+        out[k] = r;
+    }
+    return 0;
+}
+
+int rr_shift_images(rr_ctx* c, const uint8_t* imgs_u8, int n_images, const uint8_t* ref_u8, int height, int width, int max_shift,
+                    rr_shift_record* out, int64_t* xcorr, uint64_t* sse)
+{
+    int rc = check_shift(c, "rr_shift_images", imgs_u8, n_images, 65535, ref_u8, height, width, max_shift, out); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)n_images, npx = (size_t)height * width, D = 2 * (size_t)max_shift + 1, ND = D * D, chunk = std::min(n, kChunk);
+    RR_HIP(c, hipStreamSynchronize(c->stream));        // the staging buffers may be reallocated
+    RR_HIP(c, c->d_shift_in.ensure(chunk * npx));
+    RR_HIP(c, c->d_shift_ref.ensure(npx));
+    if (xcorr) RR_HIP(c, c->d_shift_conv_xcorr.ensure(chunk * ND));
+    if (sse) RR_HIP(c, c->d_shift_conv_sse.ensure(chunk * ND));
+    RR_HIP(c, hipMemcpyAsync(c->d_shift_ref.p, ref_u8, npx, hipMemcpyHostToDevice, c->stream));
+    std::vector<rr_shift_record> rec(n);
+    for (size_t at = 0; at < n; at += kChunk) {
+        const size_t m = std::min(kChunk, n - at);
+        RR_HIP(c, hipMemcpyAsync(c->d_shift_in.p, imgs_u8 + at * npx, m * npx, hipMemcpyHostToDevice, c->stream));
+        rc = rr_shift_images_device(c, c->d_shift_in.p, (int)m, c->d_shift_ref.p, height, width, max_shift, rec.data() + at,
+                                    xcorr ? reinterpret_cast<int64_t*>(c->d_shift_conv_xcorr.p) : nullptr,
+                                    sse ? reinterpret_cast<uint64_t*>(c->d_shift_conv_sse.p) : nullptr, c->stream); if (rc) return rc;
+        if (xcorr) RR_HIP(c, hipMemcpy(xcorr + at * ND, c->d_shift_conv_xcorr.p, m * ND * sizeof(int64_t), hipMemcpyDeviceToHost));
+        if (sse) RR_HIP(c, hipMemcpy(sse + at * ND, c->d_shift_conv_sse.p, m * ND * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    }
+    std::copy(rec.begin(), rec.end(), out);
+    return 0;
+}
+
+int rr_simulate_batch_shift(rr_ctx* c, const float* poses, int n_frames, const uint8_t* ref_polar_u8, const rr_cartesian_config* cfg,
+                            int max_shift, uint8_t* out_cart_u8, rr_shift_record* out, int64_t* xcorr)
+{
+    // refused before anything is simulated (the context stands in for the images: they are its own)
+    int rc = check_cartesian(c, "rr_simulate_batch_shift", ref_polar_u8, 1, cfg, out); if (rc) return rc;
+    rc = check_shift(c, "rr_simulate_batch_shift", c, n_frames, RR_MAX_BATCH, ref_polar_u8, cfg->width, cfg->width, max_shift, out); if (rc) return rc;
+    rc = check_ready(c); if (rc) return rc;
+    if (!poses) return fail(c, -3, "rr_simulate_batch_shift: null poses");
+    RR_HIP(c, hipSetDevice(c->device));
+    const rr_config& g = c->cfg;
+    const size_t npx = (size_t)g.n_cells * g.n_angles, n = (size_t)n_frames, ncart = (size_t)cfg->width * cfg->width;
+    const size_t D = 2 * (size_t)max_shift + 1, ND = D * D;
+    RR_HIP(c, hipStreamSynchronize(c->stream));        // the buffers may be reallocated below
+    RR_HIP(c, c->d_param_imgs.ensure(n * npx));
+    RR_HIP(c, c->d_ref_img.ensure(npx));
+    RR_HIP(c, c->d_shift_in.ensure(n * ncart));
+    RR_HIP(c, c->d_shift_ref.ensure(ncart));
+    if (xcorr) RR_HIP(c, c->d_shift_conv_xcorr.ensure(n * ND));
+    RR_HIP(c, hipMemcpyAsync(c->d_ref_img.p, ref_polar_u8, npx, hipMemcpyHostToDevice, c->stream));
+    rc = rr_simulate_batch_device(c, poses, n_frames, c->d_param_imgs.p, c->stream); if (rc) return rc;
+    launch_cartesian(c->d_param_imgs.p, n_frames, *cfg, g.n_cells, g.n_angles, g.scroll_image, g.theta_min, g.theta_inc, (float)g.resolution,
+                     c->d_shift_in.p, c->stream);
+    launch_cartesian(c->d_ref_img.p, 1, *cfg, g.n_cells, g.n_angles, g.scroll_image, g.theta_min, g.theta_inc, (float)g.resolution,
+                     c->d_shift_ref.p, c->stream);
+    std::vector<rr_shift_record> rec(n);
+    rc = rr_shift_images_device(c, c->d_shift_in.p, n_frames, c->d_shift_ref.p, cfg->width, cfg->width, max_shift, rec.data(),
+                                xcorr ? reinterpret_cast<int64_t*>(c->d_shift_conv_xcorr.p) : nullptr, nullptr, c->stream); if (rc) return rc;   // synchronises the stream
+    rc = report_frame_errors(c); if (rc) return rc;     // before anything is handed out
+    if (out_cart_u8) RR_HIP(c, hipMemcpy(out_cart_u8, c->d_shift_in.p, n * ncart, hipMemcpyDeviceToHost));
+    if (xcorr) RR_HIP(c, hipMemcpy(xcorr, c->d_shift_conv_xcorr.p, n * ND * sizeof(int64_t), hipMemcpyDeviceToHost));
     std::copy(rec.begin(), rec.end(), out);
     return 0;
 }

@@ -1,4 +1,4 @@
-// rr_launch.h -- every launcher of rr_kernels.hip, rr_refit.hip, rr_detect.hip, rr_metrics.hip, rr_align.hip and rr_lbvh.hip, declared ONCE: included where they
+// rr_launch.h -- every launcher of rr_kernels.hip, rr_refit.hip, rr_detect.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip and rr_lbvh.hip, declared ONCE: included where they
 // are defined (a definition that drifts from its declaration fails there) and where they are called.  Default arguments live here only.
 #pragma once
 #include "../../include/radarays_mi355.h"
@@ -55,6 +55,13 @@ void launch_align_gram(const uint8_t* imgs, const uint8_t* ref, int n_cells, int
                        long long* curve, hipStream_t s);
 void launch_align_finish(long long* curve, const unsigned long long* sums, int n_images, int n_angles, int cell_begin, int cell_end,
                          rr_align_record* out, hipStream_t s);
+// rr_shift.hip (translation registration).  col [2S+1][W][2] and box [2S+1][2S+1][2] are written whole; sums [n_images][2] and surf
+// [n_images][2S+1][2S+1] must be zero before their launches; sse [n_images][2S+1][2S+1] or null
+void launch_shift_box(const uint8_t* ref, int H, int W, int S, unsigned long long* col, unsigned long long* box, hipStream_t s);
+void launch_shift_sums(const uint8_t* imgs, int H, int W, int S, int n_images, unsigned long long* sums, hipStream_t s);
+void launch_shift_gram(const uint8_t* imgs, const uint8_t* ref, int H, int W, int S, int n_images, long long* surf, hipStream_t s);
+void launch_shift_finish(long long* surf, unsigned long long* sse, const unsigned long long* sums, const unsigned long long* box, int H, int W,
+                         int S, int n_images, rr_shift_record* out, hipStream_t s);
 void launch_copy_host(const void* src, void* dst, size_t bytes, int blocks, int xcd, hipStream_t s);
 void launch_copy_words(const void* src, void* dst, size_t bytes, hipStream_t s);
 void launch_debug_brdf(size_t n, const float* in, int model, float* out, hipStream_t s);

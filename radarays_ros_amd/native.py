@@ -33,6 +33,7 @@ SYMBOLS = [
     "rr_default_detect_config", "rr_detect_device", "rr_detect", "rr_polar_to_cartesian_device", "rr_polar_to_cartesian",
     "rr_compare_images_device", "rr_compare_images", "rr_simulate_param_sets_metrics",
     "rr_align_images_device", "rr_align_images", "rr_simulate_batch_align",
+    "rr_shift_images_device", "rr_shift_images", "rr_simulate_batch_shift",
 ]
 
 
@@ -114,6 +115,18 @@ class RRAlignRecord(C.Structure):
 
 # rr_align_record as numpy sees it (72 B)
 ALIGN_DTYPE = np.dtype([("shift", "<i4"), ("n_best", "<i4"), ("xcorr", "<i8"), ("sse", "<u8"), ("psnr", "<f8"), ("ncc", "<f8"),
+                        ("sum_x", "<u8"), ("sum_xx", "<u8"), ("sum_r", "<u8"), ("sum_rr", "<u8")])
+
+
+class RRShiftRecord(C.Structure):
+    _fields_ = [("dy", C.c_int32), ("dx", C.c_int32), ("n_best", C.c_int32), ("reserved_", C.c_int32), ("xcorr", C.c_int64),
+                ("sse", C.c_uint64), ("psnr", C.c_double), ("ncc", C.c_double), ("sub_dy", C.c_double), ("sub_dx", C.c_double),
+                ("sse_nb", C.c_uint64 * 4), ("sum_x", C.c_uint64), ("sum_xx", C.c_uint64), ("sum_r", C.c_uint64), ("sum_rr", C.c_uint64)]
+
+
+# rr_shift_record as numpy sees it (128 B)
+SHIFT_DTYPE = np.dtype([("dy", "<i4"), ("dx", "<i4"), ("n_best", "<i4"), ("reserved_", "<i4"), ("xcorr", "<i8"), ("sse", "<u8"),
+                        ("psnr", "<f8"), ("ncc", "<f8"), ("sub_dy", "<f8"), ("sub_dx", "<f8"), ("sse_nb", "<u8", (4,)),
                         ("sum_x", "<u8"), ("sum_xx", "<u8"), ("sum_r", "<u8"), ("sum_rr", "<u8")])
 
 
@@ -320,6 +333,9 @@ def lib():
     L.rr_align_images_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp]
     L.rr_align_images.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]
     L.rr_simulate_batch_align.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp]
+    L.rr_shift_images_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.rr_shift_images.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    L.rr_simulate_batch_shift.argtypes = [vp, vp, C.c_int, vp, C.POINTER(RRCartesianConfig), C.c_int, vp, vp, vp]
     for n in SYMBOLS:
         getattr(L, n)
     _LIB = L
@@ -446,6 +462,17 @@ def cartesian_config(width, pixel_size, bilinear=True):
     c.pixel_size = ps
     c.interpolation = 1 if bilinear else 0
     return c
+
+
+def shift_window(height, width, max_shift):
+    """(H, W, S) of a translation registration, range-checked before any call into the library: H, W in 1..8192, S in 0..64,
+    a template window (H - 2S) x (W - 2S) of 1..2^23 pixels"""
+    h, w, s = _int_in(height, 1, 8192, "height"), _int_in(width, 1, 8192, "width"), _int_in(max_shift, 0, 64, "max_shift")
+    if h <= 2 * s or w <= 2 * s:
+        raise ValueError("a %d x %d image leaves no template window at max_shift %d" % (h, w, s))
+    if (h - 2 * s) * (w - 2 * s) > 1 << 23:
+        raise ValueError("the template window %d x %d holds more than 2^23 pixels" % (h - 2 * s, w - 2 * s))
+    return h, w, s
 
 
 def _frames_arg(n_frames):
@@ -789,6 +816,60 @@ class Context:
                                                  None if out is None else out.ctypes.data, rec.ctypes.data,
                                                  None if curve is None else curve.ctypes.data))
         return out, rec, curve
+
+    # ---- translation registration (rr_shift.hip): the 2-D cross-correlation of images [H][W] with one reference over -S..S pixels
+    def shift_images_device(self, d_imgs_ptr, n_images, d_ref_ptr, height, width, max_shift, d_xcorr_ptr=None, d_sse_ptr=None, stream=None):
+        """rr_shift_images_device: n images [n][H][W] and one reference image in HBM -> SHIFT_DTYPE array [n] (the best shift and
+        the scores at it); d_xcorr_ptr (int64) and d_sse_ptr (uint64), HBM [n][2S+1][2S+1], receive the surfaces.  Synchronous
+        on `stream`.  Needs no config."""
+        h, w, s = shift_window(height, width, max_shift)
+        n = _frames_arg(n_images)
+        if not d_imgs_ptr or not d_ref_ptr:
+            raise ValueError("shift_images_device needs image and reference buffers")
+        rec = np.zeros(n, SHIFT_DTYPE)
+        self._ck(self._L.rr_shift_images_device(self._h, d_imgs_ptr, n, d_ref_ptr, h, w, s, rec.ctypes.data, d_xcorr_ptr, d_sse_ptr, stream))
+        return rec
+
+    def shift_images(self, imgs, ref, max_shift, want_surfaces=False):
+        """rr_shift_images on host images uint8 [n][H][W] (or one image) against ref [H][W] -> SHIFT_DTYPE array [n], and with
+        want_surfaces (records, xcorr int64 [n][2S+1][2S+1], sse uint64 [n][2S+1][2S+1])"""
+        x, r = np.asarray(imgs), np.asarray(ref)
+        if x.dtype != np.uint8 or r.dtype != np.uint8:
+            raise ValueError("images must be uint8, got %s and %s" % (x.dtype, r.dtype))
+        if x.ndim == 2:
+            x = x[None]
+        if x.ndim != 3 or r.ndim != 2 or x.shape[1:] != r.shape or not 1 <= x.shape[0] <= 65535:
+            raise ValueError("images [n][H][W] (n in 1..65535) and one reference [H][W] of the same shape, got %s and %s" % (np.asarray(imgs).shape, r.shape))
+        h, w, s = shift_window(r.shape[0], r.shape[1], max_shift)
+        x, r = np.ascontiguousarray(x), np.ascontiguousarray(r)
+        d = 2 * s + 1
+        rec = np.zeros(len(x), SHIFT_DTYPE)
+        xc = np.zeros((len(x), d, d), np.int64) if want_surfaces else None
+        sse = np.zeros((len(x), d, d), np.uint64) if want_surfaces else None
+        self._ck(self._L.rr_shift_images(self._h, x.ctypes.data, len(x), r.ctypes.data, h, w, s, rec.ctypes.data,
+                                         None if xc is None else xc.ctypes.data, None if sse is None else sse.ctypes.data))
+        return (rec, xc, sse) if want_surfaces else rec
+
+    def simulate_batch_shift(self, poses, ref_polar, width, pixel_size, max_shift, bilinear=True, want_images=False, want_xcorr=False):
+        """rr_simulate_batch_shift: up to 64 poses simulated, their images and ref_polar [n_cells][n_angles] made Cartesian
+        (width x width, pixel_size m/pixel) and registered over -S..S pixels -> (Cartesian images uint8 [n][width][width] or
+        None, SHIFT_DTYPE array [n], xcorr int64 [n][2S+1][2S+1] or None)"""
+        r = self._polar_images(ref_polar)
+        if len(r) != 1:
+            raise ValueError("one reference image, got %d" % len(r))
+        c = cartesian_config(width, pixel_size, bilinear)
+        _, _, s = shift_window(c.width, c.width, max_shift)
+        p = _rows(poses, 7, "poses")
+        if not 1 <= len(p) <= 64:
+            raise ValueError("1..64 poses, got %d" % len(p))
+        d = 2 * s + 1
+        out = np.zeros((len(p), c.width, c.width), np.uint8) if want_images else None
+        rec = np.zeros(len(p), SHIFT_DTYPE)
+        xc = np.zeros((len(p), d, d), np.int64) if want_xcorr else None
+        self._ck(self._L.rr_simulate_batch_shift(self._h, p.ctypes.data, len(p), r.ctypes.data, C.byref(c), s,
+                                                 None if out is None else out.ctypes.data, rec.ctypes.data,
+                                                 None if xc is None else xc.ctypes.data))
+        return out, rec, xc
 
     def simulate_device(self, pose, d_img_ptr, stream=None):
         p = np.ascontiguousarray(pose, np.float32)

@@ -201,6 +201,52 @@ class RadarHIP:
             images = [images]
         return self._ctx.align_images(np.stack([self._polar(im) for im in images]), self._polar(real), cell_begin, cell_end, want_curve)
 
+    # ---- translation registration (rr_shift.hip): x and y of a planar pose from the Cartesian images
+    def registerTranslation(self, images, real, width, pixel_size, max_shift, bilinear=True):
+        """mono8 polar Images (or arrays; one or a list, this model's shape) and ONE real image, all made Cartesian (width x width,
+        pixel_size m/pixel) and compared over -max_shift..max_shift pixels -> (a native.SHIFT_DTYPE array with one record per
+        image: (dy, dx) where the image's content is found in `real`, and xcorr, sse, psnr, ncc there; the correction to add to
+        each image's pose in the sensor's own axes, metres [n][2] = (forward, left) = (dy + sub_dy, dx + sub_dx) * pixel_size)"""
+        self._push()
+        if isinstance(images, Image) or (isinstance(images, np.ndarray) and images.ndim == 2):
+            images = [images]
+        polar = np.stack([self._polar(im) for im in images] + [self._polar(real)])       # the real image rides behind: one conversion
+        cart = self._ctx.polar_to_cartesian(polar, width, pixel_size, bilinear)
+        rec = self._ctx.shift_images(cart[:-1], cart[-1], max_shift)
+        return rec, self._translation(rec, pixel_size)
+
+    @staticmethod
+    def _translation(rec, pixel_size):
+        return np.stack([(rec["dy"] + rec["sub_dy"]) * pixel_size, (rec["dx"] + rec["sub_dx"]) * pixel_size], axis=1)
+
+    def registerPose(self, poses, real, width, pixel_size, max_shift, bilinear=True, cell_begin=0, cell_end=None):
+        """[n][7] simulated poses (qx qy qz qw tx ty tz) of a planar sensor against ONE real polar image -> (corrected poses
+        float32 [n][7], the native.ALIGN_DTYPE records of the yaw step, the native.SHIFT_DTYPE records of the translation step).
+        Per 64 poses: simulate_batch_align gives each pose's azimuth shift s, a turn of -s * theta_inc about the sensor's z axis;
+        the turned poses are simulated again and simulate_batch_shift gives their translation in the sensor's own axes."""
+        self._push()
+        p = np.array(poses, np.float32).reshape(-1, 7)
+        real = self._polar(real)
+        theta_inc = float(self._ctx._rrcfg.theta_inc)
+        out, yaw_recs, shift_recs = [], [], []
+        for at in range(0, len(p), 64):
+            chunk = p[at:at + 64].astype(np.float64)
+            _, yaw, _ = self._ctx.simulate_batch_align(chunk, real, cell_begin, cell_end)
+            s = yaw["shift"].astype(np.int64)
+            s = np.where(2 * s > N_ANGLES, s - N_ANGLES, s)           # x was rendered s azimuth steps ahead of `real`
+            half = -0.5 * s * theta_inc
+            bz, bw = np.sin(half), np.cos(half)                       # q * (0, 0, bz, bw): a turn in the sensor's own frame
+            ax, ay, az, aw = chunk[:, 0].copy(), chunk[:, 1].copy(), chunk[:, 2].copy(), chunk[:, 3].copy()
+            chunk[:, 0], chunk[:, 1] = ax * bw + ay * bz, ay * bw - ax * bz
+            chunk[:, 2], chunk[:, 3] = aw * bz + az * bw, aw * bw - az * bz
+            _, sh, _ = self._ctx.simulate_batch_shift(chunk, real, width, pixel_size, max_shift, bilinear)
+            v = np.concatenate([self._translation(sh, pixel_size), np.zeros((len(chunk), 1))], axis=1)
+            u, w = chunk[:, :3], chunk[:, 3:4]
+            uv = np.cross(u, v)
+            chunk[:, 4:7] += v + 2.0 * (w * uv + np.cross(u, uv))     # the correction turned into the map frame
+            out.append(chunk.astype(np.float32)); yaw_recs.append(yaw); shift_recs.append(sh)
+        return np.concatenate(out), np.concatenate(yaw_recs), np.concatenate(shift_recs)
+
     def _push(self):
         if self._dirty_cfg:
             cfg = self.m_cfg.copy(n_reflections=self.m_params.model.n_reflections)
