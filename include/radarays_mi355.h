@@ -647,6 +647,71 @@ int rr_shift_images(rr_ctx* ctx, const uint8_t* imgs_u8, int n_images, const uin
 int rr_simulate_batch_shift(rr_ctx* ctx, const float* poses, int n_frames, const uint8_t* ref_polar_u8, const rr_cartesian_config* cfg,
                             int max_shift, uint8_t* out_cart_u8, rr_shift_record* out, int64_t* xcorr);
 
+/* ---- place recognition: polar ring/sector descriptors and exact matching (rr_place.hip) ------------------------------
+ * rr_align_images and rr_shift_images refine a pose that is already close.  "Where on this map was this scan taken" is
+ * answered by a database: render the map once on a grid of poses, keep a compact signature of every rendered scan, look a
+ * real scan up in it.  The reference has no such step: the definitions below are the build's own, unpinned by anything
+ * the reference holds.
+ * Descriptor.  rr_place_config {cell_begin, cell_end, n_rings = R, n_sectors = S}; L = cell_end - cell_begin, A = n_angles.
+ *   ring r   = the cells [cell_begin + floor(r L / R), cell_begin + floor((r+1) L / R))
+ *   sector j = the image columns [floor(j A / S), floor((j+1) A / S)), as they lie in the image: scroll_image is not undone,
+ *              a shift of the match takes care of it
+ *   d[r][j]  = floor(sum of the pixels of the rectangle / pixel count of the rectangle): the sum is an exact integer, the
+ *              result a uint8
+ * Layout uint8 [R][S]: a descriptor is itself a tiny polar image of K = R S bytes.
+ * Limits: 1 <= R <= 64, 4 <= S <= 128, S <= A, R <= L, R S <= 8192, 0 <= cell_begin < cell_end <= n_cells.
+ * Match.  The definition of rr_align_images on descriptors, n_query queries against n_db candidates.  For query q and
+ * candidate c, both [R][S]:
+ *   xcorr[s] = sum_r sum_j q[r][j] c[r][(j+s) mod S] = sum(np.roll(q, s, axis=1) * c)              exact
+ *              s is the number of sectors to ADD to the query's scroll so that it lines up with the candidate, the direction
+ *              of rr_align_images
+ *   sse[s]   = Sqq + Scc - 2 xcorr[s]                                    exact, fits 32 bits: 2 * 255^2 * 8192 < 2^31
+ *   best     = the smallest s with the largest xcorr; n_best = the number of shifts that attain it
+ *   ncc      = (K xcorr - Sq Sc) / sqrt((K Sqq - Sq^2)(K Scc - Sc^2)) at the best shift: numerator and factors exact int64,
+ *              converted to f64, then one multiply, one sqrt, one divide; 0 when either factor is 0
+ *   psnr     = from sse over K pixels with the expression of rr_score_images_device (+inf at sse == 0)
+ * Ranking.  Candidates are ranked by the exact 64-bit key (sse at the best shift) << 32 | candidate index, ascending: equal
+ * SSE goes to the lower index, duplicates in the database are legal.  The call returns the top_k smallest,
+ * 1 <= top_k <= min(32, n_db), as records [n_query][top_k] on the host.  Ranking uses integers only.  Ranking by NCC is
+ * deliberately not offered: a caller for whom gain differences between real and simulated images matter re-ranks the top_k
+ * by the returned ncc.
+ * d_sse (HBM, uint32 [n_query][n_db], or NULL) receives every pair's SSE at its best shift, d_shift (HBM, uint16
+ * [n_query][n_db], or NULL; only together with d_sse) that shift.
+ * Limits: 1 <= n_query <= 64, 1 <= n_db <= 2^28.  Synchronous on `stream`, context-owned scratch, one call per context at
+ * a time: the conventions of rr_align_images_device.  The database may start at any byte.
+ * Refused with a message and nothing written: -2 without a config where one is needed (the describe calls), -3 for a null
+ * buffer, an argument outside these limits, top_k > n_db, d_shift without d_sse.
+ * Pose meaning.  The shift moves the QUERY's sectors: by the rule of rr_align_images the query's pose turned by
+ * -s (A / S) theta_inc about the sensor's z axis is the candidate's, and the candidate's pose turned by +s (A / S) theta_inc
+ * is the query's (s wrapped into (-S/2, S/2]).  Exact only when S divides A: otherwise sector widths differ by one column. */
+typedef struct rr_place_config {
+    int32_t cell_begin, cell_end;   /* the window of cells the rings divide */
+    int32_t n_rings, n_sectors;     /* R, S */
+} rr_place_config;
+typedef struct rr_place_match {   /* 40 B, no padding */
+    uint32_t index;           /* the candidate */
+    int32_t shift;            /* sectors to add to the query's scroll */
+    uint32_t sse;             /* at `shift` */
+    uint32_t n_best;          /* shifts that attain the largest xcorr */
+    int64_t xcorr;            /* at `shift` */
+    double ncc, psnr;         /* at `shift` */
+} rr_place_match;
+/* n images [n][n_cells][n_angles] in HBM -> descriptors [n][R][S] in HBM; enqueued on `stream`, not synchronised.  Needs a
+ * config (the image shape) and no mesh.  n is 1..65535. */
+int rr_describe_images_device(rr_ctx* ctx, const uint8_t* d_imgs_u8, int n, const rr_place_config* cfg, uint8_t* d_desc, void* stream);
+/* The host-buffer form, staged 64 images at a time; synchronous. */
+int rr_describe_images(rr_ctx* ctx, const uint8_t* imgs_u8, int n, const rr_place_config* cfg, uint8_t* desc);
+/* rr_simulate_batch_device into a context-owned image buffer, then rr_describe_images_device: n_frames (1..RR_MAX_BATCH)
+ * poses in, out_desc (host, [n_frames][R][S]) out.  R S bytes per pose leave the GPU instead of an image. */
+int rr_simulate_batch_describe(rr_ctx* ctx, const float* poses, int n_frames, const rr_place_config* cfg, uint8_t* out_desc);
+/* d_query [n_query][R][S] and d_db [n_db][R][S] in HBM -> out (host, [n_query][top_k]).  Needs neither a config nor a mesh. */
+int rr_match_descriptors_device(rr_ctx* ctx, const uint8_t* d_query, int n_query, const uint8_t* d_db, int n_db, int n_rings, int n_sectors,
+                                int top_k, rr_place_match* out /* host [n_query][top_k] */, uint32_t* d_sse /* HBM [n_query][n_db], or NULL */,
+                                uint16_t* d_shift /* HBM [n_query][n_db], or NULL */, void* stream);
+/* The host-buffer form: the database is staged in chunks and a running top_k kept; sse and shift host [n_query][n_db] or NULL. */
+int rr_match_descriptors(rr_ctx* ctx, const uint8_t* query, int n_query, const uint8_t* db, int n_db, int n_rings, int n_sectors, int top_k,
+                         rr_place_match* out, uint32_t* sse, uint16_t* shift);
+
 /* ---- several GPUs of one node behind one object (SURVEY.md §8b "Threading", §8e) -------------------------
  * The reference creates ONE backend object per process (src/radar_simulator.cpp:145-176) and fans out inside it
  * (OpenMP over azimuths, RadarCPU.cpp:155).  rr_multi is that object for n GPUs: one rr_ctx per device, mesh and

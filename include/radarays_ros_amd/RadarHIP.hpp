@@ -286,6 +286,37 @@ public:
         }
         return out;
     }
+    // Place recognition (rr_place_config, rr_place_match, include/radarays_mi355.h): the images' ring/sector descriptors,
+    // [n][n_rings][n_sectors] bytes; a yaw of the sensor is a circular shift of a descriptor's sectors.  Empty on error.
+    std::vector<uint8_t> describeImages(const std::vector<ImagePtr>& images, const rr_place_config& cfg)
+    {
+        std::vector<uint8_t> desc;
+        if (images.empty() || !push()) return desc;
+        const size_t npx = (size_t)m_cfg.n_cells * m_n_angles;
+        bool ok = true;
+        for (const ImagePtr& im : images) ok = ok && im && im->height == (uint32_t)m_cfg.n_cells && im->width == (uint32_t)m_n_angles && im->data.size() == npx;
+        if (!ok) { m_err = "describeImages: every image must be n_cells x n_angles mono8"; std::cout << "[RadarHIP] " << m_err << std::endl; return desc; }
+        if (!marshal::describe(m_ctx, images.size(), npx, [&](size_t k) { return images[k]->data.data(); }, cfg, desc)) { fail(); desc.clear(); }
+        return desc;
+    }
+    // One real image looked up in a database of descriptors (describeImages' layout, n_db of them): the top_k candidates by
+    // (sse, index); a hit's pose is the database pose turned by +shift * (n_angles / n_sectors) * theta_inc about the sensor's z
+    // axis (exact only when n_sectors divides n_angles).  Empty on error.
+    std::vector<rr_place_match> localize(const Image& real, const std::vector<uint8_t>& database, size_t n_db, const rr_place_config& cfg, int top_k)
+    {
+        std::vector<rr_place_match> out;
+        if (!push()) return out;
+        const size_t npx = (size_t)m_cfg.n_cells * m_n_angles;
+        const size_t K = cfg.n_rings > 0 && cfg.n_sectors > 0 ? (size_t)cfg.n_rings * (size_t)cfg.n_sectors : 0;
+        if (real.height != (uint32_t)m_cfg.n_cells || real.width != (uint32_t)m_n_angles || real.data.size() != npx || database.size() != n_db * K) {
+            m_err = "localize: the image must be n_cells x n_angles mono8 and the database n_db descriptors"; std::cout << "[RadarHIP] " << m_err << std::endl;
+            return out;
+        }
+        std::vector<uint8_t> q;
+        if (!marshal::describe(m_ctx, 1, npx, [&](size_t) { return real.data.data(); }, cfg, q) ||
+            !marshal::match_places(m_ctx, q.data(), 1, database.data(), n_db, cfg.n_rings, cfg.n_sectors, top_k, out)) { fail(); out.clear(); }
+        return out;
+    }
     const std::string& lastError() const { return m_err; }
     // radar_tools/radar_img_to_pcl (launch/tests/radar_sim_test.launch:80-84, outside the checkout) on the GPU: one mono8
     // polar image of this model's shape (simulated or real) -> its detections, a PointCloud's points plus the intensity

@@ -188,4 +188,25 @@ bool register_translation(rr_ctx* ctx, size_t n, size_t npx, PixelsOf image_pixe
     return true;
 }
 
+// place recognition (rr_place_config, rr_place_match): the same images as ring/sector descriptors, [n][n_rings][n_sectors] bytes
+// (rr_describe_images).  false: rr_last_error(ctx)
+template <typename PixelsOf>
+bool describe(rr_ctx* ctx, size_t n, size_t npx, PixelsOf image_pixels, const rr_place_config& cfg, std::vector<uint8_t>& desc)
+{
+    std::vector<uint8_t> flat(n * npx);
+    for (size_t k = 0; k < n; k++) std::copy(image_pixels(k), image_pixels(k) + npx, flat.begin() + (std::ptrdiff_t)(k * npx));
+    const size_t K = cfg.n_rings > 0 && cfg.n_sectors > 0 ? (size_t)cfg.n_rings * (size_t)cfg.n_sectors : 0;
+    desc.assign(n * K, 0);
+    return rr_describe_images(ctx, flat.data(), (int)n, &cfg, desc.data()) == 0;
+}
+
+// n_query descriptors against a database of n_db, all [n_rings][n_sectors] (rr_match_descriptors): the top_k candidates per query by
+// (sse, index), [n_query][top_k].  false: rr_last_error(ctx)
+inline bool match_places(rr_ctx* ctx, const uint8_t* query, size_t n_query, const uint8_t* db, size_t n_db, int n_rings, int n_sectors, int top_k,
+                         std::vector<rr_place_match>& out)
+{
+    out.assign(top_k > 0 ? n_query * (size_t)top_k : 0, rr_place_match{});
+    return rr_match_descriptors(ctx, query, (int)n_query, db, (int)n_db, n_rings, n_sectors, top_k, out.data(), nullptr, nullptr) == 0;
+}
+
 }  // namespace radarays_ros_amd::marshal

@@ -184,6 +184,11 @@ struct rr_ctx {
     // records; and the host forms' own staging: images [chunk][H][W] (d_conv_in is sized for polar images), the reference, the surfaces
     DevBuf<long long> d_shift_surf, d_shift_conv_xcorr; DevBuf<unsigned long long> d_shift_sums, d_shift_col, d_shift_box, d_shift_conv_sse;
     DevBuf<rr_shift_record> d_shift_rec; DevBuf<uint8_t> d_shift_in, d_shift_ref;
+    // rr_match_descriptors_device: the rolled queries and their sums, one database chunk's keys and aux words, the slices' winners, the
+    // winners so far twice over ([2][keys | aux][n_query][top_k]: read from one, written to the other), the records; and the host forms'
+    // staging: descriptors on their way down, queries and one database chunk on their way up, that chunk's sse / shift on their way down
+    DevBuf<uint8_t> d_place_rolls, d_place_desc, d_place_query, d_place_db; DevBuf<uint32_t> d_place_qsums, d_place_conv_sse;
+    DevBuf<unsigned long long> d_place_keys, d_place_aux, d_place_part, d_place_win; DevBuf<rr_place_match> d_place_rec; DevBuf<uint16_t> d_place_conv_shift;
     void* h_rb = nullptr; size_t h_rb_bytes = 0;         // page-locked: read_back()
     void* h_frame = nullptr; size_t h_frame_bytes = 0;   // page-locked: error bits + per-pass counters of rr_simulate's frame
 

@@ -1,5 +1,5 @@
 // rr_images.hip -- the C ABI's image entry points: images in, records / points / images out.  PSNR scores and metrics against a reference image
-// (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), point clouds and Cartesian images (rr_detect.hip): each in a device form, which runs on the
+// (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), place recognition (rr_place.hip), point clouds and Cartesian images (rr_detect.hip): each in a device form, which runs on the
 // caller's buffers and stream, and a host form, which stages through the context's own buffers on c->stream.
 #include "rr_ctx.h"
 #include <algorithm>
@@ -89,6 +89,40 @@ int check_cartesian(rr_ctx* c, const char* who, const void* imgs, int n_frames, 
     if (k->interpolation != 0 && k->interpolation != 1) return fail(c, -3, w + ": interpolation must be 0 (nearest) or 1 (bilinear)");
     if (!(std::isfinite(k->pixel_size) && k->pixel_size > 0.0f)) return fail(c, -3, w + ": pixel_size must be finite and > 0");
     if (c->cfg.theta_inc == 0.0f) return fail(c, -3, w + ": the config's theta_inc is 0");
+    return 0;
+}
+
+// the refusals of the describe calls: a config (the image shape), then the descriptor's own limits
+int check_describe(rr_ctx* c, const char* who, const void* imgs, int n, int n_max, const rr_place_config* p, const void* out)
+{
+    const std::string w(who);
+    int rc = check_images(c, w, imgs && out, "buffer", "n", n, n_max); if (rc) return rc;
+    if (!p) return fail(c, -3, w + ": null config");
+    if (p->n_rings < 1 || p->n_rings > 64) return fail(c, -3, w + ": n_rings must be 1..64");
+    if (p->n_sectors < 4 || p->n_sectors > 128) return fail(c, -3, w + ": n_sectors must be 4..128");
+    if (p->n_rings * p->n_sectors > 8192) return fail(c, -3, w + ": n_rings * n_sectors must be at most 8192");
+    if (p->cell_begin < 0 || p->cell_end > c->cfg.n_cells || p->cell_begin >= p->cell_end)
+        return fail(c, -3, w + ": the cell window [" + std::to_string(p->cell_begin) + ", " + std::to_string(p->cell_end) + ") must be non-empty and inside 0.." +
+                               std::to_string(c->cfg.n_cells));
+    if (p->n_rings > p->cell_end - p->cell_begin) return fail(c, -3, w + ": more rings than cells in the window");
+    if (p->n_sectors > c->cfg.n_angles) return fail(c, -3, w + ": more sectors than image columns");
+    return 0;
+}
+
+// the refusals of rr_match_descriptors_device / rr_match_descriptors: no config is needed, the shape comes with the call
+int check_match(rr_ctx* c, const char* who, const void* query, int n_query, const void* db, int n_db, int R, int S, int top_k, const void* out,
+                const void* sse, const void* shift)
+{
+    if (!c) return -1;
+    const std::string w(who);
+    if (!(query && db && out)) return fail(c, -3, w + ": null buffer");
+    if (n_query < 1 || n_query > 64) return fail(c, -3, w + ": n_query must be 1..64");
+    if (n_db < 1 || n_db > (1 << 28)) return fail(c, -3, w + ": n_db must be 1..2^28");
+    if (R < 1 || R > 64) return fail(c, -3, w + ": n_rings must be 1..64");
+    if (S < 4 || S > 128) return fail(c, -3, w + ": n_sectors must be 4..128");
+    if (R * S > 8192) return fail(c, -3, w + ": n_rings * n_sectors must be at most 8192");
+    if (top_k < 1 || top_k > 32 || top_k > n_db) return fail(c, -3, w + ": top_k must be 1..min(32, n_db)");
+    if (shift && !sse) return fail(c, -3, w + ": the shifts come with the sse matrix: shift without sse");
     return 0;
 }
 
@@ -429,6 +463,138 @@ int rr_simulate_batch_shift(rr_ctx* c, const float* poses, int n_frames, const u
     if (out_cart_u8) RR_HIP(c, hipMemcpy(out_cart_u8, c->d_shift_in.p, n * ncart, hipMemcpyDeviceToHost));
     if (xcorr) RR_HIP(c, hipMemcpy(xcorr, c->d_shift_conv_xcorr.p, n * ND * sizeof(int64_t), hipMemcpyDeviceToHost));
     std::copy(rec.begin(), rec.end(), out);
+    return 0;
+}
+
+// ---- place recognition: ring/sector descriptors and their exact matching (rr_place.hip) ------------------------------
+
+int rr_describe_images_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n, const rr_place_config* cfg, uint8_t* d_desc, void* stream)
+{
+    int rc = check_describe(c, "rr_describe_images_device", d_imgs_u8, n, 65535, cfg, d_desc); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    launch_place_describe(d_imgs_u8, n, c->cfg.n_cells, c->cfg.n_angles, *cfg, d_desc, stream_of(c, stream));
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_describe_images(rr_ctx* c, const uint8_t* imgs_u8, int n, const rr_place_config* cfg, uint8_t* desc)
+{
+    int rc = check_describe(c, "rr_describe_images", imgs_u8, n, 65535, cfg, desc); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles, K = (size_t)cfg->n_rings * cfg->n_sectors, total = (size_t)n;
+    rc = stage_images(c, imgs_u8, std::min(total, kChunk), nullptr, [&]() { RR_HIP(c, c->d_place_desc.ensure(std::min(total, kChunk) * K)); return 0; });
+    if (rc) return rc;
+    std::vector<uint8_t> all(total * K);                    // the caller's buffer is written once every chunk has succeeded
+    for (size_t at = 0; at < total; at += kChunk) {
+        const size_t m = std::min(kChunk, total - at);
+        if (at) RR_HIP(c, hipMemcpyAsync(c->d_conv_in.p, imgs_u8 + at * npx, m * npx, hipMemcpyHostToDevice, c->stream));
+        rc = rr_describe_images_device(c, c->d_conv_in.p, (int)m, cfg, c->d_place_desc.p, c->stream); if (rc) return rc;
+        RR_HIP(c, hipMemcpyAsync(all.data() + at * K, c->d_place_desc.p, m * K, hipMemcpyDeviceToHost, c->stream));
+        RR_HIP(c, hipStreamSynchronize(c->stream));         // the staging buffers are free again
+    }
+    std::copy(all.begin(), all.end(), desc);
+    return 0;
+}
+
+int rr_simulate_batch_describe(rr_ctx* c, const float* poses, int n_frames, const rr_place_config* cfg, uint8_t* out_desc)
+{
+    // refused before anything is simulated (the context stands in for the images: they are its own)
+    int rc = check_describe(c, "rr_simulate_batch_describe", c, n_frames, RR_MAX_BATCH, cfg, out_desc); if (rc) return rc;
+    rc = check_ready(c); if (rc) return rc;
+    if (!poses) return fail(c, -3, "rr_simulate_batch_describe: null poses");
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles, n = (size_t)n_frames, K = (size_t)cfg->n_rings * cfg->n_sectors;
+    RR_HIP(c, hipStreamSynchronize(c->stream));        // the buffers may be reallocated below
+    RR_HIP(c, c->d_param_imgs.ensure(n * npx));
+    RR_HIP(c, c->d_place_desc.ensure(n * K));
+    rc = rr_simulate_batch_device(c, poses, n_frames, c->d_param_imgs.p, c->stream); if (rc) return rc;
+    rc = rr_describe_images_device(c, c->d_param_imgs.p, n_frames, cfg, c->d_place_desc.p, c->stream); if (rc) return rc;
+    std::vector<uint8_t> desc(n * K);
+    rc = records_back(c, desc.data(), c->d_place_desc.p, n * K, c->stream); if (rc) return rc;
+    rc = report_frame_errors(c); if (rc) return rc;     // before anything is handed out
+    std::copy(desc.begin(), desc.end(), out_desc);
+    return 0;
+}
+
+int rr_match_descriptors_device(rr_ctx* c, const uint8_t* d_query, int n_query, const uint8_t* d_db, int n_db, int n_rings, int n_sectors, int top_k,
+                                rr_place_match* out, uint32_t* d_sse, uint16_t* d_shift, void* stream)
+{
+    int rc = check_match(c, "rr_match_descriptors_device", d_query, n_query, d_db, n_db, n_rings, n_sectors, top_k, out, d_sse, d_shift); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = stream_of(c, stream);
+    const size_t nq = (size_t)n_query, n = (size_t)n_db, k = (size_t)top_k, K = (size_t)n_rings * n_sectors;
+    // the database in chunks of at most 2^22 (query, candidate) pairs, whole tiles of 32 candidates: 64 MB of keys and aux words
+    const size_t chunk = std::min(n, std::max<size_t>(32, ((size_t)1 << 22) / nq / 32 * 32));
+    const size_t n_rolls = nq * n_sectors * (size_t)place_kpad(n_rings, n_sectors), n_part = nq * place_slices(chunk) * k, n_win = nq * k;
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "key words");
+    if (c->d_place_rolls.n < n_rolls || c->d_place_qsums.n < 2 * nq || c->d_place_keys.n < nq * chunk || c->d_place_aux.n < nq * chunk ||
+        c->d_place_part.n < n_part || c->d_place_win.n < 4 * n_win || c->d_place_rec.n < n_win) {
+        RR_HIP(c, hipStreamSynchronize(s));             // an earlier call's kernels may still read what is freed here
+        RR_HIP(c, c->d_place_rolls.ensure(n_rolls));
+        RR_HIP(c, c->d_place_qsums.ensure(2 * nq));
+        RR_HIP(c, c->d_place_keys.ensure(nq * chunk));
+        RR_HIP(c, c->d_place_aux.ensure(nq * chunk));
+        RR_HIP(c, c->d_place_part.ensure(n_part));
+        RR_HIP(c, c->d_place_win.ensure(4 * n_win));
+        RR_HIP(c, c->d_place_rec.ensure(n_win));
+    }
+    launch_place_rolls(d_query, n_query, n_rings, n_sectors, c->d_place_rolls.p, c->d_place_qsums.p, s);
+    // the winners so far, [2][keys | aux][n_query][top_k]: a chunk reads one half and writes the other.  No winner yet: every key ~0
+    unsigned long long* half[2] = { c->d_place_win.p, c->d_place_win.p + 2 * n_win };
+    RR_HIP(c, hipMemsetAsync(half[0], 0xFF, n_win * sizeof(unsigned long long), s));
+    int cur = 0;
+    for (size_t at = 0; at < n; at += chunk, cur ^= 1) {
+        const size_t m = std::min(chunk, n - at);
+        launch_place_match(c->d_place_rolls.p, c->d_place_qsums.p, n_query, d_db + at * K, m, at, n_rings, n_sectors, c->d_place_keys.p, c->d_place_aux.p,
+                           d_sse, d_shift, n, s);
+        launch_place_topk(c->d_place_keys.p, c->d_place_aux.p, n_query, m, at, top_k, c->d_place_part.p, half[cur], half[cur] + n_win,
+                          half[cur ^ 1], half[cur ^ 1] + n_win, s);
+    }
+    launch_place_finish(half[cur], half[cur] + n_win, c->d_place_qsums.p, n_query, top_k, n_rings, n_sectors, c->d_place_rec.p, s);
+    std::vector<rr_place_match> rec(n_win);
+    rc = records_back(c, rec.data(), c->d_place_rec.p, n_win * sizeof(rr_place_match), s); if (rc) return rc;
+    for (size_t e = 0; e < n_win; e++) {
+        rec[e].psnr = psnr_of(rec[e].sse, K);           // the host's log10, as rr_score_images_device
+        out[e] = rec[e];
+    }
+    return 0;
+}
+
+int rr_match_descriptors(rr_ctx* c, const uint8_t* query, int n_query, const uint8_t* db, int n_db, int n_rings, int n_sectors, int top_k,
+                         rr_place_match* out, uint32_t* sse, uint16_t* shift)
+{
+    int rc = check_match(c, "rr_match_descriptors", query, n_query, db, n_db, n_rings, n_sectors, top_k, out, sse, shift); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t nq = (size_t)n_query, n = (size_t)n_db, k = (size_t)top_k, K = (size_t)n_rings * n_sectors;
+    // the database goes up 16 MiB at a time; the chunks' winners are merged here by the same key
+    const size_t chunk = std::min(n, std::max<size_t>(k, ((size_t)16 << 20) / K));
+    RR_HIP(c, hipStreamSynchronize(c->stream));        // the staging buffers may be reallocated
+    RR_HIP(c, c->d_place_query.ensure(nq * K));
+    RR_HIP(c, c->d_place_db.ensure(chunk * K));
+    if (sse) RR_HIP(c, c->d_place_conv_sse.ensure(nq * chunk));
+    if (shift) RR_HIP(c, c->d_place_conv_shift.ensure(nq * chunk));
+    RR_HIP(c, hipMemcpyAsync(c->d_place_query.p, query, nq * K, hipMemcpyHostToDevice, c->stream));
+    auto before = [](const rr_place_match& a, const rr_place_match& b) { return a.sse != b.sse ? a.sse < b.sse : a.index < b.index; };
+    std::vector<std::vector<rr_place_match>> best(nq);
+    std::vector<rr_place_match> rec(nq * k);
+    std::vector<uint32_t> sse_all(sse ? nq * n : 0);
+    std::vector<uint16_t> shift_all(shift ? nq * n : 0);
+    for (size_t at = 0; at < n; at += chunk) {
+        const size_t m = std::min(chunk, n - at), km = std::min(k, m);
+        RR_HIP(c, hipMemcpyAsync(c->d_place_db.p, db + at * K, m * K, hipMemcpyHostToDevice, c->stream));
+        rc = rr_match_descriptors_device(c, c->d_place_query.p, n_query, c->d_place_db.p, (int)m, n_rings, n_sectors, (int)km, rec.data(),
+                                         sse ? c->d_place_conv_sse.p : nullptr, shift ? c->d_place_conv_shift.p : nullptr, c->stream); if (rc) return rc;
+        for (size_t q = 0; q < nq; q++) {
+            for (size_t j = 0; j < km; j++) { rr_place_match r = rec[q * km + j]; r.index += (uint32_t)at; best[q].push_back(r); }
+            std::sort(best[q].begin(), best[q].end(), before);
+            if (best[q].size() > k) best[q].resize(k);
+            if (sse) RR_HIP(c, hipMemcpy(sse_all.data() + q * n + at, c->d_place_conv_sse.p + q * m, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            if (shift) RR_HIP(c, hipMemcpy(shift_all.data() + q * n + at, c->d_place_conv_shift.p + q * m, m * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        }
+    }
+    for (size_t q = 0; q < nq; q++) std::copy(best[q].begin(), best[q].end(), out + q * k);
+    if (sse) std::copy(sse_all.begin(), sse_all.end(), sse);
+    if (shift) std::copy(shift_all.begin(), shift_all.end(), shift);
     return 0;
 }
 

@@ -1,4 +1,4 @@
-// rr_launch.h -- every launcher of rr_kernels.hip, rr_refit.hip, rr_detect.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip and rr_lbvh.hip, declared ONCE: included where they
+// rr_launch.h -- every launcher of rr_kernels.hip, rr_refit.hip, rr_detect.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip, rr_place.hip and rr_lbvh.hip, declared ONCE: included where they
 // are defined (a definition that drifts from its declaration fails there) and where they are called.  Default arguments live here only.
 #pragma once
 #include "../../include/radarays_mi355.h"
@@ -62,6 +62,21 @@ void launch_shift_sums(const uint8_t* imgs, int H, int W, int S, int n_images, u
 void launch_shift_gram(const uint8_t* imgs, const uint8_t* ref, int H, int W, int S, int n_images, long long* surf, hipStream_t s);
 void launch_shift_finish(long long* surf, unsigned long long* sse, const unsigned long long* sums, const unsigned long long* box, int H, int W,
                          int S, int n_images, rr_shift_record* out, hipStream_t s);
+// rr_place.hip (place recognition).  rolls [n_query * S][place_kpad]; keys and aux [n_query][n_candidates] of one database chunk whose first
+// candidate has the database index index_base; part [n_query][place_slices(n_candidates)][top_k]; old_* / win* [n_query][top_k] (old_keys ~0
+// before the first chunk); d_sse / d_shift [n_query][n_db] or null
+void launch_place_describe(const uint8_t* imgs, int n_images, int n_cells, int n_angles, const rr_place_config& p, uint8_t* desc, hipStream_t s);
+int place_kpad(int n_rings, int n_sectors);
+size_t place_slices(size_t n_candidates);
+void launch_place_rolls(const uint8_t* query, int n_query, int n_rings, int n_sectors, uint8_t* rolls, uint32_t* qsums, hipStream_t s);
+void launch_place_match(const uint8_t* rolls, const uint32_t* qsums, int n_query, const uint8_t* db, size_t n_candidates, size_t index_base,
+                        int n_rings, int n_sectors, unsigned long long* keys, unsigned long long* aux, uint32_t* d_sse, uint16_t* d_shift, size_t n_db,
+                        hipStream_t s);
+void launch_place_topk(const unsigned long long* keys, const unsigned long long* aux, int n_query, size_t n_candidates, size_t index_base, int top_k,
+                       unsigned long long* part, const unsigned long long* old_keys, const unsigned long long* old_aux, unsigned long long* win,
+                       unsigned long long* win_aux, hipStream_t s);
+void launch_place_finish(const unsigned long long* win, const unsigned long long* win_aux, const uint32_t* qsums, int n_query, int top_k, int n_rings,
+                         int n_sectors, rr_place_match* out, hipStream_t s);
 void launch_copy_host(const void* src, void* dst, size_t bytes, int blocks, int xcd, hipStream_t s);
 void launch_copy_words(const void* src, void* dst, size_t bytes, hipStream_t s);
 void launch_debug_brdf(size_t n, const float* in, int model, float* out, hipStream_t s);

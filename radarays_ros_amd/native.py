@@ -34,6 +34,7 @@ SYMBOLS = [
     "rr_compare_images_device", "rr_compare_images", "rr_simulate_param_sets_metrics",
     "rr_align_images_device", "rr_align_images", "rr_simulate_batch_align",
     "rr_shift_images_device", "rr_shift_images", "rr_simulate_batch_shift",
+    "rr_describe_images_device", "rr_describe_images", "rr_simulate_batch_describe", "rr_match_descriptors_device", "rr_match_descriptors",
 ]
 
 
@@ -128,6 +129,19 @@ class RRShiftRecord(C.Structure):
 SHIFT_DTYPE = np.dtype([("dy", "<i4"), ("dx", "<i4"), ("n_best", "<i4"), ("reserved_", "<i4"), ("xcorr", "<i8"), ("sse", "<u8"),
                         ("psnr", "<f8"), ("ncc", "<f8"), ("sub_dy", "<f8"), ("sub_dx", "<f8"), ("sse_nb", "<u8", (4,)),
                         ("sum_x", "<u8"), ("sum_xx", "<u8"), ("sum_r", "<u8"), ("sum_rr", "<u8")])
+
+
+class RRPlaceConfig(C.Structure):
+    _fields_ = [("cell_begin", C.c_int32), ("cell_end", C.c_int32), ("n_rings", C.c_int32), ("n_sectors", C.c_int32)]
+
+
+class RRPlaceMatch(C.Structure):
+    _fields_ = [("index", C.c_uint32), ("shift", C.c_int32), ("sse", C.c_uint32), ("n_best", C.c_uint32), ("xcorr", C.c_int64),
+                ("ncc", C.c_double), ("psnr", C.c_double)]
+
+
+# rr_place_match as numpy sees it (40 B)
+PLACE_DTYPE = np.dtype([("index", "<u4"), ("shift", "<i4"), ("sse", "<u4"), ("n_best", "<u4"), ("xcorr", "<i8"), ("ncc", "<f8"), ("psnr", "<f8")])
 
 
 def metrics_mask(which):
@@ -336,6 +350,11 @@ def lib():
     L.rr_shift_images_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     L.rr_shift_images.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.rr_simulate_batch_shift.argtypes = [vp, vp, C.c_int, vp, C.POINTER(RRCartesianConfig), C.c_int, vp, vp, vp]
+    L.rr_describe_images_device.argtypes = [vp, vp, C.c_int, C.POINTER(RRPlaceConfig), vp, vp]
+    L.rr_describe_images.argtypes = [vp, vp, C.c_int, C.POINTER(RRPlaceConfig), vp]
+    L.rr_simulate_batch_describe.argtypes = [vp, vp, C.c_int, C.POINTER(RRPlaceConfig), vp]
+    L.rr_match_descriptors_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.rr_match_descriptors.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     for n in SYMBOLS:
         getattr(L, n)
     _LIB = L
@@ -473,6 +492,38 @@ def shift_window(height, width, max_shift):
     if (h - 2 * s) * (w - 2 * s) > 1 << 23:
         raise ValueError("the template window %d x %d holds more than 2^23 pixels" % (h - 2 * s, w - 2 * s))
     return h, w, s
+
+
+def place_shape(n_rings, n_sectors):
+    """(R, S) of a descriptor, range-checked before any call into the library: R in 1..64, S in 4..128, R * S <= 8192"""
+    r, s = _int_in(n_rings, 1, 64, "n_rings"), _int_in(n_sectors, 4, 128, "n_sectors")
+    if r * s > 8192:
+        raise ValueError("n_rings * n_sectors must be at most 8192, got %d" % (r * s))
+    return r, s
+
+
+def place_config(n_rings, n_sectors, n_cells, n_angles, cell_begin=0, cell_end=None):
+    """RRPlaceConfig for images [n_cells][n_angles], every field range-checked here; cell_end None: n_cells"""
+    r, s = place_shape(n_rings, n_sectors)
+    if cell_end is None:
+        cell_end = n_cells
+    for v in (cell_begin, cell_end):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("cell_begin and cell_end must be integers, got %r, %r" % (cell_begin, cell_end))
+    if not 0 <= cell_begin < cell_end <= n_cells:
+        raise ValueError("the cell window [%d, %d) must be non-empty and inside 0..%d" % (cell_begin, cell_end, n_cells))
+    if r > cell_end - cell_begin:
+        raise ValueError("%d rings in a window of %d cells" % (r, cell_end - cell_begin))
+    if s > n_angles:
+        raise ValueError("%d sectors in an image of %d columns" % (s, n_angles))
+    c = RRPlaceConfig()
+    c.cell_begin, c.cell_end, c.n_rings, c.n_sectors = int(cell_begin), int(cell_end), r, s
+    return c
+
+
+def _match_args(n_query, n_db, top_k):
+    nq, n = _int_in(n_query, 1, 64, "n_query"), _int_in(n_db, 1, 1 << 28, "n_db")
+    return nq, n, _int_in(top_k, 1, min(32, n), "top_k")
 
 
 def _frames_arg(n_frames):
@@ -870,6 +921,76 @@ class Context:
                                                  None if out is None else out.ctypes.data, rec.ctypes.data,
                                                  None if xc is None else xc.ctypes.data))
         return out, rec, xc
+
+    # ---- place recognition (rr_place.hip): ring/sector descriptors of polar images and their exact matching
+    def _place_cfg(self, place_cfg):
+        """an RRPlaceConfig, a dict or a tuple (n_rings, n_sectors[, cell_begin[, cell_end]]) -> a checked RRPlaceConfig for this context's images"""
+        n_cells, n_angles = self._polar_shape()
+        if isinstance(place_cfg, RRPlaceConfig):
+            return place_config(place_cfg.n_rings, place_cfg.n_sectors, n_cells, n_angles, place_cfg.cell_begin, place_cfg.cell_end)
+        if isinstance(place_cfg, dict):
+            return place_config(n_cells=n_cells, n_angles=n_angles, **place_cfg)
+        return place_config(place_cfg[0], place_cfg[1], n_cells, n_angles, *place_cfg[2:])
+
+    def describe_images_device(self, d_imgs_ptr, n_images, place_cfg, d_desc_ptr, stream=None):
+        """rr_describe_images_device: n images [n][n_cells][n_angles] in HBM -> descriptors uint8 [n][R][S] in HBM, enqueued on `stream`"""
+        p = self._place_cfg(place_cfg)
+        n = _frames_arg(n_images)
+        if not d_imgs_ptr or not d_desc_ptr:
+            raise ValueError("describe_images_device needs image and descriptor buffers")
+        self._ck(self._L.rr_describe_images_device(self._h, d_imgs_ptr, n, C.byref(p), d_desc_ptr, stream))
+
+    def describe_images(self, imgs, place_cfg):
+        """rr_describe_images on host images [n][n_cells][n_angles] (or one image) -> descriptors uint8 [n][R][S]"""
+        x = self._polar_images(imgs)
+        p = self._place_cfg(place_cfg)
+        out = np.zeros((len(x), p.n_rings, p.n_sectors), np.uint8)
+        self._ck(self._L.rr_describe_images(self._h, x.ctypes.data, len(x), C.byref(p), out.ctypes.data))
+        return out
+
+    def simulate_batch_describe(self, poses, place_cfg):
+        """rr_simulate_batch_describe: up to 64 poses simulated and described, no image leaving the GPU -> uint8 [n][R][S]"""
+        p = self._place_cfg(place_cfg)
+        ps = _rows(poses, 7, "poses")
+        if not 1 <= len(ps) <= 64:
+            raise ValueError("1..64 poses, got %d" % len(ps))
+        out = np.zeros((len(ps), p.n_rings, p.n_sectors), np.uint8)
+        self._ck(self._L.rr_simulate_batch_describe(self._h, ps.ctypes.data, len(ps), C.byref(p), out.ctypes.data))
+        return out
+
+    def match_descriptors_device(self, d_query_ptr, n_query, d_db_ptr, n_db, n_rings, n_sectors, top_k, d_sse_ptr=None, d_shift_ptr=None, stream=None):
+        """rr_match_descriptors_device: queries [n_query][R][S] against a database [n_db][R][S], both in HBM -> PLACE_DTYPE array
+        [n_query][top_k], ranked by (sse, index); d_sse_ptr (uint32) and d_shift_ptr (uint16, only with d_sse_ptr), HBM [n_query][n_db],
+        receive every pair's SSE and shift.  Synchronous on `stream`.  Needs no config."""
+        r, s = place_shape(n_rings, n_sectors)
+        nq, n, k = _match_args(n_query, n_db, top_k)
+        if not d_query_ptr or not d_db_ptr:
+            raise ValueError("match_descriptors_device needs query and database buffers")
+        if d_shift_ptr and not d_sse_ptr:
+            raise ValueError("d_shift_ptr comes with d_sse_ptr")
+        rec = np.zeros((nq, k), PLACE_DTYPE)
+        self._ck(self._L.rr_match_descriptors_device(self._h, d_query_ptr, nq, d_db_ptr, n, r, s, k, rec.ctypes.data, d_sse_ptr, d_shift_ptr, stream))
+        return rec
+
+    def match_descriptors(self, query, db, top_k, want_full=False):
+        """rr_match_descriptors on host descriptors: query uint8 [n_query][R][S] (or one [R][S]) against db [n_db][R][S] ->
+        PLACE_DTYPE array [n_query][top_k], and with want_full (records, sse uint32 [n_query][n_db], shift uint16 [n_query][n_db])"""
+        q, d = np.asarray(query), np.asarray(db)
+        if q.dtype != np.uint8 or d.dtype != np.uint8:
+            raise ValueError("descriptors must be uint8, got %s and %s" % (q.dtype, d.dtype))
+        if q.ndim == 2:
+            q = q[None]
+        if q.ndim != 3 or d.ndim != 3 or q.shape[1:] != d.shape[1:]:
+            raise ValueError("queries [n_query][R][S] and a database [n_db][R][S] of the same R, S, got %s and %s" % (np.asarray(query).shape, d.shape))
+        r, s = place_shape(q.shape[1], q.shape[2])
+        nq, n, k = _match_args(q.shape[0], d.shape[0], top_k)
+        q, d = np.ascontiguousarray(q), np.ascontiguousarray(d)
+        rec = np.zeros((nq, k), PLACE_DTYPE)
+        sse = np.zeros((nq, n), np.uint32) if want_full else None
+        shift = np.zeros((nq, n), np.uint16) if want_full else None
+        self._ck(self._L.rr_match_descriptors(self._h, q.ctypes.data, nq, d.ctypes.data, n, r, s, k, rec.ctypes.data,
+                                              None if sse is None else sse.ctypes.data, None if shift is None else shift.ctypes.data))
+        return (rec, sse, shift) if want_full else rec
 
     def simulate_device(self, pose, d_img_ptr, stream=None):
         p = np.ascontiguousarray(pose, np.float32)

@@ -247,6 +247,64 @@ class RadarHIP:
             out.append(chunk.astype(np.float32)); yaw_recs.append(yaw); shift_recs.append(sh)
         return np.concatenate(out), np.concatenate(yaw_recs), np.concatenate(shift_recs)
 
+    # ---- place recognition (rr_place.hip): a database of yaw-invariant ring/sector descriptors, and a scan looked up in it
+    def buildPlaceDatabase(self, poses, place_cfg, on_device=False):
+        """any number of [n][7] poses, worked through 64 at a time -> their descriptors uint8 [n][R][S] (native.Context._place_cfg
+        says what place_cfg may be); no image leaves the GPU.  on_device: the database stays in HBM, as a torch tensor."""
+        self._push()
+        p = native.object_poses_array(poses)
+        cfg = self._ctx._place_cfg(place_cfg)
+        self._place_cfg = cfg
+        if not on_device:
+            if len(p) == 0:
+                return np.zeros((0, cfg.n_rings, cfg.n_sectors), np.uint8)
+            return np.concatenate([self._ctx.simulate_batch_describe(p[at:at + 64], cfg) for at in range(0, len(p), 64)])
+        import torch
+        dev = torch.device("cuda", self._ctx.device)
+        stream = torch.cuda.Stream(device=dev)      # an explicit stream, as simulatePointClouds
+        s = stream.cuda_stream
+        with torch.cuda.device(dev), torch.cuda.stream(stream):
+            db = torch.empty((len(p), cfg.n_rings, cfg.n_sectors), dtype=torch.uint8, device=dev)
+            imgs = torch.empty((min(64, max(1, len(p))), self.m_cfg.n_cells, N_ANGLES), dtype=torch.uint8, device=dev)
+            for at in range(0, len(p), 64):
+                chunk = p[at:at + 64]
+                self._ctx.simulate_batch_device(chunk, imgs.data_ptr(), s)
+                self._ctx.describe_images_device(imgs.data_ptr(), len(chunk), cfg, db[at:].data_ptr(), s)
+        self._ctx.synchronize(s)
+        return db
+
+    def localize(self, real_polar, database, poses, top_k, place_cfg=None):
+        """ONE real polar image looked up in `database` (buildPlaceDatabase's, host array or HBM tensor) -> (a native.PLACE_DTYPE
+        array [top_k], ranked by (sse, index); float32 [top_k][7]: per hit the database pose turned by the shift's yaw).  place_cfg
+        None: the one of the last buildPlaceDatabase.  The shift s moves the REAL scan's sectors, so by the rule registerPose uses for an
+        azimuth shift the real pose turned by -s * (n_angles / S) * theta_inc about the sensor's z axis is the database pose; the
+        database pose is therefore turned by +s * (n_angles / S) * theta_inc.  Exact only when S divides n_angles -- otherwise
+        sector widths differ by one column and the yaw is approximate."""
+        self._push()
+        cfg = self._ctx._place_cfg(place_cfg if place_cfg is not None else getattr(self, "_place_cfg", None) or tuple(database.shape[1:]))
+        if tuple(database.shape[1:]) != (cfg.n_rings, cfg.n_sectors):
+            raise ValueError("the database holds descriptors %s, the config says %s" % (tuple(database.shape[1:]), (cfg.n_rings, cfg.n_sectors)))
+        p = native.object_poses_array(poses)
+        if len(p) != len(database):
+            raise ValueError("%d poses for %d database entries" % (len(p), len(database)))
+        q = self._ctx.describe_images(self._polar(real_polar), cfg)
+        if isinstance(database, np.ndarray):
+            rec = self._ctx.match_descriptors(q, database, top_k)[0]
+        else:
+            import torch
+            d_q = torch.from_numpy(q).to(database.device)
+            rec = self._ctx.match_descriptors_device(d_q.data_ptr(), 1, database.data_ptr(), len(database), cfg.n_rings, cfg.n_sectors, top_k)[0]
+        S = cfg.n_sectors
+        s = rec["shift"].astype(np.int64)
+        s = np.where(2 * s > S, s - S, s)
+        half = 0.5 * s * (N_ANGLES / S) * float(self._ctx._rrcfg.theta_inc)
+        bz, bw = np.sin(half), np.cos(half)                           # q * (0, 0, bz, bw): a turn in the sensor's own frame
+        hit = p[rec["index"]].astype(np.float64)
+        ax, ay, az, aw = hit[:, 0].copy(), hit[:, 1].copy(), hit[:, 2].copy(), hit[:, 3].copy()
+        hit[:, 0], hit[:, 1] = ax * bw + ay * bz, ay * bw - ax * bz
+        hit[:, 2], hit[:, 3] = aw * bz + az * bw, aw * bw - az * bz
+        return rec, hit.astype(np.float32)
+
     def _push(self):
         if self._dirty_cfg:
             cfg = self.m_cfg.copy(n_reflections=self.m_params.model.n_reflections)
