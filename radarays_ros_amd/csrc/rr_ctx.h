@@ -30,7 +30,8 @@ struct Lane {
     DevBuf<float4> d_wA[2], d_wB[2];
     DevBuf<double2> d_wC[2];
     DevBuf<uint32_t> d_idx[2], d_count[2], d_refpos, d_sig_count, d_spill;
-    DevBuf<uint2> d_torder[2];
+    DevBuf<uint2> d_torder[2], d_sorder;
+    DevBuf<uint32_t> d_n_air;
     DevBuf<uint2> d_hit;
     DevBuf<uint8_t> d_cflag, d_cols_u8;
     DevBuf<SigRec> d_sigtmp, d_sig;

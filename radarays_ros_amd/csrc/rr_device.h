@@ -134,7 +134,12 @@ struct Params {
     uint32_t* count[2];          // [n_seg]
     uint2* torder[2];            // [n_seg][cap] trace position -> (position in idx, child slot): the order the rays of a later pass are TRACED in (coherent order, inherited from pass 0); the slot rides along so that k_trace reaches its wave with one dependent load less
     uint32_t* refpos;            // [n_seg][2*cap] child slot -> its position in the next pass' idx
-    uint8_t* cflag;              // [n_seg][2*cap] child alive flags (+ bit2 on slot 2j: hit)
+    uint8_t* cflag;              // [n_seg][2*cap] bit 0: child alive, bit 1: that child travels in air, bit 2 (slot 2j only): wave j hit
+    // Shade order of the LAST pass (k_scan of the pass before it, when that pass is the last of every frame of the launch):
+    // the waves that travel in air -- the only ones that can echo (RadarCPU.cpp:302) -- first, in increasing position, from
+    // sorder[seg][0] upwards; the waves inside a material from sorder[seg][cap - 1] downwards.  Entry = (position in idx, child slot)
+    uint2* sorder;               // [n_seg][cap]
+    uint32_t* n_air;             // [n_seg] how many of the segment's last-pass waves travel in air
     SigRec* sigtmp;              // [n_seg][2*cap] per-wave signal slots (path, air)
     uint2* hit;                  // [n_seg][cap] nearest hit of a wave: (range as float bits, or -1.0f for a miss; leaf-order triangle index): ONE 8-B store per ray
     SigRec* sig;                 // [n_seg][sigcap] ordered signal list

@@ -53,7 +53,7 @@ int ensure_frame_buffers(rr_ctx* c, Lane& L, int n_seg, bool want_f32)
     const int cap = wave_capacity(g, n_beam);
     const int sigcap = signal_capacity(g, n_beam, cap);
     const size_t S = (size_t)n_seg;
-    const size_t per_seg = (size_t)cap * (2 * 2 * 48 + 2 * 4 + 2 * 9 + 8) + (size_t)sigcap * 8 + (size_t)g.n_cells * 5;
+    const size_t per_seg = (size_t)cap * (2 * 2 * 48 + 2 * 4 + 2 * 9 + 8 + 8) + (size_t)sigcap * 8 + (size_t)g.n_cells * 5;
     size_t free_b = 0, total_b = 0;
     RR_HIP(c, hipMemGetInfo(&free_b, &total_b));
     if (S * per_seg > total_b / 2)
@@ -68,6 +68,8 @@ int ensure_frame_buffers(rr_ctx* c, Lane& L, int n_seg, bool want_f32)
     }
     RR_HIP(c, L.d_cflag.ensure(S * 2 * cap));
     RR_HIP(c, L.d_refpos.ensure(S * 2 * cap));
+    RR_HIP(c, L.d_sorder.ensure(S * cap));
+    RR_HIP(c, L.d_n_air.ensure(S));
     RR_HIP(c, L.d_sigtmp.ensure(S * 2 * cap));
     RR_HIP(c, L.d_hit.ensure(S * cap));
     RR_HIP(c, L.d_sig.ensure(S * sigcap));
@@ -114,7 +116,7 @@ void fill_params(rr_ctx* c, Lane& L, Params& P, const float pose[7], int az_begi
         P.waves[k].A = L.d_wA[k].p; P.waves[k].B = L.d_wB[k].p; P.waves[k].C = L.d_wC[k].p;
         P.idx[k] = L.d_idx[k].p; P.count[k] = L.d_count[k].p; P.torder[k] = L.d_torder[k].p;
     }
-    P.refpos = L.d_refpos.p;
+    P.refpos = L.d_refpos.p; P.sorder = L.d_sorder.p; P.n_air = L.d_n_air.p;
     P.cflag = L.d_cflag.p; P.sigtmp = L.d_sigtmp.p; P.hit = L.d_hit.p;
     P.sig = L.d_sig.p; P.sig_count = L.d_sig_count.p; P.spill = L.d_spill.p; P.counters = L.d_counters.p; P.sticky = L.d_sticky.p; P.seg_stats = L.d_seg_stats.p;
     P.cols_u8 = d_cols_u8; P.cols_f32 = d_cols_f32;

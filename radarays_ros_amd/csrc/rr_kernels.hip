@@ -562,6 +562,12 @@ void launch_mat_limits(const float4* materials, size_t n, double* limits, hipStr
     if (n) hipLaunchKernelGGL(k_mat_limits, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, materials, n, limits);
 }
 
+// direction of the reflected wave, radar_algorithms.h:73
+__device__ inline V3 reflect_dir(const V3 n, const V3 d) { return v_add(d, v_scale(v_scale(n, 2.0f), v_dot(v_neg(n), d))); }
+
+// CHILDREN = false (the last pass, where no wave has children): only renergy is formed; rdir and tenergy are left alone.  tdir
+// is still needed there: the refraction angle that rs / rp are made of is measured against it
+template <bool CHILDREN = true>
 __device__ inline void fresnel_split(V3 n, const V3 d, const float incidence_f, const double energy, const double v1, const double v2,
                                      const double angle_limit, V3& rdir, double& renergy, V3& tdir, double& tenergy)
 {
@@ -569,7 +575,7 @@ __device__ inline void fresnel_split(V3 n, const V3 d, const float incidence_f, 
     const double n1 = v2, n2 = v1;     // radar_algorithms.h:62-63
     // acosf(-d . n): the caller computed it (the BRDF angle of RadarCPU.cpp:308 is the same expression on the same values)
     const double incidence_angle = (double)incidence_f;
-    rdir = v_add(d, v_scale(v_scale(n, 2.0f), v_dot(v_neg(n), d)));   // :73
+    if constexpr (CHILDREN) rdir = reflect_dir(n, d);   // :73
     tdir = { 0.0f, 0.0f, 0.0f };
     bool transmitted = false;          // false: tdir stays the zero vector of radar_algorithms.h:66
     if (n1 > 0.0) {
@@ -630,7 +636,7 @@ __device__ inline void fresnel_split(V3 n, const V3 d, const float incidence_f, 
     const double Reff = polarization * Rs + (1.0 - polarization) * Rp;
     const double Teff = 1.0 - Reff;
     renergy = Reff * energy;
-    tenergy = Teff * energy;
+    if constexpr (CHILDREN) tenergy = Teff * energy;
 }
 
 // test hook (rr_debug_fresnel): fresnel_split exactly as k_shade calls it -- the incidence angle by acosf of the f32 dot product
@@ -709,21 +715,49 @@ __device__ inline int signal_cell(double time, double resolution)
 }
 
 // grid: (ceil(cap/64), n_seg), block 64 (one wave: no workgroup waits for its slowest wave)
-template <bool FIRST>
+// LAST: `pass` is the last ray-cast pass of EVERY frame of the launch (launch_shade).  No wave has children there, so nothing of
+// a child is computed or stored, and a wave that travels inside a material can neither echo (RadarCPU.cpp:302) nor spawn: all
+// anybody reads of it is its hit bit.  Behind pass 0 the lanes take their waves in the shade order k_scan left (Params::sorder):
+// the waves in air first, so that the 64 lanes of a wave are of one kind -- all but the one wave per segment that holds the
+// boundary -- and the waves in a material cost a hit record and two stores, not a triangle gather and a Fresnel chain.
+// Outputs stay indexed by the wave's own slot: nothing downstream sees the order
+template <bool FIRST, bool LAST>
 __global__ __launch_bounds__(64) void k_shade(const Params P, const int pass)
 {
     const int seg = blockIdx.y;
-    const int j = blockIdx.x * 64 + threadIdx.x;
+    const int lane = blockIdx.x * 64 + threadIdx.x;
     const int cur = pass & 1, nxt = cur ^ 1;
     const int count = FIRST ? P.n_beam : (int)P.count[cur][seg];
-    if (j >= count) return;
+    if (lane >= count) return;
     const int frame = seg / P.n_loc;
     const int np_f = passes_of(P, frame);          // parameter sets: this frame's own number of passes
-    const bool last = (pass == np_f - 1);
-
+    const bool last = LAST || (pass == np_f - 1);
     const size_t base2 = (size_t)seg * 2 * P.cap;
+
+    int j = lane;                                   // the wave's position in the live list
+    uint32_t slot = 0;                              // ... and the slot its parent stored it in
+    if constexpr (!FIRST && LAST) {
+        const int n_air = (int)P.n_air[seg];
+        const bool in_air = lane < n_air;
+        const uint2 oe = P.sorder[(size_t)seg * P.cap + (in_air ? lane : P.cap - 1 - (lane - n_air))];
+        j = (int)oe.x; slot = oe.y;
+        if (!in_air) {
+            // mat != air: the material behind the surface is air (RadarCPU.cpp:279), the one thing that can still go wrong
+            const size_t s0 = base2 + 2 * (size_t)j;
+            const bool hit = __uint_as_float(P.hit[(size_t)seg * P.cap + j].x) >= 0.0f;
+            if (hit && (uint32_t)P.material_id_air >= (uint32_t)P.n_materials) { atomicOr(&P.counters->overflow, 2u); atomicOr(P.sticky, 2u); }
+            const SigRec none = { -1, 0.0f };
+            P.cflag[s0] = hit ? 4 : 0;
+            P.sigtmp[s0] = none;
+            if (P.record_multi_path) { P.cflag[s0 + 1] = 0; P.sigtmp[s0 + 1] = none; }
+            return;
+        }
+    } else if constexpr (!FIRST) {
+        slot = P.idx[cur][(size_t)seg * P.cap + j];
+    }
+
     const size_t s0 = base2 + 2 * (size_t)j, s1 = s0 + 1;
-    if (FIRST && pass >= np_f) {                    // a set with n_reflections = 0: no ray is cast, the image stays empty
+    if (FIRST && !LAST && pass >= np_f) {           // a set with n_reflections = 0: no ray is cast, the image stays empty
         P.cflag[s0] = 0; P.cflag[s1] = 0;
         const SigRec none = { -1, 0.0f };
         P.sigtmp[s0] = none; P.sigtmp[s1] = none;
@@ -737,7 +771,6 @@ __global__ __launch_bounds__(64) void k_shade(const Params P, const int pass)
         const float4 b = P.beams[beam_base(P, frame) + j];
         dir = { b.x, b.y, b.z };
     } else {
-        const uint32_t slot = P.idx[cur][(size_t)seg * P.cap + j];
         const size_t w = base2 + slot;
         const float4 A = P.waves[cur].A[w], B = P.waves[cur].B[w];
         const double2 C = P.waves[cur].C[w];
@@ -794,15 +827,15 @@ __global__ __launch_bounds__(64) void k_shade(const Params P, const int pass)
             const float v_refraction = (mat != mat_refr) ? m.x : (float)0.3;
             const double angle_limit = (mat != mat_refr) ? P.mat_limits[(size_t)frame * P.mat_stride + mat_refr] : P.limit_same;
 
-            V3 rdir, tdir; double renergy, tenergy;
+            V3 rdir = { 0.0f, 0.0f, 0.0f }, tdir; double renergy, tenergy = 0.0;
             const float incidence_angle = acosf_ref(v_dot(v_neg(dir_in), normal));   // radar_algorithms.h:69 and RadarCPU.cpp:308: one value
-            fresnel_split(normal, dir_in, incidence_angle, energy, 0.3, (double)v_refraction, angle_limit, rdir, renergy, tdir, tenergy);
+            fresnel_split<!LAST>(normal, dir_in, incidence_angle, energy, 0.3, (double)v_refraction, angle_limit, rdir, renergy, tdir, tenergy);
 
             const float skip_dist = 0.001f;   // RadarCPU.cpp:374
             if (renergy > (double)P.thr)      // :288
             {
                 if (!last) {
-                    f0 |= 1;
+                    f0 |= (int)mat == P.material_id_air ? 3 : 1;      // bit 1: the child travels in air (it inherits `mat`)
                     const V3 o2 = v_add(orig, v_scale(rdir, skip_dist));
                     const double t2 = time + (double)skip_dist / 0.3;
                     P.waves[nxt].A[s0] = make_float4(o2.x, o2.y, o2.z, rdir.x);
@@ -823,6 +856,7 @@ __global__ __launch_bounds__(64) void k_shade(const Params P, const int pass)
                         const V3 dsh = { orig.x / dist, orig.y / dist, orig.z / dist };
                         const double time_to_sensor = (double)dist / 0.3;
                         const double sensor_view_scalar = (double)v_dot(dir_in, dsh);
+                        if constexpr (LAST) rdir = reflect_dir(normal, dir_in);     // (nobody else needs it in the last pass)
                         const float ang = acosf_ref(v_dot(v_neg(rdir), dsh));
                         if (sensor_view_scalar > P.multipath_threshold) {
                             sg1.strength = back_reflection_shader(ang, (float)renergy, m.y, m.z, m.w, P.brdf_model);
@@ -834,7 +868,7 @@ __global__ __launch_bounds__(64) void k_shade(const Params P, const int pass)
             }
             if (!last && tenergy > (double)P.thr)   // :367
             {
-                f1 |= 1;
+                f1 |= (int)mat_refr == P.material_id_air ? 3 : 1;
                 const V3 o2 = v_add(orig, v_scale(tdir, skip_dist));
                 const double t2 = time + (double)skip_dist / 0.3;
                 P.waves[nxt].A[s1] = make_float4(o2.x, o2.y, o2.z, tdir.x);
@@ -843,8 +877,9 @@ __global__ __launch_bounds__(64) void k_shade(const Params P, const int pass)
             }
         }
     }
-    P.cflag[s0] = f0; P.cflag[s1] = f1;
-    P.sigtmp[s0] = sg0; P.sigtmp[s1] = sg1;
+    P.cflag[s0] = f0; P.sigtmp[s0] = sg0;
+    // the last pass: the odd slot can only hold a multipath echo, and k_column stages it only then
+    if (!LAST || P.record_multi_path) { P.cflag[s1] = f1; P.sigtmp[s1] = sg1; }
 }
 
 // ---------------------------------------------------------------------------
@@ -864,10 +899,27 @@ __device__ inline int block_excl_scan(int v, int& total, int* lds /*[8]*/)
     return pre + x - v;
 }
 
-template <bool FIRST>
+// the same for two packed words riding in one scan (lds: 4 x 8 bytes = the same 8 ints, the same two barriers)
+__device__ inline unsigned long long block_excl_scan64(unsigned long long v, unsigned long long& total, int* lds /*[8]*/)
+{
+    unsigned long long* lds64 = reinterpret_cast<unsigned long long*>(lds);
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    unsigned long long x = v;
+    for (int off = 1; off < 64; off <<= 1) { const unsigned long long y = __shfl_up(x, off); if (lane >= off) x += y; }
+    if (lane == 63) lds64[wid] = x;
+    __syncthreads();
+    unsigned long long pre = 0, tot = 0;
+    for (int w = 0; w < 4; w++) { const unsigned long long s = lds64[w]; if (w < wid) pre += s; tot += s; }
+    __syncthreads();
+    total = tot;
+    return pre + x - v;
+}
+
+// ORDER: the pass this scan opens is the last of every frame of the launch -- it also leaves that pass' shade order (Params::sorder)
+template <bool FIRST, bool ORDER>
 __global__ __launch_bounds__(256) void k_scan(const Params P, const int pass)
 {
-    __shared__ int lds[8];
+    __shared__ __align__(8) int lds[8];
     const int seg = blockIdx.x;
     const int cur = pass & 1, nxt = cur ^ 1;
     const int count = FIRST ? P.n_beam : (int)P.count[cur][seg];
@@ -878,6 +930,7 @@ __global__ __launch_bounds__(256) void k_scan(const Params P, const int pass)
     int n_sig = FIRST ? 0 : (int)P.sig_count[seg];
     const int sig_before = n_sig;
     int n_hit = 0, n_refl = 0, my_hits = 0;
+    int n_airc = 0;                 // ORDER: children so far that travel in air
     unsigned ovf = 0;
     // the loads of block b + 1 are in flight while block b is scanned (a block is two barriers and a dependent scatter)
     uint8_t f_nx = 0; SigRec sr_nx = { -1, 0.0f };
@@ -892,10 +945,24 @@ __global__ __launch_bounds__(256) void k_scan(const Params P, const int pass)
         // = refractions apart: the trace order below needs the number of reflections), signals; hits are only summed
         const int c = f & 1;
         const int g = sr.cell >= 0 ? 1 : 0;
-        int tot;
-        const int pre = block_excl_scan(((s & 1) ? (c << 10) : c) | (g << 20), tot, lds);
+        int tot, pre;
+        const int packed = ((s & 1) ? (c << 10) : c) | (g << 20);
+        int air_before = 0;
+        const int a = c & (f >> 1);                                   // the child travels in air (k_shade)
+        if constexpr (ORDER) {
+            // the air children of the block: a fourth count in the same scan (the 32-bit word is full: 3 x 10 bits)
+            unsigned long long tot64;
+            const unsigned long long pre64 = block_excl_scan64((unsigned long long)(unsigned)packed | ((unsigned long long)a << 32), tot64, lds);
+            pre = (int)(unsigned)pre64; tot = (int)(unsigned)tot64;
+            air_before = n_airc + (int)(pre64 >> 32);
+            n_airc += (int)(tot64 >> 32);
+        } else pre = block_excl_scan(packed, tot, lds);
         const int pos = n_child + (pre & 1023) + ((pre >> 10) & 1023);
         if (c) { if (pos < P.cap) { P.idx[nxt][(size_t)seg * P.cap + pos] = (uint32_t)s; P.refpos[base2 + s] = (uint32_t)pos; } else { ovf = 1; P.refpos[base2 + s] = 0xFFFFFFFFu; } }
+        if constexpr (ORDER) {
+            // air_before <= pos < cap: both ends stay inside the segment's row, and they cannot meet (placed children <= cap)
+            if (c && pos < P.cap) P.sorder[(size_t)seg * P.cap + (a ? air_before : P.cap - 1 - (pos - air_before))] = make_uint2((uint32_t)pos, (uint32_t)s);
+        }
         n_child += (tot & 1023) + ((tot >> 10) & 1023);
         n_refl += tot & 1023;
         const int spos = n_sig + ((pre >> 20) & 1023);
@@ -911,6 +978,16 @@ __global__ __launch_bounds__(256) void k_scan(const Params P, const int pass)
     // trace order of the next pass: children in the (spatially sorted) trace order of their
     // parents, all reflections first, then all refractions -> neighbouring quads stay coherent
     __syncthreads();
+    if constexpr (ORDER) {
+        // the air waves of the shade order are the PLACED air children (positions rise with the slot, so they are a prefix)
+        if (n_child > P.cap) {          // overflow (reported): recount exactly
+            int mine = 0;
+            for (int k = threadIdx.x; k < n_slots; k += 256)
+                if ((P.cflag[base2 + k] & 3) == 3 && P.refpos[base2 + k] != 0xFFFFFFFFu) mine++;
+            int tot; block_excl_scan(mine, tot, lds); n_airc = tot;
+        }
+        if (threadIdx.x == 0) P.n_air[seg] = (uint32_t)n_airc;
+    }
     {
         // both children of a parent in one sweep: reflections fill [0, R), refractions [R, ...), R = the number of PLACED
         // reflections (a child beyond the capacity has no reference position and no place in the trace order)
@@ -1133,7 +1210,10 @@ __global__ __launch_bounds__(kColThreads) void k_column(const Params P)
     int count_last = 0;
     if (P.n_passes == 1) count_last = P.n_beam;
     else if (P.n_passes > 1) count_last = (int)P.count[(P.n_passes - 1) & 1][seg];
-    const int n_slots = 2 * count_last;
+    // a wave of the last pass owns two slots; the odd one can only hold a multipath echo (k_shade), so without
+    // record_multi_path -- the KAIST preset -- only the even ones are staged: half the loads, ballots and barriers
+    const int sl_sh = P.record_multi_path ? 0 : 1;            // staged entry e of the last pass = slot e << sl_sh
+    const int n_slots = (2 * count_last) >> sl_sh;
     const int S = n_list + n_slots;
     const size_t base2 = (size_t)seg * 2 * P.cap;
 
@@ -1152,7 +1232,7 @@ __global__ __launch_bounds__(kColThreads) void k_column(const Params P)
         if (tid == 2) s_odd = 0;
         // stage the chunk, keeping only the signals that land in the image (RadarCPU.cpp:414), IN ORDER:
         // ballot rank inside the wave + the counts of the waves before it (the per-wave slots of the last
-        // pass are half empty -- no multipath echo -- so the replay scans half as many entries)
+        // pass are sparse, so the replay scans fewer entries than were staged)
         int n = 0;
         // 64-bin tiles touched by the kept signals of this chunk: collected per lane in registers and OR-ed into LDS
         // once per wave (one LDS atomic per signal and tile put every lane of a wave on the same two addresses:
@@ -1166,9 +1246,10 @@ __global__ __launch_bounds__(kColThreads) void k_column(const Params P)
             if (i < n_in) {
                 if (v < n_list) r = P.sig[(size_t)seg * P.sigcap + v];
                 else {
-                    r = P.sigtmp[base2 + (v - n_list)];
+                    const int sl = (v - n_list) << sl_sh;
+                    r = P.sigtmp[base2 + sl];
                     n_valid_last += r.cell >= 0;
-                    n_hit_last += (P.cflag[base2 + (v - n_list)] >> 2) & 1;
+                    if (!(sl & 1)) n_hit_last += (P.cflag[base2 + sl] >> 2) & 1;      // the hit bit only ever lives in the even slot
                 }
             }
             const bool keep = r.cell >= 0 && r.cell < n_cells;
@@ -1664,15 +1745,28 @@ void launch_trace(const Params& P, int pass, const PoseArgs* poses, bool stats, 
 // replay to replay -- (Params, pass, PoseArgs) -- see rr_frame.hip: run_frame
 void* trace0_kernel(bool spill, bool stackless) { return (void*)trace_kernel<true>(false, spill, false, stackless); }
 
+// `pass` is the last ray-cast pass of EVERY frame of the launch (the frames of a parameter batch may bring their own pass counts:
+// a launch that mixes them keeps the kernels that decide per frame at run time)
+static bool uniform_last_pass(const Params& P, int pass)
+{
+    if (pass != P.n_passes - 1) return false;
+    if (P.set_mode) for (int f = 0; f < P.n_frames; f++) if ((int)P.frame_passes[f] != P.n_passes) return false;
+    return true;
+}
+
 void launch_shade(const Params& P, int pass, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop)
 {
     dim3 grid(((int)pass_bound(P, pass) + 63) / 64, P.n_seg);
-    launch_k(pass == 0 ? k_shade<true> : k_shade<false>, grid, dim3(64), 0, s, ev_start, ev_stop, P, pass);
+    const bool last = uniform_last_pass(P, pass);
+    const auto k = pass == 0 ? (last ? k_shade<true, true> : k_shade<true, false>) : (last ? k_shade<false, true> : k_shade<false, false>);
+    launch_k(k, grid, dim3(64), 0, s, ev_start, ev_stop, P, pass);
 }
 
 void launch_scan(const Params& P, int pass, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop)
 {
-    launch_k(pass == 0 ? k_scan<true> : k_scan<false>, dim3(P.n_seg), dim3(256), 0, s, ev_start, ev_stop, P, pass);
+    const bool order = uniform_last_pass(P, pass + 1);      // the shade launch behind the next trace launch reads it
+    const auto k = pass == 0 ? (order ? k_scan<true, true> : k_scan<true, false>) : (order ? k_scan<false, true> : k_scan<false, false>);
+    launch_k(k, dim3(P.n_seg), dim3(256), 0, s, ev_start, ev_stop, P, pass);
 }
 
 void launch_column(const Params& P, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop)
