@@ -483,6 +483,26 @@ int rr_debug_fresnel(rr_ctx* ctx, size_t n, const float* normals /*[n][3]*/, con
  * independent inputs, in5 = [n][5] (incidence angle, energy, ambient, diffuse, specular); brdf_model as in rr_config.  Tests compare
  * it with the oracle on the cases of tests/golden/pyref_brdf.npy (outputs of the reference's scripts/radarays_snell_fresnel_brdf.py). */
 int rr_debug_brdf(rr_ctx* ctx, size_t n, const float* in5 /*[n][5]*/, int brdf_model, float* out /*[n]*/);
+/* Test hook: k_column -- one azimuth's ordered echoes -> its range-bin column (RadarCPU.cpp:402-542) -- on echo streams given by
+ * the caller, through the launcher the frame path uses (so a launch of >= 1024 segments runs the 256-thread form, a smaller one
+ * the 512-thread form).  Needs rr_set_config only (no mesh): the denoiser, noise mode, scroll, n_cells, n_angles and the scale
+ * factors are the config's, the noise offsets rr_set_noise_offsets'.  The streams of n_seg = n_frames * n_loc segments (segment
+ * s = frame s / n_loc, azimuth az_begin + s % n_loc) go into the buffers of one frame lane, sized as for a frame by the
+ * config and rr_set_beam_samples (wave capacity: max_waves_per_azimuth or n_samples * 2^(n_reflections - 1); signal capacity:
+ * the sum of the passes' wave bounds, twice that with record_multi_path), in the two forms the kernel reads:
+ *   list  [n_seg][list_stride], list_count [n_seg]: the compacted echoes of passes 0 .. n_passes - 2 (read when n_passes > 1)
+ *   slots [n_seg][2 * slot_stride]: the last pass' per-wave slots, wave j = records 2j (path echo) and 2j + 1 (multipath echo),
+ *         cell < 0 = empty; slot_hit [n_seg][slot_stride]: wave j hit; slot_count [n_seg]: waves of the last pass (n_passes > 1;
+ *         with n_passes == 1 every segment has n_beam).  Without record_multi_path the kernel stages the even records only.
+ * An echo with cell >= n_cells is dropped by the kernel like an empty one.  Out: out_u8 [n_seg][n_cells], out_f32 the same or NULL,
+ * out_stats [n_seg][3] = the last pass' wave_passes, hits, signals, or NULL.  -3 (nothing written) for anything the lane's buffers
+ * cannot hold: n_passes > max(1, n_reflections), n_beam or slot_stride above the wave capacity, list_stride above the signal
+ * capacity, a count above its stride, an azimuth block outside the image.  Tests compare it with the oracle's column step. */
+typedef struct rr_echo { int32_t cell; float strength; } rr_echo;
+int rr_debug_column(rr_ctx* ctx, int n_frames, int n_loc, int az_begin, int n_passes, int n_beam, int record_multi_path,
+                    const rr_echo* list, const uint32_t* list_count, size_t list_stride,
+                    const rr_echo* slots, const uint8_t* slot_hit, const uint32_t* slot_count, size_t slot_stride,
+                    float* out_f32, uint8_t* out_u8, uint32_t* out_stats /*[n_seg][3]*/);
 int rr_get_bvh_info(rr_ctx* ctx, uint64_t* n_nodes, uint64_t* n_tris, uint32_t* depth, uint32_t* stack_need);
 /* How the later-pass trace launches are sized (round 5).  A segment holds at most n_beam * 2^pass waves in pass `pass`;
  * instead of a row of 16-ray workgroups up to that bound per segment, a row is as long as earlier batches of this context

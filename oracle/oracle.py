@@ -110,6 +110,9 @@ def lib():
     L.orc_cone_radius.restype = C.c_float
     L.orc_cone_radius.argtypes = [C.c_float, C.c_int, C.c_float, C.c_float]
     L.orc_set_uniform_stream.argtypes = [C.c_void_p, C.c_size_t]
+    L.orc_column.restype = C.c_int
+    L.orc_column.argtypes = [C.POINTER(OrcConfig), C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_int, C.c_void_p, C.c_void_p]
+    L.orc_set_echo_log.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.orc_saturate_u8.restype = C.c_uint8
     L.orc_saturate_u8.argtypes = [C.c_float]
     _LIB = L
@@ -332,11 +335,29 @@ class Scene:
         return t.value, tri.value, np.array(ng[:], np.float32)
 
 
+def column(cfg, cells, strengths, noise_offset=0.0, col=0, n_angles=400):
+    """orc_column: the column step alone (RadarCPU.cpp:402-542) on one azimuth's ordered echoes (cell, strength).
+    cfg: a RadarModelConfig-like object or an OrcConfig.  Returns (f32 [n_cells], u8 [n_cells])."""
+    oc = cfg if isinstance(cfg, OrcConfig) else make_config(cfg, n_angles)
+    ce = np.ascontiguousarray(cells, np.int32).ravel()
+    st = np.ascontiguousarray(strengths, np.float32).ravel()
+    assert ce.size == st.size
+    f32 = np.zeros(oc.n_cells, np.float32)
+    u8 = np.zeros(oc.n_cells, np.uint8)
+    rc = lib().orc_column(C.byref(oc), ce.ctypes.data, st.ctypes.data, ce.size, float(np.float32(noise_offset)), int(col),
+                          f32.ctypes.data, u8.ctypes.data)
+    if rc != 0:
+        raise RuntimeError("orc_column failed: %d" % rc)
+    return f32, u8
+
+
 def simulate(scene, materials, object_materials, cfg, beam_dirs, pose, noise_rnd=None,
              az_begin=0, az_end=None, n_angles=400, material_id_air=0, want_f32=True,
-             n_threads=0, brdf_model=0, uniform_stream=None):
+             n_threads=0, brdf_model=0, uniform_stream=None, echo_log=None):
     """RadarCPU::simulate on the oracle. materials: [(velocity, ambient, diffuse, specular)].
-    Returns (u8 [n_cells][n_angles], f32 or None, stats dict)."""
+    Returns (u8 [n_cells][n_angles], f32 or None, stats dict).
+    echo_log: a dict; it receives "cells" / "strengths" [n_angles][cap] and "counts" [n_angles], every simulated azimuth's
+    ordered echo stream as orc_column takes it (cap = echo_log.get("cap", 4096) echoes per azimuth are kept)."""
     L = lib()
     oc = make_config(cfg, n_angles, material_id_air, brdf_model=brdf_model)
     if az_end is None:
@@ -354,11 +375,19 @@ def simulate(scene, materials, object_materials, cfg, beam_dirs, pose, noise_rnd
     us = None if uniform_stream is None else np.ascontiguousarray(uniform_stream, np.float32).ravel()
     if us is not None:                  # ambient_noise == 1 with a caller's variates [n_angles][n_cells] (test hook)
         L.orc_set_uniform_stream(us.ctypes.data, len(us))
+    if echo_log is not None:
+        cap = int(echo_log.get("cap", 4096))
+        echo_log["cells"] = np.full((n_angles, cap), -1, np.int32)
+        echo_log["strengths"] = np.zeros((n_angles, cap), np.float32)
+        echo_log["counts"] = np.zeros(n_angles, np.uint32)
+        L.orc_set_echo_log(echo_log["cells"].ctypes.data, echo_log["strengths"].ctypes.data, echo_log["counts"].ctypes.data, cap)
     try:
         rc = _run_simulate(L, motion, scene, mats, materials, om, oc, bd, ps, nr, az_begin, az_end, u8, f32, n_threads, st)
     finally:
         if us is not None:
             L.orc_set_uniform_stream(None, 0)
+        if echo_log is not None:
+            L.orc_set_echo_log(None, None, None, 0)
     if rc != 0:
         raise RuntimeError("orc_simulate failed: %d" % rc)
     stats = {k: getattr(st, k) for k, _ in OrcStats._fields_}

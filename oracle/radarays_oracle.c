@@ -796,6 +796,132 @@ void orc_set_uniform_stream(const float* stream, size_t n)
     g_uniform_stream_n = stream ? n : 0;
 }
 
+/* test hook (tests/test_column_host.py): when set, every azimuth a simulate call runs writes its ordered echo stream --
+ * what its column is made from -- to cells / strengths [n_angles][cap] (the first cap echoes) and counts[n_angles] (all of
+ * them).  Not thread-safe against a running orc_simulate; set, simulate, clear. */
+static int32_t* g_echo_cells = NULL;
+static float* g_echo_strengths = NULL;
+static uint32_t* g_echo_counts = NULL;
+static size_t g_echo_cap = 0;
+void orc_set_echo_log(int32_t* cells, float* strengths, uint32_t* counts, size_t cap)
+{
+    const int on = cells && strengths && counts;
+    g_echo_cells = on ? cells : NULL; g_echo_strengths = on ? strengths : NULL; g_echo_counts = on ? counts : NULL;
+    g_echo_cap = on ? cap : 0;
+}
+
+/* RadarCPU.cpp:402-542 for ONE azimuth: its ordered echoes (cell of :413, strength) -> slice -> noise -> scale -> mono8.
+ * w[wn] / mode: the smear kernel of :48-93 (wn = 0 without denoising).  slice[n_cells] is left holding the float column
+ * before convertTo; out_u8 may be NULL.  uniform[k], k < uniform_n: the caller's variates for ambient_noise == 1
+ * (orc_set_uniform_stream), else the build's hash stream.
+ * An echo with cell < 0 is no echo: the stream's mark for an empty slot.  The reference has no such test on its smear path
+ * (:414 only asks cell < n_cells), but the only negative cell its conversion at :413 can give -- time is never negative -- is
+ * INT_MIN from a distance that is NaN or beyond int, and a window that starts there lies outside the image. */
+static void column_of(const orc_config* cfg, const float* w, int wn, int mode,
+                      const int32_t* cells, const float* strengths, size_t n,
+                      float rnd, int col, const float* uniform, size_t uniform_n,
+                      float* slice, uint8_t* out_u8)
+{
+    const int n_cells = cfg->n_cells;
+    /* :402-450 signals -> slice */
+    memset(slice, 0, (size_t)n_cells * sizeof(float));
+    float max_val = 0.0f;
+    for (size_t i = 0; i < n; i++)
+    {
+        const int cell = cells[i];
+        const double strength = (double)strengths[i];
+        if (cell >= 0 && cell < n_cells)
+        {
+            if (cfg->signal_denoising > 0) {
+                for (int vid = 0; vid < wn; vid++) {
+                    int glob_id = vid + cell - mode;
+                    if (glob_id > 0 && glob_id < n_cells) {   /* :424 */
+                        slice[glob_id] = (float)((double)slice[glob_id] + strength * (double)w[vid]);
+                        if (slice[glob_id] > max_val) max_val = slice[glob_id];
+                    }
+                }
+            } else {
+                slice[cell] = fmaxf(slice[cell], (float)strength);   /* :439 */
+                if (slice[cell] > max_val) max_val = slice[cell];
+            }
+        }
+    }
+
+    /* :453  slice *= energy_max  (cv convertTo: x * (float)alpha) */
+    {
+        const float a = (float)cfg->energy_max;
+        for (int i = 0; i < n_cells; i++) slice[i] = slice[i] * a;
+    }
+
+    if (cfg->ambient_noise)   /* :459-528 */
+    {
+        const double scale = 0.05, scale2 = 0.2;
+        const double random_begin = (double)rnd;   /* :472 (dist_uni(gen) * 1000.0, injected) */
+        for (int i = 0; i < n_cells; i++)
+        {
+            float signal = slice[i];
+            double p = 0.0;
+            if (cfg->ambient_noise == 1) {
+                p = (size_t)i < uniform_n ? (double)uniform[i]
+                                          : (double)uniform01((uint32_t)(int32_t)rnd, (uint32_t)col, (uint32_t)i);
+            } else if (cfg->ambient_noise == 2) {
+                double p1 = orc_perlin_noise(random_begin + (double)i * scale, (double)col * scale, 0.0);
+                double p2 = orc_perlin_noise(random_begin + (double)i * scale2, (double)col * scale2, 0.0);
+                p = 0.9 * p1 + 0.1 * p2;
+            }
+            float signal_max = max_val;
+            float noise_amp = orc_noise_amplitude(signal, max_val, cfg->ambient_noise_at_signal_0, cfg->ambient_noise_at_signal_1);
+            float noise_energy_max = (float)((double)signal_max * cfg->ambient_noise_energy_max);
+            float noise_energy_min = (float)((double)signal_max * cfg->ambient_noise_energy_min);
+            float energy_loss = (float)cfg->ambient_noise_energy_loss;
+            float y_noise = (float)((double)noise_amp * p);
+            float x = (float)(((double)(float)i + 0.5) * cfg->resolution);
+            y_noise = y_noise + (noise_energy_max - noise_energy_min) * expf(-energy_loss * x) + noise_energy_min;
+            y_noise = fabsf(y_noise);
+            slice[i] = signal + y_noise;
+        }
+    }
+
+    /* :533  slice *= signal_max / max_val */
+    {
+        const float a = (float)(cfg->signal_max / (double)max_val);
+        for (int i = 0; i < n_cells; i++) slice[i] = slice[i] * a;
+    }
+
+    /* :542  convertTo(col, CV_8UC1) */
+    if (out_u8) for (int i = 0; i < n_cells; i++) out_u8[i] = orc_saturate_u8(slice[i]);
+}
+
+/* RadarCPU.cpp:48-93: the smear kernel of the config (NULL, *wn = 0 without denoising); the caller frees it */
+static float* smear_of(const orc_config* cfg, int* wn, int* mode)
+{
+    float* w = NULL; *wn = 0; *mode = 0;
+    if (cfg->signal_denoising > 0) {
+        int width = 0; double mfrac = 0.0;
+        if (cfg->signal_denoising == 1) { width = cfg->signal_denoising_triangular_width; mfrac = cfg->signal_denoising_triangular_mode; }
+        else if (cfg->signal_denoising == 2) { width = cfg->signal_denoising_gaussian_width; mfrac = cfg->signal_denoising_gaussian_mode; }
+        else if (cfg->signal_denoising == 3) { width = cfg->signal_denoising_mb_width; mfrac = cfg->signal_denoising_mb_mode; }
+        if (width > 0) {
+            *mode = (int)(mfrac * width);   /* :57 */
+            w = (float*)malloc(sizeof(float) * (size_t)width);
+            orc_make_denoiser(cfg->signal_denoising, width, *mode, 1, w);
+            *wn = width;
+        }
+    }
+    return w;
+}
+
+int orc_column(const orc_config* cfg, const int32_t* cells, const float* strengths, size_t n,
+               float noise_offset, int col, float* out_f32, uint8_t* out_u8)
+{
+    if (!cfg || cfg->n_cells < 1 || !out_f32 || (n && (!cells || !strengths))) return -1;
+    int wn, mode;
+    float* w = smear_of(cfg, &wn, &mode);
+    column_of(cfg, w, wn, mode, cells, strengths, n, noise_offset, col, NULL, 0, out_f32, out_u8);
+    free(w);
+    return 0;
+}
+
 static double now_s(void)
 {
     struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts);
@@ -818,19 +944,8 @@ static int simulate_impl(const orc_scene* scene,
     if (az_begin < 0 || az_end > n_angles || az_begin > az_end) return -2;
 
     /* RadarCPU.cpp:48-93: smear kernel */
-    float* w = NULL; int wn = 0, mode = 0;
-    if (cfg->signal_denoising > 0) {
-        int width = 0; double mfrac = 0.0;
-        if (cfg->signal_denoising == 1) { width = cfg->signal_denoising_triangular_width; mfrac = cfg->signal_denoising_triangular_mode; }
-        else if (cfg->signal_denoising == 2) { width = cfg->signal_denoising_gaussian_width; mfrac = cfg->signal_denoising_gaussian_mode; }
-        else if (cfg->signal_denoising == 3) { width = cfg->signal_denoising_mb_width; mfrac = cfg->signal_denoising_mb_mode; }
-        if (width > 0) {
-            mode = (int)(mfrac * width);   /* :57 */
-            w = (float*)malloc(sizeof(float) * (size_t)width);
-            orc_make_denoiser(cfg->signal_denoising, width, mode, 1, w);
-            wn = width;
-        }
-    }
+    int wn = 0, mode = 0;
+    float* w = smear_of(cfg, &wn, &mode);
 
     const float thr = cfg->wave_energy_threshold;
 
@@ -867,6 +982,7 @@ static int simulate_impl(const orc_scene* scene,
     wave_vec waves = { 0 }, waves_new = { 0 };
     sig_vec signals = { 0 };
     float* slice = (float*)malloc((size_t)n_cells * sizeof(float) + 4);
+    int32_t* echo_cell = NULL; float* echo_str = NULL; size_t echo_cap = 0;
     #pragma omp for schedule(dynamic, 1)
     for (int angle_id = az_begin; angle_id < az_end; angle_id++)    /* :155-156 */
     {
@@ -1000,89 +1116,41 @@ static int simulate_impl(const orc_scene* scene,
             wave_vec tmp = waves; waves = waves_new; waves_new = tmp;   /* :380 */
         }
 
-        /* :402-450 signals -> slice */
-        memset(slice, 0, (size_t)n_cells * sizeof(float));
-        float max_val = 0.0f;
+        /* :402-542 signals -> slice -> column: orc_column's loop (column_of), on the azimuth's echoes as (cell, strength) */
+        if (signals.n > echo_cap) {
+            echo_cap = signals.n * 2;
+            echo_cell = (int32_t*)realloc(echo_cell, echo_cap * sizeof(int32_t));
+            echo_str = (float*)realloc(echo_str, echo_cap * sizeof(float));
+        }
         for (size_t i = 0; i < signals.n; i++)
         {
             const signal_t signal = signals.p[i];
             float half_time = (float)(signal.time / 2.0);       /* :410 */
             float signal_dist = (float)(0.3 * (double)half_time); /* :411 */
-            int cell = (int)((double)signal_dist / cfg->resolution);   /* :413 */
-            if (cell < n_cells)
-            {
-                if (cfg->signal_denoising > 0) {
-                    for (int vid = 0; vid < wn; vid++) {
-                        int glob_id = vid + cell - mode;
-                        if (glob_id > 0 && glob_id < n_cells) {   /* :424 */
-                            slice[glob_id] = (float)((double)slice[glob_id] + signal.strength * (double)w[vid]);
-                            if (slice[glob_id] > max_val) max_val = slice[glob_id];
-                        }
-                    }
-                } else if (cell >= 0) {
-                    slice[cell] = fmaxf(slice[cell], (float)signal.strength);   /* :439 */
-                    if (slice[cell] > max_val) max_val = slice[cell];
-                }
-            }
+            echo_cell[i] = (int)((double)signal_dist / cfg->resolution);   /* :413 */
+            echo_str[i] = (float)signal.strength;               /* (the shader's float, widened at :316 / :347: exact) */
         }
         tot_sig += signals.n;
-
-        /* :453  slice *= energy_max  (cv convertTo: x * (float)alpha) */
-        {
-            const float a = (float)cfg->energy_max;
-            for (int i = 0; i < n_cells; i++) slice[i] = slice[i] * a;
-        }
-
-        const int col = (cfg->scroll_image + angle_id) % n_angles;   /* :457 */
-
-        if (cfg->ambient_noise)   /* :459-528 */
-        {
-            const double scale = 0.05, scale2 = 0.2;
-            const float rnd = noise_rnd ? noise_rnd[angle_id] : 0.0f;
-            const double random_begin = (double)rnd;   /* :472 (dist_uni(gen) * 1000.0, injected) */
-            for (int i = 0; i < n_cells; i++)
-            {
-                float signal = slice[i];
-                double p = 0.0;
-                if (cfg->ambient_noise == 1) {
-                    const size_t k = (size_t)angle_id * (size_t)n_cells + (size_t)i;
-                    p = k < g_uniform_stream_n ? (double)g_uniform_stream[k]
-                                               : (double)uniform01((uint32_t)(int32_t)rnd, (uint32_t)col, (uint32_t)i);
-                } else if (cfg->ambient_noise == 2) {
-                    double p1 = orc_perlin_noise(random_begin + (double)i * scale, (double)col * scale, 0.0);
-                    double p2 = orc_perlin_noise(random_begin + (double)i * scale2, (double)col * scale2, 0.0);
-                    p = 0.9 * p1 + 0.1 * p2;
-                }
-                float signal_max = max_val;
-                float noise_amp = orc_noise_amplitude(signal, max_val, cfg->ambient_noise_at_signal_0, cfg->ambient_noise_at_signal_1);
-                float noise_energy_max = (float)((double)signal_max * cfg->ambient_noise_energy_max);
-                float noise_energy_min = (float)((double)signal_max * cfg->ambient_noise_energy_min);
-                float energy_loss = (float)cfg->ambient_noise_energy_loss;
-                float y_noise = (float)((double)noise_amp * p);
-                float x = (float)(((double)(float)i + 0.5) * cfg->resolution);
-                y_noise = y_noise + (noise_energy_max - noise_energy_min) * expf(-energy_loss * x) + noise_energy_min;
-                y_noise = fabsf(y_noise);
-                slice[i] = signal + y_noise;
+        if (g_echo_counts) {   /* test hook: the azimuth's echo stream as orc_column takes it */
+            g_echo_counts[angle_id] = (uint32_t)signals.n;
+            for (size_t i = 0; i < signals.n && i < g_echo_cap; i++) {
+                g_echo_cells[(size_t)angle_id * g_echo_cap + i] = echo_cell[i];
+                g_echo_strengths[(size_t)angle_id * g_echo_cap + i] = echo_str[i];
             }
         }
-
-        /* :533  slice *= signal_max / max_val */
         {
-            const float a = (float)(cfg->signal_max / (double)max_val);
-            for (int i = 0; i < n_cells; i++) slice[i] = slice[i] * a;
-        }
-
-        /* :542  convertTo(col, CV_8UC1) */
-        {
+            const int col = (cfg->scroll_image + angle_id) % n_angles;   /* :457 */
             const size_t cb = (size_t)(angle_id - az_begin) * (size_t)n_cells;
-            (void)col;
-            if (cols_u8) for (int i = 0; i < n_cells; i++) cols_u8[cb + i] = orc_saturate_u8(slice[i]);
+            const size_t k0 = (size_t)angle_id * (size_t)n_cells;
+            column_of(cfg, w, wn, mode, echo_cell, echo_str, signals.n, noise_rnd ? noise_rnd[angle_id] : 0.0f, col,
+                      k0 < g_uniform_stream_n ? g_uniform_stream + k0 : NULL, k0 < g_uniform_stream_n ? g_uniform_stream_n - k0 : 0,
+                      slice, cols_u8 ? cols_u8 + cb : NULL);
             if (cols_f32) memcpy(cols_f32 + cb, slice, (size_t)n_cells * sizeof(float));
         }
 
         tot_nodes += st.nodes; tot_tris += st.tris;
     }
-    free(slice); free(waves.p); free(waves_new.p); free(signals.p);
+    free(slice); free(waves.p); free(waves_new.p); free(signals.p); free(echo_cell); free(echo_str);
     }
     /* :457,542  column `col` of the image, all azimuths at once (rows of the image in parallel) */
     #pragma omp parallel for schedule(static) num_threads(n_threads)

@@ -136,6 +136,21 @@ int orc_simulate_motion(const orc_scene*,
  * hash stream).  Not thread-safe against a running orc_simulate; set, simulate, clear. */
 void orc_set_uniform_stream(const float* stream, size_t n);
 
+/* The column step of RadarCPU::simulate alone (RadarCPU.cpp:402-542) -- the loop orc_simulate itself runs per azimuth: one
+ * azimuth's ordered echoes -> slice accumulation with the config's denoiser (or the fmaxf path), running maximum,
+ * energy_max, ambient noise 0/1/2, signal_max / max, cvRound with saturation.
+ *   cells / strengths : [n] the echoes in the loop's order: range bin (:413) and strength; an echo with cell < 0 or
+ *                       cell >= n_cells is dropped (cell < 0 marks an empty slot of a stream)
+ *   noise_offset      : the azimuth's `random_begin` (:472);  col : its image column (scroll_image + azimuth) % n_angles (:457)
+ *   out_f32           : [n_cells] the float column before convertTo;  out_u8 : [n_cells] or NULL */
+int orc_column(const orc_config* cfg, const int32_t* cells, const float* strengths, size_t n,
+               float noise_offset, int col, float* out_f32, uint8_t* out_u8);
+
+/* test hook: while set, every azimuth a of an orc_simulate / orc_simulate_motion call logs its echo stream, as orc_column
+ * takes it: counts[a] = its number of echoes, cells / strengths [a * cap + k] = the first cap of them.  Arrays of n_angles
+ * rows; NULL clears.  Not thread-safe against a running orc_simulate; set, simulate, clear. */
+void orc_set_echo_log(int32_t* cells, float* strengths, uint32_t* counts, size_t cap);
+
 /* ---- per-hit math, exported one by one for the known-answer tests ---- */
 
 /* radar_algorithms.h:55-139.  in: normal, incidence dir, energy, polarization,

@@ -4,6 +4,7 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <vector>
 
 extern "C" {
 
@@ -155,6 +156,86 @@ int rr_debug_brdf(rr_ctx* c, size_t n, const float* in5, int brdf_model, float* 
     RR_HIP(c, hipGetLastError());
     RR_HIP(c, hipStreamSynchronize(c->stream));
     RR_HIP(c, hipMemcpy(out, d_out.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int rr_debug_column(rr_ctx* c, int n_frames, int n_loc, int az_begin, int n_passes, int n_beam, int record_multi_path,
+                    const rr_echo* list, const uint32_t* list_count, size_t list_stride,
+                    const rr_echo* slots, const uint8_t* slot_hit, const uint32_t* slot_count, size_t slot_stride,
+                    float* out_f32, uint8_t* out_u8, uint32_t* out_stats)
+{
+    static_assert(sizeof(rr_echo) == sizeof(SigRec) && sizeof(SegStats) == 16, "rr_debug_column copies records as they lie");
+    if (!c) return -1;
+    if (!c->have_cfg) return fail(c, -2, "rr_set_config has not been called");
+    const rr_config& g = c->cfg;
+    if (n_frames < 1 || n_frames > RR_MAX_BATCH) return fail(c, -3, "rr_debug_column: n_frames must be 1..64");
+    if (n_loc < 1 || az_begin < 0 || az_begin > g.n_angles - n_loc) return fail(c, -3, "rr_debug_column: azimuth block out of bounds");
+    if (n_passes < 1 || n_passes > std::max(1, g.n_reflections))
+        return fail(c, -3, "rr_debug_column: n_passes must be in [1, max(1, n_reflections)]: the lane's buffers are sized by the config");
+    if (n_beam < 0) return fail(c, -3, "rr_debug_column: negative n_beam");
+    if (!out_u8) return fail(c, -3, "rr_debug_column: null output");
+    const bool use_list = n_passes > 1 && list_stride > 0, use_slots = slot_stride > 0;
+    if ((use_list && (!list || !list_count)) || (use_slots && (!slots || !slot_hit)) || (use_slots && n_passes > 1 && !slot_count))
+        return fail(c, -3, "rr_debug_column: null stream");
+    RR_HIP(c, hipSetDevice(c->device));
+    int rc = upload_tables(c); if (rc) return rc;
+    const int n_seg = n_frames * n_loc;
+    const size_t S = (size_t)n_seg;
+    Lane& L = c->lanes[0];
+    rc = take_lane(c, 0, c->stream); if (rc) return rc;
+    rc = prepare_lane(c, L, n_seg, true); if (rc) return rc;
+    // what the lane's buffers cannot hold is refused before anything is written
+    const size_t cap = (size_t)L.buf_cap, sigcap = (size_t)L.buf_sigcap;
+    if ((size_t)n_beam > cap) return fail(c, -3, "rr_debug_column: n_beam exceeds the lane's wave capacity");
+    if (use_list && list_stride > sigcap) return fail(c, -3, "rr_debug_column: list_stride exceeds the lane's signal capacity");
+    if (use_slots && slot_stride > cap) return fail(c, -3, "rr_debug_column: slot_stride exceeds the lane's wave capacity");
+    if (n_passes == 1 && (size_t)n_beam > slot_stride) return fail(c, -3, "rr_debug_column: one pass stages n_beam waves per segment, more than slot_stride");
+    for (size_t s = 0; s < S; s++) {
+        if (n_passes > 1 && list_count && list_count[s] > list_stride) return fail(c, -3, "rr_debug_column: a list count exceeds list_stride");
+        if (n_passes > 1 && slot_count && slot_count[s] > slot_stride) return fail(c, -3, "rr_debug_column: a slot count exceeds slot_stride");
+    }
+    // the two stream forms as the frame path leaves them: sig / sig_count, and sigtmp / cflag bit 2 / count of the last pass
+    hipStream_t st = c->stream;
+    std::vector<uint32_t> zeros(S, 0u);
+    const int last = (n_passes - 1) & 1;
+    RR_HIP(c, hipMemcpyAsync(L.d_sig_count.p, use_list ? list_count : zeros.data(), S * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    RR_HIP(c, hipMemcpyAsync(L.d_count[last].p, (use_slots && n_passes > 1) ? slot_count : zeros.data(), S * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    if (use_list)
+        RR_HIP(c, hipMemcpy2DAsync(L.d_sig.p, sigcap * sizeof(SigRec), list, list_stride * sizeof(rr_echo), list_stride * sizeof(rr_echo), S, hipMemcpyHostToDevice, st));
+    std::vector<uint8_t> flags;
+    if (use_slots) {
+        RR_HIP(c, hipMemcpy2DAsync(L.d_sigtmp.p, 2 * cap * sizeof(SigRec), slots, 2 * slot_stride * sizeof(rr_echo), 2 * slot_stride * sizeof(rr_echo), S,
+                                   hipMemcpyHostToDevice, st));
+        flags.assign(S * 2 * slot_stride, 0);
+        for (size_t k = 0; k < S * slot_stride; k++) flags[2 * k] = slot_hit[k] ? 4 : 0;      // bit 2, even slot
+        RR_HIP(c, hipMemcpy2DAsync(L.d_cflag.p, 2 * cap, flags.data(), 2 * slot_stride, 2 * slot_stride, S, hipMemcpyHostToDevice, st));
+    }
+    Params P; std::memset(&P, 0, sizeof(P));
+    P.smear = c->d_smear.p; P.signal_denoising = c->smear.empty() ? 0 : g.signal_denoising;
+    P.smear_w = (int)c->smear.size(); P.smear_mode = c->smear_mode;
+    P.noise_rnd = g.ambient_noise ? c->d_noise.p : nullptr; P.noise_rows = c->noise_rows; P.decay = c->d_decay.p;
+    P.count[0] = L.d_count[0].p; P.count[1] = L.d_count[1].p;
+    P.cflag = L.d_cflag.p; P.sigtmp = L.d_sigtmp.p; P.sig = L.d_sig.p; P.sig_count = L.d_sig_count.p; P.seg_stats = L.d_seg_stats.p;
+    P.cols_u8 = L.d_cols_u8.p; P.cols_f32 = L.d_cols_f32.p;
+    P.az_begin = az_begin; P.n_seg = n_seg; P.n_loc = n_loc; P.n_frames = n_frames;
+    P.n_beam = n_beam; P.cap = L.buf_cap; P.sigcap = L.buf_sigcap;
+    P.n_cells = g.n_cells; P.n_angles = g.n_angles;
+    P.n_passes = n_passes; P.record_multi_path = record_multi_path != 0;
+    P.ambient_noise = g.ambient_noise; P.scroll = g.scroll_image;
+    P.resolution = g.resolution; P.energy_max_f = (float)g.energy_max; P.signal_max = g.signal_max;
+    P.noise_at_0 = g.ambient_noise_at_signal_0; P.noise_at_1 = g.ambient_noise_at_signal_1;
+    P.noise_e_max = g.ambient_noise_energy_max; P.noise_e_min = g.ambient_noise_energy_min; P.noise_e_loss = g.ambient_noise_energy_loss;
+    L.last_n_seg = 0; L.last_n_passes = 0;       // (no frame: rr_get_stats has nothing to add up on this lane)
+    launch_column(P, st);
+    RR_HIP(c, hipGetLastError());
+    const size_t px = S * (size_t)g.n_cells;
+    std::vector<SegStats> ss(out_stats ? S : 0);
+    RR_HIP(c, hipMemcpyAsync(out_u8, L.d_cols_u8.p, px, hipMemcpyDeviceToHost, st));
+    if (out_f32) RR_HIP(c, hipMemcpyAsync(out_f32, L.d_cols_f32.p, px * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (out_stats) RR_HIP(c, hipMemcpyAsync(ss.data(), L.d_seg_stats.p + (size_t)(n_passes - 1) * S, S * sizeof(SegStats), hipMemcpyDeviceToHost, st));
+    RR_HIP(c, give_lane(L, st));
+    RR_HIP(c, hipStreamSynchronize(st));
+    for (size_t s = 0; s < ss.size(); s++) { out_stats[3 * s] = ss[s].wave_passes; out_stats[3 * s + 1] = ss[s].hits; out_stats[3 * s + 2] = ss[s].signals; }
     return 0;
 }
 

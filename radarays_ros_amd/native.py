@@ -19,7 +19,7 @@ SYMBOLS = [
     "rr_set_noise_offsets", "rr_set_motion_poses", "rr_simulate", "rr_simulate_columns_device", "rr_simulate_batch_columns_device",
     "rr_assemble_image_device", "rr_assemble_blocks_device", "rr_assemble_frames_device", "rr_simulate_device",
     "rr_simulate_material_sets_device", "rr_simulate_material_sets", "rr_simulate_batch_device", "rr_synchronize", "rr_get_stats",
-    "rr_set_stats_mode", "rr_debug_trace", "rr_debug_fresnel", "rr_debug_brdf", "rr_get_bvh_info", "rr_get_trace_grid", "rr_get_graph_stats", "rr_set_timing_mode",
+    "rr_set_stats_mode", "rr_debug_trace", "rr_debug_fresnel", "rr_debug_brdf", "rr_debug_column", "rr_get_bvh_info", "rr_get_trace_grid", "rr_get_graph_stats", "rr_set_timing_mode",
     "rr_get_kernel_time", "rr_get_kernel_samples", "rr_reserve_timing_events",
     "rr_simulate_batch_host_async", "rr_wait_host", "rr_host_alloc", "rr_host_free", "rr_copy_to_host_async", "rr_deliver_to_host_async", "rr_host_delivery_route", "rr_partition", "rr_multi_plan",
     "rr_create_multi", "rr_destroy_multi", "rr_multi_last_error", "rr_multi_device_count", "rr_multi_rccl_version", "rr_multi_ctx",
@@ -87,6 +87,9 @@ class RRRadarPoint(C.Structure):
 class RRCartesianConfig(C.Structure):
     _fields_ = [("width", C.c_int32), ("interpolation", C.c_int32), ("pixel_size", C.c_float), ("reserved_", C.c_int32)]
 
+
+# rr_echo as numpy sees it (8 B): one record of an echo stream of rr_debug_column
+ECHO_DTYPE = np.dtype([("cell", "<i4"), ("strength", "<f4")])
 
 # rr_radar_point as numpy sees it (24 B: a PointCloud's point + its intensity channel, and where it came from)
 POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("intensity", "<f4"), ("column", "<u4"), ("bin", "<u4")])
@@ -278,6 +281,7 @@ def lib():
     L.rr_debug_trace.argtypes = [vp, vp, vp, C.c_size_t, vp, vp]
     L.rr_debug_fresnel.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.rr_debug_brdf.argtypes = [vp, C.c_size_t, vp, C.c_int, vp]
+    L.rr_debug_column.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp, vp, vp]
     L.rr_get_trace_grid.argtypes = [vp, vp, vp, C.POINTER(C.c_uint64)]
     L.rr_get_graph_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.rr_get_bvh_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
@@ -1142,6 +1146,37 @@ class Context:
         out = np.zeros(len(x), np.float32)
         self._ck(self._L.rr_debug_brdf(self._h, len(x), x.ctypes.data, int(brdf_model), out.ctypes.data))
         return out
+
+    def debug_column(self, n_frames, n_loc, az_begin=0, n_passes=1, n_beam=0, record_multi_path=False,
+                     echoes=None, echo_count=None, slots=None, slot_hit=None, slot_count=None):
+        """rr_debug_column: k_column on caller-given echo streams of n_seg = n_frames * n_loc segments, under the context's
+        config and noise offsets.  echoes [n_seg][list_stride] / echo_count [n_seg]: the compacted list (ECHO_DTYPE records);
+        slots [n_seg][2 * slot_stride] / slot_hit [n_seg][slot_stride] / slot_count [n_seg]: the last pass' per-wave slots.
+        Returns (f32 [n_seg][n_cells], u8 [n_seg][n_cells], stats [n_seg][3] = wave_passes, hits, signals of the last pass)."""
+        n_seg = int(n_frames) * int(n_loc)
+        n_cells = self.cfg.n_cells if self.cfg is not None else 1   # unconfigured: the library reports it
+        ls = ss = 0
+        e = ec = sl = sh = sc = None
+        if echoes is not None:
+            e = np.ascontiguousarray(echoes, ECHO_DTYPE).reshape(n_seg, -1)
+            ec = np.ascontiguousarray(echo_count, np.uint32).reshape(n_seg)
+            ls = e.shape[1]
+        if slots is not None:
+            sl = np.ascontiguousarray(slots, ECHO_DTYPE).reshape(n_seg, -1)
+            if sl.shape[1] % 2:
+                raise ValueError("slots must hold an even and an odd record per wave")
+            ss = sl.shape[1] // 2
+            sh = np.ascontiguousarray(slot_hit, np.uint8).reshape(n_seg, ss)
+            if slot_count is not None:
+                sc = np.ascontiguousarray(slot_count, np.uint32).reshape(n_seg)
+        f32 = np.zeros((max(n_seg, 0), n_cells), np.float32)
+        u8 = np.zeros((max(n_seg, 0), n_cells), np.uint8)
+        st = np.zeros((max(n_seg, 0), 3), np.uint32)
+        ptr = lambda a: None if a is None else a.ctypes.data   # noqa: E731
+        self._ck(self._L.rr_debug_column(self._h, int(n_frames), int(n_loc), int(az_begin), int(n_passes), int(n_beam),
+                                         int(bool(record_multi_path)), ptr(e), ptr(ec), ls, ptr(sl), ptr(sh), ptr(sc), ss,
+                                         f32.ctypes.data, u8.ctypes.data, st.ctypes.data))
+        return f32, u8, st
 
 
 class HostImages:
