@@ -524,7 +524,7 @@ int rr_get_graph_stats(rr_ctx* ctx, uint64_t* captures, uint64_t* replays);
  * reset!=0, measured with hipEvents on the launch stream when timing mode is
  * on; also returns the number of launches.  Used by bench.py for roofline. */
 int rr_set_timing_mode(rr_ctx* ctx, int enable /* 0 off, 1 every kernel, 2 k_trace only */);
-int rr_get_kernel_time(rr_ctx* ctx, const char* kernel /* "trace0"|"trace"|"trace_repair"|"shade"|"scan"|"column"|"assemble";
+int rr_get_kernel_time(rr_ctx* ctx, const char* kernel /* "trace0"|"trace"|"trace_repair"|"shade"|"scan"|"column"|"assemble"|"gather"|"label";
                                                             "trace" = the later-pass launches WITHOUT the k_trace_repair launch that
                                                             follows a tightened row, which is "trace_repair" */,
                        double* total_ms, uint64_t* launches, int reset);
@@ -534,6 +534,59 @@ int rr_get_kernel_time(rr_ctx* ctx, const char* kernel /* "trace0"|"trace"|"trac
 int rr_get_kernel_samples(rr_ctx* ctx, const char* kernel, float* out_ms, size_t capacity, size_t* n_out);
 /* pre-creates n timing events so that a timed region never calls hipEventCreate */
 int rr_reserve_timing_events(rr_ctx* ctx, size_t n);
+
+/* ---- echo provenance: per-echo face, object and pass; label images (rr_labels.hip) ------------------------------
+ * What a pixel is made of: which triangle and object produced a return, in which ray-cast pass (pass > 0: a multi-bounce
+ * ghost), and whether it is a multipath echo.  An opt-in variant of the pose-batch frame call returns, beside the usual image,
+ *   the echo stream: per azimuth the ordered list of echoes exactly as the column step consumes it (the reference's order: passes
+ *                    in sequence, waves in order, a wave's path echo before its multipath echo), every echo with the face it came
+ *                    from, that face's object id, the pass and the kind.  Echoes whose cell lies beyond the image are listed too
+ *                    (the column step drops them); echoes that were pruned or never emitted have no record
+ *   label images   : per pixel of the polar image the echo that contributes the largest single term to that range bin.
+ * info word of an echo = object id (bits 0..23) | pass << 24 (4 bits) | kind << 28 (0: path echo, 1: multipath echo); top bits 0.
+ * A ghost mask is `pass > 0`, a semantic mask is object -> material on the host.
+ * Definition of a label.  The reference has no such output: parity is UNPINNED and this is the build's own definition (a numpy
+ * restatement in tests/labels_ref.py checks the kernel bit for bit).  For one azimuth with ordered echoes e_0 .. e_{n-1}; W, mode
+ * and the f32 weights w[0..W) are exactly what the column step uses (signal_denoising == 0: W = 1, mode = 0, w[0] = 1):
+ *   echo k reaches bin g iff 0 <= cell_k < n_cells, 0 < g < n_cells and 0 <= g - (cell_k - mode) < W; bin 0 is never written
+ *        (RadarCPU.cpp:424)
+ *   its term is v = (float)((double)strength_k * (double)w[g - cell_k + mode]): the product is exact in f64, then one rounding
+ *   only a finite v > 0 takes part
+ *   the winner of bin g is the largest key (bits(v) << 32) | (0xFFFFFFFF - k): equal terms go to the echo that comes first
+ *   label[g] = info_k and face[g] = face_k of the winner; a bin nobody reaches gets RR_LABEL_NONE in both planes
+ * Ambient noise, energy_max and the final scale play no part: a labelled bin may still render 0, and a noisy bin may have no label.
+ * Limits.  n_cells <= RR_LABEL_MAX_CELLS (the label column is held as 64-bit keys in LDS: 64 KB; rr_set_config admits no more).  The info word holds object ids
+ * below 2^24 - 1 and passes below 16: a call on a mesh with 2^24 - 1 or more objects or a config with n_reflections > 16 (which
+ * rr_set_config does not admit either) is refused (-3).  Pose batches only: parameter batches share the hits of pass 0 between frames.  rr_set_motion_poses and
+ * rr_set_noise_offsets apply as in rr_simulate_batch_device.  The chain of a provenance call is issued kernel by kernel (never
+ * from a launch graph), the image is made by the same launches with the same arguments as rr_simulate_batch_device's: the same
+ * bytes.  The lane's provenance buffers (n_angles x n_frames lists of 16-byte records, two uint32 columns) are allocated by the
+ * first provenance call; plain batches never touch them.
+ * Refused with a message and nothing written: -2 without a config / mesh / materials / beam where the frame calls refuse, -3 for a
+ * null required buffer, n_frames outside 1..RR_MAX_BATCH, d_echoes without d_echo_counts, echo_stride == 0 with d_echoes,
+ * n_cells > RR_LABEL_MAX_CELLS, the object / pass limits above; rr_debug_labels also for a count above its stride. */
+typedef struct rr_echo_src { int32_t cell; float strength; uint32_t face; uint32_t info; } rr_echo_src;   /* 16 B */
+#define RR_LABEL_NONE 0xFFFFFFFFu
+#define RR_LABEL_MAX_CELLS 8192
+/* whole frames of n_frames (1..RR_MAX_BATCH) poses, asynchronous on `stream`, device buffers:
+ *   d_imgs_u8   [n][n_cells][n_angles]                      as rr_simulate_batch_device, same bytes
+ *   d_labels    uint32 [n][n_cells][n_angles] or NULL       info of the winning echo, image layout (scroll applied)
+ *   d_faces     uint32 [n][n_cells][n_angles] or NULL
+ *   d_echoes    rr_echo_src [n][n_angles][echo_stride] or NULL, indexed by AZIMUTH (not column), in the reference's order
+ *   d_echo_counts uint32 [n][n_angles] (required with d_echoes): the TRUE count; when it exceeds echo_stride the first
+ *               echo_stride echoes are written and nothing beyond them (the convention of rr_detect_device's offsets) */
+int rr_simulate_batch_provenance_device(rr_ctx* ctx, const float* poses, int n_frames, uint8_t* d_imgs_u8,
+                                        uint32_t* d_labels, uint32_t* d_faces, rr_echo_src* d_echoes, size_t echo_stride,
+                                        uint32_t* d_echo_counts, void* stream);
+/* one frame, host buffers, synchronous; any output may be NULL except out_u8 (out_echoes needs out_echo_counts).  Returns -7 / -8
+ * itself like rr_simulate. */
+int rr_simulate_provenance(rr_ctx* ctx, const float pose[7], uint8_t* out_u8, uint32_t* out_labels, uint32_t* out_faces,
+                           rr_echo_src* out_echoes, size_t echo_stride, uint32_t* out_echo_counts);
+/* Test hook, config only (no mesh), like rr_debug_column: the label kernel on caller-given streams of n_seg segments (segment s =
+ * azimuth az_begin + s; 1 <= n_seg, az_begin + n_seg <= n_angles), host arrays: echoes [n_seg][stride], counts [n_seg]; out columns
+ * [n_seg][n_cells], not assembled.  Denoiser and n_cells are the config's. */
+int rr_debug_labels(rr_ctx* ctx, int n_seg, int az_begin, const rr_echo_src* echoes, const uint32_t* counts, size_t stride,
+                    uint32_t* out_labels, uint32_t* out_faces);
 
 /* ---- radar point clouds and Cartesian images from polar images (rr_detect.hip) ----------------------------------
  * The reference's pipeline turns every simulated image into a point cloud with radar_tools/radar_img_to_pcl

@@ -153,6 +153,28 @@ public:
         } else if (rr_simulate(m_ctx, Tsm_last, 0, m_n_angles, msg->data.data(), nullptr, &m_stats)) return fail();
         return msg;
     }
+    // What the image is made of (rr_simulate_provenance, include/radarays_mi355.h), on device 0: the frame at the current Tsm and,
+    // per pixel, the info word (object | pass << 24 | kind << 28) and the face of the echo with the largest single term in that
+    // range bin (RR_LABEL_NONE: none); per azimuth its ordered echo stream, rows of `echo_stride` records (0: no stream), and the
+    // true counts.  A ghost mask is pass > 0, a semantic mask is object -> material.  Null on error (lastError()).
+    struct Provenance { ImagePtr image; std::vector<uint32_t> labels, faces, echo_counts; std::vector<rr_echo_src> echoes; size_t echo_stride = 0; };
+    std::shared_ptr<Provenance> simulateProvenance(double stamp, size_t echo_stride = 0)
+    {
+        if (!updateTsm()) {
+            std::cout << "Couldn't get Transform between sensor and map. Skipping..." << std::endl;
+            return {};
+        }
+        if (!push()) return {};
+        auto out = std::make_shared<Provenance>();
+        out->image = image(nullptr, stamp);
+        const size_t npx = (size_t)m_cfg.n_cells * m_n_angles;
+        out->labels.assign(npx, RR_LABEL_NONE); out->faces.assign(npx, RR_LABEL_NONE);
+        out->echo_counts.assign((size_t)m_n_angles, 0u);
+        out->echoes.resize((size_t)m_n_angles * echo_stride); out->echo_stride = echo_stride;
+        if (rr_simulate_provenance(m_ctx, Tsm_last, out->image->data.data(), out->labels.data(), out->faces.data(),
+                                   echo_stride ? out->echoes.data() : nullptr, echo_stride, out->echo_counts.data())) { fail(); return {}; }
+        return out;
+    }
     // Offline generation (the twin of integration/src/radarays_ros/RadarHIP.cpp: simulateBatch / simulateSweeps): one image
     // per pose [n][7], up to RR_MAX_BATCH poses per set of launches; with per-azimuth pose tables (include_motion,
     // RadarCPU.cpp:190-196) sweeps = [n][n_angles][7], one table per frame (rr_multi_set_motion_poses)

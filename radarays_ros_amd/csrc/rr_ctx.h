@@ -73,6 +73,13 @@ struct Lane {
     DevBuf<float> d_poses;       // [RR_MAX_BATCH][8]: Params::pose_table, written by the pass-0 trace launch of every chain
     unsigned short last_rows[kMaxPasses] = {};     // rows the lane's last batch was launched with (0: the bound)
 
+    // echo provenance (rr_labels.hip): per segment the list of tagged echoes [prov_seg][prov_cap] with its count, and the two label
+    // columns [prov_seg][prov_cells].  Allocated by the lane's first provenance call (ensure_prov_buffers); plain batches never touch them
+    DevBuf<EchoSrc> d_prov; DevBuf<uint32_t> d_prov_count, d_label_cols, d_face_cols;
+    int prov_seg = 0, prov_cap = 0, prov_cells = 0;
+    DevBuf<uint32_t> d_label_img, d_face_img;      // rr_simulate_provenance: the assembled planes on their way to the host
+    DevBuf<rr_echo_src> d_echo_out; DevBuf<uint32_t> d_echo_out_counts;      // ... and its exported echo stream
+
     hipStream_t stream = nullptr;
     hipEvent_t ev_ready = nullptr, ev_consumed = nullptr;
     bool pending_consume = false;
@@ -296,7 +303,8 @@ int settle_lane(rr_ctx* c, Lane& L, int slot = -1, const void* only_dst = nullpt
 int take_lane(rr_ctx* c, size_t li, hipStream_t s, int slot = -1);
 hipError_t give_lane(Lane& L, hipStream_t s);
 int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, uint8_t* d_cols_u8 /* null: the lane's own buffer */, float* d_cols_f32,
-              hipStream_t s, int n_frames = 1, const float4* d_matsets = nullptr, int mat_stride = 0, bool lane_f32 = false, const SetPlan* plan = nullptr);
+              hipStream_t s, int n_frames = 1, const float4* d_matsets = nullptr, int mat_stride = 0, bool lane_f32 = false, const SetPlan* plan = nullptr,
+              int provenance = 0 /* 1: the lane's echo lists are gathered; 2: and its label columns made */);
 int assemble_frames(rr_ctx* c, const Lane& L, uint8_t* dst, int n_frames, hipStream_t s);
 
 }  // namespace rr

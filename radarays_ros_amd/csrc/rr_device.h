@@ -74,6 +74,11 @@ struct WaveBuf {
 
 struct SigRec { int32_t cell; float strength; };
 
+// one echo and where it came from: rr_echo_src of the public header (16 B, one dwordx4 per record)
+struct alignas(16) EchoSrc { int32_t cell; float strength; uint32_t face; uint32_t info; };
+constexpr uint32_t kNoLabel = 0xFFFFFFFFu;   // RR_LABEL_NONE
+constexpr int kLabelMaxCells = 8192;         // k_label's column of 64-bit keys in LDS: 64 KB (RR_LABEL_MAX_CELLS)
+
 struct Counters {
     unsigned long long nodes, tris;   // stats mode only (atomics)
     unsigned long long wave_iters;    // sum over waves of traversal-loop iterations
@@ -187,6 +192,15 @@ struct Params {
     uint32_t* ovf_list;      // [n_passes][ovf_stride] segments whose count exceeds the tightened row of that pass
     int ovf_stride;
     unsigned short tight_groups[kMaxPasses];   // 16-ray workgroups per segment row of pass p; 0: the full doubling bound
+    // echo provenance (rr_labels.hip; null in every chain but rr_simulate_batch_provenance_device's): behind the k_shade launch of
+    // every pass k_echo_gather appends the pass' echoes, tagged with their face / object / pass / kind, to the segment's list --
+    // passes in sequence, slots in order: the order k_column consumes them in; behind k_column, k_label folds the list into the
+    // two label columns (label_cols null: the echo stream alone was asked for)
+    EchoSrc* prov;               // [n_seg][prov_cap]
+    uint32_t* prov_count;        // [n_seg] echoes so far: written by the gather launch of pass 0, advanced by the later ones
+    int prov_cap;
+    uint32_t* label_cols;        // [n_seg][n_cells] info of the winning echo, 0xFFFFFFFF: none
+    uint32_t* face_cols;         // [n_seg][n_cells] its face
 };
 
 struct PoseArgs { float p[64][7]; int n; };     // RR_MAX_BATCH poses by value: third argument of the pass-0 k_trace
@@ -196,6 +210,22 @@ template <> struct PosesOf<true> { using type = PoseArgs; };
 
 __host__ __device__ inline int passes_of(const Params& P, int frame) { return P.set_mode ? (int)P.frame_passes[frame] : P.n_passes; }
 __host__ __device__ inline int beam_base(const Params& P, int frame) { return P.set_mode ? (int)P.frame_beam[frame] * P.n_beam : 0; }
+
+// exclusive prefix sum of v over a 256-thread workgroup, in thread order, and the workgroup's total (k_scan's ordered compaction,
+// k_echo_gather's): two barriers, every thread of the workgroup calls it
+__device__ inline int block_excl_scan(int v, int& total, int* lds /*[8]*/)
+{
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    int x = v;
+    for (int off = 1; off < 64; off <<= 1) { const int y = __shfl_up(x, off); if (lane >= off) x += y; }
+    if (lane == 63) lds[wid] = x;
+    __syncthreads();
+    int pre = 0, tot = 0;
+    for (int w = 0; w < 4; w++) { const int s = lds[w]; if (w < wid) pre += s; tot += s; }
+    __syncthreads();
+    total = tot;
+    return pre + x - v;
+}
 
 static_assert(sizeof(Params) <= 4096, "Params is passed by value: HIP kernel arguments are limited to 4 KB");
 

@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <vector>
 
 namespace rr {
 namespace {
@@ -145,6 +146,30 @@ void fill_params(rr_ctx* c, Lane& L, Params& P, const float pose[7], int az_begi
     P.hist_host = (c->tight_grid && g.n_reflections > 1) ? L.h_hist : nullptr;              // the chain's k_column stores the history there (read without a fence by later batches)
 }
 
+// The lane's provenance buffers for its current frame buffers (after prepare_lane).  A segment's list holds at most the lane's signal
+// capacity (every pass' wave bound, twice that with record_multi_path) -- the list k_column reads -- plus the last pass' slot bound
+int ensure_prov_buffers(rr_ctx* c, Lane& L)
+{
+    const rr_config g = eff_config(c);
+    const int n_beam = (int)(c->beams.size() / 3);
+    const int last = std::max(0, g.n_reflections - 1);
+    const long last_bound = std::min<long>((long)L.buf_cap, last < 20 ? (long)n_beam << last : (long)L.buf_cap);
+    const int echo_cap = L.buf_sigcap + (int)last_bound * (g.record_multi_path ? 2 : 1);
+    if (L.d_prov.p && L.prov_seg >= L.buf_seg && L.prov_cap == echo_cap && L.prov_cells == L.buf_cells) return 0;
+    const size_t S = (size_t)L.buf_seg;
+    size_t free_b = 0, total_b = 0;
+    RR_HIP(c, hipMemGetInfo(&free_b, &total_b));
+    if (S * ((size_t)echo_cap * sizeof(EchoSrc) + (size_t)L.buf_cells * 8) > total_b / 2)
+        return fail(c, -6, "the echo lists of a provenance call need more than half of device memory; fewer frames per call or a lower max_waves_per_azimuth");
+    RR_HIP(c, hipDeviceSynchronize());      // a provenance chain in flight may still use the old buffers
+    RR_HIP(c, L.d_prov.ensure(S * (size_t)echo_cap));
+    RR_HIP(c, L.d_prov_count.ensure(S));
+    RR_HIP(c, L.d_label_cols.ensure(S * (size_t)L.buf_cells));
+    RR_HIP(c, L.d_face_cols.ensure(S * (size_t)L.buf_cells));
+    L.prov_seg = L.buf_seg; L.prov_cap = echo_cap; L.prov_cells = L.buf_cells;
+    return 0;
+}
+
 // device -> host on stream s: the library's own copy kernel (8 workgroups, all on XCD 0) when the destination is page-locked
 // (`visible`) and everything is 16-byte aligned, else hipMemcpyAsync (rr_copy_to_host_async in the header says why)
 int copy_out(rr_ctx* c, const void* d_src, void* h_dst, size_t bytes, bool visible, hipStream_t s)
@@ -237,9 +262,16 @@ int issue_chain(rr_ctx* c, const Params& Q, const PoseArgs& pa, const rr_config&
         }
         if (c->roctx) roctx_pop();
         { KernelEvents t(c, "shade"); launch_shade(Q, pass, s, t.a, t.b); }
+        if (Q.prov) { KernelEvents t(c, "gather"); launch_echo_gather(Q, pass, s, t.a, t.b); }
         if (pass < g.n_reflections - 1) { KernelEvents t(c, "scan"); launch_scan(Q, pass, s, t.a, t.b); }
     }
     { KernelEvents t(c, "column"); launch_column(Q, s, t.a, t.b); }
+    if (Q.label_cols) {
+        KernelEvents t(c, "label");
+        const bool den = Q.signal_denoising > 0;
+        launch_label(Q.prov, Q.prov_count, (size_t)Q.prov_cap, Q.n_seg, Q.n_cells, den ? Q.smear_w : 1, den ? Q.smear_mode : 0, den ? Q.smear : nullptr,
+                     Q.label_cols, Q.face_cols, s, t.a, t.b);
+    }
     return 0;
 }
 
@@ -363,6 +395,42 @@ int assemble_device(rr_ctx* c, const char* who, bool blocks, const uint8_t* d_co
     return 0;
 }
 
+// the refusals of the two provenance entry points (nothing is written)
+int check_provenance(rr_ctx* c, const char* who, const void* poses, int n_frames, const void* imgs, const void* echoes, size_t echo_stride,
+                     const void* counts)
+{
+    int rc = check_ready(c); if (rc) return rc;
+    const std::string w(who);
+    if (!poses || !imgs) return fail(c, -3, w + ": null poses/output");
+    if (n_frames < 1 || n_frames > RR_MAX_BATCH) return fail(c, -3, w + ": n_frames must be 1..64");
+    if (echoes && !counts) return fail(c, -3, w + ": an echo buffer needs a count buffer");
+    if (echoes && echo_stride == 0) return fail(c, -3, w + ": echo_stride must be positive");
+    if (c->cfg.n_cells > kLabelMaxCells) return fail(c, -3, w + ": n_cells exceeds RR_LABEL_MAX_CELLS (8192)");
+    if (c->n_objects >= 0xFFFFFFu) return fail(c, -3, w + ": the info word holds object ids below 2^24 - 1");
+    if (c->cfg.n_reflections > 16) return fail(c, -3, w + ": the info word holds passes below 16 (n_reflections <= 16)");
+    return 0;
+}
+
+// a pose batch with provenance on lane li (taken and handed back here), everything enqueued on s
+int provenance_batch(rr_ctx* c, size_t li, const float* poses, int n_frames, uint8_t* d_imgs_u8, uint32_t* d_labels, uint32_t* d_faces,
+                     rr_echo_src* d_echoes, size_t echo_stride, uint32_t* d_echo_counts, hipStream_t s)
+{
+    Lane& L = c->lanes[li];
+    const rr_config& g = c->cfg;
+    int rc = take_lane(c, li, s); if (rc) return rc;
+    rc = run_frame(c, L, poses, 0, g.n_angles, nullptr, nullptr, s, n_frames, nullptr, 0, false, nullptr, (d_labels || d_faces) ? 2 : 1);
+    if (rc) return rc;
+    rc = assemble_frames(c, L, d_imgs_u8, n_frames, s); if (rc) return rc;
+    { TimedScope t(c, s, "assemble");
+      if (d_labels) launch_assemble_u32(L.d_label_cols.p, d_labels, g.n_angles, g.n_cells, g.scroll_image, s, n_frames);
+      if (d_faces) launch_assemble_u32(L.d_face_cols.p, d_faces, g.n_angles, g.n_cells, g.scroll_image, s, n_frames); }
+    if (d_echo_counts)      // (whole frames: segment = frame * n_angles + azimuth, the layout of the caller's buffers)
+        launch_echo_export(L.d_prov.p, L.d_prov_count.p, (size_t)L.prov_cap, n_frames * g.n_angles, d_echoes, d_echoes ? echo_stride : 0, d_echo_counts, s);
+    RR_HIP(c, hipGetLastError());
+    RR_HIP(c, give_lane(L, s));
+    return 0;
+}
+
 }  // namespace
 
 void drop_graphs(Lane& L)
@@ -436,7 +504,7 @@ hipError_t give_lane(Lane& L, hipStream_t s)
 }
 
 int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, uint8_t* d_cols_u8 /* null: the lane's own buffer */, float* d_cols_f32, hipStream_t s, int n_frames,
-              const float4* d_matsets, int mat_stride, bool lane_f32, const SetPlan* plan)
+              const float4* d_matsets, int mat_stride, bool lane_f32, const SetPlan* plan, int provenance)
 {
     const rr_config g = eff_config(c);      // (a parameter batch may ask for more passes than the config)
     if (az_begin < 0 || az_end > g.n_angles || az_begin > az_end) return fail(c, -3, "azimuth range out of bounds");
@@ -450,12 +518,18 @@ int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, u
     // without a word (advisor, round 5) -- a batch under include_motion brings one table per frame (or k tables, frame f -> f % k)
     if (!d_matsets && n_frames > 1 && !c->motion.empty() && c->motion_rows == 1)
         return fail(c, -3, "a pose batch while ONE per-azimuth pose table is set (rr_set_motion_poses): give one table per frame (k x n_angles poses) or clear the table");
+    if (provenance && d_matsets) return fail(c, -3, "echo provenance is for pose batches: the frames of a parameter batch share the hits of pass 0");
     rc = prepare_lane(c, L, n_seg, lane_f32); if (rc) return rc;
+    if (provenance) { rc = ensure_prov_buffers(c, L); if (rc) return rc; }
     if (!d_cols_u8) d_cols_u8 = L.d_cols_u8.p;       // the lane's own column buffer, valid only from here on
     if (lane_f32) d_cols_f32 = L.d_cols_f32.p;
     Params P;
     fill_params(c, L, P, pose, az_begin, n_seg, d_cols_u8, d_cols_f32);
     P.n_loc = n_loc; P.n_frames = n_frames;
+    if (provenance) {
+        P.prov = L.d_prov.p; P.prov_count = L.d_prov_count.p; P.prov_cap = L.prov_cap;
+        if (provenance > 1) { P.label_cols = L.d_label_cols.p; P.face_cols = L.d_face_cols.p; }
+    }
     if (d_matsets) {   // parameter batch: one pose, one material table per frame
         P.materials = d_matsets; P.mat_limits = L.d_matset_limits.p; P.mat_stride = mat_stride;
         P.set_mode = 1;
@@ -473,6 +547,7 @@ int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, u
         if (plan->d_beams) { P.beams = plan->d_beams; P.beam_order = plan->d_order; P.beam_order2 = plan->d_order2; }
     }
     if (c->stats_mode || g.n_reflections == 0) RR_HIP(c, hipMemsetAsync(L.d_counters.p, 0, sizeof(Counters), s));
+    if (provenance && g.n_reflections == 0) RR_HIP(c, hipMemsetAsync(L.d_prov_count.p, 0, (size_t)n_seg * sizeof(uint32_t), s));     // no pass, no gather launch
     L.last_n_seg = n_seg; L.last_n_passes = g.n_reflections;
     rc = choose_trace_rows(c, L, P, g, s); if (rc) return rc;
     // the poses of the call ride in the pass-0 trace launch (by value), which also writes them into the lane's pose table for
@@ -484,10 +559,10 @@ int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, u
     P.pose_table = reinterpret_cast<float4*>(L.d_poses.p);
     // Launch graphs: a chain that has been issued before with the same shape is captured once and replayed -- one
     // hipGraphLaunch instead of 4..20 launches (host time per device entry of rr_multi: 45-81 -> ~25 us).  Only plain pose
-    // batches: no parameter batch, no timing / statistics / roctx instrumentation; whatever a captured launch bakes in is
+    // batches: no parameter batch, no timing / statistics / roctx instrumentation, no provenance chain; whatever a captured launch bakes in is
     // covered by graph_gen (tables, tree, lane buffers) or by the key (azimuth block, frames, output buffer, trace rows)
     if (L.graph_gen != c->graph_gen) { drop_graphs(L); L.graph_gen = c->graph_gen; }
-    const bool graphable = !d_matsets && c->use_graphs && !c->timing && !c->stats_mode && !c->roctx && !d_cols_f32 && g.n_reflections > 0;
+    const bool graphable = !d_matsets && c->use_graphs && !c->timing && !c->stats_mode && !c->roctx && !d_cols_f32 && !provenance && g.n_reflections > 0;
     if (graphable) {
         Lane::FrameGraph* fg = find_graph(L, az_begin, az_end, n_frames, d_cols_u8, P);
         fg->last_use = ++c->graph_clock;
@@ -544,6 +619,87 @@ int rr_simulate_batch_device(rr_ctx* c, const float* poses, int n_frames, uint8_
     rc = take_lane(c, li, s); if (rc) return rc;
     rc = render_batch(c, L, poses, n_frames, d_imgs_u8, s); if (rc) return rc;
     RR_HIP(c, give_lane(L, s));
+    return 0;
+}
+
+int rr_simulate_batch_provenance_device(rr_ctx* c, const float* poses, int n_frames, uint8_t* d_imgs_u8, uint32_t* d_labels, uint32_t* d_faces,
+                                        rr_echo_src* d_echoes, size_t echo_stride, uint32_t* d_echo_counts, void* stream)
+{
+    int rc = check_provenance(c, "rr_simulate_batch_provenance_device", poses, n_frames, d_imgs_u8, d_echoes, echo_stride, d_echo_counts); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    rc = upload_tables(c); if (rc) return rc;
+    return provenance_batch(c, c->next_lane++ % c->lanes.size(), poses, n_frames, d_imgs_u8, d_labels, d_faces, d_echoes, echo_stride, d_echo_counts,
+                            stream_of(c, stream));
+}
+
+int rr_simulate_provenance(rr_ctx* c, const float pose[7], uint8_t* out_u8, uint32_t* out_labels, uint32_t* out_faces, rr_echo_src* out_echoes,
+                           size_t echo_stride, uint32_t* out_echo_counts)
+{
+    int rc = check_provenance(c, "rr_simulate_provenance", pose, 1, out_u8, out_echoes, echo_stride, out_echo_counts); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    rc = upload_tables(c); if (rc) return rc;
+    const rr_config& g = c->cfg;
+    const size_t A = (size_t)g.n_angles, npx = A * (size_t)g.n_cells;
+    Lane& L = c->lanes[0];
+    hipStream_t s = c->stream;
+    rc = settle_lane(c, L); if (rc) return rc;               // the image is assembled in the buffer of delivery slot 0, as rr_simulate does
+    // the device-side row of the exported stream: as long as the caller's, and no longer than a list can get
+    rc = prepare_lane(c, L, (int)A); if (rc) return rc;
+    rc = ensure_prov_buffers(c, L); if (rc) return rc;
+    const size_t d_stride = out_echoes ? std::min(echo_stride, (size_t)L.prov_cap) : 0;
+    RR_HIP(c, L.slot[0].img.ensure(npx));
+    if (out_labels) RR_HIP(c, L.d_label_img.ensure(npx));
+    if (out_faces) RR_HIP(c, L.d_face_img.ensure(npx));
+    if (out_echoes) RR_HIP(c, L.d_echo_out.ensure(A * d_stride));
+    if (out_echo_counts) RR_HIP(c, L.d_echo_out_counts.ensure(A));
+    rc = provenance_batch(c, 0, pose, 1, L.slot[0].img.p, out_labels ? L.d_label_img.p : nullptr, out_faces ? L.d_face_img.p : nullptr,
+                          out_echoes ? L.d_echo_out.p : nullptr, d_stride, out_echo_counts ? L.d_echo_out_counts.p : nullptr, s);
+    if (rc) return rc;
+    // outputs are staged: a call that fails below has written nothing
+    std::vector<uint8_t> h8(npx); std::vector<uint32_t> hl(out_labels ? npx : 0), hf(out_faces ? npx : 0), hc(out_echo_counts ? A : 0);
+    std::vector<rr_echo_src> he(out_echoes ? A * d_stride : 0);
+    RR_HIP(c, hipMemcpyAsync(h8.data(), L.slot[0].img.p, npx, hipMemcpyDeviceToHost, s));
+    if (out_labels) RR_HIP(c, hipMemcpyAsync(hl.data(), L.d_label_img.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (out_faces) RR_HIP(c, hipMemcpyAsync(hf.data(), L.d_face_img.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (out_echo_counts) RR_HIP(c, hipMemcpyAsync(hc.data(), L.d_echo_out_counts.p, A * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (!he.empty()) RR_HIP(c, hipMemcpyAsync(he.data(), L.d_echo_out.p, he.size() * sizeof(rr_echo_src), hipMemcpyDeviceToHost, s));
+    RR_HIP(c, give_lane(L, s));
+    RR_HIP(c, hipStreamSynchronize(s));
+    rc = report_frame_errors(c); if (rc) return rc;
+    std::memcpy(out_u8, h8.data(), npx);
+    if (out_labels) std::memcpy(out_labels, hl.data(), npx * sizeof(uint32_t));
+    if (out_faces) std::memcpy(out_faces, hf.data(), npx * sizeof(uint32_t));
+    if (out_echo_counts) std::memcpy(out_echo_counts, hc.data(), A * sizeof(uint32_t));
+    if (out_echoes)         // only the records that exist reach the caller's rows
+        for (size_t a = 0; a < A; a++)
+            std::memcpy(out_echoes + a * echo_stride, he.data() + a * d_stride, std::min((size_t)hc[a], d_stride) * sizeof(rr_echo_src));
+    return 0;
+}
+
+int rr_debug_labels(rr_ctx* c, int n_seg, int az_begin, const rr_echo_src* echoes, const uint32_t* counts, size_t stride, uint32_t* out_labels,
+                    uint32_t* out_faces)
+{
+    if (!c) return -1;
+    if (!c->have_cfg) return fail(c, -2, "rr_set_config has not been called");
+    const rr_config& g = c->cfg;
+    if (n_seg < 1 || az_begin < 0 || az_begin > g.n_angles - n_seg) return fail(c, -3, "rr_debug_labels: azimuth block out of bounds");
+    if (!counts || !out_labels || !out_faces || (stride > 0 && !echoes)) return fail(c, -3, "rr_debug_labels: null buffer");
+    if (g.n_cells > kLabelMaxCells) return fail(c, -3, "rr_debug_labels: n_cells exceeds RR_LABEL_MAX_CELLS (8192)");
+    for (int k = 0; k < n_seg; k++) if (counts[k] > stride) return fail(c, -3, "rr_debug_labels: a count exceeds stride");
+    RR_HIP(c, hipSetDevice(c->device));
+    int rc = upload_tables(c); if (rc) return rc;
+    const size_t S = (size_t)n_seg, px = S * (size_t)g.n_cells;
+    DevBuf<EchoSrc> d_e; DevBuf<uint32_t> d_n, d_l, d_f;
+    RR_HIP(c, d_e.ensure(S * stride)); RR_HIP(c, d_n.ensure(S)); RR_HIP(c, d_l.ensure(px)); RR_HIP(c, d_f.ensure(px));
+    if (stride) RR_HIP(c, hipMemcpy(d_e.p, echoes, S * stride * sizeof(rr_echo_src), hipMemcpyHostToDevice));
+    RR_HIP(c, hipMemcpy(d_n.p, counts, S * sizeof(uint32_t), hipMemcpyHostToDevice));
+    const bool den = !c->smear.empty() && g.signal_denoising > 0;
+    launch_label(d_e.p, d_n.p, stride, n_seg, g.n_cells, den ? (int)c->smear.size() : 1, den ? c->smear_mode : 0, den ? c->d_smear.p : nullptr, d_l.p, d_f.p,
+                 c->stream);
+    RR_HIP(c, hipGetLastError());
+    RR_HIP(c, hipStreamSynchronize(c->stream));
+    RR_HIP(c, hipMemcpy(out_labels, d_l.p, px * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    RR_HIP(c, hipMemcpy(out_faces, d_f.p, px * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -885,21 +885,7 @@ __global__ __launch_bounds__(64) void k_shade(const Params P, const int pass)
 // ---------------------------------------------------------------------------
 // ordered compaction: children -> idx[nxt], signals -> sig list.  grid n_seg, block 256
 // ---------------------------------------------------------------------------
-__device__ inline int block_excl_scan(int v, int& total, int* lds /*[8]*/)
-{
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int x = v;
-    for (int off = 1; off < 64; off <<= 1) { const int y = __shfl_up(x, off); if (lane >= off) x += y; }
-    if (lane == 63) lds[wid] = x;
-    __syncthreads();
-    int pre = 0, tot = 0;
-    for (int w = 0; w < 4; w++) { const int s = lds[w]; if (w < wid) pre += s; tot += s; }
-    __syncthreads();
-    total = tot;
-    return pre + x - v;
-}
-
-// the same for two packed words riding in one scan (lds: 4 x 8 bytes = the same 8 ints, the same two barriers)
+// block_excl_scan (rr_device.h) for two packed words riding in one scan (lds: 4 x 8 bytes = the same 8 ints, the same two barriers)
 __device__ inline unsigned long long block_excl_scan64(unsigned long long v, unsigned long long& total, int* lds /*[8]*/)
 {
     unsigned long long* lds64 = reinterpret_cast<unsigned long long*>(lds);
@@ -1667,17 +1653,6 @@ void launch_encode_refs(Node4* nodes, size_t n_nodes, uint32_t tri_base4, hipStr
                                    reinterpret_cast<TriRec*>(reinterpret_cast<float4*>(nodes) + tri_base4), n_tris);
 }
 
-// One launch, with or without the timing events.  ev_start / ev_stop (timing mode) take the dispatch's own begin / end
-// timestamps -- what rocprofv3 reports as the kernel's duration -- not the time the launch spent waiting for CUs held by the
-// kernels of other streams
-template <typename... KArgs, typename... Args>
-static void launch_k(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop,
-                     const Args&... args)
-{
-    if (!ev_start) hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
-    else hipExtLaunchKernelGGL(kernel, grid, block, lds, s, ev_start, ev_stop, 0, args...);
-}
-
 // a segment holds at most n_beam * 2^pass waves in pass `pass` (each wave has <= 2 children), and never more than cap
 static long pass_bound(const Params& P, int pass) { return std::min<long>((long)P.cap, pass < 20 ? (long)P.n_beam << pass : (long)P.cap); }
 
@@ -1797,6 +1772,14 @@ void launch_assemble_f32(const float* cols, float* img, int n_angles, int n_cell
 {
     dim3 grid((n_cells + 63) / 64, (n_angles + 63) / 64), block(256);
     hipLaunchKernelGGL((k_assemble<float>), grid, block, 0, s, cols, img, n_angles, n_cells, scroll, n_angles, (size_t)n_angles * n_cells, (size_t)0);
+}
+
+// label planes (rr_labels.hip): the columns of n_frames whole frames, frame f at cols + f * n_angles * n_cells
+void launch_assemble_u32(const uint32_t* cols, uint32_t* img, int n_angles, int n_cells, int scroll, hipStream_t s, int n_frames)
+{
+    dim3 grid((n_cells + 63) / 64, (n_angles + 63) / 64, n_frames > 0 ? n_frames : 1), block(256);
+    hipLaunchKernelGGL((k_assemble<uint32_t>), grid, block, 0, s, cols, img, n_angles, n_cells, scroll, n_angles, (size_t)n_angles * n_cells,
+                       (size_t)n_angles * n_cells);
 }
 
 void launch_debug_trace(const Params& P, const float* origs, const float* dirs, int n,

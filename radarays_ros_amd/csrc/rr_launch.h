@@ -1,11 +1,23 @@
-// rr_launch.h -- every launcher of rr_kernels.hip, rr_refit.hip, rr_detect.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip, rr_place.hip and rr_lbvh.hip, declared ONCE: included where they
+// rr_launch.h -- every launcher of rr_kernels.hip, rr_labels.hip, rr_refit.hip, rr_detect.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip, rr_place.hip and rr_lbvh.hip, declared ONCE: included where they
 // are defined (a definition that drifts from its declaration fails there) and where they are called.  Default arguments live here only.
 #pragma once
 #include "../../include/radarays_mi355.h"
 #include "rr_device.h"
+#include <hip/hip_ext.h>
 #include <string>
 
 namespace rr {
+// One launch, with or without the timing events.  ev_start / ev_stop (timing mode) take the dispatch's own begin / end
+// timestamps -- what rocprofv3 reports as the kernel's duration -- not the time the launch spent waiting for CUs held by the
+// kernels of other streams
+template <typename... KArgs, typename... Args>
+inline void launch_k(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop,
+                     const Args&... args)
+{
+    if (!ev_start) hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+    else hipExtLaunchKernelGGL(kernel, grid, block, lds, s, ev_start, ev_stop, 0, args...);
+}
+
 void launch_trace(const Params& P, int pass, const PoseArgs* poses, bool stats, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,
                   hipEvent_t ev_rep_start = nullptr, hipEvent_t ev_rep_stop = nullptr, bool* repair_launched = nullptr);
 void launch_shade(const Params& P, int pass, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
@@ -15,6 +27,13 @@ void launch_decay_table(float* decay, int n_cells, double resolution, double ene
 void launch_assemble_u8(const uint8_t* cols, uint8_t* img, int n_angles, int n_cells, int scroll, hipStream_t s,
                         int n_loc = 0, size_t block_stride = 0, int n_frames = 1, size_t frame_stride = 0);
 void launch_assemble_f32(const float* cols, float* img, int n_angles, int n_cells, int scroll, hipStream_t s);
+void launch_assemble_u32(const uint32_t* cols, uint32_t* img, int n_angles, int n_cells, int scroll, hipStream_t s, int n_frames = 1);
+// rr_labels.hip (echo provenance).  launch_label: n_seg lists of `stride` records each -> two columns [n_seg][n_cells]; w null: no denoiser
+void launch_echo_gather(const Params& P, int pass, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+void launch_label(const EchoSrc* lists, const uint32_t* counts, size_t stride, int n_seg, int n_cells, int W, int mode, const float* w,
+                  uint32_t* label_cols, uint32_t* face_cols, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+void launch_echo_export(const EchoSrc* lists, const uint32_t* counts, size_t cap, int n_seg, rr_echo_src* dst, size_t stride, uint32_t* dst_counts,
+                        hipStream_t s);
 bool build_bvh4_gpu(const float* verts, size_t nv, const uint32_t* faces, size_t nf, const uint32_t* face_object,
                     Node4** d_nodes_out, size_t* n_nodes_out, TriRec** d_tris_out, size_t* n_tris_out,
                     uint32_t* depth_out, uint32_t* stack_need_out, float* inflate_out,

@@ -35,6 +35,7 @@ SYMBOLS = [
     "rr_align_images_device", "rr_align_images", "rr_simulate_batch_align",
     "rr_shift_images_device", "rr_shift_images", "rr_simulate_batch_shift",
     "rr_describe_images_device", "rr_describe_images", "rr_simulate_batch_describe", "rr_match_descriptors_device", "rr_match_descriptors",
+    "rr_simulate_batch_provenance_device", "rr_simulate_provenance", "rr_debug_labels",
 ]
 
 
@@ -90,6 +91,19 @@ class RRCartesianConfig(C.Structure):
 
 # rr_echo as numpy sees it (8 B): one record of an echo stream of rr_debug_column
 ECHO_DTYPE = np.dtype([("cell", "<i4"), ("strength", "<f4")])
+
+# rr_echo_src as numpy sees it (16 B): an echo and where it came from (rr_simulate_provenance); LABEL_NONE = RR_LABEL_NONE
+ECHO_SRC_DTYPE = np.dtype([("cell", "<i4"), ("strength", "<f4"), ("face", "<u4"), ("info", "<u4")])
+LABEL_NONE = 0xFFFFFFFF
+LABEL_MAX_CELLS = 8192
+
+
+def unpack_info(info):
+    """the info word of an echo or a label pixel -> (object id, pass, kind); kind 0: path echo, 1: multipath echo.  Arrays or scalars;
+    RR_LABEL_NONE unpacks to (0xFFFFFF, 15, 1) with the unused top bits set: mask such pixels with `info != LABEL_NONE` first."""
+    i = np.asarray(info, np.uint32)
+    return i & np.uint32(0xFFFFFF), (i >> np.uint32(24)) & np.uint32(15), (i >> np.uint32(28)) & np.uint32(1)
+
 
 # rr_radar_point as numpy sees it (24 B: a PointCloud's point + its intensity channel, and where it came from)
 POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("intensity", "<f4"), ("column", "<u4"), ("bin", "<u4")])
@@ -359,6 +373,9 @@ def lib():
     L.rr_simulate_batch_describe.argtypes = [vp, vp, C.c_int, C.POINTER(RRPlaceConfig), vp]
     L.rr_match_descriptors_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     L.rr_match_descriptors.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    L.rr_simulate_batch_provenance_device.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, C.c_size_t, vp, vp]
+    L.rr_simulate_provenance.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    L.rr_debug_labels.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_size_t, vp, vp]
     for n in SYMBOLS:
         getattr(L, n)
     _LIB = L
@@ -1177,6 +1194,50 @@ class Context:
                                          int(bool(record_multi_path)), ptr(e), ptr(ec), ls, ptr(sl), ptr(sh), ptr(sc), ss,
                                          f32.ctypes.data, u8.ctypes.data, st.ctypes.data))
         return f32, u8, st
+
+    # ---- echo provenance (include/radarays_mi355.h): per-echo face / object / pass / kind, label images
+    def simulate_batch_provenance_device(self, poses, d_imgs_ptr, d_labels_ptr=None, d_faces_ptr=None, d_echoes_ptr=None, echo_stride=0,
+                                         d_echo_counts_ptr=None, stream=None):
+        """rr_simulate_batch_provenance_device: the images of rr_simulate_batch_device and, in HBM, any of: label / face planes uint32
+        [n][n_cells][n_angles], the echo stream ECHO_SRC_DTYPE [n][n_angles][echo_stride] with its true counts uint32 [n][n_angles]."""
+        p = np.ascontiguousarray(poses, np.float32).reshape(-1, 7)
+        self._ck(self._L.rr_simulate_batch_provenance_device(self._h, p.ctypes.data, len(p), d_imgs_ptr, d_labels_ptr, d_faces_ptr, d_echoes_ptr,
+                                                             int(echo_stride), d_echo_counts_ptr, stream))
+
+    def simulate_provenance(self, pose, echo_stride=None, want_labels=True, want_faces=True):
+        """rr_simulate_provenance: one frame -> (u8 [n_cells][n_angles], labels uint32 or None, faces uint32 or None, echoes ECHO_SRC_DTYPE
+        [n_angles][echo_stride], counts uint32 [n_angles]).  echo_stride None: every echo (a first call for the counts sizes the rows);
+        0: no echo stream (echoes None, counts still true)."""
+        p = np.ascontiguousarray(pose, np.float32)
+        if p.shape != (7,):
+            raise ValueError("pose must be [7] (qx qy qz qw tx ty tz), got %s" % (p.shape,))
+        n_cells = self.cfg.n_cells if self.cfg is not None else 1   # unconfigured: the library reports it
+        A = self.n_angles
+        u8 = np.zeros((n_cells, A), np.uint8)
+        lab = np.full((n_cells, A), LABEL_NONE, np.uint32) if want_labels else None
+        fac = np.full((n_cells, A), LABEL_NONE, np.uint32) if want_faces else None
+        cnt = np.zeros(A, np.uint32)
+        ptr = lambda a: None if a is None else a.ctypes.data   # noqa: E731
+        if echo_stride is None:
+            self._ck(self._L.rr_simulate_provenance(self._h, p.ctypes.data, u8.ctypes.data, None, None, None, 0, cnt.ctypes.data))
+            echo_stride = max(int(cnt.max()), 1)
+        echo_stride = _int_in(echo_stride, 0, 1 << 30, "echo_stride")
+        ech = np.zeros((A, echo_stride), ECHO_SRC_DTYPE) if echo_stride else None
+        self._ck(self._L.rr_simulate_provenance(self._h, p.ctypes.data, u8.ctypes.data, ptr(lab), ptr(fac), ptr(ech), echo_stride, cnt.ctypes.data))
+        return u8, lab, fac, ech, cnt
+
+    def debug_labels(self, echoes, counts, az_begin=0):
+        """rr_debug_labels: the label kernel on caller-given streams, echoes ECHO_SRC_DTYPE [n_seg][stride], counts [n_seg], under the
+        context's config (denoiser, n_cells) -> (labels, faces), each uint32 [n_seg][n_cells], not assembled."""
+        cnt = np.ascontiguousarray(counts, np.uint32).ravel()
+        n_seg = len(cnt)
+        e = np.ascontiguousarray(echoes, ECHO_SRC_DTYPE).reshape(max(n_seg, 1), -1)
+        n_cells = self.cfg.n_cells if self.cfg is not None else 1
+        lab = np.zeros((n_seg, n_cells), np.uint32)
+        fac = np.zeros((n_seg, n_cells), np.uint32)
+        self._ck(self._L.rr_debug_labels(self._h, n_seg, int(az_begin), e.ctypes.data if e.size else None, cnt.ctypes.data, e.shape[1],
+                                         lab.ctypes.data, fac.ctypes.data))
+        return lab, fac
 
 
 class HostImages:

@@ -18,6 +18,9 @@ from .params import (N_ANGLES, WAVE_ENERGY_THRESHOLD, RadarModelConfig, RadarPar
                      default_params)
 
 
+unpack_info = native.unpack_info      # info word of an echo / label pixel -> (object, pass, kind)
+
+
 @dataclass
 class Header:
     stamp: float = 0.0
@@ -332,6 +335,20 @@ class RadarHIP:
         self.last_f32 = f32
         self.last_stats = stats
         return msg
+
+    def simulate_provenance(self, pose=None, echo_stride=None):
+        """What the image is made of (rr_simulate_provenance): the frame at `pose` ([7], default: the current Tsm) ->
+        (image u8 [n_cells][400], labels uint32, faces uint32, echoes native.ECHO_SRC_DTYPE [400][echo_stride], counts uint32 [400]).
+        labels / faces hold, per pixel, the info word and the face of the echo with the largest single term in that range bin
+        (native.LABEL_NONE: no echo reaches it); echoes is every azimuth's ordered echo stream, indexed by azimuth, counts its
+        true lengths.  unpack_info() splits an info word; a ghost mask is `pass > 0`."""
+        if pose is None:
+            if not self.updateTsm():
+                print("Couldn't get Transform between sensor and map. Skipping...")
+                return None
+            pose = self.Tsm_last
+        self._push()
+        return self._ctx.simulate_provenance(pose, echo_stride=echo_stride)
 
     def _batch(self, poses, sweeps, stamp):
         """Offline generation (the twin of integration/.../RadarHIP.cpp: simulateBatch / simulateSweeps): one image per pose,
