@@ -113,6 +113,7 @@ def lib():
     L.orc_column.restype = C.c_int
     L.orc_column.argtypes = [C.POINTER(OrcConfig), C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_int, C.c_void_p, C.c_void_p]
     L.orc_set_echo_log.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    L.orc_set_echo_log_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.orc_saturate_u8.restype = C.c_uint8
     L.orc_saturate_u8.argtypes = [C.c_float]
     _LIB = L
@@ -357,7 +358,9 @@ def simulate(scene, materials, object_materials, cfg, beam_dirs, pose, noise_rnd
     """RadarCPU::simulate on the oracle. materials: [(velocity, ambient, diffuse, specular)].
     Returns (u8 [n_cells][n_angles], f32 or None, stats dict).
     echo_log: a dict; it receives "cells" / "strengths" [n_angles][cap] and "counts" [n_angles], every simulated azimuth's
-    ordered echo stream as orc_column takes it (cap = echo_log.get("cap", 4096) echoes per azimuth are kept)."""
+    ordered echo stream as orc_column takes it (cap = echo_log.get("cap", 4096) echoes per azimuth are kept), and beside them
+    "faces" (u32), "passes", "kinds" (u8: 0 the path echo, 1 the record_multi_path echo) and "frac" (f64: the fractional position
+    inside the range bin) [n_angles][cap], and "waves" [n_angles][n_reflections]: the number of waves at the start of each pass."""
     L = lib()
     oc = make_config(cfg, n_angles, material_id_air, brdf_model=brdf_model)
     if az_end is None:
@@ -381,6 +384,14 @@ def simulate(scene, materials, object_materials, cfg, beam_dirs, pose, noise_rnd
         echo_log["strengths"] = np.zeros((n_angles, cap), np.float32)
         echo_log["counts"] = np.zeros(n_angles, np.uint32)
         L.orc_set_echo_log(echo_log["cells"].ctypes.data, echo_log["strengths"].ctypes.data, echo_log["counts"].ctypes.data, cap)
+        n_pass = max(int(oc.n_reflections), 1)
+        echo_log["faces"] = np.full((n_angles, cap), 0xFFFFFFFF, np.uint32)
+        echo_log["passes"] = np.zeros((n_angles, cap), np.uint8)
+        echo_log["kinds"] = np.zeros((n_angles, cap), np.uint8)
+        echo_log["frac"] = np.zeros((n_angles, cap), np.float64)
+        echo_log["waves"] = np.zeros((n_angles, n_pass), np.uint32)
+        L.orc_set_echo_log_ex(echo_log["faces"].ctypes.data, echo_log["passes"].ctypes.data, echo_log["kinds"].ctypes.data,
+                              echo_log["frac"].ctypes.data, echo_log["waves"].ctypes.data, n_pass)
     try:
         rc = _run_simulate(L, motion, scene, mats, materials, om, oc, bd, ps, nr, az_begin, az_end, u8, f32, n_threads, st)
     finally:
@@ -388,6 +399,7 @@ def simulate(scene, materials, object_materials, cfg, beam_dirs, pose, noise_rnd
             L.orc_set_uniform_stream(None, 0)
         if echo_log is not None:
             L.orc_set_echo_log(None, None, None, 0)
+            L.orc_set_echo_log_ex(None, None, None, None, None, 0)
     if rc != 0:
         raise RuntimeError("orc_simulate failed: %d" % rc)
     stats = {k: getattr(st, k) for k, _ in OrcStats._fields_}

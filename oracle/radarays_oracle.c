@@ -741,7 +741,8 @@ int orc_intersect(const orc_scene* s, const float orig[3], const float dir[3],
 /* ------------------------------------------------------------------------ */
 /* RadarCPU::simulate                                                        */
 /* ------------------------------------------------------------------------ */
-typedef struct { double time, strength; } signal_t;   /* radar_types.h:23-27 */
+typedef struct { double time, strength;   /* radar_types.h:23-27 */
+                 uint32_t face, tag; } signal_t;   /* test bookkeeping (orc_set_echo_log_ex): the face hit, pass << 1 | kind */
 
 typedef struct { wave_t* p; size_t n, cap; } wave_vec;
 typedef struct { signal_t* p; size_t n, cap; } sig_vec;
@@ -751,10 +752,10 @@ static void wv_push(wave_vec* v, const wave_t* w)
     if (v->n == v->cap) { v->cap = v->cap ? v->cap * 2 : 256; v->p = (wave_t*)realloc(v->p, v->cap * sizeof(wave_t)); }
     v->p[v->n++] = *w;
 }
-static void sv_push(sig_vec* v, double time, double strength)
+static void sv_push(sig_vec* v, double time, double strength, uint32_t face, uint32_t tag)
 {
     if (v->n == v->cap) { v->cap = v->cap ? v->cap * 2 : 256; v->p = (signal_t*)realloc(v->p, v->cap * sizeof(signal_t)); }
-    v->p[v->n].time = time; v->p[v->n].strength = strength; v->n++;
+    v->p[v->n].time = time; v->p[v->n].strength = strength; v->p[v->n].face = face; v->p[v->n].tag = tag; v->n++;
 }
 
 /* RadarCPU.cpp:497-512: amplitude of the ambient noise of one bin as a function of its signal (signal_min = 0,
@@ -808,6 +809,24 @@ void orc_set_echo_log(int32_t* cells, float* strengths, uint32_t* counts, size_t
     const int on = cells && strengths && counts;
     g_echo_cells = on ? cells : NULL; g_echo_strengths = on ? strengths : NULL; g_echo_counts = on ? counts : NULL;
     g_echo_cap = on ? cap : 0;
+}
+
+/* test hook (tests/test_stream_host.py), beside orc_set_echo_log and with its cap: where the echo came from and how close to a
+ * bin boundary it lies.  faces / passes / kinds / frac [n_angles][cap]: the face of the hit (`f` of scene_intersect), the pass,
+ * the kind (0: the path echo of RadarCPU.cpp:319, 1: the record_multi_path echo of :325-347) and the f64 fractional position
+ * (double)signal_dist / resolution - cell of :413.  waves [n_angles][max_pass]: waves.n at the start of every pass < max_pass.
+ * Only read while orc_set_echo_log is set; NULL clears.  Writes nothing the image is made from. */
+static uint32_t* g_echo_faces = NULL;
+static uint8_t* g_echo_passes = NULL;
+static uint8_t* g_echo_kinds = NULL;
+static double* g_echo_frac = NULL;
+static uint32_t* g_echo_waves = NULL;
+static size_t g_echo_max_pass = 0;
+void orc_set_echo_log_ex(uint32_t* faces, uint8_t* passes, uint8_t* kinds, double* frac, uint32_t* waves, size_t max_pass)
+{
+    const int on = faces && passes && kinds && frac && waves;
+    g_echo_faces = on ? faces : NULL; g_echo_passes = on ? passes : NULL; g_echo_kinds = on ? kinds : NULL;
+    g_echo_frac = on ? frac : NULL; g_echo_waves = on ? waves : NULL; g_echo_max_pass = on ? max_pass : 0;
 }
 
 /* RadarCPU.cpp:402-542 for ONE azimuth: its ordered echoes (cell of :413, strength) -> slice -> noise -> scale -> mono8.
@@ -1018,6 +1037,8 @@ static int simulate_impl(const orc_scene* scene,
                 #pragma omp critical(cntlog)
                 fprintf(cntlog, "%d %d %zu\n", angle_id, pass_id, waves.n);
             }
+            if (g_echo_counts && g_echo_waves && (size_t)pass_id < g_echo_max_pass)
+                g_echo_waves[(size_t)angle_id * g_echo_max_pass + (size_t)pass_id] = (uint32_t)waves.n;
             for (size_t i = 0; i < waves.n; i++)   /* :243 */
             {
                 wave_t wave = waves.p[i];
@@ -1083,7 +1104,7 @@ static int simulate_impl(const orc_scene* scene,
 
                         if (pass_id == 0 || cfg->record_multi_reflection) {   /* :319 */
                             float time_back = (float)(incidence.time * 2.0);
-                            sv_push(&signals, (double)time_back, return_energy_path);
+                            sv_push(&signals, (double)time_back, return_energy_path, f, (uint32_t)pass_id << 1);
                         }
                         if (pass_id > 0 && cfg->record_multi_path)   /* :325 */
                         {
@@ -1097,7 +1118,7 @@ static int simulate_impl(const orc_scene* scene,
                                 double return_energy_air = (double)orc_back_reflection_shader_model(
                                     (float)ang, (float)reflection.energy,
                                     material.ambient, material.diffuse, material.specular, cfg->brdf_model);
-                                sv_push(&signals, incidence.time + time_to_sensor, return_energy_air);
+                                sv_push(&signals, incidence.time + time_to_sensor, return_energy_air, f, ((uint32_t)pass_id << 1) | 1u);
                             }
                         }
                     }
@@ -1136,6 +1157,14 @@ static int simulate_impl(const orc_scene* scene,
             for (size_t i = 0; i < signals.n && i < g_echo_cap; i++) {
                 g_echo_cells[(size_t)angle_id * g_echo_cap + i] = echo_cell[i];
                 g_echo_strengths[(size_t)angle_id * g_echo_cap + i] = echo_str[i];
+            }
+            for (size_t i = 0; g_echo_faces && i < signals.n && i < g_echo_cap; i++) {
+                const size_t k = (size_t)angle_id * g_echo_cap + i;
+                const float signal_dist = (float)(0.3 * (double)(float)(signals.p[i].time / 2.0));   /* :410-411, as above */
+                g_echo_faces[k] = signals.p[i].face;
+                g_echo_passes[k] = (uint8_t)(signals.p[i].tag >> 1);
+                g_echo_kinds[k] = (uint8_t)(signals.p[i].tag & 1u);
+                g_echo_frac[k] = (double)signal_dist / cfg->resolution - (double)echo_cell[i];
             }
         }
         {

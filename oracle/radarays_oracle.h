@@ -150,6 +150,11 @@ int orc_column(const orc_config* cfg, const int32_t* cells, const float* strengt
  * takes it: counts[a] = its number of echoes, cells / strengths [a * cap + k] = the first cap of them.  Arrays of n_angles
  * rows; NULL clears.  Not thread-safe against a running orc_simulate; set, simulate, clear. */
 void orc_set_echo_log(int32_t* cells, float* strengths, uint32_t* counts, size_t cap);
+/* test hook, beside orc_set_echo_log (read only while that one is set, with its cap): per logged echo the face hit, the pass,
+ * the kind (0: the path echo of RadarCPU.cpp:319, 1: the record_multi_path echo of :325-347) and the f64 fractional bin position
+ * (double)signal_dist / resolution - cell of :413, arrays [n_angles][cap]; waves [n_angles][max_pass]: the number of waves at
+ * the start of each pass < max_pass.  NULL clears. */
+void orc_set_echo_log_ex(uint32_t* faces, uint8_t* passes, uint8_t* kinds, double* frac, uint32_t* waves, size_t max_pass);
 
 /* ---- per-hit math, exported one by one for the known-answer tests ---- */
 
