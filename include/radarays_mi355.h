@@ -588,6 +588,56 @@ int rr_simulate_provenance(rr_ctx* ctx, const float pose[7], uint8_t* out_u8, ui
 int rr_debug_labels(rr_ctx* ctx, int n_seg, int az_begin, const rr_echo_src* echoes, const uint32_t* counts, size_t stride,
                     uint32_t* out_labels, uint32_t* out_faces);
 
+/* ---- wave paths: every wave's ray, hit, parent and echo per azimuth (rr_paths.hip) -------------------------------
+ * By which route a return got there: the reference answers it with its inspection tool src/ray_reflection_test.cpp (shoot rays,
+ * follow the reflect / refract bounces, draw the paths).  An opt-in variant of the pose-batch frame call returns, beside the usual
+ * image, the wave list of every azimuth: one 64-byte record per wave that was RAY-CAST, misses included -- so the length of an
+ * azimuth's list is its share of rr_stats.wave_passes.  The definition is the build's own (the reference keeps no such list);
+ * it is pinned to the reference through the per-hit functions and the echo log of the oracle (tests/paths_ref.py restates the
+ * bounce loop of one azimuth from them).
+ * Order.  Passes in sequence; inside a pass the reference's order: the position j in the pass' live list, in pass 0 the beam index
+ * j.  A wave at position k of pass p + 1 sits in child slot s of pass p: its parent is position s >> 1 of pass p and its branch
+ * 1 + (s & 1) (1: reflection child, 2: transmission child; 0: an emitted beam).
+ * Frame.  o and d are in the azimuth's SENSOR frame, bit for bit what the wave queue holds (pass 0: o = 0, d = the beam
+ * direction); with RR_WAVES_MAP_FRAME they are q_am * o + t_am and q_am * d of the azimuth's sensor-to-map transform -- the
+ * expressions the ray-cast sets its ray up with (pass 0: o = t_am).  energy and time do not depend on the frame.  The hit
+ * point is o + range * d, formed by the caller.
+ * Echo index.  `echo` counts in the azimuth's echo stream as rr_simulate_batch_provenance_device returns it for the same pose:
+ * echoes of earlier passes + the echoes of the waves before this one in its pass.  The stream's record at that index has this
+ * wave's face, object and pass.
+ * Limits: pose batches only (-3 otherwise: parameter batches share the hits of pass 0); the object / pass limits of the
+ * provenance info word; n_frames in 1..RR_MAX_BATCH.  The chain of a paths call is issued kernel by kernel (never from a launch
+ * graph, and the lane's launch graphs are left alone); the image is made by the same launches with the same arguments as
+ * rr_simulate_batch_device's: the same bytes.  The records go straight into the caller's rows; the lane keeps 16 bytes of
+ * running state per segment, allocated by the first paths call.  rr_multi has no paths call: use the context of one device.
+ * Refused with a message and nothing written: -2 without a config / mesh / materials / beam, -3 for a null required buffer
+ * (poses, image, d_waves without d_wave_counts), wave_stride == 0 with d_waves, n_frames out of range, unknown flag bits, the
+ * object / pass limits. */
+typedef struct rr_wave_rec {          /* 64 B, four 16-B stores */
+    float    o[3];  float range;      /* start point; hit distance along d, -1.0f for a miss */
+    float    d[3];  uint32_t face;    /* direction; face id of the triangle hit, RR_LABEL_NONE for a miss */
+    double   energy, time;            /* at the START of the wave (pass 0: 1.0, 0.0; RadarCPU.cpp:107,112) */
+    uint32_t info;                    /* object id of the face (0xFFFFFF for a miss) | pass << 24 | branch << 28 | has_path_echo << 30 |
+                                         has_multipath_echo << 31 */
+    int32_t  parent;                  /* index of the parent wave in THIS azimuth's list; -1 in pass 0 */
+    uint32_t material;                /* the medium the wave travels in (pass 0: 0, RadarCPU.cpp:111) */
+    int32_t  echo;                    /* index of the wave's first echo in this azimuth's echo stream; -1 if none.  A wave with both
+                                         echoes owns echo and echo + 1 (path echo first) */
+} rr_wave_rec;
+#define RR_WAVES_MAP_FRAME 1u         /* flags: o / d in the map frame */
+#define RR_WAVES_MAX_PASSES 16        /* row length of d_pass_counts (n_reflections <= 16, as the info word demands) */
+/* whole frames of n_frames poses, asynchronous on `stream`, device buffers:
+ *   d_imgs_u8     [n][n_cells][n_angles]                       as rr_simulate_batch_device, same bytes
+ *   d_waves       rr_wave_rec [n][n_angles][wave_stride] or NULL (16-byte aligned), indexed by AZIMUTH (not column)
+ *   d_wave_counts uint32 [n][n_angles] or NULL (required with d_waves): the TRUE count; when it exceeds wave_stride the first wave_stride records
+ *                 are written and nothing beyond them; parent and echo stay true indices even when their target was cut off
+ *   d_pass_counts uint32 [n][n_angles][RR_WAVES_MAX_PASSES] or NULL: waves cast per pass (0 beyond n_reflections) */
+int rr_simulate_batch_paths_device(rr_ctx* ctx, const float* poses, int n_frames, uint8_t* d_imgs_u8, rr_wave_rec* d_waves,
+                                   size_t wave_stride, uint32_t* d_wave_counts, uint32_t* d_pass_counts, unsigned flags, void* stream);
+/* one frame, host buffers, synchronous; out_waves and out_pass_counts may be NULL.  Returns -7 / -8 itself like rr_simulate. */
+int rr_simulate_paths(rr_ctx* ctx, const float pose[7], uint8_t* out_u8, rr_wave_rec* out_waves, size_t wave_stride,
+                      uint32_t* out_wave_counts, uint32_t* out_pass_counts, unsigned flags);
+
 /* ---- radar point clouds and Cartesian images from polar images (rr_detect.hip) ----------------------------------
  * The reference's pipeline turns every simulated image into a point cloud with radar_tools/radar_img_to_pcl
  * (launch/tests/radar_sim_test.launch:80-84), a node outside the checkout: its algorithm is unknown, so parity with it is

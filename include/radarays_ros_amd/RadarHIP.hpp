@@ -12,6 +12,7 @@
 // which both include: the marshalling the ROS-typed adapter ships is the one the GPU demo executes through this class.
 // Here: the `Radar` base, the dirty flags, `Image`s, detect / toCartesian and how errors are reported.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <iostream>
@@ -174,6 +175,50 @@ public:
         if (rr_simulate_provenance(m_ctx, Tsm_last, out->image->data.data(), out->labels.data(), out->faces.data(),
                                    echo_stride ? out->echoes.data() : nullptr, echo_stride, out->echo_counts.data())) { fail(); return {}; }
         return out;
+    }
+    // By which route the waves travelled (rr_simulate_paths, include/radarays_mi355.h), on device 0: the frame at the current Tsm and,
+    // per azimuth, its list of ray-cast waves (misses included), rows of `wave_stride` records (0: one run first to learn the counts),
+    // the true counts and the waves per pass.  map_frame: o / d in the map frame.  Null on error (lastError()).
+    struct Paths { ImagePtr image; std::vector<rr_wave_rec> waves; std::vector<uint32_t> wave_counts, pass_counts; size_t wave_stride = 0; };
+    std::shared_ptr<Paths> simulatePaths(double stamp, size_t wave_stride = 0, bool map_frame = false)
+    {
+        if (!updateTsm()) {
+            std::cout << "Couldn't get Transform between sensor and map. Skipping..." << std::endl;
+            return {};
+        }
+        if (!push()) return {};
+        auto out = std::make_shared<Paths>();
+        out->image = image(nullptr, stamp);
+        out->wave_counts.assign((size_t)m_n_angles, 0u);
+        out->pass_counts.assign((size_t)m_n_angles * RR_WAVES_MAX_PASSES, 0u);
+        const unsigned flags = map_frame ? RR_WAVES_MAP_FRAME : 0u;
+        if (wave_stride == 0) {
+            if (rr_simulate_paths(m_ctx, Tsm_last, out->image->data.data(), nullptr, 0, out->wave_counts.data(), nullptr, flags)) { fail(); return {}; }
+            for (uint32_t n : out->wave_counts) wave_stride = std::max(wave_stride, (size_t)n);
+            wave_stride = std::max<size_t>(wave_stride, 1);
+        }
+        out->waves.resize((size_t)m_n_angles * wave_stride); out->wave_stride = wave_stride;
+        if (rr_simulate_paths(m_ctx, Tsm_last, out->image->data.data(), out->waves.data(), wave_stride, out->wave_counts.data(),
+                              out->pass_counts.data(), flags)) { fail(); return {}; }
+        return out;
+    }
+    // A ghost's route: the wave of ONE azimuth's list (its first n records) that owns echo k of the azimuth's echo stream, walked back
+    // along `parent` to the emitted beam -> the indices of the chain's waves, beam first (empty: no record owns echo k, or a parent
+    // lies beyond n -- a truncated row).  The polyline is records[i].o of the first, then o + range * d of every wave of the chain.
+    static std::vector<int32_t> pathToEcho(const rr_wave_rec* records, size_t n, int32_t k)
+    {
+        std::vector<int32_t> chain;
+        for (size_t i = 0; i < n && chain.empty(); i++) {
+            const int32_t owned = (int32_t)((records[i].info >> 30) & 1u) + (int32_t)(records[i].info >> 31);
+            if (records[i].echo >= 0 && records[i].echo <= k && k < records[i].echo + owned) chain.push_back((int32_t)i);
+        }
+        while (!chain.empty() && records[chain.back()].parent >= 0) {
+            const int32_t p = records[chain.back()].parent;
+            if ((size_t)p >= n || chain.size() > RR_WAVES_MAX_PASSES) return {};
+            chain.push_back(p);
+        }
+        std::reverse(chain.begin(), chain.end());
+        return chain;
     }
     // Offline generation (the twin of integration/src/radarays_ros/RadarHIP.cpp: simulateBatch / simulateSweeps): one image
     // per pose [n][7], up to RR_MAX_BATCH poses per set of launches; with per-azimuth pose tables (include_motion,

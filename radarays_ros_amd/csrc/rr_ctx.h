@@ -80,6 +80,11 @@ struct Lane {
     DevBuf<uint32_t> d_label_img, d_face_img;      // rr_simulate_provenance: the assembled planes on their way to the host
     DevBuf<rr_echo_src> d_echo_out; DevBuf<uint32_t> d_echo_out_counts;      // ... and its exported echo stream
 
+    // wave paths (rr_paths.hip): k_wave_gather's running state per segment [path_seg], allocated by the lane's first paths call
+    // (ensure_path_state); rr_simulate_paths: the records and counts on their way to the host
+    DevBuf<uint4> d_path_state; int path_seg = 0;
+    DevBuf<float4> d_wave_out; DevBuf<uint32_t> d_wave_out_counts, d_wave_out_passes;
+
     hipStream_t stream = nullptr;
     hipEvent_t ev_ready = nullptr, ev_consumed = nullptr;
     bool pending_consume = false;
@@ -304,7 +309,8 @@ int take_lane(rr_ctx* c, size_t li, hipStream_t s, int slot = -1);
 hipError_t give_lane(Lane& L, hipStream_t s);
 int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, uint8_t* d_cols_u8 /* null: the lane's own buffer */, float* d_cols_f32,
               hipStream_t s, int n_frames = 1, const float4* d_matsets = nullptr, int mat_stride = 0, bool lane_f32 = false, const SetPlan* plan = nullptr,
-              int provenance = 0 /* 1: the lane's echo lists are gathered; 2: and its label columns made */);
+              int provenance = 0 /* 1: the lane's echo lists are gathered; 2: and its label columns made */,
+              const WaveOut* paths = nullptr /* the wave records of every pass go to these rows (state: the lane's, filled in here) */);
 int assemble_frames(rr_ctx* c, const Lane& L, uint8_t* dst, int n_frames, hipStream_t s);
 
 }  // namespace rr

@@ -170,6 +170,16 @@ int ensure_prov_buffers(rr_ctx* c, Lane& L)
     return 0;
 }
 
+// The lane's running state of a paths chain for its current frame buffers (after prepare_lane): 16 bytes per segment
+int ensure_path_state(rr_ctx* c, Lane& L)
+{
+    if (L.d_path_state.p && L.path_seg >= L.buf_seg) return 0;
+    RR_HIP(c, hipDeviceSynchronize());      // a paths chain in flight may still use the old buffer
+    RR_HIP(c, L.d_path_state.ensure((size_t)L.buf_seg));
+    L.path_seg = L.buf_seg;
+    return 0;
+}
+
 // device -> host on stream s: the library's own copy kernel (8 workgroups, all on XCD 0) when the destination is page-locked
 // (`visible`) and everything is 16-byte aligned, else hipMemcpyAsync (rr_copy_to_host_async in the header says why)
 int copy_out(rr_ctx* c, const void* d_src, void* h_dst, size_t bytes, bool visible, hipStream_t s)
@@ -242,7 +252,7 @@ int choose_trace_rows(rr_ctx* c, Lane& L, Params& P, const rr_config& g, hipStre
 }
 
 // the launch chain of the batch
-int issue_chain(rr_ctx* c, const Params& Q, const PoseArgs& pa, const rr_config& g, hipStream_t s)
+int issue_chain(rr_ctx* c, const Params& Q, const PoseArgs& pa, const rr_config& g, hipStream_t s, const WaveOut* wo = nullptr)
 {
     for (int pass = 0; pass < g.n_reflections; pass++) {
         if (c->roctx) roctx_push(pass == 0 ? "trace pass 0" : "trace");
@@ -263,6 +273,7 @@ int issue_chain(rr_ctx* c, const Params& Q, const PoseArgs& pa, const rr_config&
         if (c->roctx) roctx_pop();
         { KernelEvents t(c, "shade"); launch_shade(Q, pass, s, t.a, t.b); }
         if (Q.prov) { KernelEvents t(c, "gather"); launch_echo_gather(Q, pass, s, t.a, t.b); }
+        if (wo) { KernelEvents t(c, "waves"); launch_wave_gather(Q, pass, *wo, s, t.a, t.b); }
         if (pass < g.n_reflections - 1) { KernelEvents t(c, "scan"); launch_scan(Q, pass, s, t.a, t.b); }
     }
     { KernelEvents t(c, "column"); launch_column(Q, s, t.a, t.b); }
@@ -431,6 +442,38 @@ int provenance_batch(rr_ctx* c, size_t li, const float* poses, int n_frames, uin
     return 0;
 }
 
+// the refusals of the two paths entry points (nothing is written)
+int check_paths(rr_ctx* c, const char* who, const void* poses, int n_frames, const void* imgs, const void* waves, size_t wave_stride,
+                const void* counts, unsigned flags)
+{
+    int rc = check_ready(c); if (rc) return rc;
+    const std::string w(who);
+    if (!poses || !imgs) return fail(c, -3, w + ": null poses/output");
+    if (n_frames < 1 || n_frames > RR_MAX_BATCH) return fail(c, -3, w + ": n_frames must be 1..64");
+    if (waves && !counts) return fail(c, -3, w + ": a wave buffer needs a count buffer");
+    if (waves && wave_stride == 0) return fail(c, -3, w + ": wave_stride must be positive");
+    if ((uintptr_t)waves % 16 != 0) return fail(c, -3, w + ": the wave buffer must be 16-byte aligned");
+    if (flags & ~(unsigned)RR_WAVES_MAP_FRAME) return fail(c, -3, w + ": unknown flag bits");
+    if (c->n_objects >= 0xFFFFFFu) return fail(c, -3, w + ": the info word holds object ids below 2^24 - 1");
+    if (c->cfg.n_reflections > RR_WAVES_MAX_PASSES) return fail(c, -3, w + ": the info word holds passes below 16 (n_reflections <= 16)");
+    return 0;
+}
+
+// a pose batch with wave paths on lane li (taken and handed back here), everything enqueued on s
+int paths_batch(rr_ctx* c, size_t li, const float* poses, int n_frames, uint8_t* d_imgs_u8, rr_wave_rec* d_waves, size_t wave_stride,
+                uint32_t* d_wave_counts, uint32_t* d_pass_counts, unsigned flags, hipStream_t s)
+{
+    Lane& L = c->lanes[li];
+    int rc = take_lane(c, li, s); if (rc) return rc;
+    WaveOut wo;      // (whole frames: segment = frame * n_angles + azimuth, the layout of the caller's buffers)
+    wo.recs = reinterpret_cast<float4*>(d_waves); wo.stride = d_waves ? wave_stride : 0;
+    wo.counts = d_wave_counts; wo.pass_counts = d_pass_counts; wo.state = nullptr; wo.flags = flags;
+    rc = run_frame(c, L, poses, 0, c->cfg.n_angles, nullptr, nullptr, s, n_frames, nullptr, 0, false, nullptr, 0, &wo); if (rc) return rc;
+    rc = assemble_frames(c, L, d_imgs_u8, n_frames, s); if (rc) return rc;
+    RR_HIP(c, give_lane(L, s));
+    return 0;
+}
+
 }  // namespace
 
 void drop_graphs(Lane& L)
@@ -504,7 +547,7 @@ hipError_t give_lane(Lane& L, hipStream_t s)
 }
 
 int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, uint8_t* d_cols_u8 /* null: the lane's own buffer */, float* d_cols_f32, hipStream_t s, int n_frames,
-              const float4* d_matsets, int mat_stride, bool lane_f32, const SetPlan* plan, int provenance)
+              const float4* d_matsets, int mat_stride, bool lane_f32, const SetPlan* plan, int provenance, const WaveOut* paths)
 {
     const rr_config g = eff_config(c);      // (a parameter batch may ask for more passes than the config)
     if (az_begin < 0 || az_end > g.n_angles || az_begin > az_end) return fail(c, -3, "azimuth range out of bounds");
@@ -519,8 +562,11 @@ int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, u
     if (!d_matsets && n_frames > 1 && !c->motion.empty() && c->motion_rows == 1)
         return fail(c, -3, "a pose batch while ONE per-azimuth pose table is set (rr_set_motion_poses): give one table per frame (k x n_angles poses) or clear the table");
     if (provenance && d_matsets) return fail(c, -3, "echo provenance is for pose batches: the frames of a parameter batch share the hits of pass 0");
+    if (paths && d_matsets) return fail(c, -3, "wave paths are for pose batches: the frames of a parameter batch share the hits of pass 0");
     rc = prepare_lane(c, L, n_seg, lane_f32); if (rc) return rc;
     if (provenance) { rc = ensure_prov_buffers(c, L); if (rc) return rc; }
+    WaveOut wo{};
+    if (paths) { rc = ensure_path_state(c, L); if (rc) return rc; wo = *paths; wo.state = L.d_path_state.p; }
     if (!d_cols_u8) d_cols_u8 = L.d_cols_u8.p;       // the lane's own column buffer, valid only from here on
     if (lane_f32) d_cols_f32 = L.d_cols_f32.p;
     Params P;
@@ -548,6 +594,10 @@ int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, u
     }
     if (c->stats_mode || g.n_reflections == 0) RR_HIP(c, hipMemsetAsync(L.d_counters.p, 0, sizeof(Counters), s));
     if (provenance && g.n_reflections == 0) RR_HIP(c, hipMemsetAsync(L.d_prov_count.p, 0, (size_t)n_seg * sizeof(uint32_t), s));     // no pass, no gather launch
+    if (paths && g.n_reflections == 0) {      // no pass, no gather launch
+        if (wo.counts) RR_HIP(c, hipMemsetAsync(wo.counts, 0, (size_t)n_seg * sizeof(uint32_t), s));
+        if (wo.pass_counts) RR_HIP(c, hipMemsetAsync(wo.pass_counts, 0, (size_t)n_seg * kWavePasses * sizeof(uint32_t), s));
+    }
     L.last_n_seg = n_seg; L.last_n_passes = g.n_reflections;
     rc = choose_trace_rows(c, L, P, g, s); if (rc) return rc;
     // the poses of the call ride in the pass-0 trace launch (by value), which also writes them into the lane's pose table for
@@ -559,10 +609,11 @@ int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, u
     P.pose_table = reinterpret_cast<float4*>(L.d_poses.p);
     // Launch graphs: a chain that has been issued before with the same shape is captured once and replayed -- one
     // hipGraphLaunch instead of 4..20 launches (host time per device entry of rr_multi: 45-81 -> ~25 us).  Only plain pose
-    // batches: no parameter batch, no timing / statistics / roctx instrumentation, no provenance chain; whatever a captured launch bakes in is
+    // batches: no parameter batch, no timing / statistics / roctx instrumentation, no provenance or paths chain (which
+    // does not even look at the lane's graphs: a plain batch afterwards replays as before); whatever a captured launch bakes in is
     // covered by graph_gen (tables, tree, lane buffers) or by the key (azimuth block, frames, output buffer, trace rows)
     if (L.graph_gen != c->graph_gen) { drop_graphs(L); L.graph_gen = c->graph_gen; }
-    const bool graphable = !d_matsets && c->use_graphs && !c->timing && !c->stats_mode && !c->roctx && !d_cols_f32 && !provenance && g.n_reflections > 0;
+    const bool graphable = !d_matsets && c->use_graphs && !c->timing && !c->stats_mode && !c->roctx && !d_cols_f32 && !provenance && !paths && g.n_reflections > 0;
     if (graphable) {
         Lane::FrameGraph* fg = find_graph(L, az_begin, az_end, n_frames, d_cols_u8, P);
         fg->last_use = ++c->graph_clock;
@@ -570,7 +621,7 @@ int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, u
         if (fg->ge) return replay_graph(c, fg, pa, s);
         fg->hits++;
     }
-    { HostProfScope hp(5, "ctx:   chain issued kernel by kernel"); const int rcq = issue_chain(c, P, pa, g, s); if (rcq) return rcq; }
+    { HostProfScope hp(5, "ctx:   chain issued kernel by kernel"); const int rcq = issue_chain(c, P, pa, g, s, paths ? &wo : nullptr); if (rcq) return rcq; }
     RR_HIP(c, hipGetLastError());
     return 0;
 }
@@ -673,6 +724,62 @@ int rr_simulate_provenance(rr_ctx* c, const float pose[7], uint8_t* out_u8, uint
     if (out_echoes)         // only the records that exist reach the caller's rows
         for (size_t a = 0; a < A; a++)
             std::memcpy(out_echoes + a * echo_stride, he.data() + a * d_stride, std::min((size_t)hc[a], d_stride) * sizeof(rr_echo_src));
+    return 0;
+}
+
+int rr_simulate_batch_paths_device(rr_ctx* c, const float* poses, int n_frames, uint8_t* d_imgs_u8, rr_wave_rec* d_waves, size_t wave_stride,
+                                   uint32_t* d_wave_counts, uint32_t* d_pass_counts, unsigned flags, void* stream)
+{
+    int rc = check_paths(c, "rr_simulate_batch_paths_device", poses, n_frames, d_imgs_u8, d_waves, wave_stride, d_wave_counts, flags); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    rc = upload_tables(c); if (rc) return rc;
+    return paths_batch(c, c->next_lane++ % c->lanes.size(), poses, n_frames, d_imgs_u8, d_waves, wave_stride, d_wave_counts, d_pass_counts, flags,
+                       stream_of(c, stream));
+}
+
+int rr_simulate_paths(rr_ctx* c, const float pose[7], uint8_t* out_u8, rr_wave_rec* out_waves, size_t wave_stride, uint32_t* out_wave_counts,
+                      uint32_t* out_pass_counts, unsigned flags)
+{
+    // (host rows need no alignment: they are filled by memcpy)
+    int rc = check_paths(c, "rr_simulate_paths", pose, 1, out_u8, nullptr, 0, out_wave_counts, flags); if (rc) return rc;
+    if (out_waves && !out_wave_counts) return fail(c, -3, "rr_simulate_paths: a wave buffer needs a count buffer");
+    if (out_waves && wave_stride == 0) return fail(c, -3, "rr_simulate_paths: wave_stride must be positive");
+    RR_HIP(c, hipSetDevice(c->device));
+    rc = upload_tables(c); if (rc) return rc;
+    const rr_config& g = c->cfg;
+    const size_t A = (size_t)g.n_angles, npx = A * (size_t)g.n_cells;
+    Lane& L = c->lanes[0];
+    hipStream_t s = c->stream;
+    rc = settle_lane(c, L); if (rc) return rc;               // the image is assembled in the buffer of delivery slot 0, as rr_simulate does
+    rc = prepare_lane(c, L, (int)A); if (rc) return rc;
+    // the device-side row: as long as the caller's, and no longer than a list can get (every pass' wave bound)
+    size_t longest = 0;
+    { const long n_beam = (long)(c->beams.size() / 3); long w = n_beam;
+      for (int p = 0; p < g.n_reflections; p++) { longest += (size_t)std::min<long>(w, L.buf_cap); w = std::min<long>(2 * w, L.buf_cap); } }
+    const size_t d_stride = out_waves ? std::max<size_t>(1, std::min(wave_stride, longest)) : 0;
+    RR_HIP(c, L.slot[0].img.ensure(npx));
+    if (out_waves) RR_HIP(c, L.d_wave_out.ensure(A * d_stride * 4));
+    if (out_wave_counts) RR_HIP(c, L.d_wave_out_counts.ensure(A));
+    if (out_pass_counts) RR_HIP(c, L.d_wave_out_passes.ensure(A * RR_WAVES_MAX_PASSES));
+    rc = paths_batch(c, 0, pose, 1, L.slot[0].img.p, out_waves ? reinterpret_cast<rr_wave_rec*>(L.d_wave_out.p) : nullptr, d_stride,
+                     out_wave_counts ? L.d_wave_out_counts.p : nullptr, out_pass_counts ? L.d_wave_out_passes.p : nullptr, flags, s);
+    if (rc) return rc;
+    // outputs are staged: a call that fails below has written nothing
+    std::vector<uint8_t> h8(npx); std::vector<uint32_t> hc(out_wave_counts ? A : 0), hp(out_pass_counts ? A * RR_WAVES_MAX_PASSES : 0);
+    std::vector<rr_wave_rec> hw(out_waves ? A * d_stride : 0);
+    RR_HIP(c, hipMemcpyAsync(h8.data(), L.slot[0].img.p, npx, hipMemcpyDeviceToHost, s));
+    if (out_wave_counts) RR_HIP(c, hipMemcpyAsync(hc.data(), L.d_wave_out_counts.p, A * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (out_pass_counts) RR_HIP(c, hipMemcpyAsync(hp.data(), L.d_wave_out_passes.p, hp.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (!hw.empty()) RR_HIP(c, hipMemcpyAsync(hw.data(), L.d_wave_out.p, hw.size() * sizeof(rr_wave_rec), hipMemcpyDeviceToHost, s));
+    RR_HIP(c, give_lane(L, s));
+    RR_HIP(c, hipStreamSynchronize(s));
+    rc = report_frame_errors(c); if (rc) return rc;
+    std::memcpy(out_u8, h8.data(), npx);
+    if (out_wave_counts) std::memcpy(out_wave_counts, hc.data(), A * sizeof(uint32_t));
+    if (out_pass_counts) std::memcpy(out_pass_counts, hp.data(), hp.size() * sizeof(uint32_t));
+    if (out_waves)          // only the records that exist reach the caller's rows
+        for (size_t a = 0; a < A; a++)
+            std::memcpy(out_waves + a * wave_stride, hw.data() + a * d_stride, std::min((size_t)hc[a], d_stride) * sizeof(rr_wave_rec));
     return 0;
 }
 

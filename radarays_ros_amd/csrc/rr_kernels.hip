@@ -23,36 +23,7 @@ namespace rr {
 // ---------------------------------------------------------------------------
 // common
 // ---------------------------------------------------------------------------
-__device__ inline Quat ld_quat(const float4* p) { const float4 v = *p; return { v.x, v.y, v.z, v.w }; }
-
-// Tam = Tsm * Tas (RadarCPU.cpp:201-206); Tas.t = 0.
-// ARGS: the pass-0 trace launch reads the call's poses from its own by-value argument; everything behind it from the lane's
-// pose table, which that launch wrote (rr_device.h: Params::pose_table)
-template <bool ARGS>
-__device__ __forceinline__ void azimuth_frame(const Params& P, const PoseArgs* pa, int seg, Quat& q_am, V3& t_am)
-{
-    const int frame = seg / P.n_loc, az = P.az_begin + seg % P.n_loc;
-    const Quat q_as = ld_quat(P.q_as + az);
-    const int row = P.set_mode ? 0 : frame;      // a parameter batch: every set the same pose
-    Quat q_sm; V3 t_sm;
-    if constexpr (ARGS) {
-        const float* ps = pa->p[row];
-        q_sm = { ps[0], ps[1], ps[2], ps[3] }; t_sm = { ps[4], ps[5], ps[6] };
-    } else {
-        const float4 a = P.pose_table[2 * row], b = P.pose_table[2 * row + 1];
-        q_sm = { a.x, a.y, a.z, a.w }; t_sm = { b.x, b.y, b.z };
-    }
-    if (P.motion_poses) {     // include_motion: Tsm looked up per azimuth (RadarCPU.cpp:190-196)
-        const float* ps = P.motion_poses + 7 * ((size_t)(frame % P.motion_rows) * P.n_angles + az);
-        q_sm = { ps[0], ps[1], ps[2], ps[3] }; t_sm = { ps[4], ps[5], ps[6] };
-    }
-    q_am = q_mul(q_sm, q_as);
-    // Tas.t = 0: the reference forms R_sm * 0 + t_sm (rmagine T1 * T2).  Rotating the zero vector gives (+-0, +-0, +-0) for
-    // any finite quaternion and x + (+-0) = x, so t_am IS t_sm (only the sign of a zero component of t_sm could differ, which
-    // no ray can see): 59 instructions per wave less in k_trace than the two quaternion products of the literal form
-    t_am = t_sm;
-}
-
+// (ld_quat and azimuth_frame: rr_device.h, shared with rr_paths.hip)
 struct Hit { float t; uint32_t tri; uint32_t face; };
 
 // ---------------------------------------------------------------------------

@@ -36,6 +36,7 @@ SYMBOLS = [
     "rr_shift_images_device", "rr_shift_images", "rr_simulate_batch_shift",
     "rr_describe_images_device", "rr_describe_images", "rr_simulate_batch_describe", "rr_match_descriptors_device", "rr_match_descriptors",
     "rr_simulate_batch_provenance_device", "rr_simulate_provenance", "rr_debug_labels",
+    "rr_simulate_batch_paths_device", "rr_simulate_paths",
 ]
 
 
@@ -103,6 +104,18 @@ def unpack_info(info):
     RR_LABEL_NONE unpacks to (0xFFFFFF, 15, 1) with the unused top bits set: mask such pixels with `info != LABEL_NONE` first."""
     i = np.asarray(info, np.uint32)
     return i & np.uint32(0xFFFFFF), (i >> np.uint32(24)) & np.uint32(15), (i >> np.uint32(28)) & np.uint32(1)
+
+
+# rr_wave_rec as numpy sees it (64 B): one ray-cast wave of an azimuth's wave list (rr_simulate_paths); WavRec is the same record for ctypes
+WAVE_DTYPE = np.dtype([("o", "<f4", (3,)), ("range", "<f4"), ("d", "<f4", (3,)), ("face", "<u4"), ("energy", "<f8"), ("time", "<f8"),
+                       ("info", "<u4"), ("parent", "<i4"), ("material", "<u4"), ("echo", "<i4")])
+WAVES_MAP_FRAME = 1
+WAVES_MAX_PASSES = 16
+
+
+class RRWaveRec(C.Structure):
+    _fields_ = [("o", C.c_float * 3), ("range", C.c_float), ("d", C.c_float * 3), ("face", C.c_uint32), ("energy", C.c_double),
+                ("time", C.c_double), ("info", C.c_uint32), ("parent", C.c_int32), ("material", C.c_uint32), ("echo", C.c_int32)]
 
 
 # rr_radar_point as numpy sees it (24 B: a PointCloud's point + its intensity channel, and where it came from)
@@ -375,6 +388,8 @@ def lib():
     L.rr_match_descriptors.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.rr_simulate_batch_provenance_device.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, C.c_size_t, vp, vp]
     L.rr_simulate_provenance.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    L.rr_simulate_batch_paths_device.argtypes = [vp, vp, C.c_int, vp, vp, C.c_size_t, vp, vp, C.c_uint, vp]
+    L.rr_simulate_paths.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp, C.c_uint]
     L.rr_debug_labels.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_size_t, vp, vp]
     for n in SYMBOLS:
         getattr(L, n)
@@ -1225,6 +1240,37 @@ class Context:
         ech = np.zeros((A, echo_stride), ECHO_SRC_DTYPE) if echo_stride else None
         self._ck(self._L.rr_simulate_provenance(self._h, p.ctypes.data, u8.ctypes.data, ptr(lab), ptr(fac), ptr(ech), echo_stride, cnt.ctypes.data))
         return u8, lab, fac, ech, cnt
+
+    # ---- wave paths (include/radarays_mi355.h): every ray-cast wave's ray, hit, parent and echo per azimuth
+    def simulate_batch_paths_device(self, poses, d_imgs_ptr, d_waves_ptr=None, wave_stride=0, d_wave_counts_ptr=None, d_pass_counts_ptr=None,
+                                    flags=0, stream=None):
+        """rr_simulate_batch_paths_device: the images of rr_simulate_batch_device and, in HBM, the wave lists WAVE_DTYPE
+        [n][n_angles][wave_stride] with their true counts uint32 [n][n_angles] and the waves per pass uint32 [n][n_angles][16]."""
+        p = np.ascontiguousarray(poses, np.float32).reshape(-1, 7)
+        self._ck(self._L.rr_simulate_batch_paths_device(self._h, p.ctypes.data, len(p), d_imgs_ptr, d_waves_ptr, int(wave_stride),
+                                                        d_wave_counts_ptr, d_pass_counts_ptr, int(flags), stream))
+
+    def simulate_paths(self, pose, wave_stride=None, map_frame=False):
+        """rr_simulate_paths: one frame -> (u8 [n_cells][n_angles], waves WAVE_DTYPE [n_angles][wave_stride], counts uint32 [n_angles],
+        pass_counts uint32 [n_angles][16]).  wave_stride None: every wave (a first call for the counts sizes the rows); 0: no records
+        (waves None, counts still true)."""
+        p = np.ascontiguousarray(pose, np.float32)
+        if p.shape != (7,):
+            raise ValueError("pose must be [7] (qx qy qz qw tx ty tz), got %s" % (p.shape,))
+        n_cells = self.cfg.n_cells if self.cfg is not None else 1   # unconfigured: the library reports it
+        A = self.n_angles
+        u8 = np.zeros((n_cells, A), np.uint8)
+        cnt = np.zeros(A, np.uint32)
+        pc = np.zeros((A, WAVES_MAX_PASSES), np.uint32)
+        flags = WAVES_MAP_FRAME if map_frame else 0
+        if wave_stride is None:
+            self._ck(self._L.rr_simulate_paths(self._h, p.ctypes.data, u8.ctypes.data, None, 0, cnt.ctypes.data, None, flags))
+            wave_stride = max(int(cnt.max()), 1)
+        wave_stride = _int_in(wave_stride, 0, 1 << 26, "wave_stride")
+        wav = np.zeros((A, wave_stride), WAVE_DTYPE) if wave_stride else None
+        self._ck(self._L.rr_simulate_paths(self._h, p.ctypes.data, u8.ctypes.data, None if wav is None else wav.ctypes.data, wave_stride,
+                                           cnt.ctypes.data, pc.ctypes.data, flags))
+        return u8, wav, cnt, pc
 
     def debug_labels(self, echoes, counts, az_begin=0):
         """rr_debug_labels: the label kernel on caller-given streams, echoes ECHO_SRC_DTYPE [n_seg][stride], counts [n_seg], under the

@@ -21,6 +21,54 @@ from .params import (N_ANGLES, WAVE_ENERGY_THRESHOLD, RadarModelConfig, RadarPar
 unpack_info = native.unpack_info      # info word of an echo / label pixel -> (object, pass, kind)
 
 
+# ---- wave paths: pure-numpy helpers over the records of simulate_paths (native.WAVE_DTYPE, ONE azimuth's list unless said otherwise)
+def unpack_wave_info(info):
+    """the info word of a wave record -> (object id, pass, branch, has_path_echo, has_multipath_echo); a miss has object 0xFFFFFF;
+    branch 0: emitted beam, 1: reflection child, 2: transmission child.  Arrays or scalars."""
+    i = np.asarray(info, np.uint32)
+    return (i & np.uint32(0xFFFFFF), (i >> np.uint32(24)) & np.uint32(15), (i >> np.uint32(28)) & np.uint32(3),
+            (i >> np.uint32(30)) & np.uint32(1), (i >> np.uint32(31)) & np.uint32(1))
+
+
+def hit_points(records):
+    """o + range * d of every record (f32, any shape of records -> [..., 3]); NaN for a wave that missed."""
+    r = np.asarray(records)
+    rng = r["range"].astype(np.float32)
+    p = r["o"] + rng[..., None] * r["d"]
+    p[rng < 0] = np.nan
+    return p.astype(np.float32)
+
+
+def path_to_wave(records, i):
+    """the chain of waves from the emitted beam to wave i of one azimuth's list: their indices, beam first (walks `parent`)."""
+    r = np.asarray(records)
+    chain = []
+    i = int(i)
+    while i >= 0:
+        if i >= len(r):
+            raise IndexError("wave %d lies beyond the %d records given (a truncated list?)" % (i, len(r)))
+        if len(chain) > 16:
+            raise ValueError("parent chain longer than the pass limit: not a wave list")
+        chain.append(i)
+        i = int(r["parent"][i])
+    return np.array(chain[::-1], np.int64)
+
+
+def path_to_echo(records, k):
+    """a ghost's route: the wave that owns echo k of the azimuth's echo stream, traced back to the beam ->
+    (wave indices beam first, polyline f32 [len + 1][3]: the beam's start point, then the hit point of every wave of the chain)."""
+    r = np.asarray(records)
+    k = int(k)
+    _, _, _, e0, e1 = unpack_wave_info(r["info"])
+    n_own = e0.astype(np.int64) + e1.astype(np.int64)
+    own = np.nonzero((r["echo"] >= 0) & (r["echo"] <= k) & (k < r["echo"] + n_own))[0]
+    if len(own) != 1:
+        raise IndexError("echo %d is owned by %d of the %d records given" % (k, len(own), len(r)))
+    chain = path_to_wave(r, own[0])
+    pts = np.concatenate([r["o"][chain[:1]], hit_points(r[chain])]).astype(np.float32)
+    return chain, pts
+
+
 @dataclass
 class Header:
     stamp: float = 0.0
@@ -349,6 +397,20 @@ class RadarHIP:
             pose = self.Tsm_last
         self._push()
         return self._ctx.simulate_provenance(pose, echo_stride=echo_stride)
+
+    def simulate_paths(self, pose=None, wave_stride=None, map_frame=False):
+        """By which route the waves travelled (rr_simulate_paths): the frame at `pose` ([7], default: the current Tsm) ->
+        (image u8 [n_cells][400], records native.WAVE_DTYPE [400][wave_stride], counts uint32 [400], pass_counts uint32 [400][16]).
+        records holds every azimuth's list of ray-cast waves (misses included), indexed by azimuth; counts its true lengths.
+        wave_stride None: one run to learn the counts, then the run that fills the rows.  map_frame: o / d in the map frame.
+        unpack_wave_info / hit_points / path_to_wave / path_to_echo read one azimuth's row, records[a][:counts[a]]."""
+        if pose is None:
+            if not self.updateTsm():
+                print("Couldn't get Transform between sensor and map. Skipping...")
+                return None
+            pose = self.Tsm_last
+        self._push()
+        return self._ctx.simulate_paths(pose, wave_stride=wave_stride, map_frame=map_frame)
 
     def _batch(self, poses, sweeps, stamp):
         """Offline generation (the twin of integration/.../RadarHIP.cpp: simulateBatch / simulateSweeps): one image per pose,
