@@ -8,57 +8,13 @@ import numpy as np
 import pytest
 
 from common import golden_beams, image_diff, materials_for, mats_tuple
+from dynamic_ref import about, identity_poses, posed_soup
 from radarays_ros_amd import params, scenes
 
 pytestmark = pytest.mark.gpu
 
 MEAN_DEV_TOL = 1e-5
 U8_MISMATCH_TOL = 1e-3
-IDENT = np.array([0, 0, 0, 1, 0, 0, 0], np.float32)
-
-
-# ---- the posed soup, with the library's arithmetic --------------------------------------------------------------------
-def q_rot(q, v):
-    """rr_device.h q_rot in its term order, float32, un-fused; q [n][4], v [n][3]"""
-    q = q.astype(np.float32); v = v.astype(np.float32)
-    qx, qy, qz, qw = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
-    vx, vy, vz = v[:, 0], v[:, 1], v[:, 2]
-    tx = qw * vx + qy * vz - qz * vy
-    ty = qw * vy - qx * vz + qz * vx
-    tz = qw * vz + qx * vy - qy * vx
-    tw = np.float32(0.0) - qx * vx - qy * vy - qz * vz
-    cx, cy, cz, cw = -qx, -qy, -qz, qw
-    rx = tw * cx + tx * cw + ty * cz - tz * cy
-    ry = tw * cy - tx * cz + ty * cw + tz * cx
-    rz = tw * cz + tx * cy - ty * cx + tz * cw
-    return np.stack([rx, ry, rz], -1).astype(np.float32)
-
-
-def posed_soup(scene, poses, verts=None):
-    v = scene["verts"] if verts is None else verts
-    f, o = scene["faces"], scene["face_object_id"]
-    poses = np.asarray(poses, np.float32).reshape(-1, 7)
-    corners = v[f.reshape(-1)].astype(np.float32)                # [3 nf][3]
-    P = poses[np.repeat(o, 3)]
-    moved = q_rot(P[:, :4], corners) + P[:, 4:]
-    ident = np.all(P == IDENT, axis=1)
-    moved[ident] = corners[ident]
-    out = dict(scene)
-    out["verts"] = moved.astype(np.float32)
-    out["faces"] = np.arange(3 * len(f), dtype=np.uint32).reshape(-1, 3)
-    return out
-
-
-def about(center, yaw, shift=(0.0, 0.0, 0.0)):
-    """a pose that turns by `yaw` about the vertical axis through `center`, then shifts"""
-    q = np.array([[0, 0, np.sin(yaw / 2), np.cos(yaw / 2)]], np.float32)
-    c = np.asarray(center, np.float32).reshape(1, 3)
-    t = c - q_rot(q, c) + np.asarray(shift, np.float32)
-    return np.concatenate([q[0], t[0]]).astype(np.float32)
-
-
-def identity_poses(n):
-    return np.tile(IDENT, (n, 1))
 
 
 # ---- contexts ---------------------------------------------------------------------------------------------------------
