@@ -425,8 +425,8 @@ def builder_id(builder):
 
 
 def make_config(cfg, n_angles=400, max_waves_per_azimuth=0, wave_energy_threshold=0.001,
-                ray_range_max=1000.0, brdf_model=0):
-    """RadarModelConfig (params.py) -> rr_config."""
+                ray_range_max=1000.0, brdf_model=0, theta_min=0.0, theta_inc=None):
+    """RadarModelConfig (params.py) -> rr_config.  theta_inc None: the reference's clockwise sweep, -2 pi / n_angles."""
     c = RRConfig()
     lib().rr_default_config(C.byref(c))
     c.n_cells = int(cfg.n_cells)
@@ -449,8 +449,8 @@ def make_config(cfg, n_angles=400, max_waves_per_azimuth=0, wave_energy_threshol
               "ambient_noise_energy_loss", "multipath_threshold"):
         setattr(c, k, float(getattr(cfg, k)))
     c.wave_energy_threshold = float(np.float32(wave_energy_threshold))
-    c.theta_min = 0.0
-    c.theta_inc = float(np.float32(-(2.0 * np.pi) / n_angles))   # Radar.cpp:27
+    c.theta_min = float(np.float32(theta_min))
+    c.theta_inc = float(np.float32(-(2.0 * np.pi) / n_angles if theta_inc is None else theta_inc))   # Radar.cpp:27
     c.range_max = float(ray_range_max)                            # radar_algorithms.cpp:158
     return c
 
