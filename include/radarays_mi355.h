@@ -151,6 +151,13 @@ int rr_copy_mesh(rr_ctx* ctx, rr_ctx* src);
  * change); the traversal stack bound depends on the topology only. */
 int rr_set_object_poses(rr_ctx* ctx, const float* poses /*[n][7]*/, size_t n);        /* n == n_objects */
 int rr_update_vertices(rr_ctx* ctx, const float* verts /*[nv][3]*/, size_t nv);       /* nv == rest nv: new rest geometry, poses kept */
+/* One TWIST PER OBJECT for the Doppler calls (below): float[6] = vx vy vz wx wy wz, map frame, m/s and rad/s, taken about the map
+ * origin: a point p of object b moves with v_b(p) = V_b + Omega_b x p (f32, the cross product in rr_device.h's v_cross term order, not
+ * fused).  n == n_objects, or 0: every twist back to zero; they are also zero after rr_set_mesh* / rr_copy_mesh.  The twists are
+ * stored by value and read only by the Doppler calls: nothing is drained, the tree and the launch graphs are not touched, and no
+ * other call renders differently.  Refused with the twists untouched: -2 without a mesh, -3 for a wrong count, a null array or a
+ * non-finite value. */
+int rr_set_object_twists(rr_ctx* ctx, const float* twists /*[n][6]*/, size_t n);
 /* SAH-style cost of the current boxes (sum over child records of half-area / the root's half-area, weighted 1 per inner
  * child and `count` per leaf child) and of the tree as built (measured at the first dynamic call on the tree) */
 int rr_get_tree_cost(rr_ctx* ctx, double* cost_now, double* cost_at_build);
@@ -637,6 +644,58 @@ int rr_simulate_batch_paths_device(rr_ctx* ctx, const float* poses, int n_frames
 /* one frame, host buffers, synchronous; out_waves and out_pass_counts may be NULL.  Returns -7 / -8 itself like rr_simulate. */
 int rr_simulate_paths(rr_ctx* ctx, const float pose[7], uint8_t* out_u8, rr_wave_rec* out_waves, size_t wave_stride,
                       uint32_t* out_wave_counts, uint32_t* out_pass_counts, unsigned flags);
+
+/* ---- Doppler: per-echo range rate and the FMCW range shift it causes (rr_doppler.hip) ------------------------------
+ * An FMCW sweep turns a target's range rate into a range offset, dr = kappa * v_r (kappa set by the chirp): the Doppler distortion
+ * of Navtech data (MulRan, Boreas, Oxford), next to the motion distortion of include_motion.  An opt-in variant of the pose-batch
+ * frame call renders the image from the SHIFTED echo stream and returns the range rate and the shifted cell of every echo.  The
+ * reference has no such output and renders every scene as if it stood still: parity is UNPINNED and this is the build's own
+ * definition (a numpy restatement in tests/doppler_ref.py checks the kernels bit for bit).
+ * Range rate of an echo.  For the echo of wave k of one azimuth follow `parent` (wave paths, above) back to the beam: the chain
+ * w_0 .. w_k.  Geometry in the map frame exactly as RR_WAVES_MAP_FRAME records it: u_i the direction of w_i, p_i = o_i + range_i * u_i
+ * its hit point, b_i the object of its face, v_i = v_{b_i}(p_i) (rr_set_object_twists), v_s the sensor's linear velocity in the map
+ * frame (the antenna origin is the pose's translation, so the antenna's spin moves no origin), t_am the azimuth's sensor origin.  The
+ * one-way path length is L = sum range_i; to first order (Fermat: a specular point sliding along its surface does not change L)
+ *     dL/dt = -(v_s . u_0) + sum_{i<k} v_i . (u_i - u_{i+1}) + v_k . u_k
+ *   path echo (kind 0)     : returns along the same path (time_back = 2 t): v_r = dL/dt
+ *   multipath echo (kind 1): returns straight to the sensor (RadarCPU.cpp:325-360): v_r = 0.5 * (dL/dt + (v_k - v_s) . e),
+ *                            e = normalize(p_k - t_am)
+ * Positive v_r: receding.  All f32, not fused; the sum is accumulated in the order written, from the beam to the echo; each
+ * difference u_i - u_{i+1} is formed before its dot product; dot products in rr_device.h's v_dot term order; normalize is
+ * v_normalize.  Transmission branches use the geometric length (the reference's waves all travel at 0.3 m/ns).
+ * Shifted cell.  `gain` is kappa in seconds (metres of range per m/s), finite, its sign the chirp direction.  With the echo's time as
+ * the chain forms it (RadarCPU.cpp:410-413: half_time = (float)(time / 2), signal_dist = (float)(0.3 * (double)half_time)):
+ *     r' = signal_dist + gain * v_r            (one f32 multiply, one f32 add, not fused)
+ *     cell' = (int)((double)r' / resolution)   when that quotient is finite and lies in [0, 2^31); otherwise the echo is dropped
+ * With gain == 0, or with every velocity zero, cell' is the chain's cell bit for bit.  Strength is unchanged.
+ * Outputs of rr_simulate_batch_doppler_device (device buffers, asynchronous on `stream`):
+ *   d_imgs_u8     [n][n_cells][n_angles]           the image the column step makes from the shifted stream (a list-only stream, the form
+ *                                                  rr_debug_column shows); denoiser, ambient noise, energy_max, scale and scroll as
+ *                                                  rr_simulate_batch_device
+ *   d_echo_vel    float [n][n_angles][echo_stride] or NULL: v_r of every echo
+ *   d_echo_cells  int32 [n][n_angles][echo_stride] or NULL: cell' of every echo, -1 for a dropped one
+ *                 both indexed exactly like the echo stream of rr_simulate_batch_provenance_device for the same pose: by AZIMUTH, in
+ *                 the reference's order, echoes beyond the image listed
+ *   d_echo_counts uint32 [n][n_angles] or NULL (required with either row buffer): the TRUE count; when it exceeds echo_stride the
+ *                 first echo_stride echoes are written and nothing beyond them
+ *   d_vel_img     float [n][n_cells][n_angles] or NULL: per pixel (image layout, scroll applied) the v_r of the echo that wins the bin
+ *                 by the label definition above (largest single term, ties to the earlier echo) applied to the shifted cells; NaN for
+ *                 a bin nobody reaches.  Needs n_cells <= RR_LABEL_MAX_CELLS
+ *   sensor_vel    float [n][3] per frame, or NULL: 0
+ * Pose batches only; rr_set_motion_poses (each azimuth its own t_am) and rr_set_noise_offsets apply as in the plain batch.  The chain
+ * is issued kernel by kernel, never from a launch graph, and the lane's launch graphs are left alone.  The lane's Doppler buffers (32
+ * bytes per wave and pass parity, 16 bytes per echo) are allocated by the first Doppler call; plain batches never touch them.
+ * rr_multi has no Doppler call: use the context of one device.
+ * Refused with a message and nothing written: -2 without a config / mesh / materials / beam; -3 for a null required buffer (poses,
+ * image, a row buffer without d_echo_counts), echo_stride == 0 with a row buffer, n_frames outside 1..RR_MAX_BATCH, a non-finite
+ * gain or sensor velocity, n_cells > RR_LABEL_MAX_CELLS with d_vel_img, the object / pass limits of the provenance info word. */
+int rr_simulate_batch_doppler_device(rr_ctx* ctx, const float* poses, int n_frames, const float* sensor_vel /*[n][3] or NULL = 0*/,
+                                     float gain, uint8_t* d_imgs_u8, float* d_echo_vel, size_t echo_stride, uint32_t* d_echo_counts,
+                                     int32_t* d_echo_cells, float* d_vel_img, void* stream);
+/* one frame, host buffers, synchronous; any output may be NULL except out_u8 (a row buffer needs out_echo_counts); out_f32 as
+ * rr_simulate's.  Returns -7 / -8 itself like rr_simulate. */
+int rr_simulate_doppler(rr_ctx* ctx, const float pose[7], const float sensor_vel[3], float gain, uint8_t* out_u8, float* out_f32,
+                        float* out_echo_vel, size_t echo_stride, uint32_t* out_echo_counts, int32_t* out_echo_cells, float* out_vel_img);
 
 /* ---- radar point clouds and Cartesian images from polar images (rr_detect.hip) ----------------------------------
  * The reference's pipeline turns every simulated image into a point cloud with radar_tools/radar_img_to_pcl

@@ -220,6 +220,32 @@ public:
         std::reverse(chain.begin(), chain.end());
         return chain;
     }
+    // The frame as an FMCW sweep sees a moving scene (rr_simulate_doppler, include/radarays_mi355.h), on device 0: the image of the
+    // shifted echo stream at the current Tsm and, per azimuth, every echo's range rate and shifted cell (-1: dropped), rows of
+    // `echo_stride` entries (0: one run first to learn the counts), the true counts and the velocity image (NaN: no echo reaches the
+    // bin).  sensor_vel: map frame, m/s (null: 0); gain: kappa in seconds; the objects' twists: rr_set_object_twists.  Null on error.
+    struct Doppler { ImagePtr image; std::vector<float> echo_vel, vel_image; std::vector<int32_t> echo_cells; std::vector<uint32_t> echo_counts; size_t echo_stride = 0; };
+    std::shared_ptr<Doppler> simulateDoppler(double stamp, const float* sensor_vel, float gain, size_t echo_stride = 0)
+    {
+        if (!updateTsm()) {
+            std::cout << "Couldn't get Transform between sensor and map. Skipping..." << std::endl;
+            return {};
+        }
+        if (!push()) return {};
+        auto out = std::make_shared<Doppler>();
+        out->image = image(nullptr, stamp);
+        out->echo_counts.assign((size_t)m_n_angles, 0u);
+        if (echo_stride == 0) {
+            if (rr_simulate_doppler(m_ctx, Tsm_last, sensor_vel, gain, out->image->data.data(), nullptr, nullptr, 0, out->echo_counts.data(), nullptr, nullptr)) { fail(); return {}; }
+            for (uint32_t n : out->echo_counts) echo_stride = std::max(echo_stride, (size_t)n);
+            echo_stride = std::max<size_t>(echo_stride, 1);
+        }
+        out->echo_vel.assign((size_t)m_n_angles * echo_stride, 0.0f); out->echo_cells.assign((size_t)m_n_angles * echo_stride, -1);
+        out->vel_image.assign(out->image->data.size(), 0.0f); out->echo_stride = echo_stride;
+        if (rr_simulate_doppler(m_ctx, Tsm_last, sensor_vel, gain, out->image->data.data(), nullptr, out->echo_vel.data(), echo_stride, out->echo_counts.data(),
+                                out->echo_cells.data(), out->vel_image.data())) { fail(); return {}; }
+        return out;
+    }
     // Offline generation (the twin of integration/src/radarays_ros/RadarHIP.cpp: simulateBatch / simulateSweeps): one image
     // per pose [n][7], up to RR_MAX_BATCH poses per set of launches; with per-azimuth pose tables (include_motion,
     // RadarCPU.cpp:190-196) sweeps = [n][n_angles][7], one table per frame (rr_multi_set_motion_poses)

@@ -85,6 +85,17 @@ struct Lane {
     DevBuf<uint4> d_path_state; int path_seg = 0;
     DevBuf<float4> d_wave_out; DevBuf<uint32_t> d_wave_out_counts, d_wave_out_passes;
 
+    // Doppler (rr_doppler.hip): k_rate_gather's state per wave and per segment, the rate list and the shifted list beside the lane's
+    // echo lists, what the list-only column launch needs (a zero count for the last pass' slots, statistics of its own), the winner
+    // columns; the call's sensor velocities and the twists on their way down (the host array stays alive with the lane, like the
+    // beam tables above).  Allocated by the lane's first Doppler call (ensure_dop_buffers); plain batches never touch them
+    DevBuf<float4> d_dop_state, d_dop_in; DevBuf<float2> d_dop_rate; DevBuf<SigRec> d_dop_sig; DevBuf<uint32_t> d_dop_count, d_dop_zero;
+    DevBuf<SegStats> d_dop_stats; DevBuf<float> d_dop_vel_cols;
+    std::vector<float4> h_dop_in;
+    int dop_seg = 0, dop_cap = 0, dop_echo_cap = 0, dop_cells = 0; size_t dop_obj = 0;
+    // rr_simulate_doppler: the outputs on their way to the host
+    DevBuf<float> d_dop_out_vel, d_dop_vel_img; DevBuf<int32_t> d_dop_out_cells; DevBuf<uint32_t> d_dop_out_counts;
+
     hipStream_t stream = nullptr;
     hipEvent_t ev_ready = nullptr, ev_consumed = nullptr;
     bool pending_consume = false;
@@ -124,6 +135,7 @@ struct rr_ctx {
     uint32_t n_objects = 1;
     std::vector<float> poses;              // [n_objects][7] qx qy qz qw tx ty tz
     DevBuf<float> d_poses, d_stage_poses;
+    std::vector<float> twists;             // [n_objects][6] vx vy vz wx wy wz (rr_set_object_twists): by value, read only by the Doppler calls
     bool dyn_ready = false;                // the per-level node lists below belong to the current tree
     bool rebuilding = false;               // rr_rebuild_tree: the build it runs keeps the rest data
     DevBuf<uint32_t> d_levels;             // node indices, root level first
@@ -310,7 +322,9 @@ hipError_t give_lane(Lane& L, hipStream_t s);
 int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, uint8_t* d_cols_u8 /* null: the lane's own buffer */, float* d_cols_f32,
               hipStream_t s, int n_frames = 1, const float4* d_matsets = nullptr, int mat_stride = 0, bool lane_f32 = false, const SetPlan* plan = nullptr,
               int provenance = 0 /* 1: the lane's echo lists are gathered; 2: and its label columns made */,
-              const WaveOut* paths = nullptr /* the wave records of every pass go to these rows (state: the lane's, filled in here) */);
+              const WaveOut* paths = nullptr /* the wave records of every pass go to these rows (state: the lane's, filled in here) */,
+              const DopArgs* doppler = nullptr /* gain and the caller's rows; a provenance chain whose image comes from the shifted list (the lane's buffers are filled in here) */,
+              const float* sensor_vel = nullptr /* [n_frames][3] with doppler, or null: 0 */);
 int assemble_frames(rr_ctx* c, const Lane& L, uint8_t* dst, int n_frames, hipStream_t s);
 
 }  // namespace rr

@@ -269,6 +269,23 @@ struct WaveOut {
 };
 constexpr int kWavePasses = 16;  // RR_WAVES_MAX_PASSES
 
+// Doppler (rr_doppler.hip): what k_rate_gather and the kernels behind the chain get beside Params -- like WaveOut a kernel argument
+// of its own.  Everything here is the lane's (allocated by its first Doppler call) except the caller's three output rows
+struct DopArgs {
+    const float4* in;            // [64 + 2 * n_objects]: the sensor's velocity per frame (xyz, 0), then per object (V, 0), (Omega, 0)
+    uint32_t n_objects;
+    float gain;                  // kappa, seconds
+    float4* wstate;              // [2][n_seg][cap][2] ping-pong by pass parity: (v of the hit point, running sum), (map-frame direction, -)
+    float2* rate;                // [n_seg][echo_cap] per echo of the lane's list: (v_r, signal_dist)
+    uint32_t* count;             // [n_seg] echoes so far: written by the gather launch of pass 0, advanced by the later ones
+    SigRec* shifted;             // [n_seg][echo_cap] the list k_column replays: (cell', strength)
+    float* vel_cols;             // [n_seg][n_cells] v_r of the echo that wins the bin, or null
+    float* echo_vel;             // caller: [n_seg][stride] or null
+    int32_t* echo_cells;         // caller: [n_seg][stride] or null
+    uint32_t* echo_counts;       // caller: [n_seg] or null
+    size_t stride;
+};
+
 static_assert(sizeof(Params) <= 4096, "Params is passed by value: HIP kernel arguments are limited to 4 KB");
 
 }  // namespace rr

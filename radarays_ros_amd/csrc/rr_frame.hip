@@ -180,6 +180,32 @@ int ensure_path_state(rr_ctx* c, Lane& L)
     return 0;
 }
 
+// The lane's Doppler buffers for its current frame and provenance buffers (after prepare_lane and ensure_prov_buffers): 32 bytes of
+// state per wave and pass parity, 16 bytes per echo of the lists, and the small arrays of the list-only column launch
+int ensure_dop_buffers(rr_ctx* c, Lane& L, bool want_vel)
+{
+    const size_t S = (size_t)L.buf_seg, n_in = 64 + 2 * (size_t)c->n_objects;
+    const bool fits = L.d_dop_state.p && L.dop_seg >= L.buf_seg && L.dop_cap == L.buf_cap && L.dop_echo_cap == L.prov_cap && L.dop_cells == L.buf_cells &&
+                      L.dop_obj >= n_in && (!want_vel || (L.d_dop_vel_cols.p && L.d_dop_vel_cols.n >= S * (size_t)L.buf_cells));
+    if (fits) return 0;
+    size_t free_b = 0, total_b = 0;
+    RR_HIP(c, hipMemGetInfo(&free_b, &total_b));
+    if (S * ((size_t)L.buf_cap * 64 + (size_t)L.prov_cap * 16 + (size_t)L.buf_cells * 4) > total_b / 2)
+        return fail(c, -6, "the wave states and echo lists of a Doppler call need more than half of device memory; fewer frames per call or a lower max_waves_per_azimuth");
+    RR_HIP(c, hipDeviceSynchronize());      // a Doppler chain in flight may still use the old buffers
+    RR_HIP(c, L.d_dop_state.ensure(2 * S * (size_t)L.buf_cap * 2));
+    RR_HIP(c, L.d_dop_rate.ensure(S * (size_t)L.prov_cap));
+    RR_HIP(c, L.d_dop_sig.ensure(S * (size_t)L.prov_cap));
+    RR_HIP(c, L.d_dop_count.ensure(S));
+    RR_HIP(c, L.d_dop_zero.ensure(S));
+    RR_HIP(c, hipMemset(L.d_dop_zero.p, 0, S * sizeof(uint32_t)));
+    RR_HIP(c, L.d_dop_stats.ensure(2 * S));
+    RR_HIP(c, L.d_dop_in.ensure(n_in));
+    if (want_vel) RR_HIP(c, L.d_dop_vel_cols.ensure(S * (size_t)L.buf_cells));
+    L.dop_seg = L.buf_seg; L.dop_cap = L.buf_cap; L.dop_echo_cap = L.prov_cap; L.dop_cells = L.buf_cells; L.dop_obj = n_in;
+    return 0;
+}
+
 // device -> host on stream s: the library's own copy kernel (8 workgroups, all on XCD 0) when the destination is page-locked
 // (`visible`) and everything is 16-byte aligned, else hipMemcpyAsync (rr_copy_to_host_async in the header says why)
 int copy_out(rr_ctx* c, const void* d_src, void* h_dst, size_t bytes, bool visible, hipStream_t s)
@@ -252,7 +278,8 @@ int choose_trace_rows(rr_ctx* c, Lane& L, Params& P, const rr_config& g, hipStre
 }
 
 // the launch chain of the batch
-int issue_chain(rr_ctx* c, const Params& Q, const PoseArgs& pa, const rr_config& g, hipStream_t s, const WaveOut* wo = nullptr)
+int issue_chain(rr_ctx* c, const Params& Q, const PoseArgs& pa, const rr_config& g, hipStream_t s, const WaveOut* wo = nullptr,
+                const DopArgs* da = nullptr, const Params* Qlist = nullptr /* with da: Q as the list-only column launch reads the shifted list */)
 {
     for (int pass = 0; pass < g.n_reflections; pass++) {
         if (c->roctx) roctx_push(pass == 0 ? "trace pass 0" : "trace");
@@ -274,6 +301,7 @@ int issue_chain(rr_ctx* c, const Params& Q, const PoseArgs& pa, const rr_config&
         { KernelEvents t(c, "shade"); launch_shade(Q, pass, s, t.a, t.b); }
         if (Q.prov) { KernelEvents t(c, "gather"); launch_echo_gather(Q, pass, s, t.a, t.b); }
         if (wo) { KernelEvents t(c, "waves"); launch_wave_gather(Q, pass, *wo, s, t.a, t.b); }
+        if (da) { KernelEvents t(c, "rates"); launch_rate_gather(Q, pass, *da, s, t.a, t.b); }
         if (pass < g.n_reflections - 1) { KernelEvents t(c, "scan"); launch_scan(Q, pass, s, t.a, t.b); }
     }
     { KernelEvents t(c, "column"); launch_column(Q, s, t.a, t.b); }
@@ -282,6 +310,11 @@ int issue_chain(rr_ctx* c, const Params& Q, const PoseArgs& pa, const rr_config&
         const bool den = Q.signal_denoising > 0;
         launch_label(Q.prov, Q.prov_count, (size_t)Q.prov_cap, Q.n_seg, Q.n_cells, den ? Q.smear_w : 1, den ? Q.smear_mode : 0, den ? Q.smear : nullptr,
                      Q.label_cols, Q.face_cols, s, t.a, t.b);
+    }
+    if (da) {       // Doppler: the lane's echo lists -> the shifted list, which the column step replays as a list-only stream (rr_debug_column's form)
+        { KernelEvents t(c, "shift"); launch_doppler_shift(Q, *da, s, t.a, t.b); }
+        { KernelEvents t(c, "column"); launch_column(*Qlist, s, t.a, t.b); }
+        if (da->vel_cols) { KernelEvents t(c, "winner"); launch_vel_winner(Q, *da, s, t.a, t.b); }
     }
     return 0;
 }
@@ -474,6 +507,46 @@ int paths_batch(rr_ctx* c, size_t li, const float* poses, int n_frames, uint8_t*
     return 0;
 }
 
+// the refusals of the two Doppler entry points (nothing is written): those of the paths call, and a non-finite gain or sensor velocity
+int check_doppler(rr_ctx* c, const char* who, const void* poses, int n_frames, const float* sensor_vel, float gain, const void* imgs, const void* vel,
+                  const void* cells, size_t echo_stride, const void* counts, const void* vel_img)
+{
+    int rc = check_ready(c); if (rc) return rc;
+    const std::string w(who);
+    if (!poses || !imgs) return fail(c, -3, w + ": null poses/output");
+    if (n_frames < 1 || n_frames > RR_MAX_BATCH) return fail(c, -3, w + ": n_frames must be 1..64");
+    if ((vel || cells) && !counts) return fail(c, -3, w + ": an echo buffer needs a count buffer");
+    if ((vel || cells) && echo_stride == 0) return fail(c, -3, w + ": echo_stride must be positive");
+    if (!std::isfinite(gain)) return fail(c, -3, w + ": non-finite gain");
+    for (int k = 0; sensor_vel && k < 3 * n_frames; k++) if (!std::isfinite(sensor_vel[k])) return fail(c, -3, w + ": non-finite sensor velocity");
+    if (vel_img && c->cfg.n_cells > kLabelMaxCells) return fail(c, -3, w + ": n_cells exceeds RR_LABEL_MAX_CELLS (8192) with a velocity image");
+    if (c->n_objects >= 0xFFFFFFu) return fail(c, -3, w + ": the info word holds object ids below 2^24 - 1");
+    if (c->cfg.n_reflections > 16) return fail(c, -3, w + ": the info word holds passes below 16 (n_reflections <= 16)");
+    return 0;
+}
+
+// a pose batch with Doppler on lane li (taken and handed back here), everything enqueued on s.  d_img_f32: the f32 image of ONE frame
+int doppler_batch(rr_ctx* c, size_t li, const float* poses, int n_frames, const float* sensor_vel, float gain, uint8_t* d_imgs_u8, float* d_img_f32,
+                  float* d_echo_vel, size_t echo_stride, uint32_t* d_echo_counts, int32_t* d_echo_cells, float* d_vel_img, hipStream_t s)
+{
+    Lane& L = c->lanes[li];
+    const rr_config& g = c->cfg;
+    int rc = take_lane(c, li, s); if (rc) return rc;
+    DopArgs da{};      // (whole frames: segment = frame * n_angles + azimuth, the layout of the caller's buffers; the lane's part: run_frame)
+    da.gain = gain; da.vel_cols = d_vel_img;      // (non-null: asked for)
+    da.echo_vel = d_echo_vel; da.echo_cells = d_echo_cells; da.echo_counts = d_echo_counts; da.stride = (d_echo_vel || d_echo_cells) ? echo_stride : 0;
+    rc = run_frame(c, L, poses, 0, g.n_angles, nullptr, nullptr, s, n_frames, nullptr, 0, d_img_f32 != nullptr, nullptr, 1, nullptr, &da, sensor_vel);
+    if (rc) return rc;
+    rc = assemble_frames(c, L, d_imgs_u8, n_frames, s); if (rc) return rc;
+    { TimedScope t(c, s, "assemble");
+      if (d_img_f32) launch_assemble_f32(L.d_cols_f32.p, d_img_f32, g.n_angles, g.n_cells, g.scroll_image, s);
+      if (d_vel_img) launch_assemble_u32(reinterpret_cast<const uint32_t*>(L.d_dop_vel_cols.p), reinterpret_cast<uint32_t*>(d_vel_img), g.n_angles, g.n_cells,
+                                         g.scroll_image, s, n_frames); }
+    RR_HIP(c, hipGetLastError());
+    RR_HIP(c, give_lane(L, s));
+    return 0;
+}
+
 }  // namespace
 
 void drop_graphs(Lane& L)
@@ -547,7 +620,8 @@ hipError_t give_lane(Lane& L, hipStream_t s)
 }
 
 int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, uint8_t* d_cols_u8 /* null: the lane's own buffer */, float* d_cols_f32, hipStream_t s, int n_frames,
-              const float4* d_matsets, int mat_stride, bool lane_f32, const SetPlan* plan, int provenance, const WaveOut* paths)
+              const float4* d_matsets, int mat_stride, bool lane_f32, const SetPlan* plan, int provenance, const WaveOut* paths, const DopArgs* doppler,
+              const float* sensor_vel)
 {
     const rr_config g = eff_config(c);      // (a parameter batch may ask for more passes than the config)
     if (az_begin < 0 || az_end > g.n_angles || az_begin > az_end) return fail(c, -3, "azimuth range out of bounds");
@@ -563,8 +637,26 @@ int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, u
         return fail(c, -3, "a pose batch while ONE per-azimuth pose table is set (rr_set_motion_poses): give one table per frame (k x n_angles poses) or clear the table");
     if (provenance && d_matsets) return fail(c, -3, "echo provenance is for pose batches: the frames of a parameter batch share the hits of pass 0");
     if (paths && d_matsets) return fail(c, -3, "wave paths are for pose batches: the frames of a parameter batch share the hits of pass 0");
+    if (doppler && (d_matsets || !provenance)) return fail(c, -3, "Doppler is for pose batches with their echo lists: the frames of a parameter batch share the hits of pass 0");
     rc = prepare_lane(c, L, n_seg, lane_f32); if (rc) return rc;
     if (provenance) { rc = ensure_prov_buffers(c, L); if (rc) return rc; }
+    DopArgs da{};
+    if (doppler) {
+        rc = ensure_dop_buffers(c, L, doppler->vel_cols != nullptr); if (rc) return rc;
+        da = *doppler;
+        da.in = L.d_dop_in.p; da.n_objects = c->n_objects; da.wstate = L.d_dop_state.p; da.rate = L.d_dop_rate.p; da.count = L.d_dop_count.p;
+        da.shifted = L.d_dop_sig.p; da.vel_cols = doppler->vel_cols ? L.d_dop_vel_cols.p : nullptr;
+        // the sensor's velocities and the twists ride down behind the lane's previous user.  The host array lives with the lane; the
+        // copy of the lane's previous Doppler call has left it before it is written again
+        if (L.pending_consume) RR_HIP(c, hipEventSynchronize(L.ev_consumed));
+        L.h_dop_in.assign(64 + 2 * (size_t)c->n_objects, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+        for (int f = 0; f < n_frames && sensor_vel; f++) L.h_dop_in[(size_t)f] = make_float4(sensor_vel[3 * f], sensor_vel[3 * f + 1], sensor_vel[3 * f + 2], 0.0f);
+        for (size_t o = 0; o < (size_t)c->n_objects && 6 * o + 5 < c->twists.size(); o++) {
+            const float* t = c->twists.data() + 6 * o;
+            L.h_dop_in[64 + 2 * o] = make_float4(t[0], t[1], t[2], 0.0f); L.h_dop_in[64 + 2 * o + 1] = make_float4(t[3], t[4], t[5], 0.0f);
+        }
+        RR_HIP(c, hipMemcpyAsync(L.d_dop_in.p, L.h_dop_in.data(), L.h_dop_in.size() * sizeof(float4), hipMemcpyHostToDevice, s));
+    }
     WaveOut wo{};
     if (paths) { rc = ensure_path_state(c, L); if (rc) return rc; wo = *paths; wo.state = L.d_path_state.p; }
     if (!d_cols_u8) d_cols_u8 = L.d_cols_u8.p;       // the lane's own column buffer, valid only from here on
@@ -594,6 +686,7 @@ int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, u
     }
     if (c->stats_mode || g.n_reflections == 0) RR_HIP(c, hipMemsetAsync(L.d_counters.p, 0, sizeof(Counters), s));
     if (provenance && g.n_reflections == 0) RR_HIP(c, hipMemsetAsync(L.d_prov_count.p, 0, (size_t)n_seg * sizeof(uint32_t), s));     // no pass, no gather launch
+    if (doppler && g.n_reflections == 0) RR_HIP(c, hipMemsetAsync(da.count, 0, (size_t)n_seg * sizeof(uint32_t), s));     // no pass, no gather launch
     if (paths && g.n_reflections == 0) {      // no pass, no gather launch
         if (wo.counts) RR_HIP(c, hipMemsetAsync(wo.counts, 0, (size_t)n_seg * sizeof(uint32_t), s));
         if (wo.pass_counts) RR_HIP(c, hipMemsetAsync(wo.pass_counts, 0, (size_t)n_seg * kWavePasses * sizeof(uint32_t), s));
@@ -613,7 +706,7 @@ int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, u
     // does not even look at the lane's graphs: a plain batch afterwards replays as before); whatever a captured launch bakes in is
     // covered by graph_gen (tables, tree, lane buffers) or by the key (azimuth block, frames, output buffer, trace rows)
     if (L.graph_gen != c->graph_gen) { drop_graphs(L); L.graph_gen = c->graph_gen; }
-    const bool graphable = !d_matsets && c->use_graphs && !c->timing && !c->stats_mode && !c->roctx && !d_cols_f32 && !provenance && !paths && g.n_reflections > 0;
+    const bool graphable = !d_matsets && c->use_graphs && !c->timing && !c->stats_mode && !c->roctx && !d_cols_f32 && !provenance && !paths && !doppler && g.n_reflections > 0;
     if (graphable) {
         Lane::FrameGraph* fg = find_graph(L, az_begin, az_end, n_frames, d_cols_u8, P);
         fg->last_use = ++c->graph_clock;
@@ -621,7 +714,15 @@ int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, u
         if (fg->ge) return replay_graph(c, fg, pa, s);
         fg->hits++;
     }
-    { HostProfScope hp(5, "ctx:   chain issued kernel by kernel"); const int rcq = issue_chain(c, P, pa, g, s, paths ? &wo : nullptr); if (rcq) return rcq; }
+    Params Plist;
+    if (doppler) {      // the list-only form of the column launch: two passes on paper, the list = the shifted echoes, no slot of a last pass
+        Plist = P;
+        Plist.n_passes = 2; Plist.sig = da.shifted; Plist.sig_count = da.count; Plist.sigcap = L.prov_cap;
+        Plist.count[1] = L.d_dop_zero.p; Plist.seg_stats = L.d_dop_stats.p;      // (the chain's own statistics stay as its k_column left them)
+        Plist.hist_host = nullptr; Plist.grid_hint = nullptr;
+    }
+    { HostProfScope hp(5, "ctx:   chain issued kernel by kernel");
+      const int rcq = issue_chain(c, P, pa, g, s, paths ? &wo : nullptr, doppler ? &da : nullptr, doppler ? &Plist : nullptr); if (rcq) return rcq; }
     RR_HIP(c, hipGetLastError());
     return 0;
 }
@@ -780,6 +881,69 @@ int rr_simulate_paths(rr_ctx* c, const float pose[7], uint8_t* out_u8, rr_wave_r
     if (out_waves)          // only the records that exist reach the caller's rows
         for (size_t a = 0; a < A; a++)
             std::memcpy(out_waves + a * wave_stride, hw.data() + a * d_stride, std::min((size_t)hc[a], d_stride) * sizeof(rr_wave_rec));
+    return 0;
+}
+
+int rr_simulate_batch_doppler_device(rr_ctx* c, const float* poses, int n_frames, const float* sensor_vel, float gain, uint8_t* d_imgs_u8,
+                                     float* d_echo_vel, size_t echo_stride, uint32_t* d_echo_counts, int32_t* d_echo_cells, float* d_vel_img, void* stream)
+{
+    int rc = check_doppler(c, "rr_simulate_batch_doppler_device", poses, n_frames, sensor_vel, gain, d_imgs_u8, d_echo_vel, d_echo_cells, echo_stride,
+                           d_echo_counts, d_vel_img);
+    if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    rc = upload_tables(c); if (rc) return rc;
+    return doppler_batch(c, c->next_lane++ % c->lanes.size(), poses, n_frames, sensor_vel, gain, d_imgs_u8, nullptr, d_echo_vel, echo_stride, d_echo_counts,
+                         d_echo_cells, d_vel_img, stream_of(c, stream));
+}
+
+int rr_simulate_doppler(rr_ctx* c, const float pose[7], const float sensor_vel[3], float gain, uint8_t* out_u8, float* out_f32, float* out_echo_vel,
+                        size_t echo_stride, uint32_t* out_echo_counts, int32_t* out_echo_cells, float* out_vel_img)
+{
+    int rc = check_doppler(c, "rr_simulate_doppler", pose, 1, sensor_vel, gain, out_u8, out_echo_vel, out_echo_cells, echo_stride, out_echo_counts, out_vel_img);
+    if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    rc = upload_tables(c); if (rc) return rc;
+    const rr_config& g = c->cfg;
+    const size_t A = (size_t)g.n_angles, npx = A * (size_t)g.n_cells;
+    Lane& L = c->lanes[0];
+    hipStream_t s = c->stream;
+    rc = settle_lane(c, L); if (rc) return rc;               // the image is assembled in the buffer of delivery slot 0, as rr_simulate does
+    // the device-side rows: as long as the caller's, and no longer than a list can get
+    rc = prepare_lane(c, L, (int)A, out_f32 != nullptr); if (rc) return rc;
+    rc = ensure_prov_buffers(c, L); if (rc) return rc;
+    const bool rows = out_echo_vel || out_echo_cells;
+    const size_t d_stride = rows ? std::min(echo_stride, (size_t)L.prov_cap) : 0;
+    RR_HIP(c, L.slot[0].img.ensure(npx));
+    if (out_f32) RR_HIP(c, L.d_img_f32.ensure(npx));
+    if (out_echo_vel) RR_HIP(c, L.d_dop_out_vel.ensure(A * d_stride));
+    if (out_echo_cells) RR_HIP(c, L.d_dop_out_cells.ensure(A * d_stride));
+    if (out_echo_counts) RR_HIP(c, L.d_dop_out_counts.ensure(A));
+    if (out_vel_img) RR_HIP(c, L.d_dop_vel_img.ensure(npx));
+    rc = doppler_batch(c, 0, pose, 1, sensor_vel, gain, L.slot[0].img.p, out_f32 ? L.d_img_f32.p : nullptr, out_echo_vel ? L.d_dop_out_vel.p : nullptr, d_stride,
+                       out_echo_counts ? L.d_dop_out_counts.p : nullptr, out_echo_cells ? L.d_dop_out_cells.p : nullptr,
+                       out_vel_img ? L.d_dop_vel_img.p : nullptr, s);
+    if (rc) return rc;
+    // outputs are staged: a call that fails below has written nothing
+    std::vector<uint8_t> h8(npx); std::vector<float> hf(out_f32 ? npx : 0), hv(out_echo_vel ? A * d_stride : 0), hi(out_vel_img ? npx : 0);
+    std::vector<int32_t> hcl(out_echo_cells ? A * d_stride : 0); std::vector<uint32_t> hc(out_echo_counts ? A : 0);
+    RR_HIP(c, hipMemcpyAsync(h8.data(), L.slot[0].img.p, npx, hipMemcpyDeviceToHost, s));
+    if (out_f32) RR_HIP(c, hipMemcpyAsync(hf.data(), L.d_img_f32.p, npx * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (!hv.empty()) RR_HIP(c, hipMemcpyAsync(hv.data(), L.d_dop_out_vel.p, hv.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (!hcl.empty()) RR_HIP(c, hipMemcpyAsync(hcl.data(), L.d_dop_out_cells.p, hcl.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (out_echo_counts) RR_HIP(c, hipMemcpyAsync(hc.data(), L.d_dop_out_counts.p, A * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (out_vel_img) RR_HIP(c, hipMemcpyAsync(hi.data(), L.d_dop_vel_img.p, npx * sizeof(float), hipMemcpyDeviceToHost, s));
+    RR_HIP(c, give_lane(L, s));
+    RR_HIP(c, hipStreamSynchronize(s));
+    rc = report_frame_errors(c); if (rc) return rc;
+    std::memcpy(out_u8, h8.data(), npx);
+    if (out_f32) std::memcpy(out_f32, hf.data(), npx * sizeof(float));
+    if (out_vel_img) std::memcpy(out_vel_img, hi.data(), npx * sizeof(float));
+    if (out_echo_counts) std::memcpy(out_echo_counts, hc.data(), A * sizeof(uint32_t));
+    for (size_t a = 0; rows && a < A; a++) {          // only the echoes that exist reach the caller's rows
+        const size_t m = std::min((size_t)hc[a], d_stride);
+        if (out_echo_vel) std::memcpy(out_echo_vel + a * echo_stride, hv.data() + a * d_stride, m * sizeof(float));
+        if (out_echo_cells) std::memcpy(out_echo_cells + a * echo_stride, hcl.data() + a * d_stride, m * sizeof(int32_t));
+    }
     return 0;
 }
 

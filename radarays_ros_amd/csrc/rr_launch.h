@@ -1,4 +1,4 @@
-// rr_launch.h -- every launcher of rr_kernels.hip, rr_labels.hip, rr_paths.hip, rr_refit.hip, rr_detect.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip, rr_place.hip and rr_lbvh.hip, declared ONCE: included where they
+// rr_launch.h -- every launcher of rr_kernels.hip, rr_labels.hip, rr_paths.hip, rr_doppler.hip, rr_refit.hip, rr_detect.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip, rr_place.hip and rr_lbvh.hip, declared ONCE: included where they
 // are defined (a definition that drifts from its declaration fails there) and where they are called.  Default arguments live here only.
 #pragma once
 #include "../../include/radarays_mi355.h"
@@ -36,6 +36,10 @@ void launch_echo_export(const EchoSrc* lists, const uint32_t* counts, size_t cap
                         hipStream_t s);
 // rr_paths.hip (wave paths): one record per ray-cast wave of the pass into the caller's rows
 void launch_wave_gather(const Params& P, int pass, const WaveOut& W, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+// rr_doppler.hip (Doppler): per pass the range rate of every echo; behind the chain the shifted list and the winner's rate per bin
+void launch_rate_gather(const Params& P, int pass, const DopArgs& D, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+void launch_doppler_shift(const Params& P, const DopArgs& D, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+void launch_vel_winner(const Params& P, const DopArgs& D, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 bool build_bvh4_gpu(const float* verts, size_t nv, const uint32_t* faces, size_t nf, const uint32_t* face_object,
                     Node4** d_nodes_out, size_t* n_nodes_out, TriRec** d_tris_out, size_t* n_tris_out,
                     uint32_t* depth_out, uint32_t* stack_need_out, float* inflate_out,

@@ -50,6 +50,7 @@ int keep_rest(rr_ctx* c, const float* verts, size_t nv, const uint32_t* faces, s
     c->poses.assign(7 * (size_t)n_obj, 0.0f);
     for (uint32_t o = 0; o < n_obj; o++) c->poses[7 * (size_t)o + 3] = 1.0f;
     c->build_poses = c->poses;
+    c->twists.assign(6 * (size_t)n_obj, 0.0f);
     RR_HIP(c, c->d_poses.ensure(c->poses.size()));
     RR_HIP(c, hipMemcpy(c->d_poses.p, c->poses.data(), c->poses.size() * sizeof(float), hipMemcpyHostToDevice));
     c->d_stage_v.release(); c->d_stage_poses.release();
@@ -373,6 +374,7 @@ int rr_copy_mesh(rr_ctx* c, rr_ctx* src)
     }
     RR_HIP(c, hipMemcpy(c->d_poses.p, src->poses.data(), src->poses.size() * sizeof(float), hipMemcpyHostToDevice));
     c->rest_nv = src->rest_nv; c->rest_nf = src->rest_nf; c->n_objects = src->n_objects; c->poses = src->poses;
+    c->twists.assign(6 * (size_t)src->n_objects, 0.0f);
     c->d_stage_v.release(); c->d_stage_poses.release();
     c->dyn_ready = false; c->cost_known = src->cost_known; c->cost_at_build = src->cost_at_build;
     c->build_poses = src->build_poses; c->verts_dirty = src->verts_dirty; c->have_built = false;
@@ -405,6 +407,20 @@ int rr_set_object_poses(rr_ctx* c, const float* poses, size_t n)
     std::swap(c->d_poses, c->d_stage_poses);
     c->poses.assign(poses, poses + 7 * n);
     return refit_commit(c, hp, inflate);
+}
+
+int rr_set_object_twists(rr_ctx* c, const float* twists, size_t n)
+{
+    if (!c) return -1;
+    if (!c->have_mesh) return fail(c, -2, "rr_set_mesh has not been called");
+    if (n != 0 && n != c->n_objects)
+        return fail(c, -3, "rr_set_object_twists: expected " + std::to_string(c->n_objects) + " twists (one per object) or 0, got " + std::to_string(n));
+    if (n != 0 && !twists) return fail(c, -3, "rr_set_object_twists: null twists");
+    for (size_t i = 0; i < 6 * n; i++) if (!std::isfinite(twists[i])) return fail(c, -3, "rr_set_object_twists: non-finite twist value");
+    // by value: the next Doppler call carries them down with its own arguments -- nothing is drained, no tree or launch graph is touched
+    if (n == 0) c->twists.assign(6 * (size_t)c->n_objects, 0.0f);
+    else c->twists.assign(twists, twists + 6 * n);
+    return 0;
 }
 
 int rr_update_vertices(rr_ctx* c, const float* verts, size_t nv)

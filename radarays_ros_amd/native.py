@@ -37,6 +37,7 @@ SYMBOLS = [
     "rr_describe_images_device", "rr_describe_images", "rr_simulate_batch_describe", "rr_match_descriptors_device", "rr_match_descriptors",
     "rr_simulate_batch_provenance_device", "rr_simulate_provenance", "rr_debug_labels",
     "rr_simulate_batch_paths_device", "rr_simulate_paths",
+    "rr_set_object_twists", "rr_simulate_batch_doppler_device", "rr_simulate_doppler",
 ]
 
 
@@ -391,6 +392,9 @@ def lib():
     L.rr_simulate_batch_paths_device.argtypes = [vp, vp, C.c_int, vp, vp, C.c_size_t, vp, vp, C.c_uint, vp]
     L.rr_simulate_paths.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp, C.c_uint]
     L.rr_debug_labels.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_size_t, vp, vp]
+    L.rr_set_object_twists.argtypes = [vp, vp, C.c_size_t]
+    L.rr_simulate_batch_doppler_device.argtypes = [vp, vp, C.c_int, vp, C.c_float, vp, vp, C.c_size_t, vp, vp, vp, vp]
+    L.rr_simulate_doppler.argtypes = [vp, vp, vp, C.c_float, vp, vp, vp, C.c_size_t, vp, vp, vp]
     for n in SYMBOLS:
         getattr(L, n)
     _LIB = L
@@ -611,6 +615,16 @@ class Context:
         """one rigid pose per object, [n_objects][7] = qx qy qz qw tx ty tz; the tree is refit in place (rr_set_object_poses)"""
         p = object_poses_array(poses)
         self._ck(self._L.rr_set_object_poses(self._h, p.ctypes.data, len(p)))
+
+    def set_object_twists(self, twists=None):
+        """one twist per object, [n_objects][6] = vx vy vz wx wy wz (map frame, about the map origin), read by the Doppler calls only;
+        None or an empty array: every twist back to zero (rr_set_object_twists)"""
+        t = np.zeros((0, 6), np.float32) if twists is None else np.ascontiguousarray(twists, np.float32)
+        if t.size == 0:
+            t = t.reshape(0, 6)
+        if t.ndim != 2 or t.shape[1] != 6:
+            raise ValueError("twists must be [n_objects][6] (vx vy vz wx wy wz), got %s" % (t.shape,))
+        self._ck(self._L.rr_set_object_twists(self._h, t.ctypes.data if len(t) else None, len(t)))
 
     def update_vertices(self, verts):
         """new rest vertices (same count as the mesh's), poses kept (rr_update_vertices)"""
@@ -1271,6 +1285,46 @@ class Context:
         self._ck(self._L.rr_simulate_paths(self._h, p.ctypes.data, u8.ctypes.data, None if wav is None else wav.ctypes.data, wave_stride,
                                            cnt.ctypes.data, pc.ctypes.data, flags))
         return u8, wav, cnt, pc
+
+    # ---- Doppler (include/radarays_mi355.h): per-echo range rate and the FMCW range shift it causes
+    def simulate_batch_doppler_device(self, poses, gain, d_imgs_ptr, sensor_vel=None, d_echo_vel_ptr=None, echo_stride=0, d_echo_counts_ptr=None,
+                                      d_echo_cells_ptr=None, d_vel_img_ptr=None, stream=None):
+        """rr_simulate_batch_doppler_device: the images of the shifted echo stream and, in HBM, any of: v_r float32 / cell' int32
+        [n][n_angles][echo_stride] with their true counts uint32 [n][n_angles], the winner's v_r float32 [n][n_cells][n_angles].
+        sensor_vel [n][3] (map frame, m/s) or None: 0; gain: kappa in seconds."""
+        p = np.ascontiguousarray(poses, np.float32).reshape(-1, 7)
+        v = None if sensor_vel is None else np.ascontiguousarray(sensor_vel, np.float32).reshape(-1, 3)
+        if v is not None and len(v) != len(p):
+            raise ValueError("sensor_vel must hold one velocity per pose: %d poses, %d velocities" % (len(p), len(v)))
+        self._ck(self._L.rr_simulate_batch_doppler_device(self._h, p.ctypes.data, len(p), None if v is None else v.ctypes.data, float(gain), d_imgs_ptr,
+                                                          d_echo_vel_ptr, int(echo_stride), d_echo_counts_ptr, d_echo_cells_ptr, d_vel_img_ptr, stream))
+
+    def simulate_doppler(self, pose, sensor_vel=None, gain=0.0, echo_stride=None, want_f32=False, want_vel_img=True):
+        """rr_simulate_doppler: one frame -> (u8 [n_cells][n_angles], f32 image or None, v_r float32 [n_angles][echo_stride], cell' int32
+        [n_angles][echo_stride], counts uint32 [n_angles], velocity image float32 [n_cells][n_angles] or None).  echo_stride None: every
+        echo (a first call for the counts sizes the rows); 0: no rows (None, counts still true)."""
+        p = np.ascontiguousarray(pose, np.float32)
+        if p.shape != (7,):
+            raise ValueError("pose must be [7] (qx qy qz qw tx ty tz), got %s" % (p.shape,))
+        v = None if sensor_vel is None else np.ascontiguousarray(sensor_vel, np.float32)
+        if v is not None and v.shape != (3,):
+            raise ValueError("sensor_vel must be [3] (vx vy vz), got %s" % (v.shape,))
+        n_cells = self.cfg.n_cells if self.cfg is not None else 1   # unconfigured: the library reports it
+        A = self.n_angles
+        u8 = np.zeros((n_cells, A), np.uint8)
+        f32 = np.zeros((n_cells, A), np.float32) if want_f32 else None
+        img = np.full((n_cells, A), np.nan, np.float32) if want_vel_img else None
+        cnt = np.zeros(A, np.uint32)
+        ptr = lambda a: None if a is None else a.ctypes.data   # noqa: E731
+        if echo_stride is None:
+            self._ck(self._L.rr_simulate_doppler(self._h, p.ctypes.data, ptr(v), float(gain), u8.ctypes.data, None, None, 0, cnt.ctypes.data, None, None))
+            echo_stride = max(int(cnt.max()), 1)
+        echo_stride = _int_in(echo_stride, 0, 1 << 26, "echo_stride")
+        vel = np.zeros((A, echo_stride), np.float32) if echo_stride else None
+        cel = np.full((A, echo_stride), -1, np.int32) if echo_stride else None
+        self._ck(self._L.rr_simulate_doppler(self._h, p.ctypes.data, ptr(v), float(gain), u8.ctypes.data, ptr(f32), ptr(vel), echo_stride, cnt.ctypes.data,
+                                             ptr(cel), ptr(img)))
+        return u8, f32, vel, cel, cnt, img
 
     def debug_labels(self, echoes, counts, az_begin=0):
         """rr_debug_labels: the label kernel on caller-given streams, echoes ECHO_SRC_DTYPE [n_seg][stride], counts [n_seg], under the

@@ -412,6 +412,20 @@ class RadarHIP:
         self._push()
         return self._ctx.simulate_paths(pose, wave_stride=wave_stride, map_frame=map_frame)
 
+    def simulate_doppler(self, pose=None, sensor_vel=None, gain=0.0, echo_stride=None, want_f32=False, want_vel_img=True):
+        """The frame as an FMCW sweep sees a moving scene (rr_simulate_doppler): every echo is drawn gain * v_r metres away from where the
+        mesh says it is, v_r its range rate under the objects' twists (set_object_twists on the context) and the sensor's velocity
+        sensor_vel ([3], map frame, m/s; default 0).  pose [7], default: the current Tsm.  -> (image u8 [n_cells][400], f32 image or None,
+        v_r float32 [400][echo_stride], shifted cells int32 [400][echo_stride] (-1: dropped), counts uint32 [400], velocity image float32
+        [n_cells][400] or None (NaN where no echo reaches the bin)); the rows are indexed like simulate_provenance's echo stream."""
+        if pose is None:
+            if not self.updateTsm():
+                print("Couldn't get Transform between sensor and map. Skipping...")
+                return None
+            pose = self.Tsm_last
+        self._push()
+        return self._ctx.simulate_doppler(pose, sensor_vel=sensor_vel, gain=gain, echo_stride=echo_stride, want_f32=want_f32, want_vel_img=want_vel_img)
+
     def _batch(self, poses, sweeps, stamp):
         """Offline generation (the twin of integration/.../RadarHIP.cpp: simulateBatch / simulateSweeps): one image per pose,
         up to 64 poses per set of launches, delivered to page-locked host memory (rr_simulate_batch_host_async)."""
