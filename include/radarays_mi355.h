@@ -771,6 +771,90 @@ int rr_polar_to_cartesian_device(rr_ctx* ctx, const uint8_t* d_imgs_u8, int n_fr
 int rr_polar_to_cartesian(rr_ctx* ctx, const uint8_t* imgs_u8, int n_frames, const rr_cartesian_config* cfg,
                           uint8_t* cart_u8);                                         /* host buffers, synchronous */
 
+/* ---- object annotations: per-object extents and counts from label images (rr_notes.hip) ---------------------------
+ * What every consumer of the label images does next: one record per object -- is it visible in this scan and with how many pixels,
+ * where does it sit in range and azimuth, where is its strongest return, how much of what names it is a ghost or a multipath echo.
+ * The reference has no such output: parity is UNPINNED and everything below is the build's own definition (a numpy restatement in
+ * tests/notes_ref.py checks the kernels: every integer field bit for bit, the four floats to the ulps of cosf / sinf).
+ * Inputs, in image layout with scroll applied (what the provenance call writes):
+ *   labels uint32 [n][n_cells][n_angles]   info words (object id | pass << 24 | kind << 28) or RR_LABEL_NONE
+ *   imgs   u8, same shape, or NULL         NULL reads as an image of zeros: peak and sum_intensity are 0
+ *   n_objects                              records per frame; an id >= n_objects has no record
+ *   extent_mask                            a mask of RR_NOTE_DIRECT | RR_NOTE_GHOST | RR_NOTE_MULTIPATH (0: the counts alone)
+ * Class of a labelled pixel: RR_NOTE_MULTIPATH if kind is 1; otherwise RR_NOTE_GHOST if pass > 0; otherwise RR_NOTE_DIRECT.
+ * Column to azimuth: column col holds azimuth a = (col - scroll_image) mod n_angles (the mapping of the point clouds above).
+ * Output: one rr_object_note per (frame, object id) at d_notes[f * n_objects + id], every byte of it written (reserved words 0):
+ *   n_direct, n_ghost, n_multipath   pixels naming the object, by class (always all three, whatever the mask)
+ *   n_extent                         pixels whose class is in extent_mask; only these feed the fields below
+ *   bin_min, bin_max                 range extent of those pixels; 0xFFFFFFFF and 0 when n_extent == 0
+ *   az_begin, az_count               the smallest arc of AZIMUTHS (not columns) covering them, by the arc rule
+ *   peak, peak_bin, peak_az          the largest image value among them and the bin and azimuth where it lies; equal values go to the lower
+ *                                    bin, then the lower azimuth; all 0 when n_extent == 0
+ *   sum_intensity                    sum of the image values over them
+ *   x_min, x_max, y_min, y_max       min / max over them of r * cosf(theta) and r * sinf(theta), one f32 multiply each, with
+ *                                    r = (float)(((double)bin + 0.5) * resolution) and theta = theta_min + (float)a * theta_inc exactly as
+ *                                    a detected point's; +inf / -inf when n_extent == 0
+ * Arc rule.  O = the set of azimuths that hold a pixel of the extent.  Take the longest circular run of azimuths outside O; among equal
+ * longest runs the one whose first azimuth (walking upwards, so a run through azimuth 0 begins at its high end) is lowest.  az_begin is
+ * the azimuth after that run, az_count = n_angles - the run's length: the arc is az_begin, az_begin + 1, .. (mod n_angles).  Every azimuth
+ * occupied gives (0, n_angles), none (0, 0).
+ * Skipped pixels.  A labelled pixel whose object id is >= n_objects feeds no record and is counted in d_skipped[f]; RR_LABEL_NONE is
+ * not counted there.  Nothing is lost silently.
+ * Every reduction is over integers or a min / max (the floats through an order-preserving integer mapping): a record does not depend on
+ * the order of execution, two calls on the same planes return the same bytes.
+ * Scratch is the caller's: rr_annotate_scratch_bytes bytes (64 per frame and object plus one bit per azimuth, frame and object), 16-byte
+ * aligned like d_notes; its contents before the call do not matter and mean nothing afterwards.  Like the point clouds the device forms
+ * write nothing but the caller's buffers, use no context-owned memory and read geometry and config BY VALUE when the call is made: they
+ * may run on any stream beside batches in flight.  The host forms stage through context-owned buffers and are synchronous.
+ * Out of scope: rr_multi has no annotation call (use the context of one device); parameter batches (the provenance chain is for pose
+ * batches); velocities per object; oriented boxes.
+ * Refused with a message and nothing written: -1 for a null ctx; -2 without a config (the simulate form also without a mesh, materials
+ * or beam); -3 for a null required buffer, n_frames outside 1..65535 (the simulate form: 1..RR_MAX_BATCH), n_objects < 1 or >= 2^24 - 1,
+ * unknown mask bits, n_cells > RR_LABEL_MAX_CELLS, n_angles > 65535, a scratch or record buffer that is not
+ * 16-byte aligned, scratch_bytes below rr_annotate_scratch_bytes; the label-point call also for max_points < 0 and for a source plane
+ * without its destination (or the reverse); the Cartesian call for what rr_polar_to_cartesian_device refuses and for interpolation != 0. */
+#define RR_NOTE_DIRECT    1u
+#define RR_NOTE_GHOST     2u
+#define RR_NOTE_MULTIPATH 4u
+typedef struct rr_object_note {       /* 80 B, five 16-B stores */
+    uint32_t n_direct, n_ghost, n_multipath, n_extent;
+    uint32_t bin_min, bin_max, az_begin, az_count;
+    uint32_t peak, peak_bin, peak_az, reserved0_;
+    uint64_t sum_intensity;
+    float    x_min, x_max;
+    float    y_min, y_max;
+    uint32_t reserved1_[2];
+} rr_object_note;
+/* bytes of d_scratch for a call of that shape; 0 for a shape the calls refuse (a count below 1) */
+size_t rr_annotate_scratch_bytes(int n_frames, int n_objects, int n_angles);
+int rr_annotate_labels_device(rr_ctx* ctx, const uint32_t* d_labels /*[n][n_cells][n_angles]*/, const uint8_t* d_imgs_u8_or_NULL, int n_frames,
+                              int n_objects, uint32_t extent_mask, rr_object_note* d_notes /*[n][n_objects]*/, uint32_t* d_skipped /*[n]*/,
+                              void* d_scratch, size_t scratch_bytes, void* stream);
+int rr_annotate_labels(rr_ctx* ctx, const uint32_t* labels, const uint8_t* imgs_u8_or_NULL, int n_frames, int n_objects, uint32_t extent_mask,
+                       rr_object_note* out_notes, uint32_t* out_skipped);                 /* host buffers, synchronous */
+/* The identity of detected points: for the first min(total, max_points) points of each frame (total = d_offsets[f][n_angles], the points
+ * rr_detect_device wrote at d_points + f * max_points) the label, face and range rate at the point's (bin, column), at the point's index in
+ * d_point_labels / d_point_faces / d_point_vel [n][max_points]; nothing is written past those points.  d_faces and d_vel_img (the velocity
+ * image of the Doppler call) may be NULL, each together with its destination.  A point whose bin or column lies outside the image names
+ * nothing: RR_LABEL_NONE, NaN.  One gather kernel, asynchronous on `stream`. */
+int rr_label_points_device(rr_ctx* ctx, const rr_radar_point* d_points, const uint32_t* d_offsets /*[n][n_angles+1]*/, int n_frames, int max_points,
+                           const uint32_t* d_labels, const uint32_t* d_faces_or_NULL, const float* d_vel_img_or_NULL, uint32_t* d_point_labels,
+                           uint32_t* d_point_faces, float* d_point_vel, void* stream);
+/* The instance mask of a bird's-eye image: uint32 planes (labels, faces) resampled by the NEAREST rule of rr_polar_to_cartesian_device,
+ * expression for expression, so pixel (i, j) of the mask names what pixel (i, j) of the nearest image shows; a pixel beyond the last bin
+ * is RR_LABEL_NONE.  cfg->interpolation must be 0: ids do not interpolate.  d_cart_u32 = [n][width][width]. */
+int rr_polar_to_cartesian_labels_device(rr_ctx* ctx, const uint32_t* d_planes_u32 /*[n][n_cells][n_angles]*/, int n_frames,
+                                        const rr_cartesian_config* cfg, uint32_t* d_cart_u32, void* stream);
+int rr_polar_to_cartesian_labels(rr_ctx* ctx, const uint32_t* planes_u32, int n_frames, const rr_cartesian_config* cfg,
+                                 uint32_t* cart_u32);                                  /* host buffers, synchronous */
+/* Ground-truth generation in one call: a provenance chain for n_frames (1..RR_MAX_BATCH) poses, then the annotation of its label planes with
+ * its images, on the context's stream; n_objects is the mesh's (the largest face_object_id + 1).  Only the records and skip counts (and
+ * the images, if out_imgs_u8 is not NULL: the bytes of rr_simulate_batch_device) reach the host; no label plane leaves the GPU.
+ * out_notes [n][n_objects], out_skipped [n] (always 0 here: every id is the mesh's).  Synchronous; the frame errors -7 / -8 are returned
+ * before anything is written. */
+int rr_simulate_batch_annotations(rr_ctx* ctx, const float* poses, int n_frames, uint32_t extent_mask, uint8_t* out_imgs_u8_or_NULL,
+                                  rr_object_note* out_notes, uint32_t* out_skipped);
+
 /* ---- translation registration (rr_shift.hip) ----------------------------------------------------------------------
  * rr_align_images settles the yaw; the other two degrees of freedom of a planar pose, x and y, are to first order a
  * translation of the Cartesian bird's-eye image (rr_polar_to_cartesian).  One exact 2-D cross-correlation over a window of

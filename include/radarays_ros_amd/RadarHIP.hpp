@@ -119,6 +119,7 @@ public:
                                                                         face_object.empty() ? nullptr : face_object.data())) {
             std::string e = rr_multi_last_error(m_multi); rr_destroy_multi(m_multi); throw std::runtime_error(e);
         }
+        for (uint32_t o : face_object) m_n_objects = std::max<size_t>(m_n_objects, (size_t)o + 1);
     }
     RadarHIP(std::string map_frame, std::string sensor_frame, const std::vector<float>& verts,
              const std::vector<uint32_t>& faces, const std::vector<uint32_t>& face_object, int device = 0)
@@ -410,6 +411,28 @@ public:
             !marshal::match_places(m_ctx, q.data(), 1, database.data(), n_db, cfg.n_rings, cfg.n_sectors, top_k, out)) { fail(); out.clear(); }
         return out;
     }
+    // Ground truth per object (rr_object_note, include/radarays_mi355.h), on device 0: for poses [n][7] one record per (frame, object),
+    // [n][objectCount()] -- pixel counts by class, range / azimuth / Cartesian extent, peak and summed intensity of the pixels whose class
+    // is in `extent_mask` (RR_NOTE_DIRECT | RR_NOTE_GHOST | RR_NOTE_MULTIPATH).  The label planes never leave the GPU; `images` (or null)
+    // receives the frames.  Null on error (lastError()).
+    struct Annotations { std::vector<rr_object_note> notes; std::vector<uint32_t> skipped; std::vector<ImagePtr> images; size_t n_objects = 0; };
+    size_t objectCount() const { return m_n_objects; }
+    std::shared_ptr<Annotations> simulateAnnotations(const std::vector<float>& poses, double stamp, uint32_t extent_mask = RR_NOTE_DIRECT,
+                                                     bool want_images = false)
+    {
+        if (!push()) return {};
+        if (poses.empty() || poses.size() % 7) { m_err = "poses must be [n][7]"; return {}; }
+        const size_t n = poses.size() / 7, npx = (size_t)m_cfg.n_cells * m_n_angles;
+        auto out = std::make_shared<Annotations>();
+        out->n_objects = m_n_objects;
+        std::vector<uint8_t> px;
+        if (!marshal::annotate_chunks(m_ctx, poses.data(), n, m_n_objects, npx, extent_mask, out->notes, out->skipped, want_images ? &px : nullptr)) {
+            fail(); return {};
+        }
+        for (size_t k = 0; want_images && k < n; k++) out->images.push_back(image(&px[k * npx], stamp));
+        m_push_motion = true;      // simulate() re-installs its own table (or none)
+        return out;
+    }
     const std::string& lastError() const { return m_err; }
     // radar_tools/radar_img_to_pcl (launch/tests/radar_sim_test.launch:80-84, outside the checkout) on the GPU: one mono8
     // polar image of this model's shape (simulated or real) -> its detections, a PointCloud's points plus the intensity
@@ -513,6 +536,7 @@ private:
     rr_ctx* m_ctx = nullptr;         // = the context of the first device (statistics, parameter batches)
     std::vector<float> m_motion; bool m_push_motion = false;
     int m_n_angles = 400;
+    size_t m_n_objects = 1;            // the mesh's: the largest face_object id + 1
     bool m_push_beams = false;
     uint32_t m_beam_seed = 0; bool m_have_seed = false;
     rr_stats m_stats{};

@@ -209,4 +209,20 @@ inline bool match_places(rr_ctx* ctx, const uint8_t* query, size_t n_query, cons
     return rr_match_descriptors(ctx, query, (int)n_query, db, (int)n_db, n_rings, n_sectors, top_k, out.data(), nullptr, nullptr) == 0;
 }
 
+// object annotations (rr_object_note): n poses [n][7] in chunks of RR_MAX_BATCH through rr_simulate_batch_annotations -- one record per
+// (frame, object), [n][n_objects], the skip counts [n] and, if asked for, the images [n][npx].  false: rr_last_error(ctx)
+inline bool annotate_chunks(rr_ctx* ctx, const float* poses, size_t n, size_t n_objects, size_t npx, uint32_t extent_mask,
+                            std::vector<rr_object_note>& notes, std::vector<uint32_t>& skipped, std::vector<uint8_t>* images)
+{
+    notes.assign(n * n_objects, rr_object_note{});
+    skipped.assign(n, 0u);
+    if (images) images->assign(n * npx, 0);
+    for (size_t at = 0; at < n; at += RR_MAX_BATCH) {
+        const size_t m = std::min<size_t>(RR_MAX_BATCH, n - at);
+        if (rr_simulate_batch_annotations(ctx, poses + 7 * at, (int)m, extent_mask, images ? images->data() + at * npx : nullptr,
+                                          notes.data() + at * n_objects, skipped.data() + at)) return false;
+    }
+    return true;
+}
+
 }  // namespace radarays_ros_amd::marshal

@@ -214,6 +214,9 @@ struct rr_ctx {
     // staging: descriptors on their way down, queries and one database chunk on their way up, that chunk's sse / shift on their way down
     DevBuf<uint8_t> d_place_rolls, d_place_desc, d_place_query, d_place_db; DevBuf<uint32_t> d_place_qsums, d_place_conv_sse;
     DevBuf<unsigned long long> d_place_keys, d_place_aux, d_place_part, d_place_win; DevBuf<rr_place_match> d_place_rec; DevBuf<uint16_t> d_place_conv_shift;
+    // staging of the host forms of rr_annotate_labels / rr_polar_to_cartesian_labels and of rr_simulate_batch_annotations (the device forms use none
+    // of it): planes on their way up or straight from the provenance chain, records, skip counts and resampled planes on their way down, the scratch
+    DevBuf<uint32_t> d_note_planes, d_note_skipped, d_note_cart; DevBuf<uint8_t> d_note_imgs; DevBuf<rr_object_note> d_note_rec; DevBuf<uint4> d_note_scratch;
     void* h_rb = nullptr; size_t h_rb_bytes = 0;         // page-locked: read_back()
     void* h_frame = nullptr; size_t h_frame_bytes = 0;   // page-locked: error bits + per-pass counters of rr_simulate's frame
 

@@ -1,5 +1,5 @@
 // rr_images.hip -- the C ABI's image entry points: images in, records / points / images out.  PSNR scores and metrics against a reference image
-// (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), place recognition (rr_place.hip), point clouds and Cartesian images (rr_detect.hip): each in a device form, which runs on the
+// (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), place recognition (rr_place.hip), point clouds and Cartesian images (rr_detect.hip), object annotations (rr_notes.hip): each in a device form, which runs on the
 // caller's buffers and stream, and a host form, which stages through the context's own buffers on c->stream.
 #include "rr_ctx.h"
 #include <algorithm>
@@ -89,6 +89,27 @@ int check_cartesian(rr_ctx* c, const char* who, const void* imgs, int n_frames, 
     if (k->interpolation != 0 && k->interpolation != 1) return fail(c, -3, w + ": interpolation must be 0 (nearest) or 1 (bilinear)");
     if (!(std::isfinite(k->pixel_size) && k->pixel_size > 0.0f)) return fail(c, -3, w + ": pixel_size must be finite and > 0");
     if (c->cfg.theta_inc == 0.0f) return fail(c, -3, w + ": the config's theta_inc is 0");
+    return 0;
+}
+
+// the refusals the annotation calls share: a config (the plane shape) within the limits of the label planes and of the packed azimuth
+int check_planes(rr_ctx* c, const std::string& w, bool have_buffers, int n_frames, int n_max)
+{
+    int rc = check_images(c, w, have_buffers, "buffer", "n_frames", n_frames, n_max); if (rc) return rc;
+    if (c->cfg.n_cells > RR_LABEL_MAX_CELLS) return fail(c, -3, w + ": n_cells exceeds RR_LABEL_MAX_CELLS (8192)");
+    if (c->cfg.n_angles > 65535) return fail(c, -3, w + ": n_angles must be at most 65535");
+    return 0;
+}
+
+// the refusals of rr_annotate_labels_device / rr_annotate_labels / rr_simulate_batch_annotations
+int check_annotate(rr_ctx* c, const char* who, const void* labels, int n_frames, int n_max, long long n_objects, uint32_t extent_mask, const void* notes,
+                   const void* skipped)
+{
+    const std::string w(who);
+    int rc = check_planes(c, w, labels && notes && skipped, n_frames, n_max); if (rc) return rc;
+    if (n_objects < 1 || n_objects >= 0xFFFFFF) return fail(c, -3, w + ": n_objects must be 1..2^24 - 2");
+    if (extent_mask & ~(RR_NOTE_DIRECT | RR_NOTE_GHOST | RR_NOTE_MULTIPATH))
+        return fail(c, -3, w + ": extent_mask must be a mask of RR_NOTE_DIRECT | RR_NOTE_GHOST | RR_NOTE_MULTIPATH");
     return 0;
 }
 
@@ -663,6 +684,135 @@ int rr_polar_to_cartesian(rr_ctx* c, const uint8_t* imgs_u8, int n_frames, const
     rc = rr_polar_to_cartesian_device(c, c->d_conv_in.p, n_frames, cfg, c->d_conv_cart.p, c->stream); if (rc) return rc;
     RR_HIP(c, hipMemcpyAsync(cart_u8, c->d_conv_cart.p, n_out, hipMemcpyDeviceToHost, c->stream));
     RR_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- object annotations (rr_notes.hip) --------------------------------------------------------------------------------
+size_t rr_annotate_scratch_bytes(int n_frames, int n_objects, int n_angles)
+{
+    if (n_frames < 1 || n_objects < 1 || n_angles < 1) return 0;
+    return note_scratch_bytes((size_t)n_frames, (size_t)n_objects, n_angles);
+}
+
+int rr_annotate_labels_device(rr_ctx* c, const uint32_t* d_labels, const uint8_t* d_imgs_u8, int n_frames, int n_objects, uint32_t extent_mask,
+                              rr_object_note* d_notes, uint32_t* d_skipped, void* d_scratch, size_t scratch_bytes, void* stream)
+{
+    const std::string w("rr_annotate_labels_device");
+    int rc = check_annotate(c, w.c_str(), d_labels, n_frames, 65535, n_objects, extent_mask, d_notes, d_skipped); if (rc) return rc;
+    if (!d_scratch) return fail(c, -3, w + ": null scratch");
+    if ((uintptr_t)d_scratch % 16 != 0 || (uintptr_t)d_notes % 16 != 0) return fail(c, -3, w + ": the scratch and the records must be 16-byte aligned");
+    const rr_config& g = c->cfg;
+    const size_t need = note_scratch_bytes((size_t)n_frames, (size_t)n_objects, g.n_angles);
+    if (scratch_bytes < need) return fail(c, -3, w + ": scratch of " + std::to_string(scratch_bytes) + " bytes, the call needs " + std::to_string(need));
+    RR_HIP(c, hipSetDevice(c->device));
+    launch_notes(d_labels, d_imgs_u8, n_frames, (uint32_t)n_objects, extent_mask, g.n_cells, g.n_angles, g.scroll_image, g.theta_min, g.theta_inc,
+                 g.resolution, d_notes, d_skipped, d_scratch, stream_of(c, stream));
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_annotate_labels(rr_ctx* c, const uint32_t* labels, const uint8_t* imgs_u8, int n_frames, int n_objects, uint32_t extent_mask,
+                       rr_object_note* out_notes, uint32_t* out_skipped)
+{
+    int rc = check_annotate(c, "rr_annotate_labels", labels, n_frames, 65535, n_objects, extent_mask, out_notes, out_skipped); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles, n = (size_t)n_frames, n_rec = n * (size_t)n_objects;
+    const size_t scratch = note_scratch_bytes(n, (size_t)n_objects, c->cfg.n_angles);
+    RR_HIP(c, hipStreamSynchronize(c->stream));        // the staging buffers may be reallocated
+    RR_HIP(c, c->d_note_planes.ensure(n * npx));
+    if (imgs_u8) RR_HIP(c, c->d_note_imgs.ensure(n * npx));
+    RR_HIP(c, c->d_note_rec.ensure(n_rec));
+    RR_HIP(c, c->d_note_skipped.ensure(n));
+    RR_HIP(c, c->d_note_scratch.ensure(scratch / 16));
+    RR_HIP(c, hipMemcpyAsync(c->d_note_planes.p, labels, n * npx * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if (imgs_u8) RR_HIP(c, hipMemcpyAsync(c->d_note_imgs.p, imgs_u8, n * npx, hipMemcpyHostToDevice, c->stream));
+    rc = rr_annotate_labels_device(c, c->d_note_planes.p, imgs_u8 ? c->d_note_imgs.p : nullptr, n_frames, n_objects, extent_mask, c->d_note_rec.p,
+                                   c->d_note_skipped.p, c->d_note_scratch.p, scratch, c->stream); if (rc) return rc;
+    std::vector<rr_object_note> rec(n_rec);             // the caller's buffers are written once everything has arrived
+    std::vector<uint32_t> skipped(n);
+    RR_HIP(c, hipMemcpyAsync(skipped.data(), c->d_note_skipped.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    rc = records_back(c, rec.data(), c->d_note_rec.p, n_rec * sizeof(rr_object_note), c->stream); if (rc) return rc;
+    std::copy(rec.begin(), rec.end(), out_notes);
+    std::copy(skipped.begin(), skipped.end(), out_skipped);
+    return 0;
+}
+
+int rr_label_points_device(rr_ctx* c, const rr_radar_point* d_points, const uint32_t* d_offsets, int n_frames, int max_points, const uint32_t* d_labels,
+                           const uint32_t* d_faces, const float* d_vel_img, uint32_t* d_point_labels, uint32_t* d_point_faces, float* d_point_vel,
+                           void* stream)
+{
+    const std::string w("rr_label_points_device");
+    int rc = check_planes(c, w, d_points && d_offsets && d_labels && d_point_labels, n_frames, 65535); if (rc) return rc;
+    if (max_points < 0) return fail(c, -3, w + ": max_points must be >= 0");
+    if (!d_faces != !d_point_faces) return fail(c, -3, w + ": the face plane and the points' faces come together or not at all");
+    if (!d_vel_img != !d_point_vel) return fail(c, -3, w + ": the velocity image and the points' range rates come together or not at all");
+    if (max_points == 0) return 0;
+    RR_HIP(c, hipSetDevice(c->device));
+    launch_label_points(d_points, d_offsets, n_frames, max_points, d_labels, d_faces, d_vel_img, d_point_labels, d_point_faces, d_point_vel,
+                        c->cfg.n_cells, c->cfg.n_angles, stream_of(c, stream));
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_polar_to_cartesian_labels_device(rr_ctx* c, const uint32_t* d_planes_u32, int n_frames, const rr_cartesian_config* cfg, uint32_t* d_cart_u32,
+                                        void* stream)
+{
+    int rc = check_cartesian(c, "rr_polar_to_cartesian_labels_device", d_planes_u32, n_frames, cfg, d_cart_u32); if (rc) return rc;
+    if (cfg->interpolation != 0) return fail(c, -3, "rr_polar_to_cartesian_labels_device: interpolation must be 0 (nearest): ids do not interpolate");
+    RR_HIP(c, hipSetDevice(c->device));
+    const rr_config& g = c->cfg;
+    launch_cartesian_labels(d_planes_u32, n_frames, *cfg, g.n_cells, g.n_angles, g.scroll_image, g.theta_min, g.theta_inc, (float)g.resolution,
+                            d_cart_u32, stream_of(c, stream));
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_polar_to_cartesian_labels(rr_ctx* c, const uint32_t* planes_u32, int n_frames, const rr_cartesian_config* cfg, uint32_t* cart_u32)
+{
+    int rc = check_cartesian(c, "rr_polar_to_cartesian_labels", planes_u32, n_frames, cfg, cart_u32); if (rc) return rc;
+    if (cfg->interpolation != 0) return fail(c, -3, "rr_polar_to_cartesian_labels: interpolation must be 0 (nearest): ids do not interpolate");
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles, n = (size_t)n_frames, n_out = n * cfg->width * cfg->width;
+    RR_HIP(c, hipStreamSynchronize(c->stream));        // the staging buffers may be reallocated
+    RR_HIP(c, c->d_note_planes.ensure(n * npx));
+    RR_HIP(c, c->d_note_cart.ensure(n_out));
+    RR_HIP(c, hipMemcpyAsync(c->d_note_planes.p, planes_u32, n * npx * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    rc = rr_polar_to_cartesian_labels_device(c, c->d_note_planes.p, n_frames, cfg, c->d_note_cart.p, c->stream); if (rc) return rc;
+    std::vector<uint32_t> out(n_out);
+    rc = records_back(c, out.data(), c->d_note_cart.p, n_out * sizeof(uint32_t), c->stream); if (rc) return rc;
+    std::copy(out.begin(), out.end(), cart_u32);
+    return 0;
+}
+
+int rr_simulate_batch_annotations(rr_ctx* c, const float* poses, int n_frames, uint32_t extent_mask, uint8_t* out_imgs_u8, rr_object_note* out_notes,
+                                  uint32_t* out_skipped)
+{
+    // refused before anything is simulated (the context stands in for the planes: they are its own)
+    int rc = check_annotate(c, "rr_simulate_batch_annotations", c, n_frames, RR_MAX_BATCH, c ? (long long)c->n_objects : 1, extent_mask, out_notes, out_skipped);
+    if (rc) return rc;
+    rc = check_ready(c); if (rc) return rc;
+    if (!poses) return fail(c, -3, "rr_simulate_batch_annotations: null poses");
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles, n = (size_t)n_frames, n_obj = c->n_objects, n_rec = n * n_obj;
+    const size_t scratch = note_scratch_bytes(n, n_obj, c->cfg.n_angles);
+    RR_HIP(c, hipStreamSynchronize(c->stream));        // the buffers may be reallocated below
+    RR_HIP(c, c->d_param_imgs.ensure(n * npx));
+    RR_HIP(c, c->d_note_planes.ensure(n * npx));
+    RR_HIP(c, c->d_note_rec.ensure(n_rec));
+    RR_HIP(c, c->d_note_skipped.ensure(n));
+    RR_HIP(c, c->d_note_scratch.ensure(scratch / 16));
+    rc = rr_simulate_batch_provenance_device(c, poses, n_frames, c->d_param_imgs.p, c->d_note_planes.p, nullptr, nullptr, 0, nullptr, c->stream);
+    if (rc) return rc;
+    rc = rr_annotate_labels_device(c, c->d_note_planes.p, c->d_param_imgs.p, n_frames, (int)n_obj, extent_mask, c->d_note_rec.p, c->d_note_skipped.p,
+                                   c->d_note_scratch.p, scratch, c->stream); if (rc) return rc;
+    std::vector<rr_object_note> rec(n_rec);
+    std::vector<uint32_t> skipped(n);
+    RR_HIP(c, hipMemcpyAsync(skipped.data(), c->d_note_skipped.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    rc = records_back(c, rec.data(), c->d_note_rec.p, n_rec * sizeof(rr_object_note), c->stream); if (rc) return rc;
+    rc = report_frame_errors(c); if (rc) return rc;     // before anything is handed out
+    if (out_imgs_u8) RR_HIP(c, hipMemcpy(out_imgs_u8, c->d_param_imgs.p, n * npx, hipMemcpyDeviceToHost));
+    std::copy(rec.begin(), rec.end(), out_notes);
+    std::copy(skipped.begin(), skipped.end(), out_skipped);
     return 0;
 }
 

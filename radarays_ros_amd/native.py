@@ -38,6 +38,8 @@ SYMBOLS = [
     "rr_simulate_batch_provenance_device", "rr_simulate_provenance", "rr_debug_labels",
     "rr_simulate_batch_paths_device", "rr_simulate_paths",
     "rr_set_object_twists", "rr_simulate_batch_doppler_device", "rr_simulate_doppler",
+    "rr_annotate_scratch_bytes", "rr_annotate_labels_device", "rr_annotate_labels", "rr_label_points_device",
+    "rr_polar_to_cartesian_labels_device", "rr_polar_to_cartesian_labels", "rr_simulate_batch_annotations",
 ]
 
 
@@ -105,6 +107,37 @@ def unpack_info(info):
     RR_LABEL_NONE unpacks to (0xFFFFFF, 15, 1) with the unused top bits set: mask such pixels with `info != LABEL_NONE` first."""
     i = np.asarray(info, np.uint32)
     return i & np.uint32(0xFFFFFF), (i >> np.uint32(24)) & np.uint32(15), (i >> np.uint32(28)) & np.uint32(1)
+
+
+# rr_object_note as numpy sees it (80 B): one record per (frame, object) of rr_annotate_labels; the classes of a labelled pixel
+NOTE_DTYPE = np.dtype([("n_direct", "<u4"), ("n_ghost", "<u4"), ("n_multipath", "<u4"), ("n_extent", "<u4"), ("bin_min", "<u4"), ("bin_max", "<u4"),
+                       ("az_begin", "<u4"), ("az_count", "<u4"), ("peak", "<u4"), ("peak_bin", "<u4"), ("peak_az", "<u4"), ("reserved0_", "<u4"),
+                       ("sum_intensity", "<u8"), ("x_min", "<f4"), ("x_max", "<f4"), ("y_min", "<f4"), ("y_max", "<f4"), ("reserved1_", "<u4", (2,))])
+NOTE_DIRECT, NOTE_GHOST, NOTE_MULTIPATH = 1, 2, 4
+NOTE_ALL = NOTE_DIRECT | NOTE_GHOST | NOTE_MULTIPATH
+NOTE_NAMES = {"direct": NOTE_DIRECT, "ghost": NOTE_GHOST, "multipath": NOTE_MULTIPATH}
+
+
+class RRObjectNote(C.Structure):
+    _fields_ = [("n_direct", C.c_uint32), ("n_ghost", C.c_uint32), ("n_multipath", C.c_uint32), ("n_extent", C.c_uint32),
+                ("bin_min", C.c_uint32), ("bin_max", C.c_uint32), ("az_begin", C.c_uint32), ("az_count", C.c_uint32),
+                ("peak", C.c_uint32), ("peak_bin", C.c_uint32), ("peak_az", C.c_uint32), ("reserved0_", C.c_uint32),
+                ("sum_intensity", C.c_uint64), ("x_min", C.c_float), ("x_max", C.c_float), ("y_min", C.c_float), ("y_max", C.c_float),
+                ("reserved1_", C.c_uint32 * 2)]
+
+
+def note_mask(extent):
+    """an extent mask -> its bits: an int 0..7, a class name ("direct", "ghost", "multipath") or a list of names; ValueError otherwise"""
+    if isinstance(extent, str):
+        extent = [extent]
+    if isinstance(extent, (list, tuple, set, frozenset)):
+        m = 0
+        for name in extent:
+            if not isinstance(name, str) or name not in NOTE_NAMES:
+                raise ValueError("unknown pixel class %r (direct, ghost, multipath)" % (name,))
+            m |= NOTE_NAMES[name]
+        return m
+    return _int_in(extent, 0, NOTE_ALL, "extent_mask")
 
 
 # rr_wave_rec as numpy sees it (64 B): one ray-cast wave of an azimuth's wave list (rr_simulate_paths); WavRec is the same record for ctypes
@@ -395,6 +428,14 @@ def lib():
     L.rr_set_object_twists.argtypes = [vp, vp, C.c_size_t]
     L.rr_simulate_batch_doppler_device.argtypes = [vp, vp, C.c_int, vp, C.c_float, vp, vp, C.c_size_t, vp, vp, vp, vp]
     L.rr_simulate_doppler.argtypes = [vp, vp, vp, C.c_float, vp, vp, vp, C.c_size_t, vp, vp, vp]
+    L.rr_annotate_scratch_bytes.restype = C.c_size_t
+    L.rr_annotate_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    L.rr_annotate_labels_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_uint32, vp, vp, vp, C.c_size_t, vp]
+    L.rr_annotate_labels.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_uint32, vp, vp]
+    L.rr_label_points_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.rr_polar_to_cartesian_labels_device.argtypes = [vp, vp, C.c_int, C.POINTER(RRCartesianConfig), vp, vp]
+    L.rr_polar_to_cartesian_labels.argtypes = [vp, vp, C.c_int, C.POINTER(RRCartesianConfig), vp]
+    L.rr_simulate_batch_annotations.argtypes = [vp, vp, C.c_int, C.c_uint32, vp, vp, vp]
     for n in SYMBOLS:
         getattr(L, n)
     _LIB = L
@@ -581,6 +622,7 @@ class Context:
         self.device = int(device)
         self.cfg = None
         self.n_angles = 400
+        self.n_objects = 1
 
     def close(self):
         if getattr(self, "_h", None):
@@ -605,10 +647,12 @@ class Context:
             raise ValueError("face_object_id must have one entry per face")
         fn = {"host": self._L.rr_set_mesh, "gpu": self._L.rr_set_mesh_gpu}[builder]
         self._ck(fn(self._h, v.ctypes.data, len(v), f.ctypes.data, len(f), None if o is None else o.ctypes.data))
+        self.n_objects = int(o.max()) + 1 if o is not None and len(o) else 1
 
     def copy_mesh(self, src):
         """take the finished tree of another context (same or another device): rr_copy_mesh"""
         self._ck(self._L.rr_copy_mesh(self._h, src._h))
+        self.n_objects = getattr(src, "n_objects", 1)
 
     # ---- dynamic scenes (include/radarays_mi355.h): the traced scene is every face's rest corners moved by its object's pose
     def set_object_poses(self, poses):
@@ -1114,6 +1158,91 @@ class Context:
         out = np.zeros((len(x), c.width, c.width), np.uint8)
         self._ck(self._L.rr_polar_to_cartesian(self._h, x.ctypes.data, len(x), C.byref(c), out.ctypes.data))
         return out
+
+    # ---- object annotations (rr_notes.hip): one record per object from label images; any context with a config, mesh or not
+    def _label_planes(self, planes, what="label planes"):
+        """uint32 [n][n_cells][n_angles] (or one plane) of this context's shape -> contiguous 3-D array"""
+        n_cells, n_angles = self._polar_shape()
+        x = np.asarray(planes)
+        if x.dtype != np.uint32:
+            raise ValueError("%s must be uint32, got dtype %s" % (what, x.dtype))
+        if x.ndim == 2:
+            x = x[None]
+        if x.ndim != 3 or x.shape[1:] != (n_cells, n_angles) or not 1 <= x.shape[0] <= 65535:
+            raise ValueError("%s must have shape [n][%d][%d] (n in 1..65535), got %s" % (what, n_cells, n_angles, np.asarray(planes).shape))
+        return np.ascontiguousarray(x)
+
+    def annotate_scratch_bytes(self, n_frames, n_objects):
+        """rr_annotate_scratch_bytes for this context's n_angles"""
+        self._polar_shape()
+        return int(self._L.rr_annotate_scratch_bytes(_frames_arg(n_frames), _int_in(n_objects, 1, 0xFFFFFE, "n_objects"), int(self.n_angles)))
+
+    def annotate_labels_device(self, d_labels_ptr, d_imgs_ptr, n_frames, n_objects, d_notes_ptr, d_skipped_ptr, d_scratch_ptr, scratch_bytes,
+                               extent=NOTE_DIRECT, stream=None):
+        """rr_annotate_labels_device: NOTE_DTYPE records [n_frames][n_objects] and skip counts uint32 [n_frames] in HBM, on `stream`;
+        d_imgs_ptr None: peak and sum are 0.  The scratch (annotate_scratch_bytes, 16-byte aligned) is the caller's."""
+        self._polar_shape()
+        n, k, m = _frames_arg(n_frames), _int_in(n_objects, 1, 0xFFFFFE, "n_objects"), note_mask(extent)
+        if not d_labels_ptr or not d_notes_ptr or not d_skipped_ptr or not d_scratch_ptr:
+            raise ValueError("annotate_labels_device needs label, record, skip-count and scratch buffers")
+        self._ck(self._L.rr_annotate_labels_device(self._h, d_labels_ptr, d_imgs_ptr, n, k, m, d_notes_ptr, d_skipped_ptr, d_scratch_ptr,
+                                                   int(scratch_bytes), stream))
+
+    def annotate_labels(self, labels, imgs=None, n_objects=None, extent=NOTE_DIRECT):
+        """rr_annotate_labels on host planes [n][n_cells][n_angles] (or one plane) -> (NOTE_DTYPE [n][n_objects], skipped uint32 [n]).
+        n_objects None: the mesh's object count."""
+        x = self._label_planes(labels)
+        z = None if imgs is None else self._polar_images(imgs)
+        if z is not None and z.shape != x.shape:
+            raise ValueError("%d label planes with %d images" % (len(x), len(z)))
+        k = _int_in(self.n_objects if n_objects is None else n_objects, 1, 0xFFFFFE, "n_objects")
+        notes = np.zeros((len(x), k), NOTE_DTYPE)
+        skipped = np.zeros(len(x), np.uint32)
+        self._ck(self._L.rr_annotate_labels(self._h, x.ctypes.data, None if z is None else z.ctypes.data, len(x), k, note_mask(extent),
+                                            notes.ctypes.data, skipped.ctypes.data))
+        return notes, skipped
+
+    def label_points_device(self, d_points_ptr, d_offsets_ptr, n_frames, max_points, d_labels_ptr, d_point_labels_ptr, d_faces_ptr=None,
+                            d_point_faces_ptr=None, d_vel_img_ptr=None, d_point_vel_ptr=None, stream=None):
+        """rr_label_points_device: for the points rr_detect_device wrote, the label (and face, range rate) under each, uint32 / float32
+        [n_frames][max_points] in HBM, on `stream`"""
+        self._polar_shape()
+        n, mp = _frames_arg(n_frames), _int_in(max_points, 0, 2**31 - 1, "max_points")
+        if not d_points_ptr or not d_offsets_ptr or not d_labels_ptr or not d_point_labels_ptr:
+            raise ValueError("label_points_device needs point, offset, label and output buffers")
+        if bool(d_faces_ptr) != bool(d_point_faces_ptr) or bool(d_vel_img_ptr) != bool(d_point_vel_ptr):
+            raise ValueError("a source plane and its per-point output come together")
+        self._ck(self._L.rr_label_points_device(self._h, d_points_ptr, d_offsets_ptr, n, mp, d_labels_ptr, d_faces_ptr, d_vel_img_ptr,
+                                                d_point_labels_ptr, d_point_faces_ptr, d_point_vel_ptr, stream))
+
+    def polar_to_cartesian_labels_device(self, d_planes_ptr, n_frames, width, pixel_size, d_out_ptr, stream=None):
+        """rr_polar_to_cartesian_labels_device: uint32 [n_frames][width][width] in HBM by the nearest rule, on `stream`"""
+        self._polar_shape()
+        c = cartesian_config(width, pixel_size, False)
+        n = _frames_arg(n_frames)
+        if not d_planes_ptr or not d_out_ptr:
+            raise ValueError("polar_to_cartesian_labels_device needs plane and output buffers")
+        self._ck(self._L.rr_polar_to_cartesian_labels_device(self._h, d_planes_ptr, n, C.byref(c), d_out_ptr, stream))
+
+    def polar_to_cartesian_labels(self, planes, width, pixel_size):
+        """rr_polar_to_cartesian_labels on host planes [n][n_cells][n_angles] (or one plane) -> uint32 [n][width][width]"""
+        x = self._label_planes(planes, "planes")
+        c = cartesian_config(width, pixel_size, False)
+        out = np.zeros((len(x), c.width, c.width), np.uint32)
+        self._ck(self._L.rr_polar_to_cartesian_labels(self._h, x.ctypes.data, len(x), C.byref(c), out.ctypes.data))
+        return out
+
+    def simulate_batch_annotations(self, poses, extent=NOTE_DIRECT, want_images=False):
+        """rr_simulate_batch_annotations: poses [n][7] -> (NOTE_DTYPE [n][n_objects], skipped uint32 [n], images uint8 [n][n_cells][n_angles]
+        or None); no label plane leaves the GPU"""
+        p = np.ascontiguousarray(poses, np.float32).reshape(-1, 7)
+        n_cells, n_angles = self._polar_shape()
+        notes = np.zeros((len(p), self.n_objects), NOTE_DTYPE)
+        skipped = np.zeros(len(p), np.uint32)
+        imgs = np.zeros((len(p), n_cells, n_angles), np.uint8) if want_images else None
+        self._ck(self._L.rr_simulate_batch_annotations(self._h, p.ctypes.data, len(p), note_mask(extent), None if imgs is None else imgs.ctypes.data,
+                                                       notes.ctypes.data, skipped.ctypes.data))
+        return notes, skipped, imgs
 
     def synchronize(self, stream=None):
         self._ck(self._L.rr_synchronize(self._h, stream))

@@ -231,6 +231,20 @@ class RadarHIP:
         self._ctx.synchronize(s)
         return out
 
+    # ---- object annotations (rr_notes.hip): one record per object and frame, the labels never leave the GPU
+    def simulate_annotations(self, poses, extent=native.NOTE_DIRECT, want_images=False):
+        """[n][7] poses -> (native.NOTE_DTYPE [n][n_objects], skipped uint32 [n], images or None): per 64 poses one provenance chain
+        and its annotation (rr_simulate_batch_annotations).  `extent`: the pixel classes that feed the extents, a mask of
+        native.NOTE_DIRECT | NOTE_GHOST | NOTE_MULTIPATH or class names."""
+        self._push()
+        poses = native.object_poses_array(poses)
+        mask = native.note_mask(extent)
+        notes, skipped, imgs = [], [], []
+        for at in range(0, len(poses), 64):
+            n, k, im = self._ctx.simulate_batch_annotations(poses[at:at + 64], mask, want_images)
+            notes.append(n); skipped.append(k); imgs.append(im)
+        return np.concatenate(notes), np.concatenate(skipped), (np.concatenate(imgs) if want_images else None)
+
     # ---- the "real to sim gap" (launch/tests/eval_real_to_sim.launch) and the optimiser's other objectives
     # (scripts/radaray_opti.py imports SSIM, PSNR, NMI, VoI and mutual information), on the GPU (rr_metrics.hip)
     def compareImages(self, images, real, which=native.METRIC_ALL, win_size=7):
