@@ -978,6 +978,68 @@ int rr_match_descriptors_device(rr_ctx* ctx, const uint8_t* d_query, int n_query
 int rr_match_descriptors(rr_ctx* ctx, const uint8_t* query, int n_query, const uint8_t* db, int n_db, int n_rings, int n_sectors, int top_k,
                          rr_place_match* out, uint32_t* sse, uint16_t* shift);
 
+/* ---- sweep compensation: motion and Doppler distortion taken out again (rr_deskew.hip) -------------------------------
+ * rr_set_motion_poses gives every azimuth its own sensor pose and the Doppler call draws an echo gain * v_r metres from where the mesh
+ * puts it: the two distortions of a moving spinning FMCW radar (MulRan, Boreas, Oxford).  The calls below are their inverse: points and
+ * bird's-eye images in ONE rigid frame, the reference pose's.  The reference has no such step: parity is UNPINNED and everything below is
+ * the build's own definition (a numpy restatement in tests/deskew_ref.py checks the kernels).  All f32, nothing fused, the quaternion
+ * algebra in the term order of rmagine's (rr_device.h: q_mul, q_conj, q_rot, v_sub, v_add, v_scale, v_dot).  Geometry (n_angles, theta_min,
+ * theta_inc, resolution, n_cells) and scroll_image are read BY VALUE when a call is made, as in rr_detect*.
+ * The record of frame f and azimuth a, from az_poses[f][a] = (q_a, t_a) (map from sensor: the table rr_set_motion_poses takes), the
+ * reference pose ref_poses[f] = (q_ref, t_ref), and optionally the sensor's map-frame velocity v_s = sensor_vel[f] and `gain`, both with
+ * the meaning they have in the Doppler call:
+ *     q = q_mul(q_conj(q_ref), q_a)                 t = q_rot(q_conj(q_ref), v_sub(t_a, t_ref))
+ *     theta = theta_min + (float)a * theta_inc      u = q_rot(q_a, (cosf(theta), sinf(theta), 0))
+ *     v_r = -(v_dot(v_s, u))                        (the Doppler section's dL/dt for a direct echo off a static object)
+ *     dr = gain * v_r                               sensor_vel == NULL or gain == 0: dr = 0 exactly
+ * The device form cannot look at device data: it checks nothing about the poses, the velocities or the table's contents (a non-finite
+ * record gives NaN points and 0 pixels, never an access outside the buffers); the host form refuses them.  d_table and every other
+ * rr_sweep_rec device buffer must be 16-byte aligned.
+ * Compensated points.  For each of the min(d_offsets[f][n_angles], max_points) points of frame f (what rr_detect_device wrote):
+ *     a = (column - scroll_image) mod n_angles, rec = table[f][a]
+ *     r = (float)(((double)bin + 0.5) * resolution)  (the detector's own range)      rc = r - rec.dr
+ *     p = v_scale((x, y, z), rc / r)                 out.xyz = v_add(q_rot(rec.q, p), rec.t)
+ *   intensity, column and bin are copied; one output per input in the same order, so d_offsets stays valid for the output; d_out may
+ *   equal d_points.  A point with rc <= 0 or non-finite, or whose column lies outside the image, gets x = y = z = NaN.  Slots beyond the
+ *   count are not touched.  The kernel reads the counts on the device: no host round trip.
+ * Compensated Cartesian image: the bird's-eye image in the REFERENCE frame.  Pixel (i, j) sits at P = (x, y, 0) exactly as in
+ * rr_polar_to_cartesian; "u from phi" below is that call's formula for u, "wrapped" its n_angles -> 0.
+ *     a_0 = rintf(u), wrapped, with u from phi = atan2f(y, x)                 (the uncompensated nearest rule)
+ *     for k = 1 .. iterations:  rec = table[f][a_{k-1}];  Q = q_rot(q_conj(rec.q), v_sub(P, rec.t));  phi = atan2f(Q.y, Q.x);
+ *                               u from phi;  a_k = rintf(u), wrapped
+ *     with the rec, Q and u of the last step:  rho = sqrtf(v_dot(Q, Q))  (the slant range: the fan is wide in elevation)
+ *                               rho_m = rho + rec.dr  (a gather runs the forward model);  v = rho_m / (float)resolution - 0.5f
+ *     the value is sampled at (u, v) exactly as rr_polar_to_cartesian does (v > n_cells - 0.5 gives 0, v clamped at 0, the column
+ *     mapping, nearest / bilinear, rintf, saturation); a non-finite or negative rho_m gives 0.
+ *   The iteration count is fixed, so the result is a definition, not a tolerance.  At the sweep seam (between the last and the first
+ *   azimuth) a pixel of the reference frame may have been seen twice or not at all; the iteration returns what it returns there.  With an
+ *   identity table (q = (0, 0, 0, 1), t = 0, dr = 0) the result equals rr_polar_to_cartesian_device byte for byte for every `iterations`.
+ * Like the point clouds the device forms write nothing but the caller's buffers, use no context-owned memory and may run on any stream
+ * beside batches in flight.  The host forms stage through context-owned buffers and are synchronous.
+ * Refused with a message and nothing written: -1 for a null ctx; -2 without a config; -3 for a null required buffer, n_frames outside
+ * 1..65535, a table that is not 16-byte aligned, max_points < 0, iterations outside 1..8, n_angles * 32 > 65536 (the Cartesian call keeps a
+ * frame's records in LDS), what rr_polar_to_cartesian_device refuses, a non-finite gain; rr_sweep_table (host form) also for a non-finite
+ * pose or velocity and for a quaternion whose squared norm is off 1 by more than 1e-3. */
+typedef struct rr_sweep_rec {   /* 32 B, two 16-B stores */
+    float q[4];   /* x,y,z,w: rotation from the sensor frame of this azimuth into the reference frame */
+    float t[3];   /* translation of the same transform, metres */
+    float dr;     /* metres to SUBTRACT from a measured range of this azimuth: gain * v_r of a static world */
+} rr_sweep_rec;
+int rr_sweep_table_device(rr_ctx* ctx, const float* d_az_poses /*[n][n_angles][7]*/, const float* d_ref_poses /*[n][7]*/,
+                          const float* d_sensor_vel_or_NULL /*[n][3]*/, float gain, int n_frames, rr_sweep_rec* d_table /*[n][n_angles]*/,
+                          void* stream);
+int rr_sweep_table(rr_ctx* ctx, const float* az_poses, const float* ref_poses, const float* sensor_vel_or_NULL, float gain, int n_frames,
+                   rr_sweep_rec* table);                                                 /* host buffers, synchronous */
+int rr_compensate_points_device(rr_ctx* ctx, const rr_radar_point* d_points, const uint32_t* d_offsets /*[n][n_angles+1]*/, int n_frames,
+                                int max_points, const rr_sweep_rec* d_table, rr_radar_point* d_out /* may equal d_points */, void* stream);
+int rr_compensate_points(rr_ctx* ctx, const rr_radar_point* points, const uint32_t* offsets, int n_frames, int max_points,
+                         const rr_sweep_rec* table, rr_radar_point* out);                /* host buffers, synchronous */
+int rr_polar_to_cartesian_sweep_device(rr_ctx* ctx, const uint8_t* d_imgs_u8, int n_frames, const rr_cartesian_config* cfg,
+                                       const rr_sweep_rec* d_table, int iterations /*1..8*/, uint8_t* d_cart_u8 /*[n][width][width]*/,
+                                       void* stream);
+int rr_polar_to_cartesian_sweep(rr_ctx* ctx, const uint8_t* imgs_u8, int n_frames, const rr_cartesian_config* cfg, const rr_sweep_rec* table,
+                                int iterations, uint8_t* cart_u8);                       /* host buffers, synchronous */
+
 /* ---- several GPUs of one node behind one object (SURVEY.md §8b "Threading", §8e) -------------------------
  * The reference creates ONE backend object per process (src/radar_simulator.cpp:145-176) and fans out inside it
  * (OpenMP over azimuths, RadarCPU.cpp:155).  rr_multi is that object for n GPUs: one rr_ctx per device, mesh and

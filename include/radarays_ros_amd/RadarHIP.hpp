@@ -467,6 +467,50 @@ public:
         if (rr_polar_to_cartesian(m_ctx, image->data.data(), 1, &c, msg->data.data())) return fail();
         return msg;
     }
+    // Sweep compensation (rr_deskew.hip; include/radarays_mi355.h): the record table of one sweep from its per-azimuth poses [n_angles][7]
+    // (what simulateSweeps takes), the reference pose [7] and, with a non-zero Doppler gain, the sensor's map-frame velocity.  Empty on error
+    std::vector<rr_sweep_rec> sweepTable(const std::vector<float>& az_poses, const float* ref_pose7, const float* sensor_vel3 = nullptr,
+                                         float gain = 0.0f)
+    {
+        std::vector<rr_sweep_rec> table;
+        if (!push()) return table;
+        if (!ref_pose7 || az_poses.size() != 7 * (size_t)m_n_angles) { m_err = "sweepTable: the poses must be [n_angles][7]"; return table; }
+        table.resize((size_t)m_n_angles);
+        if (rr_sweep_table(m_ctx, az_poses.data(), ref_pose7, sensor_vel3, gain, 1, table.data())) { fail(); table.clear(); }
+        return table;
+    }
+    // the detections of one image (detect(), with the offsets' total being their count) moved into the reference frame: same order, same
+    // length; NaN for a point whose corrected range is not positive.  Empty on error
+    std::vector<rr_radar_point> compensatePointClouds(const std::vector<rr_radar_point>& points, const std::vector<rr_sweep_rec>& table)
+    {
+        std::vector<rr_radar_point> out;
+        if (points.empty() || !push()) return out;
+        if (table.size() != (size_t)m_n_angles) { m_err = "compensatePointClouds: the table must be [n_angles]"; return out; }
+        std::vector<uint32_t> offs((size_t)m_n_angles + 1, 0u);       // only the total is read
+        offs.back() = (uint32_t)points.size();
+        out.resize(points.size());
+        if (rr_compensate_points(m_ctx, points.data(), offs.data(), 1, (int)points.size(), table.data(), out.data())) { fail(); out.clear(); }
+        return out;
+    }
+    // the bird's-eye image of one polar image in the reference frame of its sweep (toCartesian with the distortion taken out)
+    ImagePtr compensatedCartesian(const ImagePtr& image, const std::vector<rr_sweep_rec>& table, int width, float pixel_size, bool bilinear = true,
+                                  int iterations = 2)
+    {
+        if (!image || !push()) return {};
+        if (image->height != (uint32_t)m_cfg.n_cells || image->width != (uint32_t)m_n_angles || image->data.size() != (size_t)image->height * image->width ||
+            table.size() != (size_t)m_n_angles) {
+            m_err = "compensatedCartesian: the image is not n_cells x n_angles mono8 or the table not [n_angles]";
+            std::cout << "[RadarHIP] " << m_err << std::endl; return {};
+        }
+        rr_cartesian_config c{};
+        c.width = width; c.interpolation = bilinear ? 1 : 0; c.pixel_size = pixel_size;
+        ImagePtr msg = std::make_shared<Image>();
+        msg->stamp = image->stamp; msg->frame_id = image->frame_id;
+        msg->height = msg->width = msg->step = width > 0 ? (uint32_t)width : 0u;
+        msg->data.resize((size_t)msg->height * msg->width);
+        if (rr_polar_to_cartesian_sweep(m_ctx, image->data.data(), 1, &c, table.data(), iterations, msg->data.data())) return fail();
+        return msg;
+    }
     const rr_stats& lastStats() const { return m_stats; }
 
 private:

@@ -202,6 +202,7 @@ struct rr_ctx {
     DevBuf<uint32_t> d_mhist; DevBuf<double> d_ssim_part; DevBuf<rr_image_metrics> d_mrec; int metrics_hist = 0;
     // staging of the host forms of rr_detect / rr_polar_to_cartesian (the device forms use none of it)
     DevBuf<uint8_t> d_conv_in, d_conv_cart; DevBuf<rr_radar_point> d_conv_points; DevBuf<uint32_t> d_conv_offs;
+    DevBuf<float> d_sweep_in; DevBuf<rr_sweep_rec> d_sweep_tab; DevBuf<rr_radar_point> d_sweep_points;   // ... of the host forms of rr_sweep_table / rr_compensate_points / rr_polar_to_cartesian_sweep
     DevBuf<uint32_t> d_conv_hist;      // ... and of rr_compare_images: one chunk's joint histograms on their way to the host
     // rr_align_images_device: one chunk's curves (when the caller gives no buffer) and sums, the records; and the host forms' curves
     DevBuf<long long> d_align_curve, d_conv_curve; DevBuf<unsigned long long> d_align_sums; DevBuf<rr_align_record> d_align_rec;

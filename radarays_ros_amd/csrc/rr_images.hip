@@ -1,5 +1,5 @@
 // rr_images.hip -- the C ABI's image entry points: images in, records / points / images out.  PSNR scores and metrics against a reference image
-// (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), place recognition (rr_place.hip), point clouds and Cartesian images (rr_detect.hip), object annotations (rr_notes.hip): each in a device form, which runs on the
+// (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), place recognition (rr_place.hip), point clouds and Cartesian images (rr_detect.hip), sweep compensation (rr_deskew.hip), object annotations (rr_notes.hip): each in a device form, which runs on the
 // caller's buffers and stream, and a host form, which stages through the context's own buffers on c->stream.
 #include "rr_ctx.h"
 #include <algorithm>
@@ -89,6 +89,43 @@ int check_cartesian(rr_ctx* c, const char* who, const void* imgs, int n_frames, 
     if (k->interpolation != 0 && k->interpolation != 1) return fail(c, -3, w + ": interpolation must be 0 (nearest) or 1 (bilinear)");
     if (!(std::isfinite(k->pixel_size) && k->pixel_size > 0.0f)) return fail(c, -3, w + ": pixel_size must be finite and > 0");
     if (c->cfg.theta_inc == 0.0f) return fail(c, -3, w + ": the config's theta_inc is 0");
+    return 0;
+}
+
+// the refusals the sweep compensation calls share; a device table is read with 16-byte loads, a host table is staged
+int check_sweep(rr_ctx* c, const std::string& w, bool have_buffers, int n_frames, const void* table, bool device)
+{
+    int rc = check_images(c, w, have_buffers && table, "buffer", "n_frames", n_frames, 65535); if (rc) return rc;
+    if (device && (uintptr_t)table % 16 != 0) return fail(c, -3, w + ": the table must be 16-byte aligned");
+    return 0;
+}
+
+int check_sweep_table(rr_ctx* c, const char* who, const void* az, const void* ref, float gain, int n_frames, const void* table, bool device)
+{
+    const std::string w(who);
+    int rc = check_sweep(c, w, az && ref, n_frames, table, device); if (rc) return rc;
+    if (!std::isfinite(gain)) return fail(c, -3, w + ": gain must be finite");
+    return 0;
+}
+
+int check_compensate(rr_ctx* c, const char* who, const void* points, const void* offsets, int n_frames, int max_points, const void* table,
+                     const void* out, bool device)
+{
+    const std::string w(who);
+    int rc = check_sweep(c, w, offsets && (max_points <= 0 || (points && out)), n_frames, table, device); if (rc) return rc;
+    if (max_points < 0) return fail(c, -3, w + ": max_points must be >= 0");
+    return 0;
+}
+
+int check_cartesian_sweep(rr_ctx* c, const char* who, const void* imgs, int n_frames, const rr_cartesian_config* k, const void* table, int iterations,
+                          const void* out, bool device)
+{
+    const std::string w(who);
+    int rc = check_cartesian(c, who, imgs, n_frames, k, out); if (rc) return rc;
+    rc = check_sweep(c, w, true, n_frames, table, device); if (rc) return rc;
+    if (iterations < 1 || iterations > 8) return fail(c, -3, w + ": iterations must be 1..8");
+    if ((size_t)c->cfg.n_angles * sizeof(rr_sweep_rec) > 65536)
+        return fail(c, -3, w + ": n_angles * 32 exceeds 65536: a frame's records do not fit in LDS");
     return 0;
 }
 
@@ -682,6 +719,119 @@ int rr_polar_to_cartesian(rr_ctx* c, const uint8_t* imgs_u8, int n_frames, const
     rc = stage_images(c, imgs_u8, (size_t)n_frames, nullptr, [&]() { RR_HIP(c, c->d_conv_cart.ensure(n_out)); return 0; });
     if (rc) return rc;
     rc = rr_polar_to_cartesian_device(c, c->d_conv_in.p, n_frames, cfg, c->d_conv_cart.p, c->stream); if (rc) return rc;
+    RR_HIP(c, hipMemcpyAsync(cart_u8, c->d_conv_cart.p, n_out, hipMemcpyDeviceToHost, c->stream));
+    RR_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- sweep compensation (rr_deskew.hip) -------------------------------------------------------------------------------
+int rr_sweep_table_device(rr_ctx* c, const float* d_az_poses, const float* d_ref_poses, const float* d_sensor_vel, float gain, int n_frames,
+                          rr_sweep_rec* d_table, void* stream)
+{
+    int rc = check_sweep_table(c, "rr_sweep_table_device", d_az_poses, d_ref_poses, gain, n_frames, d_table, true); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const rr_config& g = c->cfg;
+    launch_sweep_table(d_az_poses, d_ref_poses, d_sensor_vel, gain, n_frames, g.n_angles, g.theta_min, g.theta_inc, d_table, stream_of(c, stream));
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_sweep_table(rr_ctx* c, const float* az_poses, const float* ref_poses, const float* sensor_vel, float gain, int n_frames, rr_sweep_rec* table)
+{
+    const std::string w("rr_sweep_table");
+    int rc = check_sweep_table(c, w.c_str(), az_poses, ref_poses, gain, n_frames, table, false); if (rc) return rc;
+    const size_t n = (size_t)n_frames, A = (size_t)c->cfg.n_angles, n_az = n * A * 7, n_ref = n * 7, n_vel = sensor_vel ? n * 3 : 0;
+    auto finite = [](const float* p, size_t m) { for (size_t i = 0; i < m; i++) if (!std::isfinite(p[i])) return false; return true; };
+    auto unit = [](const float* p, size_t m) {
+        for (size_t i = 0; i < m; i++) {
+            const float* q = p + 7 * i;
+            const double nn = (double)q[0] * q[0] + (double)q[1] * q[1] + (double)q[2] * q[2] + (double)q[3] * q[3];
+            if (!(std::fabs(nn - 1.0) <= 1e-3)) return false;
+        }
+        return true;
+    };
+    if (!finite(az_poses, n_az) || !finite(ref_poses, n_ref) || !finite(sensor_vel, n_vel)) return fail(c, -3, w + ": a non-finite pose or velocity");
+    if (!unit(az_poses, n * A) || !unit(ref_poses, n)) return fail(c, -3, w + ": a quaternion whose squared norm is off 1 by more than 1e-3");
+    RR_HIP(c, hipSetDevice(c->device));
+    RR_HIP(c, hipStreamSynchronize(c->stream));        // the staging buffers may be reallocated
+    RR_HIP(c, c->d_sweep_in.ensure(n_az + n_ref + n * 3));
+    RR_HIP(c, c->d_sweep_tab.ensure(n * A));
+    float* d_az = c->d_sweep_in.p;
+    float* d_ref = d_az + n_az;
+    float* d_vel = d_ref + n_ref;
+    RR_HIP(c, hipMemcpyAsync(d_az, az_poses, n_az * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    RR_HIP(c, hipMemcpyAsync(d_ref, ref_poses, n_ref * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (n_vel) RR_HIP(c, hipMemcpyAsync(d_vel, sensor_vel, n_vel * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    rc = rr_sweep_table_device(c, d_az, d_ref, n_vel ? d_vel : nullptr, gain, n_frames, c->d_sweep_tab.p, c->stream); if (rc) return rc;
+    std::vector<rr_sweep_rec> rec(n * A);               // the caller's buffer is written once everything has arrived
+    rc = records_back(c, rec.data(), c->d_sweep_tab.p, n * A * sizeof(rr_sweep_rec), c->stream); if (rc) return rc;
+    std::copy(rec.begin(), rec.end(), table);
+    return 0;
+}
+
+int rr_compensate_points_device(rr_ctx* c, const rr_radar_point* d_points, const uint32_t* d_offsets, int n_frames, int max_points,
+                                const rr_sweep_rec* d_table, rr_radar_point* d_out, void* stream)
+{
+    int rc = check_compensate(c, "rr_compensate_points_device", d_points, d_offsets, n_frames, max_points, d_table, d_out, true); if (rc) return rc;
+    if (max_points == 0) return 0;
+    RR_HIP(c, hipSetDevice(c->device));
+    const rr_config& g = c->cfg;
+    launch_compensate_points(d_points, d_offsets, n_frames, max_points, d_table, d_out, g.n_angles, g.scroll_image, g.resolution, stream_of(c, stream));
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_compensate_points(rr_ctx* c, const rr_radar_point* points, const uint32_t* offsets, int n_frames, int max_points, const rr_sweep_rec* table,
+                         rr_radar_point* out)
+{
+    int rc = check_compensate(c, "rr_compensate_points", points, offsets, n_frames, max_points, table, out, false); if (rc) return rc;
+    if (max_points == 0) return 0;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)n_frames, A = (size_t)c->cfg.n_angles, mp = (size_t)max_points, n_offs = n * (A + 1);
+    RR_HIP(c, hipStreamSynchronize(c->stream));        // the staging buffers may be reallocated
+    RR_HIP(c, c->d_sweep_points.ensure(n * mp));
+    RR_HIP(c, c->d_conv_offs.ensure(n_offs));
+    RR_HIP(c, c->d_sweep_tab.ensure(n * A));
+    RR_HIP(c, hipMemcpyAsync(c->d_conv_offs.p, offsets, n_offs * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    RR_HIP(c, hipMemcpyAsync(c->d_sweep_tab.p, table, n * A * sizeof(rr_sweep_rec), hipMemcpyHostToDevice, c->stream));
+    // the points of a frame: its first min(total, max_points) slots, in and out; nothing beyond them moves
+    auto count = [&](size_t f) { return std::min<size_t>(offsets[f * (A + 1) + A], mp); };
+    for (size_t f = 0; f < n; f++)
+        if (count(f)) RR_HIP(c, hipMemcpyAsync(c->d_sweep_points.p + f * mp, points + f * mp, count(f) * sizeof(rr_radar_point), hipMemcpyHostToDevice, c->stream));
+    rc = rr_compensate_points_device(c, c->d_sweep_points.p, c->d_conv_offs.p, n_frames, max_points, c->d_sweep_tab.p, c->d_sweep_points.p, c->stream);
+    if (rc) return rc;
+    RR_HIP(c, hipGetLastError());
+    std::vector<rr_radar_point> got(n * mp);
+    for (size_t f = 0; f < n; f++)
+        if (count(f)) RR_HIP(c, hipMemcpyAsync(got.data() + f * mp, c->d_sweep_points.p + f * mp, count(f) * sizeof(rr_radar_point), hipMemcpyDeviceToHost, c->stream));
+    RR_HIP(c, hipStreamSynchronize(c->stream));
+    for (size_t f = 0; f < n; f++) std::copy(got.begin() + f * mp, got.begin() + f * mp + count(f), out + f * mp);
+    return 0;
+}
+
+int rr_polar_to_cartesian_sweep_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_frames, const rr_cartesian_config* cfg, const rr_sweep_rec* d_table,
+                                       int iterations, uint8_t* d_cart_u8, void* stream)
+{
+    int rc = check_cartesian_sweep(c, "rr_polar_to_cartesian_sweep_device", d_imgs_u8, n_frames, cfg, d_table, iterations, d_cart_u8, true); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const rr_config& g = c->cfg;
+    launch_cartesian_sweep(d_imgs_u8, n_frames, *cfg, g.n_cells, g.n_angles, g.scroll_image, g.theta_min, g.theta_inc, (float)g.resolution, d_table,
+                           iterations, d_cart_u8, stream_of(c, stream));
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_polar_to_cartesian_sweep(rr_ctx* c, const uint8_t* imgs_u8, int n_frames, const rr_cartesian_config* cfg, const rr_sweep_rec* table, int iterations,
+                                uint8_t* cart_u8)
+{
+    int rc = check_cartesian_sweep(c, "rr_polar_to_cartesian_sweep", imgs_u8, n_frames, cfg, table, iterations, cart_u8, false);
+    if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)n_frames, A = (size_t)c->cfg.n_angles, n_out = n * cfg->width * cfg->width;
+    rc = stage_images(c, imgs_u8, n, nullptr, [&]() { RR_HIP(c, c->d_conv_cart.ensure(n_out)); RR_HIP(c, c->d_sweep_tab.ensure(n * A)); return 0; });
+    if (rc) return rc;
+    RR_HIP(c, hipMemcpyAsync(c->d_sweep_tab.p, table, n * A * sizeof(rr_sweep_rec), hipMemcpyHostToDevice, c->stream));
+    rc = rr_polar_to_cartesian_sweep_device(c, c->d_conv_in.p, n_frames, cfg, c->d_sweep_tab.p, iterations, c->d_conv_cart.p, c->stream); if (rc) return rc;
     RR_HIP(c, hipMemcpyAsync(cart_u8, c->d_conv_cart.p, n_out, hipMemcpyDeviceToHost, c->stream));
     RR_HIP(c, hipStreamSynchronize(c->stream));
     return 0;

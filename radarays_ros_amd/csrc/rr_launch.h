@@ -1,4 +1,4 @@
-// rr_launch.h -- every launcher of rr_kernels.hip, rr_labels.hip, rr_paths.hip, rr_doppler.hip, rr_refit.hip, rr_detect.hip, rr_notes.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip, rr_place.hip and rr_lbvh.hip, declared ONCE: included where they
+// rr_launch.h -- every launcher of rr_kernels.hip, rr_labels.hip, rr_paths.hip, rr_doppler.hip, rr_refit.hip, rr_detect.hip, rr_deskew.hip, rr_notes.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip, rr_place.hip and rr_lbvh.hip, declared ONCE: included where they
 // are defined (a definition that drifts from its declaration fails there) and where they are called.  Default arguments live here only.
 #pragma once
 #include "../../include/radarays_mi355.h"
@@ -67,6 +67,13 @@ void launch_detect(const uint8_t* imgs, int n_frames, const rr_detect_config& cf
                    uint32_t* offsets, hipStream_t s);
 void launch_cartesian(const uint8_t* imgs, int n_frames, const rr_cartesian_config& cfg, int n_cells, int n_angles, int scroll,
                       float theta_min, float theta_inc, float res, uint8_t* out, hipStream_t s);
+// rr_deskew.hip (sweep compensation).  table [n_frames][n_angles], 16-byte aligned; n_angles * 32 bytes of LDS per workgroup of launch_cartesian_sweep
+void launch_sweep_table(const float* az_poses, const float* ref_poses, const float* sensor_vel, float gain, int n_frames, int n_angles,
+                        float theta_min, float theta_inc, rr_sweep_rec* table, hipStream_t s);
+void launch_compensate_points(const rr_radar_point* points, const uint32_t* offsets, int n_frames, int max_points, const rr_sweep_rec* table,
+                              rr_radar_point* out, int n_angles, int scroll, double resolution, hipStream_t s);
+void launch_cartesian_sweep(const uint8_t* imgs, int n_frames, const rr_cartesian_config& cfg, int n_cells, int n_angles, int scroll, float theta_min,
+                            float theta_inc, float res, const rr_sweep_rec* table, int iterations, uint8_t* out, hipStream_t s);
 // rr_notes.hip (object annotations).  scratch: note_scratch_bytes, 16-byte aligned like notes; every word of it, of notes and of skipped is written by the launches
 size_t note_scratch_bytes(size_t n_frames, size_t n_objects, int n_angles);
 void launch_notes(const uint32_t* labels, const uint8_t* imgs, int n_frames, uint32_t n_objects, uint32_t extent_mask, int n_cells, int n_angles,

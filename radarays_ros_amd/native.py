@@ -40,6 +40,8 @@ SYMBOLS = [
     "rr_set_object_twists", "rr_simulate_batch_doppler_device", "rr_simulate_doppler",
     "rr_annotate_scratch_bytes", "rr_annotate_labels_device", "rr_annotate_labels", "rr_label_points_device",
     "rr_polar_to_cartesian_labels_device", "rr_polar_to_cartesian_labels", "rr_simulate_batch_annotations",
+    "rr_sweep_table_device", "rr_sweep_table", "rr_compensate_points_device", "rr_compensate_points",
+    "rr_polar_to_cartesian_sweep_device", "rr_polar_to_cartesian_sweep",
 ]
 
 
@@ -154,6 +156,21 @@ class RRWaveRec(C.Structure):
 
 # rr_radar_point as numpy sees it (24 B: a PointCloud's point + its intensity channel, and where it came from)
 POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("intensity", "<f4"), ("column", "<u4"), ("bin", "<u4")])
+
+# rr_sweep_rec as numpy sees it (32 B): one azimuth's transform into the reference frame and its Doppler range shift
+SWEEP_DTYPE = np.dtype([("q", "<f4", (4,)), ("t", "<f4", (3,)), ("dr", "<f4")])
+
+
+class RRSweepRec(C.Structure):
+    _fields_ = [("q", C.c_float * 4), ("t", C.c_float * 3), ("dr", C.c_float)]
+
+
+def identity_sweep_table(n_frames, n_angles):
+    """SWEEP_DTYPE [n_frames][n_angles] that compensates nothing: q = (0, 0, 0, 1), t = 0, dr = 0"""
+    t = np.zeros((int(n_frames), int(n_angles)), SWEEP_DTYPE)
+    t["q"][..., 3] = 1.0
+    return t
+
 
 # rr_default_detect_config
 DETECT_DEFAULTS = {"method": 0, "guard_cells": 2, "train_cells": 16, "k": 12, "min_intensity": 1, "min_bin": 0, "cfar_scale": 3.0}
@@ -436,6 +453,12 @@ def lib():
     L.rr_polar_to_cartesian_labels_device.argtypes = [vp, vp, C.c_int, C.POINTER(RRCartesianConfig), vp, vp]
     L.rr_polar_to_cartesian_labels.argtypes = [vp, vp, C.c_int, C.POINTER(RRCartesianConfig), vp]
     L.rr_simulate_batch_annotations.argtypes = [vp, vp, C.c_int, C.c_uint32, vp, vp, vp]
+    L.rr_sweep_table_device.argtypes = [vp, vp, vp, vp, C.c_float, C.c_int, vp, vp]
+    L.rr_sweep_table.argtypes = [vp, vp, vp, vp, C.c_float, C.c_int, vp]
+    L.rr_compensate_points_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]
+    L.rr_compensate_points.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp]
+    L.rr_polar_to_cartesian_sweep_device.argtypes = [vp, vp, C.c_int, C.POINTER(RRCartesianConfig), vp, C.c_int, vp, vp]
+    L.rr_polar_to_cartesian_sweep.argtypes = [vp, vp, C.c_int, C.POINTER(RRCartesianConfig), vp, C.c_int, vp]
     for n in SYMBOLS:
         getattr(L, n)
     _LIB = L
@@ -1157,6 +1180,127 @@ class Context:
         c = cartesian_config(width, pixel_size, bilinear)
         out = np.zeros((len(x), c.width, c.width), np.uint8)
         self._ck(self._L.rr_polar_to_cartesian(self._h, x.ctypes.data, len(x), C.byref(c), out.ctypes.data))
+        return out
+
+    # ---- sweep compensation (rr_deskew.hip): motion and Doppler distortion taken out again; any context with a config, mesh or not
+    def _sweep_inputs(self, az_poses, ref_poses, sensor_vel, gain):
+        """(az [n][n_angles][7], ref [n][7], vel [n][3] or None, gain), shape- and value-checked before any call into the library"""
+        _, n_angles = self._polar_shape()
+        ref = _rows(ref_poses, 7, "reference poses")
+        az = np.asarray(az_poses)
+        if az.dtype.kind not in "fiu":
+            raise ValueError("azimuth poses must be real numbers, got dtype %s" % az.dtype)
+        if az.ndim == 2:
+            az = az[None]
+        if az.ndim != 3 or az.shape != (len(ref), n_angles, 7) or not 1 <= len(ref) <= 65535:
+            raise ValueError("azimuth poses must have shape [n][%d][7] with one reference pose [7] per frame (n in 1..65535), got %s and %s"
+                             % (n_angles, np.asarray(az_poses).shape, np.asarray(ref_poses).shape))
+        az = np.ascontiguousarray(az, np.float32)
+        vel = None if sensor_vel is None else _rows(sensor_vel, 3, "sensor velocities")
+        if vel is not None and len(vel) != len(ref):
+            raise ValueError("sensor_vel must hold one velocity per frame: %d frames, %d velocities" % (len(ref), len(vel)))
+        try:
+            g = float(gain)
+        except (TypeError, ValueError):
+            raise ValueError("gain must be a number, got %r" % (gain,))
+        with np.errstate(over="ignore"):
+            if not np.isfinite(np.float32(g)):
+                raise ValueError("gain must be finite, got %r" % (gain,))
+        return az, ref, vel, g
+
+    def _sweep_records(self, table, n_frames):
+        """SWEEP_DTYPE [n_frames][n_angles] (or one frame's [n_angles]) of this context's shape -> contiguous 2-D array"""
+        _, n_angles = self._polar_shape()
+        t = np.asarray(table)
+        if t.dtype != SWEEP_DTYPE:
+            raise ValueError("a sweep table must have dtype SWEEP_DTYPE, got %s" % t.dtype)
+        if t.ndim == 1:
+            t = t[None]
+        if t.shape != (n_frames, n_angles):
+            raise ValueError("the sweep table must have shape [%d][%d], got %s" % (n_frames, n_angles, np.asarray(table).shape))
+        return np.ascontiguousarray(t)
+
+    def sweep_table_device(self, d_az_poses_ptr, d_ref_poses_ptr, n_frames, d_table_ptr, d_sensor_vel_ptr=None, gain=0.0, stream=None):
+        """rr_sweep_table_device: SWEEP_DTYPE records [n_frames][n_angles] in HBM (16-byte aligned) from float32 poses [n_frames][n_angles][7],
+        reference poses [n_frames][7] and optionally velocities [n_frames][3] in HBM, on `stream`"""
+        self._polar_shape()
+        n = _frames_arg(n_frames)
+        if not d_az_poses_ptr or not d_ref_poses_ptr or not d_table_ptr:
+            raise ValueError("sweep_table_device needs pose, reference pose and table buffers")
+        g = float(gain)
+        if not np.isfinite(g):
+            raise ValueError("gain must be finite, got %r" % (gain,))
+        self._ck(self._L.rr_sweep_table_device(self._h, d_az_poses_ptr, d_ref_poses_ptr, d_sensor_vel_ptr, g, n, d_table_ptr, stream))
+
+    def sweep_table(self, az_poses, ref_poses, sensor_vel=None, gain=0.0):
+        """rr_sweep_table: per-azimuth poses [n][n_angles][7] (the table set_motion_poses takes; or one frame's [n_angles][7]), reference
+        poses [n][7] and optionally map-frame sensor velocities [n][3] with the Doppler `gain` -> SWEEP_DTYPE [n][n_angles]"""
+        az, ref, vel, g = self._sweep_inputs(az_poses, ref_poses, sensor_vel, gain)
+        table = np.zeros(az.shape[:2], SWEEP_DTYPE)
+        self._ck(self._L.rr_sweep_table(self._h, az.ctypes.data, ref.ctypes.data, None if vel is None else vel.ctypes.data, g, len(ref),
+                                        table.ctypes.data))
+        return table
+
+    def compensate_points_device(self, d_points_ptr, d_offsets_ptr, n_frames, max_points, d_table_ptr, d_out_ptr=None, stream=None):
+        """rr_compensate_points_device: the points rr_detect_device wrote, moved into the reference frame; d_out_ptr None: in place"""
+        self._polar_shape()
+        n, mp = _frames_arg(n_frames), _int_in(max_points, 0, 2**31 - 1, "max_points")
+        if not d_offsets_ptr or not d_table_ptr or (mp > 0 and not d_points_ptr):
+            raise ValueError("compensate_points_device needs point, offset and table buffers")
+        self._ck(self._L.rr_compensate_points_device(self._h, d_points_ptr, d_offsets_ptr, n, mp, d_table_ptr, d_out_ptr or d_points_ptr, stream))
+
+    def compensate_points(self, points, offsets, table):
+        """rr_compensate_points on what detect() returned: a list of n POINT_DTYPE arrays and offsets uint32 [n][n_angles + 1], with a
+        sweep table SWEEP_DTYPE [n][n_angles] -> a list of n POINT_DTYPE arrays in the reference frame, same order and lengths"""
+        _, n_angles = self._polar_shape()
+        if isinstance(points, np.ndarray) and points.ndim == 1:
+            points = [points]
+        pts = [np.asarray(p) for p in points]
+        if not pts or len(pts) > 65535 or any(p.dtype != POINT_DTYPE or p.ndim != 1 for p in pts):
+            raise ValueError("points must be a list of 1..65535 one-dimensional POINT_DTYPE arrays")
+        n = len(pts)
+        offs = np.asarray(offsets)
+        if offs.ndim == 1:
+            offs = offs[None]
+        if offs.dtype != np.uint32 or offs.shape != (n, n_angles + 1):
+            raise ValueError("offsets must be uint32 [%d][%d], got %s %s" % (n, n_angles + 1, offs.dtype, offs.shape))
+        offs = np.ascontiguousarray(offs)
+        t = self._sweep_records(table, n)
+        mp = max(1, max(len(p) for p in pts))
+        if any(len(p) != min(int(offs[f, -1]), mp) for f, p in enumerate(pts)):
+            raise ValueError("every frame must hold the points its offsets count")
+        buf = np.zeros((n, mp), POINT_DTYPE)
+        for f, p in enumerate(pts):
+            buf[f, :len(p)] = p
+        self._ck(self._L.rr_compensate_points(self._h, buf.ctypes.data, offs.ctypes.data, n, mp, t.ctypes.data, buf.ctypes.data))
+        return [buf[f, :len(p)].copy() for f, p in enumerate(pts)]
+
+    @staticmethod
+    def _iterations(iterations):
+        return _int_in(iterations, 1, 8, "iterations")
+
+    def polar_to_cartesian_sweep_device(self, d_imgs_ptr, n_frames, width, pixel_size, d_table_ptr, d_out_ptr, bilinear=True, iterations=2, stream=None):
+        """rr_polar_to_cartesian_sweep_device: [n_frames][width][width] uint8 in the reference frame, in HBM, on `stream`"""
+        _, n_angles = self._polar_shape()
+        c = cartesian_config(width, pixel_size, bilinear)
+        n, it = _frames_arg(n_frames), self._iterations(iterations)
+        if n_angles * SWEEP_DTYPE.itemsize > 65536:
+            raise ValueError("n_angles * 32 exceeds 65536: a frame's records do not fit in LDS")
+        if not d_imgs_ptr or not d_table_ptr or not d_out_ptr:
+            raise ValueError("polar_to_cartesian_sweep_device needs image, table and output buffers")
+        self._ck(self._L.rr_polar_to_cartesian_sweep_device(self._h, d_imgs_ptr, n, C.byref(c), d_table_ptr, it, d_out_ptr, stream))
+
+    def polar_to_cartesian_sweep(self, imgs, table, width, pixel_size, bilinear=True, iterations=2):
+        """rr_polar_to_cartesian_sweep on host images [n][n_cells][n_angles] (or one image) and a sweep table SWEEP_DTYPE [n][n_angles]
+        -> uint8 [n][width][width] in the reference frame"""
+        x = self._polar_images(imgs)
+        c = cartesian_config(width, pixel_size, bilinear)
+        it = self._iterations(iterations)
+        t = self._sweep_records(table, len(x))
+        if x.shape[2] * SWEEP_DTYPE.itemsize > 65536:
+            raise ValueError("n_angles * 32 exceeds 65536: a frame's records do not fit in LDS")
+        out = np.zeros((len(x), c.width, c.width), np.uint8)
+        self._ck(self._L.rr_polar_to_cartesian_sweep(self._h, x.ctypes.data, len(x), C.byref(c), t.ctypes.data, it, out.ctypes.data))
         return out
 
     # ---- object annotations (rr_notes.hip): one record per object from label images; any context with a config, mesh or not

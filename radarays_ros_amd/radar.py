@@ -13,7 +13,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from . import beams, native
+from . import beams, native, scenes
 from .params import (N_ANGLES, WAVE_ENERGY_THRESHOLD, RadarModelConfig, RadarParams,
                      default_params)
 
@@ -229,6 +229,45 @@ class RadarHIP:
                 host = pts.cpu().numpy().view(native.POINT_DTYPE)
                 out.extend(host[f, :int(totals[f])].copy() for f in range(n))
         self._ctx.synchronize(s)
+        return out
+
+    # ---- sweep compensation (rr_deskew.hip): a sweep under motion, as the sensor records it and with the distortion taken out again
+    def simulate_sweep(self, pose_ref, twist, sweep_time, gain=0.0, detect=None, cartesian=None, ref_azimuth=0):
+        """One sweep of a sensor that moves with the constant body twist `twist` (vx vy vz wx wy wz, sensor frame) for `sweep_time` seconds;
+        pose_ref [7] is its pose when azimuth `ref_azimuth` is measured.  scenes.sweep_poses makes the per-azimuth poses; they are installed
+        as the motion table, the frame is simulated (through the Doppler call with the sensor's velocity when gain != 0, the plain call
+        otherwise), detected and compensated into the frame of pose_ref.  detect: a dict of rr_detect_config fields ({}: the defaults) or
+        None for no points; cartesian: a dict(width=, pixel_size=, bilinear=True, iterations=2) or None for no bird's-eye images.
+        Returns a dict: image (u8 [n_cells][400], distorted), poses [400][7], sensor_vel [3], table (native.SWEEP_DTYPE [400]), and, as asked
+        for, points_raw / offsets / points and cartesian_raw / cartesian.  The context's motion table is left as it was found, also when
+        a call raises."""
+        poses, vel = scenes.sweep_poses(pose_ref, twist, sweep_time, N_ANGLES, ref_azimuth)
+        ref = np.ascontiguousarray(pose_ref, np.float32)
+        gain = float(gain)
+        self._push()
+        ctx = self._ctx
+        out = {"poses": poses, "sensor_vel": vel}
+        ctx.set_motion_poses(poses)
+        try:
+            if gain != 0.0:
+                out["image"] = ctx.simulate_doppler(ref, sensor_vel=vel, gain=gain, echo_stride=0, want_vel_img=False)[0]
+            else:
+                out["image"] = ctx.simulate(ref)[0]
+            table = ctx.sweep_table(poses, ref, vel if gain != 0.0 else None, gain)
+            out["table"] = table[0]
+            if detect is not None:
+                pts, offs = ctx.detect(out["image"], detect)
+                out["points_raw"], out["offsets"] = pts[0], offs[0]
+                out["points"] = ctx.compensate_points(pts, offs, table)[0]
+            if cartesian is not None:
+                c = dict(cartesian)
+                width, ps, bil, it = c.pop("width"), c.pop("pixel_size"), c.pop("bilinear", True), c.pop("iterations", 2)
+                if c:
+                    raise ValueError("unknown cartesian fields: %s" % sorted(c))
+                out["cartesian_raw"] = ctx.polar_to_cartesian(out["image"], width, ps, bil)[0]
+                out["cartesian"] = ctx.polar_to_cartesian_sweep(out["image"], table, width, ps, bil, it)[0]
+        finally:
+            ctx.set_motion_poses(self._motion)
         return out
 
     # ---- object annotations (rr_notes.hip): one record per object and frame, the labels never leave the GPU

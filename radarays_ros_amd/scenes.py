@@ -251,6 +251,50 @@ def yaw_pose(x, y, z, yaw):
     return np.array([0.0, 0.0, np.sin(yaw / 2.0), np.cos(yaw / 2.0), x, y, z], np.float32)
 
 
+def sweep_poses(pose_ref, twist6, sweep_time, n_angles, ref_azimuth):
+    """The sensor poses of one sweep under a constant body twist: pose_ref [7] (qx qy qz qw tx ty tz, map from sensor) is the pose at
+    the moment azimuth `ref_azimuth` is measured, twist6 = (vx vy vz wx wy wz) in the sensor frame (m/s, rad/s), azimuth a is measured
+    at time (a - ref_azimuth) / n_angles * sweep_time.  The twist is integrated in float64 (the exponential of se(3)):
+    T(tau) = T_ref * exp(tau * twist).  Returns (float32 [n_angles][7], the one table that feeds both set_motion_poses and sweep_table;
+    float32 [3], the sensor's map-frame velocity at the reference time, what the Doppler call takes)."""
+    p = np.asarray(pose_ref, np.float64)
+    xi = np.asarray(twist6, np.float64)
+    if p.shape != (7,) or xi.shape != (6,):
+        raise ValueError("pose_ref must be [7] and twist6 [6], got %s and %s" % (p.shape, xi.shape))
+    n_angles = int(n_angles)
+    if n_angles < 1:
+        raise ValueError("n_angles must be at least 1")
+
+    def qmul(a, b):
+        ax, ay, az, aw = a
+        bx, by, bz, bw = b
+        return np.array([aw * bx + ax * bw + ay * bz - az * by, aw * by - ax * bz + ay * bw + az * bx,
+                         aw * bz + ax * by - ay * bx + az * bw, aw * bw - ax * bx - ay * by - az * bz])
+
+    def qrot(q, v):
+        return qmul(qmul(q, np.append(v, 0.0)), q * np.array([-1.0, -1.0, -1.0, 1.0]))[:3]
+
+    q_ref = p[:4] / np.linalg.norm(p[:4])
+    v, w = xi[:3], xi[3:]
+    out = np.zeros((n_angles, 7), np.float64)
+    for a in range(n_angles):
+        tau = (a - float(ref_azimuth)) / n_angles * float(sweep_time)
+        phi = w * tau                                   # the rotation vector of the step
+        th = np.linalg.norm(phi)
+        if th < 1e-12:
+            dq = np.append(0.5 * phi, 1.0)
+            dt = v * tau + 0.5 * np.cross(phi, v * tau)
+        else:
+            k = phi / th
+            dq = np.append(np.sin(0.5 * th) * k, np.cos(0.5 * th))
+            u = v * tau                                 # V(phi) u: the translation of the exponential
+            dt = u + (1.0 - np.cos(th)) / th * np.cross(k, u) + (1.0 - np.sin(th) / th) * np.cross(k, np.cross(k, u))
+        q = qmul(q_ref, dq)
+        out[a, :4] = q / np.linalg.norm(q)
+        out[a, 4:] = p[4:] + qrot(q_ref, dt)
+    return out.astype(np.float32), qrot(q_ref, v).astype(np.float32)
+
+
 def default_pose(scene_name="", height=2.0):
     """t = (1.0, 1.5, .), yaw 0.3 (cf. launch/mro_husky.launch:15,23)."""
     if scene_name.startswith("box12"):
