@@ -1040,6 +1040,70 @@ int rr_polar_to_cartesian_sweep_device(rr_ctx* ctx, const uint8_t* d_imgs_u8, in
 int rr_polar_to_cartesian_sweep(rr_ctx* ctx, const uint8_t* imgs_u8, int n_frames, const rr_cartesian_config* cfg, const rr_sweep_rec* table,
                                 int iterations, uint8_t* cart_u8);                       /* host buffers, synchronous */
 
+/* ---- scan matching: rigid 2-D registration of point clouds (rr_icp.hip) ------------------------------------------------
+ * Batched point-to-point ICP in the plane with a FIXED iteration count: which SE(2) moves each of n source clouds onto ONE target cloud.
+ * The reference has no such step: parity is UNPINNED and everything below is the build's own definition (a numpy restatement in
+ * tests/icp_ref.py checks the kernels bit for bit).  All f32 arithmetic is un-fused.
+ * Source frame f is what rr_detect_device or rr_compensate_points_device wrote at d_points + f * max_points; its count is
+ * min(d_offsets[f][n_angles], max_points), read on the device with no host round trip.  The target is
+ * d_tgt_points[0 .. min(*d_tgt_count, max_tgt)), d_tgt_count a device uint32_t* (a caller passes &offsets[g][n_angles] of any detected
+ * frame).  z, intensity, column and bin are ignored.  The source may alias the target.
+ * The state per frame is (c, s, tx, ty) in f64: the transform q ~ R p + t that maps a source point into the target's frame.
+ * d_init [n][4] f64 holds the initial states; NULL means identity.  (c, s) of an initial state is normalised once by
+ * hypot = sqrt(c*c + s*s); a non-finite or zero hypot is refused by the host form, and in the device form sets RR_ICP_DEGENERATE and
+ * makes the state the identity.
+ * One CORRESPONDENCE PASS for a state:
+ *   1. cf, sf, txf, tyf are the state rounded to f32.  For source point i:
+ *          px = (cf*x - sf*y) + txf            py = (sf*x + cf*y) + tyf
+ *   2. best = +inf, j* = NONE.  For j ascending over the target: dx = px - Tx[j], dy = py - Ty[j], d2 = dx*dx + dy*dy; take j iff
+ *      d2 < best.  So ties go to the lower index and a NaN never wins.  A target point with a non-finite coordinate, or with
+ *      |coordinate| >= 8192, is never a candidate.
+ *   3. Point i is MATCHED iff px and py are finite and below 8192 in magnitude, j* != NONE, and best <= gate2, gate2 = gate * gate in f32.
+ *   4. The matched pairs are quantised: P = (int32)rintf(p * 256.0f) per coordinate of (px, py); Q likewise from the target's coordinates.
+ *   5. These int64 sums run over the matched pairs: N, SPx, SPy, SQx, SQy, Sdot = sum(Px*Qx + Py*Qy), Scross = sum(Px*Qy - Py*Qx),
+ *      Ssse = sum((Px-Qx)^2 + (Py-Qy)^2).  With at most 65,536 points and |P| <= 2^21 no sum overflows; integer sums make the result
+ *      independent of order.
+ * One SOLVE is f64 arithmetic only (+ - * / sqrt, no trigonometry).  Every sum is converted to f64 first, the expressions are
+ * evaluated as written:
+ *     A = N*Sdot - (SPx*SQx + SPy*SQy)         B = N*Scross - (SPx*SQy - SPy*SQx)         h = sqrt(A*A + B*B)
+ *     if N < 2 or !(h > 0):  flags |= RR_ICP_DEGENERATE  (the state keeps its value in this iteration)
+ *     else:  dc = A/h   ds = B/h   mpx = (SPx/N)/256  (likewise mpy, mqx, mqy)
+ *            dtx = mqx - (dc*mpx - ds*mpy)     dty = mqy - (ds*mpx + dc*mpy)
+ *            c' = dc*c - ds*s    s' = ds*c + dc*s    tx' = (dc*tx - ds*ty) + dtx    ty' = (ds*tx + dc*ty) + dty
+ *            (c', s') divided by sqrt(c'*c' + s'*s')
+ * The call runs `iterations` times (pass, solve), then one last pass at the final state.  The count is fixed: a definition, not a
+ * tolerance.  iterations = 0 scores the initial states only (a point-cloud likelihood for n hypotheses); no solve runs then, so
+ * RR_ICP_DEGENERATE can only come from an initial state.
+ * Output per frame is one rr_icp_rec from the last pass: the state, sse = Ssse, n_matched = N, flags (RR_ICP_DEGENERATE is sticky;
+ * RR_ICP_TRUNCATED: the source's or the target's count exceeded its max).  Optionally d_corr [n][max_points] uint32 receives the last
+ * pass's j* per source point, 0xFFFFFFFF for an unmatched point (also one whose nearest lies beyond the gate); nothing is written past
+ * a frame's count.  NULL: not wanted.
+ * The device form enqueues 2 * iterations + 3 launches on `stream` (the initial states, the pairs, the last pass and the step that
+ * writes the record) with no host round trip between them.  It touches no context memory but a scratch accumulator of 64 bytes per frame
+ * that the context keeps PER STREAM (it grows with the largest n_frames seen on that stream; growing it waits for the device), so it
+ * may run on any stream beside batches in flight, and calls on different streams may overlap.  d_init and d_recs must be 8-byte aligned.
+ * The host form stages through context-owned buffers and is synchronous; its tgt_count is a value.
+ * Refused with a message and nothing written: -1 for a null ctx; -2 without a config (n_angles is the offsets' stride); -3 for a null
+ * required buffer, n_frames outside 1..65535, max_points or max_tgt outside 0..65536, iterations outside 0..64, a gate that is not
+ * finite and positive, a misaligned d_init or d_recs; the host form also for an initial state whose hypot is zero or not finite. */
+#define RR_ICP_DEGENERATE 1u   /* a solve had fewer than 2 matched pairs or no direction (h == 0), or the initial state had no direction */
+#define RR_ICP_TRUNCATED 2u    /* the source's or the target's count exceeded max_points / max_tgt: the cloud was cut */
+typedef struct rr_icp_rec {    /* 48 B */
+    double c, s, tx, ty;       /* q ~ [c -s; s c] p + (tx, ty): source frame into target frame; c*c + s*s = 1 up to rounding */
+    int64_t sse;               /* Ssse of the last pass, in (1/256 m)^2 */
+    uint32_t n_matched;        /* N of the last pass */
+    uint32_t flags;            /* RR_ICP_* */
+} rr_icp_rec;
+int rr_register_points_device(rr_ctx* ctx, const rr_radar_point* d_points, const uint32_t* d_offsets /*[n][n_angles+1]*/, int n_frames,
+                              int max_points, const rr_radar_point* d_tgt_points, const uint32_t* d_tgt_count, int max_tgt,
+                              const double* d_init_or_NULL /*[n][4]*/, float gate, int iterations /*0..64*/, rr_icp_rec* d_recs /*[n]*/,
+                              uint32_t* d_corr_or_NULL /*[n][max_points]*/, void* stream);
+int rr_register_points(rr_ctx* ctx, const rr_radar_point* points, const uint32_t* offsets, int n_frames, int max_points,
+                       const rr_radar_point* tgt_points, uint32_t tgt_count, int max_tgt, const double* init_or_NULL, float gate, int iterations,
+                       rr_icp_rec* recs, uint32_t* corr_or_NULL);                        /* host buffers, synchronous */
+/* the blocking of k_icp_pass: source points per workgroup and (x, y) pairs per LDS tile of the target (tests put counts at their edges) */
+void rr_icp_tile_sizes(int* source_tile, int* target_tile);
+
 /* ---- several GPUs of one node behind one object (SURVEY.md §8b "Threading", §8e) -------------------------
  * The reference creates ONE backend object per process (src/radar_simulator.cpp:145-176) and fans out inside it
  * (OpenMP over azimuths, RadarCPU.cpp:155).  rr_multi is that object for n GPUs: one rr_ctx per device, mesh and

@@ -13,6 +13,7 @@
 // Here: the `Radar` base, the dirty flags, `Image`s, detect / toCartesian and how errors are reported.
 #pragma once
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <iostream>
@@ -510,6 +511,47 @@ public:
         msg->data.resize((size_t)msg->height * msg->width);
         if (rr_polar_to_cartesian_sweep(m_ctx, image->data.data(), 1, &c, table.data(), iterations, msg->data.data())) return fail();
         return msg;
+    }
+    // Scan matching (rr_icp.hip; include/radarays_mi355.h): point clouds (detect() or compensatePointClouds() of simulated images) registered
+    // against ONE real cloud by planar point-to-point ICP with a fixed iteration count, from the states `init` ([n][4] = c s tx ty per
+    // cloud) or from the identity.  One rr_icp_rec per cloud: the transform that maps the cloud into the real cloud's frame, sse,
+    // n_matched, flags.  Empty on error
+    std::vector<rr_icp_rec> registerPointClouds(const std::vector<std::vector<rr_radar_point>>& clouds, const std::vector<rr_radar_point>& real,
+                                                float gate = 1.0f, int iterations = 10, const std::vector<double>& init = {})
+    {
+        std::vector<rr_icp_rec> recs;
+        if (clouds.empty() || !push()) return recs;
+        size_t mp = 1;
+        for (const auto& c : clouds) mp = std::max(mp, c.size());
+        if (mp > 65536 || real.size() > 65536 || (!init.empty() && init.size() != 4 * clouds.size())) {
+            m_err = "registerPointClouds: a cloud of more than 65536 points, or init is not [n][4]"; return recs;
+        }
+        const size_t n = clouds.size(), stride = (size_t)m_n_angles + 1;
+        std::vector<rr_radar_point> pts(n * mp);
+        std::vector<uint32_t> offs(n * stride, 0u);                   // only each frame's total is read
+        for (size_t f = 0; f < n; f++) {
+            std::copy(clouds[f].begin(), clouds[f].end(), pts.begin() + f * mp);
+            offs[f * stride + m_n_angles] = (uint32_t)clouds[f].size();
+        }
+        recs.resize(n);
+        if (rr_register_points(m_ctx, pts.data(), offs.data(), (int)n, (int)mp, real.data(), (uint32_t)real.size(), (int)real.size(),
+                               init.empty() ? nullptr : init.data(), gate, iterations, recs.data(), nullptr)) { fail(); recs.clear(); }
+        return recs;
+    }
+    // the pose hypothesis X_h (qx qy qz qw tx ty tz) whose simulated cloud gave `rec` against the real cloud, corrected: T = X^-1 X_h, so
+    // the result is X_h T^-1 -- X_h turned by -atan2(s, c) about its own z axis and moved by -R^T t in its own axes
+    static std::array<float, 7> correctedPose(const float* pose7, const rr_icp_rec& rec)
+    {
+        const double c = rec.c, s = rec.s, v[3] = { -(c * rec.tx + s * rec.ty), -(-s * rec.tx + c * rec.ty), 0.0 };
+        const double u[3] = { pose7[0], pose7[1], pose7[2] }, w = pose7[3];
+        const double uv[3] = { u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0] };
+        const double uuv[3] = { u[1] * uv[2] - u[2] * uv[1], u[2] * uv[0] - u[0] * uv[2], u[0] * uv[1] - u[1] * uv[0] };
+        const double half = -0.5 * std::atan2(s, c), bz = std::sin(half), bw = std::cos(half);
+        std::array<float, 7> out;
+        out[0] = (float)(u[0] * bw + u[1] * bz); out[1] = (float)(u[1] * bw - u[0] * bz);
+        out[2] = (float)(w * bz + u[2] * bw); out[3] = (float)(w * bw - u[2] * bz);
+        for (int k = 0; k < 3; k++) out[4 + k] = (float)(pose7[4 + k] + v[k] + 2.0 * (w * uv[k] + uuv[k]));
+        return out;
     }
     const rr_stats& lastStats() const { return m_stats; }
 

@@ -5,6 +5,7 @@
 #include "rr_launch.h"
 #include "rr_sdma.h"
 #include <map>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -203,6 +204,11 @@ struct rr_ctx {
     // staging of the host forms of rr_detect / rr_polar_to_cartesian (the device forms use none of it)
     DevBuf<uint8_t> d_conv_in, d_conv_cart; DevBuf<rr_radar_point> d_conv_points; DevBuf<uint32_t> d_conv_offs;
     DevBuf<float> d_sweep_in; DevBuf<rr_sweep_rec> d_sweep_tab; DevBuf<rr_radar_point> d_sweep_points;   // ... of the host forms of rr_sweep_table / rr_compensate_points / rr_polar_to_cartesian_sweep
+    // rr_register_points_device: the eight int64 sums per frame, one buffer per stream it has been called on (icp_mu guards the map, not the
+    // buffers: calls on one stream are ordered by that stream); and the host form's staging: source and target points, offsets + the target's
+    // count + correspondences, initial states, records
+    std::map<hipStream_t, DevBuf<long long>> icp_acc; std::mutex icp_mu;
+    DevBuf<rr_radar_point> d_icp_points; DevBuf<uint32_t> d_icp_words; DevBuf<double> d_icp_init; DevBuf<rr_icp_rec> d_icp_rec;
     DevBuf<uint32_t> d_conv_hist;      // ... and of rr_compare_images: one chunk's joint histograms on their way to the host
     // rr_align_images_device: one chunk's curves (when the caller gives no buffer) and sums, the records; and the host forms' curves
     DevBuf<long long> d_align_curve, d_conv_curve; DevBuf<unsigned long long> d_align_sums; DevBuf<rr_align_record> d_align_rec;

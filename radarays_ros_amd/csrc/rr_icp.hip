@@ -1,0 +1,221 @@
+// rr_icp.hip -- gfx950 kernels of the planar scan matcher (rr_register_points_device; the definition is in include/radarays_mi355.h):
+// n source clouds registered against ONE target cloud by point-to-point ICP with a fixed iteration count.
+//
+//   k_icp_init     one thread per frame: the initial state normalised into the frame's record (which carries the state from launch to
+//                  launch), the TRUNCATED / DEGENERATE flags, the frame's eight sums zeroed
+//   k_icp_pass     one correspondence pass.  Grid (source tiles, frames), kIcpTB threads, kIcpPPT source points per thread in registers
+//                  (a source tile is kIcpSrcTile = kIcpTB * kIcpPPT points).  The target streams through LDS in tiles of kIcpTgtTile
+//                  (x, y) pairs; a point that may not be a candidate, and the padding of the last pair, is staged as (+inf, +inf), so the
+//                  inner loop has no branch: its d2 is +inf or NaN and `d2 < best` is false.  Every lane reads the same LDS address (a
+//                  broadcast: one 16-B read is two targets for all 64 lanes) and spends it on 2 * kIcpPPT distance evaluations of
+//                  8 VALU operations each (2 sub, 2 mul, 1 add, 1 compare, 2 selects: nothing fused) and one v_mov of the index per target.  A thread walks the target in
+//                  ascending order with a strict `<`, so ties go to the lower index whatever the tiling.  The matched pairs are
+//                  quantised to 1/256 m, the eight int64 sums are reduced across the wave with shuffles and lane 0 adds them to the
+//                  frame's accumulator with one 64-bit vector atomic per sum: integer sums, so the order of arrival does not matter
+//   k_icp_solve    one thread per frame: reads the sums, zeroes them, and either takes the closed-form 2-D step in f64
+//                  (+ - * / sqrt only) or, behind the last pass, writes sse and n_matched into the record
+//
+// The sums cross from k_icp_pass to k_icp_solve and the state from k_icp_solve to k_icp_pass at KERNEL BOUNDARIES only: the XCD L2s are
+// not coherent within a launch.  Every scalar travels as a kernel argument.  No scratch memory; 8 KB of static LDS in k_icp_pass.
+#include "../../include/radarays_mi355.h"
+#include "rr_device.h"
+#include "rr_launch.h"
+
+#include <algorithm>
+
+namespace rr {
+
+namespace {
+
+constexpr int kIcpTB = 128;                          // threads of a k_icp_pass workgroup: two waves
+constexpr int kIcpPPT = 2;                           // source points a thread keeps in registers (why 2 and not more: DESIGN.md §22)
+constexpr int kIcpSrcTile = kIcpTB * kIcpPPT;        // 256
+constexpr int kIcpTgtTile = 1024;                    // (x, y) pairs of a target tile in LDS: 8 KB
+constexpr uint32_t kIcpNone = 0xFFFFFFFFu;
+constexpr float kIcpRange = 8192.0f;                 // a coordinate must be finite and below this in magnitude
+enum { S_N = 0, S_PX, S_PY, S_QX, S_QY, S_DOT, S_CROSS, S_SSE, S_COUNT };
+
+static_assert(sizeof(rr_icp_rec) == 48, "a record is 48 bytes");
+static_assert(sizeof(rr_radar_point) == 24, "x and y lead a 24-byte point");
+static_assert(kIcpTgtTile % 2 == 0 && kIcpTB % 64 == 0, "targets are read in pairs, sums are reduced per wave");
+
+__device__ inline bool in_range(float v) { return fabsf(v) < kIcpRange; }      // false for NaN and infinities
+
+__device__ inline uint32_t source_count(const uint32_t* offsets, int f, int n_angles, int max_points, bool* truncated)
+{
+    const uint32_t total = offsets[(size_t)f * (n_angles + 1) + n_angles];
+    if (truncated) *truncated = total > (uint32_t)max_points;
+    return min(total, (uint32_t)max_points);
+}
+
+__global__ void __launch_bounds__(256) k_icp_init(const double* init, const uint32_t* offsets, int n_angles, int max_points, const uint32_t* tgt_count,
+                                                  int max_tgt, rr_icp_rec* recs, long long* acc, int n_frames)
+{
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n_frames) return;
+    double c = 1.0, s = 0.0, tx = 0.0, ty = 0.0;
+    uint32_t flags = 0;
+    if (init) {
+        c = init[4 * (size_t)f]; s = init[4 * (size_t)f + 1]; tx = init[4 * (size_t)f + 2]; ty = init[4 * (size_t)f + 3];
+        const double h = sqrt(c * c + s * s);
+        if (h > 0.0 && h < (double)INFINITY) { c = c / h; s = s / h; }
+        else { flags |= RR_ICP_DEGENERATE; c = 1.0; s = 0.0; tx = 0.0; ty = 0.0; }
+    }
+    bool trunc;
+    source_count(offsets, f, n_angles, max_points, &trunc);
+    if (trunc || *tgt_count > (uint32_t)max_tgt) flags |= RR_ICP_TRUNCATED;
+    rr_icp_rec r;
+    r.c = c; r.s = s; r.tx = tx; r.ty = ty; r.sse = 0; r.n_matched = 0; r.flags = flags;
+    recs[f] = r;
+    for (int k = 0; k < S_COUNT; k++) acc[(size_t)f * S_COUNT + k] = 0;
+}
+
+__global__ void __launch_bounds__(kIcpTB) k_icp_pass(const rr_radar_point* points, const uint32_t* offsets, int n_angles, int max_points,
+                                                     const rr_radar_point* tgt, const uint32_t* tgt_count, int max_tgt, const rr_icp_rec* recs,
+                                                     float gate2, unsigned long long* acc, uint32_t* corr)
+{
+    __shared__ __align__(16) float2 tile[kIcpTgtTile];
+
+    const int f = blockIdx.y;
+    const uint32_t m = source_count(offsets, f, n_angles, max_points, nullptr);
+    const uint32_t i0 = blockIdx.x * (uint32_t)kIcpSrcTile;
+    if (i0 >= m) return;                                          // (the whole workgroup: no barrier has been met)
+    const uint32_t nt = min(*tgt_count, (uint32_t)max_tgt);
+    const rr_radar_point* src = points + (size_t)f * max_points;
+
+    const float cf = (float)recs[f].c, sf = (float)recs[f].s, txf = (float)recs[f].tx, tyf = (float)recs[f].ty;
+    float px[kIcpPPT], py[kIcpPPT], best[kIcpPPT];
+    uint32_t bj[kIcpPPT];
+#pragma unroll
+    for (int e = 0; e < kIcpPPT; e++) {
+        const uint32_t i = i0 + (uint32_t)e * kIcpTB + threadIdx.x;
+        px[e] = py[e] = __uint_as_float(0x7FC00000u);             // a slot past the count: NaN never wins and is never matched
+        if (i < m) {
+            const float x = src[i].x, y = src[i].y;
+            px[e] = (cf * x - sf * y) + txf;
+            py[e] = (sf * x + cf * y) + tyf;
+        }
+        best[e] = INFINITY; bj[e] = kIcpNone;
+    }
+
+    for (uint32_t t0 = 0; t0 < nt; t0 += kIcpTgtTile) {
+        const uint32_t cnt = min((uint32_t)kIcpTgtTile, nt - t0), padded = (cnt + 1u) & ~1u;
+        if (t0) __syncthreads();                                  // the tile before this one has been read by every wave
+        for (uint32_t k = threadIdx.x; k < padded; k += kIcpTB) {
+            float x = INFINITY, y = INFINITY;
+            if (k < cnt) {
+                const float qx = tgt[t0 + k].x, qy = tgt[t0 + k].y;
+                if (in_range(qx) && in_range(qy)) { x = qx; y = qy; }
+            }
+            tile[k] = make_float2(x, y);
+        }
+        __syncthreads();
+        const float4* pairs = reinterpret_cast<const float4*>(tile);
+        // four pairs per trip: their LDS reads are issued together, so a wave alone on its SIMD waits for the first of eight targets only
+#pragma unroll 4
+        for (uint32_t k = 0; k < padded / 2; k++) {
+            const float4 q = pairs[k];
+            const uint32_t j = t0 + 2 * k;
+#pragma unroll
+            for (int e = 0; e < kIcpPPT; e++) {
+                const float dx = px[e] - q.x, dy = py[e] - q.y;
+                const float d2 = dx * dx + dy * dy;
+                if (d2 < best[e]) { best[e] = d2; bj[e] = j; }
+            }
+#pragma unroll
+            for (int e = 0; e < kIcpPPT; e++) {
+                const float dx = px[e] - q.z, dy = py[e] - q.w;
+                const float d2 = dx * dx + dy * dy;
+                if (d2 < best[e]) { best[e] = d2; bj[e] = j + 1; }
+            }
+        }
+    }
+
+    long long sum[S_COUNT];
+#pragma unroll
+    for (int k = 0; k < S_COUNT; k++) sum[k] = 0;
+#pragma unroll
+    for (int e = 0; e < kIcpPPT; e++) {
+        const uint32_t i = i0 + (uint32_t)e * kIcpTB + threadIdx.x;
+        if (i >= m) continue;
+        uint32_t j = kIcpNone;
+        if (in_range(px[e]) && in_range(py[e]) && bj[e] != kIcpNone && best[e] <= gate2) {
+            j = bj[e];
+            const long long Px = (int32_t)rintf(px[e] * 256.0f), Py = (int32_t)rintf(py[e] * 256.0f);
+            const long long Qx = (int32_t)rintf(tgt[j].x * 256.0f), Qy = (int32_t)rintf(tgt[j].y * 256.0f);
+            sum[S_N] += 1;
+            sum[S_PX] += Px; sum[S_PY] += Py; sum[S_QX] += Qx; sum[S_QY] += Qy;
+            sum[S_DOT] += Px * Qx + Py * Qy;
+            sum[S_CROSS] += Px * Qy - Py * Qx;
+            sum[S_SSE] += (Px - Qx) * (Px - Qx) + (Py - Qy) * (Py - Qy);
+        }
+        if (corr) corr[(size_t)f * max_points + i] = j;
+    }
+#pragma unroll
+    for (int k = 0; k < S_COUNT; k++)
+        for (int d = 32; d > 0; d >>= 1) sum[k] += __shfl_xor(sum[k], d, 64);
+    if ((threadIdx.x & 63) == 0 && sum[S_N] != 0) {
+#pragma unroll
+        for (int k = 0; k < S_COUNT; k++) atomicAdd(acc + (size_t)f * S_COUNT + k, (unsigned long long)sum[k]);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_icp_solve(rr_icp_rec* recs, long long* acc, int n_frames, int last)
+{
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n_frames) return;
+    long long S[S_COUNT];
+    for (int k = 0; k < S_COUNT; k++) { S[k] = acc[(size_t)f * S_COUNT + k]; acc[(size_t)f * S_COUNT + k] = 0; }
+    rr_icp_rec* r = recs + f;
+    if (last) {
+        r->sse = S[S_SSE];
+        r->n_matched = (uint32_t)S[S_N];
+        return;
+    }
+    const double N = (double)S[S_N], SPx = (double)S[S_PX], SPy = (double)S[S_PY], SQx = (double)S[S_QX], SQy = (double)S[S_QY];
+    const double Sdot = (double)S[S_DOT], Scross = (double)S[S_CROSS];
+    const double A = N * Sdot - (SPx * SQx + SPy * SQy);
+    const double B = N * Scross - (SPx * SQy - SPy * SQx);
+    const double h = sqrt(A * A + B * B);
+    if (S[S_N] < 2 || !(h > 0.0)) { r->flags |= RR_ICP_DEGENERATE; return; }
+    const double c = r->c, s = r->s, tx = r->tx, ty = r->ty;
+    const double dc = A / h, ds = B / h;
+    const double mpx = (SPx / N) / 256.0, mpy = (SPy / N) / 256.0, mqx = (SQx / N) / 256.0, mqy = (SQy / N) / 256.0;
+    const double dtx = mqx - (dc * mpx - ds * mpy);
+    const double dty = mqy - (ds * mpx + dc * mpy);
+    const double c1 = dc * c - ds * s;
+    const double s1 = ds * c + dc * s;
+    const double tx1 = (dc * tx - ds * ty) + dtx;
+    const double ty1 = (ds * tx + dc * ty) + dty;
+    const double nrm = sqrt(c1 * c1 + s1 * s1);
+    r->c = c1 / nrm; r->s = s1 / nrm; r->tx = tx1; r->ty = ty1;
+}
+
+}  // namespace
+
+void icp_tile_sizes(int* source_tile, int* target_tile)
+{
+    if (source_tile) *source_tile = kIcpSrcTile;
+    if (target_tile) *target_tile = kIcpTgtTile;
+}
+
+size_t icp_scratch_words(size_t n_frames) { return n_frames * S_COUNT; }
+
+void launch_icp(const rr_radar_point* points, const uint32_t* offsets, int n_frames, int n_angles, int max_points, const rr_radar_point* tgt,
+                const uint32_t* tgt_count, int max_tgt, const double* init, float gate, int iterations, rr_icp_rec* recs, uint32_t* corr,
+                long long* acc, hipStream_t s)
+{
+    const float gate2 = gate * gate;
+    const unsigned fgroups = (unsigned)((n_frames + 255) / 256);
+    const dim3 grid((unsigned)((max_points + kIcpSrcTile - 1) / kIcpSrcTile), (unsigned)n_frames);
+    unsigned long long* uacc = reinterpret_cast<unsigned long long*>(acc);
+    hipLaunchKernelGGL(k_icp_init, dim3(fgroups), dim3(256), 0, s, init, offsets, n_angles, max_points, tgt_count, max_tgt, recs, acc, n_frames);
+    for (int it = 0; it <= iterations; it++) {
+        const int last = it == iterations;
+        if (grid.x) hipLaunchKernelGGL(k_icp_pass, grid, dim3(kIcpTB), 0, s, points, offsets, n_angles, max_points, tgt, tgt_count, max_tgt,
+                                       (const rr_icp_rec*)recs, gate2, uacc, last ? corr : nullptr);
+        hipLaunchKernelGGL(k_icp_solve, dim3(fgroups), dim3(256), 0, s, recs, acc, n_frames, last);
+    }
+}
+
+}  // namespace rr

@@ -129,6 +129,20 @@ int check_cartesian_sweep(rr_ctx* c, const char* who, const void* imgs, int n_fr
     return 0;
 }
 
+// the refusals of rr_register_points_device / rr_register_points
+int check_icp(rr_ctx* c, const char* who, const void* points, const void* offsets, int n_frames, int max_points, const void* tgt, bool have_count,
+              int max_tgt, float gate, int iterations, const void* recs)
+{
+    const std::string w(who);
+    const bool sizes_ok = max_points >= 0 && max_points <= 65536 && max_tgt >= 0 && max_tgt <= 65536;
+    int rc = check_images(c, w, offsets && have_count && recs && (!sizes_ok || ((max_points == 0 || points) && (max_tgt == 0 || tgt))), "buffer",
+                          "n_frames", n_frames, 65535); if (rc) return rc;
+    if (!sizes_ok) return fail(c, -3, w + ": max_points and max_tgt must be 0..65536");
+    if (iterations < 0 || iterations > 64) return fail(c, -3, w + ": iterations must be 0..64");
+    if (!(std::isfinite(gate) && gate > 0.0f)) return fail(c, -3, w + ": gate must be finite and > 0");
+    return 0;
+}
+
 // the refusals the annotation calls share: a config (the plane shape) within the limits of the label planes and of the packed azimuth
 int check_planes(rr_ctx* c, const std::string& w, bool have_buffers, int n_frames, int n_max)
 {
@@ -834,6 +848,73 @@ int rr_polar_to_cartesian_sweep(rr_ctx* c, const uint8_t* imgs_u8, int n_frames,
     rc = rr_polar_to_cartesian_sweep_device(c, c->d_conv_in.p, n_frames, cfg, c->d_sweep_tab.p, iterations, c->d_conv_cart.p, c->stream); if (rc) return rc;
     RR_HIP(c, hipMemcpyAsync(cart_u8, c->d_conv_cart.p, n_out, hipMemcpyDeviceToHost, c->stream));
     RR_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- scan matching (rr_icp.hip) ----------------------------------------------------------------------------------------
+void rr_icp_tile_sizes(int* source_tile, int* target_tile) { icp_tile_sizes(source_tile, target_tile); }
+
+int rr_register_points_device(rr_ctx* c, const rr_radar_point* d_points, const uint32_t* d_offsets, int n_frames, int max_points,
+                              const rr_radar_point* d_tgt_points, const uint32_t* d_tgt_count, int max_tgt, const double* d_init, float gate,
+                              int iterations, rr_icp_rec* d_recs, uint32_t* d_corr, void* stream)
+{
+    int rc = check_icp(c, "rr_register_points_device", d_points, d_offsets, n_frames, max_points, d_tgt_points, d_tgt_count != nullptr, max_tgt, gate,
+                       iterations, d_recs); if (rc) return rc;
+    if ((uintptr_t)d_init % 8 != 0 || (uintptr_t)d_recs % 8 != 0) return fail(c, -3, "rr_register_points_device: d_init and d_recs must be 8-byte aligned");
+    RR_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = stream_of(c, stream);
+    long long* acc = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(c->icp_mu);
+        DevBuf<long long>& b = c->icp_acc[s];
+        RR_HIP(c, b.ensure(icp_scratch_words((size_t)n_frames)));
+        acc = b.p;
+    }
+    launch_icp(d_points, d_offsets, n_frames, c->cfg.n_angles, max_points, d_tgt_points, d_tgt_count, max_tgt, d_init, gate, iterations, d_recs, d_corr,
+               acc, s);
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_register_points(rr_ctx* c, const rr_radar_point* points, const uint32_t* offsets, int n_frames, int max_points, const rr_radar_point* tgt_points,
+                       uint32_t tgt_count, int max_tgt, const double* init, float gate, int iterations, rr_icp_rec* recs, uint32_t* corr)
+{
+    const std::string w("rr_register_points");
+    int rc = check_icp(c, w.c_str(), points, offsets, n_frames, max_points, tgt_points, true, max_tgt, gate, iterations, recs); if (rc) return rc;
+    const size_t n = (size_t)n_frames, A = (size_t)c->cfg.n_angles, mp = (size_t)max_points, mt = (size_t)max_tgt, n_offs = n * (A + 1);
+    for (size_t f = 0; init && f < n; f++) {
+        const double h = std::sqrt(init[4 * f] * init[4 * f] + init[4 * f + 1] * init[4 * f + 1]);
+        if (!(h > 0.0 && std::isfinite(h))) return fail(c, -3, w + ": an initial state whose (c, s) has a zero or non-finite length");
+    }
+    RR_HIP(c, hipSetDevice(c->device));
+    RR_HIP(c, hipStreamSynchronize(c->stream));        // the staging buffers may be reallocated
+    RR_HIP(c, c->d_icp_points.ensure(n * mp + mt));
+    RR_HIP(c, c->d_icp_words.ensure(n_offs + 1 + n * mp));
+    RR_HIP(c, c->d_icp_init.ensure(n * 4));
+    RR_HIP(c, c->d_icp_rec.ensure(n));
+    rr_radar_point* d_src = c->d_icp_points.p;
+    rr_radar_point* d_tgt = d_src + n * mp;
+    uint32_t* d_offs = c->d_icp_words.p;
+    uint32_t* d_count = d_offs + n_offs;
+    uint32_t* d_corr = d_count + 1;
+    auto count = [&](size_t f) { return std::min<size_t>(offsets[f * (A + 1) + A], mp); };
+    const size_t n_tgt = std::min<size_t>(tgt_count, mt);
+    RR_HIP(c, hipMemcpyAsync(d_offs, offsets, n_offs * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    RR_HIP(c, hipMemcpyAsync(d_count, &tgt_count, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    for (size_t f = 0; f < n; f++)
+        if (count(f)) RR_HIP(c, hipMemcpyAsync(d_src + f * mp, points + f * mp, count(f) * sizeof(rr_radar_point), hipMemcpyHostToDevice, c->stream));
+    if (n_tgt) RR_HIP(c, hipMemcpyAsync(d_tgt, tgt_points, n_tgt * sizeof(rr_radar_point), hipMemcpyHostToDevice, c->stream));
+    if (init) RR_HIP(c, hipMemcpyAsync(c->d_icp_init.p, init, n * 4 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    RR_HIP(c, hipStreamSynchronize(c->stream));        // (tgt_count is this call's own variable)
+    rc = rr_register_points_device(c, d_src, d_offs, n_frames, max_points, d_tgt, d_count, max_tgt, init ? c->d_icp_init.p : nullptr, gate, iterations,
+                                   c->d_icp_rec.p, corr ? d_corr : nullptr, c->stream); if (rc) return rc;
+    std::vector<uint32_t> got(corr ? n * mp : 0);        // the caller's buffers are written once everything has arrived
+    for (size_t f = 0; corr && f < n; f++)
+        if (count(f)) RR_HIP(c, hipMemcpyAsync(got.data() + f * mp, d_corr + f * mp, count(f) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    std::vector<rr_icp_rec> rec(n);
+    rc = records_back(c, rec.data(), c->d_icp_rec.p, n * sizeof(rr_icp_rec), c->stream); if (rc) return rc;
+    std::copy(rec.begin(), rec.end(), recs);
+    for (size_t f = 0; corr && f < n; f++) std::copy(got.begin() + f * mp, got.begin() + f * mp + count(f), corr + f * mp);
     return 0;
 }
 

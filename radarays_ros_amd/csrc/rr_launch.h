@@ -1,4 +1,4 @@
-// rr_launch.h -- every launcher of rr_kernels.hip, rr_labels.hip, rr_paths.hip, rr_doppler.hip, rr_refit.hip, rr_detect.hip, rr_deskew.hip, rr_notes.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip, rr_place.hip and rr_lbvh.hip, declared ONCE: included where they
+// rr_launch.h -- every launcher of rr_kernels.hip, rr_labels.hip, rr_paths.hip, rr_doppler.hip, rr_refit.hip, rr_detect.hip, rr_deskew.hip, rr_icp.hip, rr_notes.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip, rr_place.hip and rr_lbvh.hip, declared ONCE: included where they
 // are defined (a definition that drifts from its declaration fails there) and where they are called.  Default arguments live here only.
 #pragma once
 #include "../../include/radarays_mi355.h"
@@ -74,6 +74,12 @@ void launch_compensate_points(const rr_radar_point* points, const uint32_t* offs
                               rr_radar_point* out, int n_angles, int scroll, double resolution, hipStream_t s);
 void launch_cartesian_sweep(const uint8_t* imgs, int n_frames, const rr_cartesian_config& cfg, int n_cells, int n_angles, int scroll, float theta_min,
                             float theta_inc, float res, const rr_sweep_rec* table, int iterations, uint8_t* out, hipStream_t s);
+// rr_icp.hip (scan matching).  acc: icp_scratch_words(n_frames) int64 words, zeroed by the first launch; recs and init 8-byte aligned
+void icp_tile_sizes(int* source_tile, int* target_tile);
+size_t icp_scratch_words(size_t n_frames);
+void launch_icp(const rr_radar_point* points, const uint32_t* offsets, int n_frames, int n_angles, int max_points, const rr_radar_point* tgt,
+                const uint32_t* tgt_count, int max_tgt, const double* init, float gate, int iterations, rr_icp_rec* recs, uint32_t* corr,
+                long long* acc, hipStream_t s);
 // rr_notes.hip (object annotations).  scratch: note_scratch_bytes, 16-byte aligned like notes; every word of it, of notes and of skipped is written by the launches
 size_t note_scratch_bytes(size_t n_frames, size_t n_objects, int n_angles);
 void launch_notes(const uint32_t* labels, const uint8_t* imgs, int n_frames, uint32_t n_objects, uint32_t extent_mask, int n_cells, int n_angles,

@@ -42,6 +42,7 @@ SYMBOLS = [
     "rr_polar_to_cartesian_labels_device", "rr_polar_to_cartesian_labels", "rr_simulate_batch_annotations",
     "rr_sweep_table_device", "rr_sweep_table", "rr_compensate_points_device", "rr_compensate_points",
     "rr_polar_to_cartesian_sweep_device", "rr_polar_to_cartesian_sweep",
+    "rr_register_points_device", "rr_register_points", "rr_icp_tile_sizes",
 ]
 
 
@@ -170,6 +171,58 @@ def identity_sweep_table(n_frames, n_angles):
     t = np.zeros((int(n_frames), int(n_angles)), SWEEP_DTYPE)
     t["q"][..., 3] = 1.0
     return t
+
+
+# rr_icp_rec as numpy sees it (48 B): the state (c, s, tx, ty) that maps a source point into the target's frame, and the last pass's score
+ICP_DTYPE = np.dtype([("c", "<f8"), ("s", "<f8"), ("tx", "<f8"), ("ty", "<f8"), ("sse", "<i8"), ("n_matched", "<u4"), ("flags", "<u4")])
+ICP_DEGENERATE, ICP_TRUNCATED = 1, 2
+ICP_NONE = 0xFFFFFFFF              # an unmatched point in the correspondences
+ICP_MAX_POINTS = 65536
+
+
+class RRIcpRec(C.Structure):
+    _fields_ = [("c", C.c_double), ("s", C.c_double), ("tx", C.c_double), ("ty", C.c_double), ("sse", C.c_int64), ("n_matched", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+def se2_states(yaw, tx=0.0, ty=0.0):
+    """planar transforms as rr_register_points takes them: float64 [n][4] = (cos yaw, sin yaw, tx, ty); scalars or arrays that broadcast"""
+    yaw, tx, ty = np.broadcast_arrays(np.atleast_1d(np.asarray(yaw, np.float64)), np.asarray(tx, np.float64), np.asarray(ty, np.float64))
+    return np.ascontiguousarray(np.stack([np.cos(yaw), np.sin(yaw), tx, ty], axis=1))
+
+
+def icp_tile_sizes():
+    """(source points per workgroup, target points per LDS tile) of k_icp_pass"""
+    a, b = C.c_int(0), C.c_int(0)
+    lib().rr_icp_tile_sizes(C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
+def _icp_gate(gate):
+    """the gate as the library takes it (f32): finite and positive, also after rounding"""
+    try:
+        g = float(gate)
+    except (TypeError, ValueError):
+        raise ValueError("gate must be a number, got %r" % (gate,))
+    with np.errstate(over="ignore"):
+        g32 = np.float32(g)
+    if isinstance(gate, bool) or not (np.isfinite(g32) and g32 > 0):
+        raise ValueError("gate must be finite and > 0 as a float32, got %r" % (gate,))
+    return float(g32)
+
+
+def _icp_init(init, n):
+    """None or float64 [n][4] with a finite non-zero (c, s) in every row"""
+    if init is None:
+        return None
+    x = np.asarray(init)
+    if x.dtype.kind not in "fiu" or x.shape != (n, 4):
+        raise ValueError("init must be real numbers of shape [%d][4] (c, s, tx, ty), got %s %s" % (n, x.dtype, x.shape))
+    x = np.ascontiguousarray(x, np.float64)
+    h = np.sqrt(x[:, 0] * x[:, 0] + x[:, 1] * x[:, 1])
+    if not np.all(np.isfinite(h) & (h > 0)):
+        raise ValueError("every initial state needs a finite, non-zero (c, s)")
+    return x
 
 
 # rr_default_detect_config
@@ -459,6 +512,10 @@ def lib():
     L.rr_compensate_points.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp]
     L.rr_polar_to_cartesian_sweep_device.argtypes = [vp, vp, C.c_int, C.POINTER(RRCartesianConfig), vp, C.c_int, vp, vp]
     L.rr_polar_to_cartesian_sweep.argtypes = [vp, vp, C.c_int, C.POINTER(RRCartesianConfig), vp, C.c_int, vp]
+    L.rr_register_points_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_float, C.c_int, vp, vp, vp]
+    L.rr_register_points.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_uint32, C.c_int, vp, C.c_float, C.c_int, vp, vp]
+    L.rr_icp_tile_sizes.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.rr_icp_tile_sizes.restype = None
     for n in SYMBOLS:
         getattr(L, n)
     _LIB = L
@@ -1302,6 +1359,63 @@ class Context:
         out = np.zeros((len(x), c.width, c.width), np.uint8)
         self._ck(self._L.rr_polar_to_cartesian_sweep(self._h, x.ctypes.data, len(x), C.byref(c), t.ctypes.data, it, out.ctypes.data))
         return out
+
+    # ---- scan matching (rr_icp.hip): planar point-to-point ICP of n clouds against one; any context with a config, mesh or not
+    def register_points_device(self, d_points_ptr, d_offsets_ptr, n_frames, max_points, d_tgt_points_ptr, d_tgt_count_ptr, max_tgt, d_recs_ptr,
+                               d_init_ptr=None, gate=1.0, iterations=10, d_corr_ptr=None, stream=None):
+        """rr_register_points_device: ICP_DTYPE records [n_frames] in HBM from the points [n_frames][max_points] and offsets
+        [n_frames][n_angles + 1] rr_detect_device wrote, against the target points [max_tgt] whose count is the uint32 at d_tgt_count_ptr;
+        d_init_ptr: float64 [n_frames][4] or None (identity); d_corr_ptr: uint32 [n_frames][max_points] or None; on `stream`"""
+        self._polar_shape()
+        n = _frames_arg(n_frames)
+        mp, mt = _int_in(max_points, 0, ICP_MAX_POINTS, "max_points"), _int_in(max_tgt, 0, ICP_MAX_POINTS, "max_tgt")
+        it, g = _int_in(iterations, 0, 64, "iterations"), _icp_gate(gate)
+        if not d_offsets_ptr or not d_tgt_count_ptr or not d_recs_ptr or (mp > 0 and not d_points_ptr) or (mt > 0 and not d_tgt_points_ptr):
+            raise ValueError("register_points_device needs point, offset, target, target count and record buffers")
+        self._ck(self._L.rr_register_points_device(self._h, d_points_ptr, d_offsets_ptr, n, mp, d_tgt_points_ptr, d_tgt_count_ptr, mt, d_init_ptr,
+                                                   g, it, d_recs_ptr, d_corr_ptr, stream))
+
+    def register_points(self, points_list, offsets, target_points, init=None, gate=1.0, iterations=10, want_corr=False):
+        """rr_register_points on what detect() (or compensate_points()) returned: a list of n POINT_DTYPE arrays and offsets uint32
+        [n][n_angles + 1], against ONE target POINT_DTYPE array.  init: float64 [n][4] = (c, s, tx, ty) per cloud (se2_states makes it) or
+        None for the identity; gate in metres; iterations 0..64 (0 scores the initial states).  Returns ICP_DTYPE [n]: the transform that
+        maps each cloud into the target's frame, sse, n_matched and flags; with want_corr also a list of n uint32 arrays: the target index
+        each point was matched to in the last pass, ICP_NONE for an unmatched point."""
+        _, n_angles = self._polar_shape()
+        if isinstance(points_list, np.ndarray) and points_list.ndim == 1:
+            points_list = [points_list]
+        pts = [np.asarray(p) for p in points_list]
+        if not pts or len(pts) > 65535 or any(p.dtype != POINT_DTYPE or p.ndim != 1 for p in pts):
+            raise ValueError("points must be a list of 1..65535 one-dimensional POINT_DTYPE arrays")
+        n = len(pts)
+        tgt = np.asarray(target_points)
+        if tgt.dtype != POINT_DTYPE or tgt.ndim != 1:
+            raise ValueError("the target must be a one-dimensional POINT_DTYPE array")
+        if len(tgt) > ICP_MAX_POINTS or any(len(p) > ICP_MAX_POINTS for p in pts):
+            raise ValueError("a cloud may hold at most %d points" % ICP_MAX_POINTS)
+        offs = np.asarray(offsets)
+        if offs.ndim == 1:
+            offs = offs[None]
+        if offs.dtype != np.uint32 or offs.shape != (n, n_angles + 1):
+            raise ValueError("offsets must be uint32 [%d][%d], got %s %s" % (n, n_angles + 1, offs.dtype, offs.shape))
+        offs = np.ascontiguousarray(offs)
+        mp = max(1, max(len(p) for p in pts))
+        if any(len(p) != min(int(offs[f, -1]), mp) for f, p in enumerate(pts)):
+            raise ValueError("every frame must hold the points its offsets count")
+        x0 = _icp_init(init, n)
+        it, g = _int_in(iterations, 0, 64, "iterations"), _icp_gate(gate)
+        tgt = np.ascontiguousarray(tgt)
+        buf = np.zeros((n, mp), POINT_DTYPE)
+        for f, p in enumerate(pts):
+            buf[f, :len(p)] = p
+        recs = np.zeros(n, ICP_DTYPE)
+        corr = np.full((n, mp), ICP_NONE, np.uint32) if want_corr else None
+        self._ck(self._L.rr_register_points(self._h, buf.ctypes.data, offs.ctypes.data, n, mp, tgt.ctypes.data if len(tgt) else None, len(tgt),
+                                            len(tgt), None if x0 is None else x0.ctypes.data, g, it, recs.ctypes.data,
+                                            corr.ctypes.data if want_corr else None))
+        if want_corr:
+            return recs, [corr[f, :len(p)].copy() for f, p in enumerate(pts)]
+        return recs
 
     # ---- object annotations (rr_notes.hip): one record per object from label images; any context with a config, mesh or not
     def _label_planes(self, planes, what="label planes"):

@@ -351,6 +351,75 @@ class RadarHIP:
             out.append(chunk.astype(np.float32)); yaw_recs.append(yaw); shift_recs.append(sh)
         return np.concatenate(out), np.concatenate(yaw_recs), np.concatenate(shift_recs)
 
+    # ---- scan matching (rr_icp.hip): the planar pose from point clouds, both angles and both translations in one step
+    def registerPointClouds(self, poses, real_points, detect=None, gate=1.0, iterations=10, compensate=None):
+        """[n][7] pose hypotheses (qx qy qz qw tx ty tz) of a planar sensor against ONE real point cloud (POINT_DTYPE, e.g. toPointCloud
+        of a real scan, at most 65,536 points) -> (native.ICP_DTYPE records [n], corrected poses float32 [n][7]).
+        Per 64 poses: rr_simulate_batch_device, rr_detect_device (detect: a dict of rr_detect_config fields, None: the defaults; room for
+        k * 400 points with k-strongest, for what a count-only pass finds with CA-CFAR, 65,536 at most) and rr_register_points_device on
+        one stream from the identity guess; compensate: a native.SWEEP_DTYPE table [400] that rr_compensate_points_device applies to every
+        simulated cloud first, or None.  Only the records come to the host.
+        Convention: the source is the cloud simulated at the hypothesis X_h, the target the real cloud taken at the true pose X, both in
+        their sensor's frame.  A record's (c, s, tx, ty) is T with q ~ T p, so T = X^-1 X_h and the corrected pose is X_h T^-1: the
+        hypothesis turned by -atan2(s, c) about its own z axis and moved by -R^T t in its own axes (forward, left)."""
+        import torch
+        self._push()
+        n_cells = self.m_cfg.n_cells
+        det = native.detect_config(detect, n_cells=n_cells)
+        p = native.object_poses_array(poses)
+        tgt = np.ascontiguousarray(real_points)
+        if tgt.dtype != native.POINT_DTYPE or tgt.ndim != 1 or not 1 <= len(tgt) <= native.ICP_MAX_POINTS:
+            raise ValueError("real_points must be a one-dimensional POINT_DTYPE array of 1..%d points" % native.ICP_MAX_POINTS)
+        it, g = native._int_in(iterations, 0, 64, "iterations"), native._icp_gate(gate)
+        table = None if compensate is None else self._ctx._sweep_records(compensate, 1)
+        dev = torch.device("cuda", self._ctx.device)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)   # noqa: E731
+        recs = []
+        stream = torch.cuda.Stream(device=dev)      # an explicit stream, as simulatePointClouds
+        s = stream.cuda_stream
+        with torch.cuda.device(dev), torch.cuda.stream(stream):
+            d_tgt, d_cnt = up(tgt), up(np.array([len(tgt)], np.uint32))
+            for at in range(0, len(p), 64):
+                chunk = p[at:at + 64]
+                n = len(chunk)
+                imgs = torch.empty((n, n_cells, N_ANGLES), dtype=torch.uint8, device=dev)
+                offs = torch.empty((n, N_ANGLES + 1), dtype=torch.int32, device=dev)
+                self._ctx.simulate_batch_device(chunk, imgs.data_ptr(), s)
+                if det.method == 1:
+                    mp = det.k * N_ANGLES
+                else:
+                    self._ctx.detect_device(imgs.data_ptr(), n, det, None, 0, offs.data_ptr(), s)     # counts
+                    mp = int(offs[:, -1].max().item())
+                mp = max(1, min(mp, native.ICP_MAX_POINTS))
+                pts = torch.empty((n, mp * native.POINT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+                d_rec = torch.empty(n * native.ICP_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+                self._ctx.detect_device(imgs.data_ptr(), n, det, pts.data_ptr(), mp, offs.data_ptr(), s)
+                if table is not None:
+                    d_tab = up(np.tile(table, (n, 1)))
+                    self._ctx.compensate_points_device(pts.data_ptr(), offs.data_ptr(), n, mp, d_tab.data_ptr(), None, s)
+                self._ctx.register_points_device(pts.data_ptr(), offs.data_ptr(), n, mp, d_tgt.data_ptr(), d_cnt.data_ptr(), len(tgt),
+                                                 d_rec.data_ptr(), None, g, it, None, s)
+                recs.append(d_rec.cpu().numpy().view(native.ICP_DTYPE).copy())
+        self._ctx.synchronize(s)
+        rec = np.concatenate(recs) if recs else np.zeros(0, native.ICP_DTYPE)
+        return rec, self._corrected_by(p, rec)
+
+    @staticmethod
+    def _corrected_by(poses, rec):
+        """X_h T^-1 for every hypothesis and its record (registerPointClouds says why)"""
+        out = poses.astype(np.float64)
+        c, s, tx, ty = rec["c"], rec["s"], rec["tx"], rec["ty"]
+        v = np.stack([-(c * tx + s * ty), -(-s * tx + c * ty), np.zeros(len(rec))], axis=1)      # -R^T t, in the hypothesis' own axes
+        u, w = out[:, :3].copy(), out[:, 3:4].copy()
+        uv = np.cross(u, v)
+        out[:, 4:7] += v + 2.0 * (w * uv + np.cross(u, uv))           # ... turned into the map frame
+        half = -0.5 * np.arctan2(s, c)
+        bz, bw = np.sin(half), np.cos(half)                           # q * (0, 0, bz, bw): a turn in the sensor's own frame
+        ax, ay, az, aw = u[:, 0], u[:, 1], u[:, 2], w[:, 0]
+        out[:, 0], out[:, 1] = ax * bw + ay * bz, ay * bw - ax * bz
+        out[:, 2], out[:, 3] = aw * bz + az * bw, aw * bw - az * bz
+        return out.astype(np.float32)
+
     # ---- place recognition (rr_place.hip): a database of yaw-invariant ring/sector descriptors, and a scan looked up in it
     def buildPlaceDatabase(self, poses, place_cfg, on_device=False):
         """any number of [n][7] poses, worked through 64 at a time -> their descriptors uint8 [n][R][S] (native.Context._place_cfg
