@@ -172,6 +172,18 @@ __device__ inline Hit traverse(const float4* __restrict__ base4, const uint32_t 
         const float4 A = p[0], B = p[1];
         float4 C = make_float4(0.f, 0.f, 0.f, 0.f);
         if (leaf) C = p[2];          // triangle arrays are padded: q >= cnt reads stay in bounds
+        // CULL: the pop candidate, read beside the step's loads.  A pop follows a leaf step or a node step without a hit
+        // child, neither pushes, so the first entry it takes is the one at sp - 1 NOW (pushes of this step go to sp and
+        // above): its LDS round trip ends under the wait of the global loads, not between this step and the next address
+        // ("The pop candidate").  Plain loads: the pushes below may alias them, so they are not sunk to the
+        // pop; their lgkmcnt falls there.  No stack yet: entry 0 is read (in bounds, unused).  An entry that lives in the
+        // spill buffer is not prefetched.  Pass 0 (!CULL) pops as before: its coherent waves pop in few iterations and
+        // their loads hit the L1, the read in every iteration cost it 6 % per launch
+        uint32_t pcur = 0, pk = 0;
+        if (CULL && (!SPILL || sp <= stack_lds)) {
+            const int pe = max(sp - 1, 0) * kRaysPerWave;
+            pcur = my[pe]; pk = myk[pe];
+        }
         if (!leaf) {
             // child record: A = (lo.x lo.y lo.z hi.x)  B = (hi.y hi.z ref pad)
             if (STATS) { n_nodes += (q == 0); }
@@ -227,13 +239,21 @@ __device__ inline Hit traverse(const float4* __restrict__ base4, const uint32_t 
             // would fail for every child (their entry distances are not below the parent's)
             const uint32_t ck = __float_as_uint(tcull) >> 16;
             bool more = false;
-            while (sp > 0) {
+            if (sp > 0) {
+                // first candidate: the prefetched pair (registers); only if it is culled does the walk go on in LDS, from sp - 2 down
+                sp--;
+                uint32_t k = pk;
+                if (SPILL && sp >= stack_lds) { cur = spill[(size_t)(sp - stack_lds) * spill_stride + gray]; k = 0; }
+                else cur = pcur;
+                more = k <= ck;
+            }
+            while (!more && sp > 0) {
                 sp--;
                 uint32_t k = 0;
                 if (SPILL && sp >= stack_lds) cur = spill[(size_t)(sp - stack_lds) * spill_stride + gray];
                 else { cur = my[sp * kRaysPerWave]; k = myk[sp * kRaysPerWave]; }
                 asm volatile("" : "+v"(cur), "+v"(k));      // both reads in ONE LDS round trip (the reference is not fetched after the test)
-                if (k <= ck) { more = true; break; }
+                more = k <= ck;
             }
             if (!more) break;
         }
