@@ -1,5 +1,5 @@
 // rr_api.hip -- C ABI of libradarays_mi355.so (include/radarays_mi355.h): the context's life, its parameter tables and their upload, synchronisation and errors,
-// page-locked memory; the rest is rr_scene.hip, rr_frame.hip, rr_sets.hip, rr_images.hip, rr_probe.hip.  No CPU fallback: a compute call runs the gfx950 kernels or fails with an error string.
+// page-locked memory; the rest is rr_scene.hip, rr_frame.hip, rr_side.hip, rr_sets.hip, rr_images.hip, rr_probe.hip.  No CPU fallback: a compute call runs the gfx950 kernels or fails with an error string.
 #include "rr_ctx.h"
 #include <algorithm>
 #include <cmath>

@@ -1,4 +1,4 @@
-// rr_ctx.h -- the context as the library's host files share it (rr_api.hip, rr_scene.hip, rr_frame.hip, rr_sets.hip, rr_images.hip, rr_probe.hip): rr_ctx and its
+// rr_ctx.h -- the context as the library's host files share it (rr_api.hip, rr_scene.hip, rr_frame.hip, rr_side.hip, rr_sets.hip, rr_images.hip, rr_probe.hip): rr_ctx and its
 // lanes, the error / timing / roctx helpers, the helpers that cross a file boundary.  Nothing here is public: the interface is include/radarays_mi355.h.
 #pragma once
 #include "rr_devbuf.h"
@@ -301,6 +301,21 @@ struct SetPlan {
     const float4* d_beams = nullptr; const uint32_t* d_order = nullptr; const uint32_t* d_order2 = nullptr;   // [n_groups][n_beam]; null: the ctx's tables
 };
 
+// what a call wants of run_frame beyond pose, azimuth block and stream
+struct FrameJob {
+    int n_frames = 1;
+    uint8_t* d_cols_u8 = nullptr;        // the caller's column buffer; null: the lane's own
+    float* d_cols_f32 = nullptr;         // ... and its f32 columns, or with lane_f32 the lane's own; neither: none
+    bool lane_f32 = false;
+    const float4* d_matsets = nullptr;   // a parameter batch: one material table per frame [n_frames][mat_stride], its plan (null: material
+    int mat_stride = 0;                  // sets only: the context's beams, every frame the config's passes)
+    const SetPlan* plan = nullptr;
+    int provenance = 0;                  // 1: the lane's echo lists are gathered; 2: and its label columns made
+    const WaveOut* paths = nullptr;      // the wave records of every pass go to these rows (state: the lane's, filled in by run_frame)
+    const DopArgs* doppler = nullptr;    // gain and the caller's rows: a provenance chain whose image comes from the shifted list (the lane's buffers are filled in by run_frame)
+    const float* sensor_vel = nullptr;   // ... and its sensor velocities [n_frames][3], or null: 0
+};
+
 // rr_api.hip
 int check_ready(rr_ctx* c);
 int upload_tables(rr_ctx* c);
@@ -329,12 +344,10 @@ bool host_visible(const void* p);
 int settle_lane(rr_ctx* c, Lane& L, int slot = -1, const void* only_dst = nullptr);
 int take_lane(rr_ctx* c, size_t li, hipStream_t s, int slot = -1);
 hipError_t give_lane(Lane& L, hipStream_t s);
-int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, uint8_t* d_cols_u8 /* null: the lane's own buffer */, float* d_cols_f32,
-              hipStream_t s, int n_frames = 1, const float4* d_matsets = nullptr, int mat_stride = 0, bool lane_f32 = false, const SetPlan* plan = nullptr,
-              int provenance = 0 /* 1: the lane's echo lists are gathered; 2: and its label columns made */,
-              const WaveOut* paths = nullptr /* the wave records of every pass go to these rows (state: the lane's, filled in here) */,
-              const DopArgs* doppler = nullptr /* gain and the caller's rows; a provenance chain whose image comes from the shifted list (the lane's buffers are filled in here) */,
-              const float* sensor_vel = nullptr /* [n_frames][3] with doppler, or null: 0 */);
+int ensure_prov_buffers(rr_ctx* c, Lane& L);
+// The launch chain of a batch on lane L, enqueued on s: `pose` [job.n_frames][7] (a parameter batch: one pose), azimuths [az_begin, az_end)
+// of every frame.  A plain call leaves the job empty: one frame into the lane's own columns
+int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, hipStream_t s, const FrameJob& job = {});
 int assemble_frames(rr_ctx* c, const Lane& L, uint8_t* dst, int n_frames, hipStream_t s);
 
 }  // namespace rr

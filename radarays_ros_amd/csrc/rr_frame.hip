@@ -1,5 +1,6 @@
 // rr_frame.hip -- a frame on a lane: the lane's buffers and its hand-over, run_frame (the launch chain of a batch and its launch-graph
-// cache), the rr_simulate*_device / rr_assemble_*_device entry points, the synchronous rr_simulate, the delivery of images to host memory.
+// cache), the plain rr_simulate*_device / rr_assemble_*_device entry points, the synchronous rr_simulate, the delivery of images to host
+// memory.  The entry points of the side chains (provenance, wave paths, Doppler) are in rr_side.hip.
 #include "rr_ctx.h"
 #include "rr_hostprof.h"
 #include <algorithm>
@@ -146,30 +147,6 @@ void fill_params(rr_ctx* c, Lane& L, Params& P, const float pose[7], int az_begi
     P.hist_host = (c->tight_grid && g.n_reflections > 1) ? L.h_hist : nullptr;              // the chain's k_column stores the history there (read without a fence by later batches)
 }
 
-// The lane's provenance buffers for its current frame buffers (after prepare_lane).  A segment's list holds at most the lane's signal
-// capacity (every pass' wave bound, twice that with record_multi_path) -- the list k_column reads -- plus the last pass' slot bound
-int ensure_prov_buffers(rr_ctx* c, Lane& L)
-{
-    const rr_config g = eff_config(c);
-    const int n_beam = (int)(c->beams.size() / 3);
-    const int last = std::max(0, g.n_reflections - 1);
-    const long last_bound = std::min<long>((long)L.buf_cap, last < 20 ? (long)n_beam << last : (long)L.buf_cap);
-    const int echo_cap = L.buf_sigcap + (int)last_bound * (g.record_multi_path ? 2 : 1);
-    if (L.d_prov.p && L.prov_seg >= L.buf_seg && L.prov_cap == echo_cap && L.prov_cells == L.buf_cells) return 0;
-    const size_t S = (size_t)L.buf_seg;
-    size_t free_b = 0, total_b = 0;
-    RR_HIP(c, hipMemGetInfo(&free_b, &total_b));
-    if (S * ((size_t)echo_cap * sizeof(EchoSrc) + (size_t)L.buf_cells * 8) > total_b / 2)
-        return fail(c, -6, "the echo lists of a provenance call need more than half of device memory; fewer frames per call or a lower max_waves_per_azimuth");
-    RR_HIP(c, hipDeviceSynchronize());      // a provenance chain in flight may still use the old buffers
-    RR_HIP(c, L.d_prov.ensure(S * (size_t)echo_cap));
-    RR_HIP(c, L.d_prov_count.ensure(S));
-    RR_HIP(c, L.d_label_cols.ensure(S * (size_t)L.buf_cells));
-    RR_HIP(c, L.d_face_cols.ensure(S * (size_t)L.buf_cells));
-    L.prov_seg = L.buf_seg; L.prov_cap = echo_cap; L.prov_cells = L.buf_cells;
-    return 0;
-}
-
 // The lane's running state of a paths chain for its current frame buffers (after prepare_lane): 16 bytes per segment
 int ensure_path_state(rr_ctx* c, Lane& L)
 {
@@ -277,10 +254,13 @@ int choose_trace_rows(rr_ctx* c, Lane& L, Params& P, const rr_config& g, hipStre
     return 0;
 }
 
+// what a side chain adds to the launch chain, filled in by run_frame: the wave rows; the Doppler arguments and Q as the list-only column launch reads it
+struct ChainSide { const WaveOut* wo = nullptr; const DopArgs* da = nullptr; const Params* Qlist = nullptr; };
+
 // the launch chain of the batch
-int issue_chain(rr_ctx* c, const Params& Q, const PoseArgs& pa, const rr_config& g, hipStream_t s, const WaveOut* wo = nullptr,
-                const DopArgs* da = nullptr, const Params* Qlist = nullptr /* with da: Q as the list-only column launch reads the shifted list */)
+int issue_chain(rr_ctx* c, const Params& Q, const PoseArgs& pa, const rr_config& g, hipStream_t s, const ChainSide& side = {})
 {
+    const WaveOut* wo = side.wo; const DopArgs* da = side.da;
     for (int pass = 0; pass < g.n_reflections; pass++) {
         if (c->roctx) roctx_push(pass == 0 ? "trace pass 0" : "trace");
         if (c->timing) {
@@ -313,7 +293,7 @@ int issue_chain(rr_ctx* c, const Params& Q, const PoseArgs& pa, const rr_config&
     }
     if (da) {       // Doppler: the lane's echo lists -> the shifted list, which the column step replays as a list-only stream (rr_debug_column's form)
         { KernelEvents t(c, "shift"); launch_doppler_shift(Q, *da, s, t.a, t.b); }
-        { KernelEvents t(c, "column"); launch_column(*Qlist, s, t.a, t.b); }
+        { KernelEvents t(c, "column"); launch_column(*side.Qlist, s, t.a, t.b); }
         if (da->vel_cols) { KernelEvents t(c, "winner"); launch_vel_winner(Q, *da, s, t.a, t.b); }
     }
     return 0;
@@ -399,7 +379,8 @@ int replay_graph(rr_ctx* c, Lane::FrameGraph* fg, const PoseArgs& pa, hipStream_
 // a pose batch rendered on lane L and assembled into dst (rr_simulate_batch_device, rr_simulate_batch_host_async)
 int render_batch(rr_ctx* c, Lane& L, const float* poses, int n_frames, uint8_t* dst, hipStream_t s)
 {
-    const int rc = run_frame(c, L, poses, 0, c->cfg.n_angles, nullptr, nullptr, s, n_frames); if (rc) return rc;
+    FrameJob job; job.n_frames = n_frames;
+    const int rc = run_frame(c, L, poses, 0, c->cfg.n_angles, s, job); if (rc) return rc;
     return assemble_frames(c, L, dst, n_frames, s);
 }
 
@@ -413,11 +394,12 @@ int simulate_columns(rr_ctx* c, const float* poses, int n_frames, int az_begin, 
     hipStream_t s = stream_of(c, stream);
     const size_t li = c->next_lane++ % c->lanes.size();
     Lane& L = c->lanes[li];
+    FrameJob job; job.n_frames = n_frames; job.d_cols_u8 = d_cols_u8; job.d_cols_f32 = d_cols_f32;
     int rc;
     { HostProfScope hp(0, "ctx: wait for the lane's event");
       rc = take_lane(c, li, s); if (rc) return rc; }
     { HostProfScope hp(1, "ctx: run_frame");
-      rc = run_frame(c, L, poses, az_begin, az_end, d_cols_u8, d_cols_f32, s, n_frames); if (rc) return rc; }
+      rc = run_frame(c, L, poses, az_begin, az_end, s, job); if (rc) return rc; }
     { HostProfScope hp(2, "ctx: record the lane's event");
       RR_HIP(c, give_lane(L, s)); }
     return 0;
@@ -439,120 +421,36 @@ int assemble_device(rr_ctx* c, const char* who, bool blocks, const uint8_t* d_co
     return 0;
 }
 
-// the refusals of the two provenance entry points (nothing is written)
-int check_provenance(rr_ctx* c, const char* who, const void* poses, int n_frames, const void* imgs, const void* echoes, size_t echo_stride,
-                     const void* counts)
-{
-    int rc = check_ready(c); if (rc) return rc;
-    const std::string w(who);
-    if (!poses || !imgs) return fail(c, -3, w + ": null poses/output");
-    if (n_frames < 1 || n_frames > RR_MAX_BATCH) return fail(c, -3, w + ": n_frames must be 1..64");
-    if (echoes && !counts) return fail(c, -3, w + ": an echo buffer needs a count buffer");
-    if (echoes && echo_stride == 0) return fail(c, -3, w + ": echo_stride must be positive");
-    if (c->cfg.n_cells > kLabelMaxCells) return fail(c, -3, w + ": n_cells exceeds RR_LABEL_MAX_CELLS (8192)");
-    if (c->n_objects >= 0xFFFFFFu) return fail(c, -3, w + ": the info word holds object ids below 2^24 - 1");
-    if (c->cfg.n_reflections > 16) return fail(c, -3, w + ": the info word holds passes below 16 (n_reflections <= 16)");
-    return 0;
-}
-
-// a pose batch with provenance on lane li (taken and handed back here), everything enqueued on s
-int provenance_batch(rr_ctx* c, size_t li, const float* poses, int n_frames, uint8_t* d_imgs_u8, uint32_t* d_labels, uint32_t* d_faces,
-                     rr_echo_src* d_echoes, size_t echo_stride, uint32_t* d_echo_counts, hipStream_t s)
-{
-    Lane& L = c->lanes[li];
-    const rr_config& g = c->cfg;
-    int rc = take_lane(c, li, s); if (rc) return rc;
-    rc = run_frame(c, L, poses, 0, g.n_angles, nullptr, nullptr, s, n_frames, nullptr, 0, false, nullptr, (d_labels || d_faces) ? 2 : 1);
-    if (rc) return rc;
-    rc = assemble_frames(c, L, d_imgs_u8, n_frames, s); if (rc) return rc;
-    { TimedScope t(c, s, "assemble");
-      if (d_labels) launch_assemble_u32(L.d_label_cols.p, d_labels, g.n_angles, g.n_cells, g.scroll_image, s, n_frames);
-      if (d_faces) launch_assemble_u32(L.d_face_cols.p, d_faces, g.n_angles, g.n_cells, g.scroll_image, s, n_frames); }
-    if (d_echo_counts)      // (whole frames: segment = frame * n_angles + azimuth, the layout of the caller's buffers)
-        launch_echo_export(L.d_prov.p, L.d_prov_count.p, (size_t)L.prov_cap, n_frames * g.n_angles, d_echoes, d_echoes ? echo_stride : 0, d_echo_counts, s);
-    RR_HIP(c, hipGetLastError());
-    RR_HIP(c, give_lane(L, s));
-    return 0;
-}
-
-// the refusals of the two paths entry points (nothing is written)
-int check_paths(rr_ctx* c, const char* who, const void* poses, int n_frames, const void* imgs, const void* waves, size_t wave_stride,
-                const void* counts, unsigned flags)
-{
-    int rc = check_ready(c); if (rc) return rc;
-    const std::string w(who);
-    if (!poses || !imgs) return fail(c, -3, w + ": null poses/output");
-    if (n_frames < 1 || n_frames > RR_MAX_BATCH) return fail(c, -3, w + ": n_frames must be 1..64");
-    if (waves && !counts) return fail(c, -3, w + ": a wave buffer needs a count buffer");
-    if (waves && wave_stride == 0) return fail(c, -3, w + ": wave_stride must be positive");
-    if ((uintptr_t)waves % 16 != 0) return fail(c, -3, w + ": the wave buffer must be 16-byte aligned");
-    if (flags & ~(unsigned)RR_WAVES_MAP_FRAME) return fail(c, -3, w + ": unknown flag bits");
-    if (c->n_objects >= 0xFFFFFFu) return fail(c, -3, w + ": the info word holds object ids below 2^24 - 1");
-    if (c->cfg.n_reflections > RR_WAVES_MAX_PASSES) return fail(c, -3, w + ": the info word holds passes below 16 (n_reflections <= 16)");
-    return 0;
-}
-
-// a pose batch with wave paths on lane li (taken and handed back here), everything enqueued on s
-int paths_batch(rr_ctx* c, size_t li, const float* poses, int n_frames, uint8_t* d_imgs_u8, rr_wave_rec* d_waves, size_t wave_stride,
-                uint32_t* d_wave_counts, uint32_t* d_pass_counts, unsigned flags, hipStream_t s)
-{
-    Lane& L = c->lanes[li];
-    int rc = take_lane(c, li, s); if (rc) return rc;
-    WaveOut wo;      // (whole frames: segment = frame * n_angles + azimuth, the layout of the caller's buffers)
-    wo.recs = reinterpret_cast<float4*>(d_waves); wo.stride = d_waves ? wave_stride : 0;
-    wo.counts = d_wave_counts; wo.pass_counts = d_pass_counts; wo.state = nullptr; wo.flags = flags;
-    rc = run_frame(c, L, poses, 0, c->cfg.n_angles, nullptr, nullptr, s, n_frames, nullptr, 0, false, nullptr, 0, &wo); if (rc) return rc;
-    rc = assemble_frames(c, L, d_imgs_u8, n_frames, s); if (rc) return rc;
-    RR_HIP(c, give_lane(L, s));
-    return 0;
-}
-
-// the refusals of the two Doppler entry points (nothing is written): those of the paths call, and a non-finite gain or sensor velocity
-int check_doppler(rr_ctx* c, const char* who, const void* poses, int n_frames, const float* sensor_vel, float gain, const void* imgs, const void* vel,
-                  const void* cells, size_t echo_stride, const void* counts, const void* vel_img)
-{
-    int rc = check_ready(c); if (rc) return rc;
-    const std::string w(who);
-    if (!poses || !imgs) return fail(c, -3, w + ": null poses/output");
-    if (n_frames < 1 || n_frames > RR_MAX_BATCH) return fail(c, -3, w + ": n_frames must be 1..64");
-    if ((vel || cells) && !counts) return fail(c, -3, w + ": an echo buffer needs a count buffer");
-    if ((vel || cells) && echo_stride == 0) return fail(c, -3, w + ": echo_stride must be positive");
-    if (!std::isfinite(gain)) return fail(c, -3, w + ": non-finite gain");
-    for (int k = 0; sensor_vel && k < 3 * n_frames; k++) if (!std::isfinite(sensor_vel[k])) return fail(c, -3, w + ": non-finite sensor velocity");
-    if (vel_img && c->cfg.n_cells > kLabelMaxCells) return fail(c, -3, w + ": n_cells exceeds RR_LABEL_MAX_CELLS (8192) with a velocity image");
-    if (c->n_objects >= 0xFFFFFFu) return fail(c, -3, w + ": the info word holds object ids below 2^24 - 1");
-    if (c->cfg.n_reflections > 16) return fail(c, -3, w + ": the info word holds passes below 16 (n_reflections <= 16)");
-    return 0;
-}
-
-// a pose batch with Doppler on lane li (taken and handed back here), everything enqueued on s.  d_img_f32: the f32 image of ONE frame
-int doppler_batch(rr_ctx* c, size_t li, const float* poses, int n_frames, const float* sensor_vel, float gain, uint8_t* d_imgs_u8, float* d_img_f32,
-                  float* d_echo_vel, size_t echo_stride, uint32_t* d_echo_counts, int32_t* d_echo_cells, float* d_vel_img, hipStream_t s)
-{
-    Lane& L = c->lanes[li];
-    const rr_config& g = c->cfg;
-    int rc = take_lane(c, li, s); if (rc) return rc;
-    DopArgs da{};      // (whole frames: segment = frame * n_angles + azimuth, the layout of the caller's buffers; the lane's part: run_frame)
-    da.gain = gain; da.vel_cols = d_vel_img;      // (non-null: asked for)
-    da.echo_vel = d_echo_vel; da.echo_cells = d_echo_cells; da.echo_counts = d_echo_counts; da.stride = (d_echo_vel || d_echo_cells) ? echo_stride : 0;
-    rc = run_frame(c, L, poses, 0, g.n_angles, nullptr, nullptr, s, n_frames, nullptr, 0, d_img_f32 != nullptr, nullptr, 1, nullptr, &da, sensor_vel);
-    if (rc) return rc;
-    rc = assemble_frames(c, L, d_imgs_u8, n_frames, s); if (rc) return rc;
-    { TimedScope t(c, s, "assemble");
-      if (d_img_f32) launch_assemble_f32(L.d_cols_f32.p, d_img_f32, g.n_angles, g.n_cells, g.scroll_image, s);
-      if (d_vel_img) launch_assemble_u32(reinterpret_cast<const uint32_t*>(L.d_dop_vel_cols.p), reinterpret_cast<uint32_t*>(d_vel_img), g.n_angles, g.n_cells,
-                                         g.scroll_image, s, n_frames); }
-    RR_HIP(c, hipGetLastError());
-    RR_HIP(c, give_lane(L, s));
-    return 0;
-}
-
 }  // namespace
 
 void drop_graphs(Lane& L)
 {
     for (Lane::FrameGraph& fg : L.graphs) drop_graph(fg);
     L.graphs.clear();
+}
+
+// The lane's provenance buffers for its current frame buffers (after prepare_lane).  A segment's list holds at most the lane's signal
+// capacity (every pass' wave bound, twice that with record_multi_path) -- the list k_column reads -- plus the last pass' slot bound
+int ensure_prov_buffers(rr_ctx* c, Lane& L)
+{
+    const rr_config g = eff_config(c);
+    const int n_beam = (int)(c->beams.size() / 3);
+    const int last = std::max(0, g.n_reflections - 1);
+    const long last_bound = std::min<long>((long)L.buf_cap, last < 20 ? (long)n_beam << last : (long)L.buf_cap);
+    const int echo_cap = L.buf_sigcap + (int)last_bound * (g.record_multi_path ? 2 : 1);
+    if (L.d_prov.p && L.prov_seg >= L.buf_seg && L.prov_cap == echo_cap && L.prov_cells == L.buf_cells) return 0;
+    const size_t S = (size_t)L.buf_seg;
+    size_t free_b = 0, total_b = 0;
+    RR_HIP(c, hipMemGetInfo(&free_b, &total_b));
+    if (S * ((size_t)echo_cap * sizeof(EchoSrc) + (size_t)L.buf_cells * 8) > total_b / 2)
+        return fail(c, -6, "the echo lists of a provenance call need more than half of device memory; fewer frames per call or a lower max_waves_per_azimuth");
+    RR_HIP(c, hipDeviceSynchronize());      // a provenance chain in flight may still use the old buffers
+    RR_HIP(c, L.d_prov.ensure(S * (size_t)echo_cap));
+    RR_HIP(c, L.d_prov_count.ensure(S));
+    RR_HIP(c, L.d_label_cols.ensure(S * (size_t)L.buf_cells));
+    RR_HIP(c, L.d_face_cols.ensure(S * (size_t)L.buf_cells));
+    L.prov_seg = L.buf_seg; L.prov_cap = echo_cap; L.prov_cells = L.buf_cells;
+    return 0;
 }
 
 // Size the lane's frame buffers for n_seg segments under the CURRENT config.  This is the one place
@@ -619,10 +517,10 @@ hipError_t give_lane(Lane& L, hipStream_t s)
     return e;
 }
 
-int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, uint8_t* d_cols_u8 /* null: the lane's own buffer */, float* d_cols_f32, hipStream_t s, int n_frames,
-              const float4* d_matsets, int mat_stride, bool lane_f32, const SetPlan* plan, int provenance, const WaveOut* paths, const DopArgs* doppler,
-              const float* sensor_vel)
+int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, hipStream_t s, const FrameJob& job)
 {
+    const int n_frames = job.n_frames, provenance = job.provenance;
+    const float4* d_matsets = job.d_matsets; const WaveOut* paths = job.paths; const DopArgs* doppler = job.doppler;
     const rr_config g = eff_config(c);      // (a parameter batch may ask for more passes than the config)
     if (az_begin < 0 || az_end > g.n_angles || az_begin > az_end) return fail(c, -3, "azimuth range out of bounds");
     const int n_loc = az_end - az_begin;
@@ -638,7 +536,7 @@ int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, u
     if (provenance && d_matsets) return fail(c, -3, "echo provenance is for pose batches: the frames of a parameter batch share the hits of pass 0");
     if (paths && d_matsets) return fail(c, -3, "wave paths are for pose batches: the frames of a parameter batch share the hits of pass 0");
     if (doppler && (d_matsets || !provenance)) return fail(c, -3, "Doppler is for pose batches with their echo lists: the frames of a parameter batch share the hits of pass 0");
-    rc = prepare_lane(c, L, n_seg, lane_f32); if (rc) return rc;
+    rc = prepare_lane(c, L, n_seg, job.lane_f32); if (rc) return rc;
     if (provenance) { rc = ensure_prov_buffers(c, L); if (rc) return rc; }
     DopArgs da{};
     if (doppler) {
@@ -650,7 +548,8 @@ int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, u
         // copy of the lane's previous Doppler call has left it before it is written again
         if (L.pending_consume) RR_HIP(c, hipEventSynchronize(L.ev_consumed));
         L.h_dop_in.assign(64 + 2 * (size_t)c->n_objects, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-        for (int f = 0; f < n_frames && sensor_vel; f++) L.h_dop_in[(size_t)f] = make_float4(sensor_vel[3 * f], sensor_vel[3 * f + 1], sensor_vel[3 * f + 2], 0.0f);
+        const float* v = job.sensor_vel;
+        for (int f = 0; f < n_frames && v; f++) L.h_dop_in[(size_t)f] = make_float4(v[3 * f], v[3 * f + 1], v[3 * f + 2], 0.0f);
         for (size_t o = 0; o < (size_t)c->n_objects && 6 * o + 5 < c->twists.size(); o++) {
             const float* t = c->twists.data() + 6 * o;
             L.h_dop_in[64 + 2 * o] = make_float4(t[0], t[1], t[2], 0.0f); L.h_dop_in[64 + 2 * o + 1] = make_float4(t[3], t[4], t[5], 0.0f);
@@ -659,8 +558,8 @@ int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, u
     }
     WaveOut wo{};
     if (paths) { rc = ensure_path_state(c, L); if (rc) return rc; wo = *paths; wo.state = L.d_path_state.p; }
-    if (!d_cols_u8) d_cols_u8 = L.d_cols_u8.p;       // the lane's own column buffer, valid only from here on
-    if (lane_f32) d_cols_f32 = L.d_cols_f32.p;
+    uint8_t* d_cols_u8 = job.d_cols_u8 ? job.d_cols_u8 : L.d_cols_u8.p;       // the lane's own column buffer, valid only from here on
+    float* d_cols_f32 = job.lane_f32 ? L.d_cols_f32.p : job.d_cols_f32;
     Params P;
     fill_params(c, L, P, pose, az_begin, n_seg, d_cols_u8, d_cols_f32);
     P.n_loc = n_loc; P.n_frames = n_frames;
@@ -669,11 +568,12 @@ int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, u
         if (provenance > 1) { P.label_cols = L.d_label_cols.p; P.face_cols = L.d_face_cols.p; }
     }
     if (d_matsets) {   // parameter batch: one pose, one material table per frame
-        P.materials = d_matsets; P.mat_limits = L.d_matset_limits.p; P.mat_stride = mat_stride;
+        P.materials = d_matsets; P.mat_limits = L.d_matset_limits.p; P.mat_stride = job.mat_stride;
         P.set_mode = 1;
         P.noise_rows = 1;     // every set is the SAME frame under another parameter set: one noise realisation (row 0)
         P.motion_rows = 1;    // ... and one sweep of the antenna (table 0); every set the SAME pose: q_sm / t_sm (no pose table)
         SetPlan dflt;
+        const SetPlan* plan = job.plan;
         if (!plan) {          // material sets only: one beam, every frame the config's passes
             for (int f = 0; f < n_frames; f++) { dflt.frame_passes[f] = (unsigned char)g.n_reflections; dflt.frame_beam[f] = 0; }
             dflt.group_frame[0] = 0; plan = &dflt;
@@ -706,7 +606,7 @@ int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, u
     // does not even look at the lane's graphs: a plain batch afterwards replays as before); whatever a captured launch bakes in is
     // covered by graph_gen (tables, tree, lane buffers) or by the key (azimuth block, frames, output buffer, trace rows)
     if (L.graph_gen != c->graph_gen) { drop_graphs(L); L.graph_gen = c->graph_gen; }
-    const bool graphable = !d_matsets && c->use_graphs && !c->timing && !c->stats_mode && !c->roctx && !d_cols_f32 && !provenance && !paths && !doppler && g.n_reflections > 0;
+    const bool graphable = !(provenance || paths || doppler) && !d_matsets && !d_cols_f32 && c->use_graphs && !c->timing && !c->stats_mode && !c->roctx && g.n_reflections > 0;
     if (graphable) {
         Lane::FrameGraph* fg = find_graph(L, az_begin, az_end, n_frames, d_cols_u8, P);
         fg->last_use = ++c->graph_clock;
@@ -715,14 +615,16 @@ int run_frame(rr_ctx* c, Lane& L, const float* pose, int az_begin, int az_end, u
         fg->hits++;
     }
     Params Plist;
+    ChainSide side; side.wo = paths ? &wo : nullptr;
     if (doppler) {      // the list-only form of the column launch: two passes on paper, the list = the shifted echoes, no slot of a last pass
+        side.da = &da; side.Qlist = &Plist;
         Plist = P;
         Plist.n_passes = 2; Plist.sig = da.shifted; Plist.sig_count = da.count; Plist.sigcap = L.prov_cap;
         Plist.count[1] = L.d_dop_zero.p; Plist.seg_stats = L.d_dop_stats.p;      // (the chain's own statistics stay as its k_column left them)
         Plist.hist_host = nullptr; Plist.grid_hint = nullptr;
     }
     { HostProfScope hp(5, "ctx:   chain issued kernel by kernel");
-      const int rcq = issue_chain(c, P, pa, g, s, paths ? &wo : nullptr, doppler ? &da : nullptr, doppler ? &Plist : nullptr); if (rcq) return rcq; }
+      const int rcq = issue_chain(c, P, pa, g, s, side); if (rcq) return rcq; }
     RR_HIP(c, hipGetLastError());
     return 0;
 }
@@ -771,206 +673,6 @@ int rr_simulate_batch_device(rr_ctx* c, const float* poses, int n_frames, uint8_
     rc = take_lane(c, li, s); if (rc) return rc;
     rc = render_batch(c, L, poses, n_frames, d_imgs_u8, s); if (rc) return rc;
     RR_HIP(c, give_lane(L, s));
-    return 0;
-}
-
-int rr_simulate_batch_provenance_device(rr_ctx* c, const float* poses, int n_frames, uint8_t* d_imgs_u8, uint32_t* d_labels, uint32_t* d_faces,
-                                        rr_echo_src* d_echoes, size_t echo_stride, uint32_t* d_echo_counts, void* stream)
-{
-    int rc = check_provenance(c, "rr_simulate_batch_provenance_device", poses, n_frames, d_imgs_u8, d_echoes, echo_stride, d_echo_counts); if (rc) return rc;
-    RR_HIP(c, hipSetDevice(c->device));
-    rc = upload_tables(c); if (rc) return rc;
-    return provenance_batch(c, c->next_lane++ % c->lanes.size(), poses, n_frames, d_imgs_u8, d_labels, d_faces, d_echoes, echo_stride, d_echo_counts,
-                            stream_of(c, stream));
-}
-
-int rr_simulate_provenance(rr_ctx* c, const float pose[7], uint8_t* out_u8, uint32_t* out_labels, uint32_t* out_faces, rr_echo_src* out_echoes,
-                           size_t echo_stride, uint32_t* out_echo_counts)
-{
-    int rc = check_provenance(c, "rr_simulate_provenance", pose, 1, out_u8, out_echoes, echo_stride, out_echo_counts); if (rc) return rc;
-    RR_HIP(c, hipSetDevice(c->device));
-    rc = upload_tables(c); if (rc) return rc;
-    const rr_config& g = c->cfg;
-    const size_t A = (size_t)g.n_angles, npx = A * (size_t)g.n_cells;
-    Lane& L = c->lanes[0];
-    hipStream_t s = c->stream;
-    rc = settle_lane(c, L); if (rc) return rc;               // the image is assembled in the buffer of delivery slot 0, as rr_simulate does
-    // the device-side row of the exported stream: as long as the caller's, and no longer than a list can get
-    rc = prepare_lane(c, L, (int)A); if (rc) return rc;
-    rc = ensure_prov_buffers(c, L); if (rc) return rc;
-    const size_t d_stride = out_echoes ? std::min(echo_stride, (size_t)L.prov_cap) : 0;
-    RR_HIP(c, L.slot[0].img.ensure(npx));
-    if (out_labels) RR_HIP(c, L.d_label_img.ensure(npx));
-    if (out_faces) RR_HIP(c, L.d_face_img.ensure(npx));
-    if (out_echoes) RR_HIP(c, L.d_echo_out.ensure(A * d_stride));
-    if (out_echo_counts) RR_HIP(c, L.d_echo_out_counts.ensure(A));
-    rc = provenance_batch(c, 0, pose, 1, L.slot[0].img.p, out_labels ? L.d_label_img.p : nullptr, out_faces ? L.d_face_img.p : nullptr,
-                          out_echoes ? L.d_echo_out.p : nullptr, d_stride, out_echo_counts ? L.d_echo_out_counts.p : nullptr, s);
-    if (rc) return rc;
-    // outputs are staged: a call that fails below has written nothing
-    std::vector<uint8_t> h8(npx); std::vector<uint32_t> hl(out_labels ? npx : 0), hf(out_faces ? npx : 0), hc(out_echo_counts ? A : 0);
-    std::vector<rr_echo_src> he(out_echoes ? A * d_stride : 0);
-    RR_HIP(c, hipMemcpyAsync(h8.data(), L.slot[0].img.p, npx, hipMemcpyDeviceToHost, s));
-    if (out_labels) RR_HIP(c, hipMemcpyAsync(hl.data(), L.d_label_img.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    if (out_faces) RR_HIP(c, hipMemcpyAsync(hf.data(), L.d_face_img.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    if (out_echo_counts) RR_HIP(c, hipMemcpyAsync(hc.data(), L.d_echo_out_counts.p, A * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    if (!he.empty()) RR_HIP(c, hipMemcpyAsync(he.data(), L.d_echo_out.p, he.size() * sizeof(rr_echo_src), hipMemcpyDeviceToHost, s));
-    RR_HIP(c, give_lane(L, s));
-    RR_HIP(c, hipStreamSynchronize(s));
-    rc = report_frame_errors(c); if (rc) return rc;
-    std::memcpy(out_u8, h8.data(), npx);
-    if (out_labels) std::memcpy(out_labels, hl.data(), npx * sizeof(uint32_t));
-    if (out_faces) std::memcpy(out_faces, hf.data(), npx * sizeof(uint32_t));
-    if (out_echo_counts) std::memcpy(out_echo_counts, hc.data(), A * sizeof(uint32_t));
-    if (out_echoes)         // only the records that exist reach the caller's rows
-        for (size_t a = 0; a < A; a++)
-            std::memcpy(out_echoes + a * echo_stride, he.data() + a * d_stride, std::min((size_t)hc[a], d_stride) * sizeof(rr_echo_src));
-    return 0;
-}
-
-int rr_simulate_batch_paths_device(rr_ctx* c, const float* poses, int n_frames, uint8_t* d_imgs_u8, rr_wave_rec* d_waves, size_t wave_stride,
-                                   uint32_t* d_wave_counts, uint32_t* d_pass_counts, unsigned flags, void* stream)
-{
-    int rc = check_paths(c, "rr_simulate_batch_paths_device", poses, n_frames, d_imgs_u8, d_waves, wave_stride, d_wave_counts, flags); if (rc) return rc;
-    RR_HIP(c, hipSetDevice(c->device));
-    rc = upload_tables(c); if (rc) return rc;
-    return paths_batch(c, c->next_lane++ % c->lanes.size(), poses, n_frames, d_imgs_u8, d_waves, wave_stride, d_wave_counts, d_pass_counts, flags,
-                       stream_of(c, stream));
-}
-
-int rr_simulate_paths(rr_ctx* c, const float pose[7], uint8_t* out_u8, rr_wave_rec* out_waves, size_t wave_stride, uint32_t* out_wave_counts,
-                      uint32_t* out_pass_counts, unsigned flags)
-{
-    // (host rows need no alignment: they are filled by memcpy)
-    int rc = check_paths(c, "rr_simulate_paths", pose, 1, out_u8, nullptr, 0, out_wave_counts, flags); if (rc) return rc;
-    if (out_waves && !out_wave_counts) return fail(c, -3, "rr_simulate_paths: a wave buffer needs a count buffer");
-    if (out_waves && wave_stride == 0) return fail(c, -3, "rr_simulate_paths: wave_stride must be positive");
-    RR_HIP(c, hipSetDevice(c->device));
-    rc = upload_tables(c); if (rc) return rc;
-    const rr_config& g = c->cfg;
-    const size_t A = (size_t)g.n_angles, npx = A * (size_t)g.n_cells;
-    Lane& L = c->lanes[0];
-    hipStream_t s = c->stream;
-    rc = settle_lane(c, L); if (rc) return rc;               // the image is assembled in the buffer of delivery slot 0, as rr_simulate does
-    rc = prepare_lane(c, L, (int)A); if (rc) return rc;
-    // the device-side row: as long as the caller's, and no longer than a list can get (every pass' wave bound)
-    size_t longest = 0;
-    { const long n_beam = (long)(c->beams.size() / 3); long w = n_beam;
-      for (int p = 0; p < g.n_reflections; p++) { longest += (size_t)std::min<long>(w, L.buf_cap); w = std::min<long>(2 * w, L.buf_cap); } }
-    const size_t d_stride = out_waves ? std::max<size_t>(1, std::min(wave_stride, longest)) : 0;
-    RR_HIP(c, L.slot[0].img.ensure(npx));
-    if (out_waves) RR_HIP(c, L.d_wave_out.ensure(A * d_stride * 4));
-    if (out_wave_counts) RR_HIP(c, L.d_wave_out_counts.ensure(A));
-    if (out_pass_counts) RR_HIP(c, L.d_wave_out_passes.ensure(A * RR_WAVES_MAX_PASSES));
-    rc = paths_batch(c, 0, pose, 1, L.slot[0].img.p, out_waves ? reinterpret_cast<rr_wave_rec*>(L.d_wave_out.p) : nullptr, d_stride,
-                     out_wave_counts ? L.d_wave_out_counts.p : nullptr, out_pass_counts ? L.d_wave_out_passes.p : nullptr, flags, s);
-    if (rc) return rc;
-    // outputs are staged: a call that fails below has written nothing
-    std::vector<uint8_t> h8(npx); std::vector<uint32_t> hc(out_wave_counts ? A : 0), hp(out_pass_counts ? A * RR_WAVES_MAX_PASSES : 0);
-    std::vector<rr_wave_rec> hw(out_waves ? A * d_stride : 0);
-    RR_HIP(c, hipMemcpyAsync(h8.data(), L.slot[0].img.p, npx, hipMemcpyDeviceToHost, s));
-    if (out_wave_counts) RR_HIP(c, hipMemcpyAsync(hc.data(), L.d_wave_out_counts.p, A * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    if (out_pass_counts) RR_HIP(c, hipMemcpyAsync(hp.data(), L.d_wave_out_passes.p, hp.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    if (!hw.empty()) RR_HIP(c, hipMemcpyAsync(hw.data(), L.d_wave_out.p, hw.size() * sizeof(rr_wave_rec), hipMemcpyDeviceToHost, s));
-    RR_HIP(c, give_lane(L, s));
-    RR_HIP(c, hipStreamSynchronize(s));
-    rc = report_frame_errors(c); if (rc) return rc;
-    std::memcpy(out_u8, h8.data(), npx);
-    if (out_wave_counts) std::memcpy(out_wave_counts, hc.data(), A * sizeof(uint32_t));
-    if (out_pass_counts) std::memcpy(out_pass_counts, hp.data(), hp.size() * sizeof(uint32_t));
-    if (out_waves)          // only the records that exist reach the caller's rows
-        for (size_t a = 0; a < A; a++)
-            std::memcpy(out_waves + a * wave_stride, hw.data() + a * d_stride, std::min((size_t)hc[a], d_stride) * sizeof(rr_wave_rec));
-    return 0;
-}
-
-int rr_simulate_batch_doppler_device(rr_ctx* c, const float* poses, int n_frames, const float* sensor_vel, float gain, uint8_t* d_imgs_u8,
-                                     float* d_echo_vel, size_t echo_stride, uint32_t* d_echo_counts, int32_t* d_echo_cells, float* d_vel_img, void* stream)
-{
-    int rc = check_doppler(c, "rr_simulate_batch_doppler_device", poses, n_frames, sensor_vel, gain, d_imgs_u8, d_echo_vel, d_echo_cells, echo_stride,
-                           d_echo_counts, d_vel_img);
-    if (rc) return rc;
-    RR_HIP(c, hipSetDevice(c->device));
-    rc = upload_tables(c); if (rc) return rc;
-    return doppler_batch(c, c->next_lane++ % c->lanes.size(), poses, n_frames, sensor_vel, gain, d_imgs_u8, nullptr, d_echo_vel, echo_stride, d_echo_counts,
-                         d_echo_cells, d_vel_img, stream_of(c, stream));
-}
-
-int rr_simulate_doppler(rr_ctx* c, const float pose[7], const float sensor_vel[3], float gain, uint8_t* out_u8, float* out_f32, float* out_echo_vel,
-                        size_t echo_stride, uint32_t* out_echo_counts, int32_t* out_echo_cells, float* out_vel_img)
-{
-    int rc = check_doppler(c, "rr_simulate_doppler", pose, 1, sensor_vel, gain, out_u8, out_echo_vel, out_echo_cells, echo_stride, out_echo_counts, out_vel_img);
-    if (rc) return rc;
-    RR_HIP(c, hipSetDevice(c->device));
-    rc = upload_tables(c); if (rc) return rc;
-    const rr_config& g = c->cfg;
-    const size_t A = (size_t)g.n_angles, npx = A * (size_t)g.n_cells;
-    Lane& L = c->lanes[0];
-    hipStream_t s = c->stream;
-    rc = settle_lane(c, L); if (rc) return rc;               // the image is assembled in the buffer of delivery slot 0, as rr_simulate does
-    // the device-side rows: as long as the caller's, and no longer than a list can get
-    rc = prepare_lane(c, L, (int)A, out_f32 != nullptr); if (rc) return rc;
-    rc = ensure_prov_buffers(c, L); if (rc) return rc;
-    const bool rows = out_echo_vel || out_echo_cells;
-    const size_t d_stride = rows ? std::min(echo_stride, (size_t)L.prov_cap) : 0;
-    RR_HIP(c, L.slot[0].img.ensure(npx));
-    if (out_f32) RR_HIP(c, L.d_img_f32.ensure(npx));
-    if (out_echo_vel) RR_HIP(c, L.d_dop_out_vel.ensure(A * d_stride));
-    if (out_echo_cells) RR_HIP(c, L.d_dop_out_cells.ensure(A * d_stride));
-    if (out_echo_counts) RR_HIP(c, L.d_dop_out_counts.ensure(A));
-    if (out_vel_img) RR_HIP(c, L.d_dop_vel_img.ensure(npx));
-    rc = doppler_batch(c, 0, pose, 1, sensor_vel, gain, L.slot[0].img.p, out_f32 ? L.d_img_f32.p : nullptr, out_echo_vel ? L.d_dop_out_vel.p : nullptr, d_stride,
-                       out_echo_counts ? L.d_dop_out_counts.p : nullptr, out_echo_cells ? L.d_dop_out_cells.p : nullptr,
-                       out_vel_img ? L.d_dop_vel_img.p : nullptr, s);
-    if (rc) return rc;
-    // outputs are staged: a call that fails below has written nothing
-    std::vector<uint8_t> h8(npx); std::vector<float> hf(out_f32 ? npx : 0), hv(out_echo_vel ? A * d_stride : 0), hi(out_vel_img ? npx : 0);
-    std::vector<int32_t> hcl(out_echo_cells ? A * d_stride : 0); std::vector<uint32_t> hc(out_echo_counts ? A : 0);
-    RR_HIP(c, hipMemcpyAsync(h8.data(), L.slot[0].img.p, npx, hipMemcpyDeviceToHost, s));
-    if (out_f32) RR_HIP(c, hipMemcpyAsync(hf.data(), L.d_img_f32.p, npx * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (!hv.empty()) RR_HIP(c, hipMemcpyAsync(hv.data(), L.d_dop_out_vel.p, hv.size() * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (!hcl.empty()) RR_HIP(c, hipMemcpyAsync(hcl.data(), L.d_dop_out_cells.p, hcl.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (out_echo_counts) RR_HIP(c, hipMemcpyAsync(hc.data(), L.d_dop_out_counts.p, A * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    if (out_vel_img) RR_HIP(c, hipMemcpyAsync(hi.data(), L.d_dop_vel_img.p, npx * sizeof(float), hipMemcpyDeviceToHost, s));
-    RR_HIP(c, give_lane(L, s));
-    RR_HIP(c, hipStreamSynchronize(s));
-    rc = report_frame_errors(c); if (rc) return rc;
-    std::memcpy(out_u8, h8.data(), npx);
-    if (out_f32) std::memcpy(out_f32, hf.data(), npx * sizeof(float));
-    if (out_vel_img) std::memcpy(out_vel_img, hi.data(), npx * sizeof(float));
-    if (out_echo_counts) std::memcpy(out_echo_counts, hc.data(), A * sizeof(uint32_t));
-    for (size_t a = 0; rows && a < A; a++) {          // only the echoes that exist reach the caller's rows
-        const size_t m = std::min((size_t)hc[a], d_stride);
-        if (out_echo_vel) std::memcpy(out_echo_vel + a * echo_stride, hv.data() + a * d_stride, m * sizeof(float));
-        if (out_echo_cells) std::memcpy(out_echo_cells + a * echo_stride, hcl.data() + a * d_stride, m * sizeof(int32_t));
-    }
-    return 0;
-}
-
-int rr_debug_labels(rr_ctx* c, int n_seg, int az_begin, const rr_echo_src* echoes, const uint32_t* counts, size_t stride, uint32_t* out_labels,
-                    uint32_t* out_faces)
-{
-    if (!c) return -1;
-    if (!c->have_cfg) return fail(c, -2, "rr_set_config has not been called");
-    const rr_config& g = c->cfg;
-    if (n_seg < 1 || az_begin < 0 || az_begin > g.n_angles - n_seg) return fail(c, -3, "rr_debug_labels: azimuth block out of bounds");
-    if (!counts || !out_labels || !out_faces || (stride > 0 && !echoes)) return fail(c, -3, "rr_debug_labels: null buffer");
-    if (g.n_cells > kLabelMaxCells) return fail(c, -3, "rr_debug_labels: n_cells exceeds RR_LABEL_MAX_CELLS (8192)");
-    for (int k = 0; k < n_seg; k++) if (counts[k] > stride) return fail(c, -3, "rr_debug_labels: a count exceeds stride");
-    RR_HIP(c, hipSetDevice(c->device));
-    int rc = upload_tables(c); if (rc) return rc;
-    const size_t S = (size_t)n_seg, px = S * (size_t)g.n_cells;
-    DevBuf<EchoSrc> d_e; DevBuf<uint32_t> d_n, d_l, d_f;
-    RR_HIP(c, d_e.ensure(S * stride)); RR_HIP(c, d_n.ensure(S)); RR_HIP(c, d_l.ensure(px)); RR_HIP(c, d_f.ensure(px));
-    if (stride) RR_HIP(c, hipMemcpy(d_e.p, echoes, S * stride * sizeof(rr_echo_src), hipMemcpyHostToDevice));
-    RR_HIP(c, hipMemcpy(d_n.p, counts, S * sizeof(uint32_t), hipMemcpyHostToDevice));
-    const bool den = !c->smear.empty() && g.signal_denoising > 0;
-    launch_label(d_e.p, d_n.p, stride, n_seg, g.n_cells, den ? (int)c->smear.size() : 1, den ? c->smear_mode : 0, den ? c->d_smear.p : nullptr, d_l.p, d_f.p,
-                 c->stream);
-    RR_HIP(c, hipGetLastError());
-    RR_HIP(c, hipStreamSynchronize(c->stream));
-    RR_HIP(c, hipMemcpy(out_labels, d_l.p, px * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    RR_HIP(c, hipMemcpy(out_faces, d_f.p, px * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -1114,7 +816,7 @@ int rr_simulate_device(rr_ctx* c, const float pose[7], uint8_t* d_img_u8, void* 
         const bool capturing = cap == hipStreamCaptureStatusActive;
         // the lane's previous frame may have run on ANOTHER caller stream (or a flushed host copy may still read the lane)
         rc = take_lane(c, 0, capturing ? nullptr : user); if (rc) return rc;
-        rc = run_frame(c, L, pose, 0, A, nullptr, nullptr, user); if (rc) return rc;
+        rc = run_frame(c, L, pose, 0, A, user); if (rc) return rc;
         rc = rr_assemble_image_device(c, L.d_cols_u8.p, d_img_u8, user); if (rc) return rc;
         if (!capturing) RR_HIP(c, give_lane(L, user));
         return 0;
@@ -1126,7 +828,7 @@ int rr_simulate_device(rr_ctx* c, const float pose[7], uint8_t* d_img_u8, void* 
     const size_t li = c->next_stream_lane++ % (size_t)c->stream_lanes;
     Lane& L = c->lanes[li];
     rc = take_lane(c, li, L.stream); if (rc) return rc;
-    rc = run_frame(c, L, pose, 0, A, nullptr, nullptr, L.stream); if (rc) return rc;
+    rc = run_frame(c, L, pose, 0, A, L.stream); if (rc) return rc;
     RR_HIP(c, hipEventRecord(L.ev_ready, L.stream));
     RR_HIP(c, hipStreamWaitEvent(user, L.ev_ready, 0));
     rc = rr_assemble_image_device(c, L.d_cols_u8.p, d_img_u8, user); if (rc) return rc;
@@ -1151,8 +853,8 @@ int rr_simulate(rr_ctx* c, const float pose[7], int az_begin, int az_end,
     // ordered behind the lane's previous user by an event (no device-wide drain), the error bits and the per-pass
     // counters ride home behind the image on the same stream, and ONE hipStreamSynchronize ends the call.
     rc = take_lane(c, 0, c->stream); if (rc) return rc;
-    rc = run_frame(c, L, pose, az_begin, az_end, nullptr, nullptr, c->stream, 1, nullptr, 0, out_f32 != nullptr);
-    if (rc) return rc;
+    FrameJob job; job.lane_f32 = out_f32 != nullptr;
+    rc = run_frame(c, L, pose, az_begin, az_end, c->stream, job); if (rc) return rc;
     const size_t n_st = (size_t)n_seg * (size_t)std::max(1, g.n_reflections);
     const size_t need = sizeof(Counters) + (stats ? n_st * sizeof(SegStats) : 0);
     if (c->h_frame_bytes < need) {

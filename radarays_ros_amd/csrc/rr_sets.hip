@@ -91,7 +91,8 @@ int rr_simulate_param_sets_device(rr_ctx* c, const float pose[7], const rr_param
     }
     if (!rc) {
         launch_mat_limits(L.d_matsets.p, (size_t)n_sets * n_mat, L.d_matset_limits.p, s);
-        rc = run_frame(c, L, pose, 0, g0.n_angles, nullptr, nullptr, s, n_sets, L.d_matsets.p, (int)n_mat, false, &plan);
+        FrameJob job; job.n_frames = n_sets; job.d_matsets = L.d_matsets.p; job.mat_stride = (int)n_mat; job.plan = &plan;
+        rc = run_frame(c, L, pose, 0, g0.n_angles, s, job);
     }
     c->passes_override = -1;
     if (rc) {
