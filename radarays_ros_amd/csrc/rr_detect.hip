@@ -16,6 +16,7 @@
 #include "../../include/radarays_mi355.h"
 #include "rr_device.h"
 #include "rr_launch.h"
+#include "rr_polar.h"
 
 #include <algorithm>
 
@@ -29,9 +30,7 @@ constexpr int kLdsMax = 65536;
 struct DetectArgs {
     int method, guard, train, k, min_intensity, min_bin;
     float cfar_scale;
-    int n_cells, n_angles, scroll;      // scroll in [0, n_angles)
-    float theta_min, theta_inc;
-    double resolution;
+    PolarGrid G;
     int max_points;
     int vec;                            // rows of a tile are loaded as TW-byte words
 };
@@ -55,12 +54,12 @@ __device__ inline void load_tile(const uint8_t* img, uint8_t* tile, int col0, co
     if (A.vec) {
         using W = typename RowWord<TW>::T;
 #pragma unroll 4
-        for (int r = threadIdx.x; r < A.n_cells; r += kDetTB)
-            *reinterpret_cast<W*>(tile + (size_t)r * TW) = *reinterpret_cast<const W*>(img + (size_t)r * A.n_angles + col0);
+        for (int r = threadIdx.x; r < A.G.n_cells; r += kDetTB)
+            *reinterpret_cast<W*>(tile + (size_t)r * TW) = *reinterpret_cast<const W*>(img + (size_t)r * A.G.n_angles + col0);
     } else {            // n_angles not a multiple of TW (or an unaligned base): lanes along the row, byte loads
-        for (int e = threadIdx.x; e < A.n_cells * TW; e += kDetTB) {
+        for (int e = threadIdx.x; e < A.G.n_cells * TW; e += kDetTB) {
             const int r = e / TW, c = e - r * TW;
-            tile[e] = col0 + c < A.n_angles ? img[(size_t)r * A.n_angles + col0 + c] : (uint8_t)0;
+            tile[e] = col0 + c < A.G.n_angles ? img[(size_t)r * A.G.n_angles + col0 + c] : (uint8_t)0;
         }
     }
 }
@@ -87,12 +86,12 @@ struct Emit {
     int max_points;
     int col;
     float cs, sn;                       // direction of the column's azimuth
-    double resolution;
+    const PolarGrid& G;
     __device__ void operator()(int i, int z, uint32_t nth) const
     {
         const uint32_t idx = at + nth;
         if (idx >= (uint32_t)max_points) return;
-        const float r = (float)(((double)i + 0.5) * resolution);
+        const float r = bin_range(G, i);
         rr_radar_point p;
         p.x = r * cs; p.y = r * sn; p.z = 0.0f;
         p.intensity = (float)z;
@@ -106,7 +105,7 @@ struct NoEmit { __device__ void operator()(int, int, uint32_t) const {} };
 template <int TW, class F>
 __device__ inline uint32_t cfar_chunk(const uint8_t* tile, int c, int lo, int hi, const DetectArgs& A, const F& f)
 {
-    const int N = A.n_cells, G = A.guard, T = A.train;
+    const int N = A.G.n_cells, G = A.guard, T = A.train;
     const int i0 = max(lo, A.min_bin);
     if (i0 >= hi) return 0;
     uint32_t sl = 0, sr = 0;
@@ -155,7 +154,7 @@ __global__ void __launch_bounds__(kDetTB) k_detect(const uint8_t* imgs, rr_radar
     constexpr int TPC = kDetTB / TW;
     extern __shared__ __align__(16) uint8_t smem[];
     uint8_t* tile = smem;
-    uint32_t* part = reinterpret_cast<uint32_t*>(smem + align16((size_t)TW * A.n_cells));
+    uint32_t* part = reinterpret_cast<uint32_t*>(smem + align16((size_t)TW * A.G.n_cells));
     uint32_t* hist = part + kDetTB;                         // [TW][128]: counts of values 2w (low half) and 2w + 1 (high half)
     __shared__ int sel_thr[TW], sel_need[TW];
 
@@ -163,11 +162,11 @@ __global__ void __launch_bounds__(kDetTB) k_detect(const uint8_t* imgs, rr_radar
     const int col0 = blockIdx.x * TW;
     const int c = threadIdx.x / TPC, k = threadIdx.x % TPC;
     const int col = col0 + c;
-    const int chunk = (A.n_cells + TPC - 1) / TPC;
-    const int lo = min(A.n_cells, k * chunk), hi = min(A.n_cells, lo + chunk);
-    uint32_t* offs = offsets + (size_t)f * (A.n_angles + 1);
+    const int chunk = (A.G.n_cells + TPC - 1) / TPC;
+    const int lo = min(A.G.n_cells, k * chunk), hi = min(A.G.n_cells, lo + chunk);
+    uint32_t* offs = offsets + (size_t)f * (A.G.n_angles + 1);
 
-    load_tile<TW>(imgs + (size_t)f * A.n_cells * A.n_angles, tile, col0, A);
+    load_tile<TW>(imgs + (size_t)f * A.G.n_cells * A.G.n_angles, tile, col0, A);
     int thr = 0, eq_quota = 0;
     if (METHOD == 1) {
         for (int w = threadIdx.x; w < TW * 128; w += kDetTB) hist[w] = 0;
@@ -208,15 +207,14 @@ __global__ void __launch_bounds__(kDetTB) k_detect(const uint8_t* imgs, rr_radar
                                    : kstrong_chunk<TW>(tile, c, lo, hi, A, thr, eq_quota, NoEmit{});
     uint32_t col_total;
     const uint32_t before = chunk_prefix(part, n, c, k, TPC, &col_total);
-    if (col >= A.n_angles) return;
+    if (col >= A.G.n_angles) return;
     if (!EMIT) {
         if (k == 0) offs[col] = col_total;
         return;
     }
     if (n == 0) return;
-    const int a = col - A.scroll < 0 ? col - A.scroll + A.n_angles : col - A.scroll;
-    const float theta = A.theta_min + (float)a * A.theta_inc;
-    Emit e{ points + (size_t)f * A.max_points, offs[col] + before, A.max_points, col, cosf(theta), sinf(theta), A.resolution };
+    const float theta = az_theta(A.G, az_of_col(A.G, col));
+    Emit e{ points + (size_t)f * A.max_points, offs[col] + before, A.max_points, col, cosf(theta), sinf(theta), A.G };
     if (METHOD == 0) cfar_chunk<TW>(tile, c, lo, hi, A, e);
     else kstrong_chunk<TW>(tile, c, lo, hi, A, thr, eq_quota, e);
 }
@@ -244,67 +242,38 @@ __global__ void __launch_bounds__(64) k_detect_scan(uint32_t* offsets, int n_ang
 template <int TW, int METHOD>
 void launch_detect_tw(const uint8_t* imgs, int n_frames, rr_radar_point* points, uint32_t* offsets, const DetectArgs& A, hipStream_t s)
 {
-    const dim3 grid((A.n_angles + TW - 1) / TW, n_frames);
-    const size_t lds = detect_lds(TW, METHOD, A.n_cells);
+    const dim3 grid((A.G.n_angles + TW - 1) / TW, n_frames);
+    const size_t lds = detect_lds(TW, METHOD, A.G.n_cells);
     hipLaunchKernelGGL((k_detect<TW, METHOD, false>), grid, dim3(kDetTB), lds, s, imgs, points, offsets, A);
-    hipLaunchKernelGGL(k_detect_scan, dim3(n_frames), dim3(64), 0, s, offsets, A.n_angles);
+    hipLaunchKernelGGL(k_detect_scan, dim3(n_frames), dim3(64), 0, s, offsets, A.G.n_angles);
     if (A.max_points > 0)
         hipLaunchKernelGGL((k_detect<TW, METHOD, true>), grid, dim3(kDetTB), lds, s, imgs, points, offsets, A);
 }
 
 // ---- Cartesian ----
 struct CartArgs {
-    int width;
-    float pixel_size;
-    int n_cells, n_angles, scroll;
-    float theta_min, theta_inc, res;
+    CartGrid C;
+    PolarGrid G;
     int aligned;                        // the output base is 4-byte aligned
 };
 
-__device__ inline int cart_z(const uint8_t* img, const CartArgs& A, int b, int a)
-{
-    int col = a + A.scroll;
-    if (col >= A.n_angles) col -= A.n_angles;
-    return img[(size_t)b * A.n_angles + col];
-}
-
+// pixel (i, j) from the polar image (rr_polar.h): 0 beyond the last bin
 template <int INTERP>
 __device__ inline uint8_t cart_pixel(const uint8_t* img, const CartArgs& A, int i, int j)
 {
-    const float cc = (float)(A.width - 1) * 0.5f;
-    const float x = (cc - (float)i) * A.pixel_size, y = (cc - (float)j) * A.pixel_size;
-    const float rho = sqrtf(x * x + y * y), phi = atan2f(y, x);
-    float v = rho / A.res - 0.5f;
-    if (!(v <= (float)A.n_cells - 0.5f)) return 0;
-    v = fmaxf(v, 0.0f);
-    const float na = (float)A.n_angles;
-    float u = fmodf((phi - A.theta_min) / A.theta_inc, na);
-    if (u < 0.0f) u += na;
-    if (u >= na) u -= na;
-    if (!(u >= 0.0f && u < na)) u = 0.0f;      // (only a theta_inc so small that the quotient overflows gets here)
-    if (INTERP == 0) {
-        int a = (int)rintf(u);
-        if (a >= A.n_angles) a -= A.n_angles;
-        const int b = min((int)rintf(v), A.n_cells - 1);
-        return (uint8_t)cart_z(img, A, b, a);
-    }
-    const int a0 = min((int)floorf(u), A.n_angles - 1);
-    const int a1 = a0 + 1 == A.n_angles ? 0 : a0 + 1;
-    const float fu = u - (float)a0;
-    const int b0 = (int)floorf(v), b1 = min(b0 + 1, A.n_cells - 1);
-    const float fv = v - (float)b0;
-    const float p0 = (1.0f - fu) * (float)cart_z(img, A, b0, a0) + fu * (float)cart_z(img, A, b0, a1);
-    const float p1 = (1.0f - fu) * (float)cart_z(img, A, b1, a0) + fu * (float)cart_z(img, A, b1, a1);
-    const float val = rintf((1.0f - fv) * p0 + fv * p1);
-    return (uint8_t)fminf(fmaxf(val, 0.0f), 255.0f);
+    const V3 p = pixel_xy(A.C, i, j);
+    const float rho = sqrtf(p.x * p.x + p.y * p.y), phi = atan2f(p.y, p.x);
+    float v;
+    if (!range_coord(A.G, rho, &v)) return 0;
+    return polar_sample<INTERP>(img, A.G, az_coord(A.G, phi), v);
 }
 
 // INTERP: 0 nearest, 1 bilinear (two kernels, so that traces and counters tell them apart)
 template <int INTERP>
 __global__ void __launch_bounds__(256) k_cartesian(const uint8_t* imgs, uint8_t* out, size_t total, CartArgs A)
 {
-    const uint32_t w = (uint32_t)A.width, wsq = w * w;
-    const size_t npx = (size_t)A.n_cells * A.n_angles;
+    const uint32_t w = (uint32_t)A.C.width, wsq = w * w;
+    const size_t npx = (size_t)A.G.n_cells * A.G.n_angles;
     for (size_t q = 4 * ((size_t)blockIdx.x * blockDim.x + threadIdx.x); q < total; q += 4 * (size_t)gridDim.x * blockDim.x) {
         size_t f = q / wsq;
         const uint32_t rem = (uint32_t)(q - f * wsq);
@@ -328,18 +297,16 @@ __global__ void __launch_bounds__(256) k_cartesian(const uint8_t* imgs, uint8_t*
 // the widest tile whose LDS fits (16 columns up to 3440 cells for k-strongest, 3952 for CA-CFAR; else 4)
 static int detect_tile_width(int method, int n_cells) { return detect_lds(16, method, n_cells) + 256 <= (size_t)kLdsMax ? 16 : 4; }
 
-void launch_detect(const uint8_t* imgs, int n_frames, const rr_detect_config& cfg, int n_cells, int n_angles, int scroll,
-                   float theta_min, float theta_inc, double resolution, rr_radar_point* points, int max_points,
+void launch_detect(const uint8_t* imgs, int n_frames, const rr_detect_config& cfg, const PolarGrid& G, rr_radar_point* points, int max_points,
                    uint32_t* offsets, hipStream_t s)
 {
     DetectArgs A;
     A.method = cfg.method; A.guard = cfg.guard_cells; A.train = cfg.train_cells; A.k = cfg.k;
     A.min_intensity = cfg.min_intensity; A.min_bin = cfg.min_bin; A.cfar_scale = cfg.cfar_scale;
-    A.n_cells = n_cells; A.n_angles = n_angles; A.scroll = ((scroll % n_angles) + n_angles) % n_angles;
-    A.theta_min = theta_min; A.theta_inc = theta_inc; A.resolution = resolution;
+    A.G = G;
     A.max_points = points ? max_points : 0;
-    const int tw = detect_tile_width(cfg.method, n_cells);
-    A.vec = n_angles % tw == 0 && reinterpret_cast<uintptr_t>(imgs) % tw == 0;
+    const int tw = detect_tile_width(cfg.method, G.n_cells);
+    A.vec = G.n_angles % tw == 0 && reinterpret_cast<uintptr_t>(imgs) % tw == 0;
     if (tw == 16) {
         if (cfg.method == 0) launch_detect_tw<16, 0>(imgs, n_frames, points, offsets, A, s);
         else launch_detect_tw<16, 1>(imgs, n_frames, points, offsets, A, s);
@@ -349,14 +316,9 @@ void launch_detect(const uint8_t* imgs, int n_frames, const rr_detect_config& cf
     }
 }
 
-void launch_cartesian(const uint8_t* imgs, int n_frames, const rr_cartesian_config& cfg, int n_cells, int n_angles, int scroll,
-                      float theta_min, float theta_inc, float res, uint8_t* out, hipStream_t s)
+void launch_cartesian(const uint8_t* imgs, int n_frames, const rr_cartesian_config& cfg, const PolarGrid& G, uint8_t* out, hipStream_t s)
 {
-    CartArgs A;
-    A.width = cfg.width; A.pixel_size = cfg.pixel_size;
-    A.n_cells = n_cells; A.n_angles = n_angles; A.scroll = ((scroll % n_angles) + n_angles) % n_angles;
-    A.theta_min = theta_min; A.theta_inc = theta_inc; A.res = res;
-    A.aligned = reinterpret_cast<uintptr_t>(out) % 4 == 0;
+    const CartArgs A = { { cfg.width, cfg.pixel_size }, G, reinterpret_cast<uintptr_t>(out) % 4 == 0 };
     const size_t total = (size_t)n_frames * cfg.width * cfg.width;
     const size_t groups = std::min<size_t>((total + 1023) / 1024, 8192);
     if (cfg.interpolation == 0) hipLaunchKernelGGL(k_cartesian<0>, dim3((unsigned)groups), dim3(256), 0, s, imgs, out, total, A);

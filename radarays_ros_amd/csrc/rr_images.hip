@@ -524,10 +524,9 @@ int rr_simulate_batch_shift(rr_ctx* c, const float* poses, int n_frames, const u
     if (xcorr) RR_HIP(c, c->d_shift_conv_xcorr.ensure(n * ND));
     RR_HIP(c, hipMemcpyAsync(c->d_ref_img.p, ref_polar_u8, npx, hipMemcpyHostToDevice, c->stream));
     rc = rr_simulate_batch_device(c, poses, n_frames, c->d_param_imgs.p, c->stream); if (rc) return rc;
-    launch_cartesian(c->d_param_imgs.p, n_frames, *cfg, g.n_cells, g.n_angles, g.scroll_image, g.theta_min, g.theta_inc, (float)g.resolution,
-                     c->d_shift_in.p, c->stream);
-    launch_cartesian(c->d_ref_img.p, 1, *cfg, g.n_cells, g.n_angles, g.scroll_image, g.theta_min, g.theta_inc, (float)g.resolution,
-                     c->d_shift_ref.p, c->stream);
+    const PolarGrid G = polar_grid(g);
+    launch_cartesian(c->d_param_imgs.p, n_frames, *cfg, G, c->d_shift_in.p, c->stream);
+    launch_cartesian(c->d_ref_img.p, 1, *cfg, G, c->d_shift_ref.p, c->stream);
     std::vector<rr_shift_record> rec(n);
     rc = rr_shift_images_device(c, c->d_shift_in.p, n_frames, c->d_shift_ref.p, cfg->width, cfg->width, max_shift, rec.data(),
                                 xcorr ? reinterpret_cast<int64_t*>(c->d_shift_conv_xcorr.p) : nullptr, nullptr, c->stream); if (rc) return rc;   // synchronises the stream
@@ -684,10 +683,7 @@ int rr_detect_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_frames, const rr
 {
     int rc = check_detect(c, "rr_detect_device", d_imgs_u8, n_frames, cfg, d_points, max_points, d_offsets); if (rc) return rc;
     RR_HIP(c, hipSetDevice(c->device));
-    const rr_config& g = c->cfg;
-    hipStream_t s = stream_of(c, stream);
-    launch_detect(d_imgs_u8, n_frames, *cfg, g.n_cells, g.n_angles, g.scroll_image, g.theta_min, g.theta_inc, g.resolution,
-                  max_points > 0 ? d_points : nullptr, max_points, d_offsets, s);
+    launch_detect(d_imgs_u8, n_frames, *cfg, polar_grid(c->cfg), max_points > 0 ? d_points : nullptr, max_points, d_offsets, stream_of(c, stream));
     RR_HIP(c, hipGetLastError());
     return 0;
 }
@@ -717,10 +713,7 @@ int rr_polar_to_cartesian_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_fram
 {
     int rc = check_cartesian(c, "rr_polar_to_cartesian_device", d_imgs_u8, n_frames, cfg, d_cart_u8); if (rc) return rc;
     RR_HIP(c, hipSetDevice(c->device));
-    const rr_config& g = c->cfg;
-    hipStream_t s = stream_of(c, stream);
-    launch_cartesian(d_imgs_u8, n_frames, *cfg, g.n_cells, g.n_angles, g.scroll_image, g.theta_min, g.theta_inc, (float)g.resolution,
-                     d_cart_u8, s);
+    launch_cartesian(d_imgs_u8, n_frames, *cfg, polar_grid(c->cfg), d_cart_u8, stream_of(c, stream));
     RR_HIP(c, hipGetLastError());
     return 0;
 }
@@ -744,8 +737,7 @@ int rr_sweep_table_device(rr_ctx* c, const float* d_az_poses, const float* d_ref
 {
     int rc = check_sweep_table(c, "rr_sweep_table_device", d_az_poses, d_ref_poses, gain, n_frames, d_table, true); if (rc) return rc;
     RR_HIP(c, hipSetDevice(c->device));
-    const rr_config& g = c->cfg;
-    launch_sweep_table(d_az_poses, d_ref_poses, d_sensor_vel, gain, n_frames, g.n_angles, g.theta_min, g.theta_inc, d_table, stream_of(c, stream));
+    launch_sweep_table(d_az_poses, d_ref_poses, d_sensor_vel, gain, n_frames, polar_grid(c->cfg), d_table, stream_of(c, stream));
     RR_HIP(c, hipGetLastError());
     return 0;
 }
@@ -789,8 +781,7 @@ int rr_compensate_points_device(rr_ctx* c, const rr_radar_point* d_points, const
     int rc = check_compensate(c, "rr_compensate_points_device", d_points, d_offsets, n_frames, max_points, d_table, d_out, true); if (rc) return rc;
     if (max_points == 0) return 0;
     RR_HIP(c, hipSetDevice(c->device));
-    const rr_config& g = c->cfg;
-    launch_compensate_points(d_points, d_offsets, n_frames, max_points, d_table, d_out, g.n_angles, g.scroll_image, g.resolution, stream_of(c, stream));
+    launch_compensate_points(d_points, d_offsets, n_frames, max_points, d_table, d_out, polar_grid(c->cfg), stream_of(c, stream));
     RR_HIP(c, hipGetLastError());
     return 0;
 }
@@ -828,9 +819,7 @@ int rr_polar_to_cartesian_sweep_device(rr_ctx* c, const uint8_t* d_imgs_u8, int 
 {
     int rc = check_cartesian_sweep(c, "rr_polar_to_cartesian_sweep_device", d_imgs_u8, n_frames, cfg, d_table, iterations, d_cart_u8, true); if (rc) return rc;
     RR_HIP(c, hipSetDevice(c->device));
-    const rr_config& g = c->cfg;
-    launch_cartesian_sweep(d_imgs_u8, n_frames, *cfg, g.n_cells, g.n_angles, g.scroll_image, g.theta_min, g.theta_inc, (float)g.resolution, d_table,
-                           iterations, d_cart_u8, stream_of(c, stream));
+    launch_cartesian_sweep(d_imgs_u8, n_frames, *cfg, polar_grid(c->cfg), d_table, iterations, d_cart_u8, stream_of(c, stream));
     RR_HIP(c, hipGetLastError());
     return 0;
 }
@@ -936,8 +925,7 @@ int rr_annotate_labels_device(rr_ctx* c, const uint32_t* d_labels, const uint8_t
     const size_t need = note_scratch_bytes((size_t)n_frames, (size_t)n_objects, g.n_angles);
     if (scratch_bytes < need) return fail(c, -3, w + ": scratch of " + std::to_string(scratch_bytes) + " bytes, the call needs " + std::to_string(need));
     RR_HIP(c, hipSetDevice(c->device));
-    launch_notes(d_labels, d_imgs_u8, n_frames, (uint32_t)n_objects, extent_mask, g.n_cells, g.n_angles, g.scroll_image, g.theta_min, g.theta_inc,
-                 g.resolution, d_notes, d_skipped, d_scratch, stream_of(c, stream));
+    launch_notes(d_labels, d_imgs_u8, n_frames, (uint32_t)n_objects, extent_mask, polar_grid(g), d_notes, d_skipped, d_scratch, stream_of(c, stream));
     RR_HIP(c, hipGetLastError());
     return 0;
 }
@@ -991,9 +979,7 @@ int rr_polar_to_cartesian_labels_device(rr_ctx* c, const uint32_t* d_planes_u32,
     int rc = check_cartesian(c, "rr_polar_to_cartesian_labels_device", d_planes_u32, n_frames, cfg, d_cart_u32); if (rc) return rc;
     if (cfg->interpolation != 0) return fail(c, -3, "rr_polar_to_cartesian_labels_device: interpolation must be 0 (nearest): ids do not interpolate");
     RR_HIP(c, hipSetDevice(c->device));
-    const rr_config& g = c->cfg;
-    launch_cartesian_labels(d_planes_u32, n_frames, *cfg, g.n_cells, g.n_angles, g.scroll_image, g.theta_min, g.theta_inc, (float)g.resolution,
-                            d_cart_u32, stream_of(c, stream));
+    launch_cartesian_labels(d_planes_u32, n_frames, *cfg, polar_grid(c->cfg), d_cart_u32, stream_of(c, stream));
     RR_HIP(c, hipGetLastError());
     return 0;
 }

@@ -3,6 +3,7 @@
 #pragma once
 #include "../../include/radarays_mi355.h"
 #include "rr_device.h"
+#include "rr_polar.h"
 #include <hip/hip_ext.h>
 #include <string>
 
@@ -62,18 +63,16 @@ void launch_mat_limits(const float4* materials, size_t n, double* limits, hipStr
 void* trace0_kernel(bool spill, bool stackless);
 void launch_score(const uint8_t* imgs, const uint8_t* ref, size_t npx, int n_images, unsigned long long* sse, hipStream_t s);
 // rr_detect.hip (point clouds and Cartesian images)
-void launch_detect(const uint8_t* imgs, int n_frames, const rr_detect_config& cfg, int n_cells, int n_angles, int scroll,
-                   float theta_min, float theta_inc, double resolution, rr_radar_point* points, int max_points,
+void launch_detect(const uint8_t* imgs, int n_frames, const rr_detect_config& cfg, const PolarGrid& G, rr_radar_point* points, int max_points,
                    uint32_t* offsets, hipStream_t s);
-void launch_cartesian(const uint8_t* imgs, int n_frames, const rr_cartesian_config& cfg, int n_cells, int n_angles, int scroll,
-                      float theta_min, float theta_inc, float res, uint8_t* out, hipStream_t s);
+void launch_cartesian(const uint8_t* imgs, int n_frames, const rr_cartesian_config& cfg, const PolarGrid& G, uint8_t* out, hipStream_t s);
 // rr_deskew.hip (sweep compensation).  table [n_frames][n_angles], 16-byte aligned; n_angles * 32 bytes of LDS per workgroup of launch_cartesian_sweep
-void launch_sweep_table(const float* az_poses, const float* ref_poses, const float* sensor_vel, float gain, int n_frames, int n_angles,
-                        float theta_min, float theta_inc, rr_sweep_rec* table, hipStream_t s);
+void launch_sweep_table(const float* az_poses, const float* ref_poses, const float* sensor_vel, float gain, int n_frames, const PolarGrid& G,
+                        rr_sweep_rec* table, hipStream_t s);
 void launch_compensate_points(const rr_radar_point* points, const uint32_t* offsets, int n_frames, int max_points, const rr_sweep_rec* table,
-                              rr_radar_point* out, int n_angles, int scroll, double resolution, hipStream_t s);
-void launch_cartesian_sweep(const uint8_t* imgs, int n_frames, const rr_cartesian_config& cfg, int n_cells, int n_angles, int scroll, float theta_min,
-                            float theta_inc, float res, const rr_sweep_rec* table, int iterations, uint8_t* out, hipStream_t s);
+                              rr_radar_point* out, const PolarGrid& G, hipStream_t s);
+void launch_cartesian_sweep(const uint8_t* imgs, int n_frames, const rr_cartesian_config& cfg, const PolarGrid& G, const rr_sweep_rec* table,
+                            int iterations, uint8_t* out, hipStream_t s);
 // rr_icp.hip (scan matching).  acc: icp_scratch_words(n_frames) int64 words, zeroed by the first launch; recs and init 8-byte aligned
 void icp_tile_sizes(int* source_tile, int* target_tile);
 size_t icp_scratch_words(size_t n_frames);
@@ -82,12 +81,11 @@ void launch_icp(const rr_radar_point* points, const uint32_t* offsets, int n_fra
                 long long* acc, hipStream_t s);
 // rr_notes.hip (object annotations).  scratch: note_scratch_bytes, 16-byte aligned like notes; every word of it, of notes and of skipped is written by the launches
 size_t note_scratch_bytes(size_t n_frames, size_t n_objects, int n_angles);
-void launch_notes(const uint32_t* labels, const uint8_t* imgs, int n_frames, uint32_t n_objects, uint32_t extent_mask, int n_cells, int n_angles,
-                  int scroll, float theta_min, float theta_inc, double resolution, rr_object_note* notes, uint32_t* skipped, void* scratch, hipStream_t s);
+void launch_notes(const uint32_t* labels, const uint8_t* imgs, int n_frames, uint32_t n_objects, uint32_t extent_mask, const PolarGrid& G,
+                  rr_object_note* notes, uint32_t* skipped, void* scratch, hipStream_t s);
 void launch_label_points(const rr_radar_point* points, const uint32_t* offsets, int n_frames, int max_points, const uint32_t* labels, const uint32_t* faces,
                          const float* vel, uint32_t* p_labels, uint32_t* p_faces, float* p_vel, int n_cells, int n_angles, hipStream_t s);
-void launch_cartesian_labels(const uint32_t* planes, int n_frames, const rr_cartesian_config& cfg, int n_cells, int n_angles, int scroll, float theta_min,
-                             float theta_inc, float res, uint32_t* out, hipStream_t s);
+void launch_cartesian_labels(const uint32_t* planes, int n_frames, const rr_cartesian_config& cfg, const PolarGrid& G, uint32_t* out, hipStream_t s);
 // rr_metrics.hip (images against one reference image).  hist_shape 0: workgroup-private LDS histograms, 1: global atomics
 void launch_joint_hist(const uint8_t* imgs, const uint8_t* ref, size_t npx, int n_images, uint32_t* hist, int hist_shape, hipStream_t s);
 int ssim_blocks(int n_cells, int n_angles, int win);          // workgroups (= f64 partials) per image of launch_ssim

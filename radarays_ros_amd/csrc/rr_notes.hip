@@ -13,7 +13,7 @@
 //                        a max-scan of the last occupied azimuth carries the gap across words), the packed peak key and the float keys
 //                        unpacked, the record written as five 16-B stores
 //   k_label_points       one thread per written point: the label, face and range rate under (bin, column)
-//   k_cartesian_labels   one thread per output pixel: the nearest rule of rr_detect.hip's k_cartesian, expression for expression, on uint32
+//   k_cartesian_labels   one thread per output pixel: the nearest rule of rr_detect.hip's k_cartesian (rr_polar.h) on uint32
 //
 // Every reduction is over integers or a min / max (add, min, max, or; floats through the order-preserving integer mapping fkey), so a
 // record does not depend on the order in which tiles and lanes arrive.
@@ -25,6 +25,7 @@
 #include "../../include/radarays_mi355.h"
 #include "rr_device.h"
 #include "rr_launch.h"
+#include "rr_polar.h"
 
 #include <algorithm>
 
@@ -49,10 +50,8 @@ __device__ inline uint32_t funkey_bits(uint32_t k) { return k ^ ((k >> 31) ? 0x8
 constexpr uint32_t kKeyPosInf = 0xFF800000u, kKeyNegInf = 0x007FFFFFu;      // fkey(+inf), fkey(-inf)
 
 struct NoteArgs {
-    int n_cells, n_angles, scroll;      // scroll in [0, n_angles)
+    PolarGrid G;
     uint32_t n_objects, extent_mask;
-    float theta_min, theta_inc;
-    double resolution;
     int vec;                            // rows are read as 16-B label words and 4-B image words
     int occ_words, n_chunks;
 };
@@ -85,7 +84,7 @@ __device__ inline void merge_global(uint32_t* acc_base, uint32_t* occ_base, size
     if (p.sum) atomicAdd(reinterpret_cast<unsigned long long*>(acc + A_SUM), (unsigned long long)p.sum);
     // tile column c holds azimuth a0 + c below `nowrap`, a0 + c - n_angles from there on
     uint32_t* row = occ_base + rec * (size_t)A.occ_words;
-    const int nowrap = A.n_angles - a0;
+    const int nowrap = A.G.n_angles - a0;
     const uint32_t lo = nowrap >= 32 ? p.occ : p.occ & ((1u << nowrap) - 1u);
     const uint32_t hi = nowrap >= 32 ? 0u : p.occ >> nowrap;
     const unsigned long long w = (unsigned long long)lo << (a0 & 31);
@@ -128,8 +127,8 @@ __global__ void __launch_bounds__(kNoteTB) k_note_accum(const uint32_t* labels, 
 
     const int f = blockIdx.y;
     const int tile = blockIdx.x / A.n_chunks, chunk = blockIdx.x - tile * A.n_chunks;
-    const int col0 = tile * kNoteTW, row0 = chunk * kNoteRows, row_end = min(A.n_cells, row0 + kNoteRows);
-    const int a0 = col0 - A.scroll < 0 ? col0 - A.scroll + A.n_angles : col0 - A.scroll;
+    const int col0 = tile * kNoteTW, row0 = chunk * kNoteRows, row_end = min(A.G.n_cells, row0 + kNoteRows);
+    const int a0 = az_of_col(A.G, col0);
     const size_t rec0 = (size_t)f * A.n_objects;
     const int c0 = 4 * (threadIdx.x & 7), rr = threadIdx.x >> 3;
 
@@ -138,9 +137,9 @@ __global__ void __launch_bounds__(kNoteTB) k_note_accum(const uint32_t* labels, 
     float cs[4], sn[4];
 #pragma unroll
     for (int e = 0; e < 4; e++) {
-        valid[e] = col0 + c0 + e < A.n_angles;
-        az[e] = a0 + c0 + e >= A.n_angles ? a0 + c0 + e - A.n_angles : a0 + c0 + e;
-        const float theta = A.theta_min + (float)az[e] * A.theta_inc;
+        valid[e] = col0 + c0 + e < A.G.n_angles;
+        az[e] = a0 + c0 + e >= A.G.n_angles ? a0 + c0 + e - A.G.n_angles : a0 + c0 + e;
+        const float theta = az_theta(A.G, az[e]);
         cs[e] = cosf(theta); sn[e] = sinf(theta);
     }
 
@@ -171,9 +170,9 @@ __global__ void __launch_bounds__(kNoteTB) k_note_accum(const uint32_t* labels, 
     Part cur;
     part_reset(cur, kNoId);
     uint32_t n_skip = 0;
-    const size_t plane = (size_t)f * A.n_cells * A.n_angles;
+    const size_t plane = (size_t)f * A.G.n_cells * A.G.n_angles;
     for (int row = row0 + rr; row < row_end; row += kNoteTB / 8) {
-        const size_t at = plane + (size_t)row * A.n_angles + col0 + c0;
+        const size_t at = plane + (size_t)row * A.G.n_angles + col0 + c0;
         uint32_t lab[4] = { RR_LABEL_NONE, RR_LABEL_NONE, RR_LABEL_NONE, RR_LABEL_NONE };
         uint32_t z4 = 0;
         if (A.vec) {
@@ -190,7 +189,7 @@ __global__ void __launch_bounds__(kNoteTB) k_note_accum(const uint32_t* labels, 
                     if (imgs) z4 |= (uint32_t)imgs[at + e] << (8 * e);
                 }
         }
-        const float r = (float)(((double)row + 0.5) * A.resolution);
+        const float r = bin_range(A.G, row);
 #pragma unroll
         for (int e = 0; e < 4; e++) {
             const uint32_t L = lab[e];
@@ -318,39 +317,22 @@ __global__ void __launch_bounds__(256) k_label_points(const rr_radar_point* poin
 }
 
 // ---- Cartesian instance mask ----
-struct CartLabelArgs {
-    int width;
-    float pixel_size;
-    int n_cells, n_angles, scroll;
-    float theta_min, theta_inc, res;
-};
+struct CartLabelArgs { CartGrid C; PolarGrid G; };
 
-// k_cartesian's nearest pixel (rr_detect.hip: cart_pixel<0>), expression for expression; RR_LABEL_NONE beyond the last bin
+// the nearest pixel of rr_detect.hip's k_cartesian (the same leaves of rr_polar.h); RR_LABEL_NONE beyond the last bin
 __device__ inline uint32_t cart_label(const uint32_t* plane, const CartLabelArgs& A, int i, int j)
 {
-    const float cc = (float)(A.width - 1) * 0.5f;
-    const float x = (cc - (float)i) * A.pixel_size, y = (cc - (float)j) * A.pixel_size;
-    const float rho = sqrtf(x * x + y * y), phi = atan2f(y, x);
-    float v = rho / A.res - 0.5f;
-    if (!(v <= (float)A.n_cells - 0.5f)) return RR_LABEL_NONE;
-    v = fmaxf(v, 0.0f);
-    const float na = (float)A.n_angles;
-    float u = fmodf((phi - A.theta_min) / A.theta_inc, na);
-    if (u < 0.0f) u += na;
-    if (u >= na) u -= na;
-    if (!(u >= 0.0f && u < na)) u = 0.0f;
-    int a = (int)rintf(u);
-    if (a >= A.n_angles) a -= A.n_angles;
-    const int b = min((int)rintf(v), A.n_cells - 1);
-    int col = a + A.scroll;
-    if (col >= A.n_angles) col -= A.n_angles;
-    return plane[(size_t)b * A.n_angles + col];
+    const V3 p = pixel_xy(A.C, i, j);
+    const float rho = sqrtf(p.x * p.x + p.y * p.y), phi = atan2f(p.y, p.x);
+    float v;
+    if (!range_coord(A.G, rho, &v)) return RR_LABEL_NONE;
+    return polar_nearest(plane, A.G, az_coord(A.G, phi), v);
 }
 
 __global__ void __launch_bounds__(256) k_cartesian_labels(const uint32_t* planes, uint32_t* out, size_t total, CartLabelArgs A)
 {
-    const uint32_t w = (uint32_t)A.width, wsq = w * w;
-    const size_t npx = (size_t)A.n_cells * A.n_angles;
+    const uint32_t w = (uint32_t)A.C.width, wsq = w * w;
+    const size_t npx = (size_t)A.G.n_cells * A.G.n_angles;
     for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (size_t)gridDim.x * blockDim.x) {
         const size_t f = q / wsq;
         const uint32_t rem = (uint32_t)(q - f * wsq);
@@ -370,13 +352,13 @@ size_t note_scratch_bytes(size_t n_frames, size_t n_objects, int n_angles)
     return (n_rec * (kAccWords * 4 + (size_t)occ_words_of(n_angles) * 4) + 15) & ~(size_t)15;
 }
 
-void launch_notes(const uint32_t* labels, const uint8_t* imgs, int n_frames, uint32_t n_objects, uint32_t extent_mask, int n_cells, int n_angles,
-                  int scroll, float theta_min, float theta_inc, double resolution, rr_object_note* notes, uint32_t* skipped, void* scratch, hipStream_t s)
+void launch_notes(const uint32_t* labels, const uint8_t* imgs, int n_frames, uint32_t n_objects, uint32_t extent_mask, const PolarGrid& G,
+                  rr_object_note* notes, uint32_t* skipped, void* scratch, hipStream_t s)
 {
+    const int n_cells = G.n_cells, n_angles = G.n_angles;
     NoteArgs A;
-    A.n_cells = n_cells; A.n_angles = n_angles; A.scroll = ((scroll % n_angles) + n_angles) % n_angles;
+    A.G = G;
     A.n_objects = n_objects; A.extent_mask = extent_mask;
-    A.theta_min = theta_min; A.theta_inc = theta_inc; A.resolution = resolution;
     A.vec = n_angles % 4 == 0 && reinterpret_cast<uintptr_t>(labels) % 16 == 0 && reinterpret_cast<uintptr_t>(imgs) % 4 == 0;
     A.occ_words = occ_words_of(n_angles); A.n_chunks = (n_cells + kNoteRows - 1) / kNoteRows;
     const size_t n_rec = (size_t)n_frames * n_objects, n_occ = n_rec * (size_t)A.occ_words;
@@ -398,13 +380,9 @@ void launch_label_points(const rr_radar_point* points, const uint32_t* offsets, 
     hipLaunchKernelGGL(k_label_points, grid, dim3(256), 0, s, points, offsets, max_points, labels, faces, vel, p_labels, p_faces, p_vel, n_cells, n_angles);
 }
 
-void launch_cartesian_labels(const uint32_t* planes, int n_frames, const rr_cartesian_config& cfg, int n_cells, int n_angles, int scroll, float theta_min,
-                             float theta_inc, float res, uint32_t* out, hipStream_t s)
+void launch_cartesian_labels(const uint32_t* planes, int n_frames, const rr_cartesian_config& cfg, const PolarGrid& G, uint32_t* out, hipStream_t s)
 {
-    CartLabelArgs A;
-    A.width = cfg.width; A.pixel_size = cfg.pixel_size;
-    A.n_cells = n_cells; A.n_angles = n_angles; A.scroll = ((scroll % n_angles) + n_angles) % n_angles;
-    A.theta_min = theta_min; A.theta_inc = theta_inc; A.res = res;
+    const CartLabelArgs A = { { cfg.width, cfg.pixel_size }, G };
     const size_t total = (size_t)n_frames * cfg.width * cfg.width;
     const size_t groups = std::min<size_t>((total + 255) / 256, 16384);
     hipLaunchKernelGGL(k_cartesian_labels, dim3((unsigned)groups), dim3(256), 0, s, planes, out, total, A);

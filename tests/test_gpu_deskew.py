@@ -223,6 +223,34 @@ def test_identity_table_reproduces_the_plain_conversion(width, bilinear, n_angle
     assert want.any()
 
 
+@pytest.mark.parametrize("n_angles", [5, 64])
+@pytest.mark.parametrize("width", [2, 33])
+def test_the_three_resamplers_agree_off_the_default_geometry(width, n_angles):
+    """the plain, the identity-sweep and the label resampler share one geometry (rr_polar.h); held here where the identity test above and
+    tests/test_gpu_notes.py's labels against the u8 resampler do not look: theta_min off zero, a counter-clockwise sweep, the last scroll,
+    five azimuths, 37 cells, a 2 x 2 image.  At width 2 the four pixels lie at one range: the second pixel size puts them beyond the last bin"""
+    n, n_cells = 2, 37
+    ctx = native.Context(0)
+    ctx.set_config(params.kaist_preset(n_cells=n_cells, scroll_image=n_angles - 1), n_angles, theta_min=0.7, theta_inc=2 * np.pi / n_angles)
+    g = ctx._rrcfg
+    assert g.theta_inc > 0 and g.scroll_image == n_angles - 1 and abs(g.theta_min - 0.7) < 1e-6
+    u8 = np.random.RandomState(width + n_angles).randint(1, 256, (n, n_cells, n_angles)).astype(np.uint8)      # no zero: 0 is beyond range
+    ident = native.identity_sweep_table(n, n_angles)
+    seen = []
+    for reach in (2.2, 3.2):                                            # the corners, then at width 2 every pixel, beyond the last bin
+        ps = reach * n_cells * g.resolution / width
+        near = ctx.polar_to_cartesian(u8, width, ps, False)
+        lab = ctx.polar_to_cartesian_labels(u8.astype(np.uint32), width, ps)
+        beyond = lab == native.LABEL_NONE
+        assert np.array_equal(np.where(beyond, 0, lab), near.astype(np.uint32)) and np.array_equal(beyond, near == 0)
+        bil = ctx.polar_to_cartesian(u8, width, ps, True)
+        for it in (1, 3):
+            assert ctx.polar_to_cartesian_sweep(u8, ident, width, ps, False, it).tobytes() == near.tobytes(), (reach, it)
+            assert ctx.polar_to_cartesian_sweep(u8, ident, width, ps, True, it).tobytes() == bil.tobytes(), (reach, it)
+        seen.append(beyond)
+    assert any(b.any() for b in seen) and not all(b.all() for b in seen)
+
+
 # ---- 4. a real table ---------------------------------------------------------------------------------------------------
 _cart = {}
 
