@@ -2,10 +2,12 @@
 // rm::import_embree_map's Embree build, src/radar_simulator.cpp:149, for maps that must load
 // in milliseconds instead of seconds).
 //
-//   0. early split clipping (Ernst & Greiner 2007): a face much larger than its neighbours is cut along a grid of
-//      cell size L into references {clipped box, face}; L is the smallest cell that keeps the reference count
-//      within +25 % (bisection over a counting kernel).  Without it one 15 m building face inflates every
-//      Morton-neighbourhood of 0.2 m terrain triangles it is sorted into.                 k_split<false/true>
+//   0. early split clipping (Ernst & Greiner 2007): a face much larger than its neighbours -- its longest box side
+//      more than twice the mean over all faces (k_side) -- is cut along a grid of cell size L into references
+//      {clipped box, face}; L is the smallest cell that keeps the reference count within +25 % (bisection over a
+//      counting kernel).  Without it one 15 m building face inflates every Morton-neighbourhood of 0.2 m terrain
+//      triangles it is sorted into.  A face of ordinary size is never cut: its parts would bound nothing
+//      tighter, and the budget is the large faces'.                               k_side, k_split<false/true>
 //   1. per-reference bounds + 63-bit Morton code of the centroid (cubic cells: one scale for all axes)   k_prim
 //   2. rocprim radix sort of (code, face)                             rocprim::radix_sort_pairs
 //   3. Karras 2012 binary radix tree over the sorted codes           k_karras
@@ -86,12 +88,38 @@ __device__ inline bool clip_tri_box(const float* a, const float* b, const float*
     return true;
 }
 
+// sum over the faces of (longest box side / scene extent) in 32-bit fixed point: integer adds, so the sum -- and the tree --
+// does not depend on the order the blocks arrive in.  2^28 faces of at most 2^32 each stay below 2^64.
+__global__ void k_side(const float* __restrict__ verts, const uint32_t* __restrict__ faces, uint32_t nf, float sinv,
+                       unsigned long long* __restrict__ sum)
+{
+    __shared__ unsigned long long part[256];
+    const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long q = 0;
+    if (f < nf) {
+        const float* a = verts + 3 * (size_t)faces[3 * (size_t)f + 0];
+        const float* b = verts + 3 * (size_t)faces[3 * (size_t)f + 1];
+        const float* c = verts + 3 * (size_t)faces[3 * (size_t)f + 2];
+        float side = 0.f;
+        for (int k = 0; k < 3; k++) side = fmaxf(side, fmaxf(a[k], fmaxf(b[k], c[k])) - fminf(a[k], fminf(b[k], c[k])));
+        q = (unsigned long long)fminf(side * sinv * 4294967296.0f, 4294967296.0f);
+    }
+    part[threadIdx.x] = q;
+    __syncthreads();
+    for (unsigned int s = blockDim.x / 2; s > 0; s >>= 1) {
+        if (threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) atomicAdd(sum, part[0]);
+}
+
 constexpr int kMaxCellsPerAxis = 24;     // a face is cut into at most 24 cells per axis (its own coarser grid beyond that)
 
 // EMIT = false: count[f] = references face f yields for cell size L; EMIT = true: write them at offset[f]
+// A face whose longest box side is at most min_side is kept whole.
 template <bool EMIT>
 __global__ void k_split(const float* __restrict__ verts, const uint32_t* __restrict__ faces, uint32_t nf, float L, float3 slo,
-                        uint32_t* __restrict__ count, const uint32_t* __restrict__ offset,
+                        float min_side, uint32_t* __restrict__ count, const uint32_t* __restrict__ offset,
                         Box6* __restrict__ rbox, uint32_t* __restrict__ rface)
 {
     const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
@@ -104,9 +132,11 @@ __global__ void k_split(const float* __restrict__ verts, const uint32_t* __restr
     int i0[3], nc[3]; float cell[3];
     const float org[3] = { slo.x, slo.y, slo.z };       // the grid starts at the scene's lower corner
     long total = 1;
+    float side = 0.f;
     for (int k = 0; k < 3; k++) {
         cell[k] = L;
         const float ext = bb.hi[k] - bb.lo[k];
+        side = fmaxf(side, ext);
         if (ext > L * (float)kMaxCellsPerAxis) cell[k] = ext / (float)kMaxCellsPerAxis;
         i0[k] = (int)floorf((bb.lo[k] - org[k]) / cell[k]);
         nc[k] = (int)floorf((bb.hi[k] - org[k]) / cell[k]) - i0[k] + 1;
@@ -115,7 +145,7 @@ __global__ void k_split(const float* __restrict__ verts, const uint32_t* __restr
     }
     uint32_t n = 0;
     const uint32_t base = EMIT ? offset[f] : 0u;
-    if (total == 1) {
+    if (total == 1 || !(side > min_side)) {
         if (EMIT) { rbox[base] = bb; rface[base] = f; }
         n = 1;
     } else {
@@ -342,8 +372,20 @@ bool build_bvh4_gpu(const float* verts, size_t nv, const uint32_t* faces, size_t
     size_t scan_bytes = 0;
     LB_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, d_count.p, d_offset.p, 0u, nf, rocprim::plus<uint32_t>(), stream));
     LB_HIP(d_scan_tmp.alloc(scan_bytes));
+    // only faces more than twice as long as the mean face are cut
+    float min_side = 0.f;
+    if (ext > 0.f) {
+        Tmp<unsigned long long> d_sum;
+        unsigned long long sum = 0;
+        LB_HIP(d_sum.alloc(1));
+        LB_HIP(hipMemsetAsync(d_sum.p, 0, sizeof(unsigned long long), stream));
+        hipLaunchKernelGGL(k_side, dim3(nfb), dim3(TB), 0, stream, d_verts.p, d_faces.p, (uint32_t)nf, s1, d_sum.p);
+        LB_HIP(hipMemcpyAsync(&sum, d_sum.p, sizeof(sum), hipMemcpyDeviceToHost, stream));
+        LB_HIP(hipStreamSynchronize(stream));
+        min_side = (float)(2.0 * ((double)sum / (double)nf / 4294967296.0) * (double)ext);
+    }
     auto refs_for = [&](float L, size_t& total) -> bool {
-        hipLaunchKernelGGL((k_split<false>), dim3(nfb), dim3(TB), 0, stream, d_verts.p, d_faces.p, (uint32_t)nf, L, slo, d_count.p,
+        hipLaunchKernelGGL((k_split<false>), dim3(nfb), dim3(TB), 0, stream, d_verts.p, d_faces.p, (uint32_t)nf, L, slo, min_side, d_count.p,
                            (const uint32_t*)nullptr, (Box6*)nullptr, (uint32_t*)nullptr);
         if (rocprim::exclusive_scan(d_scan_tmp.p, scan_bytes, d_count.p, d_offset.p, 0u, nf, rocprim::plus<uint32_t>(), stream) != hipSuccess) return false;
         uint32_t last_off = 0, last_cnt = 0;
@@ -370,7 +412,7 @@ bool build_bvh4_gpu(const float* verts, size_t nv, const uint32_t* faces, size_t
     if (n_refs < nf || n_refs > ref_limit + nf) { err = "gpu builder: internal error (reference count)"; return false; }
     const int n = (int)n_refs;
     LB_HIP(d_pbox.alloc(n_refs)); LB_HIP(d_rface.alloc(n_refs));
-    hipLaunchKernelGGL((k_split<true>), dim3(nfb), dim3(TB), 0, stream, d_verts.p, d_faces.p, (uint32_t)nf, L, slo, (uint32_t*)nullptr,
+    hipLaunchKernelGGL((k_split<true>), dim3(nfb), dim3(TB), 0, stream, d_verts.p, d_faces.p, (uint32_t)nf, L, slo, min_side, (uint32_t*)nullptr,
                        (const uint32_t*)d_offset.p, d_pbox.p, d_rface.p);
 
     LB_HIP(d_vals_in.alloc(n_refs)); LB_HIP(d_vals.alloc(n_refs));

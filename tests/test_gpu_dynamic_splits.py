@@ -18,22 +18,9 @@ import numpy as np
 import pytest
 
 import dynamic_ref as R
+from common import assert_trace_equals_brute_force
 
 gpu = pytest.mark.gpu
-
-
-def assert_trace_equals_brute_force(c, st, builder, step):
-    """t as f32 bits, the face id and the misses, for every ray; the message names the first ray that differs"""
-    t, face = c.debug_trace(st["o"], st["d"])
-    want_t, want_f = st["t"], st["face"]
-    hit = want_t >= 0
-    bad = np.where(hit, (t.view(np.uint32) != want_t.view(np.uint32)) | (face != want_f), ~(t < 0))
-    if bad.any():
-        i = int(np.nonzero(bad)[0][0])
-        pytest.fail("builder %s, step %s (state %s): %d of %d rays differ; ray %d got (t %r, face %d) wanted (t %r, face %d) "
-                    "origin %r direction %r" % (builder, step, st["name"], int(bad.sum()), len(bad), i, float(t[i]), int(face[i]),
-                                                 float(want_t[i]), int(want_f[i]), st["o"][i].tolist(), st["d"][i].tolist()))
-    return t, face
 
 
 # ---- the reference alone: every state, its rays, and what keeps the GPU tests from being vacuous ------------------------
