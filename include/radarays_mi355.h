@@ -1104,6 +1104,79 @@ int rr_register_points(rr_ctx* ctx, const rr_radar_point* points, const uint32_t
 /* the blocking of k_icp_pass: source points per workgroup and (x, y) pairs per LDS tile of the target (tests put counts at their edges) */
 void rr_icp_tile_sizes(int* source_tile, int* target_tile);
 
+/* ---- likelihood field: exact distance map and pose-batch scoring (rr_field.hip) ------------------------------------------
+ * The sensor model of a particle filter, and of a dense search over a lattice of (x, y, yaw): very many pose hypotheses for ONE observed
+ * scan scored against a map.  The map's points are rasterised once, the exact Euclidean distance transform is taken once, and a hypothesis
+ * then costs one table look-up per point.  The reference has no such step: parity is UNPINNED and everything below is the build's own
+ * definition (a numpy restatement in tests/field_ref.py checks the kernels bit for bit).  All f32 arithmetic is un-fused; every result is
+ * an integer and independent of order.
+ * POSE CONVENTION, stated once: a state (c, s, tx, ty) maps a cloud's sensor frame into the MAP frame, q = [c -s; s c] p + (tx, ty).  The
+ * rasteriser's states place keyframe clouds in the map; a hypothesis state of rr_score_poses places the observed scan in the map.
+ * GRID.  rr_field_config gives the shape.  The cell of a point (x, y) in the map frame:
+ *     u = (x - x0) / cell      v = (y - y0) / cell                                    in f32
+ *     the point is IN GRID iff u and v are finite, u >= 0 && u < (float)width and v >= 0 && v < (float)height; the comparisons are made
+ *     in float, before any conversion to int
+ *     ix = (int)floorf(u)      iy = (int)floorf(v)      linear index = iy * width + ix
+ * 1. rr_rasterize_points[_device]: clouds into an occupancy grid.  The clouds are laid out as rr_detect_device /
+ *    rr_compensate_points_device write them; the count of frame f is min(d_offsets[f][n_angles], max_points), read on the device; z,
+ *    intensity, column and bin are ignored.  d_states has the layout and meaning of rr_register_points_device's d_init: (c, s, tx, ty) f64
+ *    per frame, source frame into map frame; NULL means the identity.  States are used as given, rounded to f32 (cf, sf, txf, tyf); there
+ *    is no normalisation here (a record of rr_register_points is already normalised: its first 32 bytes are a state).  The mapping is
+ *    step 1 of the scan matcher:
+ *        px = (cf*x - sf*y) + txf            py = (sf*x + cf*y) + tyf
+ *    Every point that is IN GRID writes 1 into its cell; a point whose transformed coordinate is not finite is skipped.  The call only
+ *    ever writes ones, into a buffer that the caller zeroed: several calls accumulate a map from keyframes, whatever their order.
+ * 2. rr_distance_field[_device]: the exact saturated squared distance transform.  A cell is occupied iff occ >= threshold (so a thresholded
+ *    Cartesian image from rr_polar_to_cartesian is a valid map as well).  With cap2 = max_dist * max_dist:
+ *        field[iy][ix] = min(cap2, min over occupied cells (jx, jy) of (ix-jx)^2 + (iy-jy)^2)
+ *    The minimum is an exact integer; an empty map is cap2 everywhere.  d_field_u16 must not alias d_occ_u8.
+ * 3. rr_score_poses[_device]: the hot path.  The scan is ONE cloud, d_points[0 .. min(*d_count, max_points)), its count read on the device
+ *    (a caller passes &offsets[g][n_angles] of a detected frame); it is shared by all hypotheses.  d_states [n_hyp][4] is f32 (c, s, tx, ty),
+ *    used as given: no normalisation and no trigonometry on the device.  For hypothesis h and point i: the mapping above in f32, the
+ *    cell rule, the look-up, and three integer sums into one rr_field_rec:
+ *        sum_d2 over ALL points of the scan: the field value of an IN GRID point, cap2 for any other point
+ *        n_in   the points IN GRID                    n_hit  the points IN GRID whose field value <= gate * gate
+ *    A state that holds a NaN makes every point "not IN GRID": the hypothesis costs count * cap2 and no flag is needed.  With at most
+ *    65,536 points sum_d2 < 2^33.  A count of 0 gives all-zero records.  Lower sum_d2 is better; turning it into a likelihood, e.g.
+ *    exp(-sum_d2 * cell^2 / (2 sigma^2)), is the caller's job on the host.
+ * The device forms enqueue on `stream` (NULL: the context's) with no host round trip, and use NO context-owned memory at all: they may run on
+ * any stream beside batches in flight, and calls on different streams may overlap.  rr_rasterize_points_device is one launch,
+ * rr_distance_field_device two (columns, rows), rr_score_poses_device one.  The host forms stage through context-owned buffers and are
+ * synchronous; rr_rasterize_points reads occ_u8 as well as writing it (it accumulates), and rr_score_poses takes the scan's count as a value.
+ * Refused with a message and nothing written: -1 for a null ctx; -2 for the rasteriser without a config (n_angles is the offsets' stride);
+ * -3 for a null required buffer, a config field outside its stated range or a non-finite cell, x0 or y0, n_frames outside 1..65535,
+ * max_points outside 0..65536, n_hyp outside 1..2^22, threshold outside 1..255, d_states misaligned for its element type (8 bytes for the
+ * rasteriser's f64, 4 for the scorer's f32) or d_recs not 8-byte aligned. */
+typedef struct rr_field_config {   /* 32 B */
+    int32_t width, height;   /* cells, 1..4096 each */
+    float   cell;            /* metres per cell, finite, > 0 */
+    float   x0, y0;          /* map-frame coordinate of the low corner of cell (ix = 0, iy = 0), finite */
+    int32_t max_dist;        /* saturation in cells, 1..255; cap2 = max_dist * max_dist <= 65025 */
+    int32_t gate;            /* 0..max_dist: a point is a HIT iff its field value <= gate * gate */
+    int32_t reserved_;
+} rr_field_config;
+typedef struct rr_field_rec {  /* 16 B */
+    uint64_t sum_d2;   /* over ALL points of the scan: the field value of an IN GRID point, cap2 for any other point */
+    uint32_t n_in;     /* points IN GRID */
+    uint32_t n_hit;    /* points IN GRID whose field value <= gate * gate */
+} rr_field_rec;
+int rr_rasterize_points_device(rr_ctx* ctx, const rr_radar_point* d_points, const uint32_t* d_offsets /*[n][n_angles+1]*/, int n_frames,
+                               int max_points, const double* d_states_or_NULL /*[n][4]*/, const rr_field_config* cfg,
+                               uint8_t* d_occ_u8 /*[height][width]*/, void* stream);
+int rr_rasterize_points(rr_ctx* ctx, const rr_radar_point* points, const uint32_t* offsets, int n_frames, int max_points,
+                        const double* states_or_NULL, const rr_field_config* cfg, uint8_t* occ_u8);     /* host buffers, synchronous */
+int rr_distance_field_device(rr_ctx* ctx, const uint8_t* d_occ_u8, int threshold /*1..255*/, const rr_field_config* cfg,
+                             uint16_t* d_field_u16 /*[height][width]*/, void* stream);
+int rr_distance_field(rr_ctx* ctx, const uint8_t* occ_u8, int threshold, const rr_field_config* cfg, uint16_t* field_u16);   /* host buffers */
+int rr_score_poses_device(rr_ctx* ctx, const rr_radar_point* d_points, const uint32_t* d_count, int max_points,
+                          const float* d_states /*[n_hyp][4]: c, s, tx, ty*/, int n_hyp /*1..2^22*/, const uint16_t* d_field_u16,
+                          const rr_field_config* cfg, rr_field_rec* d_recs /*[n_hyp]*/, void* stream);
+int rr_score_poses(rr_ctx* ctx, const rr_radar_point* points, uint32_t count, int max_points, const float* states, int n_hyp,
+                   const uint16_t* field_u16, const rr_field_config* cfg, rr_field_rec* recs);           /* host buffers, synchronous */
+/* the blocking of the kernels: points a wave of k_field_score takes per step, hypotheses per workgroup of it, cells of a row per sweep of
+ * the transform's row pass (tests put counts and sizes at their edges) */
+void rr_field_tile_sizes(int* points_tile, int* hyps_per_group, int* row_tile);
+
 /* ---- several GPUs of one node behind one object (SURVEY.md §8b "Threading", §8e) -------------------------
  * The reference creates ONE backend object per process (src/radar_simulator.cpp:145-176) and fans out inside it
  * (OpenMP over azimuths, RadarCPU.cpp:155).  rr_multi is that object for n GPUs: one rr_ctx per device, mesh and

@@ -553,6 +553,36 @@ public:
         for (int k = 0; k < 3; k++) out[4 + k] = (float)(pose7[4 + k] + v[k] + 2.0 * (w * uv[k] + uuv[k]));
         return out;
     }
+    // Likelihood field (rr_field.hip; include/radarays_mi355.h): the map that keyframe clouds make (detect() of simulated images), each
+    // under its state -- [n][4] = c s tx ty, or empty for the identity -- as the exact saturated squared distance field [height][width].
+    // Pose convention: a state maps a cloud's sensor frame into the map frame, q = [c -s; s c] p + (tx, ty).  Empty on error
+    std::vector<uint16_t> buildLikelihoodField(const std::vector<std::vector<rr_radar_point>>& clouds, const std::vector<double>& states,
+                                               const rr_field_config& cfg)
+    {
+        std::vector<uint16_t> field;
+        if (!push()) return field;
+        if (!marshal::build_field(m_ctx, clouds, states, m_n_angles, cfg, field)) {
+            if (clouds.empty() || (!states.empty() && states.size() != 4 * clouds.size())) m_err = "buildLikelihoodField: no cloud, or states is not [n][4]";
+            else fail();
+            field.clear();
+        }
+        return field;
+    }
+    // one observed scan against hypothesis states [n][4] f32 (each the scan's sensor frame into the map frame) and a field of
+    // buildLikelihoodField: one rr_field_rec per hypothesis, lower sum_d2 is better.  Empty on error
+    std::vector<rr_field_rec> scorePoses(const std::vector<rr_radar_point>& scan, const std::vector<float>& states, const std::vector<uint16_t>& field,
+                                         const rr_field_config& cfg)
+    {
+        std::vector<rr_field_rec> recs;
+        if (!push()) return recs;
+        if (!marshal::score_poses(m_ctx, scan, states, field, cfg, recs)) {
+            if (states.empty() || states.size() % 4 || cfg.width < 1 || cfg.height < 1 || field.size() != (size_t)cfg.width * (size_t)cfg.height)
+                m_err = "scorePoses: states must be [n][4] and the field [height][width]";
+            else fail();
+            recs.clear();
+        }
+        return recs;
+    }
     const rr_stats& lastStats() const { return m_stats; }
 
 private:

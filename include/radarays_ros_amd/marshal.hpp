@@ -225,4 +225,38 @@ inline bool annotate_chunks(rr_ctx* ctx, const float* poses, size_t n, size_t n_
     return true;
 }
 
+// likelihood field (rr_field_config, rr_field_rec): n clouds, each under its state (c, s, tx, ty: sensor frame into the map frame; states
+// empty: the identity), rasterised into one occupancy grid (rr_rasterize_points) and transformed (rr_distance_field) into the field
+// [height][width].  false: rr_last_error(ctx), or a states vector that is not [n][4]
+inline bool build_field(rr_ctx* ctx, const std::vector<std::vector<rr_radar_point>>& clouds, const std::vector<double>& states, int n_angles,
+                        const rr_field_config& cfg, std::vector<uint16_t>& field)
+{
+    const size_t n = clouds.size(), stride = (size_t)n_angles + 1;
+    const size_t cells = cfg.width > 0 && cfg.height > 0 ? (size_t)cfg.width * (size_t)cfg.height : 0;
+    field.assign(cells, 0);
+    if (n == 0 || (!states.empty() && states.size() != 4 * n)) return false;
+    size_t mp = 1;
+    for (const auto& c : clouds) mp = std::max(mp, c.size());
+    std::vector<rr_radar_point> pts(n * mp);
+    std::vector<uint32_t> offs(n * stride, 0u);                       // only each frame's total is read
+    for (size_t f = 0; f < n; f++) {
+        std::copy(clouds[f].begin(), clouds[f].end(), pts.begin() + (std::ptrdiff_t)(f * mp));
+        offs[f * stride + (size_t)n_angles] = (uint32_t)clouds[f].size();
+    }
+    std::vector<uint8_t> occ(cells, 0);
+    if (rr_rasterize_points(ctx, pts.data(), offs.data(), (int)n, (int)mp, states.empty() ? nullptr : states.data(), &cfg, occ.data())) return false;
+    return rr_distance_field(ctx, occ.data(), 1, &cfg, field.data()) == 0;
+}
+
+// one scan against n hypothesis states [n][4] f32 (c, s, tx, ty: the scan's sensor frame into the map frame) and a field (rr_score_poses):
+// one record per hypothesis.  false: rr_last_error(ctx), or a states vector that is not [n][4], or a field that is not [height][width]
+inline bool score_poses(rr_ctx* ctx, const std::vector<rr_radar_point>& scan, const std::vector<float>& states, const std::vector<uint16_t>& field,
+                        const rr_field_config& cfg, std::vector<rr_field_rec>& out)
+{
+    out.assign(states.size() / 4, rr_field_rec{});
+    if (states.empty() || states.size() % 4 || cfg.width < 1 || cfg.height < 1 || field.size() != (size_t)cfg.width * (size_t)cfg.height) return false;
+    return rr_score_poses(ctx, scan.data(), (uint32_t)scan.size(), (int)scan.size(), states.data(), (int)(states.size() / 4), field.data(), &cfg,
+                          out.data()) == 0;
+}
+
 }  // namespace radarays_ros_amd::marshal

@@ -209,6 +209,10 @@ struct rr_ctx {
     // count + correspondences, initial states, records
     std::map<hipStream_t, DevBuf<long long>> icp_acc; std::mutex icp_mu;
     DevBuf<rr_radar_point> d_icp_points; DevBuf<uint32_t> d_icp_words; DevBuf<double> d_icp_init; DevBuf<rr_icp_rec> d_icp_rec;
+    // staging of the host forms of rr_rasterize_points / rr_distance_field / rr_score_poses (the device forms use no context memory at all):
+    // points, offsets + the scan's count, the rasteriser's f64 states, the scorer's f32 states, the occupancy grid, the field, the records
+    DevBuf<rr_radar_point> d_field_points; DevBuf<uint32_t> d_field_words; DevBuf<double> d_field_init; DevBuf<float> d_field_states;
+    DevBuf<uint8_t> d_field_occ; DevBuf<uint16_t> d_field_map; DevBuf<rr_field_rec> d_field_rec;
     DevBuf<uint32_t> d_conv_hist;      // ... and of rr_compare_images: one chunk's joint histograms on their way to the host
     // rr_align_images_device: one chunk's curves (when the caller gives no buffer) and sums, the records; and the host forms' curves
     DevBuf<long long> d_align_curve, d_conv_curve; DevBuf<unsigned long long> d_align_sums; DevBuf<rr_align_record> d_align_rec;

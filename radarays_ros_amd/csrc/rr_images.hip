@@ -1,5 +1,5 @@
 // rr_images.hip -- the C ABI's image entry points: images in, records / points / images out.  PSNR scores and metrics against a reference image
-// (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), place recognition (rr_place.hip), point clouds and Cartesian images (rr_detect.hip), sweep compensation (rr_deskew.hip), object annotations (rr_notes.hip): each in a device form, which runs on the
+// (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), place recognition (rr_place.hip), point clouds and Cartesian images (rr_detect.hip), sweep compensation (rr_deskew.hip), scan matching (rr_icp.hip), the likelihood field (rr_field.hip), object annotations (rr_notes.hip): each in a device form, which runs on the
 // caller's buffers and stream, and a host form, which stages through the context's own buffers on c->stream.
 #include "rr_ctx.h"
 #include <algorithm>
@@ -141,6 +141,55 @@ int check_icp(rr_ctx* c, const char* who, const void* points, const void* offset
     if (iterations < 0 || iterations > 64) return fail(c, -3, w + ": iterations must be 0..64");
     if (!(std::isfinite(gate) && gate > 0.0f)) return fail(c, -3, w + ": gate must be finite and > 0");
     return 0;
+}
+
+// the refusals the likelihood-field calls share: a grid within its stated ranges
+int check_field_grid(rr_ctx* c, const std::string& w, const rr_field_config* g)
+{
+    if (!g) return fail(c, -3, w + ": null config");
+    if (g->width < 1 || g->width > 4096 || g->height < 1 || g->height > 4096) return fail(c, -3, w + ": width and height must be 1..4096");
+    if (!(std::isfinite(g->cell) && g->cell > 0.0f)) return fail(c, -3, w + ": cell must be finite and > 0");
+    if (!(std::isfinite(g->x0) && std::isfinite(g->y0))) return fail(c, -3, w + ": x0 and y0 must be finite");
+    if (g->max_dist < 1 || g->max_dist > 255) return fail(c, -3, w + ": max_dist must be 1..255");
+    if (g->gate < 0 || g->gate > g->max_dist) return fail(c, -3, w + ": gate must be 0..max_dist");
+    return 0;
+}
+
+// the refusals of rr_rasterize_points_device / rr_rasterize_points: the config gives n_angles, the offsets' stride
+int check_rasterize(rr_ctx* c, const char* who, const void* points, const void* offsets, int n_frames, int max_points, const void* states,
+                    const rr_field_config* g, const void* occ)
+{
+    const std::string w(who);
+    const bool sizes_ok = max_points >= 0 && max_points <= 65536;
+    int rc = check_images(c, w, offsets && occ && (!sizes_ok || max_points == 0 || points), "buffer", "n_frames", n_frames, 65535); if (rc) return rc;
+    if (!sizes_ok) return fail(c, -3, w + ": max_points must be 0..65536");
+    if ((uintptr_t)states % 8 != 0) return fail(c, -3, w + ": the states must be 8-byte aligned");
+    return check_field_grid(c, w, g);
+}
+
+// the refusals of rr_distance_field_device / rr_distance_field: no config is needed, the shape comes with the call
+int check_distance_field(rr_ctx* c, const char* who, const void* occ, int threshold, const rr_field_config* g, const void* field)
+{
+    if (!c) return -1;
+    const std::string w(who);
+    if (!(occ && field)) return fail(c, -3, w + ": null buffer");
+    if (threshold < 1 || threshold > 255) return fail(c, -3, w + ": threshold must be 1..255");
+    if (occ == field) return fail(c, -3, w + ": the field must not alias the occupancy grid");
+    return check_field_grid(c, w, g);
+}
+
+// the refusals of rr_score_poses_device / rr_score_poses: no config is needed either
+int check_score_poses(rr_ctx* c, const char* who, const void* points, bool have_count, int max_points, const void* states, int n_hyp, const void* field,
+                      const rr_field_config* g, const void* recs)
+{
+    if (!c) return -1;
+    const std::string w(who);
+    const bool sizes_ok = max_points >= 0 && max_points <= 65536;
+    if (!(have_count && states && field && recs && (!sizes_ok || max_points == 0 || points))) return fail(c, -3, w + ": null buffer");
+    if (!sizes_ok) return fail(c, -3, w + ": max_points must be 0..65536");
+    if (n_hyp < 1 || n_hyp > (1 << 22)) return fail(c, -3, w + ": n_hyp must be 1..2^22");
+    if ((uintptr_t)states % 4 != 0 || (uintptr_t)recs % 8 != 0) return fail(c, -3, w + ": d_states must be 4-byte and d_recs 8-byte aligned");
+    return check_field_grid(c, w, g);
 }
 
 // the refusals the annotation calls share: a config (the plane shape) within the limits of the label planes and of the packed azimuth
@@ -904,6 +953,108 @@ int rr_register_points(rr_ctx* c, const rr_radar_point* points, const uint32_t* 
     rc = records_back(c, rec.data(), c->d_icp_rec.p, n * sizeof(rr_icp_rec), c->stream); if (rc) return rc;
     std::copy(rec.begin(), rec.end(), recs);
     for (size_t f = 0; corr && f < n; f++) std::copy(got.begin() + f * mp, got.begin() + f * mp + count(f), corr + f * mp);
+    return 0;
+}
+
+// ---- likelihood field (rr_field.hip) ------------------------------------------------------------------------------------
+void rr_field_tile_sizes(int* points_tile, int* hyps_per_group, int* row_tile) { field_tile_sizes(points_tile, hyps_per_group, row_tile); }
+
+int rr_rasterize_points_device(rr_ctx* c, const rr_radar_point* d_points, const uint32_t* d_offsets, int n_frames, int max_points,
+                               const double* d_states, const rr_field_config* cfg, uint8_t* d_occ_u8, void* stream)
+{
+    int rc = check_rasterize(c, "rr_rasterize_points_device", d_points, d_offsets, n_frames, max_points, d_states, cfg, d_occ_u8); if (rc) return rc;
+    if (max_points == 0) return 0;
+    RR_HIP(c, hipSetDevice(c->device));
+    launch_field_raster(d_points, d_offsets, n_frames, c->cfg.n_angles, max_points, d_states, *cfg, d_occ_u8, stream_of(c, stream));
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_rasterize_points(rr_ctx* c, const rr_radar_point* points, const uint32_t* offsets, int n_frames, int max_points, const double* states,
+                        const rr_field_config* cfg, uint8_t* occ_u8)
+{
+    int rc = check_rasterize(c, "rr_rasterize_points", points, offsets, n_frames, max_points, nullptr, cfg, occ_u8); if (rc) return rc;
+    if (max_points == 0) return 0;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)n_frames, A = (size_t)c->cfg.n_angles, mp = (size_t)max_points, n_offs = n * (A + 1);
+    const size_t cells = (size_t)cfg->width * cfg->height;
+    RR_HIP(c, hipStreamSynchronize(c->stream));        // the staging buffers may be reallocated
+    RR_HIP(c, c->d_field_points.ensure(n * mp));
+    RR_HIP(c, c->d_field_words.ensure(n_offs));
+    RR_HIP(c, c->d_field_init.ensure(n * 4));
+    RR_HIP(c, c->d_field_occ.ensure(cells));
+    auto count = [&](size_t f) { return std::min<size_t>(offsets[f * (A + 1) + A], mp); };
+    RR_HIP(c, hipMemcpyAsync(c->d_field_words.p, offsets, n_offs * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    for (size_t f = 0; f < n; f++)
+        if (count(f)) RR_HIP(c, hipMemcpyAsync(c->d_field_points.p + f * mp, points + f * mp, count(f) * sizeof(rr_radar_point), hipMemcpyHostToDevice, c->stream));
+    if (states) RR_HIP(c, hipMemcpyAsync(c->d_field_init.p, states, n * 4 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    RR_HIP(c, hipMemcpyAsync(c->d_field_occ.p, occ_u8, cells, hipMemcpyHostToDevice, c->stream));      // the call accumulates
+    rc = rr_rasterize_points_device(c, c->d_field_points.p, c->d_field_words.p, n_frames, max_points, states ? c->d_field_init.p : nullptr, cfg,
+                                    c->d_field_occ.p, c->stream); if (rc) return rc;
+    std::vector<uint8_t> got(cells);                   // the caller's buffer is written once everything has arrived
+    rc = records_back(c, got.data(), c->d_field_occ.p, cells, c->stream); if (rc) return rc;
+    std::copy(got.begin(), got.end(), occ_u8);
+    return 0;
+}
+
+int rr_distance_field_device(rr_ctx* c, const uint8_t* d_occ_u8, int threshold, const rr_field_config* cfg, uint16_t* d_field_u16, void* stream)
+{
+    int rc = check_distance_field(c, "rr_distance_field_device", d_occ_u8, threshold, cfg, d_field_u16); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    launch_distance_field(d_occ_u8, threshold, *cfg, d_field_u16, stream_of(c, stream));
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_distance_field(rr_ctx* c, const uint8_t* occ_u8, int threshold, const rr_field_config* cfg, uint16_t* field_u16)
+{
+    int rc = check_distance_field(c, "rr_distance_field", occ_u8, threshold, cfg, field_u16); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t cells = (size_t)cfg->width * cfg->height;
+    RR_HIP(c, hipStreamSynchronize(c->stream));        // the staging buffers may be reallocated
+    RR_HIP(c, c->d_field_occ.ensure(cells));
+    RR_HIP(c, c->d_field_map.ensure(cells));
+    RR_HIP(c, hipMemcpyAsync(c->d_field_occ.p, occ_u8, cells, hipMemcpyHostToDevice, c->stream));
+    rc = rr_distance_field_device(c, c->d_field_occ.p, threshold, cfg, c->d_field_map.p, c->stream); if (rc) return rc;
+    std::vector<uint16_t> got(cells);
+    rc = records_back(c, got.data(), c->d_field_map.p, cells * sizeof(uint16_t), c->stream); if (rc) return rc;
+    std::copy(got.begin(), got.end(), field_u16);
+    return 0;
+}
+
+int rr_score_poses_device(rr_ctx* c, const rr_radar_point* d_points, const uint32_t* d_count, int max_points, const float* d_states, int n_hyp,
+                          const uint16_t* d_field_u16, const rr_field_config* cfg, rr_field_rec* d_recs, void* stream)
+{
+    int rc = check_score_poses(c, "rr_score_poses_device", d_points, d_count != nullptr, max_points, d_states, n_hyp, d_field_u16, cfg, d_recs);
+    if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    launch_field_score(d_points, d_count, max_points, d_states, n_hyp, d_field_u16, *cfg, d_recs, stream_of(c, stream));
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_score_poses(rr_ctx* c, const rr_radar_point* points, uint32_t count, int max_points, const float* states, int n_hyp, const uint16_t* field_u16,
+                   const rr_field_config* cfg, rr_field_rec* recs)
+{
+    int rc = check_score_poses(c, "rr_score_poses", points, true, max_points, states, n_hyp, field_u16, cfg, recs); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)n_hyp, cells = (size_t)cfg->width * cfg->height, m = std::min<size_t>(count, (size_t)max_points);
+    RR_HIP(c, hipStreamSynchronize(c->stream));        // the staging buffers may be reallocated
+    RR_HIP(c, c->d_field_points.ensure(m));
+    RR_HIP(c, c->d_field_words.ensure(1));
+    RR_HIP(c, c->d_field_states.ensure(n * 4));
+    RR_HIP(c, c->d_field_map.ensure(cells));
+    RR_HIP(c, c->d_field_rec.ensure(n));
+    if (m) RR_HIP(c, hipMemcpyAsync(c->d_field_points.p, points, m * sizeof(rr_radar_point), hipMemcpyHostToDevice, c->stream));
+    RR_HIP(c, hipMemcpyAsync(c->d_field_words.p, &count, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    RR_HIP(c, hipMemcpyAsync(c->d_field_states.p, states, n * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    RR_HIP(c, hipMemcpyAsync(c->d_field_map.p, field_u16, cells * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+    RR_HIP(c, hipStreamSynchronize(c->stream));        // (count is this call's own variable)
+    rc = rr_score_poses_device(c, c->d_field_points.p, c->d_field_words.p, max_points, c->d_field_states.p, n_hyp, c->d_field_map.p, cfg,
+                               c->d_field_rec.p, c->stream); if (rc) return rc;
+    std::vector<rr_field_rec> rec(n);
+    rc = records_back(c, rec.data(), c->d_field_rec.p, n * sizeof(rr_field_rec), c->stream); if (rc) return rc;
+    std::copy(rec.begin(), rec.end(), recs);
     return 0;
 }
 

@@ -1,4 +1,4 @@
-// rr_launch.h -- every launcher of rr_kernels.hip, rr_labels.hip, rr_paths.hip, rr_doppler.hip, rr_refit.hip, rr_detect.hip, rr_deskew.hip, rr_icp.hip, rr_notes.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip, rr_place.hip and rr_lbvh.hip, declared ONCE: included where they
+// rr_launch.h -- every launcher of rr_kernels.hip, rr_labels.hip, rr_paths.hip, rr_doppler.hip, rr_refit.hip, rr_detect.hip, rr_deskew.hip, rr_icp.hip, rr_field.hip, rr_notes.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip, rr_place.hip and rr_lbvh.hip, declared ONCE: included where they
 // are defined (a definition that drifts from its declaration fails there) and where they are called.  Default arguments live here only.
 #pragma once
 #include "../../include/radarays_mi355.h"
@@ -79,6 +79,14 @@ size_t icp_scratch_words(size_t n_frames);
 void launch_icp(const rr_radar_point* points, const uint32_t* offsets, int n_frames, int n_angles, int max_points, const rr_radar_point* tgt,
                 const uint32_t* tgt_count, int max_tgt, const double* init, float gate, int iterations, rr_icp_rec* recs, uint32_t* corr,
                 long long* acc, hipStream_t s);
+// rr_field.hip (likelihood field).  No scratch: occ is only ever written with ones, field is written whole, every record of recs is written;
+// states of the rasteriser 8-byte aligned or null, recs 8-byte aligned, field must not alias occ
+void field_tile_sizes(int* points_tile, int* hyps_per_group, int* row_tile);
+void launch_field_raster(const rr_radar_point* points, const uint32_t* offsets, int n_frames, int n_angles, int max_points, const double* states,
+                         const rr_field_config& g, uint8_t* occ, hipStream_t s);
+void launch_distance_field(const uint8_t* occ, int threshold, const rr_field_config& g, uint16_t* field, hipStream_t s);
+void launch_field_score(const rr_radar_point* points, const uint32_t* count, int max_points, const float* states, int n_hyp, const uint16_t* field,
+                        const rr_field_config& g, rr_field_rec* recs, hipStream_t s);
 // rr_notes.hip (object annotations).  scratch: note_scratch_bytes, 16-byte aligned like notes; every word of it, of notes and of skipped is written by the launches
 size_t note_scratch_bytes(size_t n_frames, size_t n_objects, int n_angles);
 void launch_notes(const uint32_t* labels, const uint8_t* imgs, int n_frames, uint32_t n_objects, uint32_t extent_mask, const PolarGrid& G,

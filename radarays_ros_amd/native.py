@@ -43,6 +43,8 @@ SYMBOLS = [
     "rr_sweep_table_device", "rr_sweep_table", "rr_compensate_points_device", "rr_compensate_points",
     "rr_polar_to_cartesian_sweep_device", "rr_polar_to_cartesian_sweep",
     "rr_register_points_device", "rr_register_points", "rr_icp_tile_sizes",
+    "rr_rasterize_points_device", "rr_rasterize_points", "rr_distance_field_device", "rr_distance_field",
+    "rr_score_poses_device", "rr_score_poses", "rr_field_tile_sizes",
 ]
 
 
@@ -223,6 +225,83 @@ def _icp_init(init, n):
     if not np.all(np.isfinite(h) & (h > 0)):
         raise ValueError("every initial state needs a finite, non-zero (c, s)")
     return x
+
+
+# ---- likelihood field (rr_field.hip).  rr_field_rec as numpy sees it (16 B): the score of one pose hypothesis
+FIELD_DTYPE = np.dtype([("sum_d2", "<u8"), ("n_in", "<u4"), ("n_hit", "<u4")])
+FIELD_MAX_SIDE, FIELD_MAX_DIST, FIELD_MAX_HYP = 4096, 255, 1 << 22
+
+
+class RRFieldConfig(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("cell", C.c_float), ("x0", C.c_float), ("y0", C.c_float),
+                ("max_dist", C.c_int32), ("gate", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class RRFieldRec(C.Structure):
+    _fields_ = [("sum_d2", C.c_uint64), ("n_in", C.c_uint32), ("n_hit", C.c_uint32)]
+
+
+def _f32_finite(v, what, positive=False):
+    """a number that is finite (and > 0) as a float32 -> that float32 as a Python float"""
+    try:
+        with np.errstate(over="ignore"):
+            g = np.float32(float(v))
+    except (TypeError, ValueError):
+        raise ValueError("%s must be a number, got %r" % (what, v))
+    if isinstance(v, bool) or not np.isfinite(g) or (positive and not g > 0):
+        raise ValueError("%s must be finite%s as a float32, got %r" % (what, " and > 0" if positive else "", v))
+    return float(g)
+
+
+def field_config(width, height, cell, x0, y0, max_dist=FIELD_MAX_DIST, gate=0):
+    """rr_field_config, range-checked before any call into the library: width x height cells of `cell` metres, the low corner of cell
+    (0, 0) at (x0, y0) in the map frame, distances saturated at max_dist cells, a point a HIT within gate cells.  An RRFieldConfig passes
+    through the same checks."""
+    w, h = _int_in(width, 1, FIELD_MAX_SIDE, "width"), _int_in(height, 1, FIELD_MAX_SIDE, "height")
+    md = _int_in(max_dist, 1, FIELD_MAX_DIST, "max_dist")
+    return RRFieldConfig(w, h, _f32_finite(cell, "cell", True), _f32_finite(x0, "x0"), _f32_finite(y0, "y0"), md, _int_in(gate, 0, md, "gate"), 0)
+
+
+def _field_cfg(cfg):
+    if isinstance(cfg, RRFieldConfig):
+        return field_config(cfg.width, cfg.height, cfg.cell, cfg.x0, cfg.y0, cfg.max_dist, cfg.gate)
+    if isinstance(cfg, dict):
+        return field_config(**cfg)
+    raise ValueError("a field config must be an RRFieldConfig (native.field_config makes one) or a dict of its arguments, got %r" % (cfg,))
+
+
+def field_tile_sizes():
+    """(points a wave of k_field_score takes per step, hypotheses per workgroup of it, cells of a row per sweep of the transform's row pass)"""
+    a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+    lib().rr_field_tile_sizes(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
+def _lattice_axis(half, step, what):
+    half, step = float(half), float(step)
+    if not (np.isfinite(half) and half >= 0 and np.isfinite(step) and step > 0):
+        raise ValueError("%s needs a finite half extent >= 0 and a finite step > 0" % what)
+    k = int(np.floor(half / step + 1e-9))
+    return np.arange(-k, k + 1, dtype=np.float64) * step
+
+
+def pose_lattice(center_xy_yaw, half_extent_xy, step_xy, half_yaw, step_yaw):
+    """the hypotheses of a dense search around (x, y, yaw): every node of the lattice centre + (i * step_xy, j * step_xy, k * step_yaw) with
+    |i * step_xy| <= half_extent_xy and |k * step_yaw| <= half_yaw (radians), x slowest, yaw fastest, so the centre is the middle node.
+    Returns (states float32 [n][4] = (cos yaw, sin yaw, x, y) as rr_score_poses takes them: the scan's sensor frame into the map frame,
+    xyz float64 [n][3] = the nodes).  cos and sin are numpy's in float64, rounded once to float32: the states are inputs of the scoring,
+    so this does not touch its bit-exactness."""
+    c = np.asarray(center_xy_yaw, np.float64).reshape(-1)
+    if c.shape != (3,) or not np.all(np.isfinite(c)):
+        raise ValueError("the centre must be three finite numbers (x, y, yaw), got %r" % (center_xy_yaw,))
+    dxy, dyaw = _lattice_axis(half_extent_xy, step_xy, "the xy lattice"), _lattice_axis(half_yaw, step_yaw, "the yaw lattice")
+    n = len(dxy) * len(dxy) * len(dyaw)
+    if n > FIELD_MAX_HYP:
+        raise ValueError("a lattice of %d nodes: at most %d hypotheses per call" % (n, FIELD_MAX_HYP))
+    gx, gy, gyaw = np.meshgrid(c[0] + dxy, c[1] + dxy, c[2] + dyaw, indexing="ij")
+    xyz = np.stack([gx.ravel(), gy.ravel(), gyaw.ravel()], axis=1)
+    states = np.stack([np.cos(xyz[:, 2]), np.sin(xyz[:, 2]), xyz[:, 0], xyz[:, 1]], axis=1).astype(np.float32)
+    return np.ascontiguousarray(states), xyz
 
 
 # rr_default_detect_config
@@ -516,6 +595,15 @@ def lib():
     L.rr_register_points.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_uint32, C.c_int, vp, C.c_float, C.c_int, vp, vp]
     L.rr_icp_tile_sizes.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.rr_icp_tile_sizes.restype = None
+    fc = C.POINTER(RRFieldConfig)
+    L.rr_rasterize_points_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, fc, vp, vp]
+    L.rr_rasterize_points.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, fc, vp]
+    L.rr_distance_field_device.argtypes = [vp, vp, C.c_int, fc, vp, vp]
+    L.rr_distance_field.argtypes = [vp, vp, C.c_int, fc, vp]
+    L.rr_score_poses_device.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp, fc, vp, vp]
+    L.rr_score_poses.argtypes = [vp, vp, C.c_uint32, C.c_int, vp, C.c_int, vp, fc, vp]
+    L.rr_field_tile_sizes.argtypes = [C.POINTER(C.c_int)] * 3
+    L.rr_field_tile_sizes.restype = None
     for n in SYMBOLS:
         getattr(L, n)
     _LIB = L
@@ -1415,6 +1503,103 @@ class Context:
                                             corr.ctypes.data if want_corr else None))
         if want_corr:
             return recs, [corr[f, :len(p)].copy() for f, p in enumerate(pts)]
+        return recs
+
+    # ---- likelihood field (rr_field.hip): clouds into an occupancy grid, its exact distance transform, pose hypotheses scored against it
+    def rasterize_points_device(self, d_points_ptr, d_offsets_ptr, n_frames, max_points, field_cfg, d_occ_ptr, d_states_ptr=None, stream=None):
+        """rr_rasterize_points_device: ones into the uint8 grid [height][width] at d_occ_ptr (zeroed by the caller, or holding earlier
+        clouds) for the points [n_frames][max_points] and offsets [n_frames][n_angles + 1] rr_detect_device wrote; d_states_ptr: float64
+        [n_frames][4] = (c, s, tx, ty), each frame into the map frame, or None (identity); on `stream`"""
+        self._polar_shape()
+        n, mp, g = _frames_arg(n_frames), _int_in(max_points, 0, ICP_MAX_POINTS, "max_points"), _field_cfg(field_cfg)
+        if not d_offsets_ptr or not d_occ_ptr or (mp > 0 and not d_points_ptr):
+            raise ValueError("rasterize_points_device needs point, offset and grid buffers")
+        self._ck(self._L.rr_rasterize_points_device(self._h, d_points_ptr, d_offsets_ptr, n, mp, d_states_ptr, C.byref(g), d_occ_ptr, stream))
+
+    def rasterize_points(self, points_list, offsets, field_cfg, states=None, occ=None):
+        """rr_rasterize_points on what detect() (or compensate_points()) returned: a list of n POINT_DTYPE arrays and offsets uint32
+        [n][n_angles + 1]; states float64 [n][4] (se2_states makes them) or None; occ: a uint8 [height][width] grid to accumulate into
+        (it is not modified) or None for an empty one.  Returns the grid."""
+        _, n_angles = self._polar_shape()
+        g = _field_cfg(field_cfg)
+        if isinstance(points_list, np.ndarray) and points_list.ndim == 1:
+            points_list = [points_list]
+        pts = [np.asarray(p) for p in points_list]
+        if not pts or len(pts) > 65535 or any(p.dtype != POINT_DTYPE or p.ndim != 1 for p in pts):
+            raise ValueError("points must be a list of 1..65535 one-dimensional POINT_DTYPE arrays")
+        n = len(pts)
+        if any(len(p) > ICP_MAX_POINTS for p in pts):
+            raise ValueError("a cloud may hold at most %d points" % ICP_MAX_POINTS)
+        offs = np.asarray(offsets)
+        if offs.ndim == 1:
+            offs = offs[None]
+        if offs.dtype != np.uint32 or offs.shape != (n, n_angles + 1):
+            raise ValueError("offsets must be uint32 [%d][%d], got %s %s" % (n, n_angles + 1, offs.dtype, offs.shape))
+        offs = np.ascontiguousarray(offs)
+        mp = max(1, max(len(p) for p in pts))
+        if any(len(p) != min(int(offs[f, -1]), mp) for f, p in enumerate(pts)):
+            raise ValueError("every frame must hold the points its offsets count")
+        st = None
+        if states is not None:
+            st = np.asarray(states)
+            if st.dtype.kind not in "fiu" or st.shape != (n, 4):
+                raise ValueError("states must be real numbers of shape [%d][4] (c, s, tx, ty), got %s %s" % (n, st.dtype, st.shape))
+            st = np.ascontiguousarray(st, np.float64)
+        out = self._field_grid(occ, g, np.uint8, "occ").copy() if occ is not None else np.zeros((g.height, g.width), np.uint8)
+        buf = np.zeros((n, mp), POINT_DTYPE)
+        for f, p in enumerate(pts):
+            buf[f, :len(p)] = p
+        self._ck(self._L.rr_rasterize_points(self._h, buf.ctypes.data, offs.ctypes.data, n, mp, None if st is None else st.ctypes.data, C.byref(g),
+                                             out.ctypes.data))
+        return out
+
+    @staticmethod
+    def _field_grid(a, g, dtype, what):
+        x = np.asarray(a)
+        if x.dtype != dtype or x.shape != (g.height, g.width):
+            raise ValueError("%s must be %s [%d][%d], got %s %s" % (what, np.dtype(dtype).name, g.height, g.width, x.dtype, x.shape))
+        return np.ascontiguousarray(x)
+
+    def distance_field_device(self, d_occ_ptr, field_cfg, d_field_ptr, threshold=1, stream=None):
+        """rr_distance_field_device: the uint16 field [height][width] at d_field_ptr from the uint8 grid at d_occ_ptr (occupied: >= threshold)"""
+        g, th = _field_cfg(field_cfg), _int_in(threshold, 1, 255, "threshold")
+        if not d_occ_ptr or not d_field_ptr or d_occ_ptr == d_field_ptr:
+            raise ValueError("distance_field_device needs a grid and a field buffer that do not alias")
+        self._ck(self._L.rr_distance_field_device(self._h, d_occ_ptr, th, C.byref(g), d_field_ptr, stream))
+
+    def distance_field(self, occ, field_cfg, threshold=1):
+        """rr_distance_field: uint8 [height][width] (occupied: >= threshold) -> uint16 [height][width], min(max_dist^2, the exact squared
+        distance in cells to the nearest occupied cell)"""
+        g, th = _field_cfg(field_cfg), _int_in(threshold, 1, 255, "threshold")
+        x = self._field_grid(occ, g, np.uint8, "occ")
+        out = np.zeros((g.height, g.width), np.uint16)
+        self._ck(self._L.rr_distance_field(self._h, x.ctypes.data, th, C.byref(g), out.ctypes.data))
+        return out
+
+    def score_poses_device(self, d_points_ptr, d_count_ptr, max_points, d_states_ptr, n_hyp, d_field_ptr, field_cfg, d_recs_ptr, stream=None):
+        """rr_score_poses_device: FIELD_DTYPE records [n_hyp] in HBM for the float32 states [n_hyp][4] = (c, s, tx, ty), each the scan's
+        sensor frame into the map frame, of ONE scan: the points at d_points_ptr whose count is the uint32 at d_count_ptr; on `stream`"""
+        mp, n, g = _int_in(max_points, 0, ICP_MAX_POINTS, "max_points"), _int_in(n_hyp, 1, FIELD_MAX_HYP, "n_hyp"), _field_cfg(field_cfg)
+        if not d_count_ptr or not d_states_ptr or not d_field_ptr or not d_recs_ptr or (mp > 0 and not d_points_ptr):
+            raise ValueError("score_poses_device needs point, count, state, field and record buffers")
+        self._ck(self._L.rr_score_poses_device(self._h, d_points_ptr, d_count_ptr, mp, d_states_ptr, n, d_field_ptr, C.byref(g), d_recs_ptr, stream))
+
+    def score_poses(self, points, states, field, field_cfg):
+        """rr_score_poses: one POINT_DTYPE cloud, float32 states [n][4] (pose_lattice makes them), the uint16 field of distance_field ->
+        FIELD_DTYPE [n]; lower sum_d2 is better"""
+        g = _field_cfg(field_cfg)
+        p = np.asarray(points)
+        if p.dtype != POINT_DTYPE or p.ndim != 1 or len(p) > ICP_MAX_POINTS:
+            raise ValueError("the scan must be a one-dimensional POINT_DTYPE array of at most %d points" % ICP_MAX_POINTS)
+        st = np.asarray(states)
+        if st.dtype.kind not in "fiu" or st.ndim != 2 or st.shape[1] != 4 or not 1 <= len(st) <= FIELD_MAX_HYP:
+            raise ValueError("states must be real numbers of shape [n][4] (c, s, tx, ty), n in 1..%d, got %s %s" % (FIELD_MAX_HYP, st.dtype, st.shape))
+        st = np.ascontiguousarray(st, np.float32)
+        f = self._field_grid(field, g, np.uint16, "field")
+        p = np.ascontiguousarray(p)
+        recs = np.zeros(len(st), FIELD_DTYPE)
+        self._ck(self._L.rr_score_poses(self._h, p.ctypes.data if len(p) else None, len(p), len(p), st.ctypes.data, len(st), f.ctypes.data,
+                                        C.byref(g), recs.ctypes.data))
         return recs
 
     # ---- object annotations (rr_notes.hip): one record per object from label images; any context with a config, mesh or not

@@ -420,6 +420,70 @@ class RadarHIP:
         out[:, 2], out[:, 3] = aw * bz + az * bw, aw * bw - az * bz
         return out.astype(np.float32)
 
+    # ---- likelihood field (rr_field.hip): a map of keyframe clouds as a distance field, and very many pose hypotheses scored against it
+    @staticmethod
+    def _planar_states(poses):
+        """[n][7] poses -> float64 [n][4] = (cos yaw, sin yaw, x, y): the planar part of a pose, sensor frame into the map frame"""
+        p = np.asarray(poses, np.float64)
+        qx, qy, qz, qw = p[:, 0], p[:, 1], p[:, 2], p[:, 3]
+        yaw = np.arctan2(2.0 * (qw * qz + qx * qy), 1.0 - 2.0 * (qy * qy + qz * qz))
+        return native.se2_states(yaw, p[:, 4], p[:, 5])
+
+    def buildLikelihoodField(self, poses, field_cfg, detect_cfg=None):
+        """[n][7] keyframe poses of a planar sensor -> the likelihood field uint16 [height][width] of the map their scans make
+        (field_cfg: native.field_config).  Per 64 poses: rr_simulate_batch_device, rr_detect_device (detect_cfg: a dict of rr_detect_config
+        fields, None: the defaults) and rr_rasterize_points_device, every cloud under the planar part of its own pose, into one occupancy
+        grid on one stream; then rr_distance_field_device.  Nothing but the field leaves the GPU.
+        Convention: a state (c, s, tx, ty) maps a cloud's sensor frame into the map frame, q = R p + t; a keyframe's state is the planar
+        part of its pose, (cos yaw, sin yaw, x, y)."""
+        import torch
+        self._push()
+        n_cells = self.m_cfg.n_cells
+        det = native.detect_config(detect_cfg, n_cells=n_cells)
+        g = native._field_cfg(field_cfg)
+        p = native.object_poses_array(poses)
+        if len(p) == 0:
+            raise ValueError("a map needs at least one pose")
+        states = self._planar_states(p)
+        dev = torch.device("cuda", self._ctx.device)
+        stream = torch.cuda.Stream(device=dev)      # an explicit stream, as simulatePointClouds
+        s = stream.cuda_stream
+        with torch.cuda.device(dev), torch.cuda.stream(stream):
+            occ = torch.zeros((g.height, g.width), dtype=torch.uint8, device=dev)
+            field = torch.empty((g.height, g.width), dtype=torch.int16, device=dev)
+            for at in range(0, len(p), 64):
+                chunk = p[at:at + 64]
+                n = len(chunk)
+                imgs = torch.empty((n, n_cells, N_ANGLES), dtype=torch.uint8, device=dev)
+                offs = torch.empty((n, N_ANGLES + 1), dtype=torch.int32, device=dev)
+                self._ctx.simulate_batch_device(chunk, imgs.data_ptr(), s)
+                if det.method == 1:
+                    mp = det.k * N_ANGLES
+                else:
+                    self._ctx.detect_device(imgs.data_ptr(), n, det, None, 0, offs.data_ptr(), s)     # counts
+                    mp = int(offs[:, -1].max().item())
+                mp = max(1, min(mp, native.ICP_MAX_POINTS))
+                pts = torch.empty((n, mp * native.POINT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+                d_st = torch.from_numpy(np.ascontiguousarray(states[at:at + 64])).to(dev)
+                self._ctx.detect_device(imgs.data_ptr(), n, det, pts.data_ptr(), mp, offs.data_ptr(), s)
+                self._ctx.rasterize_points_device(pts.data_ptr(), offs.data_ptr(), n, mp, g, occ.data_ptr(), d_st.data_ptr(), s)
+            self._ctx.distance_field_device(occ.data_ptr(), g, field.data_ptr(), 1, s)
+            out = field.cpu().numpy().view(np.uint16).copy()
+        self._ctx.synchronize(s)
+        return out
+
+    def scorePoses(self, scan_points_or_image, states, field, field_cfg, detect_cfg=None):
+        """One observed scan against float32 states [n][4] (native.pose_lattice makes them) and a field of buildLikelihoodField ->
+        native.FIELD_DTYPE [n] (sum_d2, n_in, n_hit); lower sum_d2 is better.  The scan is a POINT_DTYPE cloud (e.g. toPointCloud of a
+        real scan) or a mono8 polar image [n_cells][400], which is detected first (detect_cfg as in buildLikelihoodField).
+        Convention: a hypothesis state (c, s, tx, ty) maps the scan's sensor frame into the map frame."""
+        self._push()
+        scan = np.asarray(scan_points_or_image)
+        if scan.dtype != native.POINT_DTYPE:
+            pts, _ = self._ctx.detect(self._polar(scan_points_or_image), native.detect_config(detect_cfg, n_cells=self.m_cfg.n_cells))
+            scan = pts[0]
+        return self._ctx.score_poses(scan, states, field, field_cfg)
+
     # ---- place recognition (rr_place.hip): a database of yaw-invariant ring/sector descriptors, and a scan looked up in it
     def buildPlaceDatabase(self, poses, place_cfg, on_device=False):
         """any number of [n][7] poses, worked through 64 at a time -> their descriptors uint8 [n][R][S] (native.Context._place_cfg
