@@ -206,7 +206,7 @@ public:
     }
     // A ghost's route: the wave of ONE azimuth's list (its first n records) that owns echo k of the azimuth's echo stream, walked back
     // along `parent` to the emitted beam -> the indices of the chain's waves, beam first (empty: no record owns echo k, or a parent
-    // lies beyond n -- a truncated row).  The polyline is records[i].o of the first, then o + range * d of every wave of the chain.
+    // lies beyond n -- a truncated row -- or the chain is longer than RR_WAVES_MAX_PASSES).  The polyline is records[i].o of the first, then o + range * d of every wave of the chain.
     static std::vector<int32_t> pathToEcho(const rr_wave_rec* records, size_t n, int32_t k)
     {
         std::vector<int32_t> chain;
@@ -216,7 +216,7 @@ public:
         }
         while (!chain.empty() && records[chain.back()].parent >= 0) {
             const int32_t p = records[chain.back()].parent;
-            if ((size_t)p >= n || chain.size() > RR_WAVES_MAX_PASSES) return {};
+            if ((size_t)p >= n || chain.size() >= RR_WAVES_MAX_PASSES) return {};      // one wave per pass: no longer chain is a wave list's
             chain.push_back(p);
         }
         std::reverse(chain.begin(), chain.end());
@@ -427,11 +427,13 @@ public:
         auto out = std::make_shared<Annotations>();
         out->n_objects = m_n_objects;
         std::vector<uint8_t> px;
+        // one pose per frame, as in simulateBatch: a per-azimuth table that simulate() installed would stand in for every pose given here
+        if (rr_multi_set_motion_poses(m_multi, nullptr, 0)) { mfail(); return {}; }
+        m_push_motion = true;      // simulate() re-installs its own table (or none), also after a failure below
         if (!marshal::annotate_chunks(m_ctx, poses.data(), n, m_n_objects, npx, extent_mask, out->notes, out->skipped, want_images ? &px : nullptr)) {
             fail(); return {};
         }
         for (size_t k = 0; want_images && k < n; k++) out->images.push_back(image(&px[k * npx], stamp));
-        m_push_motion = true;      // simulate() re-installs its own table (or none)
         return out;
     }
     const std::string& lastError() const { return m_err; }
