@@ -26,6 +26,9 @@ struct Delivery {
     uint64_t job = 0;
 };
 
+// the room of a host form's round trip (rr_stage.h): anonymous buffers that only grow, slot i for a call's i-th request
+using StagePool = std::vector<DevBuf<uint4>>;
+
 struct Lane {
     int buf_seg = 0, buf_cap = 0, buf_sigcap = 0, buf_cells = 0, buf_passes = 0;
     DevBuf<float4> d_wA[2], d_wB[2];
@@ -78,13 +81,10 @@ struct Lane {
     // columns [prov_seg][prov_cells].  Allocated by the lane's first provenance call (ensure_prov_buffers); plain batches never touch them
     DevBuf<EchoSrc> d_prov; DevBuf<uint32_t> d_prov_count, d_label_cols, d_face_cols;
     int prov_seg = 0, prov_cap = 0, prov_cells = 0;
-    DevBuf<uint32_t> d_label_img, d_face_img;      // rr_simulate_provenance: the assembled planes on their way to the host
-    DevBuf<rr_echo_src> d_echo_out; DevBuf<uint32_t> d_echo_out_counts;      // ... and its exported echo stream
 
     // wave paths (rr_paths.hip): k_wave_gather's running state per segment [path_seg], allocated by the lane's first paths call
-    // (ensure_path_state); rr_simulate_paths: the records and counts on their way to the host
+    // (ensure_path_state)
     DevBuf<uint4> d_path_state; int path_seg = 0;
-    DevBuf<float4> d_wave_out; DevBuf<uint32_t> d_wave_out_counts, d_wave_out_passes;
 
     // Doppler (rr_doppler.hip): k_rate_gather's state per wave and per segment, the rate list and the shifted list beside the lane's
     // echo lists, what the list-only column launch needs (a zero count for the last pass' slots, statistics of its own), the winner
@@ -94,8 +94,7 @@ struct Lane {
     DevBuf<SegStats> d_dop_stats; DevBuf<float> d_dop_vel_cols;
     std::vector<float4> h_dop_in;
     int dop_seg = 0, dop_cap = 0, dop_echo_cap = 0, dop_cells = 0; size_t dop_obj = 0;
-    // rr_simulate_doppler: the outputs on their way to the host
-    DevBuf<float> d_dop_out_vel, d_dop_vel_img; DevBuf<int32_t> d_dop_out_cells; DevBuf<uint32_t> d_dop_out_counts;
+    StagePool stage;              // the outputs of the host forms of rr_side.hip on their way to the host
 
     hipStream_t stream = nullptr;
     hipEvent_t ev_ready = nullptr, ev_consumed = nullptr;
@@ -171,7 +170,6 @@ struct rr_ctx {
     DevBuf<uint32_t> d_beam_order, d_beam_order2;
     DevBuf<int32_t> d_objmat;
     DevBuf<float> d_smear, d_noise, d_motion, d_decay;
-    DevBuf<uint8_t> d_param_imgs;   // rr_simulate_material_sets: images before the D2H copy
     // what upload_tables() has to refresh (the reference node re-reads its parameters before EVERY
     // frame, radar_simulator.cpp:85,200: setters that bring nothing new must cost nothing)
     enum : unsigned { D_CFG = 1, D_BEAMS = 2, D_MAT = 4, D_NOISE = 8, D_MOTION = 16, D_ALL = 31 };
@@ -198,36 +196,22 @@ struct rr_ctx {
     }
 
     int passes_override = -1;    // a parameter batch in the making: the largest n_reflections of its sets sizes queues and launch loops
-    DevBuf<unsigned long long> d_sse; DevBuf<uint8_t> d_ref_img;     // rr_score_images / rr_simulate_param_sets
-    // rr_compare_images_device: histograms of one chunk of images, SSIM partials [image][block], the records; RR_METRICS_HIST
-    DevBuf<uint32_t> d_mhist; DevBuf<double> d_ssim_part; DevBuf<rr_image_metrics> d_mrec; int metrics_hist = 0;
-    // staging of the host forms of rr_detect / rr_polar_to_cartesian (the device forms use none of it)
-    DevBuf<uint8_t> d_conv_in, d_conv_cart; DevBuf<rr_radar_point> d_conv_points; DevBuf<uint32_t> d_conv_offs;
-    DevBuf<float> d_sweep_in; DevBuf<rr_sweep_rec> d_sweep_tab; DevBuf<rr_radar_point> d_sweep_points;   // ... of the host forms of rr_sweep_table / rr_compensate_points / rr_polar_to_cartesian_sweep
+    // Scratch of the device forms, which run on arbitrary caller streams (grown by grow_on_stream): it is not staging and never aliases
+    // a host form's pool.  rr_score_images_device's sums; rr_compare_images_device: histograms of one chunk of images, SSIM partials
+    // [image][block], the records; RR_METRICS_HIST
+    DevBuf<unsigned long long> d_sse; DevBuf<uint32_t> d_mhist; DevBuf<double> d_ssim_part; DevBuf<rr_image_metrics> d_mrec; int metrics_hist = 0;
     // rr_register_points_device: the eight int64 sums per frame, one buffer per stream it has been called on (icp_mu guards the map, not the
-    // buffers: calls on one stream are ordered by that stream); and the host form's staging: source and target points, offsets + the target's
-    // count + correspondences, initial states, records
+    // buffers: calls on one stream are ordered by that stream)
     std::map<hipStream_t, DevBuf<long long>> icp_acc; std::mutex icp_mu;
-    DevBuf<rr_radar_point> d_icp_points; DevBuf<uint32_t> d_icp_words; DevBuf<double> d_icp_init; DevBuf<rr_icp_rec> d_icp_rec;
-    // staging of the host forms of rr_rasterize_points / rr_distance_field / rr_score_poses (the device forms use no context memory at all):
-    // points, offsets + the scan's count, the rasteriser's f64 states, the scorer's f32 states, the occupancy grid, the field, the records
-    DevBuf<rr_radar_point> d_field_points; DevBuf<uint32_t> d_field_words; DevBuf<double> d_field_init; DevBuf<float> d_field_states;
-    DevBuf<uint8_t> d_field_occ; DevBuf<uint16_t> d_field_map; DevBuf<rr_field_rec> d_field_rec;
-    DevBuf<uint32_t> d_conv_hist;      // ... and of rr_compare_images: one chunk's joint histograms on their way to the host
-    // rr_align_images_device: one chunk's curves (when the caller gives no buffer) and sums, the records; and the host forms' curves
-    DevBuf<long long> d_align_curve, d_conv_curve; DevBuf<unsigned long long> d_align_sums; DevBuf<rr_align_record> d_align_rec;
-    // rr_shift_images_device: one chunk's surface (when the caller gives no buffer) and sums, the reference's column and box sums, the
-    // records; and the host forms' own staging: images [chunk][H][W] (d_conv_in is sized for polar images), the reference, the surfaces
-    DevBuf<long long> d_shift_surf, d_shift_conv_xcorr; DevBuf<unsigned long long> d_shift_sums, d_shift_col, d_shift_box, d_shift_conv_sse;
-    DevBuf<rr_shift_record> d_shift_rec; DevBuf<uint8_t> d_shift_in, d_shift_ref;
+    // rr_align_images_device: one chunk's curves (when the caller gives no buffer) and sums, the records
+    DevBuf<long long> d_align_curve; DevBuf<unsigned long long> d_align_sums; DevBuf<rr_align_record> d_align_rec;
+    // rr_shift_images_device: one chunk's surface (when the caller gives no buffer) and sums, the reference's column and box sums, the records
+    DevBuf<long long> d_shift_surf; DevBuf<unsigned long long> d_shift_sums, d_shift_col, d_shift_box; DevBuf<rr_shift_record> d_shift_rec;
     // rr_match_descriptors_device: the rolled queries and their sums, one database chunk's keys and aux words, the slices' winners, the
-    // winners so far twice over ([2][keys | aux][n_query][top_k]: read from one, written to the other), the records; and the host forms'
-    // staging: descriptors on their way down, queries and one database chunk on their way up, that chunk's sse / shift on their way down
-    DevBuf<uint8_t> d_place_rolls, d_place_desc, d_place_query, d_place_db; DevBuf<uint32_t> d_place_qsums, d_place_conv_sse;
-    DevBuf<unsigned long long> d_place_keys, d_place_aux, d_place_part, d_place_win; DevBuf<rr_place_match> d_place_rec; DevBuf<uint16_t> d_place_conv_shift;
-    // staging of the host forms of rr_annotate_labels / rr_polar_to_cartesian_labels and of rr_simulate_batch_annotations (the device forms use none
-    // of it): planes on their way up or straight from the provenance chain, records, skip counts and resampled planes on their way down, the scratch
-    DevBuf<uint32_t> d_note_planes, d_note_skipped, d_note_cart; DevBuf<uint8_t> d_note_imgs; DevBuf<rr_object_note> d_note_rec; DevBuf<uint4> d_note_scratch;
+    // winners so far twice over ([2][keys | aux][n_query][top_k]: read from one, written to the other), the records
+    DevBuf<uint8_t> d_place_rolls; DevBuf<uint32_t> d_place_qsums;
+    DevBuf<unsigned long long> d_place_keys, d_place_aux, d_place_part, d_place_win; DevBuf<rr_place_match> d_place_rec;
+    StagePool stage;             // the round trips of the host forms on c->stream (rr_images.hip, rr_sets.hip)
     void* h_rb = nullptr; size_t h_rb_bytes = 0;         // page-locked: read_back()
     void* h_frame = nullptr; size_t h_frame_bytes = 0;   // page-locked: error bits + per-pass counters of rr_simulate's frame
 

@@ -1,7 +1,7 @@
 // rr_images.hip -- the C ABI's image entry points: images in, records / points / images out.  PSNR scores and metrics against a reference image
 // (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), place recognition (rr_place.hip), point clouds and Cartesian images (rr_detect.hip), sweep compensation (rr_deskew.hip), scan matching (rr_icp.hip), the likelihood field (rr_field.hip), object annotations (rr_notes.hip): each in a device form, which runs on the
-// caller's buffers and stream, and a host form, which stages through the context's own buffers on c->stream.
-#include "rr_ctx.h"
+// caller's buffers and stream, and a host form, which drains c->stream and makes its round trip through a Stage over the context's pool (rr_stage.h).
+#include "rr_stage.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -257,37 +257,37 @@ int records_back(rr_ctx* c, void* rec, const void* d_rec, size_t bytes, hipStrea
     return 0;
 }
 
-// the way into a host form: c->stream drained (the staging buffers may be reallocated), room for `m` images in d_conv_in, for the
-// reference image if there is one, and for whatever `ensure_more` sizes; then the reference and the `m` images go up on c->stream
-template <typename EnsureMore>
-int stage_images(rr_ctx* c, const uint8_t* imgs_u8, size_t m, const uint8_t* ref_u8, EnsureMore ensure_more)
+// The chunked host forms (compare, align, shift, describe): `n` images of `npx` bytes, kChunk at a time through one slot of the stage.
+// `chunk(d_imgs, at, m)` runs the device form on the `m` staged images, which drains c->stream, and brings that chunk's surfaces home;
+// the forms keep their records in a host vector and write the caller's once every chunk has succeeded
+template <typename Chunk>
+int in_chunks(rr_ctx* c, Stage& st, const uint8_t* imgs_u8, size_t n, size_t npx, Chunk chunk)
 {
-    const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles;
-    RR_HIP(c, hipStreamSynchronize(c->stream));
-    RR_HIP(c, c->d_conv_in.ensure(m * npx));
-    if (ref_u8) RR_HIP(c, c->d_ref_img.ensure(npx));
-    int rc = ensure_more(); if (rc) return rc;
-    if (ref_u8) RR_HIP(c, hipMemcpyAsync(c->d_ref_img.p, ref_u8, npx, hipMemcpyHostToDevice, c->stream));
-    RR_HIP(c, hipMemcpyAsync(c->d_conv_in.p, imgs_u8, m * npx, hipMemcpyHostToDevice, c->stream));
+    uint8_t* d_imgs;
+    RR_HIP(c, st.room(std::min(n, kChunk) * npx, d_imgs));
+    for (size_t at = 0; at < n; at += kChunk) {
+        const size_t m = std::min(kChunk, n - at);
+        RR_HIP(c, st.again(d_imgs, imgs_u8 + at * npx, m * npx));
+        const int rc = chunk(d_imgs, at, m); if (rc) return rc;
+    }
     return 0;
 }
 
-// rr_compare_images / rr_align_images: `n` images against a reference, kChunk at a time through d_conv_in.  `chunk(at, m, rec)` runs the device
-// form on the `m` staged images and brings that chunk's histograms or curves down; the caller's records are written once every chunk has succeeded
-template <typename Rec, typename EnsureMore, typename Chunk>
-int in_chunks(rr_ctx* c, const uint8_t* imgs_u8, size_t n, const uint8_t* ref_u8, Rec* out, EnsureMore ensure_more, Chunk chunk)
+// The per-frame point run on its way up: the offsets [n][n_angles + 1], whose last word of a frame is its total, and of every frame its
+// first min(total, max_points) points -- nothing beyond them moves.  `totals` serves the same run on the way down (Stage::out_rows)
+int up_points(rr_ctx* c, Stage& st, const rr_radar_point* points, const uint32_t* offsets, size_t n, size_t max_points, std::vector<uint32_t>& totals,
+              rr_radar_point*& d_points, uint32_t*& d_offsets)
 {
-    const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles;
-    int rc = stage_images(c, imgs_u8, std::min(n, kChunk), ref_u8, ensure_more); if (rc) return rc;
-    std::vector<Rec> rec(n);
-    for (size_t at = 0; at < n; at += kChunk) {
-        const size_t m = std::min(kChunk, n - at);
-        if (at) RR_HIP(c, hipMemcpyAsync(c->d_conv_in.p, imgs_u8 + at * npx, m * npx, hipMemcpyHostToDevice, c->stream));
-        rc = chunk(at, m, rec.data() + at); if (rc) return rc;
-    }
-    std::copy(rec.begin(), rec.end(), out);
+    const size_t A = (size_t)c->cfg.n_angles;
+    totals.resize(n);
+    for (size_t f = 0; f < n; f++) totals[f] = offsets[f * (A + 1) + A];
+    RR_HIP(c, st.up(offsets, n * (A + 1), d_offsets));
+    RR_HIP(c, st.up_rows(points, n, max_points, totals.data(), d_points));
     return 0;
 }
+
+// what every rr_simulate_batch_* form passes before anything is handed out
+auto frame_gate(rr_ctx* c) { return [c] { return report_frame_errors(c); }; }
 
 }  // namespace
 
@@ -320,7 +320,7 @@ int rr_score_images_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_images, co
     hipStream_t s = stream_of(c, stream);
     const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles;
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "sse words");
-    if (c->d_sse.n < (size_t)n_images) { RR_HIP(c, hipStreamSynchronize(s)); RR_HIP(c, c->d_sse.ensure((size_t)n_images)); }
+    RR_HIP(c, grow_on_stream(s, need(c->d_sse, (size_t)n_images)));
     RR_HIP(c, hipMemsetAsync(c->d_sse.p, 0, (size_t)n_images * sizeof(uint64_t), s));
     launch_score(d_imgs_u8, d_ref_u8, npx, n_images, c->d_sse.p, s);
     std::vector<uint64_t> sse((size_t)n_images);
@@ -347,13 +347,8 @@ int rr_compare_images_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_images, 
     const int n_blocks = ssim ? ssim_blocks(g.n_cells, g.n_angles, win_size) : 0;
     const double ssim_count = ssim ? (double)(g.n_cells - win_size + 1) * (double)(g.n_angles - win_size + 1) : 1.0;
     const bool own_hist = info && !d_joint_hist;
-    if ((psnr && c->d_sse.n < n) || (own_hist && c->d_mhist.n < chunk * kBins) || (ssim && c->d_ssim_part.n < chunk * (size_t)n_blocks) || c->d_mrec.n < n) {
-        RR_HIP(c, hipStreamSynchronize(s));             // an earlier call's kernels may still read what is freed here
-        if (psnr) RR_HIP(c, c->d_sse.ensure(n));
-        if (own_hist) RR_HIP(c, c->d_mhist.ensure(chunk * kBins));
-        if (ssim) RR_HIP(c, c->d_ssim_part.ensure(chunk * (size_t)n_blocks));
-        RR_HIP(c, c->d_mrec.ensure(n));
-    }
+    RR_HIP(c, grow_on_stream(s, need(c->d_sse, psnr ? n : 0), need(c->d_mhist, own_hist ? chunk * kBins : 0),
+                             need(c->d_ssim_part, ssim ? chunk * (size_t)n_blocks : 0), need(c->d_mrec, n)));
     if (psnr) {
         RR_HIP(c, hipMemsetAsync(c->d_sse.p, 0, n * sizeof(uint64_t), s));
         launch_score(d_imgs_u8, d_ref_u8, npx, n_images, c->d_sse.p, s);
@@ -384,16 +379,20 @@ int rr_compare_images(rr_ctx* c, const uint8_t* imgs_u8, int n_images, const uin
 {
     int rc = check_compare(c, "rr_compare_images", imgs_u8, n_images, ref_u8, which, win_size, out, joint_hist); if (rc) return rc;
     RR_HIP(c, hipSetDevice(c->device));
-    const size_t n = (size_t)n_images;
-    return in_chunks(c, imgs_u8, n, ref_u8, out,
-        [&]() { if (joint_hist) RR_HIP(c, c->d_conv_hist.ensure(std::min(n, kChunk) * kBins)); return 0; },
-        [&](size_t at, size_t m, rr_image_metrics* rec) {
-            // one chunk of the device form, its histograms into this form's own staging buffer
-            const int rcc = rr_compare_images_device(c, c->d_conv_in.p, (int)m, c->d_ref_img.p, which, win_size, rec,
-                                                     joint_hist ? c->d_conv_hist.p : nullptr, c->stream); if (rcc) return rcc;
-            if (joint_hist) RR_HIP(c, hipMemcpy(joint_hist + at * kBins, c->d_conv_hist.p, m * kBins * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            return 0;
-        });
+    const size_t n = (size_t)n_images, npx = (size_t)c->cfg.n_cells * c->cfg.n_angles;
+    RR_STAGE(c, st);
+    uint8_t* d_ref; uint32_t* d_hist = nullptr;
+    RR_HIP(c, st.up(ref_u8, npx, d_ref));
+    if (joint_hist) RR_HIP(c, st.room(std::min(n, kChunk) * kBins, d_hist));
+    std::vector<rr_image_metrics> rec(n);
+    rc = in_chunks(c, st, imgs_u8, n, npx, [&](const uint8_t* d_imgs, size_t at, size_t m) {
+        // one chunk of the device form, its histograms into this form's own room
+        const int rcc = rr_compare_images_device(c, d_imgs, (int)m, d_ref, which, win_size, rec.data() + at, d_hist, c->stream); if (rcc) return rcc;
+        if (joint_hist) RR_HIP(c, hipMemcpy(joint_hist + at * kBins, d_hist, m * kBins * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        return 0;
+    }); if (rc) return rc;
+    std::copy(rec.begin(), rec.end(), out);
+    return 0;
 }
 
 // ---- azimuth registration: the circular cross-correlation over all shifts (rr_align.hip) ------------------------------
@@ -408,12 +407,7 @@ int rr_align_images_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_images, co
     const size_t npx = (size_t)g.n_cells * g.n_angles, n = (size_t)n_images, A = (size_t)g.n_angles;
     const size_t chunk = std::min(n, kChunk);
     static_assert(sizeof(long long) == sizeof(int64_t), "curve words");
-    if ((!d_xcorr && c->d_align_curve.n < chunk * A) || c->d_align_sums.n < 2 * (chunk + 1) || c->d_align_rec.n < n) {
-        RR_HIP(c, hipStreamSynchronize(s));             // an earlier call's kernels may still read what is freed here
-        if (!d_xcorr) RR_HIP(c, c->d_align_curve.ensure(chunk * A));
-        RR_HIP(c, c->d_align_sums.ensure(2 * (chunk + 1)));
-        RR_HIP(c, c->d_align_rec.ensure(n));
-    }
+    RR_HIP(c, grow_on_stream(s, need(c->d_align_curve, d_xcorr ? 0 : chunk * A), need(c->d_align_sums, 2 * (chunk + 1)), need(c->d_align_rec, n)));
     for (size_t at = 0; at < n; at += kChunk) {
         const int m = (int)std::min(kChunk, n - at);
         const uint8_t* imgs = d_imgs_u8 + at * npx;
@@ -439,15 +433,19 @@ int rr_align_images(rr_ctx* c, const uint8_t* imgs_u8, int n_images, const uint8
 {
     int rc = check_align(c, "rr_align_images", imgs_u8, n_images, 65535, ref_u8, cell_begin, cell_end, out); if (rc) return rc;
     RR_HIP(c, hipSetDevice(c->device));
-    const size_t n = (size_t)n_images, A = (size_t)c->cfg.n_angles;
-    return in_chunks(c, imgs_u8, n, ref_u8, out,
-        [&]() { if (xcorr) RR_HIP(c, c->d_conv_curve.ensure(std::min(n, kChunk) * A)); return 0; },
-        [&](size_t at, size_t m, rr_align_record* rec) {
-            const int rcc = rr_align_images_device(c, c->d_conv_in.p, (int)m, c->d_ref_img.p, cell_begin, cell_end, rec,
-                                                   xcorr ? reinterpret_cast<int64_t*>(c->d_conv_curve.p) : nullptr, c->stream); if (rcc) return rcc;
-            if (xcorr) RR_HIP(c, hipMemcpy(xcorr + at * A, c->d_conv_curve.p, m * A * sizeof(int64_t), hipMemcpyDeviceToHost));
-            return 0;
-        });
+    const size_t n = (size_t)n_images, A = (size_t)c->cfg.n_angles, npx = (size_t)c->cfg.n_cells * A;
+    RR_STAGE(c, st);
+    uint8_t* d_ref; int64_t* d_curve = nullptr;
+    RR_HIP(c, st.up(ref_u8, npx, d_ref));
+    if (xcorr) RR_HIP(c, st.room(std::min(n, kChunk) * A, d_curve));
+    std::vector<rr_align_record> rec(n);
+    rc = in_chunks(c, st, imgs_u8, n, npx, [&](const uint8_t* d_imgs, size_t at, size_t m) {
+        const int rcc = rr_align_images_device(c, d_imgs, (int)m, d_ref, cell_begin, cell_end, rec.data() + at, d_curve, c->stream); if (rcc) return rcc;
+        if (xcorr) RR_HIP(c, hipMemcpy(xcorr + at * A, d_curve, m * A * sizeof(int64_t), hipMemcpyDeviceToHost));
+        return 0;
+    }); if (rc) return rc;
+    std::copy(rec.begin(), rec.end(), out);
+    return 0;
 }
 
 int rr_simulate_batch_align(rr_ctx* c, const float* poses, int n_frames, const uint8_t* ref_img_u8, int cell_begin, int cell_end,
@@ -459,18 +457,17 @@ int rr_simulate_batch_align(rr_ctx* c, const float* poses, int n_frames, const u
     if (!poses) return fail(c, -3, "rr_simulate_batch_align: null poses");
     RR_HIP(c, hipSetDevice(c->device));
     const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles, n = (size_t)n_frames, A = (size_t)c->cfg.n_angles;
-    RR_HIP(c, hipStreamSynchronize(c->stream));        // the buffers may be reallocated below
-    RR_HIP(c, c->d_param_imgs.ensure(n * npx));
-    RR_HIP(c, c->d_ref_img.ensure(npx));
-    if (xcorr) RR_HIP(c, c->d_conv_curve.ensure(n * A));
-    RR_HIP(c, hipMemcpyAsync(c->d_ref_img.p, ref_img_u8, npx, hipMemcpyHostToDevice, c->stream));
-    rc = rr_simulate_batch_device(c, poses, n_frames, c->d_param_imgs.p, c->stream); if (rc) return rc;
+    RR_STAGE(c, st);
+    uint8_t *d_imgs, *d_ref; int64_t* d_curve = nullptr;
+    RR_HIP(c, st.room(n * npx, d_imgs));
+    RR_HIP(c, st.up(ref_img_u8, npx, d_ref));
+    if (xcorr) RR_HIP(c, st.room(n * A, d_curve));
+    rc = rr_simulate_batch_device(c, poses, n_frames, d_imgs, c->stream); if (rc) return rc;
     std::vector<rr_align_record> rec(n);
-    rc = rr_align_images_device(c, c->d_param_imgs.p, n_frames, c->d_ref_img.p, cell_begin, cell_end, rec.data(),
-                                xcorr ? reinterpret_cast<int64_t*>(c->d_conv_curve.p) : nullptr, c->stream); if (rc) return rc;   // synchronises the stream
-    rc = report_frame_errors(c); if (rc) return rc;     // before anything is handed out
-    if (out_imgs_u8) RR_HIP(c, hipMemcpy(out_imgs_u8, c->d_param_imgs.p, n * npx, hipMemcpyDeviceToHost));
-    if (xcorr) RR_HIP(c, hipMemcpy(xcorr, c->d_conv_curve.p, n * A * sizeof(int64_t), hipMemcpyDeviceToHost));
+    rc = rr_align_images_device(c, d_imgs, n_frames, d_ref, cell_begin, cell_end, rec.data(), d_curve, c->stream); if (rc) return rc;
+    st.out(out_imgs_u8, d_imgs, n * npx, false);
+    st.out(xcorr, d_curve, n * A, false);
+    rc = st.commit(frame_gate(c)); if (rc) return rc;
     std::copy(rec.begin(), rec.end(), out);
     return 0;
 }
@@ -487,15 +484,8 @@ int rr_shift_images_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_images, co
     const size_t npx = (size_t)H * W, n = (size_t)n_images, ND = (size_t)D * D, n_col = 2 * (size_t)D * W;
     const size_t chunk = std::min(n, kChunk);
     static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(unsigned long long) == sizeof(uint64_t), "surface words");
-    if ((!d_xcorr && c->d_shift_surf.n < chunk * ND) || c->d_shift_sums.n < 2 * chunk || c->d_shift_col.n < n_col || c->d_shift_box.n < 2 * ND ||
-        c->d_shift_rec.n < n) {
-        RR_HIP(c, hipStreamSynchronize(s));             // an earlier call's kernels may still read what is freed here
-        if (!d_xcorr) RR_HIP(c, c->d_shift_surf.ensure(chunk * ND));
-        RR_HIP(c, c->d_shift_sums.ensure(2 * chunk));
-        RR_HIP(c, c->d_shift_col.ensure(n_col));
-        RR_HIP(c, c->d_shift_box.ensure(2 * ND));
-        RR_HIP(c, c->d_shift_rec.ensure(n));
-    }
+    RR_HIP(c, grow_on_stream(s, need(c->d_shift_surf, d_xcorr ? 0 : chunk * ND), need(c->d_shift_sums, 2 * chunk), need(c->d_shift_col, n_col),
+                             need(c->d_shift_box, 2 * ND), need(c->d_shift_rec, n)));
     launch_shift_box(d_ref_u8, H, W, S, c->d_shift_col.p, c->d_shift_box.p, s);      // once per call: every image meets the same reference
     for (size_t at = 0; at < n; at += kChunk) {
         const int m = (int)std::min(kChunk, n - at);
@@ -533,22 +523,19 @@ int rr_shift_images(rr_ctx* c, const uint8_t* imgs_u8, int n_images, const uint8
     int rc = check_shift(c, "rr_shift_images", imgs_u8, n_images, 65535, ref_u8, height, width, max_shift, out); if (rc) return rc;
     RR_HIP(c, hipSetDevice(c->device));
     const size_t n = (size_t)n_images, npx = (size_t)height * width, D = 2 * (size_t)max_shift + 1, ND = D * D, chunk = std::min(n, kChunk);
-    RR_HIP(c, hipStreamSynchronize(c->stream));        // the staging buffers may be reallocated
-    RR_HIP(c, c->d_shift_in.ensure(chunk * npx));
-    RR_HIP(c, c->d_shift_ref.ensure(npx));
-    if (xcorr) RR_HIP(c, c->d_shift_conv_xcorr.ensure(chunk * ND));
-    if (sse) RR_HIP(c, c->d_shift_conv_sse.ensure(chunk * ND));
-    RR_HIP(c, hipMemcpyAsync(c->d_shift_ref.p, ref_u8, npx, hipMemcpyHostToDevice, c->stream));
+    RR_STAGE(c, st);
+    uint8_t* d_ref; int64_t* d_xcorr = nullptr; uint64_t* d_sse = nullptr;
+    RR_HIP(c, st.up(ref_u8, npx, d_ref));
+    if (xcorr) RR_HIP(c, st.room(chunk * ND, d_xcorr));
+    if (sse) RR_HIP(c, st.room(chunk * ND, d_sse));
     std::vector<rr_shift_record> rec(n);
-    for (size_t at = 0; at < n; at += kChunk) {
-        const size_t m = std::min(kChunk, n - at);
-        RR_HIP(c, hipMemcpyAsync(c->d_shift_in.p, imgs_u8 + at * npx, m * npx, hipMemcpyHostToDevice, c->stream));
-        rc = rr_shift_images_device(c, c->d_shift_in.p, (int)m, c->d_shift_ref.p, height, width, max_shift, rec.data() + at,
-                                    xcorr ? reinterpret_cast<int64_t*>(c->d_shift_conv_xcorr.p) : nullptr,
-                                    sse ? reinterpret_cast<uint64_t*>(c->d_shift_conv_sse.p) : nullptr, c->stream); if (rc) return rc;
-        if (xcorr) RR_HIP(c, hipMemcpy(xcorr + at * ND, c->d_shift_conv_xcorr.p, m * ND * sizeof(int64_t), hipMemcpyDeviceToHost));
-        if (sse) RR_HIP(c, hipMemcpy(sse + at * ND, c->d_shift_conv_sse.p, m * ND * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    }
+    rc = in_chunks(c, st, imgs_u8, n, npx, [&](const uint8_t* d_imgs, size_t at, size_t m) {
+        const int rcc = rr_shift_images_device(c, d_imgs, (int)m, d_ref, height, width, max_shift, rec.data() + at, d_xcorr, d_sse, c->stream);
+        if (rcc) return rcc;
+        if (xcorr) RR_HIP(c, hipMemcpy(xcorr + at * ND, d_xcorr, m * ND * sizeof(int64_t), hipMemcpyDeviceToHost));
+        if (sse) RR_HIP(c, hipMemcpy(sse + at * ND, d_sse, m * ND * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        return 0;
+    }); if (rc) return rc;
     std::copy(rec.begin(), rec.end(), out);
     return 0;
 }
@@ -565,23 +552,23 @@ int rr_simulate_batch_shift(rr_ctx* c, const float* poses, int n_frames, const u
     const rr_config& g = c->cfg;
     const size_t npx = (size_t)g.n_cells * g.n_angles, n = (size_t)n_frames, ncart = (size_t)cfg->width * cfg->width;
     const size_t D = 2 * (size_t)max_shift + 1, ND = D * D;
-    RR_HIP(c, hipStreamSynchronize(c->stream));        // the buffers may be reallocated below
-    RR_HIP(c, c->d_param_imgs.ensure(n * npx));
-    RR_HIP(c, c->d_ref_img.ensure(npx));
-    RR_HIP(c, c->d_shift_in.ensure(n * ncart));
-    RR_HIP(c, c->d_shift_ref.ensure(ncart));
-    if (xcorr) RR_HIP(c, c->d_shift_conv_xcorr.ensure(n * ND));
-    RR_HIP(c, hipMemcpyAsync(c->d_ref_img.p, ref_polar_u8, npx, hipMemcpyHostToDevice, c->stream));
-    rc = rr_simulate_batch_device(c, poses, n_frames, c->d_param_imgs.p, c->stream); if (rc) return rc;
+    RR_STAGE(c, st);
+    uint8_t *d_imgs, *d_ref, *d_cart, *d_ref_cart; int64_t* d_xcorr = nullptr;
+    RR_HIP(c, st.room(n * npx, d_imgs));
+    RR_HIP(c, st.up(ref_polar_u8, npx, d_ref));
+    RR_HIP(c, st.room(n * ncart, d_cart));
+    RR_HIP(c, st.room(ncart, d_ref_cart));
+    if (xcorr) RR_HIP(c, st.room(n * ND, d_xcorr));
+    rc = rr_simulate_batch_device(c, poses, n_frames, d_imgs, c->stream); if (rc) return rc;
     const PolarGrid G = polar_grid(g);
-    launch_cartesian(c->d_param_imgs.p, n_frames, *cfg, G, c->d_shift_in.p, c->stream);
-    launch_cartesian(c->d_ref_img.p, 1, *cfg, G, c->d_shift_ref.p, c->stream);
+    launch_cartesian(d_imgs, n_frames, *cfg, G, d_cart, c->stream);
+    launch_cartesian(d_ref, 1, *cfg, G, d_ref_cart, c->stream);
     std::vector<rr_shift_record> rec(n);
-    rc = rr_shift_images_device(c, c->d_shift_in.p, n_frames, c->d_shift_ref.p, cfg->width, cfg->width, max_shift, rec.data(),
-                                xcorr ? reinterpret_cast<int64_t*>(c->d_shift_conv_xcorr.p) : nullptr, nullptr, c->stream); if (rc) return rc;   // synchronises the stream
-    rc = report_frame_errors(c); if (rc) return rc;     // before anything is handed out
-    if (out_cart_u8) RR_HIP(c, hipMemcpy(out_cart_u8, c->d_shift_in.p, n * ncart, hipMemcpyDeviceToHost));
-    if (xcorr) RR_HIP(c, hipMemcpy(xcorr, c->d_shift_conv_xcorr.p, n * ND * sizeof(int64_t), hipMemcpyDeviceToHost));
+    rc = rr_shift_images_device(c, d_cart, n_frames, d_ref_cart, cfg->width, cfg->width, max_shift, rec.data(), d_xcorr, nullptr, c->stream);
+    if (rc) return rc;
+    st.out(out_cart_u8, d_cart, n * ncart, false);
+    st.out(xcorr, d_xcorr, n * ND, false);
+    rc = st.commit(frame_gate(c)); if (rc) return rc;
     std::copy(rec.begin(), rec.end(), out);
     return 0;
 }
@@ -602,16 +589,16 @@ int rr_describe_images(rr_ctx* c, const uint8_t* imgs_u8, int n, const rr_place_
     int rc = check_describe(c, "rr_describe_images", imgs_u8, n, 65535, cfg, desc); if (rc) return rc;
     RR_HIP(c, hipSetDevice(c->device));
     const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles, K = (size_t)cfg->n_rings * cfg->n_sectors, total = (size_t)n;
-    rc = stage_images(c, imgs_u8, std::min(total, kChunk), nullptr, [&]() { RR_HIP(c, c->d_place_desc.ensure(std::min(total, kChunk) * K)); return 0; });
-    if (rc) return rc;
+    RR_STAGE(c, st);
+    uint8_t* d_desc;
+    RR_HIP(c, st.room(std::min(total, kChunk) * K, d_desc));
     std::vector<uint8_t> all(total * K);                    // the caller's buffer is written once every chunk has succeeded
-    for (size_t at = 0; at < total; at += kChunk) {
-        const size_t m = std::min(kChunk, total - at);
-        if (at) RR_HIP(c, hipMemcpyAsync(c->d_conv_in.p, imgs_u8 + at * npx, m * npx, hipMemcpyHostToDevice, c->stream));
-        rc = rr_describe_images_device(c, c->d_conv_in.p, (int)m, cfg, c->d_place_desc.p, c->stream); if (rc) return rc;
-        RR_HIP(c, hipMemcpyAsync(all.data() + at * K, c->d_place_desc.p, m * K, hipMemcpyDeviceToHost, c->stream));
-        RR_HIP(c, hipStreamSynchronize(c->stream));         // the staging buffers are free again
-    }
+    rc = in_chunks(c, st, imgs_u8, total, npx, [&](const uint8_t* d_imgs, size_t at, size_t m) {
+        const int rcc = rr_describe_images_device(c, d_imgs, (int)m, cfg, d_desc, c->stream); if (rcc) return rcc;
+        RR_HIP(c, hipMemcpyAsync(all.data() + at * K, d_desc, m * K, hipMemcpyDeviceToHost, c->stream));
+        RR_HIP(c, hipStreamSynchronize(c->stream));         // the rooms are free again
+        return 0;
+    }); if (rc) return rc;
     std::copy(all.begin(), all.end(), desc);
     return 0;
 }
@@ -624,16 +611,13 @@ int rr_simulate_batch_describe(rr_ctx* c, const float* poses, int n_frames, cons
     if (!poses) return fail(c, -3, "rr_simulate_batch_describe: null poses");
     RR_HIP(c, hipSetDevice(c->device));
     const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles, n = (size_t)n_frames, K = (size_t)cfg->n_rings * cfg->n_sectors;
-    RR_HIP(c, hipStreamSynchronize(c->stream));        // the buffers may be reallocated below
-    RR_HIP(c, c->d_param_imgs.ensure(n * npx));
-    RR_HIP(c, c->d_place_desc.ensure(n * K));
-    rc = rr_simulate_batch_device(c, poses, n_frames, c->d_param_imgs.p, c->stream); if (rc) return rc;
-    rc = rr_describe_images_device(c, c->d_param_imgs.p, n_frames, cfg, c->d_place_desc.p, c->stream); if (rc) return rc;
-    std::vector<uint8_t> desc(n * K);
-    rc = records_back(c, desc.data(), c->d_place_desc.p, n * K, c->stream); if (rc) return rc;
-    rc = report_frame_errors(c); if (rc) return rc;     // before anything is handed out
-    std::copy(desc.begin(), desc.end(), out_desc);
-    return 0;
+    RR_STAGE(c, st);
+    uint8_t *d_imgs, *d_desc;
+    RR_HIP(c, st.room(n * npx, d_imgs));
+    RR_HIP(c, st.hold(out_desc, n * K, d_desc));
+    rc = rr_simulate_batch_device(c, poses, n_frames, d_imgs, c->stream); if (rc) return rc;
+    rc = rr_describe_images_device(c, d_imgs, n_frames, cfg, d_desc, c->stream); if (rc) return rc;
+    return st.commit(frame_gate(c));
 }
 
 int rr_match_descriptors_device(rr_ctx* c, const uint8_t* d_query, int n_query, const uint8_t* d_db, int n_db, int n_rings, int n_sectors, int top_k,
@@ -647,17 +631,8 @@ int rr_match_descriptors_device(rr_ctx* c, const uint8_t* d_query, int n_query, 
     const size_t chunk = std::min(n, std::max<size_t>(32, ((size_t)1 << 22) / nq / 32 * 32));
     const size_t n_rolls = nq * n_sectors * (size_t)place_kpad(n_rings, n_sectors), n_part = nq * place_slices(chunk) * k, n_win = nq * k;
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "key words");
-    if (c->d_place_rolls.n < n_rolls || c->d_place_qsums.n < 2 * nq || c->d_place_keys.n < nq * chunk || c->d_place_aux.n < nq * chunk ||
-        c->d_place_part.n < n_part || c->d_place_win.n < 4 * n_win || c->d_place_rec.n < n_win) {
-        RR_HIP(c, hipStreamSynchronize(s));             // an earlier call's kernels may still read what is freed here
-        RR_HIP(c, c->d_place_rolls.ensure(n_rolls));
-        RR_HIP(c, c->d_place_qsums.ensure(2 * nq));
-        RR_HIP(c, c->d_place_keys.ensure(nq * chunk));
-        RR_HIP(c, c->d_place_aux.ensure(nq * chunk));
-        RR_HIP(c, c->d_place_part.ensure(n_part));
-        RR_HIP(c, c->d_place_win.ensure(4 * n_win));
-        RR_HIP(c, c->d_place_rec.ensure(n_win));
-    }
+    RR_HIP(c, grow_on_stream(s, need(c->d_place_rolls, n_rolls), need(c->d_place_qsums, 2 * nq), need(c->d_place_keys, nq * chunk),
+                             need(c->d_place_aux, nq * chunk), need(c->d_place_part, n_part), need(c->d_place_win, 4 * n_win), need(c->d_place_rec, n_win)));
     launch_place_rolls(d_query, n_query, n_rings, n_sectors, c->d_place_rolls.p, c->d_place_qsums.p, s);
     // the winners so far, [2][keys | aux][n_query][top_k]: a chunk reads one half and writes the other.  No winner yet: every key ~0
     unsigned long long* half[2] = { c->d_place_win.p, c->d_place_win.p + 2 * n_win };
@@ -688,12 +663,12 @@ int rr_match_descriptors(rr_ctx* c, const uint8_t* query, int n_query, const uin
     const size_t nq = (size_t)n_query, n = (size_t)n_db, k = (size_t)top_k, K = (size_t)n_rings * n_sectors;
     // the database goes up 16 MiB at a time; the chunks' winners are merged here by the same key
     const size_t chunk = std::min(n, std::max<size_t>(k, ((size_t)16 << 20) / K));
-    RR_HIP(c, hipStreamSynchronize(c->stream));        // the staging buffers may be reallocated
-    RR_HIP(c, c->d_place_query.ensure(nq * K));
-    RR_HIP(c, c->d_place_db.ensure(chunk * K));
-    if (sse) RR_HIP(c, c->d_place_conv_sse.ensure(nq * chunk));
-    if (shift) RR_HIP(c, c->d_place_conv_shift.ensure(nq * chunk));
-    RR_HIP(c, hipMemcpyAsync(c->d_place_query.p, query, nq * K, hipMemcpyHostToDevice, c->stream));
+    RR_STAGE(c, st);
+    uint8_t *d_query, *d_db; uint32_t* d_sse = nullptr; uint16_t* d_shift = nullptr;
+    RR_HIP(c, st.up(query, nq * K, d_query));
+    RR_HIP(c, st.room(chunk * K, d_db));
+    if (sse) RR_HIP(c, st.room(nq * chunk, d_sse));
+    if (shift) RR_HIP(c, st.room(nq * chunk, d_shift));
     auto before = [](const rr_place_match& a, const rr_place_match& b) { return a.sse != b.sse ? a.sse < b.sse : a.index < b.index; };
     std::vector<std::vector<rr_place_match>> best(nq);
     std::vector<rr_place_match> rec(nq * k);
@@ -701,15 +676,14 @@ int rr_match_descriptors(rr_ctx* c, const uint8_t* query, int n_query, const uin
     std::vector<uint16_t> shift_all(shift ? nq * n : 0);
     for (size_t at = 0; at < n; at += chunk) {
         const size_t m = std::min(chunk, n - at), km = std::min(k, m);
-        RR_HIP(c, hipMemcpyAsync(c->d_place_db.p, db + at * K, m * K, hipMemcpyHostToDevice, c->stream));
-        rc = rr_match_descriptors_device(c, c->d_place_query.p, n_query, c->d_place_db.p, (int)m, n_rings, n_sectors, (int)km, rec.data(),
-                                         sse ? c->d_place_conv_sse.p : nullptr, shift ? c->d_place_conv_shift.p : nullptr, c->stream); if (rc) return rc;
+        RR_HIP(c, st.again(d_db, db + at * K, m * K));
+        rc = rr_match_descriptors_device(c, d_query, n_query, d_db, (int)m, n_rings, n_sectors, (int)km, rec.data(), d_sse, d_shift, c->stream); if (rc) return rc;
         for (size_t q = 0; q < nq; q++) {
             for (size_t j = 0; j < km; j++) { rr_place_match r = rec[q * km + j]; r.index += (uint32_t)at; best[q].push_back(r); }
             std::sort(best[q].begin(), best[q].end(), before);
             if (best[q].size() > k) best[q].resize(k);
-            if (sse) RR_HIP(c, hipMemcpy(sse_all.data() + q * n + at, c->d_place_conv_sse.p + q * m, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            if (shift) RR_HIP(c, hipMemcpy(shift_all.data() + q * n + at, c->d_place_conv_shift.p + q * m, m * sizeof(uint16_t), hipMemcpyDeviceToHost));
+            if (sse) RR_HIP(c, hipMemcpy(sse_all.data() + q * n + at, d_sse + q * m, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            if (shift) RR_HIP(c, hipMemcpy(shift_all.data() + q * n + at, d_shift + q * m, m * sizeof(uint16_t), hipMemcpyDeviceToHost));
         }
     }
     for (size_t q = 0; q < nq; q++) std::copy(best[q].begin(), best[q].end(), out + q * k);
@@ -742,19 +716,16 @@ int rr_detect(rr_ctx* c, const uint8_t* imgs_u8, int n_frames, const rr_detect_c
 {
     int rc = check_detect(c, "rr_detect", imgs_u8, n_frames, cfg, points, max_points, offsets); if (rc) return rc;
     RR_HIP(c, hipSetDevice(c->device));
-    const size_t n_offs = (size_t)n_frames * (c->cfg.n_angles + 1), n_pts = (size_t)n_frames * (size_t)max_points;
-    rc = stage_images(c, imgs_u8, (size_t)n_frames, nullptr, [&]() {
-        RR_HIP(c, c->d_conv_offs.ensure(n_offs));
-        if (n_pts) RR_HIP(c, c->d_conv_points.ensure(n_pts));
-        return 0;
-    });
-    if (rc) return rc;
-    rc = rr_detect_device(c, c->d_conv_in.p, n_frames, cfg, n_pts ? c->d_conv_points.p : nullptr, max_points, c->d_conv_offs.p, c->stream);
-    if (rc) return rc;
-    RR_HIP(c, hipMemcpyAsync(offsets, c->d_conv_offs.p, n_offs * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    if (n_pts) RR_HIP(c, hipMemcpyAsync(points, c->d_conv_points.p, n_pts * sizeof(rr_radar_point), hipMemcpyDeviceToHost, c->stream));
-    RR_HIP(c, hipStreamSynchronize(c->stream));
-    return 0;
+    const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles, n_offs = (size_t)n_frames * (c->cfg.n_angles + 1), n_pts = (size_t)n_frames * (size_t)max_points;
+    RR_STAGE(c, st);
+    uint8_t* d_imgs; uint32_t* d_offs; rr_radar_point* d_points = nullptr;
+    RR_HIP(c, st.up(imgs_u8, (size_t)n_frames * npx, d_imgs));
+    RR_HIP(c, st.room(n_offs, d_offs));
+    if (n_pts) RR_HIP(c, st.room(n_pts, d_points));
+    rc = rr_detect_device(c, d_imgs, n_frames, cfg, d_points, max_points, d_offs, c->stream); if (rc) return rc;
+    st.out(offsets, d_offs, n_offs, false);
+    if (n_pts) st.out(points, d_points, n_pts, false);
+    return st.commit();
 }
 
 int rr_polar_to_cartesian_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_frames, const rr_cartesian_config* cfg,
@@ -771,13 +742,14 @@ int rr_polar_to_cartesian(rr_ctx* c, const uint8_t* imgs_u8, int n_frames, const
 {
     int rc = check_cartesian(c, "rr_polar_to_cartesian", imgs_u8, n_frames, cfg, cart_u8); if (rc) return rc;
     RR_HIP(c, hipSetDevice(c->device));
-    const size_t n_out = (size_t)n_frames * cfg->width * cfg->width;
-    rc = stage_images(c, imgs_u8, (size_t)n_frames, nullptr, [&]() { RR_HIP(c, c->d_conv_cart.ensure(n_out)); return 0; });
-    if (rc) return rc;
-    rc = rr_polar_to_cartesian_device(c, c->d_conv_in.p, n_frames, cfg, c->d_conv_cart.p, c->stream); if (rc) return rc;
-    RR_HIP(c, hipMemcpyAsync(cart_u8, c->d_conv_cart.p, n_out, hipMemcpyDeviceToHost, c->stream));
-    RR_HIP(c, hipStreamSynchronize(c->stream));
-    return 0;
+    const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles, n_out = (size_t)n_frames * cfg->width * cfg->width;
+    RR_STAGE(c, st);
+    uint8_t *d_imgs, *d_cart;
+    RR_HIP(c, st.up(imgs_u8, (size_t)n_frames * npx, d_imgs));
+    RR_HIP(c, st.room(n_out, d_cart));
+    rc = rr_polar_to_cartesian_device(c, d_imgs, n_frames, cfg, d_cart, c->stream); if (rc) return rc;
+    st.out(cart_u8, d_cart, n_out, false);
+    return st.commit();
 }
 
 // ---- sweep compensation (rr_deskew.hip) -------------------------------------------------------------------------------
@@ -808,20 +780,14 @@ int rr_sweep_table(rr_ctx* c, const float* az_poses, const float* ref_poses, con
     if (!finite(az_poses, n_az) || !finite(ref_poses, n_ref) || !finite(sensor_vel, n_vel)) return fail(c, -3, w + ": a non-finite pose or velocity");
     if (!unit(az_poses, n * A) || !unit(ref_poses, n)) return fail(c, -3, w + ": a quaternion whose squared norm is off 1 by more than 1e-3");
     RR_HIP(c, hipSetDevice(c->device));
-    RR_HIP(c, hipStreamSynchronize(c->stream));        // the staging buffers may be reallocated
-    RR_HIP(c, c->d_sweep_in.ensure(n_az + n_ref + n * 3));
-    RR_HIP(c, c->d_sweep_tab.ensure(n * A));
-    float* d_az = c->d_sweep_in.p;
-    float* d_ref = d_az + n_az;
-    float* d_vel = d_ref + n_ref;
-    RR_HIP(c, hipMemcpyAsync(d_az, az_poses, n_az * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    RR_HIP(c, hipMemcpyAsync(d_ref, ref_poses, n_ref * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if (n_vel) RR_HIP(c, hipMemcpyAsync(d_vel, sensor_vel, n_vel * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    rc = rr_sweep_table_device(c, d_az, d_ref, n_vel ? d_vel : nullptr, gain, n_frames, c->d_sweep_tab.p, c->stream); if (rc) return rc;
-    std::vector<rr_sweep_rec> rec(n * A);               // the caller's buffer is written once everything has arrived
-    rc = records_back(c, rec.data(), c->d_sweep_tab.p, n * A * sizeof(rr_sweep_rec), c->stream); if (rc) return rc;
-    std::copy(rec.begin(), rec.end(), table);
-    return 0;
+    RR_STAGE(c, st);
+    float *d_az, *d_ref, *d_vel; rr_sweep_rec* d_table;
+    RR_HIP(c, st.up(az_poses, n_az, d_az));
+    RR_HIP(c, st.up(ref_poses, n_ref, d_ref));
+    RR_HIP(c, st.up(sensor_vel, n_vel, d_vel));
+    RR_HIP(c, st.hold(table, n * A, d_table));
+    rc = rr_sweep_table_device(c, d_az, d_ref, d_vel, gain, n_frames, d_table, c->stream); if (rc) return rc;
+    return st.commit();
 }
 
 int rr_compensate_points_device(rr_ctx* c, const rr_radar_point* d_points, const uint32_t* d_offsets, int n_frames, int max_points,
@@ -841,26 +807,14 @@ int rr_compensate_points(rr_ctx* c, const rr_radar_point* points, const uint32_t
     int rc = check_compensate(c, "rr_compensate_points", points, offsets, n_frames, max_points, table, out, false); if (rc) return rc;
     if (max_points == 0) return 0;
     RR_HIP(c, hipSetDevice(c->device));
-    const size_t n = (size_t)n_frames, A = (size_t)c->cfg.n_angles, mp = (size_t)max_points, n_offs = n * (A + 1);
-    RR_HIP(c, hipStreamSynchronize(c->stream));        // the staging buffers may be reallocated
-    RR_HIP(c, c->d_sweep_points.ensure(n * mp));
-    RR_HIP(c, c->d_conv_offs.ensure(n_offs));
-    RR_HIP(c, c->d_sweep_tab.ensure(n * A));
-    RR_HIP(c, hipMemcpyAsync(c->d_conv_offs.p, offsets, n_offs * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    RR_HIP(c, hipMemcpyAsync(c->d_sweep_tab.p, table, n * A * sizeof(rr_sweep_rec), hipMemcpyHostToDevice, c->stream));
-    // the points of a frame: its first min(total, max_points) slots, in and out; nothing beyond them moves
-    auto count = [&](size_t f) { return std::min<size_t>(offsets[f * (A + 1) + A], mp); };
-    for (size_t f = 0; f < n; f++)
-        if (count(f)) RR_HIP(c, hipMemcpyAsync(c->d_sweep_points.p + f * mp, points + f * mp, count(f) * sizeof(rr_radar_point), hipMemcpyHostToDevice, c->stream));
-    rc = rr_compensate_points_device(c, c->d_sweep_points.p, c->d_conv_offs.p, n_frames, max_points, c->d_sweep_tab.p, c->d_sweep_points.p, c->stream);
-    if (rc) return rc;
-    RR_HIP(c, hipGetLastError());
-    std::vector<rr_radar_point> got(n * mp);
-    for (size_t f = 0; f < n; f++)
-        if (count(f)) RR_HIP(c, hipMemcpyAsync(got.data() + f * mp, c->d_sweep_points.p + f * mp, count(f) * sizeof(rr_radar_point), hipMemcpyDeviceToHost, c->stream));
-    RR_HIP(c, hipStreamSynchronize(c->stream));
-    for (size_t f = 0; f < n; f++) std::copy(got.begin() + f * mp, got.begin() + f * mp + count(f), out + f * mp);
-    return 0;
+    const size_t n = (size_t)n_frames, A = (size_t)c->cfg.n_angles, mp = (size_t)max_points;
+    RR_STAGE(c, st);
+    std::vector<uint32_t> totals; rr_radar_point* d_points; uint32_t* d_offs; rr_sweep_rec* d_table;
+    rc = up_points(c, st, points, offsets, n, mp, totals, d_points, d_offs); if (rc) return rc;
+    RR_HIP(c, st.up(table, n * A, d_table));
+    rc = rr_compensate_points_device(c, d_points, d_offs, n_frames, max_points, d_table, d_points, c->stream); if (rc) return rc;      // in place
+    st.out_rows(out, d_points, n, mp, mp, totals.data());
+    return st.commit();
 }
 
 int rr_polar_to_cartesian_sweep_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_frames, const rr_cartesian_config* cfg, const rr_sweep_rec* d_table,
@@ -879,14 +833,15 @@ int rr_polar_to_cartesian_sweep(rr_ctx* c, const uint8_t* imgs_u8, int n_frames,
     int rc = check_cartesian_sweep(c, "rr_polar_to_cartesian_sweep", imgs_u8, n_frames, cfg, table, iterations, cart_u8, false);
     if (rc) return rc;
     RR_HIP(c, hipSetDevice(c->device));
-    const size_t n = (size_t)n_frames, A = (size_t)c->cfg.n_angles, n_out = n * cfg->width * cfg->width;
-    rc = stage_images(c, imgs_u8, n, nullptr, [&]() { RR_HIP(c, c->d_conv_cart.ensure(n_out)); RR_HIP(c, c->d_sweep_tab.ensure(n * A)); return 0; });
-    if (rc) return rc;
-    RR_HIP(c, hipMemcpyAsync(c->d_sweep_tab.p, table, n * A * sizeof(rr_sweep_rec), hipMemcpyHostToDevice, c->stream));
-    rc = rr_polar_to_cartesian_sweep_device(c, c->d_conv_in.p, n_frames, cfg, c->d_sweep_tab.p, iterations, c->d_conv_cart.p, c->stream); if (rc) return rc;
-    RR_HIP(c, hipMemcpyAsync(cart_u8, c->d_conv_cart.p, n_out, hipMemcpyDeviceToHost, c->stream));
-    RR_HIP(c, hipStreamSynchronize(c->stream));
-    return 0;
+    const size_t n = (size_t)n_frames, A = (size_t)c->cfg.n_angles, npx = (size_t)c->cfg.n_cells * A, n_out = n * cfg->width * cfg->width;
+    RR_STAGE(c, st);
+    uint8_t *d_imgs, *d_cart; rr_sweep_rec* d_table;
+    RR_HIP(c, st.up(imgs_u8, n * npx, d_imgs));
+    RR_HIP(c, st.up(table, n * A, d_table));
+    RR_HIP(c, st.room(n_out, d_cart));
+    rc = rr_polar_to_cartesian_sweep_device(c, d_imgs, n_frames, cfg, d_table, iterations, d_cart, c->stream); if (rc) return rc;
+    st.out(cart_u8, d_cart, n_out, false);
+    return st.commit();
 }
 
 // ---- scan matching (rr_icp.hip) ----------------------------------------------------------------------------------------
@@ -919,41 +874,24 @@ int rr_register_points(rr_ctx* c, const rr_radar_point* points, const uint32_t* 
 {
     const std::string w("rr_register_points");
     int rc = check_icp(c, w.c_str(), points, offsets, n_frames, max_points, tgt_points, true, max_tgt, gate, iterations, recs); if (rc) return rc;
-    const size_t n = (size_t)n_frames, A = (size_t)c->cfg.n_angles, mp = (size_t)max_points, mt = (size_t)max_tgt, n_offs = n * (A + 1);
+    const size_t n = (size_t)n_frames, mp = (size_t)max_points, mt = (size_t)max_tgt;
     for (size_t f = 0; init && f < n; f++) {
         const double h = std::sqrt(init[4 * f] * init[4 * f] + init[4 * f + 1] * init[4 * f + 1]);
         if (!(h > 0.0 && std::isfinite(h))) return fail(c, -3, w + ": an initial state whose (c, s) has a zero or non-finite length");
     }
     RR_HIP(c, hipSetDevice(c->device));
-    RR_HIP(c, hipStreamSynchronize(c->stream));        // the staging buffers may be reallocated
-    RR_HIP(c, c->d_icp_points.ensure(n * mp + mt));
-    RR_HIP(c, c->d_icp_words.ensure(n_offs + 1 + n * mp));
-    RR_HIP(c, c->d_icp_init.ensure(n * 4));
-    RR_HIP(c, c->d_icp_rec.ensure(n));
-    rr_radar_point* d_src = c->d_icp_points.p;
-    rr_radar_point* d_tgt = d_src + n * mp;
-    uint32_t* d_offs = c->d_icp_words.p;
-    uint32_t* d_count = d_offs + n_offs;
-    uint32_t* d_corr = d_count + 1;
-    auto count = [&](size_t f) { return std::min<size_t>(offsets[f * (A + 1) + A], mp); };
-    const size_t n_tgt = std::min<size_t>(tgt_count, mt);
-    RR_HIP(c, hipMemcpyAsync(d_offs, offsets, n_offs * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    RR_HIP(c, hipMemcpyAsync(d_count, &tgt_count, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    for (size_t f = 0; f < n; f++)
-        if (count(f)) RR_HIP(c, hipMemcpyAsync(d_src + f * mp, points + f * mp, count(f) * sizeof(rr_radar_point), hipMemcpyHostToDevice, c->stream));
-    if (n_tgt) RR_HIP(c, hipMemcpyAsync(d_tgt, tgt_points, n_tgt * sizeof(rr_radar_point), hipMemcpyHostToDevice, c->stream));
-    if (init) RR_HIP(c, hipMemcpyAsync(c->d_icp_init.p, init, n * 4 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    RR_STAGE(c, st);
+    std::vector<uint32_t> totals; rr_radar_point *d_src, *d_tgt; uint32_t *d_offs, *d_count, *d_corr; double* d_init; rr_icp_rec* d_recs;
+    rc = up_points(c, st, points, offsets, n, mp, totals, d_src, d_offs); if (rc) return rc;
+    RR_HIP(c, st.up_rows(tgt_points, 1, mt, &tgt_count, d_tgt));
+    RR_HIP(c, st.up(&tgt_count, 1, d_count));
+    RR_HIP(c, st.up(init, n * 4, d_init));
+    RR_HIP(c, st.hold(recs, n, d_recs));
+    RR_HIP(c, st.hold_rows(corr, n, mp, mp, totals.data(), d_corr));
     RR_HIP(c, hipStreamSynchronize(c->stream));        // (tgt_count is this call's own variable)
-    rc = rr_register_points_device(c, d_src, d_offs, n_frames, max_points, d_tgt, d_count, max_tgt, init ? c->d_icp_init.p : nullptr, gate, iterations,
-                                   c->d_icp_rec.p, corr ? d_corr : nullptr, c->stream); if (rc) return rc;
-    std::vector<uint32_t> got(corr ? n * mp : 0);        // the caller's buffers are written once everything has arrived
-    for (size_t f = 0; corr && f < n; f++)
-        if (count(f)) RR_HIP(c, hipMemcpyAsync(got.data() + f * mp, d_corr + f * mp, count(f) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    std::vector<rr_icp_rec> rec(n);
-    rc = records_back(c, rec.data(), c->d_icp_rec.p, n * sizeof(rr_icp_rec), c->stream); if (rc) return rc;
-    std::copy(rec.begin(), rec.end(), recs);
-    for (size_t f = 0; corr && f < n; f++) std::copy(got.begin() + f * mp, got.begin() + f * mp + count(f), corr + f * mp);
-    return 0;
+    rc = rr_register_points_device(c, d_src, d_offs, n_frames, max_points, d_tgt, d_count, max_tgt, d_init, gate, iterations, d_recs, d_corr, c->stream);
+    if (rc) return rc;
+    return st.commit();
 }
 
 // ---- likelihood field (rr_field.hip) ------------------------------------------------------------------------------------
@@ -976,25 +914,15 @@ int rr_rasterize_points(rr_ctx* c, const rr_radar_point* points, const uint32_t*
     int rc = check_rasterize(c, "rr_rasterize_points", points, offsets, n_frames, max_points, nullptr, cfg, occ_u8); if (rc) return rc;
     if (max_points == 0) return 0;
     RR_HIP(c, hipSetDevice(c->device));
-    const size_t n = (size_t)n_frames, A = (size_t)c->cfg.n_angles, mp = (size_t)max_points, n_offs = n * (A + 1);
-    const size_t cells = (size_t)cfg->width * cfg->height;
-    RR_HIP(c, hipStreamSynchronize(c->stream));        // the staging buffers may be reallocated
-    RR_HIP(c, c->d_field_points.ensure(n * mp));
-    RR_HIP(c, c->d_field_words.ensure(n_offs));
-    RR_HIP(c, c->d_field_init.ensure(n * 4));
-    RR_HIP(c, c->d_field_occ.ensure(cells));
-    auto count = [&](size_t f) { return std::min<size_t>(offsets[f * (A + 1) + A], mp); };
-    RR_HIP(c, hipMemcpyAsync(c->d_field_words.p, offsets, n_offs * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    for (size_t f = 0; f < n; f++)
-        if (count(f)) RR_HIP(c, hipMemcpyAsync(c->d_field_points.p + f * mp, points + f * mp, count(f) * sizeof(rr_radar_point), hipMemcpyHostToDevice, c->stream));
-    if (states) RR_HIP(c, hipMemcpyAsync(c->d_field_init.p, states, n * 4 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    RR_HIP(c, hipMemcpyAsync(c->d_field_occ.p, occ_u8, cells, hipMemcpyHostToDevice, c->stream));      // the call accumulates
-    rc = rr_rasterize_points_device(c, c->d_field_points.p, c->d_field_words.p, n_frames, max_points, states ? c->d_field_init.p : nullptr, cfg,
-                                    c->d_field_occ.p, c->stream); if (rc) return rc;
-    std::vector<uint8_t> got(cells);                   // the caller's buffer is written once everything has arrived
-    rc = records_back(c, got.data(), c->d_field_occ.p, cells, c->stream); if (rc) return rc;
-    std::copy(got.begin(), got.end(), occ_u8);
-    return 0;
+    const size_t n = (size_t)n_frames, cells = (size_t)cfg->width * cfg->height;
+    RR_STAGE(c, st);
+    std::vector<uint32_t> totals; rr_radar_point* d_points; uint32_t* d_offs; double* d_states; uint8_t* d_occ;
+    rc = up_points(c, st, points, offsets, n, (size_t)max_points, totals, d_points, d_offs); if (rc) return rc;
+    RR_HIP(c, st.up(states, n * 4, d_states));
+    RR_HIP(c, st.up(occ_u8, cells, d_occ));      // the call accumulates
+    rc = rr_rasterize_points_device(c, d_points, d_offs, n_frames, max_points, d_states, cfg, d_occ, c->stream); if (rc) return rc;
+    st.out(occ_u8, d_occ, cells);
+    return st.commit();
 }
 
 int rr_distance_field_device(rr_ctx* c, const uint8_t* d_occ_u8, int threshold, const rr_field_config* cfg, uint16_t* d_field_u16, void* stream)
@@ -1011,15 +939,12 @@ int rr_distance_field(rr_ctx* c, const uint8_t* occ_u8, int threshold, const rr_
     int rc = check_distance_field(c, "rr_distance_field", occ_u8, threshold, cfg, field_u16); if (rc) return rc;
     RR_HIP(c, hipSetDevice(c->device));
     const size_t cells = (size_t)cfg->width * cfg->height;
-    RR_HIP(c, hipStreamSynchronize(c->stream));        // the staging buffers may be reallocated
-    RR_HIP(c, c->d_field_occ.ensure(cells));
-    RR_HIP(c, c->d_field_map.ensure(cells));
-    RR_HIP(c, hipMemcpyAsync(c->d_field_occ.p, occ_u8, cells, hipMemcpyHostToDevice, c->stream));
-    rc = rr_distance_field_device(c, c->d_field_occ.p, threshold, cfg, c->d_field_map.p, c->stream); if (rc) return rc;
-    std::vector<uint16_t> got(cells);
-    rc = records_back(c, got.data(), c->d_field_map.p, cells * sizeof(uint16_t), c->stream); if (rc) return rc;
-    std::copy(got.begin(), got.end(), field_u16);
-    return 0;
+    RR_STAGE(c, st);
+    uint8_t* d_occ; uint16_t* d_field;
+    RR_HIP(c, st.up(occ_u8, cells, d_occ));
+    RR_HIP(c, st.hold(field_u16, cells, d_field));
+    rc = rr_distance_field_device(c, d_occ, threshold, cfg, d_field, c->stream); if (rc) return rc;
+    return st.commit();
 }
 
 int rr_score_poses_device(rr_ctx* c, const rr_radar_point* d_points, const uint32_t* d_count, int max_points, const float* d_states, int n_hyp,
@@ -1038,24 +963,17 @@ int rr_score_poses(rr_ctx* c, const rr_radar_point* points, uint32_t count, int 
 {
     int rc = check_score_poses(c, "rr_score_poses", points, true, max_points, states, n_hyp, field_u16, cfg, recs); if (rc) return rc;
     RR_HIP(c, hipSetDevice(c->device));
-    const size_t n = (size_t)n_hyp, cells = (size_t)cfg->width * cfg->height, m = std::min<size_t>(count, (size_t)max_points);
-    RR_HIP(c, hipStreamSynchronize(c->stream));        // the staging buffers may be reallocated
-    RR_HIP(c, c->d_field_points.ensure(m));
-    RR_HIP(c, c->d_field_words.ensure(1));
-    RR_HIP(c, c->d_field_states.ensure(n * 4));
-    RR_HIP(c, c->d_field_map.ensure(cells));
-    RR_HIP(c, c->d_field_rec.ensure(n));
-    if (m) RR_HIP(c, hipMemcpyAsync(c->d_field_points.p, points, m * sizeof(rr_radar_point), hipMemcpyHostToDevice, c->stream));
-    RR_HIP(c, hipMemcpyAsync(c->d_field_words.p, &count, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    RR_HIP(c, hipMemcpyAsync(c->d_field_states.p, states, n * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    RR_HIP(c, hipMemcpyAsync(c->d_field_map.p, field_u16, cells * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+    const size_t n = (size_t)n_hyp, cells = (size_t)cfg->width * cfg->height;
+    RR_STAGE(c, st);
+    rr_radar_point* d_points; uint32_t* d_count; float* d_states; uint16_t* d_field; rr_field_rec* d_recs;
+    RR_HIP(c, st.up_rows(points, 1, (size_t)max_points, &count, d_points));
+    RR_HIP(c, st.up(&count, 1, d_count));
+    RR_HIP(c, st.up(states, n * 4, d_states));
+    RR_HIP(c, st.up(field_u16, cells, d_field));
+    RR_HIP(c, st.hold(recs, n, d_recs));
     RR_HIP(c, hipStreamSynchronize(c->stream));        // (count is this call's own variable)
-    rc = rr_score_poses_device(c, c->d_field_points.p, c->d_field_words.p, max_points, c->d_field_states.p, n_hyp, c->d_field_map.p, cfg,
-                               c->d_field_rec.p, c->stream); if (rc) return rc;
-    std::vector<rr_field_rec> rec(n);
-    rc = records_back(c, rec.data(), c->d_field_rec.p, n * sizeof(rr_field_rec), c->stream); if (rc) return rc;
-    std::copy(rec.begin(), rec.end(), recs);
-    return 0;
+    rc = rr_score_poses_device(c, d_points, d_count, max_points, d_states, n_hyp, d_field, cfg, d_recs, c->stream); if (rc) return rc;
+    return st.commit();
 }
 
 // ---- object annotations (rr_notes.hip) --------------------------------------------------------------------------------
@@ -1088,23 +1006,15 @@ int rr_annotate_labels(rr_ctx* c, const uint32_t* labels, const uint8_t* imgs_u8
     RR_HIP(c, hipSetDevice(c->device));
     const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles, n = (size_t)n_frames, n_rec = n * (size_t)n_objects;
     const size_t scratch = note_scratch_bytes(n, (size_t)n_objects, c->cfg.n_angles);
-    RR_HIP(c, hipStreamSynchronize(c->stream));        // the staging buffers may be reallocated
-    RR_HIP(c, c->d_note_planes.ensure(n * npx));
-    if (imgs_u8) RR_HIP(c, c->d_note_imgs.ensure(n * npx));
-    RR_HIP(c, c->d_note_rec.ensure(n_rec));
-    RR_HIP(c, c->d_note_skipped.ensure(n));
-    RR_HIP(c, c->d_note_scratch.ensure(scratch / 16));
-    RR_HIP(c, hipMemcpyAsync(c->d_note_planes.p, labels, n * npx * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    if (imgs_u8) RR_HIP(c, hipMemcpyAsync(c->d_note_imgs.p, imgs_u8, n * npx, hipMemcpyHostToDevice, c->stream));
-    rc = rr_annotate_labels_device(c, c->d_note_planes.p, imgs_u8 ? c->d_note_imgs.p : nullptr, n_frames, n_objects, extent_mask, c->d_note_rec.p,
-                                   c->d_note_skipped.p, c->d_note_scratch.p, scratch, c->stream); if (rc) return rc;
-    std::vector<rr_object_note> rec(n_rec);             // the caller's buffers are written once everything has arrived
-    std::vector<uint32_t> skipped(n);
-    RR_HIP(c, hipMemcpyAsync(skipped.data(), c->d_note_skipped.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    rc = records_back(c, rec.data(), c->d_note_rec.p, n_rec * sizeof(rr_object_note), c->stream); if (rc) return rc;
-    std::copy(rec.begin(), rec.end(), out_notes);
-    std::copy(skipped.begin(), skipped.end(), out_skipped);
-    return 0;
+    RR_STAGE(c, st);
+    uint32_t *d_labels, *d_skipped; uint8_t *d_imgs, *d_scratch; rr_object_note* d_notes;
+    RR_HIP(c, st.up(labels, n * npx, d_labels));
+    RR_HIP(c, st.up(imgs_u8, n * npx, d_imgs));
+    RR_HIP(c, st.hold(out_notes, n_rec, d_notes));
+    RR_HIP(c, st.hold(out_skipped, n, d_skipped));
+    RR_HIP(c, st.room(scratch, d_scratch));
+    rc = rr_annotate_labels_device(c, d_labels, d_imgs, n_frames, n_objects, extent_mask, d_notes, d_skipped, d_scratch, scratch, c->stream); if (rc) return rc;
+    return st.commit();
 }
 
 int rr_label_points_device(rr_ctx* c, const rr_radar_point* d_points, const uint32_t* d_offsets, int n_frames, int max_points, const uint32_t* d_labels,
@@ -1141,15 +1051,12 @@ int rr_polar_to_cartesian_labels(rr_ctx* c, const uint32_t* planes_u32, int n_fr
     if (cfg->interpolation != 0) return fail(c, -3, "rr_polar_to_cartesian_labels: interpolation must be 0 (nearest): ids do not interpolate");
     RR_HIP(c, hipSetDevice(c->device));
     const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles, n = (size_t)n_frames, n_out = n * cfg->width * cfg->width;
-    RR_HIP(c, hipStreamSynchronize(c->stream));        // the staging buffers may be reallocated
-    RR_HIP(c, c->d_note_planes.ensure(n * npx));
-    RR_HIP(c, c->d_note_cart.ensure(n_out));
-    RR_HIP(c, hipMemcpyAsync(c->d_note_planes.p, planes_u32, n * npx * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    rc = rr_polar_to_cartesian_labels_device(c, c->d_note_planes.p, n_frames, cfg, c->d_note_cart.p, c->stream); if (rc) return rc;
-    std::vector<uint32_t> out(n_out);
-    rc = records_back(c, out.data(), c->d_note_cart.p, n_out * sizeof(uint32_t), c->stream); if (rc) return rc;
-    std::copy(out.begin(), out.end(), cart_u32);
-    return 0;
+    RR_STAGE(c, st);
+    uint32_t *d_planes, *d_cart;
+    RR_HIP(c, st.up(planes_u32, n * npx, d_planes));
+    RR_HIP(c, st.hold(cart_u32, n_out, d_cart));
+    rc = rr_polar_to_cartesian_labels_device(c, d_planes, n_frames, cfg, d_cart, c->stream); if (rc) return rc;
+    return st.commit();
 }
 
 int rr_simulate_batch_annotations(rr_ctx* c, const float* poses, int n_frames, uint32_t extent_mask, uint8_t* out_imgs_u8, rr_object_note* out_notes,
@@ -1163,25 +1070,17 @@ int rr_simulate_batch_annotations(rr_ctx* c, const float* poses, int n_frames, u
     RR_HIP(c, hipSetDevice(c->device));
     const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles, n = (size_t)n_frames, n_obj = c->n_objects, n_rec = n * n_obj;
     const size_t scratch = note_scratch_bytes(n, n_obj, c->cfg.n_angles);
-    RR_HIP(c, hipStreamSynchronize(c->stream));        // the buffers may be reallocated below
-    RR_HIP(c, c->d_param_imgs.ensure(n * npx));
-    RR_HIP(c, c->d_note_planes.ensure(n * npx));
-    RR_HIP(c, c->d_note_rec.ensure(n_rec));
-    RR_HIP(c, c->d_note_skipped.ensure(n));
-    RR_HIP(c, c->d_note_scratch.ensure(scratch / 16));
-    rc = rr_simulate_batch_provenance_device(c, poses, n_frames, c->d_param_imgs.p, c->d_note_planes.p, nullptr, nullptr, 0, nullptr, c->stream);
-    if (rc) return rc;
-    rc = rr_annotate_labels_device(c, c->d_note_planes.p, c->d_param_imgs.p, n_frames, (int)n_obj, extent_mask, c->d_note_rec.p, c->d_note_skipped.p,
-                                   c->d_note_scratch.p, scratch, c->stream); if (rc) return rc;
-    std::vector<rr_object_note> rec(n_rec);
-    std::vector<uint32_t> skipped(n);
-    RR_HIP(c, hipMemcpyAsync(skipped.data(), c->d_note_skipped.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    rc = records_back(c, rec.data(), c->d_note_rec.p, n_rec * sizeof(rr_object_note), c->stream); if (rc) return rc;
-    rc = report_frame_errors(c); if (rc) return rc;     // before anything is handed out
-    if (out_imgs_u8) RR_HIP(c, hipMemcpy(out_imgs_u8, c->d_param_imgs.p, n * npx, hipMemcpyDeviceToHost));
-    std::copy(rec.begin(), rec.end(), out_notes);
-    std::copy(skipped.begin(), skipped.end(), out_skipped);
-    return 0;
+    RR_STAGE(c, st);
+    uint32_t *d_labels, *d_skipped; uint8_t *d_imgs, *d_scratch; rr_object_note* d_notes;
+    RR_HIP(c, st.room(n * npx, d_imgs));
+    RR_HIP(c, st.room(n * npx, d_labels));
+    RR_HIP(c, st.hold(out_notes, n_rec, d_notes));
+    RR_HIP(c, st.hold(out_skipped, n, d_skipped));
+    RR_HIP(c, st.room(scratch, d_scratch));
+    rc = rr_simulate_batch_provenance_device(c, poses, n_frames, d_imgs, d_labels, nullptr, nullptr, 0, nullptr, c->stream); if (rc) return rc;
+    rc = rr_annotate_labels_device(c, d_labels, d_imgs, n_frames, (int)n_obj, extent_mask, d_notes, d_skipped, d_scratch, scratch, c->stream); if (rc) return rc;
+    st.out(out_imgs_u8, d_imgs, n * npx, false);
+    return st.commit(frame_gate(c));
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // rr_sets.hip -- parameter batches: ONE pose under several parameter sets (material tables, beam samples, passes) in one launch chain, with optional scores
-#include "rr_ctx.h"
+#include "rr_stage.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -120,25 +120,32 @@ int rr_simulate_material_sets_device(rr_ctx* c, const float pose[7], const rr_ma
     return rr_simulate_param_sets_device(c, pose, ps, n_sets, n_materials, d_imgs_u8, stream);
 }
 
+}  // extern "C"
+
 namespace {
-// the images of a parameter batch in c->d_param_imgs: copy out and / or score, report the frame's error bits
-int finish_param_batch(rr_ctx* c, int n_sets, uint8_t* out_imgs_u8, const uint8_t* ref_img_u8, double* out_psnr,
-                       uint32_t which = 0, int win_size = 0, rr_image_metrics* out_metrics = nullptr)
+// The round trip the host forms share (rr_stage.h): `simulate(d_imgs)` runs a parameter batch into the stage's room; its images are scored
+// and / or copied out, the latter once the frame's error bits have come home clean
+template <class Simulate>
+int param_batch_to_host(rr_ctx* c, int n_sets, Simulate simulate, uint8_t* out_imgs_u8, const uint8_t* ref_img_u8, double* out_psnr,
+                        uint32_t which = 0, int win_size = 0, rr_image_metrics* out_metrics = nullptr)
 {
-    const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles;
-    if (out_imgs_u8) RR_HIP(c, hipMemcpyAsync(out_imgs_u8, c->d_param_imgs.p, (size_t)n_sets * npx, hipMemcpyDeviceToHost, c->stream));
-    if (ref_img_u8 && (out_psnr || out_metrics)) {
-        RR_HIP(c, c->d_ref_img.ensure(npx));
-        RR_HIP(c, hipMemcpyAsync(c->d_ref_img.p, ref_img_u8, npx, hipMemcpyHostToDevice, c->stream));
-        int rc = 0;     // (both synchronise the stream)
-        if (out_psnr) rc = rr_score_images_device(c, c->d_param_imgs.p, n_sets, c->d_ref_img.p, out_psnr, nullptr, c->stream);
-        if (!rc && out_metrics) rc = rr_compare_images_device(c, c->d_param_imgs.p, n_sets, c->d_ref_img.p, which, win_size, out_metrics, nullptr, c->stream);
-        if (rc) return rc;
-    }
-    RR_HIP(c, hipStreamSynchronize(c->stream));
-    return report_frame_errors(c);
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles, n = (size_t)n_sets;
+    RR_STAGE(c, st);
+    uint8_t *d_imgs, *d_ref;
+    RR_HIP(c, st.room(n * npx, d_imgs));
+    RR_HIP(c, st.up(out_psnr || out_metrics ? ref_img_u8 : nullptr, npx, d_ref));
+    int rc = simulate(d_imgs); if (rc) return rc;
+    // (both synchronise the stream)
+    if (d_ref && out_psnr) rc = rr_score_images_device(c, d_imgs, n_sets, d_ref, out_psnr, nullptr, c->stream);
+    if (d_ref && out_metrics && !rc) rc = rr_compare_images_device(c, d_imgs, n_sets, d_ref, which, win_size, out_metrics, nullptr, c->stream);
+    if (rc) return rc;
+    st.out(out_imgs_u8, d_imgs, n * npx, false);
+    return st.commit([c] { return report_frame_errors(c); });
 }
 }  // namespace
+
+extern "C" {
 
 int rr_simulate_material_sets(rr_ctx* c, const float pose[7], const rr_material* sets, int n_sets, size_t n_materials,
                               uint8_t* out_imgs_u8)
@@ -146,11 +153,8 @@ int rr_simulate_material_sets(rr_ctx* c, const float pose[7], const rr_material*
     if (!c) return -1;
     if (!out_imgs_u8) return fail(c, -3, "rr_simulate_material_sets: null output");
     if (n_sets < 1 || n_sets > RR_MAX_BATCH) return fail(c, -3, "rr_simulate_material_sets: n_sets must be 1..64");
-    RR_HIP(c, hipSetDevice(c->device));
-    const size_t bytes = (size_t)n_sets * c->cfg.n_cells * c->cfg.n_angles;
-    RR_HIP(c, c->d_param_imgs.ensure(bytes));
-    int rc = rr_simulate_material_sets_device(c, pose, sets, n_sets, n_materials, c->d_param_imgs.p, c->stream); if (rc) return rc;
-    return finish_param_batch(c, n_sets, out_imgs_u8, nullptr, nullptr);
+    return param_batch_to_host(c, n_sets, [&](uint8_t* d_imgs) {
+        return rr_simulate_material_sets_device(c, pose, sets, n_sets, n_materials, d_imgs, c->stream); }, out_imgs_u8, nullptr, nullptr);
 }
 
 int rr_simulate_param_sets(rr_ctx* c, const float pose[7], const rr_param_set* sets, int n_sets, size_t n_materials,
@@ -160,24 +164,18 @@ int rr_simulate_param_sets(rr_ctx* c, const float pose[7], const rr_param_set* s
     if (!out_imgs_u8 && !(ref_img_u8 && out_psnr)) return fail(c, -3, "rr_simulate_param_sets: neither an image buffer nor a reference image + score buffer");
     if ((ref_img_u8 == nullptr) != (out_psnr == nullptr)) return fail(c, -3, "rr_simulate_param_sets: ref_img_u8 and out_psnr go together");
     if (n_sets < 1 || n_sets > RR_MAX_BATCH) return fail(c, -3, "rr_simulate_param_sets: n_sets must be 1..64");
-    RR_HIP(c, hipSetDevice(c->device));
-    const size_t bytes = (size_t)n_sets * c->cfg.n_cells * c->cfg.n_angles;
-    RR_HIP(c, c->d_param_imgs.ensure(bytes));
-    int rc = rr_simulate_param_sets_device(c, pose, sets, n_sets, n_materials, c->d_param_imgs.p, c->stream); if (rc) return rc;
-    return finish_param_batch(c, n_sets, out_imgs_u8, ref_img_u8, out_psnr);
+    return param_batch_to_host(c, n_sets, [&](uint8_t* d_imgs) {
+        return rr_simulate_param_sets_device(c, pose, sets, n_sets, n_materials, d_imgs, c->stream); }, out_imgs_u8, ref_img_u8, out_psnr);
 }
 
 int rr_simulate_param_sets_metrics(rr_ctx* c, const float pose[7], const rr_param_set* sets, int n_sets, size_t n_materials,
                                    uint8_t* out_imgs_u8, const uint8_t* ref_img_u8, uint32_t which, int win_size, rr_image_metrics* out)
 {
-    // refused before anything is simulated (d_param_imgs stands in for the images: they are the context's own)
+    // refused before anything is simulated (the context stands in for the images: they are its own)
     int rc = check_compare(c, "rr_simulate_param_sets_metrics", c, 1, ref_img_u8, which, win_size, out, nullptr); if (rc) return rc;
     if (n_sets < 1 || n_sets > RR_MAX_BATCH) return fail(c, -3, "rr_simulate_param_sets_metrics: n_sets must be 1..64");
-    RR_HIP(c, hipSetDevice(c->device));
-    const size_t bytes = (size_t)n_sets * c->cfg.n_cells * c->cfg.n_angles;
-    RR_HIP(c, c->d_param_imgs.ensure(bytes));
-    rc = rr_simulate_param_sets_device(c, pose, sets, n_sets, n_materials, c->d_param_imgs.p, c->stream); if (rc) return rc;
-    return finish_param_batch(c, n_sets, out_imgs_u8, ref_img_u8, nullptr, which, win_size, out);
+    return param_batch_to_host(c, n_sets, [&](uint8_t* d_imgs) {
+        return rr_simulate_param_sets_device(c, pose, sets, n_sets, n_materials, d_imgs, c->stream); }, out_imgs_u8, ref_img_u8, nullptr, which, win_size, out);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // rr_side.hip -- the entry points of the chains that ride beside the frame chain (run_frame with a FrameJob that asks for them): echo
 // provenance, wave paths, Doppler, each as a device form for pose batches and a synchronous host form for one frame, and rr_debug_labels.
-// One refusal list (check_side), one batch step (side_batch), one staging step for the host forms (host_lane, Staged).
-#include "rr_ctx.h"
+// One refusal list (check_side), one batch step (side_batch), one staging step for the host forms (host_lane, a Stage over the lane's pool).
+#include "rr_stage.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -127,45 +127,9 @@ int host_lane(rr_ctx* c, Lane& L, bool want_f32 = false)
     return 0;
 }
 
-// The outputs of a host form on their way to the caller.  They are staged: a call that fails after its chain has run (the frame's
-// error bits come home with them) has written nothing
-struct Staged {
-    struct Out { void* dst; const void* d_src; size_t bytes, elem, d_stride, stride; const void* counts; std::vector<uint8_t> h; };
-    std::vector<Out> outs;
-
-    // An output the caller asked for (dst non-null; else d = null and that is all): n elements of the lane's buffer `buf`, grown to
-    // hold them -> d
-    template <class T> hipError_t add(void* dst, DevBuf<T>& buf, size_t n, T*& d) { return add_rows(dst, buf, n, sizeof(T), 1, 1, nullptr, d); }
-    // ... as n_rows rows of d_stride records of `elem` bytes for the caller's rows of `stride` records.  Only the records that exist
-    // reach the caller: those of row a below counts[a], where `counts` is the caller's buffer of another output (a uint32 per row)
-    template <class T>
-    hipError_t add_rows(void* dst, DevBuf<T>& buf, size_t n_rows, size_t elem, size_t d_stride, size_t stride, const void* counts, T*& d)
-    {
-        d = nullptr;
-        if (!dst) return hipSuccess;
-        const hipError_t e = buf.ensure(n_rows * d_stride * elem / sizeof(T));
-        d = buf.p;
-        outs.push_back(Out{ dst, buf.p, n_rows * d_stride * elem, elem, d_stride, stride, counts, {} });
-        return e;
-    }
-    // the copies ride home behind the batch on s; the lane is handed back behind them, and once the frame has come home clean the
-    // caller's buffers are written
-    int commit(rr_ctx* c, Lane& L, hipStream_t s)
-    {
-        for (Out& o : outs) { o.h.resize(o.bytes); RR_HIP(c, hipMemcpyAsync(o.h.data(), o.d_src, o.bytes, hipMemcpyDeviceToHost, s)); }
-        RR_HIP(c, give_lane(L, s));
-        RR_HIP(c, hipStreamSynchronize(s));
-        const int rc = report_frame_errors(c); if (rc) return rc;
-        for (const Out& o : outs) {
-            if (!o.counts) { std::memcpy(o.dst, o.h.data(), o.bytes); continue; }
-            const Out& n = *std::find_if(outs.begin(), outs.end(), [&](const Out& x) { return x.dst == o.counts; });
-            for (size_t a = 0; a < o.bytes / (o.d_stride * o.elem); a++)
-                std::memcpy((uint8_t*)o.dst + a * o.stride * o.elem, o.h.data() + a * o.d_stride * o.elem,
-                            std::min((size_t)reinterpret_cast<const uint32_t*>(n.h.data())[a], o.d_stride) * o.elem);
-        }
-        return 0;
-    }
-};
+// The way out of a host form: its outputs are held (rr_stage.h) -- a call that fails after its chain has run (the frame's error bits
+// come home with them) has written nothing.  The lane is handed back behind the copies
+int commit_lane(rr_ctx* c, Stage& st, Lane& L) { return st.commit([c] { return report_frame_errors(c); }, &L); }
 
 }  // namespace
 }  // namespace rr
@@ -189,14 +153,14 @@ int rr_simulate_provenance(rr_ctx* c, const float pose[7], uint8_t* out_u8, uint
     rc = ensure_prov_buffers(c, L); if (rc) return rc;
     const size_t A = (size_t)c->cfg.n_angles, npx = A * (size_t)c->cfg.n_cells;
     const size_t d_stride = out_echoes ? std::min(echo_stride, (size_t)L.prov_cap) : 0;      // the device-side row: as long as the caller's, and no longer than a list can get
-    Staged st; uint8_t* d_img; uint32_t *d_labels, *d_faces, *d_counts; rr_echo_src* d_echoes;
-    RR_HIP(c, st.add(out_u8, L.slot[0].img, npx, d_img));
-    RR_HIP(c, st.add(out_labels, L.d_label_img, npx, d_labels));
-    RR_HIP(c, st.add(out_faces, L.d_face_img, npx, d_faces));
-    RR_HIP(c, st.add(out_echo_counts, L.d_echo_out_counts, A, d_counts));
-    RR_HIP(c, st.add_rows(out_echoes, L.d_echo_out, A, sizeof(rr_echo_src), d_stride, echo_stride, out_echo_counts, d_echoes));
-    rc = provenance_batch(c, 0, pose, 1, d_img, d_labels, d_faces, d_echoes, d_stride, d_counts, c->stream); if (rc) return rc;
-    return st.commit(c, L, c->stream);
+    Stage st(c, L.stage, c->stream); uint32_t *d_labels, *d_faces, *d_counts; rr_echo_src* d_echoes;
+    st.out(out_u8, L.slot[0].img.p, npx);
+    RR_HIP(c, st.hold(out_labels, npx, d_labels));
+    RR_HIP(c, st.hold(out_faces, npx, d_faces));
+    RR_HIP(c, st.hold(out_echo_counts, A, d_counts));
+    RR_HIP(c, st.hold_rows(out_echoes, A, d_stride, echo_stride, out_echo_counts, d_echoes));
+    rc = provenance_batch(c, 0, pose, 1, L.slot[0].img.p, d_labels, d_faces, d_echoes, d_stride, d_counts, c->stream); if (rc) return rc;
+    return commit_lane(c, st, L);
 }
 
 int rr_simulate_batch_paths_device(rr_ctx* c, const float* poses, int n_frames, uint8_t* d_imgs_u8, rr_wave_rec* d_waves, size_t wave_stride,
@@ -219,13 +183,13 @@ int rr_simulate_paths(rr_ctx* c, const float pose[7], uint8_t* out_u8, rr_wave_r
     { const long n_beam = (long)(c->beams.size() / 3); long w = n_beam;
       for (int p = 0; p < c->cfg.n_reflections; p++) { longest += (size_t)std::min<long>(w, L.buf_cap); w = std::min<long>(2 * w, L.buf_cap); } }
     const size_t d_stride = out_waves ? std::max<size_t>(1, std::min(wave_stride, longest)) : 0;
-    Staged st; uint8_t* d_img; uint32_t *d_counts, *d_passes; float4* d_waves;
-    RR_HIP(c, st.add(out_u8, L.slot[0].img, npx, d_img));
-    RR_HIP(c, st.add(out_wave_counts, L.d_wave_out_counts, A, d_counts));
-    RR_HIP(c, st.add(out_pass_counts, L.d_wave_out_passes, A * RR_WAVES_MAX_PASSES, d_passes));
-    RR_HIP(c, st.add_rows(out_waves, L.d_wave_out, A, sizeof(rr_wave_rec), d_stride, wave_stride, out_wave_counts, d_waves));
-    rc = paths_batch(c, 0, pose, 1, d_img, reinterpret_cast<rr_wave_rec*>(d_waves), d_stride, d_counts, d_passes, flags, c->stream); if (rc) return rc;
-    return st.commit(c, L, c->stream);
+    Stage st(c, L.stage, c->stream); uint32_t *d_counts, *d_passes; rr_wave_rec* d_waves;
+    st.out(out_u8, L.slot[0].img.p, npx);
+    RR_HIP(c, st.hold(out_wave_counts, A, d_counts));
+    RR_HIP(c, st.hold(out_pass_counts, A * RR_WAVES_MAX_PASSES, d_passes));
+    RR_HIP(c, st.hold_rows(out_waves, A, d_stride, wave_stride, out_wave_counts, d_waves));
+    rc = paths_batch(c, 0, pose, 1, L.slot[0].img.p, d_waves, d_stride, d_counts, d_passes, flags, c->stream); if (rc) return rc;
+    return commit_lane(c, st, L);
 }
 
 int rr_simulate_batch_doppler_device(rr_ctx* c, const float* poses, int n_frames, const float* sensor_vel, float gain, uint8_t* d_imgs_u8,
@@ -246,15 +210,15 @@ int rr_simulate_doppler(rr_ctx* c, const float pose[7], const float sensor_vel[3
     rc = ensure_prov_buffers(c, L); if (rc) return rc;
     const size_t A = (size_t)c->cfg.n_angles, npx = A * (size_t)c->cfg.n_cells;
     const size_t d_stride = (out_echo_vel || out_echo_cells) ? std::min(echo_stride, (size_t)L.prov_cap) : 0;      // the device-side rows: as long as the caller's, and no longer than a list can get
-    Staged st; uint8_t* d_img; float *d_f32, *d_vel_img, *d_vel; uint32_t* d_counts; int32_t* d_cells;
-    RR_HIP(c, st.add(out_u8, L.slot[0].img, npx, d_img));
-    RR_HIP(c, st.add(out_f32, L.d_img_f32, npx, d_f32));
-    RR_HIP(c, st.add(out_vel_img, L.d_dop_vel_img, npx, d_vel_img));
-    RR_HIP(c, st.add(out_echo_counts, L.d_dop_out_counts, A, d_counts));
-    RR_HIP(c, st.add_rows(out_echo_vel, L.d_dop_out_vel, A, sizeof(float), d_stride, echo_stride, out_echo_counts, d_vel));
-    RR_HIP(c, st.add_rows(out_echo_cells, L.d_dop_out_cells, A, sizeof(int32_t), d_stride, echo_stride, out_echo_counts, d_cells));
-    rc = doppler_batch(c, 0, pose, 1, sensor_vel, gain, d_img, d_f32, d_vel, d_stride, d_counts, d_cells, d_vel_img, c->stream); if (rc) return rc;
-    return st.commit(c, L, c->stream);
+    Stage st(c, L.stage, c->stream); float *d_f32, *d_vel_img, *d_vel; uint32_t* d_counts; int32_t* d_cells;
+    st.out(out_u8, L.slot[0].img.p, npx);
+    RR_HIP(c, st.hold(out_f32, npx, d_f32));
+    RR_HIP(c, st.hold(out_vel_img, npx, d_vel_img));
+    RR_HIP(c, st.hold(out_echo_counts, A, d_counts));
+    RR_HIP(c, st.hold_rows(out_echo_vel, A, d_stride, echo_stride, out_echo_counts, d_vel));
+    RR_HIP(c, st.hold_rows(out_echo_cells, A, d_stride, echo_stride, out_echo_counts, d_cells));
+    rc = doppler_batch(c, 0, pose, 1, sensor_vel, gain, L.slot[0].img.p, d_f32, d_vel, d_stride, d_counts, d_cells, d_vel_img, c->stream); if (rc) return rc;
+    return commit_lane(c, st, L);
 }
 
 int rr_debug_labels(rr_ctx* c, int n_seg, int az_begin, const rr_echo_src* echoes, const uint32_t* counts, size_t stride, uint32_t* out_labels,
