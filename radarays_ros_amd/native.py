@@ -13,41 +13,6 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RADARAYS_MI355_LIB") or os.path.join(_HERE, "libradarays_mi355.so")
 _LIB = None
 
-SYMBOLS = [
-    "rr_abi_version", "rr_default_config", "rr_create", "rr_destroy", "rr_last_error",
-    "rr_set_mesh", "rr_set_mesh_gpu", "rr_copy_mesh", "rr_set_materials", "rr_set_config", "rr_set_beam_samples",
-    "rr_set_noise_offsets", "rr_set_motion_poses", "rr_simulate", "rr_simulate_columns_device", "rr_simulate_batch_columns_device",
-    "rr_assemble_image_device", "rr_assemble_blocks_device", "rr_assemble_frames_device", "rr_simulate_device",
-    "rr_simulate_material_sets_device", "rr_simulate_material_sets", "rr_simulate_batch_device", "rr_synchronize", "rr_get_stats",
-    "rr_set_stats_mode", "rr_debug_trace", "rr_debug_fresnel", "rr_debug_brdf", "rr_debug_column", "rr_get_bvh_info", "rr_get_trace_grid", "rr_get_graph_stats", "rr_set_timing_mode",
-    "rr_get_kernel_time", "rr_get_kernel_samples", "rr_reserve_timing_events",
-    "rr_simulate_batch_host_async", "rr_wait_host", "rr_host_alloc", "rr_host_free", "rr_copy_to_host_async", "rr_deliver_to_host_async", "rr_host_delivery_route", "rr_partition", "rr_multi_plan",
-    "rr_create_multi", "rr_destroy_multi", "rr_multi_last_error", "rr_multi_device_count", "rr_multi_rccl_version", "rr_multi_ctx",
-    "rr_multi_set_mesh", "rr_multi_set_mesh_gpu", "rr_multi_set_materials", "rr_multi_set_config", "rr_multi_set_beam_samples",
-    "rr_multi_set_noise_offsets", "rr_multi_set_motion_poses", "rr_multi_simulate", "rr_multi_simulate_batch",
-    "rr_multi_simulate_batch_async", "rr_multi_wait", "rr_peek_error_bits_async", "rr_get_traversal_shape",
-    "rr_cone_dirs", "rr_sample_cone_local", "rr_load_mesh_file", "rr_mesh_reorder_objects", "rr_free_mesh",
-    "rr_simulate_param_sets_device", "rr_simulate_param_sets", "rr_score_images_device",
-    "rr_set_object_poses", "rr_update_vertices", "rr_get_tree_cost", "rr_rebuild_tree",
-    "rr_multi_set_object_poses", "rr_multi_update_vertices", "rr_multi_rebuild_tree",
-    "rr_default_detect_config", "rr_detect_device", "rr_detect", "rr_polar_to_cartesian_device", "rr_polar_to_cartesian",
-    "rr_compare_images_device", "rr_compare_images", "rr_simulate_param_sets_metrics",
-    "rr_align_images_device", "rr_align_images", "rr_simulate_batch_align",
-    "rr_shift_images_device", "rr_shift_images", "rr_simulate_batch_shift",
-    "rr_describe_images_device", "rr_describe_images", "rr_simulate_batch_describe", "rr_match_descriptors_device", "rr_match_descriptors",
-    "rr_simulate_batch_provenance_device", "rr_simulate_provenance", "rr_debug_labels",
-    "rr_simulate_batch_paths_device", "rr_simulate_paths",
-    "rr_set_object_twists", "rr_simulate_batch_doppler_device", "rr_simulate_doppler",
-    "rr_annotate_scratch_bytes", "rr_annotate_labels_device", "rr_annotate_labels", "rr_label_points_device",
-    "rr_polar_to_cartesian_labels_device", "rr_polar_to_cartesian_labels", "rr_simulate_batch_annotations",
-    "rr_sweep_table_device", "rr_sweep_table", "rr_compensate_points_device", "rr_compensate_points",
-    "rr_polar_to_cartesian_sweep_device", "rr_polar_to_cartesian_sweep",
-    "rr_register_points_device", "rr_register_points", "rr_icp_tile_sizes",
-    "rr_rasterize_points_device", "rr_rasterize_points", "rr_distance_field_device", "rr_distance_field",
-    "rr_score_poses_device", "rr_score_poses", "rr_field_tile_sizes",
-]
-
-
 class RRMaterial(C.Structure):
     _fields_ = [("velocity", C.c_float), ("ambient", C.c_float),
                 ("diffuse", C.c_float), ("specular", C.c_float)]
@@ -89,15 +54,11 @@ class RRDetectConfig(C.Structure):
                 ("min_intensity", C.c_int32), ("min_bin", C.c_int32), ("cfar_scale", C.c_float), ("reserved_", C.c_int32)]
 
 
-class RRRadarPoint(C.Structure):
-    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("intensity", C.c_float),
-                ("column", C.c_uint32), ("bin", C.c_uint32)]
-
-
 class RRCartesianConfig(C.Structure):
     _fields_ = [("width", C.c_int32), ("interpolation", C.c_int32), ("pixel_size", C.c_float), ("reserved_", C.c_int32)]
 
 
+# ---- records: the numpy dtype is the one statement of each; its ctypes Structure (RR*) is derived from it.
 # rr_echo as numpy sees it (8 B): one record of an echo stream of rr_debug_column
 ECHO_DTYPE = np.dtype([("cell", "<i4"), ("strength", "<f4")])
 
@@ -123,12 +84,7 @@ NOTE_ALL = NOTE_DIRECT | NOTE_GHOST | NOTE_MULTIPATH
 NOTE_NAMES = {"direct": NOTE_DIRECT, "ghost": NOTE_GHOST, "multipath": NOTE_MULTIPATH}
 
 
-class RRObjectNote(C.Structure):
-    _fields_ = [("n_direct", C.c_uint32), ("n_ghost", C.c_uint32), ("n_multipath", C.c_uint32), ("n_extent", C.c_uint32),
-                ("bin_min", C.c_uint32), ("bin_max", C.c_uint32), ("az_begin", C.c_uint32), ("az_count", C.c_uint32),
-                ("peak", C.c_uint32), ("peak_bin", C.c_uint32), ("peak_az", C.c_uint32), ("reserved0_", C.c_uint32),
-                ("sum_intensity", C.c_uint64), ("x_min", C.c_float), ("x_max", C.c_float), ("y_min", C.c_float), ("y_max", C.c_float),
-                ("reserved1_", C.c_uint32 * 2)]
+RRObjectNote = np.ctypeslib.as_ctypes_type(NOTE_DTYPE)
 
 
 def note_mask(extent):
@@ -150,22 +106,15 @@ WAVE_DTYPE = np.dtype([("o", "<f4", (3,)), ("range", "<f4"), ("d", "<f4", (3,)),
                        ("info", "<u4"), ("parent", "<i4"), ("material", "<u4"), ("echo", "<i4")])
 WAVES_MAP_FRAME = 1
 WAVES_MAX_PASSES = 16
-
-
-class RRWaveRec(C.Structure):
-    _fields_ = [("o", C.c_float * 3), ("range", C.c_float), ("d", C.c_float * 3), ("face", C.c_uint32), ("energy", C.c_double),
-                ("time", C.c_double), ("info", C.c_uint32), ("parent", C.c_int32), ("material", C.c_uint32), ("echo", C.c_int32)]
-
+RRWaveRec = np.ctypeslib.as_ctypes_type(WAVE_DTYPE)
 
 # rr_radar_point as numpy sees it (24 B: a PointCloud's point + its intensity channel, and where it came from)
 POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("intensity", "<f4"), ("column", "<u4"), ("bin", "<u4")])
+RRRadarPoint = np.ctypeslib.as_ctypes_type(POINT_DTYPE)
 
 # rr_sweep_rec as numpy sees it (32 B): one azimuth's transform into the reference frame and its Doppler range shift
 SWEEP_DTYPE = np.dtype([("q", "<f4", (4,)), ("t", "<f4", (3,)), ("dr", "<f4")])
-
-
-class RRSweepRec(C.Structure):
-    _fields_ = [("q", C.c_float * 4), ("t", C.c_float * 3), ("dr", C.c_float)]
+RRSweepRec = np.ctypeslib.as_ctypes_type(SWEEP_DTYPE)
 
 
 def identity_sweep_table(n_frames, n_angles):
@@ -180,11 +129,7 @@ ICP_DTYPE = np.dtype([("c", "<f8"), ("s", "<f8"), ("tx", "<f8"), ("ty", "<f8"), 
 ICP_DEGENERATE, ICP_TRUNCATED = 1, 2
 ICP_NONE = 0xFFFFFFFF              # an unmatched point in the correspondences
 ICP_MAX_POINTS = 65536
-
-
-class RRIcpRec(C.Structure):
-    _fields_ = [("c", C.c_double), ("s", C.c_double), ("tx", C.c_double), ("ty", C.c_double), ("sse", C.c_int64), ("n_matched", C.c_uint32),
-                ("flags", C.c_uint32)]
+RRIcpRec = np.ctypeslib.as_ctypes_type(ICP_DTYPE)
 
 
 def se2_states(yaw, tx=0.0, ty=0.0):
@@ -230,15 +175,12 @@ def _icp_init(init, n):
 # ---- likelihood field (rr_field.hip).  rr_field_rec as numpy sees it (16 B): the score of one pose hypothesis
 FIELD_DTYPE = np.dtype([("sum_d2", "<u8"), ("n_in", "<u4"), ("n_hit", "<u4")])
 FIELD_MAX_SIDE, FIELD_MAX_DIST, FIELD_MAX_HYP = 4096, 255, 1 << 22
+RRFieldRec = np.ctypeslib.as_ctypes_type(FIELD_DTYPE)
 
 
 class RRFieldConfig(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("cell", C.c_float), ("x0", C.c_float), ("y0", C.c_float),
                 ("max_dist", C.c_int32), ("gate", C.c_int32), ("reserved_", C.c_int32)]
-
-
-class RRFieldRec(C.Structure):
-    _fields_ = [("sum_d2", C.c_uint64), ("n_in", C.c_uint32), ("n_hit", C.c_uint32)]
 
 
 def _f32_finite(v, what, positive=False):
@@ -309,52 +251,33 @@ DETECT_DEFAULTS = {"method": 0, "guard_cells": 2, "train_cells": 16, "k": 12, "m
 DETECT_METHODS = {"cfar": 0, "ca-cfar": 0, "kstrongest": 1, "k-strongest": 1, 0: 0, 1: 1}
 
 
-class RRImageMetrics(C.Structure):
-    _fields_ = [("psnr", C.c_double), ("sse", C.c_uint64), ("ssim", C.c_double), ("hx", C.c_double), ("hy", C.c_double),
-                ("hxy", C.c_double), ("mi", C.c_double), ("nmi", C.c_double), ("voi", C.c_double)]
-
-
 # rr_image_metrics as numpy sees it (72 B), and the RR_METRIC_* bits of `which`
 METRICS_DTYPE = np.dtype([("psnr", "<f8"), ("sse", "<u8"), ("ssim", "<f8"), ("hx", "<f8"), ("hy", "<f8"), ("hxy", "<f8"),
                           ("mi", "<f8"), ("nmi", "<f8"), ("voi", "<f8")])
+RRImageMetrics = np.ctypeslib.as_ctypes_type(METRICS_DTYPE)
 METRIC_PSNR, METRIC_SSIM, METRIC_INFO = 1, 2, 4
 METRIC_ALL = METRIC_PSNR | METRIC_SSIM | METRIC_INFO
 METRIC_NAMES = {"psnr": METRIC_PSNR, "ssim": METRIC_SSIM, "info": METRIC_INFO}
 
-
-class RRAlignRecord(C.Structure):
-    _fields_ = [("shift", C.c_int32), ("n_best", C.c_int32), ("xcorr", C.c_int64), ("sse", C.c_uint64), ("psnr", C.c_double),
-                ("ncc", C.c_double), ("sum_x", C.c_uint64), ("sum_xx", C.c_uint64), ("sum_r", C.c_uint64), ("sum_rr", C.c_uint64)]
-
-
 # rr_align_record as numpy sees it (72 B)
 ALIGN_DTYPE = np.dtype([("shift", "<i4"), ("n_best", "<i4"), ("xcorr", "<i8"), ("sse", "<u8"), ("psnr", "<f8"), ("ncc", "<f8"),
                         ("sum_x", "<u8"), ("sum_xx", "<u8"), ("sum_r", "<u8"), ("sum_rr", "<u8")])
-
-
-class RRShiftRecord(C.Structure):
-    _fields_ = [("dy", C.c_int32), ("dx", C.c_int32), ("n_best", C.c_int32), ("reserved_", C.c_int32), ("xcorr", C.c_int64),
-                ("sse", C.c_uint64), ("psnr", C.c_double), ("ncc", C.c_double), ("sub_dy", C.c_double), ("sub_dx", C.c_double),
-                ("sse_nb", C.c_uint64 * 4), ("sum_x", C.c_uint64), ("sum_xx", C.c_uint64), ("sum_r", C.c_uint64), ("sum_rr", C.c_uint64)]
-
+RRAlignRecord = np.ctypeslib.as_ctypes_type(ALIGN_DTYPE)
 
 # rr_shift_record as numpy sees it (128 B)
 SHIFT_DTYPE = np.dtype([("dy", "<i4"), ("dx", "<i4"), ("n_best", "<i4"), ("reserved_", "<i4"), ("xcorr", "<i8"), ("sse", "<u8"),
                         ("psnr", "<f8"), ("ncc", "<f8"), ("sub_dy", "<f8"), ("sub_dx", "<f8"), ("sse_nb", "<u8", (4,)),
                         ("sum_x", "<u8"), ("sum_xx", "<u8"), ("sum_r", "<u8"), ("sum_rr", "<u8")])
+RRShiftRecord = np.ctypeslib.as_ctypes_type(SHIFT_DTYPE)
 
 
 class RRPlaceConfig(C.Structure):
     _fields_ = [("cell_begin", C.c_int32), ("cell_end", C.c_int32), ("n_rings", C.c_int32), ("n_sectors", C.c_int32)]
 
 
-class RRPlaceMatch(C.Structure):
-    _fields_ = [("index", C.c_uint32), ("shift", C.c_int32), ("sse", C.c_uint32), ("n_best", C.c_uint32), ("xcorr", C.c_int64),
-                ("ncc", C.c_double), ("psnr", C.c_double)]
-
-
 # rr_place_match as numpy sees it (40 B)
 PLACE_DTYPE = np.dtype([("index", "<u4"), ("shift", "<i4"), ("sse", "<u4"), ("n_best", "<u4"), ("xcorr", "<i8"), ("ncc", "<f8"), ("psnr", "<f8")])
+RRPlaceMatch = np.ctypeslib.as_ctypes_type(PLACE_DTYPE)
 
 
 def metrics_mask(which):
@@ -432,6 +355,180 @@ class RRStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
 
 
+# every struct include/radarays_mi355.h gives a body -> (its ctypes Structure, its numpy dtype or None).  tests/test_abi.py holds each to
+# the header's field list and to gcc's sizeof / offsetof.
+STRUCTS = {
+    "rr_material": (RRMaterial, None), "rr_config": (RRConfig, None), "rr_stats": (RRStats, None), "rr_param_set": (RRParamSet, None),
+    "rr_image_metrics": (RRImageMetrics, METRICS_DTYPE), "rr_align_record": (RRAlignRecord, ALIGN_DTYPE),
+    "rr_echo": (np.ctypeslib.as_ctypes_type(ECHO_DTYPE), ECHO_DTYPE), "rr_echo_src": (np.ctypeslib.as_ctypes_type(ECHO_SRC_DTYPE), ECHO_SRC_DTYPE),
+    "rr_wave_rec": (RRWaveRec, WAVE_DTYPE), "rr_detect_config": (RRDetectConfig, None), "rr_radar_point": (RRRadarPoint, POINT_DTYPE),
+    "rr_cartesian_config": (RRCartesianConfig, None), "rr_object_note": (RRObjectNote, NOTE_DTYPE), "rr_shift_record": (RRShiftRecord, SHIFT_DTYPE),
+    "rr_place_config": (RRPlaceConfig, None), "rr_place_match": (RRPlaceMatch, PLACE_DTYPE), "rr_sweep_rec": (RRSweepRec, SWEEP_DTYPE),
+    "rr_icp_rec": (RRIcpRec, ICP_DTYPE), "rr_field_config": (RRFieldConfig, None), "rr_field_rec": (RRFieldRec, FIELD_DTYPE),
+    "rr_mesh": (RRMesh, None),
+}
+
+
+def _prototypes():
+    """the one table of entry points: name -> (return type, argument types), in the header's order.  A new entry point is one row here;
+    tests/test_abi.py compares every row with the header's prototype, and the header with this table."""
+    P, vp, i, sz, f, s = C.POINTER, C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_char_p
+    i32, u32, u64, u, dbl = C.c_int32, C.c_uint32, C.c_uint64, C.c_uint, C.c_double
+    return {
+        # ---- context, scene, frames
+        "rr_default_config": (None, [P(RRConfig)]),
+        "rr_create": (vp, [i]),
+        "rr_destroy": (None, [vp]),
+        "rr_last_error": (s, [vp]),
+        "rr_abi_version": (i, []),
+        "rr_set_mesh": (i, [vp, vp, sz, vp, sz, vp]),
+        "rr_set_mesh_gpu": (i, [vp, vp, sz, vp, sz, vp]),
+        "rr_copy_mesh": (i, [vp, vp]),
+        "rr_set_object_poses": (i, [vp, vp, sz]),
+        "rr_update_vertices": (i, [vp, vp, sz]),
+        "rr_set_object_twists": (i, [vp, vp, sz]),
+        "rr_get_tree_cost": (i, [vp, P(dbl), P(dbl)]),
+        "rr_rebuild_tree": (i, [vp, i]),
+        "rr_set_materials": (i, [vp, vp, sz, vp, sz, i32]),
+        "rr_set_config": (i, [vp, P(RRConfig)]),
+        "rr_set_beam_samples": (i, [vp, vp, sz]),
+        "rr_set_noise_offsets": (i, [vp, vp, sz]),
+        "rr_set_motion_poses": (i, [vp, vp, sz]),
+        "rr_simulate": (i, [vp, vp, i, i, vp, vp, P(RRStats)]),
+        "rr_simulate_columns_device": (i, [vp, vp, i, i, vp, vp, vp]),
+        "rr_simulate_batch_columns_device": (i, [vp, vp, i, i, i, vp, vp]),
+        "rr_simulate_batch_device": (i, [vp, vp, i, vp, vp]),
+        "rr_simulate_batch_host_async": (i, [vp, vp, i, vp, vp]),
+        "rr_wait_host": (i, [vp, vp]),
+        "rr_host_alloc": (vp, [sz]),
+        "rr_host_free": (None, [vp]),
+        "rr_copy_to_host_async": (i, [vp, vp, vp, sz, vp]),
+        "rr_deliver_to_host_async": (i, [vp, vp, vp, sz, vp]),
+        "rr_host_delivery_route": (i, [vp]),
+        "rr_assemble_image_device": (i, [vp, vp, vp, vp]),
+        "rr_assemble_blocks_device": (i, [vp, vp, i, sz, vp, vp]),
+        "rr_simulate_material_sets_device": (i, [vp, vp, vp, i, sz, vp, vp]),
+        "rr_simulate_material_sets": (i, [vp, vp, vp, i, sz, vp]),
+        "rr_simulate_param_sets_device": (i, [vp, vp, P(RRParamSet), i, sz, vp, vp]),
+        "rr_score_images_device": (i, [vp, vp, i, vp, vp, vp, vp]),
+        "rr_simulate_param_sets": (i, [vp, vp, P(RRParamSet), i, sz, vp, vp, vp]),
+        # ---- image metrics (rr_metrics.hip)
+        "rr_compare_images_device": (i, [vp, vp, i, vp, u32, i, vp, vp, vp]),
+        "rr_compare_images": (i, [vp, vp, i, vp, u32, i, vp, vp]),
+        "rr_simulate_param_sets_metrics": (i, [vp, vp, P(RRParamSet), i, sz, vp, vp, u32, i, vp]),
+        # ---- azimuth registration (rr_align.hip)
+        "rr_align_images_device": (i, [vp, vp, i, vp, i, i, vp, vp, vp]),
+        "rr_align_images": (i, [vp, vp, i, vp, i, i, vp, vp]),
+        "rr_simulate_batch_align": (i, [vp, vp, i, vp, i, i, vp, vp, vp]),
+        # ---- frames assembled from blocks, streams, statistics
+        "rr_assemble_frames_device": (i, [vp, vp, i, sz, i, sz, vp, vp]),
+        "rr_simulate_device": (i, [vp, vp, vp, vp]),
+        "rr_synchronize": (i, [vp, vp]),
+        "rr_peek_error_bits_async": (i, [vp, vp, vp]),
+        "rr_get_stats": (i, [vp, P(RRStats)]),
+        "rr_set_stats_mode": (i, [vp, i]),
+        "rr_get_traversal_shape": (i, [vp, vp]),
+        # ---- introspection used by tests / bench
+        "rr_debug_trace": (i, [vp, vp, vp, sz, vp, vp]),
+        "rr_debug_fresnel": (i, [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "rr_debug_brdf": (i, [vp, sz, vp, i, vp]),
+        "rr_debug_column": (i, [vp, i, i, i, i, i, i, vp, vp, sz, vp, vp, vp, sz, vp, vp, vp]),
+        "rr_get_bvh_info": (i, [vp, P(u64), P(u64), P(u32), P(u32)]),
+        "rr_get_trace_grid": (i, [vp, vp, vp, P(u64)]),
+        "rr_get_graph_stats": (i, [vp, P(u64), P(u64)]),
+        "rr_set_timing_mode": (i, [vp, i]),
+        "rr_get_kernel_time": (i, [vp, s, P(dbl), P(u64), i]),
+        "rr_get_kernel_samples": (i, [vp, s, vp, sz, P(sz)]),
+        "rr_reserve_timing_events": (i, [vp, sz]),
+        # ---- echo provenance (rr_labels.hip)
+        "rr_simulate_batch_provenance_device": (i, [vp, vp, i, vp, vp, vp, vp, sz, vp, vp]),
+        "rr_simulate_provenance": (i, [vp, vp, vp, vp, vp, vp, sz, vp]),
+        "rr_debug_labels": (i, [vp, i, i, vp, vp, sz, vp, vp]),
+        # ---- wave paths (rr_paths.hip)
+        "rr_simulate_batch_paths_device": (i, [vp, vp, i, vp, vp, sz, vp, vp, u, vp]),
+        "rr_simulate_paths": (i, [vp, vp, vp, vp, sz, vp, vp, u]),
+        # ---- Doppler (rr_doppler.hip)
+        "rr_simulate_batch_doppler_device": (i, [vp, vp, i, vp, f, vp, vp, sz, vp, vp, vp, vp]),
+        "rr_simulate_doppler": (i, [vp, vp, vp, f, vp, vp, vp, sz, vp, vp, vp]),
+        # ---- point clouds and Cartesian images (rr_detect.hip)
+        "rr_default_detect_config": (None, [P(RRDetectConfig)]),
+        "rr_detect_device": (i, [vp, vp, i, P(RRDetectConfig), vp, i, vp, vp]),
+        "rr_detect": (i, [vp, vp, i, P(RRDetectConfig), vp, i, vp]),
+        "rr_polar_to_cartesian_device": (i, [vp, vp, i, P(RRCartesianConfig), vp, vp]),
+        "rr_polar_to_cartesian": (i, [vp, vp, i, P(RRCartesianConfig), vp]),
+        # ---- object annotations (rr_notes.hip)
+        "rr_annotate_scratch_bytes": (sz, [i, i, i]),
+        "rr_annotate_labels_device": (i, [vp, vp, vp, i, i, u32, vp, vp, vp, sz, vp]),
+        "rr_annotate_labels": (i, [vp, vp, vp, i, i, u32, vp, vp]),
+        "rr_label_points_device": (i, [vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp]),
+        "rr_polar_to_cartesian_labels_device": (i, [vp, vp, i, P(RRCartesianConfig), vp, vp]),
+        "rr_polar_to_cartesian_labels": (i, [vp, vp, i, P(RRCartesianConfig), vp]),
+        "rr_simulate_batch_annotations": (i, [vp, vp, i, u32, vp, vp, vp]),
+        # ---- translation registration (rr_shift.hip)
+        "rr_shift_images_device": (i, [vp, vp, i, vp, i, i, i, vp, vp, vp, vp]),
+        "rr_shift_images": (i, [vp, vp, i, vp, i, i, i, vp, vp, vp]),
+        "rr_simulate_batch_shift": (i, [vp, vp, i, vp, P(RRCartesianConfig), i, vp, vp, vp]),
+        # ---- place recognition (rr_place.hip)
+        "rr_describe_images_device": (i, [vp, vp, i, P(RRPlaceConfig), vp, vp]),
+        "rr_describe_images": (i, [vp, vp, i, P(RRPlaceConfig), vp]),
+        "rr_simulate_batch_describe": (i, [vp, vp, i, P(RRPlaceConfig), vp]),
+        "rr_match_descriptors_device": (i, [vp, vp, i, vp, i, i, i, i, vp, vp, vp, vp]),
+        "rr_match_descriptors": (i, [vp, vp, i, vp, i, i, i, i, vp, vp, vp]),
+        # ---- sweep compensation (rr_deskew.hip)
+        "rr_sweep_table_device": (i, [vp, vp, vp, vp, f, i, vp, vp]),
+        "rr_sweep_table": (i, [vp, vp, vp, vp, f, i, vp]),
+        "rr_compensate_points_device": (i, [vp, vp, vp, i, i, vp, vp, vp]),
+        "rr_compensate_points": (i, [vp, vp, vp, i, i, vp, vp]),
+        "rr_polar_to_cartesian_sweep_device": (i, [vp, vp, i, P(RRCartesianConfig), vp, i, vp, vp]),
+        "rr_polar_to_cartesian_sweep": (i, [vp, vp, i, P(RRCartesianConfig), vp, i, vp]),
+        # ---- scan matching (rr_icp.hip)
+        "rr_register_points_device": (i, [vp, vp, vp, i, i, vp, vp, i, vp, f, i, vp, vp, vp]),
+        "rr_register_points": (i, [vp, vp, vp, i, i, vp, u32, i, vp, f, i, vp, vp]),
+        "rr_icp_tile_sizes": (None, [P(i), P(i)]),
+        # ---- likelihood field (rr_field.hip)
+        "rr_rasterize_points_device": (i, [vp, vp, vp, i, i, vp, P(RRFieldConfig), vp, vp]),
+        "rr_rasterize_points": (i, [vp, vp, vp, i, i, vp, P(RRFieldConfig), vp]),
+        "rr_distance_field_device": (i, [vp, vp, i, P(RRFieldConfig), vp, vp]),
+        "rr_distance_field": (i, [vp, vp, i, P(RRFieldConfig), vp]),
+        "rr_score_poses_device": (i, [vp, vp, vp, i, vp, i, vp, P(RRFieldConfig), vp, vp]),
+        "rr_score_poses": (i, [vp, vp, u32, i, vp, i, vp, P(RRFieldConfig), vp]),
+        "rr_field_tile_sizes": (None, [P(i), P(i), P(i)]),
+        # ---- several GPUs of one node behind one object (rr_multi.hip)
+        "rr_create_multi": (vp, [P(i), i]),
+        "rr_destroy_multi": (None, [vp]),
+        "rr_multi_last_error": (s, [vp]),
+        "rr_multi_device_count": (i, [vp]),
+        "rr_multi_rccl_version": (i, [vp]),
+        "rr_multi_ctx": (vp, [vp, i]),
+        "rr_partition": (None, [i, i, i, P(i), P(i)]),
+        "rr_multi_plan": (i, [i, i, i, i, P(i), P(sz), vp, vp, vp]),
+        "rr_multi_set_mesh": (i, [vp, vp, sz, vp, sz, vp]),
+        "rr_multi_set_mesh_gpu": (i, [vp, vp, sz, vp, sz, vp]),
+        "rr_multi_set_object_poses": (i, [vp, vp, sz]),
+        "rr_multi_update_vertices": (i, [vp, vp, sz]),
+        "rr_multi_rebuild_tree": (i, [vp, i]),
+        "rr_multi_set_materials": (i, [vp, vp, sz, vp, sz, i32]),
+        "rr_multi_set_config": (i, [vp, P(RRConfig)]),
+        "rr_multi_set_beam_samples": (i, [vp, vp, sz]),
+        "rr_multi_set_noise_offsets": (i, [vp, vp, sz]),
+        "rr_multi_set_motion_poses": (i, [vp, vp, sz]),
+        "rr_multi_simulate": (i, [vp, vp, vp]),
+        "rr_multi_simulate_batch": (i, [vp, vp, i, vp]),
+        "rr_multi_simulate_batch_async": (i, [vp, vp, i, vp]),
+        "rr_multi_wait": (i, [vp, vp]),
+        # ---- host side of the seam (no GPU involved)
+        "rr_cone_dirs": (i, [f, i, f, vp, vp, sz, vp]),
+        "rr_sample_cone_local": (i, [u32, f, sz, i, f, vp]),
+        "rr_load_mesh_file": (i, [s, P(RRMesh), s, sz]),
+        "rr_mesh_reorder_objects": (i, [P(RRMesh), P(s), sz, s, sz]),
+        "rr_free_mesh": (None, [P(RRMesh)]),
+    }
+
+
+PROTOTYPES = _prototypes()
+SYMBOLS = list(PROTOTYPES)
+
+
 def build(force=False):
     """hipcc --offload-arch=gfx950 build of the in-tree shared library."""
     src = os.path.join(_HERE, "csrc")
@@ -457,157 +554,16 @@ def lib():
     except Exception:
         pass
     L = C.CDLL(LIB_PATH)
-    vp = C.c_void_p
-    L.rr_abi_version.restype = C.c_int
-    L.rr_default_config.argtypes = [C.POINTER(RRConfig)]
-    L.rr_create.restype = vp
-    L.rr_create.argtypes = [C.c_int]
-    L.rr_destroy.argtypes = [vp]
-    L.rr_last_error.restype = C.c_char_p
-    L.rr_last_error.argtypes = [vp]
-    L.rr_set_mesh.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp]
-    L.rr_set_mesh_gpu.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp]
-    L.rr_copy_mesh.argtypes = [vp, vp]
-    L.rr_set_materials.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int32]
-    L.rr_set_config.argtypes = [vp, C.POINTER(RRConfig)]
-    L.rr_set_beam_samples.argtypes = [vp, vp, C.c_size_t]
-    L.rr_set_noise_offsets.argtypes = [vp, vp, C.c_size_t]
-    L.rr_set_motion_poses.argtypes = [vp, vp, C.c_size_t]
-    L.rr_simulate.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, C.POINTER(RRStats)]
-    L.rr_simulate_columns_device.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
-    L.rr_simulate_batch_columns_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
-    L.rr_assemble_image_device.argtypes = [vp, vp, vp, vp]
-    L.rr_assemble_blocks_device.argtypes = [vp, vp, C.c_int, C.c_size_t, vp, vp]
-    L.rr_assemble_frames_device.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_int, C.c_size_t, vp, vp]
-    L.rr_simulate_device.argtypes = [vp, vp, vp, vp]
-    L.rr_simulate_material_sets_device.argtypes = [vp, vp, vp, C.c_int, C.c_size_t, vp, vp]
-    L.rr_simulate_material_sets.argtypes = [vp, vp, vp, C.c_int, C.c_size_t, vp]
-    L.rr_simulate_batch_device.argtypes = [vp, vp, C.c_int, vp, vp]
-    L.rr_synchronize.argtypes = [vp, vp]
-    L.rr_get_stats.argtypes = [vp, C.POINTER(RRStats)]
-    L.rr_set_stats_mode.argtypes = [vp, C.c_int]
-    L.rr_set_timing_mode.argtypes = [vp, C.c_int]
-    L.rr_get_kernel_time.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int]
-    L.rr_debug_trace.argtypes = [vp, vp, vp, C.c_size_t, vp, vp]
-    L.rr_debug_fresnel.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.rr_debug_brdf.argtypes = [vp, C.c_size_t, vp, C.c_int, vp]
-    L.rr_debug_column.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp, vp, vp]
-    L.rr_get_trace_grid.argtypes = [vp, vp, vp, C.POINTER(C.c_uint64)]
-    L.rr_get_graph_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    L.rr_get_bvh_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
-                                  C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    L.rr_get_kernel_samples.argtypes = [vp, C.c_char_p, vp, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.rr_reserve_timing_events.argtypes = [vp, C.c_size_t]
-    L.rr_simulate_batch_host_async.argtypes = [vp, vp, C.c_int, vp, vp]
-    L.rr_wait_host.argtypes = [vp, vp]
-    L.rr_copy_to_host_async.argtypes = [vp, vp, vp, C.c_size_t, vp]
-    L.rr_deliver_to_host_async.argtypes = [vp, vp, vp, C.c_size_t, vp]
-    L.rr_host_delivery_route.argtypes = [vp]
-    L.rr_host_alloc.restype = vp
-    L.rr_host_alloc.argtypes = [C.c_size_t]
-    L.rr_host_free.argtypes = [vp]
-    L.rr_host_free.restype = None
-    L.rr_partition.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.rr_partition.restype = None
-    L.rr_multi_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_size_t), vp, vp, vp]
-    L.rr_create_multi.restype = vp
-    L.rr_create_multi.argtypes = [C.POINTER(C.c_int), C.c_int]
-    L.rr_destroy_multi.argtypes = [vp]
-    L.rr_destroy_multi.restype = None
-    L.rr_multi_last_error.restype = C.c_char_p
-    L.rr_multi_last_error.argtypes = [vp]
-    L.rr_multi_device_count.argtypes = [vp]
-    L.rr_multi_rccl_version.argtypes = [vp]
-    L.rr_multi_ctx.restype = vp
-    L.rr_multi_ctx.argtypes = [vp, C.c_int]
-    L.rr_multi_set_mesh.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp]
-    L.rr_multi_set_mesh_gpu.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp]
-    L.rr_multi_set_materials.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int32]
-    L.rr_multi_set_config.argtypes = [vp, C.POINTER(RRConfig)]
-    L.rr_multi_set_beam_samples.argtypes = [vp, vp, C.c_size_t]
-    L.rr_multi_set_noise_offsets.argtypes = [vp, vp, C.c_size_t]
-    L.rr_multi_set_motion_poses.argtypes = [vp, vp, C.c_size_t]
-    L.rr_multi_simulate.argtypes = [vp, vp, vp]
-    L.rr_multi_simulate_batch.argtypes = [vp, vp, C.c_int, vp]
-    L.rr_multi_simulate_batch_async.argtypes = [vp, vp, C.c_int, vp]
-    L.rr_multi_wait.argtypes = [vp, vp]
-    L.rr_peek_error_bits_async.argtypes = [vp, vp, vp]
-    L.rr_get_traversal_shape.argtypes = [vp, vp]
-    L.rr_simulate_param_sets_device.argtypes = [vp, vp, C.POINTER(RRParamSet), C.c_int, C.c_size_t, vp, vp]
-    L.rr_simulate_param_sets.argtypes = [vp, vp, C.POINTER(RRParamSet), C.c_int, C.c_size_t, vp, vp, vp]
-    L.rr_score_images_device.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
-    L.rr_cone_dirs.argtypes = [C.c_float, C.c_int, C.c_float, vp, vp, C.c_size_t, vp]
-    L.rr_sample_cone_local.argtypes = [C.c_uint32, C.c_float, C.c_size_t, C.c_int, C.c_float, vp]
-    L.rr_load_mesh_file.argtypes = [C.c_char_p, C.POINTER(RRMesh), C.c_char_p, C.c_size_t]
-    L.rr_free_mesh.argtypes = [C.POINTER(RRMesh)]
-    L.rr_mesh_reorder_objects.argtypes = [C.POINTER(RRMesh), C.POINTER(C.c_char_p), C.c_size_t, C.c_char_p, C.c_size_t]
-    L.rr_free_mesh.restype = None
-    L.rr_set_object_poses.argtypes = [vp, vp, C.c_size_t]
-    L.rr_update_vertices.argtypes = [vp, vp, C.c_size_t]
-    L.rr_get_tree_cost.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    L.rr_rebuild_tree.argtypes = [vp, C.c_int]
-    L.rr_multi_set_object_poses.argtypes = [vp, vp, C.c_size_t]
-    L.rr_multi_update_vertices.argtypes = [vp, vp, C.c_size_t]
-    L.rr_multi_rebuild_tree.argtypes = [vp, C.c_int]
-    L.rr_default_detect_config.argtypes = [C.POINTER(RRDetectConfig)]
-    L.rr_default_detect_config.restype = None
-    L.rr_detect_device.argtypes = [vp, vp, C.c_int, C.POINTER(RRDetectConfig), vp, C.c_int, vp, vp]
-    L.rr_detect.argtypes = [vp, vp, C.c_int, C.POINTER(RRDetectConfig), vp, C.c_int, vp]
-    L.rr_polar_to_cartesian_device.argtypes = [vp, vp, C.c_int, C.POINTER(RRCartesianConfig), vp, vp]
-    L.rr_polar_to_cartesian.argtypes = [vp, vp, C.c_int, C.POINTER(RRCartesianConfig), vp]
-    L.rr_compare_images_device.argtypes = [vp, vp, C.c_int, vp, C.c_uint32, C.c_int, vp, vp, vp]
-    L.rr_compare_images.argtypes = [vp, vp, C.c_int, vp, C.c_uint32, C.c_int, vp, vp]
-    L.rr_simulate_param_sets_metrics.argtypes = [vp, vp, C.POINTER(RRParamSet), C.c_int, C.c_size_t, vp, vp, C.c_uint32, C.c_int, vp]
-    L.rr_align_images_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp]
-    L.rr_align_images.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]
-    L.rr_simulate_batch_align.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp]
-    L.rr_shift_images_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
-    L.rr_shift_images.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
-    L.rr_simulate_batch_shift.argtypes = [vp, vp, C.c_int, vp, C.POINTER(RRCartesianConfig), C.c_int, vp, vp, vp]
-    L.rr_describe_images_device.argtypes = [vp, vp, C.c_int, C.POINTER(RRPlaceConfig), vp, vp]
-    L.rr_describe_images.argtypes = [vp, vp, C.c_int, C.POINTER(RRPlaceConfig), vp]
-    L.rr_simulate_batch_describe.argtypes = [vp, vp, C.c_int, C.POINTER(RRPlaceConfig), vp]
-    L.rr_match_descriptors_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
-    L.rr_match_descriptors.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
-    L.rr_simulate_batch_provenance_device.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, C.c_size_t, vp, vp]
-    L.rr_simulate_provenance.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
-    L.rr_simulate_batch_paths_device.argtypes = [vp, vp, C.c_int, vp, vp, C.c_size_t, vp, vp, C.c_uint, vp]
-    L.rr_simulate_paths.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp, C.c_uint]
-    L.rr_debug_labels.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_size_t, vp, vp]
-    L.rr_set_object_twists.argtypes = [vp, vp, C.c_size_t]
-    L.rr_simulate_batch_doppler_device.argtypes = [vp, vp, C.c_int, vp, C.c_float, vp, vp, C.c_size_t, vp, vp, vp, vp]
-    L.rr_simulate_doppler.argtypes = [vp, vp, vp, C.c_float, vp, vp, vp, C.c_size_t, vp, vp, vp]
-    L.rr_annotate_scratch_bytes.restype = C.c_size_t
-    L.rr_annotate_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-    L.rr_annotate_labels_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_uint32, vp, vp, vp, C.c_size_t, vp]
-    L.rr_annotate_labels.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_uint32, vp, vp]
-    L.rr_label_points_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]
-    L.rr_polar_to_cartesian_labels_device.argtypes = [vp, vp, C.c_int, C.POINTER(RRCartesianConfig), vp, vp]
-    L.rr_polar_to_cartesian_labels.argtypes = [vp, vp, C.c_int, C.POINTER(RRCartesianConfig), vp]
-    L.rr_simulate_batch_annotations.argtypes = [vp, vp, C.c_int, C.c_uint32, vp, vp, vp]
-    L.rr_sweep_table_device.argtypes = [vp, vp, vp, vp, C.c_float, C.c_int, vp, vp]
-    L.rr_sweep_table.argtypes = [vp, vp, vp, vp, C.c_float, C.c_int, vp]
-    L.rr_compensate_points_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]
-    L.rr_compensate_points.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp]
-    L.rr_polar_to_cartesian_sweep_device.argtypes = [vp, vp, C.c_int, C.POINTER(RRCartesianConfig), vp, C.c_int, vp, vp]
-    L.rr_polar_to_cartesian_sweep.argtypes = [vp, vp, C.c_int, C.POINTER(RRCartesianConfig), vp, C.c_int, vp]
-    L.rr_register_points_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_float, C.c_int, vp, vp, vp]
-    L.rr_register_points.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_uint32, C.c_int, vp, C.c_float, C.c_int, vp, vp]
-    L.rr_icp_tile_sizes.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.rr_icp_tile_sizes.restype = None
-    fc = C.POINTER(RRFieldConfig)
-    L.rr_rasterize_points_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, fc, vp, vp]
-    L.rr_rasterize_points.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, fc, vp]
-    L.rr_distance_field_device.argtypes = [vp, vp, C.c_int, fc, vp, vp]
-    L.rr_distance_field.argtypes = [vp, vp, C.c_int, fc, vp]
-    L.rr_score_poses_device.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp, fc, vp, vp]
-    L.rr_score_poses.argtypes = [vp, vp, C.c_uint32, C.c_int, vp, C.c_int, vp, fc, vp]
-    L.rr_field_tile_sizes.argtypes = [C.POINTER(C.c_int)] * 3
-    L.rr_field_tile_sizes.restype = None
-    for n in SYMBOLS:
-        getattr(L, n)
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(L, name)          # AttributeError: the library lacks an entry point the header declares
+        fn.restype, fn.argtypes = restype, argtypes
     _LIB = L
     return L
+
+
+def _ptr(a):
+    """an optional array -> its address, or None (a null pointer)"""
+    return None if a is None else a.ctypes.data
 
 
 def _rows(a, width, what):
@@ -618,6 +574,14 @@ def _rows(a, width, what):
     if not ((x.ndim == 2 and x.shape[1] == width) or (x.ndim == 1 and x.size % width == 0)):
         raise ValueError("%s must have shape [n][%d], got %s" % (what, width, x.shape))
     return np.ascontiguousarray(x, np.float32).reshape(-1, width)
+
+
+def _pose_batch(poses):
+    """the poses of one batched call: float32 [n][7], n in 1..64 (RR_MAX_BATCH)"""
+    p = _rows(poses, 7, "poses")
+    if not 1 <= len(p) <= 64:
+        raise ValueError("1..64 poses, got %d" % len(p))
+    return p
 
 
 def object_poses_array(poses):
@@ -779,7 +743,76 @@ def _frames_arg(n_frames):
     return _int_in(n_frames, 1, 65535, "n_frames")
 
 
-class Context:
+class _Scene:
+    """What Context and MultiContext share: the error check and the nine scene setters.  _PREFIX selects the rr_ or the rr_multi_ entry
+    points and with them the matching last-error function."""
+    _PREFIX = "rr_"
+
+    def _fn(self, name):
+        return getattr(self._L, self._PREFIX + name)
+
+    def _ck(self, rc):
+        if rc != 0:
+            raise RRError("%s (rc=%d)" % (self._fn("last_error")(self._h).decode(), rc))
+
+    def set_mesh(self, verts, faces, face_object_id=None, builder="host"):
+        v = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+        f = np.ascontiguousarray(faces, np.uint32).reshape(-1, 3)
+        o = None if face_object_id is None else np.ascontiguousarray(face_object_id, np.uint32)
+        if o is not None and len(o) != len(f):
+            raise ValueError("face_object_id must have one entry per face")
+        fn = self._fn({"host": "set_mesh", "gpu": "set_mesh_gpu"}[builder])
+        self._ck(fn(self._h, v.ctypes.data, len(v), f.ctypes.data, len(f), _ptr(o)))
+        self.n_objects = int(o.max()) + 1 if o is not None and len(o) else 1
+
+    # ---- dynamic scenes (include/radarays_mi355.h): the traced scene is every face's rest corners moved by its object's pose
+    def set_object_poses(self, poses):
+        """one rigid pose per object, [n_objects][7] = qx qy qz qw tx ty tz; the tree is refit in place (rr_set_object_poses)"""
+        p = object_poses_array(poses)
+        self._ck(self._fn("set_object_poses")(self._h, p.ctypes.data, len(p)))
+
+    def update_vertices(self, verts):
+        """new rest vertices (same count as the mesh's), poses kept (rr_update_vertices)"""
+        v = vertex_array(verts)
+        self._ck(self._fn("update_vertices")(self._h, v.ctypes.data, len(v)))
+
+    def rebuild_tree(self, builder="host"):
+        """a fresh tree of the posed scene ("host" SAH or "gpu" LBVH); rest geometry and poses stay (rr_rebuild_tree)"""
+        b = builder_id(builder)
+        self._ck(self._fn("rebuild_tree")(self._h, b))
+
+    def set_materials(self, materials, object_materials, material_id_air=0):
+        m = (RRMaterial * len(materials))(*[RRMaterial(*[float(x) for x in (t.astuple() if hasattr(t, "astuple") else t)])
+                                            for t in materials])
+        om = np.ascontiguousarray(object_materials, np.int32)
+        self._ck(self._fn("set_materials")(self._h, m, len(materials), om.ctypes.data, len(om), int(material_id_air)))
+
+    def set_config(self, cfg, n_angles=400, **kw):
+        self.cfg = cfg
+        self.n_angles = n_angles
+        self._rrcfg = make_config(cfg, n_angles, **kw)
+        self._ck(self._fn("set_config")(self._h, C.byref(self._rrcfg)))
+
+    def set_beam_samples(self, dirs):
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        self._ck(self._fn("set_beam_samples")(self._h, d.ctypes.data, len(d)))
+
+    def set_noise_offsets(self, rnd):
+        """[n_angles] offsets, or [k][n_angles] (flat or 2-D): frame f of a batch uses row f % k."""
+        r = np.ascontiguousarray(rnd, np.float32).ravel()
+        self._ck(self._fn("set_noise_offsets")(self._h, r.ctypes.data, r.size))
+
+    def set_motion_poses(self, poses):
+        """include_motion: [n_angles][7] per-azimuth poses, or [k][n_angles][7] (frame f of a batch uses table f % k);
+        None/empty switches it off."""
+        if poses is None or len(poses) == 0:
+            self._ck(self._fn("set_motion_poses")(self._h, None, 0))
+            return
+        p = np.ascontiguousarray(poses, np.float32).reshape(-1, 7)
+        self._ck(self._fn("set_motion_poses")(self._h, p.ctypes.data, len(p)))
+
+
+class Context(_Scene):
     """Owns one rr_ctx (one GPU)."""
 
     def __init__(self, device=0):
@@ -803,30 +836,10 @@ class Context:
         except Exception:
             pass
 
-    def _ck(self, rc):
-        if rc != 0:
-            raise RRError("%s (rc=%d)" % (self._L.rr_last_error(self._h).decode(), rc))
-
-    def set_mesh(self, verts, faces, face_object_id=None, builder="host"):
-        v = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
-        f = np.ascontiguousarray(faces, np.uint32).reshape(-1, 3)
-        o = None if face_object_id is None else np.ascontiguousarray(face_object_id, np.uint32)
-        if o is not None and len(o) != len(f):
-            raise ValueError("face_object_id must have one entry per face")
-        fn = {"host": self._L.rr_set_mesh, "gpu": self._L.rr_set_mesh_gpu}[builder]
-        self._ck(fn(self._h, v.ctypes.data, len(v), f.ctypes.data, len(f), None if o is None else o.ctypes.data))
-        self.n_objects = int(o.max()) + 1 if o is not None and len(o) else 1
-
     def copy_mesh(self, src):
         """take the finished tree of another context (same or another device): rr_copy_mesh"""
         self._ck(self._L.rr_copy_mesh(self._h, src._h))
         self.n_objects = getattr(src, "n_objects", 1)
-
-    # ---- dynamic scenes (include/radarays_mi355.h): the traced scene is every face's rest corners moved by its object's pose
-    def set_object_poses(self, poses):
-        """one rigid pose per object, [n_objects][7] = qx qy qz qw tx ty tz; the tree is refit in place (rr_set_object_poses)"""
-        p = object_poses_array(poses)
-        self._ck(self._L.rr_set_object_poses(self._h, p.ctypes.data, len(p)))
 
     def set_object_twists(self, twists=None):
         """one twist per object, [n_objects][6] = vx vy vz wx wy wz (map frame, about the map origin), read by the Doppler calls only;
@@ -838,51 +851,11 @@ class Context:
             raise ValueError("twists must be [n_objects][6] (vx vy vz wx wy wz), got %s" % (t.shape,))
         self._ck(self._L.rr_set_object_twists(self._h, t.ctypes.data if len(t) else None, len(t)))
 
-    def update_vertices(self, verts):
-        """new rest vertices (same count as the mesh's), poses kept (rr_update_vertices)"""
-        v = vertex_array(verts)
-        self._ck(self._L.rr_update_vertices(self._h, v.ctypes.data, len(v)))
-
     def tree_cost(self):
         """(cost of the current boxes, cost of the tree as built): rr_get_tree_cost; their ratio says when a rebuild pays"""
         a, b = C.c_double(), C.c_double()
         self._ck(self._L.rr_get_tree_cost(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
-
-    def rebuild_tree(self, builder="host"):
-        """a fresh tree of the posed scene ("host" SAH or "gpu" LBVH); rest geometry and poses stay (rr_rebuild_tree)"""
-        b = builder_id(builder)
-        self._ck(self._L.rr_rebuild_tree(self._h, b))
-
-    def set_materials(self, materials, object_materials, material_id_air=0):
-        m = (RRMaterial * len(materials))(*[RRMaterial(*[float(x) for x in (t.astuple() if hasattr(t, "astuple") else t)])
-                                            for t in materials])
-        om = np.ascontiguousarray(object_materials, np.int32)
-        self._ck(self._L.rr_set_materials(self._h, m, len(materials), om.ctypes.data, len(om), int(material_id_air)))
-
-    def set_config(self, cfg, n_angles=400, **kw):
-        self.cfg = cfg
-        self.n_angles = n_angles
-        self._rrcfg = make_config(cfg, n_angles, **kw)
-        self._ck(self._L.rr_set_config(self._h, C.byref(self._rrcfg)))
-
-    def set_beam_samples(self, dirs):
-        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
-        self._ck(self._L.rr_set_beam_samples(self._h, d.ctypes.data, len(d)))
-
-    def set_noise_offsets(self, rnd):
-        """[n_angles] offsets, or [k][n_angles] (flat or 2-D): frame f of a batch uses row f % k."""
-        r = np.ascontiguousarray(rnd, np.float32).ravel()
-        self._ck(self._L.rr_set_noise_offsets(self._h, r.ctypes.data, r.size))
-
-    def set_motion_poses(self, poses):
-        """include_motion: [n_angles][7] per-azimuth poses, or [k][n_angles][7] (frame f of a batch uses table f % k);
-        None/empty switches it off."""
-        if poses is None or len(poses) == 0:
-            self._ck(self._L.rr_set_motion_poses(self._h, None, 0))
-            return
-        p = np.ascontiguousarray(poses, np.float32).reshape(-1, 7)
-        self._ck(self._L.rr_set_motion_poses(self._h, p.ctypes.data, len(p)))
 
     def simulate(self, pose, az_begin=0, az_end=None, want_f32=False):
         """Host-buffer path (rr_simulate). Returns (u8 [n_cells][n_angles], f32|None, stats)."""
@@ -894,8 +867,7 @@ class Context:
         u8 = np.zeros((n_cells, self.n_angles), np.uint8)
         f32 = np.zeros((n_cells, self.n_angles), np.float32) if want_f32 else None
         st = RRStats()
-        self._ck(self._L.rr_simulate(self._h, p.ctypes.data, az_begin, az_end, u8.ctypes.data,
-                                     None if f32 is None else f32.ctypes.data, C.byref(st)))
+        self._ck(self._L.rr_simulate(self._h, p.ctypes.data, az_begin, az_end, u8.ctypes.data, _ptr(f32), C.byref(st)))
         return u8, f32, st.asdict()
 
     def simulate_into(self, pose, out_u8):
@@ -1017,7 +989,7 @@ class Context:
                 raise ValueError("metrics need a reference image [n_cells][n_angles] uint8")
             rec = np.zeros(len(sets), METRICS_DTYPE)
             self._ck(self._L.rr_simulate_param_sets_metrics(self._h, p.ctypes.data, arr, len(sets), int(n_materials),
-                                                            None if out is None else out.ctypes.data, ref.ctypes.data, which, win, rec.ctypes.data))
+                                                            _ptr(out), ref.ctypes.data, which, win, rec.ctypes.data))
             return out, rec
         psnr = ref = None
         if ref_u8 is not None:
@@ -1025,9 +997,7 @@ class Context:
             if ref.shape != (n_cells, self.n_angles):
                 raise ValueError("reference image must be [n_cells][n_angles] uint8")
             psnr = np.zeros(len(sets), np.float64)
-        self._ck(self._L.rr_simulate_param_sets(self._h, p.ctypes.data, arr, len(sets), int(n_materials),
-                                                None if out is None else out.ctypes.data,
-                                                None if ref is None else ref.ctypes.data, None if psnr is None else psnr.ctypes.data))
+        self._ck(self._L.rr_simulate_param_sets(self._h, p.ctypes.data, arr, len(sets), int(n_materials), _ptr(out), _ptr(ref), _ptr(psnr)))
         return out, psnr
 
     def simulate_param_sets_device(self, pose, sets, n_materials, d_imgs_ptr, stream=None):
@@ -1059,15 +1029,12 @@ class Context:
         """rr_compare_images on host images [n][n_cells][n_angles] (or one image) against ref [n_cells][n_angles] ->
         METRICS_DTYPE array [n], and with want_hist the joint histograms uint32 [n][256][256] as well"""
         x = self._polar_images(imgs)
-        r = self._polar_images(ref)
-        if len(r) != 1:
-            raise ValueError("one reference image, got %d" % len(r))
+        r = self._one_reference(ref)
         which = metrics_mask(which)
         win = _win_arg(which, win_size)
         rec = np.zeros(len(x), METRICS_DTYPE)
         hist = np.zeros((len(x), 256, 256), np.uint32) if want_hist else None
-        self._ck(self._L.rr_compare_images(self._h, x.ctypes.data, len(x), r.ctypes.data, which, win, rec.ctypes.data,
-                                           None if hist is None else hist.ctypes.data))
+        self._ck(self._L.rr_compare_images(self._h, x.ctypes.data, len(x), r.ctypes.data, which, win, rec.ctypes.data, _ptr(hist)))
         return (rec, hist) if want_hist else rec
 
     # ---- azimuth registration (rr_align.hip): the circular cross-correlation of images with one reference over all shifts
@@ -1101,33 +1068,24 @@ class Context:
         """rr_align_images on host images [n][n_cells][n_angles] (or one image) against ref [n_cells][n_angles] -> ALIGN_DTYPE
         array [n], and with want_curve xcorr int64 [n][n_angles] as well"""
         x = self._polar_images(imgs)
-        r = self._polar_images(ref)
-        if len(r) != 1:
-            raise ValueError("one reference image, got %d" % len(r))
+        r = self._one_reference(ref)
         cb, ce = self._cell_window(cell_begin, cell_end)
         rec = np.zeros(len(x), ALIGN_DTYPE)
         curve = np.zeros((len(x), self.n_angles), np.int64) if want_curve else None
-        self._ck(self._L.rr_align_images(self._h, x.ctypes.data, len(x), r.ctypes.data, cb, ce, rec.ctypes.data,
-                                         None if curve is None else curve.ctypes.data))
+        self._ck(self._L.rr_align_images(self._h, x.ctypes.data, len(x), r.ctypes.data, cb, ce, rec.ctypes.data, _ptr(curve)))
         return (rec, curve) if want_curve else rec
 
     def simulate_batch_align(self, poses, ref, cell_begin=0, cell_end=None, want_images=False, want_curve=False):
         """rr_simulate_batch_align: up to 64 poses simulated and registered against ref [n_cells][n_angles] ->
         (images uint8 [n][n_cells][n_angles] or None, ALIGN_DTYPE array [n], xcorr int64 [n][n_angles] or None)"""
-        r = self._polar_images(ref)
-        if len(r) != 1:
-            raise ValueError("one reference image, got %d" % len(r))
+        r = self._one_reference(ref)
         cb, ce = self._cell_window(cell_begin, cell_end)
-        p = _rows(poses, 7, "poses")
-        if not 1 <= len(p) <= 64:
-            raise ValueError("1..64 poses, got %d" % len(p))
+        p = _pose_batch(poses)
         n_cells, n_angles = self._polar_shape()
         out = np.zeros((len(p), n_cells, n_angles), np.uint8) if want_images else None
         rec = np.zeros(len(p), ALIGN_DTYPE)
         curve = np.zeros((len(p), n_angles), np.int64) if want_curve else None
-        self._ck(self._L.rr_simulate_batch_align(self._h, p.ctypes.data, len(p), r.ctypes.data, cb, ce,
-                                                 None if out is None else out.ctypes.data, rec.ctypes.data,
-                                                 None if curve is None else curve.ctypes.data))
+        self._ck(self._L.rr_simulate_batch_align(self._h, p.ctypes.data, len(p), r.ctypes.data, cb, ce, _ptr(out), rec.ctypes.data, _ptr(curve)))
         return out, rec, curve
 
     # ---- translation registration (rr_shift.hip): the 2-D cross-correlation of images [H][W] with one reference over -S..S pixels
@@ -1159,29 +1117,23 @@ class Context:
         rec = np.zeros(len(x), SHIFT_DTYPE)
         xc = np.zeros((len(x), d, d), np.int64) if want_surfaces else None
         sse = np.zeros((len(x), d, d), np.uint64) if want_surfaces else None
-        self._ck(self._L.rr_shift_images(self._h, x.ctypes.data, len(x), r.ctypes.data, h, w, s, rec.ctypes.data,
-                                         None if xc is None else xc.ctypes.data, None if sse is None else sse.ctypes.data))
+        self._ck(self._L.rr_shift_images(self._h, x.ctypes.data, len(x), r.ctypes.data, h, w, s, rec.ctypes.data, _ptr(xc), _ptr(sse)))
         return (rec, xc, sse) if want_surfaces else rec
 
     def simulate_batch_shift(self, poses, ref_polar, width, pixel_size, max_shift, bilinear=True, want_images=False, want_xcorr=False):
         """rr_simulate_batch_shift: up to 64 poses simulated, their images and ref_polar [n_cells][n_angles] made Cartesian
         (width x width, pixel_size m/pixel) and registered over -S..S pixels -> (Cartesian images uint8 [n][width][width] or
         None, SHIFT_DTYPE array [n], xcorr int64 [n][2S+1][2S+1] or None)"""
-        r = self._polar_images(ref_polar)
-        if len(r) != 1:
-            raise ValueError("one reference image, got %d" % len(r))
+        r = self._one_reference(ref_polar)
         c = cartesian_config(width, pixel_size, bilinear)
         _, _, s = shift_window(c.width, c.width, max_shift)
-        p = _rows(poses, 7, "poses")
-        if not 1 <= len(p) <= 64:
-            raise ValueError("1..64 poses, got %d" % len(p))
+        p = _pose_batch(poses)
         d = 2 * s + 1
         out = np.zeros((len(p), c.width, c.width), np.uint8) if want_images else None
         rec = np.zeros(len(p), SHIFT_DTYPE)
         xc = np.zeros((len(p), d, d), np.int64) if want_xcorr else None
-        self._ck(self._L.rr_simulate_batch_shift(self._h, p.ctypes.data, len(p), r.ctypes.data, C.byref(c), s,
-                                                 None if out is None else out.ctypes.data, rec.ctypes.data,
-                                                 None if xc is None else xc.ctypes.data))
+        self._ck(self._L.rr_simulate_batch_shift(self._h, p.ctypes.data, len(p), r.ctypes.data, C.byref(c), s, _ptr(out), rec.ctypes.data,
+                                                 _ptr(xc)))
         return out, rec, xc
 
     # ---- place recognition (rr_place.hip): ring/sector descriptors of polar images and their exact matching
@@ -1213,9 +1165,7 @@ class Context:
     def simulate_batch_describe(self, poses, place_cfg):
         """rr_simulate_batch_describe: up to 64 poses simulated and described, no image leaving the GPU -> uint8 [n][R][S]"""
         p = self._place_cfg(place_cfg)
-        ps = _rows(poses, 7, "poses")
-        if not 1 <= len(ps) <= 64:
-            raise ValueError("1..64 poses, got %d" % len(ps))
+        ps = _pose_batch(poses)
         out = np.zeros((len(ps), p.n_rings, p.n_sectors), np.uint8)
         self._ck(self._L.rr_simulate_batch_describe(self._h, ps.ctypes.data, len(ps), C.byref(p), out.ctypes.data))
         return out
@@ -1250,8 +1200,7 @@ class Context:
         rec = np.zeros((nq, k), PLACE_DTYPE)
         sse = np.zeros((nq, n), np.uint32) if want_full else None
         shift = np.zeros((nq, n), np.uint16) if want_full else None
-        self._ck(self._L.rr_match_descriptors(self._h, q.ctypes.data, nq, d.ctypes.data, n, r, s, k, rec.ctypes.data,
-                                              None if sse is None else sse.ctypes.data, None if shift is None else shift.ctypes.data))
+        self._ck(self._L.rr_match_descriptors(self._h, q.ctypes.data, nq, d.ctypes.data, n, r, s, k, rec.ctypes.data, _ptr(sse), _ptr(shift)))
         return (rec, sse, shift) if want_full else rec
 
     def simulate_device(self, pose, d_img_ptr, stream=None):
@@ -1263,6 +1212,13 @@ class Context:
         if self.cfg is None:
             raise RRError("rr_set_config has not been called")
         return int(self.cfg.n_cells), int(self.n_angles)
+
+    def _one_reference(self, ref):
+        """the one reference image [n_cells][n_angles] of a comparison, as _polar_images returns it"""
+        r = self._polar_images(ref)
+        if len(r) != 1:
+            raise ValueError("one reference image, got %d" % len(r))
+        return r
 
     def _polar_images(self, imgs):
         """uint8 [n][n_cells][n_angles] (or one [n_cells][n_angles] image) of this context's shape -> contiguous 3-D array"""
@@ -1382,7 +1338,7 @@ class Context:
         poses [n][7] and optionally map-frame sensor velocities [n][3] with the Doppler `gain` -> SWEEP_DTYPE [n][n_angles]"""
         az, ref, vel, g = self._sweep_inputs(az_poses, ref_poses, sensor_vel, gain)
         table = np.zeros(az.shape[:2], SWEEP_DTYPE)
-        self._ck(self._L.rr_sweep_table(self._h, az.ctypes.data, ref.ctypes.data, None if vel is None else vel.ctypes.data, g, len(ref),
+        self._ck(self._L.rr_sweep_table(self._h, az.ctypes.data, ref.ctypes.data, _ptr(vel), g, len(ref),
                                         table.ctypes.data))
         return table
 
@@ -1499,7 +1455,7 @@ class Context:
         recs = np.zeros(n, ICP_DTYPE)
         corr = np.full((n, mp), ICP_NONE, np.uint32) if want_corr else None
         self._ck(self._L.rr_register_points(self._h, buf.ctypes.data, offs.ctypes.data, n, mp, tgt.ctypes.data if len(tgt) else None, len(tgt),
-                                            len(tgt), None if x0 is None else x0.ctypes.data, g, it, recs.ctypes.data,
+                                            len(tgt), _ptr(x0), g, it, recs.ctypes.data,
                                             corr.ctypes.data if want_corr else None))
         if want_corr:
             return recs, [corr[f, :len(p)].copy() for f, p in enumerate(pts)]
@@ -1549,7 +1505,7 @@ class Context:
         buf = np.zeros((n, mp), POINT_DTYPE)
         for f, p in enumerate(pts):
             buf[f, :len(p)] = p
-        self._ck(self._L.rr_rasterize_points(self._h, buf.ctypes.data, offs.ctypes.data, n, mp, None if st is None else st.ctypes.data, C.byref(g),
+        self._ck(self._L.rr_rasterize_points(self._h, buf.ctypes.data, offs.ctypes.data, n, mp, _ptr(st), C.byref(g),
                                              out.ctypes.data))
         return out
 
@@ -1641,7 +1597,7 @@ class Context:
         k = _int_in(self.n_objects if n_objects is None else n_objects, 1, 0xFFFFFE, "n_objects")
         notes = np.zeros((len(x), k), NOTE_DTYPE)
         skipped = np.zeros(len(x), np.uint32)
-        self._ck(self._L.rr_annotate_labels(self._h, x.ctypes.data, None if z is None else z.ctypes.data, len(x), k, note_mask(extent),
+        self._ck(self._L.rr_annotate_labels(self._h, x.ctypes.data, _ptr(z), len(x), k, note_mask(extent),
                                             notes.ctypes.data, skipped.ctypes.data))
         return notes, skipped
 
@@ -1683,7 +1639,7 @@ class Context:
         notes = np.zeros((len(p), self.n_objects), NOTE_DTYPE)
         skipped = np.zeros(len(p), np.uint32)
         imgs = np.zeros((len(p), n_cells, n_angles), np.uint8) if want_images else None
-        self._ck(self._L.rr_simulate_batch_annotations(self._h, p.ctypes.data, len(p), note_mask(extent), None if imgs is None else imgs.ctypes.data,
+        self._ck(self._L.rr_simulate_batch_annotations(self._h, p.ctypes.data, len(p), note_mask(extent), _ptr(imgs),
                                                        notes.ctypes.data, skipped.ctypes.data))
         return notes, skipped, imgs
 
@@ -1790,9 +1746,8 @@ class Context:
         f32 = np.zeros((max(n_seg, 0), n_cells), np.float32)
         u8 = np.zeros((max(n_seg, 0), n_cells), np.uint8)
         st = np.zeros((max(n_seg, 0), 3), np.uint32)
-        ptr = lambda a: None if a is None else a.ctypes.data   # noqa: E731
         self._ck(self._L.rr_debug_column(self._h, int(n_frames), int(n_loc), int(az_begin), int(n_passes), int(n_beam),
-                                         int(bool(record_multi_path)), ptr(e), ptr(ec), ls, ptr(sl), ptr(sh), ptr(sc), ss,
+                                         int(bool(record_multi_path)), _ptr(e), _ptr(ec), ls, _ptr(sl), _ptr(sh), _ptr(sc), ss,
                                          f32.ctypes.data, u8.ctypes.data, st.ctypes.data))
         return f32, u8, st
 
@@ -1818,13 +1773,12 @@ class Context:
         lab = np.full((n_cells, A), LABEL_NONE, np.uint32) if want_labels else None
         fac = np.full((n_cells, A), LABEL_NONE, np.uint32) if want_faces else None
         cnt = np.zeros(A, np.uint32)
-        ptr = lambda a: None if a is None else a.ctypes.data   # noqa: E731
         if echo_stride is None:
             self._ck(self._L.rr_simulate_provenance(self._h, p.ctypes.data, u8.ctypes.data, None, None, None, 0, cnt.ctypes.data))
             echo_stride = max(int(cnt.max()), 1)
         echo_stride = _int_in(echo_stride, 0, 1 << 30, "echo_stride")
         ech = np.zeros((A, echo_stride), ECHO_SRC_DTYPE) if echo_stride else None
-        self._ck(self._L.rr_simulate_provenance(self._h, p.ctypes.data, u8.ctypes.data, ptr(lab), ptr(fac), ptr(ech), echo_stride, cnt.ctypes.data))
+        self._ck(self._L.rr_simulate_provenance(self._h, p.ctypes.data, u8.ctypes.data, _ptr(lab), _ptr(fac), _ptr(ech), echo_stride, cnt.ctypes.data))
         return u8, lab, fac, ech, cnt
 
     # ---- wave paths (include/radarays_mi355.h): every ray-cast wave's ray, hit, parent and echo per azimuth
@@ -1854,7 +1808,7 @@ class Context:
             wave_stride = max(int(cnt.max()), 1)
         wave_stride = _int_in(wave_stride, 0, 1 << 26, "wave_stride")
         wav = np.zeros((A, wave_stride), WAVE_DTYPE) if wave_stride else None
-        self._ck(self._L.rr_simulate_paths(self._h, p.ctypes.data, u8.ctypes.data, None if wav is None else wav.ctypes.data, wave_stride,
+        self._ck(self._L.rr_simulate_paths(self._h, p.ctypes.data, u8.ctypes.data, _ptr(wav), wave_stride,
                                            cnt.ctypes.data, pc.ctypes.data, flags))
         return u8, wav, cnt, pc
 
@@ -1868,7 +1822,7 @@ class Context:
         v = None if sensor_vel is None else np.ascontiguousarray(sensor_vel, np.float32).reshape(-1, 3)
         if v is not None and len(v) != len(p):
             raise ValueError("sensor_vel must hold one velocity per pose: %d poses, %d velocities" % (len(p), len(v)))
-        self._ck(self._L.rr_simulate_batch_doppler_device(self._h, p.ctypes.data, len(p), None if v is None else v.ctypes.data, float(gain), d_imgs_ptr,
+        self._ck(self._L.rr_simulate_batch_doppler_device(self._h, p.ctypes.data, len(p), _ptr(v), float(gain), d_imgs_ptr,
                                                           d_echo_vel_ptr, int(echo_stride), d_echo_counts_ptr, d_echo_cells_ptr, d_vel_img_ptr, stream))
 
     def simulate_doppler(self, pose, sensor_vel=None, gain=0.0, echo_stride=None, want_f32=False, want_vel_img=True):
@@ -1887,15 +1841,14 @@ class Context:
         f32 = np.zeros((n_cells, A), np.float32) if want_f32 else None
         img = np.full((n_cells, A), np.nan, np.float32) if want_vel_img else None
         cnt = np.zeros(A, np.uint32)
-        ptr = lambda a: None if a is None else a.ctypes.data   # noqa: E731
         if echo_stride is None:
-            self._ck(self._L.rr_simulate_doppler(self._h, p.ctypes.data, ptr(v), float(gain), u8.ctypes.data, None, None, 0, cnt.ctypes.data, None, None))
+            self._ck(self._L.rr_simulate_doppler(self._h, p.ctypes.data, _ptr(v), float(gain), u8.ctypes.data, None, None, 0, cnt.ctypes.data, None, None))
             echo_stride = max(int(cnt.max()), 1)
         echo_stride = _int_in(echo_stride, 0, 1 << 26, "echo_stride")
         vel = np.zeros((A, echo_stride), np.float32) if echo_stride else None
         cel = np.full((A, echo_stride), -1, np.int32) if echo_stride else None
-        self._ck(self._L.rr_simulate_doppler(self._h, p.ctypes.data, ptr(v), float(gain), u8.ctypes.data, ptr(f32), ptr(vel), echo_stride, cnt.ctypes.data,
-                                             ptr(cel), ptr(img)))
+        self._ck(self._L.rr_simulate_doppler(self._h, p.ctypes.data, _ptr(v), float(gain), u8.ctypes.data, _ptr(f32), _ptr(vel), echo_stride, cnt.ctypes.data,
+                                             _ptr(cel), _ptr(img)))
         return u8, f32, vel, cel, cnt, img
 
     def debug_labels(self, echoes, counts, az_begin=0):
@@ -1999,8 +1952,9 @@ def multi_plan(n_angles, n_cells, n_devices, n_frames):
     return bool(eq.value), int(bpd.value), so, ro, pb
 
 
-class MultiContext:
-    """rr_multi: several GPUs of one node behind one object (one process; RCCL inside the library)."""
+class MultiContext(_Scene):
+    """rr_multi: several GPUs of one node behind one object (one process; RCCL inside the library).  The scene setters reach every device."""
+    _PREFIX = "rr_multi_"
 
     def __init__(self, devices):
         self._L = lib()
@@ -2010,6 +1964,7 @@ class MultiContext:
             raise RRError(self._L.rr_multi_last_error(None).decode())
         self.cfg = None
         self.n_angles = 400
+        self.n_objects = 1
 
     def close(self):
         if getattr(self, "_h", None):
@@ -2022,35 +1977,12 @@ class MultiContext:
         except Exception:
             pass
 
-    def _ck(self, rc):
-        if rc != 0:
-            raise RRError("%s (rc=%d)" % (self._L.rr_multi_last_error(self._h).decode(), rc))
-
     def rccl_version(self):
         """NCCL version code of the RCCL library behind the communicator (0: none)"""
         return int(self._L.rr_multi_rccl_version(self._h))
 
     def device_count(self):
         return self._L.rr_multi_device_count(self._h)
-
-    def set_mesh(self, verts, faces, face_object_id=None, builder="host"):
-        v = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
-        f = np.ascontiguousarray(faces, np.uint32).reshape(-1, 3)
-        o = None if face_object_id is None else np.ascontiguousarray(face_object_id, np.uint32)
-        fn = {"host": self._L.rr_multi_set_mesh, "gpu": self._L.rr_multi_set_mesh_gpu}[builder]
-        self._ck(fn(self._h, v.ctypes.data, len(v), f.ctypes.data, len(f), None if o is None else o.ctypes.data))
-
-    def set_object_poses(self, poses):
-        p = object_poses_array(poses)
-        self._ck(self._L.rr_multi_set_object_poses(self._h, p.ctypes.data, len(p)))
-
-    def update_vertices(self, verts):
-        v = vertex_array(verts)
-        self._ck(self._L.rr_multi_update_vertices(self._h, v.ctypes.data, len(v)))
-
-    def rebuild_tree(self, builder="host"):
-        b = builder_id(builder)
-        self._ck(self._L.rr_multi_rebuild_tree(self._h, b))
 
     def tree_cost(self):
         """device 0's (cost now, cost as built): every device holds the same tree"""
@@ -2060,33 +1992,6 @@ class MultiContext:
         if rc != 0:
             raise RRError("%s (rc=%d)" % (self._L.rr_last_error(h).decode(), rc))
         return a.value, b.value
-
-    def set_materials(self, materials, object_materials, material_id_air=0):
-        m = (RRMaterial * len(materials))(*[RRMaterial(*[float(x) for x in (t.astuple() if hasattr(t, "astuple") else t)])
-                                            for t in materials])
-        om = np.ascontiguousarray(object_materials, np.int32)
-        self._ck(self._L.rr_multi_set_materials(self._h, m, len(materials), om.ctypes.data, len(om), int(material_id_air)))
-
-    def set_config(self, cfg, n_angles=400, **kw):
-        self.cfg, self.n_angles = cfg, n_angles
-        self._rrcfg = make_config(cfg, n_angles, **kw)
-        self._ck(self._L.rr_multi_set_config(self._h, C.byref(self._rrcfg)))
-
-    def set_beam_samples(self, dirs):
-        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
-        self._ck(self._L.rr_multi_set_beam_samples(self._h, d.ctypes.data, len(d)))
-
-    def set_noise_offsets(self, rnd):
-        r = np.ascontiguousarray(rnd, np.float32).ravel()
-        self._ck(self._L.rr_multi_set_noise_offsets(self._h, r.ctypes.data, r.size))
-
-    def set_motion_poses(self, poses):
-        """include_motion on every device: [n_angles][7], or [k][n_angles][7] (one table per frame of a batch); None: off."""
-        if poses is None or len(poses) == 0:
-            self._ck(self._L.rr_multi_set_motion_poses(self._h, None, 0))
-            return
-        p = np.ascontiguousarray(poses, np.float32).reshape(-1, 7)
-        self._ck(self._L.rr_multi_set_motion_poses(self._h, p.ctypes.data, len(p)))
 
     def simulate_batch(self, poses):
         """-> uint8 [n][n_cells][n_angles] in host memory."""

@@ -7,14 +7,42 @@ import subprocess
 
 import pytest
 
+from radarays_ros_amd import native
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "radarays_mi355.h")
 
 
+def _header():
+    """the header without its comments"""
+    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+
+
 def _declared():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(rr_[a-z0-9_]+)\s*\(", src)))
+    return sorted(set(re.findall(r"\b(rr_[a-z0-9_]+)\s*\(", _header())))
+
+
+def _prototypes():
+    """{name: (return type, [parameter declarations])} of every function the header declares"""
+    out = {}
+    for ret, name, params in re.findall(r"^[ \t]*((?:const\s+)?\w+[\s\*]+)(rr_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", _header(), flags=re.M):
+        assert name not in out, name
+        params = [p.strip() for p in params.split(",")]
+        out[name] = (re.sub(r"\s*\*", "*", " ".join(ret.split())), [] if params in ([""], ["void"]) else params)
+    return out
+
+
+def _header_structs():
+    """{struct: [field names]} of every `typedef struct name { ... } name;` in the header, the fields in declaration order.  A
+    declaration is `type a;`, `type a, b;`, `type a[n];` or `type* a;`."""
+    out = {}
+    for name, body in re.findall(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*\1\s*;", _header(), flags=re.S):
+        out[name] = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            first, *more = [re.sub(r"\[\d+\]", "", d).strip() for d in decl.split(",")]
+            out[name] += [re.search(r"(\w+)$", first).group(1)] + more
+        assert out[name] and all(re.fullmatch(r"\w+", f) for f in out[name]), (name, out[name])
+    return out
 
 
 def test_library_is_built_and_exports_every_declared_symbol(native_lib):
@@ -25,6 +53,7 @@ def test_library_is_built_and_exports_every_declared_symbol(native_lib):
     for n in names:
         assert hasattr(L, n), "missing symbol %s" % n
     assert sorted(native_lib.SYMBOLS) == names
+    assert all(getattr(native_lib.lib(), n).argtypes is not None for n in names)
 
 
 def test_no_torch_types_in_the_abi():
@@ -32,22 +61,103 @@ def test_no_torch_types_in_the_abi():
     assert "torch" not in src.lower() and "at::" not in src and "c10" not in src
 
 
-def test_struct_layouts_match_header(native_lib, tmp_path):
-    prog = tmp_path / "sz.c"
-    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "radarays_mi355.h"\n'
-                    'int main(){printf("%zu %zu %zu %zu %zu %zu\\n", sizeof(rr_config), sizeof(rr_material),'
-                    ' sizeof(rr_stats), offsetof(rr_config, resolution), offsetof(rr_config, wave_energy_threshold),'
-                    ' offsetof(rr_config, range_max));return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()
-    cfg, mat, st, off_res, off_thr, off_rm = map(int, out)
-    assert C.sizeof(native_lib.RRConfig) == cfg
-    assert C.sizeof(native_lib.RRMaterial) == mat == 16
-    assert C.sizeof(native_lib.RRStats) == st
-    assert native_lib.RRConfig.resolution.offset == off_res
-    assert native_lib.RRConfig.wave_energy_threshold.offset == off_thr
-    assert native_lib.RRConfig.range_max.offset == off_rm
+# ---- every row of native.PROTOTYPES against the header's prototype -------------------------------------------------------------------
+SCALARS = {"int": C.c_int, "unsigned": C.c_uint, "unsigned int": C.c_uint, "size_t": C.c_size_t, "int32_t": C.c_int32, "uint32_t": C.c_uint32,
+           "uint64_t": C.c_uint64, "float": C.c_float, "double": C.c_double}
+
+
+def _is_pointer(t):
+    return t in (C.c_void_p, C.c_char_p) or isinstance(t, type(C.POINTER(C.c_int)))
+
+
+def test_prototype_table_matches_the_header(native_lib):
+    """Argument count, pointer or scalar, every scalar's exact type and the return type of every entry point: a c_int where the
+    header says size_t, or a dropped argument, would load and run, and first show as wrong results on a GPU."""
+    protos = _prototypes()
+    assert len(protos) >= 130 and sorted(protos) == _declared()
+    table = native_lib.PROTOTYPES
+    assert sorted(table) == sorted(protos)                    # no row the header lacks, no prototype without a row
+    for name, (ret, params) in protos.items():
+        restype, argtypes = table[name]
+        assert len(argtypes) == len(params), (name, params)
+        for k, (p, t) in enumerate(zip(params, argtypes)):
+            if "*" in p or "[" in p:
+                assert _is_pointer(t), (name, k, p, t)
+            else:
+                ctype = re.sub(r"\s+", " ", re.sub(r"\bconst\b", "", p)).strip().rsplit(" ", 1)[0]
+                assert ctype in SCALARS, "%s: argument %d is %r, a type this test does not know" % (name, k, p)
+                assert t is SCALARS[ctype], (name, k, p, t)
+        if ret == "const char*":
+            assert restype is C.c_char_p, name
+        elif "*" in ret:
+            assert restype is C.c_void_p, name
+        else:
+            assert ret in ("int", "void", "size_t"), (name, ret)
+            assert restype is {"int": C.c_int, "void": None, "size_t": C.c_size_t}[ret], (name, ret, restype)
+
+
+# ---- every struct of the header against its Python form (native.STRUCTS) and gcc --------------------------------------------------
+# literals the layout is pinned to, beside what gcc says of the header
+SIZES = {"rr_object_note": 80, "rr_wave_rec": 64, "rr_radar_point": 24, "rr_sweep_rec": 32, "rr_icp_rec": 48, "rr_field_rec": 16,
+         "rr_field_config": 32, "rr_image_metrics": 72, "rr_align_record": 72, "rr_shift_record": 128, "rr_place_match": 40,
+         "rr_echo_src": 16, "rr_material": 16}
+OFFSETS = {"rr_wave_rec": [0, 12, 16, 28, 32, 40, 48, 52, 56, 60], "rr_field_config": [0, 4, 8, 12, 16, 20, 24, 28], "rr_field_rec": [0, 8, 12],
+           "rr_icp_rec": [0, 8, 16, 24, 32, 40, 44], "rr_echo_src": [0, 4, 8, 12]}
+FIELDS = {"rr_wave_rec": ["o", "range", "d", "face", "energy", "time", "info", "parent", "material", "echo"],
+          "rr_echo_src": ["cell", "strength", "face", "info"]}
+NO_PADDING = ["rr_place_match"]
+
+
+@pytest.fixture(scope="module")
+def gcc_layouts(tmp_path_factory):
+    """{struct: (sizeof, [(field, offsetof, sizeof field)])} as gcc lays out the header, from one program for all of its structs"""
+    structs = _header_structs()
+    lines = []
+    for name, fields in structs.items():
+        lines.append('printf("%s %%zu\\n", sizeof(%s));' % (name, name))
+        lines += ['printf("%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));' % (f, name, f, name, f) for f in fields]
+    d = tmp_path_factory.mktemp("layout")
+    (d / "layout.c").write_text('#include <stdio.h>\n#include <stddef.h>\n#include "radarays_mi355.h"\nint main(){%s return 0;}\n' % "\n".join(lines))
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(d / "layout.c"), "-o", str(d / "layout")], check=True)
+    rows = [r.split() for r in subprocess.run([str(d / "layout")], check=True, capture_output=True, text=True).stdout.splitlines()]
+    out = {}
+    for r in rows:
+        if len(r) == 2:
+            out[r[0]] = cur = (int(r[1]), [])
+        else:
+            cur[1].append((r[0], int(r[1]), int(r[2])))
+    assert {n: [f[0] for f in v[1]] for n, v in out.items()} == structs
+    return out
+
+
+def test_every_struct_of_the_header_has_a_python_form():
+    structs = _header_structs()
+    assert len(structs) >= 21 and len(structs) == len(re.findall(r"typedef\s+struct\s+\w+\s*\{", _header()))
+    assert sorted(native.STRUCTS) == sorted(structs)
+    assert set(SIZES) | set(OFFSETS) | set(FIELDS) | set(NO_PADDING) <= set(structs)
+
+
+@pytest.mark.parametrize("name", sorted(native.STRUCTS))
+def test_struct_layout_matches_header(gcc_layouts, name):
+    """Field names in the header's order, every offset, every field's size and the total size: of the ctypes Structure, and of the
+    numpy dtype where the struct is a record.  The field list is the header's own, so a field added there alone fails here."""
+    size, fields = gcc_layouts[name]
+    names, offsets, sizes = [f[0] for f in fields], [f[1] for f in fields], [f[2] for f in fields]
+    cls, dt = native.STRUCTS[name]
+    assert [f[0] for f in cls._fields_] == names
+    assert C.sizeof(cls) == size == SIZES.get(name, size)
+    assert [getattr(cls, f).offset for f in names] == offsets == OFFSETS.get(name, offsets)
+    assert [getattr(cls, f).size for f in names] == sizes
+    assert names == FIELDS.get(name, names)
+    if dt is not None:
+        assert list(dt.names) == names and dt.itemsize == size
+        assert [dt.fields[f][1] for f in names] == offsets and [dt.fields[f][0].itemsize for f in names] == sizes
+    if name in NO_PADDING:
+        assert sum(sizes) == size
+    if name == "rr_object_note":
+        assert dt.fields["sum_intensity"][1] == 48 and dt.fields["y_min"][1] == 64
+    if name == "rr_shift_record":
+        assert dt["sse_nb"].shape == (4,)
 
 
 def test_default_config_matches_reference_cfg(native_lib):

@@ -1,4 +1,5 @@
-"""Wave paths without a GPU: the record layout and the entry points of include/radarays_mi355.h ("wave paths"), the numpy helpers of
+"""Wave paths without a GPU: the constants of include/radarays_mi355.h ("wave paths"; names, prototypes and
+the record layout: tests/test_abi.py), the numpy helpers of
 radarays_ros_amd/radar.py on hand-made lists, and the restatement of the bounce loop (tests/paths_ref.py) pinned to the oracle's
 extended echo log -- exactly -- on eight azimuths of each case: the nested boxes of tests/test_gpu_labels.py ("N") and the cases A,
 B and B2 of tests/test_stream_host.py.  The premises tests/test_gpu_paths.py rests on are proven here on the oracle alone.
@@ -8,9 +9,7 @@ transmission child) and, separately, taking `parent` from the child slot s = 2 *
 of test_restatement_is_consistent red (check_list: a parent outside the previous pass; the children of one parent out of branch
 order).  tests/test_gpu_paths.py applies the same check_list to the kernel's lists and compares parent and info with the restatement
 field by field, so the same two slips in k_wave_gather fail there; those kernel mutations were reasoned, not run."""
-import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -22,7 +21,6 @@ from common import mats_tuple
 from radarays_ros_amd import radar
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ["rr_simulate_batch_paths_device", "rr_simulate_paths"]
 N_ANGLES = 400
 AZS = (0, 1, 100, 101, 200, 201, 300, 301)
 CASES = ("N", "A", "B", "B2")
@@ -91,26 +89,11 @@ def reference(oracle, case, rmp, az, map_frame=False):
 
 # ---- the interface ------------------------------------------------------------------------------------------------------------------
 def test_entry_points_are_declared_exported_and_bound(native_lib):
+    """(names, argument types and the record layout: tests/test_abi.py, for the whole header)"""
     header = open(os.path.join(ROOT, "include", "radarays_mi355.h")).read()
-    Lb = native_lib.lib()
-    for n in NEW:
-        assert n + "(" in header and n in native_lib.SYMBOLS and getattr(Lb, n).argtypes, n
-    assert "#define RR_ABI_VERSION 7" in header and Lb.rr_abi_version() == 7          # purely additive
+    assert "#define RR_ABI_VERSION 7" in header and native_lib.lib().rr_abi_version() == 7          # purely additive
     assert native_lib.WAVES_MAP_FRAME == 1 and "#define RR_WAVES_MAP_FRAME 1u" in header
     assert native_lib.WAVES_MAX_PASSES == 16 and "#define RR_WAVES_MAX_PASSES 16" in header
-
-
-def test_record_layout_matches_gcc(native_lib, tmp_path):
-    dt = native_lib.WAVE_DTYPE
-    lines = ['printf("%zu\\n", sizeof(rr_wave_rec));'] + ['printf("%%zu\\n", offsetof(rr_wave_rec, %s));' % f for f in dt.names]
-    prog = tmp_path / "layout.c"
-    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "radarays_mi355.h"\nint main(){%s return 0;}\n' % "".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)], check=True)
-    out = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert out[0] == dt.itemsize == C.sizeof(native_lib.RRWaveRec) == 64
-    assert list(dt.names) == ["o", "range", "d", "face", "energy", "time", "info", "parent", "material", "echo"] == [f[0] for f in native_lib.RRWaveRec._fields_]
-    assert out[1:] == [dt.fields[f][1] for f in dt.names] == [getattr(native_lib.RRWaveRec, f).offset for f in dt.names] == [0, 12, 16, 28, 32, 40, 48, 52, 56, 60]
 
 
 def test_calls_without_a_context_are_refused(native_lib):

@@ -1,9 +1,8 @@
 """Translation registration without a GPU: the numpy restatement (tests/shift_ref.py) agrees with the literal slice definition
-and with hand-worked cases, the entry points are declared and exported, the ctypes layout matches the header, the wrappers
+and with hand-worked cases, the feature's header text (names, prototypes and layouts: tests/test_abi.py), the wrappers
 refuse bad arguments before any call into the library, the kernels of rr_shift.hip use no scratch and at most the LDS their
 header states -- and the scene and the two poses of the simulated GPU test (tests/test_gpu_shift.py) are fixed here, where the
 restatement alone, on the oracle's images, must land within one pixel."""
-import ctypes
 import os
 import re
 import subprocess
@@ -19,7 +18,6 @@ from radarays_ros_amd import native, params, radar, scenes
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "radarays_ros_amd", "csrc")
 HEADER = os.path.join(ROOT, "include", "radarays_mi355.h")
-NEW = ["rr_shift_images_device", "rr_shift_images", "rr_simulate_batch_shift"]
 
 # the simulated case: the 12-triangle room (20 m x 16 m), 200 cells of 0.1 m, noise off; Cartesian images of 128 x 128 pixels of
 # 0.2 m; the image under test is rendered (-6, +4) pixels' worth of metres (forward, left) away from the reference's pose, at the
@@ -105,32 +103,10 @@ def test_a_cut_of_the_reference_is_found_where_it_was_cut():
 
 
 def test_shift_entry_points_are_declared_and_exported(native_lib):
+    """(names, argument types and struct layouts: tests/test_abi.py, for the whole header)"""
     header = open(HEADER).read()
-    declared = set(re.findall(r"\b(rr_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", header, flags=re.S)))
-    native_lib.build()
-    L = ctypes.CDLL(native_lib.LIB_PATH)
-    for n in NEW:
-        assert n in declared and n in native_lib.SYMBOLS, n
-        getattr(L, n)
     assert "#define RR_ABI_VERSION 7" in header
     assert "typedef struct rr_shift_record" in header
-
-
-def test_record_layout_matches_gcc(native_lib, tmp_path):
-    cls = native_lib.RRShiftRecord
-    lines = ['printf("%zu\\n", sizeof(rr_shift_record));']
-    lines += ['printf("%%zu\\n", offsetof(rr_shift_record, %s));' % f for f, _ in cls._fields_]
-    prog = tmp_path / "layout.c"
-    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "radarays_mi355.h"\nint main(){%s return 0;}\n' % "".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)], check=True)
-    out = iter(int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split())
-    assert ctypes.sizeof(cls) == next(out) == native_lib.SHIFT_DTYPE.itemsize == 128
-    assert [f for f, _ in cls._fields_] == list(native_lib.SHIFT_DTYPE.names)
-    for f, _ in cls._fields_:
-        off = next(out)
-        assert getattr(cls, f).offset == off == native_lib.SHIFT_DTYPE.fields[f][1], f
-    assert native_lib.SHIFT_DTYPE["sse_nb"].shape == (4,)
 
 
 def _unopened(n_cells=64, n_angles=16):
