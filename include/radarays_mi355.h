@@ -1177,6 +1177,76 @@ int rr_score_poses(rr_ctx* ctx, const rr_radar_point* points, uint32_t count, in
  * the transform's row pass (tests put counts and sizes at their edges) */
 void rr_field_tile_sizes(int* points_tile, int* hyps_per_group, int* row_tile);
 
+/* ---- occupancy mapping: posed scans fused into a log-odds grid (rr_occupancy.hip) -----------------------------------------
+ * The map under the likelihood field, made from evidence rather than from single detections: rr_rasterize_points writes a 1 into every
+ * cell any detection ever fell into, so one false alarm is a wall for ever, free space is not known at all and a wall seen 64 times
+ * weighs what a phantom seen once does.  Here a detection ADDS evidence to its cell, the free space a scan swept SUBTRACTS it, and the
+ * sum is thresholded.  The reference has no such step: parity is UNPINNED and everything below is the build's own definition (a numpy
+ * restatement in tests/occupancy_ref.py checks the kernels).  All f32 arithmetic is un-fused; every result is an integer and independent
+ * of order.
+ * GRID.  rr_field_config, its IN GRID rule and its cell index (above) are reused unchanged; max_dist and gate are IGNORED here (any
+ * value passes), so an evidence grid's map can be turned into a field on the same config.  The centre of cell (ix, iy), in f32:
+ *     qx = x0 + ((float)ix + 0.5f) * cell          qy = y0 + ((float)iy + 0.5f) * cell
+ * STATES are the rasteriser's: (c, s, tx, ty) f64 per scan, sensor frame into the map frame, rounded to f32 (cf, sf, txf, tyf) and used
+ * as given; NULL means the identity.
+ * EVIDENCE is int32 [height][width], zeroed by the caller; calls accumulate into it.  It holds plain, unsaturated sums, so neither the
+ * order of the scans nor the order of the calls matters.  Keeping a cell's sum within int32 is the caller's job: one call moves a cell
+ * down by at most n_frames * l_free (at most 65,535 * 127 < 2^23) and up by l_hit for every point that falls into it, so evidence
+ * cannot wrap while 127 * (all points ever fused + all scans ever fused) < 2^31, about 16.9 million points.
+ * rr_occupancy_update[_device] takes n scans laid out as rr_detect_device / rr_compensate_points_device write them (counts and offsets
+ * are read on the device; x, y and bin of a point are used) and runs three steps:
+ * 1. PROFILE.  Per scan f and image column col, with azimuth a = col - scroll (mod n_angles): the points of a column are sorted by bin,
+ *    so its FIRST detection is the point at index d_offsets[f][col], if the column has any (d_offsets[f][col + 1] > d_offsets[f][col]) and
+ *    that index is below max_points; fb is that point's bin.  fb = n_cells for a column with no detection.  A column whose detections
+ *    were all cut by max_points asserts nothing: its free_bins is 0.  Otherwise
+ *        free_bins = min(max(fb - margin_bins, 0), max_free_bin)
+ *        r = (float)((double)free_bins * resolution)          free2[f][a] = r * r              in f32
+ *    The profile goes to the caller's buffer d_profile, float [n][n_angles]: the device form uses no context memory.
+ * 2. FREE SPACE, the hot path.  Per cell and scan, all f32:
+ *        dx = qx - txf      dy = qy - tyf      px = cf*dx + sf*dy      py = cf*dy - sf*dx
+ *        u = the azimuth coordinate of atan2f(py, px) (that of rr_polar_to_cartesian: (phi - theta_min) / theta_inc mod n_angles)
+ *        a = the nearest azimuth index, rintf(u) mod n_angles          rho2 = px*px + py*py
+ *    The cell is FREE in that scan iff rho2 < free2[f][a]: ranges are compared squared.  A non-finite px or py is never free.
+ *        evidence[cell] -= l_free * (the number of scans of the call in which the cell is free)
+ *    atan2f is the device library's; the restatement's differs from it in the last place, which moves a cell on the border between two
+ *    azimuths to the other one: such cells, and nothing else, may differ from the restatement.
+ * 3. HITS.  Per point, the rasteriser's mapping px = (cf*x - sf*y) + txf, py = (sf*x + cf*y) + tyf and the IN GRID rule; every point that is
+ *    IN GRID adds l_hit to its cell (an integer atomic: several points in one cell each add, in any order).
+ * rr_occupancy_map[_device]: occ_u8 = clamp(128 + evidence, 0, 255) in integers.  128 is unknown, below it free, above it occupied;
+ * rr_distance_field(occ, threshold 129 or more) takes it as it is.
+ * The device forms enqueue on `stream` (NULL: the context's) with no host round trip and use NO context-owned memory: they may run on any
+ * stream beside batches in flight.  rr_occupancy_update_device is three launches (profile, free space, hits, in that order: the free pass
+ * writes without atomics), rr_occupancy_map_device one.  The host forms stage through context-owned buffers and are synchronous;
+ * rr_occupancy_update reads evidence_i32 as well as writing it.
+ * Refused with a message and nothing written: -1 for a null ctx; -2 for the update without a config (n_angles, n_cells, scroll_image,
+ * theta_min, theta_inc and resolution are read); -3 for a null required buffer (d_points may be null with max_points 0), a grid or model
+ * field outside its stated range, a non-finite cell, x0 or y0, a theta_inc of 0, n_frames outside 1..65535, max_points outside 0..65536,
+ * states not 8-byte aligned, d_profile or d_evidence_i32 not 4-byte aligned.
+ * LIMITS.  The map is planar.  One state per scan: a sweep's per-azimuth motion enters only through compensated points, the free pass
+ * uses the scan's single state.  Free space ends at the FIRST detection of an azimuth; radar sees past it, the model does not.  Partial
+ * azimuth coverage wraps as the Cartesian resampler's does.  No decay and no clamped log-odds inside the accumulator.  rr_multi has no
+ * such call. */
+typedef struct rr_occupancy_config {   /* 32 B */
+    int32_t l_hit;           /* 1..127: evidence added per detection */
+    int32_t l_free;          /* 0..127: evidence subtracted per free observation */
+    int32_t margin_bins;     /* 0..n_cells: bins in front of an azimuth's first detection that stay unknown */
+    int32_t max_free_bin;    /* 0..n_cells: free space is asserted for bins below it only; an azimuth with no detection is free up to it */
+    int32_t reserved_[4];
+} rr_occupancy_config;
+int rr_occupancy_update_device(rr_ctx* ctx, const rr_radar_point* d_points, const uint32_t* d_offsets /*[n][n_angles+1]*/, int n_frames,
+                               int max_points, const double* d_states_or_NULL /*[n][4]*/, const rr_field_config* cfg,
+                               const rr_occupancy_config* occ_cfg, float* d_profile /*[n][n_angles]*/,
+                               int32_t* d_evidence_i32 /*[height][width]*/, void* stream);
+int rr_occupancy_update(rr_ctx* ctx, const rr_radar_point* points, const uint32_t* offsets, int n_frames, int max_points,
+                        const double* states_or_NULL, const rr_field_config* cfg, const rr_occupancy_config* occ_cfg,
+                        int32_t* evidence_i32);                                                       /* host buffers, synchronous */
+int rr_occupancy_map_device(rr_ctx* ctx, const int32_t* d_evidence_i32, const rr_field_config* cfg, uint8_t* d_occ_u8 /*[height][width]*/,
+                            void* stream);
+int rr_occupancy_map(rr_ctx* ctx, const int32_t* evidence_i32, const rr_field_config* cfg, uint8_t* occ_u8);   /* host buffers */
+/* the blocking of k_occ_free: cells per workgroup, consecutive cells per thread, and the scans per staged profile chunk -- 0: the profile
+ * is gathered, the scans are not chunked (tests put sizes at the edges) */
+void rr_occupancy_tile_sizes(int* cells_per_group, int* cells_per_thread, int* scan_chunk);
+
 /* ---- several GPUs of one node behind one object (SURVEY.md §8b "Threading", §8e) -------------------------
  * The reference creates ONE backend object per process (src/radar_simulator.cpp:145-176) and fans out inside it
  * (OpenMP over azimuths, RadarCPU.cpp:155).  rr_multi is that object for n GPUs: one rr_ctx per device, mesh and

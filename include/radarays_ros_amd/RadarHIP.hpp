@@ -585,6 +585,26 @@ public:
         }
         return recs;
     }
+    // Occupancy mapping (rr_occupancy.hip; include/radarays_mi355.h): n clouds (detect() of scans: sorted by column, then bin), each under
+    // its state -- [n][4] = c s tx ty, or empty for the identity -- fused into `evidence`, int32 [height][width]: a detection adds
+    // occ_cfg.l_hit to its cell, every cell a scan saw to be empty loses occ_cfg.l_free.  An evidence vector of the grid's size is
+    // accumulated into, any other is replaced by zeros first.  Returns the byte map clamp(128 + evidence, 0, 255) -- 128 unknown, below it
+    // free, above it occupied -- which rr_distance_field takes at threshold 129.  Pose convention: a state maps a cloud's sensor frame
+    // into the map frame, q = [c -s; s c] p + (tx, ty).  Empty on error
+    std::vector<uint8_t> buildOccupancyMap(const std::vector<std::vector<rr_radar_point>>& clouds, const std::vector<double>& states,
+                                           const rr_field_config& cfg, const rr_occupancy_config& occ_cfg, std::vector<int32_t>& evidence)
+    {
+        std::vector<uint8_t> map;
+        if (!push()) return map;
+        if (!marshal::build_occupancy(m_ctx, clouds, states, m_n_angles, cfg, occ_cfg, evidence, map)) {
+            if (clouds.empty() || (!states.empty() && states.size() != 4 * clouds.size())) m_err = "buildOccupancyMap: no cloud, or states is not [n][4]";
+            else if (!std::all_of(clouds.begin(), clouds.end(), [&](const auto& c) { return marshal::sorted_by_column(c, m_n_angles); }))
+                m_err = "buildOccupancyMap: a cloud is not sorted by column, or names a column past n_angles";
+            else fail();
+            map.clear();
+        }
+        return map;
+    }
     const rr_stats& lastStats() const { return m_stats; }
 
 private:

@@ -259,4 +259,41 @@ inline bool score_poses(rr_ctx* ctx, const std::vector<rr_radar_point>& scan, co
                           out.data()) == 0;
 }
 
+// occupancy mapping (rr_occupancy_config): n clouds, each sorted by column then bin as rr_detect writes them and under its state (states
+// empty: the identity), fused into the int32 evidence [height][width] -- accumulated into what `evidence` holds if it has the grid's size,
+// else into zeros (rr_occupancy_update) -- and clamped into the byte map (rr_occupancy_map).  The offsets of each cloud are rebuilt from
+// its points' columns.  false: rr_last_error(ctx), or a states vector that is not [n][4], or a cloud that is not sorted by column
+inline bool sorted_by_column(const std::vector<rr_radar_point>& cloud, int n_angles)
+{
+    uint32_t last = 0;
+    for (const rr_radar_point& p : cloud) {
+        if (p.column >= (uint32_t)n_angles || p.column < last) return false;
+        last = p.column;
+    }
+    return true;
+}
+inline bool build_occupancy(rr_ctx* ctx, const std::vector<std::vector<rr_radar_point>>& clouds, const std::vector<double>& states, int n_angles,
+                            const rr_field_config& cfg, const rr_occupancy_config& occ_cfg, std::vector<int32_t>& evidence, std::vector<uint8_t>& map)
+{
+    const size_t n = clouds.size(), stride = (size_t)n_angles + 1;
+    const size_t cells = cfg.width > 0 && cfg.height > 0 ? (size_t)cfg.width * (size_t)cfg.height : 0;
+    if (evidence.size() != cells) evidence.assign(cells, 0);
+    map.assign(cells, 0);
+    if (n == 0 || (!states.empty() && states.size() != 4 * n)) return false;
+    size_t mp = 1;
+    for (const auto& c : clouds) mp = std::max(mp, c.size());
+    std::vector<rr_radar_point> pts(n * mp);
+    std::vector<uint32_t> offs(n * stride, 0u);
+    for (size_t f = 0; f < n; f++) {
+        std::copy(clouds[f].begin(), clouds[f].end(), pts.begin() + (std::ptrdiff_t)(f * mp));
+        if (!sorted_by_column(clouds[f], n_angles)) return false;
+        uint32_t* o = offs.data() + f * stride;
+        for (const rr_radar_point& p : clouds[f]) o[p.column + 1]++;   // counts, one slot up ...
+        for (size_t a = 0; a < (size_t)n_angles; a++) o[a + 1] += o[a];   // ... summed into the exclusive prefix, the total last
+    }
+    if (rr_occupancy_update(ctx, pts.data(), offs.data(), (int)n, (int)mp, states.empty() ? nullptr : states.data(), &cfg, &occ_cfg, evidence.data()))
+        return false;
+    return rr_occupancy_map(ctx, evidence.data(), &cfg, map.data()) == 0;
+}
+
 }  // namespace radarays_ros_amd::marshal

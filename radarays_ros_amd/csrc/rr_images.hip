@@ -1,5 +1,5 @@
 // rr_images.hip -- the C ABI's image entry points: images in, records / points / images out.  PSNR scores and metrics against a reference image
-// (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), place recognition (rr_place.hip), point clouds and Cartesian images (rr_detect.hip), sweep compensation (rr_deskew.hip), scan matching (rr_icp.hip), the likelihood field (rr_field.hip), object annotations (rr_notes.hip): each in a device form, which runs on the
+// (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), place recognition (rr_place.hip), point clouds and Cartesian images (rr_detect.hip), sweep compensation (rr_deskew.hip), scan matching (rr_icp.hip), the likelihood field (rr_field.hip), occupancy mapping (rr_occupancy.hip), object annotations (rr_notes.hip): each in a device form, which runs on the
 // caller's buffers and stream, and a host form, which drains c->stream and makes its round trip through a Stage over the context's pool (rr_stage.h).
 #include "rr_stage.h"
 #include <algorithm>
@@ -143,13 +143,20 @@ int check_icp(rr_ctx* c, const char* who, const void* points, const void* offset
     return 0;
 }
 
-// the refusals the likelihood-field calls share: a grid within its stated ranges
-int check_field_grid(rr_ctx* c, const std::string& w, const rr_field_config* g)
+// the refusals the likelihood-field and the occupancy calls share: the shape and the place of a grid within their stated ranges
+int check_grid_shape(rr_ctx* c, const std::string& w, const rr_field_config* g)
 {
     if (!g) return fail(c, -3, w + ": null config");
     if (g->width < 1 || g->width > 4096 || g->height < 1 || g->height > 4096) return fail(c, -3, w + ": width and height must be 1..4096");
     if (!(std::isfinite(g->cell) && g->cell > 0.0f)) return fail(c, -3, w + ": cell must be finite and > 0");
     if (!(std::isfinite(g->x0) && std::isfinite(g->y0))) return fail(c, -3, w + ": x0 and y0 must be finite");
+    return 0;
+}
+
+// ... and what the likelihood-field calls ask on top: the saturation and the gate
+int check_field_grid(rr_ctx* c, const std::string& w, const rr_field_config* g)
+{
+    int rc = check_grid_shape(c, w, g); if (rc) return rc;
     if (g->max_dist < 1 || g->max_dist > 255) return fail(c, -3, w + ": max_dist must be 1..255");
     if (g->gate < 0 || g->gate > g->max_dist) return fail(c, -3, w + ": gate must be 0..max_dist");
     return 0;
@@ -190,6 +197,38 @@ int check_score_poses(rr_ctx* c, const char* who, const void* points, bool have_
     if (n_hyp < 1 || n_hyp > (1 << 22)) return fail(c, -3, w + ": n_hyp must be 1..2^22");
     if ((uintptr_t)states % 4 != 0 || (uintptr_t)recs % 8 != 0) return fail(c, -3, w + ": d_states must be 4-byte and d_recs 8-byte aligned");
     return check_field_grid(c, w, g);
+}
+
+// the refusals of rr_occupancy_update_device / rr_occupancy_update: the config gives the polar geometry; max_dist and gate of the grid are ignored
+int check_occupancy_update(rr_ctx* c, const char* who, const void* points, const void* offsets, int n_frames, int max_points, const void* states,
+                           const rr_field_config* g, const rr_occupancy_config* o, bool have_profile, const void* profile, const void* evidence)
+{
+    const std::string w(who);
+    const bool sizes_ok = max_points >= 0 && max_points <= 65536;
+    int rc = check_images(c, w, offsets && have_profile && evidence && (!sizes_ok || max_points == 0 || points), "buffer", "n_frames", n_frames, 65535);
+    if (rc) return rc;
+    if (!sizes_ok) return fail(c, -3, w + ": max_points must be 0..65536");
+    if ((uintptr_t)states % 8 != 0) return fail(c, -3, w + ": the states must be 8-byte aligned");
+    if ((uintptr_t)profile % 4 != 0 || (uintptr_t)evidence % 4 != 0) return fail(c, -3, w + ": the profile and the evidence must be 4-byte aligned");
+    rc = check_grid_shape(c, w, g); if (rc) return rc;
+    if (!o) return fail(c, -3, w + ": null occupancy config");
+    const int n_cells = c->cfg.n_cells;
+    if (o->l_hit < 1 || o->l_hit > 127) return fail(c, -3, w + ": l_hit must be 1..127");
+    if (o->l_free < 0 || o->l_free > 127) return fail(c, -3, w + ": l_free must be 0..127");
+    if (o->margin_bins < 0 || o->margin_bins > n_cells) return fail(c, -3, w + ": margin_bins must be 0..n_cells (" + std::to_string(n_cells) + ")");
+    if (o->max_free_bin < 0 || o->max_free_bin > n_cells) return fail(c, -3, w + ": max_free_bin must be 0..n_cells (" + std::to_string(n_cells) + ")");
+    if (c->cfg.theta_inc == 0.0f) return fail(c, -3, w + ": the config's theta_inc is 0");
+    return 0;
+}
+
+// the refusals of rr_occupancy_map_device / rr_occupancy_map: no config is needed, the shape comes with the call
+int check_occupancy_map(rr_ctx* c, const char* who, const void* evidence, const rr_field_config* g, const void* occ)
+{
+    if (!c) return -1;
+    const std::string w(who);
+    if (!(evidence && occ)) return fail(c, -3, w + ": null buffer");
+    if ((uintptr_t)evidence % 4 != 0) return fail(c, -3, w + ": the evidence must be 4-byte aligned");
+    return check_grid_shape(c, w, g);
 }
 
 // the refusals the annotation calls share: a config (the plane shape) within the limits of the label planes and of the packed azimuth
@@ -973,6 +1012,65 @@ int rr_score_poses(rr_ctx* c, const rr_radar_point* points, uint32_t count, int 
     RR_HIP(c, st.hold(recs, n, d_recs));
     RR_HIP(c, hipStreamSynchronize(c->stream));        // (count is this call's own variable)
     rc = rr_score_poses_device(c, d_points, d_count, max_points, d_states, n_hyp, d_field, cfg, d_recs, c->stream); if (rc) return rc;
+    return st.commit();
+}
+
+// ---- occupancy mapping (rr_occupancy.hip) ---------------------------------------------------------------------------------
+void rr_occupancy_tile_sizes(int* cells_per_group, int* cells_per_thread, int* scan_chunk)
+{
+    occupancy_tile_sizes(cells_per_group, cells_per_thread, scan_chunk);
+}
+
+int rr_occupancy_update_device(rr_ctx* c, const rr_radar_point* d_points, const uint32_t* d_offsets, int n_frames, int max_points,
+                               const double* d_states, const rr_field_config* cfg, const rr_occupancy_config* occ_cfg, float* d_profile,
+                               int32_t* d_evidence_i32, void* stream)
+{
+    int rc = check_occupancy_update(c, "rr_occupancy_update_device", d_points, d_offsets, n_frames, max_points, d_states, cfg, occ_cfg,
+                                    d_profile != nullptr, d_profile, d_evidence_i32); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    launch_occupancy_update(d_points, d_offsets, n_frames, max_points, d_states, *cfg, *occ_cfg, polar_grid(c->cfg), d_profile, d_evidence_i32,
+                            stream_of(c, stream));
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_occupancy_update(rr_ctx* c, const rr_radar_point* points, const uint32_t* offsets, int n_frames, int max_points, const double* states,
+                        const rr_field_config* cfg, const rr_occupancy_config* occ_cfg, int32_t* evidence_i32)
+{
+    int rc = check_occupancy_update(c, "rr_occupancy_update", points, offsets, n_frames, max_points, nullptr, cfg, occ_cfg, true, nullptr,
+                                    evidence_i32); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)n_frames, cells = (size_t)cfg->width * cfg->height;
+    RR_STAGE(c, st);
+    std::vector<uint32_t> totals; rr_radar_point* d_points; uint32_t* d_offs; double* d_states; float* d_profile; int32_t* d_ev;
+    rc = up_points(c, st, points, offsets, n, (size_t)max_points, totals, d_points, d_offs); if (rc) return rc;
+    RR_HIP(c, st.up(states, n * 4, d_states));
+    RR_HIP(c, st.room(n * (size_t)c->cfg.n_angles, d_profile));
+    RR_HIP(c, st.up(evidence_i32, cells, d_ev));      // the call accumulates
+    rc = rr_occupancy_update_device(c, d_points, d_offs, n_frames, max_points, d_states, cfg, occ_cfg, d_profile, d_ev, c->stream); if (rc) return rc;
+    st.out(evidence_i32, d_ev, cells);
+    return st.commit();
+}
+
+int rr_occupancy_map_device(rr_ctx* c, const int32_t* d_evidence_i32, const rr_field_config* cfg, uint8_t* d_occ_u8, void* stream)
+{
+    int rc = check_occupancy_map(c, "rr_occupancy_map_device", d_evidence_i32, cfg, d_occ_u8); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    launch_occupancy_map(d_evidence_i32, *cfg, d_occ_u8, stream_of(c, stream));
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_occupancy_map(rr_ctx* c, const int32_t* evidence_i32, const rr_field_config* cfg, uint8_t* occ_u8)
+{
+    int rc = check_occupancy_map(c, "rr_occupancy_map", evidence_i32, cfg, occ_u8); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t cells = (size_t)cfg->width * cfg->height;
+    RR_STAGE(c, st);
+    int32_t* d_ev; uint8_t* d_occ;
+    RR_HIP(c, st.up(evidence_i32, cells, d_ev));
+    RR_HIP(c, st.hold(occ_u8, cells, d_occ));
+    rc = rr_occupancy_map_device(c, d_ev, cfg, d_occ, c->stream); if (rc) return rc;
     return st.commit();
 }
 

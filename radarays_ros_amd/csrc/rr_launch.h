@@ -1,4 +1,4 @@
-// rr_launch.h -- every launcher of rr_kernels.hip, rr_labels.hip, rr_paths.hip, rr_doppler.hip, rr_refit.hip, rr_detect.hip, rr_deskew.hip, rr_icp.hip, rr_field.hip, rr_notes.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip, rr_place.hip and rr_lbvh.hip, declared ONCE: included where they
+// rr_launch.h -- every launcher of rr_kernels.hip, rr_labels.hip, rr_paths.hip, rr_doppler.hip, rr_refit.hip, rr_detect.hip, rr_deskew.hip, rr_icp.hip, rr_field.hip, rr_occupancy.hip, rr_notes.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip, rr_place.hip and rr_lbvh.hip, declared ONCE: included where they
 // are defined (a definition that drifts from its declaration fails there) and where they are called.  Default arguments live here only.
 #pragma once
 #include "../../include/radarays_mi355.h"
@@ -87,6 +87,13 @@ void launch_field_raster(const rr_radar_point* points, const uint32_t* offsets, 
 void launch_distance_field(const uint8_t* occ, int threshold, const rr_field_config& g, uint16_t* field, hipStream_t s);
 void launch_field_score(const rr_radar_point* points, const uint32_t* count, int max_points, const float* states, int n_hyp, const uint16_t* field,
                         const rr_field_config& g, rr_field_rec* recs, hipStream_t s);
+// rr_occupancy.hip (occupancy mapping).  No scratch: profile [n_frames][n_angles] is written whole, evidence is accumulated into; states 8-byte
+// aligned or null, profile and evidence 4-byte aligned.  Three launches (profile, free space, hits) and one
+void occupancy_tile_sizes(int* cells_per_group, int* cells_per_thread, int* scan_chunk);
+void launch_occupancy_update(const rr_radar_point* points, const uint32_t* offsets, int n_frames, int max_points, const double* states,
+                             const rr_field_config& g, const rr_occupancy_config& o, const PolarGrid& G, float* profile, int32_t* evidence,
+                             hipStream_t s);
+void launch_occupancy_map(const int32_t* evidence, const rr_field_config& g, uint8_t* occ, hipStream_t s);
 // rr_notes.hip (object annotations).  scratch: note_scratch_bytes, 16-byte aligned like notes; every word of it, of notes and of skipped is written by the launches
 size_t note_scratch_bytes(size_t n_frames, size_t n_objects, int n_angles);
 void launch_notes(const uint32_t* labels, const uint8_t* imgs, int n_frames, uint32_t n_objects, uint32_t extent_mask, const PolarGrid& G,

@@ -219,6 +219,40 @@ def field_tile_sizes():
     return a.value, b.value, c.value
 
 
+# ---- occupancy mapping (rr_occupancy.hip).  rr_occupancy_config (32 B): the inverse sensor model of one update
+OCC_MAX_EVIDENCE = 127
+
+
+class RROccupancyConfig(C.Structure):
+    _fields_ = [("l_hit", C.c_int32), ("l_free", C.c_int32), ("margin_bins", C.c_int32), ("max_free_bin", C.c_int32), ("reserved_", C.c_int32 * 4)]
+
+
+def occupancy_config(l_hit, l_free, margin_bins, max_free_bin, n_cells):
+    """rr_occupancy_config, range-checked before any call into the library: l_hit (1..127) is added to a cell per detection, l_free (0..127)
+    subtracted per scan that saw it empty; margin_bins (0..n_cells) bins in front of an azimuth's first detection stay unknown; free space
+    is asserted below max_free_bin (0..n_cells) only, and an azimuth with no detection is free up to it"""
+    n = _int_in(n_cells, 1, 1 << 30, "n_cells")
+    return RROccupancyConfig(_int_in(l_hit, 1, OCC_MAX_EVIDENCE, "l_hit"), _int_in(l_free, 0, OCC_MAX_EVIDENCE, "l_free"),
+                             _int_in(margin_bins, 0, n, "margin_bins"), _int_in(max_free_bin, 0, n, "max_free_bin"), (C.c_int32 * 4)())
+
+
+def _grid_cfg(cfg):
+    """the grid of an occupancy call: an RRFieldConfig or a dict of field_config's arguments whose shape and place are range-checked;
+    max_dist and gate are ignored there and pass as they are"""
+    if isinstance(cfg, RRFieldConfig):
+        g = field_config(cfg.width, cfg.height, cfg.cell, cfg.x0, cfg.y0, 1, 0)
+        g.max_dist, g.gate = cfg.max_dist, cfg.gate
+        return g
+    return _field_cfg(cfg)
+
+
+def occupancy_tile_sizes():
+    """(cells per workgroup of k_occ_free, consecutive cells per thread of it, scans per staged profile chunk -- 0: not chunked)"""
+    a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+    lib().rr_occupancy_tile_sizes(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
 def _lattice_axis(half, step, what):
     half, step = float(half), float(step)
     if not (np.isfinite(half) and half >= 0 and np.isfinite(step) and step > 0):
@@ -365,7 +399,7 @@ STRUCTS = {
     "rr_cartesian_config": (RRCartesianConfig, None), "rr_object_note": (RRObjectNote, NOTE_DTYPE), "rr_shift_record": (RRShiftRecord, SHIFT_DTYPE),
     "rr_place_config": (RRPlaceConfig, None), "rr_place_match": (RRPlaceMatch, PLACE_DTYPE), "rr_sweep_rec": (RRSweepRec, SWEEP_DTYPE),
     "rr_icp_rec": (RRIcpRec, ICP_DTYPE), "rr_field_config": (RRFieldConfig, None), "rr_field_rec": (RRFieldRec, FIELD_DTYPE),
-    "rr_mesh": (RRMesh, None),
+    "rr_occupancy_config": (RROccupancyConfig, None), "rr_mesh": (RRMesh, None),
 }
 
 
@@ -493,6 +527,12 @@ def _prototypes():
         "rr_score_poses_device": (i, [vp, vp, vp, i, vp, i, vp, P(RRFieldConfig), vp, vp]),
         "rr_score_poses": (i, [vp, vp, u32, i, vp, i, vp, P(RRFieldConfig), vp]),
         "rr_field_tile_sizes": (None, [P(i), P(i), P(i)]),
+        # ---- occupancy mapping (rr_occupancy.hip)
+        "rr_occupancy_update_device": (i, [vp, vp, vp, i, i, vp, P(RRFieldConfig), P(RROccupancyConfig), vp, vp, vp]),
+        "rr_occupancy_update": (i, [vp, vp, vp, i, i, vp, P(RRFieldConfig), P(RROccupancyConfig), vp]),
+        "rr_occupancy_map_device": (i, [vp, vp, P(RRFieldConfig), vp, vp]),
+        "rr_occupancy_map": (i, [vp, vp, P(RRFieldConfig), vp]),
+        "rr_occupancy_tile_sizes": (None, [P(i), P(i), P(i)]),
         # ---- several GPUs of one node behind one object (rr_multi.hip)
         "rr_create_multi": (vp, [P(i), i]),
         "rr_destroy_multi": (None, [vp]),
@@ -1476,8 +1516,18 @@ class Context(_Scene):
         """rr_rasterize_points on what detect() (or compensate_points()) returned: a list of n POINT_DTYPE arrays and offsets uint32
         [n][n_angles + 1]; states float64 [n][4] (se2_states makes them) or None; occ: a uint8 [height][width] grid to accumulate into
         (it is not modified) or None for an empty one.  Returns the grid."""
-        _, n_angles = self._polar_shape()
         g = _field_cfg(field_cfg)
+        buf, offs, st = self._posed_clouds(points_list, offsets, states)
+        out = self._field_grid(occ, g, np.uint8, "occ").copy() if occ is not None else np.zeros((g.height, g.width), np.uint8)
+        self._ck(self._L.rr_rasterize_points(self._h, buf.ctypes.data, offs.ctypes.data, len(buf), buf.shape[1], _ptr(st), C.byref(g),
+                                             out.ctypes.data))
+        return out
+
+    def _posed_clouds(self, points_list, offsets, states):
+        """what the rasteriser and the occupancy update take from detect() (or compensate_points()): a list of n POINT_DTYPE arrays, offsets
+        uint32 [n][n_angles + 1] and states float64 [n][4] or None -> (the points as one POINT_DTYPE [n][max_points] block, the offsets,
+        the states), all contiguous"""
+        _, n_angles = self._polar_shape()
         if isinstance(points_list, np.ndarray) and points_list.ndim == 1:
             points_list = [points_list]
         pts = [np.asarray(p) for p in points_list]
@@ -1501,13 +1551,10 @@ class Context(_Scene):
             if st.dtype.kind not in "fiu" or st.shape != (n, 4):
                 raise ValueError("states must be real numbers of shape [%d][4] (c, s, tx, ty), got %s %s" % (n, st.dtype, st.shape))
             st = np.ascontiguousarray(st, np.float64)
-        out = self._field_grid(occ, g, np.uint8, "occ").copy() if occ is not None else np.zeros((g.height, g.width), np.uint8)
         buf = np.zeros((n, mp), POINT_DTYPE)
         for f, p in enumerate(pts):
             buf[f, :len(p)] = p
-        self._ck(self._L.rr_rasterize_points(self._h, buf.ctypes.data, offs.ctypes.data, n, mp, _ptr(st), C.byref(g),
-                                             out.ctypes.data))
-        return out
+        return buf, offs, st
 
     @staticmethod
     def _field_grid(a, g, dtype, what):
@@ -1557,6 +1604,57 @@ class Context(_Scene):
         self._ck(self._L.rr_score_poses(self._h, p.ctypes.data if len(p) else None, len(p), len(p), st.ctypes.data, len(st), f.ctypes.data,
                                         C.byref(g), recs.ctypes.data))
         return recs
+
+    # ---- occupancy mapping (rr_occupancy.hip): posed scans fused into an int32 evidence grid, and its uint8 map
+    def _occ_cfg(self, occ_cfg):
+        """an RROccupancyConfig or a dict of occupancy_config's arguments, held to this context's n_cells"""
+        n_cells, _ = self._polar_shape()
+        if isinstance(occ_cfg, RROccupancyConfig):
+            return occupancy_config(occ_cfg.l_hit, occ_cfg.l_free, occ_cfg.margin_bins, occ_cfg.max_free_bin, n_cells)
+        if isinstance(occ_cfg, dict):
+            return occupancy_config(n_cells=n_cells, **occ_cfg)
+        raise ValueError("an occupancy config must be an RROccupancyConfig (native.occupancy_config makes one) or a dict of its arguments, got %r"
+                         % (occ_cfg,))
+
+    def occupancy_update_device(self, d_points_ptr, d_offsets_ptr, n_frames, max_points, field_cfg, occ_cfg, d_profile_ptr, d_evidence_ptr,
+                                d_states_ptr=None, stream=None):
+        """rr_occupancy_update_device: the points [n_frames][max_points] and offsets [n_frames][n_angles + 1] rr_detect_device wrote, fused
+        into the int32 evidence [height][width] at d_evidence_ptr (zeroed by the caller, or holding earlier scans); d_profile_ptr: float32
+        [n_frames][n_angles] the call writes; d_states_ptr: float64 [n_frames][4] = (c, s, tx, ty), each scan's sensor frame into the map
+        frame, or None (identity); on `stream`"""
+        o = self._occ_cfg(occ_cfg)
+        n, mp, g = _frames_arg(n_frames), _int_in(max_points, 0, ICP_MAX_POINTS, "max_points"), _grid_cfg(field_cfg)
+        if not d_offsets_ptr or not d_profile_ptr or not d_evidence_ptr or (mp > 0 and not d_points_ptr):
+            raise ValueError("occupancy_update_device needs point, offset, profile and evidence buffers")
+        self._ck(self._L.rr_occupancy_update_device(self._h, d_points_ptr, d_offsets_ptr, n, mp, d_states_ptr, C.byref(g), C.byref(o), d_profile_ptr,
+                                                    d_evidence_ptr, stream))
+
+    def occupancy_update(self, points_list, offsets, field_cfg, occ_cfg, states=None, evidence=None):
+        """rr_occupancy_update on what detect() (or compensate_points()) returned: a list of n POINT_DTYPE arrays and offsets uint32
+        [n][n_angles + 1]; states float64 [n][4] (se2_states makes them), each scan's sensor frame into the map frame, or None; evidence: an
+        int32 [height][width] grid to accumulate into (it is not modified) or None for an empty one.  Returns the evidence."""
+        g, o = _grid_cfg(field_cfg), self._occ_cfg(occ_cfg)
+        buf, offs, st = self._posed_clouds(points_list, offsets, states)
+        out = self._field_grid(evidence, g, np.int32, "evidence").copy() if evidence is not None else np.zeros((g.height, g.width), np.int32)
+        self._ck(self._L.rr_occupancy_update(self._h, buf.ctypes.data, offs.ctypes.data, len(buf), buf.shape[1], _ptr(st), C.byref(g), C.byref(o),
+                                             out.ctypes.data))
+        return out
+
+    def occupancy_map_device(self, d_evidence_ptr, field_cfg, d_occ_ptr, stream=None):
+        """rr_occupancy_map_device: the uint8 map [height][width] at d_occ_ptr = clamp(128 + evidence, 0, 255) of the int32 evidence"""
+        g = _grid_cfg(field_cfg)
+        if not d_evidence_ptr or not d_occ_ptr:
+            raise ValueError("occupancy_map_device needs an evidence and a map buffer")
+        self._ck(self._L.rr_occupancy_map_device(self._h, d_evidence_ptr, C.byref(g), d_occ_ptr, stream))
+
+    def occupancy_map(self, evidence, field_cfg):
+        """rr_occupancy_map: int32 [height][width] -> uint8 [height][width]: 128 unknown, below it free, above it occupied
+        (distance_field(map, cfg, threshold=129) takes it as it is)"""
+        g = _grid_cfg(field_cfg)
+        ev = self._field_grid(evidence, g, np.int32, "evidence")
+        out = np.zeros((g.height, g.width), np.uint8)
+        self._ck(self._L.rr_occupancy_map(self._h, ev.ctypes.data, C.byref(g), out.ctypes.data))
+        return out
 
     # ---- object annotations (rr_notes.hip): one record per object from label images; any context with a config, mesh or not
     def _label_planes(self, planes, what="label planes"):

@@ -484,6 +484,38 @@ class RadarHIP:
             scan = pts[0]
         return self._ctx.score_poses(scan, states, field, field_cfg)
 
+    # ---- occupancy mapping (rr_occupancy.hip): posed scans fused into an evidence grid, and the byte map the likelihood field takes
+    def buildOccupancyMap(self, clouds, states, grid, l_hit=3, l_free=2, margin_bins=None, max_free_bin=None, evidence=None):
+        """n point clouds (POINT_DTYPE arrays as toPointCloud / simulatePointClouds return them: sorted by column, then bin) under their
+        states float64 [n][4] (None: the identity) on `grid` (native.field_config; max_dist and gate are not used) -> (evidence int32
+        [height][width], map uint8 [height][width]).  Every detection adds l_hit to its cell; every cell a scan saw to be empty -- nearer
+        than the first detection of its azimuth less margin_bins, and nearer than max_free_bin -- loses l_free; the map is
+        clamp(128 + evidence, 0, 255): 128 unknown, below it free, above it occupied, so distance_field(map, grid, threshold=129) is
+        the likelihood field of the fused map.  margin_bins None: ceil(0.71 * cell / resolution), half a cell's diagonal, so that a
+        wall's own cell is not swept free; max_free_bin None: n_cells.  evidence: an earlier call's, to accumulate into (not modified).
+        The offsets of each cloud are rebuilt from its points' columns.
+        Convention: a state (c, s, tx, ty) maps a cloud's sensor frame into the map frame, q = R p + t; a keyframe's state is the planar
+        part of its pose, (cos yaw, sin yaw, x, y)."""
+        self._push()
+        n_cells = self.m_cfg.n_cells
+        g = native._grid_cfg(grid)
+        if isinstance(clouds, np.ndarray) and clouds.ndim == 1:
+            clouds = [clouds]
+        pts = [np.asarray(c) for c in clouds]
+        if not pts or any(p.dtype != native.POINT_DTYPE or p.ndim != 1 for p in pts):
+            raise ValueError("clouds must be a non-empty list of one-dimensional POINT_DTYPE arrays")
+        offs = np.zeros((len(pts), N_ANGLES + 1), np.uint32)
+        for f, p in enumerate(pts):
+            col = p["column"].astype(np.int64)
+            if len(col) and (col.max() >= N_ANGLES or np.any(np.diff(col) < 0)):
+                raise ValueError("cloud %d is not sorted by column, or names a column past %d" % (f, N_ANGLES - 1))
+            offs[f, 1:] = np.cumsum(np.bincount(col, minlength=N_ANGLES))
+        if margin_bins is None:
+            margin_bins = min(n_cells, int(np.ceil(0.71 * g.cell / self.m_cfg.resolution)))
+        o = native.occupancy_config(l_hit, l_free, margin_bins, n_cells if max_free_bin is None else max_free_bin, n_cells)
+        ev = self._ctx.occupancy_update(pts, offs, g, o, states, evidence)
+        return ev, self._ctx.occupancy_map(ev, g)
+
     # ---- place recognition (rr_place.hip): a database of yaw-invariant ring/sector descriptors, and a scan looked up in it
     def buildPlaceDatabase(self, poses, place_cfg, on_device=False):
         """any number of [n][7] poses, worked through 64 at a time -> their descriptors uint8 [n][R][S] (native.Context._place_cfg
