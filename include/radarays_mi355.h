@@ -1247,6 +1247,80 @@ int rr_occupancy_map(rr_ctx* ctx, const int32_t* evidence_i32, const rr_field_co
  * is gathered, the scans are not chunked (tests put sizes at the edges) */
 void rr_occupancy_tile_sizes(int* cells_per_group, int* cells_per_thread, int* scan_chunk);
 
+/* ---- particle filter step: weigh, resample and move pose hypotheses (rr_filter.hip) ----------------------------------------
+ * What stands between two calls of rr_score_poses when a pose is tracked over time: the records become weights, the weights are
+ * systematically resampled, the survivors are moved by odometry plus diffusion.  Records, sums, ancestors and states stay in HBM.  The
+ * reference has no such step: parity is UNPINNED and everything below is the build's own definition (a numpy restatement in
+ * tests/filter_ref.py checks the kernels byte for byte).  Every result is an integer or a correctly rounded, un-fused f32 expression free
+ * of trigonometry, and independent of order.
+ * 1. rr_filter_resample[_device]: d_recs [n] (sum_d2 is read), a weight table uint16 [n_table] in HBM, n_out draws.
+ *        dmin = min_i sum_d2[i]                                     best = the lowest i that holds it
+ *        idx_i = min(n_table - 1, (sum_d2[i] - dmin) / quantum)     a u64 integer division
+ *        w_i = table[idx_i]
+ *        cum[i] = w_0 + ... + w_i   (u64, inclusive; an OUTPUT in the caller's buffer)        W = cum[n - 1] < 2^38        sum_w2 = sum w_i^2
+ *        r = (phase * W) >> 24                                      t_j = (j * W + r) / n_out   in u64; j * W < 2^60
+ *        ancestors[j] = min(n - 1, #{i : cum[i] <= t_j})            numpy's searchsorted(cum, t, side='right'), clamped
+ *        n_unique = 1 + #{j >= 1 : ancestors[j] != ancestors[j - 1]}   (the ancestors are non-decreasing)
+ *    The clamp also defines W == 0: every draw takes particle n - 1.  That is a definition, not an error.  The effective sample size
+ *    is total_weight^2 / sum_w2, for the caller to take from the summary.
+ * 2. rr_filter_move[_device]: d_states_in f32 [n][4] = (c, s, tx, ty), the convention of rr_score_poses; d_ancestors [n_out] or NULL,
+ *    which means a = j (and needs n_out <= n); an ancestor past n - 1 is read as n - 1.  The odometry increment (Dc, Ds, dx, dy) is in the
+ *    sensor frame and passed by value.  With mix32(x): x ^= x>>16; x *= 0x7feb352d; x ^= x>>15; x *= 0x846ca68b; x ^= x>>16 in uint32,
+ *        key = mix32(seed ^ mix32(step))          and for draw j and k in 0, 1, 2:
+ *        h = mix32(key ^ (8*j + 2*k))             g = mix32(key ^ (8*j + 2*k + 1))
+ *        v_k = (h & 0xffff) + (h >> 16) + (g & 0xffff) + (g >> 16) - 131070
+ *    an integer within +-131070, the centred sum of four uniforms, of variance (65536^2 - 1) / 3.  Then in f32, in exactly this order:
+ *        (c, s, tx, ty) = states_in[a]
+ *        nx = (float)v_0 * sigma_xy      ny = (float)v_1 * sigma_xy      t = (float)v_2 * sigma_t
+ *        ux = dx + nx                    uy = dy + ny
+ *        tx' = (c*ux - s*uy) + tx        ty' = (s*ux + c*uy) + ty
+ *        q = t*t      den = 1.0f + q     nc = (1.0f - q) / den           ns = (t + t) / den
+ *        rc = Dc*nc - Ds*ns              rs = Ds*nc + Dc*ns
+ *        c1 = c*rc - s*rs                s1 = s*rc + c*rs
+ *        m = sqrtf(c1*c1 + s1*s1)        c' = c1 / m                     s' = s1 / m
+ *    with IEEE division and square root.  states_out [n_out][4] = (c', s', tx', ty') must not overlap states_in.  Non-finite values pass
+ *    through (rr_score_poses costs a NaN state at count * cap2).
+ * The device forms enqueue on `stream` (NULL: the context's) with no host round trip and use NO context-owned memory: cum is the scan's
+ * only room.  rr_filter_resample_device is six launches (start values, minimum, tile sums, the scan of the tile sums by ONE workgroup,
+ * cum, draws), none of which waits on another workgroup; rr_filter_move_device is one.  The host forms stage through context-owned
+ * buffers and are synchronous.
+ * Refused with a message and nothing written: -1 for a null ctx; -3 for a null required buffer or config, a config field outside its
+ * stated range, reserved != 0, a non-finite or negative sigma, a non-finite increment, n or n_out outside 1..2^22, n_out > n without
+ * ancestors, states that overlap or are not 16-byte aligned, d_recs, d_cum or d_summary not 8-byte aligned, d_ancestors not 4-byte or
+ * d_table not 2-byte aligned.
+ * LIMITS.  Planar.  One scan per step.  No adaptive particle count and no KLD sampling.  The noise is a sum of four uniforms, not a
+ * Gaussian.  rr_multi has no such call. */
+typedef struct rr_filter_config {   /* 32 B */
+    uint32_t quantum;    /* 1..2^31: sum_d2 units per step of the weight table */
+    uint32_t n_table;    /* 1..4096 */
+    uint32_t phase;      /* 0..2^24 - 1: where the comb of draws starts */
+    uint32_t seed;
+    uint32_t step;       /* counter of this filter step; enters the hash */
+    float    sigma_xy;   /* finite, >= 0: metres per unit of the integer variate */
+    float    sigma_t;    /* finite, >= 0: tangent of the half angle per unit */
+    uint32_t reserved;   /* must be 0 */
+} rr_filter_config;
+typedef struct rr_filter_summary {  /* 32 B */
+    uint64_t min_sum_d2;
+    uint64_t total_weight;
+    uint64_t sum_w2;
+    uint32_t best;       /* the lowest index that holds min_sum_d2 */
+    uint32_t n_unique;   /* distinct ancestors among the n_out draws */
+} rr_filter_summary;
+int rr_filter_resample_device(rr_ctx* ctx, const rr_field_rec* d_recs /*[n]*/, int n /*1..2^22*/, const uint16_t* d_table /*[n_table]*/,
+                              int n_out /*1..2^22*/, const rr_filter_config* cfg, uint64_t* d_cum /*[n]*/, uint32_t* d_ancestors /*[n_out]*/,
+                              rr_filter_summary* d_summary, void* stream);
+int rr_filter_resample(rr_ctx* ctx, const rr_field_rec* recs, int n, const uint16_t* table, int n_out, const rr_filter_config* cfg,
+                       uint64_t* cum, uint32_t* ancestors, rr_filter_summary* summary);                 /* host buffers, synchronous */
+int rr_filter_move_device(rr_ctx* ctx, const float* d_states_in /*[n][4]*/, int n, const uint32_t* d_ancestors_or_NULL /*[n_out]*/, int n_out,
+                          float Dc, float Ds, float dx, float dy, const rr_filter_config* cfg, float* d_states_out /*[n_out][4]*/,
+                          void* stream);
+int rr_filter_move(rr_ctx* ctx, const float* states_in, int n, const uint32_t* ancestors_or_NULL, int n_out, float Dc, float Ds, float dx,
+                   float dy, const rr_filter_config* cfg, float* states_out);                             /* host buffers, synchronous */
+/* the blocking: records per scan tile (a workgroup's), draws per workgroup of the draw kernel, and the entries of cum a workgroup stages for
+ * its draws -- 0: the draws search cum in global memory (tests put n at the edges) */
+void rr_filter_tile_sizes(int* scan_tile, int* draws_per_group, int* search_tile);
+
 /* ---- several GPUs of one node behind one object (SURVEY.md §8b "Threading", §8e) -------------------------
  * The reference creates ONE backend object per process (src/radar_simulator.cpp:145-176) and fans out inside it
  * (OpenMP over azimuths, RadarCPU.cpp:155).  rr_multi is that object for n GPUs: one rr_ctx per device, mesh and

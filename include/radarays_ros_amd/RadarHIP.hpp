@@ -605,6 +605,28 @@ public:
         }
         return map;
     }
+    // Particle filter step (rr_filter.hip; include/radarays_mi355.h): ONE scan and ONE particle set, both in HBM and the caller's, as every
+    // buffer here is (d_recs [n], d_cum [n], d_ancestors [n], d_states_out [n][4], d_summary).  rr_score_poses_device,
+    // rr_filter_resample_device and rr_filter_move_device run on `stream`; only the 32-byte summary comes back, in `summary`.  The
+    // increment is the odometry (Dc, Ds, dx, dy) in the sensor frame.  n_eff_floor is the caller's resampling rule, decided here on the
+    // host from `previous`, the summary of the step before (nullptr: resample): if its effective sample size total_weight^2 / sum_w2 is at
+    // least n_eff_floor, every particle is kept and only moved.  The device never branches on it.  false on error
+    bool filterStep(const rr_radar_point* d_scan, const uint32_t* d_count, int max_points, const float* d_states_in, int n, const uint16_t* d_field,
+                    const rr_field_config& cfg, const uint16_t* d_table, const rr_filter_config& filter_cfg, const float (&increment)[4],
+                    rr_field_rec* d_recs, uint64_t* d_cum, uint32_t* d_ancestors, float* d_states_out, rr_filter_summary* d_summary,
+                    rr_filter_summary& summary, double n_eff_floor = 0.0, const rr_filter_summary* previous = nullptr, void* stream = nullptr)
+    {
+        if (!push()) return false;
+        bool resample = true;
+        if (previous && n_eff_floor > 0.0 && previous->sum_w2 > 0)
+            resample = (double)previous->total_weight * (double)previous->total_weight / (double)previous->sum_w2 < n_eff_floor;
+        if (!marshal::filter_step(m_ctx, d_scan, d_count, max_points, d_states_in, n, d_field, cfg, d_table, filter_cfg, increment, resample, d_recs,
+                                  d_cum, d_ancestors, d_states_out, d_summary, stream, summary)) {
+            fail();
+            return false;
+        }
+        return true;
+    }
     const rr_stats& lastStats() const { return m_stats; }
 
 private:

@@ -296,4 +296,24 @@ inline bool build_occupancy(rr_ctx* ctx, const std::vector<std::vector<rr_radar_
     return rr_occupancy_map(ctx, evidence.data(), &cfg, map.data()) == 0;
 }
 
+// one particle filter step on `stream`, every buffer the caller's and in HBM (rr_filter_config, rr_filter_summary): the particles d_states_in
+// [n][4] f32 scored against the field (rr_score_poses_device -> d_recs [n]), the records weighed through d_table and resampled
+// (rr_filter_resample_device -> d_cum [n], d_ancestors [n], d_summary), the survivors moved by the increment (Dc, Ds, dx, dy) plus the
+// config's diffusion into d_states_out [n][4] (rr_filter_move_device; resample false: every particle is kept, the move runs without
+// ancestors).  Only the 32-byte summary comes home.  false: rr_last_error(ctx)
+inline bool filter_step(rr_ctx* ctx, const rr_radar_point* d_scan, const uint32_t* d_count, int max_points, const float* d_states_in, int n,
+                        const uint16_t* d_field, const rr_field_config& cfg, const uint16_t* d_table, const rr_filter_config& fcfg,
+                        const float (&increment)[4], bool resample, rr_field_rec* d_recs, uint64_t* d_cum, uint32_t* d_ancestors,
+                        float* d_states_out, rr_filter_summary* d_summary, void* stream, rr_filter_summary& summary)
+{
+    summary = rr_filter_summary{};
+    if (rr_score_poses_device(ctx, d_scan, d_count, max_points, d_states_in, n, d_field, &cfg, d_recs, stream)) return false;
+    if (rr_filter_resample_device(ctx, d_recs, n, d_table, n, &fcfg, d_cum, d_ancestors, d_summary, stream)) return false;
+    if (rr_filter_move_device(ctx, d_states_in, n, resample ? d_ancestors : nullptr, n, increment[0], increment[1], increment[2], increment[3], &fcfg,
+                              d_states_out, stream))
+        return false;
+    if (rr_copy_to_host_async(ctx, d_summary, &summary, sizeof(summary), stream)) return false;
+    return rr_synchronize(ctx, stream) == 0;
+}
+
 }  // namespace radarays_ros_amd::marshal

@@ -1,5 +1,5 @@
 // rr_images.hip -- the C ABI's image entry points: images in, records / points / images out.  PSNR scores and metrics against a reference image
-// (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), place recognition (rr_place.hip), point clouds and Cartesian images (rr_detect.hip), sweep compensation (rr_deskew.hip), scan matching (rr_icp.hip), the likelihood field (rr_field.hip), occupancy mapping (rr_occupancy.hip), object annotations (rr_notes.hip): each in a device form, which runs on the
+// (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), place recognition (rr_place.hip), point clouds and Cartesian images (rr_detect.hip), sweep compensation (rr_deskew.hip), scan matching (rr_icp.hip), the likelihood field (rr_field.hip), occupancy mapping (rr_occupancy.hip), the particle filter step (rr_filter.hip), object annotations (rr_notes.hip): each in a device form, which runs on the
 // caller's buffers and stream, and a host form, which drains c->stream and makes its round trip through a Stage over the context's pool (rr_stage.h).
 #include "rr_stage.h"
 #include <algorithm>
@@ -229,6 +229,49 @@ int check_occupancy_map(rr_ctx* c, const char* who, const void* evidence, const 
     if (!(evidence && occ)) return fail(c, -3, w + ": null buffer");
     if ((uintptr_t)evidence % 4 != 0) return fail(c, -3, w + ": the evidence must be 4-byte aligned");
     return check_grid_shape(c, w, g);
+}
+
+// the refusals the particle filter calls share: a config within its stated ranges, particle and draw counts in 1..2^22
+int check_filter_config(rr_ctx* c, const std::string& w, const rr_filter_config* f, int n, int n_out)
+{
+    if (!f) return fail(c, -3, w + ": null config");
+    if (n < 1 || n > (1 << 22) || n_out < 1 || n_out > (1 << 22)) return fail(c, -3, w + ": n and n_out must be 1..2^22");
+    if (f->quantum < 1 || f->quantum > (1u << 31)) return fail(c, -3, w + ": quantum must be 1..2^31");
+    if (f->n_table < 1 || f->n_table > 4096) return fail(c, -3, w + ": n_table must be 1..4096");
+    if (f->phase >= (1u << 24)) return fail(c, -3, w + ": phase must be 0..2^24 - 1");
+    if (!(std::isfinite(f->sigma_xy) && f->sigma_xy >= 0.0f && std::isfinite(f->sigma_t) && f->sigma_t >= 0.0f))
+        return fail(c, -3, w + ": sigma_xy and sigma_t must be finite and >= 0");
+    if (f->reserved != 0) return fail(c, -3, w + ": reserved must be 0");
+    return 0;
+}
+
+// the refusals of rr_filter_resample_device / rr_filter_resample: no config of the radar is needed
+int check_filter_resample(rr_ctx* c, const char* who, const void* recs, int n, const void* table, int n_out, const rr_filter_config* f, const void* cum,
+                          const void* ancestors, const void* summary)
+{
+    if (!c) return -1;
+    const std::string w(who);
+    if (!(recs && table && cum && ancestors && summary)) return fail(c, -3, w + ": null buffer");
+    int rc = check_filter_config(c, w, f, n, n_out); if (rc) return rc;
+    if ((uintptr_t)recs % 8 != 0 || (uintptr_t)cum % 8 != 0 || (uintptr_t)summary % 8 != 0 || (uintptr_t)ancestors % 4 != 0 || (uintptr_t)table % 2 != 0)
+        return fail(c, -3, w + ": d_recs, d_cum and d_summary must be 8-byte, d_ancestors 4-byte and d_table 2-byte aligned");
+    return 0;
+}
+
+// the refusals of rr_filter_move_device / rr_filter_move
+int check_filter_move(rr_ctx* c, const char* who, const float* in, int n, const void* ancestors, int n_out, float Dc, float Ds, float dx, float dy,
+                      const rr_filter_config* f, const float* out, size_t align /*of the states: 16 on the device, 4 on the host*/)
+{
+    if (!c) return -1;
+    const std::string w(who);
+    if (!(in && out)) return fail(c, -3, w + ": null buffer");
+    int rc = check_filter_config(c, w, f, n, n_out); if (rc) return rc;
+    if (!ancestors && n_out > n) return fail(c, -3, w + ": n_out must not exceed n without ancestors");
+    if (!(std::isfinite(Dc) && std::isfinite(Ds) && std::isfinite(dx) && std::isfinite(dy))) return fail(c, -3, w + ": the increment must be finite");
+    if ((uintptr_t)in % align != 0 || (uintptr_t)out % align != 0 || (uintptr_t)ancestors % 4 != 0)
+        return fail(c, -3, w + ": the states must be " + std::to_string(align) + "-byte and the ancestors 4-byte aligned");
+    if (in < out + 4 * (size_t)n_out && out < in + 4 * (size_t)n) return fail(c, -3, w + ": states_out must not overlap states_in");
+    return 0;
 }
 
 // the refusals the annotation calls share: a config (the plane shape) within the limits of the label planes and of the packed azimuth
@@ -1071,6 +1114,59 @@ int rr_occupancy_map(rr_ctx* c, const int32_t* evidence_i32, const rr_field_conf
     RR_HIP(c, st.up(evidence_i32, cells, d_ev));
     RR_HIP(c, st.hold(occ_u8, cells, d_occ));
     rc = rr_occupancy_map_device(c, d_ev, cfg, d_occ, c->stream); if (rc) return rc;
+    return st.commit();
+}
+
+// ---- particle filter step (rr_filter.hip) -----------------------------------------------------------------------------------
+void rr_filter_tile_sizes(int* scan_tile, int* draws_per_group, int* search_tile) { filter_tile_sizes(scan_tile, draws_per_group, search_tile); }
+
+int rr_filter_resample_device(rr_ctx* c, const rr_field_rec* d_recs, int n, const uint16_t* d_table, int n_out, const rr_filter_config* cfg,
+                              uint64_t* d_cum, uint32_t* d_ancestors, rr_filter_summary* d_summary, void* stream)
+{
+    int rc = check_filter_resample(c, "rr_filter_resample_device", d_recs, n, d_table, n_out, cfg, d_cum, d_ancestors, d_summary); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    launch_filter_resample(d_recs, n, d_table, n_out, *cfg, d_cum, d_ancestors, d_summary, stream_of(c, stream));
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_filter_resample(rr_ctx* c, const rr_field_rec* recs, int n, const uint16_t* table, int n_out, const rr_filter_config* cfg, uint64_t* cum,
+                       uint32_t* ancestors, rr_filter_summary* summary)
+{
+    int rc = check_filter_resample(c, "rr_filter_resample", recs, n, table, n_out, cfg, cum, ancestors, summary); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    RR_STAGE(c, st);
+    rr_field_rec* d_recs; uint16_t* d_table; uint64_t* d_cum; uint32_t* d_anc; rr_filter_summary* d_sum;
+    RR_HIP(c, st.up(recs, (size_t)n, d_recs));
+    RR_HIP(c, st.up(table, (size_t)cfg->n_table, d_table));
+    RR_HIP(c, st.hold(cum, (size_t)n, d_cum));
+    RR_HIP(c, st.hold(ancestors, (size_t)n_out, d_anc));
+    RR_HIP(c, st.hold(summary, 1, d_sum));
+    rc = rr_filter_resample_device(c, d_recs, n, d_table, n_out, cfg, d_cum, d_anc, d_sum, c->stream); if (rc) return rc;
+    return st.commit();
+}
+
+int rr_filter_move_device(rr_ctx* c, const float* d_states_in, int n, const uint32_t* d_ancestors, int n_out, float Dc, float Ds, float dx, float dy,
+                          const rr_filter_config* cfg, float* d_states_out, void* stream)
+{
+    int rc = check_filter_move(c, "rr_filter_move_device", d_states_in, n, d_ancestors, n_out, Dc, Ds, dx, dy, cfg, d_states_out, 16); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    launch_filter_move(d_states_in, n, d_ancestors, n_out, Dc, Ds, dx, dy, *cfg, d_states_out, stream_of(c, stream));
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_filter_move(rr_ctx* c, const float* states_in, int n, const uint32_t* ancestors, int n_out, float Dc, float Ds, float dx, float dy,
+                   const rr_filter_config* cfg, float* states_out)
+{
+    int rc = check_filter_move(c, "rr_filter_move", states_in, n, ancestors, n_out, Dc, Ds, dx, dy, cfg, states_out, 4); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    RR_STAGE(c, st);
+    float* d_in; uint32_t* d_anc; float* d_out;
+    RR_HIP(c, st.up(states_in, (size_t)n * 4, d_in));
+    RR_HIP(c, st.up(ancestors, (size_t)n_out, d_anc));
+    RR_HIP(c, st.hold(states_out, (size_t)n_out * 4, d_out));
+    rc = rr_filter_move_device(c, d_in, n, d_anc, n_out, Dc, Ds, dx, dy, cfg, d_out, c->stream); if (rc) return rc;
     return st.commit();
 }
 

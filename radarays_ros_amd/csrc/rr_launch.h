@@ -1,4 +1,4 @@
-// rr_launch.h -- every launcher of rr_kernels.hip, rr_labels.hip, rr_paths.hip, rr_doppler.hip, rr_refit.hip, rr_detect.hip, rr_deskew.hip, rr_icp.hip, rr_field.hip, rr_occupancy.hip, rr_notes.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip, rr_place.hip and rr_lbvh.hip, declared ONCE: included where they
+// rr_launch.h -- every launcher of rr_kernels.hip, rr_labels.hip, rr_paths.hip, rr_doppler.hip, rr_refit.hip, rr_detect.hip, rr_deskew.hip, rr_icp.hip, rr_field.hip, rr_occupancy.hip, rr_filter.hip, rr_notes.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip, rr_place.hip and rr_lbvh.hip, declared ONCE: included where they
 // are defined (a definition that drifts from its declaration fails there) and where they are called.  Default arguments live here only.
 #pragma once
 #include "../../include/radarays_mi355.h"
@@ -94,6 +94,13 @@ void launch_occupancy_update(const rr_radar_point* points, const uint32_t* offse
                              const rr_field_config& g, const rr_occupancy_config& o, const PolarGrid& G, float* profile, int32_t* evidence,
                              hipStream_t s);
 void launch_occupancy_map(const int32_t* evidence, const rr_field_config& g, uint8_t* occ, hipStream_t s);
+// rr_filter.hip (particle filter step).  No scratch: cum [n] is the scan's only room and an output; recs, cum and summary 8-byte aligned, the states
+// 16-byte aligned and apart.  Six launches (start values, minimum, tile sums, their scan by one workgroup, cum, draws) and one
+void filter_tile_sizes(int* scan_tile, int* draws_per_group, int* search_tile);
+void launch_filter_resample(const rr_field_rec* recs, int n, const uint16_t* table, int n_out, const rr_filter_config& f, uint64_t* cum,
+                            uint32_t* ancestors, rr_filter_summary* summary, hipStream_t s);
+void launch_filter_move(const float* states_in, int n, const uint32_t* ancestors, int n_out, float Dc, float Ds, float dx, float dy,
+                        const rr_filter_config& f, float* states_out, hipStream_t s);
 // rr_notes.hip (object annotations).  scratch: note_scratch_bytes, 16-byte aligned like notes; every word of it, of notes and of skipped is written by the launches
 size_t note_scratch_bytes(size_t n_frames, size_t n_objects, int n_angles);
 void launch_notes(const uint32_t* labels, const uint8_t* imgs, int n_frames, uint32_t n_objects, uint32_t extent_mask, const PolarGrid& G,

@@ -253,6 +253,77 @@ def occupancy_tile_sizes():
     return a.value, b.value, c.value
 
 
+# ---- particle filter step (rr_filter.hip).  rr_filter_config (32 B) and rr_filter_summary (32 B) as numpy sees them
+FILTER_CONFIG_DTYPE = np.dtype([("quantum", "<u4"), ("n_table", "<u4"), ("phase", "<u4"), ("seed", "<u4"), ("step", "<u4"), ("sigma_xy", "<f4"),
+                                ("sigma_t", "<f4"), ("reserved", "<u4")])
+FILTER_SUMMARY_DTYPE = np.dtype([("min_sum_d2", "<u8"), ("total_weight", "<u8"), ("sum_w2", "<u8"), ("best", "<u4"), ("n_unique", "<u4")])
+FILTER_MAX_QUANTUM, FILTER_MAX_TABLE, FILTER_MAX_PHASE, FILTER_MAX_N = 1 << 31, 4096, (1 << 24) - 1, 1 << 22
+FILTER_VARIATE_STD = float(np.sqrt((65536.0 ** 2 - 1.0) / 3.0))    # of the integer variate: a centred sum of four 16-bit uniforms
+RRFilterConfig = np.ctypeslib.as_ctypes_type(FILTER_CONFIG_DTYPE)
+RRFilterSummary = np.ctypeslib.as_ctypes_type(FILTER_SUMMARY_DTYPE)
+
+
+def _f32_scale(v, what):
+    g = _f32_finite(v, what)
+    if g < 0:
+        raise ValueError("%s must be >= 0, got %r" % (what, v))
+    return g
+
+
+def filter_config(sigma_xy_m=0.0, sigma_yaw_rad=0.0, quantum=1, n_table=1, phase=0, seed=0, step=0):
+    """rr_filter_config, range-checked before any call into the library.  sigma_xy_m (metres) and sigma_yaw_rad (radians, below pi) are the
+    standard deviations of the diffusion; they become per-unit scales of the integer variate here, on the host: divided by
+    sqrt((65536^2 - 1) / 3), the angle as tan(yaw / 2).  quantum (1..2^31) sum_d2 units per step of the weight table of n_table
+    (1..4096) entries; phase (0..2^24 - 1) where the comb of draws starts; seed and step enter the hash.  An RRFilterConfig is re-checked
+    with _filter_cfg."""
+    sx, sy = _f32_scale(sigma_xy_m, "sigma_xy_m"), _f32_scale(sigma_yaw_rad, "sigma_yaw_rad")
+    if not sy < np.pi:
+        raise ValueError("sigma_yaw_rad must be below pi, got %r" % (sigma_yaw_rad,))
+    return RRFilterConfig(_int_in(quantum, 1, FILTER_MAX_QUANTUM, "quantum"), _int_in(n_table, 1, FILTER_MAX_TABLE, "n_table"),
+                          _int_in(phase, 0, FILTER_MAX_PHASE, "phase"), _int_in(seed, 0, 0xFFFFFFFF, "seed"), _int_in(step, 0, 0xFFFFFFFF, "step"),
+                          _f32_scale(sx / FILTER_VARIATE_STD, "sigma_xy"), _f32_scale(np.tan(0.5 * sy) / FILTER_VARIATE_STD, "sigma_t"), 0)
+
+
+def _filter_cfg(cfg):
+    """an RRFilterConfig (filter_config makes one; its fields are held to their ranges again) or a dict of filter_config's arguments"""
+    if isinstance(cfg, RRFilterConfig):
+        if cfg.reserved != 0:
+            raise ValueError("reserved must be 0, got %r" % (cfg.reserved,))
+        return RRFilterConfig(_int_in(cfg.quantum, 1, FILTER_MAX_QUANTUM, "quantum"), _int_in(cfg.n_table, 1, FILTER_MAX_TABLE, "n_table"),
+                              _int_in(cfg.phase, 0, FILTER_MAX_PHASE, "phase"), cfg.seed, cfg.step, _f32_scale(cfg.sigma_xy, "sigma_xy"),
+                              _f32_scale(cfg.sigma_t, "sigma_t"), 0)
+    if isinstance(cfg, dict):
+        return filter_config(**cfg)
+    raise ValueError("a filter config must be an RRFilterConfig (native.filter_config makes one) or a dict of its arguments, got %r" % (cfg,))
+
+
+def filter_weight_table(sigma_cells, quantum, n_table):
+    """the uint16 weight table of rr_filter_resample: table[k] = round(65535 * exp(-k * quantum / (2 sigma^2))) with sigma in cells (sum_d2
+    is in squared cells), table[0] at least 1 -- the likelihood of a particle k quanta worse than the best"""
+    sg = _f32_finite(sigma_cells, "sigma_cells", True)
+    q, nt = _int_in(quantum, 1, FILTER_MAX_QUANTUM, "quantum"), _int_in(n_table, 1, FILTER_MAX_TABLE, "n_table")
+    t = np.rint(65535.0 * np.exp(-np.arange(nt, dtype=np.float64) * q / (2.0 * sg * sg))).astype(np.uint16)
+    t[0] = max(int(t[0]), 1)
+    return t
+
+
+def filter_tile_sizes():
+    """(records per scan tile, draws per workgroup of the draw kernel, entries of cum staged per workgroup -- 0: searched in global memory)"""
+    a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+    lib().rr_filter_tile_sizes(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
+def _increment(increment):
+    """the odometry increment (Dc, Ds, dx, dy) of rr_filter_move -> four finite float32 values as Python floats; None: the identity"""
+    if increment is None:
+        return 1.0, 0.0, 0.0, 0.0
+    v = np.asarray(increment)
+    if v.dtype.kind not in "fiu" or v.shape != (4,):
+        raise ValueError("the increment must be four real numbers (Dc, Ds, dx, dy), got %r" % (increment,))
+    return tuple(_f32_finite(x, "the increment") for x in v.tolist())
+
+
 def _lattice_axis(half, step, what):
     half, step = float(half), float(step)
     if not (np.isfinite(half) and half >= 0 and np.isfinite(step) and step > 0):
@@ -399,7 +470,8 @@ STRUCTS = {
     "rr_cartesian_config": (RRCartesianConfig, None), "rr_object_note": (RRObjectNote, NOTE_DTYPE), "rr_shift_record": (RRShiftRecord, SHIFT_DTYPE),
     "rr_place_config": (RRPlaceConfig, None), "rr_place_match": (RRPlaceMatch, PLACE_DTYPE), "rr_sweep_rec": (RRSweepRec, SWEEP_DTYPE),
     "rr_icp_rec": (RRIcpRec, ICP_DTYPE), "rr_field_config": (RRFieldConfig, None), "rr_field_rec": (RRFieldRec, FIELD_DTYPE),
-    "rr_occupancy_config": (RROccupancyConfig, None), "rr_mesh": (RRMesh, None),
+    "rr_occupancy_config": (RROccupancyConfig, None), "rr_filter_config": (RRFilterConfig, FILTER_CONFIG_DTYPE),
+    "rr_filter_summary": (RRFilterSummary, FILTER_SUMMARY_DTYPE), "rr_mesh": (RRMesh, None),
 }
 
 
@@ -533,6 +605,12 @@ def _prototypes():
         "rr_occupancy_map_device": (i, [vp, vp, P(RRFieldConfig), vp, vp]),
         "rr_occupancy_map": (i, [vp, vp, P(RRFieldConfig), vp]),
         "rr_occupancy_tile_sizes": (None, [P(i), P(i), P(i)]),
+        # ---- particle filter step (rr_filter.hip)
+        "rr_filter_resample_device": (i, [vp, vp, i, vp, i, P(RRFilterConfig), vp, vp, vp, vp]),
+        "rr_filter_resample": (i, [vp, vp, i, vp, i, P(RRFilterConfig), vp, vp, vp]),
+        "rr_filter_move_device": (i, [vp, vp, i, vp, i, f, f, f, f, P(RRFilterConfig), vp, vp]),
+        "rr_filter_move": (i, [vp, vp, i, vp, i, f, f, f, f, P(RRFilterConfig), vp]),
+        "rr_filter_tile_sizes": (None, [P(i), P(i), P(i)]),
         # ---- several GPUs of one node behind one object (rr_multi.hip)
         "rr_create_multi": (vp, [P(i), i]),
         "rr_destroy_multi": (None, [vp]),
@@ -1654,6 +1732,65 @@ class Context(_Scene):
         ev = self._field_grid(evidence, g, np.int32, "evidence")
         out = np.zeros((g.height, g.width), np.uint8)
         self._ck(self._L.rr_occupancy_map(self._h, ev.ctypes.data, C.byref(g), out.ctypes.data))
+        return out
+
+    # ---- particle filter step (rr_filter.hip): records -> weights -> systematic resampling -> odometry plus diffusion
+    def filter_resample_device(self, d_recs_ptr, n, d_table_ptr, n_out, filter_cfg, d_cum_ptr, d_ancestors_ptr, d_summary_ptr, stream=None):
+        """rr_filter_resample_device: the FIELD_DTYPE records [n] score_poses_device wrote and the uint16 weight table [n_table] at
+        d_table_ptr -> the inclusive sums uint64 [n] at d_cum_ptr, the ancestors uint32 [n_out] and one FILTER_SUMMARY_DTYPE record; on
+        `stream`"""
+        f = _filter_cfg(filter_cfg)
+        n, m = _int_in(n, 1, FILTER_MAX_N, "n"), _int_in(n_out, 1, FILTER_MAX_N, "n_out")
+        if not d_recs_ptr or not d_table_ptr or not d_cum_ptr or not d_ancestors_ptr or not d_summary_ptr:
+            raise ValueError("filter_resample_device needs record, table, cum, ancestor and summary buffers")
+        self._ck(self._L.rr_filter_resample_device(self._h, d_recs_ptr, n, d_table_ptr, m, C.byref(f), d_cum_ptr, d_ancestors_ptr, d_summary_ptr,
+                                                   stream))
+
+    def filter_resample(self, recs, table, n_out, filter_cfg):
+        """rr_filter_resample: FIELD_DTYPE records [n] (score_poses returns them) and the uint16 table of filter_weight_table ->
+        (cum uint64 [n], ancestors uint32 [n_out], the FILTER_SUMMARY_DTYPE record)"""
+        f = _filter_cfg(filter_cfg)
+        r, t = np.asarray(recs), np.asarray(table)
+        if r.dtype != FIELD_DTYPE or r.ndim != 1 or not 1 <= len(r) <= FILTER_MAX_N:
+            raise ValueError("recs must be a one-dimensional FIELD_DTYPE array of 1..%d records" % FILTER_MAX_N)
+        if t.dtype != np.uint16 or t.shape != (f.n_table,):
+            raise ValueError("the table must be uint16 [n_table = %d], got %s %s" % (f.n_table, t.dtype, t.shape))
+        m = _int_in(n_out, 1, FILTER_MAX_N, "n_out")
+        r, t = np.ascontiguousarray(r), np.ascontiguousarray(t)
+        cum, anc, summary = np.zeros(len(r), np.uint64), np.zeros(m, np.uint32), np.zeros(1, FILTER_SUMMARY_DTYPE)
+        self._ck(self._L.rr_filter_resample(self._h, r.ctypes.data, len(r), t.ctypes.data, m, C.byref(f), cum.ctypes.data, anc.ctypes.data,
+                                            summary.ctypes.data))
+        return cum, anc, summary[0]
+
+    def filter_move_device(self, d_states_in_ptr, n, d_ancestors_ptr, n_out, increment, filter_cfg, d_states_out_ptr, stream=None):
+        """rr_filter_move_device: float32 states [n][4] = (c, s, tx, ty) in HBM, gathered through the uint32 ancestors [n_out] (None: draw j
+        takes state j), moved by the increment (Dc, Ds, dx, dy) in the sensor frame (None: the identity) plus the config's diffusion,
+        into the float32 [n_out][4] at d_states_out_ptr, which must not overlap the input; on `stream`"""
+        f, inc = _filter_cfg(filter_cfg), _increment(increment)
+        n, m = _int_in(n, 1, FILTER_MAX_N, "n"), _int_in(n_out, 1, FILTER_MAX_N, "n_out")
+        if not d_states_in_ptr or not d_states_out_ptr:
+            raise ValueError("filter_move_device needs both state buffers")
+        if not d_ancestors_ptr and m > n:
+            raise ValueError("n_out (%d) must not exceed n (%d) without ancestors" % (m, n))
+        self._ck(self._L.rr_filter_move_device(self._h, d_states_in_ptr, n, d_ancestors_ptr, m, *inc, C.byref(f), d_states_out_ptr, stream))
+
+    def filter_move(self, states, ancestors, increment, filter_cfg):
+        """rr_filter_move: float32 states [n][4], uint32 ancestors [n_out] or None (every state once), the increment (Dc, Ds, dx, dy) or None
+        -> the moved states float32 [n_out][4]"""
+        f, inc = _filter_cfg(filter_cfg), _increment(increment)
+        st = np.asarray(states)
+        if st.dtype.kind not in "fiu" or st.ndim != 2 or st.shape[1] != 4 or not 1 <= len(st) <= FILTER_MAX_N:
+            raise ValueError("states must be real numbers of shape [n][4] (c, s, tx, ty), n in 1..%d, got %s %s" % (FILTER_MAX_N, st.dtype, st.shape))
+        st = np.ascontiguousarray(st, np.float32)
+        anc = None
+        if ancestors is not None:
+            anc = np.asarray(ancestors)
+            if anc.dtype.kind not in "iu" or anc.ndim != 1 or not 1 <= len(anc) <= FILTER_MAX_N or anc.min() < 0 or anc.max() >= len(st):
+                raise ValueError("ancestors must be integers in [0, %d) of shape [n_out], n_out in 1..%d" % (len(st), FILTER_MAX_N))
+            anc = np.ascontiguousarray(anc, np.uint32)
+        m = len(st) if anc is None else len(anc)
+        out = np.zeros((m, 4), np.float32)
+        self._ck(self._L.rr_filter_move(self._h, st.ctypes.data, len(st), _ptr(anc), m, *inc, C.byref(f), out.ctypes.data))
         return out
 
     # ---- object annotations (rr_notes.hip): one record per object from label images; any context with a config, mesh or not

@@ -516,6 +516,71 @@ class RadarHIP:
         ev = self._ctx.occupancy_update(pts, offs, g, o, states, evidence)
         return ev, self._ctx.occupancy_map(ev, g)
 
+    # ---- particle filter step (rr_filter.hip): score, resample and move one particle set that stays in HBM
+    @staticmethod
+    def effectiveSampleSize(summary):
+        """total_weight^2 / sum_w2 of a FILTER_SUMMARY_DTYPE record: how many particles carry the weight (0.0 when every weight is 0)"""
+        w, w2 = int(summary["total_weight"]), int(summary["sum_w2"])
+        return w * w / w2 if w2 else 0.0
+
+    def filterStep(self, scan, particles, field, field_cfg, table, filter_cfg, increment=None, n_eff_floor=None, prev_summary=None):
+        """One step of a particle filter on one stream, nothing but the 32-byte summary leaving HBM: rr_score_poses_device scores the
+        particles against the field, rr_filter_resample_device turns the records into weights through `table`
+        (native.filter_weight_table) and draws the ancestors systematically, rr_filter_move_device moves the survivors by the odometry
+        `increment` (Dc, Ds, dx, dy) in the sensor frame (None: none) plus the diffusion of filter_cfg (native.filter_config; give every
+        step its own `step`, and a `phase` of the caller's choice).
+        scan: a POINT_DTYPE cloud; particles: float32 [n][4] = (c, s, tx, ty), each the scan's sensor frame into the map frame, a torch
+        tensor on this context's device (it is not modified) or anything numpy takes; field: the uint16 field of buildLikelihoodField,
+        numpy or a torch int16 tensor on the device; table: uint16 [n_table], numpy or a torch int16 tensor on the device.
+        Returns (the moved particles, a float32 [n][4] tensor on the device, the FILTER_SUMMARY_DTYPE record of the weights that were
+        drawn from).  n_eff_floor: the caller's resampling rule, decided on the host from prev_summary, the summary the PREVIOUS step
+        returned -- if its effective sample size is at least n_eff_floor, this step keeps every particle (the move runs without
+        ancestors); the device never branches on it, and the summary is computed either way."""
+        import torch
+        self._push()
+        g, f = native._field_cfg(field_cfg), native._filter_cfg(filter_cfg)
+        inc = native._increment(increment)
+        dev = torch.device("cuda", self._ctx.device)
+        pts = np.ascontiguousarray(scan)
+        if pts.dtype != native.POINT_DTYPE or pts.ndim != 1 or not 1 <= len(pts) <= native.ICP_MAX_POINTS:
+            raise ValueError("the scan must be a one-dimensional POINT_DTYPE array of 1..%d points" % native.ICP_MAX_POINTS)
+        keep_all = n_eff_floor is not None and prev_summary is not None and self.effectiveSampleSize(prev_summary) >= float(n_eff_floor)
+
+        def on_device(x, dtype, shape, what):
+            """a tensor, or an array numpy takes, -> a contiguous tensor on the device; torch has no uint16, so 16-bit words travel as int16"""
+            if not isinstance(x, torch.Tensor):
+                a = np.ascontiguousarray(x)
+                a = a.view(np.int16) if a.dtype == np.uint16 else np.ascontiguousarray(a, dtype)
+                x = torch.from_numpy(a.copy())
+            if tuple(x.shape) != shape or x.element_size() != np.dtype(dtype).itemsize or x.is_floating_point() != (np.dtype(dtype).kind == "f"):
+                raise ValueError("%s must have shape %s and %s elements, got %s %s" % (what, shape, np.dtype(dtype), tuple(x.shape), x.dtype))
+            return x.to(dev).contiguous()
+
+        n = len(particles)
+        if not 1 <= n <= native.FILTER_MAX_N:
+            raise ValueError("1..%d particles, got %d" % (native.FILTER_MAX_N, n))
+        stream = torch.cuda.Stream(device=dev)
+        s = stream.cuda_stream
+        torch.cuda.current_stream(dev).synchronize()      # the caller's tensors were made on its own stream
+        with torch.cuda.device(dev), torch.cuda.stream(stream):
+            st = on_device(particles, np.float32, (n, 4), "particles")
+            d_field = on_device(field, np.int16, (g.height, g.width), "field")
+            d_table = on_device(table, np.int16, (f.n_table,), "table")
+            d_pts = torch.from_numpy(pts.view(np.uint8).copy()).to(dev)
+            d_count = torch.tensor([len(pts)], dtype=torch.int32, device=dev)
+            recs = torch.empty((n, 2), dtype=torch.int64, device=dev)
+            cum = torch.empty(n, dtype=torch.int64, device=dev)
+            anc = torch.empty(n, dtype=torch.int32, device=dev)
+            summary = torch.empty(4, dtype=torch.int64, device=dev)
+            out = torch.empty((n, 4), dtype=torch.float32, device=dev)
+            self._ctx.score_poses_device(d_pts.data_ptr(), d_count.data_ptr(), len(pts), st.data_ptr(), n, d_field.data_ptr(), g, recs.data_ptr(), s)
+            self._ctx.filter_resample_device(recs.data_ptr(), n, d_table.data_ptr(), n, f, cum.data_ptr(), anc.data_ptr(), summary.data_ptr(), s)
+            self._ctx.filter_move_device(st.data_ptr(), n, None if keep_all else anc.data_ptr(), n, inc, f, out.data_ptr(), s)
+            home = summary.cpu().numpy().view(native.FILTER_SUMMARY_DTYPE)[0].copy()
+        self._ctx.synchronize(s)
+        self.m_filter = dict(recs=recs, cum=cum, ancestors=anc)      # the step's intermediates, on the device, for who wants to look
+        return out, home
+
     # ---- place recognition (rr_place.hip): a database of yaw-invariant ring/sector descriptors, and a scan looked up in it
     def buildPlaceDatabase(self, poses, place_cfg, on_device=False):
         """any number of [n][7] poses, worked through 64 at a time -> their descriptors uint8 [n][R][S] (native.Context._place_cfg
