@@ -1321,6 +1321,58 @@ int rr_filter_move(rr_ctx* ctx, const float* states_in, int n, const uint32_t* a
  * its draws -- 0: the draws search cum in global memory (tests put n at the edges) */
 void rr_filter_tile_sizes(int* scan_tile, int* draws_per_group, int* search_tile);
 
+/* ---- map refinement: nearest-cell transform and batched scan-to-map ICP (rr_refine.hip) -----------------------------------
+ * What comes behind a lattice node or a particle: ONE observed scan is refined against the grid map from very many starting states at
+ * once.  The map's nearest-cell (feature) transform is taken once; a hypothesis then costs one table look-up per point and iteration, and
+ * all iterations run inside one launch.  The reference has no such step: parity is UNPINNED and everything below is the build's own
+ * definition (a numpy restatement in tests/refine_ref.py checks the kernels byte for byte).  All f32 arithmetic is un-fused; every result is
+ * an integer or a correctly rounded f64 expression without trigonometry.
+ * Grid, IN GRID rule, cell index and pose convention are rr_field_config's and the likelihood field's (above), unchanged.
+ * NONE = 0xFFFFFFFF, cap2 = max_dist^2.
+ * 1. rr_nearest_field[_device]: (ctx, occ_u8, threshold 1..255, cfg, nearest_u32 [height][width], stream).
+ *    A cell is occupied iff occ >= threshold, as in rr_distance_field.
+ *    For cell (ix, iy), take over all occupied cells (jx, jy) the minimum of the 64-bit key (d2 << 32) | (jy * width + jx), with
+ *    d2 = (ix-jx)^2 + (iy-jy)^2.  Ties in distance therefore go to the lowest linear index.
+ *    nearest[iy][ix] is that linear index if the minimal d2 < cap2, else NONE.
+ *    From this definition nearest != NONE exactly where rr_distance_field gives a value below cap2, and there d2(cell, nearest) equals
+ *    that value.  nearest must not alias occ.
+ * 2. rr_refine_poses[_device]: (ctx, points, d_count, max_points 0..65536, init f64 [n_hyp][4], n_hyp 1..2^22, nearest_u32, cfg,
+ *    iterations 0..64, rr_icp_rec recs [n_hyp], stream).
+ *    ONE scan is shared by all hypotheses.  Its count is read on the device and cut at max_points, which is flagged RR_ICP_TRUNCATED.
+ *    Initial states are normalised exactly as rr_register_points does.  A state with no direction becomes the identity plus
+ *    RR_ICP_DEGENERATE (in the host form too: nothing is refused for it).
+ *    One pass at a state:
+ *      Transform.   Round the state to f32.  px = (cf*x - sf*y) + txf, py = (sf*x + cf*y) + tyf, un-fused.
+ *      Cell.        The IN GRID rule gives (ix, iy).
+ *      Look-up.     k = nearest[iy*width+ix], jx = k % width, jy = k / width.
+ *      Match test.  The point is MATCHED iff it is IN GRID, k != NONE and (ix-jx)^2 + (iy-jy)^2 <= cfg.gate^2.
+ *      Quantise.    P = (int32)rintf(p * 256.0f) per coordinate.
+ *      Target.      Q is the same quantisation of the nearest cell's centre: qx = x0 + ((float)jx + 0.5f) * cell, qy likewise.  This
+ *                   is the occupancy grid's cell-centre expression.
+ *    The eight int64 sums and the SOLVE are the scan matcher's, letter for letter: N, SPx, SPy, SQx, SQy, Sdot, Scross, Ssse; A, B, h; the
+ *    degenerate rule; composition; renormalisation.
+ *    The call runs `iterations` times (pass, solve).  Then one last pass writes sse and n_matched into the 48-byte rr_icp_rec.  The record
+ *    type is reused.  iterations = 0 scores the states as they stand.  A state that holds a NaN in its translation leaves every point not
+ *    IN GRID: N = 0, and every solve sets RR_ICP_DEGENERATE and keeps the state.
+ *    To keep the scan matcher's overflow bound (|P|, |Q| <= 2^21), the call refuses with -3 a grid any of whose four extents is at or
+ *    beyond 8192 m in magnitude.  The extents are x0, y0, x0 + width*cell and y0 + height*cell, taken in f64 from the f32 fields.
+ * Other refusals follow the scan matcher and the likelihood field: null ctx -1; null buffers, ranges and alignment (8 bytes for init and
+ * recs, 4 for nearest) -3.
+ * The device forms enqueue on `stream` (NULL: the context's) with no host round trip: rr_nearest_field_device two launches (columns, rows),
+ * rr_refine_poses_device ONE, whatever the iteration count.  They use NO context memory at all, so they run on any stream beside batches in
+ * flight.  The host forms stage through context-owned buffers and are synchronous, with the count passed as a value. */
+int rr_nearest_field_device(rr_ctx* ctx, const uint8_t* d_occ_u8, int threshold /*1..255*/, const rr_field_config* cfg,
+                            uint32_t* d_nearest_u32 /*[height][width]*/, void* stream);
+int rr_nearest_field(rr_ctx* ctx, const uint8_t* occ_u8, int threshold, const rr_field_config* cfg, uint32_t* nearest_u32);   /* host buffers */
+int rr_refine_poses_device(rr_ctx* ctx, const rr_radar_point* d_points, const uint32_t* d_count, int max_points,
+                           const double* d_init /*[n_hyp][4]: c, s, tx, ty*/, int n_hyp /*1..2^22*/, const uint32_t* d_nearest_u32,
+                           const rr_field_config* cfg, int iterations /*0..64*/, rr_icp_rec* d_recs /*[n_hyp]*/, void* stream);
+int rr_refine_poses(rr_ctx* ctx, const rr_radar_point* points, uint32_t count, int max_points, const double* init, int n_hyp,
+                    const uint32_t* nearest_u32, const rr_field_config* cfg, int iterations, rr_icp_rec* recs);   /* host buffers, synchronous */
+/* the blocking of the kernels: points a wave of k_refine takes per step, hypotheses per workgroup of it, cells of a row per sweep of the
+ * transform's row pass (tests put counts and sizes at their edges) */
+void rr_refine_tile_sizes(int* points_tile, int* hyps_per_group, int* row_tile);
+
 /* ---- several GPUs of one node behind one object (SURVEY.md §8b "Threading", §8e) -------------------------
  * The reference creates ONE backend object per process (src/radar_simulator.cpp:145-176) and fans out inside it
  * (OpenMP over azimuths, RadarCPU.cpp:155).  rr_multi is that object for n GPUs: one rr_ctx per device, mesh and

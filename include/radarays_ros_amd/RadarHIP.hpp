@@ -570,6 +570,34 @@ public:
         }
         return field;
     }
+    // Map refinement (rr_refine.hip; include/radarays_mi355.h): the nearest-cell table [height][width] of an occupancy map -- a grid of
+    // rr_rasterize_points at threshold 1, a map of buildOccupancyMap at 129 --: per cell the linear index jy * width + jx of the nearest
+    // occupied cell, 0xFFFFFFFF where none lies within cfg.max_dist.  Empty on error
+    std::vector<uint32_t> buildNearestField(const std::vector<uint8_t>& occ, const rr_field_config& cfg, int threshold = 1)
+    {
+        std::vector<uint32_t> nearest;
+        if (!push()) return nearest;
+        if (!marshal::build_nearest(m_ctx, occ, threshold, cfg, nearest)) {
+            if (cfg.width < 1 || cfg.height < 1 || occ.size() != (size_t)cfg.width * (size_t)cfg.height) m_err = "buildNearestField: the map must be [height][width]";
+            else fail();
+            nearest.clear();
+        }
+        return nearest;
+    }
+    // ... and ONE scan refined against that table from n_hyp starting states, every buffer in HBM and the caller's: d_init [n_hyp][4] f64 =
+    // c s tx ty (a state maps the scan's sensor frame into the map frame), d_recs [n_hyp].  One launch on `stream` runs every iteration;
+    // the call returns once it is enqueued, and a record's first 32 bytes are a state that rr_rasterize_points and rr_occupancy_update take
+    // as they are.  false on error
+    bool refinePoses(const rr_radar_point* d_scan, const uint32_t* d_count, int max_points, const double* d_init, int n_hyp, const uint32_t* d_nearest,
+                     const rr_field_config& cfg, rr_icp_rec* d_recs, int iterations = 10, void* stream = nullptr)
+    {
+        if (!push()) return false;
+        if (!marshal::refine_poses(m_ctx, d_scan, d_count, max_points, d_init, n_hyp, d_nearest, cfg, iterations, d_recs, stream)) {
+            fail();
+            return false;
+        }
+        return true;
+    }
     // one observed scan against hypothesis states [n][4] f32 (each the scan's sensor frame into the map frame) and a field of
     // buildLikelihoodField: one rr_field_rec per hypothesis, lower sum_d2 is better.  Empty on error
     std::vector<rr_field_rec> scorePoses(const std::vector<rr_radar_point>& scan, const std::vector<float>& states, const std::vector<uint16_t>& field,

@@ -259,6 +259,25 @@ inline bool score_poses(rr_ctx* ctx, const std::vector<rr_radar_point>& scan, co
                           out.data()) == 0;
 }
 
+// map refinement: the nearest-cell table [height][width] of an occupancy map (occupied: >= threshold; rr_nearest_field), 0xFFFFFFFF where no
+// occupied cell lies within cfg.max_dist.  false: rr_last_error(ctx), or a map that is not [height][width]
+inline bool build_nearest(rr_ctx* ctx, const std::vector<uint8_t>& occ, int threshold, const rr_field_config& cfg, std::vector<uint32_t>& nearest)
+{
+    const size_t cells = cfg.width > 0 && cfg.height > 0 ? (size_t)cfg.width * (size_t)cfg.height : 0;
+    nearest.assign(cells, 0xFFFFFFFFu);
+    if (cells == 0 || occ.size() != cells) return false;
+    return rr_nearest_field(ctx, occ.data(), threshold, &cfg, nearest.data()) == 0;
+}
+
+// ... and ONE scan refined against it from n_hyp starting states on `stream`, every buffer the caller's and in HBM: d_init [n_hyp][4] f64
+// (c, s, tx, ty: the scan's sensor frame into the map frame), d_recs [n_hyp] (rr_refine_poses_device: one launch, nothing comes home and
+// nothing is waited for).  false: rr_last_error(ctx)
+inline bool refine_poses(rr_ctx* ctx, const rr_radar_point* d_scan, const uint32_t* d_count, int max_points, const double* d_init, int n_hyp,
+                         const uint32_t* d_nearest, const rr_field_config& cfg, int iterations, rr_icp_rec* d_recs, void* stream)
+{
+    return rr_refine_poses_device(ctx, d_scan, d_count, max_points, d_init, n_hyp, d_nearest, &cfg, iterations, d_recs, stream) == 0;
+}
+
 // occupancy mapping (rr_occupancy_config): n clouds, each sorted by column then bin as rr_detect writes them and under its state (states
 // empty: the identity), fused into the int32 evidence [height][width] -- accumulated into what `evidence` holds if it has the grid's size,
 // else into zeros (rr_occupancy_update) -- and clamped into the byte map (rr_occupancy_map).  The offsets of each cloud are rebuilt from

@@ -1,5 +1,5 @@
 // rr_images.hip -- the C ABI's image entry points: images in, records / points / images out.  PSNR scores and metrics against a reference image
-// (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), place recognition (rr_place.hip), point clouds and Cartesian images (rr_detect.hip), sweep compensation (rr_deskew.hip), scan matching (rr_icp.hip), the likelihood field (rr_field.hip), occupancy mapping (rr_occupancy.hip), the particle filter step (rr_filter.hip), object annotations (rr_notes.hip): each in a device form, which runs on the
+// (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), place recognition (rr_place.hip), point clouds and Cartesian images (rr_detect.hip), sweep compensation (rr_deskew.hip), scan matching (rr_icp.hip), the likelihood field (rr_field.hip), occupancy mapping (rr_occupancy.hip), the particle filter step (rr_filter.hip), map refinement (rr_refine.hip), object annotations (rr_notes.hip): each in a device form, which runs on the
 // caller's buffers and stream, and a host form, which drains c->stream and makes its round trip through a Stage over the context's pool (rr_stage.h).
 #include "rr_stage.h"
 #include <algorithm>
@@ -271,6 +271,39 @@ int check_filter_move(rr_ctx* c, const char* who, const float* in, int n, const 
     if ((uintptr_t)in % align != 0 || (uintptr_t)out % align != 0 || (uintptr_t)ancestors % 4 != 0)
         return fail(c, -3, w + ": the states must be " + std::to_string(align) + "-byte and the ancestors 4-byte aligned");
     if (in < out + 4 * (size_t)n_out && out < in + 4 * (size_t)n) return fail(c, -3, w + ": states_out must not overlap states_in");
+    return 0;
+}
+
+// the refusals of rr_nearest_field_device / rr_nearest_field: no config is needed, the shape comes with the call
+int check_nearest_field(rr_ctx* c, const char* who, const void* occ, int threshold, const rr_field_config* g, const void* nearest)
+{
+    if (!c) return -1;
+    const std::string w(who);
+    if (!(occ && nearest)) return fail(c, -3, w + ": null buffer");
+    if (threshold < 1 || threshold > 255) return fail(c, -3, w + ": threshold must be 1..255");
+    if (occ == nearest) return fail(c, -3, w + ": the nearest-cell table must not alias the occupancy grid");
+    if ((uintptr_t)nearest % 4 != 0) return fail(c, -3, w + ": the nearest-cell table must be 4-byte aligned");
+    return check_field_grid(c, w, g);
+}
+
+// the refusals of rr_refine_poses_device / rr_refine_poses: no config is needed either; the grid must lie within +-8192 m (|P|, |Q| <= 2^21)
+int check_refine_poses(rr_ctx* c, const char* who, const void* points, bool have_count, int max_points, const void* init, int n_hyp,
+                       const void* nearest, const rr_field_config* g, int iterations, const void* recs)
+{
+    if (!c) return -1;
+    const std::string w(who);
+    const bool sizes_ok = max_points >= 0 && max_points <= 65536;
+    if (!(have_count && init && nearest && recs && (!sizes_ok || max_points == 0 || points))) return fail(c, -3, w + ": null buffer");
+    if (!sizes_ok) return fail(c, -3, w + ": max_points must be 0..65536");
+    if (n_hyp < 1 || n_hyp > (1 << 22)) return fail(c, -3, w + ": n_hyp must be 1..2^22");
+    if (iterations < 0 || iterations > 64) return fail(c, -3, w + ": iterations must be 0..64");
+    if ((uintptr_t)init % 8 != 0 || (uintptr_t)recs % 8 != 0 || (uintptr_t)nearest % 4 != 0)
+        return fail(c, -3, w + ": init and recs must be 8-byte and the nearest-cell table 4-byte aligned");
+    int rc = check_field_grid(c, w, g); if (rc) return rc;
+    const double x0 = (double)g->x0, y0 = (double)g->y0, cell = (double)g->cell;
+    const double ext[4] = {x0, y0, x0 + (double)g->width * cell, y0 + (double)g->height * cell};
+    for (double e : ext)
+        if (!(std::fabs(e) < 8192.0)) return fail(c, -3, w + ": the grid must lie within +-8192 m");
     return 0;
 }
 
@@ -1167,6 +1200,60 @@ int rr_filter_move(rr_ctx* c, const float* states_in, int n, const uint32_t* anc
     RR_HIP(c, st.up(ancestors, (size_t)n_out, d_anc));
     RR_HIP(c, st.hold(states_out, (size_t)n_out * 4, d_out));
     rc = rr_filter_move_device(c, d_in, n, d_anc, n_out, Dc, Ds, dx, dy, cfg, d_out, c->stream); if (rc) return rc;
+    return st.commit();
+}
+
+// ---- map refinement (rr_refine.hip) ---------------------------------------------------------------------------------------
+void rr_refine_tile_sizes(int* points_tile, int* hyps_per_group, int* row_tile) { refine_tile_sizes(points_tile, hyps_per_group, row_tile); }
+
+int rr_nearest_field_device(rr_ctx* c, const uint8_t* d_occ_u8, int threshold, const rr_field_config* cfg, uint32_t* d_nearest_u32, void* stream)
+{
+    int rc = check_nearest_field(c, "rr_nearest_field_device", d_occ_u8, threshold, cfg, d_nearest_u32); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    launch_nearest_field(d_occ_u8, threshold, *cfg, d_nearest_u32, stream_of(c, stream));
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_nearest_field(rr_ctx* c, const uint8_t* occ_u8, int threshold, const rr_field_config* cfg, uint32_t* nearest_u32)
+{
+    int rc = check_nearest_field(c, "rr_nearest_field", occ_u8, threshold, cfg, nearest_u32); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t cells = (size_t)cfg->width * cfg->height;
+    RR_STAGE(c, st);
+    uint8_t* d_occ; uint32_t* d_near;
+    RR_HIP(c, st.up(occ_u8, cells, d_occ));
+    RR_HIP(c, st.hold(nearest_u32, cells, d_near));
+    rc = rr_nearest_field_device(c, d_occ, threshold, cfg, d_near, c->stream); if (rc) return rc;
+    return st.commit();
+}
+
+int rr_refine_poses_device(rr_ctx* c, const rr_radar_point* d_points, const uint32_t* d_count, int max_points, const double* d_init, int n_hyp,
+                           const uint32_t* d_nearest_u32, const rr_field_config* cfg, int iterations, rr_icp_rec* d_recs, void* stream)
+{
+    int rc = check_refine_poses(c, "rr_refine_poses_device", d_points, d_count != nullptr, max_points, d_init, n_hyp, d_nearest_u32, cfg, iterations,
+                                d_recs); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    launch_refine(d_points, d_count, max_points, d_init, n_hyp, d_nearest_u32, *cfg, iterations, d_recs, stream_of(c, stream));
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_refine_poses(rr_ctx* c, const rr_radar_point* points, uint32_t count, int max_points, const double* init, int n_hyp,
+                    const uint32_t* nearest_u32, const rr_field_config* cfg, int iterations, rr_icp_rec* recs)
+{
+    int rc = check_refine_poses(c, "rr_refine_poses", points, true, max_points, init, n_hyp, nearest_u32, cfg, iterations, recs); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)n_hyp, cells = (size_t)cfg->width * cfg->height;
+    RR_STAGE(c, st);
+    rr_radar_point* d_points; uint32_t* d_count; double* d_init; uint32_t* d_near; rr_icp_rec* d_recs;
+    RR_HIP(c, st.up_rows(points, 1, (size_t)max_points, &count, d_points));
+    RR_HIP(c, st.up(&count, 1, d_count));
+    RR_HIP(c, st.up(init, n * 4, d_init));
+    RR_HIP(c, st.up(nearest_u32, cells, d_near));
+    RR_HIP(c, st.hold(recs, n, d_recs));
+    RR_HIP(c, hipStreamSynchronize(c->stream));        // (count is this call's own variable)
+    rc = rr_refine_poses_device(c, d_points, d_count, max_points, d_init, n_hyp, d_near, cfg, iterations, d_recs, c->stream); if (rc) return rc;
     return st.commit();
 }
 

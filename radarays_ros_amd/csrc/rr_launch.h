@@ -1,4 +1,4 @@
-// rr_launch.h -- every launcher of rr_kernels.hip, rr_labels.hip, rr_paths.hip, rr_doppler.hip, rr_refit.hip, rr_detect.hip, rr_deskew.hip, rr_icp.hip, rr_field.hip, rr_occupancy.hip, rr_filter.hip, rr_notes.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip, rr_place.hip and rr_lbvh.hip, declared ONCE: included where they
+// rr_launch.h -- every launcher of rr_kernels.hip, rr_labels.hip, rr_paths.hip, rr_doppler.hip, rr_refit.hip, rr_detect.hip, rr_deskew.hip, rr_icp.hip, rr_field.hip, rr_occupancy.hip, rr_filter.hip, rr_refine.hip, rr_notes.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip, rr_place.hip and rr_lbvh.hip, declared ONCE: included where they
 // are defined (a definition that drifts from its declaration fails there) and where they are called.  Default arguments live here only.
 #pragma once
 #include "../../include/radarays_mi355.h"
@@ -101,6 +101,13 @@ void launch_filter_resample(const rr_field_rec* recs, int n, const uint16_t* tab
                             uint32_t* ancestors, rr_filter_summary* summary, hipStream_t s);
 void launch_filter_move(const float* states_in, int n, const uint32_t* ancestors, int n_out, float Dc, float Ds, float dx, float dy,
                         const rr_filter_config& f, float* states_out, hipStream_t s);
+// rr_refine.hip (map refinement).  No scratch and no context memory: nearest [height][width] is written whole (pass A leaves its offsets in it,
+// pass B overwrites them), every record of recs is written; init and recs 8-byte aligned, nearest 4-byte aligned and apart from occ.  Two
+// launches (columns, rows) and ONE, whatever the iteration count
+void refine_tile_sizes(int* points_tile, int* hyps_per_group, int* row_tile);
+void launch_nearest_field(const uint8_t* occ, int threshold, const rr_field_config& g, uint32_t* nearest, hipStream_t s);
+void launch_refine(const rr_radar_point* points, const uint32_t* count, int max_points, const double* init, int n_hyp, const uint32_t* nearest,
+                   const rr_field_config& g, int iterations, rr_icp_rec* recs, hipStream_t s);
 // rr_notes.hip (object annotations).  scratch: note_scratch_bytes, 16-byte aligned like notes; every word of it, of notes and of skipped is written by the launches
 size_t note_scratch_bytes(size_t n_frames, size_t n_objects, int n_angles);
 void launch_notes(const uint32_t* labels, const uint8_t* imgs, int n_frames, uint32_t n_objects, uint32_t extent_mask, const PolarGrid& G,

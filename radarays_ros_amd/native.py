@@ -324,6 +324,28 @@ def _increment(increment):
     return tuple(_f32_finite(x, "the increment") for x in v.tolist())
 
 
+# ---- map refinement (rr_refine.hip): the nearest-cell table of a grid map (uint32 [height][width], NEAREST_NONE where no occupied cell lies
+# within max_dist) and scan-to-map ICP from many starting states; the records are ICP_DTYPE
+NEAREST_NONE = 0xFFFFFFFF
+REFINE_RANGE = 8192.0             # every extent of a refinement's grid must lie within +-REFINE_RANGE metres
+
+
+def refine_tile_sizes():
+    """(points a wave of k_refine takes per step, hypotheses per workgroup of it, cells of a row per sweep of the transform's row pass)"""
+    a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+    lib().rr_refine_tile_sizes(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
+def _refine_cfg(cfg):
+    """a field config whose four extents, taken in f64 from its f32 fields, lie within +-REFINE_RANGE"""
+    g = _field_cfg(cfg)
+    for e in (g.x0, g.y0, g.x0 + g.width * float(g.cell), g.y0 + g.height * float(g.cell)):
+        if not abs(e) < REFINE_RANGE:
+            raise ValueError("the grid of a refinement must lie within +-%g m, an extent is at %r" % (REFINE_RANGE, e))
+    return g
+
+
 def _lattice_axis(half, step, what):
     half, step = float(half), float(step)
     if not (np.isfinite(half) and half >= 0 and np.isfinite(step) and step > 0):
@@ -611,6 +633,12 @@ def _prototypes():
         "rr_filter_move_device": (i, [vp, vp, i, vp, i, f, f, f, f, P(RRFilterConfig), vp, vp]),
         "rr_filter_move": (i, [vp, vp, i, vp, i, f, f, f, f, P(RRFilterConfig), vp]),
         "rr_filter_tile_sizes": (None, [P(i), P(i), P(i)]),
+        # ---- map refinement (rr_refine.hip)
+        "rr_nearest_field_device": (i, [vp, vp, i, P(RRFieldConfig), vp, vp]),
+        "rr_nearest_field": (i, [vp, vp, i, P(RRFieldConfig), vp]),
+        "rr_refine_poses_device": (i, [vp, vp, vp, i, vp, i, vp, P(RRFieldConfig), i, vp, vp]),
+        "rr_refine_poses": (i, [vp, vp, u32, i, vp, i, vp, P(RRFieldConfig), i, vp]),
+        "rr_refine_tile_sizes": (None, [P(i), P(i), P(i)]),
         # ---- several GPUs of one node behind one object (rr_multi.hip)
         "rr_create_multi": (vp, [P(i), i]),
         "rr_destroy_multi": (None, [vp]),
@@ -1792,6 +1820,55 @@ class Context(_Scene):
         out = np.zeros((m, 4), np.float32)
         self._ck(self._L.rr_filter_move(self._h, st.ctypes.data, len(st), _ptr(anc), m, *inc, C.byref(f), out.ctypes.data))
         return out
+
+    # ---- map refinement (rr_refine.hip): the nearest-cell transform of a grid map, and ICP of one scan against it from many states
+    def nearest_field_device(self, d_occ_ptr, field_cfg, d_nearest_ptr, threshold=1, stream=None):
+        """rr_nearest_field_device: the uint32 table [height][width] at d_nearest_ptr from the uint8 grid at d_occ_ptr (occupied: >=
+        threshold): per cell the linear index of the nearest occupied cell, NEAREST_NONE where none lies within max_dist"""
+        g, th = _field_cfg(field_cfg), _int_in(threshold, 1, 255, "threshold")
+        if not d_occ_ptr or not d_nearest_ptr or d_occ_ptr == d_nearest_ptr:
+            raise ValueError("nearest_field_device needs a grid and a table buffer that do not alias")
+        self._ck(self._L.rr_nearest_field_device(self._h, d_occ_ptr, th, C.byref(g), d_nearest_ptr, stream))
+
+    def nearest_field(self, occ, field_cfg, threshold=1):
+        """rr_nearest_field: uint8 [height][width] (occupied: >= threshold) -> uint32 [height][width]: jy * width + jx of the nearest occupied
+        cell (ties to the lowest index), NEAREST_NONE where its squared distance is not below max_dist^2"""
+        g, th = _field_cfg(field_cfg), _int_in(threshold, 1, 255, "threshold")
+        x = self._field_grid(occ, g, np.uint8, "occ")
+        out = np.zeros((g.height, g.width), np.uint32)
+        self._ck(self._L.rr_nearest_field(self._h, x.ctypes.data, th, C.byref(g), out.ctypes.data))
+        return out
+
+    def refine_poses_device(self, d_points_ptr, d_count_ptr, max_points, d_init_ptr, n_hyp, d_nearest_ptr, field_cfg, d_recs_ptr, iterations=10,
+                            stream=None):
+        """rr_refine_poses_device: ICP_DTYPE records [n_hyp] in HBM from the float64 initial states [n_hyp][4] = (c, s, tx, ty), each the
+        scan's sensor frame into the map frame, of ONE scan: the points at d_points_ptr whose count is the uint32 at d_count_ptr, against the
+        uint32 table of nearest_field_device; one launch on `stream`"""
+        mp, n, g = _int_in(max_points, 0, ICP_MAX_POINTS, "max_points"), _int_in(n_hyp, 1, FIELD_MAX_HYP, "n_hyp"), _refine_cfg(field_cfg)
+        it = _int_in(iterations, 0, 64, "iterations")
+        if not d_count_ptr or not d_init_ptr or not d_nearest_ptr or not d_recs_ptr or (mp > 0 and not d_points_ptr):
+            raise ValueError("refine_poses_device needs point, count, state, table and record buffers")
+        self._ck(self._L.rr_refine_poses_device(self._h, d_points_ptr, d_count_ptr, mp, d_init_ptr, n, d_nearest_ptr, C.byref(g), it, d_recs_ptr,
+                                                stream))
+
+    def refine_poses(self, points, init, nearest, field_cfg, iterations=10):
+        """rr_refine_poses: one POINT_DTYPE cloud, initial states [n][4] = (c, s, tx, ty) (se2_states, pose_lattice or a filter's states; they
+        are widened to float64 and normalised by the library), the uint32 table of nearest_field -> ICP_DTYPE [n]: the refined state, sse,
+        n_matched and flags of the last pass; iterations 0..64 (0 scores the states as they stand)"""
+        g, it = _refine_cfg(field_cfg), _int_in(iterations, 0, 64, "iterations")
+        p = np.asarray(points)
+        if p.dtype != POINT_DTYPE or p.ndim != 1 or len(p) > ICP_MAX_POINTS:
+            raise ValueError("the scan must be a one-dimensional POINT_DTYPE array of at most %d points" % ICP_MAX_POINTS)
+        st = np.asarray(init)
+        if st.dtype.kind not in "fiu" or st.ndim != 2 or st.shape[1] != 4 or not 1 <= len(st) <= FIELD_MAX_HYP:
+            raise ValueError("init must be real numbers of shape [n][4] (c, s, tx, ty), n in 1..%d, got %s %s" % (FIELD_MAX_HYP, st.dtype, st.shape))
+        st = np.ascontiguousarray(st, np.float64)
+        nr = self._field_grid(nearest, g, np.uint32, "nearest")
+        p = np.ascontiguousarray(p)
+        recs = np.zeros(len(st), ICP_DTYPE)
+        self._ck(self._L.rr_refine_poses(self._h, p.ctypes.data if len(p) else None, len(p), len(p), st.ctypes.data, len(st), nr.ctypes.data,
+                                         C.byref(g), it, recs.ctypes.data))
+        return recs
 
     # ---- object annotations (rr_notes.hip): one record per object from label images; any context with a config, mesh or not
     def _label_planes(self, planes, what="label planes"):

@@ -581,6 +581,76 @@ class RadarHIP:
         self.m_filter = dict(recs=recs, cum=cum, ancestors=anc)      # the step's intermediates, on the device, for who wants to look
         return out, home
 
+    # ---- map refinement (rr_refine.hip): the nearest-cell table of a grid map, and one scan refined against it from many states
+    def _on_device(self, x, dtype, shape, what):
+        """a tensor, or an array numpy takes, -> a contiguous tensor on the context's device; torch lacks uint16 and uint32 arithmetic, so
+        such words travel as int16 and int32"""
+        import torch
+        dev = torch.device("cuda", self._ctx.device)
+        if not isinstance(x, torch.Tensor):
+            a = np.ascontiguousarray(x)
+            signed = {np.dtype(np.uint16): np.int16, np.dtype(np.uint32): np.int32}.get(a.dtype)
+            a = a.view(signed) if signed is not None and np.dtype(signed) == np.dtype(dtype) else np.ascontiguousarray(a, dtype)
+            x = torch.from_numpy(a.copy())
+        if tuple(x.shape) != shape or x.element_size() != np.dtype(dtype).itemsize or x.is_floating_point() != (np.dtype(dtype).kind == "f"):
+            raise ValueError("%s must have shape %s and %s elements, got %s %s" % (what, shape, np.dtype(dtype), tuple(x.shape), x.dtype))
+        return x.to(dev).contiguous()
+
+    def buildNearestField(self, occ, field_cfg, threshold=1):
+        """An occupancy map uint8 [height][width] -- a grid of rasterize_points at threshold 1, a map of buildOccupancyMap at 129; numpy or
+        a torch tensor on the device -- -> its nearest-cell table, an int32 [height][width] tensor on the device (rr_nearest_field_device;
+        the words are uint32: jy * width + jx of the nearest occupied cell, native.NEAREST_NONE = -1 as int32 where none lies within
+        max_dist).  The table stays in HBM for refinePoses."""
+        import torch
+        self._push()
+        g, th = native._field_cfg(field_cfg), native._int_in(threshold, 1, 255, "threshold")
+        dev = torch.device("cuda", self._ctx.device)
+        stream = torch.cuda.Stream(device=dev)
+        torch.cuda.current_stream(dev).synchronize()      # the caller's tensor was made on its own stream
+        with torch.cuda.device(dev), torch.cuda.stream(stream):
+            d_occ = self._on_device(occ, np.uint8, (g.height, g.width), "occ")
+            table = torch.empty((g.height, g.width), dtype=torch.int32, device=dev)
+            self._ctx.nearest_field_device(d_occ.data_ptr(), g, table.data_ptr(), th, stream.cuda_stream)
+        self._ctx.synchronize(stream.cuda_stream)
+        return table
+
+    @staticmethod
+    def refineRecords(recs):
+        """the float64 [n][6] tensor of refinePoses -> native.ICP_DTYPE [n] on the host (c, s, tx, ty, sse, n_matched, flags)"""
+        return recs.detach().cpu().contiguous().numpy().view(np.uint8).reshape(-1).view(native.ICP_DTYPE).copy()
+
+    def refinePoses(self, scan, states, nearest, field_cfg, iterations=10):
+        """ONE observed scan refined against the map from every state of `states` at once: point-to-point ICP against the nearest-cell table
+        of buildNearestField, all iterations in one launch (rr_refine_poses_device), nothing leaving HBM.
+        scan: a POINT_DTYPE cloud; states: [n][4] = (c, s, tx, ty), each the scan's sensor frame into the map frame -- float32 as
+        native.pose_lattice and filterStep give them, or float64; numpy or a torch tensor on the device; float32 is widened to float64 on
+        the device; nearest: the int32 tensor of buildNearestField (or a uint32 array); field_cfg.gate is the match gate in cells.
+        Returns a float64 [n][6] tensor on the device, one 48-byte rr_icp_rec per row: columns 0..3 are the refined state, which
+        rasterize_points and occupancy_update take as it is; refineRecords() reads all of it (sse, n_matched, flags) on the host."""
+        import torch
+        self._push()
+        g, it = native._refine_cfg(field_cfg), native._int_in(iterations, 0, 64, "iterations")
+        dev = torch.device("cuda", self._ctx.device)
+        pts = np.ascontiguousarray(scan)
+        if pts.dtype != native.POINT_DTYPE or pts.ndim != 1 or not 1 <= len(pts) <= native.ICP_MAX_POINTS:
+            raise ValueError("the scan must be a one-dimensional POINT_DTYPE array of 1..%d points" % native.ICP_MAX_POINTS)
+        n = len(states)
+        if not 1 <= n <= native.FIELD_MAX_HYP:
+            raise ValueError("1..%d states, got %d" % (native.FIELD_MAX_HYP, n))
+        wide = states.dtype == torch.float64 if isinstance(states, torch.Tensor) else np.asarray(states).dtype == np.float64
+        stream = torch.cuda.Stream(device=dev)
+        s = stream.cuda_stream
+        torch.cuda.current_stream(dev).synchronize()      # the caller's tensors were made on its own stream
+        with torch.cuda.device(dev), torch.cuda.stream(stream):
+            st = self._on_device(states, np.float64 if wide else np.float32, (n, 4), "states").to(torch.float64).contiguous()
+            d_near = self._on_device(nearest, np.int32, (g.height, g.width), "nearest")
+            d_pts = torch.from_numpy(pts.view(np.uint8).copy()).to(dev)
+            d_count = torch.tensor([len(pts)], dtype=torch.int32, device=dev)
+            recs = torch.empty((n, 6), dtype=torch.float64, device=dev)
+            self._ctx.refine_poses_device(d_pts.data_ptr(), d_count.data_ptr(), len(pts), st.data_ptr(), n, d_near.data_ptr(), g, recs.data_ptr(), it, s)
+        self._ctx.synchronize(s)
+        return recs
+
     # ---- place recognition (rr_place.hip): a database of yaw-invariant ring/sector descriptors, and a scan looked up in it
     def buildPlaceDatabase(self, poses, place_cfg, on_device=False):
         """any number of [n][7] poses, worked through 64 at a time -> their descriptors uint8 [n][R][S] (native.Context._place_cfg
