@@ -1,7 +1,7 @@
 """numpy / scipy restatement of the image metrics of include/radarays_mi355.h (rr_compare_images_device): SSIM written the
 way skimage.metrics.structural_similarity writes it for uint8 images with its defaults, the joint histogram, and the
 entropies.  The GPU tests compare the library with this file; tests/test_metrics_host.py pins this file to sklearn and to an
-integer-window-sum form of SSIM."""
+integer-window-sum form of SSIM; tests/test_metrics_edges_host.py pins both to ssim_map, the S of every window position."""
 import numpy as np
 from scipy.ndimage import uniform_filter
 
@@ -44,6 +44,25 @@ def ssim_integer(x, y, win_size=7):
     C1, C2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2
     S = ((2 * ux * uy + C1) * (2 * vxy + C2)) / ((ux * ux + uy * uy + C1) * (vx + vy + C2))
     return float(S.mean(dtype=np.float64))
+
+
+def ssim_map(x, y, win_size=7):
+    """S of every window position, [n_rows - w + 1][n_cols - w + 1] in the window's corner coordinates, from window sums taken
+    by brute force (every window's w x w pixels added up in int64; no summed-area table, no filter) and the f64 expression of
+    ssim_integer.  Its mean is the SSIM; a third route to it, and the only one that says where a position's share lies"""
+    from numpy.lib.stride_tricks import sliding_window_view
+    x = np.asarray(x).astype(np.int64)
+    y = np.asarray(y).astype(np.int64)
+    w = win_size
+
+    def wsum(a):
+        return sliding_window_view(a, (w, w)).sum(axis=(2, 3)).astype(np.float64)
+    NP = float(w * w)
+    cov_norm = NP / (NP - 1)
+    ux, uy, uxx, uyy, uxy = wsum(x) / NP, wsum(y) / NP, wsum(x * x) / NP, wsum(y * y) / NP, wsum(x * y) / NP
+    vx, vy, vxy = cov_norm * (uxx - ux * ux), cov_norm * (uyy - uy * uy), cov_norm * (uxy - ux * uy)
+    C1, C2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2
+    return ((2 * ux * uy + C1) * (2 * vxy + C2)) / ((ux * ux + uy * uy + C1) * (vx + vy + C2))
 
 
 def joint_histogram(x, y):
