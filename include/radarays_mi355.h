@@ -1373,6 +1373,79 @@ int rr_refine_poses(rr_ctx* ctx, const rr_radar_point* points, uint32_t count, i
  * transform's row pass (tests put counts and sizes at their edges) */
 void rr_refine_tile_sizes(int* points_tile, int* hyps_per_group, int* row_tile);
 
+/* ---- beam model: the grid map cast at pose hypotheses, a scan's rays scored against it (rr_cast.hip) ------------------------
+ * The complement of the likelihood field.  rr_score_poses looks only at where a scan's detections END; here every azimuth of a hypothesis
+ * is cast through the map, and the range the map predicts is compared with the range the scan measured: rays that agree, rays that stop
+ * short, rays that saw through a wall.  The same cast answers "what would a scan look like from here, according to the map".  The
+ * reference has no such step: parity is UNPINNED and everything below is the build's own definition (a numpy restatement in
+ * tests/cast_ref.py checks the kernels byte for byte).  All f32 arithmetic is un-fused; every result is an integer and independent of
+ * order.
+ * MAP.  A uint16 field exactly as rr_distance_field[_device] writes it, under its rr_field_config, whose IN GRID rule and cell index are
+ * used unchanged; `gate` is ignored (any value passes).  A cell is OCCUPIED iff its field value is 0.  No occupancy bytes are passed.
+ * DIRECTIONS.  dirs is float [n_angles][2], one (ca, sa) per azimuth INDEX a (not per image column), an input that is used as given: no
+ * trigonometry on the device.
+ * A RAY.  A hypothesis state (c, s, tx, ty) is f32, used as given with no normalisation, under the likelihood field's pose convention.
+ * The ray of azimuth a is traced over the sample bins b = bin_begin + k * bin_step < bin_end, k = 0, 1, ...; all in f32, nothing fused:
+ *     r = (float)(((double)b + 0.5) * resolution)          x = r * ca          y = r * sa
+ *     px = (c*x - s*y) + tx          py = (s*x + c*y) + ty          then the IN GRID test and the cell index
+ * The sample is a HIT iff it is IN GRID and its cell is OCCUPIED; a sample that is not IN GRID is not a hit and the march goes on.  The
+ * expected bin e[a] is the smallest sampled b that is a hit, bin_end if there is none: a NaN anywhere gives bin_end.  That brute-force
+ * march is the DEFINITION; the kernel skips samples the field value proves empty and must give the same e[a].
+ * 1. rr_scan_profile[_device]: clouds as rr_detect_device writes them.  first_bin[f][a], uint16: with col the image column of azimuth a,
+ *    the bin of the point at d_offsets[f][col] if the column has a detection (d_offsets[f][col + 1] > d_offsets[f][col]) and that index is
+ *    below max_points, cut at n_cells; n_cells otherwise.  A plain kernel, a thread per (frame, azimuth).
+ * 2. rr_cast_map[_device]: ranges[h][a] = e[a] of hypothesis h, uint16 [n_hyp][n_angles]: the expected scan of the map at each pose.
+ * 3. rr_score_beams[_device]: ONE profile first_bin[n_angles], read on the device, against n_hyp hypotheses; one rr_beam_rec each.  Per
+ *    azimuth, with m = first_bin[a]: an azimuth with m < bin_begin is left out and not counted in n_cast; m >= bin_end counts as "none".
+ *        e none and m none: n_none          e none and m finite: n_open          e finite and m none: n_through
+ *        both finite, d = m - e:   |d| <= tol_bins: n_agree      d < -tol_bins: n_short      d > tol_bins: n_through
+ *                                  and in all three sum_abs += min(|d|, clip_bins)
+ *    The five counts sum to n_cast.  Nothing of size n_hyp * n_angles is written.
+ * n_angles, n_cells and resolution are the context's config's (-2 without one).  rr_set_config caps n_cells at 8192, so a bin always fits
+ * the tables' 16 bits; the calls would refuse a config beyond 65535 (-3).
+ * The device forms enqueue ONE launch on `stream` (NULL: the context's) with no host round trip, write only the caller's buffers and use
+ * NO context-owned memory: they may run on any stream beside batches in flight.  The host forms stage through context-owned buffers and are
+ * synchronous.
+ * Refused with a message and nothing written: -1 for a null ctx; -2 without a config; -3 for a null required buffer or config, a grid
+ * field but gate outside the likelihood field's ranges, a beam field outside its stated range, a non-zero reserved word, n_hyp outside its range
+ * (1..65535 for rr_cast_map, 1..2^22 for rr_score_beams), n_frames outside 1..65535, max_points outside 0..65536, states or dirs not
+ * 4-byte, the 16-bit tables not 2-byte or the records not 8-byte aligned.
+ * LIMITS.  Planar.  First hit only: the map stops a ray where radar would see past.  One scan per rr_score_beams call.  No weight table
+ * for rr_filter_resample, which takes rr_field_rec: mixing the two scores is the caller's.  rr_multi has no such call. */
+typedef struct rr_beam_config {   /* 32 B */
+    int32_t bin_begin, bin_end;   /* 0 <= bin_begin <= bin_end <= n_cells: the bins a ray samples */
+    int32_t bin_step;             /* 1..64: every bin_step-th bin from bin_begin is a sample */
+    int32_t tol_bins;             /* 0..n_cells: |m - e| within it is agreement */
+    int32_t clip_bins;            /* 0..n_cells: what one azimuth adds to sum_abs at most */
+    int32_t reserved_[3];         /* must be 0 */
+} rr_beam_config;
+typedef struct rr_beam_rec {   /* 32 B */
+    uint32_t n_agree;     /* both finite, |m - e| <= tol_bins */
+    uint32_t n_short;     /* both finite, the scan stopped more than tol_bins in front of the map's wall */
+    uint32_t n_through;   /* the scan saw more than tol_bins past the map's wall, or saw nothing where the map has one */
+    uint32_t n_open;      /* the scan has a detection where the map has nothing */
+    uint32_t n_none;      /* neither has anything */
+    uint32_t n_cast;      /* azimuths that took part: the sum of the five */
+    uint64_t sum_abs;     /* sum over the azimuths with both finite of min(|m - e|, clip_bins) */
+} rr_beam_rec;
+int rr_scan_profile_device(rr_ctx* ctx, const rr_radar_point* d_points, const uint32_t* d_offsets /*[n][n_angles+1]*/, int n_frames,
+                           int max_points, uint16_t* d_first_bin /*[n][n_angles]*/, void* stream);
+int rr_scan_profile(rr_ctx* ctx, const rr_radar_point* points, const uint32_t* offsets, int n_frames, int max_points,
+                    uint16_t* first_bin);                                                             /* host buffers, synchronous */
+int rr_cast_map_device(rr_ctx* ctx, const float* d_states /*[n_hyp][4]: c, s, tx, ty*/, int n_hyp /*1..65535*/,
+                       const float* d_dirs /*[n_angles][2]*/, const uint16_t* d_field_u16, const rr_field_config* cfg,
+                       const rr_beam_config* beam, uint16_t* d_ranges /*[n_hyp][n_angles]*/, void* stream);
+int rr_cast_map(rr_ctx* ctx, const float* states, int n_hyp, const float* dirs, const uint16_t* field_u16, const rr_field_config* cfg,
+                const rr_beam_config* beam, uint16_t* ranges);                                        /* host buffers, synchronous */
+int rr_score_beams_device(rr_ctx* ctx, const uint16_t* d_first_bin /*[n_angles]*/, const float* d_states /*[n_hyp][4]*/,
+                          int n_hyp /*1..2^22*/, const float* d_dirs /*[n_angles][2]*/, const uint16_t* d_field_u16,
+                          const rr_field_config* cfg, const rr_beam_config* beam, rr_beam_rec* d_recs /*[n_hyp]*/, void* stream);
+int rr_score_beams(rr_ctx* ctx, const uint16_t* first_bin, const float* states, int n_hyp, const float* dirs, const uint16_t* field_u16,
+                   const rr_field_config* cfg, const rr_beam_config* beam, rr_beam_rec* recs);        /* host buffers, synchronous */
+/* the blocking of k_cast: azimuths a wave takes per step (one per lane), hypotheses a wave takes in turn, hypotheses per workgroup
+ * (tests put counts at the edges) */
+void rr_cast_tile_sizes(int* angles_tile, int* hyps_per_wave, int* hyps_per_group);
+
 /* ---- several GPUs of one node behind one object (SURVEY.md §8b "Threading", §8e) -------------------------
  * The reference creates ONE backend object per process (src/radar_simulator.cpp:145-176) and fans out inside it
  * (OpenMP over azimuths, RadarCPU.cpp:155).  rr_multi is that object for n GPUs: one rr_ctx per device, mesh and

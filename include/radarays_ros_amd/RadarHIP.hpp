@@ -598,6 +598,32 @@ public:
         }
         return true;
     }
+    // The beam model (rr_cast.hip; include/radarays_mi355.h), every buffer in HBM and the caller's: the map's field cast at n_hyp states --
+    // d_states [n_hyp][4] f32 = c s tx ty (a state maps the sensor frame into the map frame), d_dirs [n_angles][2] f32 = cos sin per azimuth
+    // index -- into d_ranges uint16 [n_hyp][n_angles], the expected bin of every azimuth (beam.bin_end: the ray meets nothing).  One launch on
+    // `stream`; the call returns once it is enqueued.  false on error
+    bool castMap(const float* d_states, int n_hyp, const float* d_dirs, const uint16_t* d_field, const rr_field_config& cfg, const rr_beam_config& beam,
+                 uint16_t* d_ranges, void* stream = nullptr)
+    {
+        if (!push()) return false;
+        if (!marshal::cast_map(m_ctx, d_states, n_hyp, d_dirs, d_field, cfg, beam, d_ranges, stream)) {
+            fail();
+            return false;
+        }
+        return true;
+    }
+    // ... and ONE scan's profile d_first_bin uint16 [n_angles] (rr_scan_profile_device) scored against those rays: one rr_beam_rec per state
+    // into d_recs [n_hyp]; more n_agree is better, n_through counts the rays that saw through a wall of the map.  false on error
+    bool scoreBeams(const uint16_t* d_first_bin, const float* d_states, int n_hyp, const float* d_dirs, const uint16_t* d_field,
+                    const rr_field_config& cfg, const rr_beam_config& beam, rr_beam_rec* d_recs, void* stream = nullptr)
+    {
+        if (!push()) return false;
+        if (!marshal::score_beams(m_ctx, d_first_bin, d_states, n_hyp, d_dirs, d_field, cfg, beam, d_recs, stream)) {
+            fail();
+            return false;
+        }
+        return true;
+    }
     // one observed scan against hypothesis states [n][4] f32 (each the scan's sensor frame into the map frame) and a field of
     // buildLikelihoodField: one rr_field_rec per hypothesis, lower sum_d2 is better.  Empty on error
     std::vector<rr_field_rec> scorePoses(const std::vector<rr_radar_point>& scan, const std::vector<float>& states, const std::vector<uint16_t>& field,

@@ -278,6 +278,21 @@ inline bool refine_poses(rr_ctx* ctx, const rr_radar_point* d_scan, const uint32
     return rr_refine_poses_device(ctx, d_scan, d_count, max_points, d_init, n_hyp, d_nearest, &cfg, iterations, d_recs, stream) == 0;
 }
 
+// the beam model (rr_beam_config), every buffer the caller's and in HBM, on `stream`: the map's field cast at n_hyp states -- d_states [n_hyp][4]
+// f32 (c, s, tx, ty: the sensor frame into the map frame), d_dirs [n_angles][2] f32 -- into d_ranges uint16 [n_hyp][n_angles]
+// (rr_cast_map_device), or scored against ONE profile d_first_bin uint16 [n_angles] of rr_scan_profile_device into d_recs [n_hyp]
+// (rr_score_beams_device): one launch each, nothing comes home and nothing is waited for.  false: rr_last_error(ctx)
+inline bool cast_map(rr_ctx* ctx, const float* d_states, int n_hyp, const float* d_dirs, const uint16_t* d_field, const rr_field_config& cfg,
+                     const rr_beam_config& beam, uint16_t* d_ranges, void* stream)
+{
+    return rr_cast_map_device(ctx, d_states, n_hyp, d_dirs, d_field, &cfg, &beam, d_ranges, stream) == 0;
+}
+inline bool score_beams(rr_ctx* ctx, const uint16_t* d_first_bin, const float* d_states, int n_hyp, const float* d_dirs, const uint16_t* d_field,
+                        const rr_field_config& cfg, const rr_beam_config& beam, rr_beam_rec* d_recs, void* stream)
+{
+    return rr_score_beams_device(ctx, d_first_bin, d_states, n_hyp, d_dirs, d_field, &cfg, &beam, d_recs, stream) == 0;
+}
+
 // occupancy mapping (rr_occupancy_config): n clouds, each sorted by column then bin as rr_detect writes them and under its state (states
 // empty: the identity), fused into the int32 evidence [height][width] -- accumulated into what `evidence` holds if it has the grid's size,
 // else into zeros (rr_occupancy_update) -- and clamped into the byte map (rr_occupancy_map).  The offsets of each cloud are rebuilt from

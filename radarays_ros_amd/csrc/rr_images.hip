@@ -1,5 +1,5 @@
 // rr_images.hip -- the C ABI's image entry points: images in, records / points / images out.  PSNR scores and metrics against a reference image
-// (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), place recognition (rr_place.hip), point clouds and Cartesian images (rr_detect.hip), sweep compensation (rr_deskew.hip), scan matching (rr_icp.hip), the likelihood field (rr_field.hip), occupancy mapping (rr_occupancy.hip), the particle filter step (rr_filter.hip), map refinement (rr_refine.hip), object annotations (rr_notes.hip): each in a device form, which runs on the
+// (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), place recognition (rr_place.hip), point clouds and Cartesian images (rr_detect.hip), sweep compensation (rr_deskew.hip), scan matching (rr_icp.hip), the likelihood field (rr_field.hip), occupancy mapping (rr_occupancy.hip), the particle filter step (rr_filter.hip), map refinement (rr_refine.hip), the beam model (rr_cast.hip), object annotations (rr_notes.hip): each in a device form, which runs on the
 // caller's buffers and stream, and a host form, which drains c->stream and makes its round trip through a Stage over the context's pool (rr_stage.h).
 #include "rr_stage.h"
 #include <algorithm>
@@ -304,6 +304,43 @@ int check_refine_poses(rr_ctx* c, const char* who, const void* points, bool have
     const double ext[4] = {x0, y0, x0 + (double)g->width * cell, y0 + (double)g->height * cell};
     for (double e : ext)
         if (!(std::fabs(e) < 8192.0)) return fail(c, -3, w + ": the grid must lie within +-8192 m");
+    return 0;
+}
+
+// the refusals of rr_scan_profile_device / rr_scan_profile: the config gives the polar geometry; a bin must fit the table's 16 bits
+int check_scan_profile(rr_ctx* c, const char* who, const void* points, const void* offsets, int n_frames, int max_points, const void* first_bin)
+{
+    const std::string w(who);
+    const bool sizes_ok = max_points >= 0 && max_points <= 65536;
+    int rc = check_images(c, w, offsets && first_bin && (!sizes_ok || max_points == 0 || points), "buffer", "n_frames", n_frames, 65535); if (rc) return rc;
+    if (!sizes_ok) return fail(c, -3, w + ": max_points must be 0..65536");
+    if (c->cfg.n_cells > 65535) return fail(c, -3, w + ": n_cells must be at most 65535");
+    if ((uintptr_t)first_bin % 2 != 0) return fail(c, -3, w + ": the profile must be 2-byte aligned");
+    return 0;
+}
+
+// the refusals of the two ray calls (rr_cast_map, rr_score_beams and their device forms): `profile` and `recs` are the score form's, `ranges` the
+// range form's (the other form passes `true` in their place)
+int check_cast(rr_ctx* c, const char* who, bool have_profile, const void* profile, const void* states, int n_hyp, int n_hyp_max, const char* n_hyp_range,
+               const void* dirs, const void* field, const rr_field_config* g, const rr_beam_config* b, bool have_out, const void* ranges, const void* recs)
+{
+    const std::string w(who);
+    int rc = check_images(c, w, have_profile && states && dirs && field && have_out, "buffer", "n_hyp", 1, 1); if (rc) return rc;
+    if (n_hyp < 1 || n_hyp > n_hyp_max) return fail(c, -3, w + ": n_hyp must be " + n_hyp_range);
+    rc = check_grid_shape(c, w, g); if (rc) return rc;
+    if (g->max_dist < 1 || g->max_dist > 255) return fail(c, -3, w + ": max_dist must be 1..255");      // (gate is ignored: any value passes)
+    if (!b) return fail(c, -3, w + ": null beam config");
+    const int n_cells = c->cfg.n_cells;
+    if (n_cells > 65535) return fail(c, -3, w + ": n_cells must be at most 65535");
+    if (b->bin_begin < 0 || b->bin_begin > b->bin_end || b->bin_end > n_cells)
+        return fail(c, -3, w + ": 0 <= bin_begin <= bin_end <= n_cells (" + std::to_string(n_cells) + ") must hold");
+    if (b->bin_step < 1 || b->bin_step > 64) return fail(c, -3, w + ": bin_step must be 1..64");
+    if (b->tol_bins < 0 || b->tol_bins > n_cells) return fail(c, -3, w + ": tol_bins must be 0..n_cells (" + std::to_string(n_cells) + ")");
+    if (b->clip_bins < 0 || b->clip_bins > n_cells) return fail(c, -3, w + ": clip_bins must be 0..n_cells (" + std::to_string(n_cells) + ")");
+    if (b->reserved_[0] != 0 || b->reserved_[1] != 0 || b->reserved_[2] != 0) return fail(c, -3, w + ": reserved must be 0");
+    if ((uintptr_t)states % 4 != 0 || (uintptr_t)dirs % 4 != 0 || (uintptr_t)field % 2 != 0 || (uintptr_t)profile % 2 != 0 || (uintptr_t)ranges % 2 != 0 ||
+        (uintptr_t)recs % 8 != 0)
+        return fail(c, -3, w + ": states and dirs must be 4-byte, the 16-bit tables 2-byte and the records 8-byte aligned");
     return 0;
 }
 
@@ -1254,6 +1291,89 @@ int rr_refine_poses(rr_ctx* c, const rr_radar_point* points, uint32_t count, int
     RR_HIP(c, st.hold(recs, n, d_recs));
     RR_HIP(c, hipStreamSynchronize(c->stream));        // (count is this call's own variable)
     rc = rr_refine_poses_device(c, d_points, d_count, max_points, d_init, n_hyp, d_near, cfg, iterations, d_recs, c->stream); if (rc) return rc;
+    return st.commit();
+}
+
+// ---- beam model (rr_cast.hip) -------------------------------------------------------------------------------------------------
+void rr_cast_tile_sizes(int* angles_tile, int* hyps_per_wave, int* hyps_per_group) { cast_tile_sizes(angles_tile, hyps_per_wave, hyps_per_group); }
+
+int rr_scan_profile_device(rr_ctx* c, const rr_radar_point* d_points, const uint32_t* d_offsets, int n_frames, int max_points, uint16_t* d_first_bin,
+                           void* stream)
+{
+    int rc = check_scan_profile(c, "rr_scan_profile_device", d_points, d_offsets, n_frames, max_points, d_first_bin); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    launch_scan_profile(d_points, d_offsets, n_frames, max_points, polar_grid(c->cfg), d_first_bin, stream_of(c, stream));
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_scan_profile(rr_ctx* c, const rr_radar_point* points, const uint32_t* offsets, int n_frames, int max_points, uint16_t* first_bin)
+{
+    int rc = check_scan_profile(c, "rr_scan_profile", points, offsets, n_frames, max_points, first_bin); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)n_frames;
+    RR_STAGE(c, st);
+    std::vector<uint32_t> totals; rr_radar_point* d_points; uint32_t* d_offs; uint16_t* d_first;
+    rc = up_points(c, st, points, offsets, n, (size_t)max_points, totals, d_points, d_offs); if (rc) return rc;
+    RR_HIP(c, st.hold(first_bin, n * (size_t)c->cfg.n_angles, d_first));
+    rc = rr_scan_profile_device(c, d_points, d_offs, n_frames, max_points, d_first, c->stream); if (rc) return rc;
+    return st.commit();
+}
+
+int rr_cast_map_device(rr_ctx* c, const float* d_states, int n_hyp, const float* d_dirs, const uint16_t* d_field_u16, const rr_field_config* cfg,
+                       const rr_beam_config* beam, uint16_t* d_ranges, void* stream)
+{
+    int rc = check_cast(c, "rr_cast_map_device", true, nullptr, d_states, n_hyp, 65535, "1..65535", d_dirs, d_field_u16, cfg, beam, d_ranges != nullptr,
+                        d_ranges, nullptr); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    launch_cast(nullptr, d_states, n_hyp, d_dirs, c->cfg.n_angles, c->cfg.resolution, d_field_u16, *cfg, *beam, d_ranges, nullptr, stream_of(c, stream));
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_cast_map(rr_ctx* c, const float* states, int n_hyp, const float* dirs, const uint16_t* field_u16, const rr_field_config* cfg,
+                const rr_beam_config* beam, uint16_t* ranges)
+{
+    int rc = check_cast(c, "rr_cast_map", true, nullptr, states, n_hyp, 65535, "1..65535", dirs, field_u16, cfg, beam, ranges != nullptr, ranges, nullptr);
+    if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)n_hyp, A = (size_t)c->cfg.n_angles, cells = (size_t)cfg->width * cfg->height;
+    RR_STAGE(c, st);
+    float* d_states; float* d_dirs; uint16_t* d_field; uint16_t* d_ranges;
+    RR_HIP(c, st.up(states, n * 4, d_states));
+    RR_HIP(c, st.up(dirs, A * 2, d_dirs));
+    RR_HIP(c, st.up(field_u16, cells, d_field));
+    RR_HIP(c, st.hold(ranges, n * A, d_ranges));
+    rc = rr_cast_map_device(c, d_states, n_hyp, d_dirs, d_field, cfg, beam, d_ranges, c->stream); if (rc) return rc;
+    return st.commit();
+}
+
+int rr_score_beams_device(rr_ctx* c, const uint16_t* d_first_bin, const float* d_states, int n_hyp, const float* d_dirs, const uint16_t* d_field_u16,
+                          const rr_field_config* cfg, const rr_beam_config* beam, rr_beam_rec* d_recs, void* stream)
+{
+    int rc = check_cast(c, "rr_score_beams_device", d_first_bin != nullptr, d_first_bin, d_states, n_hyp, 1 << 22, "1..2^22", d_dirs, d_field_u16, cfg, beam,
+                        d_recs != nullptr, nullptr, d_recs); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    launch_cast(d_first_bin, d_states, n_hyp, d_dirs, c->cfg.n_angles, c->cfg.resolution, d_field_u16, *cfg, *beam, nullptr, d_recs, stream_of(c, stream));
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_score_beams(rr_ctx* c, const uint16_t* first_bin, const float* states, int n_hyp, const float* dirs, const uint16_t* field_u16,
+                   const rr_field_config* cfg, const rr_beam_config* beam, rr_beam_rec* recs)
+{
+    int rc = check_cast(c, "rr_score_beams", first_bin != nullptr, first_bin, states, n_hyp, 1 << 22, "1..2^22", dirs, field_u16, cfg, beam, recs != nullptr,
+                        nullptr, recs); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)n_hyp, A = (size_t)c->cfg.n_angles, cells = (size_t)cfg->width * cfg->height;
+    RR_STAGE(c, st);
+    uint16_t* d_first; float* d_states; float* d_dirs; uint16_t* d_field; rr_beam_rec* d_recs;
+    RR_HIP(c, st.up(first_bin, A, d_first));
+    RR_HIP(c, st.up(states, n * 4, d_states));
+    RR_HIP(c, st.up(dirs, A * 2, d_dirs));
+    RR_HIP(c, st.up(field_u16, cells, d_field));
+    RR_HIP(c, st.hold(recs, n, d_recs));
+    rc = rr_score_beams_device(c, d_first, d_states, n_hyp, d_dirs, d_field, cfg, beam, d_recs, c->stream); if (rc) return rc;
     return st.commit();
 }
 

@@ -1,4 +1,4 @@
-// rr_launch.h -- every launcher of rr_kernels.hip, rr_labels.hip, rr_paths.hip, rr_doppler.hip, rr_refit.hip, rr_detect.hip, rr_deskew.hip, rr_icp.hip, rr_field.hip, rr_occupancy.hip, rr_filter.hip, rr_refine.hip, rr_notes.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip, rr_place.hip and rr_lbvh.hip, declared ONCE: included where they
+// rr_launch.h -- every launcher of rr_kernels.hip, rr_labels.hip, rr_paths.hip, rr_doppler.hip, rr_refit.hip, rr_detect.hip, rr_deskew.hip, rr_icp.hip, rr_field.hip, rr_occupancy.hip, rr_filter.hip, rr_refine.hip, rr_cast.hip, rr_notes.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip, rr_place.hip and rr_lbvh.hip, declared ONCE: included where they
 // are defined (a definition that drifts from its declaration fails there) and where they are called.  Default arguments live here only.
 #pragma once
 #include "../../include/radarays_mi355.h"
@@ -108,6 +108,13 @@ void refine_tile_sizes(int* points_tile, int* hyps_per_group, int* row_tile);
 void launch_nearest_field(const uint8_t* occ, int threshold, const rr_field_config& g, uint32_t* nearest, hipStream_t s);
 void launch_refine(const rr_radar_point* points, const uint32_t* count, int max_points, const double* init, int n_hyp, const uint32_t* nearest,
                    const rr_field_config& g, int iterations, rr_icp_rec* recs, hipStream_t s);
+// rr_cast.hip (beam model).  No scratch and no context memory: first_bin [n_frames][n_angles] is written whole; launch_cast writes every record
+// of recs (the score form: first_bin is ONE profile) or, with recs null, ranges [n_hyp][n_angles] whole.  ONE launch each
+void cast_tile_sizes(int* angles_tile, int* hyps_per_wave, int* hyps_per_group);
+void launch_scan_profile(const rr_radar_point* points, const uint32_t* offsets, int n_frames, int max_points, const PolarGrid& G, uint16_t* first_bin,
+                         hipStream_t s);
+void launch_cast(const uint16_t* first_bin, const float* states, int n_hyp, const float* dirs, int n_angles, double resolution, const uint16_t* field,
+                 const rr_field_config& g, const rr_beam_config& bc, uint16_t* ranges, rr_beam_rec* recs, hipStream_t s);
 // rr_notes.hip (object annotations).  scratch: note_scratch_bytes, 16-byte aligned like notes; every word of it, of notes and of skipped is written by the launches
 size_t note_scratch_bytes(size_t n_frames, size_t n_objects, int n_angles);
 void launch_notes(const uint32_t* labels, const uint8_t* imgs, int n_frames, uint32_t n_objects, uint32_t extent_mask, const PolarGrid& G,

@@ -373,6 +373,53 @@ def pose_lattice(center_xy_yaw, half_extent_xy, step_xy, half_yaw, step_yaw):
     return np.ascontiguousarray(states), xyz
 
 
+# ---- beam model (rr_cast.hip): rr_beam_config (32 B), and rr_beam_rec as numpy sees it (32 B): one hypothesis' rays against one scan
+BEAM_DTYPE = np.dtype([("n_agree", "<u4"), ("n_short", "<u4"), ("n_through", "<u4"), ("n_open", "<u4"), ("n_none", "<u4"), ("n_cast", "<u4"),
+                       ("sum_abs", "<u8")])
+BEAM_MAX_STEP, BEAM_MAX_CELLS, CAST_MAX_HYP = 64, 65535, 65535
+RRBeamRec = np.ctypeslib.as_ctypes_type(BEAM_DTYPE)
+
+
+class RRBeamConfig(C.Structure):
+    _fields_ = [("bin_begin", C.c_int32), ("bin_end", C.c_int32), ("bin_step", C.c_int32), ("tol_bins", C.c_int32), ("clip_bins", C.c_int32),
+                ("reserved_", C.c_int32 * 3)]
+
+
+def beam_config(bin_begin, bin_end, n_cells, bin_step=1, tol_bins=0, clip_bins=0):
+    """rr_beam_config, range-checked before any call into the library: a ray samples the bins bin_begin + k * bin_step below bin_end
+    (0 <= bin_begin <= bin_end <= n_cells, bin_step 1..64); a measured bin within tol_bins (0..n_cells) of the expected one agrees; one
+    azimuth adds at most clip_bins (0..n_cells) to sum_abs"""
+    n = _int_in(n_cells, 1, BEAM_MAX_CELLS, "n_cells")
+    end = _int_in(bin_end, 0, n, "bin_end")
+    return RRBeamConfig(_int_in(bin_begin, 0, end, "bin_begin"), end, _int_in(bin_step, 1, BEAM_MAX_STEP, "bin_step"),
+                        _int_in(tol_bins, 0, n, "tol_bins"), _int_in(clip_bins, 0, n, "clip_bins"), (C.c_int32 * 3)())
+
+
+def beam_directions(cfg):
+    """the direction table of the ray calls for an rr_config (make_config returns one, Context._rrcfg holds it): float32 [n_angles][2] =
+    (cos, sin) of theta_min + a * theta_inc per azimuth INDEX a, numpy's in float64, rounded once to float32.  Like pose_lattice's states
+    the table is an input of the cast, so this does not touch its bit-exactness."""
+    theta = float(cfg.theta_min) + np.arange(int(cfg.n_angles), dtype=np.float64) * float(cfg.theta_inc)
+    return np.ascontiguousarray(np.stack([np.cos(theta), np.sin(theta)], axis=1).astype(np.float32))
+
+
+def _cast_cfg(cfg):
+    """the grid of a ray call: an RRFieldConfig or a dict of field_config's arguments whose shape, place and max_dist are range-checked;
+    gate is ignored there and passes as it is"""
+    if isinstance(cfg, RRFieldConfig):
+        g = field_config(cfg.width, cfg.height, cfg.cell, cfg.x0, cfg.y0, cfg.max_dist, 0)
+        g.gate = cfg.gate
+        return g
+    return _field_cfg(cfg)
+
+
+def cast_tile_sizes():
+    """(azimuths a wave of k_cast takes per step, hypotheses a wave takes in turn, hypotheses per workgroup)"""
+    a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+    lib().rr_cast_tile_sizes(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
 # rr_default_detect_config
 DETECT_DEFAULTS = {"method": 0, "guard_cells": 2, "train_cells": 16, "k": 12, "min_intensity": 1, "min_bin": 0, "cfar_scale": 3.0}
 DETECT_METHODS = {"cfar": 0, "ca-cfar": 0, "kstrongest": 1, "k-strongest": 1, 0: 0, 1: 1}
@@ -494,6 +541,7 @@ STRUCTS = {
     "rr_icp_rec": (RRIcpRec, ICP_DTYPE), "rr_field_config": (RRFieldConfig, None), "rr_field_rec": (RRFieldRec, FIELD_DTYPE),
     "rr_occupancy_config": (RROccupancyConfig, None), "rr_filter_config": (RRFilterConfig, FILTER_CONFIG_DTYPE),
     "rr_filter_summary": (RRFilterSummary, FILTER_SUMMARY_DTYPE), "rr_mesh": (RRMesh, None),
+    "rr_beam_config": (RRBeamConfig, None), "rr_beam_rec": (RRBeamRec, BEAM_DTYPE),
 }
 
 
@@ -639,6 +687,14 @@ def _prototypes():
         "rr_refine_poses_device": (i, [vp, vp, vp, i, vp, i, vp, P(RRFieldConfig), i, vp, vp]),
         "rr_refine_poses": (i, [vp, vp, u32, i, vp, i, vp, P(RRFieldConfig), i, vp]),
         "rr_refine_tile_sizes": (None, [P(i), P(i), P(i)]),
+        # ---- beam model (rr_cast.hip)
+        "rr_scan_profile_device": (i, [vp, vp, vp, i, i, vp, vp]),
+        "rr_scan_profile": (i, [vp, vp, vp, i, i, vp]),
+        "rr_cast_map_device": (i, [vp, vp, i, vp, vp, P(RRFieldConfig), P(RRBeamConfig), vp, vp]),
+        "rr_cast_map": (i, [vp, vp, i, vp, vp, P(RRFieldConfig), P(RRBeamConfig), vp]),
+        "rr_score_beams_device": (i, [vp, vp, vp, i, vp, vp, P(RRFieldConfig), P(RRBeamConfig), vp, vp]),
+        "rr_score_beams": (i, [vp, vp, vp, i, vp, vp, P(RRFieldConfig), P(RRBeamConfig), vp]),
+        "rr_cast_tile_sizes": (None, [P(i), P(i), P(i)]),
         # ---- several GPUs of one node behind one object (rr_multi.hip)
         "rr_create_multi": (vp, [P(i), i]),
         "rr_destroy_multi": (None, [vp]),
@@ -1868,6 +1924,90 @@ class Context(_Scene):
         recs = np.zeros(len(st), ICP_DTYPE)
         self._ck(self._L.rr_refine_poses(self._h, p.ctypes.data if len(p) else None, len(p), len(p), st.ctypes.data, len(st), nr.ctypes.data,
                                          C.byref(g), it, recs.ctypes.data))
+        return recs
+
+    # ---- beam model (rr_cast.hip): a scan's first detection per azimuth, the map cast at pose hypotheses, a scan's rays scored against it
+    def _beam_cfg(self, beam_cfg):
+        """an RRBeamConfig or a dict of beam_config's arguments (n_cells is this context's), held to this context's n_cells"""
+        n_cells, _ = self._polar_shape()
+        if isinstance(beam_cfg, RRBeamConfig):
+            if any(beam_cfg.reserved_):
+                raise ValueError("reserved must be 0")
+            return beam_config(beam_cfg.bin_begin, beam_cfg.bin_end, n_cells, beam_cfg.bin_step, beam_cfg.tol_bins, beam_cfg.clip_bins)
+        if isinstance(beam_cfg, dict):
+            return beam_config(n_cells=n_cells, **beam_cfg)
+        raise ValueError("a beam config must be an RRBeamConfig (native.beam_config makes one) or a dict of its arguments, got %r" % (beam_cfg,))
+
+    def _cast_inputs(self, states, n_max, dirs, field, g):
+        """the host arrays of the two ray calls, checked -> (float32 states [n][4], float32 dirs [n_angles][2], the uint16 field)"""
+        _, n_angles = self._polar_shape()
+        st = np.asarray(states)
+        if st.dtype.kind not in "fiu" or st.ndim != 2 or st.shape[1] != 4 or not 1 <= len(st) <= n_max:
+            raise ValueError("states must be real numbers of shape [n][4] (c, s, tx, ty), n in 1..%d, got %s %s" % (n_max, st.dtype, st.shape))
+        d = np.asarray(dirs)
+        if d.dtype.kind not in "fiu" or d.shape != (n_angles, 2):
+            raise ValueError("dirs must be real numbers of shape [%d][2] (beam_directions makes them), got %s %s" % (n_angles, d.dtype, d.shape))
+        return np.ascontiguousarray(st, np.float32), np.ascontiguousarray(d, np.float32), self._field_grid(field, g, np.uint16, "field")
+
+    def scan_profile_device(self, d_points_ptr, d_offsets_ptr, n_frames, max_points, d_first_bin_ptr, stream=None):
+        """rr_scan_profile_device: uint16 [n_frames][n_angles] at d_first_bin_ptr, per azimuth INDEX the bin of the first detection among
+        the points [n_frames][max_points] and offsets [n_frames][n_angles + 1] rr_detect_device wrote, n_cells where there is none"""
+        n_cells, _ = self._polar_shape()
+        _int_in(n_cells, 1, BEAM_MAX_CELLS, "n_cells")
+        n, mp = _frames_arg(n_frames), _int_in(max_points, 0, ICP_MAX_POINTS, "max_points")
+        if not d_offsets_ptr or not d_first_bin_ptr or (mp > 0 and not d_points_ptr):
+            raise ValueError("scan_profile_device needs point, offset and profile buffers")
+        self._ck(self._L.rr_scan_profile_device(self._h, d_points_ptr, d_offsets_ptr, n, mp, d_first_bin_ptr, stream))
+
+    def scan_profile(self, points_list, offsets):
+        """rr_scan_profile on what detect() returned: a list of n POINT_DTYPE arrays and offsets uint32 [n][n_angles + 1] -> uint16
+        [n][n_angles]"""
+        n_cells, n_angles = self._polar_shape()
+        _int_in(n_cells, 1, BEAM_MAX_CELLS, "n_cells")
+        buf, offs, _ = self._posed_clouds(points_list, offsets, None)
+        out = np.zeros((len(buf), n_angles), np.uint16)
+        self._ck(self._L.rr_scan_profile(self._h, buf.ctypes.data, offs.ctypes.data, len(buf), buf.shape[1], out.ctypes.data))
+        return out
+
+    def cast_map_device(self, d_states_ptr, n_hyp, d_dirs_ptr, d_field_ptr, field_cfg, beam_cfg, d_ranges_ptr, stream=None):
+        """rr_cast_map_device: uint16 [n_hyp][n_angles] at d_ranges_ptr, the expected bin of every azimuth of the float32 states [n_hyp][4]
+        = (c, s, tx, ty), each the sensor frame into the map frame, on the uint16 field of distance_field_device; d_dirs_ptr: float32
+        [n_angles][2]; one launch on `stream`"""
+        g, b, n = _cast_cfg(field_cfg), self._beam_cfg(beam_cfg), _int_in(n_hyp, 1, CAST_MAX_HYP, "n_hyp")
+        if not d_states_ptr or not d_dirs_ptr or not d_field_ptr or not d_ranges_ptr:
+            raise ValueError("cast_map_device needs state, direction, field and range buffers")
+        self._ck(self._L.rr_cast_map_device(self._h, d_states_ptr, n, d_dirs_ptr, d_field_ptr, C.byref(g), C.byref(b), d_ranges_ptr, stream))
+
+    def cast_map(self, states, dirs, field, field_cfg, beam_cfg):
+        """rr_cast_map: float32 states [n][4], the table of beam_directions, the uint16 field of distance_field -> uint16 [n][n_angles]:
+        the expected scan of the map at each pose, bin_end where a ray meets nothing"""
+        g, b = _cast_cfg(field_cfg), self._beam_cfg(beam_cfg)
+        st, d, f = self._cast_inputs(states, CAST_MAX_HYP, dirs, field, g)
+        out = np.zeros((len(st), len(d)), np.uint16)
+        self._ck(self._L.rr_cast_map(self._h, st.ctypes.data, len(st), d.ctypes.data, f.ctypes.data, C.byref(g), C.byref(b), out.ctypes.data))
+        return out
+
+    def score_beams_device(self, d_first_bin_ptr, d_states_ptr, n_hyp, d_dirs_ptr, d_field_ptr, field_cfg, beam_cfg, d_recs_ptr, stream=None):
+        """rr_score_beams_device: BEAM_DTYPE records [n_hyp] in HBM for the float32 states [n_hyp][4] against ONE profile uint16 [n_angles]
+        (a row of scan_profile_device); one launch on `stream`"""
+        g, b, n = _cast_cfg(field_cfg), self._beam_cfg(beam_cfg), _int_in(n_hyp, 1, FIELD_MAX_HYP, "n_hyp")
+        if not d_first_bin_ptr or not d_states_ptr or not d_dirs_ptr or not d_field_ptr or not d_recs_ptr:
+            raise ValueError("score_beams_device needs profile, state, direction, field and record buffers")
+        self._ck(self._L.rr_score_beams_device(self._h, d_first_bin_ptr, d_states_ptr, n, d_dirs_ptr, d_field_ptr, C.byref(g), C.byref(b), d_recs_ptr,
+                                               stream))
+
+    def score_beams(self, first_bin, states, dirs, field, field_cfg, beam_cfg):
+        """rr_score_beams: one profile uint16 [n_angles] (a row of scan_profile), float32 states [n][4], the table of beam_directions, the
+        uint16 field of distance_field -> BEAM_DTYPE [n]; more n_agree is better, n_through counts the rays that saw through a wall"""
+        g, b = _cast_cfg(field_cfg), self._beam_cfg(beam_cfg)
+        st, d, f = self._cast_inputs(states, FIELD_MAX_HYP, dirs, field, g)
+        fb = np.asarray(first_bin)
+        if fb.dtype != np.uint16 or fb.shape != (len(d),):
+            raise ValueError("the profile must be uint16 [%d], got %s %s" % (len(d), fb.dtype, fb.shape))
+        fb = np.ascontiguousarray(fb)
+        recs = np.zeros(len(st), BEAM_DTYPE)
+        self._ck(self._L.rr_score_beams(self._h, fb.ctypes.data, st.ctypes.data, len(st), d.ctypes.data, f.ctypes.data, C.byref(g), C.byref(b),
+                                        recs.ctypes.data))
         return recs
 
     # ---- object annotations (rr_notes.hip): one record per object from label images; any context with a config, mesh or not

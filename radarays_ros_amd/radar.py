@@ -651,6 +651,70 @@ class RadarHIP:
         self._ctx.synchronize(s)
         return recs
 
+    # ---- beam model (rr_cast.hip): the map cast at pose hypotheses, and a scan's rays scored against it
+    def _scan_with_offsets(self, scan_points_or_image, detect_cfg):
+        """a POINT_DTYPE cloud (sorted by column, then bin; its offsets are rebuilt from the columns) or a mono8 polar image, which is
+        detected first -> ([cloud], offsets uint32 [1][401])"""
+        scan = np.asarray(scan_points_or_image)
+        if scan.dtype != native.POINT_DTYPE:
+            pts, offs = self._ctx.detect(self._polar(scan_points_or_image), native.detect_config(detect_cfg, n_cells=self.m_cfg.n_cells))
+            return [pts[0]], offs[:1]
+        if scan.ndim != 1:
+            raise ValueError("the scan must be a one-dimensional POINT_DTYPE array")
+        col = scan["column"].astype(np.int64)
+        if len(col) and (col.max() >= N_ANGLES or np.any(np.diff(col) < 0)):
+            raise ValueError("the scan is not sorted by column, or names a column past %d" % (N_ANGLES - 1))
+        offs = np.zeros((1, N_ANGLES + 1), np.uint32)
+        offs[0, 1:] = np.cumsum(np.bincount(col, minlength=N_ANGLES))
+        return [scan], offs
+
+    def scanProfile(self, scan_points_or_image, detect_cfg=None):
+        """One observed scan -> uint16 [400]: per azimuth INDEX the bin of its first detection, n_cells where it has none
+        (rr_scan_profile).  The scan is a POINT_DTYPE cloud or a mono8 polar image [n_cells][400], as scorePoses takes it."""
+        self._push()
+        pts, offs = self._scan_with_offsets(scan_points_or_image, detect_cfg)
+        return self._ctx.scan_profile(pts, offs)[0]
+
+    def beamDirections(self):
+        """float32 [400][2]: (cos, sin) of every azimuth index under the current config (native.beam_directions)"""
+        self._push()
+        return native.beam_directions(self._ctx._rrcfg)
+
+    def castMap(self, states, field, field_cfg, beam_cfg):
+        """The expected scan of the map at each state: float32 states [n][4] = (c, s, tx, ty), n <= 65535 (native.pose_lattice makes them),
+        each the sensor frame into the map frame, cast through the uint16 field of buildLikelihoodField (or of distance_field on a map of
+        buildOccupancyMap at threshold 129) -> an int16 [n][400] tensor on the device whose words are uint16: per azimuth index the first
+        sampled bin whose cell is occupied, beam_cfg's bin_end where the ray meets nothing (rr_cast_map_device; beam_cfg:
+        native.beam_config or a dict of its arguments).  states and field: numpy or torch tensors on the device."""
+        import torch
+        self._push()
+        g, b = native._cast_cfg(field_cfg), self._ctx._beam_cfg(beam_cfg)
+        n = len(states)
+        if not 1 <= n <= native.CAST_MAX_HYP:
+            raise ValueError("1..%d states, got %d" % (native.CAST_MAX_HYP, n))
+        dev = torch.device("cuda", self._ctx.device)
+        stream = torch.cuda.Stream(device=dev)
+        torch.cuda.current_stream(dev).synchronize()      # the caller's tensors were made on its own stream
+        with torch.cuda.device(dev), torch.cuda.stream(stream):
+            st = self._on_device(states, np.float32, (n, 4), "states")
+            d_field = self._on_device(field, np.int16, (g.height, g.width), "field")
+            d_dirs = torch.from_numpy(native.beam_directions(self._ctx._rrcfg)).to(dev)
+            ranges = torch.empty((n, N_ANGLES), dtype=torch.int16, device=dev)
+            self._ctx.cast_map_device(st.data_ptr(), n, d_dirs.data_ptr(), d_field.data_ptr(), g, b, ranges.data_ptr(), stream.cuda_stream)
+        self._ctx.synchronize(stream.cuda_stream)
+        return ranges
+
+    def scoreBeams(self, scan_points_or_image, states, field, field_cfg, beam_cfg, detect_cfg=None):
+        """One observed scan against float32 states [n][4] and the field of a map -> native.BEAM_DTYPE [n]: per state the azimuths whose
+        measured first detection agrees with the range the map predicts (n_agree), stops short of it (n_short), lies beyond it or is
+        missing where the map has a wall (n_through), and sum_abs of the clipped differences; more n_agree is better.  The scan is a
+        POINT_DTYPE cloud or a mono8 polar image, as scorePoses takes it; its profile is scanProfile's.
+        Convention: a hypothesis state (c, s, tx, ty) maps the scan's sensor frame into the map frame."""
+        self._push()
+        pts, offs = self._scan_with_offsets(scan_points_or_image, detect_cfg)
+        first = self._ctx.scan_profile(pts, offs)[0]
+        return self._ctx.score_beams(first, states, native.beam_directions(self._ctx._rrcfg), field, field_cfg, beam_cfg)
+
     # ---- place recognition (rr_place.hip): a database of yaw-invariant ring/sector descriptors, and a scan looked up in it
     def buildPlaceDatabase(self, poses, place_cfg, on_device=False):
         """any number of [n][7] poses, worked through 64 at a time -> their descriptors uint8 [n][R][S] (native.Context._place_cfg
