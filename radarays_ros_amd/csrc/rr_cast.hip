@@ -17,8 +17,10 @@
 // Every scalar travels as a kernel argument.  No scratch memory and no LDS in any kernel of the file.
 #include "../../include/radarays_mi355.h"
 #include "rr_device.h"
+#include "rr_grid.h"
 #include "rr_launch.h"
 #include "rr_polar.h"
+#include "rr_pose2d.h"
 
 namespace rr {
 
@@ -39,32 +41,21 @@ constexpr float kCastMaxSkip = 65536.0f;
 static_assert(sizeof(rr_field_config) == 32 && sizeof(rr_beam_config) == 32 && sizeof(rr_beam_rec) == 32, "the grid, the beams and a record: 32 bytes");
 static_assert(sizeof(rr_radar_point) == 24, "a 24-byte point");
 
-// the cell rule of the header (the likelihood field's): the comparisons are made in float, before any conversion to int
-__device__ inline bool cast_cell_of(float px, float py, const rr_field_config& g, uint32_t* index)
-{
-    const float u = (px - g.x0) / g.cell, v = (py - g.y0) / g.cell;
-    const bool in = u >= 0.0f && u < (float)g.width && v >= 0.0f && v < (float)g.height;
-    const int ix = in ? (int)floorf(u) : 0, iy = in ? (int)floorf(v) : 0;
-    *index = (uint32_t)(iy * g.width + ix);
-    return in;
-}
-
 __global__ void __launch_bounds__(256) k_scan_profile(const rr_radar_point* __restrict__ points, const uint32_t* __restrict__ offsets, int max_points,
                                                       PolarGrid G, uint16_t* __restrict__ first_bin)
 {
     const int f = blockIdx.y, a = blockIdx.x * 256 + threadIdx.x;
     if (a >= G.n_angles) return;
-    const int col = col_of_az(G, a);
-    const uint32_t* offs = offsets + (size_t)f * (G.n_angles + 1);
-    const uint32_t first = offs[col], next = offs[col + 1];
-    uint32_t fb = (uint32_t)G.n_cells;
-    if (next > first && first < (uint32_t)max_points) fb = min(points[(size_t)f * max_points + first].bin, (uint32_t)G.n_cells);
+    uint32_t fb = (uint32_t)G.n_cells, bin;
+    bool cut;
+    if (column_first_bin(points + (size_t)f * max_points, offsets + (size_t)f * (G.n_angles + 1), col_of_az(G, a), max_points, &bin, &cut))
+        fb = min(bin, (uint32_t)G.n_cells);
     first_bin[(size_t)f * G.n_angles + a] = (uint16_t)fb;
 }
 
 // what a ray's march needs beside its direction; the same for every lane of a wave
 struct CastWave {
-    float c, s, tx, ty;          // the hypothesis
+    Pose2 p;                     // the hypothesis (c, s, tx, ty)
     float len_cs, m1, t1;        // sqrt(c*c + s*s + tiny), |c| + |s|, |tx| + |ty|
 };
 
@@ -80,13 +71,12 @@ __device__ inline int cast_ray(const CastWave& w, float ca, float sa, const uint
     int b = bin_begin;
     while (b < bin_end) {
         const float r = (float)(((double)b + 0.5) * resolution);
-        const float x = r * ca, y = r * sa;
-        const float px = (w.c * x - w.s * y) + w.tx;
-        const float py = (w.s * x + w.c * y) + w.ty;
-        uint32_t index;
+        float px, py;
+        pose_move(w.p, r * ca, r * sa, &px, &py);
+        const GridCell q = grid_cell(px, py, g);
         int advance = 1;
-        if (cast_cell_of(px, py, g, &index)) {
-            const uint32_t d2 = field[index];
+        if (q.in) {
+            const uint32_t d2 = field[grid_index(q, g)];
             if (d2 == 0) break;                                  // a hit: e = b
             const float q = ((floorf(sqrtf((float)d2)) - kCastDiag) - err) * inv_g;
             if (q >= 1.0f) advance += (int)fminf(q, kCastMaxSkip);      // (false for a NaN)
@@ -108,10 +98,10 @@ __global__ void __launch_bounds__(kCastTB) k_cast(const float* __restrict__ stat
         const int h = h0 + t;
         if (h >= n_hyp) return;                                   // (the whole wave; the kernel has no barrier)
         CastWave w;
-        w.c = states[4 * (size_t)h]; w.s = states[4 * (size_t)h + 1]; w.tx = states[4 * (size_t)h + 2]; w.ty = states[4 * (size_t)h + 3];
-        w.len_cs = sqrtf((w.c * w.c + w.s * w.s) + kCastTiny);
-        w.m1 = fabsf(w.c) + fabsf(w.s);
-        w.t1 = fabsf(w.tx) + fabsf(w.ty);
+        w.p = pose_of(states, (size_t)h);
+        w.len_cs = sqrtf((w.p.c * w.p.c + w.p.s * w.p.s) + kCastTiny);
+        w.m1 = fabsf(w.p.c) + fabsf(w.p.s);
+        w.t1 = fabsf(w.p.tx) + fabsf(w.p.ty);
 
         uint32_t n_agree = 0, n_short = 0, n_through = 0, n_open = 0, n_none = 0, n_cast = 0;
         unsigned long long sum_abs = 0;
@@ -142,17 +132,11 @@ __global__ void __launch_bounds__(kCastTB) k_cast(const float* __restrict__ stat
             }
         }
         if (!SCORE) continue;
-        for (int k = 32; k > 0; k >>= 1) {
-            n_agree += __shfl_xor(n_agree, k, 64); n_short += __shfl_xor(n_short, k, 64); n_through += __shfl_xor(n_through, k, 64);
-            n_open += __shfl_xor(n_open, k, 64); n_none += __shfl_xor(n_none, k, 64); n_cast += __shfl_xor(n_cast, k, 64);
-            sum_abs += __shfl_xor(sum_abs, k, 64);
-        }
-        if (lane == 0) {
-            rr_beam_rec r;
-            r.n_agree = n_agree; r.n_short = n_short; r.n_through = n_through; r.n_open = n_open; r.n_none = n_none; r.n_cast = n_cast;
-            r.sum_abs = sum_abs;
-            recs[h] = r;                                          // plain vector stores, one record per hypothesis
-        }
+        rr_beam_rec r;
+        r.n_agree = wave_sum(n_agree); r.n_short = wave_sum(n_short); r.n_through = wave_sum(n_through);
+        r.n_open = wave_sum(n_open); r.n_none = wave_sum(n_none); r.n_cast = wave_sum(n_cast);
+        r.sum_abs = wave_sum(sum_abs);
+        if (lane == 0) recs[h] = r;                               // plain vector stores, one record per hypothesis
     }
 }
 

@@ -227,6 +227,13 @@ __device__ inline int block_excl_scan(int v, int& total, int* lds /*[8]*/)
     return pre + x - v;
 }
 
+// the sum of x over the 64 lanes of a wave, left in every lane (T: uint32_t, unsigned long long, long long)
+template <class T> __device__ inline T wave_sum(T x)
+{
+    for (int e = 32; e > 0; e >>= 1) x += __shfl_xor(x, e, 64);
+    return x;
+}
+
 __device__ inline Quat ld_quat(const float4* p) { const float4 v = *p; return { v.x, v.y, v.z, v.w }; }
 
 // Tam = Tsm * Tas (RadarCPU.cpp:201-206); Tas.t = 0.

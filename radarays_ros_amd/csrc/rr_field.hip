@@ -22,7 +22,9 @@
 // Every scalar travels as a kernel argument.  No scratch memory; LDS only in k_field_rows (the staged row).
 #include "../../include/radarays_mi355.h"
 #include "rr_device.h"
+#include "rr_grid.h"
 #include "rr_launch.h"
+#include "rr_pose2d.h"
 
 namespace rr {
 
@@ -33,39 +35,23 @@ constexpr int kFieldK = 8;                                       // hypotheses a
 constexpr int kFieldHypsPerGroup = (kFieldTB / 64) * kFieldK;    // 32
 constexpr int kFieldPointsTile = 64;                             // points a wave takes per step: one per lane
 constexpr int kFieldRowTile = 64;                                // threads of a k_field_rows workgroup = cells of a row per sweep
-constexpr int kFieldMaxSide = 4096, kFieldMaxDist = 255;
 
 static_assert(sizeof(rr_field_config) == 32 && sizeof(rr_field_rec) == 16, "the grid is 32 bytes, a record 16");
 static_assert(sizeof(rr_radar_point) == 24, "x and y lead a 24-byte point");
-
-// the cell rule of the header: the comparisons are made in float, before any conversion to int; a NaN or an infinity fails them
-__device__ inline bool cell_of(float px, float py, const rr_field_config& g, uint32_t* index)
-{
-    const float u = (px - g.x0) / g.cell, v = (py - g.y0) / g.cell;
-    const bool in = u >= 0.0f && u < (float)g.width && v >= 0.0f && v < (float)g.height;
-    const int ix = in ? (int)floorf(u) : 0, iy = in ? (int)floorf(v) : 0;
-    *index = (uint32_t)(iy * g.width + ix);                      // (0 for a point that is not IN GRID: an address that may be read)
-    return in;
-}
 
 __global__ void __launch_bounds__(256) k_field_raster(const rr_radar_point* points, const uint32_t* offsets, int n_angles, int max_points,
                                                       const double* states, rr_field_config g, uint8_t* occ)
 {
     const int f = blockIdx.y;
-    const uint32_t m = min(offsets[(size_t)f * (n_angles + 1) + n_angles], (uint32_t)max_points);
+    const uint32_t m = frame_count(offsets, f, n_angles, max_points, nullptr);
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= m) return;
-    float cf = 1.0f, sf = 0.0f, txf = 0.0f, tyf = 0.0f;
-    if (states) {
-        cf = (float)states[4 * (size_t)f]; sf = (float)states[4 * (size_t)f + 1];
-        txf = (float)states[4 * (size_t)f + 2]; tyf = (float)states[4 * (size_t)f + 3];
-    }
+    const Pose2 st = pose_of(states, (size_t)f);
     const rr_radar_point* src = points + (size_t)f * max_points;
-    const float x = src[i].x, y = src[i].y;
-    const float px = (cf * x - sf * y) + txf;
-    const float py = (sf * x + cf * y) + tyf;
-    uint32_t index;
-    if (cell_of(px, py, g, &index)) occ[index] = 1;
+    float px, py;
+    pose_move(st, src[i].x, src[i].y, &px, &py);
+    const GridCell q = grid_cell(px, py, g);
+    if (q.in) occ[grid_index(q, g)] = 1;
 }
 
 __global__ void __launch_bounds__(256) k_field_columns(const uint8_t* __restrict__ occ, int threshold, int W, int H, int max_dist,
@@ -76,20 +62,20 @@ __global__ void __launch_bounds__(256) k_field_columns(const uint8_t* __restrict
     int d = max_dist;
 #pragma unroll 8
     for (int iy = 0; iy < H; iy++) {
-        d = occ[(size_t)iy * W + ix] >= threshold ? 0 : min(d + 1, max_dist);
+        d = column_step(d, occ[(size_t)iy * W + ix] >= threshold, max_dist);
         field[(size_t)iy * W + ix] = (uint16_t)d;
     }
     d = max_dist;
 #pragma unroll 8
     for (int iy = H - 1; iy >= 0; iy--) {
-        d = occ[(size_t)iy * W + ix] >= threshold ? 0 : min(d + 1, max_dist);
+        d = column_step(d, occ[(size_t)iy * W + ix] >= threshold, max_dist);
         field[(size_t)iy * W + ix] = (uint16_t)min((int)field[(size_t)iy * W + ix], d);
     }
 }
 
 __global__ void __launch_bounds__(kFieldRowTile) k_field_rows(uint16_t* field, int W, int max_dist)
 {
-    __shared__ uint16_t g2[kFieldMaxSide + 2 * kFieldMaxDist];   // [max_dist apron][W][max_dist apron]
+    __shared__ uint16_t g2[kGridMaxSide + 2 * kGridMaxDist];   // [max_dist apron][W][max_dist apron]
 
     uint16_t* row = field + (size_t)blockIdx.x * W;
     const uint32_t cap2 = (uint32_t)(max_dist * max_dist);
@@ -119,12 +105,12 @@ __global__ void __launch_bounds__(kFieldTB) k_field_score(const rr_radar_point* 
     const uint32_t m = min(*count, (uint32_t)max_points);
     const uint32_t cap2 = (uint32_t)(g.max_dist * g.max_dist), gate2 = (uint32_t)(g.gate * g.gate);
 
-    float c[kFieldK], s[kFieldK], tx[kFieldK], ty[kFieldK];
+    Pose2 st[kFieldK];
     uint32_t sum[kFieldK], n_in[kFieldK], n_hit[kFieldK];
 #pragma unroll
     for (int k = 0; k < kFieldK; k++) {
         const size_t h = (size_t)min(h0 + k, n_hyp - 1);          // a slot past the last hypothesis repeats it and is not stored
-        c[k] = states[4 * h]; s[k] = states[4 * h + 1]; tx[k] = states[4 * h + 2]; ty[k] = states[4 * h + 3];
+        st[k] = pose_of(states, h);
         sum[k] = 0; n_in[k] = 0; n_hit[k] = 0;
     }
 
@@ -133,37 +119,32 @@ __global__ void __launch_bounds__(kFieldTB) k_field_score(const rr_radar_point* 
     for (uint32_t i = lane; i < m; i += kFieldPointsTile) {
         float x_next = 0.0f, y_next = 0.0f;                       // the next step's point is fetched under this step's arithmetic
         if (i + kFieldPointsTile < m) { x_next = points[i + kFieldPointsTile].x; y_next = points[i + kFieldPointsTile].y; }
-        uint32_t index[kFieldK];
-        bool in[kFieldK];
+        GridCell q[kFieldK];
 #pragma unroll
         for (int k = 0; k < kFieldK; k++) {
-            const float px = (c[k] * x - s[k] * y) + tx[k];
-            const float py = (s[k] * x + c[k] * y) + ty[k];
-            in[k] = cell_of(px, py, g, &index[k]);
+            float px, py;
+            pose_move(st[k], x, y, &px, &py);
+            q[k] = grid_cell(px, py, g);
         }
         uint32_t d[kFieldK];
 #pragma unroll
-        for (int k = 0; k < kFieldK; k++) d[k] = field[index[k]];  // kFieldK independent gathers in flight
+        for (int k = 0; k < kFieldK; k++) d[k] = field[grid_index(q[k], g)];      // kFieldK independent gathers in flight
 #pragma unroll
         for (int k = 0; k < kFieldK; k++) {
-            sum[k] += in[k] ? d[k] : cap2;
-            n_in[k] += in[k] ? 1u : 0u;
-            n_hit[k] += (in[k] && d[k] <= gate2) ? 1u : 0u;
+            sum[k] += q[k].in ? d[k] : cap2;
+            n_in[k] += q[k].in ? 1u : 0u;
+            n_hit[k] += (q[k].in && d[k] <= gate2) ? 1u : 0u;
         }
         x = x_next; y = y_next;
     }
 
 #pragma unroll
     for (int k = 0; k < kFieldK; k++) {
-        unsigned long long t = sum[k];                            // the scan's total may pass 2^32
-        for (int e = 32; e > 0; e >>= 1) {
-            t += __shfl_xor(t, e, 64);
-            n_in[k] += __shfl_xor(n_in[k], e, 64);
-            n_hit[k] += __shfl_xor(n_hit[k], e, 64);
-        }
+        const unsigned long long t = wave_sum((unsigned long long)sum[k]);      // the scan's total may pass 2^32
+        const uint32_t in_all = wave_sum(n_in[k]), hit_all = wave_sum(n_hit[k]);
         if (lane == 0 && h0 + k < n_hyp) {
             rr_field_rec r;
-            r.sum_d2 = t; r.n_in = n_in[k]; r.n_hit = n_hit[k];
+            r.sum_d2 = t; r.n_in = in_all; r.n_hit = hit_all;
             recs[h0 + k] = r;                                     // one plain vector store per hypothesis
         }
     }

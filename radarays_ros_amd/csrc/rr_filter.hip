@@ -21,6 +21,7 @@
 #include "../../include/radarays_mi355.h"
 #include "rr_device.h"
 #include "rr_launch.h"
+#include "rr_pose2d.h"
 
 namespace rr {
 
@@ -101,7 +102,8 @@ __global__ void __launch_bounds__(kFltTB) k_flt_tile(const rr_field_rec* __restr
     block_incl_scan(s, lds, total);
     if (threadIdx.x == 0) cum[tile_last(blockIdx.x, n)] = total;
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { s2 += (u64)__shfl_xor(s2, off); best = min(best, (uint32_t)__shfl_xor(best, off)); }
+    for (int off = 32; off > 0; off >>= 1) best = min(best, (uint32_t)__shfl_xor(best, off));
+    s2 = wave_sum(s2);
     if ((threadIdx.x & 63) == 0) {
         if (s2) atomicAdd(reinterpret_cast<u64*>(&sum->sum_w2), s2);
         if (best != ~0u) atomicMin(&sum->best, best);
@@ -198,15 +200,13 @@ __global__ void __launch_bounds__(kFltTB) k_flt_move(const float4* __restrict__ 
     if (j >= n_out) return;
     const uint32_t a = min(ancestors ? ancestors[j] : j, n - 1);
     const float4 st = in[a];
-    const float c = st.x, s = st.y, tx = st.z, ty = st.w;
+    const Pose2 p = { st.x, st.y, st.z, st.w };
     const float nx = variate(key, j, 0) * sigma_xy, ny = variate(key, j, 1) * sigma_xy, t = variate(key, j, 2) * sigma_t;
-    const float ux = dx + nx, uy = dy + ny;
     float4 o;
-    o.z = (c * ux - s * uy) + tx;
-    o.w = (s * ux + c * uy) + ty;
+    pose_move(p, dx + nx, dy + ny, &o.z, &o.w);
     const float q = t * t, den = 1.0f + q, nc = (1.0f - q) / den, ns = (t + t) / den;
     const float rc = Dc * nc - Ds * ns, rs = Ds * nc + Dc * ns;
-    const float c1 = c * rc - s * rs, s1 = s * rc + c * rs;
+    const float c1 = p.c * rc - p.s * rs, s1 = p.s * rc + p.c * rs;
     const float m = sqrtf(c1 * c1 + s1 * s1);
     o.x = c1 / m;
     o.y = s1 / m;

@@ -20,6 +20,7 @@
 #include "../../include/radarays_mi355.h"
 #include "rr_device.h"
 #include "rr_launch.h"
+#include "rr_pose2d.h"
 
 #include <algorithm>
 
@@ -32,8 +33,7 @@ constexpr int kIcpPPT = 2;                           // source points a thread k
 constexpr int kIcpSrcTile = kIcpTB * kIcpPPT;        // 256
 constexpr int kIcpTgtTile = 1024;                    // (x, y) pairs of a target tile in LDS: 8 KB
 constexpr uint32_t kIcpNone = 0xFFFFFFFFu;
-constexpr float kIcpRange = 8192.0f;                 // a coordinate must be finite and below this in magnitude
-enum { S_N = 0, S_PX, S_PY, S_QX, S_QY, S_DOT, S_CROSS, S_SSE, S_COUNT };
+constexpr float kIcpRange = 8192.0f;                 // a coordinate must be finite and below this in magnitude (icp_accumulate relies on it)
 
 static_assert(sizeof(rr_icp_rec) == 48, "a record is 48 bytes");
 static_assert(sizeof(rr_radar_point) == 24, "x and y lead a 24-byte point");
@@ -41,31 +41,22 @@ static_assert(kIcpTgtTile % 2 == 0 && kIcpTB % 64 == 0, "targets are read in pai
 
 __device__ inline bool in_range(float v) { return fabsf(v) < kIcpRange; }      // false for NaN and infinities
 
-__device__ inline uint32_t source_count(const uint32_t* offsets, int f, int n_angles, int max_points, bool* truncated)
-{
-    const uint32_t total = offsets[(size_t)f * (n_angles + 1) + n_angles];
-    if (truncated) *truncated = total > (uint32_t)max_points;
-    return min(total, (uint32_t)max_points);
-}
-
 __global__ void __launch_bounds__(256) k_icp_init(const double* init, const uint32_t* offsets, int n_angles, int max_points, const uint32_t* tgt_count,
                                                   int max_tgt, rr_icp_rec* recs, long long* acc, int n_frames)
 {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= n_frames) return;
-    double c = 1.0, s = 0.0, tx = 0.0, ty = 0.0;
+    Pose2d st = { 1.0, 0.0, 0.0, 0.0 };
     uint32_t flags = 0;
     if (init) {
-        c = init[4 * (size_t)f]; s = init[4 * (size_t)f + 1]; tx = init[4 * (size_t)f + 2]; ty = init[4 * (size_t)f + 3];
-        const double h = sqrt(c * c + s * s);
-        if (h > 0.0 && h < (double)INFINITY) { c = c / h; s = s / h; }
-        else { flags |= RR_ICP_DEGENERATE; c = 1.0; s = 0.0; tx = 0.0; ty = 0.0; }
+        st = { init[4 * (size_t)f], init[4 * (size_t)f + 1], init[4 * (size_t)f + 2], init[4 * (size_t)f + 3] };
+        if (icp_start(st)) flags |= RR_ICP_DEGENERATE;
     }
     bool trunc;
-    source_count(offsets, f, n_angles, max_points, &trunc);
+    frame_count(offsets, f, n_angles, max_points, &trunc);
     if (trunc || *tgt_count > (uint32_t)max_tgt) flags |= RR_ICP_TRUNCATED;
     rr_icp_rec r;
-    r.c = c; r.s = s; r.tx = tx; r.ty = ty; r.sse = 0; r.n_matched = 0; r.flags = flags;
+    r.c = st.c; r.s = st.s; r.tx = st.tx; r.ty = st.ty; r.sse = 0; r.n_matched = 0; r.flags = flags;
     recs[f] = r;
     for (int k = 0; k < S_COUNT; k++) acc[(size_t)f * S_COUNT + k] = 0;
 }
@@ -77,24 +68,20 @@ __global__ void __launch_bounds__(kIcpTB) k_icp_pass(const rr_radar_point* point
     __shared__ __align__(16) float2 tile[kIcpTgtTile];
 
     const int f = blockIdx.y;
-    const uint32_t m = source_count(offsets, f, n_angles, max_points, nullptr);
+    const uint32_t m = frame_count(offsets, f, n_angles, max_points, nullptr);
     const uint32_t i0 = blockIdx.x * (uint32_t)kIcpSrcTile;
     if (i0 >= m) return;                                          // (the whole workgroup: no barrier has been met)
     const uint32_t nt = min(*tgt_count, (uint32_t)max_tgt);
     const rr_radar_point* src = points + (size_t)f * max_points;
 
-    const float cf = (float)recs[f].c, sf = (float)recs[f].s, txf = (float)recs[f].tx, tyf = (float)recs[f].ty;
+    const Pose2 st = pose_round(recs[f].c, recs[f].s, recs[f].tx, recs[f].ty);
     float px[kIcpPPT], py[kIcpPPT], best[kIcpPPT];
     uint32_t bj[kIcpPPT];
 #pragma unroll
     for (int e = 0; e < kIcpPPT; e++) {
         const uint32_t i = i0 + (uint32_t)e * kIcpTB + threadIdx.x;
         px[e] = py[e] = __uint_as_float(0x7FC00000u);             // a slot past the count: NaN never wins and is never matched
-        if (i < m) {
-            const float x = src[i].x, y = src[i].y;
-            px[e] = (cf * x - sf * y) + txf;
-            py[e] = (sf * x + cf * y) + tyf;
-        }
+        if (i < m) pose_move(st, src[i].x, src[i].y, &px[e], &py[e]);
         best[e] = INFINITY; bj[e] = kIcpNone;
     }
 
@@ -141,19 +128,12 @@ __global__ void __launch_bounds__(kIcpTB) k_icp_pass(const rr_radar_point* point
         uint32_t j = kIcpNone;
         if (in_range(px[e]) && in_range(py[e]) && bj[e] != kIcpNone && best[e] <= gate2) {
             j = bj[e];
-            const long long Px = (int32_t)rintf(px[e] * 256.0f), Py = (int32_t)rintf(py[e] * 256.0f);
-            const long long Qx = (int32_t)rintf(tgt[j].x * 256.0f), Qy = (int32_t)rintf(tgt[j].y * 256.0f);
-            sum[S_N] += 1;
-            sum[S_PX] += Px; sum[S_PY] += Py; sum[S_QX] += Qx; sum[S_QY] += Qy;
-            sum[S_DOT] += Px * Qx + Py * Qy;
-            sum[S_CROSS] += Px * Qy - Py * Qx;
-            sum[S_SSE] += (Px - Qx) * (Px - Qx) + (Py - Qy) * (Py - Qy);
+            icp_accumulate(sum, px[e], py[e], tgt[j].x, tgt[j].y);
         }
         if (corr) corr[(size_t)f * max_points + i] = j;
     }
 #pragma unroll
-    for (int k = 0; k < S_COUNT; k++)
-        for (int d = 32; d > 0; d >>= 1) sum[k] += __shfl_xor(sum[k], d, 64);
+    for (int k = 0; k < S_COUNT; k++) sum[k] = wave_sum(sum[k]);
     if ((threadIdx.x & 63) == 0 && sum[S_N] != 0) {
 #pragma unroll
         for (int k = 0; k < S_COUNT; k++) atomicAdd(acc + (size_t)f * S_COUNT + k, (unsigned long long)sum[k]);
@@ -172,23 +152,7 @@ __global__ void __launch_bounds__(256) k_icp_solve(rr_icp_rec* recs, long long* 
         r->n_matched = (uint32_t)S[S_N];
         return;
     }
-    const double N = (double)S[S_N], SPx = (double)S[S_PX], SPy = (double)S[S_PY], SQx = (double)S[S_QX], SQy = (double)S[S_QY];
-    const double Sdot = (double)S[S_DOT], Scross = (double)S[S_CROSS];
-    const double A = N * Sdot - (SPx * SQx + SPy * SQy);
-    const double B = N * Scross - (SPx * SQy - SPy * SQx);
-    const double h = sqrt(A * A + B * B);
-    if (S[S_N] < 2 || !(h > 0.0)) { r->flags |= RR_ICP_DEGENERATE; return; }
-    const double c = r->c, s = r->s, tx = r->tx, ty = r->ty;
-    const double dc = A / h, ds = B / h;
-    const double mpx = (SPx / N) / 256.0, mpy = (SPy / N) / 256.0, mqx = (SQx / N) / 256.0, mqy = (SQy / N) / 256.0;
-    const double dtx = mqx - (dc * mpx - ds * mpy);
-    const double dty = mqy - (ds * mpx + dc * mpy);
-    const double c1 = dc * c - ds * s;
-    const double s1 = ds * c + dc * s;
-    const double tx1 = (dc * tx - ds * ty) + dtx;
-    const double ty1 = (ds * tx + dc * ty) + dty;
-    const double nrm = sqrt(c1 * c1 + s1 * s1);
-    r->c = c1 / nrm; r->s = s1 / nrm; r->tx = tx1; r->ty = ty1;
+    if (icp_solve(S, *r)) r->flags |= RR_ICP_DEGENERATE;
 }
 
 }  // namespace

@@ -1,6 +1,7 @@
 // rr_images.hip -- the C ABI's image entry points: images in, records / points / images out.  PSNR scores and metrics against a reference image
 // (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), place recognition (rr_place.hip), point clouds and Cartesian images (rr_detect.hip), sweep compensation (rr_deskew.hip), scan matching (rr_icp.hip), the likelihood field (rr_field.hip), occupancy mapping (rr_occupancy.hip), the particle filter step (rr_filter.hip), map refinement (rr_refine.hip), the beam model (rr_cast.hip), object annotations (rr_notes.hip): each in a device form, which runs on the
 // caller's buffers and stream, and a host form, which drains c->stream and makes its round trip through a Stage over the context's pool (rr_stage.h).
+#include "rr_grid.h"
 #include "rr_stage.h"
 #include <algorithm>
 #include <cmath>
@@ -147,17 +148,25 @@ int check_icp(rr_ctx* c, const char* who, const void* points, const void* offset
 int check_grid_shape(rr_ctx* c, const std::string& w, const rr_field_config* g)
 {
     if (!g) return fail(c, -3, w + ": null config");
-    if (g->width < 1 || g->width > 4096 || g->height < 1 || g->height > 4096) return fail(c, -3, w + ": width and height must be 1..4096");
+    if (g->width < 1 || g->width > kGridMaxSide || g->height < 1 || g->height > kGridMaxSide)
+        return fail(c, -3, w + ": width and height must be 1.." + std::to_string(kGridMaxSide));
     if (!(std::isfinite(g->cell) && g->cell > 0.0f)) return fail(c, -3, w + ": cell must be finite and > 0");
     if (!(std::isfinite(g->x0) && std::isfinite(g->y0))) return fail(c, -3, w + ": x0 and y0 must be finite");
     return 0;
 }
 
-// ... and what the likelihood-field calls ask on top: the saturation and the gate
-int check_field_grid(rr_ctx* c, const std::string& w, const rr_field_config* g)
+// ... what the calls that read a distance table ask on top: the saturation (the ray calls stop here: they ignore the gate, so any value passes)
+int check_dist_grid(rr_ctx* c, const std::string& w, const rr_field_config* g)
 {
     int rc = check_grid_shape(c, w, g); if (rc) return rc;
-    if (g->max_dist < 1 || g->max_dist > 255) return fail(c, -3, w + ": max_dist must be 1..255");
+    if (g->max_dist < 1 || g->max_dist > kGridMaxDist) return fail(c, -3, w + ": max_dist must be 1.." + std::to_string(kGridMaxDist));
+    return 0;
+}
+
+// ... and what the likelihood-field and refinement calls ask on top of that: the gate
+int check_field_grid(rr_ctx* c, const std::string& w, const rr_field_config* g)
+{
+    int rc = check_dist_grid(c, w, g); if (rc) return rc;
     if (g->gate < 0 || g->gate > g->max_dist) return fail(c, -3, w + ": gate must be 0..max_dist");
     return 0;
 }
@@ -327,8 +336,7 @@ int check_cast(rr_ctx* c, const char* who, bool have_profile, const void* profil
     const std::string w(who);
     int rc = check_images(c, w, have_profile && states && dirs && field && have_out, "buffer", "n_hyp", 1, 1); if (rc) return rc;
     if (n_hyp < 1 || n_hyp > n_hyp_max) return fail(c, -3, w + ": n_hyp must be " + n_hyp_range);
-    rc = check_grid_shape(c, w, g); if (rc) return rc;
-    if (g->max_dist < 1 || g->max_dist > 255) return fail(c, -3, w + ": max_dist must be 1..255");      // (gate is ignored: any value passes)
+    rc = check_dist_grid(c, w, g); if (rc) return rc;
     if (!b) return fail(c, -3, w + ": null beam config");
     const int n_cells = c->cfg.n_cells;
     if (n_cells > 65535) return fail(c, -3, w + ": n_cells must be at most 65535");

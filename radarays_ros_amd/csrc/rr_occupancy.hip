@@ -14,15 +14,17 @@
 //                     the gather, the cells of a wave are neighbours in a row and look at a narrow fan of azimuths, so
 //                     a wave's gather falls into few cache lines of a row of 4 * n_angles bytes that stays in L1; and without a staged
 //                     chunk there is no barrier, no limit on n_angles and no chunk edge
-//   k_occ_hit         grid (point tiles, scans), one thread per point: k_field_raster's mapping and cell rule, then one integer atomicAdd
+//   k_occ_hit         grid (point tiles, scans), one thread per point: the state's move and the cell rule (rr_pose2d.h, rr_grid.h), then one integer atomicAdd
 //                     of l_hit.  Launched behind k_occ_free on the same stream: the read-modify-write there is not atomic
 //   k_occ_map         one thread per cell: clamp(128 + evidence, 0, 255)
 //
 // Every scalar travels as a kernel argument.  No scratch memory and no LDS in any kernel of the file.
 #include "../../include/radarays_mi355.h"
 #include "rr_device.h"
+#include "rr_grid.h"
 #include "rr_launch.h"
 #include "rr_polar.h"
+#include "rr_pose2d.h"
 
 namespace rr {
 
@@ -35,27 +37,15 @@ constexpr int kOccCellsPerGroup = kOccTB * kOccCellsPerThread;   // 1024
 static_assert(sizeof(rr_field_config) == 32 && sizeof(rr_occupancy_config) == 32, "the grid and the model are 32 bytes each");
 static_assert(sizeof(rr_radar_point) == 24, "x and y lead a 24-byte point");
 
-// the state of scan f rounded to f32; null: the identity
-struct State32 { float c, s, tx, ty; };
-__device__ inline State32 state_of(const double* states, size_t f)
-{
-    if (!states) return { 1.0f, 0.0f, 0.0f, 0.0f };
-    return { (float)states[4 * f], (float)states[4 * f + 1], (float)states[4 * f + 2], (float)states[4 * f + 3] };
-}
-
 __global__ void __launch_bounds__(256) k_occ_profile(const rr_radar_point* __restrict__ points, const uint32_t* __restrict__ offsets, int max_points,
                                                      PolarGrid G, int margin_bins, int max_free_bin, float* __restrict__ free2)
 {
     const int f = blockIdx.y, col = blockIdx.x * 256 + threadIdx.x;
     if (col >= G.n_angles) return;
-    const uint32_t* offs = offsets + (size_t)f * (G.n_angles + 1);
-    const uint32_t first = offs[col], next = offs[col + 1];
     long long fb = G.n_cells;                                    // no detection: free as far as max_free_bin allows
-    bool cut = false;                                            // every detection of the column lies past max_points: nothing is asserted
-    if (next > first) {
-        if (first < (uint32_t)max_points) fb = points[(size_t)f * max_points + first].bin;
-        else cut = true;
-    }
+    uint32_t bin;
+    bool cut;                                                    // every detection of the column lies past max_points: nothing is asserted
+    if (column_first_bin(points + (size_t)f * max_points, offsets + (size_t)f * (G.n_angles + 1), col, max_points, &bin, &cut)) fb = bin;
     const long long free_bins = cut ? 0 : min(max(fb - margin_bins, 0ll), (long long)max_free_bin);
     const float r = (float)((double)free_bins * G.resolution);
     free2[(size_t)f * G.n_angles + az_of_col(G, col)] = r * r;
@@ -74,20 +64,19 @@ __global__ void __launch_bounds__(kOccTB) k_occ_free(const float* __restrict__ f
     for (int e = 0; e < kOccCellsPerThread; e++) {
         const uint32_t q = min(q0 + e, cells - 1);               // a slot past the last cell repeats it and is not stored
         const uint32_t iy = q / (uint32_t)g.width, ix = q - iy * (uint32_t)g.width;
-        qx[e] = g.x0 + ((float)ix + 0.5f) * g.cell;
-        qy[e] = g.y0 + ((float)iy + 0.5f) * g.cell;
+        qx[e] = cell_centre(g.x0, g.cell, ix);
+        qy[e] = cell_centre(g.y0, g.cell, iy);
         n_free[e] = 0;
     }
     for (int f = 0; f < n_frames; f++) {
-        const State32 st = state_of(states, (size_t)f);          // wave-uniform
+        const Pose2 st = pose_of(states, (size_t)f);             // wave-uniform
         const float* prof = free2 + (size_t)f * G.n_angles;
         int a[kOccCellsPerThread];
         float rho2[kOccCellsPerThread];
 #pragma unroll
         for (int e = 0; e < kOccCellsPerThread; e++) {
-            const float dx = qx[e] - st.tx, dy = qy[e] - st.ty;
-            const float px = st.c * dx + st.s * dy;
-            const float py = st.c * dy - st.s * dx;
+            float px, py;
+            pose_unmove(st, qx[e], qy[e], &px, &py);
             a[e] = az_nearest(G, az_coord(G, atan2f(py, px)));   // always inside [0, n_angles), whatever px and py are
             rho2[e] = px * px + py * py;
         }
@@ -109,30 +98,19 @@ __global__ void __launch_bounds__(kOccTB) k_occ_free(const float* __restrict__ f
     }
 }
 
-// the cell rule of the header (rr_field.hip's): the comparisons are made in float, before any conversion to int; a NaN or an infinity fails them
-__device__ inline bool cell_of(float px, float py, const rr_field_config& g, uint32_t* index)
-{
-    const float u = (px - g.x0) / g.cell, v = (py - g.y0) / g.cell;
-    const bool in = u >= 0.0f && u < (float)g.width && v >= 0.0f && v < (float)g.height;
-    const int ix = in ? (int)floorf(u) : 0, iy = in ? (int)floorf(v) : 0;
-    *index = (uint32_t)(iy * g.width + ix);
-    return in;
-}
-
 __global__ void __launch_bounds__(256) k_occ_hit(const rr_radar_point* __restrict__ points, const uint32_t* __restrict__ offsets, int n_angles,
                                                  int max_points, const double* __restrict__ states, rr_field_config g, int l_hit, int32_t* evidence)
 {
     const int f = blockIdx.y;
-    const uint32_t m = min(offsets[(size_t)f * (n_angles + 1) + n_angles], (uint32_t)max_points);
+    const uint32_t m = frame_count(offsets, f, n_angles, max_points, nullptr);
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= m) return;
-    const State32 st = state_of(states, (size_t)f);
+    const Pose2 st = pose_of(states, (size_t)f);
     const rr_radar_point* src = points + (size_t)f * max_points;
-    const float x = src[i].x, y = src[i].y;
-    const float px = (st.c * x - st.s * y) + st.tx;
-    const float py = (st.s * x + st.c * y) + st.ty;
-    uint32_t index;
-    if (cell_of(px, py, g, &index)) atomicAdd(evidence + index, l_hit);
+    float px, py;
+    pose_move(st, src[i].x, src[i].y, &px, &py);
+    const GridCell q = grid_cell(px, py, g);
+    if (q.in) atomicAdd(evidence + grid_index(q, g), l_hit);
 }
 
 __global__ void __launch_bounds__(256) k_occ_map(const int32_t* __restrict__ evidence, uint32_t cells, uint8_t* __restrict__ occ)

@@ -1,5 +1,5 @@
 // rr_polar.h -- the geometry of a polar image [n_cells][n_angles], stated once for the detectors, the annotations and the three Cartesian
-// resamplers (rr_detect.hip, rr_notes.hip, rr_deskew.hip).  Image column col holds azimuth index a = col - scroll (mod n_angles), which
+// resamplers (rr_detect.hip, rr_notes.hip, rr_deskew.hip) and for the scan profiles of the map kernels (rr_occupancy.hip, rr_cast.hip).  Image column col holds azimuth index a = col - scroll (mod n_angles), which
 // lies a steps of theta_inc from theta_min; range bin b lies at (b + 0.5) * resolution.  A point at yaw phi and range rho has the continuous
 // coordinates u = (phi - theta_min) / theta_inc (mod n_angles) and v = rho / res - 0.5.  All f32 but the bin's range, nothing fused.
 #pragma once
@@ -32,6 +32,17 @@ __device__ inline int col_of_az(const PolarGrid& G, int a)
 }
 __device__ inline float az_theta(const PolarGrid& G, int a) { return G.theta_min + (float)a * G.theta_inc; }
 template <class I> __device__ inline float bin_range(const PolarGrid& G, I b) { return (float)(((double)b + 0.5) * G.resolution); }
+
+// the first detection of image column col of one frame's point list (the points of a column are sorted by bin; offs: the frame's n_angles + 1
+// offsets): true and its bin.  False where the column has no detection, and with *cut where every detection of it lies past max_points
+__device__ inline bool column_first_bin(const rr_radar_point* frame_points, const uint32_t* offs, int col, int max_points, uint32_t* bin, bool* cut)
+{
+    const uint32_t first = offs[col], next = offs[col + 1];
+    *cut = next > first && first >= (uint32_t)max_points;
+    if (next <= first || *cut) return false;
+    *bin = frame_points[first].bin;
+    return true;
+}
 
 // the azimuth coordinate of a yaw, always in [0, n_angles)
 __device__ inline float az_coord(const PolarGrid& G, float phi)

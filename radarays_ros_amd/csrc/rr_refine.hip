@@ -23,7 +23,9 @@
 // Every scalar travels as a kernel argument.  No scratch memory; LDS only in k_near_rows (the staged row).
 #include "../../include/radarays_mi355.h"
 #include "rr_device.h"
+#include "rr_grid.h"
 #include "rr_launch.h"
+#include "rr_pose2d.h"
 
 namespace rr {
 
@@ -34,9 +36,7 @@ constexpr int kRefK = 4;                                         // hypotheses a
 constexpr int kRefHypsPerGroup = (kRefTB / 64) * kRefK;          // 16
 constexpr int kRefPointsTile = 64;                               // points a wave takes per step: one per lane
 constexpr int kNearRowTile = 256;                                // threads of a k_near_rows workgroup = cells of a row per sweep
-constexpr int kNearMaxSide = 4096, kNearMaxDist = 255;
 constexpr uint32_t kNearNone = 0xFFFFFFFFu;
-enum { S_N = 0, S_PX, S_PY, S_QX, S_QY, S_DOT, S_CROSS, S_SSE, S_COUNT };
 
 static_assert(sizeof(rr_field_config) == 32 && sizeof(rr_icp_rec) == 48, "the grid is 32 bytes, a record 48");
 static_assert(sizeof(rr_radar_point) == 24, "x and y lead a 24-byte point");
@@ -51,13 +51,13 @@ __global__ void __launch_bounds__(256) k_near_columns(const uint8_t* __restrict_
     int d = max_dist;                                            // distance down to the nearest occupied cell at or below iy (lower jy)
 #pragma unroll 8
     for (int iy = 0; iy < H; iy++) {
-        d = occ[(size_t)iy * W + ix] >= threshold ? 0 : min(d + 1, max_dist);
+        d = column_step(d, occ[(size_t)iy * W + ix] >= threshold, max_dist);
         near[(size_t)iy * W + ix] = d < max_dist ? -d : max_dist;
     }
     d = max_dist;                                                // ... and up to the nearest one at or above iy
 #pragma unroll 8
     for (int iy = H - 1; iy >= 0; iy--) {
-        d = occ[(size_t)iy * W + ix] >= threshold ? 0 : min(d + 1, max_dist);
+        d = column_step(d, occ[(size_t)iy * W + ix] >= threshold, max_dist);
         const int lo = near[(size_t)iy * W + ix];                // <= 0, or max_dist: nothing within reach below
         if (lo == max_dist || d < -lo) near[(size_t)iy * W + ix] = d;   // a tie (d == -lo) keeps the lower jy
     }
@@ -65,7 +65,7 @@ __global__ void __launch_bounds__(256) k_near_columns(const uint8_t* __restrict_
 
 __global__ void __launch_bounds__(kNearRowTile) k_near_rows(uint32_t* near, int W, int max_dist)
 {
-    __shared__ int16_t off[kNearMaxSide + 2 * kNearMaxDist];     // [max_dist apron][W][max_dist apron]
+    __shared__ int16_t off[kGridMaxSide + 2 * kGridMaxDist];     // [max_dist apron][W][max_dist apron]
 
     const int iy = blockIdx.x;
     uint32_t* row = near + (size_t)iy * W;
@@ -109,26 +109,24 @@ __global__ void __launch_bounds__(kRefTB) k_refine(const rr_radar_point* __restr
     if (h0 >= n_hyp) return;                                      // (the whole wave; the kernel has no barrier)
     const uint32_t total = *count, m = min(total, (uint32_t)max_points);
     const int gate2 = g.gate * g.gate;
-    const float inv_w = 1.0f / (float)g.width, fw = (float)g.width, fh = (float)g.height;
+    const float inv_w = 1.0f / (float)g.width;
 
-    double c[kRefK], s[kRefK], tx[kRefK], ty[kRefK];
+    Pose2d st[kRefK];
     uint32_t flags[kRefK];
 #pragma unroll
     for (int k = 0; k < kRefK; k++) {
         const size_t h = (size_t)min(h0 + k, n_hyp - 1);          // a slot past the last hypothesis repeats it and is not stored
-        c[k] = init[4 * h]; s[k] = init[4 * h + 1]; tx[k] = init[4 * h + 2]; ty[k] = init[4 * h + 3];
+        st[k] = { init[4 * h], init[4 * h + 1], init[4 * h + 2], init[4 * h + 3] };
         flags[k] = total > (uint32_t)max_points ? RR_ICP_TRUNCATED : 0u;
-        const double hyp = sqrt(c[k] * c[k] + s[k] * s[k]);
-        if (hyp > 0.0 && hyp < (double)INFINITY) { c[k] = c[k] / hyp; s[k] = s[k] / hyp; }
-        else { flags[k] |= RR_ICP_DEGENERATE; c[k] = 1.0; s[k] = 0.0; tx[k] = 0.0; ty[k] = 0.0; }
+        if (icp_start(st[k])) flags[k] |= RR_ICP_DEGENERATE;
     }
 
     for (int it = 0; it <= iterations; it++) {
-        float cf[kRefK], sf[kRefK], txf[kRefK], tyf[kRefK];
+        Pose2 stf[kRefK];
         long long sum[kRefK][S_COUNT];
 #pragma unroll
         for (int k = 0; k < kRefK; k++) {
-            cf[k] = (float)c[k]; sf[k] = (float)s[k]; txf[k] = (float)tx[k]; tyf[k] = (float)ty[k];
+            stf[k] = pose_round(st[k].c, st[k].s, st[k].tx, st[k].ty);
 #pragma unroll
             for (int e = 0; e < S_COUNT; e++) sum[k][e] = 0;
         }
@@ -139,35 +137,22 @@ __global__ void __launch_bounds__(kRefTB) k_refine(const rr_radar_point* __restr
             float x_next = 0.0f, y_next = 0.0f;                   // the next step's point is fetched under this step's arithmetic
             if (i + kRefPointsTile < m) { x_next = points[i + kRefPointsTile].x; y_next = points[i + kRefPointsTile].y; }
             float px[kRefK], py[kRefK];
-            int ix[kRefK], iy[kRefK];
-            bool in[kRefK];
+            GridCell q[kRefK];
 #pragma unroll
             for (int k = 0; k < kRefK; k++) {
-                px[k] = (cf[k] * x - sf[k] * y) + txf[k];
-                py[k] = (sf[k] * x + cf[k] * y) + tyf[k];
-                const float u = (px[k] - g.x0) / g.cell, v = (py[k] - g.y0) / g.cell;      // the cell rule of the header, in float
-                in[k] = u >= 0.0f && u < fw && v >= 0.0f && v < fh;
-                ix[k] = in[k] ? (int)floorf(u) : 0; iy[k] = in[k] ? (int)floorf(v) : 0;    // (cell 0 for a point not IN GRID: it may be read)
+                pose_move(stf[k], x, y, &px[k], &py[k]);
+                q[k] = grid_cell(px[k], py[k], g);
             }
             uint32_t nk[kRefK];
 #pragma unroll
-            for (int k = 0; k < kRefK; k++) nk[k] = near[iy[k] * g.width + ix[k]];         // kRefK independent gathers in flight
+            for (int k = 0; k < kRefK; k++) nk[k] = near[grid_index(q[k], g)];             // kRefK independent gathers in flight
 #pragma unroll
             for (int k = 0; k < kRefK; k++) {
                 int jx, jy;
                 split_index(nk[k], g.width, inv_w, &jx, &jy);
-                const int ddx = ix[k] - jx, ddy = iy[k] - jy;
-                if (in[k] && nk[k] != kNearNone && ddx * ddx + ddy * ddy <= gate2) {
-                    const float qx = g.x0 + ((float)jx + 0.5f) * g.cell, qy = g.y0 + ((float)jy + 0.5f) * g.cell;
-                    const int32_t Px = (int32_t)rintf(px[k] * 256.0f), Py = (int32_t)rintf(py[k] * 256.0f);
-                    const int32_t Qx = (int32_t)rintf(qx * 256.0f), Qy = (int32_t)rintf(qy * 256.0f);
-                    const int32_t ex = Px - Qx, ey = Py - Qy;     // |P|, |Q| <= 2^21: every product below fits 32 x 32 -> 64
-                    sum[k][S_N] += 1;
-                    sum[k][S_PX] += Px; sum[k][S_PY] += Py; sum[k][S_QX] += Qx; sum[k][S_QY] += Qy;
-                    sum[k][S_DOT] += (long long)Px * Qx + (long long)Py * Qy;
-                    sum[k][S_CROSS] += (long long)Px * Qy - (long long)Py * Qx;
-                    sum[k][S_SSE] += (long long)ex * ex + (long long)ey * ey;
-                }
+                const int ddx = q[k].ix - jx, ddy = q[k].iy - jy;
+                if (q[k].in && nk[k] != kNearNone && ddx * ddx + ddy * ddy <= gate2)
+                    icp_accumulate(sum[k], px[k], py[k], cell_centre(g.x0, g.cell, jx), cell_centre(g.y0, g.cell, jy));
             }
             x = x_next; y = y_next;
         }
@@ -176,35 +161,16 @@ __global__ void __launch_bounds__(kRefTB) k_refine(const rr_radar_point* __restr
         for (int k = 0; k < kRefK; k++) {
             long long S[S_COUNT];
 #pragma unroll
-            for (int e = 0; e < S_COUNT; e++) {
-                S[e] = sum[k][e];
-                for (int d = 32; d > 0; d >>= 1) S[e] += __shfl_xor(S[e], d, 64);          // the total in every lane
-            }
+            for (int e = 0; e < S_COUNT; e++) S[e] = wave_sum(sum[k][e]);                  // the total in every lane
             if (it == iterations) {
                 if (lane == 0 && h0 + k < n_hyp) {
                     rr_icp_rec r;
-                    r.c = c[k]; r.s = s[k]; r.tx = tx[k]; r.ty = ty[k]; r.sse = S[S_SSE]; r.n_matched = (uint32_t)S[S_N]; r.flags = flags[k];
+                    r.c = st[k].c; r.s = st[k].s; r.tx = st[k].tx; r.ty = st[k].ty; r.sse = S[S_SSE]; r.n_matched = (uint32_t)S[S_N]; r.flags = flags[k];
                     recs[h0 + k] = r;
                 }
                 continue;
             }
-            // the SOLVE of the scan matcher (rr_icp.hip: k_icp_solve), letter for letter
-            const double N = (double)S[S_N], SPx = (double)S[S_PX], SPy = (double)S[S_PY], SQx = (double)S[S_QX], SQy = (double)S[S_QY];
-            const double Sdot = (double)S[S_DOT], Scross = (double)S[S_CROSS];
-            const double A = N * Sdot - (SPx * SQx + SPy * SQy);
-            const double B = N * Scross - (SPx * SQy - SPy * SQx);
-            const double h = sqrt(A * A + B * B);
-            if (S[S_N] < 2 || !(h > 0.0)) { flags[k] |= RR_ICP_DEGENERATE; continue; }
-            const double dc = A / h, ds = B / h;
-            const double mpx = (SPx / N) / 256.0, mpy = (SPy / N) / 256.0, mqx = (SQx / N) / 256.0, mqy = (SQy / N) / 256.0;
-            const double dtx = mqx - (dc * mpx - ds * mpy);
-            const double dty = mqy - (ds * mpx + dc * mpy);
-            const double c1 = dc * c[k] - ds * s[k];
-            const double s1 = ds * c[k] + dc * s[k];
-            const double tx1 = (dc * tx[k] - ds * ty[k]) + dtx;
-            const double ty1 = (ds * tx[k] + dc * ty[k]) + dty;
-            const double nrm = sqrt(c1 * c1 + s1 * s1);
-            c[k] = c1 / nrm; s[k] = s1 / nrm; tx[k] = tx1; ty[k] = ty1;
+            if (icp_solve(S, st[k])) flags[k] |= RR_ICP_DEGENERATE;                        // the SOLVE of the scan matcher (rr_pose2d.h)
         }
     }
 }
