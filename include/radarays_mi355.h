@@ -1446,6 +1446,64 @@ int rr_score_beams(rr_ctx* ctx, const uint16_t* first_bin, const float* states, 
  * (tests put counts at the edges) */
 void rr_cast_tile_sizes(int* angles_tile, int* hyps_per_wave, int* hyps_per_group);
 
+/* ---- mesh maps: the scene's triangles sliced into the grid map (rr_slice.hip) -------------------------------------------------
+ * The way from the mesh a context holds to the grid the map calls work on: every cell of an rr_field_config grid that some posed triangle
+ * touches inside a height band [z_lo, z_hi] is marked, in the uint8 convention of rr_rasterize_points, so rr_distance_field,
+ * rr_nearest_field and everything behind them take the result as it is.  A slice is geometry only: no occlusion, no visibility, no
+ * materials.  The reference has no such step: parity is UNPINNED and everything below is the build's own definition (a numpy restatement in
+ * tests/slice_ref.py checks the kernels byte for byte).  All f32 arithmetic is un-fused; every result is independent of order.
+ * GEOMETRY.  The context's current scene: every face's rest corners moved by its object's pose, with the arithmetic of the dynamic scenes
+ * (rr_set_object_poses).  What the context holds on the device is iterated: its triangle records; a face that the tree builders cut has
+ * several records, which write the same values.  An empty mesh writes nothing and returns 0.
+ * CELL SPACE.  A corner (x, y, z) has u = (x - x0) / cell and v = (y - y0) / cell, the grid's rule above; z stays in metres.  A record
+ * with a u, v or z that is not finite is skipped.
+ * BAND.  z_lo <= z_hi, both finite; z_lo == z_hi is a plane.  A record is rejected on the raw values, with no arithmetic, if
+ * max(za, zb, zc) < z_lo or min(za, zb, zc) > z_hi.
+ * CELL PREDICATE.  Cell (ix, iy) is marked by a record iff no axis of a separating-axis test separates the triangle in (u, v, z) from the
+ * CLOSED box [ix, ix+1] x [iy, iy+1] x [z_lo, z_hi].  Touching counts as overlap: a reject needs a strict inequality that holds, so a NaN
+ * (an overflowed product of huge coordinates) rejects nothing.  The axes, and the order of operations:
+ *     box axes    z as under BAND; u: rejected iff max(u) < (float)ix or min(u) > (float)(ix + 1), on the raw values; v likewise
+ *     per record  edges e0 = p1 - p0, e1 = p2 - p1, e2 = p0 - p2 from the RAW corners p_k = (u_k, v_k, z_k); the normal n = e0 x e1:
+ *                 nu = e0v*e1z - e0z*e1v      nv = e0z*e1u - e0u*e1z      nz = e0u*e1v - e0v*e1u
+ *                 cz = (z_lo + z_hi) * 0.5f   hz = (z_hi - z_lo) * 0.5f   and for a cell hu = hv = 0.5f
+ *     per cell    the corners are centred on the cell first: c_k = (u_k - (ix + 0.5f), v_k - (iy + 0.5f), z_k - cz); then the products
+ *     normal      d = (nu*c0u + nv*c0v) + nz*c0z      r = (hu*|nu| + hv*|nv|) + hz*|nz|      rejected iff d > r or d < -r
+ *     edge j      against the corners a = c_j and b = c_(j+2) (the third projects as a does); with e = e_j, each rejected iff both
+ *                 projections are > r or both are < -r:
+ *                 (1,0,0) x e:   ez*av - ev*az,  ez*bv - ev*bz      r = hv*|ez| + hz*|ev|
+ *                 (0,1,0) x e:   eu*az - ez*au,  eu*bz - ez*bu      r = hu*|ez| + hz*|eu|
+ *                 (0,0,1) x e:   ev*au - eu*av,  ev*bu - eu*bv      r = hu*|ev| + hv*|eu|
+ * An axis that vanishes (a zero-area or collinear triangle) gives 0 > 0: it rejects nothing and the other axes decide.
+ * CANDIDATE CELLS.  The u and v box axes pass exactly for ix in ceil(min u) - 1 .. floor(max u) and iy likewise (the closed box of the cell
+ * below an integer minimum touches it), clamped to the grid in float before any conversion to int.  The definition is the predicate over
+ * EVERY cell of the grid; the kernels walk the candidates only, and their tile prefilter never drops a cell the predicate marks (DESIGN.md
+ * §28).
+ * OUTPUTS.  d_occ_u8[iy][ix] = 1 for every marked cell: ones only, into a buffer that the caller zeroed or that already holds a map, so
+ * the call composes with rr_rasterize_points and with several bands or calls in any order.  With d_object_u32: d_object_u32[iy][ix] =
+ * min(what it held, object id) over all records that mark the cell; the caller fills it with 0xFFFFFFFF.  d_skip_u8 [n_objects]: a
+ * non-zero byte leaves that object's records out entirely (a static prior map without the parked and moving objects).
+ * The device form enqueues on `stream` (NULL: the context's) with no host round trip: a 4-byte memset and two launches.  It reads the scene
+ * the context holds when the kernels run, so the CALLER orders it against rr_set_mesh*, rr_set_object_poses, rr_update_vertices and
+ * rr_rebuild_tree (they drain the device before they change it; a slice must not be enqueued while one of them runs).  It keeps a
+ * context-owned list of one word per record, one per stream it has been called on: calls on different streams may overlap.  The host form
+ * stages through context-owned buffers, is synchronous and ACCUMULATES: it reads occ_u8 and object_u32 as well as writing them.
+ * Refused with a message and nothing written: -1 for a null ctx; -2 when no mesh has been set; -3 for a null config, grid or d_occ_u8, a
+ * grid field outside rr_field_config's stated ranges, z_lo or z_hi not finite or z_lo > z_hi, flags != 0, or a d_object_u32 that is not
+ * 4-byte aligned.
+ * LIMITS.  A cell column is marked or not: no coverage fraction, no 3-D voxels.  rr_multi has no such call. */
+typedef struct rr_slice_config {   /* 16 B */
+    float    z_lo, z_hi;   /* the band in metres, map frame: finite, z_lo <= z_hi */
+    uint32_t flags;        /* must be 0 */
+    int32_t  reserved_;
+} rr_slice_config;
+int rr_slice_mesh_device(rr_ctx* ctx, const rr_slice_config* slice, const rr_field_config* cfg, const uint8_t* d_skip_u8_or_NULL /*[n_objects]*/,
+                         uint8_t* d_occ_u8 /*[height][width]*/, uint32_t* d_object_u32_or_NULL /*[height][width]*/, void* stream);
+int rr_slice_mesh(rr_ctx* ctx, const rr_slice_config* slice, const rr_field_config* cfg, const uint8_t* skip_u8_or_NULL, uint8_t* occ_u8,
+                  uint32_t* object_u32_or_NULL);                                        /* host buffers, synchronous, accumulating */
+/* the blocking of the kernels: the largest candidate box (in cells) a record's own thread tests, the side of a tile of k_slice_large, the
+ * threads of a workgroup of either kernel (tests put boxes, grid sides and record counts at the edges) */
+void rr_slice_tile_sizes(int* small_cells, int* tile_side, int* group_size);
+
 /* ---- several GPUs of one node behind one object (SURVEY.md §8b "Threading", §8e) -------------------------
  * The reference creates ONE backend object per process (src/radar_simulator.cpp:145-176) and fans out inside it
  * (OpenMP over azimuths, RadarCPU.cpp:155).  rr_multi is that object for n GPUs: one rr_ctx per device, mesh and

@@ -624,6 +624,31 @@ public:
         }
         return true;
     }
+    // Mesh maps (rr_slice.hip; include/radarays_mi355.h): the loaded mesh itself as the grid map [height][width] -- a 1 in every cell that some
+    // triangle, under its object's current pose, touches inside the height band [z_lo, z_hi] (metres, map frame), on the first device's
+    // context.  skip_objects: object ids left out entirely (the parked and moving objects of a dynamic scene); objects (or null): receives
+    // the smallest object id per cell, 0xFFFFFFFF where nothing marks it; occ: a map [height][width] to accumulate into, or empty.  The map
+    // goes on to rr_distance_field (scorePoses, castMap, scoreBeams) or buildNearestField (refinePoses) as it is.  Empty on error
+    std::vector<uint8_t> buildMeshMap(const rr_field_config& cfg, float z_lo, float z_hi, const std::vector<uint32_t>& skip_objects = {},
+                                      std::vector<uint32_t>* objects = nullptr, const std::vector<uint8_t>& occ = {})
+    {
+        const size_t cells = cfg.width > 0 && cfg.height > 0 ? (size_t)cfg.width * (size_t)cfg.height : 0;
+        if (!occ.empty() && occ.size() != cells) { m_err = "buildMeshMap: the map to accumulate into must be [height][width]"; return {}; }
+        std::vector<uint8_t> skip(skip_objects.empty() ? 0 : m_n_objects, 0);
+        for (uint32_t o : skip_objects) {
+            if (o >= m_n_objects) { m_err = "buildMeshMap: skip_objects names an object the mesh does not have"; return {}; }
+            skip[o] = 1;
+        }
+        std::vector<uint8_t> map = occ.empty() ? std::vector<uint8_t>(cells, 0) : occ;
+        if (objects) objects->assign(cells, 0xFFFFFFFFu);
+        const rr_slice_config band = { z_lo, z_hi, 0, 0 };
+        if (rr_slice_mesh(m_ctx, &band, &cfg, skip.empty() ? nullptr : skip.data(), map.data(), objects ? objects->data() : nullptr)) {
+            fail();
+            if (objects) objects->clear();
+            return {};
+        }
+        return map;
+    }
     // one observed scan against hypothesis states [n][4] f32 (each the scan's sensor frame into the map frame) and a field of
     // buildLikelihoodField: one rr_field_rec per hypothesis, lower sum_d2 is better.  Empty on error
     std::vector<rr_field_rec> scorePoses(const std::vector<rr_radar_point>& scan, const std::vector<float>& states, const std::vector<uint16_t>& field,

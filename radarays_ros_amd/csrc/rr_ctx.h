@@ -203,6 +203,8 @@ struct rr_ctx {
     // rr_register_points_device: the eight int64 sums per frame, one buffer per stream it has been called on (icp_mu guards the map, not the
     // buffers: calls on one stream are ordered by that stream)
     std::map<hipStream_t, DevBuf<long long>> icp_acc; std::mutex icp_mu;
+    // rr_slice_mesh_device: the large list (its counter, then one word per triangle record), one buffer per stream like icp_acc
+    std::map<hipStream_t, DevBuf<uint32_t>> slice_list; std::mutex slice_mu;
     // rr_align_images_device: one chunk's curves (when the caller gives no buffer) and sums, the records
     DevBuf<long long> d_align_curve; DevBuf<unsigned long long> d_align_sums; DevBuf<rr_align_record> d_align_rec;
     // rr_shift_images_device: one chunk's surface (when the caller gives no buffer) and sums, the reference's column and box sums, the records

@@ -1,5 +1,5 @@
 // rr_grid.h -- the grid map of rr_field_config, stated once for the likelihood field, occupancy mapping, map refinement and the beam model
-// (rr_field.hip, rr_occupancy.hip, rr_refine.hip, rr_cast.hip).  A map-frame point (px, py) has the cell coordinates u = (px - x0) / cell and
+// (rr_field.hip, rr_occupancy.hip, rr_refine.hip, rr_cast.hip) and for the mesh slicer (rr_slice.hip).  A map-frame point (px, py) has the cell coordinates u = (px - x0) / cell and
 // v = (py - y0) / cell; it is IN GRID iff 0 <= u < width and 0 <= v < height, compared in float before any conversion to int, and then lies in
 // cell (floor u, floor v), whose linear index is iy * width + ix and whose centre is x0 + (ix + 0.5) * cell.  All f32, nothing fused.
 #pragma once
@@ -12,9 +12,11 @@ constexpr int kGridMaxSide = 4096, kGridMaxDist = 255;           // width and he
 
 // the cell rule of the header.  A NaN or an infinity fails the comparisons; a point that is not IN GRID gets cell (0, 0), an address that may be read
 struct GridCell { bool in; int ix, iy; };
+// the cell coordinate of a map-frame coordinate along one axis: origin is x0 or y0 (the mesh slicer takes a triangle's corners through it)
+__device__ inline float cell_coord(float p, float origin, float cell) { return (p - origin) / cell; }
 __device__ inline GridCell grid_cell(float px, float py, const rr_field_config& g)
 {
-    const float u = (px - g.x0) / g.cell, v = (py - g.y0) / g.cell;
+    const float u = cell_coord(px, g.x0, g.cell), v = cell_coord(py, g.y0, g.cell);
     const bool in = u >= 0.0f && u < (float)g.width && v >= 0.0f && v < (float)g.height;
     return { in, in ? (int)floorf(u) : 0, in ? (int)floorf(v) : 0 };
 }

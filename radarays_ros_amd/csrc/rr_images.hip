@@ -1,5 +1,5 @@
 // rr_images.hip -- the C ABI's image entry points: images in, records / points / images out.  PSNR scores and metrics against a reference image
-// (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), place recognition (rr_place.hip), point clouds and Cartesian images (rr_detect.hip), sweep compensation (rr_deskew.hip), scan matching (rr_icp.hip), the likelihood field (rr_field.hip), occupancy mapping (rr_occupancy.hip), the particle filter step (rr_filter.hip), map refinement (rr_refine.hip), the beam model (rr_cast.hip), object annotations (rr_notes.hip): each in a device form, which runs on the
+// (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), place recognition (rr_place.hip), point clouds and Cartesian images (rr_detect.hip), sweep compensation (rr_deskew.hip), scan matching (rr_icp.hip), the likelihood field (rr_field.hip), occupancy mapping (rr_occupancy.hip), the particle filter step (rr_filter.hip), map refinement (rr_refine.hip), the beam model (rr_cast.hip), mesh maps (rr_slice.hip), object annotations (rr_notes.hip): each in a device form, which runs on the
 // caller's buffers and stream, and a host form, which drains c->stream and makes its round trip through a Stage over the context's pool (rr_stage.h).
 #include "rr_grid.h"
 #include "rr_stage.h"
@@ -349,6 +349,21 @@ int check_cast(rr_ctx* c, const char* who, bool have_profile, const void* profil
     if ((uintptr_t)states % 4 != 0 || (uintptr_t)dirs % 4 != 0 || (uintptr_t)field % 2 != 0 || (uintptr_t)profile % 2 != 0 || (uintptr_t)ranges % 2 != 0 ||
         (uintptr_t)recs % 8 != 0)
         return fail(c, -3, w + ": states and dirs must be 4-byte, the 16-bit tables 2-byte and the records 8-byte aligned");
+    return 0;
+}
+
+// the refusals of rr_slice_mesh_device / rr_slice_mesh: a mesh, no config of the radar
+int check_slice(rr_ctx* c, const char* who, const rr_slice_config* sc, const rr_field_config* g, const void* occ, const void* objects)
+{
+    if (!c) return -1;
+    if (!c->have_mesh) return fail(c, -2, "rr_set_mesh has not been called");
+    const std::string w(who);
+    if (!sc) return fail(c, -3, w + ": null slice config");
+    int rc = check_field_grid(c, w, g); if (rc) return rc;
+    if (!occ) return fail(c, -3, w + ": null buffer");
+    if (!(std::isfinite(sc->z_lo) && std::isfinite(sc->z_hi) && sc->z_lo <= sc->z_hi)) return fail(c, -3, w + ": z_lo and z_hi must be finite and z_lo <= z_hi");
+    if (sc->flags != 0) return fail(c, -3, w + ": flags must be 0");
+    if ((uintptr_t)objects % 4 != 0) return fail(c, -3, w + ": the object plane must be 4-byte aligned");
     return 0;
 }
 
@@ -1382,6 +1397,45 @@ int rr_score_beams(rr_ctx* c, const uint16_t* first_bin, const float* states, in
     RR_HIP(c, st.up(field_u16, cells, d_field));
     RR_HIP(c, st.hold(recs, n, d_recs));
     rc = rr_score_beams_device(c, d_first, d_states, n_hyp, d_dirs, d_field, cfg, beam, d_recs, c->stream); if (rc) return rc;
+    return st.commit();
+}
+
+// ---- mesh maps (rr_slice.hip) ---------------------------------------------------------------------------------------------------
+void rr_slice_tile_sizes(int* small_cells, int* tile_side, int* group_size) { slice_tile_sizes(small_cells, tile_side, group_size); }
+
+int rr_slice_mesh_device(rr_ctx* c, const rr_slice_config* slice, const rr_field_config* cfg, const uint8_t* d_skip_u8, uint8_t* d_occ_u8,
+                         uint32_t* d_object_u32, void* stream)
+{
+    int rc = check_slice(c, "rr_slice_mesh_device", slice, cfg, d_occ_u8, d_object_u32); if (rc) return rc;
+    if (c->n_tris == 0) return 0;                                     // an empty mesh writes nothing
+    RR_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = stream_of(c, stream);
+    uint32_t* list = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(c->slice_mu);
+        DevBuf<uint32_t>& b = c->slice_list[s];
+        RR_HIP(c, grow_on_stream(s, need(b, slice_scratch_words((size_t)c->n_tris))));
+        list = b.p;
+    }
+    launch_slice(reinterpret_cast<const TriRec*>(c->d_bvh.p + c->tri_base4), (size_t)c->n_tris, c->d_rest_v.p, c->d_rest_f.p, c->d_poses.p, d_skip_u8,
+                 *slice, *cfg, d_occ_u8, d_object_u32, list, s);
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_slice_mesh(rr_ctx* c, const rr_slice_config* slice, const rr_field_config* cfg, const uint8_t* skip_u8, uint8_t* occ_u8, uint32_t* object_u32)
+{
+    int rc = check_slice(c, "rr_slice_mesh", slice, cfg, occ_u8, object_u32); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t cells = (size_t)cfg->width * cfg->height;
+    RR_STAGE(c, st);
+    uint8_t* d_skip; uint8_t* d_occ; uint32_t* d_obj;
+    RR_HIP(c, st.up(skip_u8, (size_t)c->n_objects, d_skip));
+    RR_HIP(c, st.up(occ_u8, cells, d_occ));                          // the call accumulates
+    RR_HIP(c, st.up(object_u32, cells, d_obj));
+    rc = rr_slice_mesh_device(c, slice, cfg, d_skip, d_occ, d_obj, c->stream); if (rc) return rc;
+    st.out(occ_u8, d_occ, cells);
+    st.out(object_u32, d_obj, cells);
     return st.commit();
 }
 

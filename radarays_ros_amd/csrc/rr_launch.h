@@ -1,4 +1,4 @@
-// rr_launch.h -- every launcher of rr_kernels.hip, rr_labels.hip, rr_paths.hip, rr_doppler.hip, rr_refit.hip, rr_detect.hip, rr_deskew.hip, rr_icp.hip, rr_field.hip, rr_occupancy.hip, rr_filter.hip, rr_refine.hip, rr_cast.hip, rr_notes.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip, rr_place.hip and rr_lbvh.hip, declared ONCE: included where they
+// rr_launch.h -- every launcher of rr_kernels.hip, rr_labels.hip, rr_paths.hip, rr_doppler.hip, rr_refit.hip, rr_detect.hip, rr_deskew.hip, rr_icp.hip, rr_field.hip, rr_occupancy.hip, rr_filter.hip, rr_refine.hip, rr_cast.hip, rr_slice.hip, rr_notes.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip, rr_place.hip and rr_lbvh.hip, declared ONCE: included where they
 // are defined (a definition that drifts from its declaration fails there) and where they are called.  Default arguments live here only.
 #pragma once
 #include "../../include/radarays_mi355.h"
@@ -115,6 +115,13 @@ void launch_scan_profile(const rr_radar_point* points, const uint32_t* offsets, 
                          hipStream_t s);
 void launch_cast(const uint16_t* first_bin, const float* states, int n_hyp, const float* dirs, int n_angles, double resolution, const uint16_t* field,
                  const rr_field_config& g, const rr_beam_config& bc, uint16_t* ranges, rr_beam_rec* recs, hipStream_t s);
+// rr_slice.hip (mesh maps).  occ is only ever written with ones, objects (or null) only ever lowered.  scratch: slice_scratch_words uint32 words for n records
+// (the large list's counter, zeroed on s by the call, then the list); skip [n_objects] or null.  A memset and two launches
+void slice_tile_sizes(int* small_cells, int* tile_side, int* group_size);
+int slice_large_groups();
+size_t slice_scratch_words(size_t n_records);
+void launch_slice(const TriRec* tris, size_t n, const float* verts, const uint32_t* faces, const float* poses, const uint8_t* skip,
+                  const rr_slice_config& sc, const rr_field_config& g, uint8_t* occ, uint32_t* objects, uint32_t* scratch, hipStream_t s);
 // rr_notes.hip (object annotations).  scratch: note_scratch_bytes, 16-byte aligned like notes; every word of it, of notes and of skipped is written by the launches
 size_t note_scratch_bytes(size_t n_frames, size_t n_objects, int n_angles);
 void launch_notes(const uint32_t* labels, const uint8_t* imgs, int n_frames, uint32_t n_objects, uint32_t extent_mask, const PolarGrid& G,

@@ -420,6 +420,41 @@ def cast_tile_sizes():
     return a.value, b.value, c.value
 
 
+# ---- mesh maps (rr_slice.hip): rr_slice_config (16 B), the height band of a slice of the scene's triangles into the grid map
+OBJECT_NONE = 0xFFFFFFFF          # what an object plane holds where no triangle marks the cell
+
+
+class RRSliceConfig(C.Structure):
+    _fields_ = [("z_lo", C.c_float), ("z_hi", C.c_float), ("flags", C.c_uint32), ("reserved_", C.c_int32)]
+
+
+def slice_config(z_lo, z_hi):
+    """rr_slice_config, range-checked before any call into the library: the band [z_lo, z_hi] in metres of the map frame, both finite as
+    float32 and z_lo <= z_hi (equal: a plane)"""
+    lo, hi = _f32_finite(z_lo, "z_lo"), _f32_finite(z_hi, "z_hi")
+    if lo > hi:
+        raise ValueError("z_lo must not exceed z_hi, got %r > %r" % (z_lo, z_hi))
+    return RRSliceConfig(lo, hi, 0, 0)
+
+
+def _slice_cfg(cfg):
+    """an RRSliceConfig (slice_config makes one; held to its ranges again) or a (z_lo, z_hi) pair"""
+    if isinstance(cfg, RRSliceConfig):
+        if cfg.flags != 0:
+            raise ValueError("flags must be 0, got %r" % (cfg.flags,))
+        return slice_config(cfg.z_lo, cfg.z_hi)
+    if isinstance(cfg, (tuple, list)) and len(cfg) == 2:
+        return slice_config(*cfg)
+    raise ValueError("a slice config must be an RRSliceConfig (native.slice_config makes one) or a (z_lo, z_hi) pair, got %r" % (cfg,))
+
+
+def slice_tile_sizes():
+    """(the largest candidate box, in cells, that a record's own thread tests; the side of a tile of k_slice_large; threads per workgroup)"""
+    a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+    lib().rr_slice_tile_sizes(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
 # rr_default_detect_config
 DETECT_DEFAULTS = {"method": 0, "guard_cells": 2, "train_cells": 16, "k": 12, "min_intensity": 1, "min_bin": 0, "cfar_scale": 3.0}
 DETECT_METHODS = {"cfar": 0, "ca-cfar": 0, "kstrongest": 1, "k-strongest": 1, 0: 0, 1: 1}
@@ -541,7 +576,7 @@ STRUCTS = {
     "rr_icp_rec": (RRIcpRec, ICP_DTYPE), "rr_field_config": (RRFieldConfig, None), "rr_field_rec": (RRFieldRec, FIELD_DTYPE),
     "rr_occupancy_config": (RROccupancyConfig, None), "rr_filter_config": (RRFilterConfig, FILTER_CONFIG_DTYPE),
     "rr_filter_summary": (RRFilterSummary, FILTER_SUMMARY_DTYPE), "rr_mesh": (RRMesh, None),
-    "rr_beam_config": (RRBeamConfig, None), "rr_beam_rec": (RRBeamRec, BEAM_DTYPE),
+    "rr_beam_config": (RRBeamConfig, None), "rr_beam_rec": (RRBeamRec, BEAM_DTYPE), "rr_slice_config": (RRSliceConfig, None),
 }
 
 
@@ -695,6 +730,10 @@ def _prototypes():
         "rr_score_beams_device": (i, [vp, vp, vp, i, vp, vp, P(RRFieldConfig), P(RRBeamConfig), vp, vp]),
         "rr_score_beams": (i, [vp, vp, vp, i, vp, vp, P(RRFieldConfig), P(RRBeamConfig), vp]),
         "rr_cast_tile_sizes": (None, [P(i), P(i), P(i)]),
+        # ---- mesh maps (rr_slice.hip)
+        "rr_slice_mesh_device": (i, [vp, P(RRSliceConfig), P(RRFieldConfig), vp, vp, vp, vp]),
+        "rr_slice_mesh": (i, [vp, P(RRSliceConfig), P(RRFieldConfig), vp, vp, vp]),
+        "rr_slice_tile_sizes": (None, [P(i), P(i), P(i)]),
         # ---- several GPUs of one node behind one object (rr_multi.hip)
         "rr_create_multi": (vp, [P(i), i]),
         "rr_destroy_multi": (None, [vp]),
@@ -1925,6 +1964,45 @@ class Context(_Scene):
         self._ck(self._L.rr_refine_poses(self._h, p.ctypes.data if len(p) else None, len(p), len(p), st.ctypes.data, len(st), nr.ctypes.data,
                                          C.byref(g), it, recs.ctypes.data))
         return recs
+
+    # ---- mesh maps (rr_slice.hip): the context's posed triangles sliced into the grid map
+    def _skip_bytes(self, skip_objects):
+        """object ids to leave out (or None / empty: none) -> uint8 [n_objects] or None"""
+        if skip_objects is None:
+            return None
+        ids = np.asarray(list(skip_objects))
+        if ids.size == 0:
+            return None
+        n = int(getattr(self, "n_objects", 1))
+        if ids.dtype.kind not in "iu" or ids.ndim != 1 or ids.min() < 0 or ids.max() >= n:
+            raise ValueError("skip_objects must be object ids in 0..%d, got %r" % (n - 1, skip_objects))
+        skip = np.zeros(n, np.uint8)
+        skip[ids] = 1
+        return skip
+
+    def slice_mesh_device(self, slice_cfg, field_cfg, d_occ_ptr, d_object_ptr=None, d_skip_ptr=None, stream=None):
+        """rr_slice_mesh_device: a 1 into every cell of the uint8 grid [height][width] at d_occ_ptr that a posed triangle touches inside the
+        band; with d_object_ptr the smallest object id per cell into that uint32 plane (filled with OBJECT_NONE by the caller); d_skip_ptr
+        uint8 [n_objects], non-zero: the object is left out.  Enqueued on `stream`; the caller orders it against the scene setters"""
+        sc, g = _slice_cfg(slice_cfg), _field_cfg(field_cfg)
+        if not d_occ_ptr or (d_object_ptr and d_object_ptr % 4):
+            raise ValueError("slice_mesh_device needs a grid buffer, and a 4-byte aligned object plane if one is given")
+        self._ck(self._L.rr_slice_mesh_device(self._h, C.byref(sc), C.byref(g), d_skip_ptr, d_occ_ptr, d_object_ptr, stream))
+
+    def slice_mesh(self, slice_cfg, field_cfg, skip_objects=None, with_objects=False, occ=None, objects=None):
+        """rr_slice_mesh: the scene's triangles inside the band -> uint8 [height][width] of zeros and ones, accumulated into a copy of `occ`
+        when one is given; with_objects (or `objects`, a plane to lower): also the uint32 plane of the smallest object id per cell,
+        OBJECT_NONE where nothing marks it.  skip_objects: object ids to leave out.  Returns occ or (occ, objects)"""
+        sc, g = _slice_cfg(slice_cfg), _field_cfg(field_cfg)
+        skip = self._skip_bytes(skip_objects)
+        out = np.zeros((g.height, g.width), np.uint8) if occ is None else self._field_grid(occ, g, np.uint8, "occ").copy()
+        obj = None
+        if objects is not None:
+            obj = self._field_grid(objects, g, np.uint32, "objects").copy()
+        elif with_objects:
+            obj = np.full((g.height, g.width), OBJECT_NONE, np.uint32)
+        self._ck(self._L.rr_slice_mesh(self._h, C.byref(sc), C.byref(g), _ptr(skip), out.ctypes.data, _ptr(obj)))
+        return out if obj is None else (out, obj)
 
     # ---- beam model (rr_cast.hip): a scan's first detection per azimuth, the map cast at pose hypotheses, a scan's rays scored against it
     def _beam_cfg(self, beam_cfg):

@@ -715,6 +715,20 @@ class RadarHIP:
         first = self._ctx.scan_profile(pts, offs)[0]
         return self._ctx.score_beams(first, states, native.beam_directions(self._ctx._rrcfg), field, field_cfg, beam_cfg)
 
+    # ---- mesh maps (rr_slice.hip): the loaded mesh itself as the grid map, no scans in between
+    def buildMeshMap(self, field_cfg, z_lo, z_hi, skip_objects=(), with_objects=False, occ=None):
+        """The scene's triangles as a prior map: uint8 [height][width], a 1 in every cell of field_cfg's grid that some triangle -- every
+        face's rest corners moved by its object's current pose (setObjectPoses) -- touches inside the height band [z_lo, z_hi] (metres,
+        map frame; around the sensor plane), 0 elsewhere (rr_slice_mesh).  Geometry only: no occlusion, no materials, no noise.
+        skip_objects: object ids left out entirely, e.g. the parked and moving objects of a dynamic scene.  with_objects: also the uint32
+        plane of the smallest object id per cell (native.OBJECT_NONE where nothing marks it), a semantic map through object_materials.
+        occ: a map to accumulate into (a copy of it is returned): another band, or a grid of rasterize_points.
+        Returns occ, or (occ, objects), as numpy arrays.
+        The chain: buildMeshMap -> the transform of buildLikelihoodField (Context.distance_field at threshold 1) for scorePoses, castMap
+        and scoreBeams; -> buildNearestField for refinePoses."""
+        out = self._ctx.slice_mesh(native.slice_config(z_lo, z_hi), field_cfg, skip_objects, with_objects, occ)
+        return out
+
     # ---- place recognition (rr_place.hip): a database of yaw-invariant ring/sector descriptors, and a scan looked up in it
     def buildPlaceDatabase(self, poses, place_cfg, on_device=False):
         """any number of [n][7] poses, worked through 64 at a time -> their descriptors uint8 [n][R][S] (native.Context._place_cfg
