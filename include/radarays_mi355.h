@@ -1504,6 +1504,70 @@ int rr_slice_mesh(rr_ctx* ctx, const rr_slice_config* slice, const rr_field_conf
  * threads of a workgroup of either kernel (tests put boxes, grid sides and record counts at the edges) */
 void rr_slice_tile_sizes(int* small_cells, int* tile_side, int* group_size);
 
+/* ---- connected components: the clusters of polar images, the segments of grid maps (rr_components.hip) ------------------------------
+ * The step between "pixels" and "things": the foreground of a thresholded uint8 plane grouped into its connected components, as a label
+ * plane, a cleaned plane and one record per component.  One primitive serves the returns of a polar image (a cylinder: the column axis may
+ * wrap) and the occupied cells of a grid map (small components dropped before the map goes on to rr_distance_field, rr_nearest_field or
+ * rr_cast_map).  The reference has no such step: parity is UNPINNED and everything below is the build's own definition (a numpy restatement
+ * in tests/components_ref.py checks the kernels byte for byte).  Integers only; every result is independent of order.
+ * INPUT.  uint8 planes [n][height][width], row-major.  A pixel is foreground iff value >= threshold.  Two foreground pixels are neighbours
+ * iff they differ by one in row or column (connectivity 4) or by at most one in both (connectivity 8).  With wrap_x, column width-1 is also
+ * the left neighbour of column 0, diagonally as well under connectivity 8.  Rows never wrap; planes never touch each other.
+ * DEFINITION.  A component is a class of the transitive closure of "neighbours".  The LABEL of a foreground pixel is the linear index
+ * row * width + col of the smallest-index pixel of its component (the component's root); background is RR_LABEL_NONE.  A component with
+ * fewer than min_pixels pixels is DROPPED: its pixels read RR_LABEL_NONE as well and are 0 in the cleaned plane, which keeps the input's
+ * value under every kept pixel.  Kept components are listed in ascending root order; a component's id is its index in that list
+ * (a binary search of the roots for a label gives it).
+ * RECORDS.  For each plane the first min(kept, max_components) records in root order are written, every byte of them, and nothing beyond:
+ * the convention of rr_detect_device's offsets.  d_counts [n][2] holds the TRUE number of kept components (also past max_components) and
+ * the number of dropped ones.  row_min .. col_max are the plain extents.  col_lo_max is the largest occupied column < width / 2, col_hi_min
+ * the smallest occupied column >= width / 2, each RR_LABEL_NONE if there is none: with RR_COMP_SEAM they give the circular arc of a seam
+ * component narrower than half the circle, col_hi_min .. width-1, 0 .. col_lo_max.  All four column fields, the row extents, the flags and
+ * the peak are order-independent min / max / or values, the counts and sums integer sums.  peak is the largest plane value in the
+ * component, at (peak_row, peak_col); ties go to the lower linear index.  The sums run over the component's pixels in plain row and column
+ * coordinates (a seam component's centroid is the caller's to unwrap).
+ * The device form enqueues on `stream` (NULL: the context's): eight launches, no memset, no host round trip, no workgroup waiting for
+ * another.  All working memory is the caller's d_scratch (rr_components_scratch_bytes; its contents before the call do not matter, and
+ * the next call may have another shape): no context memory, so calls may run on any stream beside batches in flight.  The link plane of the
+ * union-find is d_labels when one is given.  The cleaned plane must not overlap the input.  The host form stages through context-owned
+ * buffers and is synchronous.  No config or mesh is needed in the context: the shape comes with the call.
+ * Refused with a message and nothing written: -1 for a null ctx; -3 for a null planes, config, counts or scratch buffer, n_planes outside
+ * 1..65535, a config field outside its stated range or reserved_ != 0, wrap_x with width < 3, records or scratch that are not 16-byte
+ * aligned, scratch_bytes below rr_components_scratch_bytes, d_comps given with max_components == 0 or missing with max_components > 0, a
+ * cleaned plane that overlaps the input.
+ * LIMITS.  No neighbourhood wider than 8 (bridging gaps between sparse detections is a dilation the caller does first); no dense ids in the
+ * label plane; 2-D only.  rr_multi has no such call. */
+typedef struct rr_components_config {   /* 32 B */
+    int32_t height, width;     /* 1..8192 each */
+    int32_t threshold;         /* 1..255: foreground iff value >= threshold */
+    int32_t connectivity;      /* 4 or 8 */
+    int32_t wrap_x;            /* 0 | 1; 1 needs width >= 3 */
+    int32_t min_pixels;        /* >= 1: smaller components are dropped */
+    int32_t max_components;    /* >= 0: records written per plane; 0 counts only */
+    int32_t reserved_;         /* 0 */
+} rr_components_config;
+
+#define RR_COMP_SEAM   1u   /* holds two neighbouring pixels across the wrap seam */
+#define RR_COMP_BORDER 2u   /* touches row 0 or H-1, or (wrap_x == 0) column 0 or W-1 */
+typedef struct rr_component {           /* 80 B, five 16-B stores, every byte written */
+    uint32_t root, n_pixels, row_min, row_max;
+    uint32_t col_min, col_max, col_lo_max, col_hi_min;
+    uint32_t peak, peak_row, peak_col, flags;
+    uint64_t sum_intensity, sum_row;
+    uint64_t sum_col, reserved_;
+} rr_component;
+
+size_t rr_components_scratch_bytes(int n_planes, const rr_components_config* cfg);   /* 0 for a refused shape */
+/* the tile of the first kernel, in pixels (tests put shapes, bridges and chains at its borders) */
+void   rr_components_tile_sizes(int* tile_w, int* tile_h);
+int rr_label_components_device(rr_ctx* ctx, const uint8_t* d_planes_u8, int n_planes, const rr_components_config* cfg,
+        uint32_t* d_labels_or_NULL /*[n][H][W]*/, uint8_t* d_clean_u8_or_NULL /*[n][H][W]*/,
+        rr_component* d_comps /*[n][max_components], NULL iff max_components == 0*/,
+        uint32_t* d_counts /*[n][2]: kept (TRUE total, also past max_components), dropped*/,
+        void* d_scratch, size_t scratch_bytes, void* stream);
+int rr_label_components(rr_ctx* ctx, const uint8_t* planes_u8, int n_planes, const rr_components_config* cfg,
+        uint32_t* labels_or_NULL, uint8_t* clean_u8_or_NULL, rr_component* comps, uint32_t* counts);   /* host, synchronous */
+
 /* ---- several GPUs of one node behind one object (SURVEY.md §8b "Threading", §8e) -------------------------
  * The reference creates ONE backend object per process (src/radar_simulator.cpp:145-176) and fans out inside it
  * (OpenMP over azimuths, RadarCPU.cpp:155).  rr_multi is that object for n GPUs: one rr_ctx per device, mesh and

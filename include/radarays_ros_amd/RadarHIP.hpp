@@ -649,6 +649,46 @@ public:
         }
         return map;
     }
+    // Connected components (rr_components.hip; include/radarays_mi355.h).  The returns of n polar images [n][n_cells][n_angles] mono8 grouped
+    // into clusters: the components of the pixels >= threshold on the cylinder (the azimuth axis wraps; RR_COMP_SEAM marks a cluster across
+    // the first and last column), clusters below min_pixels dropped.  clusters[a]: image a's first max_components records in ascending root
+    // order; counts [n][2]: kept, dropped; labels (or null): [n][n_cells][n_angles], the smallest linear index of the pixel's cluster,
+    // 0xFFFFFFFF elsewhere.  false on error
+    bool clusterImages(const std::vector<uint8_t>& images, int n_images, int threshold, std::vector<std::vector<rr_component>>& clusters,
+                       std::vector<uint32_t>& counts, std::vector<uint32_t>* labels = nullptr, int connectivity = 8, int min_pixels = 1,
+                       int max_components = 4096)
+    {
+        const rr_components_config cfg = { m_cfg.n_cells, m_n_angles, threshold, connectivity, 1, min_pixels, max_components, 0 };
+        if (!marshal::label_components(m_ctx, images, n_images, cfg, clusters, counts, labels, nullptr)) {
+            if (n_images < 1 || images.size() != (size_t)n_images * (size_t)m_cfg.n_cells * (size_t)m_n_angles) m_err = "clusterImages: the images must be [n][n_cells][n_angles] mono8";
+            else fail();
+            return false;
+        }
+        return true;
+    }
+    // ... and the occupied cells (>= threshold) of a grid map [height][width] grouped into segments without wrap, segments below min_cells
+    // dropped: the cleaned map (the input's bytes under every kept cell, 0 elsewhere) for rr_distance_field / buildNearestField / castMap at
+    // the same threshold, and every kept segment's record in ascending root order.  Empty on error
+    std::vector<uint8_t> segmentMap(const std::vector<uint8_t>& occ, const rr_field_config& grid, int threshold, std::vector<rr_component>& segments,
+                                    int min_cells = 1, int connectivity = 8)
+    {
+        std::vector<std::vector<rr_component>> comps;
+        std::vector<uint32_t> counts;
+        std::vector<uint8_t> clean;
+        rr_components_config cfg = { grid.height, grid.width, threshold, connectivity, 0, min_cells, 4096, 0 };
+        segments.clear();
+        for (int round = 0; round < 2; round++) {                  // (a second time, with room for every record, when there are more than 4096)
+            if (!marshal::label_components(m_ctx, occ, 1, cfg, comps, counts, nullptr, &clean)) {
+                if (grid.width < 1 || grid.height < 1 || occ.size() != (size_t)grid.width * (size_t)grid.height) m_err = "segmentMap: the map must be [height][width]";
+                else fail();
+                return {};
+            }
+            if (counts[0] <= (uint32_t)cfg.max_components) break;
+            cfg.max_components = (int32_t)counts[0];
+        }
+        segments = comps[0];
+        return clean;
+    }
     // one observed scan against hypothesis states [n][4] f32 (each the scan's sensor frame into the map frame) and a field of
     // buildLikelihoodField: one rr_field_rec per hypothesis, lower sum_d2 is better.  Empty on error
     std::vector<rr_field_rec> scorePoses(const std::vector<rr_radar_point>& scan, const std::vector<float>& states, const std::vector<uint16_t>& field,

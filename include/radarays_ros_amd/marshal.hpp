@@ -269,6 +269,28 @@ inline bool build_nearest(rr_ctx* ctx, const std::vector<uint8_t>& occ, int thre
     return rr_nearest_field(ctx, occ.data(), threshold, &cfg, nearest.data()) == 0;
 }
 
+// Connected components (rr_label_components, host form): uint8 planes [n][height][width] -> per plane the kept components' records in
+// ascending root order (comps[a]: the first min(kept, max_components)), counts [n][2] = kept, dropped, and as asked for (non-null) the
+// label planes and the cleaned planes.  false: a plane buffer of the wrong size, or rr_last_error(ctx)
+inline bool label_components(rr_ctx* ctx, const std::vector<uint8_t>& planes, int n_planes, const rr_components_config& cfg,
+                             std::vector<std::vector<rr_component>>& comps, std::vector<uint32_t>& counts, std::vector<uint32_t>* labels,
+                             std::vector<uint8_t>* clean)
+{
+    comps.clear(); counts.clear();
+    const size_t npx = cfg.width > 0 && cfg.height > 0 ? (size_t)cfg.width * (size_t)cfg.height : 0;
+    if (n_planes < 1 || npx == 0 || planes.size() != (size_t)n_planes * npx || cfg.max_components < 0) return false;
+    const size_t n = (size_t)n_planes, cap = (size_t)cfg.max_components;
+    std::vector<rr_component> recs(n * cap);
+    counts.assign(2 * n, 0u);
+    if (labels) labels->assign(n * npx, 0xFFFFFFFFu);
+    if (clean) clean->assign(n * npx, 0);
+    if (rr_label_components(ctx, planes.data(), n_planes, &cfg, labels ? labels->data() : nullptr, clean ? clean->data() : nullptr,
+                            cap ? recs.data() : nullptr, counts.data()) != 0) return false;
+    comps.resize(n);
+    for (size_t a = 0; a < n; a++) comps[a].assign(recs.begin() + a * cap, recs.begin() + a * cap + std::min<size_t>(counts[2 * a], cap));
+    return true;
+}
+
 // ... and ONE scan refined against it from n_hyp starting states on `stream`, every buffer the caller's and in HBM: d_init [n_hyp][4] f64
 // (c, s, tx, ty: the scan's sensor frame into the map frame), d_recs [n_hyp] (rr_refine_poses_device: one launch, nothing comes home and
 // nothing is waited for).  false: rr_last_error(ctx)

@@ -1,5 +1,5 @@
 // rr_images.hip -- the C ABI's image entry points: images in, records / points / images out.  PSNR scores and metrics against a reference image
-// (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), place recognition (rr_place.hip), point clouds and Cartesian images (rr_detect.hip), sweep compensation (rr_deskew.hip), scan matching (rr_icp.hip), the likelihood field (rr_field.hip), occupancy mapping (rr_occupancy.hip), the particle filter step (rr_filter.hip), map refinement (rr_refine.hip), the beam model (rr_cast.hip), mesh maps (rr_slice.hip), object annotations (rr_notes.hip): each in a device form, which runs on the
+// (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), place recognition (rr_place.hip), point clouds and Cartesian images (rr_detect.hip), sweep compensation (rr_deskew.hip), scan matching (rr_icp.hip), the likelihood field (rr_field.hip), occupancy mapping (rr_occupancy.hip), the particle filter step (rr_filter.hip), map refinement (rr_refine.hip), the beam model (rr_cast.hip), mesh maps (rr_slice.hip), connected components (rr_components.hip), object annotations (rr_notes.hip): each in a device form, which runs on the
 // caller's buffers and stream, and a host form, which drains c->stream and makes its round trip through a Stage over the context's pool (rr_stage.h).
 #include "rr_grid.h"
 #include "rr_stage.h"
@@ -364,6 +364,36 @@ int check_slice(rr_ctx* c, const char* who, const rr_slice_config* sc, const rr_
     if (!(std::isfinite(sc->z_lo) && std::isfinite(sc->z_hi) && sc->z_lo <= sc->z_hi)) return fail(c, -3, w + ": z_lo and z_hi must be finite and z_lo <= z_hi");
     if (sc->flags != 0) return fail(c, -3, w + ": flags must be 0");
     if ((uintptr_t)objects % 4 != 0) return fail(c, -3, w + ": the object plane must be 4-byte aligned");
+    return 0;
+}
+
+// the refusals of rr_components_scratch_bytes and, behind it, of the component calls: the shape alone
+const char* bad_components_shape(int n_planes, const rr_components_config* g)
+{
+    if (!g) return "null config";
+    if (n_planes < 1 || n_planes > 65535) return "n_planes must be 1..65535";
+    if (g->height < 1 || g->height > 8192 || g->width < 1 || g->width > 8192) return "height and width must be 1..8192";
+    if (g->threshold < 1 || g->threshold > 255) return "threshold must be 1..255";
+    if (g->connectivity != 4 && g->connectivity != 8) return "connectivity must be 4 or 8";
+    if (g->wrap_x != 0 && g->wrap_x != 1) return "wrap_x must be 0 or 1";
+    if (g->wrap_x && g->width < 3) return "wrap_x needs width >= 3";
+    if (g->min_pixels < 1) return "min_pixels must be >= 1";
+    if (g->max_components < 0) return "max_components must be >= 0";
+    if (g->reserved_ != 0) return "reserved_ must be 0";
+    return nullptr;
+}
+
+// the refusals of rr_label_components_device / rr_label_components: no config of the radar and no mesh, the shape comes with the call
+int check_components(rr_ctx* c, const char* who, const void* planes, int n_planes, const rr_components_config* g, const void* clean, const void* comps,
+                     const void* counts)
+{
+    if (!c) return -1;
+    const std::string w(who);
+    if (!(planes && counts)) return fail(c, -3, w + ": null buffer");
+    if (const char* bad = bad_components_shape(n_planes, g)) return fail(c, -3, w + ": " + bad);
+    if (!comps != (g->max_components == 0)) return fail(c, -3, w + ": the records come with max_components > 0 and only with it");
+    const uintptr_t a = (uintptr_t)planes, b = (uintptr_t)clean, bytes = (uintptr_t)n_planes * g->height * g->width;
+    if (clean && a < b + bytes && b < a + bytes) return fail(c, -3, w + ": the cleaned plane must not overlap the input");
     return 0;
 }
 
@@ -1437,6 +1467,59 @@ int rr_slice_mesh(rr_ctx* c, const rr_slice_config* slice, const rr_field_config
     st.out(occ_u8, d_occ, cells);
     st.out(object_u32, d_obj, cells);
     return st.commit();
+}
+
+// ---- connected components (rr_components.hip) -------------------------------------------------------------------------------------
+void rr_components_tile_sizes(int* tile_w, int* tile_h) { components_tile_sizes(tile_w, tile_h); }
+
+size_t rr_components_scratch_bytes(int n_planes, const rr_components_config* cfg)
+{
+    if (bad_components_shape(n_planes, cfg)) return 0;
+    return components_scratch_bytes((size_t)n_planes, (size_t)cfg->height * cfg->width);
+}
+
+int rr_label_components_device(rr_ctx* c, const uint8_t* d_planes_u8, int n_planes, const rr_components_config* cfg, uint32_t* d_labels,
+                               uint8_t* d_clean_u8, rr_component* d_comps, uint32_t* d_counts, void* d_scratch, size_t scratch_bytes, void* stream)
+{
+    const std::string w("rr_label_components_device");
+    int rc = check_components(c, w.c_str(), d_planes_u8, n_planes, cfg, d_clean_u8, d_comps, d_counts); if (rc) return rc;
+    if (!d_scratch) return fail(c, -3, w + ": null scratch");
+    if ((uintptr_t)d_scratch % 16 != 0 || (uintptr_t)d_comps % 16 != 0) return fail(c, -3, w + ": the scratch and the records must be 16-byte aligned");
+    if ((uintptr_t)d_labels % 4 != 0 || (uintptr_t)d_counts % 4 != 0) return fail(c, -3, w + ": the label plane and the counts must be 4-byte aligned");
+    const size_t need = rr_components_scratch_bytes(n_planes, cfg);
+    if (scratch_bytes < need) return fail(c, -3, w + ": scratch of " + std::to_string(scratch_bytes) + " bytes, the call needs " + std::to_string(need));
+    RR_HIP(c, hipSetDevice(c->device));
+    launch_components(d_planes_u8, n_planes, *cfg, d_labels, d_clean_u8, d_comps, d_counts, d_scratch, stream_of(c, stream));
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_label_components(rr_ctx* c, const uint8_t* planes_u8, int n_planes, const rr_components_config* cfg, uint32_t* labels, uint8_t* clean_u8,
+                        rr_component* comps, uint32_t* counts)
+{
+    int rc = check_components(c, "rr_label_components", planes_u8, n_planes, cfg, clean_u8, comps, counts); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)n_planes, npx = (size_t)cfg->height * cfg->width, cap = (size_t)cfg->max_components;
+    const size_t scratch = rr_components_scratch_bytes(n_planes, cfg);
+    RR_STAGE(c, st);
+    uint8_t *d_planes, *d_clean, *d_scratch; uint32_t *d_labels, *d_counts; rr_component* d_comps;
+    RR_HIP(c, st.up(planes_u8, n * npx, d_planes));
+    RR_HIP(c, st.hold(labels, n * npx, d_labels));
+    RR_HIP(c, st.hold(clean_u8, n * npx, d_clean));
+    // the records of plane a that exist, min(kept, max_components), and nothing beyond them: the kept totals are every second word of counts
+    std::vector<uint32_t> kept(n);
+    std::vector<uint32_t> both(2 * n);
+    RR_HIP(c, st.hold_rows(comps, n, cap, cap, kept.data(), d_comps));
+    RR_HIP(c, st.room(2 * n, d_counts));
+    RR_HIP(c, st.room(scratch, d_scratch));
+    rc = rr_label_components_device(c, d_planes, n_planes, cfg, d_labels, d_clean, d_comps, d_counts, d_scratch, scratch, c->stream); if (rc) return rc;
+    // (the totals come home first, on their own, because the records' scatter reads them)
+    RR_HIP(c, hipMemcpyAsync(both.data(), d_counts, 2 * n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    RR_HIP(c, hipStreamSynchronize(c->stream));
+    for (size_t a = 0; a < n; a++) kept[a] = both[2 * a];
+    rc = st.commit(); if (rc) return rc;
+    std::memcpy(counts, both.data(), 2 * n * sizeof(uint32_t));
+    return 0;
 }
 
 // ---- object annotations (rr_notes.hip) --------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-// rr_launch.h -- every launcher of rr_kernels.hip, rr_labels.hip, rr_paths.hip, rr_doppler.hip, rr_refit.hip, rr_detect.hip, rr_deskew.hip, rr_icp.hip, rr_field.hip, rr_occupancy.hip, rr_filter.hip, rr_refine.hip, rr_cast.hip, rr_slice.hip, rr_notes.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip, rr_place.hip and rr_lbvh.hip, declared ONCE: included where they
+// rr_launch.h -- every launcher of rr_kernels.hip, rr_labels.hip, rr_paths.hip, rr_doppler.hip, rr_refit.hip, rr_detect.hip, rr_deskew.hip, rr_icp.hip, rr_field.hip, rr_occupancy.hip, rr_filter.hip, rr_refine.hip, rr_cast.hip, rr_slice.hip, rr_components.hip, rr_notes.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip, rr_place.hip and rr_lbvh.hip, declared ONCE: included where they
 // are defined (a definition that drifts from its declaration fails there) and where they are called.  Default arguments live here only.
 #pragma once
 #include "../../include/radarays_mi355.h"
@@ -122,6 +122,12 @@ int slice_large_groups();
 size_t slice_scratch_words(size_t n_records);
 void launch_slice(const TriRec* tris, size_t n, const float* verts, const uint32_t* faces, const float* poses, const uint8_t* skip,
                   const rr_slice_config& sc, const rr_field_config& g, uint8_t* occ, uint32_t* objects, uint32_t* scratch, hipStream_t s);
+// rr_components.hip (connected components).  scratch: components_scratch_bytes, 16-byte aligned like comps; its contents before the call do not matter.
+// labels (or null: the link plane lives in the scratch), clean (or null), comps (null iff max_components == 0); totals [n_planes][2].  Eight launches
+void components_tile_sizes(int* tile_w, int* tile_h);
+size_t components_scratch_bytes(size_t n_planes, size_t npx);
+void launch_components(const uint8_t* planes, int n_planes, const rr_components_config& cfg, uint32_t* labels, uint8_t* clean, rr_component* comps,
+                       uint32_t* totals, void* scratch, hipStream_t s);
 // rr_notes.hip (object annotations).  scratch: note_scratch_bytes, 16-byte aligned like notes; every word of it, of notes and of skipped is written by the launches
 size_t note_scratch_bytes(size_t n_frames, size_t n_objects, int n_angles);
 void launch_notes(const uint32_t* labels, const uint8_t* imgs, int n_frames, uint32_t n_objects, uint32_t extent_mask, const PolarGrid& G,

@@ -455,8 +455,55 @@ def slice_tile_sizes():
     return a.value, b.value, c.value
 
 
+# ---- connected components (rr_components.hip): rr_components_config (32 B) and rr_component (80 B), one record per kept component
+COMPONENT_DTYPE = np.dtype([("root", "<u4"), ("n_pixels", "<u4"), ("row_min", "<u4"), ("row_max", "<u4"), ("col_min", "<u4"), ("col_max", "<u4"),
+                            ("col_lo_max", "<u4"), ("col_hi_min", "<u4"), ("peak", "<u4"), ("peak_row", "<u4"), ("peak_col", "<u4"), ("flags", "<u4"),
+                            ("sum_intensity", "<u8"), ("sum_row", "<u8"), ("sum_col", "<u8"), ("reserved_", "<u8")])
+COMP_SEAM, COMP_BORDER = 1, 2
+COMPONENTS_MAX_SIDE, COMPONENTS_MAX_PLANES = 8192, 65535
+RRComponent = np.ctypeslib.as_ctypes_type(COMPONENT_DTYPE)
+
+
+class RRComponentsConfig(C.Structure):
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("threshold", C.c_int32), ("connectivity", C.c_int32), ("wrap_x", C.c_int32),
+                ("min_pixels", C.c_int32), ("max_components", C.c_int32), ("reserved_", C.c_int32)]
+
+
+def components_config(height, width, threshold, connectivity=8, wrap_x=False, min_pixels=1, max_components=4096):
+    """rr_components_config, range-checked before any call into the library: planes of height x width pixels (1..8192 each), foreground
+    iff value >= threshold (1..255), neighbours by connectivity 4 or 8, column width-1 the left neighbour of column 0 with wrap_x (which
+    needs width >= 3), components below min_pixels dropped, at most max_components records written per plane (0: counts only)"""
+    h, w = _int_in(height, 1, COMPONENTS_MAX_SIDE, "height"), _int_in(width, 1, COMPONENTS_MAX_SIDE, "width")
+    if isinstance(connectivity, bool) or connectivity not in (4, 8):
+        raise ValueError("connectivity must be 4 or 8, got %r" % (connectivity,))
+    if not isinstance(wrap_x, (bool, np.bool_)) and wrap_x not in (0, 1):
+        raise ValueError("wrap_x must be a bool, got %r" % (wrap_x,))
+    if wrap_x and w < 3:
+        raise ValueError("wrap_x needs width >= 3, got %d" % w)
+    return RRComponentsConfig(h, w, _int_in(threshold, 1, 255, "threshold"), int(connectivity), int(bool(wrap_x)),
+                              _int_in(min_pixels, 1, 0x7FFFFFFF, "min_pixels"), _int_in(max_components, 0, 0x7FFFFFFF, "max_components"), 0)
+
+
+def _components_cfg(cfg):
+    """an RRComponentsConfig (components_config makes one; held to its ranges again) or a dict of components_config's arguments"""
+    if isinstance(cfg, RRComponentsConfig):
+        if cfg.reserved_ != 0:
+            raise ValueError("reserved_ must be 0, got %r" % (cfg.reserved_,))
+        return components_config(cfg.height, cfg.width, cfg.threshold, cfg.connectivity, cfg.wrap_x, cfg.min_pixels, cfg.max_components)
+    if isinstance(cfg, dict):
+        return components_config(**cfg)
+    raise ValueError("a components config must be an RRComponentsConfig (native.components_config makes one) or a dict of its arguments, got %r" % (cfg,))
+
+
+def components_tile_sizes():
+    """(width, height) in pixels of the tile a workgroup of k_cc_tile labels in LDS"""
+    a, b = C.c_int(0), C.c_int(0)
+    lib().rr_components_tile_sizes(C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
 # rr_default_detect_config
-DETECT_DEFAULTS = {"method": 0, "guard_cells": 2, "train_cells": 16, "k": 12, "min_intensity": 1, "min_bin": 0, "cfar_scale": 3.0}
+DETECT_DEFAULTS ={"method": 0, "guard_cells": 2, "train_cells": 16, "k": 12, "min_intensity": 1, "min_bin": 0, "cfar_scale": 3.0}
 DETECT_METHODS = {"cfar": 0, "ca-cfar": 0, "kstrongest": 1, "k-strongest": 1, 0: 0, 1: 1}
 
 
@@ -577,6 +624,7 @@ STRUCTS = {
     "rr_occupancy_config": (RROccupancyConfig, None), "rr_filter_config": (RRFilterConfig, FILTER_CONFIG_DTYPE),
     "rr_filter_summary": (RRFilterSummary, FILTER_SUMMARY_DTYPE), "rr_mesh": (RRMesh, None),
     "rr_beam_config": (RRBeamConfig, None), "rr_beam_rec": (RRBeamRec, BEAM_DTYPE), "rr_slice_config": (RRSliceConfig, None),
+    "rr_components_config": (RRComponentsConfig, None), "rr_component": (RRComponent, COMPONENT_DTYPE),
 }
 
 
@@ -734,6 +782,11 @@ def _prototypes():
         "rr_slice_mesh_device": (i, [vp, P(RRSliceConfig), P(RRFieldConfig), vp, vp, vp, vp]),
         "rr_slice_mesh": (i, [vp, P(RRSliceConfig), P(RRFieldConfig), vp, vp, vp]),
         "rr_slice_tile_sizes": (None, [P(i), P(i), P(i)]),
+        # ---- connected components (rr_components.hip)
+        "rr_components_scratch_bytes": (sz, [i, P(RRComponentsConfig)]),
+        "rr_components_tile_sizes": (None, [P(i), P(i)]),
+        "rr_label_components_device": (i, [vp, vp, i, P(RRComponentsConfig), vp, vp, vp, vp, vp, sz, vp]),
+        "rr_label_components": (i, [vp, vp, i, P(RRComponentsConfig), vp, vp, vp, vp]),
         # ---- several GPUs of one node behind one object (rr_multi.hip)
         "rr_create_multi": (vp, [P(i), i]),
         "rr_destroy_multi": (None, [vp]),
@@ -2003,6 +2056,106 @@ class Context(_Scene):
             obj = np.full((g.height, g.width), OBJECT_NONE, np.uint32)
         self._ck(self._L.rr_slice_mesh(self._h, C.byref(sc), C.byref(g), _ptr(skip), out.ctypes.data, _ptr(obj)))
         return out if obj is None else (out, obj)
+
+    # ---- connected components (rr_components.hip): thresholded uint8 planes -> label planes, cleaned planes, one record per component
+    @staticmethod
+    def _component_planes(planes, g):
+        """uint8 [n][height][width] (or one plane) -> contiguous [n][height][width], n in 1..65535"""
+        x = np.asarray(planes)
+        if x.dtype != np.uint8 or x.ndim not in (2, 3) or x.shape[-2:] != (g.height, g.width):
+            raise ValueError("planes must be uint8 [n][%d][%d] or one such plane, got %s %s" % (g.height, g.width, x.dtype, x.shape))
+        x = np.ascontiguousarray(x).reshape(-1, g.height, g.width)
+        if not 1 <= len(x) <= COMPONENTS_MAX_PLANES:
+            raise ValueError("1..%d planes, got %d" % (COMPONENTS_MAX_PLANES, len(x)))
+        return x
+
+    @staticmethod
+    def components_scratch_bytes(n_planes, cfg):
+        """rr_components_scratch_bytes: the bytes of scratch rr_label_components_device needs for n_planes planes of cfg's shape"""
+        g = _components_cfg(cfg)
+        return int(lib().rr_components_scratch_bytes(_int_in(n_planes, 1, COMPONENTS_MAX_PLANES, "n_planes"), C.byref(g)))
+
+    def label_components_device(self, d_planes_ptr, n_planes, cfg, d_labels_ptr, d_clean_ptr, d_comps_ptr, d_counts_ptr, d_scratch_ptr, scratch_bytes,
+                                stream=None):
+        """rr_label_components_device on raw device addresses: uint8 planes [n][H][W] -> labels uint32 [n][H][W] (or None), the cleaned planes
+        uint8 [n][H][W] (or None, never overlapping the input), COMPONENT_DTYPE records [n][max_components] (None iff max_components is 0)
+        and counts uint32 [n][2] = (kept, dropped).  The scratch (components_scratch_bytes, 16-byte aligned like the records) is the
+        caller's; nothing of the context is used, so the call may run on any stream.  Every argument is checked here first."""
+        g, n = _components_cfg(cfg), _int_in(n_planes, 1, COMPONENTS_MAX_PLANES, "n_planes")
+        if not (d_planes_ptr and d_counts_ptr and d_scratch_ptr):
+            raise ValueError("label_components_device needs plane, count and scratch buffers")
+        if bool(d_comps_ptr) != (g.max_components > 0):
+            raise ValueError("the records come with max_components > 0 and only with it")
+        if (d_comps_ptr or 0) % 16 or d_scratch_ptr % 16 or (d_labels_ptr or 0) % 4 or d_counts_ptr % 4:
+            raise ValueError("the records and the scratch must be 16-byte aligned, the label plane and the counts 4-byte aligned")
+        nbytes = n * g.height * g.width
+        if d_clean_ptr and d_planes_ptr < d_clean_ptr + nbytes and d_clean_ptr < d_planes_ptr + nbytes:
+            raise ValueError("the cleaned planes must not overlap the input")
+        need = self.components_scratch_bytes(n, g)
+        if isinstance(scratch_bytes, bool) or not isinstance(scratch_bytes, (int, np.integer)) or scratch_bytes < need:
+            raise ValueError("scratch of %r bytes, the call needs %d" % (scratch_bytes, need))
+        self._ck(self._L.rr_label_components_device(self._h, d_planes_ptr, n, C.byref(g), d_labels_ptr, d_clean_ptr, d_comps_ptr, d_counts_ptr,
+                                                    d_scratch_ptr, int(scratch_bytes), stream))
+
+    def label_components_tensors(self, d_planes, cfg, labels=True, clean=False, stream=None):
+        """the device form on a torch uint8 tensor [n][H][W] (or [H][W]) of this context's device: allocates the outputs and sizes and owns
+        the scratch as a torch byte tensor, enqueues on `stream` (a raw handle; None: the context's own stream) and returns a dict of tensors
+        that stay in HBM: labels int32 [n][H][W] (the words are uint32, LABEL_NONE reads -1) and clean uint8 [n][H][W] as asked for, comps
+        uint8 [n][max_components * 80] (component_records views them on the host), counts int32 [n][2], and the scratch, which the caller keeps
+        alive until the stream has passed the call"""
+        import torch
+        g = _components_cfg(cfg)
+        if not isinstance(d_planes, torch.Tensor) or d_planes.dtype != torch.uint8 or d_planes.dim() not in (2, 3) or \
+                tuple(d_planes.shape[-2:]) != (g.height, g.width) or not d_planes.is_cuda or not d_planes.is_contiguous():
+            raise ValueError("planes must be a contiguous uint8 tensor [n][%d][%d] on the device" % (g.height, g.width))
+        n = 1 if d_planes.dim() == 2 else int(d_planes.shape[0])
+        dev = d_planes.device
+        out = {"counts": torch.empty((n, 2), dtype=torch.int32, device=dev)}
+        if labels:
+            out["labels"] = torch.empty((n, g.height, g.width), dtype=torch.int32, device=dev)
+        if clean:
+            out["clean"] = torch.empty((n, g.height, g.width), dtype=torch.uint8, device=dev)
+        if g.max_components:
+            out["comps"] = torch.empty((n, g.max_components * COMPONENT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        nbytes = self.components_scratch_bytes(n, g)
+        out["scratch"] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ptr = lambda k: out[k].data_ptr() if k in out else None      # noqa: E731
+        self.label_components_device(d_planes.data_ptr(), n, g, ptr("labels"), ptr("clean"), ptr("comps"), ptr("counts"), ptr("scratch"), nbytes, stream)
+        return out
+
+    @staticmethod
+    def component_counts(counts):
+        """the counts of a call (a torch tensor on the device, or numpy) -> uint32 [n][2] = (kept, dropped) on the host"""
+        c = counts.detach().cpu().numpy() if hasattr(counts, "detach") else np.asarray(counts)
+        return np.ascontiguousarray(c).view(np.uint32).reshape(-1, 2)
+
+    @staticmethod
+    def component_records(comps, counts):
+        """the records and counts of a call, brought home (torch tensors or numpy) -> a list with one COMPONENT_DTYPE array per plane: the
+        min(kept, max_components) records that were written"""
+        k = Context.component_counts(counts)
+        if comps is None:
+            return [np.zeros(0, COMPONENT_DTYPE) for _ in k]
+        c = np.ascontiguousarray(comps.detach().cpu().numpy() if hasattr(comps, "detach") else comps).view(np.uint8).reshape(len(k), -1).view(COMPONENT_DTYPE)
+        return [c[a, :min(int(k[a, 0]), c.shape[1])].copy() for a in range(len(k))]
+
+    def label_components(self, planes, cfg, labels=True, clean=False):
+        """rr_label_components on host planes uint8 [n][H][W] (or one plane): returns a dict with labels uint32 [n][H][W] (LABEL_NONE on the
+        background and on dropped components) and clean uint8 [n][H][W] as asked for, comps (a list with one COMPONENT_DTYPE array per plane:
+        the first min(kept, max_components) components in ascending root order) and counts uint32 [n][2] = (kept, dropped)"""
+        g = _components_cfg(cfg)
+        x = self._component_planes(planes, g)
+        n = len(x)
+        out = {"counts": np.zeros((n, 2), np.uint32)}
+        if labels:
+            out["labels"] = np.empty(x.shape, np.uint32)
+        if clean:
+            out["clean"] = np.empty(x.shape, np.uint8)
+        recs = np.zeros((n, g.max_components), COMPONENT_DTYPE) if g.max_components else None
+        self._ck(self._L.rr_label_components(self._h, x.ctypes.data, n, C.byref(g), _ptr(out.get("labels")), _ptr(out.get("clean")), _ptr(recs),
+                                             out["counts"].ctypes.data))
+        out["comps"] = self.component_records(recs, out["counts"])
+        return out
 
     # ---- beam model (rr_cast.hip): a scan's first detection per azimuth, the map cast at pose hypotheses, a scan's rays scored against it
     def _beam_cfg(self, beam_cfg):

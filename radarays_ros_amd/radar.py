@@ -729,6 +729,55 @@ class RadarHIP:
         out = self._ctx.slice_mesh(native.slice_config(z_lo, z_hi), field_cfg, skip_objects, with_objects, occ)
         return out
 
+    # ---- connected components (rr_components.hip): the returns of polar images as clusters, the occupied cells of a grid map as segments
+    def _label(self, planes, cfg, labels, clean):
+        """numpy planes: the host form; a torch tensor on the device: the device form on a stream of its own, nothing leaving HBM"""
+        try:
+            import torch
+            on_device = isinstance(planes, torch.Tensor)
+        except ImportError:
+            on_device = False
+        if not on_device:
+            return self._ctx.label_components(planes, cfg, labels, clean)
+        dev = planes.device
+        stream = torch.cuda.Stream(device=dev)            # an explicit stream, as simulatePointClouds
+        torch.cuda.current_stream(dev).synchronize()      # the caller's tensor was made on its own stream
+        with torch.cuda.device(dev), torch.cuda.stream(stream):
+            out = self._ctx.label_components_tensors(planes, cfg, labels, clean, stream.cuda_stream)
+        self._ctx.synchronize(stream.cuda_stream)
+        del out["scratch"]
+        return out
+
+    def clusterImages(self, imgs_u8, threshold, connectivity=8, min_pixels=1, max_components=4096):
+        """Polar images uint8 [n][n_cells][400] (or one image), real or simulated -> their returns grouped into clusters: the connected
+        components of the pixels >= threshold (rr_label_components), rows range bins and columns azimuths.  A polar image is a cylinder, so
+        the column axis wraps: a cluster across the first and last column is one (its record carries native.COMP_SEAM, and col_hi_min ..
+        399, 0 .. col_lo_max is its arc); the scroll of the image does not matter.  Clusters below min_pixels are dropped.
+        numpy images take the host form and return numpy; a torch uint8 tensor on the context's device takes the device form on a stream of
+        its own and returns tensors that never leave HBM (native.Context.label_components_tensors; component_records brings records home).
+        Returns a dict: labels [n][n_cells][400] (the smallest linear index of the pixel's cluster, native.LABEL_NONE elsewhere), comps (per
+        image the first max_components COMPONENT_DTYPE records in ascending root order) and counts [n][2] = (kept, dropped).
+        Sparse CFAR points rarely touch: dilate first where gaps are to be bridged."""
+        cfg = native.components_config(self.m_cfg.n_cells, N_ANGLES, threshold, connectivity, True, min_pixels, max_components)
+        return self._label(imgs_u8, cfg, True, False)
+
+    def segmentMap(self, occ_u8, field_cfg, threshold, min_cells=1, connectivity=8):
+        """A grid map uint8 [height][width] of field_cfg's grid (a grid of rasterize_points or buildMeshMap at threshold 1, a map of
+        buildOccupancyMap at 129; numpy, or a torch tensor on the device) -> (the cleaned map, the records): the occupied cells grouped into
+        segments without wrap, segments below min_cells dropped -- a three-cell phantom that survived the evidence threshold is no zero of
+        the distance field any more.  The cleaned map keeps the input's bytes under every kept cell and is 0 elsewhere, so it goes on to
+        distance_field / buildNearestField / castMap at the same threshold.  The records: COMPONENT_DTYPE, every kept segment in ascending
+        root order (the map is labelled once for the count, then with room for every record, when there are more than 4096)."""
+        g = native._field_cfg(field_cfg)
+        cfg = native.components_config(g.height, g.width, threshold, connectivity, False, min_cells, 4096)
+        out = self._label(occ_u8, cfg, False, True)
+        kept = int(native.Context.component_counts(out["counts"])[0, 0])
+        if kept > cfg.max_components:
+            cfg.max_components = kept
+            out = self._label(occ_u8, cfg, False, True)
+        recs = out["comps"] if isinstance(out["comps"], list) else native.Context.component_records(out["comps"], out["counts"])
+        return out["clean"][0], recs[0]
+
     # ---- place recognition (rr_place.hip): a database of yaw-invariant ring/sector descriptors, and a scan looked up in it
     def buildPlaceDatabase(self, poses, place_cfg, on_device=False):
         """any number of [n][7] poses, worked through 64 at a time -> their descriptors uint8 [n][R][S] (native.Context._place_cfg
