@@ -1568,6 +1568,85 @@ int rr_label_components_device(rr_ctx* ctx, const uint8_t* d_planes_u8, int n_pl
 int rr_label_components(rr_ctx* ctx, const uint8_t* planes_u8, int n_planes, const rr_components_config* cfg,
         uint32_t* labels_or_NULL, uint8_t* clean_u8_or_NULL, rr_component* comps, uint32_t* counts);   /* host, synchronous */
 
+/* ---- correlative scan matching: exact pyramid search of the likelihood field (rr_correlate.hip) -----------------------------------
+ * The search over a WIDE pose window that stands between place recognition (a coarse candidate) and rr_refine_poses / rr_register_points
+ * (a guess within a few cells): one scan, n_rot yaws, every whole-cell translation of a window of up to +-2047 cells.  A min-pyramid of
+ * the distance field bounds every block of translations from below, so almost all of the window is never visited; on whole-cell offsets
+ * the pruning is EXACT: the result is the argmin an exhaustive search of the same nodes gives, byte for byte.  The reference has no such
+ * step: parity is UNPINNED and everything below is the build's own definition (a numpy restatement in tests/correlate_ref.py checks the
+ * kernels byte for byte).  All f32 arithmetic is un-fused; every result is an integer and independent of order.
+ * INPUTS.  One scan, d_points[0 .. min(*d_count, max_points)), the count read on the device, max_points 0..65536.  A field uint16
+ * [height][width] exactly as rr_distance_field writes it (every value <= cap2 = max_dist * max_dist) under its rr_field_config, as plane 0
+ * of a pyramid.  n_rot in 1..4096 ANCHOR states f32 (c, s, tx, ty), used as given: each places the scan at the centre of the window under
+ * one yaw.  An rr_corr_config.  The call is refused if n_rot * (2*half_x+1) * (2*half_y+1) >= 2^31.
+ * ANCHORED CELL.  For rotation r and point i: px, py by the likelihood field's mapping in un-fused f32; u = (px - x0) / cell, v likewise.
+ * The point is USABLE iff u and v are finite and |u|, |v| < 16384; then bx = (int)floorf(u), by = (int)floorf(v), which may be negative or
+ * beyond the grid.  An unusable point costs cap2 at every node.
+ * SCORE.  F(x, y) = field[y][x] inside the grid, cap2 outside.  score(r, dx, dy) = sum over ALL points of F(bx + dx, by + dy) for
+ * |dx| <= half_x, |dy| <= half_y.  At (dx, dy) = (0, 0) this is exactly rr_score_poses's sum_d2 for the anchor state.  THE DIFFERENCE:
+ * any other offset moves the ANCHORED CELL by whole cells; it is not the metric state (tx + dx * cell, ty + dy * cell) rounded again,
+ * which rr_score_poses would put through the division once more and may land a point one cell aside.  That is what makes the bound exact.
+ * The node index is (r * (2*half_y+1) + dy + half_y) * (2*half_x+1) + dx + half_x; the result is the node of smallest (score, index).
+ * PYRAMID.  rr_field_pyramid[_device] writes levels + 1 planes [height][width] uint16: plane 0 is the field, P_h[y][x] the minimum over
+ * 0 <= a, b < 2^h of F(x + a, y + b), built level from level (four reads at stride 2^(h-1), cap2 beyond the edge).  d_pyramid_u16 may be
+ * d_field_u16 itself (a field computed into the head of the pyramid's buffer: plane 0 is then left as it is); any other overlap is the
+ * caller's error.  A pyramid of more levels than a search uses serves it as well.
+ * LOOK-UP.  Q_h(x, y) for any integers: cap2 if x >= width, y >= height, x + 2^h <= 0 or y + 2^h <= 0; otherwise P_h[max(y,0)][max(x,0)]
+ * (a clamped window is a superset of the clipped one: still a lower bound).
+ * CANDIDATES.  (r, ox, oy) at level h covers dx in [ox, ox + 2^h) and dy likewise, clipped to the window; its bound is
+ * LB = sum over the points of Q_h(bx + ox, by + oy), cap2 for an unusable point.  The top-level candidates start at -half + j * 2^levels;
+ * children are the four offsets at stride 2^(h-1), those that start beyond half_x or half_y dropped.
+ * SEARCH, deterministic.  1. Greedy descent: the top-level candidate of smallest (LB, r, oy, ox), of its children the smallest again, down
+ * to level 0; U is that node's exact score.  2. Level-synchronous pruning with that fixed U: a candidate survives iff LB <= U (ties reach
+ * level 0), survivors are expanded, at level 0 the bound is the score.  3. The winner is the smallest packed key score << 31 | index
+ * (score < 2^33).  levels = 0 evaluates every node: the exhaustive search in the same code.
+ * OVERFLOW.  If the survivors of a level h >= 1 exceed `capacity`, the record is the greedy node with RR_CORR_OVERFLOW set; nothing
+ * further is examined; kept[h] holds the true count, the counts of the levels below are 0.  Survivor counts do not depend on order, so
+ * the outcome is deterministic.  Level 0 keeps no list and cannot overflow.
+ * RECORD.  evaluated[h] and kept[h] are the bounds computed and the survivors at level h in step 2 (the descent's own 4 * levels bounds
+ * and the first pass over the top level, which finds its start, are not counted; entries above `levels` are 0).
+ * The device forms enqueue on `stream` (NULL: the context's) with no host round trip: rr_field_pyramid_device levels + 1 launches (levels
+ * when plane 0 is in place), rr_correlate_scan_device levels + 5 (cells, top, descent, top again, one per level below the top sized by
+ * `capacity` with the live count read on the device, finish).  No workgroup waits for another.  All working memory is the caller's
+ * d_scratch (rr_correlate_scratch_bytes; its contents before the call do not matter): no context memory, so calls may run on any stream
+ * beside batches in flight, each call with a scratch of its own.  The host forms stage through context-owned buffers and are synchronous.
+ * Refused with a message and nothing written: -1 for a null ctx; -3 for a null required buffer or config, a grid field outside
+ * rr_field_config's stated ranges, a search field outside its stated range or a non-zero reserved word, max_points outside 0..65536,
+ * n_rot outside 1..4096, 2^31 nodes or more, d_rot not 4-byte, the pyramid not 2-byte, the record or the scratch not 16-byte aligned,
+ * scratch_bytes below rr_correlate_scratch_bytes.  rr_multi has no such call. */
+typedef struct rr_corr_config {   /* 32 B */
+    int32_t half_x, half_y;    /* 0..2047 cells: the window is |dx| <= half_x, |dy| <= half_y */
+    int32_t levels;            /* 0..8: the top-level candidates are 2^levels cells wide; 0 is the exhaustive search */
+    int32_t capacity;          /* 1..2^24: candidates per list */
+    int32_t reserved_[4];      /* 0 */
+} rr_corr_config;
+
+#define RR_CORR_OVERFLOW 1u   /* a level's survivors exceeded capacity: the record is the greedy node */
+typedef struct rr_corr_rec {     /* 112 B, seven 16-B stores, every byte written */
+    int32_t  rot, dx, dy;      /* the winner: its anchor state and its offset in cells */
+    uint32_t flags;
+    uint64_t sum_d2;           /* of the winner, as in rr_field_rec: its score */
+    uint32_t n_in, n_hit;      /* of the winner, as in rr_field_rec */
+    uint64_t upper;            /* U, the greedy node's score */
+    uint32_t evaluated[9];     /* bounds computed per level */
+    uint32_t kept[9];          /* survivors per level */
+} rr_corr_rec;
+
+size_t rr_correlate_scratch_bytes(int n_rot, int max_points, const rr_corr_config* cfg);   /* 0 for a refused shape */
+/* the blocking of the kernels: points a wave takes per step, top-level candidates of one row per wave of k_corr_top, parents per wave of
+ * k_corr_expand (tests put counts and windows at their edges) */
+void   rr_correlate_tile_sizes(int* points_tile, int* tops_per_wave, int* parents_per_wave);
+int rr_field_pyramid_device(rr_ctx* ctx, const uint16_t* d_field_u16 /*[height][width]*/, const rr_field_config* cfg, int levels /*0..8*/,
+                            uint16_t* d_pyramid_u16 /*[levels+1][height][width]*/, void* stream);
+int rr_field_pyramid(rr_ctx* ctx, const uint16_t* field_u16, const rr_field_config* cfg, int levels, uint16_t* pyramid_u16);   /* host buffers */
+int rr_correlate_scan_device(rr_ctx* ctx, const rr_radar_point* d_points, const uint32_t* d_count, int max_points,
+                             const float* d_rot /*[n_rot][4]: c, s, tx, ty*/, int n_rot /*1..4096*/,
+                             const uint16_t* d_pyramid_u16 /*[levels+1][height][width]*/, const rr_field_config* cfg, const rr_corr_config* corr,
+                             rr_corr_rec* d_rec /*one record*/, void* d_scratch, size_t scratch_bytes, void* stream);
+int rr_correlate_scan(rr_ctx* ctx, const rr_radar_point* points, uint32_t count, int max_points, const float* rot, int n_rot,
+                      const uint16_t* pyramid_u16, const rr_field_config* cfg, const rr_corr_config* corr,
+                      rr_corr_rec* rec);                                                  /* host buffers, synchronous */
+
 /* ---- several GPUs of one node behind one object (SURVEY.md §8b "Threading", §8e) -------------------------
  * The reference creates ONE backend object per process (src/radar_simulator.cpp:145-176) and fans out inside it
  * (OpenMP over azimuths, RadarCPU.cpp:155).  rr_multi is that object for n GPUs: one rr_ctx per device, mesh and

@@ -704,6 +704,36 @@ public:
         }
         return recs;
     }
+    // Correlative scan matching (rr_correlate.hip; include/radarays_mi355.h): one observed scan searched over a WIDE window around a coarse
+    // candidate -- every yaw of `yaws` (radians) and every whole-cell offset |dx| <= corr.half_x, |dy| <= corr.half_y of the scan anchored
+    // at (centre_x, centre_y) -- against a field of buildLikelihoodField.  The record holds the winner (rot indexes yaws; dx, dy in cells),
+    // its score as scorePoses counts it, and what the search cost per level; pose_xyyaw (or null) receives the winner's metric pose
+    // (centre_x + dx * cell, centre_y + dy * cell, yaws[rot]): the start for refinePoses.  The pruning is exact: corr.levels = 0 searches
+    // every node and gives the same record apart from the counts.  Pose convention: an anchor state maps the scan's sensor frame into the
+    // map frame.  false on error
+    bool correlateScan(const std::vector<rr_radar_point>& scan, const std::vector<double>& yaws, double centre_x, double centre_y,
+                       const std::vector<uint16_t>& field, const rr_field_config& cfg, const rr_corr_config& corr, rr_corr_rec& rec,
+                       double* pose_xyyaw = nullptr)
+    {
+        rec = rr_corr_rec{};
+        std::vector<float> rot;                                    // (the call needs neither the config nor the scene: nothing is pushed)
+        for (double yaw : yaws) {
+            rot.push_back((float)std::cos(yaw)); rot.push_back((float)std::sin(yaw));
+            rot.push_back((float)centre_x); rot.push_back((float)centre_y);
+        }
+        if (!marshal::correlate_scan(m_ctx, scan, rot, field, cfg, corr, rec)) {
+            if (yaws.empty() || cfg.width < 1 || cfg.height < 1 || field.size() != (size_t)cfg.width * (size_t)cfg.height)
+                m_err = "correlateScan: yaws must not be empty and the field must be [height][width]";
+            else fail();
+            return false;
+        }
+        if (pose_xyyaw) {
+            pose_xyyaw[0] = centre_x + (double)rec.dx * (double)cfg.cell;
+            pose_xyyaw[1] = centre_y + (double)rec.dy * (double)cfg.cell;
+            pose_xyyaw[2] = yaws[(size_t)rec.rot];
+        }
+        return true;
+    }
     // Occupancy mapping (rr_occupancy.hip; include/radarays_mi355.h): n clouds (detect() of scans: sorted by column, then bin), each under
     // its state -- [n][4] = c s tx ty, or empty for the identity -- fused into `evidence`, int32 [height][width]: a detection adds
     // occ_cfg.l_hit to its cell, every cell a scan saw to be empty loses occ_cfg.l_free.  An evidence vector of the grid's size is

@@ -259,6 +259,22 @@ inline bool score_poses(rr_ctx* ctx, const std::vector<rr_radar_point>& scan, co
                           out.data()) == 0;
 }
 
+// Correlative scan matching (rr_field_pyramid, rr_correlate_scan, host forms): one scan, n_rot anchor states [n_rot][4] f32 (c, s, tx, ty: the
+// scan's sensor frame into the map frame at the centre of the window) and a field [height][width] -> the record of the node of smallest
+// (sum_d2, index) over every rotation and every whole-cell offset of corr's window.  The field's min-pyramid is built for the call.
+// false: rr_last_error(ctx), or a states vector that is not [n][4], or a field that is not [height][width], or levels outside 0..8
+inline bool correlate_scan(rr_ctx* ctx, const std::vector<rr_radar_point>& scan, const std::vector<float>& rot, const std::vector<uint16_t>& field,
+                           const rr_field_config& cfg, const rr_corr_config& corr, rr_corr_rec& out)
+{
+    out = rr_corr_rec{};
+    const size_t cells = cfg.width > 0 && cfg.height > 0 ? (size_t)cfg.width * (size_t)cfg.height : 0;
+    if (rot.empty() || rot.size() % 4 || cells == 0 || field.size() != cells || corr.levels < 0 || corr.levels > 8) return false;
+    std::vector<uint16_t> pyramid(((size_t)corr.levels + 1) * cells);
+    if (rr_field_pyramid(ctx, field.data(), &cfg, corr.levels, pyramid.data())) return false;
+    return rr_correlate_scan(ctx, scan.data(), (uint32_t)scan.size(), (int)scan.size(), rot.data(), (int)(rot.size() / 4), pyramid.data(), &cfg, &corr,
+                             &out) == 0;
+}
+
 // map refinement: the nearest-cell table [height][width] of an occupancy map (occupied: >= threshold; rr_nearest_field), 0xFFFFFFFF where no
 // occupied cell lies within cfg.max_dist.  false: rr_last_error(ctx), or a map that is not [height][width]
 inline bool build_nearest(rr_ctx* ctx, const std::vector<uint8_t>& occ, int threshold, const rr_field_config& cfg, std::vector<uint32_t>& nearest)

@@ -1,5 +1,5 @@
 // rr_images.hip -- the C ABI's image entry points: images in, records / points / images out.  PSNR scores and metrics against a reference image
-// (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), place recognition (rr_place.hip), point clouds and Cartesian images (rr_detect.hip), sweep compensation (rr_deskew.hip), scan matching (rr_icp.hip), the likelihood field (rr_field.hip), occupancy mapping (rr_occupancy.hip), the particle filter step (rr_filter.hip), map refinement (rr_refine.hip), the beam model (rr_cast.hip), mesh maps (rr_slice.hip), connected components (rr_components.hip), object annotations (rr_notes.hip): each in a device form, which runs on the
+// (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), place recognition (rr_place.hip), point clouds and Cartesian images (rr_detect.hip), sweep compensation (rr_deskew.hip), scan matching (rr_icp.hip), the likelihood field (rr_field.hip), occupancy mapping (rr_occupancy.hip), the particle filter step (rr_filter.hip), map refinement (rr_refine.hip), the beam model (rr_cast.hip), mesh maps (rr_slice.hip), connected components (rr_components.hip), correlative scan matching (rr_correlate.hip), object annotations (rr_notes.hip): each in a device form, which runs on the
 // caller's buffers and stream, and a host form, which drains c->stream and makes its round trip through a Stage over the context's pool (rr_stage.h).
 #include "rr_grid.h"
 #include "rr_stage.h"
@@ -395,6 +395,45 @@ int check_components(rr_ctx* c, const char* who, const void* planes, int n_plane
     const uintptr_t a = (uintptr_t)planes, b = (uintptr_t)clean, bytes = (uintptr_t)n_planes * g->height * g->width;
     if (clean && a < b + bytes && b < a + bytes) return fail(c, -3, w + ": the cleaned plane must not overlap the input");
     return 0;
+}
+
+// the refusals of rr_correlate_scratch_bytes and, behind it, of rr_correlate_scan[_device]: the shape of the search alone
+const char* bad_correlate_shape(int n_rot, int max_points, const rr_corr_config* k)
+{
+    if (!k) return "null search config";
+    if (n_rot < 1 || n_rot > 4096) return "n_rot must be 1..4096";
+    if (max_points < 0 || max_points > 65536) return "max_points must be 0..65536";
+    if (k->half_x < 0 || k->half_x > 2047 || k->half_y < 0 || k->half_y > 2047) return "half_x and half_y must be 0..2047";
+    if (k->levels < 0 || k->levels > 8) return "levels must be 0..8";
+    if (k->capacity < 1 || k->capacity > (1 << 24)) return "capacity must be 1..2^24";
+    if (k->reserved_[0] || k->reserved_[1] || k->reserved_[2] || k->reserved_[3]) return "reserved_ must be 0";
+    if ((long long)n_rot * (2 * k->half_x + 1) * (2 * k->half_y + 1) >= (1ll << 31)) return "the window holds 2^31 nodes or more";
+    return nullptr;
+}
+
+// the refusals of rr_field_pyramid_device / rr_field_pyramid: no config is needed, the shape comes with the call
+int check_pyramid(rr_ctx* c, const char* who, const void* field, const rr_field_config* g, int levels, const void* pyramid)
+{
+    if (!c) return -1;
+    const std::string w(who);
+    if (!(field && pyramid)) return fail(c, -3, w + ": null buffer");
+    if (levels < 0 || levels > 8) return fail(c, -3, w + ": levels must be 0..8");
+    if ((uintptr_t)field % 2 != 0 || (uintptr_t)pyramid % 2 != 0) return fail(c, -3, w + ": the field and the pyramid must be 2-byte aligned");
+    return check_field_grid(c, w, g);
+}
+
+// the refusals of rr_correlate_scan_device / rr_correlate_scan
+int check_correlate(rr_ctx* c, const char* who, const void* points, bool have_count, int max_points, const void* rot, int n_rot, const void* pyramid,
+                    const rr_field_config* g, const rr_corr_config* k, const void* rec, bool device)
+{
+    if (!c) return -1;
+    const std::string w(who);
+    const bool sizes_ok = max_points >= 0 && max_points <= 65536;
+    if (!(have_count && rot && pyramid && rec && (!sizes_ok || max_points == 0 || points))) return fail(c, -3, w + ": null buffer");
+    if (const char* bad = bad_correlate_shape(n_rot, max_points, k)) return fail(c, -3, w + ": " + bad);
+    if ((uintptr_t)rot % 4 != 0 || (uintptr_t)pyramid % 2 != 0 || (device && (uintptr_t)rec % 16 != 0))
+        return fail(c, -3, w + ": d_rot must be 4-byte, the pyramid 2-byte and the record 16-byte aligned");
+    return check_field_grid(c, w, g);
 }
 
 // the refusals the annotation calls share: a config (the plane shape) within the limits of the label planes and of the packed azimuth
@@ -1520,6 +1559,76 @@ int rr_label_components(rr_ctx* c, const uint8_t* planes_u8, int n_planes, const
     rc = st.commit(); if (rc) return rc;
     std::memcpy(counts, both.data(), 2 * n * sizeof(uint32_t));
     return 0;
+}
+
+// ---- correlative scan matching (rr_correlate.hip) ----------------------------------------------------------------------------------
+void rr_correlate_tile_sizes(int* points_tile, int* tops_per_wave, int* parents_per_wave)
+{
+    correlate_tile_sizes(points_tile, tops_per_wave, parents_per_wave);
+}
+
+size_t rr_correlate_scratch_bytes(int n_rot, int max_points, const rr_corr_config* cfg)
+{
+    if (bad_correlate_shape(n_rot, max_points, cfg)) return 0;
+    return correlate_scratch_bytes((size_t)n_rot, (size_t)max_points, cfg->levels, (size_t)cfg->capacity);
+}
+
+int rr_field_pyramid_device(rr_ctx* c, const uint16_t* d_field_u16, const rr_field_config* cfg, int levels, uint16_t* d_pyramid_u16, void* stream)
+{
+    int rc = check_pyramid(c, "rr_field_pyramid_device", d_field_u16, cfg, levels, d_pyramid_u16); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    launch_field_pyramid(d_field_u16, *cfg, levels, d_pyramid_u16, stream_of(c, stream));
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_field_pyramid(rr_ctx* c, const uint16_t* field_u16, const rr_field_config* cfg, int levels, uint16_t* pyramid_u16)
+{
+    int rc = check_pyramid(c, "rr_field_pyramid", field_u16, cfg, levels, pyramid_u16); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t cells = (size_t)cfg->width * cfg->height;
+    RR_STAGE(c, st);
+    uint16_t *d_field, *d_pyramid;
+    RR_HIP(c, st.up(field_u16, cells, d_field));
+    RR_HIP(c, st.hold(pyramid_u16, ((size_t)levels + 1) * cells, d_pyramid));
+    rc = rr_field_pyramid_device(c, d_field, cfg, levels, d_pyramid, c->stream); if (rc) return rc;
+    return st.commit();
+}
+
+int rr_correlate_scan_device(rr_ctx* c, const rr_radar_point* d_points, const uint32_t* d_count, int max_points, const float* d_rot, int n_rot,
+                             const uint16_t* d_pyramid_u16, const rr_field_config* cfg, const rr_corr_config* corr, rr_corr_rec* d_rec,
+                             void* d_scratch, size_t scratch_bytes, void* stream)
+{
+    const std::string w("rr_correlate_scan_device");
+    int rc = check_correlate(c, w.c_str(), d_points, d_count != nullptr, max_points, d_rot, n_rot, d_pyramid_u16, cfg, corr, d_rec, true); if (rc) return rc;
+    if (!d_scratch) return fail(c, -3, w + ": null scratch");
+    if ((uintptr_t)d_scratch % 16 != 0) return fail(c, -3, w + ": the scratch must be 16-byte aligned");
+    const size_t need = rr_correlate_scratch_bytes(n_rot, max_points, corr);
+    if (scratch_bytes < need) return fail(c, -3, w + ": scratch of " + std::to_string(scratch_bytes) + " bytes, the call needs " + std::to_string(need));
+    RR_HIP(c, hipSetDevice(c->device));
+    launch_correlate(d_points, d_count, max_points, d_rot, n_rot, d_pyramid_u16, *cfg, *corr, d_rec, d_scratch, stream_of(c, stream));
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_correlate_scan(rr_ctx* c, const rr_radar_point* points, uint32_t count, int max_points, const float* rot, int n_rot, const uint16_t* pyramid_u16,
+                      const rr_field_config* cfg, const rr_corr_config* corr, rr_corr_rec* rec)
+{
+    int rc = check_correlate(c, "rr_correlate_scan", points, true, max_points, rot, n_rot, pyramid_u16, cfg, corr, rec, false); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t cells = (size_t)cfg->width * cfg->height, scratch = rr_correlate_scratch_bytes(n_rot, max_points, corr);
+    RR_STAGE(c, st);
+    rr_radar_point* d_points; uint32_t* d_count; float* d_rot; uint16_t* d_pyramid; rr_corr_rec* d_rec; uint8_t* d_scratch;
+    RR_HIP(c, st.up_rows(points, 1, (size_t)max_points, &count, d_points));
+    RR_HIP(c, st.up(&count, 1, d_count));
+    RR_HIP(c, st.up(rot, (size_t)n_rot * 4, d_rot));
+    RR_HIP(c, st.up(pyramid_u16, ((size_t)corr->levels + 1) * cells, d_pyramid));
+    RR_HIP(c, st.hold(rec, 1, d_rec));
+    RR_HIP(c, st.room(scratch, d_scratch));
+    RR_HIP(c, hipStreamSynchronize(c->stream));        // (count is this call's own variable)
+    rc = rr_correlate_scan_device(c, d_points, d_count, max_points, d_rot, n_rot, d_pyramid, cfg, corr, d_rec, d_scratch, scratch, c->stream);
+    if (rc) return rc;
+    return st.commit();
 }
 
 // ---- object annotations (rr_notes.hip) --------------------------------------------------------------------------------

@@ -128,6 +128,14 @@ void components_tile_sizes(int* tile_w, int* tile_h);
 size_t components_scratch_bytes(size_t n_planes, size_t npx);
 void launch_components(const uint8_t* planes, int n_planes, const rr_components_config& cfg, uint32_t* labels, uint8_t* clean, rr_component* comps,
                        uint32_t* totals, void* scratch, hipStream_t s);
+// rr_correlate.hip (correlative scan matching).  No context memory.  pyramid [levels + 1][height][width] is written whole (plane 0 only when it is
+// not the field itself): levels + 1 launches.  scratch: correlate_scratch_bytes, 16-byte aligned like rec; its contents before the call do not
+// matter.  levels + 5 launches, every one below the top level sized by the capacity
+void correlate_tile_sizes(int* points_tile, int* tops_per_wave, int* parents_per_wave);
+size_t correlate_scratch_bytes(size_t n_rot, size_t max_points, int levels, size_t capacity);
+void launch_field_pyramid(const uint16_t* field, const rr_field_config& g, int levels, uint16_t* pyramid, hipStream_t s);
+void launch_correlate(const rr_radar_point* points, const uint32_t* count, int max_points, const float* rot, int n_rot, const uint16_t* pyramid,
+                      const rr_field_config& g, const rr_corr_config& c, rr_corr_rec* rec, void* scratch, hipStream_t s);
 // rr_notes.hip (object annotations).  scratch: note_scratch_bytes, 16-byte aligned like notes; every word of it, of notes and of skipped is written by the launches
 size_t note_scratch_bytes(size_t n_frames, size_t n_objects, int n_angles);
 void launch_notes(const uint32_t* labels, const uint8_t* imgs, int n_frames, uint32_t n_objects, uint32_t extent_mask, const PolarGrid& G,

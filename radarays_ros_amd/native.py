@@ -502,6 +502,52 @@ def components_tile_sizes():
     return a.value, b.value
 
 
+# ---- correlative scan matching (rr_correlate.hip): rr_corr_config (32 B) and rr_corr_rec (112 B), the one record of a search
+CORR_DTYPE = np.dtype([("rot", "<i4"), ("dx", "<i4"), ("dy", "<i4"), ("flags", "<u4"), ("sum_d2", "<u8"), ("n_in", "<u4"), ("n_hit", "<u4"),
+                       ("upper", "<u8"), ("evaluated", "<u4", (9,)), ("kept", "<u4", (9,))])
+CORR_OVERFLOW = 1
+CORR_MAX_HALF, CORR_MAX_LEVELS, CORR_MAX_ROT, CORR_MAX_CAPACITY, CORR_MAX_NODES = 2047, 8, 4096, 1 << 24, 1 << 31
+RRCorrRec = np.ctypeslib.as_ctypes_type(CORR_DTYPE)
+
+
+class RRCorrConfig(C.Structure):
+    _fields_ = [("half_x", C.c_int32), ("half_y", C.c_int32), ("levels", C.c_int32), ("capacity", C.c_int32), ("reserved_", C.c_int32 * 4)]
+
+
+def corr_config(half_x, half_y, levels=4, capacity=1 << 16):
+    """rr_corr_config, range-checked before any call into the library: the window |dx| <= half_x, |dy| <= half_y in cells (0..2047 each),
+    top-level candidates 2^levels cells wide (levels 0..8; 0 is the exhaustive search), at most `capacity` candidates per list (1..2^24)"""
+    return RRCorrConfig(_int_in(half_x, 0, CORR_MAX_HALF, "half_x"), _int_in(half_y, 0, CORR_MAX_HALF, "half_y"),
+                        _int_in(levels, 0, CORR_MAX_LEVELS, "levels"), _int_in(capacity, 1, CORR_MAX_CAPACITY, "capacity"), (C.c_int32 * 4)(0, 0, 0, 0))
+
+
+def _corr_cfg(cfg, n_rot=None):
+    """an RRCorrConfig (corr_config makes one; held to its ranges again) or a dict of corr_config's arguments; with n_rot, the node count too"""
+    if isinstance(cfg, RRCorrConfig):
+        if any(cfg.reserved_):
+            raise ValueError("reserved_ must be 0")
+        k = corr_config(cfg.half_x, cfg.half_y, cfg.levels, cfg.capacity)
+    elif isinstance(cfg, dict):
+        k = corr_config(**cfg)
+    else:
+        raise ValueError("a search config must be an RRCorrConfig (native.corr_config makes one) or a dict of its arguments, got %r" % (cfg,))
+    if n_rot is not None and n_rot * (2 * k.half_x + 1) * (2 * k.half_y + 1) >= CORR_MAX_NODES:
+        raise ValueError("%d rotations of a %d x %d window are 2^31 nodes or more" % (n_rot, 2 * k.half_x + 1, 2 * k.half_y + 1))
+    return k
+
+
+def correlate_tile_sizes():
+    """(points a wave takes per step, top-level candidates of one row per wave of k_corr_top, parents per wave of k_corr_expand)"""
+    a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+    lib().rr_correlate_tile_sizes(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
+def corr_node(rec, half_x, half_y):
+    """the node index of a record's winner: (rot * (2*half_y+1) + dy + half_y) * (2*half_x+1) + dx + half_x"""
+    return (int(rec["rot"]) * (2 * half_y + 1) + int(rec["dy"]) + half_y) * (2 * half_x + 1) + int(rec["dx"]) + half_x
+
+
 # rr_default_detect_config
 DETECT_DEFAULTS ={"method": 0, "guard_cells": 2, "train_cells": 16, "k": 12, "min_intensity": 1, "min_bin": 0, "cfar_scale": 3.0}
 DETECT_METHODS = {"cfar": 0, "ca-cfar": 0, "kstrongest": 1, "k-strongest": 1, 0: 0, 1: 1}
@@ -625,6 +671,7 @@ STRUCTS = {
     "rr_filter_summary": (RRFilterSummary, FILTER_SUMMARY_DTYPE), "rr_mesh": (RRMesh, None),
     "rr_beam_config": (RRBeamConfig, None), "rr_beam_rec": (RRBeamRec, BEAM_DTYPE), "rr_slice_config": (RRSliceConfig, None),
     "rr_components_config": (RRComponentsConfig, None), "rr_component": (RRComponent, COMPONENT_DTYPE),
+    "rr_corr_config": (RRCorrConfig, None), "rr_corr_rec": (RRCorrRec, CORR_DTYPE),
 }
 
 
@@ -787,6 +834,13 @@ def _prototypes():
         "rr_components_tile_sizes": (None, [P(i), P(i)]),
         "rr_label_components_device": (i, [vp, vp, i, P(RRComponentsConfig), vp, vp, vp, vp, vp, sz, vp]),
         "rr_label_components": (i, [vp, vp, i, P(RRComponentsConfig), vp, vp, vp, vp]),
+        # ---- correlative scan matching (rr_correlate.hip)
+        "rr_correlate_scratch_bytes": (sz, [i, i, P(RRCorrConfig)]),
+        "rr_correlate_tile_sizes": (None, [P(i), P(i), P(i)]),
+        "rr_field_pyramid_device": (i, [vp, vp, P(RRFieldConfig), i, vp, vp]),
+        "rr_field_pyramid": (i, [vp, vp, P(RRFieldConfig), i, vp]),
+        "rr_correlate_scan_device": (i, [vp, vp, vp, i, vp, i, vp, P(RRFieldConfig), P(RRCorrConfig), vp, vp, sz, vp]),
+        "rr_correlate_scan": (i, [vp, vp, u32, i, vp, i, vp, P(RRFieldConfig), P(RRCorrConfig), vp]),
         # ---- several GPUs of one node behind one object (rr_multi.hip)
         "rr_create_multi": (vp, [P(i), i]),
         "rr_destroy_multi": (None, [vp]),
@@ -2156,6 +2210,77 @@ class Context(_Scene):
                                              out["counts"].ctypes.data))
         out["comps"] = self.component_records(recs, out["counts"])
         return out
+
+    # ---- correlative scan matching (rr_correlate.hip): the min-pyramid of a field, and the exact search of a window of whole-cell offsets
+    @staticmethod
+    def _pyramid_planes(a, g, levels, what="pyramid"):
+        """uint16 [n][height][width] with n > levels -> contiguous, its first levels + 1 planes"""
+        x = np.asarray(a)
+        if x.dtype != np.uint16 or x.ndim != 3 or x.shape[1:] != (g.height, g.width) or len(x) < levels + 1:
+            raise ValueError("%s must be uint16 [%d or more][%d][%d], got %s %s" % (what, levels + 1, g.height, g.width, x.dtype, x.shape))
+        return np.ascontiguousarray(x[:levels + 1])
+
+    def field_pyramid_device(self, d_field_ptr, field_cfg, levels, d_pyramid_ptr, stream=None):
+        """rr_field_pyramid_device: uint16 planes [levels + 1][height][width] at d_pyramid_ptr from the field at d_field_ptr, which may be the
+        pyramid's own plane 0"""
+        g, lv = _field_cfg(field_cfg), _int_in(levels, 0, CORR_MAX_LEVELS, "levels")
+        if not d_field_ptr or not d_pyramid_ptr or d_field_ptr % 2 or d_pyramid_ptr % 2:
+            raise ValueError("field_pyramid_device needs a field and a pyramid buffer, 2-byte aligned")
+        self._ck(self._L.rr_field_pyramid_device(self._h, d_field_ptr, C.byref(g), lv, d_pyramid_ptr, stream))
+
+    def field_pyramid(self, field, field_cfg, levels):
+        """rr_field_pyramid: the uint16 field of distance_field -> uint16 [levels + 1][height][width]; plane 0 is the field, plane h the minimum
+        over the 2^h x 2^h cells from each cell on, max_dist^2 beyond the edge"""
+        g, lv = _field_cfg(field_cfg), _int_in(levels, 0, CORR_MAX_LEVELS, "levels")
+        f = self._field_grid(field, g, np.uint16, "field")
+        out = np.zeros((lv + 1, g.height, g.width), np.uint16)
+        self._ck(self._L.rr_field_pyramid(self._h, f.ctypes.data, C.byref(g), lv, out.ctypes.data))
+        return out
+
+    @staticmethod
+    def correlate_scratch_bytes(n_rot, max_points, corr_cfg):
+        """rr_correlate_scratch_bytes: the bytes of scratch rr_correlate_scan_device needs"""
+        n = _int_in(n_rot, 1, CORR_MAX_ROT, "n_rot")
+        k = _corr_cfg(corr_cfg, n)
+        return int(lib().rr_correlate_scratch_bytes(n, _int_in(max_points, 0, ICP_MAX_POINTS, "max_points"), C.byref(k)))
+
+    def correlate_scan_device(self, d_points_ptr, d_count_ptr, max_points, d_rot_ptr, n_rot, d_pyramid_ptr, field_cfg, corr_cfg, d_rec_ptr,
+                              d_scratch_ptr, scratch_bytes, stream=None):
+        """rr_correlate_scan_device on raw device addresses: one CORR_DTYPE record at d_rec_ptr for ONE scan (the points at d_points_ptr whose
+        count is the uint32 at d_count_ptr), the float32 anchor states [n_rot][4] = (c, s, tx, ty) and the pyramid of field_pyramid_device.
+        The scratch (correlate_scratch_bytes, 16-byte aligned like the record) is the caller's; nothing of the context is used, so the call
+        may run on any stream.  Every argument is checked here first."""
+        mp, n, g = _int_in(max_points, 0, ICP_MAX_POINTS, "max_points"), _int_in(n_rot, 1, CORR_MAX_ROT, "n_rot"), _field_cfg(field_cfg)
+        k = _corr_cfg(corr_cfg, n)
+        if not (d_count_ptr and d_rot_ptr and d_pyramid_ptr and d_rec_ptr and d_scratch_ptr) or (mp > 0 and not d_points_ptr):
+            raise ValueError("correlate_scan_device needs point, count, state, pyramid, record and scratch buffers")
+        if d_rot_ptr % 4 or d_pyramid_ptr % 2 or d_rec_ptr % 16 or d_scratch_ptr % 16:
+            raise ValueError("the states must be 4-byte, the pyramid 2-byte, the record and the scratch 16-byte aligned")
+        need = self.correlate_scratch_bytes(n, mp, k)
+        if isinstance(scratch_bytes, bool) or not isinstance(scratch_bytes, (int, np.integer)) or scratch_bytes < need:
+            raise ValueError("scratch of %r bytes, the call needs %d" % (scratch_bytes, need))
+        self._ck(self._L.rr_correlate_scan_device(self._h, d_points_ptr, d_count_ptr, mp, d_rot_ptr, n, d_pyramid_ptr, C.byref(g), C.byref(k),
+                                                  d_rec_ptr, d_scratch_ptr, int(scratch_bytes), stream))
+
+    def correlate_scan(self, points, rot_states, pyramid, field_cfg, corr_cfg):
+        """rr_correlate_scan: one POINT_DTYPE cloud, float32 anchor states [n_rot][4] (se2-style (cos yaw, sin yaw, x, y): the scan's sensor
+        frame into the map frame at the centre of the window), the uint16 pyramid of field_pyramid -> one CORR_DTYPE record: the node of
+        smallest (sum_d2, index) over every rotation and every whole-cell offset of the window"""
+        g = _field_cfg(field_cfg)
+        p = np.asarray(points)
+        if p.dtype != POINT_DTYPE or p.ndim != 1 or len(p) > ICP_MAX_POINTS:
+            raise ValueError("the scan must be a one-dimensional POINT_DTYPE array of at most %d points" % ICP_MAX_POINTS)
+        st = np.asarray(rot_states)
+        if st.dtype.kind not in "fiu" or st.ndim != 2 or st.shape[1] != 4 or not 1 <= len(st) <= CORR_MAX_ROT:
+            raise ValueError("the anchor states must be real numbers of shape [n][4] (c, s, tx, ty), n in 1..%d, got %s %s" % (CORR_MAX_ROT, st.dtype, st.shape))
+        st = np.ascontiguousarray(st, np.float32)
+        k = _corr_cfg(corr_cfg, len(st))
+        py = self._pyramid_planes(pyramid, g, k.levels)
+        p = np.ascontiguousarray(p)
+        rec = np.zeros(1, CORR_DTYPE)
+        self._ck(self._L.rr_correlate_scan(self._h, p.ctypes.data if len(p) else None, len(p), len(p), st.ctypes.data, len(st), py.ctypes.data,
+                                           C.byref(g), C.byref(k), rec.ctypes.data))
+        return rec[0]
 
     # ---- beam model (rr_cast.hip): a scan's first detection per azimuth, the map cast at pose hypotheses, a scan's rays scored against it
     def _beam_cfg(self, beam_cfg):

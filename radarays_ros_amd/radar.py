@@ -484,6 +484,33 @@ class RadarHIP:
             scan = pts[0]
         return self._ctx.score_poses(scan, states, field, field_cfg)
 
+    def correlateScan(self, scan_points_or_image, yaws, centre_xy, field_or_pyramid, field_cfg, corr_cfg, detect_cfg=None):
+        """One observed scan searched over a WIDE window around a coarse candidate (a hit of localize): every yaw of `yaws` (radians) and
+        every whole-cell offset |dx| <= half_x, |dy| <= half_y (corr_cfg: native.corr_config) of the scan anchored at centre_xy, against a
+        field of buildLikelihoodField [height][width] or its pyramid of native.Context.field_pyramid [levels + 1 or more][height][width]
+        (a field's pyramid is built for the call) -> (a native.CORR_DTYPE record, (x, y, yaw)).  The record holds the winner (rot indexes
+        yaws; dx, dy in cells), its sum_d2 / n_in / n_hit as scorePoses counts them, U and the bounds evaluated and kept per level; the
+        pose is the winner's metric pose (centre + (dx, dy) * cell, yaws[rot]): the start for refinePoses.  A min-pyramid of the field
+        prunes the window exactly: levels = 0 searches every node and gives the same record apart from the counts.  The scan is a
+        POINT_DTYPE cloud or a mono8 polar image, as in scorePoses.
+        Convention: an anchor state (cos yaw, sin yaw, x, y) maps the scan's sensor frame into the map frame."""
+        self._push()
+        scan = np.asarray(scan_points_or_image)
+        if scan.dtype != native.POINT_DTYPE:
+            pts, _ = self._ctx.detect(self._polar(scan_points_or_image), native.detect_config(detect_cfg, n_cells=self.m_cfg.n_cells))
+            scan = pts[0]
+        g = native._field_cfg(field_cfg)
+        yaw = np.atleast_1d(np.asarray(yaws, np.float64))
+        cx, cy = (float(v) for v in centre_xy)
+        if yaw.ndim != 1 or not 1 <= len(yaw) <= native.CORR_MAX_ROT or not np.all(np.isfinite(yaw)) or not (np.isfinite(cx) and np.isfinite(cy)):
+            raise ValueError("yaws must be 1..%d finite angles and centre_xy two finite numbers" % native.CORR_MAX_ROT)
+        k = native._corr_cfg(corr_cfg, len(yaw))
+        rot = native.se2_states(yaw, cx, cy).astype(np.float32)
+        f = np.asarray(field_or_pyramid)
+        pyramid = f if f.ndim == 3 else self._ctx.field_pyramid(f, g, k.levels)
+        rec = self._ctx.correlate_scan(scan, rot, pyramid, g, k)
+        return rec, (cx + int(rec["dx"]) * g.cell, cy + int(rec["dy"]) * g.cell, float(yaw[int(rec["rot"])]))
+
     # ---- occupancy mapping (rr_occupancy.hip): posed scans fused into an evidence grid, and the byte map the likelihood field takes
     def buildOccupancyMap(self, clouds, states, grid, l_hit=3, l_free=2, margin_bins=None, max_free_bin=None, evidence=None):
         """n point clouds (POINT_DTYPE arrays as toPointCloud / simulatePointClouds return them: sorted by column, then bin) under their
