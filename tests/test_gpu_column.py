@@ -3,7 +3,8 @@ orc_column, the oracle's column step (tests/test_column_host.py ties it to orc_s
 
 With ambient_noise = 0 the kernel calls no libm and DESIGN.md §4 claims bit equality: every segment's f32 column, u8 column and
 last-pass counters are compared exactly.  With noise on, the decay table's expf is the GPU's: the constants of
-tests/test_gpu_parity.py over all pixels of the case.
+tests/test_gpu_parity.py over all pixels of the case (test_noise); tests/test_gpu_column_noise.py compares the rest of the noise
+path exactly.
 
 A segment's stream is what the kernel stages, in order: the compacted list of passes 0 .. P-2, then the last pass' per-wave
 slots -- both records of a wave with record_multi_path, else the even one only; a record with cell < 0 is empty, one with
@@ -344,8 +345,10 @@ def test_noise(ctx, oracle, noise, den, rows):
     """Ambient noise 1 and 2 on 64 segments x 3424 bins, every column with its own offset, one row of offsets or one per frame,
     az_begin > 0, n_loc < n_angles and a scroll, so that the azimuth, the image column and the noise row are different numbers.
     Columns of three kinds: echoes in one 64-bin tile only (every other wave takes the "all 64 bins empty" amplitude), echoes in
-    every tile, and tiles whose only non-zero bin is their last.  The decay table's expf is the GPU's libm: the tolerances of
-    tests/test_gpu_parity.py over all pixels."""
+    every tile, and tiles whose only non-zero bin is their last.  This is the statistical check over the one term that is not
+    exact, the decay table's expf (the GPU's libm), at the presets' energies and the full column width: the tolerances of
+    tests/test_gpu_parity.py over all pixels.  The exact checks are next door, tests/test_gpu_column_noise.py: everything but
+    that term bit for bit, and expf bounded per pixel."""
     n_cells, n_frames, n_loc, az_begin = 3424, 4, 16, 100
     rs = np.random.RandomState(41 + noise)
     first_nonzero = 2 if den else 0          # tri9, mode 3: tap 0 weighs 0, tap 1 is the window's first non-zero bin
