@@ -162,10 +162,7 @@ def _icp_init(init, n):
     """None or float64 [n][4] with a finite non-zero (c, s) in every row"""
     if init is None:
         return None
-    x = np.asarray(init)
-    if x.dtype.kind not in "fiu" or x.shape != (n, 4):
-        raise ValueError("init must be real numbers of shape [%d][4] (c, s, tx, ty), got %s %s" % (n, x.dtype, x.shape))
-    x = np.ascontiguousarray(x, np.float64)
+    x = _states(init, np.float64, "init", n=n)
     h = np.sqrt(x[:, 0] * x[:, 0] + x[:, 1] * x[:, 1])
     if not np.all(np.isfinite(h) & (h > 0)):
         raise ValueError("every initial state needs a finite, non-zero (c, s)")
@@ -930,6 +927,70 @@ def _pose_batch(poses):
     if not 1 <= len(p) <= 64:
         raise ValueError("1..64 poses, got %d" % len(p))
     return p
+
+
+_A_CLOUD = "one-dimensional POINT_DTYPE array"      # the words every refusal of a cloud shares
+
+
+def _scan(points, lo, what):
+    """one POINT_DTYPE cloud -> contiguous.  lo 0 or 1: it holds lo..ICP_MAX_POINTS points; lo None: its length is the caller's to check"""
+    p = np.asarray(points)
+    if p.dtype != POINT_DTYPE or p.ndim != 1 or (lo is not None and not lo <= len(p) <= ICP_MAX_POINTS):
+        span = "" if lo is None else (" of at most %d points", " of 1..%d points")[lo] % ICP_MAX_POINTS
+        raise ValueError("%s must be a %s%s" % (what, _A_CLOUD, span))
+    return np.ascontiguousarray(p)
+
+
+def _states(states, dtype, what, n_max=None, n=None):
+    """real numbers [n][4] = (c, s, tx, ty) -> contiguous `dtype`; n is in 1..n_max, or exactly the `n` given"""
+    x = np.asarray(states)
+    if n is None:
+        fits, rows = x.ndim == 2 and x.shape[1] == 4 and 1 <= len(x) <= n_max, "[n][4] (c, s, tx, ty), n in 1..%d" % n_max
+    else:
+        fits, rows = x.shape == (n, 4), "[%d][4] (c, s, tx, ty)" % n
+    if x.dtype.kind not in "fiu" or not fits:
+        raise ValueError("%s must be real numbers of shape %s, got %s %s" % (what, rows, x.dtype, x.shape))
+    return np.ascontiguousarray(x, dtype)
+
+
+def _cloud_list(points):
+    """1..65535 POINT_DTYPE arrays in a list (or one such array) -> the list.  The first step of _clouds"""
+    if isinstance(points, np.ndarray) and points.ndim == 1:
+        points = [points]
+    pts = [np.asarray(p) for p in points]
+    if not pts or len(pts) > 65535 or any(p.dtype != POINT_DTYPE or p.ndim != 1 for p in pts):
+        raise ValueError("points must be a list of 1..65535 %ss" % _A_CLOUD)
+    return pts
+
+
+def _cloud_offsets(offsets, n, n_angles):
+    """uint32 [n][n_angles + 1] (or one frame's [n_angles + 1]) -> contiguous and two-dimensional.  The second step of _clouds"""
+    offs = np.asarray(offsets)
+    if offs.ndim == 1:
+        offs = offs[None]
+    if offs.dtype != np.uint32 or offs.shape != (n, n_angles + 1):
+        raise ValueError("offsets must be uint32 [%d][%d], got %s %s" % (n, n_angles + 1, offs.dtype, offs.shape))
+    return np.ascontiguousarray(offs)
+
+
+def _clouds(points, offsets, n_angles, cap):
+    """what detect() (or compensate_points()) returned, a list of n POINT_DTYPE arrays and offsets uint32 [n][n_angles + 1] -> (the points
+    as one zero-padded POINT_DTYPE [n][max_points] block, the contiguous offsets, the n lengths).  cap: a cloud holds at most ICP_MAX_POINTS
+    points.  Refused in this order: the list, the cap, the offsets, a frame that does not hold the points its offsets count.  A caller
+    with a check of its own between two of these takes the steps before it by themselves (_cloud_list, _cloud_offsets) and hands their
+    results in here, where they pass again: of two faults it then reports the one it always has."""
+    pts = _cloud_list(points)
+    lens = [len(p) for p in pts]
+    if cap and max(lens) > ICP_MAX_POINTS:
+        raise ValueError("a cloud may hold at most %d points" % ICP_MAX_POINTS)
+    offs = _cloud_offsets(offsets, len(pts), n_angles)
+    mp = max(1, max(lens))
+    if any(k != min(int(offs[f, -1]), mp) for f, k in enumerate(lens)):
+        raise ValueError("every frame must hold the points its offsets count")
+    buf = np.zeros((len(pts), mp), POINT_DTYPE)
+    for f, p in enumerate(pts):
+        buf[f, :len(p)] = p
+    return buf, offs, lens
 
 
 def object_poses_array(poses):
@@ -1702,27 +1763,12 @@ class Context(_Scene):
         """rr_compensate_points on what detect() returned: a list of n POINT_DTYPE arrays and offsets uint32 [n][n_angles + 1], with a
         sweep table SWEEP_DTYPE [n][n_angles] -> a list of n POINT_DTYPE arrays in the reference frame, same order and lengths"""
         _, n_angles = self._polar_shape()
-        if isinstance(points, np.ndarray) and points.ndim == 1:
-            points = [points]
-        pts = [np.asarray(p) for p in points]
-        if not pts or len(pts) > 65535 or any(p.dtype != POINT_DTYPE or p.ndim != 1 for p in pts):
-            raise ValueError("points must be a list of 1..65535 one-dimensional POINT_DTYPE arrays")
-        n = len(pts)
-        offs = np.asarray(offsets)
-        if offs.ndim == 1:
-            offs = offs[None]
-        if offs.dtype != np.uint32 or offs.shape != (n, n_angles + 1):
-            raise ValueError("offsets must be uint32 [%d][%d], got %s %s" % (n, n_angles + 1, offs.dtype, offs.shape))
-        offs = np.ascontiguousarray(offs)
-        t = self._sweep_records(table, n)
-        mp = max(1, max(len(p) for p in pts))
-        if any(len(p) != min(int(offs[f, -1]), mp) for f, p in enumerate(pts)):
-            raise ValueError("every frame must hold the points its offsets count")
-        buf = np.zeros((n, mp), POINT_DTYPE)
-        for f, p in enumerate(pts):
-            buf[f, :len(p)] = p
-        self._ck(self._L.rr_compensate_points(self._h, buf.ctypes.data, offs.ctypes.data, n, mp, t.ctypes.data, buf.ctypes.data))
-        return [buf[f, :len(p)].copy() for f, p in enumerate(pts)]
+        pts = _cloud_list(points)
+        offs = _cloud_offsets(offsets, len(pts), n_angles)
+        t = self._sweep_records(table, len(pts))      # a bad table is reported before a frame that does not hold its points
+        buf, offs, lens = _clouds(pts, offs, n_angles, False)
+        self._ck(self._L.rr_compensate_points(self._h, buf.ctypes.data, offs.ctypes.data, len(buf), buf.shape[1], t.ctypes.data, buf.ctypes.data))
+        return [buf[f, :k].copy() for f, k in enumerate(lens)]
 
     @staticmethod
     def _iterations(iterations):
@@ -1774,39 +1820,21 @@ class Context(_Scene):
         maps each cloud into the target's frame, sse, n_matched and flags; with want_corr also a list of n uint32 arrays: the target index
         each point was matched to in the last pass, ICP_NONE for an unmatched point."""
         _, n_angles = self._polar_shape()
-        if isinstance(points_list, np.ndarray) and points_list.ndim == 1:
-            points_list = [points_list]
-        pts = [np.asarray(p) for p in points_list]
-        if not pts or len(pts) > 65535 or any(p.dtype != POINT_DTYPE or p.ndim != 1 for p in pts):
-            raise ValueError("points must be a list of 1..65535 one-dimensional POINT_DTYPE arrays")
-        n = len(pts)
-        tgt = np.asarray(target_points)
-        if tgt.dtype != POINT_DTYPE or tgt.ndim != 1:
-            raise ValueError("the target must be a one-dimensional POINT_DTYPE array")
-        if len(tgt) > ICP_MAX_POINTS or any(len(p) > ICP_MAX_POINTS for p in pts):
+        pts = _cloud_list(points_list)
+        tgt = _scan(target_points, None, "the target")      # a bad target is reported before a cloud over the cap, and is held to it too
+        if len(tgt) > ICP_MAX_POINTS:
             raise ValueError("a cloud may hold at most %d points" % ICP_MAX_POINTS)
-        offs = np.asarray(offsets)
-        if offs.ndim == 1:
-            offs = offs[None]
-        if offs.dtype != np.uint32 or offs.shape != (n, n_angles + 1):
-            raise ValueError("offsets must be uint32 [%d][%d], got %s %s" % (n, n_angles + 1, offs.dtype, offs.shape))
-        offs = np.ascontiguousarray(offs)
-        mp = max(1, max(len(p) for p in pts))
-        if any(len(p) != min(int(offs[f, -1]), mp) for f, p in enumerate(pts)):
-            raise ValueError("every frame must hold the points its offsets count")
+        buf, offs, lens = _clouds(pts, offsets, n_angles, True)
+        n, mp = buf.shape
         x0 = _icp_init(init, n)
         it, g = _int_in(iterations, 0, 64, "iterations"), _icp_gate(gate)
-        tgt = np.ascontiguousarray(tgt)
-        buf = np.zeros((n, mp), POINT_DTYPE)
-        for f, p in enumerate(pts):
-            buf[f, :len(p)] = p
         recs = np.zeros(n, ICP_DTYPE)
         corr = np.full((n, mp), ICP_NONE, np.uint32) if want_corr else None
         self._ck(self._L.rr_register_points(self._h, buf.ctypes.data, offs.ctypes.data, n, mp, tgt.ctypes.data if len(tgt) else None, len(tgt),
                                             len(tgt), _ptr(x0), g, it, recs.ctypes.data,
                                             corr.ctypes.data if want_corr else None))
         if want_corr:
-            return recs, [corr[f, :len(p)].copy() for f, p in enumerate(pts)]
+            return recs, [corr[f, :k].copy() for f, k in enumerate(lens)]
         return recs
 
     # ---- likelihood field (rr_field.hip): clouds into an occupancy grid, its exact distance transform, pose hypotheses scored against it
@@ -1836,33 +1864,8 @@ class Context(_Scene):
         uint32 [n][n_angles + 1] and states float64 [n][4] or None -> (the points as one POINT_DTYPE [n][max_points] block, the offsets,
         the states), all contiguous"""
         _, n_angles = self._polar_shape()
-        if isinstance(points_list, np.ndarray) and points_list.ndim == 1:
-            points_list = [points_list]
-        pts = [np.asarray(p) for p in points_list]
-        if not pts or len(pts) > 65535 or any(p.dtype != POINT_DTYPE or p.ndim != 1 for p in pts):
-            raise ValueError("points must be a list of 1..65535 one-dimensional POINT_DTYPE arrays")
-        n = len(pts)
-        if any(len(p) > ICP_MAX_POINTS for p in pts):
-            raise ValueError("a cloud may hold at most %d points" % ICP_MAX_POINTS)
-        offs = np.asarray(offsets)
-        if offs.ndim == 1:
-            offs = offs[None]
-        if offs.dtype != np.uint32 or offs.shape != (n, n_angles + 1):
-            raise ValueError("offsets must be uint32 [%d][%d], got %s %s" % (n, n_angles + 1, offs.dtype, offs.shape))
-        offs = np.ascontiguousarray(offs)
-        mp = max(1, max(len(p) for p in pts))
-        if any(len(p) != min(int(offs[f, -1]), mp) for f, p in enumerate(pts)):
-            raise ValueError("every frame must hold the points its offsets count")
-        st = None
-        if states is not None:
-            st = np.asarray(states)
-            if st.dtype.kind not in "fiu" or st.shape != (n, 4):
-                raise ValueError("states must be real numbers of shape [%d][4] (c, s, tx, ty), got %s %s" % (n, st.dtype, st.shape))
-            st = np.ascontiguousarray(st, np.float64)
-        buf = np.zeros((n, mp), POINT_DTYPE)
-        for f, p in enumerate(pts):
-            buf[f, :len(p)] = p
-        return buf, offs, st
+        buf, offs, _ = _clouds(points_list, offsets, n_angles, True)
+        return buf, offs, None if states is None else _states(states, np.float64, "states", n=len(buf))
 
     @staticmethod
     def _field_grid(a, g, dtype, what):
@@ -1899,15 +1902,9 @@ class Context(_Scene):
         """rr_score_poses: one POINT_DTYPE cloud, float32 states [n][4] (pose_lattice makes them), the uint16 field of distance_field ->
         FIELD_DTYPE [n]; lower sum_d2 is better"""
         g = _field_cfg(field_cfg)
-        p = np.asarray(points)
-        if p.dtype != POINT_DTYPE or p.ndim != 1 or len(p) > ICP_MAX_POINTS:
-            raise ValueError("the scan must be a one-dimensional POINT_DTYPE array of at most %d points" % ICP_MAX_POINTS)
-        st = np.asarray(states)
-        if st.dtype.kind not in "fiu" or st.ndim != 2 or st.shape[1] != 4 or not 1 <= len(st) <= FIELD_MAX_HYP:
-            raise ValueError("states must be real numbers of shape [n][4] (c, s, tx, ty), n in 1..%d, got %s %s" % (FIELD_MAX_HYP, st.dtype, st.shape))
-        st = np.ascontiguousarray(st, np.float32)
+        p = _scan(points, 0, "the scan")
+        st = _states(states, np.float32, "states", FIELD_MAX_HYP)
         f = self._field_grid(field, g, np.uint16, "field")
-        p = np.ascontiguousarray(p)
         recs = np.zeros(len(st), FIELD_DTYPE)
         self._ck(self._L.rr_score_poses(self._h, p.ctypes.data if len(p) else None, len(p), len(p), st.ctypes.data, len(st), f.ctypes.data,
                                         C.byref(g), recs.ctypes.data))
@@ -2008,10 +2005,7 @@ class Context(_Scene):
         """rr_filter_move: float32 states [n][4], uint32 ancestors [n_out] or None (every state once), the increment (Dc, Ds, dx, dy) or None
         -> the moved states float32 [n_out][4]"""
         f, inc = _filter_cfg(filter_cfg), _increment(increment)
-        st = np.asarray(states)
-        if st.dtype.kind not in "fiu" or st.ndim != 2 or st.shape[1] != 4 or not 1 <= len(st) <= FILTER_MAX_N:
-            raise ValueError("states must be real numbers of shape [n][4] (c, s, tx, ty), n in 1..%d, got %s %s" % (FILTER_MAX_N, st.dtype, st.shape))
-        st = np.ascontiguousarray(st, np.float32)
+        st = _states(states, np.float32, "states", FILTER_MAX_N)
         anc = None
         if ancestors is not None:
             anc = np.asarray(ancestors)
@@ -2058,15 +2052,9 @@ class Context(_Scene):
         are widened to float64 and normalised by the library), the uint32 table of nearest_field -> ICP_DTYPE [n]: the refined state, sse,
         n_matched and flags of the last pass; iterations 0..64 (0 scores the states as they stand)"""
         g, it = _refine_cfg(field_cfg), _int_in(iterations, 0, 64, "iterations")
-        p = np.asarray(points)
-        if p.dtype != POINT_DTYPE or p.ndim != 1 or len(p) > ICP_MAX_POINTS:
-            raise ValueError("the scan must be a one-dimensional POINT_DTYPE array of at most %d points" % ICP_MAX_POINTS)
-        st = np.asarray(init)
-        if st.dtype.kind not in "fiu" or st.ndim != 2 or st.shape[1] != 4 or not 1 <= len(st) <= FIELD_MAX_HYP:
-            raise ValueError("init must be real numbers of shape [n][4] (c, s, tx, ty), n in 1..%d, got %s %s" % (FIELD_MAX_HYP, st.dtype, st.shape))
-        st = np.ascontiguousarray(st, np.float64)
+        p = _scan(points, 0, "the scan")
+        st = _states(init, np.float64, "init", FIELD_MAX_HYP)
         nr = self._field_grid(nearest, g, np.uint32, "nearest")
-        p = np.ascontiguousarray(p)
         recs = np.zeros(len(st), ICP_DTYPE)
         self._ck(self._L.rr_refine_poses(self._h, p.ctypes.data if len(p) else None, len(p), len(p), st.ctypes.data, len(st), nr.ctypes.data,
                                          C.byref(g), it, recs.ctypes.data))
@@ -2267,16 +2255,10 @@ class Context(_Scene):
         frame into the map frame at the centre of the window), the uint16 pyramid of field_pyramid -> one CORR_DTYPE record: the node of
         smallest (sum_d2, index) over every rotation and every whole-cell offset of the window"""
         g = _field_cfg(field_cfg)
-        p = np.asarray(points)
-        if p.dtype != POINT_DTYPE or p.ndim != 1 or len(p) > ICP_MAX_POINTS:
-            raise ValueError("the scan must be a one-dimensional POINT_DTYPE array of at most %d points" % ICP_MAX_POINTS)
-        st = np.asarray(rot_states)
-        if st.dtype.kind not in "fiu" or st.ndim != 2 or st.shape[1] != 4 or not 1 <= len(st) <= CORR_MAX_ROT:
-            raise ValueError("the anchor states must be real numbers of shape [n][4] (c, s, tx, ty), n in 1..%d, got %s %s" % (CORR_MAX_ROT, st.dtype, st.shape))
-        st = np.ascontiguousarray(st, np.float32)
+        p = _scan(points, 0, "the scan")
+        st = _states(rot_states, np.float32, "the anchor states", CORR_MAX_ROT)
         k = _corr_cfg(corr_cfg, len(st))
         py = self._pyramid_planes(pyramid, g, k.levels)
-        p = np.ascontiguousarray(p)
         rec = np.zeros(1, CORR_DTYPE)
         self._ck(self._L.rr_correlate_scan(self._h, p.ctypes.data if len(p) else None, len(p), len(p), st.ctypes.data, len(st), py.ctypes.data,
                                            C.byref(g), C.byref(k), rec.ctypes.data))
@@ -2297,13 +2279,11 @@ class Context(_Scene):
     def _cast_inputs(self, states, n_max, dirs, field, g):
         """the host arrays of the two ray calls, checked -> (float32 states [n][4], float32 dirs [n_angles][2], the uint16 field)"""
         _, n_angles = self._polar_shape()
-        st = np.asarray(states)
-        if st.dtype.kind not in "fiu" or st.ndim != 2 or st.shape[1] != 4 or not 1 <= len(st) <= n_max:
-            raise ValueError("states must be real numbers of shape [n][4] (c, s, tx, ty), n in 1..%d, got %s %s" % (n_max, st.dtype, st.shape))
+        st = _states(states, np.float32, "states", n_max)
         d = np.asarray(dirs)
         if d.dtype.kind not in "fiu" or d.shape != (n_angles, 2):
             raise ValueError("dirs must be real numbers of shape [%d][2] (beam_directions makes them), got %s %s" % (n_angles, d.dtype, d.shape))
-        return np.ascontiguousarray(st, np.float32), np.ascontiguousarray(d, np.float32), self._field_grid(field, g, np.uint16, "field")
+        return st, np.ascontiguousarray(d, np.float32), self._field_grid(field, g, np.uint16, "field")
 
     def scan_profile_device(self, d_points_ptr, d_offsets_ptr, n_frames, max_points, d_first_bin_ptr, stream=None):
         """rr_scan_profile_device: uint16 [n_frames][n_angles] at d_first_bin_ptr, per azimuth INDEX the bin of the first detection among

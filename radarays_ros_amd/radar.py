@@ -206,8 +206,7 @@ class RadarHIP:
         one stream into device buffers; only the offsets and the points come to the host, no image does."""
         import torch
         self._push()
-        n_cells = self.m_cfg.n_cells
-        det = native.detect_config(cfg, n_cells=n_cells)
+        det = native.detect_config(cfg, n_cells=self.m_cfg.n_cells)
         poses = native.object_poses_array(poses)
         dev = torch.device("cuda", self._ctx.device)
         out = []
@@ -215,21 +214,42 @@ class RadarHIP:
         stream = torch.cuda.Stream(device=dev)
         s = stream.cuda_stream
         with torch.cuda.device(dev), torch.cuda.stream(stream):
-            for at in range(0, len(poses), 64):
-                chunk = poses[at:at + 64]
-                n = len(chunk)
-                imgs = torch.empty((n, n_cells, N_ANGLES), dtype=torch.uint8, device=dev)
-                offs = torch.empty((n, N_ANGLES + 1), dtype=torch.int32, device=dev)
-                self._ctx.simulate_batch_device(chunk, imgs.data_ptr(), s)
-                self._ctx.detect_device(imgs.data_ptr(), n, det, None, 0, offs.data_ptr(), s)     # counts
-                totals = offs[:, -1].cpu().numpy().view(np.uint32)
-                mp = max(1, int(totals.max()))
-                pts = torch.empty((n, mp * native.POINT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-                self._ctx.detect_device(imgs.data_ptr(), n, det, pts.data_ptr(), mp, offs.data_ptr(), s)
+            for _, n, _, pts, _, totals in self._detected_chunks(poses, det, s, capped=False):
                 host = pts.cpu().numpy().view(native.POINT_DTYPE)
                 out.extend(host[f, :int(totals[f])].copy() for f in range(n))
         self._ctx.synchronize(s)
         return out
+
+    def _detected_chunks(self, poses, det, s, capped):
+        """The per-64-poses device loop under simulatePointClouds, registerPointClouds and buildLikelihoodField.  Per chunk:
+        rr_simulate_batch_device and rr_detect_device on the stream `s` into fresh device tensors -> (offset of the chunk, n, offs int32
+        [n][401], pts uint8 [n][max_points * 24], max_points, the counted totals uint32 [n] or None).  capped False: room for every
+        detection, which a count-only call finds first.  capped True: k * 400 with k-strongest and no count-only call, what that call
+        finds with CA-CFAR, ICP_MAX_POINTS at the most.
+        The caller holds the `with` of the stream and iterates inside it: what it allocates before the loop and copies home after it
+        belongs on that stream too, and a generator suspended inside a `with` of its own would keep torch on the stream for as long as
+        an error raised in the caller's loop body is held."""
+        import torch
+        n_cells = self.m_cfg.n_cells
+        dev = torch.device("cuda", self._ctx.device)
+        for at in range(0, len(poses), 64):
+            chunk = poses[at:at + 64]
+            n = len(chunk)
+            imgs = torch.empty((n, n_cells, N_ANGLES), dtype=torch.uint8, device=dev)
+            offs = torch.empty((n, N_ANGLES + 1), dtype=torch.int32, device=dev)
+            self._ctx.simulate_batch_device(chunk, imgs.data_ptr(), s)
+            if capped and det.method == 1:
+                totals, mp = None, det.k * N_ANGLES
+            else:
+                self._ctx.detect_device(imgs.data_ptr(), n, det, None, 0, offs.data_ptr(), s)     # counts
+                totals = offs[:, -1].cpu().numpy().view(np.uint32)
+                mp = int(totals.max())
+            if capped:
+                mp = min(mp, native.ICP_MAX_POINTS)
+            mp = max(1, mp)
+            pts = torch.empty((n, mp * native.POINT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+            self._ctx.detect_device(imgs.data_ptr(), n, det, pts.data_ptr(), mp, offs.data_ptr(), s)
+            yield at, n, offs, pts, mp, totals
 
     # ---- sweep compensation (rr_deskew.hip): a sweep under motion, as the sensor records it and with the distortion taken out again
     def simulate_sweep(self, pose_ref, twist, sweep_time, gain=0.0, detect=None, cartesian=None, ref_azimuth=0):
@@ -364,12 +384,9 @@ class RadarHIP:
         hypothesis turned by -atan2(s, c) about its own z axis and moved by -R^T t in its own axes (forward, left)."""
         import torch
         self._push()
-        n_cells = self.m_cfg.n_cells
-        det = native.detect_config(detect, n_cells=n_cells)
+        det = native.detect_config(detect, n_cells=self.m_cfg.n_cells)
         p = native.object_poses_array(poses)
-        tgt = np.ascontiguousarray(real_points)
-        if tgt.dtype != native.POINT_DTYPE or tgt.ndim != 1 or not 1 <= len(tgt) <= native.ICP_MAX_POINTS:
-            raise ValueError("real_points must be a one-dimensional POINT_DTYPE array of 1..%d points" % native.ICP_MAX_POINTS)
+        tgt = native._scan(np.ascontiguousarray(real_points), 1, "real_points")      # ascontiguousarray: one record alone is a cloud of one
         it, g = native._int_in(iterations, 0, 64, "iterations"), native._icp_gate(gate)
         table = None if compensate is None else self._ctx._sweep_records(compensate, 1)
         dev = torch.device("cuda", self._ctx.device)
@@ -379,21 +396,8 @@ class RadarHIP:
         s = stream.cuda_stream
         with torch.cuda.device(dev), torch.cuda.stream(stream):
             d_tgt, d_cnt = up(tgt), up(np.array([len(tgt)], np.uint32))
-            for at in range(0, len(p), 64):
-                chunk = p[at:at + 64]
-                n = len(chunk)
-                imgs = torch.empty((n, n_cells, N_ANGLES), dtype=torch.uint8, device=dev)
-                offs = torch.empty((n, N_ANGLES + 1), dtype=torch.int32, device=dev)
-                self._ctx.simulate_batch_device(chunk, imgs.data_ptr(), s)
-                if det.method == 1:
-                    mp = det.k * N_ANGLES
-                else:
-                    self._ctx.detect_device(imgs.data_ptr(), n, det, None, 0, offs.data_ptr(), s)     # counts
-                    mp = int(offs[:, -1].max().item())
-                mp = max(1, min(mp, native.ICP_MAX_POINTS))
-                pts = torch.empty((n, mp * native.POINT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+            for _, n, offs, pts, mp, _ in self._detected_chunks(p, det, s, capped=True):
                 d_rec = torch.empty(n * native.ICP_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-                self._ctx.detect_device(imgs.data_ptr(), n, det, pts.data_ptr(), mp, offs.data_ptr(), s)
                 if table is not None:
                     d_tab = up(np.tile(table, (n, 1)))
                     self._ctx.compensate_points_device(pts.data_ptr(), offs.data_ptr(), n, mp, d_tab.data_ptr(), None, s)
@@ -438,8 +442,7 @@ class RadarHIP:
         part of its pose, (cos yaw, sin yaw, x, y)."""
         import torch
         self._push()
-        n_cells = self.m_cfg.n_cells
-        det = native.detect_config(detect_cfg, n_cells=n_cells)
+        det = native.detect_config(detect_cfg, n_cells=self.m_cfg.n_cells)
         g = native._field_cfg(field_cfg)
         p = native.object_poses_array(poses)
         if len(p) == 0:
@@ -451,21 +454,8 @@ class RadarHIP:
         with torch.cuda.device(dev), torch.cuda.stream(stream):
             occ = torch.zeros((g.height, g.width), dtype=torch.uint8, device=dev)
             field = torch.empty((g.height, g.width), dtype=torch.int16, device=dev)
-            for at in range(0, len(p), 64):
-                chunk = p[at:at + 64]
-                n = len(chunk)
-                imgs = torch.empty((n, n_cells, N_ANGLES), dtype=torch.uint8, device=dev)
-                offs = torch.empty((n, N_ANGLES + 1), dtype=torch.int32, device=dev)
-                self._ctx.simulate_batch_device(chunk, imgs.data_ptr(), s)
-                if det.method == 1:
-                    mp = det.k * N_ANGLES
-                else:
-                    self._ctx.detect_device(imgs.data_ptr(), n, det, None, 0, offs.data_ptr(), s)     # counts
-                    mp = int(offs[:, -1].max().item())
-                mp = max(1, min(mp, native.ICP_MAX_POINTS))
-                pts = torch.empty((n, mp * native.POINT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+            for at, n, offs, pts, mp, _ in self._detected_chunks(p, det, s, capped=True):
                 d_st = torch.from_numpy(np.ascontiguousarray(states[at:at + 64])).to(dev)
-                self._ctx.detect_device(imgs.data_ptr(), n, det, pts.data_ptr(), mp, offs.data_ptr(), s)
                 self._ctx.rasterize_points_device(pts.data_ptr(), offs.data_ptr(), n, mp, g, occ.data_ptr(), d_st.data_ptr(), s)
             self._ctx.distance_field_device(occ.data_ptr(), g, field.data_ptr(), 1, s)
             out = field.cpu().numpy().view(np.uint16).copy()
@@ -478,11 +468,17 @@ class RadarHIP:
         real scan) or a mono8 polar image [n_cells][400], which is detected first (detect_cfg as in buildLikelihoodField).
         Convention: a hypothesis state (c, s, tx, ty) maps the scan's sensor frame into the map frame."""
         self._push()
-        scan = np.asarray(scan_points_or_image)
-        if scan.dtype != native.POINT_DTYPE:
-            pts, _ = self._ctx.detect(self._polar(scan_points_or_image), native.detect_config(detect_cfg, n_cells=self.m_cfg.n_cells))
-            scan = pts[0]
+        scan, _ = self._scan_or_image(scan_points_or_image, detect_cfg)
         return self._ctx.score_poses(scan, states, field, field_cfg)
+
+    def _scan_or_image(self, scan_points_or_image, detect_cfg):
+        """a POINT_DTYPE cloud, or a mono8 polar image, which is detected first -> (the cloud, the offsets uint32 [1][401] of the detection
+        or None for a cloud that was given)"""
+        scan = np.asarray(scan_points_or_image)
+        if scan.dtype == native.POINT_DTYPE:
+            return scan, None
+        pts, offs = self._ctx.detect(self._polar(scan_points_or_image), native.detect_config(detect_cfg, n_cells=self.m_cfg.n_cells))
+        return pts[0], offs[:1]
 
     def correlateScan(self, scan_points_or_image, yaws, centre_xy, field_or_pyramid, field_cfg, corr_cfg, detect_cfg=None):
         """One observed scan searched over a WIDE window around a coarse candidate (a hit of localize): every yaw of `yaws` (radians) and
@@ -495,10 +491,7 @@ class RadarHIP:
         POINT_DTYPE cloud or a mono8 polar image, as in scorePoses.
         Convention: an anchor state (cos yaw, sin yaw, x, y) maps the scan's sensor frame into the map frame."""
         self._push()
-        scan = np.asarray(scan_points_or_image)
-        if scan.dtype != native.POINT_DTYPE:
-            pts, _ = self._ctx.detect(self._polar(scan_points_or_image), native.detect_config(detect_cfg, n_cells=self.m_cfg.n_cells))
-            scan = pts[0]
+        scan, _ = self._scan_or_image(scan_points_or_image, detect_cfg)
         g = native._field_cfg(field_cfg)
         yaw = np.atleast_1d(np.asarray(yaws, np.float64))
         cx, cy = (float(v) for v in centre_xy)
@@ -530,7 +523,7 @@ class RadarHIP:
             clouds = [clouds]
         pts = [np.asarray(c) for c in clouds]
         if not pts or any(p.dtype != native.POINT_DTYPE or p.ndim != 1 for p in pts):
-            raise ValueError("clouds must be a non-empty list of one-dimensional POINT_DTYPE arrays")
+            raise ValueError("clouds must be a non-empty list of %ss" % native._A_CLOUD)
         offs = np.zeros((len(pts), N_ANGLES + 1), np.uint32)
         for f, p in enumerate(pts):
             col = p["column"].astype(np.int64)
@@ -568,31 +561,21 @@ class RadarHIP:
         g, f = native._field_cfg(field_cfg), native._filter_cfg(filter_cfg)
         inc = native._increment(increment)
         dev = torch.device("cuda", self._ctx.device)
-        pts = np.ascontiguousarray(scan)
-        if pts.dtype != native.POINT_DTYPE or pts.ndim != 1 or not 1 <= len(pts) <= native.ICP_MAX_POINTS:
-            raise ValueError("the scan must be a one-dimensional POINT_DTYPE array of 1..%d points" % native.ICP_MAX_POINTS)
+        pts = native._scan(np.ascontiguousarray(scan), 1, "the scan")
         keep_all = n_eff_floor is not None and prev_summary is not None and self.effectiveSampleSize(prev_summary) >= float(n_eff_floor)
-
-        def on_device(x, dtype, shape, what):
-            """a tensor, or an array numpy takes, -> a contiguous tensor on the device; torch has no uint16, so 16-bit words travel as int16"""
-            if not isinstance(x, torch.Tensor):
-                a = np.ascontiguousarray(x)
-                a = a.view(np.int16) if a.dtype == np.uint16 else np.ascontiguousarray(a, dtype)
-                x = torch.from_numpy(a.copy())
-            if tuple(x.shape) != shape or x.element_size() != np.dtype(dtype).itemsize or x.is_floating_point() != (np.dtype(dtype).kind == "f"):
-                raise ValueError("%s must have shape %s and %s elements, got %s %s" % (what, shape, np.dtype(dtype), tuple(x.shape), x.dtype))
-            return x.to(dev).contiguous()
-
         n = len(particles)
         if not 1 <= n <= native.FILTER_MAX_N:
             raise ValueError("1..%d particles, got %d" % (native.FILTER_MAX_N, n))
+        if not isinstance(particles, torch.Tensor) and np.asarray(particles).dtype == np.uint16:
+            # uint16 states: read as numbers by castMap and refinePoses, always refused here, as words that travel as int16
+            raise ValueError("particles must have shape %s and float32 elements, got %s torch.int16" % ((n, 4), np.shape(particles)))
         stream = torch.cuda.Stream(device=dev)
         s = stream.cuda_stream
         torch.cuda.current_stream(dev).synchronize()      # the caller's tensors were made on its own stream
         with torch.cuda.device(dev), torch.cuda.stream(stream):
-            st = on_device(particles, np.float32, (n, 4), "particles")
-            d_field = on_device(field, np.int16, (g.height, g.width), "field")
-            d_table = on_device(table, np.int16, (f.n_table,), "table")
+            st = self._on_device(particles, np.float32, (n, 4), "particles")
+            d_field = self._on_device(field, np.int16, (g.height, g.width), "field")
+            d_table = self._on_device(table, np.int16, (f.n_table,), "table")
             d_pts = torch.from_numpy(pts.view(np.uint8).copy()).to(dev)
             d_count = torch.tensor([len(pts)], dtype=torch.int32, device=dev)
             recs = torch.empty((n, 2), dtype=torch.int64, device=dev)
@@ -658,9 +641,7 @@ class RadarHIP:
         self._push()
         g, it = native._refine_cfg(field_cfg), native._int_in(iterations, 0, 64, "iterations")
         dev = torch.device("cuda", self._ctx.device)
-        pts = np.ascontiguousarray(scan)
-        if pts.dtype != native.POINT_DTYPE or pts.ndim != 1 or not 1 <= len(pts) <= native.ICP_MAX_POINTS:
-            raise ValueError("the scan must be a one-dimensional POINT_DTYPE array of 1..%d points" % native.ICP_MAX_POINTS)
+        pts = native._scan(np.ascontiguousarray(scan), 1, "the scan")
         n = len(states)
         if not 1 <= n <= native.FIELD_MAX_HYP:
             raise ValueError("1..%d states, got %d" % (native.FIELD_MAX_HYP, n))
@@ -682,12 +663,10 @@ class RadarHIP:
     def _scan_with_offsets(self, scan_points_or_image, detect_cfg):
         """a POINT_DTYPE cloud (sorted by column, then bin; its offsets are rebuilt from the columns) or a mono8 polar image, which is
         detected first -> ([cloud], offsets uint32 [1][401])"""
-        scan = np.asarray(scan_points_or_image)
-        if scan.dtype != native.POINT_DTYPE:
-            pts, offs = self._ctx.detect(self._polar(scan_points_or_image), native.detect_config(detect_cfg, n_cells=self.m_cfg.n_cells))
-            return [pts[0]], offs[:1]
-        if scan.ndim != 1:
-            raise ValueError("the scan must be a one-dimensional POINT_DTYPE array")
+        scan, offs = self._scan_or_image(scan_points_or_image, detect_cfg)
+        if offs is not None:
+            return [scan], offs
+        scan = native._scan(scan, None, "the scan")
         col = scan["column"].astype(np.int64)
         if len(col) and (col.max() >= N_ANGLES or np.any(np.diff(col) < 0)):
             raise ValueError("the scan is not sorted by column, or names a column past %d" % (N_ANGLES - 1))
