@@ -1647,6 +1647,125 @@ int rr_correlate_scan(rr_ctx* ctx, const rr_radar_point* points, uint32_t count,
                       const uint16_t* pyramid_u16, const rr_field_config* cfg, const rr_corr_config* corr,
                       rr_corr_rec* rec);                                                  /* host buffers, synchronous */
 
+/* ---- oriented surface points and point-to-line scan matching (rr_surfels.hip) ----------------------------------------------------
+ * What rr_register_points lacks: a detected cloud reduced to a sparse set of ORIENTED SURFACE POINTS (a local mean with a normal taken
+ * from the local scatter), and a batched matcher whose residual is only the distance component ALONG that normal, so a cloud no longer
+ * slides along a sparsely sampled wall.  The reference has no such step: parity is UNPINNED and everything below is the build's own
+ * definition (a numpy restatement in tests/surfels_ref.py checks the kernels byte for byte).  Integer sums, f64 steps of + - * / sqrt
+ * without trigonometry, a fixed iteration count; all f32 arithmetic is un-fused.
+ *
+ * 1. rr_surface_points[_device]: n clouds -> oriented surface points.  The clouds are laid out as rr_detect_device /
+ *    rr_compensate_points_device write them; the count of frame f is min(d_offsets[f][n_angles], max_points), read on the device; a cut
+ *    count sets RR_SURFELS_TRUNCATED.  z, intensity, column and bin are ignored.  With cell_q = (int32)rintf(cell * 256.0f) (1..4096):
+ *    QUANTISE.  A point is a candidate iff x and y are finite and below 8192 in magnitude; X = (int32)rintf(x * 256.0f), Y likewise.
+ *    CELL.  half = (width * cell_q) / 2 (integer division); U = X + half, V = Y + half; ix = floor(U / cell_q), iy = floor(V / cell_q)
+ *    (FLOOR, not truncation: U may be negative); the point is dropped unless 0 <= ix, iy < width.  The linear cell index is
+ *    iy * width + ix.  Coordinates RELATIVE to the cell's own origin: rx = U - ix * cell_q, ry = V - iy * cell_q, both in [0, cell_q).
+ *    PER-CELL SUMS.  Six int64 sums per cell over its points: N, Sx = sum rx, Sy = sum ry, Sxx = sum rx*rx, Sxy = sum rx*ry, Syy = sum ry*ry.
+ *    SAMPLE.  A surface point exists for each cell that holds at least one point itself; its sample is every point of the 3 x 3 block
+ *    of cells around it, clipped at the grid edge.  The sums of the neighbour at (ix + a, iy + b), a, b in -1..1, are shifted to the
+ *    centre cell's origin exactly, with ox = a * cell_q, oy = b * cell_q:
+ *        Sx + N*ox      Sy + N*oy      Sxx + 2*ox*Sx + N*ox*ox      Sxy + ox*Sy + oy*Sx + N*ox*oy      Syy + 2*oy*Sy + N*oy*oy
+ *    and added up; N, Sx .. Syy below are those totals.
+ *    SCATTER, exact int64:  Cxx = N*Sxx - Sx*Sx    Cxy = N*Sxy - Sx*Sy    Cyy = N*Syy - Sy*Sy.
+ *    PROOF.  A shifted coordinate lies in [-cell_q, 2*cell_q), so it is below 2^13 in magnitude; N <= 65536 = 2^16 (a frame has no more
+ *    points).  So |Sx| <= 2^29, Sxx <= 2^42, N*Sxx <= 2^58 and Sx*Sx <= 2^58: every product stays below 2^59, every scatter entry
+ *    within +-2^59, and T, d, o below within +-2^60.
+ *    EIGEN STEP, f64, + - * / sqrt only, evaluated as written.  T = Cxx + Cyy, d = Cxx - Cyy, o = 2*Cxy as int64, each converted to f64:
+ *        h = sqrt(d*d + o*o)     lmax = (T + h) / 2     v = (T - h) / 2, lmin = v if v > 0, else 0
+ *        the tangent (tx, ty) is (h + d, o) if d >= 0, else (o, h - d), each divided by sqrt(tx*tx + ty*ty)
+ *        the mean in quantised units: mx = (double)(ix*cell_q - half) + (double)Sx / (double)N, my likewise
+ *        the normal is (-ty, tx), negated iff nx*mx + ny*my > 0: normals face the sensor at the origin
+ *    KEEP the surface point iff N >= min_points, h > 0 and lmin <= (double)max_ratio * lmax.  (h == 0: one repeated point, or a
+ *    sample with no direction, as the corners of a square.)
+ *    RECORD.  x = (float)(mx / 256.0), y likewise; nx, ny rounded to f32; with den = ((double)N * (double)N) * 65536.0,
+ *    var_n = (float)(lmin / den), var_t = (float)(lmax / den): the variance across and along the surface in m^2; count = N; cell.
+ *    OUTPUT.  Per frame the first min(kept, max_surfels) records in ascending cell order, every byte of them, and nothing beyond; no
+ *    execution order can change a byte.  d_counts [n][2] holds the TRUE number kept (also past max_surfels) and the flags
+ *    (RR_SURFELS_TRUNCATED; RR_SURFELS_CAPPED: kept > max_surfels): the convention of rr_label_components.
+ *    The device form enqueues on `stream` (NULL: the context's) a memset of the sums and four launches: bin (one 64-bit integer vector
+ *    atomic per sum into the point's own cell), gather-and-decide (a launch of its own: the launch boundary makes the sums visible; per
+ *    chunk of cells the number kept), the scan of the chunks by one workgroup per frame, and write.  No host round trip, no workgroup
+ *    waiting for another.  All working memory is the caller's d_scratch (rr_surfels_scratch_bytes: 48 bytes of sums and one flag byte
+ *    per cell and frame, and the scan's partials; its contents before the call do not matter): no context memory, so calls may run on
+ *    any stream beside batches in flight.  The host form stages through context-owned buffers and is synchronous.
+ *    Refused with a message and nothing written: -1 for a null ctx; -2 without a config (n_angles is the offsets' stride); -3 for a
+ *    null required buffer or config, n_frames outside 1..65535, max_points outside 0..65536, max_surfels outside 0..2^20, a config
+ *    field outside its stated range or a non-zero reserved word, records or scratch that are not 16-byte aligned, counts that are not
+ *    4-byte aligned, d_surfels given with max_surfels == 0 or missing with max_surfels > 0, scratch_bytes below rr_surfels_scratch_bytes.
+ *
+ * 2. rr_register_surfels[_device]: n source clouds registered against ONE target of surface points by point-to-line ICP with a FIXED
+ *    iteration count.  The call shape, the state (c, s, tx, ty) in f64, d_init and its normalisation, the flags, the record and d_corr
+ *    are those of rr_register_points_device; the target is d_tgt_surfels[0 .. min(*d_tgt_count, max_tgt)), the count a device uint32_t*
+ *    (a caller passes &counts[g][0] of rr_surface_points_device with max_tgt = its max_surfels).
+ *    One CORRESPONDENCE PASS is steps 1 to 3 of rr_register_points with the surfels' means (x, y) as the target and a range limit of
+ *    2048 in place of 8192: ascending walk, strict d2 < best (ties go to the lower index, a NaN never wins), matched iff px and py are
+ *    finite and below 2048 in magnitude, j* != NONE and best <= gate2.  A target surfel is a candidate iff x and y are finite and below
+ *    2048 in magnitude AND nx and ny are finite and at most 1 in magnitude.
+ *    SUMS.  For a matched pair: P = (int32)rintf(p * 64.0f) per coordinate of the moved point, Q likewise from the surfel's mean,
+ *    M = (int32)rintf(n * 1024.0f) per coordinate of its normal.  e = P - Q, r = Mx*ex + My*ey, a = (Px*My - Py*Mx, Mx, My).
+ *    BOUNDS.  |P|, |Q| <= 2^17, |M| <= 2^10, |e| <= 2^18, so |r| <= 2^29, |a0| <= 2^28, |a1|, |a2| <= 2^10.  Per term and, over at
+ *    most 65,536 = 2^16 pairs, per sum:
+ *        a0*a0 <= 2^56 (sum 2^72)   a0*r <= 2^57 (sum 2^73)   r*r <= 2^58 (sum 2^74): TWO LIMBS each
+ *        a0*a1, a0*a2 <= 2^38 (2^54)   a1*r, a2*r <= 2^39 (2^55)   a1*a1, a1*a2, a2*a2 <= 2^20 (2^36)   N <= 2^16: one int64 each
+ *    A two-limb term T is split BEFORE any reduction as lo = T & 0xFFFFFFFF (0 .. 2^32-1, its sum below 2^48) and hi = T >> 32
+ *    (arithmetic, |hi| <= 2^26, its sum within +-2^42); the solve recombines (double)hi * 4294967296.0 + (double)lo.  So the fourteen
+ *    int64 sums per frame are N, H00lo, H00hi, H01, H02, H11, H12, H22, g0lo, g0hi, g1, g2, rrlo, rrhi (H = sum a a^T, g = sum a*r),
+ *    all exact integers: the result is independent of order.
+ *    One SOLVE is f64, + - * / only but for the closing sqrt of rr_register_points' renormalisation, evaluated as written.  H delta = -g
+ *    by an explicit LDL^T:
+ *        d0 = H00                              l10 = H01/d0    l20 = H02/d0
+ *        d1 = H11 - l10*H01                    m21 = H12 - l20*H01    l21 = m21/d1
+ *        d2 = (H22 - l20*H02) - l21*m21
+ *        z0 = -g0    z1 = -g1 - l10*z0    z2 = (-g2 - l20*z0) - l21*z1
+ *        x2 = z2/d2    x1 = z1/d1 - l21*x2    x0 = (z0/d0 - l10*x1) - l20*x2
+ *    if N < 3 or a pivot d0, d1, d2 is not > 0 (tested as each is formed): flags |= RR_ICP_DEGENERATE and the state keeps its value
+ *    in this iteration.  Else theta = x0 (radians: the units cancel), dtx = x1 / 64, dty = x2 / 64, and the turn by Cayley:
+ *        u = theta/2    dc = (1 - u*u) / (1 + u*u)    ds = (2*u) / (1 + u*u)
+ *    composed onto the state and renormalised exactly as rr_register_points does (c', s', tx', ty' from dc, ds, dtx, dty).
+ *    The call runs `iterations` times (pass, solve), then one last pass.  The record: the state, n_matched = N, flags, and
+ *    sse = rrhi * 2^32 + rrlo in (1/65536 m)^2 (r is in 1/64 m times 1/1024), saturated to INT64_MAX if rrhi >= 2^30.
+ *    The device form enqueues 2 * iterations + 3 launches with no host round trip and touches no context memory but a scratch
+ *    accumulator of 112 bytes per frame kept PER STREAM, as rr_register_points_device does; d_init and d_recs must be 8-byte, the
+ *    target 16-byte aligned.  Refusals are those of rr_register_points[_device].
+ *    LIMITS.  No surfel-to-surfel matching, no weights beyond the gate.  A corridor whose normals are all parallel leaves H singular:
+ *    for normals along an axis or a diagonal a pivot is exactly 0 and the frame is DEGENERATE; for a general direction the rounding
+ *    of the pivots decides.  rr_multi has no such call. */
+typedef struct rr_surfel_config {   /* 32 B */
+    float   cell;              /* metres; cell_q = rintf(cell * 256) in 1..4096 */
+    int32_t width;             /* 1..1024 cells per side of a square grid centred on the sensor origin */
+    int32_t min_points;        /* 2..65536: fewest points of a sample */
+    float   max_ratio;         /* 0..1: largest lmin / lmax */
+    int32_t reserved_[4];      /* 0 */
+} rr_surfel_config;
+
+#define RR_SURFELS_TRUNCATED 1u   /* the frame's count exceeded max_points: the cloud was cut */
+#define RR_SURFELS_CAPPED    2u   /* more surface points were kept than max_surfels: the first max_surfels were written */
+typedef struct rr_surfel {     /* 32 B, two 16-B stores, every byte written */
+    float x, y;                /* the sample's mean, metres */
+    float nx, ny;              /* the unit normal, facing the origin */
+    float var_n, var_t;        /* variance across and along the surface, m^2 */
+    uint32_t count;            /* N of the sample */
+    uint32_t cell;             /* linear cell index iy * width + ix */
+} rr_surfel;
+
+size_t rr_surfels_scratch_bytes(int n_frames, const rr_surfel_config* cfg);   /* 0 for a refused shape */
+/* the blocking of the kernels: points per workgroup of the binning launch, cells per chunk of the scan (tests put counts at their edges) */
+void   rr_surfels_tile_sizes(int* points_tile, int* cells_chunk);
+int rr_surface_points_device(rr_ctx* ctx, const rr_radar_point* d_points, const uint32_t* d_offsets /*[n][n_angles+1]*/, int n_frames,
+                             int max_points, const rr_surfel_config* cfg, rr_surfel* d_surfels /*[n][max_surfels], NULL iff max_surfels == 0*/,
+                             int max_surfels, uint32_t* d_counts /*[n][2]: kept (TRUE total), flags*/, void* d_scratch, size_t scratch_bytes,
+                             void* stream);
+int rr_surface_points(rr_ctx* ctx, const rr_radar_point* points, const uint32_t* offsets, int n_frames, int max_points,
+                      const rr_surfel_config* cfg, rr_surfel* surfels, int max_surfels, uint32_t* counts);   /* host buffers, synchronous */
+int rr_register_surfels_device(rr_ctx* ctx, const rr_radar_point* d_points, const uint32_t* d_offsets /*[n][n_angles+1]*/, int n_frames,
+                               int max_points, const rr_surfel* d_tgt_surfels, const uint32_t* d_tgt_count, int max_tgt,
+                               const double* d_init_or_NULL /*[n][4]*/, float gate, int iterations /*0..64*/, rr_icp_rec* d_recs /*[n]*/,
+                               uint32_t* d_corr_or_NULL /*[n][max_points]*/, void* stream);
+int rr_register_surfels(rr_ctx* ctx, const rr_radar_point* points, const uint32_t* offsets, int n_frames, int max_points,
+                        const rr_surfel* tgt_surfels, uint32_t tgt_count, int max_tgt, const double* init_or_NULL, float gate, int iterations,
+                        rr_icp_rec* recs, uint32_t* corr_or_NULL);                       /* host buffers, synchronous */
+
 /* ---- several GPUs of one node behind one object (SURVEY.md §8b "Threading", §8e) -------------------------
  * The reference creates ONE backend object per process (src/radar_simulator.cpp:145-176) and fans out inside it
  * (OpenMP over azimuths, RadarCPU.cpp:155).  rr_multi is that object for n GPUs: one rr_ctx per device, mesh and

@@ -540,6 +540,42 @@ public:
                                init.empty() ? nullptr : init.data(), gate, iterations, recs.data(), nullptr)) { fail(); recs.clear(); }
         return recs;
     }
+    // Oriented surface points (rr_surfels.hip; include/radarays_mi355.h): clouds (detect() of scans) reduced to sparse surface points, per
+    // occupied cell of cfg's grid the mean of the 3 x 3 block of cells around it and the unit normal of the block's scatter, facing the
+    // sensor.  surfels[f]: cloud f's first max_surfels records in ascending cell order; counts [n][2]: kept (the TRUE total), flags
+    // (RR_SURFELS_*).  false on error
+    bool surfacePoints(const std::vector<std::vector<rr_radar_point>>& clouds, const rr_surfel_config& cfg, std::vector<std::vector<rr_surfel>>& surfels,
+                       std::vector<uint32_t>& counts, int max_surfels = 4096)
+    {
+        surfels.clear(); counts.clear();
+        if (!push()) return false;
+        if (!marshal::surface_points(m_ctx, clouds, m_n_angles, cfg, max_surfels, surfels, counts)) {
+            size_t mp = 0;
+            for (const auto& c : clouds) mp = std::max(mp, c.size());
+            if (clouds.empty() || mp > 65536 || max_surfels < 0) m_err = "surfacePoints: no cloud, a cloud of more than 65536 points, or max_surfels < 0";
+            else fail();
+            return false;
+        }
+        return true;
+    }
+    // ... and registerPointClouds with a point-to-line residual: the clouds registered against ONE target of surface points (surfacePoints
+    // of the real cloud) by planar ICP with a fixed iteration count, from `init` ([n][4] = c s tx ty per cloud) or from the identity.  One
+    // rr_icp_rec per cloud (sse in (1/65536 m)^2); the pose convention is registerPointClouds', so correctedPose applies.  Empty on error
+    std::vector<rr_icp_rec> registerSurfacePoints(const std::vector<std::vector<rr_radar_point>>& clouds, const std::vector<rr_surfel>& target,
+                                                  float gate = 1.0f, int iterations = 10, const std::vector<double>& init = {})
+    {
+        std::vector<rr_icp_rec> recs;
+        if (!push()) return recs;
+        if (!marshal::register_surfels(m_ctx, clouds, m_n_angles, target, init, gate, iterations, recs)) {
+            size_t mp = 0;
+            for (const auto& c : clouds) mp = std::max(mp, c.size());
+            if (clouds.empty() || mp > 65536 || target.size() > 65536 || (!init.empty() && init.size() != 4 * clouds.size()))
+                m_err = "registerSurfacePoints: no cloud, more than 65536 points or surface points, or init is not [n][4]";
+            else fail();
+            recs.clear();
+        }
+        return recs;
+    }
     // the pose hypothesis X_h (qx qy qz qw tx ty tz) whose simulated cloud gave `rec` against the real cloud, corrected: T = X^-1 X_h, so
     // the result is X_h T^-1 -- X_h turned by -atan2(s, c) about its own z axis and moved by -R^T t in its own axes
     static std::array<float, 7> correctedPose(const float* pose7, const rr_icp_rec& rec)

@@ -275,6 +275,67 @@ inline bool correlate_scan(rr_ctx* ctx, const std::vector<rr_radar_point>& scan,
                              &out) == 0;
 }
 
+// n clouds as the cloud calls take them: pts [n][mp] and offs [n][n_angles + 1], of which only each frame's total is read.  Returns mp, the
+// longest cloud (1 at the least); 0 for no cloud or a cloud of more than 65536 points
+inline size_t pack_clouds(const std::vector<std::vector<rr_radar_point>>& clouds, int n_angles, std::vector<rr_radar_point>& pts, std::vector<uint32_t>& offs)
+{
+    const size_t n = clouds.size(), stride = (size_t)n_angles + 1;
+    size_t mp = 1;
+    for (const auto& c : clouds) mp = std::max(mp, c.size());
+    if (n == 0 || mp > 65536) return 0;
+    pts.assign(n * mp, rr_radar_point{});
+    offs.assign(n * stride, 0u);
+    for (size_t f = 0; f < n; f++) {
+        std::copy(clouds[f].begin(), clouds[f].end(), pts.begin() + (std::ptrdiff_t)(f * mp));
+        offs[f * stride + (size_t)n_angles] = (uint32_t)clouds[f].size();
+    }
+    return mp;
+}
+
+// Oriented surface points (rr_surfel_config, rr_surfel; rr_surface_points, host form): n clouds -> per cloud its first
+// min(kept, max_surfels) surface points in ascending cell order, and counts [n][2] = kept (the TRUE total), flags.
+// false: rr_last_error(ctx), or no cloud, a cloud of more than 65536 points or a negative max_surfels
+inline bool surface_points(rr_ctx* ctx, const std::vector<std::vector<rr_radar_point>>& clouds, int n_angles, const rr_surfel_config& cfg,
+                           int max_surfels, std::vector<std::vector<rr_surfel>>& surfels, std::vector<uint32_t>& counts)
+{
+    surfels.clear(); counts.clear();
+    const size_t n = clouds.size();
+    std::vector<rr_radar_point> pts; std::vector<uint32_t> offs;
+    const size_t mp = pack_clouds(clouds, n_angles, pts, offs);
+    if (mp == 0 || max_surfels < 0) return false;
+    const size_t cap = (size_t)max_surfels;
+    std::vector<rr_surfel> recs(n * cap);
+    counts.assign(2 * n, 0u);
+    if (rr_surface_points(ctx, pts.data(), offs.data(), (int)n, (int)mp, &cfg, cap ? recs.data() : nullptr, max_surfels, counts.data()) != 0) {
+        counts.clear();
+        return false;
+    }
+    surfels.resize(n);
+    for (size_t f = 0; f < n; f++)
+        surfels[f].assign(recs.begin() + (std::ptrdiff_t)(f * cap), recs.begin() + (std::ptrdiff_t)(f * cap + std::min<size_t>(counts[2 * f], cap)));
+    return true;
+}
+
+// ... and n clouds registered against ONE target of surface points by point-to-line ICP (rr_register_surfels, host form), from the states
+// `init` ([n][4] = c s tx ty per cloud) or, if it is empty, from the identity: one rr_icp_rec per cloud.  false: rr_last_error(ctx), or no
+// cloud, a cloud or a target of more than 65536 records, or an init that is not [n][4]
+inline bool register_surfels(rr_ctx* ctx, const std::vector<std::vector<rr_radar_point>>& clouds, int n_angles, const std::vector<rr_surfel>& target,
+                             const std::vector<double>& init, float gate, int iterations, std::vector<rr_icp_rec>& recs)
+{
+    recs.clear();
+    const size_t n = clouds.size();
+    std::vector<rr_radar_point> pts; std::vector<uint32_t> offs;
+    const size_t mp = pack_clouds(clouds, n_angles, pts, offs);
+    if (mp == 0 || target.size() > 65536 || (!init.empty() && init.size() != 4 * n)) return false;
+    recs.resize(n);
+    if (rr_register_surfels(ctx, pts.data(), offs.data(), (int)n, (int)mp, target.empty() ? nullptr : target.data(), (uint32_t)target.size(),
+                            (int)target.size(), init.empty() ? nullptr : init.data(), gate, iterations, recs.data(), nullptr) != 0) {
+        recs.clear();
+        return false;
+    }
+    return true;
+}
+
 // map refinement: the nearest-cell table [height][width] of an occupancy map (occupied: >= threshold; rr_nearest_field), 0xFFFFFFFF where no
 // occupied cell lies within cfg.max_dist.  false: rr_last_error(ctx), or a map that is not [height][width]
 inline bool build_nearest(rr_ctx* ctx, const std::vector<uint8_t>& occ, int threshold, const rr_field_config& cfg, std::vector<uint32_t>& nearest)

@@ -78,6 +78,16 @@ public:
     bool simulateParamSets(const std::vector<RadarParams>& sets, ros::Time stamp, std::vector<sensor_msgs::ImagePtr>* images,
                            const sensor_msgs::Image* real = nullptr, std::vector<double>* psnr = nullptr);
 
+    // Oriented surface points and point-to-line scan matching (radarays_mi355.h, "oriented surface points"; device 0): clouds of
+    // rr_detect reduced to sparse surface points -- surfels[f]: cloud f's first max_surfels records in ascending cell order,
+    // counts [n][2] = kept, flags -- and clouds registered against ONE such target, from `init` ([n][4] = c s tx ty) or from the
+    // identity: one rr_icp_rec per cloud, the transform that maps the cloud into the target's frame.  false / empty on error
+    bool surfacePoints(const std::vector<std::vector<rr_radar_point> >& clouds, const rr_surfel_config& cfg,
+                       std::vector<std::vector<rr_surfel> >& surfels, std::vector<uint32_t>& counts, int max_surfels = 4096);
+    std::vector<rr_icp_rec> registerSurfacePoints(const std::vector<std::vector<rr_radar_point> >& clouds, const std::vector<rr_surfel>& target,
+                                                  float gate = 1.0f, int iterations = 10,
+                                                  const std::vector<double>& init = std::vector<double>());
+
 protected:
     void init(const std::vector<float>& verts, const std::vector<uint32_t>& faces, const std::vector<uint32_t>& face_object,
               const std::vector<int>& devices, bool build_on_gpu);

@@ -424,4 +424,37 @@ bool RadarHIP::simulateParamSets(const std::vector<RadarParams>& sets, ros::Time
     return true;
 }
 
+bool RadarHIP::surfacePoints(const std::vector<std::vector<rr_radar_point> >& clouds, const rr_surfel_config& cfg,
+                             std::vector<std::vector<rr_surfel> >& surfels, std::vector<uint32_t>& counts, int max_surfels)
+{
+    if(!pushState())
+    {
+        return false;
+    }
+    if(!marshal::surface_points(m_ctx, clouds, m_n_angles, cfg, max_surfels, surfels, counts))
+    {
+        ROS_WARN_STREAM("[RadarHIP] surfacePoints: " << (clouds.empty() || max_surfels < 0 ? "no cloud, or max_surfels < 0" : rr_last_error(m_ctx)));
+        return false;
+    }
+    return true;
+}
+
+std::vector<rr_icp_rec> RadarHIP::registerSurfacePoints(const std::vector<std::vector<rr_radar_point> >& clouds,
+                                                         const std::vector<rr_surfel>& target, float gate, int iterations,
+                                                         const std::vector<double>& init)
+{
+    std::vector<rr_icp_rec> recs;
+    if(!pushState())
+    {
+        return recs;
+    }
+    if(!marshal::register_surfels(m_ctx, clouds, m_n_angles, target, init, gate, iterations, recs))
+    {
+        const bool shape = clouds.empty() || (!init.empty() && init.size() != 4 * clouds.size());
+        ROS_WARN_STREAM("[RadarHIP] registerSurfacePoints: " << (shape ? "no cloud, or init is not [n][4]" : rr_last_error(m_ctx)));
+        recs.clear();
+    }
+    return recs;
+}
+
 } // namespace radarays_ros

@@ -203,6 +203,8 @@ struct rr_ctx {
     // rr_register_points_device: the eight int64 sums per frame, one buffer per stream it has been called on (icp_mu guards the map, not the
     // buffers: calls on one stream are ordered by that stream)
     std::map<hipStream_t, DevBuf<long long>> icp_acc; std::mutex icp_mu;
+    // rr_register_surfels_device: the fourteen int64 sums per frame, per stream in the same way (icp_mu guards this map too)
+    std::map<hipStream_t, DevBuf<long long>> line_acc;
     // rr_slice_mesh_device: the large list (its counter, then one word per triangle record), one buffer per stream like icp_acc
     std::map<hipStream_t, DevBuf<uint32_t>> slice_list; std::mutex slice_mu;
     // rr_align_images_device: one chunk's curves (when the caller gives no buffer) and sums, the records

@@ -144,6 +144,33 @@ int check_icp(rr_ctx* c, const char* who, const void* points, const void* offset
     return 0;
 }
 
+// the refusals of rr_surfels_scratch_bytes and, behind it, of the surface-point calls: the shape alone
+const char* bad_surfels_shape(int n_frames, const rr_surfel_config* g)
+{
+    if (!g) return "null config";
+    if (n_frames < 1 || n_frames > 65535) return "n_frames must be 1..65535";
+    if (!(std::isfinite(g->cell) && g->cell > 0.0f && g->cell <= 16.0f) || rintf(g->cell * 256.0f) < 1.0f || rintf(g->cell * 256.0f) > 4096.0f)
+        return "cell must give rintf(cell * 256) in 1..4096";
+    if (g->width < 1 || g->width > 1024) return "width must be 1..1024";
+    if (g->min_points < 2 || g->min_points > 65536) return "min_points must be 2..65536";
+    if (!(g->max_ratio >= 0.0f && g->max_ratio <= 1.0f)) return "max_ratio must be 0..1";
+    for (int k = 0; k < 4; k++) if (g->reserved_[k] != 0) return "reserved_ must be 0";
+    return nullptr;
+}
+
+// the refusals of rr_surface_points_device / rr_surface_points: the config gives n_angles, the offsets' stride
+int check_surfels(rr_ctx* c, const std::string& w, const void* points, const void* offsets, int n_frames, int max_points, const rr_surfel_config* g,
+                  const void* surfels, int max_surfels, const void* counts)
+{
+    const bool sizes_ok = max_points >= 0 && max_points <= 65536;
+    int rc = check_images(c, w, offsets && counts && (!sizes_ok || max_points == 0 || points), "buffer", "n_frames", n_frames, 65535); if (rc) return rc;
+    if (!sizes_ok) return fail(c, -3, w + ": max_points must be 0..65536");
+    if (const char* bad = bad_surfels_shape(n_frames, g)) return fail(c, -3, w + ": " + bad);
+    if (max_surfels < 0 || max_surfels > (1 << 20)) return fail(c, -3, w + ": max_surfels must be 0..1048576");
+    if (!surfels != (max_surfels == 0)) return fail(c, -3, w + ": the records come with max_surfels > 0 and only with it");
+    return 0;
+}
+
 // the refusals the likelihood-field and the occupancy calls share: the shape and the place of a grid within their stated ranges
 int check_grid_shape(rr_ctx* c, const std::string& w, const rr_field_config* g)
 {
@@ -1627,6 +1654,105 @@ int rr_correlate_scan(rr_ctx* c, const rr_radar_point* points, uint32_t count, i
     RR_HIP(c, st.room(scratch, d_scratch));
     RR_HIP(c, hipStreamSynchronize(c->stream));        // (count is this call's own variable)
     rc = rr_correlate_scan_device(c, d_points, d_count, max_points, d_rot, n_rot, d_pyramid, cfg, corr, d_rec, d_scratch, scratch, c->stream);
+    if (rc) return rc;
+    return st.commit();
+}
+
+// ---- oriented surface points and point-to-line scan matching (rr_surfels.hip) ------------------------------------------------------
+void rr_surfels_tile_sizes(int* points_tile, int* cells_chunk) { surfels_tile_sizes(points_tile, cells_chunk); }
+
+size_t rr_surfels_scratch_bytes(int n_frames, const rr_surfel_config* cfg)
+{
+    if (bad_surfels_shape(n_frames, cfg)) return 0;
+    return surfels_scratch_bytes((size_t)n_frames, (size_t)cfg->width * cfg->width);
+}
+
+int rr_surface_points_device(rr_ctx* c, const rr_radar_point* d_points, const uint32_t* d_offsets, int n_frames, int max_points,
+                             const rr_surfel_config* cfg, rr_surfel* d_surfels, int max_surfels, uint32_t* d_counts, void* d_scratch,
+                             size_t scratch_bytes, void* stream)
+{
+    const std::string w("rr_surface_points_device");
+    int rc = check_surfels(c, w, d_points, d_offsets, n_frames, max_points, cfg, d_surfels, max_surfels, d_counts); if (rc) return rc;
+    if (!d_scratch) return fail(c, -3, w + ": null scratch");
+    if ((uintptr_t)d_scratch % 16 != 0 || (uintptr_t)d_surfels % 16 != 0) return fail(c, -3, w + ": the scratch and the records must be 16-byte aligned");
+    if ((uintptr_t)d_counts % 4 != 0) return fail(c, -3, w + ": the counts must be 4-byte aligned");
+    const size_t need = rr_surfels_scratch_bytes(n_frames, cfg);
+    if (scratch_bytes < need) return fail(c, -3, w + ": scratch of " + std::to_string(scratch_bytes) + " bytes, the call needs " + std::to_string(need));
+    RR_HIP(c, hipSetDevice(c->device));
+    RR_HIP(c, launch_surface_points(d_points, d_offsets, n_frames, c->cfg.n_angles, max_points, *cfg, d_surfels, max_surfels, d_counts, d_scratch,
+                                    stream_of(c, stream)));
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_surface_points(rr_ctx* c, const rr_radar_point* points, const uint32_t* offsets, int n_frames, int max_points, const rr_surfel_config* cfg,
+                      rr_surfel* surfels, int max_surfels, uint32_t* counts)
+{
+    int rc = check_surfels(c, "rr_surface_points", points, offsets, n_frames, max_points, cfg, surfels, max_surfels, counts); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)n_frames, cap = (size_t)max_surfels, scratch = rr_surfels_scratch_bytes(n_frames, cfg);
+    RR_STAGE(c, st);
+    std::vector<uint32_t> totals, kept(n), both(2 * n); rr_radar_point* d_points; uint32_t *d_offs, *d_counts; rr_surfel* d_surfels; uint8_t* d_scratch;
+    rc = up_points(c, st, points, offsets, n, (size_t)max_points, totals, d_points, d_offs); if (rc) return rc;
+    // the records of frame f that exist, min(kept, max_surfels), and nothing beyond them: the kept totals are every second word of counts
+    RR_HIP(c, st.hold_rows(surfels, n, cap, cap, kept.data(), d_surfels));
+    RR_HIP(c, st.room(2 * n, d_counts));
+    RR_HIP(c, st.room(scratch, d_scratch));
+    rc = rr_surface_points_device(c, d_points, d_offs, n_frames, max_points, cfg, d_surfels, max_surfels, d_counts, d_scratch, scratch, c->stream);
+    if (rc) return rc;
+    // (the totals come home first, on their own, because the records' scatter reads them)
+    RR_HIP(c, hipMemcpyAsync(both.data(), d_counts, 2 * n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    RR_HIP(c, hipStreamSynchronize(c->stream));
+    for (size_t f = 0; f < n; f++) kept[f] = both[2 * f];
+    rc = st.commit(); if (rc) return rc;
+    std::memcpy(counts, both.data(), 2 * n * sizeof(uint32_t));
+    return 0;
+}
+
+int rr_register_surfels_device(rr_ctx* c, const rr_radar_point* d_points, const uint32_t* d_offsets, int n_frames, int max_points,
+                               const rr_surfel* d_tgt_surfels, const uint32_t* d_tgt_count, int max_tgt, const double* d_init, float gate,
+                               int iterations, rr_icp_rec* d_recs, uint32_t* d_corr, void* stream)
+{
+    int rc = check_icp(c, "rr_register_surfels_device", d_points, d_offsets, n_frames, max_points, d_tgt_surfels, d_tgt_count != nullptr, max_tgt, gate,
+                       iterations, d_recs); if (rc) return rc;
+    if ((uintptr_t)d_init % 8 != 0 || (uintptr_t)d_recs % 8 != 0) return fail(c, -3, "rr_register_surfels_device: d_init and d_recs must be 8-byte aligned");
+    if ((uintptr_t)d_tgt_surfels % 16 != 0) return fail(c, -3, "rr_register_surfels_device: the target must be 16-byte aligned");
+    RR_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = stream_of(c, stream);
+    long long* acc = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(c->icp_mu);
+        DevBuf<long long>& b = c->line_acc[s];
+        RR_HIP(c, b.ensure(line_scratch_words((size_t)n_frames)));
+        acc = b.p;
+    }
+    launch_register_surfels(d_points, d_offsets, n_frames, c->cfg.n_angles, max_points, d_tgt_surfels, d_tgt_count, max_tgt, d_init, gate, iterations,
+                            d_recs, d_corr, acc, s);
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_register_surfels(rr_ctx* c, const rr_radar_point* points, const uint32_t* offsets, int n_frames, int max_points, const rr_surfel* tgt_surfels,
+                        uint32_t tgt_count, int max_tgt, const double* init, float gate, int iterations, rr_icp_rec* recs, uint32_t* corr)
+{
+    const std::string w("rr_register_surfels");
+    int rc = check_icp(c, w.c_str(), points, offsets, n_frames, max_points, tgt_surfels, true, max_tgt, gate, iterations, recs); if (rc) return rc;
+    const size_t n = (size_t)n_frames, mp = (size_t)max_points, mt = (size_t)max_tgt;
+    for (size_t f = 0; init && f < n; f++) {
+        const double h = std::sqrt(init[4 * f] * init[4 * f] + init[4 * f + 1] * init[4 * f + 1]);
+        if (!(h > 0.0 && std::isfinite(h))) return fail(c, -3, w + ": an initial state whose (c, s) has a zero or non-finite length");
+    }
+    RR_HIP(c, hipSetDevice(c->device));
+    RR_STAGE(c, st);
+    std::vector<uint32_t> totals; rr_radar_point* d_src; rr_surfel* d_tgt; uint32_t *d_offs, *d_count, *d_corr; double* d_init; rr_icp_rec* d_recs;
+    rc = up_points(c, st, points, offsets, n, mp, totals, d_src, d_offs); if (rc) return rc;
+    RR_HIP(c, st.up_rows(tgt_surfels, 1, mt, &tgt_count, d_tgt));
+    RR_HIP(c, st.up(&tgt_count, 1, d_count));
+    RR_HIP(c, st.up(init, n * 4, d_init));
+    RR_HIP(c, st.hold(recs, n, d_recs));
+    RR_HIP(c, st.hold_rows(corr, n, mp, mp, totals.data(), d_corr));
+    RR_HIP(c, hipStreamSynchronize(c->stream));        // (tgt_count is this call's own variable)
+    rc = rr_register_surfels_device(c, d_src, d_offs, n_frames, max_points, d_tgt, d_count, max_tgt, d_init, gate, iterations, d_recs, d_corr, c->stream);
     if (rc) return rc;
     return st.commit();
 }

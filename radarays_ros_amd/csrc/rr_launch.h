@@ -136,6 +136,17 @@ size_t correlate_scratch_bytes(size_t n_rot, size_t max_points, int levels, size
 void launch_field_pyramid(const uint16_t* field, const rr_field_config& g, int levels, uint16_t* pyramid, hipStream_t s);
 void launch_correlate(const rr_radar_point* points, const uint32_t* count, int max_points, const float* rot, int n_rot, const uint16_t* pyramid,
                       const rr_field_config& g, const rr_corr_config& c, rr_corr_rec* rec, void* scratch, hipStream_t s);
+// rr_surfels.hip (oriented surface points, point-to-line scan matching).  scratch: surfels_scratch_bytes for n_cells = width * width, 16-byte aligned
+// like surfels (null iff max_surfels == 0); its contents before the call do not matter; counts [n_frames][2].  A memset (its error is returned) and
+// four launches.  acc: line_scratch_words(n_frames) int64 words, zeroed by the first launch; recs and init 8-byte, tgt 16-byte aligned
+void surfels_tile_sizes(int* points_tile, int* cells_chunk);
+size_t surfels_scratch_bytes(size_t n_frames, size_t n_cells);
+hipError_t launch_surface_points(const rr_radar_point* points, const uint32_t* offsets, int n_frames, int n_angles, int max_points,
+                                 const rr_surfel_config& cfg, rr_surfel* surfels, int max_surfels, uint32_t* counts, void* scratch, hipStream_t s);
+size_t line_scratch_words(size_t n_frames);
+void launch_register_surfels(const rr_radar_point* points, const uint32_t* offsets, int n_frames, int n_angles, int max_points, const rr_surfel* tgt,
+                             const uint32_t* tgt_count, int max_tgt, const double* init, float gate, int iterations, rr_icp_rec* recs,
+                             uint32_t* corr, long long* acc, hipStream_t s);
 // rr_notes.hip (object annotations).  scratch: note_scratch_bytes, 16-byte aligned like notes; every word of it, of notes and of skipped is written by the launches
 size_t note_scratch_bytes(size_t n_frames, size_t n_objects, int n_angles);
 void launch_notes(const uint32_t* labels, const uint8_t* imgs, int n_frames, uint32_t n_objects, uint32_t extent_mask, const PolarGrid& G,

@@ -92,4 +92,77 @@ template <class State> __device__ inline bool icp_solve(const long long* S, Stat
     return false;
 }
 
+// ---- the point-to-line step of the header (rr_register_surfels): the fourteen sums over the matched pairs, and the LDL^T solve ----
+enum { L_N = 0, L_H00LO, L_H00HI, L_H01, L_H02, L_H11, L_H12, L_H22, L_G0LO, L_G0HI, L_G1, L_G2, L_RRLO, L_RRHI, L_COUNT };
+
+// a term that may pass 2^63 over 65,536 pairs, split before any reduction: lo in 0 .. 2^32-1, hi the arithmetic shift
+__device__ inline void line_limbs(long long* sum, int lo, long long t)
+{
+    sum[lo] += t & 0xFFFFFFFFll;
+    sum[lo + 1] += t >> 32;
+}
+__device__ inline double line_join(const long long* S, int lo) { return (double)S[lo + 1] * 4294967296.0 + (double)S[lo]; }
+
+// one matched pair: moved point p and surfel mean q quantised to 1/64 m, the surfel's normal to 1/1024.  Exact because the matcher matches
+// only coordinates below kLineRange = 2048 and normal components of at most 1 in magnitude: |P|, |Q| <= 2^17, |M| <= 2^10, so |r| <= 2^29,
+// |a0| <= 2^28, and every term is below 2^58 (the header lists each term's and each sum's bound)
+__device__ inline void line_accumulate(long long* sum, float px, float py, float qx, float qy, float nx, float ny)
+{
+    const int32_t Px = (int32_t)rintf(px * 64.0f), Py = (int32_t)rintf(py * 64.0f);
+    const int32_t Qx = (int32_t)rintf(qx * 64.0f), Qy = (int32_t)rintf(qy * 64.0f);
+    const long long Mx = (int32_t)rintf(nx * 1024.0f), My = (int32_t)rintf(ny * 1024.0f);
+    const long long ex = Px - Qx, ey = Py - Qy;
+    const long long r = Mx * ex + My * ey;
+    const long long a0 = (long long)Px * My - (long long)Py * Mx;
+    sum[L_N] += 1;
+    line_limbs(sum, L_H00LO, a0 * a0);
+    sum[L_H01] += a0 * Mx; sum[L_H02] += a0 * My;
+    sum[L_H11] += Mx * Mx; sum[L_H12] += Mx * My; sum[L_H22] += My * My;
+    line_limbs(sum, L_G0LO, a0 * r);
+    sum[L_G1] += Mx * r; sum[L_G2] += My * r;
+    line_limbs(sum, L_RRLO, r * r);
+}
+
+// sse of the record: rrhi * 2^32 + rrlo in (1/65536 m)^2, saturated
+__device__ inline long long line_sse(const long long* S)
+{
+    return S[L_RRHI] >= (1ll << 30) ? 0x7FFFFFFFFFFFFFFFll : S[L_RRHI] * 4294967296ll + S[L_RRLO];
+}
+
+// the SOLVE: H delta = -g by an explicit LDL^T, f64, + - * / and the renormalisation's sqrt, evaluated as written.  True for a degenerate
+// step (fewer than 3 pairs, or a pivot that is not > 0): the state is kept
+template <class State> __device__ inline bool line_solve(const long long* S, State& st)
+{
+    if (S[L_N] < 3) return true;
+    const double H00 = line_join(S, L_H00LO), H01 = (double)S[L_H01], H02 = (double)S[L_H02];
+    const double H11 = (double)S[L_H11], H12 = (double)S[L_H12], H22 = (double)S[L_H22];
+    const double g0 = line_join(S, L_G0LO), g1 = (double)S[L_G1], g2 = (double)S[L_G2];
+    const double d0 = H00;
+    if (!(d0 > 0.0)) return true;
+    const double l10 = H01 / d0, l20 = H02 / d0;
+    const double d1 = H11 - l10 * H01;
+    if (!(d1 > 0.0)) return true;
+    const double m21 = H12 - l20 * H01;
+    const double l21 = m21 / d1;
+    const double d2 = (H22 - l20 * H02) - l21 * m21;
+    if (!(d2 > 0.0)) return true;
+    const double z0 = -g0;
+    const double z1 = -g1 - l10 * z0;
+    const double z2 = (-g2 - l20 * z0) - l21 * z1;
+    const double x2 = z2 / d2;
+    const double x1 = z1 / d1 - l21 * x2;
+    const double x0 = (z0 / d0 - l10 * x1) - l20 * x2;
+    const double u = x0 / 2.0;
+    const double dc = (1.0 - u * u) / (1.0 + u * u), ds = (2.0 * u) / (1.0 + u * u);
+    const double dtx = x1 / 64.0, dty = x2 / 64.0;
+    const double c = st.c, s = st.s, tx = st.tx, ty = st.ty;
+    const double c1 = dc * c - ds * s;
+    const double s1 = ds * c + dc * s;
+    const double tx1 = (dc * tx - ds * ty) + dtx;
+    const double ty1 = (ds * tx + dc * ty) + dty;
+    const double nrm = sqrt(c1 * c1 + s1 * s1);
+    st.c = c1 / nrm; st.s = s1 / nrm; st.tx = tx1; st.ty = ty1;
+    return false;
+}
+
 }  // namespace rr

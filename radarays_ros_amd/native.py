@@ -545,6 +545,58 @@ def corr_node(rec, half_x, half_y):
     return (int(rec["rot"]) * (2 * half_y + 1) + int(rec["dy"]) + half_y) * (2 * half_x + 1) + int(rec["dx"]) + half_x
 
 
+# ---- oriented surface points and point-to-line scan matching (rr_surfels.hip): rr_surfel_config (32 B) and rr_surfel (32 B)
+SURFEL_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("var_n", "<f4"), ("var_t", "<f4"), ("count", "<u4"), ("cell", "<u4")])
+SURFELS_TRUNCATED, SURFELS_CAPPED = 1, 2
+SURFELS_MAX_WIDTH, SURFELS_MAX_CELL_Q, SURFELS_MAX_RECORDS = 1024, 4096, 1 << 20
+RRSurfel = np.ctypeslib.as_ctypes_type(SURFEL_DTYPE)
+
+
+class RRSurfelConfig(C.Structure):
+    _fields_ = [("cell", C.c_float), ("width", C.c_int32), ("min_points", C.c_int32), ("max_ratio", C.c_float), ("reserved_", C.c_int32 * 4)]
+
+
+def surfel_cell_q(cell):
+    """cell_q = rintf(cell * 256) of a cell size in metres, as the library takes it (f32)"""
+    try:
+        with np.errstate(over="ignore", invalid="ignore"):
+            q = np.rint(np.float32(cell) * np.float32(256.0))
+    except (TypeError, ValueError):
+        raise ValueError("cell must be a number, got %r" % (cell,))
+    if isinstance(cell, bool) or not (np.isfinite(q) and 1 <= q <= SURFELS_MAX_CELL_Q):
+        raise ValueError("cell must give rintf(cell * 256) in 1..%d, got %r" % (SURFELS_MAX_CELL_Q, cell))
+    return int(q)
+
+
+def surfel_config(cell, width, min_points=3, max_ratio=0.1):
+    """rr_surfel_config, range-checked before any call into the library: square cells of `cell` metres (rintf(cell * 256) in 1..4096),
+    `width` cells per side (1..1024) centred on the sensor, a surface point needs min_points (2..65536) points in its 3 x 3 block and
+    lambda_min <= max_ratio * lambda_max (max_ratio in 0..1)"""
+    surfel_cell_q(cell)
+    if isinstance(max_ratio, bool) or not isinstance(max_ratio, (int, float, np.integer, np.floating)) or not 0.0 <= float(np.float32(max_ratio)) <= 1.0:
+        raise ValueError("max_ratio must be a number in [0, 1], got %r" % (max_ratio,))
+    return RRSurfelConfig(float(np.float32(cell)), _int_in(width, 1, SURFELS_MAX_WIDTH, "width"), _int_in(min_points, 2, 65536, "min_points"),
+                          float(np.float32(max_ratio)), (C.c_int32 * 4)(0, 0, 0, 0))
+
+
+def _surfel_cfg(cfg):
+    """an RRSurfelConfig (surfel_config makes one; held to its ranges again) or a dict of surfel_config's arguments"""
+    if isinstance(cfg, RRSurfelConfig):
+        if any(cfg.reserved_):
+            raise ValueError("reserved_ must be 0")
+        return surfel_config(cfg.cell, cfg.width, cfg.min_points, cfg.max_ratio)
+    if isinstance(cfg, dict):
+        return surfel_config(**cfg)
+    raise ValueError("a surfel config must be an RRSurfelConfig (native.surfel_config makes one) or a dict of its arguments, got %r" % (cfg,))
+
+
+def surfels_tile_sizes():
+    """(points per workgroup of the binning launch, cells per chunk of the scan) of rr_surfels.hip"""
+    a, b = C.c_int(0), C.c_int(0)
+    lib().rr_surfels_tile_sizes(C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
 # rr_default_detect_config
 DETECT_DEFAULTS ={"method": 0, "guard_cells": 2, "train_cells": 16, "k": 12, "min_intensity": 1, "min_bin": 0, "cfar_scale": 3.0}
 DETECT_METHODS = {"cfar": 0, "ca-cfar": 0, "kstrongest": 1, "k-strongest": 1, 0: 0, 1: 1}
@@ -669,6 +721,7 @@ STRUCTS = {
     "rr_beam_config": (RRBeamConfig, None), "rr_beam_rec": (RRBeamRec, BEAM_DTYPE), "rr_slice_config": (RRSliceConfig, None),
     "rr_components_config": (RRComponentsConfig, None), "rr_component": (RRComponent, COMPONENT_DTYPE),
     "rr_corr_config": (RRCorrConfig, None), "rr_corr_rec": (RRCorrRec, CORR_DTYPE),
+    "rr_surfel_config": (RRSurfelConfig, None), "rr_surfel": (RRSurfel, SURFEL_DTYPE),
 }
 
 
@@ -838,6 +891,13 @@ def _prototypes():
         "rr_field_pyramid": (i, [vp, vp, P(RRFieldConfig), i, vp]),
         "rr_correlate_scan_device": (i, [vp, vp, vp, i, vp, i, vp, P(RRFieldConfig), P(RRCorrConfig), vp, vp, sz, vp]),
         "rr_correlate_scan": (i, [vp, vp, u32, i, vp, i, vp, P(RRFieldConfig), P(RRCorrConfig), vp]),
+        # ---- oriented surface points and point-to-line scan matching (rr_surfels.hip)
+        "rr_surfels_scratch_bytes": (sz, [i, P(RRSurfelConfig)]),
+        "rr_surfels_tile_sizes": (None, [P(i), P(i)]),
+        "rr_surface_points_device": (i, [vp, vp, vp, i, i, P(RRSurfelConfig), vp, i, vp, vp, sz, vp]),
+        "rr_surface_points": (i, [vp, vp, vp, i, i, P(RRSurfelConfig), vp, i, vp]),
+        "rr_register_surfels_device": (i, [vp, vp, vp, i, i, vp, vp, i, vp, f, i, vp, vp, vp]),
+        "rr_register_surfels": (i, [vp, vp, vp, i, i, vp, u32, i, vp, f, i, vp, vp]),
         # ---- several GPUs of one node behind one object (rr_multi.hip)
         "rr_create_multi": (vp, [P(i), i]),
         "rr_destroy_multi": (None, [vp]),
@@ -1833,6 +1893,84 @@ class Context(_Scene):
         self._ck(self._L.rr_register_points(self._h, buf.ctypes.data, offs.ctypes.data, n, mp, tgt.ctypes.data if len(tgt) else None, len(tgt),
                                             len(tgt), _ptr(x0), g, it, recs.ctypes.data,
                                             corr.ctypes.data if want_corr else None))
+        if want_corr:
+            return recs, [corr[f, :k].copy() for f, k in enumerate(lens)]
+        return recs
+
+    # ---- oriented surface points and point-to-line scan matching (rr_surfels.hip); any context with a config, mesh or not
+    @staticmethod
+    def surfels_scratch_bytes(n_frames, cfg):
+        """rr_surfels_scratch_bytes: the bytes of scratch rr_surface_points_device needs for n_frames clouds under cfg"""
+        g = _surfel_cfg(cfg)
+        return int(lib().rr_surfels_scratch_bytes(_frames_arg(n_frames), C.byref(g)))
+
+    def surface_points_device(self, d_points_ptr, d_offsets_ptr, n_frames, max_points, cfg, d_surfels_ptr, max_surfels, d_counts_ptr, d_scratch_ptr,
+                              scratch_bytes, stream=None):
+        """rr_surface_points_device on raw device addresses: the points [n_frames][max_points] and offsets [n_frames][n_angles + 1]
+        rr_detect_device wrote -> SURFEL_DTYPE records [n_frames][max_surfels] in ascending cell order (None iff max_surfels is 0) and counts
+        uint32 [n_frames][2] = (kept, flags).  The scratch (surfels_scratch_bytes, 16-byte aligned like the records) is the caller's; nothing
+        of the context is used, so the call may run on any stream.  Every argument is checked here first."""
+        self._polar_shape()
+        g, n = _surfel_cfg(cfg), _frames_arg(n_frames)
+        mp, ms = _int_in(max_points, 0, ICP_MAX_POINTS, "max_points"), _int_in(max_surfels, 0, SURFELS_MAX_RECORDS, "max_surfels")
+        if not (d_offsets_ptr and d_counts_ptr and d_scratch_ptr) or (mp > 0 and not d_points_ptr):
+            raise ValueError("surface_points_device needs point, offset, count and scratch buffers")
+        if bool(d_surfels_ptr) != (ms > 0):
+            raise ValueError("the records come with max_surfels > 0 and only with it")
+        if (d_surfels_ptr or 0) % 16 or d_scratch_ptr % 16 or d_counts_ptr % 4:
+            raise ValueError("the records and the scratch must be 16-byte aligned, the counts 4-byte aligned")
+        need = self.surfels_scratch_bytes(n, g)
+        if isinstance(scratch_bytes, bool) or not isinstance(scratch_bytes, (int, np.integer)) or scratch_bytes < need:
+            raise ValueError("scratch of %r bytes, the call needs %d" % (scratch_bytes, need))
+        self._ck(self._L.rr_surface_points_device(self._h, d_points_ptr, d_offsets_ptr, n, mp, C.byref(g), d_surfels_ptr, ms, d_counts_ptr,
+                                                  d_scratch_ptr, int(scratch_bytes), stream))
+
+    def surface_points(self, points_list, offsets, cfg, max_surfels=4096):
+        """rr_surface_points on what detect() (or compensate_points()) returned: a list of n POINT_DTYPE arrays and offsets uint32
+        [n][n_angles + 1] -> (a list with one SURFEL_DTYPE array per cloud: its first min(kept, max_surfels) surface points in ascending
+        cell order, counts uint32 [n][2] = (kept, flags))"""
+        _, n_angles = self._polar_shape()
+        g, ms = _surfel_cfg(cfg), _int_in(max_surfels, 0, SURFELS_MAX_RECORDS, "max_surfels")
+        buf, offs, _ = _clouds(points_list, offsets, n_angles, True)
+        n, mp = buf.shape
+        recs = np.zeros((n, ms), SURFEL_DTYPE) if ms else None
+        counts = np.zeros((n, 2), np.uint32)
+        self._ck(self._L.rr_surface_points(self._h, buf.ctypes.data, offs.ctypes.data, n, mp, C.byref(g), _ptr(recs), ms, counts.ctypes.data))
+        return [recs[f, :min(int(counts[f, 0]), ms)].copy() if ms else np.zeros(0, SURFEL_DTYPE) for f in range(n)], counts
+
+    def register_surfels_device(self, d_points_ptr, d_offsets_ptr, n_frames, max_points, d_tgt_surfels_ptr, d_tgt_count_ptr, max_tgt, d_recs_ptr,
+                                d_init_ptr=None, gate=1.0, iterations=10, d_corr_ptr=None, stream=None):
+        """rr_register_surfels_device: register_points_device with SURFEL_DTYPE records [max_tgt] (16-byte aligned) as the target, whose
+        count is the uint32 at d_tgt_count_ptr (&counts[g][0] of surface_points_device): point-to-line ICP"""
+        self._polar_shape()
+        n = _frames_arg(n_frames)
+        mp, mt = _int_in(max_points, 0, ICP_MAX_POINTS, "max_points"), _int_in(max_tgt, 0, ICP_MAX_POINTS, "max_tgt")
+        it, g = _int_in(iterations, 0, 64, "iterations"), _icp_gate(gate)
+        if not d_offsets_ptr or not d_tgt_count_ptr or not d_recs_ptr or (mp > 0 and not d_points_ptr) or (mt > 0 and not d_tgt_surfels_ptr):
+            raise ValueError("register_surfels_device needs point, offset, target, target count and record buffers")
+        if (d_tgt_surfels_ptr or 0) % 16:
+            raise ValueError("the target must be 16-byte aligned")
+        self._ck(self._L.rr_register_surfels_device(self._h, d_points_ptr, d_offsets_ptr, n, mp, d_tgt_surfels_ptr, d_tgt_count_ptr, mt, d_init_ptr,
+                                                    g, it, d_recs_ptr, d_corr_ptr, stream))
+
+    def register_surfels(self, points_list, offsets, target_surfels, init=None, gate=1.0, iterations=10, want_corr=False):
+        """rr_register_surfels: register_points with ONE SURFEL_DTYPE array (what surface_points returned for the target cloud) as the
+        target and a point-to-line residual.  Returns ICP_DTYPE [n] (sse in (1/65536 m)^2); with want_corr also the matched surfel index
+        per point, ICP_NONE for an unmatched point."""
+        _, n_angles = self._polar_shape()
+        pts = _cloud_list(points_list)
+        tgt = np.asarray(target_surfels)
+        if tgt.dtype != SURFEL_DTYPE or tgt.ndim != 1 or len(tgt) > ICP_MAX_POINTS:
+            raise ValueError("the target must be a one-dimensional SURFEL_DTYPE array of at most %d records" % ICP_MAX_POINTS)
+        tgt = np.ascontiguousarray(tgt)
+        buf, offs, lens = _clouds(pts, offsets, n_angles, True)
+        n, mp = buf.shape
+        x0 = _icp_init(init, n)
+        it, g = _int_in(iterations, 0, 64, "iterations"), _icp_gate(gate)
+        recs = np.zeros(n, ICP_DTYPE)
+        corr = np.full((n, mp), ICP_NONE, np.uint32) if want_corr else None
+        self._ck(self._L.rr_register_surfels(self._h, buf.ctypes.data, offs.ctypes.data, n, mp, tgt.ctypes.data if len(tgt) else None, len(tgt),
+                                             len(tgt), _ptr(x0), g, it, recs.ctypes.data, _ptr(corr)))
         if want_corr:
             return recs, [corr[f, :k].copy() for f, k in enumerate(lens)]
         return recs

@@ -408,6 +408,46 @@ class RadarHIP:
         rec = np.concatenate(recs) if recs else np.zeros(0, native.ICP_DTYPE)
         return rec, self._corrected_by(p, rec)
 
+    # ---- oriented surface points and point-to-line scan matching (rr_surfels.hip)
+    def surfacePoints(self, points, surfel_cfg, max_surfels=4096):
+        """ONE point cloud (POINT_DTYPE, e.g. toPointCloud of a scan, at most 65,536 points) or a list of them -> (a list with one
+        native.SURFEL_DTYPE array per cloud: its oriented surface points in ascending cell order, counts uint32 [n][2] = (kept, flags))
+        by rr_surface_points.  surfel_cfg: native.surfel_config or a dict of its arguments."""
+        self._push()
+        pts = native._cloud_list(points)
+        offs = np.zeros((len(pts), N_ANGLES + 1), np.uint32)
+        offs[:, -1] = [len(p) for p in pts]                           # (the calls read a frame's total only)
+        return self._ctx.surface_points(pts, offs, surfel_cfg, max_surfels)
+
+    def registerSurfacePoints(self, poses, real_points, surfel_cfg, detect=None, gate=1.0, iterations=10, max_surfels=4096):
+        """registerPointClouds with a point-to-line residual: the real cloud is reduced to oriented surface points once (surfacePoints), and
+        per 64 poses rr_simulate_batch_device, rr_detect_device and rr_register_surfels_device run on one stream from the identity guess.
+        -> (native.ICP_DTYPE records [n], corrected poses float32 [n][7]).  The pose convention is registerPointClouds': T = X^-1 X_h and
+        the corrected pose is X_h T^-1."""
+        import torch
+        self._push()
+        det = native.detect_config(detect, n_cells=self.m_cfg.n_cells)
+        p = native.object_poses_array(poses)
+        it, g = native._int_in(iterations, 0, 64, "iterations"), native._icp_gate(gate)
+        tgt = self.surfacePoints(native._scan(np.ascontiguousarray(real_points), 1, "real_points"), surfel_cfg, max_surfels)[0][0]
+        if len(tgt) > native.ICP_MAX_POINTS:
+            raise ValueError("the target may hold at most %d surface points" % native.ICP_MAX_POINTS)
+        dev = torch.device("cuda", self._ctx.device)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)   # noqa: E731
+        recs = []
+        stream = torch.cuda.Stream(device=dev)
+        s = stream.cuda_stream
+        with torch.cuda.device(dev), torch.cuda.stream(stream):
+            d_tgt, d_cnt = up(tgt if len(tgt) else np.zeros(1, native.SURFEL_DTYPE)), up(np.array([len(tgt)], np.uint32))
+            for _, n, offs, pts, mp, _ in self._detected_chunks(p, det, s, capped=True):
+                d_rec = torch.empty(n * native.ICP_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+                self._ctx.register_surfels_device(pts.data_ptr(), offs.data_ptr(), n, mp, d_tgt.data_ptr(), d_cnt.data_ptr(), len(tgt),
+                                                  d_rec.data_ptr(), None, g, it, None, s)
+                recs.append(d_rec.cpu().numpy().view(native.ICP_DTYPE).copy())
+        self._ctx.synchronize(s)
+        rec = np.concatenate(recs) if recs else np.zeros(0, native.ICP_DTYPE)
+        return rec, self._corrected_by(p, rec)
+
     @staticmethod
     def _corrected_by(poses, rec):
         """X_h T^-1 for every hypothesis and its record (registerPointClouds says why)"""
