@@ -1766,6 +1766,123 @@ int rr_register_surfels(rr_ctx* ctx, const rr_radar_point* points, const uint32_
                         const rr_surfel* tgt_surfels, uint32_t tgt_count, int max_tgt, const double* init_or_NULL, float gate, int iterations,
                         rr_icp_rec* recs, uint32_t* corr_or_NULL);                       /* host buffers, synchronous */
 
+/* ---- pose-graph optimisation: batched SE(2) Gauss-Newton with preconditioned conjugate gradients (rr_graph.hip) -----------------
+ * The back end behind the matchers: N rigid 2-D states tied by E relative measurements (an odometry chain and its loop closures) are made
+ * consistent, and the result is the pose table the map calls take.  The reference has no such step: parity is UNPINNED and everything below
+ * is the build's own definition (a numpy restatement in tests/graph_ref.py checks the kernels byte for byte).  All arithmetic is f64,
+ * + - * / sqrt only, un-fused and evaluated as written; every sum has a stated order; no atomic takes part in the arithmetic.
+ * OUT OF SCOPE: full 3 x 3 information matrices (an edge carries two weights), 3-D poses, incremental re-solves, marginal covariances.
+ *
+ * NODES.  states f64 [N][4] = (c, s, tx, ty), the layout of rr_icp_rec's state, taken as given (a caller passes a unit (c, s)); one byte
+ * per node, non-zero: the node is FIXED.  EDGES.  rr_graph_edge: (c, s, tx, ty) is the measured state of node j in node i's frame -- a
+ * record of rr_register_points, rr_register_surfels or rr_refine_poses with target scan i and source scan j, as it comes.
+ * RESIDUAL of an edge, with (ci, si, txi, tyi) and (cj, sj, txj, tyj) the states of its nodes and z the measurement:
+ *     dx = txj - txi    dy = tyj - tyi    ux = ci*dx + si*dy    uy = ci*dy - si*dx    etx = ux - z.tx    ety = uy - z.ty
+ *     a = ci*cj + si*sj    b = ci*sj - si*cj    rc = z.c*a + z.s*b    rs = z.c*b - z.s*a    den = 1.0 + rc    er = (2.0*rs) / den
+ * (er is twice the tangent of half the angle of R_z^T R_i^T R_j: no trigonometry anywhere).
+ * FLAGS of an edge, decided anew at every linearisation, in this order:
+ *     RR_GRAPH_EDGE_BAD      i == j, i >= N or j >= N, a field that is not finite, or a negative weight (no state is read)
+ *     RR_GRAPH_EDGE_FLIPPED  den is not >= 2^-20 (the turn is within about a milliradian of pi)
+ *     RR_GRAPH_EDGE_BAD      chi below is not finite
+ * A flagged edge takes no part in that iteration.  With wt = (double)w_t, wr = (double)w_r:
+ *     chi = wt*(etx*etx + ety*ety) + wr*(er*er)        kk = 1.0 + (er*er) / 4.0
+ * COST.  chi2 = the sum of chi over the unflagged edges, in the order of REDUCTION below over the edge index (a flagged edge adds 0.0).
+ * With robust_k > 0 an edge's weights are scaled once per linearisation: sc = 1.0 / (1.0 + chi / (robust_k*robust_k)), wt = wt*sc,
+ * wr = wr*sc (the Cauchy weight of iteratively re-weighted least squares; the record's chi2 stays the unscaled sum).
+ * UPDATE.  delta = (dth, dx, dy) per node: t <- t + (dx, dy), R <- R * Cayley(dth), renormalised:
+ *     u = dth / 2.0    dc = (1.0 - u*u) / (1.0 + u*u)    ds = (2.0*u) / (1.0 + u*u)
+ *     c1 = c*dc - s*ds    s1 = s*dc + c*ds    n = sqrt(c1*c1 + s1*s1)    c = c1/n    s = s1/n    tx = tx + dx    ty = ty + dy
+ * A node whose delta is zero in all three components keeps every byte of its state.  The JACOBIANS are the exact derivatives of the
+ * residuals under this update (the Cayley turn has unit derivative at 0, and d er / d dth_j = kk):
+ *     node i:  d(etx, ety, er) / d(dth, dx, dy) = [ uy -ci -si ; -ux si -ci ; -kk 0 0 ]      node j:  [ 0 ci si ; 0 -si ci ; kk 0 0 ]
+ * so a fixed point is a stationary point of the stated cost.
+ * GATHER.  Node n adds the terms of its incident unflagged edges IN ASCENDING EDGE INDEX, acc = acc + term from 0.0, by the LIST SUM: a
+ * list of at most 64 entries (flagged ones included in the count) is summed one after the other; a longer one is split over 64 lanes, lane
+ * l summing entries l, l + 64, l + 128, ... of the list one after the other from 0.0, and the 64 lane sums are then halved:
+ * for h = 32, 16, .. 1: lane[t] = lane[t] + lane[t + h] for t < h.  The terms, with nn = ci*ci + si*si:
+ *     as node i:  H00 = wt*(uy*uy + ux*ux) + wr*(kk*kk)    H01 = -(wt*(uy*ci + ux*si))    H02 = wt*(ux*ci - uy*si)    H11 = wt*nn
+ *                 g0 = wt*(uy*etx - ux*ety) - wr*(kk*er)    g1 = wt*(si*ety - ci*etx)    g2 = -(wt*(si*etx + ci*ety))
+ *     as node j:  H00 = wr*(kk*kk)    H01 = 0    H02 = 0    H11 = wt*nn    g0 = wr*(kk*er)    g1 = wt*(ci*etx - si*ety)    g2 = wt*(si*etx + ci*ety)
+ * (H22 = H11 and H12 = 0 exactly.)  The node's block is [ H00+lambda H01 H02 ; H01 H11+lambda 0 ; H02 0 H11+lambda ]: lambda is added
+ * to the diagonal as it is (H + lambda * I), so a graph without a fixed node needs lambda > 0 for a definite system.  The block is
+ * factored by the explicit LDL^T of rr_register_surfels (d0, l10, l20, d1, m21, l21, d2 with H12 = 0); a FIXED node, and a node one of
+ * whose pivots is not > 0 (a DEAD block, counted in the record; an unfixed node without edges at lambda = 0), has delta = 0 in this
+ * iteration and its rows and columns are dropped.  M^-1 v is that LDL^T's solve (z0 = v0, z1 = v1 - l10*z0, z2 = (v2 - l20*z0) - l21*z1,
+ * x2 = z2/d2, x1 = z1/d1 - l21*x2, x0 = (z0/d0 - l10*x1) - l20*x2).
+ * SOLVE of (H + lambda*I) delta = -g by preconditioned conjugate gradients, matrix-free, a FIXED count of cg_iterations:
+ *     x = 0    r = -g    z = M^-1 r    rz_0 = <r, z>
+ *     step k = 0 ..:  p = z (k = 0), else p = z + (rz_k / rz_(k-1)) * p, per component
+ *                     q_n = the LIST SUM over n's edges of the product terms below, then q_n = q_n + lambda * p_n per component
+ *                     pAp = <p, q>; if pAp or rz_k is not > 0 or not finite: the solve STOPS, the remaining steps of this outer iteration
+ *                     are no-ops and k is recorded (decided on the device; -g = 0 stops at k = 0)
+ *                     alpha = rz_k / pAp    x = x + alpha*p    r = r - alpha*q    z = M^-1 r    rz_(k+1) = <r, z>
+ *     product terms of an edge with pi = p_i, pj = p_j:
+ *         v0 = ((uy*pi0 - ci*pi1) - si*pi2) + (ci*pj1 + si*pj2)    v1 = ((si*pi1 - ux*pi0) - ci*pi2) + (ci*pj2 - si*pj1)    v2 = kk*(pj0 - pi0)
+ *         y0 = wt*v0    y1 = wt*v1    y2 = wr*v2
+ *         as node i:  (uy*y0 - ux*y1) - kk*y2,   si*y1 - ci*y0,   -(si*y0 + ci*y1)        as node j:  kk*y2,   ci*y0 - si*y1,   si*y0 + ci*y1
+ * REDUCTION.  <a, b> is ((a0*b0 + a1*b1) + a2*b2) per node (0.0 for a dropped node), then over the node index: values are taken in CHUNKS
+ * of 256 consecutive indices (the last one padded with 0.0); inside a chunk for h = 128, 64, .. 1: v[t] = v[t] + v[t + h] for t < h, the
+ * chunk's partial is v[0]; the partials P[0 .. m) are combined by s[t] = P[t] + P[t + 256] + P[t + 512] + ... one after the other from 0.0
+ * for t = 0..255, and the same halving over s.  chi2 is reduced over the edge index in the same way.
+ * An OUTER ITERATION linearises every edge, gathers, solves and updates; `iterations` of them run, then one last linearisation.
+ * recs[it], it < iterations: chi2 BEFORE step it, the edges used and flagged, the dead blocks and the step at which the solve stopped
+ * (-1: it ran its cg_iterations); recs[iterations]: chi2 and the edge counts of the final states, dead = 0, cg_stop = -1.  Every byte is
+ * written.  iterations = 0 returns the states byte for byte and recs[0] with the input's chi2.  edge_flags (one byte per edge, may be
+ * NULL) holds the flags of the last linearisation.
+ *
+ * rr_graph_plan[_device] builds the per-node incidence lists once, on the device without a read-back: a count (integer atomics), a scan,
+ * a fill and a per-list sort, so that a node's list is in ascending edge index whichever way it was filled.  The plan depends on the
+ * edges' ENDPOINTS and on N and E alone -- an edge with i == j or an index >= N is left out of it; a field that is not finite is found at
+ * each linearisation -- and may be reused for any number of solves while the endpoints stay.  Its bytes are a function of the endpoints.
+ * rr_optimize_graph_device enqueues on `stream` (NULL: the context's), per outer iteration, a linearisation, a gather, two launches per
+ * CG step, an update and a record launch; no host round trip, no workgroup waiting for another (values cross between workgroups at KERNEL
+ * BOUNDARIES only), no context memory: all working memory is the caller's d_scratch (rr_graph_scratch_bytes: 96 bytes of terms and a flag
+ * byte per edge, 193 bytes per node, and the reductions' partials; its contents before the call do not matter), so solves may run on any
+ * streams beside each other and beside batches in flight.  The host forms stage through context-owned buffers and are synchronous.
+ * LIMITS: N in 1..2^20, E in 0..2^22 (edges may be NULL iff E == 0), iterations 0..256, cg_iterations 0..1024.
+ * Refused with a message and nothing written: -1 for a null ctx; -3 for a null required buffer or config, N or E out of range, iterations
+ * or cg_iterations over their caps, a lambda or robust_k that is negative or not finite, a non-zero reserved word, plan_bytes below
+ * rr_graph_plan_bytes or scratch_bytes below rr_graph_scratch_bytes, states, edges, records, plan or scratch that are not 16-byte
+ * aligned (device forms).  No config of the radar is needed. */
+typedef struct rr_graph_edge {   /* 48 B */
+    uint32_t i, j;             /* the edge measures node j in node i's frame */
+    double c, s, tx, ty;       /* the measured state: a matcher's record with target i and source j */
+    float w_t;                 /* 1/m^2: isotropic weight of the translation residual, in i's frame */
+    float w_r;                 /* weight of the rotation residual */
+} rr_graph_edge;
+
+typedef struct rr_graph_config {   /* 32 B */
+    int32_t iterations;        /* 0..256 outer iterations */
+    int32_t cg_iterations;     /* 0..1024 CG steps per outer iteration */
+    double  lambda;            /* >= 0, added to the diagonal of H */
+    double  robust_k;          /* 0: plain least squares; > 0: the Cauchy kernel's scale, in units of sqrt(chi) */
+    int32_t reserved_[2];      /* 0 */
+} rr_graph_config;
+
+#define RR_GRAPH_EDGE_FLIPPED 1u
+#define RR_GRAPH_EDGE_BAD     2u
+typedef struct rr_graph_rec {  /* 32 B, every byte written */
+    double   chi2;             /* the cost before this record's step (the last record: of the final states) */
+    uint32_t n_used;           /* unflagged edges */
+    uint32_t n_flipped;        /* edges flagged RR_GRAPH_EDGE_FLIPPED */
+    uint32_t n_bad;            /* edges flagged RR_GRAPH_EDGE_BAD */
+    uint32_t n_dead;           /* unfixed nodes whose block had a pivot that is not > 0 */
+    int32_t  cg_stop;          /* the CG step at which the solve stopped early, or -1 */
+    uint32_t reserved_;        /* 0 */
+} rr_graph_rec;
+
+/* the blocking of the kernels: nodes per chunk of a reduction, edges per chunk of the linearisation (tests put counts at their edges) */
+void   rr_graph_tile_sizes(int* node_chunk, int* edge_tile);
+size_t rr_graph_plan_bytes(int n_nodes, int n_edges);                                                 /* 0 for a refused shape */
+size_t rr_graph_scratch_bytes(int n_nodes, int n_edges, const rr_graph_config* cfg);                  /* 0 for a refused shape */
+int rr_graph_plan_device(rr_ctx* ctx, const rr_graph_edge* d_edges, int n_nodes, int n_edges, void* d_plan, size_t plan_bytes, void* stream);
+int rr_graph_plan(rr_ctx* ctx, const rr_graph_edge* edges, int n_nodes, int n_edges, void* plan, size_t plan_bytes);   /* host buffers, synchronous */
+int rr_optimize_graph_device(rr_ctx* ctx, double* d_states /*[N][4], in and out*/, const uint8_t* d_fixed /*[N]*/, const rr_graph_edge* d_edges,
+                             int n_nodes, int n_edges, const void* d_plan, const rr_graph_config* cfg, rr_graph_rec* d_recs /*[iterations+1]*/,
+                             uint8_t* d_edge_flags_or_NULL /*[E]*/, void* d_scratch, size_t scratch_bytes, void* stream);
+int rr_optimize_graph(rr_ctx* ctx, double* states, const uint8_t* fixed, const rr_graph_edge* edges, int n_nodes, int n_edges, const void* plan,
+                      const rr_graph_config* cfg, rr_graph_rec* recs, uint8_t* edge_flags_or_NULL);   /* host buffers, synchronous */
+
 /* ---- several GPUs of one node behind one object (SURVEY.md §8b "Threading", §8e) -------------------------
  * The reference creates ONE backend object per process (src/radar_simulator.cpp:145-176) and fans out inside it
  * (OpenMP over azimuths, RadarCPU.cpp:155).  rr_multi is that object for n GPUs: one rr_ctx per device, mesh and

@@ -576,6 +576,24 @@ public:
         }
         return recs;
     }
+    // Pose-graph optimisation (rr_graph.hip; include/radarays_mi355.h): the back end behind the matchers.  states [N][4] = c s tx ty per node
+    // (e.g. the integrated odometry) are optimised in place against the edges -- edge k says that node j sits at (c, s, tx, ty) in node i's
+    // frame: a record of registerPointClouds / registerSurfacePoints / refinePoses with target i and source j, as it comes -- by
+    // cfg.iterations Gauss-Newton steps of cfg.cg_iterations CG steps each; cfg.robust_k > 0 weighs false closures down.  One rr_graph_rec
+    // per step and one for the result (chi2, edges used and flagged, dead blocks, the CG step a solve stopped at).  Empty on error, and
+    // the states keep their values
+    std::vector<rr_graph_rec> optimizePoseGraph(std::vector<double>& states, const std::vector<uint8_t>& fixed, const std::vector<rr_graph_edge>& edges,
+                                                const rr_graph_config& cfg)
+    {
+        std::vector<rr_graph_rec> recs;
+        if (!marshal::optimize_graph(m_ctx, states, fixed, edges, cfg, recs)) {
+            if (fixed.empty() || states.size() != 4 * fixed.size() || cfg.iterations < 0 || cfg.iterations > 256)
+                m_err = "optimizePoseGraph: no node, states that are not [N][4] for N = fixed.size(), or iterations outside 0..256";
+            else fail();
+            recs.clear();
+        }
+        return recs;
+    }
     // the pose hypothesis X_h (qx qy qz qw tx ty tz) whose simulated cloud gave `rec` against the real cloud, corrected: T = X^-1 X_h, so
     // the result is X_h T^-1 -- X_h turned by -atan2(s, c) about its own z axis and moved by -R^T t in its own axes
     static std::array<float, 7> correctedPose(const float* pose7, const rr_icp_rec& rec)

@@ -336,6 +336,29 @@ inline bool register_surfels(rr_ctx* ctx, const std::vector<std::vector<rr_radar
     return true;
 }
 
+// Pose-graph optimisation (rr_graph_edge, rr_graph_config, rr_graph_rec; rr_graph_plan and rr_optimize_graph, host forms): states [N][4] =
+// (c, s, tx, ty) in and out, a fixed byte per node, the edges (a matcher's record with target i and source j is an edge as it comes) ->
+// the optimised states and cfg.iterations + 1 records; the plan is built here.  false: rr_last_error(ctx), or states that are not [N][4]
+// for N = fixed.size() in 1..2^20, more than 2^22 edges, or iterations outside 0..256 -- and the states keep their values
+inline bool optimize_graph(rr_ctx* ctx, std::vector<double>& states, const std::vector<uint8_t>& fixed, const std::vector<rr_graph_edge>& edges,
+                           const rr_graph_config& cfg, std::vector<rr_graph_rec>& recs)
+{
+    recs.clear();
+    const size_t n = fixed.size(), ne = edges.size();
+    if (n < 1 || n > ((size_t)1 << 20) || states.size() != 4 * n || ne > ((size_t)1 << 22) || cfg.iterations < 0 || cfg.iterations > 256) return false;
+    std::vector<uint8_t> plan(rr_graph_plan_bytes((int)n, (int)ne));
+    const rr_graph_edge* e = ne ? edges.data() : nullptr;
+    if (plan.empty() || rr_graph_plan(ctx, e, (int)n, (int)ne, plan.data(), plan.size()) != 0) return false;
+    std::vector<double> x(states);
+    recs.resize((size_t)cfg.iterations + 1);
+    if (rr_optimize_graph(ctx, x.data(), fixed.data(), e, (int)n, (int)ne, plan.data(), &cfg, recs.data(), nullptr) != 0) {
+        recs.clear();
+        return false;
+    }
+    states.swap(x);
+    return true;
+}
+
 // map refinement: the nearest-cell table [height][width] of an occupancy map (occupied: >= threshold; rr_nearest_field), 0xFFFFFFFF where no
 // occupied cell lies within cfg.max_dist.  false: rr_last_error(ctx), or a map that is not [height][width]
 inline bool build_nearest(rr_ctx* ctx, const std::vector<uint8_t>& occ, int threshold, const rr_field_config& cfg, std::vector<uint32_t>& nearest)

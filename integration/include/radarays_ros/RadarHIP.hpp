@@ -88,6 +88,12 @@ public:
                                                   float gate = 1.0f, int iterations = 10,
                                                   const std::vector<double>& init = std::vector<double>());
 
+    // Pose-graph optimisation (radarays_mi355.h, "pose-graph optimisation"; device 0): states [N][4] = c s tx ty per node, optimised in
+    // place against the edges (a matcher's record with target i and source j is an edge as it comes): one rr_graph_rec per Gauss-Newton
+    // step and one for the result.  Empty on error, and the states keep their values
+    std::vector<rr_graph_rec> optimizePoseGraph(std::vector<double>& states, const std::vector<uint8_t>& fixed,
+                                                const std::vector<rr_graph_edge>& edges, const rr_graph_config& cfg);
+
 protected:
     void init(const std::vector<float>& verts, const std::vector<uint32_t>& faces, const std::vector<uint32_t>& face_object,
               const std::vector<int>& devices, bool build_on_gpu);

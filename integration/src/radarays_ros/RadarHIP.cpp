@@ -457,4 +457,17 @@ std::vector<rr_icp_rec> RadarHIP::registerSurfacePoints(const std::vector<std::v
     return recs;
 }
 
+std::vector<rr_graph_rec> RadarHIP::optimizePoseGraph(std::vector<double>& states, const std::vector<uint8_t>& fixed,
+                                                     const std::vector<rr_graph_edge>& edges, const rr_graph_config& cfg)
+{
+    std::vector<rr_graph_rec> recs;
+    if(!marshal::optimize_graph(m_ctx, states, fixed, edges, cfg, recs))
+    {
+        const bool shape = fixed.empty() || states.size() != 4 * fixed.size() || cfg.iterations < 0 || cfg.iterations > 256;
+        ROS_WARN_STREAM("[RadarHIP] optimizePoseGraph: " << (shape ? "no node, states that are not [N][4], or iterations outside 0..256" : rr_last_error(m_ctx)));
+        recs.clear();
+    }
+    return recs;
+}
+
 } // namespace radarays_ros

@@ -1,5 +1,5 @@
 // rr_images.hip -- the C ABI's image entry points: images in, records / points / images out.  PSNR scores and metrics against a reference image
-// (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), place recognition (rr_place.hip), point clouds and Cartesian images (rr_detect.hip), sweep compensation (rr_deskew.hip), scan matching (rr_icp.hip), the likelihood field (rr_field.hip), occupancy mapping (rr_occupancy.hip), the particle filter step (rr_filter.hip), map refinement (rr_refine.hip), the beam model (rr_cast.hip), mesh maps (rr_slice.hip), connected components (rr_components.hip), correlative scan matching (rr_correlate.hip), object annotations (rr_notes.hip): each in a device form, which runs on the
+// (rr_metrics.hip), azimuth registration (rr_align.hip), translation registration (rr_shift.hip), place recognition (rr_place.hip), point clouds and Cartesian images (rr_detect.hip), sweep compensation (rr_deskew.hip), scan matching (rr_icp.hip), the likelihood field (rr_field.hip), occupancy mapping (rr_occupancy.hip), the particle filter step (rr_filter.hip), map refinement (rr_refine.hip), the beam model (rr_cast.hip), mesh maps (rr_slice.hip), connected components (rr_components.hip), correlative scan matching (rr_correlate.hip), pose-graph optimisation (rr_graph.hip), object annotations (rr_notes.hip): each in a device form, which runs on the
 // caller's buffers and stream, and a host form, which drains c->stream and makes its round trip through a Stage over the context's pool (rr_stage.h).
 #include "rr_grid.h"
 #include "rr_stage.h"
@@ -168,6 +168,47 @@ int check_surfels(rr_ctx* c, const std::string& w, const void* points, const voi
     if (const char* bad = bad_surfels_shape(n_frames, g)) return fail(c, -3, w + ": " + bad);
     if (max_surfels < 0 || max_surfels > (1 << 20)) return fail(c, -3, w + ": max_surfels must be 0..1048576");
     if (!surfels != (max_surfels == 0)) return fail(c, -3, w + ": the records come with max_surfels > 0 and only with it");
+    return 0;
+}
+
+// the refusals of rr_graph_plan_bytes / rr_graph_scratch_bytes and, behind them, of the pose-graph calls: the shape alone
+const char* bad_graph_shape(int n_nodes, int n_edges)
+{
+    if (n_nodes < 1 || n_nodes > (1 << 20)) return "n_nodes must be 1..1048576";
+    if (n_edges < 0 || n_edges > (1 << 22)) return "n_edges must be 0..4194304";
+    return nullptr;
+}
+
+const char* bad_graph_config(const rr_graph_config* g)
+{
+    if (!g) return "null config";
+    if (g->iterations < 0 || g->iterations > 256) return "iterations must be 0..256";
+    if (g->cg_iterations < 0 || g->cg_iterations > 1024) return "cg_iterations must be 0..1024";
+    if (!(std::isfinite(g->lambda) && g->lambda >= 0.0)) return "lambda must be finite and >= 0";
+    if (!(std::isfinite(g->robust_k) && g->robust_k >= 0.0)) return "robust_k must be finite and >= 0";
+    if (g->reserved_[0] != 0 || g->reserved_[1] != 0) return "reserved_ must be 0";
+    return nullptr;
+}
+
+// the refusals of rr_graph_plan_device / rr_graph_plan: no config of the radar is needed
+int check_graph_plan(rr_ctx* c, const std::string& w, const void* edges, int n_nodes, int n_edges, const void* plan, size_t plan_bytes)
+{
+    if (!c) return -1;
+    if (const char* bad = bad_graph_shape(n_nodes, n_edges)) return fail(c, -3, w + ": " + bad);
+    if (!plan || (n_edges > 0 && !edges)) return fail(c, -3, w + ": null buffer");
+    const size_t need = graph_plan_bytes((size_t)n_nodes, (size_t)n_edges);
+    if (plan_bytes < need) return fail(c, -3, w + ": plan of " + std::to_string(plan_bytes) + " bytes, the call needs " + std::to_string(need));
+    return 0;
+}
+
+// the refusals of rr_optimize_graph_device / rr_optimize_graph
+int check_graph(rr_ctx* c, const std::string& w, const void* states, const void* fixed, const void* edges, int n_nodes, int n_edges, const void* plan,
+                const rr_graph_config* g, const void* recs)
+{
+    if (!c) return -1;
+    if (const char* bad = bad_graph_shape(n_nodes, n_edges)) return fail(c, -3, w + ": " + bad);
+    if (const char* bad = bad_graph_config(g)) return fail(c, -3, w + ": " + bad);
+    if (!states || !fixed || !plan || !recs || (n_edges > 0 && !edges)) return fail(c, -3, w + ": null buffer");
     return 0;
 }
 
@@ -1753,6 +1794,84 @@ int rr_register_surfels(rr_ctx* c, const rr_radar_point* points, const uint32_t*
     RR_HIP(c, st.hold_rows(corr, n, mp, mp, totals.data(), d_corr));
     RR_HIP(c, hipStreamSynchronize(c->stream));        // (tgt_count is this call's own variable)
     rc = rr_register_surfels_device(c, d_src, d_offs, n_frames, max_points, d_tgt, d_count, max_tgt, d_init, gate, iterations, d_recs, d_corr, c->stream);
+    if (rc) return rc;
+    return st.commit();
+}
+
+// ---- pose-graph optimisation (rr_graph.hip) ---------------------------------------------------------------------------------------
+void rr_graph_tile_sizes(int* node_chunk, int* edge_tile) { graph_tile_sizes(node_chunk, edge_tile); }
+
+size_t rr_graph_plan_bytes(int n_nodes, int n_edges)
+{
+    if (bad_graph_shape(n_nodes, n_edges)) return 0;
+    return graph_plan_bytes((size_t)n_nodes, (size_t)n_edges);
+}
+
+size_t rr_graph_scratch_bytes(int n_nodes, int n_edges, const rr_graph_config* cfg)
+{
+    if (bad_graph_shape(n_nodes, n_edges) || bad_graph_config(cfg)) return 0;
+    return graph_scratch_bytes((size_t)n_nodes, (size_t)n_edges, (size_t)cfg->cg_iterations);
+}
+
+int rr_graph_plan_device(rr_ctx* c, const rr_graph_edge* d_edges, int n_nodes, int n_edges, void* d_plan, size_t plan_bytes, void* stream)
+{
+    const std::string w("rr_graph_plan_device");
+    int rc = check_graph_plan(c, w, d_edges, n_nodes, n_edges, d_plan, plan_bytes); if (rc) return rc;
+    if ((uintptr_t)d_edges % 16 != 0 || (uintptr_t)d_plan % 16 != 0) return fail(c, -3, w + ": the edges and the plan must be 16-byte aligned");
+    RR_HIP(c, hipSetDevice(c->device));
+    RR_HIP(c, launch_graph_plan(d_edges, n_nodes, n_edges, d_plan, stream_of(c, stream)));
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_graph_plan(rr_ctx* c, const rr_graph_edge* edges, int n_nodes, int n_edges, void* plan, size_t plan_bytes)
+{
+    int rc = check_graph_plan(c, "rr_graph_plan", edges, n_nodes, n_edges, plan, plan_bytes); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t need = graph_plan_bytes((size_t)n_nodes, (size_t)n_edges);
+    RR_STAGE(c, st);
+    rr_graph_edge* d_edges; uint8_t* d_plan;
+    RR_HIP(c, st.up(n_edges > 0 ? edges : nullptr, (size_t)n_edges, d_edges));
+    RR_HIP(c, st.hold(static_cast<uint8_t*>(plan), need, d_plan));
+    rc = rr_graph_plan_device(c, d_edges, n_nodes, n_edges, d_plan, need, c->stream); if (rc) return rc;
+    return st.commit();
+}
+
+int rr_optimize_graph_device(rr_ctx* c, double* d_states, const uint8_t* d_fixed, const rr_graph_edge* d_edges, int n_nodes, int n_edges,
+                             const void* d_plan, const rr_graph_config* cfg, rr_graph_rec* d_recs, uint8_t* d_edge_flags, void* d_scratch,
+                             size_t scratch_bytes, void* stream)
+{
+    const std::string w("rr_optimize_graph_device");
+    int rc = check_graph(c, w, d_states, d_fixed, d_edges, n_nodes, n_edges, d_plan, cfg, d_recs); if (rc) return rc;
+    if (!d_scratch) return fail(c, -3, w + ": null scratch");
+    if ((uintptr_t)d_states % 16 != 0 || (uintptr_t)d_edges % 16 != 0 || (uintptr_t)d_recs % 16 != 0 || (uintptr_t)d_plan % 16 != 0 ||
+        (uintptr_t)d_scratch % 16 != 0)
+        return fail(c, -3, w + ": the states, the edges, the records, the plan and the scratch must be 16-byte aligned");
+    const size_t need = rr_graph_scratch_bytes(n_nodes, n_edges, cfg);
+    if (scratch_bytes < need) return fail(c, -3, w + ": scratch of " + std::to_string(scratch_bytes) + " bytes, the call needs " + std::to_string(need));
+    RR_HIP(c, hipSetDevice(c->device));
+    launch_optimize_graph(d_states, d_fixed, d_edges, n_nodes, n_edges, d_plan, *cfg, d_recs, d_edge_flags, d_scratch, stream_of(c, stream));
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_optimize_graph(rr_ctx* c, double* states, const uint8_t* fixed, const rr_graph_edge* edges, int n_nodes, int n_edges, const void* plan,
+                      const rr_graph_config* cfg, rr_graph_rec* recs, uint8_t* edge_flags)
+{
+    int rc = check_graph(c, "rr_optimize_graph", states, fixed, edges, n_nodes, n_edges, plan, cfg, recs); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t N = (size_t)n_nodes, E = (size_t)n_edges, scratch = rr_graph_scratch_bytes(n_nodes, n_edges, cfg);
+    RR_STAGE(c, st);
+    double* d_states; uint8_t *d_fixed, *d_plan, *d_flags, *d_scratch; rr_graph_edge* d_edges; rr_graph_rec* d_recs;
+    RR_HIP(c, st.up(static_cast<const double*>(states), 4 * N, d_states));
+    st.out(states, static_cast<const double*>(d_states), 4 * N);
+    RR_HIP(c, st.up(fixed, N, d_fixed));
+    RR_HIP(c, st.up(n_edges > 0 ? edges : nullptr, E, d_edges));
+    RR_HIP(c, st.up(static_cast<const uint8_t*>(plan), graph_plan_bytes(N, E), d_plan));
+    RR_HIP(c, st.hold(recs, (size_t)cfg->iterations + 1, d_recs));
+    RR_HIP(c, st.hold(n_edges > 0 ? edge_flags : nullptr, E, d_flags));
+    RR_HIP(c, st.room(scratch, d_scratch));
+    rc = rr_optimize_graph_device(c, d_states, d_fixed, d_edges, n_nodes, n_edges, d_plan, cfg, d_recs, d_flags, d_scratch, scratch, c->stream);
     if (rc) return rc;
     return st.commit();
 }

@@ -147,6 +147,15 @@ size_t line_scratch_words(size_t n_frames);
 void launch_register_surfels(const rr_radar_point* points, const uint32_t* offsets, int n_frames, int n_angles, int max_points, const rr_surfel* tgt,
                              const uint32_t* tgt_count, int max_tgt, const double* init, float gate, int iterations, rr_icp_rec* recs,
                              uint32_t* corr, long long* acc, hipStream_t s);
+// rr_graph.hip (pose-graph optimisation).  plan: graph_plan_bytes, scratch: graph_scratch_bytes, states, edges and recs 16-byte aligned; every
+// byte of the plan is written (two memsets, whose error is returned, and six launches); the scratch's contents before the call do not matter.
+// edges may be null iff n_edges == 0.  Per outer iteration 4 + 2 * cg_iterations launches, then a linearisation and a record
+void graph_tile_sizes(int* node_chunk, int* edge_tile);
+size_t graph_plan_bytes(size_t n_nodes, size_t n_edges);
+size_t graph_scratch_bytes(size_t n_nodes, size_t n_edges, size_t cg_iterations);
+hipError_t launch_graph_plan(const rr_graph_edge* edges, int n_nodes, int n_edges, void* plan, hipStream_t s);
+void launch_optimize_graph(double* states, const uint8_t* fixed, const rr_graph_edge* edges, int n_nodes, int n_edges, const void* plan,
+                           const rr_graph_config& cfg, rr_graph_rec* recs, uint8_t* edge_flags, void* scratch, hipStream_t s);
 // rr_notes.hip (object annotations).  scratch: note_scratch_bytes, 16-byte aligned like notes; every word of it, of notes and of skipped is written by the launches
 size_t note_scratch_bytes(size_t n_frames, size_t n_objects, int n_angles);
 void launch_notes(const uint32_t* labels, const uint8_t* imgs, int n_frames, uint32_t n_objects, uint32_t extent_mask, const PolarGrid& G,

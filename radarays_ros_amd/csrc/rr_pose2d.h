@@ -165,4 +165,32 @@ template <class State> __device__ inline bool line_solve(const long long* S, Sta
     return false;
 }
 
+// ---- the block preconditioner of the header (rr_optimize_graph): line_solve's LDL^T kept as factors, for a block with H12 = 0 ----
+struct Ldl3 { double l10, l20, l21, d0, d1, d2; };
+
+// the factors of [ H00 H01 H02 ; H01 H11 0 ; H02 0 H22 ]; false for a pivot that is not > 0 (tested as each is formed)
+__device__ inline bool ldl3_factor(double H00, double H01, double H02, double H11, double H22, Ldl3& f)
+{
+    f.d0 = H00;
+    if (!(f.d0 > 0.0)) return false;
+    f.l10 = H01 / f.d0; f.l20 = H02 / f.d0;
+    f.d1 = H11 - f.l10 * H01;
+    if (!(f.d1 > 0.0)) return false;
+    const double m21 = 0.0 - f.l20 * H01;
+    f.l21 = m21 / f.d1;
+    f.d2 = (H22 - f.l20 * H02) - f.l21 * m21;
+    return f.d2 > 0.0;
+}
+
+// x = (L D L^T)^-1 v
+__device__ inline void ldl3_solve(const Ldl3& f, const double* v, double* x)
+{
+    const double z0 = v[0];
+    const double z1 = v[1] - f.l10 * z0;
+    const double z2 = (v[2] - f.l20 * z0) - f.l21 * z1;
+    x[2] = z2 / f.d2;
+    x[1] = z1 / f.d1 - f.l21 * x[2];
+    x[0] = (z0 / f.d0 - f.l10 * x[1]) - f.l20 * x[2];
+}
+
 }  // namespace rr

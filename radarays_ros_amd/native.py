@@ -597,6 +597,88 @@ def surfels_tile_sizes():
     return a.value, b.value
 
 
+# ---- pose-graph optimisation (rr_graph.hip): rr_graph_edge (48 B), rr_graph_config (32 B) and rr_graph_rec (32 B)
+GRAPH_EDGE_DTYPE = np.dtype([("i", "<u4"), ("j", "<u4"), ("c", "<f8"), ("s", "<f8"), ("tx", "<f8"), ("ty", "<f8"), ("w_t", "<f4"), ("w_r", "<f4")])
+GRAPH_REC_DTYPE = np.dtype([("chi2", "<f8"), ("n_used", "<u4"), ("n_flipped", "<u4"), ("n_bad", "<u4"), ("n_dead", "<u4"), ("cg_stop", "<i4"),
+                            ("reserved_", "<u4")])
+GRAPH_EDGE_FLIPPED, GRAPH_EDGE_BAD = 1, 2
+GRAPH_MAX_NODES, GRAPH_MAX_EDGES, GRAPH_MAX_ITERATIONS, GRAPH_MAX_CG_ITERATIONS = 1 << 20, 1 << 22, 256, 1024
+RRGraphEdge = np.ctypeslib.as_ctypes_type(GRAPH_EDGE_DTYPE)
+RRGraphRec = np.ctypeslib.as_ctypes_type(GRAPH_REC_DTYPE)
+
+
+class RRGraphConfig(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("cg_iterations", C.c_int32), ("lambda", C.c_double), ("robust_k", C.c_double), ("reserved_", C.c_int32 * 2)]
+
+
+def _graph_real(v, what):
+    """a finite real >= 0 as the library takes it (f64)"""
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not (np.isfinite(v) and v >= 0):
+        raise ValueError("%s must be finite and >= 0, got %r" % (what, v))
+    return float(v)
+
+
+def graph_config(iterations=10, cg_iterations=50, lam=0.0, robust_k=0.0):
+    """rr_graph_config, range-checked before any call into the library: `iterations` outer Gauss-Newton iterations (0..256) of
+    `cg_iterations` CG steps each (0..1024), `lam` added to the diagonal of H (>= 0; a graph without a fixed node needs > 0),
+    robust_k the Cauchy kernel's scale (0: plain least squares)"""
+    g = RRGraphConfig(_int_in(iterations, 0, GRAPH_MAX_ITERATIONS, "iterations"), _int_in(cg_iterations, 0, GRAPH_MAX_CG_ITERATIONS, "cg_iterations"),
+                      0.0, _graph_real(robust_k, "robust_k"), (C.c_int32 * 2)(0, 0))
+    setattr(g, "lambda", _graph_real(lam, "lambda"))
+    return g
+
+
+def _graph_cfg(cfg):
+    """an RRGraphConfig (graph_config makes one; held to its ranges again) or a dict of graph_config's arguments"""
+    if isinstance(cfg, RRGraphConfig):
+        if any(cfg.reserved_):
+            raise ValueError("reserved_ must be 0")
+        return graph_config(cfg.iterations, cfg.cg_iterations, getattr(cfg, "lambda"), cfg.robust_k)
+    if isinstance(cfg, dict):
+        return graph_config(**cfg)
+    raise ValueError("a graph config must be an RRGraphConfig (native.graph_config makes one) or a dict of its arguments, got %r" % (cfg,))
+
+
+def graph_edges(i, j, states, w_t=1.0, w_r=1.0):
+    """matcher records packed into GRAPH_EDGE_DTYPE [E]: edge k says that node j[k] sits at states[k] in node i[k]'s frame.  states: ICP_DTYPE
+    records (rr_register_points, rr_register_surfels or rr_refine_poses with target scan i and source scan j, as they come) or float64
+    [E][4] = (c, s, tx, ty); w_t (1/m^2) and w_r: scalars or arrays that broadcast"""
+    i, j = np.atleast_1d(np.asarray(i)), np.atleast_1d(np.asarray(j))
+    if i.ndim != 1 or i.shape != j.shape or i.dtype.kind not in "iu" or j.dtype.kind not in "iu":
+        raise ValueError("i and j must be integer arrays of one length")
+    if len(i) and (min(i.min(), j.min()) < 0 or max(i.max(), j.max()) > 0xFFFFFFFF):
+        raise ValueError("a node index must fit 32 bits")
+    st = np.asarray(states)
+    if st.dtype == ICP_DTYPE:
+        st = np.stack([st[k] for k in ("c", "s", "tx", "ty")], axis=-1)
+    st = np.asarray(st, np.float64).reshape(-1, 4)
+    if len(st) != len(i):
+        raise ValueError("one state per edge: %d states for %d edges" % (len(st), len(i)))
+    e = np.zeros(len(i), GRAPH_EDGE_DTYPE)
+    e["i"], e["j"] = i, j
+    e["c"], e["s"], e["tx"], e["ty"] = st[:, 0], st[:, 1], st[:, 2], st[:, 3]
+    e["w_t"], e["w_r"] = np.broadcast_to(np.asarray(w_t, np.float32), e.shape), np.broadcast_to(np.asarray(w_r, np.float32), e.shape)
+    return e
+
+
+def graph_tile_sizes():
+    """(nodes per chunk of a reduction, edges per chunk of the linearisation) of rr_graph.hip"""
+    a, b = C.c_int(0), C.c_int(0)
+    lib().rr_graph_tile_sizes(C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
+def _graph_edges_arg(edges):
+    e = np.asarray(edges)
+    if e.dtype != GRAPH_EDGE_DTYPE or e.ndim != 1:
+        raise ValueError("edges must be a one-dimensional GRAPH_EDGE_DTYPE array (native.graph_edges makes one)")
+    return np.ascontiguousarray(e)
+
+
+def _graph_shape(n_nodes, n_edges):
+    return _int_in(n_nodes, 1, GRAPH_MAX_NODES, "n_nodes"), _int_in(n_edges, 0, GRAPH_MAX_EDGES, "n_edges")
+
+
 # rr_default_detect_config
 DETECT_DEFAULTS ={"method": 0, "guard_cells": 2, "train_cells": 16, "k": 12, "min_intensity": 1, "min_bin": 0, "cfar_scale": 3.0}
 DETECT_METHODS = {"cfar": 0, "ca-cfar": 0, "kstrongest": 1, "k-strongest": 1, 0: 0, 1: 1}
@@ -722,6 +804,7 @@ STRUCTS = {
     "rr_components_config": (RRComponentsConfig, None), "rr_component": (RRComponent, COMPONENT_DTYPE),
     "rr_corr_config": (RRCorrConfig, None), "rr_corr_rec": (RRCorrRec, CORR_DTYPE),
     "rr_surfel_config": (RRSurfelConfig, None), "rr_surfel": (RRSurfel, SURFEL_DTYPE),
+    "rr_graph_edge": (RRGraphEdge, GRAPH_EDGE_DTYPE), "rr_graph_config": (RRGraphConfig, None), "rr_graph_rec": (RRGraphRec, GRAPH_REC_DTYPE),
 }
 
 
@@ -898,6 +981,14 @@ def _prototypes():
         "rr_surface_points": (i, [vp, vp, vp, i, i, P(RRSurfelConfig), vp, i, vp]),
         "rr_register_surfels_device": (i, [vp, vp, vp, i, i, vp, vp, i, vp, f, i, vp, vp, vp]),
         "rr_register_surfels": (i, [vp, vp, vp, i, i, vp, u32, i, vp, f, i, vp, vp]),
+        # ---- pose-graph optimisation (rr_graph.hip)
+        "rr_graph_tile_sizes": (None, [P(i), P(i)]),
+        "rr_graph_plan_bytes": (sz, [i, i]),
+        "rr_graph_scratch_bytes": (sz, [i, i, P(RRGraphConfig)]),
+        "rr_graph_plan_device": (i, [vp, vp, i, i, vp, sz, vp]),
+        "rr_graph_plan": (i, [vp, vp, i, i, vp, sz]),
+        "rr_optimize_graph_device": (i, [vp, vp, vp, vp, i, i, vp, P(RRGraphConfig), vp, vp, vp, sz, vp]),
+        "rr_optimize_graph": (i, [vp, vp, vp, vp, i, i, vp, P(RRGraphConfig), vp, vp]),
         # ---- several GPUs of one node behind one object (rr_multi.hip)
         "rr_create_multi": (vp, [P(i), i]),
         "rr_destroy_multi": (None, [vp]),
@@ -1974,6 +2065,84 @@ class Context(_Scene):
         if want_corr:
             return recs, [corr[f, :k].copy() for f, k in enumerate(lens)]
         return recs
+
+    # ---- pose-graph optimisation (rr_graph.hip); any context, with a config or not
+    @staticmethod
+    def graph_plan_bytes(n_nodes, n_edges):
+        """rr_graph_plan_bytes: the bytes of the incidence plan of a graph of n_nodes nodes and n_edges edges"""
+        n, e = _graph_shape(n_nodes, n_edges)
+        return int(lib().rr_graph_plan_bytes(n, e))
+
+    @staticmethod
+    def graph_scratch_bytes(n_nodes, n_edges, cfg):
+        """rr_graph_scratch_bytes: the bytes of scratch rr_optimize_graph_device needs under cfg"""
+        n, e = _graph_shape(n_nodes, n_edges)
+        g = _graph_cfg(cfg)
+        return int(lib().rr_graph_scratch_bytes(n, e, C.byref(g)))
+
+    def graph_plan_device(self, d_edges_ptr, n_nodes, n_edges, d_plan_ptr, plan_bytes, stream=None):
+        """rr_graph_plan_device on raw device addresses: GRAPH_EDGE_DTYPE records [n_edges] (None iff n_edges is 0) -> the incidence plan
+        (graph_plan_bytes, 16-byte aligned like the edges), every byte of it written.  Every argument is checked here first."""
+        n, e = _graph_shape(n_nodes, n_edges)
+        if not d_plan_ptr or (e > 0 and not d_edges_ptr):
+            raise ValueError("graph_plan_device needs edge and plan buffers")
+        if (d_edges_ptr or 0) % 16 or d_plan_ptr % 16:
+            raise ValueError("the edges and the plan must be 16-byte aligned")
+        need = self.graph_plan_bytes(n, e)
+        if isinstance(plan_bytes, bool) or not isinstance(plan_bytes, (int, np.integer)) or plan_bytes < need:
+            raise ValueError("plan of %r bytes, the call needs %d" % (plan_bytes, need))
+        self._ck(self._L.rr_graph_plan_device(self._h, d_edges_ptr, n, e, d_plan_ptr, int(plan_bytes), stream))
+
+    def graph_plan(self, edges, n_nodes):
+        """rr_graph_plan: GRAPH_EDGE_DTYPE [E] (native.graph_edges makes them) and the node count -> the incidence plan as uint8 bytes: every
+        node's edges in ascending edge index.  It depends on the endpoints alone and serves any number of optimize_graph calls."""
+        e = _graph_edges_arg(edges)
+        n, ne = _graph_shape(n_nodes, len(e))
+        plan = np.zeros(self.graph_plan_bytes(n, ne), np.uint8)
+        self._ck(self._L.rr_graph_plan(self._h, e.ctypes.data if ne else None, n, ne, plan.ctypes.data, plan.nbytes))
+        return plan
+
+    def optimize_graph_device(self, d_states_ptr, d_fixed_ptr, d_edges_ptr, n_nodes, n_edges, d_plan_ptr, cfg, d_recs_ptr, d_scratch_ptr, scratch_bytes,
+                              d_edge_flags_ptr=None, stream=None):
+        """rr_optimize_graph_device on raw device addresses: float64 states [n_nodes][4] in and out, a fixed byte per node, the edges, their
+        plan -> GRAPH_REC_DTYPE [iterations + 1] and, if asked for, a flag byte per edge.  The scratch (graph_scratch_bytes) is the caller's;
+        nothing of the context is used, so the call may run on any stream.  Every argument is checked here first."""
+        n, e = _graph_shape(n_nodes, n_edges)
+        g = _graph_cfg(cfg)
+        if not (d_states_ptr and d_fixed_ptr and d_plan_ptr and d_recs_ptr and d_scratch_ptr) or (e > 0 and not d_edges_ptr):
+            raise ValueError("optimize_graph_device needs state, fixed, edge, plan, record and scratch buffers")
+        if d_states_ptr % 16 or (d_edges_ptr or 0) % 16 or d_plan_ptr % 16 or d_recs_ptr % 16 or d_scratch_ptr % 16:
+            raise ValueError("the states, the edges, the plan, the records and the scratch must be 16-byte aligned")
+        need = self.graph_scratch_bytes(n, e, g)
+        if isinstance(scratch_bytes, bool) or not isinstance(scratch_bytes, (int, np.integer)) or scratch_bytes < need:
+            raise ValueError("scratch of %r bytes, the call needs %d" % (scratch_bytes, need))
+        self._ck(self._L.rr_optimize_graph_device(self._h, d_states_ptr, d_fixed_ptr, d_edges_ptr, n, e, d_plan_ptr, C.byref(g), d_recs_ptr,
+                                                  d_edge_flags_ptr, d_scratch_ptr, int(scratch_bytes), stream))
+
+    def optimize_graph(self, states, fixed, edges, cfg, plan=None, want_flags=False):
+        """rr_optimize_graph: float64 states [N][4] = (c, s, tx, ty) (native.se2_states), a fixed flag per node, GRAPH_EDGE_DTYPE edges and a
+        graph_config (or a dict of its arguments) -> (the optimised states, GRAPH_REC_DTYPE [iterations + 1]); with want_flags also the flag
+        byte per edge of the last linearisation.  plan: what graph_plan returned for these endpoints, or None to build it here."""
+        x = np.array(states, np.float64, order="C")
+        if x.ndim != 2 or x.shape[1] != 4:
+            raise ValueError("states must have shape [n][4], got %s" % (x.shape,))
+        e = _graph_edges_arg(edges)
+        n, ne = _graph_shape(len(x), len(e))
+        fx = np.ascontiguousarray(np.asarray(fixed) != 0, np.uint8)
+        if fx.shape != (n,):
+            raise ValueError("one fixed flag per node, got shape %s" % (fx.shape,))
+        g = _graph_cfg(cfg)
+        if plan is None:
+            plan = self.graph_plan(e, n)
+        plan = np.asarray(plan)
+        if plan.dtype != np.uint8 or plan.ndim != 1 or plan.nbytes < self.graph_plan_bytes(n, ne):
+            raise ValueError("the plan must be the uint8 bytes graph_plan returned for this graph")
+        plan = np.ascontiguousarray(plan)
+        recs = np.zeros(g.iterations + 1, GRAPH_REC_DTYPE)
+        flags = np.zeros(ne, np.uint8) if want_flags else None
+        self._ck(self._L.rr_optimize_graph(self._h, x.ctypes.data, fx.ctypes.data, e.ctypes.data if ne else None, n, ne, plan.ctypes.data, C.byref(g),
+                                           recs.ctypes.data, _ptr(flags) if ne else None))
+        return (x, recs, flags) if want_flags else (x, recs)
 
     # ---- likelihood field (rr_field.hip): clouds into an occupancy grid, its exact distance transform, pose hypotheses scored against it
     def rasterize_points_device(self, d_points_ptr, d_offsets_ptr, n_frames, max_points, field_cfg, d_occ_ptr, d_states_ptr=None, stream=None):

@@ -448,6 +448,16 @@ class RadarHIP:
         rec = np.concatenate(recs) if recs else np.zeros(0, native.ICP_DTYPE)
         return rec, self._corrected_by(p, rec)
 
+    # ---- pose-graph optimisation (rr_graph.hip)
+    def optimizePoseGraph(self, states, fixed, edges, iterations=10, cg_iterations=50, lam=0.0, robust_k=0.0, plan=None):
+        """The back end behind the matchers: float64 states [N][4] = (c, s, tx, ty) (native.se2_states; e.g. the integrated odometry), a
+        fixed flag per node and native.GRAPH_EDGE_DTYPE edges (native.graph_edges packs matcher records: edge k says that node j sits at the
+        record's state in node i's frame) -> (the optimised states, native.GRAPH_REC_DTYPE [iterations + 1]: chi2 before every step and of
+        the result, the edges used and flagged, the dead blocks, the CG step at which a solve stopped) by rr_optimize_graph.  robust_k > 0
+        turns the Cauchy kernel on against false closures; lam is added to the diagonal (a graph without a fixed node needs lam > 0);
+        plan: Context.graph_plan of these endpoints, to reuse it across solves.  The states go on to buildOccupancyMap as they are."""
+        return self._ctx.optimize_graph(states, fixed, edges, native.graph_config(iterations, cg_iterations, lam, robust_k), plan=plan)
+
     @staticmethod
     def _corrected_by(poses, rec):
         """X_h T^-1 for every hypothesis and its record (registerPointClouds says why)"""
