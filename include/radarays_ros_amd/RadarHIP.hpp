@@ -517,27 +517,20 @@ public:
     // Scan matching (rr_icp.hip; include/radarays_mi355.h): point clouds (detect() or compensatePointClouds() of simulated images) registered
     // against ONE real cloud by planar point-to-point ICP with a fixed iteration count, from the states `init` ([n][4] = c s tx ty per
     // cloud) or from the identity.  One rr_icp_rec per cloud: the transform that maps the cloud into the real cloud's frame, sse,
-    // n_matched, flags.  Empty on error
+    // n_matched, flags (rr_register_points, through marshal::register_clouds).  Empty on error
     std::vector<rr_icp_rec> registerPointClouds(const std::vector<std::vector<rr_radar_point>>& clouds, const std::vector<rr_radar_point>& real,
                                                 float gate = 1.0f, int iterations = 10, const std::vector<double>& init = {})
     {
         std::vector<rr_icp_rec> recs;
         if (clouds.empty() || !push()) return recs;
-        size_t mp = 1;
-        for (const auto& c : clouds) mp = std::max(mp, c.size());
-        if (mp > 65536 || real.size() > 65536 || (!init.empty() && init.size() != 4 * clouds.size())) {
-            m_err = "registerPointClouds: a cloud of more than 65536 points, or init is not [n][4]"; return recs;
+        if (!marshal::register_clouds(m_ctx, clouds, m_n_angles, real, init, gate, iterations, recs)) {
+            size_t mp = 0;
+            for (const auto& c : clouds) mp = std::max(mp, c.size());
+            if (mp > 65536 || real.size() > 65536 || (!init.empty() && init.size() != 4 * clouds.size()))
+                m_err = "registerPointClouds: a cloud of more than 65536 points, or init is not [n][4]";
+            else fail();
+            recs.clear();
         }
-        const size_t n = clouds.size(), stride = (size_t)m_n_angles + 1;
-        std::vector<rr_radar_point> pts(n * mp);
-        std::vector<uint32_t> offs(n * stride, 0u);                   // only each frame's total is read
-        for (size_t f = 0; f < n; f++) {
-            std::copy(clouds[f].begin(), clouds[f].end(), pts.begin() + f * mp);
-            offs[f * stride + m_n_angles] = (uint32_t)clouds[f].size();
-        }
-        recs.resize(n);
-        if (rr_register_points(m_ctx, pts.data(), offs.data(), (int)n, (int)mp, real.data(), (uint32_t)real.size(), (int)real.size(),
-                               init.empty() ? nullptr : init.data(), gate, iterations, recs.data(), nullptr)) { fail(); recs.clear(); }
         return recs;
     }
     // Oriented surface points (rr_surfels.hip; include/radarays_mi355.h): clouds (detect() of scans) reduced to sparse surface points, per

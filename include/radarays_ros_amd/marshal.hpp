@@ -316,11 +316,22 @@ inline bool surface_points(rr_ctx* ctx, const std::vector<std::vector<rr_radar_p
     return true;
 }
 
-// ... and n clouds registered against ONE target of surface points by point-to-line ICP (rr_register_surfels, host form), from the states
-// `init` ([n][4] = c s tx ty per cloud) or, if it is empty, from the identity: one rr_icp_rec per cloud.  false: rr_last_error(ctx), or no
-// cloud, a cloud or a target of more than 65536 records, or an init that is not [n][4]
-inline bool register_surfels(rr_ctx* ctx, const std::vector<std::vector<rr_radar_point>>& clouds, int n_angles, const std::vector<rr_surfel>& target,
-                             const std::vector<double>& init, float gate, int iterations, std::vector<rr_icp_rec>& recs)
+// Scan matching (rr_register_points / rr_register_surfels, host forms): n clouds registered against ONE target, a cloud by point-to-point ICP
+// or surface points by point-to-line ICP, from the states `init` ([n][4] = c s tx ty per cloud) or, if it is empty, from the identity: one
+// rr_icp_rec per cloud.  false: rr_last_error(ctx), or no cloud, a cloud or a target of more than 65536 records, or an init that is not [n][4]
+inline int register_call(rr_ctx* ctx, const rr_radar_point* pts, const uint32_t* offs, int n, int mp, const rr_radar_point* tgt, uint32_t count,
+                         const double* init, float gate, int iterations, rr_icp_rec* recs)
+{
+    return rr_register_points(ctx, pts, offs, n, mp, tgt, count, (int)count, init, gate, iterations, recs, nullptr);
+}
+inline int register_call(rr_ctx* ctx, const rr_radar_point* pts, const uint32_t* offs, int n, int mp, const rr_surfel* tgt, uint32_t count,
+                         const double* init, float gate, int iterations, rr_icp_rec* recs)
+{
+    return rr_register_surfels(ctx, pts, offs, n, mp, tgt, count, (int)count, init, gate, iterations, recs, nullptr);
+}
+template <class Target>
+inline bool register_clouds(rr_ctx* ctx, const std::vector<std::vector<rr_radar_point>>& clouds, int n_angles, const std::vector<Target>& target,
+                            const std::vector<double>& init, float gate, int iterations, std::vector<rr_icp_rec>& recs)
 {
     recs.clear();
     const size_t n = clouds.size();
@@ -328,12 +339,17 @@ inline bool register_surfels(rr_ctx* ctx, const std::vector<std::vector<rr_radar
     const size_t mp = pack_clouds(clouds, n_angles, pts, offs);
     if (mp == 0 || target.size() > 65536 || (!init.empty() && init.size() != 4 * n)) return false;
     recs.resize(n);
-    if (rr_register_surfels(ctx, pts.data(), offs.data(), (int)n, (int)mp, target.empty() ? nullptr : target.data(), (uint32_t)target.size(),
-                            (int)target.size(), init.empty() ? nullptr : init.data(), gate, iterations, recs.data(), nullptr) != 0) {
+    if (register_call(ctx, pts.data(), offs.data(), (int)n, (int)mp, target.empty() ? nullptr : target.data(), (uint32_t)target.size(),
+                      init.empty() ? nullptr : init.data(), gate, iterations, recs.data()) != 0) {
         recs.clear();
         return false;
     }
     return true;
+}
+inline bool register_surfels(rr_ctx* ctx, const std::vector<std::vector<rr_radar_point>>& clouds, int n_angles, const std::vector<rr_surfel>& target,
+                             const std::vector<double>& init, float gate, int iterations, std::vector<rr_icp_rec>& recs)
+{
+    return register_clouds(ctx, clouds, n_angles, target, init, gate, iterations, recs);
 }
 
 // Pose-graph optimisation (rr_graph_edge, rr_graph_config, rr_graph_rec; rr_graph_plan and rr_optimize_graph, host forms): states [N][4] =

@@ -200,11 +200,10 @@ struct rr_ctx {
     // a host form's pool.  rr_score_images_device's sums; rr_compare_images_device: histograms of one chunk of images, SSIM partials
     // [image][block], the records; RR_METRICS_HIST
     DevBuf<unsigned long long> d_sse; DevBuf<uint32_t> d_mhist; DevBuf<double> d_ssim_part; DevBuf<rr_image_metrics> d_mrec; int metrics_hist = 0;
-    // rr_register_points_device: the eight int64 sums per frame, one buffer per stream it has been called on (icp_mu guards the map, not the
-    // buffers: calls on one stream are ordered by that stream)
+    // rr_register_points_device / rr_register_surfels_device: the eight or fourteen int64 sums per frame, one buffer per stream either has been
+    // called on, sized by the larger call (icp_mu guards the map, not the buffers: calls on one stream are ordered by that stream, and each
+    // call's first launch zeroes what it uses; a buffer grows through hipFree, which waits for the device)
     std::map<hipStream_t, DevBuf<long long>> icp_acc; std::mutex icp_mu;
-    // rr_register_surfels_device: the fourteen int64 sums per frame, per stream in the same way (icp_mu guards this map too)
-    std::map<hipStream_t, DevBuf<long long>> line_acc;
     // rr_slice_mesh_device: the large list (its counter, then one word per triangle record), one buffer per stream like icp_acc
     std::map<hipStream_t, DevBuf<uint32_t>> slice_list; std::mutex slice_mu;
     // rr_align_images_device: one chunk's curves (when the caller gives no buffer) and sums, the records

@@ -601,6 +601,67 @@ int up_points(rr_ctx* c, Stage& st, const rr_radar_point* points, const uint32_t
 // what every rr_simulate_batch_* form passes before anything is handed out
 auto frame_gate(rr_ctx* c) { return [c] { return report_frame_errors(c); }; }
 
+// ---- the two scan matchers' entry points (rr_icp.hip) ----
+// what they differ in besides the target's type: the launcher, the accumulator's size, and the line matcher's one refusal of its own
+struct PointMatch {
+    static constexpr auto launch = launch_icp;
+    static constexpr auto scratch_words = icp_scratch_words;
+    static const char* refuse_target(const void*) { return nullptr; }
+};
+struct LineMatch {
+    static constexpr auto launch = launch_register_surfels;
+    static constexpr auto scratch_words = line_scratch_words;
+    static const char* refuse_target(const void* t) { return (uintptr_t)t % 16 != 0 ? ": the target must be 16-byte aligned" : nullptr; }      // (one 16-byte load per surfel)
+};
+
+template <class M, class Target>
+int register_device(rr_ctx* c, const std::string& w, const rr_radar_point* d_points, const uint32_t* d_offsets, int n_frames, int max_points,
+                    const Target* d_tgt, const uint32_t* d_tgt_count, int max_tgt, const double* d_init, float gate, int iterations,
+                    rr_icp_rec* d_recs, uint32_t* d_corr, void* stream)
+{
+    int rc = check_icp(c, w.c_str(), d_points, d_offsets, n_frames, max_points, d_tgt, d_tgt_count != nullptr, max_tgt, gate, iterations, d_recs);
+    if (rc) return rc;
+    if ((uintptr_t)d_init % 8 != 0 || (uintptr_t)d_recs % 8 != 0) return fail(c, -3, w + ": d_init and d_recs must be 8-byte aligned");
+    if (const char* why = M::refuse_target(d_tgt)) return fail(c, -3, w + why);
+    RR_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = stream_of(c, stream);
+    long long* acc = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(c->icp_mu);
+        DevBuf<long long>& b = c->icp_acc[s];
+        RR_HIP(c, b.ensure(M::scratch_words((size_t)n_frames)));
+        acc = b.p;
+    }
+    M::launch(d_points, d_offsets, n_frames, c->cfg.n_angles, max_points, d_tgt, d_tgt_count, max_tgt, d_init, gate, iterations, d_recs, d_corr, acc, s);
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+template <class M, class Target>
+int register_host(rr_ctx* c, const std::string& w, const rr_radar_point* points, const uint32_t* offsets, int n_frames, int max_points,
+                  const Target* tgt, uint32_t tgt_count, int max_tgt, const double* init, float gate, int iterations, rr_icp_rec* recs,
+                  uint32_t* corr)
+{
+    int rc = check_icp(c, w.c_str(), points, offsets, n_frames, max_points, tgt, true, max_tgt, gate, iterations, recs); if (rc) return rc;
+    const size_t n = (size_t)n_frames, mp = (size_t)max_points, mt = (size_t)max_tgt;
+    for (size_t f = 0; init && f < n; f++) {
+        const double h = std::sqrt(init[4 * f] * init[4 * f] + init[4 * f + 1] * init[4 * f + 1]);
+        if (!(h > 0.0 && std::isfinite(h))) return fail(c, -3, w + ": an initial state whose (c, s) has a zero or non-finite length");
+    }
+    RR_HIP(c, hipSetDevice(c->device));
+    RR_STAGE(c, st);
+    std::vector<uint32_t> totals; rr_radar_point* d_src; Target* d_tgt; uint32_t *d_offs, *d_count, *d_corr; double* d_init; rr_icp_rec* d_recs;
+    rc = up_points(c, st, points, offsets, n, mp, totals, d_src, d_offs); if (rc) return rc;
+    RR_HIP(c, st.up_rows(tgt, 1, mt, &tgt_count, d_tgt));
+    RR_HIP(c, st.up(&tgt_count, 1, d_count));
+    RR_HIP(c, st.up(init, n * 4, d_init));
+    RR_HIP(c, st.hold(recs, n, d_recs));
+    RR_HIP(c, st.hold_rows(corr, n, mp, mp, totals.data(), d_corr));
+    RR_HIP(c, hipStreamSynchronize(c->stream));        // (tgt_count is this call's own variable)
+    rc = register_device<M>(c, w + "_device", d_src, d_offs, n_frames, max_points, d_tgt, d_count, max_tgt, d_init, gate, iterations, d_recs, d_corr, c->stream);
+    if (rc) return rc;
+    return st.commit();
+}
 }  // namespace
 
 // the refusals of rr_compare_images_device / rr_compare_images / rr_simulate_param_sets_metrics
@@ -1163,47 +1224,31 @@ int rr_register_points_device(rr_ctx* c, const rr_radar_point* d_points, const u
                               const rr_radar_point* d_tgt_points, const uint32_t* d_tgt_count, int max_tgt, const double* d_init, float gate,
                               int iterations, rr_icp_rec* d_recs, uint32_t* d_corr, void* stream)
 {
-    int rc = check_icp(c, "rr_register_points_device", d_points, d_offsets, n_frames, max_points, d_tgt_points, d_tgt_count != nullptr, max_tgt, gate,
-                       iterations, d_recs); if (rc) return rc;
-    if ((uintptr_t)d_init % 8 != 0 || (uintptr_t)d_recs % 8 != 0) return fail(c, -3, "rr_register_points_device: d_init and d_recs must be 8-byte aligned");
-    RR_HIP(c, hipSetDevice(c->device));
-    hipStream_t s = stream_of(c, stream);
-    long long* acc = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(c->icp_mu);
-        DevBuf<long long>& b = c->icp_acc[s];
-        RR_HIP(c, b.ensure(icp_scratch_words((size_t)n_frames)));
-        acc = b.p;
-    }
-    launch_icp(d_points, d_offsets, n_frames, c->cfg.n_angles, max_points, d_tgt_points, d_tgt_count, max_tgt, d_init, gate, iterations, d_recs, d_corr,
-               acc, s);
-    RR_HIP(c, hipGetLastError());
-    return 0;
+    return register_device<PointMatch>(c, "rr_register_points_device", d_points, d_offsets, n_frames, max_points, d_tgt_points, d_tgt_count, max_tgt, d_init,
+                                       gate, iterations, d_recs, d_corr, stream);
 }
 
 int rr_register_points(rr_ctx* c, const rr_radar_point* points, const uint32_t* offsets, int n_frames, int max_points, const rr_radar_point* tgt_points,
                        uint32_t tgt_count, int max_tgt, const double* init, float gate, int iterations, rr_icp_rec* recs, uint32_t* corr)
 {
-    const std::string w("rr_register_points");
-    int rc = check_icp(c, w.c_str(), points, offsets, n_frames, max_points, tgt_points, true, max_tgt, gate, iterations, recs); if (rc) return rc;
-    const size_t n = (size_t)n_frames, mp = (size_t)max_points, mt = (size_t)max_tgt;
-    for (size_t f = 0; init && f < n; f++) {
-        const double h = std::sqrt(init[4 * f] * init[4 * f] + init[4 * f + 1] * init[4 * f + 1]);
-        if (!(h > 0.0 && std::isfinite(h))) return fail(c, -3, w + ": an initial state whose (c, s) has a zero or non-finite length");
-    }
-    RR_HIP(c, hipSetDevice(c->device));
-    RR_STAGE(c, st);
-    std::vector<uint32_t> totals; rr_radar_point *d_src, *d_tgt; uint32_t *d_offs, *d_count, *d_corr; double* d_init; rr_icp_rec* d_recs;
-    rc = up_points(c, st, points, offsets, n, mp, totals, d_src, d_offs); if (rc) return rc;
-    RR_HIP(c, st.up_rows(tgt_points, 1, mt, &tgt_count, d_tgt));
-    RR_HIP(c, st.up(&tgt_count, 1, d_count));
-    RR_HIP(c, st.up(init, n * 4, d_init));
-    RR_HIP(c, st.hold(recs, n, d_recs));
-    RR_HIP(c, st.hold_rows(corr, n, mp, mp, totals.data(), d_corr));
-    RR_HIP(c, hipStreamSynchronize(c->stream));        // (tgt_count is this call's own variable)
-    rc = rr_register_points_device(c, d_src, d_offs, n_frames, max_points, d_tgt, d_count, max_tgt, d_init, gate, iterations, d_recs, d_corr, c->stream);
-    if (rc) return rc;
-    return st.commit();
+    return register_host<PointMatch>(c, "rr_register_points", points, offsets, n_frames, max_points, tgt_points, tgt_count, max_tgt, init, gate, iterations,
+                                     recs, corr);
+}
+
+// (rr_surfels.hip makes the target of this one)
+int rr_register_surfels_device(rr_ctx* c, const rr_radar_point* d_points, const uint32_t* d_offsets, int n_frames, int max_points,
+                               const rr_surfel* d_tgt_surfels, const uint32_t* d_tgt_count, int max_tgt, const double* d_init, float gate,
+                               int iterations, rr_icp_rec* d_recs, uint32_t* d_corr, void* stream)
+{
+    return register_device<LineMatch>(c, "rr_register_surfels_device", d_points, d_offsets, n_frames, max_points, d_tgt_surfels, d_tgt_count, max_tgt, d_init,
+                                      gate, iterations, d_recs, d_corr, stream);
+}
+
+int rr_register_surfels(rr_ctx* c, const rr_radar_point* points, const uint32_t* offsets, int n_frames, int max_points, const rr_surfel* tgt_surfels,
+                        uint32_t tgt_count, int max_tgt, const double* init, float gate, int iterations, rr_icp_rec* recs, uint32_t* corr)
+{
+    return register_host<LineMatch>(c, "rr_register_surfels", points, offsets, n_frames, max_points, tgt_surfels, tgt_count, max_tgt, init, gate, iterations,
+                                    recs, corr);
 }
 
 // ---- likelihood field (rr_field.hip) ------------------------------------------------------------------------------------
@@ -1748,54 +1793,6 @@ int rr_surface_points(rr_ctx* c, const rr_radar_point* points, const uint32_t* o
     rc = st.commit(); if (rc) return rc;
     std::memcpy(counts, both.data(), 2 * n * sizeof(uint32_t));
     return 0;
-}
-
-int rr_register_surfels_device(rr_ctx* c, const rr_radar_point* d_points, const uint32_t* d_offsets, int n_frames, int max_points,
-                               const rr_surfel* d_tgt_surfels, const uint32_t* d_tgt_count, int max_tgt, const double* d_init, float gate,
-                               int iterations, rr_icp_rec* d_recs, uint32_t* d_corr, void* stream)
-{
-    int rc = check_icp(c, "rr_register_surfels_device", d_points, d_offsets, n_frames, max_points, d_tgt_surfels, d_tgt_count != nullptr, max_tgt, gate,
-                       iterations, d_recs); if (rc) return rc;
-    if ((uintptr_t)d_init % 8 != 0 || (uintptr_t)d_recs % 8 != 0) return fail(c, -3, "rr_register_surfels_device: d_init and d_recs must be 8-byte aligned");
-    if ((uintptr_t)d_tgt_surfels % 16 != 0) return fail(c, -3, "rr_register_surfels_device: the target must be 16-byte aligned");
-    RR_HIP(c, hipSetDevice(c->device));
-    hipStream_t s = stream_of(c, stream);
-    long long* acc = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(c->icp_mu);
-        DevBuf<long long>& b = c->line_acc[s];
-        RR_HIP(c, b.ensure(line_scratch_words((size_t)n_frames)));
-        acc = b.p;
-    }
-    launch_register_surfels(d_points, d_offsets, n_frames, c->cfg.n_angles, max_points, d_tgt_surfels, d_tgt_count, max_tgt, d_init, gate, iterations,
-                            d_recs, d_corr, acc, s);
-    RR_HIP(c, hipGetLastError());
-    return 0;
-}
-
-int rr_register_surfels(rr_ctx* c, const rr_radar_point* points, const uint32_t* offsets, int n_frames, int max_points, const rr_surfel* tgt_surfels,
-                        uint32_t tgt_count, int max_tgt, const double* init, float gate, int iterations, rr_icp_rec* recs, uint32_t* corr)
-{
-    const std::string w("rr_register_surfels");
-    int rc = check_icp(c, w.c_str(), points, offsets, n_frames, max_points, tgt_surfels, true, max_tgt, gate, iterations, recs); if (rc) return rc;
-    const size_t n = (size_t)n_frames, mp = (size_t)max_points, mt = (size_t)max_tgt;
-    for (size_t f = 0; init && f < n; f++) {
-        const double h = std::sqrt(init[4 * f] * init[4 * f] + init[4 * f + 1] * init[4 * f + 1]);
-        if (!(h > 0.0 && std::isfinite(h))) return fail(c, -3, w + ": an initial state whose (c, s) has a zero or non-finite length");
-    }
-    RR_HIP(c, hipSetDevice(c->device));
-    RR_STAGE(c, st);
-    std::vector<uint32_t> totals; rr_radar_point* d_src; rr_surfel* d_tgt; uint32_t *d_offs, *d_count, *d_corr; double* d_init; rr_icp_rec* d_recs;
-    rc = up_points(c, st, points, offsets, n, mp, totals, d_src, d_offs); if (rc) return rc;
-    RR_HIP(c, st.up_rows(tgt_surfels, 1, mt, &tgt_count, d_tgt));
-    RR_HIP(c, st.up(&tgt_count, 1, d_count));
-    RR_HIP(c, st.up(init, n * 4, d_init));
-    RR_HIP(c, st.hold(recs, n, d_recs));
-    RR_HIP(c, st.hold_rows(corr, n, mp, mp, totals.data(), d_corr));
-    RR_HIP(c, hipStreamSynchronize(c->stream));        // (tgt_count is this call's own variable)
-    rc = rr_register_surfels_device(c, d_src, d_offs, n_frames, max_points, d_tgt, d_count, max_tgt, d_init, gate, iterations, d_recs, d_corr, c->stream);
-    if (rc) return rc;
-    return st.commit();
 }
 
 // ---- pose-graph optimisation (rr_graph.hip) ---------------------------------------------------------------------------------------

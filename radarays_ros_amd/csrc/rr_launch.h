@@ -73,12 +73,17 @@ void launch_compensate_points(const rr_radar_point* points, const uint32_t* offs
                               rr_radar_point* out, const PolarGrid& G, hipStream_t s);
 void launch_cartesian_sweep(const uint8_t* imgs, int n_frames, const rr_cartesian_config& cfg, const PolarGrid& G, const rr_sweep_rec* table,
                             int iterations, uint8_t* out, hipStream_t s);
-// rr_icp.hip (scan matching).  acc: icp_scratch_words(n_frames) int64 words, zeroed by the first launch; recs and init 8-byte aligned
+// rr_icp.hip (scan matching: one matcher, point-to-point against a cloud and point-to-line against surface points).  acc: icp_scratch_words /
+// line_scratch_words(n_frames) int64 words, zeroed by the first launch; recs and init 8-byte, a surfel target 16-byte aligned
 void icp_tile_sizes(int* source_tile, int* target_tile);
 size_t icp_scratch_words(size_t n_frames);
 void launch_icp(const rr_radar_point* points, const uint32_t* offsets, int n_frames, int n_angles, int max_points, const rr_radar_point* tgt,
                 const uint32_t* tgt_count, int max_tgt, const double* init, float gate, int iterations, rr_icp_rec* recs, uint32_t* corr,
                 long long* acc, hipStream_t s);
+size_t line_scratch_words(size_t n_frames);
+void launch_register_surfels(const rr_radar_point* points, const uint32_t* offsets, int n_frames, int n_angles, int max_points, const rr_surfel* tgt,
+                             const uint32_t* tgt_count, int max_tgt, const double* init, float gate, int iterations, rr_icp_rec* recs,
+                             uint32_t* corr, long long* acc, hipStream_t s);
 // rr_field.hip (likelihood field).  No scratch: occ is only ever written with ones, field is written whole, every record of recs is written;
 // states of the rasteriser 8-byte aligned or null, recs 8-byte aligned, field must not alias occ
 void field_tile_sizes(int* points_tile, int* hyps_per_group, int* row_tile);
@@ -136,17 +141,13 @@ size_t correlate_scratch_bytes(size_t n_rot, size_t max_points, int levels, size
 void launch_field_pyramid(const uint16_t* field, const rr_field_config& g, int levels, uint16_t* pyramid, hipStream_t s);
 void launch_correlate(const rr_radar_point* points, const uint32_t* count, int max_points, const float* rot, int n_rot, const uint16_t* pyramid,
                       const rr_field_config& g, const rr_corr_config& c, rr_corr_rec* rec, void* scratch, hipStream_t s);
-// rr_surfels.hip (oriented surface points, point-to-line scan matching).  scratch: surfels_scratch_bytes for n_cells = width * width, 16-byte aligned
+// rr_surfels.hip (oriented surface points).  scratch: surfels_scratch_bytes for n_cells = width * width, 16-byte aligned
 // like surfels (null iff max_surfels == 0); its contents before the call do not matter; counts [n_frames][2].  A memset (its error is returned) and
-// four launches.  acc: line_scratch_words(n_frames) int64 words, zeroed by the first launch; recs and init 8-byte, tgt 16-byte aligned
+// four launches
 void surfels_tile_sizes(int* points_tile, int* cells_chunk);
 size_t surfels_scratch_bytes(size_t n_frames, size_t n_cells);
 hipError_t launch_surface_points(const rr_radar_point* points, const uint32_t* offsets, int n_frames, int n_angles, int max_points,
                                  const rr_surfel_config& cfg, rr_surfel* surfels, int max_surfels, uint32_t* counts, void* scratch, hipStream_t s);
-size_t line_scratch_words(size_t n_frames);
-void launch_register_surfels(const rr_radar_point* points, const uint32_t* offsets, int n_frames, int n_angles, int max_points, const rr_surfel* tgt,
-                             const uint32_t* tgt_count, int max_tgt, const double* init, float gate, int iterations, rr_icp_rec* recs,
-                             uint32_t* corr, long long* acc, hipStream_t s);
 // rr_graph.hip (pose-graph optimisation).  plan: graph_plan_bytes, scratch: graph_scratch_bytes, states, edges and recs 16-byte aligned; every
 // byte of the plan is written (two memsets, whose error is returned, and six launches); the scratch's contents before the call do not matter.
 // edges may be null iff n_edges == 0.  Per outer iteration 4 + 2 * cg_iterations launches, then a linearisation and a record

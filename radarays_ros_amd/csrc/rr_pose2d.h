@@ -55,7 +55,7 @@ template <class State> __device__ inline bool icp_start(State& st)
 }
 
 // one matched pair, moved point p and target q, quantised to 1/256 m and added to the eight sums.
-// Exact because |P|, |Q| <= 2^21: the matcher matches only coordinates below kIcpRange = 8192 in magnitude, refinement only points IN GRID and
+// Exact because |P|, |Q| <= 2^21: the matcher matches only coordinates below PointResidual::kRange = 8192 in magnitude, refinement only points IN GRID and
 // cell centres of a grid that its check holds within +-8192 m.  So P - Q fits 32 bits and every product 32 x 32 -> 64; the sums are integers
 __device__ inline void icp_accumulate(long long* sum, float px, float py, float qx, float qy)
 {
@@ -92,6 +92,28 @@ template <class State> __device__ inline bool icp_solve(const long long* S, Stat
     return false;
 }
 
+// The residuals of the matcher (rr_icp.hip).  A residual names its target record, its sums and its coordinate range, and gives: stage(), the
+// (x, y) of target j for the LDS tile, or (+inf, +inf) if it may not be a candidate; accumulate(), which fetches what it needs of the matched
+// target; solve() and sse().  Point-to-point: x and y lead a 24-byte point, the step above
+struct PointResidual {
+    using Target = rr_radar_point;
+    enum { COUNT = S_COUNT, N = S_N };
+    static constexpr float kRange = 8192.0f;                     // a coordinate must be finite and below this in magnitude (icp_accumulate relies on it)
+    static __device__ inline bool in_range(float v) { return fabsf(v) < kRange; }      // false for NaN and infinities
+    static __device__ inline float2 stage(const Target* tgt, uint32_t j, bool live)
+    {
+        float x = INFINITY, y = INFINITY;
+        if (live) {
+            const float qx = tgt[j].x, qy = tgt[j].y;
+            if (in_range(qx) && in_range(qy)) { x = qx; y = qy; }
+        }
+        return make_float2(x, y);
+    }
+    static __device__ inline void accumulate(long long* sum, float px, float py, const Target* tgt, uint32_t j) { icp_accumulate(sum, px, py, tgt[j].x, tgt[j].y); }
+    template <class State> static __device__ inline bool solve(const long long* S, State& st) { return icp_solve(S, st); }
+    static __device__ inline long long sse(const long long* S) { return S[S_SSE]; }
+};
+
 // ---- the point-to-line step of the header (rr_register_surfels): the fourteen sums over the matched pairs, and the LDL^T solve ----
 enum { L_N = 0, L_H00LO, L_H00HI, L_H01, L_H02, L_H11, L_H12, L_H22, L_G0LO, L_G0HI, L_G1, L_G2, L_RRLO, L_RRHI, L_COUNT };
 
@@ -104,7 +126,7 @@ __device__ inline void line_limbs(long long* sum, int lo, long long t)
 __device__ inline double line_join(const long long* S, int lo) { return (double)S[lo + 1] * 4294967296.0 + (double)S[lo]; }
 
 // one matched pair: moved point p and surfel mean q quantised to 1/64 m, the surfel's normal to 1/1024.  Exact because the matcher matches
-// only coordinates below kLineRange = 2048 and normal components of at most 1 in magnitude: |P|, |Q| <= 2^17, |M| <= 2^10, so |r| <= 2^29,
+// only coordinates below LineResidual::kRange = 2048 and normal components of at most 1 in magnitude: |P|, |Q| <= 2^17, |M| <= 2^10, so |r| <= 2^29,
 // |a0| <= 2^28, and every term is below 2^58 (the header lists each term's and each sum's bound)
 __device__ inline void line_accumulate(long long* sum, float px, float py, float qx, float qy, float nx, float ny)
 {
@@ -164,6 +186,31 @@ template <class State> __device__ inline bool line_solve(const long long* S, Sta
     st.c = c1 / nrm; st.s = s1 / nrm; st.tx = tx1; st.ty = ty1;
     return false;
 }
+
+// point-to-line: (x, y, nx, ny) leads a 32-byte surfel and is one 16-byte load; a normal component above 1 in magnitude (or NaN) is no candidate
+struct LineResidual {
+    using Target = rr_surfel;
+    enum { COUNT = L_COUNT, N = L_N };
+    static constexpr float kRange = 2048.0f;                     // a coordinate must be finite and below this in magnitude (line_accumulate relies on it)
+    static __device__ inline float4 lead(const Target* tgt, uint32_t j) { return reinterpret_cast<const float4*>(tgt)[2 * (size_t)j]; }
+    static __device__ inline bool in_range(float v) { return fabsf(v) < kRange; }
+    static __device__ inline float2 stage(const Target* tgt, uint32_t j, bool live)
+    {
+        float x = INFINITY, y = INFINITY;
+        if (live) {
+            const float4 q = lead(tgt, j);
+            if (in_range(q.x) && in_range(q.y) && fabsf(q.z) <= 1.0f && fabsf(q.w) <= 1.0f) { x = q.x; y = q.y; }
+        }
+        return make_float2(x, y);
+    }
+    static __device__ inline void accumulate(long long* sum, float px, float py, const Target* tgt, uint32_t j)
+    {
+        const float4 q = lead(tgt, j);                               // the normal is fetched once, here
+        line_accumulate(sum, px, py, q.x, q.y, q.z, q.w);
+    }
+    template <class State> static __device__ inline bool solve(const long long* S, State& st) { return line_solve(S, st); }
+    static __device__ inline long long sse(const long long* S) { return line_sse(S); }
+};
 
 // ---- the block preconditioner of the header (rr_optimize_graph): line_solve's LDL^T kept as factors, for a block with H12 = 0 ----
 struct Ldl3 { double l10, l20, l21, d0, d1, d2; };

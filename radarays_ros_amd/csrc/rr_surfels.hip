@@ -1,5 +1,5 @@
-// rr_surfels.hip -- gfx950 kernels of the oriented surface points (rr_surface_points_device) and of the point-to-line scan matcher
-// (rr_register_surfels_device).  The definitions are in include/radarays_mi355.h: integer sums, so no execution order can change a byte.
+// rr_surfels.hip -- gfx950 kernels of the oriented surface points (rr_surface_points_device).  The definition is in include/radarays_mi355.h:
+// integer sums, so no execution order can change a byte.
 //
 // Surface points, a memset of the sums and four launches:
 //   k_sf_bin       one thread per point: the point's cell and its six int64 sums, one 64-bit vector atomic per sum into the cell's own row
@@ -14,13 +14,8 @@
 //                  same steps again (a few hundred cells of a million: cheaper than a record per cell in the scratch) and writes its
 //                  record in two 16-B stores
 //
-// Point-to-line registration: k_sr_init, k_sr_pass and k_sr_solve are k_icp_init, k_icp_pass and k_icp_solve of rr_icp.hip with surfels as
-// the target: the same LDS streaming of the target's (x, y), the same broadcast reads, the same two points per thread, the same strict `<`
-// walk.  The matched surfel's normal is fetched once, after the loop.  The search loop is not shared with k_icp_pass as a template: the
-// staging differs (a 16-B load and a test of the normal against a 24-byte point and a test of two words), and rr_icp.hip stays as it was.
-// Fourteen int64 sums per frame (rr_pose2d.h: line_accumulate), reduced across the wave with 64-bit shuffles, then one vector atomic per
-// sum from lane 0; the sums cross to k_sr_solve and the state back at KERNEL BOUNDARIES only.
-// No scratch (private) memory; 8 KB of static LDS in k_sr_pass, 32 bytes in the scan kernels.
+// The point-to-line matcher that takes these records as its target is rr_icp.hip's, with LineResidual of rr_pose2d.h.
+// No scratch (private) memory; 32 bytes of static LDS in the scan kernels.
 #include "../../include/radarays_mi355.h"
 #include "rr_device.h"
 #include "rr_launch.h"
@@ -193,134 +188,6 @@ size_t sf_sums_bytes(size_t n, size_t cells) { return align16(n * cells * kSfSum
 size_t sf_flags_bytes(size_t n, size_t chunks) { return align16(n * chunks * kSfTB * sizeof(uint32_t)); }
 size_t sf_part_bytes(size_t n, size_t chunks) { return align16(n * chunks * sizeof(uint32_t)); }
 
-// ---- point-to-line registration ------------------------------------------------------------------------------------------------------
-constexpr int kSrTB = 128;                           // threads of a k_sr_pass workgroup: two waves
-constexpr int kSrPPT = 2;                            // source points a thread keeps in registers
-constexpr int kSrSrcTile = kSrTB * kSrPPT;           // 256
-constexpr int kSrTgtTile = 1024;                     // (x, y) pairs of a target tile in LDS: 8 KB
-constexpr uint32_t kSrNone = 0xFFFFFFFFu;
-constexpr float kLineRange = 2048.0f;                // a coordinate must be finite and below this in magnitude (line_accumulate relies on it)
-
-static_assert(kSrTgtTile % 2 == 0 && kSrTB % 64 == 0, "targets are read in pairs, sums are reduced per wave");
-
-__device__ inline bool line_in_range(float v) { return fabsf(v) < kLineRange; }      // false for NaN and infinities
-
-__global__ void __launch_bounds__(256) k_sr_init(const double* init, const uint32_t* offsets, int n_angles, int max_points, const uint32_t* tgt_count,
-                                                 int max_tgt, rr_icp_rec* recs, long long* acc, int n_frames)
-{
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= n_frames) return;
-    Pose2d st = { 1.0, 0.0, 0.0, 0.0 };
-    uint32_t flags = 0;
-    if (init) {
-        st = { init[4 * (size_t)f], init[4 * (size_t)f + 1], init[4 * (size_t)f + 2], init[4 * (size_t)f + 3] };
-        if (icp_start(st)) flags |= RR_ICP_DEGENERATE;
-    }
-    bool trunc;
-    frame_count(offsets, f, n_angles, max_points, &trunc);
-    if (trunc || *tgt_count > (uint32_t)max_tgt) flags |= RR_ICP_TRUNCATED;
-    rr_icp_rec r;
-    r.c = st.c; r.s = st.s; r.tx = st.tx; r.ty = st.ty; r.sse = 0; r.n_matched = 0; r.flags = flags;
-    recs[f] = r;
-    for (int k = 0; k < L_COUNT; k++) acc[(size_t)f * L_COUNT + k] = 0;
-}
-
-__global__ void __launch_bounds__(kSrTB) k_sr_pass(const rr_radar_point* points, const uint32_t* offsets, int n_angles, int max_points,
-                                                   const rr_surfel* tgt, const uint32_t* tgt_count, int max_tgt, const rr_icp_rec* recs,
-                                                   float gate2, unsigned long long* acc, uint32_t* corr)
-{
-    __shared__ __align__(16) float2 tile[kSrTgtTile];
-
-    const int f = blockIdx.y;
-    const uint32_t m = frame_count(offsets, f, n_angles, max_points, nullptr);
-    const uint32_t i0 = blockIdx.x * (uint32_t)kSrSrcTile;
-    if (i0 >= m) return;                                          // (the whole workgroup: no barrier has been met)
-    const uint32_t nt = min(*tgt_count, (uint32_t)max_tgt);
-    const rr_radar_point* src = points + (size_t)f * max_points;
-    const float4* tgt4 = reinterpret_cast<const float4*>(tgt);    // (x, y, nx, ny) leads a 32-byte record
-
-    const Pose2 st = pose_round(recs[f].c, recs[f].s, recs[f].tx, recs[f].ty);
-    float px[kSrPPT], py[kSrPPT], best[kSrPPT];
-    uint32_t bj[kSrPPT];
-#pragma unroll
-    for (int e = 0; e < kSrPPT; e++) {
-        const uint32_t i = i0 + (uint32_t)e * kSrTB + threadIdx.x;
-        px[e] = py[e] = __uint_as_float(0x7FC00000u);             // a slot past the count: NaN never wins and is never matched
-        if (i < m) pose_move(st, src[i].x, src[i].y, &px[e], &py[e]);
-        best[e] = INFINITY; bj[e] = kSrNone;
-    }
-
-    for (uint32_t t0 = 0; t0 < nt; t0 += kSrTgtTile) {
-        const uint32_t cnt = min((uint32_t)kSrTgtTile, nt - t0), padded = (cnt + 1u) & ~1u;
-        if (t0) __syncthreads();                                  // the tile before this one has been read by every wave
-        for (uint32_t k = threadIdx.x; k < padded; k += kSrTB) {
-            float x = INFINITY, y = INFINITY;
-            if (k < cnt) {
-                const float4 q = tgt4[2 * (size_t)(t0 + k)];
-                if (line_in_range(q.x) && line_in_range(q.y) && fabsf(q.z) <= 1.0f && fabsf(q.w) <= 1.0f) { x = q.x; y = q.y; }
-            }
-            tile[k] = make_float2(x, y);
-        }
-        __syncthreads();
-        const float4* pairs = reinterpret_cast<const float4*>(tile);
-#pragma unroll 4
-        for (uint32_t k = 0; k < padded / 2; k++) {
-            const float4 q = pairs[k];
-            const uint32_t j = t0 + 2 * k;
-#pragma unroll
-            for (int e = 0; e < kSrPPT; e++) {
-                const float dx = px[e] - q.x, dy = py[e] - q.y;
-                const float d2 = dx * dx + dy * dy;
-                if (d2 < best[e]) { best[e] = d2; bj[e] = j; }
-            }
-#pragma unroll
-            for (int e = 0; e < kSrPPT; e++) {
-                const float dx = px[e] - q.z, dy = py[e] - q.w;
-                const float d2 = dx * dx + dy * dy;
-                if (d2 < best[e]) { best[e] = d2; bj[e] = j + 1; }
-            }
-        }
-    }
-
-    long long sum[L_COUNT];
-#pragma unroll
-    for (int k = 0; k < L_COUNT; k++) sum[k] = 0;
-#pragma unroll
-    for (int e = 0; e < kSrPPT; e++) {
-        const uint32_t i = i0 + (uint32_t)e * kSrTB + threadIdx.x;
-        if (i >= m) continue;
-        uint32_t j = kSrNone;
-        if (line_in_range(px[e]) && line_in_range(py[e]) && bj[e] != kSrNone && best[e] <= gate2) {
-            j = bj[e];
-            const float4 q = tgt4[2 * (size_t)j];                 // the normal is fetched once, here
-            line_accumulate(sum, px[e], py[e], q.x, q.y, q.z, q.w);
-        }
-        if (corr) corr[(size_t)f * max_points + i] = j;
-    }
-#pragma unroll
-    for (int k = 0; k < L_COUNT; k++) sum[k] = wave_sum(sum[k]);
-    if ((threadIdx.x & 63) == 0 && sum[L_N] != 0) {
-#pragma unroll
-        for (int k = 0; k < L_COUNT; k++) atomicAdd(acc + (size_t)f * L_COUNT + k, (unsigned long long)sum[k]);
-    }
-}
-
-__global__ void __launch_bounds__(256) k_sr_solve(rr_icp_rec* recs, long long* acc, int n_frames, int last)
-{
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= n_frames) return;
-    long long S[L_COUNT];
-#pragma unroll
-    for (int k = 0; k < L_COUNT; k++) { S[k] = acc[(size_t)f * L_COUNT + k]; acc[(size_t)f * L_COUNT + k] = 0; }
-    rr_icp_rec* r = recs + f;
-    if (last) {
-        r->sse = line_sse(S);
-        r->n_matched = (uint32_t)S[L_N];
-        return;
-    }
-    if (line_solve(S, *r)) r->flags |= RR_ICP_DEGENERATE;
-}
-
 }  // namespace
 
 void surfels_tile_sizes(int* points_tile, int* cells_chunk)
@@ -353,25 +220,6 @@ hipError_t launch_surface_points(const rr_radar_point* points, const uint32_t* o
     if (max_surfels > 0)
         hipLaunchKernelGGL(k_sf_write, cgrid, dim3(kSfTB), 0, s, (const long long*)sums, (const uint32_t*)flags, (const uint32_t*)partials, surfels, A);
     return hipSuccess;
-}
-
-size_t line_scratch_words(size_t n_frames) { return n_frames * L_COUNT; }
-
-void launch_register_surfels(const rr_radar_point* points, const uint32_t* offsets, int n_frames, int n_angles, int max_points, const rr_surfel* tgt,
-                             const uint32_t* tgt_count, int max_tgt, const double* init, float gate, int iterations, rr_icp_rec* recs,
-                             uint32_t* corr, long long* acc, hipStream_t s)
-{
-    const float gate2 = gate * gate;
-    const unsigned fgroups = (unsigned)((n_frames + 255) / 256);
-    const dim3 grid((unsigned)((max_points + kSrSrcTile - 1) / kSrSrcTile), (unsigned)n_frames);
-    unsigned long long* uacc = reinterpret_cast<unsigned long long*>(acc);
-    hipLaunchKernelGGL(k_sr_init, dim3(fgroups), dim3(256), 0, s, init, offsets, n_angles, max_points, tgt_count, max_tgt, recs, acc, n_frames);
-    for (int it = 0; it <= iterations; it++) {
-        const int last = it == iterations;
-        if (grid.x) hipLaunchKernelGGL(k_sr_pass, grid, dim3(kSrTB), 0, s, points, offsets, n_angles, max_points, tgt, tgt_count, max_tgt,
-                                       (const rr_icp_rec*)recs, gate2, uacc, last ? corr : nullptr);
-        hipLaunchKernelGGL(k_sr_solve, dim3(fgroups), dim3(256), 0, s, recs, acc, n_frames, last);
-    }
 }
 
 }  // namespace rr

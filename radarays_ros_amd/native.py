@@ -1955,14 +1955,36 @@ class Context(_Scene):
         """rr_register_points_device: ICP_DTYPE records [n_frames] in HBM from the points [n_frames][max_points] and offsets
         [n_frames][n_angles + 1] rr_detect_device wrote, against the target points [max_tgt] whose count is the uint32 at d_tgt_count_ptr;
         d_init_ptr: float64 [n_frames][4] or None (identity); d_corr_ptr: uint32 [n_frames][max_points] or None; on `stream`"""
+        self._register_device("register_points_device", 1, d_points_ptr, d_offsets_ptr, n_frames, max_points,
+                              d_tgt_points_ptr, d_tgt_count_ptr, max_tgt, d_recs_ptr, d_init_ptr, gate, iterations, d_corr_ptr, stream)
+
+    def _register_device(self, name, tgt_align, d_points_ptr, d_offsets_ptr, n_frames, max_points, d_tgt_ptr, d_tgt_count_ptr, max_tgt, d_recs_ptr,
+                         d_init_ptr, gate, iterations, d_corr_ptr, stream):
+        """the device form of either matcher: rr_`name` of the library (looked up once every argument has passed), the target at a multiple of
+        tgt_align bytes"""
         self._polar_shape()
         n = _frames_arg(n_frames)
         mp, mt = _int_in(max_points, 0, ICP_MAX_POINTS, "max_points"), _int_in(max_tgt, 0, ICP_MAX_POINTS, "max_tgt")
         it, g = _int_in(iterations, 0, 64, "iterations"), _icp_gate(gate)
-        if not d_offsets_ptr or not d_tgt_count_ptr or not d_recs_ptr or (mp > 0 and not d_points_ptr) or (mt > 0 and not d_tgt_points_ptr):
-            raise ValueError("register_points_device needs point, offset, target, target count and record buffers")
-        self._ck(self._L.rr_register_points_device(self._h, d_points_ptr, d_offsets_ptr, n, mp, d_tgt_points_ptr, d_tgt_count_ptr, mt, d_init_ptr,
-                                                   g, it, d_recs_ptr, d_corr_ptr, stream))
+        if not d_offsets_ptr or not d_tgt_count_ptr or not d_recs_ptr or (mp > 0 and not d_points_ptr) or (mt > 0 and not d_tgt_ptr):
+            raise ValueError("%s needs point, offset, target, target count and record buffers" % name)
+        if (d_tgt_ptr or 0) % tgt_align:
+            raise ValueError("the target must be %d-byte aligned" % tgt_align)
+        self._ck(getattr(self._L, "rr_" + name)(self._h, d_points_ptr, d_offsets_ptr, n, mp, d_tgt_ptr, d_tgt_count_ptr, mt, d_init_ptr, g, it, d_recs_ptr, d_corr_ptr, stream))
+
+    def _register(self, name, pts, offsets, n_angles, tgt, init, gate, iterations, want_corr):
+        """the host form of either matcher, rr_`name` of the library, on a validated cloud list and target array"""
+        buf, offs, lens = _clouds(pts, offsets, n_angles, True)
+        n, mp = buf.shape
+        x0 = _icp_init(init, n)
+        it, g = _int_in(iterations, 0, 64, "iterations"), _icp_gate(gate)
+        recs = np.zeros(n, ICP_DTYPE)
+        corr = np.full((n, mp), ICP_NONE, np.uint32) if want_corr else None
+        self._ck(getattr(self._L, "rr_" + name)(self._h, buf.ctypes.data, offs.ctypes.data, n, mp, tgt.ctypes.data if len(tgt) else None, len(tgt), len(tgt),
+                                                _ptr(x0), g, it, recs.ctypes.data, _ptr(corr)))
+        if want_corr:
+            return recs, [corr[f, :k].copy() for f, k in enumerate(lens)]
+        return recs
 
     def register_points(self, points_list, offsets, target_points, init=None, gate=1.0, iterations=10, want_corr=False):
         """rr_register_points on what detect() (or compensate_points()) returned: a list of n POINT_DTYPE arrays and offsets uint32
@@ -1975,18 +1997,7 @@ class Context(_Scene):
         tgt = _scan(target_points, None, "the target")      # a bad target is reported before a cloud over the cap, and is held to it too
         if len(tgt) > ICP_MAX_POINTS:
             raise ValueError("a cloud may hold at most %d points" % ICP_MAX_POINTS)
-        buf, offs, lens = _clouds(pts, offsets, n_angles, True)
-        n, mp = buf.shape
-        x0 = _icp_init(init, n)
-        it, g = _int_in(iterations, 0, 64, "iterations"), _icp_gate(gate)
-        recs = np.zeros(n, ICP_DTYPE)
-        corr = np.full((n, mp), ICP_NONE, np.uint32) if want_corr else None
-        self._ck(self._L.rr_register_points(self._h, buf.ctypes.data, offs.ctypes.data, n, mp, tgt.ctypes.data if len(tgt) else None, len(tgt),
-                                            len(tgt), _ptr(x0), g, it, recs.ctypes.data,
-                                            corr.ctypes.data if want_corr else None))
-        if want_corr:
-            return recs, [corr[f, :k].copy() for f, k in enumerate(lens)]
-        return recs
+        return self._register("register_points", pts, offsets, n_angles, tgt, init, gate, iterations, want_corr)
 
     # ---- oriented surface points and point-to-line scan matching (rr_surfels.hip); any context with a config, mesh or not
     @staticmethod
@@ -2033,16 +2044,8 @@ class Context(_Scene):
                                 d_init_ptr=None, gate=1.0, iterations=10, d_corr_ptr=None, stream=None):
         """rr_register_surfels_device: register_points_device with SURFEL_DTYPE records [max_tgt] (16-byte aligned) as the target, whose
         count is the uint32 at d_tgt_count_ptr (&counts[g][0] of surface_points_device): point-to-line ICP"""
-        self._polar_shape()
-        n = _frames_arg(n_frames)
-        mp, mt = _int_in(max_points, 0, ICP_MAX_POINTS, "max_points"), _int_in(max_tgt, 0, ICP_MAX_POINTS, "max_tgt")
-        it, g = _int_in(iterations, 0, 64, "iterations"), _icp_gate(gate)
-        if not d_offsets_ptr or not d_tgt_count_ptr or not d_recs_ptr or (mp > 0 and not d_points_ptr) or (mt > 0 and not d_tgt_surfels_ptr):
-            raise ValueError("register_surfels_device needs point, offset, target, target count and record buffers")
-        if (d_tgt_surfels_ptr or 0) % 16:
-            raise ValueError("the target must be 16-byte aligned")
-        self._ck(self._L.rr_register_surfels_device(self._h, d_points_ptr, d_offsets_ptr, n, mp, d_tgt_surfels_ptr, d_tgt_count_ptr, mt, d_init_ptr,
-                                                    g, it, d_recs_ptr, d_corr_ptr, stream))
+        self._register_device("register_surfels_device", 16, d_points_ptr, d_offsets_ptr, n_frames, max_points,
+                              d_tgt_surfels_ptr, d_tgt_count_ptr, max_tgt, d_recs_ptr, d_init_ptr, gate, iterations, d_corr_ptr, stream)
 
     def register_surfels(self, points_list, offsets, target_surfels, init=None, gate=1.0, iterations=10, want_corr=False):
         """rr_register_surfels: register_points with ONE SURFEL_DTYPE array (what surface_points returned for the target cloud) as the
@@ -2054,17 +2057,7 @@ class Context(_Scene):
         if tgt.dtype != SURFEL_DTYPE or tgt.ndim != 1 or len(tgt) > ICP_MAX_POINTS:
             raise ValueError("the target must be a one-dimensional SURFEL_DTYPE array of at most %d records" % ICP_MAX_POINTS)
         tgt = np.ascontiguousarray(tgt)
-        buf, offs, lens = _clouds(pts, offsets, n_angles, True)
-        n, mp = buf.shape
-        x0 = _icp_init(init, n)
-        it, g = _int_in(iterations, 0, 64, "iterations"), _icp_gate(gate)
-        recs = np.zeros(n, ICP_DTYPE)
-        corr = np.full((n, mp), ICP_NONE, np.uint32) if want_corr else None
-        self._ck(self._L.rr_register_surfels(self._h, buf.ctypes.data, offs.ctypes.data, n, mp, tgt.ctypes.data if len(tgt) else None, len(tgt),
-                                             len(tgt), _ptr(x0), g, it, recs.ctypes.data, _ptr(corr)))
-        if want_corr:
-            return recs, [corr[f, :k].copy() for f, k in enumerate(lens)]
-        return recs
+        return self._register("register_surfels", pts, offsets, n_angles, tgt, init, gate, iterations, want_corr)
 
     # ---- pose-graph optimisation (rr_graph.hip); any context, with a config or not
     @staticmethod

@@ -382,31 +382,37 @@ class RadarHIP:
         Convention: the source is the cloud simulated at the hypothesis X_h, the target the real cloud taken at the true pose X, both in
         their sensor's frame.  A record's (c, s, tx, ty) is T with q ~ T p, so T = X^-1 X_h and the corrected pose is X_h T^-1: the
         hypothesis turned by -atan2(s, c) about its own z axis and moved by -R^T t in its own axes (forward, left)."""
-        import torch
+        import torch  # noqa: F401  (a missing torch is reported before any argument, as it always was)
         self._push()
         det = native.detect_config(detect, n_cells=self.m_cfg.n_cells)
         p = native.object_poses_array(poses)
         tgt = native._scan(np.ascontiguousarray(real_points), 1, "real_points")      # ascontiguousarray: one record alone is a cloud of one
         it, g = native._int_in(iterations, 0, 64, "iterations"), native._icp_gate(gate)
         table = None if compensate is None else self._ctx._sweep_records(compensate, 1)
+        rec = self._register_chunks(p, det, tgt, len(tgt), self._ctx.register_points_device, g, it, table)
+        return rec, self._corrected_by(p, rec)
+
+    def _register_chunks(self, p, det, tgt, count, register_device, g, it, table=None):
+        """the loop under both matchers: the target records uploaded once with their count, then per chunk of hypotheses simulate, detect,
+        the sweep table (or None) applied to the simulated clouds, and `register_device` from the identity guess, on one explicit stream
+        (as simulatePointClouds) -> the records of all chunks.  Only the records come to the host."""
+        import torch
         dev = torch.device("cuda", self._ctx.device)
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)   # noqa: E731
         recs = []
-        stream = torch.cuda.Stream(device=dev)      # an explicit stream, as simulatePointClouds
+        stream = torch.cuda.Stream(device=dev)
         s = stream.cuda_stream
         with torch.cuda.device(dev), torch.cuda.stream(stream):
-            d_tgt, d_cnt = up(tgt), up(np.array([len(tgt)], np.uint32))
+            d_tgt, d_cnt = up(tgt), up(np.array([count], np.uint32))
             for _, n, offs, pts, mp, _ in self._detected_chunks(p, det, s, capped=True):
                 d_rec = torch.empty(n * native.ICP_DTYPE.itemsize, dtype=torch.uint8, device=dev)
                 if table is not None:
                     d_tab = up(np.tile(table, (n, 1)))
                     self._ctx.compensate_points_device(pts.data_ptr(), offs.data_ptr(), n, mp, d_tab.data_ptr(), None, s)
-                self._ctx.register_points_device(pts.data_ptr(), offs.data_ptr(), n, mp, d_tgt.data_ptr(), d_cnt.data_ptr(), len(tgt),
-                                                 d_rec.data_ptr(), None, g, it, None, s)
+                register_device(pts.data_ptr(), offs.data_ptr(), n, mp, d_tgt.data_ptr(), d_cnt.data_ptr(), count, d_rec.data_ptr(), None, g, it, None, s)
                 recs.append(d_rec.cpu().numpy().view(native.ICP_DTYPE).copy())
         self._ctx.synchronize(s)
-        rec = np.concatenate(recs) if recs else np.zeros(0, native.ICP_DTYPE)
-        return rec, self._corrected_by(p, rec)
+        return np.concatenate(recs) if recs else np.zeros(0, native.ICP_DTYPE)
 
     # ---- oriented surface points and point-to-line scan matching (rr_surfels.hip)
     def surfacePoints(self, points, surfel_cfg, max_surfels=4096):
@@ -424,7 +430,7 @@ class RadarHIP:
         per 64 poses rr_simulate_batch_device, rr_detect_device and rr_register_surfels_device run on one stream from the identity guess.
         -> (native.ICP_DTYPE records [n], corrected poses float32 [n][7]).  The pose convention is registerPointClouds': T = X^-1 X_h and
         the corrected pose is X_h T^-1."""
-        import torch
+        import torch  # noqa: F401
         self._push()
         det = native.detect_config(detect, n_cells=self.m_cfg.n_cells)
         p = native.object_poses_array(poses)
@@ -432,20 +438,7 @@ class RadarHIP:
         tgt = self.surfacePoints(native._scan(np.ascontiguousarray(real_points), 1, "real_points"), surfel_cfg, max_surfels)[0][0]
         if len(tgt) > native.ICP_MAX_POINTS:
             raise ValueError("the target may hold at most %d surface points" % native.ICP_MAX_POINTS)
-        dev = torch.device("cuda", self._ctx.device)
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)   # noqa: E731
-        recs = []
-        stream = torch.cuda.Stream(device=dev)
-        s = stream.cuda_stream
-        with torch.cuda.device(dev), torch.cuda.stream(stream):
-            d_tgt, d_cnt = up(tgt if len(tgt) else np.zeros(1, native.SURFEL_DTYPE)), up(np.array([len(tgt)], np.uint32))
-            for _, n, offs, pts, mp, _ in self._detected_chunks(p, det, s, capped=True):
-                d_rec = torch.empty(n * native.ICP_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-                self._ctx.register_surfels_device(pts.data_ptr(), offs.data_ptr(), n, mp, d_tgt.data_ptr(), d_cnt.data_ptr(), len(tgt),
-                                                  d_rec.data_ptr(), None, g, it, None, s)
-                recs.append(d_rec.cpu().numpy().view(native.ICP_DTYPE).copy())
-        self._ctx.synchronize(s)
-        rec = np.concatenate(recs) if recs else np.zeros(0, native.ICP_DTYPE)
+        rec = self._register_chunks(p, det, tgt if len(tgt) else np.zeros(1, native.SURFEL_DTYPE), len(tgt), self._ctx.register_surfels_device, g, it)
         return rec, self._corrected_by(p, rec)
 
     # ---- pose-graph optimisation (rr_graph.hip)

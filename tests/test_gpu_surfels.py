@@ -219,7 +219,7 @@ def test_surface_points_refusals(ctx):
 # ---- point-to-line registration -------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def tiles():
-    return native.icp_tile_sizes()                                    # k_sr_pass has k_icp_pass's blocking
+    return native.icp_tile_sizes()                                    # both matchers are k_icp_pass: one blocking
 
 
 def target_surfels(rs, count):
@@ -453,6 +453,54 @@ def test_two_streams_register_different_batches_at_once_beside_a_batch_in_flight
     c.simulate_batch_device(poses, imgs.data_ptr(), None)
     c.synchronize()
     assert np.array_equal(imgs.cpu().numpy(), busy) and busy.any()    # ... and the batch beside them was not disturbed
+
+
+def test_both_matchers_share_one_streams_accumulator_while_it_grows(tiles):
+    """point-to-line on 3 frames, point-to-point on 70, point-to-line on 3 again, on one stream with no synchronisation in between: the
+    accumulator of that stream grows under calls in flight and holds fourteen words per frame, then eight, then fourteen.  Every byte is
+    that of the same call made alone on a fresh context"""
+    _, T = tiles
+    rs = np.random.RandomState(77)
+    surf = target_surfels(rs, T + 1)
+    cloud_tgt = np.stack([surf["x"], surf["y"]], -1).astype(np.float32)
+    mp = 300
+    calls = []
+    for line, n in ((True, 3), (False, 70), (True, 3)):
+        clouds = [source_for(rs, surf, mp - f % 7, yaw=0.02 + 0.001 * f) for f in range(n)]
+        pts, offs, _ = packed(clouds, mp)
+        tgt = surf if line else P.points_of(cloud_tgt)
+        calls.append((line, n, dict(pts=dev(pts), offs=dev(offs), tgt=dev(tgt), cnt=dev(np.array([len(tgt)], np.uint32)),
+                                    rec=torch.zeros(n * 48, dtype=torch.uint8, device=DEV), corr=torch.zeros(n * mp * 4, dtype=torch.uint8, device=DEV))))
+    torch.cuda.synchronize()
+
+    def enqueue(c, line, n, b, stream):
+        p = {k: v.data_ptr() for k, v in b.items()}
+        fn = c.register_surfels_device if line else c.register_points_device
+        fn(p["pts"], p["offs"], n, mp, p["tgt"], p["cnt"], T + 1, p["rec"], None, GATE, 2, p["corr"], stream)
+
+    def results(b):
+        return b["rec"].cpu().numpy().tobytes(), b["corr"].cpu().numpy().tobytes()
+
+    def fresh():
+        c = native.Context(0)
+        c.set_config(params.kaist_preset(n_cells=64), N_ANGLES)
+        return c
+
+    c, s = fresh(), torch.cuda.Stream(device=DEV)
+    for line, n, b in calls:
+        enqueue(c, line, n, b, s.cuda_stream)
+    torch.cuda.synchronize()
+    together = [results(b) for _, _, b in calls]
+    alone = []
+    for line, n, b in calls:
+        b["rec"].zero_(); b["corr"].zero_()
+        torch.cuda.synchronize()
+        ci = fresh()
+        enqueue(ci, line, n, b, s.cuda_stream)
+        torch.cuda.synchronize()
+        alone.append(results(b))
+    assert together == alone
+    assert all(any(r[0]) and any(r[1]) for r in alone) and alone[0] != alone[2]
 
 
 def test_register_refusals(ctx):

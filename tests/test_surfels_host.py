@@ -248,13 +248,14 @@ def test_the_facade_has_the_calls_and_the_documents_name_them():
     readme, design, baseline, integ = (open(os.path.join(ROOT, f)).read() for f in ("README.md", "DESIGN.md", "BASELINE.md", "INTEGRATION.md"))
     for n in NEW:
         assert n in integ or n.replace("_device", "[_device]") in integ, n
-    assert "registerSurfacePoints" in readme and "## 31." in design and "k_sr_pass" in design and "## 28." in baseline
+    assert "registerSurfacePoints" in readme and "## 31." in design and "k_icp_pass<LineResidual>" in design and "## 28." in baseline
 
 
 def test_surfel_kernels_use_no_scratch_and_the_lds_they_were_designed_for(native_lib):
     if not os.path.exists("/opt/rocm/bin/hipcc"):
         pytest.skip("no hipcc")
-    r = subprocess.run(["make", "-s", "-C", CSRC, "resource-usage-surfels"], capture_output=True, text=True, timeout=600)
+    # the surface-point kernels are rr_surfels.hip's; the point-to-line matcher is rr_icp.hip's kernels instantiated for LineResidual
+    r = subprocess.run(["make", "-s", "-C", CSRC, "resource-usage-surfels", "resource-usage-icp"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
     rows, cur = {}, None
     for line in (r.stdout + r.stderr).splitlines():
@@ -267,13 +268,15 @@ def test_surfel_kernels_use_no_scratch_and_the_lds_they_were_designed_for(native
             if m and cur is not None:
                 cur[name] = int(m.group(1))
     names = " ".join(rows)
-    for k in ("k_sf_bin", "k_sf_decide", "k_sf_offsets", "k_sf_write", "k_sr_init", "k_sr_pass", "k_sr_solve"):
+    for k in ("k_sf_bin", "k_sf_decide", "k_sf_offsets", "k_sf_write"):
         assert k in names, (k, sorted(rows))
+    for k in ("k_icp_init", "k_icp_pass", "k_icp_solve"):
+        assert any(k in name and "LineResidual" in name for name in rows), (k, sorted(rows))
     _, tgt_tile = native_lib.icp_tile_sizes()
     for name, u in rows.items():
         assert u["scratch"] == 0, (name, u)
         scan = any(k in name for k in ("k_sf_decide", "k_sf_offsets", "k_sf_write"))
-        assert u["lds"] == (8 * tgt_tile if "k_sr_pass" in name else 32 if scan else 0), (name, u)
+        assert u["lds"] == (8 * tgt_tile if "k_icp_pass" in name else 32 if scan else 0), (name, u)
         assert u["vgprs"] <= 128, (name, u)                            # four waves per SIMD at the least
 
 
