@@ -364,7 +364,9 @@ int rr_simulate_param_sets(rr_ctx* ctx, const float pose[7], const rr_param_set*
  * `which` is a mask of RR_METRIC_* bits; the fields of a metric not asked for are 0.  d_joint_hist (HBM, uint32
  * [n_images][256][256], or NULL) receives the histograms; it needs RR_METRIC_INFO.  Synchronous on `stream` like
  * rr_score_images_device, and like it the call uses context-owned scratch (at most 64 images' histograms, 16 MB: more images
- * are worked through in chunks), so one call per context at a time.  A config is needed, a mesh is not.
+ * are worked through in chunks), one set per stream the call has been made on.  The device forms of this header that keep scratch in
+ * the context share that set: it grows to the largest request a stream has seen, growing it drains that stream, and it is freed with
+ * the context; a form called on a further stream costs one more set.  A config is needed, a mesh is not.
  * Refused with a message and nothing written: -2 without a config; -3 for a null buffer, n_images outside 1..65535, which == 0
  * or with unknown bits, an even or out-of-range win_size, an image smaller than the window, d_joint_hist without
  * RR_METRIC_INFO. */
@@ -411,8 +413,8 @@ int rr_simulate_param_sets_metrics(rr_ctx* ctx, const float pose[7], const rr_pa
  *   shift   = the smallest s that attains max xcorr (also the minimum SSE and the maximum ncc: everything else is
  *             shift-invariant); n_best = the number of shifts that attain it
  * A record holds xcorr, sse, psnr and ncc AT `shift`; d_xcorr (HBM, int64 [n_images][n_angles], or NULL) receives the whole
- * curve.  Synchronous on `stream`, context-owned scratch, more than 64 images in chunks, one call per context at a time: the
- * conventions of rr_compare_images_device.  A config is needed, a mesh is not (rr_simulate_batch_align needs what
+ * curve.  Synchronous on `stream`, context-owned scratch, one set per stream the call has been made on, more than 64 images in
+ * chunks: the conventions of rr_compare_images_device.  A config is needed, a mesh is not (rr_simulate_batch_align needs what
  * rr_simulate_batch_device needs).
  * Refused with a message and nothing written: -2 without a config; -3 for a null buffer, n_images outside 1..65535, a window
  * that is empty or outside 0..n_cells, a window of more than 2^23 pixels (which keeps N xcorr inside int64). */
@@ -879,8 +881,8 @@ int rr_simulate_batch_annotations(rr_ctx* ctx, const float* poses, int n_frames,
  *             outside -S..S or the denominator is <= 0
  * A record holds xcorr, sse, psnr, ncc, sum_r and sum_rr AT the best shift, and the SSE of its four neighbours (UINT64_MAX
  * where a neighbour lies outside -S..S).  d_xcorr and d_sse (HBM, [n_images][2S+1][2S+1], index [dy+S][dx+S], or NULL)
- * receive the whole surfaces.  Synchronous on `stream`, context-owned scratch, more than 64 images in chunks, one call per
- * context at a time: the conventions of rr_align_images_device.
+ * receive the whole surfaces.  Synchronous on `stream`, context-owned scratch, one set per stream the call has been made on,
+ * more than 64 images in chunks: the conventions of rr_align_images_device.
  * Limits: H, W in 1..8192; 0 <= S <= 64; H > 2S and W > 2S; N <= 2^23 (which keeps N xcorr inside int64); n_images 1..65535.
  * Refused with a message and nothing written: -3 for a null buffer or an argument outside these limits.
  * Pose meaning.  rr_polar_to_cartesian puts pixel (i, j) at forward (c - i) pixel_size and left (c - j) pixel_size, and a
@@ -943,8 +945,8 @@ int rr_simulate_batch_shift(rr_ctx* ctx, const float* poses, int n_frames, const
  * by the returned ncc.
  * d_sse (HBM, uint32 [n_query][n_db], or NULL) receives every pair's SSE at its best shift, d_shift (HBM, uint16
  * [n_query][n_db], or NULL; only together with d_sse) that shift.
- * Limits: 1 <= n_query <= 64, 1 <= n_db <= 2^28.  Synchronous on `stream`, context-owned scratch, one call per context at
- * a time: the conventions of rr_align_images_device.  The database may start at any byte.
+ * Limits: 1 <= n_query <= 64, 1 <= n_db <= 2^28.  Synchronous on `stream`, context-owned scratch, one set per stream the call has
+ * been made on: the conventions of rr_align_images_device.  The database may start at any byte.
  * Refused with a message and nothing written: -2 without a config where one is needed (the describe calls), -3 for a null
  * buffer, an argument outside these limits, top_k > n_db, d_shift without d_sse.
  * Pose meaning.  The shift moves the QUERY's sectors: by the rule of rr_align_images the query's pose turned by
@@ -1080,7 +1082,7 @@ int rr_polar_to_cartesian_sweep(rr_ctx* ctx, const uint8_t* imgs_u8, int n_frame
  * a frame's count.  NULL: not wanted.
  * The device form enqueues 2 * iterations + 3 launches on `stream` (the initial states, the pairs, the last pass and the step that
  * writes the record) with no host round trip between them.  It touches no context memory but a scratch accumulator of 64 bytes per frame
- * that the context keeps PER STREAM (it grows with the largest n_frames seen on that stream; growing it waits for the device), so it
+ * that the context keeps PER STREAM (it grows with the largest n_frames seen on that stream; growing it drains that stream), so it
  * may run on any stream beside batches in flight, and calls on different streams may overlap.  d_init and d_recs must be 8-byte aligned.
  * The host form stages through context-owned buffers and is synchronous; its tgt_count is a value.
  * Refused with a message and nothing written: -1 for a null ctx; -2 without a config (n_angles is the offsets' stride); -3 for a null
@@ -1484,8 +1486,9 @@ void rr_cast_tile_sizes(int* angles_tile, int* hyps_per_wave, int* hyps_per_grou
  * non-zero byte leaves that object's records out entirely (a static prior map without the parked and moving objects).
  * The device form enqueues on `stream` (NULL: the context's) with no host round trip: a 4-byte memset and two launches.  It reads the scene
  * the context holds when the kernels run, so the CALLER orders it against rr_set_mesh*, rr_set_object_poses, rr_update_vertices and
- * rr_rebuild_tree (they drain the device before they change it; a slice must not be enqueued while one of them runs).  It keeps a
- * context-owned list of one word per record, one per stream it has been called on: calls on different streams may overlap.  The host form
+ * rr_rebuild_tree (they drain the device before they change it; a slice must not be enqueued while one of them runs).  It uses
+ * context-owned scratch, one set per stream the call has been made on (a list of one word per record; growing it drains that stream):
+ * calls on different streams may overlap.  The host form
  * stages through context-owned buffers, is synchronous and ACCUMULATES: it reads occ_u8 and object_u32 as well as writing them.
  * Refused with a message and nothing written: -1 for a null ctx; -2 when no mesh has been set; -3 for a null config, grid or d_occ_u8, a
  * grid field outside rr_field_config's stated ranges, z_lo or z_hi not finite or z_lo > z_hi, flags != 0, or a d_object_u32 that is not

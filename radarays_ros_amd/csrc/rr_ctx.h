@@ -26,7 +26,7 @@ struct Delivery {
     uint64_t job = 0;
 };
 
-// the room of a host form's round trip (rr_stage.h): anonymous buffers that only grow, slot i for a call's i-th request
+// the room of a host form's round trip and of a device form's scratch (rr_stage.h): anonymous buffers that only grow, slot i for a call's i-th request
 using StagePool = std::vector<DevBuf<uint4>>;
 
 struct Lane {
@@ -196,24 +196,14 @@ struct rr_ctx {
     }
 
     int passes_override = -1;    // a parameter batch in the making: the largest n_reflections of its sets sizes queues and launch loops
-    // Scratch of the device forms, which run on arbitrary caller streams (grown by grow_on_stream): it is not staging and never aliases
-    // a host form's pool.  rr_score_images_device's sums; rr_compare_images_device: histograms of one chunk of images, SSIM partials
-    // [image][block], the records; RR_METRICS_HIST
-    DevBuf<unsigned long long> d_sse; DevBuf<uint32_t> d_mhist; DevBuf<double> d_ssim_part; DevBuf<rr_image_metrics> d_mrec; int metrics_hist = 0;
-    // rr_register_points_device / rr_register_surfels_device: the eight or fourteen int64 sums per frame, one buffer per stream either has been
-    // called on, sized by the larger call (icp_mu guards the map, not the buffers: calls on one stream are ordered by that stream, and each
-    // call's first launch zeroes what it uses; a buffer grows through hipFree, which waits for the device)
-    std::map<hipStream_t, DevBuf<long long>> icp_acc; std::mutex icp_mu;
-    // rr_slice_mesh_device: the large list (its counter, then one word per triangle record), one buffer per stream like icp_acc
-    std::map<hipStream_t, DevBuf<uint32_t>> slice_list; std::mutex slice_mu;
-    // rr_align_images_device: one chunk's curves (when the caller gives no buffer) and sums, the records
-    DevBuf<long long> d_align_curve; DevBuf<unsigned long long> d_align_sums; DevBuf<rr_align_record> d_align_rec;
-    // rr_shift_images_device: one chunk's surface (when the caller gives no buffer) and sums, the reference's column and box sums, the records
-    DevBuf<long long> d_shift_surf; DevBuf<unsigned long long> d_shift_sums, d_shift_col, d_shift_box; DevBuf<rr_shift_record> d_shift_rec;
-    // rr_match_descriptors_device: the rolled queries and their sums, one database chunk's keys and aux words, the slices' winners, the
-    // winners so far twice over ([2][keys | aux][n_query][top_k]: read from one, written to the other), the records
-    DevBuf<uint8_t> d_place_rolls; DevBuf<uint32_t> d_place_qsums;
-    DevBuf<unsigned long long> d_place_keys, d_place_aux, d_place_part, d_place_win; DevBuf<rr_place_match> d_place_rec;
+    // Scratch of the device forms, which run on arbitrary caller streams: one pool per stream a form has been called on, its slots shared by
+    // every form (rr_stage.h: Scratch).  It lives with the context, is used on the caller's stream only -- calls on one stream are ordered by
+    // that stream, calls on different streams may overlap on the GPU -- and grows only with that stream drained.  scratch_mu guards the map,
+    // not the pools.  It is not staging and never aliases a host form's pool below: a host form holds slots of its stage while the device form
+    // it calls takes scratch on the same stream
+    std::map<hipStream_t, StagePool> scratch; std::mutex scratch_mu;
+    StagePool& scratch_of(hipStream_t s) { std::lock_guard<std::mutex> lock(scratch_mu); return scratch[s]; }
+    int metrics_hist = 0;        // RR_METRICS_HIST
     StagePool stage;             // the round trips of the host forms on c->stream (rr_images.hip, rr_sets.hip)
     void* h_rb = nullptr; size_t h_rb_bytes = 0;         // page-locked: read_back()
     void* h_frame = nullptr; size_t h_frame_bytes = 0;   // page-locked: error bits + per-pass counters of rr_simulate's frame

@@ -625,13 +625,9 @@ int register_device(rr_ctx* c, const std::string& w, const rr_radar_point* d_poi
     if (const char* why = M::refuse_target(d_tgt)) return fail(c, -3, w + why);
     RR_HIP(c, hipSetDevice(c->device));
     hipStream_t s = stream_of(c, stream);
-    long long* acc = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(c->icp_mu);
-        DevBuf<long long>& b = c->icp_acc[s];
-        RR_HIP(c, b.ensure(M::scratch_words((size_t)n_frames)));
-        acc = b.p;
-    }
+    Scratch sc(c->scratch_of(s), s);
+    long long* acc;      // the eight or fourteen int64 sums per frame: the call's first launch zeroes what it uses
+    RR_HIP(c, sc.room(M::scratch_words((size_t)n_frames), acc));
     M::launch(d_points, d_offsets, n_frames, c->cfg.n_angles, max_points, d_tgt, d_tgt_count, max_tgt, d_init, gate, iterations, d_recs, d_corr, acc, s);
     RR_HIP(c, hipGetLastError());
     return 0;
@@ -693,11 +689,13 @@ int rr_score_images_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_images, co
     hipStream_t s = stream_of(c, stream);
     const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles;
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "sse words");
-    RR_HIP(c, grow_on_stream(s, need(c->d_sse, (size_t)n_images)));
-    RR_HIP(c, hipMemsetAsync(c->d_sse.p, 0, (size_t)n_images * sizeof(uint64_t), s));
-    launch_score(d_imgs_u8, d_ref_u8, npx, n_images, c->d_sse.p, s);
+    Scratch sc(c->scratch_of(s), s);
+    unsigned long long* d_sums;
+    RR_HIP(c, sc.room((size_t)n_images, d_sums));
+    RR_HIP(c, hipMemsetAsync(d_sums, 0, (size_t)n_images * sizeof(uint64_t), s));
+    launch_score(d_imgs_u8, d_ref_u8, npx, n_images, d_sums, s);
     std::vector<uint64_t> sse((size_t)n_images);
-    rc = records_back(c, sse.data(), c->d_sse.p, sse.size() * sizeof(uint64_t), s); if (rc) return rc;
+    rc = records_back(c, sse.data(), d_sums, sse.size() * sizeof(uint64_t), s); if (rc) return rc;
     for (int k = 0; k < n_images; k++) {
         if (out_sse) out_sse[k] = sse[(size_t)k];
         if (out_psnr) out_psnr[k] = psnr_of(sse[(size_t)k], npx);
@@ -720,26 +718,30 @@ int rr_compare_images_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_images, 
     const int n_blocks = ssim ? ssim_blocks(g.n_cells, g.n_angles, win_size) : 0;
     const double ssim_count = ssim ? (double)(g.n_cells - win_size + 1) * (double)(g.n_angles - win_size + 1) : 1.0;
     const bool own_hist = info && !d_joint_hist;
-    RR_HIP(c, grow_on_stream(s, need(c->d_sse, psnr ? n : 0), need(c->d_mhist, own_hist ? chunk * kBins : 0),
-                             need(c->d_ssim_part, ssim ? chunk * (size_t)n_blocks : 0), need(c->d_mrec, n)));
+    // the sums, the histograms of one chunk of images, the SSIM partials [image][block], the records: each null where the call has no use for it
+    Scratch sc(c->scratch_of(s), s);
+    unsigned long long* d_sums; uint32_t* d_hist; double* d_part; rr_image_metrics* d_rec;
+    RR_HIP(c, sc.room(psnr ? n : 0, d_sums));
+    RR_HIP(c, sc.room(own_hist ? chunk * kBins : 0, d_hist));
+    RR_HIP(c, sc.room(ssim ? chunk * (size_t)n_blocks : 0, d_part));
+    RR_HIP(c, sc.room(n, d_rec));
     if (psnr) {
-        RR_HIP(c, hipMemsetAsync(c->d_sse.p, 0, n * sizeof(uint64_t), s));
-        launch_score(d_imgs_u8, d_ref_u8, npx, n_images, c->d_sse.p, s);
+        RR_HIP(c, hipMemsetAsync(d_sums, 0, n * sizeof(uint64_t), s));
+        launch_score(d_imgs_u8, d_ref_u8, npx, n_images, d_sums, s);
     }
     for (size_t at = 0; at < n; at += kChunk) {
         const int m = (int)std::min(kChunk, n - at);
         const uint8_t* imgs = d_imgs_u8 + at * npx;
-        uint32_t* H = !info ? nullptr : d_joint_hist ? d_joint_hist + at * kBins : c->d_mhist.p;
+        uint32_t* H = !info ? nullptr : d_joint_hist ? d_joint_hist + at * kBins : d_hist;
         if (info) {
             RR_HIP(c, hipMemsetAsync(H, 0, (size_t)m * kBins * sizeof(uint32_t), s));
             launch_joint_hist(imgs, d_ref_u8, npx, m, H, c->metrics_hist, s);
         }
-        if (ssim) launch_ssim(imgs, d_ref_u8, g.n_cells, g.n_angles, win_size, m, c->d_ssim_part.p, s);
-        launch_metrics_finish(H, ssim ? c->d_ssim_part.p : nullptr, n_blocks, ssim_count, psnr ? c->d_sse.p + at : nullptr, npx,
-                              c->d_mrec.p + at, m, s);
+        if (ssim) launch_ssim(imgs, d_ref_u8, g.n_cells, g.n_angles, win_size, m, d_part, s);
+        launch_metrics_finish(H, d_part, n_blocks, ssim_count, psnr ? d_sums + at : nullptr, npx, d_rec + at, m, s);
     }
     std::vector<rr_image_metrics> rec(n);
-    rc = records_back(c, rec.data(), c->d_mrec.p, n * sizeof(rr_image_metrics), s); if (rc) return rc;
+    rc = records_back(c, rec.data(), d_rec, n * sizeof(rr_image_metrics), s); if (rc) return rc;
     for (size_t k = 0; k < n; k++) {
         if (psnr) rec[k].psnr = psnr_of(rec[k].sse, npx);     // the host's log10, as rr_score_images_device: the same bits
         out[k] = rec[k];
@@ -780,19 +782,24 @@ int rr_align_images_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_images, co
     const size_t npx = (size_t)g.n_cells * g.n_angles, n = (size_t)n_images, A = (size_t)g.n_angles;
     const size_t chunk = std::min(n, kChunk);
     static_assert(sizeof(long long) == sizeof(int64_t), "curve words");
-    RR_HIP(c, grow_on_stream(s, need(c->d_align_curve, d_xcorr ? 0 : chunk * A), need(c->d_align_sums, 2 * (chunk + 1)), need(c->d_align_rec, n)));
+    // one chunk's curves (when the caller gives no buffer) and sums, the records
+    Scratch sc(c->scratch_of(s), s);
+    long long* d_curve; unsigned long long* d_sums; rr_align_record* d_rec;
+    RR_HIP(c, sc.room(d_xcorr ? 0 : chunk * A, d_curve));
+    RR_HIP(c, sc.room(2 * (chunk + 1), d_sums));
+    RR_HIP(c, sc.room(n, d_rec));
     for (size_t at = 0; at < n; at += kChunk) {
         const int m = (int)std::min(kChunk, n - at);
         const uint8_t* imgs = d_imgs_u8 + at * npx;
-        long long* curve = d_xcorr ? reinterpret_cast<long long*>(d_xcorr) + at * A : c->d_align_curve.p;
+        long long* curve = d_xcorr ? reinterpret_cast<long long*>(d_xcorr) + at * A : d_curve;
         RR_HIP(c, hipMemsetAsync(curve, 0, (size_t)m * A * sizeof(long long), s));
-        RR_HIP(c, hipMemsetAsync(c->d_align_sums.p, 0, 2 * ((size_t)m + 1) * sizeof(unsigned long long), s));
-        launch_align_sums(imgs, d_ref_u8, g.n_cells, g.n_angles, cell_begin, cell_end, m, c->d_align_sums.p, s);
+        RR_HIP(c, hipMemsetAsync(d_sums, 0, 2 * ((size_t)m + 1) * sizeof(unsigned long long), s));
+        launch_align_sums(imgs, d_ref_u8, g.n_cells, g.n_angles, cell_begin, cell_end, m, d_sums, s);
         launch_align_gram(imgs, d_ref_u8, g.n_cells, g.n_angles, cell_begin, cell_end, m, curve, s);
-        launch_align_finish(curve, c->d_align_sums.p, m, g.n_angles, cell_begin, cell_end, c->d_align_rec.p + at, s);
+        launch_align_finish(curve, d_sums, m, g.n_angles, cell_begin, cell_end, d_rec + at, s);
     }
     std::vector<rr_align_record> rec(n);
-    rc = records_back(c, rec.data(), c->d_align_rec.p, n * sizeof(rr_align_record), s); if (rc) return rc;
+    rc = records_back(c, rec.data(), d_rec, n * sizeof(rr_align_record), s); if (rc) return rc;
     const size_t n_win = (size_t)(cell_end - cell_begin) * A;
     for (size_t k = 0; k < n; k++) {
         rec[k].psnr = psnr_of(rec[k].sse, n_win);       // the host's log10, as rr_score_images_device
@@ -857,22 +864,28 @@ int rr_shift_images_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_images, co
     const size_t npx = (size_t)H * W, n = (size_t)n_images, ND = (size_t)D * D, n_col = 2 * (size_t)D * W;
     const size_t chunk = std::min(n, kChunk);
     static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(unsigned long long) == sizeof(uint64_t), "surface words");
-    RR_HIP(c, grow_on_stream(s, need(c->d_shift_surf, d_xcorr ? 0 : chunk * ND), need(c->d_shift_sums, 2 * chunk), need(c->d_shift_col, n_col),
-                             need(c->d_shift_box, 2 * ND), need(c->d_shift_rec, n)));
-    launch_shift_box(d_ref_u8, H, W, S, c->d_shift_col.p, c->d_shift_box.p, s);      // once per call: every image meets the same reference
+    // one chunk's surface (when the caller gives no buffer) and sums, the reference's column and box sums, the records
+    Scratch sc(c->scratch_of(s), s);
+    long long* d_surf; unsigned long long *d_sums, *d_col, *d_box; rr_shift_record* d_rec;
+    RR_HIP(c, sc.room(d_xcorr ? 0 : chunk * ND, d_surf));
+    RR_HIP(c, sc.room(2 * chunk, d_sums));
+    RR_HIP(c, sc.room(n_col, d_col));
+    RR_HIP(c, sc.room(2 * ND, d_box));
+    RR_HIP(c, sc.room(n, d_rec));
+    launch_shift_box(d_ref_u8, H, W, S, d_col, d_box, s);      // once per call: every image meets the same reference
     for (size_t at = 0; at < n; at += kChunk) {
         const int m = (int)std::min(kChunk, n - at);
         const uint8_t* imgs = d_imgs_u8 + at * npx;
-        long long* surf = d_xcorr ? reinterpret_cast<long long*>(d_xcorr) + at * ND : c->d_shift_surf.p;
+        long long* surf = d_xcorr ? reinterpret_cast<long long*>(d_xcorr) + at * ND : d_surf;
         unsigned long long* sse = d_sse ? reinterpret_cast<unsigned long long*>(d_sse) + at * ND : nullptr;
         RR_HIP(c, hipMemsetAsync(surf, 0, (size_t)m * ND * sizeof(long long), s));
-        RR_HIP(c, hipMemsetAsync(c->d_shift_sums.p, 0, 2 * (size_t)m * sizeof(unsigned long long), s));
-        launch_shift_sums(imgs, H, W, S, m, c->d_shift_sums.p, s);
+        RR_HIP(c, hipMemsetAsync(d_sums, 0, 2 * (size_t)m * sizeof(unsigned long long), s));
+        launch_shift_sums(imgs, H, W, S, m, d_sums, s);
         launch_shift_gram(imgs, d_ref_u8, H, W, S, m, surf, s);
-        launch_shift_finish(surf, sse, c->d_shift_sums.p, c->d_shift_box.p, H, W, S, m, c->d_shift_rec.p + at, s);
+        launch_shift_finish(surf, sse, d_sums, d_box, H, W, S, m, d_rec + at, s);
     }
     std::vector<rr_shift_record> rec(n);
-    rc = records_back(c, rec.data(), c->d_shift_rec.p, n * sizeof(rr_shift_record), s); if (rc) return rc;
+    rc = records_back(c, rec.data(), d_rec, n * sizeof(rr_shift_record), s); if (rc) return rc;
     const size_t n_win = (size_t)(H - 2 * S) * (W - 2 * S);
     // the sub-pixel offset along one axis from the exact SSE before, at and after the best shift (each below 2^39)
     auto sub = [](uint64_t before, uint64_t at_best, uint64_t after) {
@@ -1004,23 +1017,29 @@ int rr_match_descriptors_device(rr_ctx* c, const uint8_t* d_query, int n_query, 
     const size_t chunk = std::min(n, std::max<size_t>(32, ((size_t)1 << 22) / nq / 32 * 32));
     const size_t n_rolls = nq * n_sectors * (size_t)place_kpad(n_rings, n_sectors), n_part = nq * place_slices(chunk) * k, n_win = nq * k;
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "key words");
-    RR_HIP(c, grow_on_stream(s, need(c->d_place_rolls, n_rolls), need(c->d_place_qsums, 2 * nq), need(c->d_place_keys, nq * chunk),
-                             need(c->d_place_aux, nq * chunk), need(c->d_place_part, n_part), need(c->d_place_win, 4 * n_win), need(c->d_place_rec, n_win)));
-    launch_place_rolls(d_query, n_query, n_rings, n_sectors, c->d_place_rolls.p, c->d_place_qsums.p, s);
+    // the rolled queries and their sums, one database chunk's keys and aux words, the slices' winners, the winners so far twice over, the records
+    Scratch sc(c->scratch_of(s), s);
+    uint8_t* d_rolls; uint32_t* d_qsums; unsigned long long *d_keys, *d_aux, *d_part, *d_win; rr_place_match* d_rec;
+    RR_HIP(c, sc.room(n_rolls, d_rolls));
+    RR_HIP(c, sc.room(2 * nq, d_qsums));
+    RR_HIP(c, sc.room(nq * chunk, d_keys));
+    RR_HIP(c, sc.room(nq * chunk, d_aux));
+    RR_HIP(c, sc.room(n_part, d_part));
+    RR_HIP(c, sc.room(4 * n_win, d_win));
+    RR_HIP(c, sc.room(n_win, d_rec));
+    launch_place_rolls(d_query, n_query, n_rings, n_sectors, d_rolls, d_qsums, s);
     // the winners so far, [2][keys | aux][n_query][top_k]: a chunk reads one half and writes the other.  No winner yet: every key ~0
-    unsigned long long* half[2] = { c->d_place_win.p, c->d_place_win.p + 2 * n_win };
+    unsigned long long* half[2] = { d_win, d_win + 2 * n_win };
     RR_HIP(c, hipMemsetAsync(half[0], 0xFF, n_win * sizeof(unsigned long long), s));
     int cur = 0;
     for (size_t at = 0; at < n; at += chunk, cur ^= 1) {
         const size_t m = std::min(chunk, n - at);
-        launch_place_match(c->d_place_rolls.p, c->d_place_qsums.p, n_query, d_db + at * K, m, at, n_rings, n_sectors, c->d_place_keys.p, c->d_place_aux.p,
-                           d_sse, d_shift, n, s);
-        launch_place_topk(c->d_place_keys.p, c->d_place_aux.p, n_query, m, at, top_k, c->d_place_part.p, half[cur], half[cur] + n_win,
-                          half[cur ^ 1], half[cur ^ 1] + n_win, s);
+        launch_place_match(d_rolls, d_qsums, n_query, d_db + at * K, m, at, n_rings, n_sectors, d_keys, d_aux, d_sse, d_shift, n, s);
+        launch_place_topk(d_keys, d_aux, n_query, m, at, top_k, d_part, half[cur], half[cur] + n_win, half[cur ^ 1], half[cur ^ 1] + n_win, s);
     }
-    launch_place_finish(half[cur], half[cur] + n_win, c->d_place_qsums.p, n_query, top_k, n_rings, n_sectors, c->d_place_rec.p, s);
+    launch_place_finish(half[cur], half[cur] + n_win, d_qsums, n_query, top_k, n_rings, n_sectors, d_rec, s);
     std::vector<rr_place_match> rec(n_win);
-    rc = records_back(c, rec.data(), c->d_place_rec.p, n_win * sizeof(rr_place_match), s); if (rc) return rc;
+    rc = records_back(c, rec.data(), d_rec, n_win * sizeof(rr_place_match), s); if (rc) return rc;
     for (size_t e = 0; e < n_win; e++) {
         rec[e].psnr = psnr_of(rec[e].sse, K);           // the host's log10, as rr_score_images_device
         out[e] = rec[e];
@@ -1592,13 +1611,9 @@ int rr_slice_mesh_device(rr_ctx* c, const rr_slice_config* slice, const rr_field
     if (c->n_tris == 0) return 0;                                     // an empty mesh writes nothing
     RR_HIP(c, hipSetDevice(c->device));
     hipStream_t s = stream_of(c, stream);
-    uint32_t* list = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(c->slice_mu);
-        DevBuf<uint32_t>& b = c->slice_list[s];
-        RR_HIP(c, grow_on_stream(s, need(b, slice_scratch_words((size_t)c->n_tris))));
-        list = b.p;
-    }
+    Scratch sc(c->scratch_of(s), s);
+    uint32_t* list;      // the large list: its counter, then one word per triangle record
+    RR_HIP(c, sc.room(slice_scratch_words((size_t)c->n_tris), list));
     launch_slice(reinterpret_cast<const TriRec*>(c->d_bvh.p + c->tri_base4), (size_t)c->n_tris, c->d_rest_v.p, c->d_rest_f.p, c->d_poses.p, d_skip_u8,
                  *slice, *cfg, d_occ_u8, d_object_u32, list, s);
     RR_HIP(c, hipGetLastError());

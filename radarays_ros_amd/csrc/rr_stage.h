@@ -1,8 +1,11 @@
-// rr_stage.h -- Stage: the round trip of a host form.  Its inputs go up into fresh room, a device form runs on that room, its outputs come
-// home.  The room is a pool of anonymous buffers that only grow (rr_ctx::stage for the forms on c->stream, Lane::stage for the host forms
-// of rr_side.hip, because lanes overlap in time): request i of a call takes slot i, so a pointer handed out earlier in the call never moves,
-// and every pointer is hipMalloc's own (the device forms refuse unaligned tables, states and records).
-// The caller drains its stream before it opens a Stage: a slot that grows is freed first, and an earlier call's kernels may still read it.
+// rr_stage.h -- Scratch: a call's rooms in a pool of anonymous device buffers that only grow.  Stage: the round trip of a host form over such
+// a pool.  Its inputs go up into fresh room, a device form runs on that room, its outputs come home.
+//
+// The pools: rr_ctx::stage for the host forms on c->stream, Lane::stage for the host forms of rr_side.hip (lanes overlap in time), and for
+// the device forms one pool per stream they have been called on (rr_ctx::scratch_of).  Request i of a call takes slot i, so a pointer handed
+// out earlier in the call never moves, and every pointer is hipMalloc's own (16-byte aligned: the device forms refuse unaligned tables,
+// states and records, and kernels read scratch with 16-byte loads).  A slot that grows is freed first, and an earlier call's kernels may
+// still read it: the stream is drained before that, once per call at the most.  A host form drains its stream itself before it opens its Stage.
 //
 // The rule for outputs, said once: a HELD output goes through a host vector and reaches the caller in commit(), after every copy has
 // landed and the gate has passed -- a call that fails at any step has written nothing through it.  A DIRECT output is copied straight
@@ -12,24 +15,41 @@
 #pragma once
 #include "rr_ctx.h"
 #include "rr_rows.h"
+#include <algorithm>
 
 namespace rr {
 
-struct Stage {
-    struct Out { void* dst; const void* d_src; size_t bytes, elem, n_rows, d_stride, stride; const void* counts; bool held; std::vector<uint8_t> h; };
-    rr_ctx* c; StagePool& pool; hipStream_t s; size_t used = 0;
-    std::vector<Out> outs;
-    Stage(rr_ctx* c_, StagePool& pool_, hipStream_t s_) : c(c_), pool(pool_), s(s_) {}
+struct Scratch {
+    StagePool& pool; hipStream_t s; size_t used = 0; bool drained;
+    Scratch(StagePool& pool_, hipStream_t s_, bool drained_ = false) : pool(pool_), s(s_), drained(drained_) {}
 
-    // room for n elements -> d
+    // room for n elements -> d.  n = 0 takes its slot all the same (a form keeps its slot order with and without its optional rooms), allocates
+    // nothing and gives null
     template <class T> hipError_t room(size_t n, T*& d)
     {
+        d = nullptr;
         if (used == pool.size()) pool.emplace_back();
         DevBuf<uint4>& b = pool[used++];
-        const hipError_t e = b.ensure((n * sizeof(T) + sizeof(uint4) - 1) / sizeof(uint4));
-        d = reinterpret_cast<T*>(b.p);
-        return e;
+        const size_t words = (n * sizeof(T) + sizeof(uint4) - 1) / sizeof(uint4);
+        if (words > b.n) {
+            hipError_t e = drained ? hipSuccess : hipStreamSynchronize(s);
+            drained = true;
+            if (e == hipSuccess) e = b.ensure(words);
+            if (e != hipSuccess) return e;
+        }
+        if (words) d = reinterpret_cast<T*>(b.p);
+        return hipSuccess;
     }
+};
+
+struct Stage : Scratch {
+    struct Out { void* dst; const void* d_src; size_t bytes, elem, n_rows, d_stride, stride; const void* counts; bool held; std::vector<uint8_t> h; };
+    rr_ctx* c;
+    std::vector<Out> outs;
+    Stage(rr_ctx* c_, StagePool& pool_, hipStream_t s_) : Scratch(pool_, s_, true), c(c_) {}      // (drained by the caller)
+
+    // room for n elements -> d, never null: the device forms refuse a null buffer, an empty one too
+    template <class T> hipError_t room(size_t n, T*& d) { return Scratch::room(std::max<size_t>(n, 1), d); }
     // a host array the caller gave (else d = null and that is all) into fresh room -> d; again(): the next chunk into the same room
     template <class T> hipError_t up(const T* h, size_t n, T*& d)
     {

@@ -77,9 +77,9 @@ def main():
         return ctx.match_descriptors_device(q.data_ptr(), nq, db.data_ptr(), n, R, S, TOP_K)
     rec = lib(max(N_QUERY), min(N_DB))
     assert rec[0][0]["index"] == 77_777 and rec[0][0]["sse"] == 0 and rec[0][0]["shift"] == S - 9, rec[0][0]
-    # exact check on a slice: int64 matmul on the device
+    # exact check on a slice: an f64 matmul on the device (torch has no integer one here), exact because a sum stays below 255^2 K < 2^53
     sl = 4096
-    xc = (rolled(q).long() @ db[:sl].reshape(sl, K).long().T).reshape(max(N_QUERY), S, sl)
+    xc = (rolled(q).double() @ db[:sl].reshape(sl, K).double().T).long().reshape(max(N_QUERY), S, sl)
     top = xc.max(dim=1).values
     sse = (q.long() ** 2).sum(dim=(1, 2))[:, None] + (db[:sl].long() ** 2).sum(dim=(1, 2))[None, :] - 2 * top
     d_sse = torch.zeros((max(N_QUERY), sl), dtype=torch.int32, device=dev)
@@ -107,7 +107,7 @@ def main():
             med = {k: round(float(np.median(v)), 1) for k, v in times.items()}
             # how far fp32 is off, on the first 65536 candidates
             m = min(n, 65536)
-            exact = (rolled(q[:nq]).long() @ db[:m].reshape(m, K).long().T).reshape(nq, S, m)
+            exact = (rolled(q[:nq]).double() @ db[:m].reshape(m, K).double().T).long().reshape(nq, S, m)
             approx = (rolls @ db_t[:, :m]).reshape(nq, S, m)
             err = float((approx.double() - exact.double()).abs().max())
             moved = int((approx.argmax(dim=1) != exact.argmax(dim=1)).sum())
