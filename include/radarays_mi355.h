@@ -758,6 +758,59 @@ int rr_detect_device(rr_ctx* ctx, const uint8_t* d_imgs_u8 /*[n][n_cells][n_angl
                      int max_points, uint32_t* d_offsets /*[n][n_angles+1]*/, void* stream);
 int rr_detect(rr_ctx* ctx, const uint8_t* imgs_u8, int n_frames, const rr_detect_config* cfg,
               rr_radar_point* points, int max_points, uint32_t* offsets);        /* host buffers, synchronous */
+
+/* Windowed CFAR (rr_window.hip): a training window over range AND azimuth, and an ordered-statistic threshold, beside the two
+ * detectors above.  The build's own definition like them (tests/window_ref.py restates it with loops and sorted()); the image is
+ * z[b][col], N = n_cells bins by A = n_angles columns in the context's current shape. */
+typedef struct rr_window_detect_config {
+    int32_t method;          /* 0 CA, 1 GO, 2 SO, 3 OS */
+    int32_t guard_range;     /* Gr 0..1024 */
+    int32_t train_range;     /* Tr 0..1024 */
+    int32_t guard_azimuth;   /* Ga 0..32 */
+    int32_t train_azimuth;   /* Ta 0..32 */
+    int32_t rank_permille;   /* OS: 1..1000 */
+    int32_t min_intensity;   /* 0..255 */
+    int32_t min_bin;         /* 0..n_cells-1 */
+    float   scale;           /* finite, >= 0 */
+    int32_t reserved_[3];
+} rr_window_detect_config;
+
+/* method 3 (OS), guard_range 2, train_range 16, guard_azimuth 1, train_azimuth 2, rank_permille 750, min_intensity 1, min_bin 0,
+ * scale 3.0 */
+void rr_default_window_detect_config(rr_window_detect_config* cfg);
+
+/* Training cells of the cell under test (i, c): the cells (b, c') with |b - i| <= Gr + Tr and |c' - c| <= Ga + Ta (column distance
+ *   on the circle) minus the guard box |b - i| <= Gr, |c' - c| <= Ga.  Rows are clipped to [0, N); columns wrap mod A (the scroll is
+ *   a rotation of columns, so wrapping columns is wrapping azimuths); cells below min_bin train too.  n = their count, S = their sum.
+ * Refused with -3, nothing written: a field outside its range, Tr + Ta == 0, 2 (Ga + Ta) + 1 > A, an unclipped window
+ *   (2 (Gr + Tr) + 1) (2 (Ga + Ta) + 1) of more than 65,535 cells (so 255 * n < 2^24: every product below is an exact f32 integer),
+ *   method 1 or 2 with Tr == 0, and whatever rr_detect refuses of frames and buffers.
+ * Candidates: bins i >= min_bin with z >= min_intensity and n > 0.
+ * CA (0): a detection iff (float)(z * n) > scale * (float)S.  With Ga = Ta = 0 this is rr_detect's method 0.
+ * GO (1) / SO (2): the near half is the training cells of rows < i, the far half those of rows > i (training cells of row i belong
+ *   to neither).  The means are compared exactly, S_near * n_far against S_far * n_near in uint64: GO takes the half with the
+ *   greater mean, SO the smaller, ties go to near; if one half is empty both take the other, if both are there is no detection.
+ *   Then the CA test with that half's (n_h, S_h).
+ * OS (3): r = max(1, (n * rank_permille + 999) / 1000), v = the r-th smallest training value (1-based); a detection iff
+ *   (float)z > scale * (float)v.
+ * Output: points, order, d_offsets, truncation and max_points == 0 exactly as rr_detect_device; the geometry is rr_detect's.
+ *   d_mask (or NULL): uint8 [n][N][A], 255 at a detection and 0 elsewhere, written whole; it goes into rr_label_components as it is.
+ * The device form reads config and geometry by value, touches no context memory and needs no room but the caller's buffers (a count
+ * pass, the scan of rr_detect, an emit pass), so it may run on any stream beside batches in flight. */
+int rr_detect_window_device(rr_ctx* ctx, const uint8_t* d_imgs_u8 /*[n][n_cells][n_angles]*/, int n_frames,
+                            const rr_window_detect_config* cfg, rr_radar_point* d_points /*[n][max_points] or NULL if max_points==0*/,
+                            int max_points, uint32_t* d_offsets /*[n][n_angles+1]*/, uint8_t* d_mask /*[n][n_cells][n_angles] or NULL*/,
+                            void* stream);
+int rr_detect_window(rr_ctx* ctx, const uint8_t* imgs_u8, int n_frames, const rr_window_detect_config* cfg,
+                     rr_radar_point* points, int max_points, uint32_t* offsets, uint8_t* mask);   /* host buffers, synchronous */
+/* The tile a launch uses for this config and shape: out = (rows, columns, halo rows, halo columns).  A workgroup owns `columns`
+ * adjacent columns of a frame and walks down them `rows` bins at a time, staging each step with Gr + Tr halo rows above and below
+ * and Ga + Ta wrapped halo columns left and right.  `columns` shrinks as n_cells grows (16 up to 1024 bins, 8 up to 2048, 4 beyond),
+ * so the workgroup count grows with n_cells.  The tile depends on the config and the shape alone: a base that is not 16-byte aligned
+ * (or n_angles % 16 != 0) changes how a step is loaded (bytes, not 16-byte words from the multiple of 16 at or below the halo), not
+ * the tile.  0, or -3 for a config or shape the detector refuses. */
+int rr_detect_window_tile_sizes(const rr_window_detect_config* cfg, int n_cells, int n_angles, int out[4]);
+
 /* Cartesian bird's-eye image, all in f32 with no fused operations.  c = (width - 1) * 0.5f; pixel (row i, col j) sits at
  * x = (c - i) * pixel_size (forward = up), y = (c - j) * pixel_size (left = left); rho = sqrtf(x*x + y*y), phi = atan2f(y, x).
  *   u = (phi - theta_min) / theta_inc, then u = fmodf(u, n_angles), + n_angles if negative, - n_angles if that gave n_angles

@@ -10,7 +10,7 @@
 // becomes float[7] (quaternion xyzw + translation).  INTEGRATION.md shows the ROS-typed twin.
 // What the two classes do alike -- config copy, materials, beam draw, chunked batches, parameter sets -- is marshal.hpp,
 // which both include: the marshalling the ROS-typed adapter ships is the one the GPU demo executes through this class.
-// Here: the `Radar` base, the dirty flags, `Image`s, detect / toCartesian and how errors are reported.
+// Here: the `Radar` base, the dirty flags, `Image`s, detect / detectWindow / toCartesian and how errors are reported.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -452,6 +452,24 @@ public:
         if (rr_detect(m_ctx, image->data.data(), 1, &cfg, nullptr, 0, offs.data())) { fail(); return pts; }      // count
         pts.resize(offs.back());
         if (!pts.empty() && rr_detect(m_ctx, image->data.data(), 1, &cfg, pts.data(), (int)pts.size(), offs.data())) { fail(); pts.clear(); }
+        return pts;
+    }
+    // ... by the windowed CFAR (rr_window_detect_config: a training window over range and azimuth under CA / GO / SO, or an ordered-statistic
+    // threshold; rr_default_window_detect_config gives the defaults): the same points, and as asked for (non-null) the uint8 detection mask
+    // [n_cells][n_angles], 255 at a detection, which labelComponents takes as it is.  ok (or null) tells an image without detections from an
+    // error (lastError())
+    std::vector<rr_radar_point> detectWindow(const ImagePtr& image, const rr_window_detect_config& cfg, std::vector<uint8_t>* mask = nullptr,
+                                             bool* ok = nullptr)
+    {
+        std::vector<rr_radar_point> pts;
+        if (ok) *ok = false;
+        if (mask) mask->clear();
+        if (!image || !push()) return pts;
+        if (image->height != (uint32_t)m_cfg.n_cells || image->width != (uint32_t)m_n_angles || image->data.size() != (size_t)image->height * image->width) {
+            m_err = "detectWindow: the image is not n_cells x n_angles mono8"; std::cout << "[RadarHIP] " << m_err << std::endl; return pts;
+        }
+        if (!marshal::detect_window(m_ctx, image->data.data(), image->data.size(), m_n_angles, cfg, pts, mask)) { fail(); return pts; }
+        if (ok) *ok = true;
         return pts;
     }
     // the Cartesian bird's-eye image of one polar image: width x width mono8, forward = up, left = left, pixel_size m per pixel

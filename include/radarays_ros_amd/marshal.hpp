@@ -407,6 +407,27 @@ inline bool label_components(rr_ctx* ctx, const std::vector<uint8_t>& planes, in
     return true;
 }
 
+// Windowed CFAR (rr_detect_window, host form) of ONE polar image of npx = n_cells * n_angles pixels: a count-only call sizes the points, a
+// second call writes them (sorted by column, then bin) and, as asked for (non-null), the uint8 detection mask [n_cells][n_angles].
+// false: rr_last_error(ctx)
+inline bool detect_window(rr_ctx* ctx, const uint8_t* image, size_t npx, int n_angles, const rr_window_detect_config& cfg,
+                          std::vector<rr_radar_point>& pts, std::vector<uint8_t>* mask)
+{
+    pts.clear();
+    if (mask) mask->clear();
+    std::vector<uint32_t> offs((size_t)n_angles + 1);
+    if (rr_detect_window(ctx, image, 1, &cfg, nullptr, 0, offs.data(), nullptr) != 0) return false;      // count
+    pts.resize(offs.back());
+    if (mask) mask->assign(npx, 0);
+    if (pts.empty() && !mask) return true;
+    if (rr_detect_window(ctx, image, 1, &cfg, pts.empty() ? nullptr : pts.data(), (int)pts.size(), offs.data(), mask ? mask->data() : nullptr) != 0) {
+        pts.clear();
+        if (mask) mask->clear();
+        return false;
+    }
+    return true;
+}
+
 // ... and ONE scan refined against it from n_hyp starting states on `stream`, every buffer the caller's and in HBM: d_init [n_hyp][4] f64
 // (c, s, tx, ty: the scan's sensor frame into the map frame), d_recs [n_hyp] (rr_refine_poses_device: one launch, nothing comes home and
 // nothing is waited for).  false: rr_last_error(ctx)

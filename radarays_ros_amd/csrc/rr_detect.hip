@@ -245,7 +245,7 @@ void launch_detect_tw(const uint8_t* imgs, int n_frames, rr_radar_point* points,
     const dim3 grid((A.G.n_angles + TW - 1) / TW, n_frames);
     const size_t lds = detect_lds(TW, METHOD, A.G.n_cells);
     hipLaunchKernelGGL((k_detect<TW, METHOD, false>), grid, dim3(kDetTB), lds, s, imgs, points, offsets, A);
-    hipLaunchKernelGGL(k_detect_scan, dim3(n_frames), dim3(64), 0, s, offsets, A.G.n_angles);
+    launch_detect_scan(offsets, n_frames, A.G.n_angles, s);
     if (A.max_points > 0)
         hipLaunchKernelGGL((k_detect<TW, METHOD, true>), grid, dim3(kDetTB), lds, s, imgs, points, offsets, A);
 }
@@ -314,6 +314,12 @@ void launch_detect(const uint8_t* imgs, int n_frames, const rr_detect_config& cf
         if (cfg.method == 0) launch_detect_tw<4, 0>(imgs, n_frames, points, offsets, A, s);
         else launch_detect_tw<4, 1>(imgs, n_frames, points, offsets, A, s);
     }
+}
+
+// the scan between a count and an emit pass, for rr_window.hip too
+void launch_detect_scan(uint32_t* offsets, int n_frames, int n_angles, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_detect_scan, dim3(n_frames), dim3(64), 0, s, offsets, n_angles);
 }
 
 void launch_cartesian(const uint8_t* imgs, int n_frames, const rr_cartesian_config& cfg, const PolarGrid& G, uint8_t* out, hipStream_t s)

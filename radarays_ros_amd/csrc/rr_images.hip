@@ -1120,6 +1120,85 @@ int rr_detect(rr_ctx* c, const uint8_t* imgs_u8, int n_frames, const rr_detect_c
     return st.commit();
 }
 
+// ---- windowed CFAR (rr_window.hip) -------------------------------------------------------------------------------------
+void rr_default_window_detect_config(rr_window_detect_config* cfg)
+{
+    if (!cfg) return;
+    std::memset(cfg, 0, sizeof(*cfg));
+    cfg->method = 3; cfg->guard_range = 2; cfg->train_range = 16; cfg->guard_azimuth = 1; cfg->train_azimuth = 2;
+    cfg->rank_permille = 750; cfg->min_intensity = 1; cfg->min_bin = 0; cfg->scale = 3.0f;
+}
+
+// what is wrong with a window config for images of n_cells x n_angles, or null
+static const char* window_config_error(const rr_window_detect_config* d, int n_cells, int n_angles)
+{
+    if (!d) return "null config";
+    if (d->method < 0 || d->method > 3) return "method must be 0 (CA), 1 (GO), 2 (SO) or 3 (OS)";
+    if (d->guard_range < 0 || d->guard_range > 1024) return "guard_range must be 0..1024";
+    if (d->train_range < 0 || d->train_range > 1024) return "train_range must be 0..1024";
+    if (d->guard_azimuth < 0 || d->guard_azimuth > 32) return "guard_azimuth must be 0..32";
+    if (d->train_azimuth < 0 || d->train_azimuth > 32) return "train_azimuth must be 0..32";
+    if (d->rank_permille < 1 || d->rank_permille > 1000) return "rank_permille must be 1..1000";
+    if (d->min_intensity < 0 || d->min_intensity > 255) return "min_intensity must be 0..255";
+    if (d->min_bin < 0 || d->min_bin >= n_cells) return "min_bin must be 0..n_cells-1";
+    if (!(std::isfinite(d->scale) && d->scale >= 0.0f)) return "scale must be finite and >= 0";
+    if (d->reserved_[0] || d->reserved_[1] || d->reserved_[2]) return "reserved_ must be 0";
+    if (d->train_range + d->train_azimuth == 0) return "no training cells: train_range + train_azimuth is 0";
+    const int wc = 2 * (d->guard_azimuth + d->train_azimuth) + 1, wr = 2 * (d->guard_range + d->train_range) + 1;
+    if (wc > n_angles) return "the column window 2 (guard_azimuth + train_azimuth) + 1 exceeds n_angles";
+    if ((long long)wr * wc > 65535) return "a window of more than 65,535 cells";
+    if ((d->method == 1 || d->method == 2) && d->train_range == 0) return "GO / SO need train_range >= 1";
+    return nullptr;
+}
+
+static int check_detect_window(rr_ctx* c, const char* who, const void* imgs, int n_frames, const rr_window_detect_config* d, const void* points,
+                               int max_points, const void* offsets)
+{
+    const std::string w(who);
+    int rc = check_images(c, w, imgs != nullptr, "images", "n_frames", n_frames, 65535); if (rc) return rc;
+    if (!offsets) return fail(c, -3, w + ": null offsets");
+    if (max_points < 0) return fail(c, -3, w + ": max_points must be >= 0");
+    if (max_points > 0 && !points) return fail(c, -3, w + ": null points with max_points > 0");
+    if (const char* e = window_config_error(d, c->cfg.n_cells, c->cfg.n_angles)) return fail(c, -3, w + ": " + e);
+    return 0;
+}
+
+int rr_detect_window_tile_sizes(const rr_window_detect_config* cfg, int n_cells, int n_angles, int out[4])
+{
+    if (!out || n_cells < 1 || n_angles < 1 || window_config_error(cfg, n_cells, n_angles)) return -3;
+    return window_tile_sizes(*cfg, n_cells, n_angles, out) ? 0 : -3;
+}
+
+int rr_detect_window_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_frames, const rr_window_detect_config* cfg, rr_radar_point* d_points,
+                            int max_points, uint32_t* d_offsets, uint8_t* d_mask, void* stream)
+{
+    int rc = check_detect_window(c, "rr_detect_window_device", d_imgs_u8, n_frames, cfg, d_points, max_points, d_offsets); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    RR_HIP(c, launch_detect_window(d_imgs_u8, n_frames, *cfg, polar_grid(c->cfg), max_points > 0 ? d_points : nullptr, max_points, d_offsets, d_mask,
+                                   stream_of(c, stream)));
+    RR_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rr_detect_window(rr_ctx* c, const uint8_t* imgs_u8, int n_frames, const rr_window_detect_config* cfg, rr_radar_point* points,
+                     int max_points, uint32_t* offsets, uint8_t* mask)
+{
+    int rc = check_detect_window(c, "rr_detect_window", imgs_u8, n_frames, cfg, points, max_points, offsets); if (rc) return rc;
+    RR_HIP(c, hipSetDevice(c->device));
+    const size_t npx = (size_t)c->cfg.n_cells * c->cfg.n_angles, n_offs = (size_t)n_frames * (c->cfg.n_angles + 1), n_pts = (size_t)n_frames * (size_t)max_points;
+    RR_STAGE(c, st);
+    uint8_t *d_imgs, *d_mask = nullptr; uint32_t* d_offs; rr_radar_point* d_points = nullptr;
+    RR_HIP(c, st.up(imgs_u8, (size_t)n_frames * npx, d_imgs));
+    RR_HIP(c, st.room(n_offs, d_offs));
+    if (n_pts) RR_HIP(c, st.room(n_pts, d_points));
+    if (mask) RR_HIP(c, st.room((size_t)n_frames * npx, d_mask));
+    rc = rr_detect_window_device(c, d_imgs, n_frames, cfg, d_points, max_points, d_offs, d_mask, c->stream); if (rc) return rc;
+    st.out(offsets, d_offs, n_offs, false);
+    if (n_pts) st.out(points, d_points, n_pts, false);
+    if (mask) st.out(mask, d_mask, (size_t)n_frames * npx, false);
+    return st.commit();
+}
+
 int rr_polar_to_cartesian_device(rr_ctx* c, const uint8_t* d_imgs_u8, int n_frames, const rr_cartesian_config* cfg,
                                  uint8_t* d_cart_u8, void* stream)
 {

@@ -1,4 +1,4 @@
-// rr_launch.h -- every launcher of rr_kernels.hip, rr_labels.hip, rr_paths.hip, rr_doppler.hip, rr_refit.hip, rr_detect.hip, rr_deskew.hip, rr_icp.hip, rr_field.hip, rr_occupancy.hip, rr_filter.hip, rr_refine.hip, rr_cast.hip, rr_slice.hip, rr_components.hip, rr_notes.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip, rr_place.hip and rr_lbvh.hip, declared ONCE: included where they
+// rr_launch.h -- every launcher of rr_kernels.hip, rr_labels.hip, rr_paths.hip, rr_doppler.hip, rr_refit.hip, rr_detect.hip, rr_window.hip, rr_deskew.hip, rr_icp.hip, rr_field.hip, rr_occupancy.hip, rr_filter.hip, rr_refine.hip, rr_cast.hip, rr_slice.hip, rr_components.hip, rr_notes.hip, rr_metrics.hip, rr_align.hip, rr_shift.hip, rr_place.hip and rr_lbvh.hip, declared ONCE: included where they
 // are defined (a definition that drifts from its declaration fails there) and where they are called.  Default arguments live here only.
 #pragma once
 #include "../../include/radarays_mi355.h"
@@ -66,6 +66,12 @@ void launch_score(const uint8_t* imgs, const uint8_t* ref, size_t npx, int n_ima
 void launch_detect(const uint8_t* imgs, int n_frames, const rr_detect_config& cfg, const PolarGrid& G, rr_radar_point* points, int max_points,
                    uint32_t* offsets, hipStream_t s);
 void launch_cartesian(const uint8_t* imgs, int n_frames, const rr_cartesian_config& cfg, const PolarGrid& G, uint8_t* out, hipStream_t s);
+void launch_detect_scan(uint32_t* offsets /*[n_frames][n_angles + 1]*/, int n_frames, int n_angles, hipStream_t s);
+// rr_window.hip (windowed CFAR).  No scratch and no context memory: a count pass into offsets, launch_detect_scan, an emit pass; mask
+// [n_frames][n_cells][n_angles] or null is written whole by the count pass.  tile: (rows, columns, halo rows, halo columns), whatever the base's alignment
+bool window_tile_sizes(const rr_window_detect_config& cfg, int n_cells, int n_angles, int out[4]);
+hipError_t launch_detect_window(const uint8_t* imgs, int n_frames, const rr_window_detect_config& cfg, const PolarGrid& G, rr_radar_point* points,
+                                int max_points, uint32_t* offsets, uint8_t* mask, hipStream_t s);
 // rr_deskew.hip (sweep compensation).  table [n_frames][n_angles], 16-byte aligned; n_angles * 32 bytes of LDS per workgroup of launch_cartesian_sweep
 void launch_sweep_table(const float* az_poses, const float* ref_poses, const float* sensor_vel, float gain, int n_frames, const PolarGrid& G,
                         rr_sweep_rec* table, hipStream_t s);

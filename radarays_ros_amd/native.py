@@ -54,6 +54,12 @@ class RRDetectConfig(C.Structure):
                 ("min_intensity", C.c_int32), ("min_bin", C.c_int32), ("cfar_scale", C.c_float), ("reserved_", C.c_int32)]
 
 
+class RRWindowDetectConfig(C.Structure):
+    _fields_ = [("method", C.c_int32), ("guard_range", C.c_int32), ("train_range", C.c_int32), ("guard_azimuth", C.c_int32),
+                ("train_azimuth", C.c_int32), ("rank_permille", C.c_int32), ("min_intensity", C.c_int32), ("min_bin", C.c_int32),
+                ("scale", C.c_float), ("reserved_", C.c_int32 * 3)]
+
+
 class RRCartesianConfig(C.Structure):
     _fields_ = [("width", C.c_int32), ("interpolation", C.c_int32), ("pixel_size", C.c_float), ("reserved_", C.c_int32)]
 
@@ -683,6 +689,12 @@ def _graph_shape(n_nodes, n_edges):
 DETECT_DEFAULTS ={"method": 0, "guard_cells": 2, "train_cells": 16, "k": 12, "min_intensity": 1, "min_bin": 0, "cfar_scale": 3.0}
 DETECT_METHODS = {"cfar": 0, "ca-cfar": 0, "kstrongest": 1, "k-strongest": 1, 0: 0, 1: 1}
 
+# rr_default_window_detect_config
+WINDOW_DEFAULTS = {"method": 3, "guard_range": 2, "train_range": 16, "guard_azimuth": 1, "train_azimuth": 2, "rank_permille": 750,
+                   "min_intensity": 1, "min_bin": 0, "scale": 3.0}
+WINDOW_METHODS = {"ca": 0, "go": 1, "so": 2, "os": 3, 0: 0, 1: 1, 2: 2, 3: 3}
+WINDOW_MAX_CELLS = 65535
+
 
 # rr_image_metrics as numpy sees it (72 B), and the RR_METRIC_* bits of `which`
 METRICS_DTYPE = np.dtype([("psnr", "<f8"), ("sse", "<u8"), ("ssim", "<f8"), ("hx", "<f8"), ("hy", "<f8"), ("hxy", "<f8"),
@@ -795,6 +807,7 @@ STRUCTS = {
     "rr_image_metrics": (RRImageMetrics, METRICS_DTYPE), "rr_align_record": (RRAlignRecord, ALIGN_DTYPE),
     "rr_echo": (np.ctypeslib.as_ctypes_type(ECHO_DTYPE), ECHO_DTYPE), "rr_echo_src": (np.ctypeslib.as_ctypes_type(ECHO_SRC_DTYPE), ECHO_SRC_DTYPE),
     "rr_wave_rec": (RRWaveRec, WAVE_DTYPE), "rr_detect_config": (RRDetectConfig, None), "rr_radar_point": (RRRadarPoint, POINT_DTYPE),
+    "rr_window_detect_config": (RRWindowDetectConfig, None),
     "rr_cartesian_config": (RRCartesianConfig, None), "rr_object_note": (RRObjectNote, NOTE_DTYPE), "rr_shift_record": (RRShiftRecord, SHIFT_DTYPE),
     "rr_place_config": (RRPlaceConfig, None), "rr_place_match": (RRPlaceMatch, PLACE_DTYPE), "rr_sweep_rec": (RRSweepRec, SWEEP_DTYPE),
     "rr_icp_rec": (RRIcpRec, ICP_DTYPE), "rr_field_config": (RRFieldConfig, None), "rr_field_rec": (RRFieldRec, FIELD_DTYPE),
@@ -893,6 +906,10 @@ def _prototypes():
         "rr_default_detect_config": (None, [P(RRDetectConfig)]),
         "rr_detect_device": (i, [vp, vp, i, P(RRDetectConfig), vp, i, vp, vp]),
         "rr_detect": (i, [vp, vp, i, P(RRDetectConfig), vp, i, vp]),
+        "rr_default_window_detect_config": (None, [P(RRWindowDetectConfig)]),
+        "rr_detect_window_device": (i, [vp, vp, i, P(RRWindowDetectConfig), vp, i, vp, vp, vp]),
+        "rr_detect_window": (i, [vp, vp, i, P(RRWindowDetectConfig), vp, i, vp, vp]),
+        "rr_detect_window_tile_sizes": (i, [P(RRWindowDetectConfig), i, i, P(i)]),
         "rr_polar_to_cartesian_device": (i, [vp, vp, i, P(RRCartesianConfig), vp, vp]),
         "rr_polar_to_cartesian": (i, [vp, vp, i, P(RRCartesianConfig), vp]),
         # ---- object annotations (rr_notes.hip)
@@ -1237,6 +1254,65 @@ def detect_config(cfg=None, n_cells=None, **kw):
         raise ValueError("cfar_scale must be finite and >= 0, got %r" % (scale,))
     c.cfar_scale = scale
     return c
+
+
+def window_detect_config(cfg=None, n_cells=None, n_angles=None, **kw):
+    """RRWindowDetectConfig from an RRWindowDetectConfig, a dict and/or keywords over WINDOW_DEFAULTS; every field and every refusal of
+    the header is checked here (min_bin against n_cells, the column window against n_angles, when they are given), before any call into
+    the library.  method: 0 / "ca", 1 / "go", 2 / "so", 3 / "os"."""
+    d = dict(WINDOW_DEFAULTS)
+    if isinstance(cfg, RRWindowDetectConfig):
+        if any(cfg.reserved_):
+            raise ValueError("reserved_ must be 0")
+        d.update({k: getattr(cfg, k) for k in WINDOW_DEFAULTS})
+    elif isinstance(cfg, dict):
+        d.update(cfg)
+    elif cfg is not None:
+        raise ValueError("window detection config must be an RRWindowDetectConfig or a dict, got %r" % (cfg,))
+    d.update(kw)
+    unknown = set(d) - set(WINDOW_DEFAULTS)
+    if unknown:
+        raise ValueError("unknown window detection config fields: %s" % sorted(unknown))
+    m = d["method"].lower() if isinstance(d["method"], str) else d["method"]
+    m = WINDOW_METHODS.get(m) if isinstance(m, (str, int, np.integer)) and not isinstance(m, bool) else None
+    if m is None:
+        raise ValueError("method must be 0 / 'ca', 1 / 'go', 2 / 'so' or 3 / 'os', got %r" % (d["method"],))
+    c = RRWindowDetectConfig()
+    c.method = m
+    c.guard_range, c.train_range = _int_in(d["guard_range"], 0, 1024, "guard_range"), _int_in(d["train_range"], 0, 1024, "train_range")
+    c.guard_azimuth, c.train_azimuth = _int_in(d["guard_azimuth"], 0, 32, "guard_azimuth"), _int_in(d["train_azimuth"], 0, 32, "train_azimuth")
+    c.rank_permille = _int_in(d["rank_permille"], 1, 1000, "rank_permille")
+    c.min_intensity = _int_in(d["min_intensity"], 0, 255, "min_intensity")
+    c.min_bin = _int_in(d["min_bin"], 0, (int(n_cells) if n_cells is not None else 8192) - 1, "min_bin")
+    try:
+        scale = float(d["scale"])
+    except (TypeError, ValueError):
+        raise ValueError("scale must be a number, got %r" % (d["scale"],))
+    with np.errstate(over="ignore"):
+        finite = bool(np.isfinite(np.float32(scale)))
+    if not (finite and scale >= 0.0):
+        raise ValueError("scale must be finite and >= 0, got %r" % (scale,))
+    c.scale = scale
+    if c.train_range + c.train_azimuth == 0:
+        raise ValueError("no training cells: train_range + train_azimuth is 0")
+    wr, wc = 2 * (c.guard_range + c.train_range) + 1, 2 * (c.guard_azimuth + c.train_azimuth) + 1
+    if n_angles is not None and wc > int(n_angles):
+        raise ValueError("the column window of %d columns exceeds n_angles = %d" % (wc, n_angles))
+    if wr * wc > WINDOW_MAX_CELLS:
+        raise ValueError("a window of %d x %d cells holds more than %d" % (wr, wc, WINDOW_MAX_CELLS))
+    if m in (1, 2) and c.train_range == 0:
+        raise ValueError("GO / SO need train_range >= 1")
+    return c
+
+
+def detect_window_tile_sizes(cfg, n_cells, n_angles):
+    """rr_detect_window_tile_sizes: (rows, columns, halo rows, halo columns) of the tile a launch uses for this config and shape"""
+    n_cells, n_angles = _int_in(n_cells, 1, 2**31 - 1, "n_cells"), _int_in(n_angles, 1, 2**31 - 1, "n_angles")
+    c = window_detect_config(cfg, n_cells=n_cells, n_angles=n_angles)
+    out = (C.c_int * 4)()
+    if lib().rr_detect_window_tile_sizes(C.byref(c), n_cells, n_angles, out) != 0:
+        raise ValueError("rr_detect_window_tile_sizes refused the config")
+    return tuple(out)
 
 
 def cartesian_config(width, pixel_size, bilinear=True):
@@ -1825,6 +1901,42 @@ class Context(_Scene):
             f = int(over[0])
             raise RRError("detect: frame %d has %d detections, max_points is %d (%d frame(s) truncated)" % (f, int(totals[f]), mp, len(over)))
         return [pts[f, :min(int(totals[f]), mp)].copy() for f in range(n)], offs
+
+    # ---- windowed CFAR (rr_window.hip): the same outputs as detect, and the detection mask
+    def detect_window_device(self, d_imgs_ptr, n_frames, cfg=None, d_points_ptr=None, max_points=0, d_offsets_ptr=None, d_mask_ptr=None, stream=None, **kw):
+        """rr_detect_window_device: points and offsets as detect_device, and with d_mask_ptr the uint8 mask [n_frames][n_cells][n_angles]
+        (255 at a detection), all in HBM, on `stream`.  max_points = 0 counts only."""
+        n_cells, n_angles = self._polar_shape()
+        c = window_detect_config(cfg, n_cells=n_cells, n_angles=n_angles, **kw)
+        n = _frames_arg(n_frames)
+        mp = _int_in(max_points, 0, 2**31 - 1, "max_points")
+        if not d_imgs_ptr or not d_offsets_ptr or (mp > 0 and not d_points_ptr):
+            raise ValueError("detect_window_device needs image and offset buffers (and a point buffer when max_points > 0)")
+        self._ck(self._L.rr_detect_window_device(self._h, d_imgs_ptr, n, C.byref(c), d_points_ptr, mp, d_offsets_ptr, d_mask_ptr, stream))
+
+    def detect_window(self, imgs, cfg=None, max_points=None, mask=False, allow_truncation=False, **kw):
+        """rr_detect_window on host images [n][n_cells][n_angles] (or one image).  Returns (list of n POINT_DTYPE arrays, offsets uint32
+        [n][n_angles + 1]) as detect does, and with mask=True a third value, the uint8 mask [n][n_cells][n_angles].  max_points None:
+        room for every detection (a count-only call first); a truncated frame raises RRError unless allow_truncation=True."""
+        x = self._polar_images(imgs)
+        n_cells, n_angles = self._polar_shape()
+        c = window_detect_config(cfg, n_cells=n_cells, n_angles=n_angles, **kw)
+        n = len(x)
+        offs = np.zeros((n, n_angles + 1), np.uint32)
+        if max_points is None:
+            self._ck(self._L.rr_detect_window(self._h, x.ctypes.data, n, C.byref(c), None, 0, offs.ctypes.data, None))
+            max_points = int(offs[:, -1].max())
+        mp = _int_in(max_points, 0, 2**31 - 1, "max_points")
+        pts = np.zeros((n, max(mp, 1)), POINT_DTYPE)
+        m = np.zeros(x.shape, np.uint8) if mask else None
+        self._ck(self._L.rr_detect_window(self._h, x.ctypes.data, n, C.byref(c), pts.ctypes.data if mp else None, mp, offs.ctypes.data, _ptr(m)))
+        totals = offs[:, -1]
+        over = np.nonzero(totals > mp)[0]
+        if len(over) and not allow_truncation:
+            f = int(over[0])
+            raise RRError("detect_window: frame %d has %d detections, max_points is %d (%d frame(s) truncated)" % (f, int(totals[f]), mp, len(over)))
+        clouds = [pts[f, :min(int(totals[f]), mp)].copy() for f in range(n)]
+        return (clouds, offs, m) if mask else (clouds, offs)
 
     def polar_to_cartesian_device(self, d_imgs_ptr, n_frames, width, pixel_size, d_out_ptr, bilinear=True, stream=None):
         """rr_polar_to_cartesian_device: [n_frames][width][width] uint8 in HBM, on `stream`"""

@@ -201,12 +201,26 @@ class RadarHIP:
         return Image(header=Header(stamp=stamp, frame_id=self.m_sensor_frame), height=u8.shape[0], width=u8.shape[1],
                      encoding="mono8", step=u8.shape[1], data=u8)
 
-    def simulatePointClouds(self, poses, **cfg):
+    def detectWindow(self, image, mask=False, **cfg):
+        """one mono8 polar Image -> POINT_DTYPE array as toPointCloud, by the windowed CFAR (rr_window.hip; cfg: rr_window_detect_config
+        fields, method 0 / "ca", 1 / "go", 2 / "so", 3 / "os", native.WINDOW_DEFAULTS for the rest); with mask=True also the uint8
+        detection mask [n_cells][n_angles], 255 at a detection"""
+        self._push()
+        out = self._ctx.detect_window(self._polar(image), cfg, mask=mask)
+        return (out[0][0], out[2][0]) if mask else out[0][0]
+
+    def simulatePointClouds(self, poses, window=None, **cfg):
         """[n][7] poses -> n point clouds (POINT_DTYPE arrays).  Per 64 poses: rr_simulate_batch_device and rr_detect_device on
-        one stream into device buffers; only the offsets and the points come to the host, no image does."""
+        one stream into device buffers; only the offsets and the points come to the host, no image does.  window (a dict of
+        rr_window_detect_config fields or a native.window_detect_config; {}: its defaults): rr_detect_window_device detects instead"""
         import torch
         self._push()
-        det = native.detect_config(cfg, n_cells=self.m_cfg.n_cells)
+        if window is None:
+            det = native.detect_config(cfg, n_cells=self.m_cfg.n_cells)
+        elif cfg:
+            raise ValueError("window= comes without rr_detect_config fields, got %s" % sorted(cfg))
+        else:
+            det = native.window_detect_config(window, n_cells=self.m_cfg.n_cells, n_angles=N_ANGLES)
         poses = native.object_poses_array(poses)
         dev = torch.device("cuda", self._ctx.device)
         out = []
@@ -232,23 +246,30 @@ class RadarHIP:
         import torch
         n_cells = self.m_cfg.n_cells
         dev = torch.device("cuda", self._ctx.device)
+        windowed = isinstance(det, native.RRWindowDetectConfig)          # (simulatePointClouds alone passes one, uncapped)
+
+        def detect(d_imgs, n, d_pts, mp, d_offs):
+            if windowed:
+                self._ctx.detect_window_device(d_imgs, n, det, d_pts, mp, d_offs, None, s)
+            else:
+                self._ctx.detect_device(d_imgs, n, det, d_pts, mp, d_offs, s)
         for at in range(0, len(poses), 64):
             chunk = poses[at:at + 64]
             n = len(chunk)
             imgs = torch.empty((n, n_cells, N_ANGLES), dtype=torch.uint8, device=dev)
             offs = torch.empty((n, N_ANGLES + 1), dtype=torch.int32, device=dev)
             self._ctx.simulate_batch_device(chunk, imgs.data_ptr(), s)
-            if capped and det.method == 1:
+            if capped and not windowed and det.method == 1:
                 totals, mp = None, det.k * N_ANGLES
             else:
-                self._ctx.detect_device(imgs.data_ptr(), n, det, None, 0, offs.data_ptr(), s)     # counts
+                detect(imgs.data_ptr(), n, None, 0, offs.data_ptr())     # counts
                 totals = offs[:, -1].cpu().numpy().view(np.uint32)
                 mp = int(totals.max())
             if capped:
                 mp = min(mp, native.ICP_MAX_POINTS)
             mp = max(1, mp)
             pts = torch.empty((n, mp * native.POINT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-            self._ctx.detect_device(imgs.data_ptr(), n, det, pts.data_ptr(), mp, offs.data_ptr(), s)
+            detect(imgs.data_ptr(), n, pts.data_ptr(), mp, offs.data_ptr())
             yield at, n, offs, pts, mp, totals
 
     # ---- sweep compensation (rr_deskew.hip): a sweep under motion, as the sensor records it and with the distortion taken out again
